@@ -19,6 +19,12 @@ Launch for N > 1: either the driver's  python -m torch.distributed.run --nnodes=
                   torch.distributed.run line, a free port). WORLD_SIZE set but different from --gpus is an error (exit 2), never a
                   silently smaller run. Fewer GPUs than ranks (a one-GPU box): the ranks share devices through the mailbox
                   communicator -- a functional check of the N > 1 path, flagged `ranks_share_gpus` in the line, not a scaling number.
+
+Default run: set-up, clock spin-up, W warm-up steps, K timed steps, one JSON line with the headline (`value`, `ms_per_step`, the workload's `config`,
+`final_pose`). `--full` adds everything else the script measures or checks: extraction timings, the fully bracketed per-kernel pass, HIP events on the
+dominant kernel inside the timed region, the synchronous / keyframe-cadence / scan2map / whole-frame / out-grown-box / saturation legs, predicted scaling,
+both rooflines, the CPU baseline and, at N > 1, the same-map N = 1 reference and the per-rank figures. `--dump-outputs DIR` writes the pose the last timed
+step returned to DIR/pose.npy (float64; with --config4 also DIR/config4_poses.npy); the inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -429,9 +435,20 @@ def main():
                          "for kernel traces and PMC passes, whose per-kernel averages should be the headline workload's alone")
     ap.add_argument("--spinup-ms", type=float, default=150.0,
                     help="milliseconds of an unrelated torch matmul before the warm-up steps (clock ramp of a GPU that idled through the host-side setup); 0: none")
-    ap.add_argument("--profile-events", type=int, default=1,
-                    help="1: HIP-event bracket the dominant kernel (surf correspondence) inside the timed region; 0: none")
+    ap.add_argument("--profile-events", type=int, default=None,
+                    help="1: HIP-event bracket the dominant kernel (surf correspondence) inside the timed region; 0: none. Default: 1 with --full "
+                         "(the roofline reads them), 0 otherwise")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: per-LiDAR extraction timings, the fully bracketed per-kernel pass, the synchronous and keyframe-cadence "
+                         "loops, scan2map / whole-frame / out-grown-box / saturation legs, predicted scaling, both rooflines, the CPU baseline and, at N > 1, the "
+                         "same-map N = 1 reference and the per-rank figures. Without it the run sets up, warms up, times the steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step to DIR/<name>.npy (float64): pose.npy = the pose of the "
+                         "last timed frame [x, y, z, qx, qy, qz, qw]; with --config4 also config4_poses.npy = its four pose blocks")
     args = ap.parse_args()
+    full = args.full
+    if args.profile_events is None:
+        args.profile_events = 1 if full else 0
 
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -485,19 +502,20 @@ def main():
     p0 = synth.perturbed_pose(gt, seed=43)
     ctx = mla.Context(local_rank)
 
-    # --- feature extraction on the GPU (the product's extractCloud), one launch set per LiDAR; timed separately
+    # --- feature extraction on the GPU (the product's extractCloud), one launch set per LiDAR; timed separately (--full)
     extracted, extract_ms = [], []
     for s in scans:
         ctx.scan_upload(s.points, s.scan_start, s.scan_end)
-        ctx.extract_run()          # warm
-        ctx.synchronize()
-        ctx.profile_enable(1 << mla.K_EXTRACT)
-        ctx.profile_reset()
-        for _ in range(10):
-            ctx.extract_run()
-        ms, n = ctx.profile_get(mla.K_EXTRACT)
-        ctx.profile_enable(0)
-        extract_ms.append(ms / max(n, 1))
+        ctx.extract_run()          # warm (without --full: the one run whose lists the features are made of)
+        if full:
+            ctx.synchronize()
+            ctx.profile_enable(1 << mla.K_EXTRACT)
+            ctx.profile_reset()
+            for _ in range(10):
+                ctx.extract_run()
+            ms, n = ctx.profile_get(mla.K_EXTRACT)
+            ctx.profile_enable(0)
+            extract_ms.append(ms / max(n, 1))
         extracted.append(ctx.extract_fetch())
     # all LiDARs of the frame as ONE scan (clouds concatenated, ring tables offset): a ring is a workgroup, so the launch set costs the
     # same as for one LiDAR
@@ -505,19 +523,20 @@ def main():
     all_pts = np.concatenate([s.points for s in scans])
     all_start = np.concatenate([s.scan_start + offs[i] for i, s in enumerate(scans)]).astype(np.int32)
     all_end = np.concatenate([s.scan_end + offs[i] for i, s in enumerate(scans)]).astype(np.int32)
-    ctx.scan_upload(all_pts, all_start, all_end)
-    ctx.extract_run()
-    ctx.synchronize()
-    ctx.profile_enable(1 << mla.K_EXTRACT)
-    ctx.profile_reset()
-    for _ in range(10):
+    if full:
+        ctx.scan_upload(all_pts, all_start, all_end)
         ctx.extract_run()
-    ms, nn = ctx.profile_get(mla.K_EXTRACT)
-    ctx.profile_enable(0)
-    extract_all_ms = ms / max(nn, 1)
-    both = ctx.extract_fetch()
-    n_sharp_each = sum(len(e["sharp"]) for e in extracted)
-    assert len(both["sharp"]) == n_sharp_each, "batched extraction must give the per-LiDAR results back to back"
+        ctx.synchronize()
+        ctx.profile_enable(1 << mla.K_EXTRACT)
+        ctx.profile_reset()
+        for _ in range(10):
+            ctx.extract_run()
+        ms, nn = ctx.profile_get(mla.K_EXTRACT)
+        ctx.profile_enable(0)
+        extract_all_ms = ms / max(nn, 1)
+        both = ctx.extract_fetch()
+        n_sharp_each = sum(len(e["sharp"]) for e in extracted)
+        assert len(both["sharp"]) == n_sharp_each, "batched extraction must give the per-LiDAR results back to back"
     surf, corner = fuse_features(synth, scans, extracted, thin=not args.dense_features)
     n_scan_points = int(sum(len(s.points) for s in scans))
 
@@ -525,7 +544,7 @@ def main():
     #     problem (the N = 1 bench line uses the 500k map; a ratio against it would compare two problems). Synchronous submission, like the sharded loop below, and
     #     the pipelined form beside it. A context of its own, closed before the sharded leg starts; the other ranks wait at the barrier.
     n1_ref = None
-    if world > 1:
+    if world > 1 and full:
         if rank == 0:
             n1_ref = single_gpu_reference(mla, torch, local_rank, surf_map, corner_map, surf, corner, p0, args.steps, args.warmup)
             log(f"[rank 0] same-map N=1 reference ({preset}): {n1_ref}")
@@ -780,39 +799,40 @@ def main():
     value = n_valid_step / (elapsed / args.steps)
     queries_per_s = m_total * GN_ITERS / (elapsed / args.steps)
 
-    # a second, fully instrumented pass (every kernel bracketed) for the per-kernel breakdown; not part of `value`
-    n_prof = max(args.steps // 4, 5)
-    ctx.profile_enable(mla.K_ALL)
-    ctx.profile_reset()
-    sync_all()
-    t1 = time.perf_counter()
-    for _ in range(n_prof):
-        step()
-    drain()
-    sync_all()
-    ms_per_step_all_events = 1e3 * (time.perf_counter() - t1) / n_prof
-    prof = {k: ctx.profile_get(k) for k in range(9)}
-    ctx.profile_enable(0)
-    # the same frames submitted synchronously (pose read before the next frame's staging is enqueued): what rounds 1 and 2 reported
-    # (this loop also brackets iteration 0's launch -- the search alone, which a pipelined, chained frame no longer has: its first launch completes the previous frame)
-    ctx.profile_enable((1 << mla.K_KNN) if args.profile_events else 0)
-    ctx.profile_sample(3)
-    ctx.profile_reset()
-    sync_all()
-    t1s = time.perf_counter()
-    for _ in range(n_prof):
-        step_sync()
-    sync_all()
-    ms_per_step_sync = 1e3 * (time.perf_counter() - t1s) / n_prof
-    cold_sync = ctx.profile_get(mla.K_KNN)
-    ctx.profile_enable(0)
-    ctx.profile_sample(1)
+    # a second, fully instrumented pass (every kernel bracketed) for the per-kernel breakdown; not part of `value` (--full)
+    if full:
+        n_prof = max(args.steps // 4, 5)
+        ctx.profile_enable(mla.K_ALL)
+        ctx.profile_reset()
+        sync_all()
+        t1 = time.perf_counter()
+        for _ in range(n_prof):
+            step()
+        drain()
+        sync_all()
+        ms_per_step_all_events = 1e3 * (time.perf_counter() - t1) / n_prof
+        prof = {k: ctx.profile_get(k) for k in range(9)}
+        ctx.profile_enable(0)
+        # the same frames submitted synchronously (pose read before the next frame's staging is enqueued): what rounds 1 and 2 reported
+        # (this loop also brackets iteration 0's launch -- the search alone, which a pipelined, chained frame no longer has: its first launch completes the previous frame)
+        ctx.profile_enable((1 << mla.K_KNN) if args.profile_events else 0)
+        ctx.profile_sample(3)
+        ctx.profile_reset()
+        sync_all()
+        t1s = time.perf_counter()
+        for _ in range(n_prof):
+            step_sync()
+        sync_all()
+        ms_per_step_sync = 1e3 * (time.perf_counter() - t1s) / n_prof
+        cold_sync = ctx.profile_get(mla.K_KNN)
+        ctx.profile_enable(0)
+        ctx.profile_sample(1)
 
     # the same timed loop at the reference's keyframe cadences (a frame is saved as a keyframe after DISTANCE_KEYFRAMES = 1 m or ORIENTATION_KEYFRAMES = 1 deg of motion,
     # config_realvehicle_hercules.yaml:142-143: every frame for a vehicle at >= 10 m/s and 10 Hz, every ~10th at walking pace): the frame after a keyframe cannot have
     # its maps staged beside the previous solve
     keyframe_cadence = None
-    if pipelined and args.restage_every == 0 and not args.no_supplementary:
+    if full and pipelined and args.restage_every == 0 and not args.no_supplementary:
         keyframe_cadence = {}
         for kc in (1, 2, 5, 10):
             cadence[0], frame_no[0] = kc, 0
@@ -823,7 +843,7 @@ def main():
 
     # --- N > 1: what every rank measured, the exchange by itself, and (--comm both) the same loop over the other communicator
     per_rank = exchange_us = other_comm = None
-    if world > 1:
+    if world > 1 and full:
         mine = dict(rank=rank, device=local_rank,
                     knn_us=(round(1e3 * prof[mla.K_KNN][0] / prof[mla.K_KNN][1], 3) if prof[mla.K_KNN][1] else None),
                     fit_us=(round(1e3 * prof[mla.K_FIT][0] / prof[mla.K_FIT][1], 3) if prof[mla.K_FIT][1] else None),
@@ -858,7 +878,7 @@ def main():
     # supplementary: the reference's own per-frame call, scan2MapOptimization = index build + 2 outer x (match all, evalHessian +
     # evalDegenracy, Ceres-shaped Levenberg-Marquardt <= 30 iterations) -- not `value`, reported beside it
     s2m_ms = None
-    if world == 1 and not args.no_supplementary:
+    if full and world == 1 and not args.no_supplementary:
         for _ in range(3):
             ctx.map_rebuild(mla.ALL_KINDS)
             s2m_pose, s2m_stats = ctx.scan2map(p0, opts)
@@ -911,7 +931,7 @@ def main():
     # A context of its own (the main context's staged features stay what the other legs expect). Two clocks: every stage followed by a wait (ms per stage; the
     # waits are part of what is measured), and the frame with no wait but the one for the pose (ms_per_frame).
     frame = None
-    if world == 1 and not args.no_supplementary and len(scans) >= 2 and not args.dense_features:
+    if full and world == 1 and not args.no_supplementary and len(scans) >= 2 and not args.dense_features:
         fctx = mla.Context(local_rank)
         try:
             f_ext = np.array([np.concatenate([r_[4:7], r_[:4]]) for r_ in synth.HERCULES_BODY_T_LASER])[:len(scans)]
@@ -1052,7 +1072,7 @@ def main():
 
     # supplementary (N = 1): what N = 2 / 4 / 8 should show on this frame, per split, from each rank's share solved alone on this GPU
     predicted = None
-    if world == 1 and not args.no_supplementary and not args.dense_features:
+    if full and world == 1 and not args.no_supplementary and not args.dense_features:
         try:
             predicted = predicted_scaling(mla, torch, shard, local_rank, surf_map, corner_map, surf, corner, np.asarray(pose, np.float64), center)
         except Exception as ex:      # (a supplementary leg must not cost the line)
@@ -1079,19 +1099,20 @@ def main():
     Tm = synth.pose_to_mat(p0)
     planes = shard.wedge_planes(center, world, rank)
     bytes_per_launch, bytes_ball, cbars, cballs, n_owned = 0.0, 0.0, {}, {}, {}
-    for name, feats, lmap in (("surf", surf, local_surf_map), ("corner", corner, local_corner_map)):
-        fm = synth.transform_points(feats[:, :3], Tm)
-        own = (shard.owned_mask(fm, *planes) if args.shard_mode == "map" else (np.arange(len(feats)) % world) == rank) if world > 1 else np.ones(len(feats), bool)
-        cb, cball = candidate_stats(lmap, fm[own], h)
-        cbars[name], cballs[name], n_owned[name] = round(cb, 2), round(cball, 2), int(own.sum())
-        # B_feat = 16 (query) + 27 x 8 (cell begin/end) + 12 x C-bar (candidate xyz); the partial normal equations
-        # (232 B per 256-feature tile) are negligible. This is the figure `achieved` uses.
-        bytes_per_launch += int(own.sum()) * (16.0 + 27 * 8 + 12.0 * cb)
-        # the same formula with only the cells an exact search cannot avoid (those the 5th-neighbour ball touches): the near-cells-first
-        # search reads between this and the 27-cell figure
-        bytes_ball += int(own.sum()) * (16.0 + 27 * 8 + 12.0 * cball)
+    if full:       # (candidate counts over the map on the host: seconds at 500k points)
+        for name, feats, lmap in (("surf", surf, local_surf_map), ("corner", corner, local_corner_map)):
+            fm = synth.transform_points(feats[:, :3], Tm)
+            own = (shard.owned_mask(fm, *planes) if args.shard_mode == "map" else (np.arange(len(feats)) % world) == rank) if world > 1 else np.ones(len(feats), bool)
+            cb, cball = candidate_stats(lmap, fm[own], h)
+            cbars[name], cballs[name], n_owned[name] = round(cb, 2), round(cball, 2), int(own.sum())
+            # B_feat = 16 (query) + 27 x 8 (cell begin/end) + 12 x C-bar (candidate xyz); the partial normal equations
+            # (232 B per 256-feature tile) are negligible. This is the figure `achieved` uses.
+            bytes_per_launch += int(own.sum()) * (16.0 + 27 * 8 + 12.0 * cb)
+            # the same formula with only the cells an exact search cannot avoid (those the 5th-neighbour ball touches): the near-cells-first
+            # search reads between this and the 27-cell figure
+            bytes_ball += int(own.sum()) * (16.0 + 27 * 8 + 12.0 * cball)
     roofline = None
-    if knn_n > 0:
+    if full and knn_n > 0:
         dur_s = 1e-3 * knn_ms / knn_n
         ach = bytes_per_launch / dur_s / 1e9
         _lanes = (ctx.map_info(mla.SURF)["knn_lanes"], ctx.map_info(mla.CORNER)["knn_lanes"])
@@ -1146,7 +1167,7 @@ def main():
     # second roofline object: the TIME-dominant kernel (fit + gates + residual / Jacobian + reduction + the fused Gauss-Newton finish). Duration from the
     # fully instrumented pass (every kernel bracketed; not the timed region, where only the correspondence kernel carries events).
     roofline_fit = None
-    if prof[mla.K_FIT][1]:
+    if full and prof[mla.K_FIT][1]:
         fit_s = 1e-3 * prof[mla.K_FIT][0] / prof[mla.K_FIT][1]
         n_own = sum(n_owned.values())
         tiles = (len(surf) + 255) // 256 + (len(corner) + 255) // 256
@@ -1166,7 +1187,7 @@ def main():
     # supplementary: a frame whose map has OUTGROWN the sticky grid box: every step stages a cloud that alternately has / has not a few points 40 m
     # outside the box of the previous one, so the bounds pass + re-layout path of mlh_map_set_pair is what is timed. Not `value`.
     outgrow_ms = None
-    if world == 1 and not args.no_map_rebuild and not args.map_rebuild_only and not args.no_supplementary:
+    if full and world == 1 and not args.no_map_rebuild and not args.map_rebuild_only and not args.no_supplementary:
         ext = torch.tensor([[1.0, 1.0, 0.0], [-1.0, -1.0, 0.0]], device="cuda") * float(np.abs(local_surf_map[:, :2]).max() + 40.0)
         grown = torch.cat([d_surf_map[:, :3], ext.to(d_surf_map.dtype)], dim=0).contiguous()
         plain = d_surf_map[:, :3].contiguous()
@@ -1188,7 +1209,7 @@ def main():
     #     point is a query: ~10x the launch), same maps, same solve. Supplementary (`roofline.saturated`): it says at which launch size the correspondence kernel's
     #     rate stops being set by the length of one query's dependent chain.
     saturated = None
-    if world == 1 and not args.dense_features and roofline is not None and not args.no_supplementary:
+    if full and world == 1 and not args.dense_features and roofline is not None and not args.no_supplementary:
         surf_d, corner_d = fuse_features(synth, scans, extracted, thin=False)
         ctx.features_set(mla.SURF, torch.from_numpy(surf_d).cuda())
         ctx.features_set(mla.CORNER, torch.from_numpy(corner_d).cuda())
@@ -1229,11 +1250,11 @@ def main():
     #     mlh_gn_solve_blocks on this run's map, sharded like the single-pose frame: the headline with --config4, a supplementary leg at --gpus 8 (the
     #     configuration BASELINE.json quotes config 4 on) otherwise. Last thing measured: it replaces the context's staged features.
     cfg4 = None
-    if args.config4 or world == 8:
+    if args.config4 or (full and world == 8):
         scans4 = list(scans)[:4] + [synth.simulate_scan(sc, gt, synth.HERCULES_BODY_T_LASER[i], N_RINGS, seed=7 + i) for i in range(len(scans), 4)]
         surf_b, corner_b, poses0 = config4_blocks(mla, synth, ctx, scans4, gt)
         ref4 = None
-        if world > 1:
+        if world > 1 and full:
             if rank == 0:
                 ref4 = single_gpu_config4(mla, torch, local_rank, surf_map, corner_map, surf_b, corner_b, poses0, args.steps, args.warmup)
             dist.barrier()
@@ -1261,7 +1282,7 @@ def main():
                     n1_same_map_ms_per_step=(ref4 or {}).get("ms_per_step"),
                     speedup_vs_n1_same_map=(round(ref4["ms_per_step"] / (1e3 * el4 / args.steps), 4) if ref4 else None),
                     pose_vs_n1_same_map_m=(float(np.abs(np.asarray(ref4["poses"])[:, :3] - np.asarray(poses4_t)[:, :3]).max()) if ref4 else None))
-        if world > 1:
+        if world > 1 and full:
             # the same frame with the BLOCKS dealt over the ranks instead of the map (replicated here): no exchange at all, and the only split of this path that can
             # shorten a frame whose kernels are latency-bound
             s_b, poses_b, owner_b = block_sharded_config4(mla, torch, dist, dist_dev, local_rank, rank, world, surf_map, corner_map, surf_b, corner_b, poses0,
@@ -1278,7 +1299,7 @@ def main():
                 ranks_share_gpus=bool(shared_gpus))
 
     owned_all = local_map_all = None
-    if world > 1:
+    if world > 1 and full:
         t_own = torch.zeros((world, 2), dtype=torch.int64, device=dist_dev)
         t_own[rank, 0], t_own[rank, 1] = n_owned["surf"], n_owned["corner"]
         dist.all_reduce(t_own)
@@ -1308,23 +1329,11 @@ def main():
                                hip_events_in_timed_region=(f"dominant kernel, 1 launch in {2 * GN_ITERS + 1} of each of its two forms" if args.profile_events else "none")),
                    queries_per_s=round(queries_per_s, 1), valid_correspondences_per_step=n_valid_step,
                    ms_per_gn_iter=round(ms_per_step / GN_ITERS, 4),
-                   ms_per_step_all_kernels_bracketed=round(ms_per_step_all_events, 4),
-                   ms_per_step_synchronous_submission=round(ms_per_step_sync, 4),
-                   ms_per_step_by_keyframe_cadence=keyframe_cadence,
-                   keyframe_cadence_note=("`value` / ms_per_step: no frame of the timed region is a keyframe, i.e. every frame reuses the previous frame's local map, which is what the reference does between "
-                                          "keyframes (lidar_mapper_keyframe.cpp:257-261) and what makes staging beside the solve legal. every_K: each K-th frame is saved as a keyframe, the "
-                                          "next frame's maps are staged only after its pose has been read (facade: PipelinedMapper; every_1 = a keyframe per frame = synchronous staging)"),
                    frame_submission=(("pipelined + overlapped staging: frame k+1's maps are staged and indexed on a second stream, into the other map set, while frame k's solve "
                                       "runs (mlh_map_set_pair_overlapped); frame k+1's solve is submitted behind it with its start pose chained on the device from frame k's result "
                                       "(mlh_gn_solve_begin_chained: transformUpdate + transformAssociateToMap); poses are collected one frame late (mlh_gn_solve_end)" if not args.no_overlap_staging else
                                       "pipelined: frame k's pose is collected after frame k+1's map staging and solve (start pose chained on the device) have been enqueued behind its solve")
                                      if pipelined else "synchronous: every pose is read before the next frame is staged"),
-                   kernel_us_per_launch={name: (round(1e3 * prof[k][0] / prof[k][1], 3) if prof[k][1] else None)
-                                         for name, k in (("knn_features (surf+corner)", mla.K_KNN),
-                                                         ("knn_features behind the previous iteration's finish (iterations >= 1)", mla.K_KNN_PRE),
-                                                         ("knn_features of a chained frame's iteration 0 (previous frame's final + publication + chain, then the cold search)", mla.K_KNN_FIRST),
-                                                         ("fit_linearize+gn_finish (surf+corner)", mla.K_FIT),
-                                                         ("map_index_build (both maps, 4 launches)", mla.K_GRID_BUILD))},
                    multi_gpu=(None if world == 1 else dict(
                        shard_mode=args.shard_mode,
                        communicator=("mailbox" if comm_kind == "p2p" else "rccl"), communicator_requested=args.comm, ranks_seen_by_the_collective=comm_state["ranks_seen"],
@@ -1339,16 +1348,29 @@ def main():
                        speedup_vs_n1_same_map=(round(n1_ref["ms_per_step"] / ms_per_step, 4) if n1_ref else None),
                        owned_features_per_rank=owned_all, local_map_points_per_rank=local_map_all,
                        per_rank_kernel_us=per_rank, exchange_us_standalone_allreduce_of_32_f64=exchange_us, other_communicator=other_comm,
-                       allreduce_us_per_call_rank0=(round(1e3 * prof[mla.K_ALLREDUCE][0] / prof[mla.K_ALLREDUCE][1], 3) if prof[mla.K_ALLREDUCE][1] else None),
-                       solve_update_us_per_call_rank0=(round(1e3 * prof[mla.K_SOLVE][0] / prof[mla.K_SOLVE][1], 3) if prof[mla.K_SOLVE][1] else None),
+                       allreduce_us_per_call_rank0=(round(1e3 * prof[mla.K_ALLREDUCE][0] / prof[mla.K_ALLREDUCE][1], 3) if full and prof[mla.K_ALLREDUCE][1] else None),
+                       solve_update_us_per_call_rank0=(round(1e3 * prof[mla.K_SOLVE][0] / prof[mla.K_SOLVE][1], 3) if full and prof[mla.K_SOLVE][1] else None),
                        note=("per GN iteration and rank: correspondence kernel + fit kernel whose finishing workgroup exchanges the 32-double record with the peers and solves (2 launches, as unsharded)" if comm_kind == "p2p" else "per GN iteration and rank: correspondence kernel + fit kernel (local reduce) + ONE ncclAllReduce of 32 f64 + the redundant 6x6 solve launch"))),
-                   extract_ms_per_lidar_scan=[round(x, 4) for x in extract_ms],
-                   extract_points_per_s=round(n_scan_points / (1e-3 * sum(extract_ms)), 1),
-                   extract_ms_all_lidars_one_launch_set=round(extract_all_ms, 4),
                    final_pose=[round(float(x), 9) for x in pose],
-                   gpu_clock_spinup_ms=round(spin_ms, 1),
-                   ms_per_step_map_outgrows_its_grid_box=(round(outgrow_ms, 4) if outgrow_ms is not None else None),
-                   roofline=roofline, roofline_time_dominant_kernel=roofline_fit)
+                   gpu_clock_spinup_ms=round(spin_ms, 1))
+        if full:       # what the default run leaves out: the per-kernel and submission-mode figures, the extraction timings, the rooflines
+            out.update(ms_per_step_all_kernels_bracketed=round(ms_per_step_all_events, 4),
+                       ms_per_step_synchronous_submission=round(ms_per_step_sync, 4),
+                       ms_per_step_by_keyframe_cadence=keyframe_cadence,
+                       keyframe_cadence_note=("`value` / ms_per_step: no frame of the timed region is a keyframe, i.e. every frame reuses the previous frame's local map, which is what the reference does between "
+                                              "keyframes (lidar_mapper_keyframe.cpp:257-261) and what makes staging beside the solve legal. every_K: each K-th frame is saved as a keyframe, the "
+                                              "next frame's maps are staged only after its pose has been read (facade: PipelinedMapper; every_1 = a keyframe per frame = synchronous staging)"),
+                       kernel_us_per_launch={name: (round(1e3 * prof[k][0] / prof[k][1], 3) if prof[k][1] else None)
+                                             for name, k in (("knn_features (surf+corner)", mla.K_KNN),
+                                                             ("knn_features behind the previous iteration's finish (iterations >= 1)", mla.K_KNN_PRE),
+                                                             ("knn_features of a chained frame's iteration 0 (previous frame's final + publication + chain, then the cold search)", mla.K_KNN_FIRST),
+                                                             ("fit_linearize+gn_finish (surf+corner)", mla.K_FIT),
+                                                             ("map_index_build (both maps, 4 launches)", mla.K_GRID_BUILD))},
+                       extract_ms_per_lidar_scan=[round(x, 4) for x in extract_ms],
+                       extract_points_per_s=round(n_scan_points / (1e-3 * sum(extract_ms)), 1),
+                       extract_ms_all_lidars_one_launch_set=round(extract_all_ms, 4),
+                       ms_per_step_map_outgrows_its_grid_box=(round(outgrow_ms, 4) if outgrow_ms is not None else None),
+                       roofline=roofline, roofline_time_dominant_kernel=roofline_fit)
         if cfg4 is not None:
             out["config4"] = cfg4
             if args.config4:      # config 4's frame is the headline; the single-pose frame's numbers stay in the line as `config2_leg`
@@ -1374,7 +1396,7 @@ def main():
                                         "the call the reference makes once per frame (lidar_mapper_keyframe.cpp:423-639)")
 
     # --- CPU baseline: the oracle (port of the reference's CPU path), bounded sample, rank 0 at N = 1 only
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import oracle as O
         O.build()
@@ -1464,6 +1486,14 @@ def main():
             except Exception as ex:
                 out["frame"]["cpu_port_error"] = str(ex)[:200]
     if rank == 0:
+        if args.dump_outputs:
+            # what the caller of the timed path received from its last step (every rank holds the same pose: the solve's sums are all-reduced)
+            dumped = dict(pose=np.asarray(pose, np.float64))
+            if args.config4:
+                dumped["config4_poses"] = np.asarray(poses4_t, np.float64)
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name_, a_ in dumped.items():
+                np.save(os.path.join(args.dump_outputs, f"{name_}.npy"), a_)
         print(json.dumps(out))
     ctx.close()
     if world > 1:

@@ -12,18 +12,20 @@ and the reference's own TYPES those lines are written against:
   cloudFeature, PointPlaneFeature, FeatureWithScore, ScanInfo    estimator/src/estimator/parameters.h:161-207
   class Pose + the members used here        estimator/src/estimator/pose.h:38-66; pose.cpp:16-41, 99-113
 
-The cut text lives in tests/host/refcut/_gen/ only for the duration of the compile (never committed); the executable goes to tests/host/refcut/_build/
-(git-ignored, travels to the GPU box like the built .so files). Needs /root/reference: on a box without it the prebuilt executable is used."""
+The driver is tests/host/refcut/refcut_selftest.cpp. The cut text lives in oracle/_ref/refcut/_gen/ only for the duration of the compile (never committed); the
+executable goes to oracle/_ref/refcut/ (git-ignored, built next to libmloam_ref.so and shipped with it). Needs the reference tree: where it is absent, the
+prebuilt executable is used."""
 import os
 import shutil
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(os.path.dirname(os.path.dirname(HERE)))
+ROOT = os.path.dirname(os.path.dirname(HERE))
 REF = os.environ.get("MLOAM_REFERENCE", "/root/reference")
-GEN = os.path.join(HERE, "_gen")
-OUT = os.path.join(HERE, "_build")
+SRC_DIR = os.path.join(ROOT, "tests", "host", "refcut")
+OUT = os.path.join(ROOT, "oracle", "_ref", "refcut")
+GEN = os.path.join(OUT, "_gen")
 EXE = os.path.join(OUT, "refcut_selftest")
 CUTS = [
     ("point_with_cov.inc", "mloam_pcl/include/mloam_pcl/point_with_cov.hpp", 43, 112, "namespace pcl"),
@@ -40,7 +42,7 @@ CUTS = [
     ("set_input_cloud.inc", "estimator/src/lidarMapper/lidar_mapper_keyframe.cpp", 433, 434, "kdtree_surf_from_map->setInputCloud(laser_cloud_surf_from_map_cov_ds);"),
     ("add_residual_blocks.inc", "estimator/src/lidarMapper/lidar_mapper_keyframe.cpp", 537, 571, "for (const size_t &fid : sel_surf_feature_idx)"),
 ]
-SOURCES = ["refcut_selftest.cpp", "build_refcut.py"]
+SOURCES = [os.path.join(SRC_DIR, "refcut_selftest.cpp"), os.path.abspath(__file__)]
 FACADE = os.path.join(ROOT, "m-loam_amd", "host", "mloam_facade.hpp")
 
 
@@ -48,7 +50,7 @@ def compile_cmd(out, src, extra=()):
     lib = os.path.join(ROOT, "m-loam_amd", "lib")
     return ["g++", "-O2", "-std=c++17", "-fopenmp", "-ffp-contract=off", "-Wall", "-Wno-unused-variable", "-Wno-unused-but-set-variable", "-Wno-invalid-offsetof", "-Wno-pedantic", "-Wno-mismatched-new-delete", "-Wno-sign-compare",
             "-DMLOAM_FACADE_USE_PCL_TYPES", "-DMLOAM_FACADE_CERES_BASES", "-I", os.path.join(ROOT, "tests", "host", "pcl_stub"), "-I", os.path.join(ROOT, "m-loam_amd", "host"),
-            "-I", os.path.join(ROOT, "include"), *extra, "-o", out, src, "-L", lib, "-lmloam_hip", "-Wl,-rpath,$ORIGIN/../../../../m-loam_amd/lib", f"-Wl,-rpath,{lib}",
+            "-I", os.path.join(ROOT, "include"), *extra, "-o", out, src, "-L", lib, "-lmloam_hip", "-Wl,-rpath,$ORIGIN/../../../m-loam_amd/lib", f"-Wl,-rpath,{lib}",
             "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib"]
 
 
@@ -57,7 +59,7 @@ def build(force=False, out=None, verbose=False):
     exe = out or EXE
     if not os.path.isdir(os.path.join(REF, "estimator", "src")):
         return exe if os.path.exists(exe) else None
-    deps = [os.path.join(HERE, f) for f in SOURCES] + [FACADE, os.path.join(ROOT, "include", "mloam_hip.h"), os.path.join(ROOT, "oracle", "ref", "mini_eigen.hpp")]
+    deps = list(SOURCES) + [FACADE, os.path.join(ROOT, "include", "mloam_hip.h"), os.path.join(ROOT, "oracle", "ref", "mini_eigen.hpp")]
     stub = os.path.join(ROOT, "tests", "host", "pcl_stub")
     for d, _, fs in os.walk(stub):
         deps += [os.path.join(d, f) for f in fs]
@@ -73,7 +75,7 @@ def build(force=False, out=None, verbose=False):
             lines = open(os.path.join(REF, rel)).read().split("\n")
             assert must in lines[a - 1], f"{rel}:{a} is not '{must}' -- the reference tree differs from the surveyed one"
             open(os.path.join(GEN, name), "w").write("\n".join(lines[a - 1:b]) + "\n")
-        cmd = compile_cmd(exe, os.path.join(HERE, "refcut_selftest.cpp"))
+        cmd = compile_cmd(exe, os.path.join(SRC_DIR, "refcut_selftest.cpp"), extra=("-I", OUT))       # "_gen/*.inc" resolve under OUT
         if verbose:
             print(" ".join(cmd))
         subprocess.run(cmd, check=True)

@@ -29,7 +29,7 @@ out = {
     "workload": f"2x64_vs_500k_{tag}",
     "kernel": f"mlh::{main} (iterations >= 1 of a solve: the previous iteration's finish in every workgroup, then the bounded search)",
     "source": f"rocprofv3 --pmc FETCH_SIZE GRBM_GUI_ACTIVE / --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum / --pmc SQ_* (separate passes, --kernel-trace only; scripts/profile_round6.sh), "
-              f"python bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-supplementary --profile-events 0 --synchronous; means over {get(main, 'FETCH_SIZE')[0]} dispatches; FETCH_SIZE doubled per "
+              f"python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-supplementary --profile-events 0 --synchronous; means over {get(main, 'FETCH_SIZE')[0]} dispatches; FETCH_SIZE doubled per "
               f"MI355X_MICROARCH.md (gfx950 reports 1/2 of wide coalesced reads); see profiles/{tag}_pmc_summary.txt",
     "fetch_size_kb_raw": get(main, "FETCH_SIZE")[1], "write_size_kb": get(main, "WRITE_SIZE")[1],
     "tcc_hit": get(main, "TCC_HIT_sum")[1], "tcc_miss": get(main, "TCC_MISS_sum")[1],

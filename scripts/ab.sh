@@ -9,7 +9,7 @@ for rep in $(seq 1 $REPS); do
   for v in "$@"; do
     i=$((i+1))
     vv="$v"; [ "$v" = "-" ] && vv=""
-    env $vv timeout 300 python bench.py --steps ${STEPS:-400} --warmup 20 --no-cpu-baseline $BENCH_ARGS > $OUT/ab_$i.json 2> $OUT/ab_$i.err
+    env $vv timeout 300 python bench.py --full --steps ${STEPS:-400} --warmup 20 --no-cpu-baseline $BENCH_ARGS > $OUT/ab_$i.json 2> $OUT/ab_$i.err
     python - "$v" $OUT/ab_$i.json <<'PY'
 import json, sys
 try:

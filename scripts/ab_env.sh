@@ -4,7 +4,7 @@
 VAR=$1; A=$2; B=$3; REPS=${4:-2}; shift 4
 for rep in $(seq 1 $REPS); do
   for v in "$A" "$B"; do
-    if [ "$v" = "-" ]; then r=$(env -u $VAR python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1); else r=$(env $VAR=$v python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1); fi
+    if [ "$v" = "-" ]; then r=$(env -u $VAR python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1); else r=$(env $VAR=$v python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1); fi
     echo "$r" | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); f=d.get('frame') or {}; s=d.get('scan2map') or {}

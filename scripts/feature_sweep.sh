@@ -8,7 +8,7 @@ OUT=$REPO/gpurun_out/sweep_$TAG
 mkdir -p $OUT
 row() {  # $1 = label, rest = bench flags
   local label=$1; shift
-  timeout 400 python bench.py --steps 60 --warmup 5 --no-cpu-baseline "$@" > $OUT/$label.json 2> $OUT/$label.err
+  timeout 400 python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline "$@" > $OUT/$label.json 2> $OUT/$label.err
   python - "$label" $OUT/$label.json <<'PY'
 import json, sys
 try:
@@ -25,7 +25,7 @@ except Exception as e:
 PY
 }
 {
-echo "# scripts/feature_sweep.sh (one MI355X, 500k map): python bench.py --steps 60 --warmup 5 --no-cpu-baseline --lidars N [--dense-features]"
+echo "# scripts/feature_sweep.sh (one MI355X, 500k map): python bench.py --full --steps 60 --warmup 5 --no-cpu-baseline --lidars N [--dense-features]"
 echo "# frac = SURVEY 8(d) 27-cell bytes / duration of the dominant correspondence launch (iterations >= 1: search behind the previous iteration's finish) / 8 TB/s;"
 echo "# unavoidable = the cells the 5th-neighbour ball touches; search-only = iteration 0's launch (no prologue, no bound)"
 for n in 1 2 3 4; do row thin_${n}x64 --lidars $n; done
@@ -37,7 +37,7 @@ for label in "thin_2x64 --lidars 2" "dense_4x64 --lidars 4 --dense-features"; do
   i=0
   for C in "FETCH_SIZE GRBM_GUI_ACTIVE" "WRITE_SIZE TCC_HIT_sum TCC_MISS_sum"; do
     i=$((i+1))
-    timeout 300 rocprofv3 --kernel-trace --pmc $C -d $OUT/pmc_${name}_$i -o pmc -- python $REPO/bench.py --steps 12 --warmup 2 --no-cpu-baseline --no-supplementary --profile-events 0 --synchronous "$@" > /dev/null 2> $OUT/pmc_${name}_$i.log
+    timeout 300 rocprofv3 --kernel-trace --pmc $C -d $OUT/pmc_${name}_$i -o pmc -- python $REPO/bench.py --full --steps 12 --warmup 2 --no-cpu-baseline --no-supplementary --profile-events 0 --synchronous "$@" > /dev/null 2> $OUT/pmc_${name}_$i.log
     DBP=$(find $OUT/pmc_${name}_$i -name '*.db' | head -1)
     [ -n "$DBP" ] && python $REPO/profiles/summarize_pmc.py $DBP knn_features_kernel > $OUT/pmc_${name}_$i.txt
     rm -rf $OUT/pmc_${name}_$i

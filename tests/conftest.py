@@ -13,8 +13,8 @@ if ROOT not in sys.path:
 sys.path.insert(0, os.path.join(ROOT, "oracle"))
 
 
-# The strongest pins compare against the reference's OWN lines: oracle/_ref/libmloam_ref.so and tests/host/refcut/_build/refcut_selftest, built where
-# /root/reference exists and travelling to the GPU box as built files. A box where they are expected but absent must FAIL those tests, not skip them
+# The strongest pins compare against the reference's OWN lines: oracle/_ref/libmloam_ref.so and oracle/_ref/refcut/refcut_selftest, built where
+# the reference tree exists and shipped to the GPU machine as built files. A box where they are expected but absent must FAIL those tests, not skip them
 # (VERDICT r04): MLOAM_REQUIRE_REF=1 turns every skip whose reason is the missing reference build into a failure. Default: required wherever the reference tree
 # is mounted, and wherever the built product library travelled (then the checkers built next to it should have travelled too); MLOAM_REQUIRE_REF=0 opts out
 # (a fresh clone that only built the product).

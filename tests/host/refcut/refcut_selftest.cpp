@@ -1,6 +1,6 @@
 // TEST INFRASTRUCTURE ONLY -- the reference's own call sites of the hot path, compiled VERBATIM against the drop-in boundary.
 //
-// tests/host/refcut/build_refcut.py cuts the line ranges named below out of /root/reference into _gen/*.inc (never committed, deleted after the compile); this
+// oracle/ref/build_refcut.py cuts the line ranges named below out of the reference tree into _gen/*.inc (never committed, deleted after the compile); this
 // file supplies what surrounds those lines in the reference -- the declarations of the variables they name -- and nothing else. Everything the cut lines CALL is
 // m-loam_amd/host/mloam_facade.hpp (-DMLOAM_FACADE_USE_PCL_TYPES -DMLOAM_FACADE_CERES_BASES) over headers shaped like PCL / boost / Eigen / Ceres
 // (tests/host/pcl_stub); every TYPE they name is the reference's own, cut as well: pcl::PointXYZIWithCov, common::PointICloud, cloudFeature, PointPlaneFeature,

@@ -1,4 +1,4 @@
-"""Row (b), on the reference's own text. tests/host/refcut/build_refcut.py cuts the reference's CALL SITES of the hot path -- the estimator's OpenMP front end
+"""Row (b), on the reference's own text. oracle/ref/build_refcut.py cuts the reference's CALL SITES of the hot path -- the estimator's OpenMP front end
 (estimator.cpp:248-270), kdtree_*_from_map->setInputCloud (lidar_mapper_keyframe.cpp:433-434), the AddResidualBlock loops (cpp:537-571) -- and the reference's own
 TYPES (pcl::PointXYZIWithCov, common::PointICloud, cloudFeature, PointPlaneFeature, ScanInfo, Pose) out of /root/reference and compiles them, unchanged, against
 m-loam_amd/host/mloam_facade.hpp in its in-tree mode (-DMLOAM_FACADE_USE_PCL_TYPES -DMLOAM_FACADE_CERES_BASES) over headers shaped like PCL / boost / Eigen / Ceres
@@ -17,7 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _refcut():
-    spec = importlib.util.spec_from_file_location("build_refcut", os.path.join(ROOT, "tests", "host", "refcut", "build_refcut.py"))
+    spec = importlib.util.spec_from_file_location("build_refcut", os.path.join(ROOT, "oracle", "ref", "build_refcut.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod

@@ -1,9 +1,11 @@
-"""bench.py honours the driver's contract: exactly one JSON line on stdout with the required keys and types."""
+"""bench.py honours the driver's contract: exactly one JSON line on stdout with the required keys and types. The default run prints the headline alone;
+--full adds the rest (rooflines, CPU baseline, per-kernel and submission-mode figures, the N > 1 references), which most of these tests read."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -11,7 +13,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def test_bench_json_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-seconds", "1.0"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--cpu-seconds", "1.0", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -47,6 +49,28 @@ def test_bench_json_line():
     assert d["frame_submission"].startswith("pipelined") and d["ms_per_step_synchronous_submission"] > 0
 
 
+def test_bench_default_run_is_the_headline_and_dumps_its_outputs(tmp_path):
+    """the default run (no --full) times exactly --steps steps and prints the headline alone; --dump-outputs writes the pose the last timed step returned"""
+    out = tmp_path / "outputs"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2", "--dump-outputs", str(out)],
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    for k, t in (("metric", str), ("value", float), ("unit", str), ("ms_per_step", float), ("higher_is_better", bool), ("dtype", str), ("config", dict)):
+        assert isinstance(d[k], t), (k, d[k])
+    assert d["steps"] == 7 and d["warmup"] == 2 and d["n_gpus"] == 1 and d["higher_is_better"] is True and d["ms_per_step"] > 0
+    n_valid = sum(a + b for a, b in d["config"]["n_valid_per_iter_surf_corner"])
+    assert n_valid == d["valid_correspondences_per_step"] and abs(d["value"] - n_valid / (d["ms_per_step"] * 1e-3)) < 1e-3 * d["value"]
+    for k in ("roofline", "cpu_baseline", "kernel_us_per_launch", "ms_per_step_synchronous_submission", "scan2map", "frame"):
+        assert k not in d, k
+    pose = np.load(out / "pose.npy")
+    assert pose.dtype == np.float64 and pose.shape == (7,)
+    np.testing.assert_allclose(pose, d["final_pose"], rtol=0, atol=1e-9)
+    assert abs(np.linalg.norm(pose[3:]) - 1.0) < 1e-9
+    assert sorted(p.name for p in out.iterdir()) == ["pose.npy"]
+
 def _bench(*flags, env=None, timeout=900):
     e = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):      # as typed at a shell: no launcher around it
@@ -59,7 +83,7 @@ def test_bench_gpus_2_without_a_launcher_spawns_two_ranks():
     """`python bench.py --gpus 2` with no launcher (Next 1): the script spawns its two ranks itself; on this one-GPU box they share the device through the
     mailbox communicator. The line says n_gpus 2, carries both ranks' owned counts, what the collective saw, the same-map N = 1 reference measured by rank 0 alone
     before the sharded leg, per-rank kernel times, and says plainly that ranks sharing a GPU are not a scaling measurement."""
-    r = _bench("--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--map-preset", "500k")
+    r = _bench("--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--map-preset", "500k", "--full")
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
@@ -89,7 +113,7 @@ def test_bench_rank_count_mismatch_is_an_error():
 def test_bench_config4_two_ranks_sharing_the_gpu():
     """BASELINE config 4's frame (4 x 64 rings, four pose blocks, N_NEIGH 5/10/10/10 + CHECK_FOV) through the sharded mlh_gn_solve_blocks as the headline of an
     N = 2 run: equal poses to the same frame solved by rank 0 alone on the whole map"""
-    r = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--map-preset", "500k", "--config4")
+    r = _bench("--gpus", "2", "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--map-preset", "500k", "--config4", "--full")
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-3000:])
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     c4 = d["config4"]

@@ -268,13 +268,13 @@ def test_reference_call_sites_on_the_gpu(tmp_path, orc, case16, feats16):
     MapIndex::Ptr; the match functions filling the REFERENCE's PointPlaneFeature at the REFERENCE's Pose (validity == the oracle's); cpp:537-571 building one residual
     block per matched feature in a ceres::Problem that owns them, each block's r / J == the batched device evaluation (mlh_linearize) to 1e-9."""
     import importlib.util
-    spec = importlib.util.spec_from_file_location("build_refcut", os.path.join(ROOT, "tests", "host", "refcut", "build_refcut.py"))
+    spec = importlib.util.spec_from_file_location("build_refcut", os.path.join(ROOT, "oracle", "ref", "build_refcut.py"))
     rc = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(rc)
     exe = rc.build()
     if exe is None:
         if os.environ.get("MLOAM_REQUIRE_REF") == "1":
-            pytest.fail("MLOAM_REQUIRE_REF=1 but neither /root/reference nor the prebuilt tests/host/refcut/_build/refcut_selftest is here")
+            pytest.fail("MLOAM_REQUIRE_REF=1 but neither the reference tree nor the prebuilt oracle/_ref/refcut/refcut_selftest is here")
         pytest.skip("no reference tree and no prebuilt refcut_selftest")
     sc = case16["scans"][0]
     d = str(tmp_path)

@@ -50,8 +50,8 @@ def test_sharded_solver_over_two_rccl_ranks(mode):
 
 @needs_two
 def test_bench_two_ranks():
-    """bench.py --gpus 2 as the driver launches it: one JSON line from rank 0, the communicator formed, the all-reduce measured"""
-    r = _torchrun(2, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline")
+    """bench.py --gpus 2 --full as the driver launches it: one JSON line from rank 0, the communicator formed, the all-reduce measured (per-rank figures need --full)"""
+    r = _torchrun(2, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--no-cpu-baseline", "--full")
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
