@@ -328,6 +328,53 @@ int mlh_cloud_uct_associate_to_map(mlh_ctx *ctx, const void *points, int stride_
 int mlh_compound_pose_with_cov(const double pose_1[7], const double cov_1[36], const double pose_2[7], const double cov_2[36],
                                double pose_cp[7], double cov_cp[36]);
 
+/* ---------------------------------------------------------------- (f5) keyframe store + local map on the device
+ * saveKeyframe (lidar_mapper_keyframe.cpp:641-683) and extractSurroundingKeyFrames (cpp:254-354) with clearCloud (cpp:921-927): the context keeps
+ * the mapper's keyframes (pose with its cov_, the f32 position, the surf / corner clouds) and builds the local map from them in HBM.
+ * The save / no-save decision stays with the caller (saveKeyframe's distance / orientation test; the C++ facade's KeyframePolicy restates it).
+ * mlh_keyframe_save: one keyframe; pose [t, q(xyzw)] and its 6x6 covariance (cov_mapping), the two clouds as records of `stride_bytes` with xyz at
+ *   offset 0 and the LiDAR id (intensity) at `intensity_offset_bytes`, in `mem`. Only xyz and the LiDAR id are kept (cloudUCTAssociateToMap recomputes
+ *   the covariance, cpp:1143-1155). *key_out (may be NULL) <- the keyframe's index.
+ * mlh_keyframe_save_staged: the same with the context's current feature sets (what mlh_downsample_current_scan(_pair) / mlh_features_set left),
+ *   copied device to device.
+ * mlh_local_map_assemble: extractSurroundingKeyFrames around pose_cur. In the reference's order:
+ *   - no keyframes, or both filtered map clouds non-empty (cpp:256-261): nothing happens, *rebuilt = 0;
+ *   - radiusSearch(pose_cur.t_ as f32, surrounding_kf_radius): nearest first, equal distances by index;
+ *   - the cache (surrounding_existing_keyframes_id + the transformed clouds): entries that left the radius are erased (order kept), entering ones
+ *     appended in search order and transformed ONCE, with the ext_poses / ext_covs of this call (cloudUCTAssociateToMap, the arithmetic of
+ *     mlh_cloud_uct_associate_to_map bit for bit); a later call with other extrinsics does not re-transform cached entries;
+ *   - VoxelGridCovarianceMLOAM<PointI>(map_sur_kf_res) over the cached keyframes' positions, intensity = position in the cache: the clouds of the
+ *     entry each output point names are appended, in output order. REPRODUCED: keyframes that share a position voxel contribute only the voxel's
+ *     last member (std::sort order) -- with the shipped configs (map_sur_kf_res 1.0, distance_keyframes 1.0) this happens often;
+ *   - `+=` onto the pre-filter clouds, which only mlh_local_map_clear empties. REPRODUCED: while one kind filters to empty, every call rebuilds and
+ *     appends the same keyframes again;
+ *   - the two covariance filters (leaf_surf / leaf_corner, trace_threshold) through the context's voxel filter (mlh_set_voxel_member_order applies).
+ *   *n_surf_ds / *n_corner_ds <- the filtered counts; kf_ids_out (may be NULL; capacity >= the number of keyframes) <- the ids appended this call, in
+ *   order, *n_ids (may be NULL) their number. Two host waits per call (one more when a buffer grows); launches do not depend on the number of keyframes.
+ *   Beside a solve submitted with mlh_*_begin the call is correct (it reads no map index and writes nothing a solve reads) but it is enqueued behind
+ *   the solve on the context's stream and its waits include the solve.
+ * mlh_local_map_cloud: the pre-filter (filtered = 0) or filtered (1) map cloud of `kind`: 48-byte PointIWithCov records in HBM
+ *   {x, y, z, intensity, cov_vec[6], cov_trace, pad}, stride 48, intensity offset 12, cov offset 16, trace offset 40 -- for mlh_map_set_pair(_overlapped)
+ *   (..., MLH_MEM_DEVICE). Valid until the next assemble / clear / reset.
+ * mlh_keyframes_reset empties store, cache and map clouds and frees their memory (as does mlh_destroy). Outputs of mlh_local_map_info may be NULL. */
+typedef struct mlh_local_map_opts {
+    float surrounding_kf_radius;  /* SURROUNDING_KF_RADIUS, >= 0 */
+    float map_sur_kf_res;         /* MAP_SUR_KF_RES, > 0 */
+    float leaf_surf, leaf_corner; /* MAP_SURF_RES, MAP_CORNER_RES, > 0 */
+    double trace_threshold;       /* TRACE_THRESHOLD_MAPPING */
+    int with_ua;                  /* with_ua_flag */
+    double cov_measurement[9];    /* COV_MEASUREMENT, 3x3 */
+} mlh_local_map_opts;
+int mlh_keyframes_reset(mlh_ctx *ctx);
+int mlh_keyframe_save(mlh_ctx *ctx, const double pose[7], const double cov[36], const void *surf, int n_surf, const void *corner, int n_corner,
+                      int stride_bytes, int intensity_offset_bytes, int mem, int32_t *key_out);
+int mlh_keyframe_save_staged(mlh_ctx *ctx, const double pose[7], const double cov[36], int32_t *key_out);
+int mlh_local_map_assemble(mlh_ctx *ctx, const double pose_cur[7], const double *ext_poses, const double *ext_covs, int n_lidar, const mlh_local_map_opts *opts,
+                           int32_t *rebuilt, int32_t *n_surf_ds, int32_t *n_corner_ds, int32_t *kf_ids_out, int32_t *n_ids);
+int mlh_local_map_clear(mlh_ctx *ctx);
+int mlh_local_map_cloud(mlh_ctx *ctx, int kind, int filtered, const void **device_points, int32_t *n);
+int mlh_local_map_info(mlh_ctx *ctx, int32_t *n_keyframes, int32_t *n_cached, int64_t *store_bytes, int64_t *cache_bytes);
+
 /* ---------------------------------------------------------------- (a5) local map index
  * replaces pcl::KdTreeFLANN<PointT>::setInputCloud(cloud) as used at
  *   estimator/src/lidarMapper/lidar_mapper_keyframe.cpp:433-434 (and estimator.cpp:1095-1109, 1230-1233).

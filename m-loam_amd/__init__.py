@@ -42,6 +42,22 @@ class BlockOpts(C.Structure):
     _fields_ = [("n_blocks", C.c_int), ("k_neigh", C.c_int * 8), ("eig_thre", C.c_double * 8), ("freeze", C.c_int * 8)]
 
 
+class LocalMapOpts(C.Structure):
+    """mlh_local_map_opts: extractSurroundingKeyFrames' parameters"""
+    _fields_ = [("surrounding_kf_radius", C.c_float), ("map_sur_kf_res", C.c_float), ("leaf_surf", C.c_float), ("leaf_corner", C.c_float),
+                ("trace_threshold", C.c_double), ("with_ua", C.c_int), ("cov_measurement", C.c_double * 9)]
+
+
+def local_map_opts(surrounding_kf_radius=50.0, map_sur_kf_res=1.0, leaf_surf=0.4, leaf_corner=0.2, trace_threshold=0.6, with_ua=True, cov_measurement=None):
+    o = LocalMapOpts()
+    o.surrounding_kf_radius, o.map_sur_kf_res, o.leaf_surf, o.leaf_corner = surrounding_kf_radius, map_sur_kf_res, leaf_surf, leaf_corner
+    o.trace_threshold, o.with_ua = trace_threshold, int(bool(with_ua))
+    cm = np.diag([0.0025] * 3) if cov_measurement is None else np.asarray(cov_measurement, np.float64)
+    for i, v in enumerate(np.ascontiguousarray(cm, np.float64).reshape(9)):
+        o.cov_measurement[i] = float(v)
+    return o
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -115,6 +131,14 @@ def load_library():
     dp = C.POINTER(C.c_double)
     lib.mlh_cloud_uct_associate_to_map.argtypes = [vp, vp, ci, ci, ci, ci, ci, vp, vp, vp, vp, ci, vp, ci, cd, vp, C.POINTER(C.c_int32), ci]
     lib.mlh_compound_pose_with_cov.argtypes = [vp, vp, vp, vp, vp, vp]
+    i32p = C.POINTER(C.c_int32)
+    lib.mlh_keyframes_reset.argtypes = [vp]
+    lib.mlh_keyframe_save.argtypes = [vp, vp, vp, vp, ci, vp, ci, ci, ci, ci, i32p]
+    lib.mlh_keyframe_save_staged.argtypes = [vp, vp, vp, i32p]
+    lib.mlh_local_map_assemble.argtypes = [vp, vp, vp, vp, ci, C.POINTER(LocalMapOpts), i32p, i32p, i32p, i32p, i32p]
+    lib.mlh_local_map_clear.argtypes = [vp]
+    lib.mlh_local_map_cloud.argtypes = [vp, ci, ci, C.POINTER(vp), i32p]
+    lib.mlh_local_map_info.argtypes = [vp, i32p, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.mlh_downsample_current_scan.argtypes = [vp, ci, vp, ci, ci, ci, ci, cf, vp, vp, ci, vp, ci, cd, vp, C.POINTER(C.c_int32)]
     lib.mlh_track_opts_default.argtypes = [vp]
     lib.mlh_track_opts_default.restype = None
@@ -194,7 +218,28 @@ EXPORTED_SYMBOLS = [
     "mlh_match_linearize", "mlh_match_coeffs", "mlh_linearize", "mlh_good_feature_matching", "mlh_solver_opts_default", "mlh_gn_solve", "mlh_gn_solve_begin", "mlh_gn_solve_begin_chained", "mlh_gn_solve_end", "mlh_features_copy", "mlh_scan2map", "mlh_scan2map_begin", "mlh_scan2map_begin_chained", "mlh_scan2map_end",
     "mlh_shard_set", "mlh_shard_set_features", "mlh_comm_unique_id", "mlh_comm_init", "mlh_p2p_mailbox", "mlh_p2p_comm_init", "mlh_allreduce_f64",
     "mlh_pose_plus", "mlh_eval_degeneracy",
+    "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
 ]
+
+
+_hip = None
+
+
+def _hip_runtime():
+    """the HIP runtime the library is linked against (already mapped into the process by load_library)"""
+    global _hip
+    if _hip is None:
+        load_library()
+        for name in ("libamdhip64.so", "libamdhip64.so.7", "libamdhip64.so.6", os.path.join("/opt/rocm/lib", "libamdhip64.so")):
+            try:
+                _hip = C.CDLL(name)
+                break
+            except OSError:
+                continue
+        if _hip is None:
+            raise MlhError("the HIP runtime library could not be loaded")
+        _hip.hipMemcpy.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int]
+    return _hip
 
 
 def _p(a):
@@ -620,6 +665,72 @@ class Context:
         cov_off, tr_off = (16, 40) if ncol >= 11 else (-1, -1)
         self._ck(self.lib.mlh_voxel_filter(self.h, _p(a), ncol * 4, n, 12 if ncol >= 4 else -1, cov_off, tr_off, leaf, trace_threshold, _p(out), C.byref(cnt), MEM_HOST))
         return out[:cnt.value].copy()
+
+    # ---- keyframe store + local map (saveKeyframe / extractSurroundingKeyFrames / clearCloud on the device)
+    def keyframes_reset(self):
+        self._ck(self.lib.mlh_keyframes_reset(self.h))
+
+    def keyframe_save(self, pose, cov, surf, corner):
+        """saveKeyframe's store: pose [t, q(xyzw)], its 6x6 cov, the surf / corner clouds ((n, >= 4) [x y z lidar ...] arrays or device clouds) -> key"""
+        p = np.ascontiguousarray(pose, np.float64).reshape(7)
+        c = np.ascontiguousarray(cov, np.float64).reshape(36)
+        (ps, ss, ns, ms, ks), (pc, sc, nc, mc, kc) = _src(surf), _src(corner)
+        if ns == 0:
+            ss, ms = sc, mc
+        if nc == 0:
+            sc, mc = ss, ms
+        assert ss == sc and ms == mc and ss >= 16, "both clouds share record stride (>= 4 floats) and memory kind"
+        key = C.c_int32(-1)
+        self._ck(self.lib.mlh_keyframe_save(self.h, _p(p), _p(c), ps, ns, pc, nc, ss, 12, ms, C.byref(key)))
+        return key.value
+
+    def keyframe_save_staged(self, pose, cov):
+        """saveKeyframe with the context's staged feature sets (device to device) -> key"""
+        p = np.ascontiguousarray(pose, np.float64).reshape(7)
+        c = np.ascontiguousarray(cov, np.float64).reshape(36)
+        key = C.c_int32(-1)
+        self._ck(self.lib.mlh_keyframe_save_staged(self.h, _p(p), _p(c), C.byref(key)))
+        return key.value
+
+    def local_map_assemble(self, pose_cur, ext_poses, ext_covs, opts: LocalMapOpts):
+        """extractSurroundingKeyFrames -> dict(rebuilt, n_surf_ds, n_corner_ds, kf_ids (the ids appended this call, in order))"""
+        p = np.ascontiguousarray(pose_cur, np.float64).reshape(7)
+        ep = np.ascontiguousarray(ext_poses, np.float64).reshape(-1, 7)
+        ec = None if ext_covs is None else np.ascontiguousarray(ext_covs, np.float64).reshape(-1, 36)
+        nk = C.c_int32(0)
+        self._ck(self.lib.mlh_local_map_info(self.h, C.byref(nk), None, None, None))
+        ids = np.zeros(max(nk.value, 1), np.int32)
+        rb, a, b, n = C.c_int32(0), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mlh_local_map_assemble(self.h, _p(p), _p(ep), _p(ec), len(ep), C.byref(opts), C.byref(rb), C.byref(a), C.byref(b),
+                                                 ids.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(n)))
+        return dict(rebuilt=bool(rb.value), n_surf_ds=a.value, n_corner_ds=b.value, kf_ids=ids[:n.value].copy())
+
+    def local_map_cloud(self, kind, filtered=True) -> "DeviceCloud":
+        """the local map cloud of `kind` in HBM (48-byte PointIWithCov records): filtered = the _ds cloud, else the pre-filter one"""
+        ptr, n = C.c_void_p(), C.c_int32(0)
+        self._ck(self.lib.mlh_local_map_cloud(self.h, kind, int(bool(filtered)), C.byref(ptr), C.byref(n)))
+        return DeviceCloud(ptr.value, n.value, 48)
+
+    def local_map_fetch(self, kind, filtered=True):
+        """the same cloud copied to the host as (n, 11) float32 [x y z i cov6 trace]"""
+        dc = self.local_map_cloud(kind, filtered)
+        if dc.n == 0:
+            return np.zeros((0, 11), np.float32)
+        self.synchronize()
+        out = np.zeros((dc.n, 12), np.float32)
+        e = _hip_runtime().hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(dc.ptr), C.c_size_t(dc.n * 48), 2)   # hipMemcpyDeviceToHost
+        if e != 0:
+            raise MlhError(f"hipMemcpy of the local map failed ({e})")
+        return out[:, :11].copy()
+
+    def local_map_clear(self):
+        """clearCloud: the four map clouds (the cache and the store stay)"""
+        self._ck(self.lib.mlh_local_map_clear(self.h))
+
+    def local_map_info(self) -> dict:
+        a, b, c, d = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self.lib.mlh_local_map_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
+        return dict(n_keyframes=a.value, n_cached=b.value, store_bytes=c.value, cache_bytes=d.value)
 
     # ---- map / features
     def map_set(self, kind, points, min_match_sq_dis=1.0):

@@ -473,6 +473,7 @@ void mlh_destroy(mlh_ctx *ctx)
     { VoxBuf &v = ctx->vox; v.in.release(); v.bounds.release(); v.cell.release(); v.word_of.release(); v.wpre.release(); v.cnt.release(); v.members.release(); v.vox_of.release(); v.sorted_idx.release(); v.leader.release(); v.out.release(); v.sums.release(); v.total.release(); }
     ctx->state.release(); ctx->partials.release(); ctx->ticket.release(); ctx->stats.release(); ctx->knn_q.release(); ctx->knn_idx.release(); ctx->knn_d.release(); ctx->tmp.release(); ctx->stdsort.release(); ctx->allreduce_buf.release(); ctx->oob_flag.release();
     comm_destroy(ctx);
+    keyframes_release(ctx);
     if (ctx->h_state) (void)hipHostFree(ctx->h_state);
     if (ctx->h_solve) (void)hipHostFree(ctx->h_solve);
     if (ctx->h_occ) (void)hipHostFree(ctx->h_occ);

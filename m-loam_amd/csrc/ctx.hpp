@@ -205,6 +205,28 @@ struct VoxBuf {   // scratch of mlh_voxel_filter
     DevBuf in, bounds, cell, wpre, cnt, vox_of, word_of, sorted_idx, members, leader, out, sums, total;
 };
 
+// The mapper's keyframe store and the local map extractSurroundingKeyFrames builds from it (keyframes.hip; lidar_mapper_keyframe.cpp:254-354, 641-683)
+struct KfStore {
+    struct Key { double pose[7], cov[36]; float pos[3]; size_t off[2]; int n[2]; };        // one saved keyframe: pose + cov_, f32 position, its two clouds in `pts`
+    struct Entry { int id; size_t off[2]; int n[2]; int slot; };                            // one cached keyframe: reserved records in `cache` (kept counts: cnt[2 slot + kind])
+    std::vector<Key> keys;
+    DevBuf pts;                  // float4 {x, y, z, lidar} of every saved cloud, appended
+    size_t pts_used = 0;
+    std::vector<Entry> entries;  // surrounding_existing_keyframes_id + the transformed clouds, in the reference's order
+    std::vector<int> free_slots;
+    int n_slots = 0;
+    DevBuf cache, cache_tmp;     // 48-byte PointIWithCov records of the cached clouds (reserved ranges)
+    size_t cache_used = 0;
+    DevBuf cnt;                  // int per (slot, kind): kept records of a cached cloud (device only)
+    DevBuf pre[2], flt[2];       // laser_cloud_{surf,corner}_from_map_cov and their _ds, 48-byte records
+    int pre_n[2] = {0, 0}, flt_n[2] = {0, 0};
+    DevBuf dstate;               // ints: [0..1] pre-filter lengths, [2..13] their bounds (order-preserving int encoding), [14..15] filtered counts, [16] scan total
+    DevBuf tab;                  // per-call tables (segments, poses, gather lists)
+    DevBuf stage, keep, scan;    // batched association: staged records, keep flags, their scan
+    std::vector<unsigned char> htab;
+    int *h_pin = nullptr;        // pinned landing place of the two read-backs
+};
+
 struct SegBuf {    // ImageSegmenter scratch (segment.hip)
     DevBuf raw, pix, owner, range, ground, keep;
     DevBuf edge;               // the cluster search's angle verdicts per pixel (seg_edge_kernel)
@@ -347,6 +369,7 @@ struct mlh_ctx {
     unsigned long long publish_seq = 0;
     mlh::DevBuf uct_buf;     // point-uncertainty scratch
     mlh::VoxBuf vox;
+    mlh::KfStore kf;         // keyframe store + local map (keyframes.hip)
     mlh::OdomSet odom;
     mlh::SegBuf seg;
     mlh::TrackSet track;
@@ -584,6 +607,8 @@ int voxel_filter_run2(mlh_ctx *ctx, const void *src0, int n0, const float bounds
 int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf, const float bounds_surf[6], float leaf_surf, const void *corner, int n_corner,
                                      const float bounds_corner[6], float leaf_corner, int stride, int intensity_off, const double *ext_poses, const double *ext_covs,
                                      int n_lidar, const double cov_meas[9], int with_ua, double trace_thr, int *n_surf_out, int *n_corner_out, bool defer = false);
+// keyframes.hip
+void keyframes_release(mlh_ctx *ctx);
 // grid.hip
 int grid_build(mlh_ctx *ctx, int kind_mask, bool recompute_bounds);
 int grid_build_grids(mlh_ctx *ctx, mlh::MapGrid **grids, int n_grids, bool recompute_bounds, int *pub_oob = nullptr, mlh::HostPublish *pub = nullptr,

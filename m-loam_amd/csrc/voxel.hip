@@ -18,6 +18,7 @@
 #include <cstdlib>
 #include "dev_math.hpp"
 #include "sort_dev.hpp"
+#include "uct_dev.hpp"
 #include <cfloat>
 
 namespace mlh {
@@ -280,74 +281,6 @@ struct UctArgs {
     const int *n_dev = nullptr;  // optional device-side record count (<= n): the launch covers n, records past *n_dev are dropped
 };
 
-// evalPointUncertainty of one record (associate_uct.hpp:196-215) as downsampleCurrentScan / cloudUCTAssociateToMap call it: the point is taken back into its
-// LiDAR's frame through that LiDAR's extrinsic (pointAssociateToMap: f64 math, f32 store), then cov = G diag(pose covariance, measurement covariance) G^T with
-// G = [ I | -[T p]x | R ]. One body for point_uncertainty_kernel and the thinning pipeline's fused aggregate (vsp_aggregate_kernel): the same operations in the same order.
-__device__ __forceinline__ void eval_point_cov(const double *ext, const double *upose, const double *upose_cov, int n_lidar, const double *meas, int with_ua,
-                                               float x, float y, float z, float inten, double (&cov)[3][3])
-{
-    int idx = int(inten);
-    idx = idx < 0 ? 0 : (idx >= n_lidar ? n_lidar - 1 : idx);
-    for (int r_ = 0; r_ < 3; ++r_) for (int c_ = 0; c_ < 3; ++c_) cov[r_][c_] = 0.0;
-    if (with_ua) {
-        const double *e = ext + idx * 7;
-        const q4 qe{e[3], e[4], e[5], e[6]};
-        const d3 te{e[0], e[1], e[2]};
-        // point_sel = pose_ext^-1 * point_ori, through pointAssociateToMap (f64 math, f32 store) -- cpp:382 / cpp:1148
-        const q4 qi{-qe.x, -qe.y, -qe.z, qe.w};
-        const d3 mt = qrot(qi, te);
-        const d3 ps = qrot(qi, d3{double(x), double(y), double(z)});
-        const float sel[3] = {float(ps.x - mt.x), float(ps.y - mt.y), float(ps.z - mt.z)};
-        const double *u = upose + idx * 7;
-        const q4 q{u[3], u[4], u[5], u[6]};
-        const d3 t{u[0], u[1], u[2]};
-        // T * [p; 1]
-        double R[9];
-        qtorot(q, R);
-        const double p[3] = {double(sel[0]), double(sel[1]), double(sel[2])};
-        double tp[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) tp[r] = R[r * 3 + 0] * p[0] + R[r * 3 + 1] * p[1] + R[r * 3 + 2] * p[2] + (r == 0 ? t.x : (r == 1 ? t.y : t.z));
-        // G = [ I | -[tp]x | R ]  (3 x 9)
-        double G[3][9];
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) { G[r][c] = (r == c) ? 1.0 : 0.0; G[r][6 + c] = R[r * 3 + c]; }
-        G[0][3] = 0.0;    G[0][4] = tp[2];  G[0][5] = -tp[1];
-        G[1][3] = -tp[2]; G[1][4] = 0.0;    G[1][5] = tp[0];
-        G[2][3] = tp[1];  G[2][4] = -tp[0]; G[2][5] = 0.0;
-        const double *Cp = upose_cov + idx * 36;
-        double GC[3][9];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < 6; ++k) s += G[r][k] * Cp[k * 6 + c];
-                GC[r][c] = s;
-            }
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < 3; ++k) s += G[r][6 + k] * meas[k * 3 + c];
-                GC[r][6 + c] = s;
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < 3; ++r)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                double s = 0.0;
-#pragma unroll
-                for (int k = 0; k < 9; ++k) s += GC[r][k] * G[c][k];
-                cov[r][c] = s;
-            }
-    }
-}
-
 __global__ __launch_bounds__(256) void point_uncertainty_kernel(UctArgs A)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -355,31 +288,26 @@ __global__ __launch_bounds__(256) void point_uncertainty_kernel(UctArgs A)
     if (A.n_dev && i >= *A.n_dev) { A.keep[i] = 0; if (A.keep2) A.keep2[i] = 0; return; }
     const float *rec = reinterpret_cast<const float *>(A.src + size_t(i) * A.stride);
     const float inten = A.intensity_off >= 0 ? *reinterpret_cast<const float *>(A.src + size_t(i) * A.stride + A.intensity_off) : 0.f;
-    double cov[3][3];
-    eval_point_cov(A.ext, A.upose, A.upose_cov, A.n_lidar, A.meas, A.with_ua, rec[0], rec[1], rec[2], inten, cov);
-    const double tr = cov[0][0] + cov[1][1] + cov[2][2];
-    const int keep = (A.with_ua && A.trace_thr > 0.0 && tr > A.trace_thr) ? 0 : 1;
-    A.keep[i] = keep;
-    if (A.keep2) A.keep2[i] = keep;       // a second copy for the in-place scan that turns the flags into output slots
-    const float c6[6] = {float(cov[0][0]), float(cov[0][1]), float(cov[0][2]), float(cov[1][1]), float(cov[1][2]), float(cov[2][2])};
+    const UctPoint u = uct_point(A.ext, A.upose, A.upose_cov, A.n_lidar, A.meas, A.with_ua, A.trace_thr, rec[0], rec[1], rec[2], inten);
+    A.keep[i] = u.keep;
+    if (A.keep2) A.keep2[i] = u.keep;       // a second copy for the in-place scan that turns the flags into output slots
     if (A.cov6) {
         float *o = A.cov6 + size_t(i) * 6;
 #pragma unroll
-        for (int k = 0; k < 6; ++k) o[k] = c6[k];
+        for (int k = 0; k < 6; ++k) o[k] = u.c6[k];
     }
-    if (A.rec_out && keep) {
+    if (A.rec_out && u.keep) {
         // point_cov = pose_global * point_ori with the new covariance (cpp:1152-1154); the other fields travel unchanged (po = pi)
         unsigned char *o = A.rec_out + size_t(i) * A.stride;
         for (int k = 0; k < A.stride / 4; ++k) reinterpret_cast<float *>(o)[k] = rec[k];
-        const d3 g = qrot(q4{A.gpose[3], A.gpose[4], A.gpose[5], A.gpose[6]}, d3{double(rec[0]), double(rec[1]), double(rec[2])});
         float *ox = reinterpret_cast<float *>(o);
-        ox[0] = float(g.x + A.gpose[0]); ox[1] = float(g.y + A.gpose[1]); ox[2] = float(g.z + A.gpose[2]);
+        uct_to_map(A.gpose, rec[0], rec[1], rec[2], ox);
         if (A.cov_off >= 0) {
             float *oc = reinterpret_cast<float *>(o + A.cov_off);
 #pragma unroll
-            for (int k = 0; k < 6; ++k) oc[k] = c6[k];
+            for (int k = 0; k < 6; ++k) oc[k] = u.c6[k];
         }
-        if (A.trace_off >= 0) *reinterpret_cast<float *>(o + A.trace_off) = float(tr);
+        if (A.trace_off >= 0) *reinterpret_cast<float *>(o + A.trace_off) = float(u.tr);
     }
 }
 

@@ -223,6 +223,8 @@ struct Params {
     double LAMBDA_THRE_CALIB = 70.0;
     // keyframes of the mapper (parameters.cpp:98-100, 268-270; values of config_realvehicle_hercules.yaml:142-144)
     float DISTANCE_KEYFRAMES = 1.0f, ORIENTATION_KEYFRAMES = 1.0f, SURROUNDING_KF_RADIUS = 50.0f;
+    // the local map's resolutions (parameters.cpp; config_realvehicle_hercules.yaml: map_sur_kf_res, map_surf_res = 2 x 0.2, map_corner_res = 0.2)
+    float MAP_SUR_KF_RES = 1.0f, MAP_SURF_RES = 0.4f, MAP_CORNER_RES = 0.2f;
 };
 inline Params &params() { static Params p; return p; }
 
@@ -1659,6 +1661,12 @@ public:
         dev_.check(mlh_map_set_pair_overlapped(dev_.ctx(), surf_map.points.data(), (int)surf_map.size(), corner_map.points.data(), (int)corner_map.size(),
                                                (int)sizeof(PointIWithCov), params().MIN_MATCH_SQ_DIS, MLH_MEM_HOST));
     }
+    // the same for maps already in HBM (KeyframeMap::surfMapDevice / cornerMapDevice: 48-byte records)
+    void setInputCloudsDevice(const void *surf_map, int n_surf, const void *corner_map, int n_corner)
+    {
+        dev_.check(mlh_map_set_pair_overlapped(dev_.ctx(), surf_map, n_surf, corner_map, n_corner, (int)sizeof(PointIWithCov), params().MIN_MATCH_SQ_DIS,
+                                               MLH_MEM_DEVICE));
+    }
     void setFeatures(const PointICovCloud &surf_cov, const PointICovCloud &corner_cov)
     {
         dev_.check(mlh_features_set(dev_.ctx(), MLH_SURF, surf_cov.points.data(), 48, (int)surf_cov.size(), 16, 20, MLH_MEM_HOST));
@@ -1814,6 +1822,80 @@ private:
     Quat q_prev_;
 };
 
+// The mapper's keyframes and local map in HBM (mlh_keyframe_save* / mlh_local_map_*): saveKeyframe (cpp:641-683), extractSurroundingKeyFrames (cpp:254-354) and
+// clearCloud (cpp:921-927) under the reference's names. The map clouds stay on the device; surfMapDevice / cornerMapDevice hand them to mlh_map_set_pair(_overlapped)
+// (48-byte PointIWithCov records, MLH_MEM_DEVICE). Shares the Device (and its stream) with the solve that reads the maps.
+class KeyframeMap {
+public:
+    KeyframeMap(Device &dev, KeyframePolicy &kf, bool with_ua_flag = false) : dev_(dev), kf_(kf)
+    {
+        const Params &P = params();
+        o_.surrounding_kf_radius = P.SURROUNDING_KF_RADIUS; o_.map_sur_kf_res = P.MAP_SUR_KF_RES;
+        o_.leaf_surf = P.MAP_SURF_RES; o_.leaf_corner = P.MAP_CORNER_RES;
+        o_.trace_threshold = P.TRACE_THRESHOLD_MAPPING; o_.with_ua = with_ua_flag ? 1 : 0;
+        for (int i = 0; i < 9; ++i) o_.cov_measurement[i] = P.COV_MEASUREMENT[i];
+        dev_.check(mlh_keyframes_reset(dev_.ctx()));
+    }
+    // pose_ext (with cov_) as the reference keeps them: used for the keyframes that enter the cache from the next extractSurroundingKeyFrames on
+    void setExtrinsics(const std::vector<Pose> &pose_ext) { pose_ext_ = pose_ext; }
+    mlh_local_map_opts &opts() { return o_; }
+    // saveKeyframe(): KeyframePolicy's test, then the context's staged feature sets (what downsampleCurrentScan left on the device) are stored; -1 when not saved
+    int saveKeyframe(const Pose &pose_wmap_curr)
+    {
+        const int idx = kf_.save(pose_wmap_curr);
+        if (idx >= 0) { int32_t key = -1; dev_.check(mlh_keyframe_save_staged(dev_.ctx(), param(pose_wmap_curr).data(), pose_wmap_curr.cov_.data(), &key)); }
+        return idx;
+    }
+    // the same with the frame's clouds from the host (laser_cloud_surf_cov / laser_cloud_corner_cov)
+    int saveKeyframe(const Pose &pose_wmap_curr, const PointICovCloud &surf_cov, const PointICovCloud &corner_cov)
+    {
+        const int idx = kf_.save(pose_wmap_curr);
+        if (idx >= 0) store(pose_wmap_curr, surf_cov, corner_cov);
+        return idx;
+    }
+    // the store only (the caller has already taken saveKeyframe's decision through the same KeyframePolicy)
+    void store(const Pose &pose_wmap_curr, const PointICovCloud &surf_cov, const PointICovCloud &corner_cov)
+    {
+        int32_t key = -1;
+        dev_.check(mlh_keyframe_save(dev_.ctx(), param(pose_wmap_curr).data(), pose_wmap_curr.cov_.data(), surf_cov.points.data(), (int)surf_cov.size(),
+                                     corner_cov.points.data(), (int)corner_cov.size(), (int)sizeof(PointIWithCov), 16, MLH_MEM_HOST, &key));
+    }
+    // extractSurroundingKeyFrames(): true when the map was rebuilt; the ids appended come back in lastIds()
+    bool extractSurroundingKeyFrames(const Pose &pose_wmap_curr)
+    {
+        if (pose_ext_.empty()) throw Error("KeyframeMap: setExtrinsics first");
+        std::vector<double> e, c;
+        for (const Pose &p : pose_ext_) { const auto a = param(p); e.insert(e.end(), a.begin(), a.end()); c.insert(c.end(), p.cov_.begin(), p.cov_.end()); }
+        int32_t rebuilt = 0, n_ids = 0;
+        ids_.assign(size_t(kf_.pose_keyframes_3d.size()) + 1, 0);
+        dev_.check(mlh_local_map_assemble(dev_.ctx(), param(pose_wmap_curr).data(), e.data(), c.data(), (int)pose_ext_.size(), &o_, &rebuilt, &n_ds_[0], &n_ds_[1],
+                                          ids_.data(), &n_ids));
+        ids_.resize(size_t(n_ids));
+        return rebuilt != 0;
+    }
+    void clearCloud() { dev_.check(mlh_local_map_clear(dev_.ctx())); }
+    // laser_cloud_{surf,corner}_from_map_cov_ds in HBM
+    const void *surfMapDevice(int32_t *n) const { return cloud(MLH_SURF, 1, n); }
+    const void *cornerMapDevice(int32_t *n) const { return cloud(MLH_CORNER, 1, n); }
+    const std::vector<int32_t> &lastIds() const { return ids_; }
+    Device &device() { return dev_; }
+    KeyframePolicy &policy() { return kf_; }
+private:
+    static std::array<double, 7> param(const Pose &p) { std::array<double, 7> a; p.toParam(a.data()); return a; }
+    const void *cloud(int kind, int filtered, int32_t *n) const
+    {
+        const void *p = nullptr;
+        dev_.check(mlh_local_map_cloud(dev_.ctx(), kind, filtered, &p, n));
+        return p;
+    }
+    Device &dev_;
+    KeyframePolicy &kf_;
+    mlh_local_map_opts o_{};
+    std::vector<Pose> pose_ext_;
+    std::vector<int32_t> ids_;
+    int32_t n_ds_[2] = {0, 0};
+};
+
 // The mapper's frame loop, pipelined, with the precondition of the overlap checked per frame instead of assumed:
 //   frame k's local map is the previous frame's, unchanged, unless frame k - 1 was saved as a keyframe (then it is rebuilt around the prior of frame k from the
 //   keyframes' clouds -- frame k - 1's own cloud at its SOLVED pose among them). So while frame k - 1 is being solved, frame k's maps can be staged beside it
@@ -1828,6 +1910,10 @@ public:
     typedef std::function<void(int, const Pose &)> OnKeyframe;      // (keyframe index, its pose): store the frame's clouds (saveKeyframe, cpp:673-683)
     PipelinedMapper(Device &dev, KeyframePolicy &kf, Assemble assemble, OnKeyframe on_keyframe, int gn_iters = 5, bool with_ua_flag = false)
         : pipe_(dev, gn_iters, with_ua_flag), kf_(kf), assemble_(std::move(assemble)), on_keyframe_(std::move(on_keyframe)) {}
+    // the local map made on the device: a saved frame's clouds go to km's store, rebuild() is clearCloud + extractSurroundingKeyFrames there, and the maps are
+    // staged by device pointer (km must live on `dev` and use the same KeyframePolicy)
+    PipelinedMapper(Device &dev, KeyframeMap &km, int gn_iters = 5, bool with_ua_flag = false)
+        : pipe_(dev, gn_iters, with_ua_flag), kf_(km.policy()), km_(&km) {}
     void setInitialMap(const PointICovCloud &surf_map, const PointICovCloud &corner_map) { surf_map_ = surf_map; corner_map_ = corner_map; }
     void setInitialPose(const Pose &pose_wmap_curr, const Pose &pose_wodom_curr) { wmap_wodom_ = poseMul(pose_wmap_curr, poseInverse(pose_wodom_curr)); }
     struct Counters { int frames = 0, overlapped = 0, waited = 0, redone = 0, keyframes = 0; } counters;
@@ -1836,9 +1922,10 @@ public:
     bool process(const PointICovCloud &surf_cov, const PointICovCloud &corner_cov, const Pose &pose_wodom_curr, Pose &pose_prev)
     {
         ++counters.frames;
+        if (km_) { s_prev_.points.swap(s_fl_.points); c_prev_.points.swap(c_fl_.points); s_fl_ = surf_cov; c_fl_ = corner_cov; }   // saveKeyframe stores a frame's own clouds
         const Pose prior = poseMul(wmap_wodom_, pose_wodom_curr);             // transformAssociateToMap with the correction known NOW (frame k - 2's while k - 1 is in flight)
         if (!in_flight_) {
-            pipe_.setInputClouds(surf_map_, corner_map_);
+            stageMaps();
             pipe_.setFeatures(surf_cov, corner_cov);
             pipe_.submit(prior);
             in_flight_ = true; prior_in_flight_ = prior; wodom_in_flight_ = pose_wodom_curr;
@@ -1847,7 +1934,7 @@ public:
         const bool predicted_keyframe = kf_.wouldSave(prior_in_flight_);
         if (!predicted_keyframe) {
             // frame k - 1 is not expected to be saved: frame k matches against the same local map -- stage it and submit frame k behind the solve in flight
-            pipe_.setInputClouds(surf_map_, corner_map_);
+            stageMaps();
             pipe_.setFeatures(surf_cov, corner_cov);
             pipe_.submitChained(wodom_in_flight_, pose_wodom_curr);
             pose_prev = pipe_.collect();                                      // frame k - 1
@@ -1859,7 +1946,7 @@ public:
                 ++counters.redone;
                 const Pose prior_k = poseMul(wmap_wodom_, pose_wodom_curr);
                 rebuild(prior_k);
-                pipe_.setInputClouds(surf_map_, corner_map_);
+                stageMaps();
                 pipe_.submit(prior_k);
                 prior_in_flight_ = prior_k;
             } else {
@@ -1873,7 +1960,7 @@ public:
             const bool saved = closeFrame(pose_prev);
             const Pose prior_k = poseMul(wmap_wodom_, pose_wodom_curr);
             if (saved) rebuild(prior_k);
-            pipe_.setInputClouds(surf_map_, corner_map_);
+            stageMaps();
             pipe_.setFeatures(surf_cov, corner_cov);
             pipe_.submit(prior_k);
             prior_in_flight_ = prior_k;
@@ -1885,24 +1972,41 @@ public:
     {
         Pose p = pipe_.collect();
         in_flight_ = false;
-        closeFrame(p);
+        closeFrame(p, true);
         return p;
     }
     const PointICovCloud &surfMap() const { return surf_map_; }
     const PointICovCloud &cornerMap() const { return corner_map_; }
 private:
     // transformUpdate + saveKeyframe for the frame whose pose just came back (cpp:1076-1079)
-    bool closeFrame(const Pose &pose_wmap_curr)
+    bool closeFrame(const Pose &pose_wmap_curr, bool in_flight_frame = false)
     {
         wmap_wodom_ = poseMul(pose_wmap_curr, poseInverse(wodom_in_flight_));
         const int idx = kf_.save(pose_wmap_curr);
         if (idx < 0) return false;
         ++counters.keyframes;
+        if (km_) km_->store(pose_wmap_curr, in_flight_frame ? s_fl_ : s_prev_, in_flight_frame ? c_fl_ : c_prev_);
         if (on_keyframe_) on_keyframe_(idx, pose_wmap_curr);
         return true;
     }
+    void stageMaps()
+    {
+        if (km_ && dev_map_) {
+            int32_t ns = 0, nc = 0;
+            const void *s = km_->surfMapDevice(&ns), *c = km_->cornerMapDevice(&nc);
+            pipe_.setInputCloudsDevice(s, ns, c, nc);
+        } else {
+            pipe_.setInputClouds(surf_map_, corner_map_);
+        }
+    }
     void rebuild(const Pose &prior)
     {
+        if (km_) {
+            km_->clearCloud();                                      // the map after a keyframe (cpp:1101), then rebuilt around the prior
+            km_->extractSurroundingKeyFrames(prior);
+            dev_map_ = true;
+            return;
+        }
         PointICovCloud s, c;
         assemble_(kf_.surrounding(prior), prior, s, c);
         surf_map_ = std::move(s); corner_map_ = std::move(c);
@@ -1911,6 +2015,9 @@ private:
     KeyframePolicy &kf_;
     Assemble assemble_;
     OnKeyframe on_keyframe_;
+    KeyframeMap *km_ = nullptr;
+    bool dev_map_ = false;
+    PointICovCloud s_fl_, c_fl_, s_prev_, c_prev_;      // (KeyframeMap path) the clouds of the frame in flight and of the one before it
     PointICovCloud surf_map_, corner_map_;
     Pose wmap_wodom_, prior_in_flight_, wodom_in_flight_;
     bool in_flight_ = false;
