@@ -531,8 +531,7 @@ typedef struct mlh_iter_stat {
  * (pose_local_parameterization.cpp:26-45). This is BASELINE.json's "GN iteration". stats may be NULL. */
 int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solver_opts *opts, mlh_iter_stat *stats);
 /* How the iterations of mlh_gn_solve / mlh_gn_solve_begin* are laid out on the device. Neither switch changes a result (same arithmetic in the same order; the
- * tests compare the variants bit for bit); they exist for A/B measurements and as the reference forms in the tests. Environment at mlh_create: MLH_GN_DEFER,
- * MLH_KNN_WARM (0 / 1).
+ * tests compare the variants bit for bit); they exist for A/B measurements and as the reference forms in the tests. This call is the only way to set them.
  *   deferred_finish 1 (default): on one GPU, without per-iteration statistics and for frame-sized launches (at most 160 fit tiles = 40 960 feature slots; larger
  *       launches keep the classic form, where the redundant sums would cost more than the serial tail they replace), every iteration but the last leaves the J^T J / J^T r records of its tiles in HBM and
  *       the NEXT iteration's correspondence launch starts by summing them, solving and applying Plus in every workgroup redundantly (the kernel boundary is the only
@@ -542,7 +541,7 @@ int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solv
  *       mlh_gn_solve_begin_chained completes it in its first correspondence launch -- sum, solve, Plus, the pose published to that solve's host record and stored as the
  *       state's pose from there, then this frame's chained start pose (lidar_mapper_keyframe.cpp:145-160) computed in the same prologue: neither the serial finish nor
  *       the chain launch stand between two frames. mlh_gn_solve_end, or any other solver call, completes a solve no successor took with a one-workgroup launch.
- *       0: the last iteration finishes and publishes in its own fit launch. Environment: MLH_GN_FINAL_DEFER.
+ *       0: the last iteration finishes and publishes in its own fit launch.
  *   knn_warm_start 1 (default): iterations >= 1 bound the 5-NN search of a feature by the distances from its new position to the five neighbours the previous
  *       iteration found (an upper bound of the fifth-neighbour distance: the search stays exact, feature_extract.hpp:666/813); 0: every iteration searches cold. */
 int mlh_set_gn_schedule(mlh_ctx *ctx, int deferred_finish, int knn_warm_start, int final_in_successor);

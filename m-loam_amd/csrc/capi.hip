@@ -414,9 +414,6 @@ int mlh_create(mlh_ctx **out, int device_id)
     if (!c) return MLH_ERR_NOMEM;
     c->device = device_id;
     if (const char *e = std::getenv("MLH_KNN_LANES")) c->knn_lanes_override = std::atoi(e);
-    if (const char *e = std::getenv("MLH_GN_DEFER")) c->gn_defer = std::atoi(e);
-    if (const char *e = std::getenv("MLH_KNN_WARM")) c->knn_warm = std::atoi(e);
-    if (const char *e = std::getenv("MLH_GN_FINAL_DEFER")) c->gn_final_defer = std::atoi(e);
     if (query_device_caps(c) != MLH_OK) { delete c; return MLH_ERR_HIP; }
     // the solver's stream: the whole device, or -- MLH_SOLVER_CU_MASK=<hex word>[,<hex word>...], bit i of word w = compute unit 32 w + i -- a part of it (a
     // deployment that keeps compute units for other work; the tests of the residency gates)
@@ -1467,16 +1464,58 @@ static MatchArgs args_from_opts(const mlh_solver_opts *o, int kind_mask, int pos
     return a;
 }
 
+// the kinds a solve covers: bit k when kind k has features staged and its map built
+static int solve_kind_mask(const mlh_ctx *ctx)
+{
+    return ((ctx->feat[0].m > 0 && ctx->map[0].built) ? 1 : 0) | ((ctx->feat[1].m > 0 && ctx->map[1].built) ? 2 : 0);
+}
+static int tiles_of(int m) { return (m + 255) / 256; }      // (the fit / linearise kernels' tile: 256 features, match.hip and track.hip)
+static int feature_tiles(const mlh_ctx *ctx, int kind_mask = 3)
+{
+    return ((kind_mask & 1) ? tiles_of(ctx->feat[0].m) : 0) + ((kind_mask & 2) ? tiles_of(ctx->feat[1].m) : 0);
+}
+// scan2MapOptimization runs only when the map has > 50 surf and > 10 corner points (lidar_mapper_keyframe.cpp:429)
+static bool scan2map_has_maps(const mlh_ctx *ctx)
+{
+    return ctx->map[MLH_SURF].built && ctx->map[MLH_CORNER].built && ctx->map[MLH_SURF].n > 50 && ctx->map[MLH_CORNER].n > 10;
+}
+
+// The profiler's events of a collected solve: the kernel that published may still be retiring, so where one of the `retiring` kernels is profiled its own stop
+// event needs the stream to drain first
+static int prof_drain(mlh_ctx *ctx, uint32_t retiring = ~0u)
+{
+    if (ctx->prof.pending.empty()) return MLH_OK;
+    if (ctx->prof.mask & retiring) MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    prof_collect(ctx);
+    return MLH_OK;
+}
+
 // The deferred finish makes EVERY workgroup of the next correspondence launch sum the fit tiles' records: cheap for a mapper frame (88 records, ~1 000
 // workgroups: +3.5 us against the 5 us the fit kernel's serial tail costs), quadratic in the launch size beyond it -- measured (profiles/r04_feature_sweep.txt):
 // even at 27-34 k features (108-133 tiles), a loss from ~100 k features on (447 tiles: +14 us), 4x the launch at 450 k. Launches with more tiles than this keep the
 // classic finish, whose one serial tail is noise next to a 100 us kernel.
 static bool gn_defer_applies(const mlh_ctx *ctx, int kind_mask)
 {
-    if (!ctx->gn_defer || distributed(ctx)) return false;
-    int tiles = 0;
-    for (int k = 0; k < 2; ++k) if (kind_mask & (1 << k)) tiles += (ctx->feat[k].m + 256 - 1) / 256;      // (the fit kernel's tile: 256 features, match.hip)
-    return tiles <= GN_DEFER_MAX_TILES;
+    return ctx->gn_defer && !distributed(ctx) && feature_tiles(ctx, kind_mask) <= GN_DEFER_MAX_TILES;
+}
+
+// The arguments of Gauss-Newton iteration `it` of `n_iters` (the start pose goes in with iteration 0's). Iterations >= 1 re-find the neighbours of the same features
+// in the same map: the previous iteration's five bound the search (not with ownership planes: a feature that changes hands between iterations would bring another
+// frame's records). `defer`: one GPU, no per-iteration statistics -- the fit launch of every iteration but the last (or every one, `leave_final`) only leaves its
+// tiles' records, and the next iteration's correspondence launch, whose every workgroup sums and solves for itself (match.hip: knn_features_kernel<.., PRE>), finishes
+// it; the start pose then goes in with iteration 1 as well (iteration 0's pose, the one iteration 1 updates).
+static MatchArgs gn_iter_args(const mlh_ctx *ctx, const mlh_solver_opts *opts, int mask, int it, int n_iters, const double *pose, bool defer, bool leave_final = false)
+{
+    MatchArgs a = args_from_opts(opts, mask, 0);
+    if (it == 0) a.init_pose = pose;
+    a.warm = it >= 1 && ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi;
+    a.finish = 1;
+    if (defer) {
+        a.gn_iter = it; a.gn_iters = n_iters;
+        if (it == 1) a.init_pose = pose;
+        if (it < n_iters - 1 || leave_final) a.finish = 0;
+    }
+    return a;
 }
 
 static int fetch_pose_and_stats(mlh_ctx *ctx, double pose[7], mlh_iter_stat *stats, int n_stats)
@@ -1508,30 +1547,19 @@ int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solv
     { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
     int rc = ensure_state(ctx, n_iters);
     if (rc) return rc;
-    const int mask = ((ctx->feat[0].m > 0 && ctx->map[0].built) ? 1 : 0) | ((ctx->feat[1].m > 0 && ctx->map[1].built) ? 2 : 0);
+    const int mask = solve_kind_mask(ctx);
     if (!mask) return fail(ctx, MLH_ERR_STATE, "no map/features staged");
     // the pose goes in with the first iteration's kernel arguments and (single GPU, no statistics wanted) comes back through
     // pinned host memory written by the last iteration's finish: 2 launches per iteration and nothing else
     unsigned long long seq = 0;
     bool fused_publish = false;
+    const bool defer = !stats && n_iters >= 2 && gn_defer_applies(ctx, mask);
     for (int it = 0; it < n_iters; ++it) {
-        MatchArgs a = args_from_opts(opts, mask, 0);
-        if (it == 0) a.init_pose = pose_inout;
-        // iterations >= 1 re-find the neighbours of the same features in the same map: the previous iteration's five bound the search (not with ownership
-        // planes: a feature that changes hands between iterations would bring another frame's records)
-        a.warm = it >= 1 && ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi;
+        MatchArgs a = gn_iter_args(ctx, opts, mask, it, n_iters, pose_inout, defer);
         if (!distributed(ctx) || ctx->p2p.active) {
             // single GPU: two launches per iteration; the fit kernel's last workgroup reduces, solves and updates the pose. Several ranks joined by the
             // mailbox communicator: the same two launches -- that workgroup exchanges the summed record with the peers (one hop) before it solves
-            a.finish = 1;
             a.stat_slot = stats ? it : -1;
-            if (!stats && n_iters >= 2 && gn_defer_applies(ctx, mask)) {
-                // one GPU, no per-iteration statistics: only the LAST iteration keeps that finish; the others leave their tiles' records to the next
-                // iteration's correspondence launch, whose every workgroup sums and solves for itself (match.hip: knn_features_kernel<.., PRE>)
-                a.gn_iter = it; a.gn_iters = n_iters;
-                if (it == 1) a.init_pose = pose_inout;       // iteration 0's pose, the one iteration 1 updates
-                if (it < n_iters - 1) a.finish = 0;
-            }
             if (it == n_iters - 1 && !stats) {
                 if ((rc = publish_slot(ctx, &a.publish, &seq))) return rc;
                 a.publish_seq = seq;
@@ -1550,11 +1578,7 @@ int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solv
     if (fused_publish) {
         HostPublish hp;
         if ((rc = wait_published(ctx, seq, hp))) return rc;
-        if (!ctx->prof.pending.empty()) {
-            // the fit kernel that published may still be retiring: its own stop event (if one was requested) needs the stream to drain
-            if (ctx->prof.mask & ((1u << MLH_K_FIT) | (1u << MLH_K_SOLVE))) MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            prof_collect(ctx);
-        }
+        if ((rc = prof_drain(ctx, (1u << MLH_K_FIT) | (1u << MLH_K_SOLVE)))) return rc;
         for (int i = 0; i < 7; ++i) pose_inout[i] = hp.x[i];
         return MLH_OK;
     }
@@ -1574,7 +1598,7 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     int rc = ensure_state(ctx, 0);
     if (rc) return rc;
-    const int mask = ((ctx->feat[0].m > 0 && ctx->map[0].built) ? 1 : 0) | ((ctx->feat[1].m > 0 && ctx->map[1].built) ? 2 : 0);
+    const int mask = solve_kind_mask(ctx);
     if (!mask) return fail(ctx, MLH_ERR_STATE, "no map/features staged");
     if (!ctx->h_solve) {
         MLH_HIP(ctx, hipHostMalloc(&ctx->h_solve, 2 * sizeof(HostPublish), hipHostMallocDefault));      // one record per solve in flight
@@ -1586,9 +1610,7 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     const bool defer = n_iters >= 2 && gn_defer_applies(ctx, mask);
     // The previous solve may have left its LAST iteration as tile records (gn_pending). A chained, deferred solve completes it in its own first launch -- unless this
     // frame needs a larger record buffer (the records would not survive the reallocation); everything else completes it now, before the chain launch reads the pose.
-    size_t tiles_now = 0;
-    for (int k = 0; k < 2; ++k) if (mask & (1 << k)) tiles_now += size_t((ctx->feat[k].m + 255) / 256);
-    const bool consume = !pose_in && defer && ctx->gn_pending.active && sizeof(double) * NE_STRIDE * tiles_now <= ctx->partials.cap;
+    const bool consume = !pose_in && defer && ctx->gn_pending.active && sizeof(double) * NE_STRIDE * size_t(feature_tiles(ctx, mask)) <= ctx->partials.cap;
     mlh_ctx::GnPending pend = ctx->gn_pending;
     if (ctx->gn_pending.active && !consume && (rc = gn_flush_pending(ctx))) return rc;
     if (!pose_in && !consume) {                    // chained: the start pose is made on the device from the pose the previous solve left there
@@ -1602,22 +1624,15 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     const int base = ctx->gn_slot_base;
     ctx->gn_slot_base ^= 2;
     for (int it = 0; it < n_iters; ++it) {
-        MatchArgs a = args_from_opts(opts, mask, 0);
-        if (it == 0) a.init_pose = pose_in;        // null when chained: the kernels read the state's pose (or compute it: `consume`)
-        a.finish = 1;
-        a.stat_slot = -1;
-        a.warm = it >= 1 && ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi;
-        if (defer) {     // the finish moves into the next iteration's correspondence launch (see mlh_gn_solve)
-            a.gn_iter = it; a.gn_iters = n_iters; a.gn_slot_base = base;
-            if (it == 1) a.init_pose = pose_in;
-            if (it < n_iters - 1 || leave_final) a.finish = 0;
-            if (consume) {
-                a.pre_final = true;                // iteration 0: complete the predecessor, publish its pose, chain; iterations >= 1: pose 0 sits in its slot
-                if (it == 0) {
-                    a.pre_final_tiles = pend.tiles; a.pre_final_slot = pend.slot; a.pre_final_thre = pend.thre; a.pre_final_freeze = pend.freeze;
-                    a.pre_final_publish = static_cast<HostPublish *>(pend.rec); a.pre_final_seq = pend.seq;
-                    a.chain_prev = wodom_prev; a.chain_cur = wodom_cur;
-                }
+        // (pose_in is null when chained: the kernels read the state's pose, or compute it: `consume`)
+        MatchArgs a = gn_iter_args(ctx, opts, mask, it, n_iters, pose_in, defer, leave_final);
+        if (defer) a.gn_slot_base = base;
+        if (consume) {
+            a.pre_final = true;                // iteration 0: complete the predecessor, publish its pose, chain; iterations >= 1: pose 0 sits in its slot
+            if (it == 0) {
+                a.pre_final_tiles = pend.tiles; a.pre_final_slot = pend.slot; a.pre_final_thre = pend.thre; a.pre_final_freeze = pend.freeze;
+                a.pre_final_publish = static_cast<HostPublish *>(pend.rec); a.pre_final_seq = pend.seq;
+                a.chain_prev = wodom_prev; a.chain_cur = wodom_cur;
             }
         }
         if (it == n_iters - 1 && !leave_final) {
@@ -1670,10 +1685,7 @@ int mlh_gn_solve_end(mlh_ctx *ctx, double pose_out[7])
     ctx->solve_collected = seq;
     ctx->solve_pending = ctx->solve_seq != ctx->solve_collected;
     if (rc) return rc;
-    if (!ctx->prof.pending.empty() && !ctx->solve_pending) {
-        if (ctx->prof.mask & ((1u << MLH_K_FIT) | (1u << MLH_K_SOLVE))) MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        prof_collect(ctx);
-    }
+    if (!ctx->solve_pending && (rc = prof_drain(ctx, (1u << MLH_K_FIT) | (1u << MLH_K_SOLVE)))) return rc;
     for (int i = 0; i < 7; ++i) pose_out[i] = hp.x[i];
     return MLH_OK;
 }
@@ -1689,7 +1701,7 @@ int mlh_gn_solve_blocks(mlh_ctx *ctx, double *poses_inout, int n_iters, const ml
     if (rc) return rc;
     if ((rc = upload_pose(ctx, poses_inout))) return rc;
     for (int b = 1; b < nb; ++b) if ((rc = upload_block_pose(ctx, b, poses_inout + 7 * b))) return rc;
-    const int mask = ((ctx->feat[0].m > 0 && ctx->map[0].built) ? 1 : 0) | ((ctx->feat[1].m > 0 && ctx->map[1].built) ? 2 : 0);
+    const int mask = solve_kind_mask(ctx);
     if (!mask) return fail(ctx, MLH_ERR_STATE, "no map/features staged");
     // The finish in the consumer, per pose block (one GPU, no statistics): a correspondence workgroup serves features of ONE block, so its prologue sums that block's
     // records only and solves that block only -- the four serial finishes of the classic last workgroup (20 us of a 40 us fit launch on config 4's frame) become one
@@ -1737,22 +1749,10 @@ int mlh_gn_solve_blocks(mlh_ctx *ctx, double *poses_inout, int n_iters, const ml
 // The host-polled form: chunks of LM launches with the loop's verdict read between them (statistics, good-feature selections, RCCL ranks, and the re-solve of a frame
 // whose loop outgrew its look-ahead).
 // The Levenberg-Marquardt launches of scan2map in the consumer-side form (match.hip: lm_consume_kernel) -- the default where it applies (one GPU, every feature
-// used, no statistics asked for); MLH_LM_CONSUMER=0 keeps the classic launches (read at every call: an A/B can flip it between two frames of one process).
-// ... and the whole LM loop of an outer iteration as ONE launch whose workgroups synchronise among themselves (match.hip: lm_loop_kernel); MLH_LM_LOOP=0 keeps
-// one launch per LM iteration (read at every call, as above)
-static bool lm_loop_enabled()
-{
-    const char *e = std::getenv("MLH_LM_LOOP");
-    return !(e && std::atoi(e) == 0);
-}
-static int feature_tiles(const mlh_ctx *ctx)
-{
-    int tiles = 0;
-    for (int k = 0; k < 2; ++k) tiles += (ctx->feat[k].m + 256 - 1) / 256;      // (the fit / linearise kernels' tile: 256 features, match.hip)
-    return tiles;
-}
-// ... where every tile's workgroup can be resident at once on what this context's stream may use of the device (mlh_ctx::caps, asked at mlh_create)
-static bool lm_loop_applies(const mlh_ctx *ctx, int which, int tiles) { return lm_loop_enabled() && loop_tiles_ok(ctx, which, tiles); }
+// used, no statistics asked for) -- and the whole LM loop of an outer iteration as ONE launch whose workgroups synchronise among themselves (match.hip:
+// lm_loop_kernel); Schedule::LM_CONSUMER and Schedule::LM_LOOP (ctx.hpp) keep the classic launches / one launch per LM iteration.
+// ... the latter where every tile's workgroup can be resident at once on what this context's stream may use of the device (mlh_ctx::caps, asked at mlh_create)
+static bool lm_loop_applies(const mlh_ctx *ctx, int which, int tiles) { return schedule_on(Schedule::LM_LOOP) && loop_tiles_ok(ctx, which, tiles); }
 // The barrier of a one-launch loop was given up on (`done` bit 2 of its publication): the gate comes down, and the caller solves the frame again through the
 // launch-per-iteration form -- same arithmetic, same pose bits, no residency requirement
 static void note_loop_timeout(mlh_ctx *ctx, int which, int tiles, bool solved_again)
@@ -1761,27 +1761,24 @@ static void note_loop_timeout(mlh_ctx *ctx, int which, int tiles, bool solved_ag
     if (solved_again) ++ctx->caps.loop_fallbacks;
 }
 
-// MLH_S2M_WARM=0: every outer iteration searches unbounded (A/B)
-static bool s2m_warm_applies(const mlh_ctx *ctx)
+// The pose a one-launch loop published to rec / seq (rec null: the context's record 0), into pose_out. *given_up: the loop's barrier was given up on (`done` bit 2)
+// -- pose_out is left as it was, and the caller solves the frame again through the launch-per-iteration form (note_loop_timeout)
+static int collect_loop_pose(mlh_ctx *ctx, unsigned long long seq, HostPublish *rec, double pose_out[7], bool *given_up)
 {
-    const char *e = std::getenv("MLH_S2M_WARM");
-    if (e && std::atoi(e) == 0) return false;
-    return ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi && ctx->own_mod <= 1;
+    HostPublish hp;
+    int rc = wait_published(ctx, seq, hp, rec);
+    if (rc) return rc;
+    *given_up = (hp.done & 4) != 0;
+    if (*given_up) return MLH_OK;
+    if ((rc = prof_drain(ctx))) return rc;
+    for (int i = 0; i < 7; ++i) pose_out[i] = hp.x[i];
+    return MLH_OK;
 }
 
-static bool lm_consumer_switch()
-{
-    const char *e = std::getenv("MLH_LM_CONSUMER");
-    return !(e && std::atoi(e) == 0);
-}
-static bool lm_consumer_enabled(const mlh_ctx *ctx)
-{
-    if (!lm_consumer_switch()) return false;
-    // every workgroup sums every tile's record: the same size limit as the Gauss-Newton path's deferred finish (GN_DEFER_MAX_TILES)
-    int tiles = 0;
-    for (int k = 0; k < 2; ++k) tiles += (ctx->feat[k].m + 256 - 1) / 256;
-    return tiles <= GN_DEFER_MAX_TILES;
-}
+static bool s2m_warm_applies(const mlh_ctx *ctx) { return ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi && ctx->own_mod <= 1; }
+
+// every workgroup sums every tile's record: the same size limit as the Gauss-Newton path's deferred finish (GN_DEFER_MAX_TILES)
+static bool lm_consumer_enabled(const mlh_ctx *ctx) { return schedule_on(Schedule::LM_CONSUMER) && feature_tiles(ctx) <= GN_DEFER_MAX_TILES; }
 
 // scan2MapOptimization matches through ActiveFeatureSelection::goodFeatureMatching, which passes n_neigh = 5 and CHECK_FOV = false to match*PointFromMap whatever
 // the caller's configuration says (lidar_mapper.h:256-283, every gf_method): MLH_FLAG_CHECK_FOV does not apply to the scan2map entry points. (The flag is for
@@ -1794,6 +1791,54 @@ static mlh_solver_opts scan2map_opts(const mlh_solver_opts *o)
     return c;
 }
 
+// One outer iteration of scan2map in the one-launch-loop form: the match launch (its fit rides in the loop launch where loop_fit_fusable says so), then the launch
+// that runs the iteration's whole LM loop on the device. The start pose goes in with outer iteration 0; the last one publishes pose and verdict to rec / seq.
+// m_dev: the feature counts on the device (mlh_downsample_scan2map), or null.
+static int enqueue_s2m_loop_outer(mlh_ctx *ctx, const mlh_solver_opts *opts, int outer, const double *pose, const int *m_dev, HostPublish *rec, unsigned long long seq)
+{
+    MatchArgs a = args_from_opts(opts, 3, 0);
+    a.finish = 0; a.lm_max_it = opts->max_lm_iterations; a.m_dev = m_dev;
+    if (outer == 0) a.init_pose = pose;
+    a.warm = outer >= 1 && s2m_warm_applies(ctx);
+    a.no_fit = loop_fit_fusable(a);
+    int rc = match_launch(ctx, a);
+    if (rc) return rc;
+    MatchArgs b = args_from_opts(opts, 3, 1);
+    b.finish = 0; b.lmc = 3; b.lmc_j = 1; b.lm_max_it = opts->max_lm_iterations; b.m_dev = m_dev; b.fit_in_loop = a.no_fit;
+    b.lm_expect_done = outer == 0 ? -1 : 1;
+    if (outer == 0) b.init_pose = pose;
+    if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
+    return lm_consume_launch(ctx, b);
+}
+
+// The match launch of an outer iteration in the forms with a launch per LM iteration: its finish runs the LM begin, or (lmc) it only leaves its tiles' records to
+// the first consumer launch. Outer iterations behind the first search the same map for the same features from a pose a few centimetres away: bounded by the
+// neighbours the previous one left (knn_feature_warm: still the exact 5-NN). `unpolled` (scan2map_submit): the host has not read the previous LM loop's verdict --
+// the device raises lm_overflow if that loop has not terminated.
+static MatchArgs s2m_begin_args(const mlh_ctx *ctx, const mlh_solver_opts *opts, bool lmc, int outer, const double *pose, bool unpolled)
+{
+    MatchArgs a = args_from_opts(opts, 3, 0);
+    a.finish = lmc ? 0 : 3; a.lm_max_it = opts->max_lm_iterations;
+    if (outer == 0) { a.init_pose = pose; a.lm_expect_done = -1; }
+    else if (unpolled) a.lm_expect_done = 1;
+    a.warm = outer >= 1 && s2m_warm_applies(ctx);
+    return a;
+}
+
+// The j-th (from 0) LM launch behind that match launch: the consumer-side form (lmc: sums its predecessor's records, runs the LM begin (j = 0) or step, evaluates at
+// the candidate) or the classic one (finish 4: the linearise kernel's last workgroup runs the step). `unpolled` as above.
+static MatchArgs s2m_lm_args(const mlh_solver_opts *opts, bool lmc, int outer, int j, const double *pose, bool unpolled)
+{
+    MatchArgs a = args_from_opts(opts, 3, 1);
+    a.finish = 4; a.lm_max_it = opts->max_lm_iterations;
+    if (lmc) {
+        a.finish = 0; a.lmc = j == 0 ? 1 : 2; a.lmc_j = j + 1;
+        if (j == 0 && outer == 0) { a.init_pose = pose; a.lm_expect_done = -1; }
+        else if (j == 0 && unpolled) a.lm_expect_done = 1;
+    }
+    return a;
+}
+
 static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts_in, mlh_iter_stat *stats, bool allow_loop = true)
 {
     if (!ctx || !pose_inout || !opts_in || opts_in->max_outer <= 0) return MLH_ERR_INVALID;
@@ -1802,8 +1847,7 @@ static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_
     { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
     int rc = ensure_state(ctx, opts->max_outer);
     if (rc) return rc;
-    // scan2MapOptimization runs only when the map has > 50 surf and > 10 corner points (lidar_mapper_keyframe.cpp:429)
-    if (!(ctx->map[MLH_SURF].built && ctx->map[MLH_CORNER].built && ctx->map[MLH_SURF].n > 50 && ctx->map[MLH_CORNER].n > 10)) {
+    if (!scan2map_has_maps(ctx)) {
         if (stats) std::memset(stats, 0, sizeof(mlh_iter_stat) * size_t(opts->max_outer));
         return MLH_OK;
     }
@@ -1824,30 +1868,16 @@ static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_
         HostPublish *rec = nullptr;
         unsigned long long seq = 0;
         if ((rc = publish_slot(ctx, &rec, &seq, 0))) return rc;
-        for (int outer = 0; outer < opts->max_outer; ++outer) {
-            MatchArgs a = args_from_opts(opts, 3, 0);
-            a.finish = 0; a.lm_max_it = opts->max_lm_iterations;
-            if (outer == 0) a.init_pose = pose_inout;
-            a.warm = outer >= 1 && s2m_warm_applies(ctx);
-            a.no_fit = loop_fit_fusable(a);                 // (the fit rides in the loop launch below)
-            if ((rc = match_launch(ctx, a))) return rc;
-            MatchArgs b = args_from_opts(opts, 3, 1);
-            b.finish = 0; b.lmc = 3; b.lmc_j = 1; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 0; b.fit_in_loop = a.no_fit;
-            b.lm_expect_done = outer == 0 ? -1 : 1;
-            if (outer == 0) b.init_pose = pose_inout;
-            if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
-            if ((rc = lm_consume_launch(ctx, b))) return rc;
-        }
-        HostPublish hp;
-        if ((rc = wait_published(ctx, seq, hp, rec))) return rc;
-        if (hp.done & 4) {
+        for (int outer = 0; outer < opts->max_outer; ++outer)
+            if ((rc = enqueue_s2m_loop_outer(ctx, opts, outer, pose_inout, nullptr, rec, seq))) return rc;
+        bool given_up = false;
+        if ((rc = collect_loop_pose(ctx, seq, rec, pose_inout, &given_up))) return rc;
+        if (given_up) {
             // the loop's workgroups did not all arrive at a barrier (not all resident at once beside whatever else runs here): the frame again, from the start
             // pose the caller still holds, through the launch-per-iteration form
             note_loop_timeout(ctx, 0, loop_tiles, true);
             return scan2map_polled(ctx, pose_inout, opts, stats, false);
         }
-        if (!ctx->prof.pending.empty()) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); prof_collect(ctx); }
-        for (int i = 0; i < 7; ++i) pose_inout[i] = hp.x[i];
         return MLH_OK;
     }
     if (!fused && (rc = upload_pose(ctx, pose_inout))) return rc;
@@ -1862,12 +1892,8 @@ static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_
     std::mt19937 rng((uint32_t)opts->gf_seed);
     for (int outer = 0; outer < opts->max_outer; ++outer) {
         if (fused) {
-            MatchArgs a = args_from_opts(opts, 3, 0);
-            a.finish = lmc ? 0 : 3; a.stat_slot = stats ? outer : -1; a.lm_max_it = opts->max_lm_iterations; a.lm_min_blocks = 0;
-            if (outer == 0) { a.init_pose = pose_inout; a.lm_expect_done = -1; }
-            // outer iterations behind the first search the same map for the same features from a pose a few centimetres away: bounded by the neighbours the
-            // previous outer iteration left (knn_feature_warm: still the exact 5-NN)
-            a.warm = outer >= 1 && s2m_warm_applies(ctx);
+            MatchArgs a = s2m_begin_args(ctx, opts, lmc, outer, pose_inout, false);
+            a.stat_slot = stats ? outer : -1;
             if ((rc = match_launch(ctx, a))) return rc;
         } else if (opts->gf_method == MLH_GF_WO) {
             if ((rc = match_launch(ctx, args_from_opts(opts, 3, 0)))) return rc;
@@ -1913,12 +1939,7 @@ static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_
             const int lm_cap = opts->max_lm_iterations + (lmc ? 1 : 0);     // launches after which the loop has terminated by itself
             auto enqueue_chunk = [&](int count) -> int {
                 for (int j = 0; j < count; ++j) {
-                    MatchArgs a = args_from_opts(opts, 3, 1);
-                    a.finish = 4; a.lm_max_it = opts->max_lm_iterations;
-                    if (lmc) {
-                        a.finish = 0; a.lmc = lm_j == 0 ? 1 : 2; a.lmc_j = ++lm_j; a.lm_min_blocks = 0;
-                        if (a.lmc == 1 && outer == 0) { a.init_pose = pose_inout; a.lm_expect_done = -1; }
-                    }
+                    MatchArgs a = s2m_lm_args(opts, lmc, outer, lm_j++, pose_inout, false);
                     if (j == count - 1) {                   // the chunk's last launch publishes (no publication launch)
                         unsigned long long seq = 0;
                         int prc = publish_slot(ctx, &a.publish, &seq, lm_chunk_idx);
@@ -1957,18 +1978,16 @@ static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_
         if (stats && (rc = lm_finish_launch(ctx, outer))) return rc;     // fills the record's LM summary
     }
     if (gf_loop_rec) {
-        HostPublish hp;
-        if ((rc = wait_published(ctx, gf_loop_seq, hp, gf_loop_rec))) return rc;
-        if (hp.done & 4) {               // as above (the selection's draws start from opts->gf_seed again: the same frame)
+        bool given_up = false;
+        if ((rc = collect_loop_pose(ctx, gf_loop_seq, gf_loop_rec, pose_inout, &given_up))) return rc;
+        if (given_up) {                  // as above (the selection's draws start from opts->gf_seed again: the same frame)
             note_loop_timeout(ctx, 0, loop_tiles, true);
             return scan2map_polled(ctx, pose_inout, opts, stats, false);
         }
-        if (!ctx->prof.pending.empty()) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); prof_collect(ctx); }
-        for (int i = 0; i < 7; ++i) pose_inout[i] = hp.x[i];
         return MLH_OK;
     }
     if (fused_lm && !stats && have_hp) {
-        if (!ctx->prof.pending.empty()) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); prof_collect(ctx); }
+        if ((rc = prof_drain(ctx))) return rc;
         for (int i = 0; i < 7; ++i) pose_inout[i] = last_hp.x[i];
         return MLH_OK;
     }
@@ -2001,7 +2020,7 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     mlh_ctx::SolveSlot &slot = ctx->solve_slot[seq & 1];
     // everything that can refuse the frame is checked BEFORE the chain launch below rewrites the device pose: a refused mlh_scan2map_begin_chained leaves the
     // state as it found it, so the caller's retry does not apply transformUpdate / transformAssociateToMap twice
-    const bool have_maps = ctx->map[MLH_SURF].built && ctx->map[MLH_CORNER].built && ctx->map[MLH_SURF].n > 50 && ctx->map[MLH_CORNER].n > 10;
+    const bool have_maps = scan2map_has_maps(ctx);
     if (have_maps && (ctx->feat[0].m <= 0 || ctx->feat[1].m <= 0)) return fail(ctx, MLH_ERR_STATE, "features_set is required for both kinds");
     slot.kind = 1; slot.chained = pose_in == nullptr; slot.opts = *opts; slot.epoch = ctx->stage_epoch; slot.tainted = false;
     if (pose_in) for (int i = 0; i < 7; ++i) slot.start[i] = pose_in[i];
@@ -2011,7 +2030,7 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
         MLH_LAUNCH(chain_pose_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->state.as<SolverState>(), pa, pb, rec);
         MLH_HIP(ctx, hipGetLastError());
     }
-    // scan2MapOptimization runs only when the map has > 50 surf and > 10 corner points (lidar_mapper_keyframe.cpp:429): otherwise the start pose is the result
+    // scan2MapOptimization runs only where scan2map_has_maps: otherwise the start pose is the result
     if (!have_maps) {
         slot.kind = 2;
         if (!pose_in) {          // chained: the start pose exists on the device only
@@ -2027,35 +2046,13 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     // ... or one launch per LM loop, which ends on the device when the loop does: no budget, nothing to overflow (an explicit lm_lookahead keeps the launches it counts)
     const bool loop = lmc && lm_lookahead <= 0 && lm_loop_applies(ctx, 0, feature_tiles(ctx));
     slot.loop_tiles = loop ? feature_tiles(ctx) : 0;
-    for (int outer = 0; loop && outer < opts->max_outer; ++outer) {
-        MatchArgs a = args_from_opts(opts, 3, 0);
-        a.finish = 0; a.lm_max_it = opts->max_lm_iterations;
-        if (outer == 0) a.init_pose = pose_in;
-        a.warm = outer >= 1 && s2m_warm_applies(ctx);
-        a.no_fit = loop_fit_fusable(a);
-        if ((rc = match_launch(ctx, a))) return rc;
-        MatchArgs b = args_from_opts(opts, 3, 1);
-        b.finish = 0; b.lmc = 3; b.lmc_j = 1; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 0; b.fit_in_loop = a.no_fit;
-        b.lm_expect_done = outer == 0 ? -1 : 1;
-        if (outer == 0) b.init_pose = pose_in;
-        if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
-        if ((rc = lm_consume_launch(ctx, b))) return rc;
-    }
+    for (int outer = 0; loop && outer < opts->max_outer; ++outer)
+        if ((rc = enqueue_s2m_loop_outer(ctx, opts, outer, pose_in, nullptr, rec, seq))) return rc;
     for (int outer = 0; !loop && outer < opts->max_outer; ++outer) {
-        MatchArgs a = args_from_opts(opts, 3, 0);
-        a.finish = lmc ? 0 : 3; a.stat_slot = -1; a.lm_max_it = opts->max_lm_iterations; a.lm_min_blocks = 0;
-        a.lm_expect_done = outer == 0 ? -1 : 1;
-        if (outer == 0) a.init_pose = pose_in;
-        a.warm = outer >= 1 && s2m_warm_applies(ctx);
-        if ((rc = match_launch(ctx, a))) return rc;
+        if ((rc = match_launch(ctx, s2m_begin_args(ctx, opts, lmc, outer, pose_in, true)))) return rc;
         const int n_launch = budget + (lmc ? 1 : 0);
         for (int j = 0; j < n_launch; ++j) {
-            MatchArgs b = args_from_opts(opts, 3, 1);
-            b.finish = 4; b.lm_max_it = opts->max_lm_iterations;
-            if (lmc) {
-                b.finish = 0; b.lmc = j == 0 ? 1 : 2; b.lmc_j = j + 1; b.lm_min_blocks = 0;
-                if (j == 0) { b.lm_expect_done = outer == 0 ? -1 : 1; if (outer == 0) b.init_pose = pose_in; }
-            }
+            MatchArgs b = s2m_lm_args(opts, lmc, outer, j, pose_in, true);
             if (outer == opts->max_outer - 1 && j == n_launch - 1) { b.publish = rec; b.publish_seq = seq; }
             if ((rc = lmc ? lm_consume_launch(ctx, b) : linearize_launch(ctx, b))) return rc;
         }
@@ -2100,7 +2097,7 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
     // a younger solve chained behind THIS one began from whatever pose this one left on the device: if this one did not produce a result, neither did that one
     auto taint_successor = [&]() { if (ctx->solve_pending && ctx->solve_slot[(seq + 1) & 1].chained) ctx->solve_slot[(seq + 1) & 1].tainted = true; };
     if (rc) { taint_successor(); return rc; }
-    if (!ctx->prof.pending.empty() && !ctx->solve_pending) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); prof_collect(ctx); }
+    if (!ctx->solve_pending && (rc = prof_drain(ctx))) return rc;
     const bool barrier_given_up = slot.kind == 1 && (hp.done & 4);       // (a one-launch LM loop whose workgroups were not all resident: lm_loop_kernel)
     if (barrier_given_up) demote_loop_gate(ctx, 0, slot.loop_tiles);
     if (slot.kind == 1 && !barrier_given_up) {
@@ -2140,28 +2137,10 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
     return fail(ctx, MLH_ERR_INCOMPLETE, "mlh_scan2map_end: the frame did not finish inside its look-ahead and cannot be solved again here (status 1); status_out is NULL");
 }
 
-// The synchronous call: the polled form. MLH_S2M_LOOKAHEAD=1 (A/B runs) makes it the split submission collected at once where nothing stands against that -- no
-// statistics, every feature used (wo_gf), no RCCL communicator, no solve in flight: the whole frame (per outer iteration the match launch + the look-ahead budget of
-// LM launches) enqueued without the host reading the loop's verdict in between, a frame that outgrows the budget solved again by the polled form (status 2); the
-// same poses, bit for bit. Measured in one gpurun call, two alternations (profiles/r05_knockout_experiments.txt): 0.2436 / 0.2435 ms per frame against the polled
-// form's 0.2421 / 0.2422 -- the polls were already hidden behind the chunk enqueued ahead, and the launches that find `done` cost what the polls did. Not the default.
-// (Measured on round 4's launches. Since the LM loop of an outer iteration is ONE launch that ends on the device -- scan2map_polled's first branch -- the default
-// synchronous call enqueues the whole frame at once anyway and there is no budget left to look ahead of; the switch remains for the launches-per-iteration forms.)
+// The synchronous call: the polled form (where the LM loop of an outer iteration is one launch, its first branch enqueues the whole frame at once)
 int mlh_scan2map(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts, mlh_iter_stat *stats)
 {
-    if (!ctx || !pose_inout || !opts || opts->max_outer <= 0) return MLH_ERR_INVALID;
-    static const bool lookahead = std::getenv("MLH_S2M_LOOKAHEAD") && std::atoi(std::getenv("MLH_S2M_LOOKAHEAD")) != 0;
-    const bool eligible = lookahead && !stats && opts->gf_method == MLH_GF_WO && !ctx->comm && ctx->solve_seq == ctx->solve_collected;
-    if (!eligible) return scan2map_polled(ctx, pose_inout, opts, stats);
-    int rc = scan2map_submit(ctx, pose_inout, nullptr, nullptr, opts, 0);
-    if (rc) return rc;
-    double out[7];
-    int32_t status = 0;
-    rc = mlh_scan2map_end(ctx, out, &status);
-    if (rc) return rc;
-    if (status == 1 || status == 3) return fail(ctx, MLH_ERR_STATE, "mlh_scan2map: the frame could not be completed (internal: look-ahead overflow without a re-solve)");
-    for (int i = 0; i < 7; ++i) pose_inout[i] = out[i];
-    return MLH_OK;
+    return scan2map_polled(ctx, pose_inout, opts, stats);
 }
 
 // downsampleCurrentScan + scan2MapOptimization with no host read between them (include/mloam_hip.h)
@@ -2182,12 +2161,10 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     const bool fused_pair = mem == MLH_MEM_DEVICE && !ctx->fused_dirty && stride_bytes == 16 && intensity_offset_bytes == 12 && n_surf > 0 && n_corner > 0 &&
                             surf_points == ctx->fused[MLH_SURF].p && n_surf == ctx->fused_n[MLH_SURF] &&
                             corner_points == ctx->fused[MLH_CORNER].p && n_corner == ctx->fused_n[MLH_CORNER];
-    const bool have_maps = ctx->map[MLH_SURF].built && ctx->map[MLH_CORNER].built && ctx->map[MLH_SURF].n > 50 && ctx->map[MLH_CORNER].n > 10;
     // the loop kernel's barrier wants every tile's workgroup resident: the BOUND's tiles, since the real count is not known here
-    const int bound_tiles = (n_surf + 255) / 256 + (n_corner + 255) / 256;
-    static const bool off = std::getenv("MLH_FUSED_THIN_SOLVE") && std::atoi(std::getenv("MLH_FUSED_THIN_SOLVE")) == 0;      // (A/B: always the two calls)
-    if (off || !fused_pair || !have_maps || distributed(ctx) || ctx->comm || opts->gf_method != MLH_GF_WO || !lm_consumer_switch() || !lm_loop_applies(ctx, 1, bound_tiles) ||
-        ctx->solve_seq != ctx->solve_collected || ctx->vox_member_order != 1)
+    const int bound_tiles = tiles_of(n_surf) + tiles_of(n_corner);
+    if (!fused_pair || !scan2map_has_maps(ctx) || distributed(ctx) || ctx->comm || opts->gf_method != MLH_GF_WO || !schedule_on(Schedule::LM_CONSUMER) ||
+        !lm_loop_applies(ctx, 1, bound_tiles) || ctx->solve_seq != ctx->solve_collected || ctx->vox_member_order != 1)
         return two_calls();
     { const int frc = gn_flush_pending(ctx); if (frc) return frc; }
     int rc = ensure_state(ctx, 0);
@@ -2218,22 +2195,10 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     HostPublish *rec = nullptr;
     unsigned long long seq = 0;
     if ((rc = publish_slot(ctx, &rec, &seq, 0))) return rc;
-    for (int outer = 0; outer < opts->max_outer && !rc; ++outer) {
-        MatchArgs a = args_from_opts(opts, 3, 0);
-        a.finish = 0; a.lm_max_it = opts->max_lm_iterations; a.m_dev = ctx->thin_counts_dev;
-        if (outer == 0) a.init_pose = pose_inout;
-        a.warm = outer >= 1 && s2m_warm_applies(ctx);
-        a.no_fit = loop_fit_fusable(a);
-        if ((rc = match_launch(ctx, a))) break;
-        MatchArgs b = args_from_opts(opts, 3, 1);
-        b.finish = 0; b.lmc = 3; b.lmc_j = 1; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 0; b.m_dev = ctx->thin_counts_dev; b.fit_in_loop = a.no_fit;
-        b.lm_expect_done = outer == 0 ? -1 : 1;
-        if (outer == 0) b.init_pose = pose_inout;
-        if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
-        rc = lm_consume_launch(ctx, b);
-    }
-    HostPublish hp;
-    if (!rc) rc = wait_published(ctx, seq, hp, rec);
+    for (int outer = 0; outer < opts->max_outer && !rc; ++outer) rc = enqueue_s2m_loop_outer(ctx, opts, outer, pose_inout, ctx->thin_counts_dev, rec, seq);
+    double pose[7];
+    bool given_up = false;
+    if (!rc) rc = collect_loop_pose(ctx, seq, rec, pose, &given_up);
     // the counts were published by the thinning's last launch, long before the pose: no wait here in practice
     int real[2] = {0, 0};
     if (!rc) {
@@ -2246,14 +2211,13 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     *n_surf_features = real[0]; *n_corner_features = real[1];
     if ((rc = device_error_check(ctx))) return rc;
     if (real[0] <= 0 || real[1] <= 0) return fail(ctx, MLH_ERR_STATE, "features_set is required for both kinds");      // (what mlh_scan2map says of an empty kind)
-    if (hp.done & 4) {
+    if (given_up) {
         // the loop's workgroups (sized for the un-thinned clouds) did not all arrive at a barrier: the thinned sets are staged and counted by now -- the solve again,
         // as the second of the two calls, through the launch-per-iteration form
         note_loop_timeout(ctx, 1, bound_tiles, true);
         return scan2map_polled(ctx, pose_inout, opts, nullptr, false);
     }
-    if (!ctx->prof.pending.empty()) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); prof_collect(ctx); }
-    for (int i = 0; i < 7; ++i) pose_inout[i] = hp.x[i];
+    for (int i = 0; i < 7; ++i) pose_inout[i] = pose[i];
     return MLH_OK;
 }
 
@@ -2596,36 +2560,13 @@ static int track_cloud_impl(mlh_ctx *ctx, double pose_inout[7], const mlh_track_
     // pinned host memory: 2 + max_lm_iterations launches per round and nothing else. With records: the state is uploaded and read back.
     const bool lean = stats == nullptr;
     if (!lean && (rc = upload_pose(ctx, pose_inout))) return rc;
-    unsigned long long seq = 0;
     // lean, one GPU, a frame's worth of features: a round is TWO launches -- the match and one launch that runs the round's LM loop to its end on the device
-    // (track.hip: track_lm_loop_kernel); MLH_TRACK_LOOP=0 keeps 2 + max_lm_iterations launches per round (A/B; read at every call)
-    {
-        const char *e = std::getenv("MLH_TRACK_LOOP");
-        const int tiles = (T.m[0] + 255) / 256 + (T.m[1] + 255) / 256;
-        if (lean && allow_loop && !(e && std::atoi(e) == 0) && !distributed(ctx) && loop_tiles_ok(ctx, 2, tiles)) {
-            HostPublish *rec = nullptr;
-            if ((rc = publish_slot(ctx, &rec, &seq))) return rc;
-            for (int outer = 0; outer < opts->max_outer; ++outer) {
-                TrackArgs m = track_args(opts, 0);
-                if (outer == 0) m.init_pose = pose_inout;
-                if ((rc = track_match_launch(ctx, 3, m))) return rc;
-                TrackArgs b = track_args(opts, 0);
-                b.finish = 0; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 10; b.stat_slot = -1;
-                if (outer == 0) b.init_pose = pose_inout;
-                if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
-                if ((rc = track_lm_loop_launch(ctx, 3, b))) return rc;
-            }
-            HostPublish hp;
-            if ((rc = wait_published(ctx, seq, hp))) return rc;
-            if (hp.done & 4) {           // a barrier given up on: the rounds again, from the pose the caller still holds, a launch per LM iteration
-                note_loop_timeout(ctx, 2, tiles, true);
-                return track_cloud_impl(ctx, pose_inout, opts, stats, false);
-            }
-            if (!ctx->prof.pending.empty()) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); prof_collect(ctx); }
-            for (int i = 0; i < 7; ++i) pose_inout[i] = hp.x[i];
-            return MLH_OK;
-        }
-    }
+    // (track.hip: track_lm_loop_kernel; Schedule::TRACK_LOOP, ctx.hpp, keeps 2 + max_lm_iterations launches per round)
+    const int tiles = tiles_of(T.m[0]) + tiles_of(T.m[1]);
+    const bool loop = lean && allow_loop && schedule_on(Schedule::TRACK_LOOP) && !distributed(ctx) && loop_tiles_ok(ctx, 2, tiles);
+    HostPublish *rec = nullptr;
+    unsigned long long seq = 0;
+    if (loop && (rc = publish_slot(ctx, &rec, &seq))) return rc;
     for (int outer = 0; outer < opts->max_outer; ++outer) {
         // lidar_tracker.cpp:42-121: match at the current estimate, then Ceres on the fixed correspondences (Huber 0.1, <= 4 iterations,
         // no degeneracy handling); fewer than 10 correspondences -> the round is skipped
@@ -2634,8 +2575,13 @@ static int track_cloud_impl(mlh_ctx *ctx, double pose_inout[7], const mlh_track_
         if (lean && outer == 0) m.init_pose = pose_inout;
         if ((rc = track_match_launch(ctx, 3, m))) return rc;
         TrackArgs b = track_args(opts, 0);
-        b.finish = 3; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 10; b.stat_slot = stats ? outer : -1;
+        b.finish = loop ? 0 : 3; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 10; b.stat_slot = stats ? outer : -1;
         if (lean && outer == 0) b.init_pose = pose_inout;
+        if (loop) {
+            if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
+            if ((rc = track_lm_loop_launch(ctx, 3, b))) return rc;
+            continue;
+        }
         if ((rc = track_linearize_launch(ctx, 3, b))) return rc;
         for (int it = 0; it < opts->max_lm_iterations; ++it) {
             TrackArgs s = track_args(opts, 1);
@@ -2649,10 +2595,12 @@ static int track_cloud_impl(mlh_ctx *ctx, double pose_inout[7], const mlh_track_
         if (stats && (rc = lm_finish_launch(ctx, outer))) return rc;     // fills the record's LM summary
     }
     if (lean) {
-        HostPublish hp;
-        if ((rc = wait_published(ctx, seq, hp))) return rc;
-        if (!ctx->prof.pending.empty()) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); prof_collect(ctx); }
-        for (int i = 0; i < 7; ++i) pose_inout[i] = hp.x[i];
+        bool given_up = false;         // (only a loop launch gives a barrier up)
+        if ((rc = collect_loop_pose(ctx, seq, rec, pose_inout, &given_up))) return rc;
+        if (given_up) {                // the rounds again, from the pose the caller still holds, a launch per LM iteration
+            note_loop_timeout(ctx, 2, tiles, true);
+            return track_cloud_impl(ctx, pose_inout, opts, stats, false);
+        }
         return MLH_OK;
     }
     return fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer);

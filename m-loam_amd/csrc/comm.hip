@@ -230,7 +230,7 @@ int mlh_p2p_mailbox(mlh_ctx *ctx, void *ipc_handle_64_bytes)
     // relying on what an XCD's L2 does with remotely written lines of ordinary (coarse-grained) memory. Ordinary memory otherwise (ranks sharing a device).
     hipIpcMemHandle_t h;
     bool have = false;
-    if (!std::getenv("MLH_P2P_COARSE") && hipExtMallocWithFlags(&ctx->p2p.mailbox, sizeof(P2pMailbox), hipDeviceMallocFinegrained) == hipSuccess) {
+    if (hipExtMallocWithFlags(&ctx->p2p.mailbox, sizeof(P2pMailbox), hipDeviceMallocFinegrained) == hipSuccess) {
         if (hipMemset(ctx->p2p.mailbox, 0, sizeof(P2pMailbox)) == hipSuccess && hipIpcGetMemHandle(&h, ctx->p2p.mailbox) == hipSuccess) have = true;
         else { (void)hipFree(ctx->p2p.mailbox); ctx->p2p.mailbox = nullptr; }
     }

@@ -406,7 +406,7 @@ struct mlh_ctx {
     int fused_parts = 0;
     float fused_minmax[2][6];   // folded by mlh_fused_cloud: the voxel filter of a fused cloud needs no bounds pass of its own
     int knn_lanes_override = 0;   // MLH_KNN_LANES=8|16|32, or SSCC (816, 832, 1632: surf lanes, corner lanes), in the environment at mlh_create: pins the correspondence kernel's lanes per query (tests, tuning)
-    int gn_final_defer = 1;       // MLH_GN_FINAL_DEFER=0: a solve submitted with mlh_gn_solve_begin* finishes its LAST iteration in its own fit launch (classic); 1: that
+    int gn_final_defer = 1;       // mlh_set_gn_schedule: 0: a solve submitted with mlh_gn_solve_begin* finishes its LAST iteration in its own fit launch (classic); 1: that
                                   // iteration, too, only leaves its records -- the next mlh_gn_solve_begin_chained completes it in its first launch (and publishes the pose
                                   // from there), mlh_gn_solve_end or any other solver call completes it with a one-workgroup launch if no successor did
     struct GnPending {            // the last iteration of the newest submitted solve is still a set of tile records
@@ -417,8 +417,8 @@ struct mlh_ctx {
         unsigned long long seq = 0;
     } gn_pending;
     int gn_slot_base = 0;         // xi slots of the next solve
-    int gn_defer = 1;             // MLH_GN_DEFER=0: Gauss-Newton solves keep the classic finish (the fit kernel's last-arriving workgroup) in every iteration (A/B, tests)
-    int knn_warm = 1;             // MLH_KNN_WARM=0: iterations >= 1 of a solve search without the previous iteration's neighbours as a bound (A/B, tests)
+    int gn_defer = 1;             // mlh_set_gn_schedule: 0: Gauss-Newton solves keep the classic finish (the fit kernel's last-arriving workgroup) in every iteration (A/B, tests)
+    int knn_warm = 1;             // mlh_set_gn_schedule: 0: iterations >= 1 of a solve search without the previous iteration's neighbours as a bound (A/B, tests)
     // multi-GPU
     bool shard_lo = false, shard_hi = false;
     float lo_plane[4] = {0, 0, 0, 0}, hi_plane[4] = {0, 0, 0, 0};
@@ -672,15 +672,32 @@ int lm_loop_occupancy(int blocks_per_cu[2]);      // hipOccupancyMaxActiveBlocks
 int track_loop_occupancy(int *blocks_per_cu);     // ... of track_lm_loop_kernel (track.hip)
 // the arrival counters of the fused finishes and of lm_loop_kernel's barrier: four zeroed words, whoever asks first ([0]: the finish tickets of match.hip and
 // track.hip; [1] arrivals, [2] departures, [3] release flag of the loop kernel). One place, so that no caller can leave the others' words unallocated or unzeroed.
+// The schedule switches that select the reference forms of the solvers (the tests compare them bit for bit): "=0" in the environment takes the reference form. Read
+// at every call: tests run both forms in one process.
+//   LM_CONSUMER  MLH_LM_CONSUMER=0: scan2map's LM steps in the classic launches (the linearise kernel's last workgroup) instead of the consumer of the records
+//   LM_LOOP      MLH_LM_LOOP=0: one launch per LM iteration instead of scan2map's whole LM loop in one launch (match.hip: lm_loop_kernel)
+//   LOOP_TAGGED  MLH_LOOP_TAGGED=0: the one-launch loop exchanges plain records behind a grid barrier instead of tagged records, and keeps the fit launch of its own
+//   TRACK_LOOP   MLH_TRACK_LOOP=0: track_cloud runs 2 + max_lm_iterations launches per round instead of two (track.hip: track_lm_loop_kernel)
+enum class Schedule { LM_CONSUMER, LM_LOOP, LOOP_TAGGED, TRACK_LOOP };
+inline bool schedule_on(Schedule s)
+{
+    const char *e = nullptr;
+    switch (s) {
+        case Schedule::LM_CONSUMER: e = std::getenv("MLH_LM_CONSUMER"); break;
+        case Schedule::LM_LOOP: e = std::getenv("MLH_LM_LOOP"); break;
+        case Schedule::LOOP_TAGGED: e = std::getenv("MLH_LOOP_TAGGED"); break;
+        case Schedule::TRACK_LOOP: e = std::getenv("MLH_TRACK_LOOP"); break;
+    }
+    return !(e && std::atoi(e) == 0);
+}
+
 // The tagged record sets of the one-launch LM loops (match.hip: lm_loop_kernel, track.hip: track_lm_loop_kernel; reduce_dev.hpp: lmc_sum_records_tagged): two sets of
 // 64 words per tile, and the number this launch's tags carry. *buf stays null where the loop keeps its grid barrier (MLH_LOOP_TAGGED=0; more iterations than the tag's
 // iteration byte counts). Zero is never a tag: a fresh allocation and a wrap of the 24-bit launch number clear the words.
 inline hipError_t loop_tagged_arm(mlh_ctx *ctx, size_t tiles, int lm_max_it, unsigned long long **buf, unsigned *tag_base)
 {
-    const char *env = std::getenv("MLH_LOOP_TAGGED");           // (read at every call, as the other schedule switches: tests run both forms in one process)
-    const bool off = env && std::atoi(env) == 0;
     *buf = nullptr; *tag_base = 0u;
-    if (off || lm_max_it > 200 || tiles == 0) return hipSuccess;
+    if (!schedule_on(Schedule::LOOP_TAGGED) || lm_max_it > 200 || tiles == 0) return hipSuccess;
     const size_t bytes = sizeof(unsigned long long) * 64 * tiles * 2;
     bool clear = bytes > ctx->loop_tagged.cap;
     hipError_t e = ctx->loop_tagged.ensure(bytes);

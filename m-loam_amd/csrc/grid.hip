@@ -519,10 +519,8 @@ int map_stage_and_build(mlh_ctx *ctx, int n_maps, const int *kinds, const unsign
         J.hi[0] = reuse ? g.ox + float(g.nx) * g.h : INFINITY; J.hi[1] = reuse ? g.oy + float(g.ny) * g.h : INFINITY;
         J.hi[2] = reuse ? g.oz + float(g.nz) * g.h : INFINITY;
     }
-    // every staged kind keeps its geometry (a mapper between keyframes): pack + fit check ride in the index build's first launch (pack_count_kernel);
-    // MLH_GRID_PACK_LAUNCH=1 keeps the launch of their own (A/B runs)
-    static const bool pack_apart = std::getenv("MLH_GRID_PACK_LAUNCH") && std::atoi(std::getenv("MLH_GRID_PACK_LAUNCH")) != 0;
-    const bool pack_in_build = need_bounds == 0 && !pack_apart;
+    // every staged kind keeps its geometry (a mapper between keyframes): pack + fit check ride in the index build's first launch (pack_count_kernel)
+    const bool pack_in_build = need_bounds == 0;
     if (!pack_in_build) MLH_LAUNCH(pack_check_kernel, dim3(G.j[0].nb + G.j[1].nb), dim3(256), 0, st, G);
     // the fit flags are final once the clouds are packed: they leave for the host NOW, and the optimistic index build of the kinds whose
     // geometry is reused is enqueued behind them -- the host learns the outcome (and can go on enqueueing the frame's solver launches)

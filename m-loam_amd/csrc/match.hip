@@ -1718,9 +1718,7 @@ int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a)
 
 bool loop_fit_fusable(const MatchArgs &loop_args)
 {
-    const char *env = std::getenv("MLH_LOOP_TAGGED"), *env_fit = std::getenv("MLH_LOOP_FIT");      // (A/B switches, read at every call: MLH_LOOP_FIT=0 keeps the fit launch)
-    if ((env && std::atoi(env) == 0) || (env_fit && std::atoi(env_fit) == 0)) return false;
-    return loop_args.lm_max_it <= 200 && loop_args.n_blocks == 1 && !loop_args.dense;
+    return schedule_on(Schedule::LOOP_TAGGED) && loop_args.lm_max_it <= 200 && loop_args.n_blocks == 1 && !loop_args.dense;
 }
 
 int lm_loop_occupancy(int blocks_per_cu[2])

@@ -813,10 +813,9 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
     const auto tp2 = std::chrono::steady_clock::now();
     int hs2 = 1;
     while (hs2 < hs) hs2 <<= 1;
-    static const bool host_rows = std::getenv("MLH_SEG_HOST_ROWS") != nullptr;       // (A/B runs: the round-4 host assembly)
     // seg_rows_kernel's dynamic LDS (20 bytes per padded row pixel: 80 KB at 4 096 columns) has to be granted per DEVICE, once, before a launch that needs it; a
     // device that does not grant it (a part with less LDS per compute unit) takes the host assembly below instead of failing the call
-    bool device_rows = hs2 <= SEG_ROW_MAX && !host_rows;
+    bool device_rows = hs2 <= SEG_ROW_MAX;
     if (device_rows) device_rows = seg_rows_lds_granted(ctx->device, size_t(20) * size_t(hs2));
     if (device_rows) {
         // ---- rows, erasure, concatenation and gather on the device (seg_rows_kernel / seg_rows_gather_kernel); the host keeps the outlier list only
@@ -905,7 +904,7 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
         }
         return MLH_OK;
     }
-    // ---- host assembly (rows longer than SEG_ROW_MAX pixels; MLH_SEG_HOST_ROWS=1)
+    // ---- host assembly (rows longer than SEG_ROW_MAX pixels; a device that does not grant the LDS)
     // the rows as the reference fills them: every pixel owner, in input order; cloud_scan_order = its position at fill time. One pass over the input
     // indices (a pixel's owner is an input index: bucket the pixels by owner, walk the indices upwards) gives every row already sorted and every
     // pixel its rank; the outlier erasure -- "erase what is NOW at the position recorded at fill time", stale positions included (U2) -- runs on an

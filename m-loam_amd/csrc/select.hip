@@ -827,8 +827,6 @@ int good_feature_finish(mlh_ctx *ctx, int kind, int method, double ratio, std::m
     FeatSet &f = ctx->feat[kind];
     if (!ctx->select_staged[kind]) return fail(ctx, MLH_ERR_STATE, "good_feature_finish without good_feature_stage");
     ctx->select_staged[kind] = false;
-    static const bool timing = std::getenv("MLH_SEL_TIMING") != nullptr;
-    const auto tc0 = std::chrono::steady_clock::now();
     MLH_HIP(ctx, stream_flag_wait(ctx, ctx->select_seq[kind]));
     Rows R;
     const size_t m = size_t(f.m);
@@ -853,7 +851,6 @@ int good_feature_finish(mlh_ctx *ctx, int kind, int method, double ratio, std::m
     R.valid = reinterpret_cast<const uint8_t *>(cb + off_v); R.J = reinterpret_cast<const double *>(cb); R.pts = reinterpret_cast<const float4 *>(cb + off_p);
     if (matched_out) for (size_t i = 0; i < m; ++i) matched_out[i] = R.matched(i) ? 1 : 0;
 
-    const auto tc1 = std::chrono::steady_clock::now();
     const size_t n_use = static_cast<size_t>(m * ratio);   // num_use_features (lidar_mapper.h:247)
     std::vector<size_t> sel;
     sel.reserve(method == MLH_GF_WO ? m : n_use);
@@ -869,7 +866,6 @@ int good_feature_finish(mlh_ctx *ctx, int kind, int method, double ratio, std::m
         case MLH_GF_GD_FLOAT: select_greedy(R, n_use, rng, sel, H); break;
         default: return fail(ctx, MLH_ERR_INVALID, "unknown gf_method");
     }
-    const auto tc2 = std::chrono::steady_clock::now();
     // keep only the selected correspondences valid on the device: one verdict byte per feature goes back, a launch writes them into the records
     if (method != MLH_GF_WO) {
         uint8_t *keep = reinterpret_cast<uint8_t *>(hb + off_k);     // (sequential writes into the pinned block: the mapping is fine for those)
@@ -882,12 +878,6 @@ int good_feature_finish(mlh_ctx *ctx, int kind, int method, double ratio, std::m
         MLH_HIP(ctx, hipGetLastError());
     }
     sel_out.assign(sel.begin(), sel.end());
-    if (timing) {
-        const auto tc3 = std::chrono::steady_clock::now();
-        auto us = [](std::chrono::steady_clock::time_point x, std::chrono::steady_clock::time_point y) { return std::chrono::duration<double, std::micro>(y - x).count(); };
-        std::fprintf(stderr, "[good_feature_finish] kind %d m %zu: wait for the rows + copy out of the pinned block %.0f us | selection loop %.0f us (%zu picks) | flags enqueued %.0f us\n", kind, m,
-                     us(tc0, tc1), us(tc1, tc2), sel.size(), us(tc2, tc3));
-    }
     return MLH_OK;
 }
 

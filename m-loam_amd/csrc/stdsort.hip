@@ -905,18 +905,15 @@ static int stdsort_levels(mlh_ctx *ctx, StdSortArgs A, int longest, size_t nbig,
         const int grid_big = int(std::min<size_t>(nbig, 64));
         // wide levels: as long as a range can still be longer than SS_WIDE_MIN -- the sizes roughly halve per level; two more levels for the unbalanced
         // partitions. A wide range met later than that is partitioned by one workgroup, as all were until round 5 (same result).
-        static const bool wide_off = std::getenv("MLH_SS_WIDE_OFF") != nullptr;      // (A/B runs)
         int n_wide_levels = 0;
         const bool fits = size_t(A.n) / SS_WIDE_WAVE + 64 <= size_t(A.n) / 2 && size_t(A.n) / SS_WIDE_MIN * SS_WIDE_INFO + 64 <= size_t(A.n);
-        if (!wide_off && fits && longest > SS_WIDE_MIN) {
+        if (fits && longest > SS_WIDE_MIN) {
             int lg = 0;
             while ((SS_WIDE_MIN << lg) < longest) ++lg;
-            static const int extra = std::getenv("MLH_SS_WIDE_EXTRA") ? std::atoi(std::getenv("MLH_SS_WIDE_EXTRA")) : MLH_SS_WIDE_EXTRA;      // (A/B runs)
-            n_wide_levels = std::min(n_levels, lg + extra);
+            n_wide_levels = std::min(n_levels, lg + MLH_SS_WIDE_EXTRA);
         }
-        // the mid launch behind the wide levels instead of the remaining big levels (MLH_SS_MID_OFF: A/B runs; a device that does not grant its 144 KB of LDS)
-        static const bool mid_off = std::getenv("MLH_SS_MID_OFF") != nullptr;
-        const bool mid = !mid_off && n_wide_levels < SS_BIG_LEVELS && stdsort_mid_lds_granted(ctx->device);
+        // the mid launch behind the wide levels instead of the remaining big levels (not on a device that does not grant its 144 KB of LDS)
+        const bool mid = n_wide_levels < SS_BIG_LEVELS && stdsort_mid_lds_granted(ctx->device);
         if (mid) n_levels = n_wide_levels;
         const int n_wide_wg = A.n / SS_WIDE_CHUNK + A.n / SS_WIDE_MIN + 4;     // >= the chunks of all wide ranges of a level
         for (int level = 0; level < n_levels; ++level) {

@@ -764,8 +764,7 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
     hipStream_t st = ctx->stream;
     VoxBuf &V = ctx->vox;
     const int n = n_surf + n_corner;
-    static const bool old_pipeline = std::getenv("MLH_THIN_SLOTS_FIRST") != nullptr;       // (A/B runs: the round-4 pipeline)
-    if (ctx->vox_member_order == 1 && n_lidar <= 4 && n_surf > 0 && n_corner > 0 && stride >= 12 && !(stride & 3) && leaf_surf > 0.f && leaf_corner > 0.f && !old_pipeline) {
+    if (ctx->vox_member_order == 1 && n_lidar <= 4 && n_surf > 0 && n_corner > 0 && stride >= 12 && !(stride & 3) && leaf_surf > 0.f && leaf_corner > 0.f) {
         // ---- sort first (see above). The two grids' geometry as voxel_filter_run2 lays it out.
         VoxKeyGen G;
         const float *hb[2] = {bounds_surf, bounds_corner};

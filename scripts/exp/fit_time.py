@@ -32,4 +32,4 @@ for mode in ("gn_solve", "begin+end"):
         else:
             ctx.gn_solve_begin(p0, 5, opts); ctx.gn_solve_end()
     ctx.synchronize(); dt = (time.perf_counter() - t0) / 400
-    print(f"  {mode:10s} {1e3 * dt:.4f} ms per solve (MLH_GN_FINAL_DEFER={os.environ.get('MLH_GN_FINAL_DEFER', '1')})")
+    print(f"  {mode:10s} {1e3 * dt:.4f} ms per solve")
