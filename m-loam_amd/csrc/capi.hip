@@ -100,8 +100,8 @@ void prof_collect(mlh_ctx *ctx)
     p.pending.clear();
 }
 
-// AoS records (stride bytes) -> float4 {x,y,z,w}; w = f32 at w_off, or the record index (as int bits) when w_off == -2, or 0
-__global__ __launch_bounds__(256) void pack_points_kernel(const unsigned char *__restrict__ src, int stride, int n, int w_off,
+// AoS records (stride bytes) -> float4 {x,y,z,w}; w = f32 at w_off, or what PACK_W_* says (ctx.hpp)
+__global__ __launch_bounds__(256) void pack_points_kernel(const unsigned char *__restrict__ src, int stride, int n, int w_off, float w_value,
                                                           int cov_off, float4 *__restrict__ out, float4 *__restrict__ covd)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -109,7 +109,8 @@ __global__ __launch_bounds__(256) void pack_points_kernel(const unsigned char *_
     const float *rec = reinterpret_cast<const float *>(src + size_t(i) * stride);
     float4 p;
     p.x = rec[0]; p.y = rec[1]; p.z = rec[2];
-    if (w_off == -2) p.w = __int_as_float(i);
+    if (w_off == PACK_W_INDEX) p.w = __int_as_float(i);
+    else if (w_off == PACK_W_VALUE) p.w = w_value;
     else if (w_off >= 0) p.w = *reinterpret_cast<const float *>(src + size_t(i) * stride + w_off);
     else p.w = 0.f;
     out[i] = p;
@@ -123,21 +124,37 @@ __global__ __launch_bounds__(256) void pack_points_kernel(const unsigned char *_
     }
 }
 
-static int stage_points(mlh_ctx *ctx, const void *points, int stride, int n, int mem, int w_off, int cov_off, DevBuf &dst, DevBuf *covd,
-                        DevBuf &tmp)
+void pack_points_launch(hipStream_t st, const unsigned char *dev, int stride, int n, int w_off, float w_value, int cov_off, float4 *out, float4 *covd)
 {
-    if (!points || n <= 0 || stride < 12 || (stride & 3)) return fail(ctx, MLH_ERR_INVALID, "bad point buffer (null, n <= 0, or stride not a multiple of 4 >= 12)");
-    MLH_HIP(ctx, dst.ensure(sizeof(float4) * size_t(n)));
-    if (covd) MLH_HIP(ctx, covd->ensure(sizeof(float4) * size_t(n)));
-    const unsigned char *src = static_cast<const unsigned char *>(points);
-    if (mem == MLH_MEM_HOST) {
-        MLH_HIP(ctx, tmp.ensure(size_t(n) * stride));
-        MLH_HIP(ctx, hipMemcpyAsync(tmp.p, points, size_t(n) * stride, hipMemcpyHostToDevice, ctx->stream));
-        src = tmp.as<unsigned char>();
-    }
-    MLH_LAUNCH(pack_points_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, src, stride, n, w_off, cov_off,
-                       dst.as<float4>(), covd ? covd->as<float4>() : nullptr);
+    MLH_LAUNCH(pack_points_kernel, dim3((n + 255) / 256), dim3(256), 0, st, dev, stride, n, w_off, w_value, cov_off, out, covd);
+}
+
+int records_check(mlh_ctx *ctx, const char *entry, const Records &r, bool allow_empty)
+{
+    const char *fault = records_fault(r, allow_empty);
+    return fault ? fail(ctx, MLH_ERR_INVALID, (std::string(entry) + ": bad " + fault + " (records: stride a multiple of 4 >= 12, every field inside it)").c_str()) : MLH_OK;
+}
+
+int records_stage(mlh_ctx *ctx, const Records &r, DevBuf &staging, hipStream_t st, const unsigned char **dev, size_t at)
+{
+    *dev = r.p;
+    if (r.mem != MLH_MEM_HOST || r.n == 0) return MLH_OK;
+    MLH_HIP(ctx, staging.ensure(at + r.bytes()));
+    *dev = staging.as<unsigned char>() + at;
+    MLH_HIP(ctx, hipMemcpyAsync(staging.as<unsigned char>() + at, r.p, r.bytes(), hipMemcpyHostToDevice, st));
+    return MLH_OK;
+}
+
+// validated records -> dst (float4, w as w_off says) and, with covd, the covariance diagonals; *dev_src (optional) = where the records were read from
+static int stage_points(mlh_ctx *ctx, const Records &r, int w_off, DevBuf &dst, DevBuf *covd, DevBuf &tmp, const unsigned char **dev_src = nullptr)
+{
+    MLH_HIP(ctx, dst.ensure(sizeof(float4) * size_t(r.n)));
+    if (covd) MLH_HIP(ctx, covd->ensure(sizeof(float4) * size_t(r.n)));
+    const unsigned char *src;
+    { const int rc = records_stage(ctx, r, tmp, ctx->stream, &src); if (rc) return rc; }
+    pack_points_launch(ctx->stream, src, r.stride, r.n, w_off, 0.f, r.cov_off, dst.as<float4>(), covd ? covd->as<float4>() : nullptr);
     MLH_HIP(ctx, hipGetLastError());
+    if (dev_src) *dev_src = src;
     return MLH_OK;
 }
 
@@ -557,7 +574,7 @@ static int scan_wait_readers(mlh_ctx *ctx)
 int mlh_scan_upload_ahead(mlh_ctx *ctx, const void *points, int stride_bytes, int n)
 {
     if (!ctx) return MLH_ERR_INVALID;
-    if (!points || n <= 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(ctx, MLH_ERR_INVALID, "bad point buffer (null, n <= 0, or stride not a multiple of 4 >= 12)");
+    { const int rc = records_check(ctx, "mlh_scan_upload_ahead", records_of(points, stride_bytes, n, MLH_MEM_HOST)); if (rc) return rc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     mlh_ctx::ScanAhead &A = ctx->ahead;
     if (!A.cs) {
@@ -600,23 +617,23 @@ int mlh_scan_upload(mlh_ctx *ctx, const void *points, int stride_bytes, int inte
     sb.extracted = false;
     sb.voxelised = false;
     sb.h_lists_valid = sb.h_vox_valid = false;
-    if (intensity_offset_bytes >= 0 && intensity_offset_bytes + 4 > stride_bytes) return fail(ctx, MLH_ERR_INVALID, "intensity offset outside the record");
+    Records rec = records_of(points, stride_bytes, n, mem, intensity_offset_bytes);
+    { const int rc = records_check(ctx, "mlh_scan_upload", rec); if (rc) return rc; }
     // A caller's PAGEABLE buffer (a ROS message) goes through hipMemcpyAsync as it is: like cudaMemcpyAsync, the call returns once the pageable source has been
     // copied into the runtime's own staging memory (the DMA to the device may still be in flight), so the buffer is the caller's again when this call returns,
     // and nothing here waits for the stream. MLH_SCAN_STAGE_PINNED=1 makes that independent of the runtime: the points are first copied into a pinned block the
     // context owns (two halves, an event per half) and go to the device from there -- measured +0.08 ms per two-LiDAR frame (the runtime writes small pageable
     // copies faster than an explicit memcpy + DMA pair: scripts/framebench.py, C++ leg, 0.859 against 0.940 ms, two alternations), hence not the default.
     // (A buffer the caller pinned is copied from in place; that case waits below.)
-    const void *src_points = points;
     bool caller_pinned = false;
     int pts_half = -1;
-    if (mem == MLH_MEM_HOST && points && n > 0 && stride_bytes >= 12) {
+    if (mem == MLH_MEM_HOST) {
         hipPointerAttribute_t at;
         caller_pinned = hipPointerGetAttributes(&at, points) == hipSuccess && at.type == hipMemoryTypeHost;
         (void)hipGetLastError();
         static const bool stage_pinned = std::getenv("MLH_SCAN_STAGE_PINNED") && std::atoi(std::getenv("MLH_SCAN_STAGE_PINNED")) != 0;
         if (!caller_pinned && stage_pinned) {
-            const size_t bytes = size_t(n) * stride_bytes;
+            const size_t bytes = rec.bytes();
             if (bytes > ctx->h_pts_cap) {
                 MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
                 if (ctx->h_pts) (void)hipHostFree(ctx->h_pts);
@@ -631,24 +648,23 @@ int mlh_scan_upload(mlh_ctx *ctx, const void *points, int stride_bytes, int inte
             if (ctx->ev_pts_used[pts_half]) MLH_HIP(ctx, hipEventSynchronize(ctx->ev_pts[pts_half]));      // two uploads ago
             void *dst = static_cast<char *>(ctx->h_pts) + size_t(pts_half) * ctx->h_pts_cap;
             std::memcpy(dst, points, bytes);
-            src_points = dst;
+            rec.p = static_cast<const unsigned char *>(dst);
         }
     }
     // sent ahead (mlh_scan_upload_ahead with this very buffer)? then the points are on the device already, or on their way: the main stream waits for their arrival and
     // packs from there. Any other host upload drops what was sent ahead (it was another scan's).
     mlh_ctx::ScanAhead &AH = ctx->ahead;
-    int pts_mem = mem;
     bool from_ahead = false;
     if (mem == MLH_MEM_HOST && AH.valid) {
         if (AH.src == points && AH.n == n && AH.stride == stride_bytes && pts_half < 0) {
             MLH_HIP(ctx, hipStreamWaitEvent(ctx->stream, AH.ev_arrived, 0));
             if (AH.src_pinned) MLH_HIP(ctx, hipEventSynchronize(AH.ev_arrived));      // issued a frame ago: long done
-            src_points = AH.buf.p; pts_mem = MLH_MEM_DEVICE; from_ahead = true; caller_pinned = false;
+            rec.p = AH.buf.as<unsigned char>(); rec.mem = MLH_MEM_DEVICE; from_ahead = true; caller_pinned = false;
             ++AH.used;
         }
         AH.valid = false;
     }
-    int rc = stage_points(ctx, src_points, stride_bytes, n, pts_mem, intensity_offset_bytes >= 0 ? intensity_offset_bytes : -1, -1, sb.pts, nullptr, ctx->tmp);
+    int rc = stage_points(ctx, rec, intensity_offset_bytes >= 0 ? intensity_offset_bytes : PACK_W_ZERO, sb.pts, nullptr, ctx->tmp);
     if (rc) return rc;
     if (from_ahead) { MLH_HIP(ctx, hipEventRecord(AH.ev_consumed, ctx->stream)); AH.consumed_recorded = true; }
     if (pts_half >= 0) {
@@ -712,7 +728,7 @@ int mlh_segment_cloud(mlh_ctx *ctx, const void *points, int stride_bytes, int in
 {
     if (!ctx || !prm) return MLH_ERR_INVALID;
     if (outlier_out && outlier_capacity < 0) return fail(ctx, MLH_ERR_INVALID, "negative outlier capacity");
-    if (intensity_offset_bytes >= 0 && intensity_offset_bytes + 4 > stride_bytes) return fail(ctx, MLH_ERR_INVALID, "intensity offset outside the record");
+    { const int rc = records_check(ctx, "mlh_segment_cloud", records_of(points, stride_bytes, n, mem, intensity_offset_bytes)); if (rc) return rc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     { const int wrc = scan_wait_readers(ctx); if (wrc) return wrc; }
     return segment_cloud_run(ctx, points, stride_bytes, intensity_offset_bytes, n, mem, *prm, cloud_out, n_out, scan_start, scan_end, outlier_out, outlier_capacity, n_outlier);
@@ -780,6 +796,7 @@ int mlh_point_uncertainty(mlh_ctx *ctx, const void *points, int stride_bytes, in
                           double trace_threshold, float *cov_vec_out, int32_t *keep_out)
 {
     if (!ctx || !ext_poses || !ext_covs || !cov_measurement || !cov_vec_out || !keep_out) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_point_uncertainty", records_of(points, stride_bytes, n, mem, intensity_offset_bytes)); if (rc) return rc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     return point_uncertainty_run(ctx, points, stride_bytes, n, intensity_offset_bytes, mem, ext_poses, ext_covs, n_lidar, cov_measurement,
                                  trace_threshold, cov_vec_out, keep_out);
@@ -885,6 +902,7 @@ int mlh_cloud_uct_associate_to_map(mlh_ctx *ctx, const void *points, int stride_
                                    void *out, int32_t *n_out, int mem)
 {
     if (!ctx) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_cloud_uct_associate_to_map", records_of(points, stride_bytes, n, mem, intensity_offset_bytes, cov_offset_bytes, trace_offset_bytes)); if (rc) return rc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     return cloud_uct_associate_run(ctx, points, stride_bytes, n, intensity_offset_bytes, cov_offset_bytes, trace_offset_bytes, pose_global,
                                    cov_global, ext_poses, ext_covs, n_lidar, cov_measurement, with_ua, trace_threshold, out, n_out, mem);
@@ -902,6 +920,7 @@ int mlh_voxel_filter(mlh_ctx *ctx, const void *points, int stride_bytes, int n, 
                      int trace_offset_bytes, float leaf, float trace_threshold, void *out, int32_t *n_out, int mem)
 {
     if (!ctx) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_voxel_filter", records_of(points, stride_bytes, n, mem, intensity_offset_bytes, cov_offset_bytes, trace_offset_bytes)); if (rc) return rc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     return voxel_filter_run(ctx, points, stride_bytes, n, intensity_offset_bytes, cov_offset_bytes, trace_offset_bytes, leaf, trace_threshold,
                             out, n_out, mem);
@@ -912,54 +931,54 @@ int mlh_voxel_filter(mlh_ctx *ctx, const void *points, int stride_bytes, int n, 
 int mlh_voxel_grid(mlh_ctx *ctx, const void *points, int stride_bytes, int n, int intensity_offset_bytes, float leaf, void *out, int32_t *n_out, int mem)
 {
     if (!ctx || intensity_offset_bytes < 12) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_voxel_grid", records_of(points, stride_bytes, n, mem, intensity_offset_bytes)); if (rc) return rc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     return voxel_filter_run(ctx, points, stride_bytes, n, intensity_offset_bytes, -1, -1, leaf, 0.f, out, n_out, mem, nullptr, true, true);
 }
 
-int mlh_transform_point_cloud(mlh_ctx *ctx, void *points, int stride_bytes, int n, const double pose[7], int mem)
+// the way out of the two in-place transforms: a host cloud goes home from `dev` and is waited for; a failed launch drains the stream first
+static int transform_finish(mlh_ctx *ctx, int rc, const Records &r, void *points, const unsigned char *dev)
 {
-    if (!ctx || !points || !pose || n < 0 || stride_bytes < 12 || (stride_bytes & 3)) return MLH_ERR_INVALID;
-    if (n == 0) return MLH_OK;
-    MLH_HIP(ctx, hipSetDevice(ctx->device));
-    unsigned char *dev = static_cast<unsigned char *>(points);
-    const size_t bytes = size_t(n) * stride_bytes;
-    if (mem == MLH_MEM_HOST) {
-        MLH_HIP(ctx, ctx->tmp.ensure(bytes));
-        MLH_HIP(ctx, hipMemcpyAsync(ctx->tmp.p, points, bytes, hipMemcpyHostToDevice, ctx->stream));
-        dev = ctx->tmp.as<unsigned char>();
-    }
-    { int rc = transform_cloud_launch(ctx, dev, stride_bytes, n, pose); if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; } }
-    if (mem == MLH_MEM_HOST) {
-        MLH_HIP(ctx, hipMemcpyAsync(points, ctx->tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if (r.mem == MLH_MEM_HOST) {
+        MLH_HIP(ctx, hipMemcpyAsync(points, dev, r.bytes(), hipMemcpyDeviceToHost, ctx->stream));
         MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     return MLH_OK;
+}
+
+int mlh_transform_point_cloud(mlh_ctx *ctx, void *points, int stride_bytes, int n, const double pose[7], int mem)
+{
+    if (!ctx || !points || !pose) return MLH_ERR_INVALID;
+    const Records r = records_of(points, stride_bytes, n, mem);
+    { const int rc = records_check(ctx, "mlh_transform_point_cloud", r, true); if (rc) return rc; }
+    if (n == 0) return MLH_OK;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    const unsigned char *dev;
+    { const int rc = records_stage(ctx, r, ctx->tmp, ctx->stream, &dev); if (rc) return rc; }
+    return transform_finish(ctx, transform_cloud_launch(ctx, const_cast<unsigned char *>(dev), stride_bytes, n, pose), r, points, dev);
 }
 
 // ---------------------------------------------------------------- map
 // host records are copied to the staging buffer first (both clouds back to back); device records are read in place
 static int map_set_impl(mlh_ctx *ctx, int n_maps, const int *kinds, const void *const *points, const int *n, int stride_bytes, float min_match_sq_dis, int mem)
 {
-    if (ctx) ++ctx->stage_epoch;      // (mlh_scan2map_end: a frame in flight may only be re-solved on the inputs it was submitted with)
+    if (ctx) ++ctx->stage_epoch;
     if (!(min_match_sq_dis > 0.f)) return fail(ctx, MLH_ERR_INVALID, "min_match_sq_dis must be positive");
-    if (stride_bytes < 12 || (stride_bytes & 3)) return fail(ctx, MLH_ERR_INVALID, "bad point buffer (stride not a multiple of 4 >= 12)");
-    for (int k = 0; k < n_maps; ++k) if (!points[k] || n[k] <= 0) return fail(ctx, MLH_ERR_INVALID, "bad point buffer (null or n <= 0)");
-    MLH_HIP(ctx, hipSetDevice(ctx->device));
-    const unsigned char *src[2] = {nullptr, nullptr};
-    if (mem == MLH_MEM_HOST) {
-        size_t off[2] = {0, 0}, total = 0;
-        for (int k = 0; k < n_maps; ++k) { off[k] = total; total += ((size_t(n[k]) * stride_bytes + 255) / 256) * 256; }
-        // the overlapped path runs on the staging stream beside whatever the main stream has queued (a scan upload's pack kernel may still be reading ctx->tmp):
-        // it stages through a buffer of its own
-        DevBuf &tmp = (ctx->stream2 && ctx->stream == ctx->stream2) ? ctx->tmp_stage : ctx->tmp;
-        MLH_HIP(ctx, tmp.ensure(total));
-        for (int k = 0; k < n_maps; ++k) {
-            MLH_HIP(ctx, hipMemcpyAsync(tmp.as<unsigned char>() + off[k], points[k], size_t(n[k]) * stride_bytes, hipMemcpyHostToDevice, ctx->stream));
-            src[k] = tmp.as<unsigned char>() + off[k];
-        }
-    } else {
-        for (int k = 0; k < n_maps; ++k) src[k] = static_cast<const unsigned char *>(points[k]);
+    Records r[2];
+    size_t off[2] = {0, 0}, total = 0;
+    for (int k = 0; k < n_maps; ++k) {
+        r[k] = records_of(points[k], stride_bytes, n[k], mem);
+        { const int rc = records_check(ctx, n_maps == 1 ? "mlh_map_set" : "mlh_map_set_pair", r[k]); if (rc) return rc; }
+        off[k] = total; total += ((r[k].bytes() + 255) / 256) * 256;
     }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    // the overlapped path runs on the staging stream beside whatever the main stream has queued (a scan upload's pack kernel may still be reading ctx->tmp):
+    // it stages through a buffer of its own
+    DevBuf &tmp = (ctx->stream2 && ctx->stream == ctx->stream2) ? ctx->tmp_stage : ctx->tmp;
+    if (mem == MLH_MEM_HOST) MLH_HIP(ctx, tmp.ensure(total));
+    const unsigned char *src[2] = {nullptr, nullptr};
+    for (int k = 0; k < n_maps; ++k) { const int rc = records_stage(ctx, r[k], tmp, ctx->stream, &src[k], off[k]); if (rc) return rc; }
     HostPublish *pub;
     unsigned long long seq;
     int rc = publish_slot(ctx, &pub, &seq);
@@ -1162,29 +1181,13 @@ __global__ void pad_fill_kernel(float4 *pts, float4 *covd, int from, int to)
     if (i < to) { pts[i] = make_float4(0.f, 0.f, 0.f, -1.f); covd[i] = make_float4(0.f, 0.f, 0.f, 0.f); }
 }
 
-// AoS records -> float4 at an offset; the stored w is the pose-block id (>= 0)
-__global__ __launch_bounds__(256) void pack_block_kernel(const unsigned char *__restrict__ src, int stride, int n, int cov_off, float wval,
-                                                         float4 *__restrict__ out, float4 *__restrict__ covd)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const float *rec = reinterpret_cast<const float *>(src + size_t(i) * stride);
-    out[i] = make_float4(rec[0], rec[1], rec[2], wval);
-    float4 c = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (cov_off >= 0) {
-        const float *cv = reinterpret_cast<const float *>(src + size_t(i) * stride + cov_off);
-        c.x = cv[0]; c.y = cv[3]; c.z = cv[5];
-    }
-    covd[i] = c;
-}
-
 int mlh_features_set_block(mlh_ctx *ctx, int kind, int block, const void *points, int stride_bytes, int n, int cov_offset_bytes, int mem)
 {
-    if (ctx) ++ctx->stage_epoch;      // (mlh_scan2map_end: a frame in flight may only be re-solved on the inputs it was submitted with)
+    if (ctx) ++ctx->stage_epoch;
     if (!ctx || kind < 0 || kind > 1 || block < 0 || block >= 8) return MLH_ERR_INVALID;
     // (n == 0: a LiDAR without features of this kind in this frame -- the block exists, holds nothing, contributes no residuals; `points` may be null then)
-    if ((!points && n > 0) || n < 0 || stride_bytes < 12 || (stride_bytes & 3)) return fail(ctx, MLH_ERR_INVALID, "bad point buffer");
-    if (cov_offset_bytes >= 0 && cov_offset_bytes + 24 > stride_bytes) return fail(ctx, MLH_ERR_INVALID, "cov_offset_bytes + 24 exceeds the record stride");
+    const Records r = records_of(points, stride_bytes, n, mem, -1, cov_offset_bytes);
+    { const int rc = records_check(ctx, "mlh_features_set_block", r, true); if (rc) return rc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     FeatSet &f = ctx->feat[kind];
     if (block == 0) { f.m = 0; f.n_blocks = 0; f.has_cov = false; }
@@ -1196,15 +1199,10 @@ int mlh_features_set_block(mlh_ctx *ctx, int kind, int block, const void *points
     MLH_HIP(ctx, f.covd.grow(sizeof(float4) * total, sizeof(float4) * size_t(f.m), ctx->stream));
     if (start > f.m)
         MLH_LAUNCH(pad_fill_kernel, dim3((start - f.m + 255) / 256), dim3(256), 0, ctx->stream, f.pts.as<float4>(), f.covd.as<float4>(), f.m, start);
-    const unsigned char *src = static_cast<const unsigned char *>(points);
-    if (mem == MLH_MEM_HOST && n > 0) {
-        MLH_HIP(ctx, ctx->tmp.ensure(size_t(n) * stride_bytes));
-        MLH_HIP(ctx, hipMemcpyAsync(ctx->tmp.p, points, size_t(n) * stride_bytes, hipMemcpyHostToDevice, ctx->stream));
-        src = ctx->tmp.as<unsigned char>();
-    }
-    if (n > 0)
-        MLH_LAUNCH(pack_block_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, src, stride_bytes, n, cov_offset_bytes, float(block),
-                           f.pts.as<float4>() + start, f.covd.as<float4>() + start);
+    const unsigned char *src;
+    { const int rc = records_stage(ctx, r, ctx->tmp, ctx->stream, &src); if (rc) return rc; }
+    // the stored w is the pose-block id (>= 0; the padding's is < 0)
+    if (n > 0) pack_points_launch(ctx->stream, src, stride_bytes, n, PACK_W_VALUE, float(block), cov_offset_bytes, f.pts.as<float4>() + start, f.covd.as<float4>() + start);
     MLH_HIP(ctx, hipGetLastError());
     MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     f.blk_start[block] = start;
@@ -1219,24 +1217,18 @@ int mlh_features_set_block(mlh_ctx *ctx, int kind, int block, const void *points
 int mlh_features_set(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int n, int intensity_offset_bytes,
                      int cov_offset_bytes, int mem)
 {
-    if (ctx) ++ctx->stage_epoch;      // (mlh_scan2map_end: a frame in flight may only be re-solved on the inputs it was submitted with)
+    if (ctx) ++ctx->stage_epoch;
     if (!ctx || kind < 0 || kind > 1) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     FeatSet &f = ctx->feat[kind];
     f.matched = false;
     f.m = 0;
-    if (cov_offset_bytes >= 0 && cov_offset_bytes + 24 > stride_bytes) return fail(ctx, MLH_ERR_INVALID, "cov_offset_bytes + 24 exceeds the record stride");
-    if (intensity_offset_bytes >= 0 && intensity_offset_bytes + 4 > stride_bytes) return fail(ctx, MLH_ERR_INVALID, "intensity offset exceeds the record stride");
-    (void)intensity_offset_bytes;   // the LiDAR index is not needed by the single-pose path; the slot marks padding in block mode
-    int rc = stage_points(ctx, points, stride_bytes, n, mem, -1, cov_offset_bytes, f.pts, &f.covd, ctx->tmp);
-    if (rc) return rc;
+    const Records r = records_of(points, stride_bytes, n, mem, intensity_offset_bytes, cov_offset_bytes);
+    int rc = records_check(ctx, "mlh_features_set", r);
+    // (w stays 0: the LiDAR index is not needed by the single-pose path; the slot marks padding in block mode)
+    if (rc || (rc = stage_points(ctx, r, PACK_W_ZERO, f.pts, &f.covd, ctx->tmp))) return rc;
     MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    f.m = n;
-    f.n_blocks = 1;
-    f.blk_start[0] = 0;
-    f.blk_real[0] = n;
-    for (int b = 1; b <= 8; ++b) f.blk_start[b] = n;
-    f.has_cov = cov_offset_bytes >= 0;
+    f.single_block(n, cov_offset_bytes >= 0);
     return MLH_OK;
 }
 
@@ -1245,7 +1237,7 @@ int mlh_features_set(mlh_ctx *ctx, int kind, const void *points, int stride_byte
 // (there: a ROS message through host memory). Ordered after everything `src` has enqueued (waited for here); the copies run on dst's stream.
 int mlh_features_copy(mlh_ctx *dst, mlh_ctx *src, int kind)
 {
-    if (dst) ++dst->stage_epoch;      // (mlh_scan2map_end: a frame in flight may only be re-solved on the inputs it was submitted with)
+    if (dst) ++dst->stage_epoch;
     if (!dst || !src || dst == src || kind < 0 || kind > 1) return MLH_ERR_INVALID;
     if (dst->device != src->device) return fail(dst, MLH_ERR_UNSUPPORTED, "mlh_features_copy: both contexts must be on the same device");
     MLH_HIP(dst, hipSetDevice(dst->device));
@@ -1270,27 +1262,39 @@ int mlh_features_copy(mlh_ctx *dst, mlh_ctx *src, int kind)
     return MLH_OK;
 }
 
+// are these records this context's own fused cloud of `kind` (mlh_fused_cloud: device float4 records whose exact bounding box is known)?
+static bool is_fused_cloud(const mlh_ctx *ctx, int kind, const void *points, int n, int stride_bytes, int mem)
+{
+    return mem == MLH_MEM_DEVICE && !ctx->fused_dirty && n > 0 && points == ctx->fused[kind].p && n == ctx->fused_n[kind] && stride_bytes == 16;
+}
+// ... and the pair both fused clouds, read with the intensity where mlh_fused_cloud puts it: they go through ONE thinning pipeline
+static bool is_fused_pair(const mlh_ctx *ctx, const void *surf, int n_surf, const void *corner, int n_corner, int stride_bytes, int intensity_offset_bytes, int mem)
+{
+    return intensity_offset_bytes == 12 && is_fused_cloud(ctx, MLH_SURF, surf, n_surf, stride_bytes, mem) && is_fused_cloud(ctx, MLH_CORNER, corner, n_corner, stride_bytes, mem);
+}
+
 // downsampleCurrentScan for one feature kind, device-resident: the result IS the kind's feature set
 int mlh_downsample_current_scan(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int n, int intensity_offset_bytes, int mem,
                                 float leaf, const double *ext_poses, const double *ext_covs, int n_lidar, const double cov_measurement[9],
                                 int with_ua, double trace_threshold, float *features_out, int32_t *n_features)
 {
-    if (ctx) ++ctx->stage_epoch;      // (mlh_scan2map_end: a frame in flight may only be re-solved on the inputs it was submitted with)
+    if (ctx) ++ctx->stage_epoch;
     if (!ctx || kind < 0 || kind > 1 || !n_features) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     FeatSet &f = ctx->feat[kind];
     f.matched = false;
     f.m = 0;
+    { const int rc = records_check(ctx, "mlh_downsample_current_scan", records_of(points, stride_bytes, n, mem, intensity_offset_bytes)); if (rc) return rc; }
     float *d_out = nullptr;
     if (features_out) {
-        MLH_HIP(ctx, ctx->tmp.ensure(sizeof(float) * 11 * size_t(n > 0 ? n : 1)));
+        MLH_HIP(ctx, ctx->tmp.ensure(sizeof(float) * 11 * size_t(n)));
         d_out = ctx->tmp.as<float>();
     }
     int m = 0;
     // a fused cloud of this context brings its exact bounding box along (mlh_fused_cloud): no bounds pass
     const float *known_bounds = nullptr;
     for (int k = 0; k < 2; ++k)
-        if (mem == MLH_MEM_DEVICE && !ctx->fused_dirty && n > 0 && points == ctx->fused[k].p && n == ctx->fused_n[k] && stride_bytes == 16) known_bounds = ctx->fused_minmax[k];
+        if (is_fused_cloud(ctx, k, points, n, stride_bytes, mem)) known_bounds = ctx->fused_minmax[k];
     int rc = downsample_current_scan_run(ctx, points, stride_bytes, n, intensity_offset_bytes, mem, leaf, ext_poses, ext_covs, n_lidar, cov_measurement,
                                          with_ua, trace_threshold, f.pts, f.covd, d_out, &m, known_bounds);
     if (rc) return rc;
@@ -1299,12 +1303,7 @@ int mlh_downsample_current_scan(mlh_ctx *ctx, int kind, const void *points, int 
         MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     }
     *n_features = m;
-    f.m = m;
-    f.n_blocks = 1;
-    f.blk_start[0] = 0;
-    f.blk_real[0] = m;
-    for (int b = 1; b <= 8; ++b) f.blk_start[b] = m;
-    f.has_cov = true;
+    f.single_block(m, true);
     return MLH_OK;
 }
 
@@ -1316,12 +1315,10 @@ int mlh_downsample_current_scan_pair(mlh_ctx *ctx, const void *surf_points, int 
                                      int n_lidar, const double cov_measurement[9], int with_ua, double trace_threshold, int32_t *n_surf_features,
                                      int32_t *n_corner_features)
 {
-    if (ctx) ++ctx->stage_epoch;      // (mlh_scan2map_end: a frame in flight may only be re-solved on the inputs it was submitted with)
+    if (ctx) ++ctx->stage_epoch;
     if (!ctx || !n_surf_features || !n_corner_features) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    const bool fused_pair = mem == MLH_MEM_DEVICE && !ctx->fused_dirty && stride_bytes == 16 && intensity_offset_bytes == 12 && n_surf > 0 && n_corner > 0 &&
-                            surf_points == ctx->fused[MLH_SURF].p && n_surf == ctx->fused_n[MLH_SURF] &&
-                            corner_points == ctx->fused[MLH_CORNER].p && n_corner == ctx->fused_n[MLH_CORNER];
+    const bool fused_pair = is_fused_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, intensity_offset_bytes, mem);
     if (fused_pair) {
         for (int k = 0; k < 2; ++k) { ctx->feat[k].matched = false; ctx->feat[k].m = 0; }
         int m[2] = {0, 0};
@@ -1329,12 +1326,7 @@ int mlh_downsample_current_scan_pair(mlh_ctx *ctx, const void *surf_points, int 
                                                   ctx->fused_minmax[MLH_CORNER], leaf_corner, stride_bytes, intensity_offset_bytes, ext_poses, ext_covs, n_lidar,
                                                   cov_measurement, with_ua, trace_threshold, &m[0], &m[1]);
         if (rc == MLH_OK) {
-            for (int k = 0; k < 2; ++k) {
-                FeatSet &f = ctx->feat[k];
-                f.m = m[k]; f.n_blocks = 1; f.blk_start[0] = 0; f.blk_real[0] = m[k];
-                for (int b = 1; b <= 8; ++b) f.blk_start[b] = m[k];
-                f.has_cov = true;
-            }
+            for (int k = 0; k < 2; ++k) ctx->feat[k].single_block(m[k], true);
             *n_surf_features = m[0];
             *n_corner_features = m[1];
             return MLH_OK;
@@ -2158,9 +2150,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
         if (rc) return rc;
         return mlh_scan2map(ctx, pose_inout, opts, nullptr);
     };
-    const bool fused_pair = mem == MLH_MEM_DEVICE && !ctx->fused_dirty && stride_bytes == 16 && intensity_offset_bytes == 12 && n_surf > 0 && n_corner > 0 &&
-                            surf_points == ctx->fused[MLH_SURF].p && n_surf == ctx->fused_n[MLH_SURF] &&
-                            corner_points == ctx->fused[MLH_CORNER].p && n_corner == ctx->fused_n[MLH_CORNER];
+    const bool fused_pair = is_fused_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, intensity_offset_bytes, mem);
     // the loop kernel's barrier wants every tile's workgroup resident: the BOUND's tiles, since the real count is not known here
     const int bound_tiles = tiles_of(n_surf) + tiles_of(n_corner);
     if (!fused_pair || !scan2map_has_maps(ctx) || distributed(ctx) || ctx->comm || opts->gf_method != MLH_GF_WO || !schedule_on(Schedule::LM_CONSUMER) ||
@@ -2177,14 +2167,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
                                           &m[0], &m[1], true);
     if (rc == MLH_ERR_UNSUPPORTED) return two_calls();
     if (rc) return rc;
-    auto stage_counts = [&](const int cnt[2]) {
-        for (int k = 0; k < 2; ++k) {
-            FeatSet &f = ctx->feat[k];
-            f.m = cnt[k]; f.n_blocks = 1; f.blk_start[0] = 0; f.blk_real[0] = cnt[k];
-            for (int b = 1; b <= 8; ++b) f.blk_start[b] = cnt[k];
-            f.has_cov = true;
-        }
-    };
+    auto stage_counts = [&](const int cnt[2]) { for (int k = 0; k < 2; ++k) ctx->feat[k].single_block(cnt[k], true); };
     if (m[0] >= 0) {                       // the thinning took a pipeline that waits for its counts anyway: the solve as usual
         stage_counts(m);
         *n_surf_features = m[0]; *n_corner_features = m[1];
@@ -2243,13 +2226,13 @@ static int track_stage_prev(mlh_ctx *ctx, int kind, const void *points, int stri
     TrackSet &T = ctx->track;
     MapGrid &g = T.grid[kind];
     g.built = false;
-    int rc = stage_points(ctx, points, stride_bytes, n, mem, -2, -1, g.raw, nullptr, ctx->tmp);
-    if (rc) return rc;
-    const unsigned char *d_src = (mem == MLH_MEM_HOST) ? ctx->tmp.as<unsigned char>() : static_cast<const unsigned char *>(points);
+    const Records r = records_of(points, stride_bytes, n, mem, intensity_offset_bytes);
+    const unsigned char *d_src;
+    int rc = records_check(ctx, "mlh_track_set_prev", r);
+    if (rc || (rc = stage_points(ctx, r, PACK_W_INDEX, g.raw, nullptr, ctx->tmp, &d_src))) return rc;
     // second copy in the original order with the ring id in w: what the scan-line walks stream over
     MLH_HIP(ctx, T.walk[kind].ensure(sizeof(float4) * size_t(n)));
-    MLH_LAUNCH(pack_points_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_src, stride_bytes, n, intensity_offset_bytes, -1,
-                       T.walk[kind].as<float4>(), (float4 *)nullptr);
+    pack_points_launch(ctx->stream, d_src, stride_bytes, n, intensity_offset_bytes, 0.f, -1, T.walk[kind].as<float4>(), nullptr);
     if ((rc = track_set_prev_rings(ctx, kind, d_src, stride_bytes, n, intensity_offset_bytes, host_bad))) return rc;
     g.n = n;
     g.min_match_sq_dis = distance_sq_threshold / float(TRACK_SHELLS * TRACK_SHELLS);   // cell edge = 1.001 * sqrt(thr) / TRACK_SHELLS
@@ -2288,8 +2271,9 @@ int mlh_track_set_prev(mlh_ctx *ctx, int kind, const void *points, int stride_by
 static int track_stage_cur(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int m, int intensity_offset_bytes, int mem)
 {
     TrackSet &T = ctx->track;
-    int rc = stage_points(ctx, points, stride_bytes, m, mem, intensity_offset_bytes >= 0 ? intensity_offset_bytes : -1, -1, T.cur[kind], nullptr, ctx->tmp);
-    if (rc) return rc;
+    const Records r = records_of(points, stride_bytes, m, mem, intensity_offset_bytes);
+    int rc = records_check(ctx, "mlh_track_set_cur", r);
+    if (rc || (rc = stage_points(ctx, r, intensity_offset_bytes >= 0 ? intensity_offset_bytes : PACK_W_ZERO, T.cur[kind], nullptr, ctx->tmp))) return rc;
     MLH_HIP(ctx, T.corr[kind].ensure(sizeof(Corr) * size_t(m)));
     T.m[kind] = m;
     return MLH_OK;
@@ -2354,18 +2338,15 @@ int mlh_track_set_from_scan(mlh_ctx *ctx, int which, float distance_sq_threshold
 int mlh_transform_to_end(mlh_ctx *ctx, void *points, int stride_bytes, int n, int intensity_offset_bytes, const double pose[7], int b_distortion,
                          float scan_period, int mem)
 {
-    if (!ctx || !points || !pose || n < 0 || stride_bytes < 16 || (stride_bytes & 3) || intensity_offset_bytes < 12 || !(scan_period > 0.f)) return MLH_ERR_INVALID;
+    if (!ctx || !points || !pose || intensity_offset_bytes < 12 || !(scan_period > 0.f)) return MLH_ERR_INVALID;
+    const Records r = records_of(points, stride_bytes, n, mem, intensity_offset_bytes);
+    { const int rc = records_check(ctx, "mlh_transform_to_end", r, true); if (rc) return rc; }
     if (n == 0) return MLH_OK;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    if (mem == MLH_MEM_DEVICE) return transform_to_end_launch(ctx, points, stride_bytes, n, intensity_offset_bytes, pose, b_distortion, scan_period);
-    const size_t bytes = size_t(n) * stride_bytes;
-    MLH_HIP(ctx, ctx->tmp.ensure(bytes));
-    MLH_HIP(ctx, hipMemcpyAsync(ctx->tmp.p, points, bytes, hipMemcpyHostToDevice, ctx->stream));
-    int rc = transform_to_end_launch(ctx, ctx->tmp.p, stride_bytes, n, intensity_offset_bytes, pose, b_distortion, scan_period);
-    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
-    MLH_HIP(ctx, hipMemcpyAsync(points, ctx->tmp.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return MLH_OK;
+    const unsigned char *dev;
+    { const int rc = records_stage(ctx, r, ctx->tmp, ctx->stream, &dev); if (rc) return rc; }
+    const int rc = transform_to_end_launch(ctx, const_cast<unsigned char *>(dev), stride_bytes, n, intensity_offset_bytes, pose, b_distortion, scan_period);
+    return mem == MLH_MEM_DEVICE ? rc : transform_finish(ctx, rc, r, points, dev);      // (a device cloud: nothing to wait for either way)
 }
 
 // Estimator::undistortMeasurements (estimator.cpp:376-410) for the scan the context holds: its points (laser_cloud, and with them the

@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <sched.h>
 #include "../../include/mloam_hip.h"
+#include "records.hpp"
 
 namespace mlh {
 
@@ -177,6 +178,12 @@ struct FeatSet {
     int nbr_stride = 5;
     bool has_cov = false;
     bool matched = false;
+    // the set is one pose block of `count` features (mlh_features_set and the thinning calls; mlh_features_set_block is the several-block form)
+    void single_block(int count, bool with_cov)
+    {
+        m = count; n_blocks = 1; blk_start[0] = 0; blk_real[0] = count; has_cov = with_cov;
+        for (int b = 1; b <= 8; ++b) blk_start[b] = count;
+    }
 };
 
 struct ScanBuf {
@@ -350,7 +357,9 @@ struct mlh_ctx {
         int loop_tiles = 0;            // > 0: the frame's LM loops were submitted as one launch each over this many workgroups (lm_loop_kernel)
     } solve_slot[2];
     int lm_lookahead_auto = 10;           // mlh_scan2map_begin(lm_lookahead = 0): the previous frame's largest LM iteration count + 2 (10 until a frame has been collected)
-    unsigned long long stage_epoch = 0;   // bumped by every call that restages a map or a feature set: a re-solve of an in-flight frame is only sound on unchanged inputs
+    // Bumped on entry by every call that restages a map or a feature set (also when it then fails: the set is disturbed). A frame in flight remembers the value it was
+    // submitted under (SolveSlot::epoch); mlh_scan2map_end re-solves it only while that value stands: a re-solve is only sound on the inputs the frame was submitted with.
+    unsigned long long stage_epoch = 0;
     bool solve_pending = false;
     bool map_read_unsynced = false;   // a launch that reads the current map set was enqueued and its call did not wait for it (mlh_pure_odom_add_matches)
     // mlh_scan_upload_ahead: the NEXT scan's points copied to the device on a stream of their own (the copy engine beside this frame's kernels); the mlh_scan_upload
@@ -476,6 +485,16 @@ int fail_launch(mlh_ctx *ctx, const char *kernel, hipError_t e);
             if (_le != hipSuccess) return ::mlh::fail_launch((ctx), _k, _le);      \
         }                                                                          \
     } while (0)
+
+// ---- intake of a caller's records (records.hpp, capi.hip): every entry point that takes a cloud validates it with records_check (MLH_ERR_INVALID, mlh_last_error
+// = "<entry>: bad <argument>") and reads it where records_stage says; the *_run functions below take records their entry point has validated
+int records_check(mlh_ctx *ctx, const char *entry, const mlh::Records &r, bool allow_empty = false);
+// *dev = where kernels read the records: the caller's own pointer (MLH_MEM_DEVICE), or `staging` + `at` bytes behind a copy enqueued on `st` (MLH_MEM_HOST; whoever
+// stages several clouds into one buffer sizes it first). Which buffer stages is the caller's choice: it encodes which streams may still be reading which buffer.
+int records_stage(mlh_ctx *ctx, const mlh::Records &r, mlh::DevBuf &staging, hipStream_t st, const unsigned char **dev, size_t at = 0);
+// the one pack kernel: records -> float4 {x, y, z, w} (+ the covariance diagonal when covd != nullptr); w = the f32 at byte offset w_off >= 0, or one of
+enum { PACK_W_ZERO = -1, PACK_W_INDEX = -2 /* the record's index, as int bits */, PACK_W_VALUE = -3 /* w_value */ };
+void pack_points_launch(hipStream_t st, const unsigned char *dev, int stride, int n, int w_off, float w_value, int cov_off, float4 *out, float4 *covd);
 
 // profiling brackets (HIP events on the context's stream)
 void prof_begin(mlh_ctx *ctx, int id);

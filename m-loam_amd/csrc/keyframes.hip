@@ -61,14 +61,6 @@ __device__ __forceinline__ int seg_of(const T *s, int n, int i, int T::*key)
     return lo;
 }
 
-__global__ __launch_bounds__(256) void kf_pack_kernel(const unsigned char *__restrict__ src, int stride, int ioff, int n, float4 *__restrict__ dst)
-{
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float *r = reinterpret_cast<const float *>(src + size_t(i) * stride);
-    dst[i] = make_float4(r[0], r[1], r[2], *reinterpret_cast<const float *>(src + size_t(i) * stride + ioff));
-}
-
 __global__ __launch_bounds__(256) void kf_uct_kernel(const float4 *__restrict__ store, const KfSeg *__restrict__ segs, int nseg, const double *__restrict__ par,
                                                      int n_lidar, Meas meas, int with_ua, double trace_thr, int N, float4 *__restrict__ stage,
                                                      int *__restrict__ keep, int *__restrict__ keep2)
@@ -271,13 +263,9 @@ static int keyframe_store(mlh_ctx *ctx, const double pose[7], const double cov[3
             if (packed) {
                 MLH_HIP(ctx, hipMemcpyAsync(dst + K.pts_used, src[k], sizeof(float4) * size_t(n[k]), hipMemcpyDeviceToDevice, st));
             } else {
-                const unsigned char *s = static_cast<const unsigned char *>(src[k]);
-                if (mem == MLH_MEM_HOST) {
-                    MLH_HIP(ctx, ctx->tmp.ensure(size_t(n[k]) * stride));
-                    MLH_HIP(ctx, hipMemcpyAsync(ctx->tmp.p, src[k], size_t(n[k]) * stride, hipMemcpyHostToDevice, st));
-                    s = ctx->tmp.as<unsigned char>();
-                }
-                MLH_LAUNCH(kf_pack_kernel, dim3((n[k] + 255) / 256), dim3(256), 0, st, s, stride, ioff, n[k], dst + K.pts_used);
+                const unsigned char *s;
+                { const int rc = records_stage(ctx, records_of(src[k], stride, n[k], mem), ctx->tmp, st, &s); if (rc) return rc; }
+                pack_points_launch(st, s, stride, n[k], ioff, 0.f, -1, dst + K.pts_used, nullptr);
             }
             K.pts_used += size_t(n[k]);
         }
@@ -292,11 +280,10 @@ static int keyframe_store(mlh_ctx *ctx, const double pose[7], const double cov[3
 int keyframe_save_run(mlh_ctx *ctx, const double pose[7], const double cov[36], const void *surf, int n_surf, const void *corner, int n_corner, int stride,
                       int ioff, int mem, int32_t *key_out)
 {
-    if (!pose || !cov || n_surf < 0 || n_corner < 0 || (n_surf > 0 && !surf) || (n_corner > 0 && !corner) || stride < 12 || (stride & 3) || ioff < 0 ||
-        ioff > stride - 4 || (ioff & 3) || (mem != MLH_MEM_HOST && mem != MLH_MEM_DEVICE) || bad_pose(pose))
-        return fail(ctx, MLH_ERR_INVALID, "mlh_keyframe_save: bad arguments");
+    if (!pose || !cov || ioff < 0 || bad_pose(pose)) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframe_save: bad arguments");
     const void *src[2] = {surf, corner};
     const int n[2] = {n_surf, n_corner};
+    for (int k = 0; k < 2; ++k) { const int rc = records_check(ctx, "mlh_keyframe_save", records_of(src[k], stride, n[k], mem, ioff), true); if (rc) return rc; }
     return keyframe_store(ctx, pose, cov, src, n, stride, ioff, mem, false, key_out);
 }
 

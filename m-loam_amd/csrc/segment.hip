@@ -699,17 +699,12 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
 {
     SegSetup S;
     if (!seg_setup(prm, S)) return fail(ctx, MLH_ERR_UNSUPPORTED, "ImageSegmenter is set up for 16, 32 or 64 vertical scans (image_segmenter.cpp:18-61)");
-    if (!points || n <= 0 || stride < 12 || (stride & 3)) return fail(ctx, MLH_ERR_INVALID, "bad point buffer");
     if (prm.horizon_scans <= 0 || prm.horizon_scans > 65535) return fail(ctx, MLH_ERR_INVALID, "horizon_scans out of range");
     hipStream_t st = ctx->stream;
     const int vs = S.vs, hs = S.hs, npx = vs * hs;
     SegBuf &B = ctx->seg;
-    const unsigned char *src = static_cast<const unsigned char *>(points);
-    if (mem == MLH_MEM_HOST) {
-        MLH_HIP(ctx, B.raw.ensure(size_t(n) * stride));
-        MLH_HIP(ctx, hipMemcpyAsync(B.raw.p, points, size_t(n) * stride, hipMemcpyHostToDevice, st));
-        src = B.raw.as<unsigned char>();
-    }
+    const unsigned char *src;
+    { const int rc = records_stage(ctx, records_of(points, stride, n, mem), B.raw, st, &src); if (rc) return rc; }
     MLH_HIP(ctx, B.pix.ensure(sizeof(int) * size_t(n)));
     MLH_HIP(ctx, B.owner.ensure(sizeof(int) * size_t(npx)));
     MLH_HIP(ctx, B.range.ensure(sizeof(float) * size_t(npx)));

@@ -324,14 +324,10 @@ __global__ __launch_bounds__(256) void compact_records_kernel(const unsigned cha
 int point_uncertainty_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int mem, const double *ext_poses,
                           const double *ext_covs, int n_lidar, const double cov_meas[9], double trace_thr, float *cov6_host, int *keep_host)
 {
-    if (!points || n <= 0 || stride < 12 || (stride & 3) || n_lidar <= 0 || n_lidar > 16) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
+    if (n_lidar <= 0 || n_lidar > 16) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     hipStream_t st = ctx->stream;
-    const unsigned char *src = static_cast<const unsigned char *>(points);
-    if (mem == MLH_MEM_HOST) {
-        MLH_HIP(ctx, ctx->tmp.ensure(size_t(n) * stride));
-        MLH_HIP(ctx, hipMemcpyAsync(ctx->tmp.p, points, size_t(n) * stride, hipMemcpyHostToDevice, st));
-        src = ctx->tmp.as<unsigned char>();
-    }
+    const unsigned char *src;
+    { const int rc = records_stage(ctx, records_of(points, stride, n, mem), ctx->tmp, st, &src); if (rc) return rc; }
     MLH_HIP(ctx, ctx->uct_buf.ensure(sizeof(double) * size_t(n_lidar) * 43 + sizeof(float) * 6 * size_t(n) + sizeof(int) * size_t(n) + 64));
     double *d_ext = ctx->uct_buf.as<double>();
     double *d_cov = d_ext + size_t(n_lidar) * 7;
@@ -401,16 +397,11 @@ int cloud_uct_associate_run(mlh_ctx *ctx, const void *points, int stride, int n,
                             const double pose_global[7], const double cov_global[36], const double *ext_poses, const double *ext_covs,
                             int n_lidar, const double cov_meas[9], int with_ua, double trace_thr, void *out, int *n_out, int mem)
 {
-    if (!points || n <= 0 || stride < 12 || (stride & 3) || n_lidar <= 0 || n_lidar > 16 || !out || !n_out || !pose_global || !ext_poses)
-        return fail(ctx, MLH_ERR_INVALID, "bad arguments");
+    if (n_lidar <= 0 || n_lidar > 16 || !out || !n_out || !pose_global || !ext_poses) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     if (with_ua && (!cov_global || !ext_covs || !cov_meas)) return fail(ctx, MLH_ERR_INVALID, "with_ua needs the pose / extrinsic / measurement covariances");
     hipStream_t st = ctx->stream;
-    const unsigned char *src = static_cast<const unsigned char *>(points);
-    if (mem == MLH_MEM_HOST) {
-        MLH_HIP(ctx, ctx->tmp.ensure(size_t(n) * stride));
-        MLH_HIP(ctx, hipMemcpyAsync(ctx->tmp.p, points, size_t(n) * stride, hipMemcpyHostToDevice, st));
-        src = ctx->tmp.as<unsigned char>();
-    }
+    const unsigned char *src;
+    { const int rc = records_stage(ctx, records_of(points, stride, n, mem), ctx->tmp, st, &src); if (rc) return rc; }
     // per-LiDAR constants: extrinsics (for pose_ext^-1), compound poses and their covariances
     std::vector<double> h(size_t(n_lidar) * (7 + 7 + 36), 0.0);
     double *h_ext = h.data(), *h_cp = h_ext + size_t(n_lidar) * 7, *h_cc = h_cp + size_t(n_lidar) * 7;
@@ -764,7 +755,7 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
     hipStream_t st = ctx->stream;
     VoxBuf &V = ctx->vox;
     const int n = n_surf + n_corner;
-    if (ctx->vox_member_order == 1 && n_lidar <= 4 && n_surf > 0 && n_corner > 0 && stride >= 12 && !(stride & 3) && leaf_surf > 0.f && leaf_corner > 0.f) {
+    if (ctx->vox_member_order == 1 && n_lidar <= 4 && n_surf > 0 && n_corner > 0 && leaf_surf > 0.f && leaf_corner > 0.f) {
         // ---- sort first (see above). The two grids' geometry as voxel_filter_run2 lays it out.
         VoxKeyGen G;
         const float *hb[2] = {bounds_surf, bounds_corner};

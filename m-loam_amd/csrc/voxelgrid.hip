@@ -413,16 +413,12 @@ __global__ __launch_bounds__(256) void vbounds_kernel(const unsigned char *src, 
 int voxel_filter_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off, float leaf,
                      float trace_thr, void *out_host, int *n_out, int mem, const float *known_bounds, bool sync_total, bool centroid_all)
 {
-    if (!points || n <= 0 || stride < 12 || (stride & 3) || !(leaf > 0.f) || !n_out) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
+    if (!(leaf > 0.f) || !n_out) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     // out_host == nullptr: the thinned records stay in ctx->vox.out (device) for the caller's next kernel
     hipStream_t st = ctx->stream;
     VoxBuf &V = ctx->vox;
-    const unsigned char *src = static_cast<const unsigned char *>(points);
-    if (mem == MLH_MEM_HOST) {
-        MLH_HIP(ctx, V.in.ensure(size_t(n) * stride));
-        MLH_HIP(ctx, hipMemcpyAsync(V.in.p, points, size_t(n) * stride, hipMemcpyHostToDevice, st));
-        src = V.in.as<unsigned char>();
-    }
+    const unsigned char *src;
+    { const int rc = records_stage(ctx, records_of(points, stride, n, mem), V.in, st, &src); if (rc) return rc; }
     // bounds -> min_b / div_b (getMinMax3D + the floor arithmetic of applyFilter :84-116)
     float hb[6] = {FLT_MAX, FLT_MAX, FLT_MAX, -FLT_MAX, -FLT_MAX, -FLT_MAX};
     if (known_bounds) {
@@ -522,7 +518,7 @@ int voxel_filter_run(mlh_ctx *ctx, const void *points, int stride, int n, int in
 int voxel_filter_run2(mlh_ctx *ctx, const void *src0, int n0, const float bounds0[6], float leaf0, const void *src1, int n1, const float bounds1[6],
                       float leaf1, int stride, int intensity_off, int *first_voxels_word)
 {
-    if (!src0 || !src1 || n0 <= 0 || n1 <= 0 || stride < 12 || (stride & 3) || !(leaf0 > 0.f) || !(leaf1 > 0.f)) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
+    if (!(leaf0 > 0.f) || !(leaf1 > 0.f)) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     hipStream_t st = ctx->stream;
     VoxBuf &V = ctx->vox;
     const float *hb[2] = {bounds0, bounds1};

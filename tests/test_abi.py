@@ -96,6 +96,18 @@ def test_std_sort_mt_equals_std_sort(tmp_path):
     assert " 0 mismatches" in out, out
 
 
+def test_records_validation(tmp_path):
+    """One validation for every caller's record buffer (m-loam_amd/csrc/records.hpp, pure host C++): the layouts in use are accepted; a field that does not fit
+    the stride or is misaligned, a bad stride, a null base with n > 0, n == 0 where the call does not allow it and an unknown mem are each named."""
+    import subprocess
+    ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    exe = str(tmp_path / "records_check")
+    subprocess.run(["g++", "-O2", "-std=c++17", "-Wall", "-Werror", "-I", os.path.join(ROOT, "m-loam_amd", "csrc"), "-o", exe,
+                    os.path.join(ROOT, "tests", "host", "records_check.cpp")], check=True)
+    out = subprocess.run([exe], check=True, capture_output=True, text=True).stdout
+    assert " 0 mismatches" in out, out
+
+
 def test_facade_window_degeneracy_policy(tmp_path, orc):
     """The facade's evalDegenracy(local_param_ids, window normal equations, frame_cnt, state) = Estimator::evalDegenracy (estimator.cpp:1598-1680):
     host code over mlh_eval_degeneracy, so it runs without a GPU. Held against the CPU restatement (which tests/test_oracle_ref_pin.py holds

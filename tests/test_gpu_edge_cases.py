@@ -1,5 +1,6 @@
 """Edge cases of the HIP path against the oracle: skipped / ragged / very long rings, tiny and non-tile-multiple feature sets,
 queries with no neighbours, maps too small to match, call-order and argument errors through the C-ABI status codes."""
+import ctypes as C
 import os
 
 import numpy as np
@@ -14,6 +15,17 @@ def ctx(mla):
     c = mla.Context(0)
     yield c
     c.close()
+
+
+def _p(a):
+    return a.ctypes.data_as(C.c_void_p)
+
+
+def _rejects_records(c, rc):
+    """a record buffer whose field does not fit the stride is refused by the one validation (MLH_ERR_INVALID = -1, the message names the argument) before
+    anything is enqueued"""
+    assert rc == -1, rc
+    assert "offset_bytes" in c.lib.mlh_last_error(c.h).decode()
 
 
 def _ring_scan(rng, lens, noise=0.02):
@@ -159,6 +171,19 @@ def test_voxel_filter_edge_cases(ctx, orc):
     far = np.zeros((4, 4), np.float32)
     far[1, 0] = 3.0e3; far[2, 1] = 3.0e3                            # (3e3 / 0.001)^2 voxels: the voxel index would overflow int32
     np.testing.assert_array_equal(ctx.voxel_filter(far, 0.001), far)
+    # the raw signature: offsets that exactly fit the 44-byte record (trace 40 + 4, covariance 16 + 24) give the result pinned above; one word further, a
+    # misaligned offset, or a covariance / trace in a record too short for it is an argument error
+    out, cnt = np.zeros_like(blob), C.c_int32(0)
+    vf = lambda a, stride, i_off, c_off, t_off: ctx.lib.mlh_voxel_filter(ctx.h, _p(a), stride, len(a), i_off, c_off, t_off, 0.4, 1.0, _p(out), C.byref(cnt), 0)
+    assert vf(blob, 44, 12, 16, 40) == 0
+    np.testing.assert_array_equal(out[:cnt.value], got)
+    for i_off, c_off, t_off in [(12, 16, 44), (12, 24, 40), (44, 16, 40), (12, 16, 41), (12, 18, 40), (14, 16, 40), (12, -1, 4096)]:
+        _rejects_records(ctx, vf(blob, 44, i_off, c_off, t_off))
+    out4 = np.zeros_like(one)
+    assert ctx.lib.mlh_voxel_filter(ctx.h, _p(one), 16, 1, 12, -1, -1, 0.4, 0.0, _p(out4), C.byref(cnt), 0) == 0 and cnt.value == 1
+    np.testing.assert_array_equal(out4, one)
+    for i_off, c_off, t_off in [(16, -1, -1), (12, 0, -1), (12, -1, 16)]:
+        _rejects_records(ctx, ctx.lib.mlh_voxel_filter(ctx.h, _p(one), 16, 1, i_off, c_off, t_off, 0.4, 0.0, _p(out4), C.byref(cnt), 0))
     with pytest.raises(Exception):
         ctx.voxel_filter(np.zeros((0, 4), np.float32), 0.4)
     with pytest.raises(Exception):
@@ -178,6 +203,29 @@ def test_association_and_odom_edge_cases(ctx, orc, synth):
     allp = ctx.cloud_uct_associate_to_map(pts, pg, cg, ext, ext_cov, meas, True, 1e9)
     assert len(allp) == 300
     np.testing.assert_allclose(allp[:, :3], pts[:, :3] + pg[:3].astype(np.float32), atol=1e-5)
+    # the raw signatures: offsets that exactly fit the record give the results pinned above (and, for the uncertainty, the oracle's); an intensity,
+    # covariance or trace that does not fit the stride is an argument error
+    out, cnt = np.zeros_like(pts), C.c_int32(0)
+    flat = [np.ascontiguousarray(a, np.float64) for a in (pg, cg, ext, ext_cov, meas)]
+    ua = lambda i_off, c_off, t_off: ctx.lib.mlh_cloud_uct_associate_to_map(ctx.h, _p(pts), 44, 300, i_off, c_off, t_off, _p(flat[0]), _p(flat[1]), _p(flat[2]),
+                                                                          _p(flat[3]), 2, _p(flat[4]), 1, 1e9, _p(out), C.byref(cnt), 0)
+    assert ua(12, 16, 40) == 0 and cnt.value == 300
+    np.testing.assert_array_equal(out, allp)
+    for i_off, c_off, t_off in [(12, 16, 44), (12, 24, 40), (44, 16, 40), (12, 16, 42), (12, 17, 40), (13, 16, 40)]:
+        _rejects_records(ctx, ua(i_off, c_off, t_off))
+    pts4 = np.ascontiguousarray(pts[:, :4])
+    cov6, keep = np.zeros((300, 6), np.float32), np.zeros(300, np.int32)
+    pu = lambda a, stride, i_off: ctx.lib.mlh_point_uncertainty(ctx.h, _p(a), stride, 300, i_off, 0, _p(flat[2]), _p(flat[3]), 2, _p(flat[4]), 1e9, _p(cov6), _p(keep))
+    assert pu(pts4, 16, 12) == 0 and keep.all()
+    cov_w, keep_w = ctx.point_uncertainty(pts4, ext, ext_cov, meas, 1e9)
+    np.testing.assert_array_equal(cov6, cov_w)
+    first = pts[:, 3] == 0                                        # LiDAR 0: identity extrinsics, so point_sel is the point itself
+    ref = orc.eval_point_uncertainty(pts4[first, :3], ext[0], ext_cov[0], meas)
+    ref6 = np.stack([ref[:, 0, 0], ref[:, 0, 1], ref[:, 0, 2], ref[:, 1, 1], ref[:, 1, 2], ref[:, 2, 2]], axis=1)
+    np.testing.assert_allclose(cov6[first], ref6, rtol=2e-5, atol=1e-7)      # (tests/test_gpu_parity.py::test_point_uncertainty_parity's bound)
+    assert pu(pts, 44, 40) == 0                                   # the last word of a longer record
+    for a, stride, i_off in [(pts4, 16, 16), (pts4, 16, 13), (pts4, 16, 4096), (pts, 44, 44), (pts, 44, 42)]:
+        _rejects_records(ctx, pu(a, stride, i_off))
     with pytest.raises(Exception):
         ctx.pure_odom_set(np.array([2], np.int32), np.zeros((1, 3)), np.zeros((1, 6)), np.array([0], np.int32), np.array([0], np.int32))
     with pytest.raises(Exception):
