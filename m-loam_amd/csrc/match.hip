@@ -22,6 +22,7 @@
 #include "dev_math.hpp"
 #include "solver_dev.hpp"
 #include "p2p_dev.hpp"
+#include "kparams.hpp"
 #include <hip/hip_ext.h>
 #include <cfloat>
 #include <cstdlib>
@@ -174,85 +175,6 @@ __device__ __forceinline__ bool in_laser_fov(const q4 &q, const d3 &t, float sx,
     return check1 < 0 && check2 > 0;
 }
 
-constexpr int MAX_BLOCKS = 8;
-
-struct KindP {
-    GridDev grid;
-    const float4 *feat;      // {x,y,z,intensity}; intensity < 0 marks a padding slot between pose blocks
-    const float4 *covd;      // {cxx,cyy,czz,_} or null
-    float4 *nbr;             // nbr_stride per feature: {x,y,z, sq-dist} of the k-th neighbour (w = +inf when missing)
-    Corr *corr;
-    double *r_out;           // nullable
-    double *J_out;           // nullable
-    int m;                   // feature slots (real + padding)
-    int tiles_a;             // correspondence-kernel tiles (TPB / lanes features each)
-    int lanes;               // lanes per query of the correspondence kernel for this kind (8 or 16)
-    int tiles_b;             // fit / linearise tiles (256 features each)
-    int nbr_stride;          // max K over the blocks
-    int blk_start[MAX_BLOCKS + 1];   // first slot of every pose block (multiples of 256), blk_start[n_blocks] = m
-};
-
-struct KParams {
-    KindP k[2];              // [MLH_SURF], [MLH_CORNER]; m = 0 when a kind is not part of the launch
-    double *partials;        // tiles_b(surf) + tiles_b(corner) records
-    SolverState *state;
-    int pose_sel;
-    uint32_t flags;
-    float min_match_sq_dis, min_plane_dis;
-    double huber_delta, cov_measurement_trace;
-    int has_lo, has_hi;      // multi-GPU ownership half-spaces (mlh_shard_set)
-    int own_mod, own_rem;    // ... or ownership by feature index: slot f belongs to this rank iff f % own_mod == own_rem (mlh_shard_set_features)
-    float lo[4], hi[4];
-    // pose blocks (BASELINE config 4: block 0 = body pose, block n = extrinsic of LiDAR n; 1 block otherwise)
-    int n_blocks;
-    int kb[MAX_BLOCKS];      // N_NEIGH per block (5 or 10)
-    double thre_b[MAX_BLOCKS];   // eigen threshold per block
-    int freeze_b[MAX_BLOCKS];    // 0: project the degenerate directions out (evalDegenracy); 1: do not update the block at all
-    // fused Gauss-Newton finish: the last workgroup to arrive sums the partials, solves and updates the pose(s)
-    int use_init;            // block 0's pose is init_pose (first iteration of a solve: no separate upload launch)
-    double init_pose[7];
-    HostPublish *publish;    // the finish of the last iteration hands the result to the host through pinned memory
-    unsigned long long publish_seq;
-    int knn_lanes;           // lanes per query of the correspondence kernel: 8 or 16 for every kind of the launch, 0 = per kind (KindP::lanes)
-    int finish;              // 0: none, 1: GN (reduce + solve + Plus), 2: reduce into SolverState::ne only (multi-GPU),
-                             // 3: Levenberg-Marquardt begin (fit kernel), 4: Levenberg-Marquardt step (linearize kernel)
-    int lm_max_it, lm_min_blocks;
-    int lm_expect_done;      // MatchArgs::lm_expect_done
-    unsigned *ticket;
-    IterStatDev *stat;       // n_blocks consecutive records, or null
-    // sharded over several ranks with the mailbox communicator: the finishing workgroup exchanges each block's summed record with the peers (one hop, inside
-    // this launch) before it solves -- a sharded Gauss-Newton iteration is the same two launches as an unsharded one. n_ranks <= 1: nothing is exchanged
-    P2pDev p2p;
-    // Gauss-Newton with the finish done by the consumer (MatchArgs::gn_iter): the correspondence kernel of iteration i >= 1 completes iteration i - 1 first
-    int pre_finish;          // 1: sum the pre_tiles records the previous fit launch left in `partials`, solve, Plus -> this iteration's pose
-    int pre_tiles;
-    int pre_from_init;       // the previous iteration's pose is init_pose (kernel arguments); otherwise *x_prev
-    int pre_from_state;      // ... or the state's own poses (x for block 0, xb[b] otherwise): iteration 1 of a solve over pose blocks
-    // (x_prev / x_next / pose0 are the poses of block 0; block b's sit 7 doubles x b further)
-    const double *x_prev;
-    double *x_next;          // the workgroup that serves tile 0 stores the new pose here (the fit kernel of the same iteration reads it as pose0)
-    const double *pose0;     // block 0's pose of this launch when it is neither init_pose nor the state's x / cand (iterations >= 1 of a deferred-finish solve)
-    int warm;                // the neighbour records hold the previous iteration's neighbours of the same features in the same map
-    // pre_finish == 2 (MatchArgs::pre_final): the records are the PREVIOUS solve's last iteration; its pose is published from here, then this frame's start pose chained from it
-    HostPublish *pre_publish;
-    unsigned long long pre_publish_seq;
-    double pre_thre;
-    int pre_freeze;
-    double chain_prev[7], chain_cur[7];
-    // Levenberg-Marquardt with the step done by the consumer (lm_consume_kernel): the records the previous launch left, the state its writer left, the state this
-    // launch's writer leaves
-    const double *partials_in;
-    const LmState *lm_in;
-    LmState *lm_out;
-    // feature counts read on the DEVICE (mlh_downsample_scan2map: the solve is enqueued behind the thinning without the host reading what the thinning kept): the
-    // launches are sized for an upper bound (KindP::m, tiles_*), the DEVM kernel variants take the counts -- and the tiles that follow from them -- from here
-    const int *m_dev;        // [2]: surf, corner
-    unsigned long long loop_timeout_ticks;   // lm_loop_kernel: a barrier wait longer than this (100 MHz wall clock) gives the loop up (mlh_ctx::caps)
-    unsigned long long *loop_tagged;   // lm_loop_kernel: two sets of tagged records (64 words per tile), or null: records + grid barrier (MLH_LOOP_TAGGED=0)
-    unsigned loop_tag_base;  // this launch's tag: (launch number << 8); the iteration goes into the low byte
-    int debug_stall;         // MLH_DEBUG_LOOP_STALL=1 (tests): one workgroup of lm_loop_kernel never arrives at its second barrier -- the loop must end with the error bit, not hang
-};
-
 __device__ __forceinline__ int block_of_slot(const KindP &K, int n_blocks, int f)
 {
     int b = 0;
@@ -270,15 +192,59 @@ __device__ __forceinline__ void load_pose(const KParams &P, int b, q4 &q, d3 &t)
     if (P.use_init && b == 0) {            // uniform: straight from the kernel-argument segment
         t = d3{P.init_pose[0], P.init_pose[1], P.init_pose[2]};
         q = q4{P.init_pose[3], P.init_pose[4], P.init_pose[5], P.init_pose[6]};
-    } else if (P.pose0) {                  // iteration >= 1 of a deferred-finish solve: the slot this iteration's correspondence launch filled (one per pose block)
-        const double *pose = P.pose0 + 7 * b;
-        t = d3{pose[0], pose[1], pose[2]};
-        q = q4{pose[3], pose[4], pose[5], pose[6]};
-    } else {
-        const double *pose = block_pose(P, b);
+    } else {                               // where the host found this launch's poses (KParams::pose_b0 / pose_bn): one trip behind the arguments
+        const double *pose = b == 0 ? P.pose_b0 : P.pose_bn + 7 * b;
         t = d3{pose[0], pose[1], pose[2]};
         q = q4{pose[3], pose[4], pose[5], pose[6]};
     }
+}
+
+// ---- kernel arguments: one batch of scalar loads at kernel entry
+// Left alone, the compiler fetches an argument where it is first used: inside the branch that needs it, behind whatever that branch already waited for. The fit
+// kernel then pays seven scalar-memory round trips in series before its first vector load (profiles/r07_launch_floor.txt prices a trip at ~0.16 us on the
+// chain). Each kernel of the Gauss-Newton path therefore names what its path reads as the inputs of ONE empty asm statement at entry: all of them have to be in
+// registers there, so their loads are issued together and wait once, and a later use of the same field is the same value, whatever branch it sits in. (One
+// statement, not one per value: the scheduler places a load between two statements if it likes, behind the first one's wait. Neighbouring words go in as one
+// vector operand -- a statement takes 30.)
+typedef int arg_i4 __attribute__((ext_vector_type(4)));
+typedef float arg_f4 __attribute__((ext_vector_type(4)));
+typedef float arg_f2 __attribute__((ext_vector_type(2)));
+typedef double arg_d2 __attribute__((ext_vector_type(2)));
+typedef double arg_d4 __attribute__((ext_vector_type(4)));
+#define MLH_KIND_COUNTS(K_) arg_i4{(K_).m, (K_).tiles_a, (K_).tiles_b, (K_).nbr_stride}
+#define MLH_WORDS(P_) arg_i4{int((P_).flags), (P_).own_mode, (P_).n_blocks, (P_).use_init}
+#define MLH_GRID_ORIGIN(K_) arg_f4{(K_).grid.ox, (K_).grid.oy, (K_).grid.oz, (K_).grid.inv_h}
+#define MLH_GRID_DIMS(K_) arg_i4{(K_).grid.nx, (K_).grid.ny, (K_).grid.nz, (K_).grid.n}
+
+// the workgroup's kind, selected field by field from the two copies the entry batch left in registers (an index into the argument segment instead would be a
+// second round trip behind the tile counts)
+__device__ __forceinline__ KindL pick_kind(bool second, const KindL &a, const KindL &b)
+{
+    KindL k;
+    k.feat = second ? b.feat : a.feat;
+    k.covd = second ? b.covd : a.covd;
+    k.nbr = second ? b.nbr : a.nbr;
+    k.corr = second ? b.corr : a.corr;
+    k.r_out = second ? b.r_out : a.r_out;
+    k.J_out = second ? b.J_out : a.J_out;
+    k.m = second ? b.m : a.m;
+    k.tiles_a = second ? b.tiles_a : a.tiles_a;
+    k.tiles_b = second ? b.tiles_b : a.tiles_b;
+    k.nbr_stride = second ? b.nbr_stride : a.nbr_stride;
+    k.lanes = second ? b.lanes : a.lanes;
+    k.pad_ = 0;
+    k.grid.sorted = second ? b.grid.sorted : a.grid.sorted;
+    k.grid.raw = second ? b.grid.raw : a.grid.raw;
+    k.grid.cell_start = second ? b.grid.cell_start : a.grid.cell_start;
+    k.grid.ox = second ? b.grid.ox : a.grid.ox;
+    k.grid.oy = second ? b.grid.oy : a.grid.oy;
+    k.grid.oz = second ? b.grid.oz : a.grid.oz;
+    k.grid.inv_h = second ? b.grid.inv_h : a.grid.inv_h;
+    k.grid.nx = second ? b.grid.nx : a.grid.nx;
+    k.grid.ny = second ? b.grid.ny : a.grid.ny;
+    k.grid.nz = second ? b.grid.nz : a.grid.nz;
+    k.grid.n = second ? b.grid.n : a.grid.n;
+    return k;
 }
 
 // pointAssociateToMap (utility.h:103-117): f64 q*p + t, stored to f32
@@ -288,13 +254,20 @@ __device__ __forceinline__ void associate_to_map(const q4 &q, const d3 &t, const
     sx = float(w.x + t.x); sy = float(w.y + t.y); sz = float(w.z + t.z);
 }
 
-__device__ __forceinline__ bool owns(const KParams &P, int f, float sx, float sy, float sz)
+// (own_mode: KParams::own_mode, as the caller holds it)
+__device__ __forceinline__ bool owns(const KParams &P, int own_mode, int f, float sx, float sy, float sz)
 {
-    bool own = P.own_mod <= 1 || (f % P.own_mod) == P.own_rem;
-    if (P.has_lo) own = own && ((((P.lo[0] * sx + P.lo[1] * sy) + P.lo[2] * sz) + P.lo[3]) >= 0.f);
-    if (P.has_hi) own = own && ((((P.hi[0] * sx + P.hi[1] * sy) + P.hi[2] * sz) + P.hi[3]) < 0.f);
+    if (own_mode == 0) return true;            // one rank (uniform): one word of the arguments
+    // sharded: the ownership fields in one batch -- both planes evaluated whether set or not (an unset one is all zeros), so that no field waits inside a branch
+    const int own_mod = P.own_mod, own_rem = P.own_rem;
+    const float l0 = P.lo[0], l1 = P.lo[1], l2 = P.lo[2], l3 = P.lo[3], h0 = P.hi[0], h1 = P.hi[1], h2 = P.hi[2], h3 = P.hi[3];
+    bool own = !(own_mode & 4) || (f % (own_mod > 1 ? own_mod : 1)) == own_rem;
+    const bool in_lo = (((l0 * sx + l1 * sy) + l2 * sz) + l3) >= 0.f, in_hi = (((h0 * sx + h1 * sy) + h2 * sz) + h3) < 0.f;
+    own = own && (!(own_mode & 1) || in_lo);
+    own = own && (!(own_mode & 2) || in_hi);
     return own;
 }
+__device__ __forceinline__ bool owns(const KParams &P, int f, float sx, float sy, float sz) { return owns(P, P.own_mode, f, sx, sy, sz); }
 
 // ---- correspondence kernel: 8 lanes per feature, 32 features per workgroup, both feature kinds in one launch
 
@@ -331,7 +304,7 @@ __device__ __forceinline__ bool owns(const KParams &P, int f, float sx, float sy
     } while (0)
 
 template <int K, int G>
-__device__ __forceinline__ void knn_feature(const KParams &P, const KindP &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run)
+__device__ __forceinline__ void knn_feature(const KParams &P, const KindL &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run)
 {
     unsigned long long keys[K];
     if constexpr (G == 32) knn_group_bounded<K, 32, true>(Kd.grid, sx, sy, sz, gl, lds_run, 0x7f800000u, keys);
@@ -346,7 +319,7 @@ __device__ __forceinline__ void knn_feature(const KParams &P, const KindP &Kd, i
 // iteration left -- K points of the SAME map. Their largest squared distance from the query's new position bounds the K-th neighbour's from above, so the search
 // is a single walk over the cells within that bound (knn_group_bounded). A feature that had fewer than K neighbours (w = +inf) searches as before.
 template <int K, int G, int NREC>
-__device__ __forceinline__ void knn_feature_warm(const KParams &P, const KindP &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run, const float4 (&old)[NREC])
+__device__ __forceinline__ void knn_feature_warm(const KParams &P, const KindL &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run, const float4 (&old)[NREC])
 {
     unsigned bits = 0u;
 #pragma unroll
@@ -370,7 +343,7 @@ __device__ __forceinline__ void knn_feature_warm(const KParams &P, const KindP &
 // MB = more than one pose block in the launch (config 4); without it the block bookkeeping (a per-lane block index and the
 // per-block K lookup it drags along) compiles away
 template <int G, bool MB, bool K10, bool PRE, bool WARM>
-__device__ __forceinline__ void knn_features_body(const KParams &P, const KindP &K, int tile, int *s_run, const double *s_pose, int m_feat)
+__device__ __forceinline__ void knn_features_body(const KParams &P, const KindL &K, int kind, int own_mode, int tile, int *s_run, const double *s_pose, int m_feat)
 {
     constexpr int FPB = TPB / G;          // queries per workgroup
     constexpr int RUNW = 2 * KNN_RUN_WORDS;
@@ -380,7 +353,7 @@ __device__ __forceinline__ void knn_features_body(const KParams &P, const KindP 
     if (f >= m_feat) return;
     const float4 fp = K.feat[f];
     if (fp.w < 0.f) return;               // padding slot
-    const int b = MB ? block_of_slot(K, P.n_blocks, f) : 0;
+    const int b = MB ? block_of_slot(P.k[kind], P.n_blocks, f) : 0;
     constexpr int NREC = WARM ? ((K10 ? 10 : 5) + G - 1) / G : 1;
     float4 old[NREC];
     if constexpr (WARM) {                  // requested together with the feature, before the pose is known
@@ -402,7 +375,7 @@ __device__ __forceinline__ void knn_features_body(const KParams &P, const KindP 
     float sx, sy, sz;
     associate_to_map(q, t, fp, sx, sy, sz);
     MLH_KSTAGE(1);
-    if (!owns(P, f, sx, sy, sz)) return;     // uniform over the lane group
+    if (!owns(P, own_mode, f, sx, sy, sz)) return;     // uniform over the lane group
     // K10: some pose block of the launch asks for 10 neighbours (buildCalibMap's non-reference LiDARs); without it the K = 10 search is not
     // even compiled in, so the ordinary frame's kernel keeps the K = 5 register footprint
     if constexpr (WARM) {
@@ -424,12 +397,12 @@ __device__ __forceinline__ void knn_features_body(const KParams &P, const KindP 
 template <int MODE, bool MB = false>
 __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_pose, double *f_ne, double *f_cnt2, double *f_scratch)
 {
+    // (the pose is requested here and stored behind the records' sum: its trip and the records' run together, not one behind the other)
+    double pose_v = 0.0;
     if (threadIdx.x < 7) {
-        double v;
-        if (P.pre_from_init) v = P.init_pose[threadIdx.x];
-        else if (MB && P.pre_from_state) v = (b == 0 ? P.state->x : P.state->xb[b])[threadIdx.x];
-        else v = P.x_prev[7 * b + threadIdx.x];
-        s_pose[threadIdx.x] = v;
+        if (P.pre_from_init) pose_v = P.init_pose[threadIdx.x];
+        else if (MB && P.pre_from_state) pose_v = (b == 0 ? P.state->x : P.state->xb[b])[threadIdx.x];
+        else pose_v = P.x_prev[7 * b + threadIdx.x];
     }
     {
         constexpr int NS = TPB / 32, U = 12;
@@ -457,6 +430,7 @@ __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_p
             for (int u = 0; u < U; ++u) ch[u & 3] += tv[u];
         }
         f_scratch[sl * 32 + c] = (ch[0] + ch[1]) + (ch[2] + ch[3]);
+        if (threadIdx.x < 7) s_pose[threadIdx.x] = pose_v;
         __syncthreads();
         if (threadIdx.x < 32) {
             double tsum = 0.0;
@@ -498,12 +472,47 @@ __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
 {
     __shared__ int s_run[(G == 16) ? (TPB / 16) * 2 * KNN_RUN_WORDS : (TPB / 8) * 2 * KNN_RUN_WORDS];
     __shared__ double s_pose[PRE ? 8 : 1];
-    int m0 = P.k[0].m, m1 = P.k[1].m, ta0 = P.k[0].tiles_a;
-    int total = P.k[0].tiles_a + P.k[1].tiles_a;
+    // every argument this launch's path reads -- tile counts, the prologue's, the search's of both kinds, ownership --: one batch, one wait
+    const KindL k0 = P.k[0], k1 = P.k[1];
+    {
+        const arg_i4 c0 = MLH_KIND_COUNTS(k0), c1 = MLH_KIND_COUNTS(k1), d0 = MLH_GRID_DIMS(k0), d1 = MLH_GRID_DIMS(k1), w = MLH_WORDS(P);
+        const arg_f4 o0 = MLH_GRID_ORIGIN(k0), o1 = MLH_GRID_ORIGIN(k1);
+        const int kb0 = P.kb[0];
+#define MLH_KNN_KINDS "s"(k0.feat), "s"(k0.nbr), "s"(c0), "s"(k0.lanes), "s"(k0.grid.sorted), "s"(k0.grid.raw), "s"(k0.grid.cell_start), "s"(o0), "s"(d0), "s"(k1.feat), "s"(k1.nbr), \
+                      "s"(c1), "s"(k1.lanes), "s"(k1.grid.sorted), "s"(k1.grid.raw), "s"(k1.grid.cell_start), "s"(o1), "s"(d1), "s"(w), "s"(kb0)
+        if constexpr (PRE == 0) {
+            const arg_d4 ip0{P.init_pose[0], P.init_pose[1], P.init_pose[2], P.init_pose[3]};
+            const arg_d2 ip1{P.init_pose[4], P.init_pose[5]};
+            const double ip2 = P.init_pose[6];
+            const double *const pose_b0 = P.pose_b0, *const pose_bn = P.pose_bn;
+            asm volatile("; kernel arguments in registers" ::MLH_KNN_KINDS, "s"(ip0), "s"(ip1), "s"(ip2), "s"(pose_b0), "s"(pose_bn));
+        } else {
+            // (a start pose in the arguments is read per lane, by index: nothing to name)
+            const double *const x_prev = P.x_prev;
+            double *const x_next = P.x_next, *const partials = P.partials;
+            const int pre_tiles = P.pre_tiles, pre_from_init = P.pre_from_init;
+            if constexpr (PRE == 1) {
+                const double thre0 = P.thre_b[0];
+                const int freeze0 = P.freeze_b[0];
+                asm volatile("; kernel arguments in registers" ::MLH_KNN_KINDS, "s"(x_prev), "s"(x_next), "s"(partials), "s"(pre_tiles), "s"(pre_from_init), "s"(thre0), "s"(freeze0));
+            } else {
+                SolverState *const state = P.state;
+                HostPublish *const pre_publish = P.pre_publish;
+                const unsigned long long pre_publish_seq = P.pre_publish_seq;
+                const double pre_thre = P.pre_thre;
+                const int pre_freeze = P.pre_freeze;
+                asm volatile("; kernel arguments in registers" ::MLH_KNN_KINDS, "s"(x_prev), "s"(x_next), "s"(partials), "s"(pre_tiles), "s"(pre_from_init), "s"(state), "s"(pre_publish),
+                             "s"(pre_publish_seq), "s"(pre_thre), "s"(pre_freeze));
+            }
+        }
+#undef MLH_KNN_KINDS
+    }
+    int m0 = k0.m, m1 = k1.m, ta0 = k0.tiles_a;
+    int total = k0.tiles_a + k1.tiles_a;
     if constexpr (DEVM) {
         static_assert(G == 0 && !MB && PRE == 0, "device-side counts: per-kind lanes, one block, no prologue");
         m0 = P.m_dev[0]; m1 = P.m_dev[1];
-        const int f0 = TPB / P.k[0].lanes, f1 = TPB / P.k[1].lanes;
+        const int f0 = TPB / k0.lanes, f1 = TPB / k1.lanes;
         ta0 = (m0 + f0 - 1) / f0;
         total = ta0 + (m1 + f1 - 1) / f1;
         if ((int(blockIdx.x) >> 3) >= ((total + 7) >> 3)) return;     // (xcd_tile is a bijection only on the first 8 * ceil(total / 8) workgroups)
@@ -513,6 +522,15 @@ __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
 #ifdef MLH_KNN_HEAVY_FIRST
     tile = total - 1 - tile;       // A/B build only (scripts/build_variant.py): the corner tiles -- the queries with the most candidates -- are dispatched first
 #endif
+    const int kind = tile >= ta0 ? 1 : 0;
+    // this workgroup's kind and the ownership word, as values the compiler cannot fetch again: behind the prologue it would rather re-read both kinds' arguments
+    // and select once more than keep the selection in registers
+    KindL K = pick_kind(kind != 0, k0, k1);
+    int own_mode = P.own_mode;
+    if constexpr (PRE != 0 && !MB) {
+        asm volatile("" : "+s"(K.feat), "+s"(K.nbr), "+s"(K.nbr_stride), "+s"(K.lanes), "+s"(K.grid.sorted), "+s"(K.grid.raw), "+s"(K.grid.cell_start), "+s"(own_mode));
+        // (the grid's origin and dimensions are left out: the compiler selects those four-word groups as vectors, on the vector unit)
+    }
     if constexpr (PRE != 0) {
         __shared__ double f_ne[NE_STRIDE], f_cnt2[2], f_scratch[(TPB / 32) * 32];
         int pb = 0;
@@ -520,12 +538,11 @@ __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
         if constexpr (MB) {
             // pose blocks start on 256-slot boundaries and a workgroup serves 16 or 32 consecutive slots of ONE kind: all of them in one block. The block's pose is
             // written by the workgroup of its first surf tile (the host defers a solve over blocks only when every block has surf features)
-            const int kk = tile >= P.k[0].tiles_a ? 1 : 0;
-            const int tk = kk ? tile - P.k[0].tiles_a : tile;
-            const int lanes = (G == 0) ? P.k[kk].lanes : G;
+            const int tk = kind ? tile - ta0 : tile;
+            const int lanes = (G == 0) ? K.lanes : G;
             const int f0 = tk * (TPB / lanes);
-            pb = block_of_slot(P.k[kk], P.n_blocks, f0);
-            writer = kk == 0 && f0 == P.k[0].blk_start[pb];
+            pb = block_of_slot(P.k[kind], P.n_blocks, f0);
+            writer = kind == 0 && f0 == P.k[0].blk_start[pb];
         }
         gn_prologue<PRE, MB>(P, pb, s_pose, f_ne, f_cnt2, f_scratch);
         if constexpr (PRE == 2) {
@@ -545,16 +562,14 @@ __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
         }
         if (writer && threadIdx.x < 7) P.x_next[7 * pb + threadIdx.x] = s_pose[threadIdx.x];
     }
-    const int kind = tile >= ta0 ? 1 : 0;
     if (kind) tile -= ta0;
-    const KindP &K = P.k[kind];
     const int m_feat = kind ? m1 : m0;
     if constexpr (G == 0) {
-        if (K.lanes == 8) knn_features_body<8, MB, K10, PRE != 0, WARM>(P, K, tile, s_run, s_pose, m_feat);
-        else if (K.lanes == 32) knn_features_body<32, MB, K10, PRE != 0, WARM>(P, K, tile, s_run, s_pose, m_feat);
-        else knn_features_body<16, MB, K10, PRE != 0, WARM>(P, K, tile, s_run, s_pose, m_feat);
+        if (K.lanes == 8) knn_features_body<8, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
+        else if (K.lanes == 32) knn_features_body<32, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
+        else knn_features_body<16, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
     } else {
-        knn_features_body<G, MB, K10, PRE != 0, WARM>(P, K, tile, s_run, s_pose, m_feat);
+        knn_features_body<G, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
     }
 }
 
@@ -617,15 +632,16 @@ __device__ __forceinline__ double feature_weight(const KParams &P, const KindP &
 }
 
 // the same from a covariance diagonal the caller already holds in registers (requested together with the feature: no dependent trip)
-__device__ __forceinline__ double feature_weight_pref(const KParams &P, const KindP &K, const float4 &cd)
+__device__ __forceinline__ double feature_weight_pref(uint32_t flags, double cov_measurement_trace, const KindL &K, const float4 &cd)
 {
-    double trace = P.cov_measurement_trace;
-    if ((P.flags & MLH_FLAG_WITH_UA)) {
+    double trace = cov_measurement_trace;
+    if ((flags & MLH_FLAG_WITH_UA)) {
         trace = 0.0;
         if (K.covd) trace = (double(cd.x) + double(cd.y)) + double(cd.z);
     }
     return sqrt_info_of(trace);
 }
+__device__ __forceinline__ double feature_weight_pref(const KParams &P, const KindL &K, const float4 &cd) { return feature_weight_pref(P.flags, P.cov_measurement_trace, K, cd); }
 
 // Fused tail: the last workgroup to arrive (agent-scope release/acquire around an atomic ticket) sums the partial records
 // in fixed order, runs the degeneracy test + the 6x6 solve + Plus for every pose block and re-arms the ticket: a GN iteration
@@ -764,14 +780,19 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
 
 // v: the feature's neighbour records {x, y, z, sq-dist}, already in registers (the kernel requests them together with the feature itself)
 template <int K, int KV>
-__device__ __forceinline__ bool fit_feature(const KParams &P, int kind, const float4 (&v)[KV], float (&coef)[6])
+__device__ __forceinline__ bool fit_feature(float min_match_sq_dis, float min_plane_dis, int kind, const float4 (&v)[KV], float (&coef)[6])
 {
     static_assert(K <= KV, "neighbour buffer too small");
-    if (!(v[K - 1].w < P.min_match_sq_dis)) return false;     // sq_dis[k-1] < MIN_MATCH_SQ_DIS (hpp:667/814)
+    if (!(v[K - 1].w < min_match_sq_dis)) return false;     // sq_dis[k-1] < MIN_MATCH_SQ_DIS (hpp:667/814)
     float ax[K], ay[K], az[K];
 #pragma unroll
     for (int j = 0; j < K; ++j) { ax[j] = v[j].x; ay[j] = v[j].y; az[j] = v[j].z; }
-    return kind == MLH_SURF ? fit_plane<K>(ax, ay, az, P.min_plane_dis, coef) : fit_line<K>(ax, ay, az, coef);
+    return kind == MLH_SURF ? fit_plane<K>(ax, ay, az, min_plane_dis, coef) : fit_line<K>(ax, ay, az, coef);
+}
+template <int K, int KV>
+__device__ __forceinline__ bool fit_feature(const KParams &P, int kind, const float4 (&v)[KV], float (&coef)[6])
+{
+    return fit_feature<K, KV>(P.min_match_sq_dis, P.min_plane_dis, kind, v, coef);
 }
 
 // ---- fit + gates + residual/Jacobian + normal-equation reduction: one lane per feature, both kinds in one launch
@@ -783,8 +804,32 @@ template <int KMAX, bool LM, bool FIN = true, bool DEVM = false>
 __global__ __launch_bounds__(TPB) void fit_linearize_kernel(KParams P)
 {
     __shared__ double s_red[4 * 32];
-    int m0 = P.k[0].m, m1 = P.k[1].m, tb0 = P.k[0].tiles_b;
-    int total = P.k[0].tiles_b + P.k[1].tiles_b;
+    // every argument the taken path reads, both kinds': one batch, one wait (the pose, behind its pointer, leaves as a vector load together with the feature's)
+    const KindL k0 = P.k[0], k1 = P.k[1];
+    {
+        const arg_i4 c0 = MLH_KIND_COUNTS(k0), c1 = MLH_KIND_COUNTS(k1), w = MLH_WORDS(P);
+        const arg_f2 gate{P.min_match_sq_dis, P.min_plane_dis};
+        const arg_d2 loss{P.huber_delta, P.cov_measurement_trace};
+        const arg_d4 ip0{P.init_pose[0], P.init_pose[1], P.init_pose[2], P.init_pose[3]};
+        const arg_d2 ip1{P.init_pose[4], P.init_pose[5]};
+        const double ip2 = P.init_pose[6];
+        double *const partials = P.partials;
+        const double *const pose_b0 = P.pose_b0, *const pose_bn = P.pose_bn;
+        const int finish = P.finish;
+        asm volatile("; kernel arguments in registers" ::"s"(k0.feat), "s"(k0.covd), "s"(k0.nbr), "s"(k0.corr), "s"(k0.r_out), "s"(k0.J_out), "s"(c0), "s"(k1.feat), "s"(k1.covd),
+                     "s"(k1.nbr), "s"(k1.corr), "s"(k1.r_out), "s"(k1.J_out), "s"(c1), "s"(w), "s"(gate), "s"(loss), "s"(ip0), "s"(ip1), "s"(ip2), "s"(partials), "s"(pose_b0),
+                     "s"(pose_bn), "s"(finish));
+    }
+    // what the kernel's tail reads (gates, weight, loss, the record's address), as values the compiler cannot fetch again: it would rather re-read an argument behind
+    // the fit than keep it in a register, one more scalar round trip each time
+    uint32_t flags = P.flags;
+    int own_mode = P.own_mode;
+    float min_match_sq_dis = P.min_match_sq_dis, min_plane_dis = P.min_plane_dis;
+    double huber_delta = P.huber_delta, cov_measurement_trace = P.cov_measurement_trace;
+    double *partials = P.partials;
+    asm volatile("" : "+s"(flags), "+s"(own_mode), "+s"(min_match_sq_dis), "+s"(min_plane_dis), "+s"(huber_delta), "+s"(cov_measurement_trace), "+s"(partials));
+    int m0 = k0.m, m1 = k1.m, tb0 = k0.tiles_b;
+    int total = k0.tiles_b + k1.tiles_b;
     if constexpr (DEVM) {            // (the counts from the device, knn_features_kernel<.., DEVM>)
         m0 = P.m_dev[0]; m1 = P.m_dev[1];
         tb0 = (m0 + TPB - 1) / TPB;
@@ -795,11 +840,11 @@ __global__ __launch_bounds__(TPB) void fit_linearize_kernel(KParams P)
     if (gtile >= total) return;
     const int kind = gtile >= tb0 ? 1 : 0;
     const int tile = kind ? gtile - tb0 : gtile;
-    const KindP &K = P.k[kind];
+    const KindL K = pick_kind(kind != 0, k0, k1);
     const int m_feat = kind ? m1 : m0;
     MLH_STAGE(gtile, 0);
     const int f = tile * TPB + threadIdx.x;
-    const int b = block_of_slot(K, P.n_blocks, tile * TPB);       // uniform over the workgroup (blocks start on tile boundaries)
+    const int b = P.n_blocks > 1 ? block_of_slot(P.k[kind], P.n_blocks, tile * TPB) : 0;       // uniform over the workgroup (blocks start on tile boundaries)
     q4 q;
     d3 t;
     load_pose(P, b, q, t);
@@ -820,14 +865,14 @@ __global__ __launch_bounds__(TPB) void fit_linearize_kernel(KParams P)
         const float4 *nb = K.nbr + size_t(f) * K.nbr_stride;
 #pragma unroll
         for (int j = 0; j < KMAX; ++j) nbv[j] = nb[j];
-        if ((P.flags & MLH_FLAG_WITH_UA) && K.covd) cdv = K.covd[f];       // the weight's covariance diagonal rides in the same trip
+        if ((flags & MLH_FLAG_WITH_UA) && K.covd) cdv = K.covd[f];       // the weight's covariance diagonal rides in the same trip
         MLH_STAGE(gtile, 5);
-        const bool need_pos = P.has_lo || P.has_hi || (P.flags & MLH_FLAG_CHECK_FOV);
+        const bool need_pos = (own_mode & 3) || (flags & MLH_FLAG_CHECK_FOV);
         float sx = 0.f, sy = 0.f, sz = 0.f;
         if (need_pos) associate_to_map(q, t, fp, sx, sy, sz);
-        if (fp.w >= 0.f && owns(P, f, sx, sy, sz)) {
-            valid = (KMAX == 10 && P.kb[b] == 10) ? fit_feature<KMAX, KMAX>(P, kind, nbv, coef) : fit_feature<5, KMAX>(P, kind, nbv, coef);
-            if (valid && (P.flags & MLH_FLAG_CHECK_FOV)) valid = in_laser_fov(q, t, sx, sy, sz);
+        if (fp.w >= 0.f && owns(P, own_mode, f, sx, sy, sz)) {
+            valid = (KMAX == 10 && P.kb[b] == 10) ? fit_feature<KMAX, KMAX>(min_match_sq_dis, min_plane_dis, kind, nbv, coef) : fit_feature<5, KMAX>(min_match_sq_dis, min_plane_dis, kind, nbv, coef);
+            if (valid && (flags & MLH_FLAG_CHECK_FOV)) valid = in_laser_fov(q, t, sx, sy, sz);
         }
         MLH_STAGE(gtile, 6);
         Corr c;
@@ -839,7 +884,7 @@ __global__ __launch_bounds__(TPB) void fit_linearize_kernel(KParams P)
     }
     MLH_STAGE(gtile, 1);
     if (valid) {
-        const double w = feature_weight_pref(P, K, cdv);
+        const double w = feature_weight_pref(flags, cov_measurement_trace, K, cdv);
         double R[9];
         qtorot(q, R);
         const d3 p{double(fp.x), double(fp.y), double(fp.z)};
@@ -852,7 +897,7 @@ __global__ __launch_bounds__(TPB) void fit_linearize_kernel(KParams P)
         for (int i = 0; i < 6; ++i) K.J_out[size_t(f) * 6 + i] = L.J[i];
     }
     MLH_STAGE(gtile, 2);
-    reduce_rows(valid, L, P.huber_delta, (P.flags & MLH_FLAG_NO_LOSS) != 0, kind, s_red, P.partials + size_t(gtile) * NE_STRIDE);
+    reduce_rows(valid, L, huber_delta, (flags & MLH_FLAG_NO_LOSS) != 0, kind, s_red, partials + size_t(gtile) * NE_STRIDE);
     MLH_STAGE(gtile, 3);
     if constexpr (FIN) { if (P.finish) fused_gn_finish<LM>(P, total); }
     MLH_STAGE(gtile, 4);
@@ -1486,9 +1531,8 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
     P.min_plane_dis = a.min_plane_dis;
     P.huber_delta = a.huber_delta;
     P.cov_measurement_trace = a.cov_measurement_trace;
-    P.has_lo = ctx->shard_lo ? 1 : 0;
-    P.has_hi = ctx->shard_hi ? 1 : 0;
     P.own_mod = ctx->own_mod; P.own_rem = ctx->own_rem;
+    P.own_mode = (ctx->shard_lo ? 1 : 0) | (ctx->shard_hi ? 2 : 0) | (ctx->own_mod > 1 ? 4 : 0);
     for (int i = 0; i < 4; ++i) { P.lo[i] = ctx->lo_plane[i]; P.hi[i] = ctx->hi_plane[i]; }
     P.finish = a.finish;
     P.lm_max_it = a.lm_max_it; P.lm_min_blocks = a.lm_min_blocks; P.lm_expect_done = a.lm_expect_done;
@@ -1539,6 +1583,11 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         P.pre_thre = a.pre_final_thre;
         P.pre_freeze = a.pre_final_freeze;
         for (int i = 0; i < 7; ++i) { P.chain_prev[i] = a.chain_prev[i]; P.chain_cur[i] = a.chain_cur[i]; }
+    }
+    {   // where the launch's poses are, when they are not init_pose (load_pose)
+        SolverState *S = ctx->state.as<SolverState>();
+        P.pose_b0 = P.pose0 ? P.pose0 : (P.pose_sel ? S->cand : S->x);
+        P.pose_bn = P.pose0 ? P.pose0 : &S->xb[0][0];
     }
     P.m_dev = a.m_dev;
     P.publish = (a.finish == 1 || a.finish == 4 || a.lmc) ? a.publish : nullptr;
