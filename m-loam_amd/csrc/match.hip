@@ -117,6 +117,22 @@ __device__ __forceinline__ void eval_edge(const d3 &p, const float (&c)[6], doub
     o.J[3] = w * j0; o.J[4] = w * j1; o.J[5] = w * j2;
 }
 
+// residual and 1 x 6 Jacobian of one factor at the pose (q, t); a slot without a valid correspondence contributes a zero row
+__device__ __forceinline__ Lin eval_factor(bool valid, int kind, const d3 &p, const float (&coef)[6], double w, const q4 &q, const d3 &t)
+{
+    Lin L;
+    L.r = 0.0;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) L.J[i] = 0.0;
+    if (valid) {
+        double R[9];
+        qtorot(q, R);
+        if (kind == MLH_SURF) eval_plane(p, coef, w, q, t, R, L);
+        else eval_edge(p, coef, w, q, t, R, L);
+    }
+    return L;
+}
+
 // accumulate one (possibly invalid) row and reduce the 29 sums over the workgroup -> partials[tile]
 // (mult: how many identical residual blocks the row stands for -- 1, except for the feature a selection picked repeatedly, select.hip: apply_keep_kernel)
 template <int MODE = 0>      // 0: plain stores, 1: agent-scope monotonic stores, 2: tagged words (reduce_dev.hpp: reduce_acc32)
@@ -453,7 +469,7 @@ __device__ __forceinline__ void publish_final_pose(const KParams &P, const doubl
     for (int i = 0; i < 7; ++i) P.state->x[i] = s_pose[i];
     if (P.pre_publish) {
         for (int i = 0; i < 7; ++i) P.pre_publish->x[i] = s_pose[i];
-        __hip_atomic_store(&P.pre_publish->seq, P.pre_publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+        publish_seq(P.pre_publish, P.pre_publish_seq);
     }
 }
 
@@ -519,9 +535,6 @@ __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
     }
     int tile = xcd_tile(total);
     if (tile >= total) return;
-#ifdef MLH_KNN_HEAVY_FIRST
-    tile = total - 1 - tile;       // A/B build only (scripts/build_variant.py): the corner tiles -- the queries with the most candidates -- are dispatched first
-#endif
     const int kind = tile >= ta0 ? 1 : 0;
     // this workgroup's kind and the ownership word, as values the compiler cannot fetch again: behind the prologue it would rather re-read both kinds' arguments
     // and select once more than keep the selection in registers
@@ -643,25 +656,41 @@ __device__ __forceinline__ double feature_weight_pref(uint32_t flags, double cov
 }
 __device__ __forceinline__ double feature_weight_pref(const KParams &P, const KindL &K, const float4 &cd) { return feature_weight_pref(P.flags, P.cov_measurement_trace, K, cd); }
 
+// correspondence, feature and (with uncertainty weighting) covariance diagonal of slot f < K.m, requested together: ONE round trip, whatever `valid` turns out to be
+__device__ __forceinline__ void load_tile_inputs(const KParams &P, const KindP &K, int f, Corr &c, float4 &fp, float4 &cdv)
+{
+    c = K.corr[f];
+    fp = K.feat[f];
+    if ((P.flags & MLH_FLAG_WITH_UA) && K.covd) cdv = K.covd[f];
+}
+
+// the publication of the launch-per-iteration LM forms: bit 1 from the split submission's look-ahead bookkeeping, the largest iteration count of the frame's loops
+template <typename X>
+__device__ __forceinline__ void lmc_publish(const KParams &P, const X &x, int done, int overflow, double used_max, int iteration)
+{
+    publish_pose(P.publish, P.publish_seq, x, done | (overflow ? 2 : 0), fmax(used_max, double(iteration)));
+}
+
+// the records of pose block b: its surf tiles, then its corner tiles (one block: every record, whatever the tile size)
+__device__ __forceinline__ void block_sum_args(const KParams &P, int b, int total_tiles, SumArgs &sa)
+{
+    sa.p = P.partials;
+    sa.lo[0] = P.k[0].m > 0 ? P.k[0].blk_start[b] / TPB : 0;
+    sa.hi[0] = P.k[0].m > 0 ? (P.k[0].blk_start[b + 1] + TPB - 1) / TPB : 0;
+    sa.lo[1] = P.k[0].tiles_b + (P.k[1].m > 0 ? P.k[1].blk_start[b] / TPB : 0);
+    sa.hi[1] = P.k[0].tiles_b + (P.k[1].m > 0 ? (P.k[1].blk_start[b + 1] + TPB - 1) / TPB : 0);
+    if (P.n_blocks == 1) { sa.lo[0] = 0; sa.hi[0] = total_tiles; sa.lo[1] = 0; sa.hi[1] = 0; }
+}
+
 // Fused tail: the last workgroup to arrive (agent-scope release/acquire around an atomic ticket) sums the partial records
 // in fixed order, runs the degeneracy test + the 6x6 solve + Plus for every pose block and re-arms the ticket: a GN iteration
 // costs two launches.
 template <bool LM, int NT = TPB>
 __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tiles)
 {
-    __shared__ int s_last;
     __shared__ double f_ne[NE_STRIDE], f_cnt2[2], f_scratch[(NT / 32) * 32];   // f_scratch doubles as the Jacobi work area (DEG_WORK <= 256)
-    __syncthreads();                               // this workgroup's partial record is written
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned tk = atomicAdd(P.ticket, 1u);
-        s_last = (tk == unsigned(total_tiles - 1)) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!last_workgroup_arrives(P.ticket, total_tiles)) return;
     MLH_STAGE(4095, 0);
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (P.use_init && threadIdx.x < 7) P.state->x[threadIdx.x] = P.init_pose[threadIdx.x];   // the state's pose is born here
     __syncthreads();
     if constexpr (LM) {
@@ -698,12 +727,8 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
             else lm_step_body_wave(f_ne, P.state, P.lm_max_it, xo, done);
             if (threadIdx.x == 0) {
                 *P.ticket = 0u;
-                if (P.publish) {     // last launch of a chunk of LM steps: the pose and the `done` flag go to the host from here
-                    for (int i = 0; i < 7; ++i) P.publish->x[i] = xo[i];
-                    P.publish->done = done | (P.state->lm_overflow ? 2 : 0);
-                    P.publish->xb[2][0] = fmax(P.state->lm_used_max, double(P.state->iteration));
-                    __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-                }
+                // last launch of a chunk of LM steps: the pose and the `done` flag go to the host from here
+                if (P.publish) lmc_publish(P, xo, done, P.state->lm_overflow, P.state->lm_used_max, P.state->iteration);
             }
         }
         MLH_STAGE(4095, 2);
@@ -720,11 +745,7 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
         } else {
             for (int b = 0; b < P.n_blocks; ++b) {         // one record per pose block, all-reduced in one message
                 SumArgs sa;
-                sa.p = P.partials;
-                sa.lo[0] = P.k[0].m > 0 ? P.k[0].blk_start[b] / TPB : 0;
-                sa.hi[0] = P.k[0].m > 0 ? (P.k[0].blk_start[b + 1] + TPB - 1) / TPB : 0;
-                sa.lo[1] = P.k[0].tiles_b + (P.k[1].m > 0 ? P.k[1].blk_start[b] / TPB : 0);
-                sa.hi[1] = P.k[0].tiles_b + (P.k[1].m > 0 ? (P.k[1].blk_start[b + 1] + TPB - 1) / TPB : 0);
+                block_sum_args(P, b, total_tiles, sa);
                 sum_partials<NT, (NT > 256 ? 21 : 12)>(sa, f_ne, f_cnt2, f_scratch);
                 if (threadIdx.x < NE_STRIDE) P.state->neb[b][threadIdx.x] = f_ne[threadIdx.x];
                 __syncthreads();
@@ -735,12 +756,7 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
     }
     for (int b = 0; b < P.n_blocks; ++b) {
         SumArgs sa;
-        sa.p = P.partials;
-        sa.lo[0] = P.k[0].m > 0 ? P.k[0].blk_start[b] / TPB : 0;
-        sa.hi[0] = P.k[0].m > 0 ? (P.k[0].blk_start[b + 1] + TPB - 1) / TPB : 0;
-        sa.lo[1] = P.k[0].tiles_b + (P.k[1].m > 0 ? P.k[1].blk_start[b] / TPB : 0);
-        sa.hi[1] = P.k[0].tiles_b + (P.k[1].m > 0 ? (P.k[1].blk_start[b + 1] + TPB - 1) / TPB : 0);
-        if (P.n_blocks == 1) { sa.lo[0] = 0; sa.hi[0] = total_tiles; sa.lo[1] = 0; sa.hi[1] = 0; }   // one block: every record (any tile size)
+        block_sum_args(P, b, total_tiles, sa);
         sum_partials<NT, (NT > 256 ? 21 : 12)>(sa, f_ne, f_cnt2, f_scratch);
         bool exchanged = true;
         if (P.p2p.n_ranks > 1) {                     // this rank's sums -> everybody's sums (rank order: the same bits on every rank)
@@ -768,13 +784,7 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
     }
     if (threadIdx.x == 0) {
         *P.ticket = 0u;
-#if defined(MLH_EXP) && MLH_EXP == 5
-        if (P.publish) __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-#elif defined(MLH_EXP) && MLH_EXP == 6
-        (void)0;
-#else
-        if (P.publish) __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-#endif
+        if (P.publish) publish_seq(P.publish, P.publish_seq);     // (the pose blocks went into x / xb[b] above)
     }
 }
 
@@ -849,10 +859,6 @@ __global__ __launch_bounds__(TPB) void fit_linearize_kernel(KParams P)
     d3 t;
     load_pose(P, b, q, t);
     bool valid = false;
-    Lin L;
-    L.r = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) L.J[i] = 0.0;
     float coef[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     float4 fp = make_float4(0.f, 0.f, 0.f, -1.f), cdv = make_float4(0.f, 0.f, 0.f, 0.f);
     if (f < m_feat) {
@@ -883,14 +889,7 @@ __global__ __launch_bounds__(TPB) void fit_linearize_kernel(KParams P)
         K.corr[f] = c;
     }
     MLH_STAGE(gtile, 1);
-    if (valid) {
-        const double w = feature_weight_pref(flags, cov_measurement_trace, K, cdv);
-        double R[9];
-        qtorot(q, R);
-        const d3 p{double(fp.x), double(fp.y), double(fp.z)};
-        if (kind == MLH_SURF) eval_plane(p, coef, w, q, t, R, L);
-        else eval_edge(p, coef, w, q, t, R, L);
-    }
+    const Lin L = eval_factor(valid, kind, d3{double(fp.x), double(fp.y), double(fp.z)}, coef, valid ? feature_weight_pref(flags, cov_measurement_trace, K, cdv) : 0.0, q, t);
     if (K.r_out && f < m_feat) {
         K.r_out[f] = L.r;
 #pragma unroll
@@ -929,12 +928,8 @@ __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
     if (gtile >= total) return;
     if (P.pose_sel && P.state->done) {   // candidate evaluation after the device-side LM loop has terminated: keep the partials defined, do no work
         if (threadIdx.x < 32) P.partials[size_t(gtile) * NE_STRIDE + threadIdx.x] = 0.0;
-        if (LM && P.publish && gtile == 0 && threadIdx.x == 0) {      // ... but the host may be waiting for this launch's publication
-            for (int i = 0; i < 7; ++i) P.publish->x[i] = P.state->x[i];
-            P.publish->done = P.state->done | (P.state->lm_overflow ? 2 : 0);
-            P.publish->xb[2][0] = fmax(P.state->lm_used_max, double(P.state->iteration));
-            __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
+        if (LM && P.publish && gtile == 0 && threadIdx.x == 0)        // ... but the host may be waiting for this launch's publication
+            lmc_publish(P, P.state->x, P.state->done, P.state->lm_overflow, P.state->lm_used_max, P.state->iteration);
         return;
     }
     const int kind = gtile >= P.k[0].tiles_b ? 1 : 0;
@@ -945,29 +940,13 @@ __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
     const double *pose = block_pose(P, block_of_slot(K, P.n_blocks, tile * TPB));
     const q4 q{pose[3], pose[4], pose[5], pose[6]};
     const d3 t{pose[0], pose[1], pose[2]};
-    bool valid = false;
-    int mult = 1;
-    Lin L;
-    L.r = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) L.J[i] = 0.0;
-    if (f < K.m) {
-        // correspondence, feature and (with uncertainty weighting) its covariance diagonal in ONE round trip, whatever `valid` turns out to be
-        const Corr c = K.corr[f];
-        const float4 fp = K.feat[f];
-        float4 cdv = make_float4(0.f, 0.f, 0.f, 0.f);
-        if ((P.flags & MLH_FLAG_WITH_UA) && K.covd) cdv = K.covd[f];
-        if (c.valid) {
-            valid = true;
-            mult = c.valid;
-            const double w = feature_weight_pref(P, K, cdv);
-            double R[9];
-            qtorot(q, R);
-            const d3 p{double(fp.x), double(fp.y), double(fp.z)};
-            if (kind == MLH_SURF) eval_plane(p, c.c, w, q, t, R, L);
-            else eval_edge(p, c.c, w, q, t, R, L);
-        }
-    }
+    Corr c;
+    c.valid = 0;
+    float4 fp = make_float4(0.f, 0.f, 0.f, 0.f), cdv = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (f < K.m) load_tile_inputs(P, K, f, c, fp, cdv);
+    const bool valid = f < K.m && c.valid != 0;
+    const int mult = valid ? c.valid : 1;
+    const Lin L = eval_factor(valid, kind, d3{double(fp.x), double(fp.y), double(fp.z)}, c.c, valid ? feature_weight_pref(P, K, cdv) : 0.0, q, t);
     if (K.r_out && f < K.m) {
         K.r_out[f] = L.r;
 #pragma unroll
@@ -990,14 +969,6 @@ __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
 // into SolverState::x, which only launches behind this one read); the records alternate between two buffers the same way. A launch that finds the loop terminated
 // copies the state forward and leaves (the host enqueues a look-ahead of launches without reading the verdict in between, as before).
 // FIRST: the launch behind a match launch whose fit kernel ran with finish 0 -- the records are at the state's pose (or init_pose), the LM loop begins here.
-__device__ __forceinline__ void lmc_publish(const KParams &P, const double (&x)[7], int done, int overflow, double used_max, int iteration)
-{
-    for (int i = 0; i < 7; ++i) P.publish->x[i] = x[i];
-    P.publish->done = done | (overflow ? 2 : 0);
-    P.publish->xb[2][0] = fmax(used_max, double(iteration));
-    __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 template <bool FIRST>
 __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
 {
@@ -1020,11 +991,7 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
                 const double *src = reinterpret_cast<const double *>(Si);
                 double *dst = reinterpret_cast<double *>(So);
                 for (int i = lane; i < NW; i += 64) dst[i] = src[i];
-                if (P.publish && lane == 0) {
-                    double x[7];
-                    for (int i = 0; i < 7; ++i) x[i] = Si->x[i];
-                    lmc_publish(P, x, Si->done, Si->lm_overflow, Si->lm_used_max, Si->iteration);
-                }
+                if (P.publish && lane == 0) lmc_publish(P, Si->x, Si->done, Si->lm_overflow, Si->lm_used_max, Si->iteration);
             }
             return;
         }
@@ -1037,11 +1004,7 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
     Corr c;
     c.valid = 0;
     float4 fp = make_float4(0.f, 0.f, 0.f, 0.f), cdv = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (f < K.m) {
-        c = K.corr[f];
-        fp = K.feat[f];
-        if ((P.flags & MLH_FLAG_WITH_UA) && K.covd) cdv = K.covd[f];
-    }
+    if (f < K.m) load_tile_inputs(P, K, f, c, fp, cdv);
     lmc_sum_records(P.partials_in, total, f_ne, f_scratch);
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
@@ -1076,22 +1039,9 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
     if (s_done) return;                    // terminated by this launch: nothing to evaluate (the next launch finds `done` and reads no records)
     const q4 q{s_cand[3], s_cand[4], s_cand[5], s_cand[6]};
     const d3 t{s_cand[0], s_cand[1], s_cand[2]};
-    bool valid = false;
-    int mult = 1;
-    Lin L;
-    L.r = 0.0;
-#pragma unroll
-    for (int i = 0; i < 6; ++i) L.J[i] = 0.0;
-    if (f < K.m && c.valid) {
-        valid = true;
-        mult = c.valid;
-        const double w = feature_weight_pref(P, K, cdv);
-        double R9[9];
-        qtorot(q, R9);
-        const d3 p{double(fp.x), double(fp.y), double(fp.z)};
-        if (kind == MLH_SURF) eval_plane(p, c.c, w, q, t, R9, L);
-        else eval_edge(p, c.c, w, q, t, R9, L);
-    }
+    const bool valid = f < K.m && c.valid != 0;
+    const int mult = valid ? c.valid : 1;
+    const Lin L = eval_factor(valid, kind, d3{double(fp.x), double(fp.y), double(fp.z)}, c.c, valid ? feature_weight_pref(P, K, cdv) : 0.0, q, t);
     reduce_rows(valid, L, P.huber_delta, (P.flags & MLH_FLAG_NO_LOSS) != 0, kind, s_red, P.partials + size_t(gtile) * NE_STRIDE, mult);
 }
 
@@ -1099,7 +1049,7 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
 // (~4.4 us of an ~8.9 us launch on the 88-tile mapper frame) and a look-ahead of launches behind the loop's end; the tiles of a frame that qualifies for the
 // consumer-side schedule whose workgroups are all resident at once (the host asks the device: mlh_ctx::caps, capi.hip: set_loop_gates) can synchronise among themselves instead:
 //   every workgroup: tile inputs -> registers (once); sum the fit launch's records; LM begin; then, until the loop terminates:
-//     evaluate the tile at the candidate -> record (buffer (it + 1) & 1) -> grid barrier (release; one atomic arrival; spin on the counter; acquire)
+//     evaluate the tile at the candidate -> record (buffer (it + 1) & 1) -> grid barrier (reduce_dev.hpp: loop_barrier_arrive -- one atomic arrival, a poll of the counter)
 //     -> sum all records -> LM step (the state stays in LDS: every workgroup runs the identical arithmetic on identical inputs, so they agree on accept / reject,
 //     on the next candidate and on the iteration the loop ends at, without exchanging anything but the records).
 // The loop ends on the device when Ceres' loop would: no look-ahead budget, no launches that find `done`, nothing for the host to poll between LM iterations,
@@ -1110,22 +1060,11 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
 // never became resident beside another context's kernels, a fault), the loop is given up: P.ticket[3] tells every workgroup still to come or still polling, bit 2 of
 // the published `done` word tells the host, which solves the frame again through the launch-per-iteration form (lm_consume_kernel: no residency requirement) --
 // a slow frame, not a lost one. The later loop launches of such a frame (lm_overflow == 4 in the state) leave at once.
-// MLH_LOOP_COH 1: the records cross the barrier as agent-scope monotonic stores / loads (write-through, read past the L2 of the reader's XCD) -- no L2 write-back
-// and invalidate around the barrier; 0: plain stores + release fence / acquire fence + plain loads
-#ifndef MLH_LOOP_COH
-#define MLH_LOOP_COH 1
-#endif
-#ifndef MLH_LOOP_SPLIT_STEP
-#define MLH_LOOP_SPLIT_STEP 0
-#endif
-#ifndef MLH_LOOP_SLEEP
-#define MLH_LOOP_SLEEP 1
-#endif
-// MLH_LOOP_KEEP_REGS 1 (round 6): the first wavefront keeps the LM state's registers from step to step (lm_step_wave_keep) instead of loading them from and storing
-// them to the LDS state around every step: scan2map 0.184 -> 0.176 ms (three alternations: 0.1836 / 0.1844 / 0.1840 against 0.1761 / 0.1768 / 0.1755), the same bits
-#ifndef MLH_LOOP_KEEP_REGS
-#define MLH_LOOP_KEEP_REGS 1
-#endif
+// The records cross the barrier as agent-scope monotonic stores / loads (write-through, read past the L2 of the reader's XCD): no L2 write-back and invalidate
+// around the barrier. A waiting thread sleeps one s_sleep unit between polls (polling without it was slower, profiles/r05_knockout_experiments.txt).
+// The first wavefront keeps the LM state's registers from step to step (lm_step_wave_keep) and stores them to the LDS state once, behind the loop: scan2map
+// 0.184 -> 0.176 ms against a state that goes through LDS around every step, the same bits (profiles/r06_knockout_experiments.txt). Splitting the step over two
+// wavefronts was not faster (profiles/r05_knockout_experiments.txt).
 // FIT (round 6): the launch begins with the outer iteration's FIT -- fit_linearize_kernel's body for this tile: neighbour records -> line / plane fit + gates -> the
 // correspondence record (stored: later launches and callers read it) -> residual + Jacobian at the start pose -> the tile's record, tagged with iteration 0 and
 // summed by polling like every other record of the loop -- instead of reading what a fit launch in front of it left. One launch boundary fewer per outer iteration;
@@ -1137,9 +1076,6 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
     __shared__ double f_ne[NE_STRIDE], f_scratch[(TPB / 32) * 32];
     __shared__ double s_cand[8];
     __shared__ int s_done, s_timeout;
-#if MLH_LOOP_SPLIT_STEP
-    __shared__ double s_gmax;
-#endif
     __shared__ LmState s_lm;
     int m0 = P.k[0].m, m1 = P.k[1].m, tb0 = P.k[0].tiles_b;
     int total = P.k[0].tiles_b + P.k[1].tiles_b;
@@ -1151,10 +1087,9 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
             // the thinning kept nothing of either kind: no tile exists, nobody would publish -- the first workgroup of the launch the host waits for does (bit 3:
             // "no features"; the host reports what mlh_scan2map reports for an empty feature set, include/mloam_hip.h)
             if (blockIdx.x == 0 && threadIdx.x == 0 && P.publish) {
-                for (int i = 0; i < 7; ++i) P.publish->x[i] = P.use_init ? P.init_pose[i] : P.state->x[i];
-                P.publish->done = 1 | 8;
-                P.publish->xb[2][0] = 0.0;
-                __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                double x[7];
+                for (int i = 0; i < 7; ++i) x[i] = P.use_init ? P.init_pose[i] : P.state->x[i];
+                publish_pose(P.publish, P.publish_seq, x, 1 | 8, 0.0);
             }
             return;
         }
@@ -1192,9 +1127,7 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
             K.corr[f] = c;
         }
     } else if (f < m_feat) {
-        c = K.corr[f];
-        fp = K.feat[f];
-        if ((P.flags & MLH_FLAG_WITH_UA) && K.covd) cdv = K.covd[f];
+        load_tile_inputs(P, K, f, c, fp, cdv);
     }
     const bool valid = f < m_feat && c.valid != 0;
     const int mult = valid ? c.valid : 1;
@@ -1203,7 +1136,7 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
     const size_t set = size_t(NE_STRIDE) * size_t(total);
     // given up already -- by a workgroup of this launch that waited in vain, or by an earlier loop of this frame: nothing to do but leave
     if (threadIdx.x == 0)
-        s_timeout = (__hip_atomic_load(P.ticket + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u || (P.lm_expect_done >= 0 && P.state->lm_overflow == 4)) ? 2 : 0;
+        s_timeout = (loop_barrier_given_up(P.ticket) || (P.lm_expect_done >= 0 && P.state->lm_overflow == 4)) ? 2 : 0;
     if constexpr (FIT) {
         __syncthreads();                               // s_timeout
         if (s_timeout == 0) {                          // (uniform)
@@ -1213,16 +1146,7 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
             for (int i = 0; i < 7; ++i) xs[i] = P.use_init ? P.init_pose[i] : P.state->x[i];
             const q4 q0{xs[3], xs[4], xs[5], xs[6]};
             const d3 t0{xs[0], xs[1], xs[2]};
-            Lin L0;
-            L0.r = 0.0;
-#pragma unroll
-            for (int i = 0; i < 6; ++i) L0.J[i] = 0.0;
-            if (valid) {
-                double R9[9];
-                qtorot(q0, R9);
-                if (kind == MLH_SURF) eval_plane(p, c.c, w, q0, t0, R9, L0);
-                else eval_edge(p, c.c, w, q0, t0, R9, L0);
-            }
+            const Lin L0 = eval_factor(valid, kind, p, c.c, w, q0, t0);
             const unsigned tag0 = P.loop_tag_base;     // iteration byte 0: the fit's record (the loop's iterations carry 1, 2, ...)
             unsigned long long *trec0 = P.loop_tagged;  // set 0 (iteration `it` writes set (it + 1) & 1: 1, 0, 1, ...; set 0 is written again by iteration 1, which
                                                         // no workgroup reaches before every workgroup has stored its iteration-0 record -- behind its read of this one)
@@ -1234,10 +1158,8 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
     }
     const bool skipped = s_timeout != 0;           // (uniform: written before the sum's barriers)
     if (threadIdx.x == 0 && skipped) s_done = 1;
-#if MLH_LOOP_KEEP_REGS
     LmRegs Rk;                     // (first wavefront only: the LM state's registers, kept from step to step; stored to s_lm once, behind the loop)
     double candk[7], x_cost_k = 0.0;
-#endif
     if (threadIdx.x < 64 && !skipped) {
         const int lane = threadIdx.x;
         LmRegs R;
@@ -1247,11 +1169,9 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
         lm_begin_wave_pp(f_ne, f_scratch, x, &s_lm, true, P.thre_b[0], P.lm_max_it, P.lm_min_blocks, R, cand);
         if (lane < 7) s_cand[lane] = pick7(cand, lane);
         if (lane == 0) s_done = R.done;
-#if MLH_LOOP_KEEP_REGS
         Rk = R; x_cost_k = f_ne[NE_COST];
 #pragma unroll
         for (int i = 0; i < 7; ++i) candk[i] = cand[i];
-#endif
     }
     __syncthreads();
     int it = 0;
@@ -1259,23 +1179,14 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
         if (it == 2) MLH_STAGE(gtile, 0);                 // (debug build only: the third iteration's stages, scripts/stageclock_loop.py)
         const q4 q{s_cand[3], s_cand[4], s_cand[5], s_cand[6]};
         const d3 t{s_cand[0], s_cand[1], s_cand[2]};
-        Lin L;
-        L.r = 0.0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) L.J[i] = 0.0;
-        if (valid) {
-            double R9[9];
-            qtorot(q, R9);
-            if (kind == MLH_SURF) eval_plane(p, c.c, w, q, t, R9, L);
-            else eval_edge(p, c.c, w, q, t, R9, L);
-        }
+        const Lin L = eval_factor(valid, kind, p, c.c, w, q, t);
         if (it == 2) MLH_STAGE(gtile, 1);
+        const bool stall = P.debug_stall && it == 1 && gtile == (total > 1 ? 1 : 0);      // (tests: this workgroup's record / arrival never comes)
         if (P.loop_tagged) {
             // (round 6) the record leaves as tagged words and is summed by polling for the tag: no arrival atomic, no counter poll between the store and the loads
             const unsigned tag = P.loop_tag_base | unsigned(it + 1);
             unsigned long long *trec = P.loop_tagged + size_t(total) * 64 * size_t((it + 1) & 1);
-            const bool stall = P.debug_stall && it == 1 && gtile == (total > 1 ? 1 : 0);
-            if (stall) {                                               // (tests: this workgroup's record never arrives)
+            if (stall) {
                 if (threadIdx.x == 0) { s_timeout = 1; __hip_atomic_store(P.ticket + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
                 __syncthreads();
             } else {
@@ -1287,102 +1198,39 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
             if (s_timeout) break;
         } else {
             double *rec = P.partials + set * size_t((it + 1) & 1);
-            reduce_rows<MLH_LOOP_COH != 0>(valid, L, P.huber_delta, (P.flags & MLH_FLAG_NO_LOSS) != 0, kind, s_red, rec + size_t(gtile) * NE_STRIDE, mult);
+            reduce_rows<1>(valid, L, P.huber_delta, (P.flags & MLH_FLAG_NO_LOSS) != 0, kind, s_red, rec + size_t(gtile) * NE_STRIDE, mult);
             // (the record's 32 words are stored by the first 32 lanes of the wavefront thread 0 belongs to: its s_waitcnt covers them)
-            if (!MLH_LOOP_COH) __syncthreads();
             if (it == 2) MLH_STAGE(gtile, 2);
             if (threadIdx.x == 0) {
-                if (!MLH_LOOP_COH) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                const unsigned target = unsigned(total) * unsigned(it + 1);
-                const bool stall = P.debug_stall && it == 1 && gtile == (total > 1 ? 1 : 0);
-                if (stall) { s_timeout = 1; __hip_atomic_store(P.ticket + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-                else {
-                    __hip_atomic_fetch_add(P.ticket + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    unsigned spins = 0;
-                    long long t0 = 0;
-                    while (__hip_atomic_load(P.ticket + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < target) {
-                        if (MLH_LOOP_SLEEP) __builtin_amdgcn_s_sleep(MLH_LOOP_SLEEP);
-                        if ((++spins & 63u) == 0u) {      // (a completed barrier takes ~2 us = a few polls: the clock and the word below are only read by a wait that is already long)
-                            const long long now = wall_clock64();
-                            if (t0 == 0) t0 = now;
-                            const bool late = (unsigned long long)(now - t0) > P.loop_timeout_ticks;
-                            if (late) __hip_atomic_store(P.ticket + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                            if (late || __hip_atomic_load(P.ticket + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { s_timeout = 1; break; }
-                        }
-                    }
-                }
-                if (!MLH_LOOP_COH) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-                asm volatile("" ::: "memory");
+                if (stall) __hip_atomic_store(P.ticket + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (stall || !loop_barrier_arrive(P.ticket, total, it + 1, P.loop_timeout_ticks)) s_timeout = 1;
             }
             __syncthreads();
             if (it == 2) MLH_STAGE(gtile, 3);
             if (s_timeout) break;
-            lmc_sum_records<MLH_LOOP_COH != 0>(rec, total, f_ne, f_scratch);
+            lmc_sum_records<true>(rec, total, f_ne, f_scratch);
         }
         if (it == 2) MLH_STAGE(gtile, 4);
-#if MLH_LOOP_SPLIT_STEP
-        {
-            // the LM step on the first wavefront, the gradient max-norm an ACCEPTED step needs on the second, side by side (lm_step_wave_spec1 / 2)
-            LmRegs R;
-            double cand[7];
-            LmStepSpec sp;
-            if (threadIdx.x < 64) lm_step_wave_spec1(f_ne, &s_lm, P.lm_max_it, R, cand, sp);
-            else if (threadIdx.x < 128) {
-                LmRegs Q;
-#pragma unroll
-                for (int i = 0; i < 7; ++i) Q.x[i] = s_lm.cand[i];
-#pragma unroll
-                for (int i = 0; i < 6; ++i) Q.g[i] = f_ne[NE_G + i];
-                const double gm = gradient_max_norm_wave(Q, s_lm.V, threadIdx.x & 63);
-                if (threadIdx.x == 64) s_gmax = gm;
-            }
-            __syncthreads();
-            if (threadIdx.x < 64) {
-                const int lane = threadIdx.x;
-                lm_step_wave_spec2(&s_lm, &s_lm, true, R, cand, sp, s_gmax);
-                if (lane < 7) s_cand[lane] = pick7(cand, lane);
-                if (lane == 0) s_done = R.done;
-            }
-        }
-#elif MLH_LOOP_KEEP_REGS
         if (threadIdx.x < 64) {
             const int lane = threadIdx.x;
             lm_step_wave_keep(f_ne, &s_lm, P.lm_max_it, Rk, candk, x_cost_k);
             if (lane < 7) s_cand[lane] = pick7(candk, lane);
             if (lane == 0) s_done = Rk.done;
         }
-#else
-        if (threadIdx.x < 64) {
-            const int lane = threadIdx.x;
-            LmRegs R;
-            double cand[7];
-            lm_step_wave_pp(f_ne, &s_lm, &s_lm, true, P.lm_max_it, R, cand);
-            if (lane < 7) s_cand[lane] = pick7(cand, lane);
-            if (lane == 0) s_done = R.done;
-        }
-#endif
         __syncthreads();
         if (it == 2) MLH_STAGE(gtile, 5);
         ++it;
     }
-#if MLH_LOOP_KEEP_REGS
     if (threadIdx.x < 64 && !skipped) {            // the state the publication below (and nothing else) reads
         lm_state_store_pp(Rk, candk, s_lm.ne, s_lm.V, &s_lm, threadIdx.x);
         __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         __builtin_amdgcn_wave_barrier();
     }
-#endif
     if (writer && threadIdx.x < 64 && skipped) {
         // the loop never began here: the pose in the state is what the last loop that ran left; the failure travels on to the launch that publishes
         if (threadIdx.x == 0) {
             P.state->lm_overflow = 4;
-            if (P.publish) {
-                for (int i = 0; i < 7; ++i) P.publish->x[i] = P.state->x[i];
-                P.publish->done = 4;
-                P.publish->xb[2][0] = P.state->lm_used_max;
-                __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            if (P.publish) publish_pose(P.publish, P.publish_seq, P.state->x, 4, P.state->lm_used_max);
         }
     }
     else if (writer && threadIdx.x < 64) {
@@ -1397,22 +1245,10 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
             P.state->lm_overflow = failed ? 4 : 0;
             P.state->done = s_lm.done;
             P.state->iteration = s_lm.iteration;
-            if (P.publish) {
-                for (int i = 0; i < 7; ++i) P.publish->x[i] = s_lm.x[i];
-                P.publish->done = (s_lm.done ? 1 : 0) | (failed ? 4 : 0);
-                P.publish->xb[2][0] = used;
-                __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            if (P.publish) publish_pose(P.publish, P.publish_seq, s_lm.x, (s_lm.done ? 1 : 0) | (failed ? 4 : 0), used);
         }
     }
-    if (threadIdx.x == 0) {                // the last workgroup to leave re-arms the barrier for the next launch
-        const unsigned left = atomicAdd(P.ticket + 2, 1u);
-        if (left == unsigned(total - 1)) {
-            __hip_atomic_store(P.ticket + 1, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(P.ticket + 2, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(P.ticket + 3, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    if (threadIdx.x == 0) loop_barrier_leave(P.ticket, total);      // the last workgroup to leave re-arms the barrier for the next launch
 }
 
 // stand-alone exact 5-NN for mlh_knn (queries already in the map frame)

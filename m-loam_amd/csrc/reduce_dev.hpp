@@ -81,6 +81,42 @@ __device__ __forceinline__ void reduce_acc32(double (&acc)[32], int kind, double
     }
 }
 
+// ---- the HostPublish record (ctx.hpp), written by ONE thread of the launch the host waits for: the pose, the `done` word, then `seq` -- last, as a system-scope
+// release store, so a host that finds the sequence number it waits for finds this launch's record behind it. Bits of `done`: 1 the loop has terminated, 2 the
+// look-ahead of launches overflowed (a loop had not ended where the host assumed it had), 4 a grid barrier was given up, 8 the launch had no features.
+__device__ __forceinline__ void publish_seq(HostPublish *pub, unsigned long long seq)
+{
+    __hip_atomic_store(&pub->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+// x: the pose, seven doubles in registers or behind a pointer. USED: the mapper's LM schedules also report the largest iteration count a loop of the frame took
+template <bool USED = true, typename X>
+__device__ __forceinline__ void publish_pose(HostPublish *pub, unsigned long long seq, const X &x, int done, double used_max = 0.0)
+{
+    for (int i = 0; i < 7; ++i) pub->x[i] = x[i];
+    pub->done = done;
+    if constexpr (USED) pub->xb[2][0] = used_max;
+    publish_seq(pub, seq);
+}
+
+// The fused tails' ticket (match.hip: fused_gn_finish, track.hip: track_linearize_kernel), by every thread of a workgroup whose partial record has been stored: true
+// in the LAST workgroup of the launch's `total` to arrive (agent-scope release in front of the ticket, acquire behind it: the other workgroups' records are visible
+// to thread 0's wavefront, and to the rest behind the caller's next barrier); that workgroup re-arms the ticket when it is done.
+__device__ __forceinline__ bool last_workgroup_arrives(unsigned *ticket, int total)
+{
+    __shared__ int s_last;
+    __syncthreads();                               // this workgroup's partial record is written
+    if (threadIdx.x == 0) {
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        const unsigned tk = atomicAdd(ticket, 1u);
+        s_last = (tk == unsigned(total - 1)) ? 1 : 0;
+    }
+    __syncthreads();
+    if (!s_last) return false;
+    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    return true;
+}
+
 // ---- shared by the one-launch Levenberg-Marquardt loops (match.hip: lm_loop_kernel, track.hip: track_lm_loop_kernel)
 // the tiles' records summed by EVERY workgroup in sum_partials<TPB, 12>'s order (same slices, same four chains, same association: the same bits everywhere);
 // COH: the records were stored with agent-scope monotonic stores by other workgroups of the SAME launch and are read with agent-scope loads
@@ -117,9 +153,6 @@ __device__ __forceinline__ void lmc_sum_records(const double *rec, int ntot, dou
 // an arrival atomic + a poll of its counter + the loads. Same slices, same chains, same association as lmc_sum_records: the same bits. A word that does not arrive
 // within timeout_ticks of the 100 MHz wall clock (a workgroup that never became resident, a fault) gives the loop up exactly as the barrier did: counters[3] tells
 // the other workgroups, *s_timeout (LDS, read by the caller behind this function's barriers) this one.
-#ifndef MLH_LOOP_TAG_SLEEP
-#define MLH_LOOP_TAG_SLEEP 1
-#endif
 __device__ __forceinline__ void lmc_sum_records_tagged(const unsigned long long *rec, int ntot, unsigned tag, double *f_ne, double *f_scratch, unsigned *counters,
                                                        unsigned long long timeout_ticks, int *s_timeout)
 {
@@ -143,7 +176,7 @@ __device__ __forceinline__ void lmc_sum_records_tagged(const unsigned long long 
 #pragma unroll
             for (int u = 0; u < U; ++u) stale = stale || unsigned(w0[u]) != tag || unsigned(w1[u]) != tag;
             if (!stale) break;
-            if (MLH_LOOP_TAG_SLEEP) __builtin_amdgcn_s_sleep(MLH_LOOP_TAG_SLEEP);
+            __builtin_amdgcn_s_sleep(1);
 #pragma unroll
             for (int u = 0; u < U; ++u) {
                 const int jj = j + NS * u;

@@ -162,21 +162,12 @@ __global__ __launch_bounds__(FPS_THREADS) void fps_order_kernel(const float4 *__
 // The box test is conservative by 1e-4 relative against ~3e-7 of rounding in either distance, and only applied to a squared box distance in the normal range;
 // a cloud with ANY non-finite coordinate (fps_keys_kernel's flag) is left to fps_order_kernel, launched behind this one and gated on the same word: its
 // comparisons treat NaN as the host's do.
-// (A/B, ms per config-5 frame, two alternations: 8 wavefronts x 32 slots 14.05 / 14.08, 16 x 16 13.25 / 13.20 -- a pick's five or so buckets collide less often on
-// one wavefront)
-#ifndef MLH_FPP_WAVES
-#define MLH_FPP_WAVES 16
-#endif
-constexpr int FPP_WAVES = MLH_FPP_WAVES, FPP_SLOTS = 256 / FPP_WAVES, FPP_THREADS = FPP_WAVES * 64;      // 16 384 points, as the dense kernel
-static_assert(FPP_WAVES == 8 || FPP_WAVES == 16, "8 wavefronts x 32 slots or 16 x 16");
+// 16 wavefronts x 16 slots: 13.25 / 13.20 ms per config-5 frame against 14.05 / 14.08 for 8 x 32 (two alternations) -- a pick's five or so buckets collide less
+// often on one wavefront
+constexpr int FPP_WAVES = 16, FPP_SLOTS = 256 / FPP_WAVES, FPP_THREADS = FPP_WAVES * 64;      // 16 384 points, as the dense kernel
 static_assert(FPP_WAVES * FPP_SLOTS * 64 == FPS_THREADS * FPS_PMAX, "both fps kernels take the same clouds");
 constexpr int FPR_TPB = 256, FPR_PARTS = 8, FPR_TILE = 1024;
-#if MLH_FPP_WAVES == 8
-#define FPP_FOR32(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15) \
-                     M(16) M(17) M(18) M(19) M(20) M(21) M(22) M(23) M(24) M(25) M(26) M(27) M(28) M(29) M(30) M(31)
-#else
 #define FPP_FOR32(M) M(0) M(1) M(2) M(3) M(4) M(5) M(6) M(7) M(8) M(9) M(10) M(11) M(12) M(13) M(14) M(15)
-#endif
 
 __device__ __forceinline__ unsigned fpp_ord(float f) { const unsigned b = __float_as_uint(f); return b ^ ((b >> 31) ? 0xffffffffu : 0x80000000u); }   // float order -> unsigned order
 __device__ __forceinline__ float fpp_unord(unsigned u) { return __uint_as_float(u ^ ((u >> 31) ? 0x80000000u : 0xffffffffu)); }

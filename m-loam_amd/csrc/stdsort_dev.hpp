@@ -15,18 +15,12 @@
 namespace mlh {
 
 constexpr int SS_THRESHOLD = 16;      // std::_S_threshold
-// the wave-level partition of a range longer than one tile (ss_wave_partition): tiles / swaps a lane keeps in flight, the pair count by search (A/B builds)
-#ifndef MLH_SS_HEAP_PAR
-#define MLH_SS_HEAP_PAR 0
-#endif
+// the wave-level partition of a range longer than one tile (ss_wave_partition): tiles / swaps a lane keeps in flight (A/B builds)
 #ifndef MLH_SS_WAVE_U
 #define MLH_SS_WAVE_U 4
 #endif
 #ifndef MLH_SS_WAVE_SWAP_U
 #define MLH_SS_WAVE_SWAP_U 2
-#endif
-#ifndef MLH_SS_WAVE_SEARCH
-#define MLH_SS_WAVE_SEARCH 1
 #endif
 
 struct IntLess { __device__ __forceinline__ bool operator()(int a, int b) const { return a < b; } };
@@ -112,38 +106,8 @@ __device__ __forceinline__ void ss_heap_sort_wave64(int *k, int *v, int len_, Le
     const int lane = threadIdx.x & 63, len = __builtin_amdgcn_readfirstlane(len_);
     int key_r = lane < len ? k[lane] : 0, val_r = lane < len ? v[lane] : 0;
     auto rd = [&](int reg, int i) { return __builtin_amdgcn_readlane(reg, i); };
-#if MLH_SS_HEAP_PAR
-    // __adjust_heap (+ its trailing __push_heap) for ALL levels at once. The library first walks the hole down to a leaf, always to the larger child (the right one
-    // on a tie; the only child of the last inner node of an even-sized heap), moving that child up -- a path that depends on the heap's content alone -- and then walks
-    // the new value up that same path while the element above it is smaller. With one element per lane: every lane compares its two children (two shuffles), two
-    // ballots make "which child does node p prefer" a uniform mask, each lane tests its own ancestors against the mask (is it on the path from the hole, and how
-    // deep), a third ballot finds where the upward walk stops -- the deepest path node that is the hole's start or holds an element not smaller than the value --,
-    // path nodes above that point take their preferred child's element, the point takes the value. Built, equal to libstdc++ on every test and soak -- and SLOWER than
-    // the level-by-level form below (23.8 against 16.8 us per heap sort of 31-94 elements: four ds_bpermute, three ballots and the 64-bit mask tests cost more than six
-    // levels of scalar-indexed v_readlane + select): not the default (profiles/r05_knockout_experiments.txt item 19).
-    auto adjust = [&](int hole, int n, int key, int val) {
-        const int lc = 2 * lane + 1, rc = 2 * lane + 2;
-        const int kl = __shfl(key_r, lc & 63), kr = __shfl(key_r, rc & 63), vl = __shfl(val_r, lc & 63), vr = __shfl(val_r, rc & 63);
-        const bool two = rc < n, has = lc < n;                      // (lc == n - 1 without a right child: n even, lane == (n - 2) / 2)
-        const bool pick_l = two ? less(kr, kl) : true;
-        const int kc = pick_l ? kl : kr, vc = pick_l ? vl : vr;     // the preferred child's element
-        const unsigned long long HAS = __ballot(has), PL = __ballot(has && pick_l);
-        bool on = lane < n;
-        int x = lane, depth = 0;
-        while (x > hole) {                                          // (at most six trips; lanes outside the hole's subtree fall below it)
-            const int p = (x - 1) >> 1;
-            on = on && ((HAS >> p) & 1ull) && ((((PL >> p) & 1ull) != 0ull) == ((x & 1) != 0));
-            x = p;
-            ++depth;
-        }
-        on = on && x == hole;
-        const bool f = on && (depth == 0 || !less(key_r, key));
-        const unsigned long long F = __ballot(f);                  // never empty: the hole itself
-        const int jstar = 63 - __clzll((long long)F);
-        if (on && lane < jstar) { key_r = kc; val_r = vc; }
-        else if (lane == jstar) { key_r = key; val_r = val; }
-    };
-#else
+    // (Sifting all levels at once -- shuffles + ballots over the hole's path -- was built, equal to libstdc++, and slower than this level-by-level form: 23.8 against
+    // 16.8 us per heap sort of 31-94 elements, profiles/r05_knockout_experiments.txt item 19.)
     // every index and every travelling element is wavefront-uniform and is KEPT in scalar registers (readfirstlane where the compiler cannot see it): a sift level
     // is two v_readlane (the children's keys), a scalar compare and two selects (which child, its key -- already read), one v_readlane (its value), two
     // v_writelane into the hole's lane. (Round 6; through round 5 the make-heap phase ran with its indices in vector registers -- v_readfirstlane + wait states
@@ -181,7 +145,6 @@ __device__ __forceinline__ void ss_heap_sort_wave64(int *k, int *v, int len_, Le
         }
         wr(key_r, key, hole); wr(val_r, val, hole);
     };
-#endif
     if (len >= 2) {
         int parent = (len - 2) / 2;
         while (true) {
@@ -195,11 +158,7 @@ __device__ __forceinline__ void ss_heap_sort_wave64(int *k, int *v, int len_, Le
         --last;
         const int key = rd(key_r, last), val = rd(val_r, last);
         const int k0 = rd(key_r, 0), v0 = rd(val_r, 0);
-#if MLH_SS_HEAP_PAR
-        key_r = (lane == last) ? k0 : key_r; val_r = (lane == last) ? v0 : val_r;
-#else
         wr(key_r, k0, last); wr(val_r, v0, last);
-#endif
         adjust(0, last, key, val);
     }
     if (lane < len) { k[lane] = key_r; v[lane] = val_r; }
@@ -288,9 +247,8 @@ __device__ __forceinline__ int ss_wave_partition(int *keys, int *vals, int *lt, 
         ss_wg_fence();
         const int npair = min(nL, nR), rlast = f + nR - 1;                    // the k-th right stop from the right: rt[rlast - k]
         // K = how many pairs cross: L[k] < R[k] holds for a PREFIX of k (the left stops ascend, the right stops counted from the right descend), so a 64-ary search
-        // finds it in one or two rounds where testing every pair took npair / 64 (13 for a ring's 1 670 voxel keys)
+        // finds it in one or two rounds where testing every pair took npair / 64 (13 for a ring's 1 670 voxel keys) -- profiles/r05_knockout_experiments.txt
         int K;
-#if MLH_SS_WAVE_SEARCH
         {
             int lo_k = 0, hi_k = npair;
             while (hi_k > lo_k) {                                            // uniform
@@ -304,13 +262,6 @@ __device__ __forceinline__ int ss_wave_partition(int *keys, int *vals, int *lt, 
             }
             K = lo_k;
         }
-#else
-        K = 0;
-        for (int base = 0; base < npair; base += 64) {
-            const int k = base + lane;
-            K += __popcll(__ballot(k < npair && lt[f + k] < rt[rlast - k]));
-        }
-#endif
         // the swaps, MLH_SS_WAVE_SWAP_U pairs per lane in flight: positions, then the elements, then the stores (the pairs are disjoint)
         for (int k0 = lane; k0 < K; k0 += 64 * MLH_SS_WAVE_SWAP_U) {
             int pp[MLH_SS_WAVE_SWAP_U], qq[MLH_SS_WAVE_SWAP_U], kp[MLH_SS_WAVE_SWAP_U], kq[MLH_SS_WAVE_SWAP_U], vp[MLH_SS_WAVE_SWAP_U], vq[MLH_SS_WAVE_SWAP_U];

@@ -315,13 +315,6 @@ __device__ __forceinline__ V3 row_skew3(const V3 &a, const V3 &v)             //
     return {a.y * v.z - a.z * v.y, a.z * v.x - a.x * v.z, a.x * v.y - a.y * v.x};
 }
 
-__device__ __forceinline__ void track_publish(const TrackParamsDev &P)
-{
-    for (int i = 0; i < 7; ++i) P.publish->x[i] = P.state->x[i];
-    P.publish->done = P.state->done;
-    __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-}
-
 // the normal-equation terms of ONE matched feature at pose (q, t): LidarScanPlaneNormFactor (1 residual) or LidarScanEdgeFactorVector (3), Huber on the block's
 // squared norm -- what track_linearize_kernel and track_lm_loop_kernel accumulate (acc: zeroed by the caller)
 __device__ __forceinline__ void track_eval(const TrackParamsDev &P, int kind, const Corr &c, const float4 &fp, const q4 &q, const d3 &t, double (&acc)[32])
@@ -397,7 +390,7 @@ __global__ __launch_bounds__(TPB) void track_linearize_kernel(TrackParamsDev P)
     if (gtile >= total) return;
     if (P.pose_sel && P.state->done) {       // the LM loop has terminated: keep the partials defined, do no work
         if (threadIdx.x < 32) P.partials[size_t(gtile) * NE_STRIDE + threadIdx.x] = 0.0;
-        if (P.publish && gtile == 0 && threadIdx.x == 0) track_publish(P);      // the host may be waiting for this launch's record
+        if (P.publish && gtile == 0 && threadIdx.x == 0) publish_pose<false>(P.publish, P.publish_seq, P.state->x, P.state->done);      // the host may be waiting for this launch's record
         return;
     }
     const int kind = gtile >= P.k[0].tiles_b ? 1 : 0;
@@ -422,17 +415,8 @@ __global__ __launch_bounds__(TPB) void track_linearize_kernel(TrackParamsDev P)
     // fused tail (as match.hip: fused_gn_finish): the last workgroup to arrive sums the partial records in fixed order and runs the
     // Levenberg-Marquardt begin / step -- an LM iteration of the tracker is ONE launch (lidar_tracker.cpp:66-70, 106-113: no degeneracy
     // handling, rounds with fewer than 10 correspondences are skipped)
-    __shared__ int s_last;
     __shared__ double f_ne[NE_STRIDE], f_cnt2[2], f_scratch[8 * 32];
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        s_last = (atomicAdd(P.ticket, 1u) == unsigned(total - 1)) ? 1 : 0;
-    }
-    __syncthreads();
-    if (!s_last) return;
-    if (threadIdx.x == 0) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    if (!last_workgroup_arrives(P.ticket, total)) return;
     __syncthreads();
     SumArgs sa;
     sa.p = P.partials;
@@ -446,11 +430,7 @@ __global__ __launch_bounds__(TPB) void track_linearize_kernel(TrackParamsDev P)
         else lm_step_body_wave(f_ne, P.state, P.lm_max_it, xo, done);
         if (threadIdx.x == 0) {
             *P.ticket = 0u;
-            if (P.publish) {
-                for (int i = 0; i < 7; ++i) P.publish->x[i] = xo[i];
-                P.publish->done = done;
-                __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
+            if (P.publish) publish_pose<false>(P.publish, P.publish_seq, xo, done);
         }
     }
 }
@@ -531,9 +511,9 @@ __global__ __launch_bounds__(TPB) void track_lm_loop_kernel(TrackParamsDev P)
             P.state->iteration = have ? s_lm.iteration : 0;
             P.state->lm_overflow = s_timeout ? 4 : 0;              // (a later round of the call finds it and leaves; the round that publishes reports it)
             if (P.publish) {
-                for (int i = 0; i < 7; ++i) P.publish->x[i] = have ? s_lm.x[i] : (P.use_init ? P.init_pose[i] : P.state->x[i]);
-                P.publish->done = 1 | (s_timeout ? 4 : 0);
-                __hip_atomic_store(&P.publish->seq, P.publish_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+                double x[7];
+                for (int i = 0; i < 7; ++i) x[i] = have ? s_lm.x[i] : (P.use_init ? P.init_pose[i] : P.state->x[i]);
+                publish_pose<false>(P.publish, P.publish_seq, x, 1 | (s_timeout ? 4 : 0));
             }
         }
     }

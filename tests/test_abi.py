@@ -68,6 +68,19 @@ def test_product_does_not_reference_the_oracle():
                 assert "oracle" not in txt.lower().replace("oracle-free", ""), os.path.join(dp, f)
 
 
+def test_retired_ab_switches_stay_out_of_the_kernels():
+    """the compile-time A/B switches whose losing arms were deleted (verdicts: profiles/r05_knockout_experiments.txt, r06_knockout_experiments.txt) are not named
+    anywhere under m-loam_amd/csrc again"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    retired = ("MLH_LOOP_COH", "MLH_LOOP_SPLIT_STEP", "MLH_LOOP_KEEP_REGS", "MLH_LOOP_SLEEP", "MLH_LOOP_TAG_SLEEP", "MLH_EXP", "MLH_KNN_HEAVY_FIRST",
+               "MLH_SS_HEAP_PAR", "MLH_SS_WAVE_SEARCH", "MLH_FPP_WAVES")
+    pat = re.compile(r"\b(" + "|".join(retired) + r")\b")
+    for dp, _, files in os.walk(os.path.join(root, "m-loam_amd", "csrc")):
+        for f in files:
+            txt = open(os.path.join(dp, f), errors="ignore").read()
+            assert not pat.search(txt), (os.path.join(dp, f), pat.search(txt).group(0))
+
+
 def test_compound_pose_with_cov_host(mla, orc):
     """mlh_compound_pose_with_cov is host arithmetic (no GPU needed): it must agree with the oracle's restatement of
     compoundPoseWithCov (associate_uct.hpp:90-147), which test_oracle_numerics pins against Monte-Carlo sampling."""
