@@ -1,7 +1,6 @@
 // extern "C" surface of libmloam_hip.so (see include/mloam_hip.h for the contract and the reference interfaces each
 // entry point replaces). Host logic only: staging, launch sequencing, result unpacking.
 #include "ctx.hpp"
-#include <chrono>
 #include <cstdlib>
 #include "dev_math.hpp"
 #include <algorithm>
@@ -237,15 +236,10 @@ __global__ void stream_flag_kernel(unsigned long long *h, unsigned long long seq
 
 hipError_t stream_flag_post(mlh_ctx *ctx, unsigned long long *seq_out)
 {
-    if (!ctx->h_sync) {
-        void *p = nullptr;
-        hipError_t e = hipHostMalloc(&p, 64, hipHostMallocDefault);
-        if (e != hipSuccess) return e;
-        ctx->h_sync = static_cast<unsigned long long *>(p);
-        *ctx->h_sync = 0;
-    }
+    const hipError_t e = ctx->h_sync.ensure(64, 0, true);
+    if (e != hipSuccess) return e;
     const unsigned long long seq = ++ctx->sync_seq;
-    MLH_LAUNCH(stream_flag_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->h_sync, seq);
+    MLH_LAUNCH(stream_flag_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->h_sync.as<unsigned long long>(), seq);
     *seq_out = seq;
     return hipGetLastError();
 }
@@ -253,13 +247,8 @@ hipError_t stream_flag_post(mlh_ctx *ctx, unsigned long long *seq_out)
 // the word only grows (one stream, launches in order): anything at or past `seq` means the work enqueued before that post is done
 hipError_t stream_flag_wait(mlh_ctx *ctx, unsigned long long seq)
 {
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(ctx->h_sync, __ATOMIC_ACQUIRE) < seq) {
-        if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return hipStreamSynchronize(ctx->stream);
-        host_wait_relax(spins);
-    }
-    return hipSuccess;
+    const unsigned long long *word = ctx->h_sync.as<unsigned long long>();
+    return host_spin([=] { return __atomic_load_n(word, __ATOMIC_ACQUIRE) >= seq; }) ? hipSuccess : hipStreamSynchronize(ctx->stream);
 }
 
 hipError_t stream_wait_spin(mlh_ctx *ctx)
@@ -276,11 +265,8 @@ hipError_t stream_wait_spin(mlh_ctx *ctx)
 // is polling. which < 0: record 0; otherwise record 1 + (which & 1).
 static int publish_slot(mlh_ctx *ctx, HostPublish **h, unsigned long long *seq, int which = -1)
 {
-    if (!ctx->h_state) {
-        MLH_HIP(ctx, hipHostMalloc(&ctx->h_state, 3 * sizeof(HostPublish), hipHostMallocDefault));
-        std::memset(ctx->h_state, 0, 3 * sizeof(HostPublish));
-    }
-    *h = static_cast<HostPublish *>(ctx->h_state) + (which < 0 ? 0 : 1 + (which & 1));
+    MLH_HIP(ctx, ctx->h_state.ensure(3 * sizeof(HostPublish), 0, true));
+    *h = ctx->h_state.as<HostPublish>() + (which < 0 ? 0 : 1 + (which & 1));
     *seq = ++ctx->publish_seq;
     return MLH_OK;
 }
@@ -288,18 +274,8 @@ static int publish_slot(mlh_ctx *ctx, HostPublish **h, unsigned long long *seq, 
 // spin until the device has stored `seq`; every kernel enqueued before the publishing one has completed when this returns
 static int wait_published(mlh_ctx *ctx, unsigned long long seq, HostPublish &out, void *record = nullptr)
 {
-    HostPublish *h = static_cast<HostPublish *>(record ? record : ctx->h_state);
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) != seq) {
-        if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-            // not the fast case (a long LM run, a profiler, a fault): fall back to the blocking wait, which also surfaces errors
-            MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            if (__atomic_load_n(&h->seq, __ATOMIC_ACQUIRE) != seq) return fail(ctx, MLH_ERR_HIP, "pose publication did not arrive");
-            break;
-        }
-        host_wait_relax(spins);
-    }
+    HostPublish *h = static_cast<HostPublish *>(record ? record : ctx->h_state.p);
+    { const int rc = host_wait_seq(ctx, &h->seq, seq, ctx->stream, "pose publication did not arrive"); if (rc) return rc; }
     out = *h;
     // several ranks joined by the mailbox communicator: the launches behind this publication exchanged records with the peers inside their finish. A peer that
     // never arrived leaves the error word set (p2p_dev.hpp): no solve entry point returns a pose built on partial sums as if it were the job's
@@ -465,54 +441,25 @@ void mlh_destroy(mlh_ctx *ctx)
 {
     if (!ctx) return;
     (void)hipSetDevice(ctx->device);
+    // every stream runs dry before anything it may still use is let go of
     (void)hipStreamSynchronize(ctx->stream);
+    if (ctx->stream2) (void)hipStreamSynchronize(ctx->stream2);
+    if (ctx->ahead.cs) (void)hipStreamSynchronize(ctx->ahead.cs);
     prof_collect(ctx);
     for (auto e : ctx->prof.pool) (void)hipEventDestroy(e);
-    for (int k = 0; k < 2; ++k) {
-        for (int set = 0; set < 2; ++set) {
-            MapGrid &m = ctx->map_sets[set][k];
-            m.raw.release(); m.sorted.release(); m.cell_id.release(); m.cell_start.release(); m.cell_fill.release(); m.block_sums.release(); m.bounds.release(); m.occ.release();
-        }
-        FeatSet &f = ctx->feat[k];
-        f.pts.release(); f.covd.release(); f.corr.release(); f.nbr.release(); f.r.release(); f.J.release(); f.flag8.release(); f.fps_order.release();
-    }
-    ScanBuf &s = ctx->scan;
-    s.pts.release(); s.start.release(); s.end.release(); s.curvature.release(); s.label.release(); s.picked.release(); s.stage.release();
-    s.ring_counts.release(); s.ring_offsets.release(); s.totals.release();
-    for (int i = 0; i < 4; ++i) s.lists[i].release();
-    s.vox_stage.release(); s.vox_out.release(); s.ring_vox.release(); s.vox_keys.release(); s.vox_perm.release(); ctx->uct_buf.release(); ctx->fused[0].release(); ctx->fused[1].release(); ctx->fused_cnt.release(); ctx->fused_part.release();
-    { TrackSet &t = ctx->track; for (int k = 0; k < 2; ++k) { MapGrid &m = t.grid[k]; m.raw.release(); m.sorted.release(); m.cell_id.release(); m.cell_start.release(); m.cell_fill.release(); m.block_sums.release(); m.bounds.release(); t.ring[k].release(); t.ring_start[k].release(); t.walk[k].release(); t.cur[k].release(); t.corr[k].release(); } }
-    { OdomSet &o = ctx->odom; o.tab.release(); o.idx.release(); o.poses.release(); o.r.release(); o.J.release(); o.perm.release(); o.tile_group.release(); o.partial.release(); o.ne_out.release(); o.solve_aux.release(); }
-    { SegBuf &g = ctx->seg; g.raw.release(); g.pix.release(); g.owner.release(); g.range.release(); g.ground.release(); g.keep.release(); }
-    { VoxBuf &v = ctx->vox; v.in.release(); v.bounds.release(); v.cell.release(); v.word_of.release(); v.wpre.release(); v.cnt.release(); v.members.release(); v.vox_of.release(); v.sorted_idx.release(); v.leader.release(); v.out.release(); v.sums.release(); v.total.release(); }
-    ctx->state.release(); ctx->partials.release(); ctx->ticket.release(); ctx->stats.release(); ctx->knn_q.release(); ctx->knn_idx.release(); ctx->knn_d.release(); ctx->tmp.release(); ctx->stdsort.release(); ctx->allreduce_buf.release(); ctx->oob_flag.release();
     comm_destroy(ctx);
     keyframes_release(ctx);
-    if (ctx->h_state) (void)hipHostFree(ctx->h_state);
-    if (ctx->h_solve) (void)hipHostFree(ctx->h_solve);
-    if (ctx->h_occ) (void)hipHostFree(ctx->h_occ);
-    for (int k = 0; k < 2; ++k) if (ctx->select_host[k]) (void)hipHostFree(ctx->select_host[k]);
-    if (ctx->vox_order_host) (void)hipHostFree(ctx->vox_order_host);
-    if (ctx->fused_host) (void)hipHostFree(ctx->fused_host);
-    if (ctx->h_scratch) (void)hipHostFree(ctx->h_scratch);
-    if (ctx->h_sync) (void)hipHostFree(ctx->h_sync);
     if (ctx->ev_handover) (void)hipEventDestroy(ctx->ev_handover);
-    if (ctx->h_rings) (void)hipHostFree(ctx->h_rings);
-    if (ctx->h_pts) (void)hipHostFree(ctx->h_pts);
-    for (int i = 0; i < 2; ++i) if (ctx->ev_pts[i]) (void)hipEventDestroy(ctx->ev_pts[i]);
-    for (int i = 0; i < 2; ++i) if (ctx->ev_rings[i]) (void)hipEventDestroy(ctx->ev_rings[i]);
-    if (ctx->h_dev_err) (void)hipHostFree(ctx->h_dev_err);
     for (int i = 0; i < 2; ++i) if (ctx->ev_set_built[i]) (void)hipEventDestroy(ctx->ev_set_built[i]);
-    if (ctx->stream2) { (void)hipStreamSynchronize(ctx->stream2); (void)hipStreamDestroy(ctx->stream2); }
     if (ctx->ev_scan_reader) (void)hipEventDestroy(ctx->ev_scan_reader);
-    if (ctx->ahead.cs) {
-        (void)hipStreamSynchronize(ctx->ahead.cs); (void)hipStreamDestroy(ctx->ahead.cs);
-        if (ctx->ahead.ev_arrived) (void)hipEventDestroy(ctx->ahead.ev_arrived);
-        if (ctx->ahead.ev_consumed) (void)hipEventDestroy(ctx->ahead.ev_consumed);
-        ctx->ahead.buf.release();
-    }
-    (void)hipStreamDestroy(ctx->stream);
+    if (ctx->ahead.ev_arrived) (void)hipEventDestroy(ctx->ahead.ev_arrived);
+    if (ctx->ahead.ev_consumed) (void)hipEventDestroy(ctx->ahead.ev_consumed);
+    // The device and pinned blocks: every DevBuf / PinnedBuf member frees its own -- the device is set and every stream drained. The streams themselves go LAST, behind
+    // the frees, as they always did for most of the memory. (With them destroyed first, the two programs that hold no other stream on the device -- the C++
+    // framebench, scripts/soak_schedule.py -- did not end on the MI355X; in this order a process that creates, uses and destroys two contexts does.)
+    hipStream_t streams[3] = {ctx->ahead.cs, ctx->stream2, ctx->stream};
     delete ctx;
+    for (hipStream_t st : streams) if (st) (void)hipStreamDestroy(st);
 }
 
 const char *mlh_last_error(const mlh_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -634,19 +581,8 @@ int mlh_scan_upload(mlh_ctx *ctx, const void *points, int stride_bytes, int inte
         static const bool stage_pinned = std::getenv("MLH_SCAN_STAGE_PINNED") && std::atoi(std::getenv("MLH_SCAN_STAGE_PINNED")) != 0;
         if (!caller_pinned && stage_pinned) {
             const size_t bytes = rec.bytes();
-            if (bytes > ctx->h_pts_cap) {
-                MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                if (ctx->h_pts) (void)hipHostFree(ctx->h_pts);
-                ctx->h_pts = nullptr; ctx->h_pts_cap = 0;
-                const size_t cap = ((bytes + bytes / 4 + 4095) / 4096) * 4096;
-                MLH_HIP(ctx, hipHostMalloc(&ctx->h_pts, 2 * cap, hipHostMallocDefault));
-                ctx->h_pts_cap = cap;
-                for (int i = 0; i < 2; ++i) if (!ctx->ev_pts[i]) MLH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_pts[i], hipEventDisableTiming));
-                ctx->ev_pts_used[0] = ctx->ev_pts_used[1] = false;
-            }
-            pts_half = int(ctx->pts_turn++ & 1);
-            if (ctx->ev_pts_used[pts_half]) MLH_HIP(ctx, hipEventSynchronize(ctx->ev_pts[pts_half]));      // two uploads ago
-            void *dst = static_cast<char *>(ctx->h_pts) + size_t(pts_half) * ctx->h_pts_cap;
+            void *dst = nullptr;
+            MLH_HIP(ctx, ctx->h_pts.take(bytes, ((bytes + bytes / 4 + 4095) / 4096) * 4096, ctx->stream, &pts_half, &dst));
             std::memcpy(dst, points, bytes);
             rec.p = static_cast<const unsigned char *>(dst);
         }
@@ -667,26 +603,15 @@ int mlh_scan_upload(mlh_ctx *ctx, const void *points, int stride_bytes, int inte
     int rc = stage_points(ctx, rec, intensity_offset_bytes >= 0 ? intensity_offset_bytes : PACK_W_ZERO, sb.pts, nullptr, ctx->tmp);
     if (rc) return rc;
     if (from_ahead) { MLH_HIP(ctx, hipEventRecord(AH.ev_consumed, ctx->stream)); AH.consumed_recorded = true; }
-    if (pts_half >= 0) {
-        MLH_HIP(ctx, hipEventRecord(ctx->ev_pts[pts_half], ctx->stream));
-        ctx->ev_pts_used[pts_half] = true;
-    }
+    if (pts_half >= 0) MLH_HIP(ctx, ctx->h_pts.record(pts_half, ctx->stream));
     // The ring tables go to the device from a pinned block the context owns (two halves, used alternately; an event says when a half's copy has been read):
     // nothing has to be waited for before this call returns, so the host enqueues the extraction while the points are still being uploaded -- a blocking
     // wait here was ~40 us of idle GPU per frame (profiles/r03_frame_timeline.txt: the gap in front of the curvature kernel).
     const size_t ring_bytes = sizeof(int) * 2 * size_t(n_rings);
-    if (ring_bytes > ctx->h_rings_cap) {
-        MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->h_rings) (void)hipHostFree(ctx->h_rings);
-        ctx->h_rings = nullptr; ctx->h_rings_cap = 0;
-        MLH_HIP(ctx, hipHostMalloc(&ctx->h_rings, 2 * (ring_bytes + ring_bytes / 2), hipHostMallocDefault));
-        ctx->h_rings_cap = ring_bytes + ring_bytes / 2;
-        for (int i = 0; i < 2; ++i) if (!ctx->ev_rings[i]) MLH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_rings[i], hipEventDisableTiming));
-        ctx->ev_rings_used[0] = ctx->ev_rings_used[1] = false;
-    }
-    const int half = int(ctx->rings_turn++ & 1);
-    if (ctx->ev_rings_used[half]) MLH_HIP(ctx, hipEventSynchronize(ctx->ev_rings[half]));        // two uploads ago: long done
-    int *hs = reinterpret_cast<int *>(static_cast<char *>(ctx->h_rings) + size_t(half) * ctx->h_rings_cap), *he = hs + n_rings;
+    int half = 0;
+    void *ring_dst = nullptr;
+    MLH_HIP(ctx, ctx->h_rings.take(ring_bytes, ring_bytes + ring_bytes / 2, ctx->stream, &half, &ring_dst));
+    int *hs = static_cast<int *>(ring_dst), *he = hs + n_rings;
     if (mem == MLH_MEM_HOST) {
         std::memcpy(hs, scan_start, sizeof(int) * n_rings);
         std::memcpy(he, scan_end, sizeof(int) * n_rings);
@@ -708,8 +633,7 @@ int mlh_scan_upload(mlh_ctx *ctx, const void *points, int stride_bytes, int inte
     MLH_HIP(ctx, sb.start.ensure(sizeof(int) * 2 * size_t(n_rings)));                  // [start | end], as they sit in the pinned block: one copy
     MLH_HIP(ctx, hipMemcpyAsync(sb.start.p, hs, sizeof(int) * 2 * n_rings, hipMemcpyHostToDevice, ctx->stream));
     sb.end_alias = sb.start.as<int>() + n_rings;
-    MLH_HIP(ctx, hipEventRecord(ctx->ev_rings[half], ctx->stream));
-    ctx->ev_rings_used[half] = true;
+    MLH_HIP(ctx, ctx->h_rings.record(half, ctx->stream));
     // a buffer the CALLER pinned is read by the copy engine in place, asynchronously, and is the caller's to reuse after this call: that (rare) case waits here
     if (caller_pinned) MLH_HIP(ctx, stream_wait_spin(ctx));
     sb.n = n; sb.n_rings = n_rings; sb.max_ring_len = max_len;
@@ -1016,7 +940,7 @@ int mlh_map_set_pair_overlapped(mlh_ctx *ctx, const void *surf_points, int n_sur
                                 float min_match_sq_dis, int mem)
 {
     if (!ctx) return MLH_ERR_INVALID;
-    if (!ctx->solve_pending && mem != MLH_MEM_DEVICE) return mlh_map_set_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, min_match_sq_dis, mem);
+    if (!ctx->solves.pending() && mem != MLH_MEM_DEVICE) return mlh_map_set_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, min_match_sq_dis, mem);
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->map_read_unsynced) {
         // mlh_pure_odom_add_matches returns with its map-reading launch still queued. Whatever set it reads, it must be done before a set is rewritten -- also
@@ -1058,12 +982,12 @@ int mlh_map_set_pair_overlapped(mlh_ctx *ctx, const void *surf_points, int n_sur
     // The other set's last reader is the solve submitted BEFORE the one in flight; with at most one solve in flight here it has been collected, i.e. it is done:
     // no device-side wait is needed before its buffers are overwritten. (Round 3 first ordered the two streams with events on the solver's stream -- a record
     // after every solve, a wait before the next: two barrier packets, ~10 us of idle stream per frame in the kernel trace. Both are gone: the host orders.)
-    if (ctx->solve_seq - ctx->solve_collected > 1) return fail(ctx, MLH_ERR_STATE, "collect the older solve (mlh_gn_solve_end) before staging the next frame's maps");
+    if (ctx->solves.in_flight() > 1) return fail(ctx, MLH_ERR_STATE, "collect the older solve (mlh_gn_solve_end) before staging the next frame's maps");
     const int target = 1 - ctx->map_set_cur;
     // ... unless the caller stages twice beside ONE solve (begin on A; overlapped -> B; overlapped -> A again with that solve uncollected): then the target's reader
     // is the solve in flight, and the set is rewritten only once the main stream has run dry (scripts/soak_schedule.py found this as a rare, timing-dependent
     // difference of 1e-5 m: the index of A rebuilt under a correspondence launch)
-    if (ctx->set_reader_seq[target] > ctx->solve_collected) MLH_HIP(ctx, stream_wait_spin(ctx));
+    if (ctx->solves.set_has_reader(target)) MLH_HIP(ctx, stream_wait_spin(ctx));
     hipStream_t main_stream = ctx->stream;
     ctx->stream = ctx->stream2;                    // everything map_set_impl enqueues (and its profiling brackets) goes to the staging stream ...
     ctx->map = ctx->map_sets[target];              // ... and into the other set
@@ -1077,15 +1001,8 @@ int mlh_map_set_pair_overlapped(mlh_ctx *ctx, const void *surf_points, int n_sur
     // the index must be complete before anything that reads it is enqueued on the solver's stream: waited for HERE, on the host (the build is ~30 us of
     // small launches, the solve in flight another ~100), so that the solver's stream carries no cross-stream wait at all
     MLH_HIP(ctx, hipEventRecord(ctx->ev_set_built[target], ctx->stream2));
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned spins = 0;
-        while (hipEventQuery(ctx->ev_set_built[target]) == hipErrorNotReady) {
-            if ((++spins & 0xff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream2)); break; }
-            host_wait_relax(spins);
-        }
-    }
-    return MLH_OK;
+    hipEvent_t built = ctx->ev_set_built[target];
+    return host_wait(ctx, [=] { return hipEventQuery(built) != hipErrorNotReady; }, ctx->stream2, nullptr);
 }
 
 int mlh_map_rebuild(mlh_ctx *ctx, int kind)
@@ -1586,19 +1503,16 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
 {
     // several ranks: fine with the mailbox communicator (the exchange happens inside the launches, the host is not involved); not over RCCL
     if (ctx->comm) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_gn_solve_begin under an RCCL communicator: the sharded solve there is a host-driven sequence of launches and collectives (use the mailbox communicator)");
-    if (ctx->solve_seq - ctx->solve_collected >= 2) return fail(ctx, MLH_ERR_STATE, "two solves are already in flight: collect the older one with mlh_gn_solve_end first");
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_state(ctx, 0);
+    unsigned long long seq = 0;
+    HostPublish *rec = nullptr;
+    mlh_ctx::SolveSlot *slot = nullptr;
+    int rc = ctx->solves.admit(ctx, "two solves are already in flight: collect the older one with mlh_gn_solve_end first", &seq, &rec, &slot);
     if (rc) return rc;
+    if ((rc = ensure_state(ctx, 0))) return rc;
     const int mask = solve_kind_mask(ctx);
     if (!mask) return fail(ctx, MLH_ERR_STATE, "no map/features staged");
-    if (!ctx->h_solve) {
-        MLH_HIP(ctx, hipHostMalloc(&ctx->h_solve, 2 * sizeof(HostPublish), hipHostMallocDefault));      // one record per solve in flight
-        std::memset(ctx->h_solve, 0, 2 * sizeof(HostPublish));
-    }
-    const unsigned long long seq = ctx->solve_seq + 1;
-    ctx->solve_slot[seq & 1].kind = 0;
-    HostPublish *rec = static_cast<HostPublish *>(ctx->h_solve) + (seq & 1);
+    slot->kind = 0;
     const bool defer = n_iters >= 2 && gn_defer_applies(ctx, mask);
     // The previous solve may have left its LAST iteration as tile records (gn_pending). A chained, deferred solve completes it in its own first launch -- unless this
     // frame needs a larger record buffer (the records would not survive the reallocation); everything else completes it now, before the chain launch reads the pose.
@@ -1643,9 +1557,7 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
         ctx->gn_pending.rec = rec;
         ctx->gn_pending.seq = seq;
     }
-    ctx->solve_seq = seq;
-    ctx->set_reader_seq[ctx->map_set_cur] = seq;
-    ctx->solve_pending = true;
+    ctx->solves.commit(seq, ctx->map_set_cur);
     return MLH_OK;
 }
 
@@ -1658,26 +1570,25 @@ int mlh_gn_solve_begin(mlh_ctx *ctx, const double pose_in[7], int n_iters, const
 int mlh_gn_solve_begin_chained(mlh_ctx *ctx, const double wodom_prev[7], const double wodom_cur[7], int n_iters, const mlh_solver_opts *opts)
 {
     if (!ctx || !wodom_prev || !wodom_cur || !opts || n_iters <= 0) return MLH_ERR_INVALID;
-    if (ctx->solve_seq == 0) return fail(ctx, MLH_ERR_STATE, "mlh_gn_solve_begin_chained continues from the pose a previous solve left on the device: submit the first frame with mlh_gn_solve_begin");
+    if (ctx->solves.submitted == 0) return fail(ctx, MLH_ERR_STATE, "mlh_gn_solve_begin_chained continues from the pose a previous solve left on the device: submit the first frame with mlh_gn_solve_begin");
     return gn_solve_submit(ctx, nullptr, wodom_prev, wodom_cur, n_iters, opts);
 }
 
 int mlh_gn_solve_end(mlh_ctx *ctx, double pose_out[7])
 {
     if (!ctx || !pose_out) return MLH_ERR_INVALID;
-    if (ctx->solve_seq == ctx->solve_collected) return fail(ctx, MLH_ERR_STATE, "no solve in flight (mlh_gn_solve_begin)");
-    const unsigned long long seq = ctx->solve_collected + 1;        // the oldest one
-    if (ctx->solve_slot[seq & 1].kind != 0) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_scan2map_begin: collect it with mlh_scan2map_end");
+    if (!ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, "no solve in flight (mlh_gn_solve_begin)");
+    const unsigned long long seq = ctx->solves.oldest();
+    if (ctx->solves.slot[seq & 1].kind != 0) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_scan2map_begin: collect it with mlh_scan2map_end");
     if (ctx->gn_pending.active && ctx->gn_pending.seq == seq) {      // nobody chained a successor behind it: its last iteration is completed here
         const int frc = gn_flush_pending(ctx);
         if (frc) return frc;
     }
     HostPublish hp;
-    int rc = wait_published(ctx, seq, hp, static_cast<HostPublish *>(ctx->h_solve) + (seq & 1));
-    ctx->solve_collected = seq;
-    ctx->solve_pending = ctx->solve_seq != ctx->solve_collected;
+    int rc = wait_published(ctx, seq, hp, ctx->solves.record(seq));
+    ctx->solves.retire(seq);
     if (rc) return rc;
-    if (!ctx->solve_pending && (rc = prof_drain(ctx, (1u << MLH_K_FIT) | (1u << MLH_K_SOLVE)))) return rc;
+    if (!ctx->solves.pending() && (rc = prof_drain(ctx, (1u << MLH_K_FIT) | (1u << MLH_K_SOLVE)))) return rc;
     for (int i = 0; i < 7; ++i) pose_out[i] = hp.x[i];
     return MLH_OK;
 }
@@ -1998,18 +1909,15 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     if (ctx->comm) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_scan2map_begin under an RCCL communicator: the sharded LM iteration there is a host-driven sequence of launches and collectives (use the mailbox communicator)");
     if (opts->gf_method != MLH_GF_WO) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_scan2map_begin with a good-feature selection: the selection loops run on the host between the launches (use mlh_scan2map)");
     if (opts->max_outer <= 0) return fail(ctx, MLH_ERR_INVALID, "max_outer must be positive");
-    if (ctx->solve_seq - ctx->solve_collected >= 2) return fail(ctx, MLH_ERR_STATE, "two solves are already in flight: collect the older one first");
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
-    int rc = ensure_state(ctx, 0);
+    unsigned long long seq = 0;
+    HostPublish *rec = nullptr;
+    mlh_ctx::SolveSlot *slot_p = nullptr;
+    int rc = ctx->solves.admit(ctx, "two solves are already in flight: collect the older one first", &seq, &rec, &slot_p);
     if (rc) return rc;
-    if (!ctx->h_solve) {
-        MLH_HIP(ctx, hipHostMalloc(&ctx->h_solve, 2 * sizeof(HostPublish), hipHostMallocDefault));
-        std::memset(ctx->h_solve, 0, 2 * sizeof(HostPublish));
-    }
-    const unsigned long long seq = ctx->solve_seq + 1;
-    HostPublish *rec = static_cast<HostPublish *>(ctx->h_solve) + (seq & 1);
-    mlh_ctx::SolveSlot &slot = ctx->solve_slot[seq & 1];
+    mlh_ctx::SolveSlot &slot = *slot_p;
+    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
+    if ((rc = ensure_state(ctx, 0))) return rc;
     // everything that can refuse the frame is checked BEFORE the chain launch below rewrites the device pose: a refused mlh_scan2map_begin_chained leaves the
     // state as it found it, so the caller's retry does not apply transformUpdate / transformAssociateToMap twice
     const bool have_maps = scan2map_has_maps(ctx);
@@ -2029,10 +1937,10 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
             MLH_LAUNCH(publish_kernel, dim3(1), dim3(64), 0, ctx->stream, (const SolverState *)ctx->state.as<SolverState>(), rec, seq);
             MLH_HIP(ctx, hipGetLastError());
         }
-        ctx->solve_seq = seq; ctx->solve_pending = true;
+        ctx->solves.commit(seq, -1);      // (nothing of it reads a map)
         return MLH_OK;
     }
-    const int budget = std::max(1, std::min(lm_lookahead > 0 ? lm_lookahead : ctx->lm_lookahead_auto, opts->max_lm_iterations));
+    const int budget = std::max(1, std::min(lm_lookahead > 0 ? lm_lookahead : ctx->solves.lm_lookahead_auto, opts->max_lm_iterations));
     // the consumer-side form of the LM launches (scan2map_polled): budget + 1 launches run `budget` LM steps
     const bool lmc = !ctx->p2p.active && lm_consumer_enabled(ctx);
     // ... or one launch per LM loop, which ends on the device when the loop does: no budget, nothing to overflow (an explicit lm_lookahead keeps the launches it counts)
@@ -2049,9 +1957,7 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
             if ((rc = lmc ? lm_consume_launch(ctx, b) : linearize_launch(ctx, b))) return rc;
         }
     }
-    ctx->solve_seq = seq;
-    ctx->set_reader_seq[ctx->map_set_cur] = seq;
-    ctx->solve_pending = true;
+    ctx->solves.commit(seq, ctx->map_set_cur);
     return MLH_OK;
 }
 
@@ -2064,7 +1970,7 @@ int mlh_scan2map_begin(mlh_ctx *ctx, const double pose_in[7], const mlh_solver_o
 int mlh_scan2map_begin_chained(mlh_ctx *ctx, const double wodom_prev[7], const double wodom_cur[7], const mlh_solver_opts *opts, int lm_lookahead)
 {
     if (!ctx || !wodom_prev || !wodom_cur || !opts) return MLH_ERR_INVALID;
-    if (ctx->solve_seq == 0) return fail(ctx, MLH_ERR_STATE, "mlh_scan2map_begin_chained continues from the pose a previous solve left on the device: submit the first frame with mlh_scan2map_begin");
+    if (ctx->solves.submitted == 0) return fail(ctx, MLH_ERR_STATE, "mlh_scan2map_begin_chained continues from the pose a previous solve left on the device: submit the first frame with mlh_scan2map_begin");
     return scan2map_submit(ctx, nullptr, wodom_prev, wodom_cur, opts, lm_lookahead);
 }
 
@@ -2072,9 +1978,9 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
 {
     if (!ctx || !pose_out) return MLH_ERR_INVALID;
     if (status_out) *status_out = 0;
-    if (ctx->solve_seq == ctx->solve_collected) return fail(ctx, MLH_ERR_STATE, "no solve in flight (mlh_scan2map_begin)");
-    const unsigned long long seq = ctx->solve_collected + 1;        // the oldest one
-    mlh_ctx::SolveSlot slot = ctx->solve_slot[seq & 1];
+    if (!ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, "no solve in flight (mlh_scan2map_begin)");
+    const unsigned long long seq = ctx->solves.oldest();
+    mlh_ctx::SolveSlot slot = ctx->solves.slot[seq & 1];
     if (slot.kind == 0) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_gn_solve_begin: collect it with mlh_gn_solve_end");
     HostPublish hp;
     int rc = MLH_OK;
@@ -2082,14 +1988,12 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
         for (int i = 0; i < 7; ++i) hp.x[i] = slot.start[i];
         hp.done = 1;
     } else {
-        rc = wait_published(ctx, seq, hp, static_cast<HostPublish *>(ctx->h_solve) + (seq & 1));
+        rc = wait_published(ctx, seq, hp, ctx->solves.record(seq));
     }
-    ctx->solve_collected = seq;
-    ctx->solve_pending = ctx->solve_seq != ctx->solve_collected;
-    // a younger solve chained behind THIS one began from whatever pose this one left on the device: if this one did not produce a result, neither did that one
-    auto taint_successor = [&]() { if (ctx->solve_pending && ctx->solve_slot[(seq + 1) & 1].chained) ctx->solve_slot[(seq + 1) & 1].tainted = true; };
+    ctx->solves.retire(seq);
+    auto taint_successor = [&]() { ctx->solves.taint_successor(seq); };
     if (rc) { taint_successor(); return rc; }
-    if (!ctx->solve_pending && (rc = prof_drain(ctx))) return rc;
+    if (!ctx->solves.pending() && (rc = prof_drain(ctx))) return rc;
     const bool barrier_given_up = slot.kind == 1 && (hp.done & 4);       // (a one-launch LM loop whose workgroups were not all resident: lm_loop_kernel)
     if (barrier_given_up) demote_loop_gate(ctx, 0, slot.loop_tiles);
     if (slot.kind == 1 && !barrier_given_up) {
@@ -2097,7 +2001,7 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
         // overflowed doubles it
         const int used = int(hp.xb[2][0]);
         const bool ok = (hp.done & 1) && !(hp.done & 2);
-        ctx->lm_lookahead_auto = ok ? std::max(3, used + 2) : std::min(2 * std::max(ctx->lm_lookahead_auto, 4), slot.opts.max_lm_iterations);
+        ctx->solves.lm_lookahead_auto = ok ? std::max(3, used + 2) : std::min(2 * std::max(ctx->solves.lm_lookahead_auto, 4), slot.opts.max_lm_iterations);
     }
     if (slot.kind == 2 || ((hp.done & 1) && !(hp.done & 6))) {
         for (int i = 0; i < 7; ++i) pose_out[i] = hp.x[i];
@@ -2113,7 +2017,7 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
     // the look-ahead was too short for this frame -- or its one-launch loop gave its barrier up
     double start[7];
     for (int i = 0; i < 7; ++i) start[i] = slot.chained ? hp.xb[1][i] : slot.start[i];
-    if (!ctx->solve_pending && ctx->stage_epoch == slot.epoch && !slot.tainted) {
+    if (!ctx->solves.pending() && ctx->stage_epoch == slot.epoch && !slot.tainted) {
         // nothing younger is chained behind it and the frame's maps and features are still the staged ones: solve it as mlh_scan2map would have (after a barrier
         // given up on: through the launch-per-iteration form)
         for (int i = 0; i < 7; ++i) pose_out[i] = start[i];
@@ -2154,7 +2058,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     // the loop kernel's barrier wants every tile's workgroup resident: the BOUND's tiles, since the real count is not known here
     const int bound_tiles = tiles_of(n_surf) + tiles_of(n_corner);
     if (!fused_pair || !scan2map_has_maps(ctx) || distributed(ctx) || ctx->comm || opts->gf_method != MLH_GF_WO || !schedule_on(Schedule::LM_CONSUMER) ||
-        !lm_loop_applies(ctx, 1, bound_tiles) || ctx->solve_seq != ctx->solve_collected || ctx->vox_member_order != 1)
+        !lm_loop_applies(ctx, 1, bound_tiles) || ctx->solves.pending() || ctx->vox_member_order != 1)
         return two_calls();
     { const int frc = gn_flush_pending(ctx); if (frc) return frc; }
     int rc = ensure_state(ctx, 0);
@@ -2184,10 +2088,8 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     if (!rc) rc = collect_loop_pose(ctx, seq, rec, pose, &given_up);
     // the counts were published by the thinning's last launch, long before the pose: no wait here in practice
     int real[2] = {0, 0};
-    if (!rc) {
-        if (__atomic_load_n(ctx->thin_seq_host, __ATOMIC_ACQUIRE) != ctx->thin_seq) { MLH_HIP(ctx, hipStreamSynchronize(ctx->stream)); }
-        if (__atomic_load_n(ctx->thin_seq_host, __ATOMIC_ACQUIRE) != ctx->thin_seq) rc = fail(ctx, MLH_ERR_HIP, "the thinned feature counts did not arrive");
-        else { real[0] = ctx->thin_counts_host[0]; real[1] = ctx->thin_counts_host[1]; }
+    if (!rc && !(rc = host_wait_seq(ctx, ctx->thin_seq_host, ctx->thin_seq, ctx->stream, "the thinned feature counts did not arrive"))) {
+        real[0] = ctx->thin_counts_host[0]; real[1] = ctx->thin_counts_host[1];
     }
     if (rc) { (void)hipStreamSynchronize(ctx->stream); for (int k = 0; k < 2; ++k) { ctx->feat[k].m = 0; ctx->feat[k].matched = false; } return rc; }
     stage_counts(real);
@@ -2474,30 +2376,16 @@ int mlh_fused_cloud(mlh_ctx *ctx, int kind, const void **device_points, int32_t 
             *n = 0;
             return MLH_OK;
         }
-        if (!ctx->fused_host) {
-            MLH_HIP(ctx, hipHostMalloc(&ctx->fused_host, 128, hipHostMallocDefault));
-            std::memset(ctx->fused_host, 0, 128);
-            ctx->fused_host_cap = 128;
-        }
-        int *h_cnt = static_cast<int *>(ctx->fused_host);
-        float *h_box = reinterpret_cast<float *>(static_cast<char *>(ctx->fused_host) + 16);
-        unsigned long long *h_seq = reinterpret_cast<unsigned long long *>(static_cast<char *>(ctx->fused_host) + 64);
+        MLH_HIP(ctx, ctx->fused_host.ensure(sizeof(FusedPublish), 0, true));
+        FusedPublish *pub = ctx->fused_host.as<FusedPublish>();
+        int *h_cnt = pub->count;
+        float *h_box = pub->box;
+        unsigned long long *h_seq = &pub->seq;
         const unsigned long long seq = ++ctx->fused_seq;
         MLH_LAUNCH(fused_publish_kernel, dim3(1), dim3(256), 0, ctx->stream, (const int *)(ctx->fused_cnt.as<int>() + 2 * ctx->fused_parts),
                            (const float *)ctx->fused_part.as<float>(), FUSE_BLOCKS, ctx->fused_parts, h_cnt, h_box, h_seq, seq);
         MLH_HIP(ctx, hipGetLastError());
-        {
-            const auto t0 = std::chrono::steady_clock::now();
-            unsigned spins = 0;
-            while (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != seq) {
-                if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-                    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    if (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != seq) return fail(ctx, MLH_ERR_HIP, "the fused clouds' sizes did not arrive");
-                    break;
-                }
-                host_wait_relax(spins);
-            }
-        }
+        { const int rc = host_wait_seq(ctx, h_seq, seq, ctx->stream, "the fused clouds' sizes did not arrive"); if (rc) return rc; }
         ctx->fused_n[0] = h_cnt[0]; ctx->fused_n[1] = h_cnt[1];
         for (int k = 0; k < 2; ++k) for (int d = 0; d < 6; ++d) ctx->fused_minmax[k][d] = h_box[k * 6 + d];
         ctx->fused_dirty = false;

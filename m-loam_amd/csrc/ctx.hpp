@@ -5,6 +5,8 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <chrono>
+#include <cstddef>
 #include <string>
 #include <vector>
 #include <cstdlib>
@@ -85,6 +87,30 @@ struct HostPublish {
     unsigned long long seq;
 };
 
+// The context's 256 pinned bytes of small read-backs (mlh_ctx::h_scratch). The kernels that publish the thinned feature counts receive the addresses of
+// thin_counts and thin_seq (voxel.hip); a copy lands in read_back (read_back_int).
+struct ScratchBlock {
+    int pad0[8];
+    int read_back;                     // one device int on its way to the host
+    int pad1[7];
+    int thin_counts[2];                // the thinned surf / corner feature counts ...
+    int pad2[14];
+    unsigned long long thin_seq;       // ... and the sequence number their publication stores last (system-scope release)
+    unsigned char pad3[120];
+};
+static_assert(offsetof(ScratchBlock, read_back) == 32 && offsetof(ScratchBlock, thin_counts) == 64 && offsetof(ScratchBlock, thin_seq) == 128 &&
+              sizeof(ScratchBlock) == 256, "the scratch block's layout is what the thinning kernels were handed pointers into");
+
+// pinned record mlh_fused_cloud's publication launch fills (fused_publish_kernel gets the three addresses)
+struct FusedPublish {
+    int count[4];                      // the two record counts (padded to 4 ints)
+    float box[12];                     // 2 x 6 bounds
+    unsigned long long seq;            // stored last, with system-scope release
+    unsigned char pad[56];
+};
+static_assert(offsetof(FusedPublish, count) == 0 && offsetof(FusedPublish, box) == 16 && offsetof(FusedPublish, seq) == 64 && sizeof(FusedPublish) == 128,
+              "the fused-cloud publication: counts at 0, bounds at 16, sequence word at 64, 128 bytes");
+
 struct IterStatDev {        // mirrors mlh_iter_stat, written by the device-side update kernels
     int n_surf, n_corner, is_degenerate, lm_iterations, successful_steps, termination;
     double cost, final_cost;
@@ -132,6 +158,69 @@ struct DevBuf {
     }
     void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
     template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+// Page-locked host memory, owned the way DevBuf owns device memory: every pinned block of the library is one of these (the only place that allocates or frees one),
+// a member of the context or of one of its sub-structures, and freed with it.
+struct PinnedBuf {
+    void *p = nullptr;
+    size_t cap = 0;
+    PinnedBuf() = default;
+    PinnedBuf(const PinnedBuf &) = delete;
+    PinnedBuf &operator=(const PinnedBuf &) = delete;
+    ~PinnedBuf() { release(); }
+    // A block of at least `bytes`. One that is too small is DROPPED, contents and all, for a new one of bytes + margin (`zeroed`: cleared; otherwise untouched, the
+    // first touch of a large staging block is its user's). Never synchronises: a caller whose stream may still be copying into or out of the old block drains it first.
+    hipError_t ensure(size_t bytes, size_t margin = 0, bool zeroed = false)
+    {
+        if (bytes <= cap) return hipSuccess;
+        release();
+        const hipError_t e = hipHostMalloc(&p, bytes + margin, hipHostMallocDefault);
+        if (e != hipSuccess) { p = nullptr; return e; }
+        cap = bytes + margin;
+        if (zeroed) std::memset(p, 0, cap);
+        return hipSuccess;
+    }
+    void release() { if (p) { (void)hipHostFree(p); p = nullptr; cap = 0; } }
+    template <typename T> T *as() const { return static_cast<T *>(p); }
+};
+
+// A pinned landing place in two halves used alternately, an event per half: what the host puts into a half goes to the device by a copy enqueued behind it, and the
+// half is written again two turns later -- by then that copy has long run, and the event says so without a wait on the stream (mlh_scan_upload: points, ring tables).
+struct PinnedHalves {
+    PinnedBuf buf;
+    size_t half_bytes = 0;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    bool used[2] = {false, false};
+    unsigned turn = 0;
+    PinnedHalves() = default;
+    PinnedHalves(const PinnedHalves &) = delete;
+    PinnedHalves &operator=(const PinnedHalves &) = delete;
+    ~PinnedHalves() { for (int i = 0; i < 2; ++i) if (ev[i]) (void)hipEventDestroy(ev[i]); }     // (with the context: its streams have been drained by then)
+    // the next half, `bytes` of it usable, once the copy enqueued out of it two turns ago has run; growing (to halves of `half_cap` >= bytes) drains `st` first
+    hipError_t take(size_t bytes, size_t half_cap, hipStream_t st, int *half, void **dst)
+    {
+        if (bytes > half_bytes) {
+            hipError_t e = hipStreamSynchronize(st);
+            if (e != hipSuccess) return e;
+            half_bytes = 0;
+            if ((e = buf.ensure(2 * half_cap)) != hipSuccess) return e;      // (half_cap >= bytes > half_bytes: always larger than the block it replaces)
+            half_bytes = half_cap;
+            for (int i = 0; i < 2; ++i) if (!ev[i] && (e = hipEventCreateWithFlags(&ev[i], hipEventDisableTiming)) != hipSuccess) return e;
+            used[0] = used[1] = false;
+        }
+        *half = int(turn++ & 1);
+        if (used[*half]) { const hipError_t e = hipEventSynchronize(ev[*half]); if (e != hipSuccess) return e; }
+        *dst = buf.as<char>() + size_t(*half) * half_bytes;
+        return hipSuccess;
+    }
+    // the copy out of `half` has been enqueued on `st`
+    hipError_t record(int half, hipStream_t st)
+    {
+        const hipError_t e = hipEventRecord(ev[half], st);
+        if (e == hipSuccess) used[half] = true;
+        return e;
+    }
 };
 
 struct MapGrid {
@@ -231,24 +320,21 @@ struct KfStore {
     DevBuf tab;                  // per-call tables (segments, poses, gather lists)
     DevBuf stage, keep, scan;    // batched association: staged records, keep flags, their scan
     std::vector<unsigned char> htab;
-    int *h_pin = nullptr;        // pinned landing place of the two read-backs
+    PinnedBuf h_pin;             // landing place of the two read-backs (32 ints)
 };
 
 struct SegBuf {    // ImageSegmenter scratch (segment.hip)
     DevBuf raw, pix, owner, range, ground, keep;
     DevBuf edge;               // the cluster search's angle verdicts per pixel (seg_edge_kernel)
     DevBuf outmask, row_cnt;   // device row assembly: the outlier pixels' bit mask (from the host's cluster search), per-row counts of kept points (+ first kept index)
-    void *h_rows = nullptr;    // pinned: [vs + 2] ints the row kernels leave for the host (kept points per row, total, first kept point index)
-    size_t h_rows_cap = 0;
+    PinnedBuf h_rows;      // [vs + 2] ints the row kernels leave for the host (kept points per row, total, first kept point index)
     DevBuf unc;            // points / ground pairs whose bin the device cannot decide (an angle within an ulp-scale margin of a bin edge): [counters 2 x int][records]
     DevBuf fix;            // the host's verdicts for the undecided points: {point index, pixel}
-    void *h_unc = nullptr; // pinned mirror of `unc`
-    size_t h_unc_cap = 0;
-    void *h_img = nullptr;     // pinned: range / owner / ground images as the cluster search reads them, and the outlier mask it writes
-    size_t h_img_cap = 0;
+    PinnedBuf h_unc;       // mirror of `unc`
+    PinnedBuf h_img;       // range / owner / ground images as the cluster search reads them, and the outlier mask it writes
     void *h_bfs = nullptr;     // plain: labels and the cluster search's queue / pushed-pixel arrays
     size_t h_bfs_cap = 0;
-    ~SegBuf() { if (h_unc) (void)hipHostFree(h_unc); if (h_rows) (void)hipHostFree(h_rows); if (h_img) (void)hipHostFree(h_img); std::free(h_bfs); }
+    ~SegBuf() { std::free(h_bfs); }
 };
 
 struct OdomSet {   // staged LidarPureOdom factor table (odom.hip)
@@ -291,6 +377,8 @@ struct Profile {
     std::vector<Pending> pending;
     std::vector<hipEvent_t> pool;
 };
+
+int fail(mlh_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
 
 }  // namespace mlh
 
@@ -339,15 +427,8 @@ struct mlh_ctx {
     mlh::DevBuf knn_q, knn_idx, knn_d;
     mlh::DevBuf tmp;         // H2D staging of caller records before packing
     mlh::DevBuf tmp_stage;   // the same for mlh_map_set_pair_overlapped, whose copies and pack kernels run on the staging stream beside the main stream's
-    void *h_pts = nullptr;   // pinned landing place (two halves) of a caller's PAGEABLE scan points (mlh_scan_upload)
-    size_t h_pts_cap = 0;    // bytes per half
-    hipEvent_t ev_pts[2] = {nullptr, nullptr};
-    bool ev_pts_used[2] = {false, false};
-    unsigned pts_turn = 0;
-    void *h_solve = nullptr; // pinned HostPublish record of a solve submitted with mlh_gn_solve_begin (collected by mlh_gn_solve_end)
-    unsigned long long solve_seq = 0, solve_collected = 0;   // submitted / collected solves (at most two apart)
-    unsigned long long set_reader_seq[2] = {0, 0};            // the youngest submitted solve that reads map set 0 / 1 (mlh_map_set_pair_overlapped: a set is rewritten only behind its readers)
-    struct SolveSlot {                 // what mlh_scan2map_end needs to know about the solve whose record is h_solve[seq & 1]
+    mlh::PinnedHalves h_pts;     // landing place of a caller's PAGEABLE scan points (mlh_scan_upload, MLH_SCAN_STAGE_PINNED=1)
+    struct SolveSlot {                 // what mlh_scan2map_end needs to know about the solve whose record is SolveLedger::record(seq)
         int kind = 0;                  // 0: Gauss-Newton (mlh_gn_solve_begin*), 1: scan2map (mlh_scan2map_begin*), 2: scan2map on maps too small to optimise against (the start pose comes back)
         bool chained = false;
         double start[7] = {0, 0, 0, 0, 0, 0, 1};
@@ -355,12 +436,42 @@ struct mlh_ctx {
         unsigned long long epoch = 0;  // stage_epoch at submission
         bool tainted = false;          // chained behind a frame whose LM loop outgrew its look-ahead: began from an unfinished pose (mlh_scan2map_end status 3)
         int loop_tiles = 0;            // > 0: the frame's LM loops were submitted as one launch each over this many workgroups (lm_loop_kernel)
-    } solve_slot[2];
-    int lm_lookahead_auto = 10;           // mlh_scan2map_begin(lm_lookahead = 0): the previous frame's largest LM iteration count + 2 (10 until a frame has been collected)
+    };
+    // The solves submitted with mlh_gn_solve_begin* / mlh_scan2map_begin* and not yet collected: at most two, numbered from 1 in submission order; solve `seq` publishes
+    // into its own pinned record and is described by slot[seq & 1].
+    struct SolveLedger {
+        mlh::PinnedBuf records;                                   // HostPublish x 2
+        unsigned long long submitted = 0, collected = 0;          // (at most two apart)
+        unsigned long long set_reader[2] = {0, 0};                // the youngest submitted solve that reads map set 0 / 1
+        SolveSlot slot[2];
+        int lm_lookahead_auto = 10;       // mlh_scan2map_begin(lm_lookahead = 0): the previous frame's largest LM iteration count + 2 (10 until a frame has been collected)
+        int in_flight() const { return int(submitted - collected); }
+        bool pending() const { return submitted != collected; }
+        mlh::HostPublish *record(unsigned long long seq) const { return records.as<mlh::HostPublish>() + (seq & 1); }
+        // the next solve's number, record and slot -- or `refusal` (MLH_ERR_STATE) while two are in flight. Nothing is counted until commit().
+        int admit(mlh_ctx *ctx, const char *refusal, unsigned long long *seq, mlh::HostPublish **rec, SolveSlot **s)
+        {
+            if (in_flight() >= 2) return mlh::fail(ctx, MLH_ERR_STATE, refusal);
+            const hipError_t e = records.ensure(2 * sizeof(mlh::HostPublish), 0, true);      // one record per solve in flight
+            if (e != hipSuccess) return mlh::fail(ctx, MLH_ERR_HIP, "pinned records of the solves in flight", e);
+            *seq = submitted + 1; *rec = record(*seq); *s = &slot[*seq & 1];
+            return MLH_OK;
+        }
+        // solve `seq` has been enqueued; reader_of_set >= 0: its launches read that map set (mlh_map_set_pair_overlapped rewrites a set only behind its readers)
+        void commit(unsigned long long seq, int reader_of_set)
+        {
+            submitted = seq;
+            if (reader_of_set >= 0) set_reader[reader_of_set] = seq;
+        }
+        unsigned long long oldest() const { return collected + 1; }
+        void retire(unsigned long long seq) { collected = seq; }
+        bool set_has_reader(int set) const { return set_reader[set] > collected; }
+        // a younger solve chained behind `seq` began from whatever pose that one left on the device: if `seq` did not produce a result, neither did that one
+        void taint_successor(unsigned long long seq) { if (pending() && slot[(seq + 1) & 1].chained) slot[(seq + 1) & 1].tainted = true; }
+    } solves;
     // Bumped on entry by every call that restages a map or a feature set (also when it then fails: the set is disturbed). A frame in flight remembers the value it was
     // submitted under (SolveSlot::epoch); mlh_scan2map_end re-solves it only while that value stands: a re-solve is only sound on the inputs the frame was submitted with.
     unsigned long long stage_epoch = 0;
-    bool solve_pending = false;
     bool map_read_unsynced = false;   // a launch that reads the current map set was enqueued and its call did not wait for it (mlh_pure_odom_add_matches)
     // mlh_scan_upload_ahead: the NEXT scan's points copied to the device on a stream of their own (the copy engine beside this frame's kernels); the mlh_scan_upload
     // that names the same host buffer packs from `buf` instead of copying
@@ -373,8 +484,8 @@ struct mlh_ctx {
         bool valid = false, consumed_recorded = false, src_pinned = false;
         unsigned long long issued = 0, used = 0;     // (tests)
     } ahead;
-    void *h_state = nullptr; // pinned HostPublish record the device writes the result pose(s) into (capi.hip)
-    void *h_occ = nullptr;   // pinned mirror of the two maps' occupancy totals (grid.hip): {cells, squares} per kind, written behind every index build
+    mlh::PinnedBuf h_state;  // three HostPublish records the device writes the result pose(s) into (capi.hip: publish_slot)
+    mlh::PinnedBuf h_occ;    // mirror of the two maps' occupancy totals (grid.hip): {cells, squares} per kind, written behind every index build
     unsigned long long publish_seq = 0;
     mlh::DevBuf uct_buf;     // point-uncertainty scratch
     mlh::VoxBuf vox;
@@ -384,18 +495,14 @@ struct mlh_ctx {
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}
     int fused_n[2] = {0, 0};   // valid when !fused_dirty
-    int *h_dev_err = nullptr;   // one pinned int a kernel sets when it has to give up (device std::sort: a wait that was never released); see device_error_check
-    void *h_rings = nullptr;                // pinned ring tables of mlh_scan_upload (two halves) ...
-    size_t h_rings_cap = 0;                 // ... bytes per half
-    hipEvent_t ev_rings[2] = {nullptr, nullptr};
-    bool ev_rings_used[2] = {false, false};
-    unsigned rings_turn = 0;
+    mlh::PinnedBuf h_dev_err;   // one int a kernel sets when it has to give up (device std::sort: a wait that was never released); see device_error_check
+    mlh::PinnedHalves h_rings;  // the ring tables of mlh_scan_upload on their way to the device
     hipEvent_t ev_handover = nullptr;      // mlh_features_copy: recorded on the source context's stream, waited for on this one's
     // mlh_fuse_add_scan_from(dst, this): a launch on ANOTHER context's stream reads this context's scan buffers; recorded there behind it, waited for on this
     // context's stream by whatever rewrites the scan next (scan_wait_readers). Set by the thread that drives dst while this context is idle.
     hipEvent_t ev_scan_reader = nullptr;
     std::atomic<bool> scan_reader_pending{false};
-    unsigned long long *h_sync = nullptr;   // pinned word stream_wait_spin's launch stores into
+    mlh::PinnedBuf h_sync;                  // the word stream_wait_spin's launch stores into
     unsigned long long sync_seq = 0;
     unsigned long long counts_seq = 0;      // publications of the thinned feature counts straight from a kernel (voxel.hip)
     // downsample_current_scan_pair_run(.., defer = true): the thinning was enqueued and NOT waited for -- where its two counts will be (device; pinned host + the
@@ -404,10 +511,9 @@ struct mlh_ctx {
     const int *thin_counts_host = nullptr;
     const unsigned long long *thin_seq_host = nullptr;
     unsigned long long thin_seq = 0;
-    void *h_scratch = nullptr;  // 256 pinned bytes: the landing place of the few-int read-backs (record counts) that end a staging call
-    void *fused_host = nullptr; // pinned record mlh_fused_cloud's publication launch fills: [2 counts (padded to 4 ints)][2 x 6 bounds][sequence word at byte 64]
+    mlh::PinnedBuf h_scratch;   // one ScratchBlock: the landing place of the few-int read-backs (record counts) that end a staging call
+    mlh::PinnedBuf fused_host;  // one FusedPublish
     unsigned long long fused_seq = 0;
-    size_t fused_host_cap = 0;
     mlh::DevBuf fused_cnt;   // the two record counts, device side (appends never wait for the host)
     size_t fused_bound[2] = {0, 0};   // host-side upper bounds of the counts (capacity)
     bool fused_dirty = false;
@@ -445,10 +551,8 @@ struct mlh_ctx {
     int vox_member_order = 1;          // voxel filters, members of a voxel: 1 = in the order libstdc++'s std::sort leaves them (the reference's), produced on the device
                                        // (stdsort.hip); 2 = the same through a host pass that calls the platform's own std::sort; 0 = in point-index order
     mlh::DevBuf stdsort;               // scratch of device_std_sort_by_key
-    void *vox_order_host = nullptr; // pinned staging of that host pass (voxelgrid.hip): [slot n][members n]
-    size_t vox_order_host_cap = 0;
-    void *select_host[2] = {nullptr, nullptr}; // pinned staging of the good-feature selection, per feature kind (select.hip)
-    size_t select_host_cap[2] = {0, 0};
+    mlh::PinnedBuf vox_order_host;  // staging of that host pass (voxelgrid.hip): [slot n][members n]
+    mlh::PinnedBuf select_host[2];  // staging of the good-feature selection, per feature kind (select.hip)
     std::vector<char> select_rows[2];   // the same rows in ordinary (CPU-cached) memory: what the selection loops read
     unsigned long long select_seq[2] = {0, 0};  // stream_flag_post after each kind's copies to the host
     bool select_staged[2] = {false, false};
@@ -459,8 +563,6 @@ struct mlh_ctx {
 };
 
 namespace mlh {
-
-int fail(mlh_ctx *ctx, int code, const char *what, hipError_t e = hipSuccess);
 
 // MLH_CHECK_LAUNCH=1 (debug runs): hipGetLastError() right behind EVERY kernel launch, so that a bad launch configuration is reported under the name of the kernel
 // that caused it instead of surfacing at the next synchronisation under another call's name. The error is sticky for the calling thread: the next MLH_HIP check
@@ -535,17 +637,15 @@ int device_exclusive_scan(mlh_ctx *ctx, int *data, long long n, mlh::DevBuf &sum
 // the context's pinned error word instead of leaving a wrong order behind silently; every call that waits for the stream afterwards reports it.
 inline int *device_error_word(mlh_ctx *ctx)
 {
-    if (!ctx->h_dev_err) {
-        void *p = nullptr;
-        if (hipHostMalloc(&p, sizeof(int), hipHostMallocDefault) == hipSuccess) { ctx->h_dev_err = static_cast<int *>(p); *ctx->h_dev_err = 0; }
-    }
-    return ctx->h_dev_err;
+    (void)ctx->h_dev_err.ensure(sizeof(int), 0, true);       // (nullptr on allocation failure)
+    return ctx->h_dev_err.as<int>();
 }
 inline int device_error_check(mlh_ctx *ctx)
 {
-    if (ctx->h_dev_err && *static_cast<volatile int *>(ctx->h_dev_err) != 0) {
-        const int code = *ctx->h_dev_err;
-        *ctx->h_dev_err = 0;
+    int *word = ctx->h_dev_err.as<int>();
+    if (word && *static_cast<volatile int *>(word) != 0) {
+        const int code = *word;
+        *word = 0;
         if (code == 2)
             return fail(ctx, MLH_ERR_STATE, "a peer rank did not arrive at a mailbox exchange within 5 s: the normal equations were NOT summed over the job, no update was applied from them, "
                                             "and the ranks may no longer hold the same pose -- the result of this call is not valid");
@@ -556,7 +656,7 @@ inline int device_error_check(mlh_ctx *ctx)
 // One turn of a host-side wait on a pinned word (the publications of the solves, the staging hand-shakes, the few-int read-backs): those waits are microseconds
 // long, so the default is to spin (`pause`) -- a sleeping thread's wake-up costs tens. A process with one thread per LiDAR + the mapper + the tracker, each in
 // such a wait, burns that many cores; MLH_HOST_WAIT=yield (read once per process) spins the first 64 turns (~2 us: the common case still pays nothing) and then
-// gives the core to whoever is runnable between two looks. Either way a wait falls back to the blocking hipStreamSynchronize after 200 ms.
+// gives the core to whoever is runnable between two looks. Either way a wait falls back to the blocking hipStreamSynchronize after 200 ms (host_spin below).
 inline void host_wait_relax(unsigned spins)
 {
     static const bool yield_mode = [] { const char *e = std::getenv("MLH_HOST_WAIT"); return e && std::strcmp(e, "yield") == 0; }();
@@ -565,11 +665,36 @@ inline void host_wait_relax(unsigned spins)
     __builtin_ia32_pause();
 #endif
 }
-// 64 pinned ints owned by the context (lazily allocated); nullptr on allocation failure
-inline int *pinned_ints(mlh_ctx *ctx)
+// THE host-side wait: looks (acquire loads of a pinned word, an event query) with host_wait_relax between them, the clock read every 1024 looks. True: `arrived`
+// held at a look; false: it did not for 200 ms (a long LM run, a profiler, a fault) -- the caller goes on to the blocking wait on its stream.
+template <typename Arrived> inline bool host_spin(Arrived arrived)
 {
-    if (!ctx->h_scratch && hipHostMalloc(&ctx->h_scratch, 256, hipHostMallocDefault) != hipSuccess) ctx->h_scratch = nullptr;
-    return static_cast<int *>(ctx->h_scratch);
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned spins = 0;
+    while (!arrived()) {
+        if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) return false;
+        host_wait_relax(spins);
+    }
+    return true;
+}
+// ... with that blocking wait on `st`, which also surfaces errors. `late` (may be null): the failure (MLH_ERR_HIP) when `arrived` does not hold even behind it.
+template <typename Arrived> inline int host_wait(mlh_ctx *ctx, Arrived arrived, hipStream_t st, const char *late)
+{
+    if (host_spin(arrived)) return MLH_OK;
+    MLH_HIP(ctx, hipStreamSynchronize(st));
+    if (late && !arrived()) return fail(ctx, MLH_ERR_HIP, late);
+    return MLH_OK;
+}
+// the publication that ends such a wait: `word` holds exactly `seq` (a sequence number stored with system-scope release behind the data it announces)
+inline int host_wait_seq(mlh_ctx *ctx, const unsigned long long *word, unsigned long long seq, hipStream_t st, const char *late)
+{
+    return host_wait(ctx, [=] { return __atomic_load_n(word, __ATOMIC_ACQUIRE) == seq; }, st, late);
+}
+// the context's pinned ScratchBlock (lazily allocated); nullptr on allocation failure
+inline ScratchBlock *scratch_block(mlh_ctx *ctx)
+{
+    (void)ctx->h_scratch.ensure(sizeof(ScratchBlock));
+    return ctx->h_scratch.as<ScratchBlock>();
 }
 // Everything enqueued on the context's stream so far (kernels, and copies into PINNED host memory) has completed when this returns. A one-thread launch stores a
 // sequence number into pinned host memory (system-scope release) and the host spins on that word: a few microseconds, where hipStreamSynchronize's wake-up
@@ -582,8 +707,8 @@ hipError_t stream_flag_wait(mlh_ctx *ctx, unsigned long long seq);
 // *out <- one device int, through the pinned block (a pageable landing place costs a staging hop); waits for the stream
 inline hipError_t read_back_int(mlh_ctx *ctx, const void *dev, int *out)
 {
-    int *h = pinned_ints(ctx);
-    int *dst = h ? h + 8 : out;
+    ScratchBlock *h = scratch_block(ctx);
+    int *dst = h ? &h->read_back : out;
     hipError_t e = hipMemcpyAsync(dst, dev, sizeof(int), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess) e = h ? stream_wait_spin(ctx) : hipStreamSynchronize(ctx->stream);
     if (e == hipSuccess && h) *out = *dst;

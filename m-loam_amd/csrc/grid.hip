@@ -13,7 +13,6 @@
 // so the next build starts from zeros without a clear launch; with few chunks (<= 4096) the add pass also sums the chunk
 // totals before it itself instead of a separate single-workgroup scan launch.
 #include "ctx.hpp"
-#include <chrono>
 #include <cmath>
 #include <climits>
 
@@ -529,11 +528,8 @@ int map_stage_and_build(mlh_ctx *ctx, int n_maps, const int *kinds, const unsign
     const bool build_follows = need_bounds != ((1 << n_maps) - 1);
     if (!build_follows) MLH_LAUNCH(publish_flag_kernel, dim3(1), dim3(64), 0, st, G.oob, pub, seq);
     MLH_HIP(ctx, hipGetLastError());
-    if (!ctx->h_occ) {
-        MLH_HIP(ctx, hipHostMalloc(&ctx->h_occ, sizeof(long long) * 4, hipHostMallocDefault));
-        std::memset(ctx->h_occ, 0, sizeof(long long) * 4);
-    }
-    long long *h_occ = static_cast<long long *>(ctx->h_occ);
+    MLH_HIP(ctx, ctx->h_occ.ensure(sizeof(long long) * 4, 0, true));
+    long long *h_occ = ctx->h_occ.as<long long>();
     for (int k = 0; k < n_maps; ++k) grids[k]->occ_host = h_occ + 2 * kinds[k];
     // occupancy statistics (they only steer the lanes-per-query choice): what the previous staging call's builds left in the pinned mirror
     for (int k = 0; k < n_maps; ++k) if (!(need_bounds & (1 << k)) && h_occ[2 * kinds[k]] > 0) {
@@ -552,18 +548,7 @@ int map_stage_and_build(mlh_ctx *ctx, int n_maps, const int *kinds, const unsign
         if (rc) return rc;
     }
     // spin on the pinned record (pack + fit check have completed when the sequence number arrives; the builds may still be running)
-    {
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned spins = 0;
-        while (__atomic_load_n(&pub->seq, __ATOMIC_ACQUIRE) != seq) {
-            if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-                MLH_HIP(ctx, hipStreamSynchronize(st));
-                if (__atomic_load_n(&pub->seq, __ATOMIC_ACQUIRE) != seq) return fail(ctx, MLH_ERR_HIP, "map staging did not complete");
-                break;
-            }
-            host_wait_relax(spins);
-        }
-    }
+    { const int rc = host_wait_seq(ctx, &pub->seq, seq, st, "map staging did not complete"); if (rc) return rc; }
     const int oob = int(pub->done);
     for (int k = 0; k < n_maps; ++k) if (oob & (1 << k)) need_bounds |= 1 << k;
     if (need_bounds) {

@@ -239,7 +239,6 @@ void keyframes_release(mlh_ctx *ctx)
     K.stage.release(); K.keep.release(); K.scan.release();
     for (int k = 0; k < 2; ++k) { K.pre[k].release(); K.flt[k].release(); K.pre_n[k] = K.flt_n[k] = 0; }
     std::vector<unsigned char>().swap(K.htab);
-    if (K.h_pin) { (void)hipHostFree(K.h_pin); K.h_pin = nullptr; }
 }
 
 // saveKeyframe's store (cpp:664-681): the pose, the f32 position, the two clouds appended to the store. src[k] are device float4 records (staged) or
@@ -424,7 +423,8 @@ int local_map_assemble_run(mlh_ctx *ctx, const double pose_cur[7], const double 
     // buffers (growth of a store / arena / cloud that holds data waits for its copy: the one exception to the two waits)
     MLH_HIP(ctx, K.cnt.grow(sizeof(int) * size_t(2 * K.n_slots + 2), K.cnt.cap, st));
     MLH_HIP(ctx, K.dstate.ensure(sizeof(int) * 20));
-    if (!K.h_pin) MLH_HIP(ctx, hipHostMalloc(reinterpret_cast<void **>(&K.h_pin), sizeof(int) * 32, hipHostMallocDefault));
+    MLH_HIP(ctx, K.h_pin.ensure(sizeof(int) * 32));
+    int *h_pin = K.h_pin.as<int>();
     if (compact) MLH_HIP(ctx, K.cache_tmp.ensure(size_t(REC) * std::max<size_t>(2 * K.cache_used, 1024)));   // live + entering, with room for turnover
     for (int k = 0; k < 2; ++k) MLH_HIP(ctx, K.pre[k].grow(size_t(REC) * (size_t(K.pre_n[k]) + size_t(ub[k]) + 1), size_t(REC) * size_t(K.pre_n[k]), st));
     if (N > 0) {
@@ -477,12 +477,12 @@ int local_map_assemble_run(mlh_ctx *ctx, const double pose_cur[7], const double 
                    (const int *)cnt, (const long long *)d_ofs, K.pre[0].as<float4>(), K.pre[1].as<float4>(), ds);
     MLH_HIP(ctx, hipGetLastError());
     // wait 1: the pre-filter lengths and bounds
-    MLH_HIP(ctx, hipMemcpyAsync(K.h_pin, ds, sizeof(int) * 14, hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, hipMemcpyAsync(h_pin, ds, sizeof(int) * 14, hipMemcpyDeviceToHost, st));
     MLH_HIP(ctx, stream_wait_spin(ctx));
     float bounds[2][6];
     for (int k = 0; k < 2; ++k) {
-        K.pre_n[k] = K.h_pin[k];
-        for (int d = 0; d < 6; ++d) bounds[k][d] = dec_f(K.h_pin[2 + 6 * k + d]);
+        K.pre_n[k] = h_pin[k];
+        for (int d = 0; d < 6; ++d) bounds[k][d] = dec_f(h_pin[2 + 6 * k + d]);
     }
     // the two covariance filters (cpp:343-346), results left in the context
     const float leaf[2] = {o->leaf_surf, o->leaf_corner};
@@ -496,9 +496,9 @@ int local_map_assemble_run(mlh_ctx *ctx, const double pose_cur[7], const double 
         MLH_HIP(ctx, hipMemcpyAsync(ds + 14 + k, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, st));
     }
     // wait 2: the filtered counts
-    MLH_HIP(ctx, hipMemcpyAsync(K.h_pin + 16, ds + 14, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, hipMemcpyAsync(h_pin + 16, ds + 14, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
     MLH_HIP(ctx, stream_wait_spin(ctx));
-    K.flt_n[0] = K.h_pin[16]; K.flt_n[1] = K.h_pin[17];
+    K.flt_n[0] = h_pin[16]; K.flt_n[1] = h_pin[17];
     *n_surf_ds = K.flt_n[0]; *n_corner_ds = K.flt_n[1];
     return device_error_check(ctx);
 }

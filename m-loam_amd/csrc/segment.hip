@@ -519,13 +519,8 @@ static int seg_host_carve(mlh_ctx *ctx, SegBuf &B, int npx, SegHost &H)
 {
     const size_t words = (size_t(npx) + 31) / 32;
     const size_t img = sizeof(float) * size_t(npx) + sizeof(int) * size_t(npx) + sizeof(unsigned) * words + 2 * size_t(npx) + 64;
-    if (B.h_img_cap < img) {
-        if (B.h_img) (void)hipHostFree(B.h_img);
-        B.h_img = nullptr; B.h_img_cap = 0;
-        MLH_HIP(ctx, hipHostMalloc(&B.h_img, img, hipHostMallocDefault));
-        B.h_img_cap = img;
-    }
-    unsigned char *p = static_cast<unsigned char *>(B.h_img);
+    MLH_HIP(ctx, B.h_img.ensure(img));
+    unsigned char *p = B.h_img.as<unsigned char>();
     H.range = reinterpret_cast<float *>(p); p += sizeof(float) * size_t(npx);
     H.owner = reinterpret_cast<int *>(p); p += sizeof(int) * size_t(npx);
     H.outmask = reinterpret_cast<unsigned *>(p); p += sizeof(unsigned) * words;
@@ -716,12 +711,7 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
     MLH_HIP(ctx, B.unc.ensure(unc_bytes));
     MLH_HIP(ctx, hipMemsetAsync(B.unc.p, 0, 16, st));
     const size_t h_need = 16 + sizeof(float4) * size_t(std::max(n, 2 * npx));
-    if (B.h_unc_cap < h_need) {
-        if (B.h_unc) (void)hipHostFree(B.h_unc);
-        B.h_unc = nullptr; B.h_unc_cap = 0;
-        MLH_HIP(ctx, hipHostMalloc(&B.h_unc, h_need, hipHostMallocDefault));
-        B.h_unc_cap = h_need;
-    }
+    MLH_HIP(ctx, B.h_unc.ensure(h_need));
     SegDev D;
     D.src = src; D.stride = stride; D.intensity_off = intensity_off; D.n = n; D.S = S; D.roi_range = prm.roi_range;
     D.pix = B.pix.as<int>(); D.owner = B.owner.as<int>(); D.range_mat = B.range.as<float>(); D.ground = B.ground.as<unsigned char>();
@@ -733,9 +723,9 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
     int n_undecided_pts = 0;
     {
         // the points whose bin the device left open: fetched (counters + the first records in one copy), decided with the host's libm, sent back, claimed
-        int *hc = static_cast<int *>(B.h_unc);
-        float4 *hp = reinterpret_cast<float4 *>(static_cast<unsigned char *>(B.h_unc) + 16);
-        MLH_HIP(ctx, hipMemcpyAsync(B.h_unc, B.unc.p, 16 + sizeof(float4) * size_t(std::min(n, SEG_UNC_FIRST)), hipMemcpyDeviceToHost, st));
+        int *hc = B.h_unc.as<int>();
+        float4 *hp = reinterpret_cast<float4 *>(B.h_unc.as<unsigned char>() + 16);
+        MLH_HIP(ctx, hipMemcpyAsync(B.h_unc.p, B.unc.p, 16 + sizeof(float4) * size_t(std::min(n, SEG_UNC_FIRST)), hipMemcpyDeviceToHost, st));
         MLH_HIP(ctx, stream_wait_spin(ctx));
         n_undecided_pts = std::min(hc[0], n);
         if (n_undecided_pts > SEG_UNC_FIRST) {
@@ -786,8 +776,8 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
     int n_undecided_gnd = 0;
     {
         // the ground pairs within the margin of 10 degrees: decided here, with the host's libm, straight into the ground image the cluster search reads
-        int *hc = static_cast<int *>(B.h_unc);
-        float4 *hg = reinterpret_cast<float4 *>(static_cast<unsigned char *>(B.h_unc) + 16);
+        int *hc = B.h_unc.as<int>();
+        float4 *hg = reinterpret_cast<float4 *>(B.h_unc.as<unsigned char>() + 16);
         MLH_HIP(ctx, hipMemcpyAsync(hc, B.unc.p, 16, hipMemcpyDeviceToHost, st));
         MLH_HIP(ctx, hipMemcpyAsync(hg, D.unc_gnd, sizeof(float4) * 2 * size_t(std::min(npx, SEG_UNC_FIRST)), hipMemcpyDeviceToHost, st));
         MLH_HIP(ctx, stream_wait_spin(ctx));
@@ -828,12 +818,7 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
         MLH_HIP(ctx, B.outmask.ensure(mask_bytes));
         MLH_HIP(ctx, B.row_cnt.ensure(sizeof(int) * size_t(vs)));
         MLH_HIP(ctx, B.keep.ensure(sizeof(int) * size_t(npx)));
-        if (B.h_rows_cap < sizeof(int) * size_t(vs + 2)) {
-            if (B.h_rows) (void)hipHostFree(B.h_rows);
-            B.h_rows = nullptr; B.h_rows_cap = 0;
-            MLH_HIP(ctx, hipHostMalloc(&B.h_rows, sizeof(int) * size_t(vs + 2) * 2, hipHostMallocDefault));
-            B.h_rows_cap = sizeof(int) * size_t(vs + 2) * 2;
-        }
+        MLH_HIP(ctx, B.h_rows.ensure(sizeof(int) * size_t(vs + 2), sizeof(int) * size_t(vs + 2)));
         ScanBuf &sb = ctx->scan;
         sb.extracted = false; sb.voxelised = false; sb.h_lists_valid = sb.h_vox_valid = false;
         MLH_HIP(ctx, sb.pts.ensure(sizeof(float4) * size_t(std::max(std::min(n, npx), 1))));
@@ -846,7 +831,7 @@ int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensit
         R.vs = vs; R.hs = hs; R.hs2 = hs2; R.segment_flag = prm.segment_flag ? 1 : 0;
         const size_t lds = size_t(20) * size_t(hs2);
         MLH_LAUNCH(seg_rows_kernel, dim3(vs), dim3(SEG_ROW_TPB), lds, st, R);
-        int *h_rows = static_cast<int *>(B.h_rows);
+        int *h_rows = B.h_rows.as<int>();
         MLH_LAUNCH(seg_rows_gather_kernel, dim3(4, vs), dim3(256), 0, st, D, (const int *)B.keep.as<int>(), (const int *)B.row_cnt.as<int>(), sb.pts.as<float4>(),
                    sb.start.as<int>(), sb.end.as<int>(), h_rows);
         MLH_HIP(ctx, hipGetLastError());

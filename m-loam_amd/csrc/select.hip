@@ -766,17 +766,14 @@ int good_feature_stage(mlh_ctx *ctx, int kind, int method, double ratio, std::mt
     // pinned staging (grow-only, owned by the context, one block per kind): [J 6m][pts m][valid m bytes, padded][keep m bytes, padded][fps: count, order m]
     const size_t mp = (m + 63) & ~size_t(63);
     const size_t off_p = sizeof(double) * 6 * m, off_v = off_p + sizeof(float4) * m, off_k = off_v + mp, off_o = off_k + mp, need = off_o + sizeof(int) * (m + 1);
-    if (need > ctx->select_host_cap[kind]) {
+    if (need > ctx->select_host[kind].cap) {
         MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));          // a copy of an earlier call may still be using the old block
-        if (ctx->select_host[kind]) (void)hipHostFree(ctx->select_host[kind]);
-        ctx->select_host[kind] = nullptr; ctx->select_host_cap[kind] = 0;
-        MLH_HIP(ctx, hipHostMalloc(&ctx->select_host[kind], need + need / 4, hipHostMallocDefault));
-        ctx->select_host_cap[kind] = need + need / 4;
+        MLH_HIP(ctx, ctx->select_host[kind].ensure(need, need / 4));
     }
     MLH_HIP(ctx, f.flag8.ensure(mp));
     MLH_LAUNCH(pack_valid_kernel, dim3(unsigned((m + 255) / 256)), dim3(256), 0, ctx->stream, f.corr.as<Corr>(), int(m), f.flag8.as<uint8_t>());
     MLH_HIP(ctx, hipGetLastError());
-    char *hb = static_cast<char *>(ctx->select_host[kind]);
+    char *hb = ctx->select_host[kind].as<char>();
     MLH_HIP(ctx, hipMemcpyAsync(hb + off_v, f.flag8.p, m, hipMemcpyDeviceToHost, ctx->stream));
     MLH_HIP(ctx, hipMemcpyAsync(hb, f.J.p, sizeof(double) * 6 * m, hipMemcpyDeviceToHost, ctx->stream));
     ctx->select_fps_start[kind] = -1;
@@ -823,7 +820,7 @@ int good_feature_finish(mlh_ctx *ctx, int kind, int method, double ratio, std::m
     const size_t m = size_t(f.m);
     const size_t mp = (m + 63) & ~size_t(63);
     const size_t off_p = sizeof(double) * 6 * m, off_v = off_p + sizeof(float4) * m, off_k = off_v + mp, off_o = off_k + mp;
-    char *hb = static_cast<char *>(ctx->select_host[kind]);
+    char *hb = ctx->select_host[kind].as<char>();
     R.m = m;
     const int *fps_dev = reinterpret_cast<const int *>(hb + off_o);                     // [count or -1][visiting order]
     const bool fps_host = method == MLH_GF_FPS && m > 0 && fps_dev[0] < 0;
@@ -940,14 +937,11 @@ int odom_good_feature_select(mlh_ctx *ctx, int kind, float gf_ratio, std::mt1993
     const size_t m = size_t(f.m);
     const size_t mp = (m + 63) & ~size_t(63);
     const size_t off_v = sizeof(double) * 6 * m, off_k = off_v + mp, need = off_k + mp;
-    if (need > ctx->select_host_cap[kind]) {
+    if (need > ctx->select_host[kind].cap) {
         MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (ctx->select_host[kind]) (void)hipHostFree(ctx->select_host[kind]);
-        ctx->select_host[kind] = nullptr; ctx->select_host_cap[kind] = 0;
-        MLH_HIP(ctx, hipHostMalloc(&ctx->select_host[kind], need + need / 4, hipHostMallocDefault));
-        ctx->select_host_cap[kind] = need + need / 4;
+        MLH_HIP(ctx, ctx->select_host[kind].ensure(need, need / 4));
     }
-    char *hb = static_cast<char *>(ctx->select_host[kind]);
+    char *hb = ctx->select_host[kind].as<char>();
     const size_t n_use = static_cast<size_t>(m * double(gf_ratio));
     const bool need_rows = n_use > 0 && static_cast<size_t>(1.0 * m / n_use) > 1;      // subsets of one never look at a score (select_greedy_odom)
     if (need_rows) MLH_HIP(ctx, hipMemcpyAsync(hb, f.J.p, sizeof(double) * 6 * m, hipMemcpyDeviceToHost, ctx->stream));

@@ -14,7 +14,6 @@
 //                        Sigma_meas) G^T]_3x3 with G = [(T p)^odot | T D], f64, stored to the f32 cov_vec of PointXYZIWithCov;
 //                        points whose trace exceeds TRACE_THRESHOLD_MAPPING are dropped (order-preserving compaction).
 #include "ctx.hpp"
-#include <chrono>
 #include <cstdlib>
 #include "dev_math.hpp"
 #include "sort_dev.hpp"
@@ -745,6 +744,47 @@ __global__ __launch_bounds__(VSP_TPB) void vsp_features_kernel(VspArgs A)
     }
 }
 
+// The thinned feature counts on their way to the host: the kernel that knows them stores them into the context's pinned ScratchBlock and its sequence word last
+// (thin_counts_arm, before the launch); thin_counts_collect waits for that word behind the launch -- or, `defer`, leaves where to look with the context: the caller
+// enqueues the solve behind the thinning without knowing the counts (mlh_downsample_scan2map) and reads them when it reads the pose.
+struct ThinCountsPub {
+    int *host_counts = nullptr;              // all null / 0 without the pinned block: the counts are then copied back from the device
+    unsigned long long *host_seq = nullptr, seq = 0;
+};
+static ThinCountsPub thin_counts_arm(mlh_ctx *ctx)
+{
+    ThinCountsPub P;
+    if (ScratchBlock *h = scratch_block(ctx)) {
+        P.host_counts = h->thin_counts;
+        P.host_seq = &h->thin_seq;
+        if (ctx->counts_seq == 0) *P.host_seq = 0;
+        P.seq = ++ctx->counts_seq;
+    }
+    return P;
+}
+static int thin_counts_collect(mlh_ctx *ctx, const ThinCountsPub &P, const int *dev_counts, bool defer, int *n_surf_out, int *n_corner_out)
+{
+    hipStream_t st = ctx->stream;
+    if (defer && P.host_seq) {
+        ctx->thin_counts_dev = dev_counts; ctx->thin_counts_host = P.host_counts; ctx->thin_seq_host = P.host_seq; ctx->thin_seq = P.seq;
+        *n_surf_out = -1; *n_corner_out = -1;
+        return MLH_OK;
+    }
+    if (P.host_seq) {
+        const int rc = host_wait_seq(ctx, P.host_seq, P.seq, st, "the thinned feature counts did not arrive");
+        if (rc) return rc;
+        *n_surf_out = P.host_counts[0];
+        *n_corner_out = P.host_counts[1];
+    } else {
+        int stack_counts[2] = {0, 0};
+        MLH_HIP(ctx, hipMemcpyAsync(stack_counts, dev_counts, sizeof(stack_counts), hipMemcpyDeviceToHost, st));
+        MLH_HIP(ctx, hipStreamSynchronize(st));
+        *n_surf_out = stack_counts[0];
+        *n_corner_out = stack_counts[1];
+    }
+    return device_error_check(ctx);
+}
+
 // downsampleCurrentScan for the surf AND the corner cloud in one set of launches (device-resident clouds with known bounding boxes:
 // the fused clouds). Same results as two downsample_current_scan_run calls.
 int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf, const float bounds_surf[6], float leaf_surf, const void *corner, int n_corner,
@@ -803,44 +843,13 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
             A.n_lidar = n_lidar; A.with_ua = with_ua ? 1 : 0; A.trace_thr = trace_thr;
             A.pts0 = f0.pts.as<float4>(); A.covd0 = f0.covd.as<float4>(); A.pts1 = f1.pts.as<float4>(); A.covd1 = f1.covd.as<float4>();
             A.counts = V.total.as<int>() + 2;
-            A.host_counts = nullptr; A.host_seq = nullptr; A.seq = 0;
-            if (int *hp = pinned_ints(ctx)) {
-                A.host_counts = hp + 16;
-                A.host_seq = reinterpret_cast<unsigned long long *>(hp + 32);
-                if (ctx->counts_seq == 0) *A.host_seq = 0;
-                A.seq = ++ctx->counts_seq;
-            }
+            const ThinCountsPub P = thin_counts_arm(ctx);
+            A.host_counts = P.host_counts; A.host_seq = P.host_seq; A.seq = P.seq;
             MLH_LAUNCH(vsp_heads_kernel, dim3(A.nch), dim3(VSP_TPB), 0, st, A);
             MLH_LAUNCH(vsp_aggregate_kernel, dim3(A.nch), dim3(VSP_TPB), 0, st, A);
             MLH_LAUNCH(vsp_features_kernel, dim3(A.nch), dim3(VSP_TPB), 0, st, A);
             MLH_HIP(ctx, hipGetLastError());
-            if (defer && A.host_seq) {
-                // the caller enqueues the solve behind this without knowing the counts (mlh_downsample_scan2map): they are read when the pose is
-                ctx->thin_counts_dev = A.counts; ctx->thin_counts_host = A.host_counts; ctx->thin_seq_host = A.host_seq; ctx->thin_seq = A.seq;
-                *n_surf_out = -1; *n_corner_out = -1;
-                return MLH_OK;
-            }
-            if (A.host_seq) {
-                const auto t0 = std::chrono::steady_clock::now();
-                unsigned spins = 0;
-                while (__atomic_load_n(A.host_seq, __ATOMIC_ACQUIRE) != A.seq) {
-                    if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-                        MLH_HIP(ctx, hipStreamSynchronize(st));
-                        if (__atomic_load_n(A.host_seq, __ATOMIC_ACQUIRE) != A.seq) return fail(ctx, MLH_ERR_HIP, "the thinned feature counts did not arrive");
-                        break;
-                    }
-                    host_wait_relax(spins);
-                }
-                *n_surf_out = A.host_counts[0];
-                *n_corner_out = A.host_counts[1];
-            } else {
-                int stack_counts[2] = {0, 0};
-                MLH_HIP(ctx, hipMemcpyAsync(stack_counts, A.counts, sizeof(stack_counts), hipMemcpyDeviceToHost, st));
-                MLH_HIP(ctx, hipStreamSynchronize(st));
-                *n_surf_out = stack_counts[0];
-                *n_corner_out = stack_counts[1];
-            }
-            return device_error_check(ctx);
+            return thin_counts_collect(ctx, P, A.counts, defer, n_surf_out, n_corner_out);
         }
     }
     MLH_HIP(ctx, ctx->uct_buf.ensure(sizeof(double) * size_t(n_lidar) * 43 + sizeof(float) * 6 * size_t(n) + 64));
@@ -871,41 +880,13 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
     FeatSet &f0 = ctx->feat[MLH_SURF], &f1 = ctx->feat[MLH_CORNER];
     MLH_HIP(ctx, f0.pts.ensure(sizeof(float4) * size_t(n_surf))); MLH_HIP(ctx, f0.covd.ensure(sizeof(float4) * size_t(n_surf)));
     MLH_HIP(ctx, f1.pts.ensure(sizeof(float4) * size_t(n_corner))); MLH_HIP(ctx, f1.covd.ensure(sizeof(float4) * size_t(n_corner)));
-    // pinned record for the counts: ints 16..17 and the 64-bit word at byte 128 of the context's pinned scratch block
-    int *h_counts = nullptr;
-    unsigned long long *h_seq = nullptr, seq = 0;
-    if (int *hp = pinned_ints(ctx)) {
-        h_counts = hp + 16;
-        h_seq = reinterpret_cast<unsigned long long *>(hp + 32);
-        if (ctx->counts_seq == 0) *h_seq = 0;
-        seq = ++ctx->counts_seq;
-    }
+    const ThinCountsPub P = thin_counts_arm(ctx);
     MLH_LAUNCH(features_from_kept_pair_kernel, dim3(nb), dim3(256), 0, st, (const unsigned char *)V.out.as<unsigned char>(), stride, intensity_off, n,
                        (const int *)V.total.as<int>(), (const int *)V.wpre.as<int>(), first_word, (const int *)V.leader.as<int>(), (const int *)V.vox_of.as<int>(),
                        (const int *)(V.total.as<int>() + 1), (const float *)d_c6, f0.pts.as<float4>(), f0.covd.as<float4>(), f1.pts.as<float4>(), f1.covd.as<float4>(),
-                       V.total.as<int>() + 2, h_counts, h_seq, seq);
+                       V.total.as<int>() + 2, P.host_counts, P.host_seq, P.seq);
     MLH_HIP(ctx, hipGetLastError());
-    if (h_seq) {
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned spins = 0;
-        while (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != seq) {
-            if ((++spins & 0x3ff) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(200)) {
-                MLH_HIP(ctx, hipStreamSynchronize(st));
-                if (__atomic_load_n(h_seq, __ATOMIC_ACQUIRE) != seq) return fail(ctx, MLH_ERR_HIP, "the thinned feature counts did not arrive");
-                break;
-            }
-            host_wait_relax(spins);
-        }
-        *n_surf_out = h_counts[0];
-        *n_corner_out = h_counts[1];
-    } else {
-        int stack_counts[2] = {0, 0};
-        MLH_HIP(ctx, hipMemcpyAsync(stack_counts, V.total.as<int>() + 2, sizeof(stack_counts), hipMemcpyDeviceToHost, st));
-        MLH_HIP(ctx, hipStreamSynchronize(st));
-        *n_surf_out = stack_counts[0];
-        *n_corner_out = stack_counts[1];
-    }
-    return device_error_check(ctx);
+    return thin_counts_collect(ctx, P, V.total.as<int>() + 2, false, n_surf_out, n_corner_out);
 }
 
 }  // namespace mlh

@@ -350,14 +350,11 @@ static int members_in_std_sort_order(mlh_ctx *ctx, const VoxArgs &A)
 {
     hipStream_t st = ctx->stream;
     const size_t n = size_t(A.n), need = 2 * sizeof(int) * n;
-    if (need > ctx->vox_order_host_cap) {
+    if (need > ctx->vox_order_host.cap) {
         MLH_HIP(ctx, hipStreamSynchronize(st));                           // an earlier call's upload may still be reading the old block
-        if (ctx->vox_order_host) (void)hipHostFree(ctx->vox_order_host);
-        ctx->vox_order_host = nullptr; ctx->vox_order_host_cap = 0;
-        MLH_HIP(ctx, hipHostMalloc(&ctx->vox_order_host, need + need / 4, hipHostMallocDefault));
-        ctx->vox_order_host_cap = need + need / 4;
+        MLH_HIP(ctx, ctx->vox_order_host.ensure(need, need / 4));
     }
-    int *slot = static_cast<int *>(ctx->vox_order_host), *members = slot + n;
+    int *slot = ctx->vox_order_host.as<int>(), *members = slot + n;
     MLH_HIP(ctx, hipMemcpyAsync(slot, A.vox_of, sizeof(int) * n, hipMemcpyDeviceToHost, st));
     MLH_HIP(ctx, hipStreamSynchronize(st));
     // one filter call per cloud in the reference: one sort per cloud

@@ -406,3 +406,18 @@ sys.exit(1 if bad else 0)
 ''' % (ROOT, names)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, (r.returncode, r.stdout[-600:], r.stderr[-1500:])
+
+
+def test_pinned_memory_and_host_waits_have_one_owner(mla):
+    """The host side of every host-device hand-shake is written once (csrc/ctx.hpp): pinned blocks are allocated and freed by PinnedBuf alone, the 200 ms wait
+    policy exists in one place, and the hand-kept twins of those owners (capacities, the derived solve_pending flag) are gone."""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(mla.__file__)), "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))}
+    assert len(text) >= 20
+    pinned_users = sorted(f for f, t in text.items() if "hipHostMalloc" in t or "hipHostFree" in t)
+    assert len(pinned_users) == 1, pinned_users
+    owner = text[pinned_users[0]]
+    assert "struct PinnedBuf" in owner and "hipHostMalloc" in owner and "hipHostFree" in owner
+    assert sum(t.count("milliseconds(200)") for t in text.values()) == 1
+    for gone in ("solve_pending", "h_pts_cap", "h_rings_cap", "select_host_cap", "vox_order_host_cap"):
+        assert not [f for f, t in text.items() if gone in t], gone
