@@ -173,6 +173,7 @@ static int ensure_state(mlh_ctx *ctx, int n_stats)
 // pinned host memory and then stores a sequence number with system-scope release; the host spins on that word (acquire) --
 // microseconds instead of the tens of microseconds an interrupt-driven hipStreamSynchronize wake-up costs per frame.
 struct PoseArg { double p[7]; };
+static void pose_copy(double dst[7], const double src[7]) { for (int i = 0; i < 7; ++i) dst[i] = src[i]; }
 __global__ void init_state_kernel(SolverState *S, PoseArg pose)
 {
     double *w = reinterpret_cast<double *>(S);
@@ -214,7 +215,7 @@ static int upload_pose(mlh_ctx *ctx, const double pose[7])
     // state, so that solve has to be completed (and published to ITS host record) before, not by the match launch that follows
     { const int frc = gn_flush_pending(ctx); if (frc) return frc; }
     PoseArg a;
-    for (int i = 0; i < 7; ++i) a.p[i] = pose[i];
+    pose_copy(a.p, pose);
     MLH_LAUNCH(init_state_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->state.as<SolverState>(), a);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
@@ -223,10 +224,27 @@ static int upload_pose(mlh_ctx *ctx, const double pose[7])
 static int upload_block_pose(mlh_ctx *ctx, int b, const double pose[7])
 {
     PoseArg a;
-    for (int i = 0; i < 7; ++i) a.p[i] = pose[i];
+    pose_copy(a.p, pose);
     MLH_LAUNCH(set_block_pose_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->state.as<SolverState>(), b, a);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
+}
+
+// The chained start pose, made on the device from the pose the previous solve left there; start_out (may be null): see chain_pose_kernel
+static int enqueue_chain_pose(mlh_ctx *ctx, const double *wodom_prev, const double *wodom_cur, HostPublish *start_out)
+{
+    PoseArg pa, pb;
+    pose_copy(pa.p, wodom_prev); pose_copy(pb.p, wodom_cur);
+    MLH_LAUNCH(chain_pose_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->state.as<SolverState>(), pa, pb, start_out);
+    MLH_HIP(ctx, hipGetLastError());
+    return MLH_OK;
+}
+
+// What a solver entry point begins with: the last iteration a solve submitted with mlh_gn_solve_begin* may have left as records, and the state (+ n_stats records)
+static int solver_begin(mlh_ctx *ctx, int n_stats)
+{
+    const int rc = gn_flush_pending(ctx);
+    return rc ? rc : ensure_state(ctx, n_stats);
 }
 
 __global__ void stream_flag_kernel(unsigned long long *h, unsigned long long seq)
@@ -386,6 +404,10 @@ static void demote_loop_gate(mlh_ctx *c, int which, int tiles)
     set_loop_gates(c);
 }
 static bool loop_tiles_ok(const mlh_ctx *c, int which, int tiles) { return tiles > 0 && tiles <= c->caps.loop_max_tiles[which]; }
+// The barrier of a one-launch loop was given up on (DONE_GIVEN_UP: its workgroups were not all resident at once beside whatever else runs here). Counted and the
+// gate lowered; the caller then solves the frame again from the start pose it still holds through a launch-per-iteration form: same arithmetic, same pose bits, no
+// residency requirement. (mlh_scan2map_end, which may have to hand the frame back instead, uses the pieces separately.)
+static void note_loop_given_up(mlh_ctx *ctx, int gate, int tiles) { demote_loop_gate(ctx, gate, tiles); ++ctx->caps.loop_fallbacks; }
 
 }  // namespace mlh
 
@@ -1418,11 +1440,11 @@ static MatchArgs gn_iter_args(const mlh_ctx *ctx, const mlh_solver_opts *opts, i
     MatchArgs a = args_from_opts(opts, mask, 0);
     if (it == 0) a.init_pose = pose;
     a.warm = it >= 1 && ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi;
-    a.finish = 1;
+    a.finish = TAIL_GN;
     if (defer) {
         a.gn_iter = it; a.gn_iters = n_iters;
         if (it == 1) a.init_pose = pose;
-        if (it < n_iters - 1 || leave_final) a.finish = 0;
+        if (it < n_iters - 1 || leave_final) a.finish = TAIL_RECORDS;
     }
     return a;
 }
@@ -1434,7 +1456,7 @@ static int fetch_pose_and_stats(mlh_ctx *ctx, double pose[7], mlh_iter_stat *sta
         int rc = fetch_published(ctx, hp);
         if (rc) return rc;
         if (!ctx->prof.pending.empty()) prof_collect(ctx);     // their events precede the publication in stream order: complete
-        for (int i = 0; i < 7; ++i) pose[i] = hp.x[i];
+        pose_copy(pose, hp.x);
         return MLH_OK;
     }
     SolverState hs;
@@ -1444,7 +1466,7 @@ static int fetch_pose_and_stats(mlh_ctx *ctx, double pose[7], mlh_iter_stat *sta
     MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     prof_collect(ctx);
     if (ctx->p2p.active) { const int erc = device_error_check(ctx); if (erc) return erc; }      // (see wait_published)
-    for (int i = 0; i < 7; ++i) pose[i] = hs.x[i];
+    pose_copy(pose, hs.x);
     for (int i = 0; i < n_stats; ++i) copy_stat(hd[i], stats[i]);
     return MLH_OK;
 }
@@ -1453,15 +1475,14 @@ int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solv
 {
     if (!ctx || !pose_inout || !opts || n_iters <= 0) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
-    int rc = ensure_state(ctx, n_iters);
+    int rc = solver_begin(ctx, n_iters);
     if (rc) return rc;
     const int mask = solve_kind_mask(ctx);
     if (!mask) return fail(ctx, MLH_ERR_STATE, "no map/features staged");
     // the pose goes in with the first iteration's kernel arguments and (single GPU, no statistics wanted) comes back through
     // pinned host memory written by the last iteration's finish: 2 launches per iteration and nothing else
     unsigned long long seq = 0;
-    bool fused_publish = false;
+    const bool fused_publish = !stats && (!distributed(ctx) || ctx->p2p.active);
     const bool defer = !stats && n_iters >= 2 && gn_defer_applies(ctx, mask);
     for (int it = 0; it < n_iters; ++it) {
         MatchArgs a = gn_iter_args(ctx, opts, mask, it, n_iters, pose_inout, defer);
@@ -1469,16 +1490,15 @@ int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solv
             // single GPU: two launches per iteration; the fit kernel's last workgroup reduces, solves and updates the pose. Several ranks joined by the
             // mailbox communicator: the same two launches -- that workgroup exchanges the summed record with the peers (one hop) before it solves
             a.stat_slot = stats ? it : -1;
-            if (it == n_iters - 1 && !stats) {
+            if (it == n_iters - 1 && fused_publish) {
                 if ((rc = publish_slot(ctx, &a.publish, &seq))) return rc;
                 a.publish_seq = seq;
-                fused_publish = true;
             }
             if ((rc = match_launch(ctx, a))) return rc;
         } else {
             // multi-GPU: the fit kernel's last workgroup leaves this rank's sums in the solver state, then ONE all-reduce of
             // 32 doubles, then every rank runs the identical solve
-            a.finish = 2;
+            a.finish = TAIL_REDUCE;
             if ((rc = match_launch(ctx, a))) return rc;
             if ((rc = comm_allreduce_state(ctx, 0))) return rc;
             if ((rc = gn_update_prereduced_launch(ctx, opts->map_eig_thre, stats ? it : -1))) return rc;
@@ -1488,7 +1508,7 @@ int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solv
         HostPublish hp;
         if ((rc = wait_published(ctx, seq, hp))) return rc;
         if ((rc = prof_drain(ctx, (1u << MLH_K_FIT) | (1u << MLH_K_SOLVE)))) return rc;
-        for (int i = 0; i < 7; ++i) pose_inout[i] = hp.x[i];
+        pose_copy(pose_inout, hp.x);
         return MLH_OK;
     }
     return fetch_pose_and_stats(ctx, pose_inout, stats, n_iters);
@@ -1512,19 +1532,14 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     if ((rc = ensure_state(ctx, 0))) return rc;
     const int mask = solve_kind_mask(ctx);
     if (!mask) return fail(ctx, MLH_ERR_STATE, "no map/features staged");
-    slot->kind = 0;
+    slot->kind = mlh_ctx::SolveSlot::GN;
     const bool defer = n_iters >= 2 && gn_defer_applies(ctx, mask);
     // The previous solve may have left its LAST iteration as tile records (gn_pending). A chained, deferred solve completes it in its own first launch -- unless this
     // frame needs a larger record buffer (the records would not survive the reallocation); everything else completes it now, before the chain launch reads the pose.
     const bool consume = !pose_in && defer && ctx->gn_pending.active && sizeof(double) * NE_STRIDE * size_t(feature_tiles(ctx, mask)) <= ctx->partials.cap;
     mlh_ctx::GnPending pend = ctx->gn_pending;
     if (ctx->gn_pending.active && !consume && (rc = gn_flush_pending(ctx))) return rc;
-    if (!pose_in && !consume) {                    // chained: the start pose is made on the device from the pose the previous solve left there
-        PoseArg pa, pb;
-        for (int i = 0; i < 7; ++i) { pa.p[i] = wodom_prev[i]; pb.p[i] = wodom_cur[i]; }
-        MLH_LAUNCH(chain_pose_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->state.as<SolverState>(), pa, pb, static_cast<HostPublish *>(nullptr));
-        MLH_HIP(ctx, hipGetLastError());
-    }
+    if (!pose_in && !consume && (rc = enqueue_chain_pose(ctx, wodom_prev, wodom_cur, nullptr))) return rc;
     // this solve's own last iteration: left to a successor (or to mlh_gn_solve_end) when the schedule says so
     const bool leave_final = defer && ctx->gn_final_defer;
     const int base = ctx->gn_slot_base;
@@ -1579,7 +1594,7 @@ int mlh_gn_solve_end(mlh_ctx *ctx, double pose_out[7])
     if (!ctx || !pose_out) return MLH_ERR_INVALID;
     if (!ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, "no solve in flight (mlh_gn_solve_begin)");
     const unsigned long long seq = ctx->solves.oldest();
-    if (ctx->solves.slot[seq & 1].kind != 0) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_scan2map_begin: collect it with mlh_scan2map_end");
+    if (ctx->solves.slot[seq & 1].kind != mlh_ctx::SolveSlot::GN) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_scan2map_begin: collect it with mlh_scan2map_end");
     if (ctx->gn_pending.active && ctx->gn_pending.seq == seq) {      // nobody chained a successor behind it: its last iteration is completed here
         const int frc = gn_flush_pending(ctx);
         if (frc) return frc;
@@ -1589,7 +1604,7 @@ int mlh_gn_solve_end(mlh_ctx *ctx, double pose_out[7])
     ctx->solves.retire(seq);
     if (rc) return rc;
     if (!ctx->solves.pending() && (rc = prof_drain(ctx, (1u << MLH_K_FIT) | (1u << MLH_K_SOLVE)))) return rc;
-    for (int i = 0; i < 7; ++i) pose_out[i] = hp.x[i];
+    pose_copy(pose_out, hp.x);
     return MLH_OK;
 }
 
@@ -1598,9 +1613,8 @@ int mlh_gn_solve_blocks(mlh_ctx *ctx, double *poses_inout, int n_iters, const ml
 {
     if (!ctx || !poses_inout || !opts || !bo || n_iters <= 0 || bo->n_blocks <= 0 || bo->n_blocks > 8) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
     const int nb = bo->n_blocks;
-    int rc = ensure_state(ctx, n_iters * nb);
+    int rc = solver_begin(ctx, n_iters * nb);
     if (rc) return rc;
     if ((rc = upload_pose(ctx, poses_inout))) return rc;
     for (int b = 1; b < nb; ++b) if ((rc = upload_block_pose(ctx, b, poses_inout + 7 * b))) return rc;
@@ -1621,17 +1635,17 @@ int mlh_gn_solve_blocks(mlh_ctx *ctx, double *poses_inout, int n_iters, const ml
         a.n_blocks = nb;
         for (int b = 0; b < nb; ++b) { a.k_neigh[b] = bo->k_neigh[b]; a.eig_thre[b] = bo->eig_thre[b]; a.freeze[b] = bo->freeze[b]; }
         if (!distributed(ctx) || ctx->p2p.active) {      // (mailbox communicator: the blocks' records are exchanged inside the finish, one after the other)
-            a.finish = 1;
+            a.finish = TAIL_GN;
             a.stat_slot = stats ? it * nb : -1;
             if (defer_blocks) {
                 a.gn_iter = it; a.gn_iters = n_iters; a.gn_blocks = true;
                 a.warm = it >= 1;
-                if (it < n_iters - 1) a.finish = 0;
+                if (it < n_iters - 1) a.finish = TAIL_RECORDS;
             }
             if ((rc = match_launch(ctx, a))) return rc;
         } else {
             // multi-GPU: per-block local sums in the fit kernel's last workgroup, ONE all-reduce of nb x 32 doubles, identical updates
-            a.finish = 2;
+            a.finish = TAIL_REDUCE;
             if ((rc = match_launch(ctx, a))) return rc;
             if ((rc = comm_allreduce_blocks(ctx, nb))) return rc;
             if ((rc = gn_update_blocks_prereduced_launch(ctx, nb, bo->eig_thre, bo->freeze, stats ? it * nb : -1))) return rc;
@@ -1643,45 +1657,49 @@ int mlh_gn_solve_blocks(mlh_ctx *ctx, double *poses_inout, int n_iters, const ml
     if ((rc = fetch_published(ctx, hs))) return rc;
     if (stats) MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     prof_collect(ctx);
-    for (int i = 0; i < 7; ++i) poses_inout[i] = hs.x[i];
-    for (int b = 1; b < nb; ++b) for (int i = 0; i < 7; ++i) poses_inout[7 * b + i] = hs.xb[b][i];
+    pose_copy(poses_inout, hs.x);
+    for (int b = 1; b < nb; ++b) pose_copy(poses_inout + 7 * b, hs.xb[b]);
     for (size_t i = 0; stats && i < hd.size(); ++i) copy_stat(hd[i], stats[i]);
     return MLH_OK;
 }
 
-// The host-polled form: chunks of LM launches with the loop's verdict read between them (statistics, good-feature selections, RCCL ranks, and the re-solve of a frame
-// whose loop outgrew its look-ahead).
-// The Levenberg-Marquardt launches of scan2map in the consumer-side form (match.hip: lm_consume_kernel) -- the default where it applies (one GPU, every feature
-// used, no statistics asked for) -- and the whole LM loop of an outer iteration as ONE launch whose workgroups synchronise among themselves (match.hip:
-// lm_loop_kernel); Schedule::LM_CONSUMER and Schedule::LM_LOOP (ctx.hpp) keep the classic launches / one launch per LM iteration.
-// ... the latter where every tile's workgroup can be resident at once on what this context's stream may use of the device (mlh_ctx::caps, asked at mlh_create)
-static bool lm_loop_applies(const mlh_ctx *ctx, int which, int tiles) { return schedule_on(Schedule::LM_LOOP) && loop_tiles_ok(ctx, which, tiles); }
-// The barrier of a one-launch loop was given up on (`done` bit 2 of its publication): the gate comes down, and the caller solves the frame again through the
-// launch-per-iteration form -- same arithmetic, same pose bits, no residency requirement
-static void note_loop_timeout(mlh_ctx *ctx, int which, int tiles, bool solved_again)
+// ---------------------------------------------------------------- scan2MapOptimization: the forms a frame's launches take
+enum class S2mForm {   // per outer iteration: correspondences (+ a good-feature selection), then a Levenberg-Marquardt loop on them -- where that loop runs:
+    HOST_STEPPED,      // stand-alone kernels: lm_begin_launch, then linearize_launch + lm_step_launch per iteration, the verdict fetched between chunks of them
+    FUSED_CHUNKS,      // the classic launches: the begin / step in the last workgroup of the launch that evaluated (TAIL_LM_BEGIN / _STEP), polled between chunks
+    CONSUMER_CHUNKS,   // the consumer-side launches: the begin / step in every workgroup of the NEXT launch (LMC_BEGIN / _STEP) -- one launch more per loop
+    LOOP               // an outer iteration's whole loop as ONE launch whose workgroups synchronise among themselves (LMC_LOOP); the frame is enqueued at once
+};
+static bool s2m_selects(const mlh_solver_opts *opts) { return opts->gf_method != MLH_GF_WO; }
+
+// THE decision: mlh_scan2map, mlh_scan2map_begin* and mlh_downsample_scan2map all ask here (DESIGN.md section 5 has it as a table). allow_loop: the caller has not
+// ruled the one-launch loop out; gate / tiles: the residency gate the loop launch would pass (mlh_ctx::caps::loop_max_tiles) and the workgroups it would have.
+static S2mForm s2m_form(const mlh_ctx *ctx, const mlh_solver_opts *opts, bool want_stats, bool allow_loop, int gate, int tiles)
 {
-    demote_loop_gate(ctx, which, tiles);
-    if (solved_again) ++ctx->caps.loop_fallbacks;
+    const bool one_gpu = !distributed(ctx);
+    // the mailbox communicator's exchange rides in the fused finish; under RCCL, and for a selection's rows on several ranks, the host steps through the iterations
+    if (!one_gpu && !(ctx->p2p.active && !s2m_selects(opts))) return S2mForm::HOST_STEPPED;
+    // Consumer-side: one GPU, nobody reading per-iteration statistics, few enough tiles that every workgroup summing every tile's record pays (the Gauss-Newton
+    // path's limit). Gate 1 -- the fused thinning + solve call, which sizes its launches for the UN-thinned clouds -- deliberately tests that bound against its own
+    // gate only (FUSED_LOOP_MAX_TILES, set_loop_gates): the thinned frame it solves is far below the limit.
+    if (!one_gpu || want_stats || !schedule_on(Schedule::LM_CONSUMER) || (gate != 1 && tiles > GN_DEFER_MAX_TILES)) return S2mForm::FUSED_CHUNKS;
+    if (allow_loop && schedule_on(Schedule::LM_LOOP) && loop_tiles_ok(ctx, gate, tiles)) return S2mForm::LOOP;      // (every tile's workgroup resident at once)
+    return s2m_selects(opts) ? S2mForm::FUSED_CHUNKS : S2mForm::CONSUMER_CHUNKS;      // (linearize_launch's LM begin has no consumer-side chunk form)
 }
 
-// The pose a one-launch loop published to rec / seq (rec null: the context's record 0), into pose_out. *given_up: the loop's barrier was given up on (`done` bit 2)
-// -- pose_out is left as it was, and the caller solves the frame again through the launch-per-iteration form (note_loop_timeout)
+// The pose a one-launch loop published to rec / seq, into pose_out. *given_up: DONE_GIVEN_UP -- pose_out is left as it was (note_loop_given_up)
 static int collect_loop_pose(mlh_ctx *ctx, unsigned long long seq, HostPublish *rec, double pose_out[7], bool *given_up)
 {
     HostPublish hp;
     int rc = wait_published(ctx, seq, hp, rec);
     if (rc) return rc;
-    *given_up = (hp.done & 4) != 0;
-    if (*given_up) return MLH_OK;
-    if ((rc = prof_drain(ctx))) return rc;
-    for (int i = 0; i < 7; ++i) pose_out[i] = hp.x[i];
+    *given_up = (hp.done & DONE_GIVEN_UP) != 0;
+    if (*given_up || (rc = prof_drain(ctx))) return rc;
+    pose_copy(pose_out, hp.x);
     return MLH_OK;
 }
 
 static bool s2m_warm_applies(const mlh_ctx *ctx) { return ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi && ctx->own_mod <= 1; }
-
-// every workgroup sums every tile's record: the same size limit as the Gauss-Newton path's deferred finish (GN_DEFER_MAX_TILES)
-static bool lm_consumer_enabled(const mlh_ctx *ctx) { return schedule_on(Schedule::LM_CONSUMER) && feature_tiles(ctx) <= GN_DEFER_MAX_TILES; }
 
 // scan2MapOptimization matches through ActiveFeatureSelection::goodFeatureMatching, which passes n_neigh = 5 and CHECK_FOV = false to match*PointFromMap whatever
 // the caller's configuration says (lidar_mapper.h:256-283, every gf_method): MLH_FLAG_CHECK_FOV does not apply to the scan2map entry points. (The flag is for
@@ -1694,207 +1712,199 @@ static mlh_solver_opts scan2map_opts(const mlh_solver_opts *o)
     return c;
 }
 
-// One outer iteration of scan2map in the one-launch-loop form: the match launch (its fit rides in the loop launch where loop_fit_fusable says so), then the launch
-// that runs the iteration's whole LM loop on the device. The start pose goes in with outer iteration 0; the last one publishes pose and verdict to rec / seq.
-// m_dev: the feature counts on the device (mlh_downsample_scan2map), or null.
-static int enqueue_s2m_loop_outer(mlh_ctx *ctx, const mlh_solver_opts *opts, int outer, const double *pose, const int *m_dev, HostPublish *rec, unsigned long long seq)
+// The match launch of an outer iteration (records_only: a consumer-side launch runs the LM begin). Outer iterations behind the first search the same map for the
+// same features from a pose a few centimetres away: bounded by the neighbours the previous one left (knn_feature_warm: still the exact 5-NN). `unpolled`
+// (scan2map_submit): the host has not read the previous LM loop's verdict.
+static MatchArgs s2m_begin_args(const mlh_ctx *ctx, const mlh_solver_opts *opts, bool records_only, int outer, const double *pose, bool unpolled)
 {
     MatchArgs a = args_from_opts(opts, 3, 0);
-    a.finish = 0; a.lm_max_it = opts->max_lm_iterations; a.m_dev = m_dev;
-    if (outer == 0) a.init_pose = pose;
-    a.warm = outer >= 1 && s2m_warm_applies(ctx);
-    a.no_fit = loop_fit_fusable(a);
-    int rc = match_launch(ctx, a);
-    if (rc) return rc;
-    MatchArgs b = args_from_opts(opts, 3, 1);
-    b.finish = 0; b.lmc = 3; b.lmc_j = 1; b.lm_max_it = opts->max_lm_iterations; b.m_dev = m_dev; b.fit_in_loop = a.no_fit;
-    b.lm_expect_done = outer == 0 ? -1 : 1;
-    if (outer == 0) b.init_pose = pose;
-    if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
-    return lm_consume_launch(ctx, b);
-}
-
-// The match launch of an outer iteration in the forms with a launch per LM iteration: its finish runs the LM begin, or (lmc) it only leaves its tiles' records to
-// the first consumer launch. Outer iterations behind the first search the same map for the same features from a pose a few centimetres away: bounded by the
-// neighbours the previous one left (knn_feature_warm: still the exact 5-NN). `unpolled` (scan2map_submit): the host has not read the previous LM loop's verdict --
-// the device raises lm_overflow if that loop has not terminated.
-static MatchArgs s2m_begin_args(const mlh_ctx *ctx, const mlh_solver_opts *opts, bool lmc, int outer, const double *pose, bool unpolled)
-{
-    MatchArgs a = args_from_opts(opts, 3, 0);
-    a.finish = lmc ? 0 : 3; a.lm_max_it = opts->max_lm_iterations;
-    if (outer == 0) { a.init_pose = pose; a.lm_expect_done = -1; }
-    else if (unpolled) a.lm_expect_done = 1;
+    a.finish = records_only ? TAIL_RECORDS : TAIL_LM_BEGIN; a.lm_max_it = opts->max_lm_iterations;
+    if (outer == 0) { a.init_pose = pose; a.lm_expect_done = LM_FIRST_OF_SOLVE; }
+    else if (unpolled) a.lm_expect_done = LM_VERDICT_UNREAD;
     a.warm = outer >= 1 && s2m_warm_applies(ctx);
     return a;
 }
 
-// The j-th (from 0) LM launch behind that match launch: the consumer-side form (lmc: sums its predecessor's records, runs the LM begin (j = 0) or step, evaluates at
-// the candidate) or the classic one (finish 4: the linearise kernel's last workgroup runs the step). `unpolled` as above.
+// The j-th (from 0) LM launch behind that match launch, consumer-side (lmc) or classic. `unpolled` as above.
 static MatchArgs s2m_lm_args(const mlh_solver_opts *opts, bool lmc, int outer, int j, const double *pose, bool unpolled)
 {
     MatchArgs a = args_from_opts(opts, 3, 1);
-    a.finish = 4; a.lm_max_it = opts->max_lm_iterations;
+    a.finish = TAIL_LM_STEP; a.lm_max_it = opts->max_lm_iterations;
     if (lmc) {
-        a.finish = 0; a.lmc = j == 0 ? 1 : 2; a.lmc_j = j + 1;
-        if (j == 0 && outer == 0) { a.init_pose = pose; a.lm_expect_done = -1; }
-        else if (j == 0 && unpolled) a.lm_expect_done = 1;
+        a.finish = TAIL_RECORDS; a.lmc = j == 0 ? LMC_BEGIN : LMC_STEP; a.lmc_j = j + 1;
+        if (j == 0 && outer == 0) { a.init_pose = pose; a.lm_expect_done = LM_FIRST_OF_SOLVE; }
+        else if (j == 0 && unpolled) a.lm_expect_done = LM_VERDICT_UNREAD;
     }
     return a;
 }
 
+// The launch that runs outer iteration `outer`'s whole LM loop on the device. The start pose goes in with the first one (pose null: the state holds it), the last
+// one publishes pose and verdict to rec / seq. `match_in_front`: the match launch enqueued in front of it, whose fit moves into the loop launch where
+// loop_fit_fusable says so -- no_fit and fit_in_loop leave here as a pair -- or null: a linearise launch over a selection's rows is in front.
+static MatchArgs s2m_loop_args(const mlh_solver_opts *opts, int outer, const double *pose, HostPublish *rec, unsigned long long seq, MatchArgs *match_in_front)
+{
+    MatchArgs b = args_from_opts(opts, 3, 1);
+    b.lmc = LMC_LOOP; b.lmc_j = 1; b.lm_max_it = opts->max_lm_iterations;
+    b.lm_expect_done = outer == 0 ? LM_FIRST_OF_SOLVE : LM_VERDICT_UNREAD;
+    if (outer == 0) b.init_pose = pose;
+    if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
+    if (match_in_front) { b.m_dev = match_in_front->m_dev; match_in_front->no_fit = b.fit_in_loop = loop_fit_fusable(*match_in_front); }
+    return b;
+}
+
+// The selection step of an outer iteration: goodFeatureMatching for corners, then surfs (cpp:503-533), each against a fresh 1e-6 * I. Both kinds' dense passes and
+// their copies to the host are enqueued first: the corner selection loop runs on the host while the surf pass and its copies are still in flight, and each kind's
+// flags go back without a wait (the linearise launch that evaluates the selected rows -- problem.Evaluate, cpp:575-581 -- is behind them on the stream)
+static int s2m_select(mlh_ctx *ctx, const mlh_solver_opts *opts, std::mt19937 &rng)
+{
+    int rc;
+    std::vector<int32_t> sel;
+    for (int kind : {MLH_CORNER, MLH_SURF})
+        if ((rc = good_feature_stage(ctx, kind, opts->gf_method, opts->gf_ratio, rng, opts->min_match_sq_dis, opts->min_plane_dis, true))) return rc;
+    if ((rc = good_feature_fps_flush(ctx))) return rc;      // ('fps': the two kinds' loops side by side in one launch; nothing pending otherwise)
+    for (int kind : {MLH_CORNER, MLH_SURF}) {
+        double Hsel[36];
+        for (int i = 0; i < 36; ++i) Hsel[i] = (i % 7 == 0) ? 1e-6 : 0.0;
+        if ((rc = good_feature_finish(ctx, kind, opts->gf_method, opts->gf_ratio, rng, sel, Hsel, nullptr))) return rc;
+    }
+    return MLH_OK;
+}
+
+// A whole frame in the LOOP form, enqueued: per outer iteration the match launch -- or the selection and the linearisation of the rows it kept, which leaves records;
+// the pose then stays on the device, each selection starts from it -- and the loop launch. m_dev: the feature counts on the device (mlh_downsample_scan2map), or null.
+static int enqueue_s2m_loop_frame(mlh_ctx *ctx, const mlh_solver_opts *opts, const double *pose, const int *m_dev, HostPublish *rec, unsigned long long seq)
+{
+    int rc = s2m_selects(opts) ? upload_pose(ctx, pose) : MLH_OK;
+    std::mt19937 rng((uint32_t)opts->gf_seed);
+    for (int outer = 0; outer < opts->max_outer && !rc; ++outer) {
+        MatchArgs a = args_from_opts(opts, 3, 0), b;
+        a.lm_max_it = opts->max_lm_iterations; a.m_dev = m_dev;
+        if (s2m_selects(opts)) {
+            if ((rc = s2m_select(ctx, opts, rng)) || (rc = linearize_launch(ctx, a))) return rc;
+            b = s2m_loop_args(opts, outer, nullptr, rec, seq, nullptr);
+        } else {
+            if (outer == 0) a.init_pose = pose;
+            a.warm = outer >= 1 && s2m_warm_applies(ctx);
+            b = s2m_loop_args(opts, outer, pose, rec, seq, &a);
+            if ((rc = match_launch(ctx, a))) return rc;
+        }
+        rc = lm_consume_launch(ctx, b);
+    }
+    return rc;
+}
+
+// LM iterations enqueued between two looks at the device-side verdict: six first (the mapper's solves converge in 5-7), then two at a time -- launches enqueued
+// after convergence are no-ops, but each still costs a dispatch (profiles/r03_frame_timeline.txt: five of them behind a 7-iteration solve)
+constexpr int S2M_FIRST_CHUNK = 6, S2M_NEXT_CHUNK = 2;
+
+// One outer iteration's LM launches (FUSED_CHUNKS, or CONSUMER_CHUNKS: lmc) in chunks, each ending in a launch that publishes pose + `done` itself. The chunk
+// after the one whose verdict the host is waiting for is already enqueued (into the other of the two pinned records: *chunk_idx counts on through the frame): when
+// the verdict is "not yet" the GPU has gone on without the host's round trip (~15 us of idle stream per poll in profiles/r03_frame_cpp_timeline_*.txt), when it
+// is "done" the chunk ahead is two launches that find `done` set and leave. *verdict: the last publication read.
+static int s2m_lm_chunks(mlh_ctx *ctx, const mlh_solver_opts *opts, bool lmc, int outer, const double *pose, int *chunk_idx, HostPublish *verdict)
+{
+    struct Pending { unsigned long long seq; HostPublish *rec; } pend[2];
+    int rc, n_pend = 0, enq = 0, lm_j = 0;
+    const int lm_cap = opts->max_lm_iterations + (lmc ? 1 : 0);     // launches after which the loop has terminated by itself
+    auto enqueue_chunk = [&](int count) -> int {
+        for (int j = 0; j < count; ++j) {
+            MatchArgs a = s2m_lm_args(opts, lmc, outer, lm_j++, pose, false);
+            if (j == count - 1) {                   // the chunk's last launch publishes (no publication launch)
+                if ((rc = publish_slot(ctx, &a.publish, &a.publish_seq, *chunk_idx))) return rc;
+                pend[n_pend++] = Pending{a.publish_seq, a.publish};
+            }
+            if ((rc = lmc ? lm_consume_launch(ctx, a) : linearize_launch(ctx, a))) return rc;
+        }
+        ++*chunk_idx;
+        enq += count;
+        return MLH_OK;
+    };
+    if ((rc = enqueue_chunk(std::min(S2M_FIRST_CHUNK + (lmc ? 1 : 0), lm_cap)))) return rc;
+    for (;;) {
+        if (enq < lm_cap && n_pend < 2 && (rc = enqueue_chunk(std::min(S2M_NEXT_CHUNK, lm_cap - enq)))) return rc;
+        // pinned-memory poll of the device-side `done` flag (no copy engine, no blocking wait)
+        if ((rc = wait_published(ctx, pend[0].seq, *verdict, pend[0].rec))) return rc;
+        pend[0] = pend[1]; --n_pend;
+        if ((verdict->done & DONE_TERMINATED) || n_pend == 0) return MLH_OK;
+    }
+}
+
+// One outer iteration's LM loop in the HOST_STEPPED form, behind a launch that left the rows' sums in the state
+static int s2m_lm_host_stepped(mlh_ctx *ctx, const mlh_solver_opts *opts, int stat_slot)
+{
+    int rc = lm_begin_launch(ctx, opts->map_eig_thre, opts->max_lm_iterations, stat_slot);
+    for (int it = 0, j_end = 0; !rc && it < opts->max_lm_iterations; it = j_end) {
+        j_end = std::min(it + (it == 0 ? S2M_FIRST_CHUNK : S2M_NEXT_CHUNK), opts->max_lm_iterations);
+        for (int j = it; j < j_end; ++j) {
+            if ((rc = linearize_launch(ctx, args_from_opts(opts, 3, 1)))) return rc;
+            if ((rc = lm_step_launch(ctx, opts->max_lm_iterations, -1))) return rc;
+        }
+        HostPublish hp;
+        if ((rc = fetch_published(ctx, hp))) return rc;
+        if (hp.done) break;      // (publish_kernel: SolverState::done)
+    }
+    return rc;
+}
+
+// A frame in a form with a launch per LM iteration (statistics, RCCL ranks, frames beyond the loop's gates, the re-solve of a frame whose loop was given up or
+// outgrew its look-ahead): the host reads each loop's verdict before it enqueues the next outer iteration
+static int s2m_polled_frame(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts, mlh_iter_stat *stats, S2mForm form)
+{
+    const bool in_launch = form != S2mForm::HOST_STEPPED, lmc = form == S2mForm::CONSUMER_CHUNKS;
+    int rc;
+    // (every feature used, the LM begin in the match launch's own tail or its consumer: the pose goes in with the first launch's kernel arguments instead)
+    if ((!in_launch || s2m_selects(opts)) && (rc = upload_pose(ctx, pose_inout))) return rc;
+    HostPublish verdict;       // in_launch: the last chunk's publication already carries the pose
+    int chunk_idx = 0;
+    std::mt19937 rng((uint32_t)opts->gf_seed);
+    for (int outer = 0; outer < opts->max_outer; ++outer) {
+        const int stat_slot = stats ? outer : -1;
+        if (s2m_selects(opts)) {
+            if ((rc = s2m_select(ctx, opts, rng))) return rc;
+            MatchArgs a = args_from_opts(opts, 3, 0);      // the evaluation of the rows it kept: the LM begin rides in its tail, or lm_begin_launch follows
+            if (in_launch) { a.finish = TAIL_LM_BEGIN; a.stat_slot = stat_slot; a.lm_max_it = opts->max_lm_iterations; }
+            rc = linearize_launch(ctx, a);
+        } else if (in_launch) {
+            MatchArgs a = s2m_begin_args(ctx, opts, lmc, outer, pose_inout, false);
+            a.stat_slot = stat_slot;
+            rc = match_launch(ctx, a);
+        } else rc = match_launch(ctx, args_from_opts(opts, 3, 0));
+        if (rc) return rc;
+        if ((rc = in_launch ? s2m_lm_chunks(ctx, opts, lmc, outer, pose_inout, &chunk_idx, &verdict) : s2m_lm_host_stepped(ctx, opts, stat_slot))) return rc;
+        if (stats && (rc = lm_finish_launch(ctx, outer))) return rc;     // fills the record's LM summary
+    }
+    if (in_launch && !stats) {
+        if ((rc = prof_drain(ctx))) return rc;
+        pose_copy(pose_inout, verdict.x);
+        return MLH_OK;
+    }
+    return fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer);
+}
+
+// The synchronous solve. allow_loop = false (mlh_scan2map_end / mlh_downsample_scan2map, behind a loop that was given up): a launch-per-iteration form
 static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts_in, mlh_iter_stat *stats, bool allow_loop = true)
 {
     if (!ctx || !pose_inout || !opts_in || opts_in->max_outer <= 0) return MLH_ERR_INVALID;
     const mlh_solver_opts opts_v = scan2map_opts(opts_in), *opts = &opts_v;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
-    int rc = ensure_state(ctx, opts->max_outer);
+    int rc = solver_begin(ctx, opts->max_outer);
     if (rc) return rc;
     if (!scan2map_has_maps(ctx)) {
         if (stats) std::memset(stats, 0, sizeof(mlh_iter_stat) * size_t(opts->max_outer));
         return MLH_OK;
     }
     if (ctx->feat[0].m <= 0 || ctx->feat[1].m <= 0) return fail(ctx, MLH_ERR_STATE, "features_set is required for both kinds");
-    // one GPU, every feature used (wo_gf): the LM begin rides in the match launch and every LM step in its linearise launch -- an outer
-    // iteration is 2 + (LM iterations) launches, the pose goes in with the first launch's kernel arguments
-    const bool fused = (!distributed(ctx) || ctx->p2p.active) && opts->gf_method == MLH_GF_WO;      // (mailbox communicator: the exchange rides in the finish)
-    // with a feature selection (one GPU): the dense passes and the selection come first, then the LM begin rides in the launch that evaluates the
-    // selected rows and every LM step in its linearise launch, as above
-    const bool fused_lm = fused || !distributed(ctx);
-    // ... and with nobody asking for per-iteration statistics, on one GPU: the LM step rides in the CONSUMER of the records -- the match launch leaves its tiles'
-    // records, every LM launch begins by summing its predecessor's and running the begin / step in all workgroups, then evaluates at the candidate (one launch more
-    // per loop: the last evaluation's verdict is the next launch's)
-    const bool lmc = fused && !stats && !distributed(ctx) && lm_consumer_enabled(ctx);
-    const int loop_tiles = feature_tiles(ctx);
-    if (lmc && allow_loop && lm_loop_applies(ctx, 0, loop_tiles)) {
-        // the LM loop of every outer iteration is one launch that ends when the loop does: the whole frame is enqueued at once, the last launch publishes
-        HostPublish *rec = nullptr;
-        unsigned long long seq = 0;
-        if ((rc = publish_slot(ctx, &rec, &seq, 0))) return rc;
-        for (int outer = 0; outer < opts->max_outer; ++outer)
-            if ((rc = enqueue_s2m_loop_outer(ctx, opts, outer, pose_inout, nullptr, rec, seq))) return rc;
-        bool given_up = false;
-        if ((rc = collect_loop_pose(ctx, seq, rec, pose_inout, &given_up))) return rc;
-        if (given_up) {
-            // the loop's workgroups did not all arrive at a barrier (not all resident at once beside whatever else runs here): the frame again, from the start
-            // pose the caller still holds, through the launch-per-iteration form
-            note_loop_timeout(ctx, 0, loop_tiles, true);
-            return scan2map_polled(ctx, pose_inout, opts, stats, false);
-        }
-        return MLH_OK;
-    }
-    if (!fused && (rc = upload_pose(ctx, pose_inout))) return rc;
-    // LM iterations enqueued between two looks at the device-side `done` flag: six first (the mapper's solves converge in 5-7), then two at a time -- launches
-    // enqueued after convergence are no-ops, but each still costs a dispatch (profiles/r03_frame_timeline.txt: five of them behind a 7-iteration solve)
-    const int first_chunk = 6, next_chunk = 2;
-    HostPublish last_hp;
-    bool have_hp = false;  // fused path: the last chunk's publication already carries the pose
-    int lm_chunk_idx = 0;  // which of the two pinned publication records the next chunk writes
-    HostPublish *gf_loop_rec = nullptr;      // a good-feature frame whose LM loops ran as one launch each: the record its last launch publishes into
-    unsigned long long gf_loop_seq = 0;
-    std::mt19937 rng((uint32_t)opts->gf_seed);
-    for (int outer = 0; outer < opts->max_outer; ++outer) {
-        if (fused) {
-            MatchArgs a = s2m_begin_args(ctx, opts, lmc, outer, pose_inout, false);
-            a.stat_slot = stats ? outer : -1;
-            if ((rc = match_launch(ctx, a))) return rc;
-        } else if (opts->gf_method == MLH_GF_WO) {
-            if ((rc = match_launch(ctx, args_from_opts(opts, 3, 0)))) return rc;
-        } else {
-            // goodFeatureMatching for corners, then surfs (cpp:503-533), each against a fresh 1e-6*I; then the evaluation of the
-            // selected residual blocks at the current pose (problem.Evaluate, cpp:575-581)
-            // Both kinds' dense passes and their copies to the host are enqueued first: the corner selection loop runs on the host while the surf pass
-            // and its copies are still in flight, and each kind's flags go back without a wait (the linearise launch is behind them on the stream)
-            std::vector<int32_t> sel;
-            for (int kind : {MLH_CORNER, MLH_SURF})
-                if ((rc = good_feature_stage(ctx, kind, opts->gf_method, opts->gf_ratio, rng, opts->min_match_sq_dis, opts->min_plane_dis, true))) return rc;
-            if ((rc = good_feature_fps_flush(ctx))) return rc;      // ('fps': the two kinds' loops side by side in one launch; nothing pending otherwise)
-            for (int kind : {MLH_CORNER, MLH_SURF}) {
-                double Hsel[36];
-                for (int i = 0; i < 36; ++i) Hsel[i] = (i % 7 == 0) ? 1e-6 : 0.0;
-                if ((rc = good_feature_finish(ctx, kind, opts->gf_method, opts->gf_ratio, rng, sel, Hsel, nullptr))) return rc;
-            }
-            MatchArgs a = args_from_opts(opts, 3, 0);
-            if (fused_lm) { a.finish = 3; a.stat_slot = stats ? outer : -1; a.lm_max_it = opts->max_lm_iterations; a.lm_min_blocks = 0; }
-            // the selected rows' LM loop as one launch (as the wo_gf frame's, above): the linearisation of the selection only leaves its records
-            const bool loop_gf = fused_lm && !stats && !distributed(ctx) && lm_consumer_enabled(ctx) && allow_loop && lm_loop_applies(ctx, 0, loop_tiles);
-            if (loop_gf) a.finish = 0;
-            if ((rc = linearize_launch(ctx, a))) return rc;
-            if (loop_gf) {
-                MatchArgs b = args_from_opts(opts, 3, 1);
-                b.finish = 0; b.lmc = 3; b.lmc_j = 1; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 0;
-                b.lm_expect_done = outer == 0 ? -1 : 1;
-                if (outer == opts->max_outer - 1) {         // the last loop launch publishes pose (and a barrier given up on, if any)
-                    if ((rc = publish_slot(ctx, &gf_loop_rec, &gf_loop_seq, 0))) return rc;
-                    b.publish = gf_loop_rec; b.publish_seq = gf_loop_seq;
-                }
-                if ((rc = lm_consume_launch(ctx, b))) return rc;
-                continue;                                   // (the pose stays on the device: the next outer iteration's selection starts from it)
-            }
-        }
-        if (!fused_lm && (rc = lm_begin_launch(ctx, opts->map_eig_thre, opts->max_lm_iterations, stats ? outer : -1))) return rc;
-        if (fused_lm) {
-            // Chunks of LM launches, each ending in a launch that publishes pose + `done` itself. The chunk after the one whose verdict the host is waiting for
-            // is already enqueued (into the other pinned record): when the verdict is "not yet" the GPU has gone on without the host's round trip (~15 us of idle
-            // stream per poll in profiles/r03_frame_cpp_timeline_*.txt), when it is "done" the chunk ahead is two launches that find `done` set and leave.
-            struct Pending { unsigned long long seq; HostPublish *rec; } pend[2];
-            int n_pend = 0, enq = 0, lm_j = 0;
-            const int lm_cap = opts->max_lm_iterations + (lmc ? 1 : 0);     // launches after which the loop has terminated by itself
-            auto enqueue_chunk = [&](int count) -> int {
-                for (int j = 0; j < count; ++j) {
-                    MatchArgs a = s2m_lm_args(opts, lmc, outer, lm_j++, pose_inout, false);
-                    if (j == count - 1) {                   // the chunk's last launch publishes (no publication launch)
-                        unsigned long long seq = 0;
-                        int prc = publish_slot(ctx, &a.publish, &seq, lm_chunk_idx);
-                        if (prc) return prc;
-                        a.publish_seq = seq;
-                        pend[n_pend++] = Pending{seq, a.publish};
-                    }
-                    int lrc = lmc ? lm_consume_launch(ctx, a) : linearize_launch(ctx, a);
-                    if (lrc) return lrc;
-                }
-                ++lm_chunk_idx;
-                enq += count;
-                return MLH_OK;
-            };
-            if ((rc = enqueue_chunk(std::min(first_chunk + (lmc ? 1 : 0), lm_cap)))) return rc;
-            for (;;) {
-                if (enq < lm_cap && n_pend < 2 && (rc = enqueue_chunk(std::min(next_chunk, lm_cap - enq)))) return rc;
-                HostPublish hp;                             // pinned-memory poll of the device-side `done` flag (no copy engine, no blocking wait)
-                if ((rc = wait_published(ctx, pend[0].seq, hp, pend[0].rec))) return rc;
-                last_hp = hp; have_hp = true;
-                pend[0] = pend[1]; --n_pend;
-                if ((hp.done & 1) || n_pend == 0) break;
-            }
-        } else {
-            for (int it = 0, j_end = 0; it < opts->max_lm_iterations; it = j_end) {
-                j_end = std::min(it + (it == 0 ? first_chunk : next_chunk), opts->max_lm_iterations);
-                for (int j = it; j < j_end; ++j) {
-                    if ((rc = linearize_launch(ctx, args_from_opts(opts, 3, 1)))) return rc;
-                    if ((rc = lm_step_launch(ctx, opts->max_lm_iterations, -1))) return rc;
-                }
-                HostPublish hp;
-                if ((rc = fetch_published(ctx, hp))) return rc;
-                if (hp.done) break;
-            }
-        }
-        if (stats && (rc = lm_finish_launch(ctx, outer))) return rc;     // fills the record's LM summary
-    }
-    if (gf_loop_rec) {
-        bool given_up = false;
-        if ((rc = collect_loop_pose(ctx, gf_loop_seq, gf_loop_rec, pose_inout, &given_up))) return rc;
-        if (given_up) {                  // as above (the selection's draws start from opts->gf_seed again: the same frame)
-            note_loop_timeout(ctx, 0, loop_tiles, true);
-            return scan2map_polled(ctx, pose_inout, opts, stats, false);
-        }
-        return MLH_OK;
-    }
-    if (fused_lm && !stats && have_hp) {
-        if ((rc = prof_drain(ctx))) return rc;
-        for (int i = 0; i < 7; ++i) pose_inout[i] = last_hp.x[i];
-        return MLH_OK;
-    }
-    return fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer);
+    const int tiles = feature_tiles(ctx);
+    const S2mForm form = s2m_form(ctx, opts, stats != nullptr, allow_loop, 0, tiles);
+    if (form != S2mForm::LOOP) return s2m_polled_frame(ctx, pose_inout, opts, stats, form);
+    HostPublish *rec = nullptr;       // the whole frame is enqueued at once, the last loop launch publishes
+    unsigned long long seq = 0;
+    bool given_up = false;
+    if ((rc = publish_slot(ctx, &rec, &seq, 0)) || (rc = enqueue_s2m_loop_frame(ctx, opts, pose_inout, nullptr, rec, seq))) return rc;
+    if ((rc = collect_loop_pose(ctx, seq, rec, pose_inout, &given_up)) || !given_up) return rc;
+    // (a selection's draws start from opts->gf_seed again: the same frame)
+    note_loop_given_up(ctx, 0, tiles);
+    return s2m_polled_frame(ctx, pose_inout, opts, stats, s2m_form(ctx, opts, stats != nullptr, false, 0, tiles));
 }
 
 // ---- scan2MapOptimization, submitted and collected separately (the call the reference makes once per frame, pipelined like mlh_gn_solve_begin / _end).
@@ -1916,23 +1926,17 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     int rc = ctx->solves.admit(ctx, "two solves are already in flight: collect the older one first", &seq, &rec, &slot_p);
     if (rc) return rc;
     mlh_ctx::SolveSlot &slot = *slot_p;
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
-    if ((rc = ensure_state(ctx, 0))) return rc;
+    if ((rc = solver_begin(ctx, 0))) return rc;
     // everything that can refuse the frame is checked BEFORE the chain launch below rewrites the device pose: a refused mlh_scan2map_begin_chained leaves the
     // state as it found it, so the caller's retry does not apply transformUpdate / transformAssociateToMap twice
     const bool have_maps = scan2map_has_maps(ctx);
     if (have_maps && (ctx->feat[0].m <= 0 || ctx->feat[1].m <= 0)) return fail(ctx, MLH_ERR_STATE, "features_set is required for both kinds");
-    slot.kind = 1; slot.chained = pose_in == nullptr; slot.opts = *opts; slot.epoch = ctx->stage_epoch; slot.tainted = false;
-    if (pose_in) for (int i = 0; i < 7; ++i) slot.start[i] = pose_in[i];
-    if (!pose_in) {
-        PoseArg pa, pb;
-        for (int i = 0; i < 7; ++i) { pa.p[i] = wodom_prev[i]; pb.p[i] = wodom_cur[i]; }
-        MLH_LAUNCH(chain_pose_kernel, dim3(1), dim3(64), 0, ctx->stream, ctx->state.as<SolverState>(), pa, pb, rec);
-        MLH_HIP(ctx, hipGetLastError());
-    }
+    slot.kind = mlh_ctx::SolveSlot::SCAN2MAP; slot.chained = pose_in == nullptr; slot.opts = *opts; slot.epoch = ctx->stage_epoch; slot.tainted = false;
+    if (pose_in) pose_copy(slot.start, pose_in);
+    else if ((rc = enqueue_chain_pose(ctx, wodom_prev, wodom_cur, rec))) return rc;
     // scan2MapOptimization runs only where scan2map_has_maps: otherwise the start pose is the result
     if (!have_maps) {
-        slot.kind = 2;
+        slot.kind = mlh_ctx::SolveSlot::SCAN2MAP_NO_MAP;
         if (!pose_in) {          // chained: the start pose exists on the device only
             MLH_LAUNCH(publish_kernel, dim3(1), dim3(64), 0, ctx->stream, (const SolverState *)ctx->state.as<SolverState>(), rec, seq);
             MLH_HIP(ctx, hipGetLastError());
@@ -1941,13 +1945,13 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
         return MLH_OK;
     }
     const int budget = std::max(1, std::min(lm_lookahead > 0 ? lm_lookahead : ctx->solves.lm_lookahead_auto, opts->max_lm_iterations));
-    // the consumer-side form of the LM launches (scan2map_polled): budget + 1 launches run `budget` LM steps
-    const bool lmc = !ctx->p2p.active && lm_consumer_enabled(ctx);
-    // ... or one launch per LM loop, which ends on the device when the loop does: no budget, nothing to overflow (an explicit lm_lookahead keeps the launches it counts)
-    const bool loop = lmc && lm_lookahead <= 0 && lm_loop_applies(ctx, 0, feature_tiles(ctx));
-    slot.loop_tiles = loop ? feature_tiles(ctx) : 0;
-    for (int outer = 0; loop && outer < opts->max_outer; ++outer)
-        if ((rc = enqueue_s2m_loop_outer(ctx, opts, outer, pose_in, nullptr, rec, seq))) return rc;
+    // Consumer-side (`budget + 1` launches run `budget` LM steps) unless the mailbox communicator is active -- or one launch per LM loop, which ends on the device
+    // when the loop does: no budget, nothing to overflow. An explicit lm_lookahead keeps the launches it counts: it rules the loop out.
+    const int tiles = feature_tiles(ctx);
+    const S2mForm form = s2m_form(ctx, opts, false, lm_lookahead <= 0, 0, tiles);
+    const bool loop = form == S2mForm::LOOP, lmc = form == S2mForm::CONSUMER_CHUNKS;
+    slot.loop_tiles = loop ? tiles : 0;
+    if (loop && (rc = enqueue_s2m_loop_frame(ctx, opts, pose_in, nullptr, rec, seq))) return rc;
     for (int outer = 0; !loop && outer < opts->max_outer; ++outer) {
         if ((rc = match_launch(ctx, s2m_begin_args(ctx, opts, lmc, outer, pose_in, true)))) return rc;
         const int n_launch = budget + (lmc ? 1 : 0);
@@ -1981,59 +1985,51 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
     if (!ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, "no solve in flight (mlh_scan2map_begin)");
     const unsigned long long seq = ctx->solves.oldest();
     mlh_ctx::SolveSlot slot = ctx->solves.slot[seq & 1];
-    if (slot.kind == 0) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_gn_solve_begin: collect it with mlh_gn_solve_end");
+    if (slot.kind == mlh_ctx::SolveSlot::GN) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_gn_solve_begin: collect it with mlh_gn_solve_end");
     HostPublish hp;
     int rc = MLH_OK;
-    if (slot.kind == 2 && !slot.chained) {
-        for (int i = 0; i < 7; ++i) hp.x[i] = slot.start[i];
-        hp.done = 1;
-    } else {
-        rc = wait_published(ctx, seq, hp, ctx->solves.record(seq));
-    }
+    const bool solved = slot.kind == mlh_ctx::SolveSlot::SCAN2MAP;       // (otherwise the maps were too small to optimise against: the start pose is the result)
+    if (solved || slot.chained) rc = wait_published(ctx, seq, hp, ctx->solves.record(seq));
+    else { pose_copy(hp.x, slot.start); hp.done = DONE_TERMINATED; }
     ctx->solves.retire(seq);
-    auto taint_successor = [&]() { ctx->solves.taint_successor(seq); };
-    if (rc) { taint_successor(); return rc; }
+    if (rc) { ctx->solves.taint_successor(seq); return rc; }
     if (!ctx->solves.pending() && (rc = prof_drain(ctx))) return rc;
-    const bool barrier_given_up = slot.kind == 1 && (hp.done & 4);       // (a one-launch LM loop whose workgroups were not all resident: lm_loop_kernel)
+    const bool barrier_given_up = solved && (hp.done & DONE_GIVEN_UP);       // (a one-launch LM loop whose workgroups were not all resident: lm_loop_kernel)
     if (barrier_given_up) demote_loop_gate(ctx, 0, slot.loop_tiles);
-    if (slot.kind == 1 && !barrier_given_up) {
+    if (solved && !barrier_given_up) {
         // the next frame's automatic look-ahead: what this frame's longest LM loop used, plus two (consecutive mapper frames need about the same); a frame that
         // overflowed doubles it
         const int used = int(hp.xb[2][0]);
-        const bool ok = (hp.done & 1) && !(hp.done & 2);
+        const bool ok = (hp.done & DONE_TERMINATED) && !(hp.done & DONE_OVERFLOWED);
         ctx->solves.lm_lookahead_auto = ok ? std::max(3, used + 2) : std::min(2 * std::max(ctx->solves.lm_lookahead_auto, 4), slot.opts.max_lm_iterations);
     }
-    if (slot.kind == 2 || ((hp.done & 1) && !(hp.done & 6))) {
-        for (int i = 0; i < 7; ++i) pose_out[i] = hp.x[i];
+    if (!solved || ((hp.done & DONE_TERMINATED) && !(hp.done & (DONE_OVERFLOWED | DONE_GIVEN_UP)))) {
+        pose_copy(pose_out, hp.x);
         if (slot.tainted) {
             // this frame was chained behind one whose LM loop outgrew its look-ahead: it began from that frame's UNFINISHED pose. Its own loops terminated, but the
             // result is not the mapper's; a solve chained behind THIS one inherits the mark.
-            taint_successor();
+            ctx->solves.taint_successor(seq);
             if (status_out) { *status_out = 3; return MLH_OK; }
             return fail(ctx, MLH_ERR_INCOMPLETE, "mlh_scan2map_end: the frame was chained behind one that did not finish inside its look-ahead (status 3) and status_out is NULL");
         }
         return MLH_OK;
     }
     // the look-ahead was too short for this frame -- or its one-launch loop gave its barrier up
-    double start[7];
-    for (int i = 0; i < 7; ++i) start[i] = slot.chained ? hp.xb[1][i] : slot.start[i];
+    pose_copy(pose_out, slot.chained ? hp.xb[1] : slot.start);
     if (!ctx->solves.pending() && ctx->stage_epoch == slot.epoch && !slot.tainted) {
         // nothing younger is chained behind it and the frame's maps and features are still the staged ones: solve it as mlh_scan2map would have (after a barrier
-        // given up on: through the launch-per-iteration form)
-        for (int i = 0; i < 7; ++i) pose_out[i] = start[i];
+        // given up on: the second half of note_loop_given_up -- the gate came down above)
         if (status_out) *status_out = 2;
         if (barrier_given_up) ++ctx->caps.loop_fallbacks;
         return scan2map_polled(ctx, pose_out, &slot.opts, nullptr, !barrier_given_up);
     }
-    for (int i = 0; i < 7; ++i) pose_out[i] = start[i];
     // a younger solve chained behind this frame started from its unfinished pose: marked, and reported at ITS end (status 3)
-    taint_successor();
+    ctx->solves.taint_successor(seq);
     if (status_out) { *status_out = slot.tainted ? 3 : 1; return MLH_OK; }
     // the pose handed back is NOT a result, and this caller has no way to see that: a distinct return code instead of success
     return fail(ctx, MLH_ERR_INCOMPLETE, "mlh_scan2map_end: the frame did not finish inside its look-ahead and cannot be solved again here (status 1); status_out is NULL");
 }
 
-// The synchronous call: the polled form (where the LM loop of an outer iteration is one launch, its first branch enqueues the whole frame at once)
 int mlh_scan2map(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts, mlh_iter_stat *stats)
 {
     return scan2map_polled(ctx, pose_inout, opts, stats);
@@ -2057,11 +2053,12 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     const bool fused_pair = is_fused_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, intensity_offset_bytes, mem);
     // the loop kernel's barrier wants every tile's workgroup resident: the BOUND's tiles, since the real count is not known here
     const int bound_tiles = tiles_of(n_surf) + tiles_of(n_corner);
-    if (!fused_pair || !scan2map_has_maps(ctx) || distributed(ctx) || ctx->comm || opts->gf_method != MLH_GF_WO || !schedule_on(Schedule::LM_CONSUMER) ||
-        !lm_loop_applies(ctx, 1, bound_tiles) || ctx->solves.pending() || ctx->vox_member_order != 1)
+    // The one-call form exists as a frame of loop launches only (gate 1: see s2m_form), for device-resident clouds thinned by the one pipeline that publishes its
+    // counts from a kernel (the reference's member order on the device), every feature used, nothing in flight
+    if (!fused_pair || !scan2map_has_maps(ctx) || s2m_selects(opts) || s2m_form(ctx, opts, false, true, 1, bound_tiles) != S2mForm::LOOP || ctx->solves.pending() ||
+        ctx->vox_member_order != 1)
         return two_calls();
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }
-    int rc = ensure_state(ctx, 0);
+    int rc = solver_begin(ctx, 0);
     if (rc) return rc;
     ++ctx->stage_epoch;
     for (int k = 0; k < 2; ++k) { ctx->feat[k].matched = false; ctx->feat[k].m = 0; }
@@ -2082,7 +2079,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     HostPublish *rec = nullptr;
     unsigned long long seq = 0;
     if ((rc = publish_slot(ctx, &rec, &seq, 0))) return rc;
-    for (int outer = 0; outer < opts->max_outer && !rc; ++outer) rc = enqueue_s2m_loop_outer(ctx, opts, outer, pose_inout, ctx->thin_counts_dev, rec, seq);
+    rc = enqueue_s2m_loop_frame(ctx, opts, pose_inout, ctx->thin_counts_dev, rec, seq);
     double pose[7];
     bool given_up = false;
     if (!rc) rc = collect_loop_pose(ctx, seq, rec, pose, &given_up);
@@ -2096,13 +2093,9 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     *n_surf_features = real[0]; *n_corner_features = real[1];
     if ((rc = device_error_check(ctx))) return rc;
     if (real[0] <= 0 || real[1] <= 0) return fail(ctx, MLH_ERR_STATE, "features_set is required for both kinds");      // (what mlh_scan2map says of an empty kind)
-    if (given_up) {
-        // the loop's workgroups (sized for the un-thinned clouds) did not all arrive at a barrier: the thinned sets are staged and counted by now -- the solve again,
-        // as the second of the two calls, through the launch-per-iteration form
-        note_loop_timeout(ctx, 1, bound_tiles, true);
-        return scan2map_polled(ctx, pose_inout, opts, nullptr, false);
-    }
-    for (int i = 0; i < 7; ++i) pose_inout[i] = pose[i];
+    // given up (workgroups sized for the un-thinned clouds): the thinned sets are staged and counted by now -- the solve again, as the second of the two calls
+    if (given_up) { note_loop_given_up(ctx, 1, bound_tiles); return scan2map_polled(ctx, pose_inout, opts, nullptr, false); }
+    pose_copy(pose_inout, pose);
     return MLH_OK;
 }
 
@@ -2397,10 +2390,9 @@ int mlh_fused_cloud(mlh_ctx *ctx, int kind, const void **device_points, int32_t 
 
 int mlh_track_match(mlh_ctx *ctx, int kind, const double pose[7], const mlh_track_opts *opts, uint8_t *valid, double *coeffs)
 {
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
     if (!ctx || kind < 0 || kind > 1 || !pose || !opts) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = ensure_state(ctx, 0);
+    int rc = solver_begin(ctx, 0);
     if (rc) return rc;
     TrackArgs a = track_args(opts, 0);
     a.init_pose = pose;
@@ -2416,35 +2408,25 @@ int mlh_track_match(mlh_ctx *ctx, int kind, const double pose[7], const mlh_trac
     return MLH_OK;
 }
 
-static int track_cloud_impl(mlh_ctx *ctx, double pose_inout[7], const mlh_track_opts *opts, mlh_iter_stat *stats, bool allow_loop)
+// LidarTracker::trackCloud's rounds (lidar_tracker.cpp:42-121: match at the current estimate, then Ceres on the fixed correspondences -- Huber 0.1, <= 4
+// iterations, no degeneracy handling; fewer than 10 correspondences -> the round is skipped). Without per-round records the pose goes in with the first round's
+// kernel arguments and comes back from the last launch through pinned host memory; with records the state is uploaded and read back. `loop`: a round is the match
+// and ONE launch that runs its LM loop to the end on the device (track.hip: track_lm_loop_kernel; *given_up: it gave its barrier up); otherwise the LM begin /
+// step run in the linearisation kernel's last workgroup, 2 + max_lm_iterations launches per round.
+static int track_rounds(mlh_ctx *ctx, double pose_inout[7], const mlh_track_opts *opts, mlh_iter_stat *stats, bool loop, bool *given_up)
 {
-    { const int frc = gn_flush_pending(ctx); if (frc) return frc; }      // (a solve submitted with mlh_gn_solve_begin* may have left its last iteration as records)
-    if (!ctx || !pose_inout || !opts || opts->max_outer <= 0 || opts->max_lm_iterations <= 0) return MLH_ERR_INVALID;
-    MLH_HIP(ctx, hipSetDevice(ctx->device));
-    TrackSet &T = ctx->track;
-    if (!(T.grid[0].built && T.grid[1].built && T.m[0] > 0 && T.m[1] > 0)) return fail(ctx, MLH_ERR_STATE, "track_set_prev / track_set_cur are required for both kinds");
-    int rc = ensure_state(ctx, opts->max_outer);
-    if (rc) return rc;
-    // Without per-round records the pose goes in with the first round's kernel arguments and comes back from the last launch through
-    // pinned host memory: 2 + max_lm_iterations launches per round and nothing else. With records: the state is uploaded and read back.
     const bool lean = stats == nullptr;
+    int rc;
     if (!lean && (rc = upload_pose(ctx, pose_inout))) return rc;
-    // lean, one GPU, a frame's worth of features: a round is TWO launches -- the match and one launch that runs the round's LM loop to its end on the device
-    // (track.hip: track_lm_loop_kernel; Schedule::TRACK_LOOP, ctx.hpp, keeps 2 + max_lm_iterations launches per round)
-    const int tiles = tiles_of(T.m[0]) + tiles_of(T.m[1]);
-    const bool loop = lean && allow_loop && schedule_on(Schedule::TRACK_LOOP) && !distributed(ctx) && loop_tiles_ok(ctx, 2, tiles);
     HostPublish *rec = nullptr;
     unsigned long long seq = 0;
     if (loop && (rc = publish_slot(ctx, &rec, &seq))) return rc;
     for (int outer = 0; outer < opts->max_outer; ++outer) {
-        // lidar_tracker.cpp:42-121: match at the current estimate, then Ceres on the fixed correspondences (Huber 0.1, <= 4 iterations,
-        // no degeneracy handling); fewer than 10 correspondences -> the round is skipped
-        // (the LM begin / step run in the linearisation kernel's last workgroup: 2 + max_lm_iterations launches per round)
         TrackArgs m = track_args(opts, 0);
         if (lean && outer == 0) m.init_pose = pose_inout;
         if ((rc = track_match_launch(ctx, 3, m))) return rc;
         TrackArgs b = track_args(opts, 0);
-        b.finish = loop ? 0 : 3; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 10; b.stat_slot = stats ? outer : -1;
+        b.finish = loop ? TAIL_RECORDS : TAIL_LM_BEGIN; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 10; b.stat_slot = stats ? outer : -1;
         if (lean && outer == 0) b.init_pose = pose_inout;
         if (loop) {
             if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
@@ -2454,7 +2436,7 @@ static int track_cloud_impl(mlh_ctx *ctx, double pose_inout[7], const mlh_track_
         if ((rc = track_linearize_launch(ctx, 3, b))) return rc;
         for (int it = 0; it < opts->max_lm_iterations; ++it) {
             TrackArgs s = track_args(opts, 1);
-            s.finish = 4; s.lm_max_it = opts->max_lm_iterations;
+            s.finish = TAIL_LM_STEP; s.lm_max_it = opts->max_lm_iterations;
             if (lean && outer == opts->max_outer - 1 && it == opts->max_lm_iterations - 1) {
                 if ((rc = publish_slot(ctx, &s.publish, &seq))) return rc;
                 s.publish_seq = seq;
@@ -2463,21 +2445,25 @@ static int track_cloud_impl(mlh_ctx *ctx, double pose_inout[7], const mlh_track_
         }
         if (stats && (rc = lm_finish_launch(ctx, outer))) return rc;     // fills the record's LM summary
     }
-    if (lean) {
-        bool given_up = false;         // (only a loop launch gives a barrier up)
-        if ((rc = collect_loop_pose(ctx, seq, rec, pose_inout, &given_up))) return rc;
-        if (given_up) {                // the rounds again, from the pose the caller still holds, a launch per LM iteration
-            note_loop_timeout(ctx, 2, tiles, true);
-            return track_cloud_impl(ctx, pose_inout, opts, stats, false);
-        }
-        return MLH_OK;
-    }
-    return fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer);
+    return lean ? collect_loop_pose(ctx, seq, rec, pose_inout, given_up) : fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer);
 }
 
 int mlh_track_cloud(mlh_ctx *ctx, double pose_inout[7], const mlh_track_opts *opts, mlh_iter_stat *stats)
 {
-    return track_cloud_impl(ctx, pose_inout, opts, stats, true);
+    if (!ctx || !pose_inout || !opts || opts->max_outer <= 0 || opts->max_lm_iterations <= 0) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    const TrackSet &T = ctx->track;
+    int rc = gn_flush_pending(ctx);      // (not solver_begin: the state is allocated only behind the check of what was staged)
+    if (rc) return rc;
+    if (!(T.grid[0].built && T.grid[1].built && T.m[0] > 0 && T.m[1] > 0)) return fail(ctx, MLH_ERR_STATE, "track_set_prev / track_set_cur are required for both kinds");
+    if ((rc = ensure_state(ctx, opts->max_outer))) return rc;
+    // the loop: no statistics, one GPU, a frame's worth of features (Schedule::TRACK_LOOP, ctx.hpp, keeps the launch per LM iteration)
+    const int tiles = tiles_of(T.m[0]) + tiles_of(T.m[1]);
+    const bool loop = !stats && schedule_on(Schedule::TRACK_LOOP) && !distributed(ctx) && loop_tiles_ok(ctx, 2, tiles);
+    bool given_up = false;
+    if ((rc = track_rounds(ctx, pose_inout, opts, stats, loop, &given_up)) || !given_up) return rc;
+    note_loop_given_up(ctx, 2, tiles);
+    return track_rounds(ctx, pose_inout, opts, stats, false, &given_up);
 }
 
 int mlh_good_feature_matching(mlh_ctx *ctx, int kind, const double pose[7], int gf_method, double gf_ratio, uint64_t seed,

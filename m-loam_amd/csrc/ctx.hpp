@@ -83,9 +83,35 @@ struct LmState {
 struct HostPublish {
     double x[7];
     double xb[8][7];
-    long long done;          // SolverState::done at publication (the LM driver polls it)
+    long long done;          // DoneBits at publication (the LM driver polls it)
     unsigned long long seq;
 };
+
+// ---------------------------------------------------------------- the solver's launch modes
+// Named once, here; the hosts (capi.hip, the launchers of match.hip / track.hip) and the kernels use the names, never the numbers. Unscoped, `int` underneath and
+// the values the fields have always had: the parameter blocks' layouts and the kernels' comparisons are what they were.
+enum LaunchTail : int {   // ::finish -- what the last workgroup of a fit / linearise launch does behind its tiles' records
+    TAIL_RECORDS = 0,     // nothing: the launch leaves the records (a consumer sums them)
+    TAIL_GN = 1,          // the Gauss-Newton finish: reduce + 6 x 6 solve + Plus
+    TAIL_REDUCE = 2,      // the local reduce into SolverState::ne only (an RCCL all-reduce and an update kernel follow)
+    TAIL_LM_BEGIN = 3,    // the Levenberg-Marquardt begin (match_launch; linearize_launch on the rows a selection kept; track_linearize_launch)
+    TAIL_LM_STEP = 4      // the Levenberg-Marquardt step (linearize_launch, track_linearize_launch)
+};
+// MatchArgs::lmc -- the consumer-side LM launches (lm_consume_launch): every workgroup sums the records its predecessor left, then runs the LM begin (BEGIN: behind a
+// match launch that left records) or step (STEP) and evaluates at the candidate -- or (LOOP) the whole loop of an outer iteration in this launch (lm_loop_kernel)
+enum LmConsumer : int { LMC_NONE = 0, LMC_BEGIN = 1, LMC_STEP = 2, LMC_LOOP = 3 };
+// ::lm_expect_done -- what an LM begin may assume about the previous outer iteration's loop: there is none, this is the first of a solve (clears lm_overflow and
+// lm_used_max); the host READ its verdict before it enqueued this launch; or it did not (UNREAD): if that loop has not terminated, SolverState::lm_overflow is raised
+// (the launches go on; the host discards the result). Ordered: >= LM_VERDICT_READ is "not the first".
+enum LmExpect : int { LM_FIRST_OF_SOLVE = -1, LM_VERDICT_READ = 0, LM_VERDICT_UNREAD = 1 };
+// KParams::pre_finish (the kernels' PRE template argument carries the same values as an int) -- the prologue of a correspondence launch completes the previous
+// Gauss-Newton ITERATION of its own solve from the records that iteration's fit launch left, or the predecessor SOLVE's last iteration: publishes that solve's pose
+// and chains this frame's start pose from it
+enum PreFinish : int { PRE_NONE = 0, PRE_ITERATION = 1, PRE_SOLVE = 2 };
+enum : int { LM_OVERFLOW_BARRIER_GIVEN_UP = 4 };   // SolverState::lm_overflow: 0 / 1 = a loop outgrew its look-ahead; this value (the one-launch loops store it) = a barrier was given up on
+// HostPublish::done (reduce_dev.hpp: publish_pose): the LM loop has terminated (a Gauss-Newton solve: the pose is final) | the look-ahead of launches overflowed, a
+// loop had not ended where the host assumed it had | a one-launch loop gave a barrier up | the launch had no features
+enum DoneBits : int { DONE_TERMINATED = 1, DONE_OVERFLOWED = 2, DONE_GIVEN_UP = 4, DONE_NO_FEATURES = 8 };
 
 // The context's 256 pinned bytes of small read-backs (mlh_ctx::h_scratch). The kernels that publish the thinned feature counts receive the addresses of
 // thin_counts and thin_seq (voxel.hip); a copy lands in read_back (read_back_int).
@@ -361,9 +387,9 @@ struct TrackArgs {
     const double *init_pose = nullptr;
     float dist_sq_thr = 25.f, nearby_scan = 2.5f;
     double huber_delta = 0.1;
-    int finish = 0;          // track_linearize_launch: 3 / 4 = its last workgroup runs the Levenberg-Marquardt begin / step (solver_dev.hpp)
+    LaunchTail finish = TAIL_RECORDS;        // track_linearize_launch: TAIL_LM_BEGIN / TAIL_LM_STEP (solver_dev.hpp has the bodies)
     int lm_max_it = 4, lm_min_blocks = 10, stat_slot = -1;
-    HostPublish *publish = nullptr;          // finish 3 / 4: this launch hands pose + done flag to the host (pinned memory)
+    HostPublish *publish = nullptr;          // an LM begin / step / loop launch: it hands pose + done bits to the host (pinned memory)
     unsigned long long publish_seq = 0;
 };
 
@@ -429,7 +455,7 @@ struct mlh_ctx {
     mlh::DevBuf tmp_stage;   // the same for mlh_map_set_pair_overlapped, whose copies and pack kernels run on the staging stream beside the main stream's
     mlh::PinnedHalves h_pts;     // landing place of a caller's PAGEABLE scan points (mlh_scan_upload, MLH_SCAN_STAGE_PINNED=1)
     struct SolveSlot {                 // what mlh_scan2map_end needs to know about the solve whose record is SolveLedger::record(seq)
-        int kind = 0;                  // 0: Gauss-Newton (mlh_gn_solve_begin*), 1: scan2map (mlh_scan2map_begin*), 2: scan2map on maps too small to optimise against (the start pose comes back)
+        enum Kind : int { GN /* mlh_gn_solve_begin* */, SCAN2MAP /* mlh_scan2map_begin* */, SCAN2MAP_NO_MAP /* ... on maps too small to optimise against: the start pose comes back */ } kind = GN;
         bool chained = false;
         double start[7] = {0, 0, 0, 0, 0, 0, 1};
         mlh_solver_opts opts;
@@ -768,11 +794,9 @@ struct MatchArgs {
     double huber_delta = 0.1, cov_measurement_trace = 0.0075;
     bool dense = false;  // also write r / J per feature
     int pose_sel = 0;    // 0: SolverState::x, 1: SolverState::cand
-    int finish = 0;      // 1: the fit kernel's last workgroup completes the GN iteration (reduce + solve + Plus); 2: local reduce only;
-                         // 3 / 4: it runs the Levenberg-Marquardt begin (match_launch) / step (linearize_launch)
+    LaunchTail finish = TAIL_RECORDS;
     int lm_max_it = 30, lm_min_blocks = 0;
-    int lm_expect_done = 0;   // finish == 3 (LM begin): -1 = first outer iteration of a solve (clears SolverState::lm_overflow); 1 = a later outer iteration submitted without the
-                              // host having seen the previous LM loop's verdict: if that loop has not terminated, lm_overflow is raised (the launches go on; the host discards)
+    LmExpect lm_expect_done = LM_VERDICT_READ;   // read by the launch that runs an LM begin (TAIL_LM_BEGIN, LMC_BEGIN, LMC_LOOP)
     int stat_slot = -1;
     int n_blocks = 1;    // pose blocks
     int k_neigh[8] = {5, 5, 5, 5, 5, 5, 5, 5};
@@ -795,16 +819,14 @@ struct MatchArgs {
     HostPublish *pre_final_publish = nullptr;
     unsigned long long pre_final_seq = 0;
     const double *chain_prev = nullptr, *chain_cur = nullptr;   // host: the two odometry poses of the chain (7 doubles each)
-    // Levenberg-Marquardt with the step done by the consumer (lm_consume_launch): 1 = the first launch behind a match launch whose fit kernel only left its records
-    // (finish 0) -- sums them, runs the LM begin, evaluates at the first candidate; 2 = a later launch -- sums the records at the candidate, runs the LM step,
-    // evaluates at the next candidate. lmc_j: the launch's number within its loop (1, 2, ...: record buffer (j - 1) & 1 is read, j & 1 written)
-    int lmc = 0, lmc_j = 0;
-    // round 6: the fit of an outer iteration inside the loop launch that follows it (lm_loop_kernel<.., FIT>): match_launch with `no_fit` ends behind the
-    // correspondence kernel, lm_consume_launch (lmc == 3) with `fit_in_loop` begins with the fit -- one launch boundary fewer per outer iteration. Only together,
-    // and only where loop_fit_fusable() says so (tagged records: the fit's record leaves as the loop's own do).
+    LmConsumer lmc = LMC_NONE;
+    int lmc_j = 0;       // lm_consume_launch: the launch's number within its loop (1, 2, ...: record buffer (j - 1) & 1 is read, j & 1 written)
+    // The fit of an outer iteration inside the loop launch that follows it (lm_loop_kernel<.., FIT>; one launch boundary fewer): match_launch with `no_fit` ends behind
+    // the correspondence kernel, lm_consume_launch (LMC_LOOP) with `fit_in_loop` begins with the fit. Only together, and only where loop_fit_fusable() says so (tagged
+    // records: the fit's record leaves as the loop's own do); capi.hip builds the pair in one place (s2m_loop_args).
     bool no_fit = false, fit_in_loop = false;
     const int *m_dev = nullptr;   // device: the two feature counts (surf, corner) when the host has not read them (mlh_downsample_scan2map); FeatSet::m then holds upper bounds
-    HostPublish *publish = nullptr;          // pinned host record the finish writes the pose(s) to (finish == 1 only)
+    HostPublish *publish = nullptr;          // pinned host record the launch writes the pose(s) to: honoured by TAIL_GN, TAIL_LM_STEP and every consumer-side launch
     unsigned long long publish_seq = 0;
 };
 int match_launch(mlh_ctx *ctx, const MatchArgs &a);

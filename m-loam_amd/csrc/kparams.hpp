@@ -57,17 +57,16 @@ struct KParams {
     HostPublish *publish;    // the finish of the last iteration hands the result to the host through pinned memory
     unsigned long long publish_seq;
     int knn_lanes;           // lanes per query of the correspondence kernel: 8 or 16 for every kind of the launch, 0 = per kind (KindP::lanes)
-    int finish;              // 0: none, 1: GN (reduce + solve + Plus), 2: reduce into SolverState::ne only (multi-GPU),
-                             // 3: Levenberg-Marquardt begin (fit kernel), 4: Levenberg-Marquardt step (linearize kernel)
+    LaunchTail finish;
     int lm_max_it, lm_min_blocks;
-    int lm_expect_done;      // MatchArgs::lm_expect_done
+    LmExpect lm_expect_done;
     unsigned *ticket;
     IterStatDev *stat;       // n_blocks consecutive records, or null
     // sharded over several ranks with the mailbox communicator: the finishing workgroup exchanges each block's summed record with the peers (one hop, inside
     // this launch) before it solves -- a sharded Gauss-Newton iteration is the same two launches as an unsharded one. n_ranks <= 1: nothing is exchanged
     P2pDev p2p;
     // Gauss-Newton with the finish done by the consumer (MatchArgs::gn_iter): the correspondence kernel of iteration i >= 1 completes iteration i - 1 first
-    int pre_finish;          // 1: sum the pre_tiles records the previous fit launch left in `partials`, solve, Plus -> this iteration's pose
+    PreFinish pre_finish;    // its records: the pre_tiles records the previous fit launch left in `partials`
     int pre_tiles;
     int pre_from_init;       // the previous iteration's pose is init_pose (kernel arguments); otherwise *x_prev
     int pre_from_state;      // ... or the state's own poses (x for block 0, xb[b] otherwise): iteration 1 of a solve over pose blocks
@@ -76,7 +75,7 @@ struct KParams {
     double *x_next;          // the workgroup that serves tile 0 stores the new pose here (the fit kernel of the same iteration reads it as pose0)
     const double *pose0;     // block 0's pose of this launch when it is neither init_pose nor the state's x / cand (iterations >= 1 of a deferred-finish solve)
     int warm;                // the neighbour records hold the previous iteration's neighbours of the same features in the same map
-    // pre_finish == 2 (MatchArgs::pre_final): the records are the PREVIOUS solve's last iteration; its pose is published from here, then this frame's start pose chained from it
+    // PRE_SOLVE (MatchArgs::pre_final): the records are the PREVIOUS solve's last iteration; its pose is published from here, then this frame's start pose chained from it
     HostPublish *pre_publish;
     unsigned long long pre_publish_seq;
     double pre_thre;

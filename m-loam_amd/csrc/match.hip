@@ -668,7 +668,7 @@ __device__ __forceinline__ void load_tile_inputs(const KParams &P, const KindP &
 template <typename X>
 __device__ __forceinline__ void lmc_publish(const KParams &P, const X &x, int done, int overflow, double used_max, int iteration)
 {
-    publish_pose(P.publish, P.publish_seq, x, done | (overflow ? 2 : 0), fmax(used_max, double(iteration)));
+    publish_pose(P.publish, P.publish_seq, x, done | (overflow ? DONE_OVERFLOWED : 0), fmax(used_max, double(iteration)));
 }
 
 // the records of pose block b: its surf tiles, then its corner tiles (one block: every record, whatever the tile size)
@@ -715,12 +715,12 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
                 done = 1;
                 if (threadIdx.x == 0) P.state->done = 1;
             }
-            else if (P.finish == 3) {
+            else if (P.finish == TAIL_LM_BEGIN) {
                 // split submission: this outer iteration was enqueued without anybody having seen the previous LM loop end. If it has not, the frame's result is
                 // not the reference's (<= max_num_iterations per outer iteration): flagged, published with the pose, and the host re-solves or reports
                 if (threadIdx.x == 0 && P.lm_expect_done) {
-                    P.state->lm_overflow = (P.lm_expect_done > 0 && (P.state->lm_overflow || !P.state->done)) ? 1 : 0;
-                    P.state->lm_used_max = P.lm_expect_done > 0 ? fmax(P.state->lm_used_max, double(P.state->iteration)) : 0.0;      // the loop that just ended
+                    P.state->lm_overflow = (P.lm_expect_done > LM_VERDICT_READ && (P.state->lm_overflow || !P.state->done)) ? 1 : 0;
+                    P.state->lm_used_max = P.lm_expect_done > LM_VERDICT_READ ? fmax(P.state->lm_used_max, double(P.state->iteration)) : 0.0;      // the loop that just ended
                 }
                 lm_begin_body_wave(f_ne, f_cnt2, f_scratch, P.state, P.thre_b[0], P.lm_max_it, P.stat, P.lm_min_blocks, xo, done);
             }
@@ -734,7 +734,7 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
         MLH_STAGE(4095, 2);
         return;
     }
-    if (P.finish == 2) {
+    if (P.finish == TAIL_REDUCE) {
         // multi-GPU: only the local reduction happens here; the all-reduce and the (redundant, identical) solve follow
         if (P.n_blocks == 1) {
             SumArgs sa;
@@ -955,7 +955,7 @@ __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
     MLH_STAGE(gtile, 2);
     reduce_rows(valid, L, P.huber_delta, (P.flags & MLH_FLAG_NO_LOSS) != 0, kind, s_red, P.partials + size_t(gtile) * NE_STRIDE, mult);
     MLH_STAGE(gtile, 3);
-    if constexpr (LM) { if (P.finish == 3 || P.finish == 4) fused_gn_finish<true>(P, total); }   // 3: the LM begin on rows a selection kept (scan2map with good-feature selection)
+    if constexpr (LM) { if (P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP) fused_gn_finish<true>(P, total); }   // (the begin: on rows a selection kept -- scan2map with good-feature selection)
     MLH_STAGE(gtile, 4);
 }
 
@@ -968,7 +968,7 @@ __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
 // runs under the step. The state lives in two LmState records: launch g reads [(g - 1) & 1], its tile-0 workgroup writes [g & 1] (and mirrors the accepted pose
 // into SolverState::x, which only launches behind this one read); the records alternate between two buffers the same way. A launch that finds the loop terminated
 // copies the state forward and leaves (the host enqueues a look-ahead of launches without reading the verdict in between, as before).
-// FIRST: the launch behind a match launch whose fit kernel ran with finish 0 -- the records are at the state's pose (or init_pose), the LM loop begins here.
+// FIRST: the launch behind a match launch whose fit kernel left records (TAIL_RECORDS) -- the records are at the state's pose (or init_pose), the LM loop begins here.
 template <bool FIRST>
 __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
 {
@@ -1018,8 +1018,8 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
             for (int i = 0; i < 7; ++i) x[i] = P.use_init ? P.init_pose[i] : P.state->x[i];
             // (split submission: this outer iteration was enqueued without anybody having seen the previous LM loop end -- fused_gn_finish's bookkeeping)
             if (P.lm_expect_done) {
-                overflow = (P.lm_expect_done > 0 && (Si->lm_overflow || !Si->done)) ? 1 : 0;
-                used_max = P.lm_expect_done > 0 ? fmax(Si->lm_used_max, double(Si->iteration)) : 0.0;
+                overflow = (P.lm_expect_done > LM_VERDICT_READ && (Si->lm_overflow || !Si->done)) ? 1 : 0;
+                used_max = P.lm_expect_done > LM_VERDICT_READ ? fmax(Si->lm_used_max, double(Si->iteration)) : 0.0;
             } else { overflow = Si->lm_overflow; used_max = Si->lm_used_max; }
             lm_begin_wave_pp(f_ne, f_scratch, x, So, writer, P.thre_b[0], P.lm_max_it, P.lm_min_blocks, R, cand);
             if (writer && P.use_init && lane < 7) P.state->x[lane] = pick7(x, lane);       // the state's pose is born here
@@ -1057,9 +1057,9 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
 // Barrier: P.ticket[1] counts arrivals (monotonic over the launch: iteration `it` waits for total * (it + 1)), P.ticket[2] counts workgroups that have left; the
 // last one to leave zeroes both for the next launch. Residency is the HOST's business (capi.hip: loop_tiles_ok -- the occupancy query x the compute units the
 // solver's stream may use, asked at mlh_create); should a barrier nevertheless not complete within P.loop_timeout_ticks of the 100 MHz wall clock (a workgroup that
-// never became resident beside another context's kernels, a fault), the loop is given up: P.ticket[3] tells every workgroup still to come or still polling, bit 2 of
-// the published `done` word tells the host, which solves the frame again through the launch-per-iteration form (lm_consume_kernel: no residency requirement) --
-// a slow frame, not a lost one. The later loop launches of such a frame (lm_overflow == 4 in the state) leave at once.
+// never became resident beside another context's kernels, a fault), the loop is given up: P.ticket[3] tells every workgroup still to come or still polling, DONE_GIVEN_UP
+// in the published `done` word tells the host, which solves the frame again through the launch-per-iteration form (lm_consume_kernel: no residency requirement) --
+// a slow frame, not a lost one. The later loop launches of such a frame (lm_overflow == LM_OVERFLOW_BARRIER_GIVEN_UP in the state) leave at once.
 // The records cross the barrier as agent-scope monotonic stores / loads (write-through, read past the L2 of the reader's XCD): no L2 write-back and invalidate
 // around the barrier. A waiting thread sleeps one s_sleep unit between polls (polling without it was slower, profiles/r05_knockout_experiments.txt).
 // The first wavefront keeps the LM state's registers from step to step (lm_step_wave_keep) and stores them to the LDS state once, behind the loop: scan2map
@@ -1089,7 +1089,7 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
             if (blockIdx.x == 0 && threadIdx.x == 0 && P.publish) {
                 double x[7];
                 for (int i = 0; i < 7; ++i) x[i] = P.use_init ? P.init_pose[i] : P.state->x[i];
-                publish_pose(P.publish, P.publish_seq, x, 1 | 8, 0.0);
+                publish_pose(P.publish, P.publish_seq, x, DONE_TERMINATED | DONE_NO_FEATURES, 0.0);
             }
             return;
         }
@@ -1136,7 +1136,7 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
     const size_t set = size_t(NE_STRIDE) * size_t(total);
     // given up already -- by a workgroup of this launch that waited in vain, or by an earlier loop of this frame: nothing to do but leave
     if (threadIdx.x == 0)
-        s_timeout = (loop_barrier_given_up(P.ticket) || (P.lm_expect_done >= 0 && P.state->lm_overflow == 4)) ? 2 : 0;
+        s_timeout = (loop_barrier_given_up(P.ticket) || (P.lm_expect_done >= LM_VERDICT_READ && P.state->lm_overflow == LM_OVERFLOW_BARRIER_GIVEN_UP)) ? 2 : 0;
     if constexpr (FIT) {
         __syncthreads();                               // s_timeout
         if (s_timeout == 0) {                          // (uniform)
@@ -1229,23 +1229,23 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
     if (writer && threadIdx.x < 64 && skipped) {
         // the loop never began here: the pose in the state is what the last loop that ran left; the failure travels on to the launch that publishes
         if (threadIdx.x == 0) {
-            P.state->lm_overflow = 4;
-            if (P.publish) publish_pose(P.publish, P.publish_seq, P.state->x, 4, P.state->lm_used_max);
+            P.state->lm_overflow = LM_OVERFLOW_BARRIER_GIVEN_UP;
+            if (P.publish) publish_pose(P.publish, P.publish_seq, P.state->x, DONE_GIVEN_UP, P.state->lm_used_max);
         }
     }
     else if (writer && threadIdx.x < 64) {
         const int lane = threadIdx.x;
         if (lane < 7) P.state->x[lane] = s_lm.x[lane];          // read by the launches BEHIND this one only (the other workgroups took their start pose long ago)
         if (lane == 0) {
-            const double used = P.lm_expect_done < 0 ? double(s_lm.iteration) : fmax(P.state->lm_used_max, double(s_lm.iteration));
+            const double used = P.lm_expect_done < LM_VERDICT_READ ? double(s_lm.iteration) : fmax(P.state->lm_used_max, double(s_lm.iteration));
             // (a barrier given up on in an EARLIER outer iteration of the frame must not be lost: lm_overflow -- unused otherwise by this schedule -- carries it to the
             // launch that publishes)
-            const int failed = (s_timeout ? 1 : 0) | ((P.lm_expect_done >= 0 && P.state->lm_overflow == 4) ? 1 : 0);
+            const int failed = (s_timeout ? 1 : 0) | ((P.lm_expect_done >= LM_VERDICT_READ && P.state->lm_overflow == LM_OVERFLOW_BARRIER_GIVEN_UP) ? 1 : 0);
             P.state->lm_used_max = used;
-            P.state->lm_overflow = failed ? 4 : 0;
+            P.state->lm_overflow = failed ? LM_OVERFLOW_BARRIER_GIVEN_UP : 0;
             P.state->done = s_lm.done;
             P.state->iteration = s_lm.iteration;
-            if (P.publish) publish_pose(P.publish, P.publish_seq, s_lm.x, (s_lm.done ? 1 : 0) | (failed ? 4 : 0), used);
+            if (P.publish) publish_pose(P.publish, P.publish_seq, s_lm.x, (s_lm.done ? DONE_TERMINATED : 0) | (failed ? DONE_GIVEN_UP : 0), used);
         }
     }
     if (threadIdx.x == 0) loop_barrier_leave(P.ticket, total);      // the last workgroup to leave re-arms the barrier for the next launch
@@ -1372,9 +1372,8 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
     for (int i = 0; i < 4; ++i) { P.lo[i] = ctx->lo_plane[i]; P.hi[i] = ctx->hi_plane[i]; }
     P.finish = a.finish;
     P.lm_max_it = a.lm_max_it; P.lm_min_blocks = a.lm_min_blocks; P.lm_expect_done = a.lm_expect_done;
-    // the mailbox communicator rides in the finishing workgroup of a Gauss-Newton launch (finish == 1) and of an LM begin / step launch (3 / 4); other launches
-    // exchange nothing
-    if ((a.finish == 1 || a.finish == 3 || a.finish == 4) && ctx->p2p.active) p2p_fill(ctx, P.p2p);
+    // the mailbox communicator rides in the finishing workgroup of a Gauss-Newton launch and of an LM begin / step launch; other launches exchange nothing
+    if ((a.finish == TAIL_GN || a.finish == TAIL_LM_BEGIN || a.finish == TAIL_LM_STEP) && ctx->p2p.active) p2p_fill(ctx, P.p2p);
     else { P2pDev none{}; none.n_ranks = 1; P.p2p = none; }
     P.use_init = a.init_pose ? 1 : 0;
     for (int i = 0; i < 7; ++i) P.init_pose[i] = a.init_pose ? a.init_pose[i] : 0.0;
@@ -1383,7 +1382,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         // iteration i >= 1 of a deferred-finish solve over pose blocks: every block's pose of iteration i in SolverState::xib[i & 1][b]; iteration 1 updates the poses
         // the state holds (x, xb[b])
         SolverState *S = ctx->state.as<SolverState>();
-        P.pre_finish = 1;
+        P.pre_finish = PRE_ITERATION;
         P.pre_tiles = tiles_b_total;
         P.pre_from_init = 0;
         P.pre_from_state = a.gn_iter == 1 ? 1 : 0;
@@ -1396,7 +1395,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         // iteration 1 finds pose 0 where iteration 0 found it -- the kernel arguments, the state's x (a chained solve behind a chain launch), or iteration 0's slot
         // (a chained solve whose first launch computed the start pose itself, MatchArgs::pre_final)
         SolverState *S = ctx->state.as<SolverState>();
-        P.pre_finish = 1;
+        P.pre_finish = PRE_ITERATION;
         P.pre_tiles = tiles_b_total;
         P.pre_from_init = (a.gn_iter == 1 && a.init_pose) ? 1 : 0;
         P.x_prev = (a.gn_iter == 1 && !a.pre_final) ? S->x : S->xi[a.gn_slot_base + ((a.gn_iter - 1) & 1)];
@@ -1407,7 +1406,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         // iteration 0 of a chained solve that completes its predecessor first (knn_features_kernel<.., PRE = 2>): the predecessor's records, thresholds, last pose slot
         // and host record; this frame's start pose goes to xi[base] (the fit kernel of this iteration and iteration 1's prologue read it there)
         SolverState *S = ctx->state.as<SolverState>();
-        P.pre_finish = 2;
+        P.pre_finish = PRE_SOLVE;
         P.pre_tiles = a.pre_final_tiles;
         P.pre_from_init = 0;
         P.x_prev = S->xi[a.pre_final_slot];
@@ -1426,7 +1425,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         P.pose_bn = P.pose0 ? P.pose0 : &S->xb[0][0];
     }
     P.m_dev = a.m_dev;
-    P.publish = (a.finish == 1 || a.finish == 4 || a.lmc) ? a.publish : nullptr;
+    P.publish = (a.finish == TAIL_GN || a.finish == TAIL_LM_STEP || a.lmc) ? a.publish : nullptr;
     if (a.lmc) {
         if (!ctx->lm_pp.p) {
             if ((e = ctx->lm_pp.ensure(2 * sizeof(LmState))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc lm state", e);
@@ -1438,7 +1437,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         const size_t set = size_t(NE_STRIDE) * size_t(tiles_b_total);
         P.partials_in = ctx->partials.as<double>() + set * size_t((a.lmc_j - 1) & 1);
         P.partials = ctx->partials.as<double>() + set * size_t(a.lmc_j & 1);
-        if (a.lmc == 3) { P.partials_in = ctx->partials.as<double>(); P.partials = ctx->partials.as<double>(); }     // (the loop kernel alternates by itself)
+        if (a.lmc == LMC_LOOP) { P.partials_in = ctx->partials.as<double>(); P.partials = ctx->partials.as<double>(); }     // (the loop kernel alternates by itself)
     }
     P.publish_seq = a.publish_seq;
     P.ticket = ctx->ticket.as<unsigned>();
@@ -1465,7 +1464,7 @@ int gn_flush_pending(mlh_ctx *ctx)
     SolverState *S = ctx->state.as<SolverState>();
     P.partials = ctx->partials.as<double>();
     P.state = S;
-    P.pre_finish = 2;
+    P.pre_finish = PRE_SOLVE;
     P.pre_tiles = ctx->gn_pending.tiles;
     P.x_prev = S->xi[ctx->gn_pending.slot];
     P.pre_publish = static_cast<HostPublish *>(ctx->gn_pending.rec);
@@ -1491,7 +1490,7 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
     for (int b = 0; b < P.n_blocks; ++b) k10 = k10 || P.kb[b] == 10;
     if (P.m_dev) {
         // the feature counts are on the device only (mlh_downsample_scan2map): per-kind lanes, both kinds, one block, K = 5, records only
-        if (mb || k10 || P.finish != 0 || P.pre_finish || (a.kind_mask & 3) != 3) return fail(ctx, MLH_ERR_UNSUPPORTED, "device-side feature counts: one block, N_NEIGH 5, both kinds, records only");
+        if (mb || k10 || P.finish != TAIL_RECORDS || P.pre_finish || (a.kind_mask & 3) != 3) return fail(ctx, MLH_ERR_UNSUPPORTED, "device-side feature counts: one block, N_NEIGH 5, both kinds, records only");
         if (P.warm) launch_timed(ctx, MLH_K_KNN, knn_features_kernel<0, false, false, 0, true, true>, grid_a, P);
         else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<0, false, false, 0, false, true>, grid_a, P);
         if (!a.no_fit) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, false, false, true>, grid_b, P);
@@ -1506,7 +1505,7 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
             else { if (k10) launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, false, true>, grid_a, P); else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, false, false>, grid_a, P); } \
         } while (0)
 #define MLH_KNN_LAUNCH_GN(G_) do { \
-            if (P.pre_finish == 2) launch_timed(ctx, MLH_K_KNN_FIRST, knn_features_kernel<G_, false, false, 2, false>, grid_a, P); \
+            if (P.pre_finish == PRE_SOLVE) launch_timed(ctx, MLH_K_KNN_FIRST, knn_features_kernel<G_, false, false, 2, false>, grid_a, P); \
             else if (P.pre_finish && P.warm) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, false, false, 1, true>, grid_a, P); \
             else if (P.pre_finish) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, false, false, 1, false>, grid_a, P); \
             else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, false, false, 0, true>, grid_a, P); \
@@ -1517,7 +1516,7 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
         } while (0)
         if ((P.pre_finish || P.warm) && (mb || k10 || a.gn_blocks)) {     // (a.gn_blocks: a blocks solve over ONE block keeps the blocks' pose slots)
             // a solve over pose blocks (or with N_NEIGH = 10): the finish in the consumer and the bounded search come together or not at all
-            if (!(P.pre_finish == 1 && P.warm)) return fail(ctx, MLH_ERR_UNSUPPORTED, "pose blocks: the deferred finish and the bounded search are one schedule");
+            if (!(P.pre_finish == PRE_ITERATION && P.warm)) return fail(ctx, MLH_ERR_UNSUPPORTED, "pose blocks: the deferred finish and the bounded search are one schedule");
             if (P.knn_lanes == 0) MLH_KNN_LAUNCH_GN_MB(0);
             else if (P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_MB(16);
             else MLH_KNN_LAUNCH_GN_MB(8);
@@ -1536,17 +1535,17 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
     }
     if (a.no_fit) {
         // the fit rides in the loop launch behind this one (lm_consume_launch, fit_in_loop): single block, N_NEIGH 5, both kinds, records only
-        if (k10 || P.n_blocks != 1 || P.finish != 0 || (a.kind_mask & 3) != 3 || a.dense) return fail(ctx, MLH_ERR_UNSUPPORTED, "match_launch without its fit: single block, N_NEIGH 5, both kinds, records only");
+        if (k10 || P.n_blocks != 1 || P.finish != TAIL_RECORDS || (a.kind_mask & 3) != 3 || a.dense) return fail(ctx, MLH_ERR_UNSUPPORTED, "match_launch without its fit: single block, N_NEIGH 5, both kinds, records only");
         MLH_HIP(ctx, hipGetLastError());
         for (int k = 0; k < 2; ++k) ctx->feat[k].matched = false;
         return MLH_OK;
     }
-    if (P.finish == 3) {
+    if (P.finish == TAIL_LM_BEGIN) {
         if (k10 || P.n_blocks != 1) return fail(ctx, MLH_ERR_UNSUPPORTED, "the fused Levenberg-Marquardt begin is single-block, N_NEIGH = 5");
         launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, true>, grid_b, P);
-    } else if (k10 && P.finish == 0) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<10, false, false>, grid_b, P);
+    } else if (k10 && P.finish == TAIL_RECORDS) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<10, false, false>, grid_b, P);
     else if (k10) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<10, false>, grid_b, P);
-    else if (P.finish == 0) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, false, false>, grid_b, P);
+    else if (P.finish == TAIL_RECORDS) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, false, false>, grid_b, P);
     else launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
     for (int k = 0; k < 2; ++k) if (a.kind_mask & (1 << k)) ctx->feat[k].matched = true;
@@ -1561,7 +1560,7 @@ int linearize_launch(mlh_ctx *ctx, const MatchArgs &a)
     int rc = fill_params(ctx, a, P);
     if (rc) return rc;
     const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
-    if (P.finish == 3 || P.finish == 4) launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<true>, grid_b, P);
+    if (P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP) launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<true>, grid_b, P);
     else launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
@@ -1571,19 +1570,19 @@ int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a)
 {
     for (int k = 0; k < 2; ++k)
         if ((a.kind_mask & (1 << k)) && !ctx->feat[k].matched && !a.fit_in_loop) return fail(ctx, MLH_ERR_STATE, "the Levenberg-Marquardt launches need a previous match of this kind");
-    if (a.lmc < 1 || a.lmc > 3 || a.lmc_j < 1 || a.n_blocks > 1 || a.dense) return fail(ctx, MLH_ERR_INVALID, "lm_consume_launch: single block, no dense rows");
-    if (a.fit_in_loop && (a.lmc != 3 || (a.kind_mask & 3) != 3 || !loop_fit_fusable(a))) return fail(ctx, MLH_ERR_INVALID, "the fit rides in the one-launch loop with tagged records only");
+    if (a.lmc == LMC_NONE || a.lmc_j < 1 || a.n_blocks > 1 || a.dense) return fail(ctx, MLH_ERR_INVALID, "lm_consume_launch: single block, no dense rows");
+    if (a.fit_in_loop && (a.lmc != LMC_LOOP || (a.kind_mask & 3) != 3 || !loop_fit_fusable(a))) return fail(ctx, MLH_ERR_INVALID, "the fit rides in the one-launch loop with tagged records only");
     KParams P;
     int rc = fill_params(ctx, a, P);
     if (rc) return rc;
     if (P.p2p.n_ranks > 1) return fail(ctx, MLH_ERR_UNSUPPORTED, "the consumer-side Levenberg-Marquardt schedule is single-GPU");
     const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
-    if (a.lmc == 3) {
+    if (a.lmc == LMC_LOOP) {
         { const char *e = std::getenv("MLH_DEBUG_LOOP_STALL"); P.debug_stall = (e && std::atoi(e) != 0) ? 1 : 0; }
         // every tile's workgroup has to be resident for the barrier: the host's gate (capi.hip: loop_tiles_ok) is what the device admits, asked at mlh_create
         if (P.k[0].tiles_b + P.k[1].tiles_b > ctx->caps.loop_max_tiles[P.m_dev ? 1 : 0]) return fail(ctx, MLH_ERR_INVALID, "lm_loop_kernel: more tiles than can be resident at once on this device");
         P.loop_timeout_ticks = ctx->caps.loop_timeout_ticks;
-        if (a.lm_expect_done < 0) ++ctx->caps.loop_launches;      // (the first loop of a frame)
+        if (a.lm_expect_done == LM_FIRST_OF_SOLVE) ++ctx->caps.loop_launches;      // (the first loop of a frame)
         // the iterations' records as tagged words summed by polling (MLH_LOOP_TAGGED=0: plain records behind a grid barrier, as through round 5)
         { hipError_t e = loop_tagged_arm(ctx, size_t(P.k[0].tiles_b + P.k[1].tiles_b), a.lm_max_it, &P.loop_tagged, &P.loop_tag_base); if (e != hipSuccess) return fail(ctx, MLH_ERR_HIP, "tagged records", e); }
         if (a.fit_in_loop) {
@@ -1595,7 +1594,7 @@ int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a)
         else if (P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true>, grid_b, P);
         else launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false>, grid_b, P);
     }
-    else if (a.lmc == 1) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<true>, grid_b, P);
+    else if (a.lmc == LMC_BEGIN) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<true>, grid_b, P);
     else launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;

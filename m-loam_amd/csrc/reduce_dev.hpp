@@ -82,8 +82,7 @@ __device__ __forceinline__ void reduce_acc32(double (&acc)[32], int kind, double
 }
 
 // ---- the HostPublish record (ctx.hpp), written by ONE thread of the launch the host waits for: the pose, the `done` word, then `seq` -- last, as a system-scope
-// release store, so a host that finds the sequence number it waits for finds this launch's record behind it. Bits of `done`: 1 the loop has terminated, 2 the
-// look-ahead of launches overflowed (a loop had not ended where the host assumed it had), 4 a grid barrier was given up, 8 the launch had no features.
+// release store, so a host that finds the sequence number it waits for finds this launch's record behind it. `done`: DoneBits (ctx.hpp).
 __device__ __forceinline__ void publish_seq(HostPublish *pub, unsigned long long seq)
 {
     __hip_atomic_store(&pub->seq, seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);

@@ -57,7 +57,8 @@ struct TrackParamsDev {
     SolverState *state;
     double *partials;
     int pose_sel;            // 0: state->x, 1: state->cand
-    int finish, lm_max_it, lm_min_blocks;   // fused Levenberg-Marquardt begin (3) / step (4) in the linearisation kernel's last workgroup
+    LaunchTail finish;                      // TAIL_LM_BEGIN / TAIL_LM_STEP: in the linearisation kernel's last workgroup
+    int lm_max_it, lm_min_blocks;
     unsigned *ticket;
     IterStatDev *stat;
     HostPublish *publish;    // this launch publishes pose + done flag to pinned host memory
@@ -426,7 +427,7 @@ __global__ __launch_bounds__(TPB) void track_linearize_kernel(TrackParamsDev P)
     if (threadIdx.x < 64) {          // one wavefront runs the LM begin / step (solver_dev.hpp: rows of the 6 x 6 objects on lanes)
         double xo[7];
         int done = 0;
-        if (P.finish == 3) lm_begin_body_wave(f_ne, f_cnt2, f_scratch, P.state, -1.0, P.lm_max_it, P.stat, P.lm_min_blocks, xo, done);
+        if (P.finish == TAIL_LM_BEGIN) lm_begin_body_wave(f_ne, f_cnt2, f_scratch, P.state, -1.0, P.lm_max_it, P.stat, P.lm_min_blocks, xo, done);
         else lm_step_body_wave(f_ne, P.state, P.lm_max_it, xo, done);
         if (threadIdx.x == 0) {
             *P.ticket = 0u;
@@ -460,9 +461,9 @@ __global__ __launch_bounds__(TPB) void track_lm_loop_kernel(TrackParamsDev P)
     if (f < K.m) { c = K.corr[f]; fp = K.cur[f]; }
     const bool valid = f < K.m && c.valid != 0;
     const size_t set = size_t(NE_STRIDE) * size_t(total);
-    // given up already -- by a workgroup of this launch that waited in vain, or by an earlier round of this call (lm_overflow == 4; the first round, whose pose
+    // given up already -- by a workgroup of this launch that waited in vain, or by an earlier round of this call (lm_overflow == LM_OVERFLOW_BARRIER_GIVEN_UP; the first round, whose pose
     // comes with the kernel arguments, clears it): nothing to do but leave; the failure travels on to the round that publishes
-    if (threadIdx.x == 0) s_timeout = (loop_barrier_given_up(P.ticket) || (!P.use_init && P.state->lm_overflow == 4)) ? 2 : 0;
+    if (threadIdx.x == 0) s_timeout = (loop_barrier_given_up(P.ticket) || (!P.use_init && P.state->lm_overflow == LM_OVERFLOW_BARRIER_GIVEN_UP)) ? 2 : 0;
     // the round's pose: the records of the begin are taken there
     if (threadIdx.x < 7) s_cand[threadIdx.x] = P.use_init ? P.init_pose[threadIdx.x] : P.state->x[threadIdx.x];
     __syncthreads();
@@ -509,11 +510,11 @@ __global__ __launch_bounds__(TPB) void track_lm_loop_kernel(TrackParamsDev P)
         if (lane == 0) {
             P.state->done = have ? s_lm.done : 1;
             P.state->iteration = have ? s_lm.iteration : 0;
-            P.state->lm_overflow = s_timeout ? 4 : 0;              // (a later round of the call finds it and leaves; the round that publishes reports it)
+            P.state->lm_overflow = s_timeout ? LM_OVERFLOW_BARRIER_GIVEN_UP : 0;              // (a later round of the call finds it and leaves; the round that publishes reports it)
             if (P.publish) {
                 double x[7];
                 for (int i = 0; i < 7; ++i) x[i] = have ? s_lm.x[i] : (P.use_init ? P.init_pose[i] : P.state->x[i]);
-                publish_pose<false>(P.publish, P.publish_seq, x, 1 | (s_timeout ? 4 : 0));
+                publish_pose<false>(P.publish, P.publish_seq, x, DONE_TERMINATED | (s_timeout ? DONE_GIVEN_UP : 0));
             }
         }
     }

@@ -81,6 +81,32 @@ def test_retired_ab_switches_stay_out_of_the_kernels():
             assert not pat.search(txt), (os.path.join(dp, f), pat.search(txt).group(0))
 
 
+def test_solver_launch_modes_are_named_not_numbered():
+    """the launch modes of the solvers are the enums of ctx.hpp (LaunchTail, LmConsumer, LmExpect, PreFinish, LM_OVERFLOW_BARRIER_GIVEN_UP, DoneBits): under
+    m-loam_amd/csrc no line compares or assigns finish, lmc, lm_expect_done, pre_finish or lm_overflow against a bare integer literal, in either order, and none
+    masks a publication's `done` word with one. (The enumerators' own definitions do not name the fields, so nothing needs exempting.)"""
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    field = r"\b(?:finish|lmc|lm_expect_done|pre_finish|lm_overflow)\b"
+    op = r"(?:==|!=|<=|>=|<|>|=)"
+    num = r"[-+]?\d+\b"
+    pats = [re.compile(field + r"\s*" + op + r"\s*" + num),                 # P.finish == 3, a.lmc = 2, lm_expect_done >= 0
+            re.compile(r"(?<![\w.])" + num + r"\s*" + op + r"\s*[\w.>-]*" + field),   # 3 == P.finish
+            re.compile(r"\bdone\s*&\s*~?\s*" + num),                        # hp.done & 6
+            re.compile(r"(?<![\w.])" + num + r"\s*&\s*[\w.>-]*\bdone\b")]   # 4 & hp.done
+    # the patterns do find what they are for
+    for bad in ("if (P.finish == 3) x;", "a.lmc = 2;", "P.lm_expect_done >= 0", "S->lm_overflow == 4", "if (0 != P.pre_finish)", "(hp.done & 6)", "4 & hp.done"):
+        assert any(p.search(bad) for p in pats), bad
+    for good in ("a.finish = TAIL_GN;", "int lmc_j = 0;", "hp.done & DONE_GIVEN_UP", "S->done = 1;", "P.lm_expect_done > LM_VERDICT_READ", "finish_count = 3;"):
+        assert not any(p.search(good) for p in pats), good
+    found = []
+    for dp, _, files in os.walk(os.path.join(root, "m-loam_amd", "csrc")):
+        for f in files:
+            for n, line in enumerate(open(os.path.join(dp, f), errors="ignore"), 1):
+                if any(p.search(line) for p in pats):
+                    found.append((f, n, line.strip()[:120]))
+    assert not found, found
+
+
 def test_compound_pose_with_cov_host(mla, orc):
     """mlh_compound_pose_with_cov is host arithmetic (no GPU needed): it must agree with the oracle's restatement of
     compoundPoseWithCov (associate_uct.hpp:90-147), which test_oracle_numerics pins against Monte-Carlo sampling."""
