@@ -47,7 +47,10 @@ enum {
 enum {
     MLH_FLAG_CHECK_FOV = 1u << 0,   /* CHECK_FOV argument of match*FromMap (feature_extract.hpp:696-715) */
     MLH_FLAG_WITH_UA = 1u << 1,     /* with_ua_flag: weight from the feature's own covariance (lidar_mapper_keyframe.cpp:541-544) */
-    MLH_FLAG_NO_LOSS = 1u << 2      /* reduce un-corrected rows (ActiveFeatureSelection's H, lidar_mapper.h:162-164) */
+    MLH_FLAG_NO_LOSS = 1u << 2,     /* reduce un-corrected rows (ActiveFeatureSelection's H, lidar_mapper.h:162-164) */
+    MLH_FLAG_POSE_COV = 1u << 3     /* mlh_scan2map, mlh_scan2map_begin*, mlh_downsample_scan2map: the solve also delivers evalHessian at the pose it returns and its
+                                     * inverse (lidar_mapper_keyframe.cpp:600-606), read with mlh_scan2map_cov. Ignored by mlh_gn_solve*, mlh_match_linearize and
+                                     * every other call that takes solver options: they run no Levenberg-Marquardt loop whose state holds that matrix */
 };
 
 /* ---------------------------------------------------------------- context */
@@ -499,7 +502,7 @@ typedef struct mlh_solver_opts {
     double huber_delta;              /* ceres::HuberLoss(0.1), lidar_mapper_keyframe.cpp:443 */
     double map_eig_thre;             /* MAP_EIG_THRE, evalDegenracy, lidar_mapper_keyframe.cpp:1178-1189 */
     double cov_measurement_trace;    /* trace(COV_MEASUREMENT) used when with_ua is off (cpp:543-544) */
-    uint32_t flags;                  /* MLH_FLAG_WITH_UA | MLH_FLAG_CHECK_FOV. CHECK_FOV applies to mlh_gn_solve* (estimator.cpp:1142, 1149 pass it); the mlh_scan2map*
+    uint32_t flags;                  /* MLH_FLAG_WITH_UA | MLH_FLAG_CHECK_FOV | MLH_FLAG_POSE_COV (the mlh_scan2map* entry points only: mlh_scan2map_cov). CHECK_FOV applies to mlh_gn_solve* (estimator.cpp:1142, 1149 pass it); the mlh_scan2map*
                                       * entry points ignore it, as scan2MapOptimization does: its matching goes through goodFeatureMatching, which hard-codes
                                       * n_neigh = 5 and CHECK_FOV = false (lidar_mapper.h:256-283) */
     int max_outer;                   /* max_iter = 2, cpp:439 */
@@ -578,10 +581,11 @@ int mlh_gn_solve_blocks(mlh_ctx *ctx, double *poses_inout, int n_iters, const ml
 /* scan2MapOptimization(): max_outer x { goodFeatureMatching (corner, then surf; wo_gf = all matched features),
  * evalHessian + evalDegenracy, Levenberg-Marquardt (Ceres trust-region semantics, <= max_lm_iterations) on the selected,
  * fixed correspondences }. Device-resident for wo_gf; the other gf methods add one host round trip per outer iteration for
- * the selection loop. replaces lidar_mapper_keyframe.cpp:423-639. stats: max_outer records, or NULL (then evalDegenracy takes
+ * the selection loop. replaces lidar_mapper_keyframe.cpp:423-599 and 628-639; with MLH_FLAG_POSE_COV in opts->flags also :600-606 and what :632 stores
+ * (mlh_scan2map_cov below). stats: max_outer records, or NULL (then evalDegenracy takes
  * the eigen-decomposition only when H - thre*I is not positive definite, i.e. when something IS degenerate). */
 int mlh_scan2map(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts, mlh_iter_stat *stats);
-/* scan2MapOptimization submitted and collected separately (lidar_mapper_keyframe.cpp:423-639 as the mapper's per-frame call, :145-160 for the chained start pose):
+/* scan2MapOptimization submitted and collected separately (lidar_mapper_keyframe.cpp:423-599 and 628-639 -- :600-606 with MLH_FLAG_POSE_COV -- as the mapper's per-frame call, :145-160 for the chained start pose):
  * mlh_scan2map_begin enqueues the whole solve and returns. lm_lookahead = 0 (automatic): per outer iteration the match launch and ONE launch that runs the
  * Levenberg-Marquardt loop to its end on the device -- nothing to overflow -- wherever that launch applies (one GPU, at most mlh_get_info's loop_max_tiles fit
  * tiles: 160 = 40 960 feature slots on a whole MI355X, fewer on a part of one);
@@ -604,6 +608,24 @@ int mlh_scan2map(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts
 int mlh_scan2map_begin(mlh_ctx *ctx, const double pose_in[7], const mlh_solver_opts *opts, int lm_lookahead);
 int mlh_scan2map_begin_chained(mlh_ctx *ctx, const double wodom_prev[7], const double wodom_cur[7], const mlh_solver_opts *opts, int lm_lookahead);
 int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out);
+/* The pose covariance of the most recently COLLECTED scan2map solve -- mlh_scan2map or mlh_downsample_scan2map has returned, or mlh_scan2map_end has returned that
+ * solve -- whose options carried MLH_FLAG_POSE_COV (lidar_mapper_keyframe.cpp:600-622 and the assignment at :632):
+ *   H_final_out (nullable)  evalHessian at the returned pose: J^T J, Huber-corrected, over the residual blocks of the last outer iteration (problem.Evaluate at the
+ *                           pose the last ceres::Solve returned, cpp:600-605);
+ *   cov_out                 its inverse (cov_mapping = mat_H.inverse(), cpp:606), computed as Eigen's fixed-size inverse is: LU with partial pivoting, solved against
+ *                           the identity. A singular H gives the inf / NaN that gives; nothing is special-cased.
+ * Both row-major 6 x 6 in the order of the pose's tangent [t, theta], like mlh_iter_stat::H. No evaluation launch and no host wait are added: when the
+ * Levenberg-Marquardt loop ends, its state's record at the current pose IS that Hessian (the record is replaced by the candidate's exactly when a step is accepted),
+ * so the wavefront that publishes the pose inverts it and stores both matrices in front of the pose. They are copied out of the pinned record when the solve is
+ * collected: two solves in flight do not overwrite each other's, and every form the solve's launches can take delivers the same bits. A local map below
+ * scan2MapOptimization's minimum (cpp:429: nothing is optimised) gives two zero matrices (cpp:637).
+ * The rule of cpp:607-608 -- cov_mapping is ZERO while the mapper holds at most 10 keyframes -- is the caller's: the library does not know the mapper's keyframe
+ * count at this call (the facade's scan2MapOptimization applies it). With with_ua_flag off the reference stores zero as well (cpp:621).
+ * MLH_ERR_STATE (with a text): nothing collected yet, the collected solve did not set the flag, or its pose_out was not a result (mlh_scan2map_end statuses 1, 3;
+ * a call that returned an error -- a frame whose thinning kept no feature of a kind among them, which mlh_downsample_scan2map reports as MLH_ERR_STATE like
+ * mlh_scan2map does an empty feature set: there is no record to invert, and nothing is delivered).
+ * Under an RCCL or mailbox communicator a flagged solve is refused with MLH_ERR_UNSUPPORTED before anything is enqueued. */
+int mlh_scan2map_cov(mlh_ctx *ctx, double cov_out[36], double H_final_out[36]);
 /* downsampleCurrentScan (both kinds) and scan2MapOptimization back to back WITHOUT the host reading what the thinning kept (lidar_mapper_keyframe.cpp:356-421 ->
  * :423-639, as process() calls them one after the other, cpp:1000-1112): the solve's launches are sized for an upper bound (the input clouds) and take the feature
  * counts from device memory; the counts come back with the pose. Same results as mlh_downsample_current_scan_pair followed by mlh_scan2map(stats = NULL), bit for

@@ -21,7 +21,7 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mloam_hip.h")
 SURF, CORNER = 0, 1
 ALL_KINDS = -1
 MEM_HOST, MEM_DEVICE = 0, 1
-FLAG_CHECK_FOV, FLAG_WITH_UA, FLAG_NO_LOSS = 1, 2, 4
+FLAG_CHECK_FOV, FLAG_WITH_UA, FLAG_NO_LOSS, FLAG_POSE_COV = 1, 2, 4, 8
 GF_METHODS = {"wo_gf": 0, "rnd": 1, "fps": 2, "gd_fix": 3, "gd_float": 4}
 K_KNN, K_FIT, K_LINEARIZE, K_SOLVE, K_GRID_BUILD, K_EXTRACT, K_ALLREDUCE, K_KNN_PRE, K_KNN_FIRST = range(9)
 K_ALL = 0x1FF
@@ -174,6 +174,7 @@ def load_library():
     lib.mlh_scan2map_begin.argtypes = [vp, vp, C.POINTER(SolverOpts), ci]
     lib.mlh_scan2map_begin_chained.argtypes = [vp, vp, vp, C.POINTER(SolverOpts), ci]
     lib.mlh_scan2map_end.argtypes = [vp, vp, vp]
+    lib.mlh_scan2map_cov.argtypes = [vp, vp, vp]
     lib.mlh_std_sort_permutation.argtypes = [vp, vp, ci, ci, vp, ci]
     lib.mlh_debug_bad_launch.argtypes = [vp]
     lib.mlh_pure_odom_begin.argtypes = [vp]
@@ -215,7 +216,7 @@ EXPORTED_SYMBOLS = [
     "mlh_point_uncertainty", "mlh_downsample_current_scan", "mlh_voxel_filter", "mlh_pure_odom_set", "mlh_pure_odom_evaluate", "mlh_pure_odom_normal_eq", "mlh_track_opts_default", "mlh_track_set_prev", "mlh_track_set_cur",
     "mlh_track_set_from_scan", "mlh_downsample_current_scan_pair", "mlh_downsample_scan2map", "mlh_voxel_grid", "mlh_transform_point_cloud", "mlh_transform_to_end", "mlh_scan_undistort", "mlh_fuse_reset", "mlh_fuse_add_scan", "mlh_fuse_add_scan_from", "mlh_fuse_add_rings", "mlh_fused_cloud", "mlh_track_match", "mlh_track_cloud", "mlh_cloud_uct_associate_to_map", "mlh_compound_pose_with_cov",
     "mlh_map_set", "mlh_map_set_pair", "mlh_map_set_pair_overlapped", "mlh_map_rebuild", "mlh_map_info", "mlh_set_voxel_member_order", "mlh_debug_bad_launch", "mlh_set_extract_tie_order", "mlh_set_gn_schedule", "mlh_std_sort_permutation", "mlh_pure_odom_begin", "mlh_pure_odom_add_matches", "mlh_pure_odom_add_matches_gf", "mlh_pure_odom_gn_solve", "mlh_knn", "mlh_features_set", "mlh_features_set_block", "mlh_gn_solve_blocks",
-    "mlh_match_linearize", "mlh_match_coeffs", "mlh_linearize", "mlh_good_feature_matching", "mlh_solver_opts_default", "mlh_gn_solve", "mlh_gn_solve_begin", "mlh_gn_solve_begin_chained", "mlh_gn_solve_end", "mlh_features_copy", "mlh_scan2map", "mlh_scan2map_begin", "mlh_scan2map_begin_chained", "mlh_scan2map_end",
+    "mlh_match_linearize", "mlh_match_coeffs", "mlh_linearize", "mlh_good_feature_matching", "mlh_solver_opts_default", "mlh_gn_solve", "mlh_gn_solve_begin", "mlh_gn_solve_begin_chained", "mlh_gn_solve_end", "mlh_features_copy", "mlh_scan2map", "mlh_scan2map_begin", "mlh_scan2map_begin_chained", "mlh_scan2map_end", "mlh_scan2map_cov",
     "mlh_shard_set", "mlh_shard_set_features", "mlh_comm_unique_id", "mlh_comm_init", "mlh_p2p_mailbox", "mlh_p2p_comm_init", "mlh_allreduce_f64",
     "mlh_pose_plus", "mlh_eval_degeneracy",
     "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
@@ -273,11 +274,14 @@ def default_track_opts(**kw) -> TrackOpts:
     return o
 
 
-def default_opts(**kw) -> SolverOpts:
+def default_opts(pose_cov: bool = False, **kw) -> SolverOpts:
+    """mlh_solver_opts_default, then the given fields; pose_cov=True adds FLAG_POSE_COV to whatever `flags` says (Context.scan2map_cov reads the result)"""
     o = SolverOpts()
     load_library().mlh_solver_opts_default(C.byref(o))
     for k, v in kw.items():
         setattr(o, k, v)
+    if pose_cov:
+        o.flags |= FLAG_POSE_COV
     return o
 
 
@@ -944,6 +948,13 @@ class Context:
         st = C.c_int32(0)
         self._ck(self.lib.mlh_scan2map_end(self.h, _p(p), C.byref(st)))
         return p, int(st.value)
+
+    def scan2map_cov(self):
+        """-> (cov, H_final), 6 x 6 each in the tangent's order [t, theta]: evalHessian at the pose the most recently collected scan2map solve returned and its
+        inverse (mlh_scan2map_cov; the solve's options must carry FLAG_POSE_COV)"""
+        cov, H = np.zeros((6, 6)), np.zeros((6, 6))
+        self._ck(self.lib.mlh_scan2map_cov(self.h, _p(cov), _p(H)))
+        return cov, H
 
     def scan2map(self, pose, opts: SolverOpts | None = None, want_stats=True):
         opts = opts or default_opts()

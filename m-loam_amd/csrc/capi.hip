@@ -357,9 +357,10 @@ static int query_device_caps(mlh_ctx *c)
     if (hipGetDeviceProperties(&prop, c->device) != hipSuccess) return MLH_ERR_HIP;
     c->caps.cu_count = prop.multiProcessorCount;
     c->caps.cu_solver = prop.multiProcessorCount;
-    int occ[2] = {0, 0}, occ_t = 0;
-    if (lm_loop_occupancy(occ) != MLH_OK || track_loop_occupancy(&occ_t) != MLH_OK) return MLH_ERR_HIP;
+    int occ[2] = {0, 0}, occ_cov[2] = {0, 0}, occ_t = 0;
+    if (lm_loop_occupancy(occ, occ_cov) != MLH_OK || track_loop_occupancy(&occ_t) != MLH_OK) return MLH_ERR_HIP;
     c->caps.blocks_per_cu[0] = occ[0]; c->caps.blocks_per_cu[1] = occ[1]; c->caps.blocks_per_cu[2] = occ_t;
+    c->caps.blocks_per_cu_cov[0] = occ_cov[0]; c->caps.blocks_per_cu_cov[1] = occ_cov[1];
     unsigned long long us = 20000;                // a completed barrier takes ~2 us; another context's longest kernel in the way, < 1 ms
     if (const char *e = std::getenv("MLH_LOOP_TIMEOUT_US")) { const long long v = std::atoll(e); if (v > 0) us = (unsigned long long)v; }
     c->caps.loop_timeout_ticks = us * 100ull;     // wall_clock64(): 100 MHz
@@ -383,15 +384,18 @@ static void set_loop_gates(mlh_ctx *c)
     const int by_size[3] = {GN_DEFER_MAX_TILES, FUSED_LOOP_MAX_TILES, GN_DEFER_MAX_TILES};
     int by_hand = -1;
     if (const char *e = std::getenv("MLH_LOOP_MAX_TILES")) by_hand = std::max(0, std::atoi(e));
-    for (int i = 0; i < 3; ++i) {
-        const int per_cu = std::max(0, std::min(c->caps.blocks_per_cu[i], 6));
+    auto gate_of = [&](int i, int blocks_per_cu) {
+        const int per_cu = std::max(0, std::min(blocks_per_cu, 6));
         long long resident = (long long)per_cu * c->caps.cu_solver;
         resident = std::max(0ll, resident - std::max<long long>(c->caps.cu_solver / 8, 8));
         int gate = int(std::min<long long>(resident, by_size[i]));
         if (by_hand >= 0) gate = std::min(gate, by_hand);
         if (c->caps.loop_demoted[i] >= 0) gate = std::min(gate, c->caps.loop_demoted[i]);
-        c->caps.loop_max_tiles[i] = gate;
-    }
+        return gate;
+    };
+    for (int i = 0; i < 3; ++i) c->caps.loop_max_tiles[i] = gate_of(i, c->caps.blocks_per_cu[i]);
+    // a frame that carries MLH_FLAG_POSE_COV ends in the loop kernel's covariance instantiation: both instantiations' workgroups have to be resident
+    for (int i = 0; i < 2; ++i) c->caps.loop_max_tiles_cov[i] = std::min(c->caps.loop_max_tiles[i], gate_of(i, c->caps.blocks_per_cu_cov[i]));
 }
 
 // A loop kernel of kind `which` came back with its barrier given up on at `tiles` workgroups: that many are evidently not resident together here. Half of it from
@@ -403,7 +407,10 @@ static void demote_loop_gate(mlh_ctx *c, int which, int tiles)
     c->caps.loop_demoted[which] = std::min(cur, tiles) / 2;
     set_loop_gates(c);
 }
-static bool loop_tiles_ok(const mlh_ctx *c, int which, int tiles) { return tiles > 0 && tiles <= c->caps.loop_max_tiles[which]; }
+static bool loop_tiles_ok(const mlh_ctx *c, int which, int tiles, bool cov = false)
+{
+    return tiles > 0 && tiles <= ((cov && which < 2) ? c->caps.loop_max_tiles_cov : c->caps.loop_max_tiles)[which];
+}
 // The barrier of a one-launch loop was given up on (DONE_GIVEN_UP: its workgroups were not all resident at once beside whatever else runs here). Counted and the
 // gate lowered; the caller then solves the frame again from the start pose it still holds through a launch-per-iteration form: same arithmetic, same pose bits, no
 // residency requirement. (mlh_scan2map_end, which may have to hand the frame back instead, uses the pieces separately.)
@@ -1389,7 +1396,7 @@ void mlh_solver_opts_default(mlh_solver_opts *o)
 static MatchArgs args_from_opts(const mlh_solver_opts *o, int kind_mask, int pose_sel)
 {
     MatchArgs a;
-    a.kind_mask = kind_mask; a.eig_thre[0] = o->map_eig_thre; a.flags = o->flags & (MLH_FLAG_CHECK_FOV | MLH_FLAG_WITH_UA);
+    a.kind_mask = kind_mask; a.eig_thre[0] = o->map_eig_thre; a.flags = o->flags & (MLH_FLAG_CHECK_FOV | MLH_FLAG_WITH_UA | MLH_FLAG_POSE_COV);      // (POSE_COV: read by the LM launchers of scan2map only, match.hip: pose_cov_launch)
     a.min_match_sq_dis = o->min_match_sq_dis; a.min_plane_dis = o->min_plane_dis;
     a.huber_delta = o->huber_delta; a.cov_measurement_trace = o->cov_measurement_trace; a.dense = false; a.pose_sel = pose_sel;
     return a;
@@ -1672,6 +1679,29 @@ enum class S2mForm {   // per outer iteration: correspondences (+ a good-feature
 };
 static bool s2m_selects(const mlh_solver_opts *opts) { return opts->gf_method != MLH_GF_WO; }
 
+// ---- MLH_FLAG_POSE_COV: H at the returned pose and its inverse ride in the publication that carries the pose (reduce_dev.hpp: publish_pose_cov); what
+// mlh_scan2map_cov hands out is copied from that record when the solve is collected
+static bool wants_pose_cov(const mlh_solver_opts *opts) { return (opts->flags & MLH_FLAG_POSE_COV) != 0; }
+// a scan2map solve is being collected: until it has produced a result there is nothing for the getter
+static void pose_cov_open(mlh_ctx *ctx, const mlh_solver_opts *opts)
+{
+    ctx->pose_cov.state = wants_pose_cov(opts) ? mlh_ctx::PoseCov::NOT_A_RESULT : mlh_ctx::PoseCov::UNFLAGGED;
+}
+// ... and has: hp = the publication its pose came with, or null -- nothing was optimised (a local map below cpp:429's minimum): both matrices zero (cpp:637)
+static void pose_cov_collect(mlh_ctx *ctx, const mlh_solver_opts *opts, const HostPublish *hp)
+{
+    if (!wants_pose_cov(opts)) { ctx->pose_cov.state = mlh_ctx::PoseCov::UNFLAGGED; return; }
+    for (int i = 0; i < 36; ++i) { ctx->pose_cov.H[i] = hp ? hp->H_final[i] : 0.0; ctx->pose_cov.cov[i] = hp ? hp->cov[i] : 0.0; }
+    ctx->pose_cov.state = mlh_ctx::PoseCov::VALID;
+}
+// the multi-rank forms exchange records inside their launches or step through them on the host: they publish no covariance, so the flag is refused up front
+static int pose_cov_refuse_distributed(mlh_ctx *ctx, const mlh_solver_opts *opts)
+{
+    if (wants_pose_cov(opts) && distributed(ctx))
+        return fail(ctx, MLH_ERR_UNSUPPORTED, "MLH_FLAG_POSE_COV under an RCCL or mailbox communicator: the pose covariance is delivered by the single-GPU forms of scan2map only");
+    return MLH_OK;
+}
+
 // THE decision: mlh_scan2map, mlh_scan2map_begin* and mlh_downsample_scan2map all ask here (DESIGN.md section 5 has it as a table). allow_loop: the caller has not
 // ruled the one-launch loop out; gate / tiles: the residency gate the loop launch would pass (mlh_ctx::caps::loop_max_tiles) and the workgroups it would have.
 static S2mForm s2m_form(const mlh_ctx *ctx, const mlh_solver_opts *opts, bool want_stats, bool allow_loop, int gate, int tiles)
@@ -1683,12 +1713,12 @@ static S2mForm s2m_form(const mlh_ctx *ctx, const mlh_solver_opts *opts, bool wa
     // path's limit). Gate 1 -- the fused thinning + solve call, which sizes its launches for the UN-thinned clouds -- deliberately tests that bound against its own
     // gate only (FUSED_LOOP_MAX_TILES, set_loop_gates): the thinned frame it solves is far below the limit.
     if (!one_gpu || want_stats || !schedule_on(Schedule::LM_CONSUMER) || (gate != 1 && tiles > GN_DEFER_MAX_TILES)) return S2mForm::FUSED_CHUNKS;
-    if (allow_loop && schedule_on(Schedule::LM_LOOP) && loop_tiles_ok(ctx, gate, tiles)) return S2mForm::LOOP;      // (every tile's workgroup resident at once)
+    if (allow_loop && schedule_on(Schedule::LM_LOOP) && loop_tiles_ok(ctx, gate, tiles, wants_pose_cov(opts))) return S2mForm::LOOP;      // (every tile's workgroup resident at once)
     return s2m_selects(opts) ? S2mForm::FUSED_CHUNKS : S2mForm::CONSUMER_CHUNKS;      // (linearize_launch's LM begin has no consumer-side chunk form)
 }
 
-// The pose a one-launch loop published to rec / seq, into pose_out. *given_up: DONE_GIVEN_UP -- pose_out is left as it was (note_loop_given_up)
-static int collect_loop_pose(mlh_ctx *ctx, unsigned long long seq, HostPublish *rec, double pose_out[7], bool *given_up)
+// The pose a one-launch loop published to rec / seq, into pose_out (hp_out, nullable: the whole publication -- a scan2map caller collects its matrices from it once the call is known to succeed). *given_up: DONE_GIVEN_UP -- pose_out is left as it was (note_loop_given_up)
+static int collect_loop_pose(mlh_ctx *ctx, unsigned long long seq, HostPublish *rec, double pose_out[7], bool *given_up, HostPublish *hp_out = nullptr)
 {
     HostPublish hp;
     int rc = wait_published(ctx, seq, hp, rec);
@@ -1696,6 +1726,7 @@ static int collect_loop_pose(mlh_ctx *ctx, unsigned long long seq, HostPublish *
     *given_up = (hp.done & DONE_GIVEN_UP) != 0;
     if (*given_up || (rc = prof_drain(ctx))) return rc;
     pose_copy(pose_out, hp.x);
+    if (hp_out) *hp_out = hp;
     return MLH_OK;
 }
 
@@ -1730,6 +1761,7 @@ static MatchArgs s2m_lm_args(const mlh_solver_opts *opts, bool lmc, int outer, i
 {
     MatchArgs a = args_from_opts(opts, 3, 1);
     a.finish = TAIL_LM_STEP; a.lm_max_it = opts->max_lm_iterations;
+    if (outer != opts->max_outer - 1) a.flags &= ~uint32_t(MLH_FLAG_POSE_COV);      // (the covariance belongs to the LAST outer iteration's loop: earlier chunks publish the default way)
     if (lmc) {
         a.finish = TAIL_RECORDS; a.lmc = j == 0 ? LMC_BEGIN : LMC_STEP; a.lmc_j = j + 1;
         if (j == 0 && outer == 0) { a.init_pose = pose; a.lm_expect_done = LM_FIRST_OF_SOLVE; }
@@ -1852,6 +1884,7 @@ static int s2m_polled_frame(mlh_ctx *ctx, double pose_inout[7], const mlh_solver
 {
     const bool in_launch = form != S2mForm::HOST_STEPPED, lmc = form == S2mForm::CONSUMER_CHUNKS;
     int rc;
+    if (!in_launch && (rc = pose_cov_refuse_distributed(ctx, opts))) return rc;      // (HOST_STEPPED is a multi-rank form: s2m_form)
     // (every feature used, the LM begin in the match launch's own tail or its consumer: the pose goes in with the first launch's kernel arguments instead)
     if ((!in_launch || s2m_selects(opts)) && (rc = upload_pose(ctx, pose_inout))) return rc;
     HostPublish verdict;       // in_launch: the last chunk's publication already carries the pose
@@ -1876,9 +1909,12 @@ static int s2m_polled_frame(mlh_ctx *ctx, double pose_inout[7], const mlh_solver
     if (in_launch && !stats) {
         if ((rc = prof_drain(ctx))) return rc;
         pose_copy(pose_inout, verdict.x);
+        pose_cov_collect(ctx, opts, &verdict);
         return MLH_OK;
     }
-    return fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer);
+    if ((rc = fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer))) return rc;
+    if (in_launch) pose_cov_collect(ctx, opts, &verdict);      // (the last chunk's publication: the loop's last launch, statistics or not)
+    return MLH_OK;
 }
 
 // The synchronous solve. allow_loop = false (mlh_scan2map_end / mlh_downsample_scan2map, behind a loop that was given up): a launch-per-iteration form
@@ -1887,10 +1923,13 @@ static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_
     if (!ctx || !pose_inout || !opts_in || opts_in->max_outer <= 0) return MLH_ERR_INVALID;
     const mlh_solver_opts opts_v = scan2map_opts(opts_in), *opts = &opts_v;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
-    int rc = solver_begin(ctx, opts->max_outer);
+    int rc = pose_cov_refuse_distributed(ctx, opts);
     if (rc) return rc;
+    pose_cov_open(ctx, opts);
+    if ((rc = solver_begin(ctx, opts->max_outer))) return rc;
     if (!scan2map_has_maps(ctx)) {
         if (stats) std::memset(stats, 0, sizeof(mlh_iter_stat) * size_t(opts->max_outer));
+        pose_cov_collect(ctx, opts, nullptr);
         return MLH_OK;
     }
     if (ctx->feat[0].m <= 0 || ctx->feat[1].m <= 0) return fail(ctx, MLH_ERR_STATE, "features_set is required for both kinds");
@@ -1901,7 +1940,9 @@ static int scan2map_polled(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_
     unsigned long long seq = 0;
     bool given_up = false;
     if ((rc = publish_slot(ctx, &rec, &seq, 0)) || (rc = enqueue_s2m_loop_frame(ctx, opts, pose_inout, nullptr, rec, seq))) return rc;
-    if ((rc = collect_loop_pose(ctx, seq, rec, pose_inout, &given_up)) || !given_up) return rc;
+    HostPublish hp;
+    if ((rc = collect_loop_pose(ctx, seq, rec, pose_inout, &given_up, &hp))) return rc;
+    if (!given_up) { pose_cov_collect(ctx, opts, &hp); return MLH_OK; }
     // (a selection's draws start from opts->gf_seed again: the same frame)
     note_loop_given_up(ctx, 0, tiles);
     return s2m_polled_frame(ctx, pose_inout, opts, stats, s2m_form(ctx, opts, stats != nullptr, false, 0, tiles));
@@ -1919,6 +1960,7 @@ static int scan2map_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     if (ctx->comm) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_scan2map_begin under an RCCL communicator: the sharded LM iteration there is a host-driven sequence of launches and collectives (use the mailbox communicator)");
     if (opts->gf_method != MLH_GF_WO) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_scan2map_begin with a good-feature selection: the selection loops run on the host between the launches (use mlh_scan2map)");
     if (opts->max_outer <= 0) return fail(ctx, MLH_ERR_INVALID, "max_outer must be positive");
+    { const int crc = pose_cov_refuse_distributed(ctx, opts); if (crc) return crc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     unsigned long long seq = 0;
     HostPublish *rec = nullptr;
@@ -1992,6 +2034,7 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
     if (solved || slot.chained) rc = wait_published(ctx, seq, hp, ctx->solves.record(seq));
     else { pose_copy(hp.x, slot.start); hp.done = DONE_TERMINATED; }
     ctx->solves.retire(seq);
+    pose_cov_open(ctx, &slot.opts);
     if (rc) { ctx->solves.taint_successor(seq); return rc; }
     if (!ctx->solves.pending() && (rc = prof_drain(ctx))) return rc;
     const bool barrier_given_up = solved && (hp.done & DONE_GIVEN_UP);       // (a one-launch LM loop whose workgroups were not all resident: lm_loop_kernel)
@@ -2012,6 +2055,7 @@ int mlh_scan2map_end(mlh_ctx *ctx, double pose_out[7], int32_t *status_out)
             if (status_out) { *status_out = 3; return MLH_OK; }
             return fail(ctx, MLH_ERR_INCOMPLETE, "mlh_scan2map_end: the frame was chained behind one that did not finish inside its look-ahead (status 3) and status_out is NULL");
         }
+        pose_cov_collect(ctx, &slot.opts, solved ? &hp : nullptr);
         return MLH_OK;
     }
     // the look-ahead was too short for this frame -- or its one-launch loop gave its barrier up
@@ -2035,6 +2079,20 @@ int mlh_scan2map(mlh_ctx *ctx, double pose_inout[7], const mlh_solver_opts *opts
     return scan2map_polled(ctx, pose_inout, opts, stats);
 }
 
+int mlh_scan2map_cov(mlh_ctx *ctx, double cov_out[36], double H_final_out[36])
+{
+    if (!ctx || !cov_out) return MLH_ERR_INVALID;
+    switch (ctx->pose_cov.state) {
+    case mlh_ctx::PoseCov::NONE: return fail(ctx, MLH_ERR_STATE, "mlh_scan2map_cov: no scan2map solve has been collected yet");
+    case mlh_ctx::PoseCov::UNFLAGGED: return fail(ctx, MLH_ERR_STATE, "mlh_scan2map_cov: the most recently collected scan2map solve did not set MLH_FLAG_POSE_COV");
+    case mlh_ctx::PoseCov::NOT_A_RESULT: return fail(ctx, MLH_ERR_STATE, "mlh_scan2map_cov: the most recently collected scan2map solve did not return a result (an error, or mlh_scan2map_end status 1 / 3)");
+    case mlh_ctx::PoseCov::VALID: break;
+    }
+    std::memcpy(cov_out, ctx->pose_cov.cov, sizeof(ctx->pose_cov.cov));
+    if (H_final_out) std::memcpy(H_final_out, ctx->pose_cov.H, sizeof(ctx->pose_cov.H));
+    return MLH_OK;
+}
+
 // downsampleCurrentScan + scan2MapOptimization with no host read between them (include/mloam_hip.h)
 int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, const void *corner_points, int n_corner, int stride_bytes,
                             int intensity_offset_bytes, int mem, float leaf_surf, float leaf_corner, const double *ext_poses, const double *ext_covs,
@@ -2043,6 +2101,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
 {
     if (!ctx || !pose_inout || !opts_in || !n_surf_features || !n_corner_features || opts_in->max_outer <= 0) return MLH_ERR_INVALID;
     const mlh_solver_opts opts_v = scan2map_opts(opts_in), *opts = &opts_v;      // (CHECK_FOV does not apply to scan2map: see scan2map_opts)
+    { const int crc = pose_cov_refuse_distributed(ctx, opts); if (crc) return crc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     auto two_calls = [&]() -> int {
         int rc = mlh_downsample_current_scan_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, intensity_offset_bytes, mem, leaf_surf, leaf_corner,
@@ -2060,6 +2119,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
         return two_calls();
     int rc = solver_begin(ctx, 0);
     if (rc) return rc;
+    pose_cov_open(ctx, opts);
     ++ctx->stage_epoch;
     for (int k = 0; k < 2; ++k) { ctx->feat[k].matched = false; ctx->feat[k].m = 0; }
     int m[2] = {0, 0};
@@ -2082,7 +2142,8 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     rc = enqueue_s2m_loop_frame(ctx, opts, pose_inout, ctx->thin_counts_dev, rec, seq);
     double pose[7];
     bool given_up = false;
-    if (!rc) rc = collect_loop_pose(ctx, seq, rec, pose, &given_up);
+    HostPublish hp;
+    if (!rc) rc = collect_loop_pose(ctx, seq, rec, pose, &given_up, &hp);
     // the counts were published by the thinning's last launch, long before the pose: no wait here in practice
     int real[2] = {0, 0};
     if (!rc && !(rc = host_wait_seq(ctx, ctx->thin_seq_host, ctx->thin_seq, ctx->stream, "the thinned feature counts did not arrive"))) {
@@ -2096,6 +2157,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
     // given up (workgroups sized for the un-thinned clouds): the thinned sets are staged and counted by now -- the solve again, as the second of the two calls
     if (given_up) { note_loop_given_up(ctx, 1, bound_tiles); return scan2map_polled(ctx, pose_inout, opts, nullptr, false); }
     pose_copy(pose_inout, pose);
+    pose_cov_collect(ctx, opts, &hp);      // (behind every error return: a call that failed leaves nothing for mlh_scan2map_cov)
     return MLH_OK;
 }
 

@@ -85,7 +85,14 @@ struct HostPublish {
     double xb[8][7];
     long long done;          // DoneBits at publication (the LM driver polls it)
     unsigned long long seq;
+    // MLH_FLAG_POSE_COV (reduce_dev.hpp: publish_pose_cov): the Hessian at the published pose -- the LM state's record at x, mirrored as IterStatDev::H is -- and its
+    // inverse (lidar_mapper_keyframe.cpp:600-606), row-major in the tangent's order [t, theta]; stored in front of `seq` by a publication whose LM loop has terminated
+    double H_final[36];
+    double cov[36];
 };
+static_assert(offsetof(HostPublish, x) == 0 && offsetof(HostPublish, xb) == 56 && offsetof(HostPublish, done) == 504 && offsetof(HostPublish, seq) == 512 &&
+              offsetof(HostPublish, H_final) == 520 && offsetof(HostPublish, cov) == 808 && sizeof(HostPublish) == 1096,
+              "the publication record: pose, block poses, done word and sequence word where they have always been; the two matrices behind them");
 
 // ---------------------------------------------------------------- the solver's launch modes
 // Named once, here; the hosts (capi.hip, the launchers of match.hip / track.hip) and the kernels use the names, never the numbers. Unscoped, `int` underneath and
@@ -423,6 +430,8 @@ struct mlh_ctx {
         int loop_demoted[3] = {-1, -1, -1};   // >= 0: a barrier was given up on -- the gate this context keeps below from then on
         int blocks_per_cu[3] = {0, 0, 0}; // hipOccupancyMaxActiveBlocksPerMultiprocessor: lm_loop_kernel<false>, lm_loop_kernel<true>, track_lm_loop_kernel
         int loop_max_tiles[3] = {0, 0, 0};// workgroups of those kernels the host will put behind one in-kernel barrier (0: never -- the launch-per-iteration forms)
+        int blocks_per_cu_cov[2] = {0, 0};   // the same two numbers for lm_loop_kernel's MLH_FLAG_POSE_COV instantiations, which a flagged frame's last loop launch is
+        int loop_max_tiles_cov[2] = {0, 0};
         unsigned long long loop_timeout_ticks = 0;   // a barrier wait longer than this many 100 MHz ticks gives the loop up (MLH_LOOP_TIMEOUT_US, default 20 ms)
         unsigned long long loop_launches = 0;        // frames / rounds solved through the one-launch loop
         unsigned long long loop_timeouts = 0;        // ... that came back with the barrier given up on
@@ -513,6 +522,11 @@ struct mlh_ctx {
     mlh::PinnedBuf h_state;  // three HostPublish records the device writes the result pose(s) into (capi.hip: publish_slot)
     mlh::PinnedBuf h_occ;    // mirror of the two maps' occupancy totals (grid.hip): {cells, squares} per kind, written behind every index build
     unsigned long long publish_seq = 0;
+    // mlh_scan2map_cov: the two matrices of the most recently collected scan2map solve, copied out of its pinned record at collection (capi.hip: pose_cov_*)
+    struct PoseCov {
+        enum State : int { NONE /* nothing collected yet */, VALID, UNFLAGGED /* collected without MLH_FLAG_POSE_COV */, NOT_A_RESULT /* its pose_out was not a result */ } state = NONE;
+        double H[36], cov[36];
+    } pose_cov;
     mlh::DevBuf uct_buf;     // point-uncertainty scratch
     mlh::VoxBuf vox;
     mlh::KfStore kf;         // keyframe store + local map (keyframes.hip)
@@ -834,7 +848,7 @@ int gn_flush_pending(mlh_ctx *ctx);      // completes a pending last iteration w
 int linearize_launch(mlh_ctx *ctx, const MatchArgs &a);
 int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a);
 bool loop_fit_fusable(const MatchArgs &loop_args);   // the loop launch described by these arguments would exchange tagged records (ctx.hpp: loop_tagged_arm's conditions)
-int lm_loop_occupancy(int blocks_per_cu[2]);      // hipOccupancyMaxActiveBlocksPerMultiprocessor of lm_loop_kernel<false> / <true>
+int lm_loop_occupancy(int blocks_per_cu[2], int blocks_per_cu_cov[2]);      // hipOccupancyMaxActiveBlocksPerMultiprocessor of lm_loop_kernel<false> / <true>; _cov: of the instantiations that publish the pose covariance
 int track_loop_occupancy(int *blocks_per_cu);     // ... of track_lm_loop_kernel (track.hip)
 // the arrival counters of the fused finishes and of lm_loop_kernel's barrier: four zeroed words, whoever asks first ([0]: the finish tickets of match.hip and
 // track.hip; [1] arrivals, [2] departures, [3] release flag of the loop kernel). One place, so that no caller can leave the others' words unallocated or unzeroed.

@@ -685,7 +685,8 @@ __device__ __forceinline__ void block_sum_args(const KParams &P, int b, int tota
 // Fused tail: the last workgroup to arrive (agent-scope release/acquire around an atomic ticket) sums the partial records
 // in fixed order, runs the degeneracy test + the 6x6 solve + Plus for every pose block and re-arms the ticket: a GN iteration
 // costs two launches.
-template <bool LM, int NT = TPB>
+// COV (LM only; MLH_FLAG_POSE_COV): a publication whose loop has terminated carries H at the pose and its inverse (reduce_dev.hpp: publish_pose_cov)
+template <bool LM, int NT = TPB, bool COV = false>
 __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tiles)
 {
     __shared__ double f_ne[NE_STRIDE], f_cnt2[2], f_scratch[(NT / 32) * 32];   // f_scratch doubles as the Jacobi work area (DEG_WORK <= 256)
@@ -709,6 +710,7 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
         if (threadIdx.x < 64) {      // one wavefront runs the LM begin / step (solver_dev.hpp: rows of the 6 x 6 objects on lanes)
             double xo[7];
             int done = 0;
+            [[maybe_unused]] bool fresh = false;   // (COV) the record at the pose this call leaves is f_ne -- behind a begin or an accepted step; the state's otherwise
             if (!exchanged) {        // a peer timed out: no decision on partial sums -- the loop ends here, the pose stays, the host reports the error word
 #pragma unroll
                 for (int i = 0; i < 7; ++i) xo[i] = P.state->x[i];
@@ -723,8 +725,11 @@ __device__ __forceinline__ void fused_gn_finish(const KParams &P, int total_tile
                     P.state->lm_used_max = P.lm_expect_done > LM_VERDICT_READ ? fmax(P.state->lm_used_max, double(P.state->iteration)) : 0.0;      // the loop that just ended
                 }
                 lm_begin_body_wave(f_ne, f_cnt2, f_scratch, P.state, P.thre_b[0], P.lm_max_it, P.stat, P.lm_min_blocks, xo, done);
+                if constexpr (COV) fresh = true;
             }
+            else if constexpr (COV) lm_step_body_wave(f_ne, P.state, P.lm_max_it, xo, done, &fresh);
             else lm_step_body_wave(f_ne, P.state, P.lm_max_it, xo, done);
+            if constexpr (COV) { if (P.publish && done && exchanged) publish_pose_cov(P.publish, fresh ? f_ne : P.state->ne); }
             if (threadIdx.x == 0) {
                 *P.ticket = 0u;
                 // last launch of a chunk of LM steps: the pose and the `done` flag go to the host from here
@@ -919,15 +924,17 @@ extern "C" int mlh_debug_stage_clock_knn(unsigned long long *out, int n_words)
 namespace mlh {
 #endif
 
-template <bool LM>
+template <bool LM, bool COV = false>
 __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
 {
+    static_assert(LM || !COV, "the covariance rides in a Levenberg-Marquardt publication");
     __shared__ double s_red[4 * 32];
     const int total = P.k[0].tiles_b + P.k[1].tiles_b;
     const int gtile = xcd_tile(total);
     if (gtile >= total) return;
     if (P.pose_sel && P.state->done) {   // candidate evaluation after the device-side LM loop has terminated: keep the partials defined, do no work
         if (threadIdx.x < 32) P.partials[size_t(gtile) * NE_STRIDE + threadIdx.x] = 0.0;
+        if constexpr (COV) { if (P.publish && gtile == 0 && threadIdx.x < 64) publish_pose_cov(P.publish, P.state->ne); }     // (the record an earlier launch left at the pose)
         if (LM && P.publish && gtile == 0 && threadIdx.x == 0)        // ... but the host may be waiting for this launch's publication
             lmc_publish(P, P.state->x, P.state->done, P.state->lm_overflow, P.state->lm_used_max, P.state->iteration);
         return;
@@ -955,7 +962,7 @@ __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
     MLH_STAGE(gtile, 2);
     reduce_rows(valid, L, P.huber_delta, (P.flags & MLH_FLAG_NO_LOSS) != 0, kind, s_red, P.partials + size_t(gtile) * NE_STRIDE, mult);
     MLH_STAGE(gtile, 3);
-    if constexpr (LM) { if (P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP) fused_gn_finish<true>(P, total); }   // (the begin: on rows a selection kept -- scan2map with good-feature selection)
+    if constexpr (LM) { if (P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP) fused_gn_finish<true, TPB, COV>(P, total); }   // (the begin: on rows a selection kept -- scan2map with good-feature selection)
     MLH_STAGE(gtile, 4);
 }
 
@@ -969,7 +976,7 @@ __global__ __launch_bounds__(TPB) void linearize_kernel(KParams P)
 // into SolverState::x, which only launches behind this one read); the records alternate between two buffers the same way. A launch that finds the loop terminated
 // copies the state forward and leaves (the host enqueues a look-ahead of launches without reading the verdict in between, as before).
 // FIRST: the launch behind a match launch whose fit kernel left records (TAIL_RECORDS) -- the records are at the state's pose (or init_pose), the LM loop begins here.
-template <bool FIRST>
+template <bool FIRST, bool COV = false>
 __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
 {
     __shared__ double s_red[4 * 32];
@@ -991,6 +998,7 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
                 const double *src = reinterpret_cast<const double *>(Si);
                 double *dst = reinterpret_cast<double *>(So);
                 for (int i = lane; i < NW; i += 64) dst[i] = src[i];
+                if constexpr (COV) { if (P.publish) publish_pose_cov(P.publish, Si->ne); }
                 if (P.publish && lane == 0) lmc_publish(P, Si->x, Si->done, Si->lm_overflow, Si->lm_used_max, Si->iteration);
             }
             return;
@@ -1030,6 +1038,12 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
         }
         if (lane < 7) s_cand[lane] = pick7(cand, lane);
         if (lane == 0) s_done = R.done;
+        if constexpr (COV) {
+            // the record at R.x: this launch's sums behind a begin or an accepted step (the state's count of those went up), the state's record otherwise
+            bool fresh = FIRST;
+            if constexpr (!FIRST) fresh = R.num_successful != Si->num_successful;
+            if (writer && P.publish && R.done) publish_pose_cov(P.publish, fresh ? f_ne : Si->ne);
+        }
         if (writer && lane == 0) {
             So->lm_overflow = overflow; So->lm_used_max = used_max;
             if (P.publish) lmc_publish(P, R.x, R.done, overflow, used_max, R.iteration);
@@ -1069,7 +1083,8 @@ __global__ __launch_bounds__(TPB) void lm_consume_kernel(KParams P)
 // correspondence record (stored: later launches and callers read it) -> residual + Jacobian at the start pose -> the tile's record, tagged with iteration 0 and
 // summed by polling like every other record of the loop -- instead of reading what a fit launch in front of it left. One launch boundary fewer per outer iteration;
 // the same operations on the same values: the same bits. Tagged records only (P.loop_tagged: the host's loop_fit_fusable()).
-template <bool DEVM = false, bool FIT = false>
+// COV (MLH_FLAG_POSE_COV, the frame's last loop launch): the publication carries H at the pose -- s_lm.ne -- and its inverse.
+template <bool DEVM = false, bool FIT = false, bool COV = false>
 __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: two workgroups per compute unit -- 256 registers in all; the residency gates count on them)
 {
     __shared__ double s_red[4 * 32];
@@ -1236,6 +1251,7 @@ __global__ __launch_bounds__(TPB, 2) void lm_loop_kernel(KParams P)      // (2: 
     else if (writer && threadIdx.x < 64) {
         const int lane = threadIdx.x;
         if (lane < 7) P.state->x[lane] = s_lm.x[lane];          // read by the launches BEHIND this one only (the other workgroups took their start pose long ago)
+        if constexpr (COV) { if (P.publish && s_lm.done) publish_pose_cov(P.publish, s_lm.ne); }
         if (lane == 0) {
             const double used = P.lm_expect_done < LM_VERDICT_READ ? double(s_lm.iteration) : fmax(P.state->lm_used_max, double(s_lm.iteration));
             // (a barrier given up on in an EARLIER outer iteration of the frame must not be lost: lm_overflow -- unused otherwise by this schedule -- carries it to the
@@ -1552,6 +1568,8 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
     return MLH_OK;
 }
 
+static bool pose_cov_launch(const KParams &P) { return (P.flags & MLH_FLAG_POSE_COV) != 0 && P.publish != nullptr; }
+
 int linearize_launch(mlh_ctx *ctx, const MatchArgs &a)
 {
     for (int k = 0; k < 2; ++k)
@@ -1560,7 +1578,10 @@ int linearize_launch(mlh_ctx *ctx, const MatchArgs &a)
     int rc = fill_params(ctx, a, P);
     if (rc) return rc;
     const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
-    if (P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP) launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<true>, grid_b, P);
+    // (the covariance of MLH_FLAG_POSE_COV rides in a publication: launches that publish nothing are the default kernels)
+    const bool lm = P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP;
+    if (lm && pose_cov_launch(P)) launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<true, true>, grid_b, P);
+    else if (lm) launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<true>, grid_b, P);
     else launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
@@ -1580,21 +1601,28 @@ int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a)
     if (a.lmc == LMC_LOOP) {
         { const char *e = std::getenv("MLH_DEBUG_LOOP_STALL"); P.debug_stall = (e && std::atoi(e) != 0) ? 1 : 0; }
         // every tile's workgroup has to be resident for the barrier: the host's gate (capi.hip: loop_tiles_ok) is what the device admits, asked at mlh_create
-        if (P.k[0].tiles_b + P.k[1].tiles_b > ctx->caps.loop_max_tiles[P.m_dev ? 1 : 0]) return fail(ctx, MLH_ERR_INVALID, "lm_loop_kernel: more tiles than can be resident at once on this device");
+        const bool cov = pose_cov_launch(P);
+        if (P.k[0].tiles_b + P.k[1].tiles_b > (cov ? ctx->caps.loop_max_tiles_cov : ctx->caps.loop_max_tiles)[P.m_dev ? 1 : 0]) return fail(ctx, MLH_ERR_INVALID, "lm_loop_kernel: more tiles than can be resident at once on this device");
         P.loop_timeout_ticks = ctx->caps.loop_timeout_ticks;
         if (a.lm_expect_done == LM_FIRST_OF_SOLVE) ++ctx->caps.loop_launches;      // (the first loop of a frame)
         // the iterations' records as tagged words summed by polling (MLH_LOOP_TAGGED=0: plain records behind a grid barrier, as through round 5)
         { hipError_t e = loop_tagged_arm(ctx, size_t(P.k[0].tiles_b + P.k[1].tiles_b), a.lm_max_it, &P.loop_tagged, &P.loop_tag_base); if (e != hipSuccess) return fail(ctx, MLH_ERR_HIP, "tagged records", e); }
         if (a.fit_in_loop) {
             if (!P.loop_tagged) return fail(ctx, MLH_ERR_INVALID, "the fit rides in the one-launch loop with tagged records only");
-            if (P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true, true>, grid_b, P);
+            if (cov && P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true, true, true>, grid_b, P);
+            else if (cov) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false, true, true>, grid_b, P);
+            else if (P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true, true>, grid_b, P);
             else launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false, true>, grid_b, P);
             for (int k = 0; k < 2; ++k) ctx->feat[k].matched = true;
         }
+        else if (cov && P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true, false, true>, grid_b, P);
+        else if (cov) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false, false, true>, grid_b, P);
         else if (P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true>, grid_b, P);
         else launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false>, grid_b, P);
     }
+    else if (a.lmc == LMC_BEGIN && pose_cov_launch(P)) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<true, true>, grid_b, P);
     else if (a.lmc == LMC_BEGIN) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<true>, grid_b, P);
+    else if (pose_cov_launch(P)) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<false, true>, grid_b, P);
     else launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
@@ -1605,7 +1633,7 @@ bool loop_fit_fusable(const MatchArgs &loop_args)
     return schedule_on(Schedule::LOOP_TAGGED) && loop_args.lm_max_it <= 200 && loop_args.n_blocks == 1 && !loop_args.dense;
 }
 
-int lm_loop_occupancy(int blocks_per_cu[2])
+int lm_loop_occupancy(int blocks_per_cu[2], int blocks_per_cu_cov[2])
 {
     // (the forms with and without the fit in front: the smaller number gates both)
     int with_fit[2] = {0, 0};
@@ -1614,6 +1642,12 @@ int lm_loop_occupancy(int blocks_per_cu[2])
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[0], lm_loop_kernel<false, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[1], lm_loop_kernel<true, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
     for (int i = 0; i < 2; ++i) blocks_per_cu[i] = std::min(blocks_per_cu[i], with_fit[i]);
+    // the instantiations that publish the covariance (MLH_FLAG_POSE_COV): gated by their own numbers
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu_cov[0], lm_loop_kernel<false, false, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu_cov[1], lm_loop_kernel<true, false, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[0], lm_loop_kernel<false, true, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[1], lm_loop_kernel<true, true, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
+    for (int i = 0; i < 2; ++i) blocks_per_cu_cov[i] = std::min(blocks_per_cu_cov[i], with_fit[i]);
     return MLH_OK;
 }
 

@@ -2,6 +2,7 @@
 // the scan-to-map and scan-to-scan linearisation kernels.
 #pragma once
 #include "ctx.hpp"
+#include "solver_dev.hpp"
 
 namespace mlh {
 
@@ -95,6 +96,26 @@ __device__ __forceinline__ void publish_pose(HostPublish *pub, unsigned long lon
     pub->done = done;
     if constexpr (USED) pub->xb[2][0] = used_max;
     publish_seq(pub, seq);
+}
+
+// MLH_FLAG_POSE_COV: the two matrices of a publication whose LM loop has terminated -- H at the published pose (`ne`: the LM state's record at x, any memory; its 21
+// sums mirrored as IterStatDev::H is filled) and its inverse (solver_dev.hpp: inv6_wave) -- into the record, IN FRONT of the publish_pose the caller's lane 0 issues
+// next: lane r stores row r of H_final, lane c column c of cov, plain vector stores; every lane then releases at system scope, so the sequence word, stored last by
+// lane 0, still finds the whole record behind it. Called by all 64 lanes of one wavefront, converged. A function of its own, not inlined: the kernels that call it
+// keep the register allocation of their loops.
+__device__ __noinline__ void publish_pose_cov(HostPublish *pub, const double *ne)
+{
+    const int lane = threadIdx.x & 63;
+    double Hrow[6], col[6];
+    inv6_wave(ne, lane, Hrow, col);
+    if (lane < 6) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) pub->H_final[lane * 6 + j] = Hrow[j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) pub->cov[i * 6 + lane] = col[i];
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+    __builtin_amdgcn_wave_barrier();
 }
 
 // The fused tails' ticket (match.hip: fused_gn_finish, track.hip: track_linearize_kernel), by every thread of a workgroup whose partial record has been stored: true

@@ -4,6 +4,7 @@
 #pragma once
 #include "ctx.hpp"
 #include "dev_math.hpp"
+#include "inv6.hpp"
 
 namespace mlh {
 
@@ -550,6 +551,64 @@ __device__ __forceinline__ void gn_finish_wave(const double *ne, const double *c
     for (int q = 0; q < 7; ++q) x_out[q] = wave_bcast(x_out[q], 0);
 }
 
+// ---------------------------------------------------------------- the pose covariance: H^-1 on ONE wavefront (lidar_mapper_keyframe.cpp:600-606)
+// inv6_lu (inv6.hpp) spread over the lanes, in the style of the lane-per-row Cholesky above: lane r < 6 owns ROW r of the matrix being factorised (a[]), lane c < 6
+// owns COLUMN c of the right-hand side (y[]: the identity going in, column c of the inverse coming out). A step's pivot candidates, the two rows it exchanges, its
+// multipliers and -- in the upper solve -- the rows of U travel by v_readlane (the pivot's lane is uniform, not constant); no LDS trip. Same operations in the same
+// order as inv6_lu, element for element: the comparisons of the pivot search, the quotients by the pivot, a(i, j) -= m(i) a(k, j), y(i) -= m(i) y(k) in ascending k,
+// the upper solve's terms in ascending j. A zero pivot divides as IEEE does. Called by all 64 lanes, converged; lanes >= 6 compute along on zeros and are ignored.
+// ne: the record whose upper-packed J^T J is inverted (any memory). Hrow: row `lane` of H (lanes < 6).
+__device__ __forceinline__ void inv6_wave(const double *ne, int lane, double (&Hrow)[6], double (&y)[6])
+{
+    double a[6];
+#pragma unroll
+    for (int c = 0; c < 6; ++c) {
+        const int r = lane < 6 ? lane : 0;
+        const int i = r < c ? r : c, j = r < c ? c : r;
+        const double v = ne[i * 6 - (i * (i - 1)) / 2 + (j - i)];
+        a[c] = lane < 6 ? v : 0.0;
+        Hrow[c] = a[c];
+        y[c] = lane == c ? 1.0 : 0.0;
+    }
+#pragma unroll
+    for (int k = 0; k < 6; ++k) {
+        int p = k;
+        double best = fabs(wave_bcast(a[k], k));
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) { const double v = fabs(wave_bcast(a[k], i)); if (v > best) { best = v; p = i; } }
+        // rows k and p change places (p == k: every element goes back where it was); the pivot row is uniform from here on
+        double rowp[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) {
+            const double rk = wave_bcast(a[j], k);
+            rowp[j] = wave_bcast(a[j], p);
+            a[j] = lane == k ? rowp[j] : (lane == p ? rk : a[j]);
+        }
+        {
+            const double yk = y[k];
+            double yp = yk;
+#pragma unroll
+            for (int i = k + 1; i < 6; ++i) if (p == i) { yp = y[i]; y[i] = yk; }
+            y[k] = yp;
+        }
+        const double m = a[k] / rowp[k];              // (the multiplier of this lane's row: kept by the rows below the pivot)
+        if (lane > k) {
+            a[k] = m;
+#pragma unroll
+            for (int j = k + 1; j < 6; ++j) a[j] -= m * rowp[j];
+        }
+#pragma unroll
+        for (int i = k + 1; i < 6; ++i) y[i] -= wave_bcast(m, i) * y[k];
+    }
+#pragma unroll
+    for (int i = 5; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int j = i + 1; j < 6; ++j) s -= wave_bcast(a[j], i) * y[j];
+        y[i] = s / wave_bcast(a[i], i);
+    }
+}
+
 // ---------------------------------------------------------------- Levenberg-Marquardt (Ceres trust-region semantics)
 // Bodies of the LM begin / step, run by ONE thread after the record has been summed into LDS. They are device functions so
 // that both the stand-alone single-workgroup kernels (solver.hip: multi-GPU, tracker, good-feature paths) and the last-arriving
@@ -836,7 +895,8 @@ __device__ __forceinline__ void lm_regs_store(const LmRegs &R, const double (&ca
 
 // lm_step_body on a wavefront. ce: the summed record at the candidate pose (LDS). All 64 lanes, converged. x_out / done_out: the state's pose and `done`
 // flag as this call leaves them (uniform; what a publication that follows needs, without reading back what other lanes have just stored).
-__device__ __forceinline__ void lm_step_body_wave(const double *ce, SolverState *S, int max_it, double (&x_out)[7], int &done_out)
+// accepted (nullable): set when the step was accepted -- the record at the state's pose is then `ce`, and S->ne otherwise (what a covariance publication inverts).
+__device__ __forceinline__ void lm_step_body_wave(const double *ce, SolverState *S, int max_it, double (&x_out)[7], int &done_out, bool *accepted = nullptr)
 {
     const int lane = threadIdx.x & 63;
     LmRegs R;
@@ -862,6 +922,7 @@ __device__ __forceinline__ void lm_step_body_wave(const double *ce, SolverState 
             for (int i = 0; i < 7; ++i) R.x[i] = cand[i];
             if (lane < 7) S->x[lane] = lane == 0 ? cand[0] : (lane == 1 ? cand[1] : (lane == 2 ? cand[2] : (lane == 3 ? cand[3] : (lane == 4 ? cand[4] : (lane == 5 ? cand[5] : cand[6])))));
             if (lane < NE_STRIDE) S->ne[lane] = ce[lane];
+            if (accepted) *accepted = true;
 #pragma unroll
             for (int i = 0; i < 6; ++i) R.g[i] = ce[NE_G + i];
             ne_now = ce;                               // same values; LDS, and no wait for the stores above

@@ -1600,20 +1600,38 @@ inline void setVoxelMemberOrderMode(Device &dev, int mode) { dev.check(mlh_set_v
 // ------------------------------------------------------------------ scan2MapOptimization() (gf_method "wo_gf")
 struct Scan2MapReport {
     std::vector<mlh_iter_stat> outer;   // one per outer iteration: matched counts, H, eigenvalues, LM iterations, costs
+    double cov_trace = 0.0;             // trace of cov_mapping as stored in pose_wmap_curr.cov_ (cpp:612)
 };
+
+namespace detail {
+// cov_mapping of the scan2map solve the context collected last (cpp:600-622): H^-1 from mlh_scan2map_cov with with_ua_flag -- zero while the mapper holds at most
+// 10 keyframes (cpp:607-608; n_keyframes < 0: no count given, H^-1) -- and zero without it (cpp:621). The solve must have carried MLH_FLAG_POSE_COV.
+inline void cov_mapping(Device &dev, bool with_ua_flag, int n_keyframes, double cov[36])
+{
+    for (int i = 0; i < 36; ++i) cov[i] = 0.0;
+    if (!with_ua_flag) return;
+    double h_inv[36];
+    dev.check(mlh_scan2map_cov(dev.ctx(), h_inv, nullptr));
+    if (n_keyframes >= 0 && n_keyframes <= 10) return;
+    for (int i = 0; i < 36; ++i) cov[i] = h_inv[i];
+}
+}  // namespace detail
 
 // Replaces the body of scan2MapOptimization (lidar_mapper_keyframe.cpp:423-639): index build for both maps, max_iter x
 // { match all features, evalHessian + evalDegenracy, Levenberg-Marquardt with Ceres' trust-region semantics }, all on the GPU.
-// pose_wmap_curr: the stand-in Pose or the reference's own (Eigen members; its T_ is refreshed through update()).
+// pose_wmap_curr: the stand-in Pose or the reference's own (Eigen members; its T_ is refreshed through update()). Its cov_ is written as cpp:600-622 and 632 leave
+// it: with with_ua_flag the inverse of evalHessian at the returned pose (delivered by the solve itself: MLH_FLAG_POSE_COV) -- zero while n_keyframes, the mapper's
+// pose_keyframes_6d.size() at this call, is at most 10 (-1: no count given, the inverse) --, zero without the flag.
 template <typename PoseT>
 inline void scan2MapOptimization(Device &dev, const PointICovCloud &laser_cloud_surf_from_map_cov_ds, const PointICovCloud &laser_cloud_corner_from_map_cov_ds,
                                  const PointICovCloud &laser_cloud_surf_cov, const PointICovCloud &laser_cloud_corner_cov, PoseT &pose_wmap_curr,
-                                 bool with_ua_flag, Scan2MapReport *report = nullptr, int max_iter = 2)
+                                 bool with_ua_flag, Scan2MapReport *report = nullptr, int max_iter = 2, int n_keyframes = -1)
 {
     const Params &P = params();
     if (!(laser_cloud_surf_from_map_cov_ds.size() > 50 && laser_cloud_corner_from_map_cov_ds.size() > 10)) {   // cpp:429
         const double zero[36] = {0};
         detail::pose_cov_set(pose_wmap_curr, zero);
+        if (report) report->cov_trace = 0.0;
         return;
     }
     MapIndex<PointIWithCov> kdtree_surf_from_map(dev, MLH_SURF), kdtree_corner_from_map(dev, MLH_CORNER);
@@ -1624,13 +1642,20 @@ inline void scan2MapOptimization(Device &dev, const PointICovCloud &laser_cloud_
     mlh_solver_opts o;
     mlh_solver_opts_default(&o);
     o.min_match_sq_dis = P.MIN_MATCH_SQ_DIS; o.min_plane_dis = P.MIN_PLANE_DIS; o.huber_delta = P.HUBER_DELTA; o.map_eig_thre = P.MAP_EIG_THRE;
-    o.cov_measurement_trace = P.COV_MEASUREMENT_TRACE; o.flags = with_ua_flag ? MLH_FLAG_WITH_UA : 0u; o.max_outer = max_iter;
+    o.cov_measurement_trace = P.COV_MEASUREMENT_TRACE; o.flags = with_ua_flag ? (MLH_FLAG_WITH_UA | MLH_FLAG_POSE_COV) : 0u; o.max_outer = max_iter;
     double pose[7];
     detail::pose_to_param(pose_wmap_curr, pose);
     std::vector<mlh_iter_stat> stats(max_iter);
     dev.check(mlh_scan2map(dev.ctx(), pose, &o, stats.data()));
     detail::pose_from_param(pose_wmap_curr, pose);
-    if (report) report->outer = stats;
+    double cov[36];
+    detail::cov_mapping(dev, with_ua_flag, n_keyframes, cov);
+    detail::pose_cov_set(pose_wmap_curr, cov);
+    if (report) {
+        report->outer = stats;
+        report->cov_trace = 0.0;
+        for (int i = 0; i < 6; ++i) report->cov_trace += cov[i * 7];
+    }
 }
 
 // The feature-cloud "message" between an estimator-side Device and a mapper-side Device on the same GPU (the reference's nodes exchange host clouds over ROS:
@@ -1648,12 +1673,13 @@ inline void handOverFeatures(Device &to, Device &from)
 // in flight; poses come back in submission order.
 class FramePipeline {
 public:
-    explicit FramePipeline(Device &dev, int gn_iters = 5, bool with_ua_flag = false) : dev_(dev), iters_(gn_iters)
+    explicit FramePipeline(Device &dev, int gn_iters = 5, bool with_ua_flag = false) : dev_(dev), iters_(gn_iters), with_ua_(with_ua_flag)
     {
         const Params &P = params();
         mlh_solver_opts_default(&o_);
         o_.min_match_sq_dis = P.MIN_MATCH_SQ_DIS; o_.min_plane_dis = P.MIN_PLANE_DIS; o_.huber_delta = P.HUBER_DELTA; o_.map_eig_thre = P.MAP_EIG_THRE;
-        o_.cov_measurement_trace = P.COV_MEASUREMENT_TRACE; o_.flags = with_ua_flag ? MLH_FLAG_WITH_UA : 0u;
+        // (the covariance flag means something to the scan2map submissions only: useScan2Map)
+        o_.cov_measurement_trace = P.COV_MEASUREMENT_TRACE; o_.flags = with_ua_flag ? (MLH_FLAG_WITH_UA | MLH_FLAG_POSE_COV) : 0u;
     }
     // kdtree_*_from_map->setInputCloud (cpp:433-434) for the frame about to be submitted; overlapped with the solve in flight when there is one
     void setInputClouds(const PointICovCloud &surf_map, const PointICovCloud &corner_map)
@@ -1696,7 +1722,11 @@ public:
     // with scan2MapOptimization(...) on its inputs (it overflowed the look-ahead with a younger frame chained behind it); 3 = the frame was chained behind a frame
     // that ended with 1 / 3 (it began from an unfinished pose): resubmit it after the predecessor has been solved.
     void useScan2Map(bool on, int lm_lookahead = 0) { scan2map_ = on; lm_lookahead_ = lm_lookahead; }
+    // the mapper's pose_keyframes_6d.size() when the frame collected next was solved (cpp:607-608: cov_mapping is zero up to 10 keyframes); -1: no count, H^-1
+    void setKeyframeCount(int n_keyframes) { n_keyframes_ = n_keyframes; }
     int lastStatus() const { return last_status_; }
+    // the pose with cov_ as scan2MapOptimization leaves it (the rule of scan2MapOptimization(...) above; a Gauss-Newton frame, and a pose that is not a result --
+    // status 1 / 3 --, carry zero)
     Pose collect()
     {
         double p[7];
@@ -1706,6 +1736,9 @@ public:
         --in_flight_;
         Pose r;
         r.fromParam(p);
+        double cov[36] = {0};
+        if (scan2map_ && (last_status_ == 0 || last_status_ == 2)) detail::cov_mapping(dev_, with_ua_, n_keyframes_, cov);
+        detail::pose_cov_set(r, cov);
         return r;
     }
     int inFlight() const { return in_flight_; }
@@ -1713,8 +1746,8 @@ private:
     Device &dev_;
     mlh_solver_opts o_;
     int iters_, in_flight_ = 0;
-    bool scan2map_ = false;
-    int lm_lookahead_ = 0, last_status_ = 0;
+    bool with_ua_ = false, scan2map_ = false;
+    int lm_lookahead_ = 0, last_status_ = 0, n_keyframes_ = -1;
 };
 
 // ------------------------------------------------------------------ what makes staging beside the solve legal, as code
@@ -1914,6 +1947,9 @@ public:
     // staged by device pointer (km must live on `dev` and use the same KeyframePolicy)
     PipelinedMapper(Device &dev, KeyframeMap &km, int gn_iters = 5, bool with_ua_flag = false)
         : pipe_(dev, gn_iters, with_ua_flag), kf_(km.policy()), km_(&km) {}
+    // the frames solved by scan2MapOptimization (FramePipeline::useScan2Map); with with_ua_flag every pose then carries cov_mapping, and saveKeyframe stores it
+    void useScan2Map(bool on, int lm_lookahead = 0) { pipe_.useScan2Map(on, lm_lookahead); }
+    void setOnKeyframe(OnKeyframe on_keyframe) { on_keyframe_ = std::move(on_keyframe); }
     void setInitialMap(const PointICovCloud &surf_map, const PointICovCloud &corner_map) { surf_map_ = surf_map; corner_map_ = corner_map; }
     void setInitialPose(const Pose &pose_wmap_curr, const Pose &pose_wodom_curr) { wmap_wodom_ = poseMul(pose_wmap_curr, poseInverse(pose_wodom_curr)); }
     struct Counters { int frames = 0, overlapped = 0, waited = 0, redone = 0, keyframes = 0; } counters;
@@ -1937,12 +1973,12 @@ public:
             stageMaps();
             pipe_.setFeatures(surf_cov, corner_cov);
             pipe_.submitChained(wodom_in_flight_, pose_wodom_curr);
-            pose_prev = pipe_.collect();                                      // frame k - 1
+            pose_prev = collectFrame();                                      // frame k - 1
             const bool saved = closeFrame(pose_prev);
             if (saved) {
                 // wrong prediction (the result crossed the keyframe threshold the prior stayed under): frame k was matched against a map without keyframe k - 1.
                 // Its solve is allowed to finish and dropped; the map is rebuilt as the reference would have, and frame k is solved again from the host-side prior.
-                (void)pipe_.collect();
+                (void)collectFrame();
                 ++counters.redone;
                 const Pose prior_k = poseMul(wmap_wodom_, pose_wodom_curr);
                 rebuild(prior_k);
@@ -1955,7 +1991,7 @@ public:
             }
         } else {
             // frame k - 1 is expected to be saved as a keyframe: frame k's map contains its cloud at its solved pose -- nothing to stage before that pose is known
-            pose_prev = pipe_.collect();
+            pose_prev = collectFrame();
             ++counters.waited;
             const bool saved = closeFrame(pose_prev);
             const Pose prior_k = poseMul(wmap_wodom_, pose_wodom_curr);
@@ -1970,7 +2006,7 @@ public:
     }
     Pose finish()
     {
-        Pose p = pipe_.collect();
+        Pose p = collectFrame();
         in_flight_ = false;
         closeFrame(p, true);
         return p;
@@ -1978,6 +2014,12 @@ public:
     const PointICovCloud &surfMap() const { return surf_map_; }
     const PointICovCloud &cornerMap() const { return corner_map_; }
 private:
+    // the oldest frame's pose; the keyframes saved so far are the mapper's pose_keyframes_6d when that frame's scan2MapOptimization ran (its own saveKeyframe follows)
+    Pose collectFrame()
+    {
+        pipe_.setKeyframeCount(int(kf_.pose_keyframes_3d.size()));
+        return pipe_.collect();
+    }
     // transformUpdate + saveKeyframe for the frame whose pose just came back (cpp:1076-1079)
     bool closeFrame(const Pose &pose_wmap_curr, bool in_flight_frame = false)
     {
