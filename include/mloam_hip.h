@@ -643,7 +643,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
  * (lidar_scan_factor.hpp:24-64, 236-279) under HuberLoss(0.1), ceres::Solve with max_num_iterations = 4, two rounds.
  * kind MLH_CORNER: previous = "corner_points_less_sharp", current = "corner_points_sharp";
  * kind MLH_SURF:   previous = "surf_points_less_flat",    current = "surf_points_flat"   (lidar_tracker.cpp:30-38).
- * Previous-frame clouds must be ordered by ring id = int(intensity) (as extractCloud emits them); 0 <= id < 255. */
+ * Previous-frame clouds must be ordered by ring id = int(intensity) (as extractCloud emits them); 0 <= id <= 255. */
 typedef struct mlh_track_opts {
     float distance_sq_threshold;     /* DISTANCE_SQ_THRESHOLD, config distance_sq_threshold (25) */
     float nearby_scan;               /* NEARBY_SCAN, config nearby_scan (2.5) */

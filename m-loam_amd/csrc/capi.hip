@@ -2207,7 +2207,7 @@ static int track_build_prev(mlh_ctx *ctx, int kind_mask, const int *host_bad)
     for (int k = 0; k < 2; ++k)
         if ((kind_mask & (1 << k)) && host_bad[k]) {
             ctx->track.grid[k].built = false;
-            return fail(ctx, MLH_ERR_INVALID, "previous-frame cloud must be ordered by ring id (int(intensity) non-decreasing, 0 <= id < 255)");
+            return fail(ctx, MLH_ERR_INVALID, "previous-frame cloud must be ordered by ring id (int(intensity) non-decreasing, 0 <= id <= 255)");
         }
     return MLH_OK;
 }

@@ -383,7 +383,8 @@ struct OdomSet {   // staged LidarPureOdom factor table (odom.hip)
 
 constexpr int FUSE_BLOCKS = 64;           // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
-constexpr int TRACK_RING_SLOTS = 258;   // ring ids 0..255 (+ the slots the walks' upper bound can reach)
+constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
+constexpr int TRACK_RING_SLOTS = TRACK_MAX_RING + 3;   // ring_start[0 .. 256] + the slot the walks' upper bound is clamped to
 struct TrackSet {   // scan-to-scan odometry (track.hip): previous frame's clouds + indices, current frame's features
     MapGrid grid[2];
     DevBuf ring[2], ring_start[2], walk[2], cur[2], corr[2];

@@ -43,6 +43,7 @@ constexpr unsigned BACKWARD_BIT = 0x40000000u;
 
 struct TrackKind {
     GridDev grid;            // previous frame's cloud, indexed
+    float cell_h;            // cell edge of that index (a quarter of the acceptance radius it was built for): each kind has its own
     const float4 *walk;      // the same cloud in its original (ring-ordered) order: {x, y, z, ring id as float}
     const int *ring;         // ring id of every previous-frame point
     const int *ring_start;   // ring_start[r] = first index whose ring id is >= r   (0 .. max_ring + 1 valid, beyond: n)
@@ -66,7 +67,6 @@ struct TrackParamsDev {
     int use_init;
     double init_pose[7];
     float dist_sq_thr;
-    float cell_h;            // cell edge of the previous-frame indices (a quarter of the acceptance radius)
     int shells;              // cube half-width (in cells) that covers the acceptance radius
     int nearby_floor;        // floor(NEARBY_SCAN): rings id - nf .. id + nf take part in the walks
     double huber_delta;
@@ -212,7 +212,7 @@ __global__ __launch_bounds__(TPB) void track_match_kernel(TrackParamsDev P)
     const d3 r = qrot(q, d3{double(fp.x), double(fp.y), double(fp.z)});
     const float sx = float(r.x + t.x), sy = float(r.y + t.y), sz = float(r.z + t.z);
     unsigned long long nn[1];
-    nn[0] = nearest_in_radius(K.grid, P.cell_h, P.shells, sx, sy, sz, gl, s_run + grp * 36);
+    nn[0] = nearest_in_radius(K.grid, K.cell_h, P.shells, sx, sy, sz, gl, s_run + grp * 36);
     MLH_TSTAGE(1);
     bool valid = false;
     float c6[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -523,7 +523,7 @@ __global__ __launch_bounds__(TPB) void track_lm_loop_kernel(TrackParamsDev P)
 
 // ring ids + ring_start table of a previous-frame cloud; flags non-monotone / out-of-range ring ids
 __global__ __launch_bounds__(256) void track_rings_kernel(const unsigned char *src, int stride, int n, int intensity_off, int *ring, int *ring_start,
-                                                          int n_slots, int *bad)
+                                                          int max_ring, int *bad)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
@@ -532,7 +532,7 @@ __global__ __launch_bounds__(256) void track_rings_kernel(const unsigned char *s
     ring[i] = r;
     // the previous point's id bounds the loop below: it is validated like this point's own (a malformed id there would start the
     // loop at a negative slot, or make it very long)
-    if (r < 0 || r >= n_slots - 1 || r < prev || prev < -1 || prev >= n_slots - 1) { atomicOr(bad, 1); return; }
+    if (r < 0 || r > max_ring || r < prev || prev < -1 || prev > max_ring) { atomicOr(bad, 1); return; }
     for (int k = prev + 1; k <= r; ++k) ring_start[k] = i;
 }
 
@@ -553,7 +553,7 @@ int track_set_prev_rings(mlh_ctx *ctx, int kind, const unsigned char *d_src, int
     int *bad = T.ring_start[kind].as<int>() + TRACK_RING_SLOTS;
     MLH_LAUNCH(fill_int_kernel, dim3((TRACK_RING_SLOTS + 1 + 255) / 256), dim3(256), 0, ctx->stream, T.ring_start[kind].as<int>(), TRACK_RING_SLOTS, n);   // (also clears the flag)
     MLH_LAUNCH(track_rings_kernel, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, d_src, stride, n, intensity_off, T.ring[kind].as<int>(),
-                       T.ring_start[kind].as<int>(), TRACK_RING_SLOTS, bad);
+                       T.ring_start[kind].as<int>(), TRACK_MAX_RING, bad);
     MLH_HIP(ctx, hipGetLastError());
     MLH_HIP(ctx, hipMemcpyAsync(host_bad, bad, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     return MLH_OK;
@@ -568,9 +568,8 @@ static int fill_track_params(mlh_ctx *ctx, int kind_mask, const TrackArgs &a, Tr
         if (!(kind_mask & (1 << k))) continue;
         if (!T.grid[k].built || T.m[k] <= 0) return fail(ctx, MLH_ERR_STATE, "track_set_prev / track_set_cur have not been called for this kind");
         if (a.dist_sq_thr > 0.f && std::sqrt(a.dist_sq_thr) > T.grid[k].h * float(TRACK_SHELLS)) return fail(ctx, MLH_ERR_INVALID, "distance_sq_threshold exceeds the value the index was built for");
-        P.cell_h = T.grid[k].h;
         TrackKind &K = P.k[k];
-        K.grid = T.grid[k].dev();
+        K.grid = T.grid[k].dev(); K.cell_h = T.grid[k].h;
         K.walk = T.walk[k].as<float4>(); K.ring = T.ring[k].as<int>(); K.ring_start = T.ring_start[k].as<int>(); K.n_ring_slots = TRACK_RING_SLOTS;
         K.cur = T.cur[k].as<float4>(); K.corr = T.corr[k].as<Corr>(); K.m = T.m[k];
         K.tiles_a = (K.m + TRK_FPB - 1) / TRK_FPB; K.tiles_b = (K.m + TPB - 1) / TPB;
