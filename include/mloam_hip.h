@@ -471,6 +471,14 @@ int mlh_linearize(mlh_ctx *ctx, int kind, const double pose[7], uint32_t flags, 
 /* the correspondences of `kind` currently live on the device (after mlh_match_linearize, or -- only the selected ones -- after
  * mlh_good_feature_matching): valid[m], coeffs[m x 6] (PointPlaneFeature::coeffs_: plane n, d / line X1, X2; zeros where invalid) */
 int mlh_match_coeffs(mlh_ctx *ctx, int kind, uint8_t *valid, double *coeffs, int32_t *n_valid);
+/* Test and diagnosis aid, no reference counterpart: the neighbour records the most recent correspondence launch of `kind` left on the device (after
+ * mlh_match_linearize, mlh_gn_solve*, mlh_scan2map*: the LAST iteration's search), copied as they stand. records_out (HOST, may be NULL to ask for the stride
+ * only): m x stride records of four floats {x, y, z, squared distance} -- the K nearest map points of feature slot f at records_out[(f * stride + t) * 4],
+ * t = 0 .. K - 1 ascending by (squared distance, map index), {0, 0, 0, +inf} where the search left none (a feature with fewer than K points in its 27 cells has
+ * none at all). *k_stride_out (may be NULL) <- stride, the records per feature slot (5, or 10 once a launch asked for K = 10). Slots t >= K of a feature, the
+ * padding slots between pose blocks and the features this rank does not own hold whatever was there before. Waits for the context's stream, then copies:
+ * no launch, nothing on a hot path. MLH_ERR_STATE when no correspondence launch of this kind has run since its map or features were last staged. */
+int mlh_match_neighbours(mlh_ctx *ctx, int kind, float *records_out, int32_t *k_stride_out);
 
 /* ---------------------------------------------------------------- (a13) good-feature selection
  * replaces ActiveFeatureSelection::goodFeatureMatching (estimator/src/lidarMapper/lidar_mapper.h:229-573).

@@ -186,6 +186,7 @@ def load_library():
     lib.mlh_gn_solve_blocks.argtypes = [vp, vp, ci, C.POINTER(SolverOpts), C.POINTER(BlockOpts), vp]
     lib.mlh_match_linearize.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, cd, cd, vp, vp, vp, vp, vp, vp, C.POINTER(cd), C.POINTER(C.c_int32)]
     lib.mlh_match_coeffs.argtypes = [vp, ci, vp, vp, C.POINTER(C.c_int32)]
+    lib.mlh_match_neighbours.argtypes = [vp, ci, vp, C.POINTER(C.c_int32)]
     lib.mlh_linearize.argtypes = [vp, ci, vp, C.c_uint32, cd, cd, vp, vp, vp, vp, C.POINTER(cd), C.POINTER(C.c_int32)]
     lib.mlh_good_feature_matching.argtypes = [vp, ci, vp, ci, cd, C.c_uint64, cf, cf, vp, C.POINTER(C.c_int32), vp, vp]
     lib.mlh_solver_opts_default.argtypes = [C.POINTER(SolverOpts)]
@@ -216,7 +217,7 @@ EXPORTED_SYMBOLS = [
     "mlh_point_uncertainty", "mlh_downsample_current_scan", "mlh_voxel_filter", "mlh_pure_odom_set", "mlh_pure_odom_evaluate", "mlh_pure_odom_normal_eq", "mlh_track_opts_default", "mlh_track_set_prev", "mlh_track_set_cur",
     "mlh_track_set_from_scan", "mlh_downsample_current_scan_pair", "mlh_downsample_scan2map", "mlh_voxel_grid", "mlh_transform_point_cloud", "mlh_transform_to_end", "mlh_scan_undistort", "mlh_fuse_reset", "mlh_fuse_add_scan", "mlh_fuse_add_scan_from", "mlh_fuse_add_rings", "mlh_fused_cloud", "mlh_track_match", "mlh_track_cloud", "mlh_cloud_uct_associate_to_map", "mlh_compound_pose_with_cov",
     "mlh_map_set", "mlh_map_set_pair", "mlh_map_set_pair_overlapped", "mlh_map_rebuild", "mlh_map_info", "mlh_set_voxel_member_order", "mlh_debug_bad_launch", "mlh_set_extract_tie_order", "mlh_set_gn_schedule", "mlh_std_sort_permutation", "mlh_pure_odom_begin", "mlh_pure_odom_add_matches", "mlh_pure_odom_add_matches_gf", "mlh_pure_odom_gn_solve", "mlh_knn", "mlh_features_set", "mlh_features_set_block", "mlh_gn_solve_blocks",
-    "mlh_match_linearize", "mlh_match_coeffs", "mlh_linearize", "mlh_good_feature_matching", "mlh_solver_opts_default", "mlh_gn_solve", "mlh_gn_solve_begin", "mlh_gn_solve_begin_chained", "mlh_gn_solve_end", "mlh_features_copy", "mlh_scan2map", "mlh_scan2map_begin", "mlh_scan2map_begin_chained", "mlh_scan2map_end", "mlh_scan2map_cov",
+    "mlh_match_linearize", "mlh_match_coeffs", "mlh_match_neighbours", "mlh_linearize", "mlh_good_feature_matching", "mlh_solver_opts_default", "mlh_gn_solve", "mlh_gn_solve_begin", "mlh_gn_solve_begin_chained", "mlh_gn_solve_end", "mlh_features_copy", "mlh_scan2map", "mlh_scan2map_begin", "mlh_scan2map_begin_chained", "mlh_scan2map_end", "mlh_scan2map_cov",
     "mlh_shard_set", "mlh_shard_set_features", "mlh_comm_unique_id", "mlh_comm_init", "mlh_p2p_mailbox", "mlh_p2p_comm_init", "mlh_allreduce_f64",
     "mlh_pose_plus", "mlh_eval_degeneracy",
     "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
@@ -876,6 +877,14 @@ class Context:
                                               cov_measurement_trace, _p(valid), _p(coeffs), _p(r), _p(J), _p(H), _p(g),
                                               C.byref(cost), C.byref(cnt)))
         return dict(valid=valid, coeffs=coeffs, r=r, J=J, H=H, g=g, cost=cost.value, count=cnt.value)
+
+    def match_neighbours(self, kind):
+        """mlh_match_neighbours: the neighbour records of the last correspondence launch of `kind` -> (m, stride, 4) float32 [x y z squared distance]"""
+        stride = C.c_int32(0)
+        self._ck(self.lib.mlh_match_neighbours(self.h, kind, None, C.byref(stride)))
+        rec = np.zeros((self._m[kind], stride.value, 4), np.float32)
+        self._ck(self.lib.mlh_match_neighbours(self.h, kind, _p(rec), C.byref(stride)))
+        return rec
 
     def linearize(self, kind, pose, flags=0, huber_delta=0.1, cov_measurement_trace=0.0075, dense=True):
         m = self._m[kind]

@@ -1338,6 +1338,19 @@ int mlh_match_coeffs(mlh_ctx *ctx, int kind, uint8_t *valid, double *coeffs, int
     return MLH_OK;
 }
 
+int mlh_match_neighbours(mlh_ctx *ctx, int kind, float *records_out, int32_t *k_stride_out)
+{
+    if (!ctx || kind < 0 || kind > 1) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    FeatSet &f = ctx->feat[kind];
+    if (!f.matched || f.m <= 0 || !f.nbr.p) return fail(ctx, MLH_ERR_STATE, "no neighbour records of this kind on the device (match first)");
+    if (k_stride_out) *k_stride_out = f.nbr_stride;
+    if (!records_out) return MLH_OK;
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    MLH_HIP(ctx, hipMemcpy(records_out, f.nbr.p, sizeof(float4) * size_t(f.nbr_stride) * size_t(f.m), hipMemcpyDeviceToHost));
+    return MLH_OK;
+}
+
 int mlh_match_linearize(mlh_ctx *ctx, int kind, const double pose[7], int k_neigh, uint32_t flags,
                         float min_match_sq_dis, float min_plane_dis, double huber_delta, double cov_measurement_trace,
                         uint8_t *valid, double *coeffs, double *r, double *J,

@@ -369,28 +369,38 @@ static int bounds_finish(mlh_ctx *ctx, MapGrid &g, const int *hp, float min_matc
         for (int d = 0; d < 3; ++d) { hb[d] = std::min(hb[d], hp[blk * 6 + d]); hb[3 + d] = std::max(hb[3 + d], hp[blk * 6 + 3 + d]); }
     float mn[3], mx[3];
     for (int d = 0; d < 3; ++d) { mn[d] = key_to_float(hb[d]); mx[d] = key_to_float(hb[3 + d]); }
+    // a geometry becomes the kind's (and reusable by the next staging call) only once every check has passed and every buffer for it is sized: a refusal
+    // leaves the kind without a box -- a "valid" box whose cell count does not fit an int, with cell arrays sized for another, would be built into by the
+    // next cloud that fits it (make_job narrows ncell, the count pass adds into cell_start[c + 1] far outside the allocation)
+    g.geom_valid = false;
+    g.built = false;
     for (int d = 0; d < 3; ++d)
         if (!std::isfinite(mn[d]) || !std::isfinite(mx[d])) return fail(ctx, MLH_ERR_INVALID, "map cloud has non-finite coordinates");
-    g.h = std::sqrt(min_match_sq_dis) * 1.001f;
-    g.inv_h = 1.0f / g.h;
+    const float h = std::sqrt(min_match_sq_dis) * 1.001f, inv_h = 1.0f / h;
     // the box is laid GRID_MARGIN cells wider than the cloud (one cell in z): the next frames' local maps -- the same keyframe window
     // moved a little -- then fit the geometry already set up, and mlh_map_set skips this host round trip (map_stage_and_build)
-    g.ox = mn[0] - GRID_MARGIN_XY * g.h; g.oy = mn[1] - GRID_MARGIN_XY * g.h; g.oz = mn[2] - GRID_MARGIN_Z * g.h;
-    g.nx = int(std::floor((mx[0] + GRID_MARGIN_XY * g.h - g.ox) * g.inv_h)) + 1;
-    g.ny = int(std::floor((mx[1] + GRID_MARGIN_XY * g.h - g.oy) * g.inv_h)) + 1;
-    g.nz = int(std::floor((mx[2] + GRID_MARGIN_Z * g.h - g.oz) * g.inv_h)) + 1;
-    g.geom_sq_dis = min_match_sq_dis;
-    g.geom_valid = true;
-    g.ncell = (long long)g.nx * g.ny * g.nz;
-    if (g.ncell >= (1ll << 31) - 2 * SCAN_CHUNK) return fail(ctx, MLH_ERR_UNSUPPORTED, "map extent needs more than 2^31 cells");
-    const int nb = int((g.ncell + SCAN_CHUNK) / SCAN_CHUNK);   // covers ncell + 1 entries
+    const float ox = mn[0] - GRID_MARGIN_XY * h, oy = mn[1] - GRID_MARGIN_XY * h, oz = mn[2] - GRID_MARGIN_Z * h;
+    // (the counts as doubles first: a cloud with a point tens of kilometres out gives a quotient beyond int, whose conversion is undefined)
+    const double fnx = std::floor((mx[0] + GRID_MARGIN_XY * h - ox) * inv_h) + 1.0, fny = std::floor((mx[1] + GRID_MARGIN_XY * h - oy) * inv_h) + 1.0,
+                 fnz = std::floor((mx[2] + GRID_MARGIN_Z * h - oz) * inv_h) + 1.0;
+    const double cell_limit = double((1ll << 31) - 2 * SCAN_CHUNK);
+    if (!(fnx >= 1.0 && fny >= 1.0 && fnz >= 1.0) || !(fnx * fny * fnz < cell_limit)) return fail(ctx, MLH_ERR_UNSUPPORTED, "map extent needs more than 2^31 cells");
+    const int nx = int(fnx), ny = int(fny), nz = int(fnz);
+    const long long ncell = (long long)nx * ny * nz;
+    const int nb = int((ncell + SCAN_CHUNK) / SCAN_CHUNK);   // covers ncell + 1 entries
     MLH_HIP(ctx, g.sorted.ensure(sizeof(float4) * size_t(n)));
-    MLH_HIP(ctx, g.cell_start.ensure(sizeof(int) * size_t(g.ncell + 16)));   // 3 ints of lead-in (alignment of cell_start + 1) + padded tail
-    MLH_HIP(ctx, g.cell_fill.ensure(sizeof(int) * size_t(g.ncell + 16)));    // the twin (cleared by one build for the next)
-    MLH_HIP(ctx, g.cell_id.ensure(sizeof(int) * size_t(n)));                 // per-point rank inside its cell
+    MLH_HIP(ctx, g.cell_start.ensure(sizeof(int) * size_t(ncell + 16)));   // 3 ints of lead-in (alignment of cell_start + 1) + padded tail
+    MLH_HIP(ctx, g.cell_fill.ensure(sizeof(int) * size_t(ncell + 16)));    // the twin (cleared by one build for the next)
+    MLH_HIP(ctx, g.cell_id.ensure(sizeof(int) * size_t(n)));               // per-point rank inside its cell
+    MLH_HIP(ctx, g.block_sums.ensure(sizeof(int) * size_t(nb + 1)));
+    g.h = h; g.inv_h = inv_h;
+    g.ox = ox; g.oy = oy; g.oz = oz;
+    g.nx = nx; g.ny = ny; g.nz = nz;
+    g.ncell = ncell;
     g.cur = 0;
     g.twin_clean = false;
-    MLH_HIP(ctx, g.block_sums.ensure(sizeof(int) * size_t(nb + 1)));
+    g.geom_sq_dis = min_match_sq_dis;
+    g.geom_valid = true;
     return MLH_OK;
 }
 
@@ -429,6 +439,9 @@ static int grid_build_grids_packed(mlh_ctx *ctx, MapGrid **grids, int n_grids, b
     int nj = 0;
     for (int k = 0; k < n_grids && k < 2; ++k)
         if (grids[k]->n <= 0 || !grids[k]->raw.p) return fail(ctx, MLH_ERR_STATE, "no points staged for this index");
+    // a build without a bounds pass goes into the box the kind already has: after a refused staging call there is none
+    for (int k = 0; k < n_grids && k < 2; ++k)
+        if (!recompute_bounds && !grids[k]->geom_valid) return fail(ctx, MLH_ERR_STATE, "this index has no grid box (the last staging call for it failed)");
     if (recompute_bounds) {
         // the bounding boxes of all point sets in ONE host round trip (which also completes whatever the caller enqueued before)
         int hp[2][6 * BOUNDS_BLOCKS];

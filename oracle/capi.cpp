@@ -86,6 +86,14 @@ int orc_knn(void *h, const float *queries, int nq, int k, int *idx, float *d2)
     return 0;
 }
 
+// pointAssociateToMap over a cloud (the map-frame position every map match searches from): out[n * 3]
+int orc_associate_to_map(const float *pts, int stride, int n, const double *pose7, float *out)
+{
+    Pose pose = pose_from_param(pose7);
+    for (int i = 0; i < n; ++i) point_associate_to_map(pts + size_t(i) * stride, out + size_t(i) * 3, pose);
+    return 0;
+}
+
 // dense per-feature match: valid[n], coeffs[n*6]
 int orc_match(void *h, char type, const float *feats, int stride, int n, const double *pose7, int n_neigh, int check_fov,
               float min_match_sq_dis, float min_plane_dis, unsigned char *valid, double *coeffs)

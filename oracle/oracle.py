@@ -485,6 +485,15 @@ class Map:
         return valid, coeffs
 
 
+def associate_to_map(points, pose7):
+    """pointAssociateToMap over a cloud: (n, >= 3) f32 -> (n, 3) f32, the positions the map matches search from (f64 rotation + translation, rounded to f32)"""
+    p = np.ascontiguousarray(points, np.float32)
+    out = np.zeros((p.shape[0], 3), np.float32)
+    pose = np.ascontiguousarray(pose7, np.float64)
+    lib().orc_associate_to_map(_ptr(p), p.shape[1], p.shape[0], _ptr(pose), _ptr(out))
+    return out
+
+
 def factor_eval(kind: str, point, coeff, cov_trace: float, pose7):
     point = np.ascontiguousarray(point, np.float64)
     coeff = np.ascontiguousarray(np.concatenate([np.asarray(coeff, np.float64), np.zeros(6)])[:6])
