@@ -378,6 +378,55 @@ int mlh_local_map_clear(mlh_ctx *ctx);
 int mlh_local_map_cloud(mlh_ctx *ctx, int kind, int filtered, const void **device_points, int32_t *n);
 int mlh_local_map_info(mlh_ctx *ctx, int32_t *n_keyframes, int32_t *n_cached, int64_t *store_bytes, int64_t *cache_bytes);
 
+/* ---------------------------------------------------------------- (f7) the global map on the device
+ * pubGlobalMap (lidar_mapper_keyframe.cpp:780-851, the map part: cpp:796-849) and saveGlobalMap (cpp:853-919, without the PCD writing): THE map, built in HBM
+ * from the keyframe store in one call instead of three calls and a host wait per keyframe.
+ * mlh_keyframe_attach_outlier: saveKeyframe's third cloud (laser_cloud_outlier_cov, cpp:673, 677, 681), attached to an already saved keyframe. `points` is what
+ *   downsampleCurrentScan left of the outlier cloud (cpp:366-368, 405-418: thinned at MAP_OUTLIER_RES, trace-gated); only xyz and the LiDAR id are kept.
+ *   MLH_ERR_INVALID for a key that does not exist or bad records (as mlh_keyframe_save), MLH_ERR_STATE when the keyframe already has an outlier cloud; n == 0
+ *   attaches nothing. A keyframe without one has an empty outlier cloud. The local map never reads it.
+ * mlh_global_map_assemble, in the reference's order:
+ *   - no keyframes (cpp:796): MLH_OK, all counts 0, *n_ids = 0;
+ *   - selection (cpp:804-810): radiusSearch(pose_cur.t_ as f32, kf_radius), nearest first, equal distances by index (d2 <= r * r in f32); kf_radius < 0: no
+ *     search, every keyframe in index order (saveGlobalMap, cpp:865-866). The hits, in that order, go through VoxelGridCovarianceMLOAM<PointI>(kf_res), plain
+ *     branch, with intensity = the KEYFRAME'S OWN INDEX (cpp:666, 808; not a cache position as in the local map). REPRODUCED: with the shipped values (kf_res
+ *     10, keyframes 1 m apart) many keyframes share a position voxel, and only each voxel's last member in std::sort order reaches the map.
+ *     NOT reproduced: saveGlobalMap pushes onto global_map_keyframes without clearing what a concurrent pubGlobalMap left there (cpp:865-866), which depends
+ *     on another thread's timing; kf_radius < 0 means a clean list. mlh_global_map_select is this step alone (host arithmetic, no context);
+ *   - association: every selected keyframe is transformed on every call (no cache; the reference has none here) with its own stored pose and cov_ and the
+ *     ext_poses / ext_covs of this call: cloudUCTAssociateToMap, the arithmetic of mlh_cloud_uct_associate_to_map bit for bit; points whose trace exceeds
+ *     trace_threshold are dropped with with_ua (cpp:1147-1148), order preserved. split 0: one cloud, per keyframe surf, corner, outlier (cpp:818-827);
+ *     split 1: cloud 0 = per keyframe surf, outlier, cloud 1 = per keyframe corner (cpp:872-882);
+ *   - one covariance filter per output cloud at `leaf` (cpp:839-842 / 896-901) through the context's voxel filter (mlh_set_voxel_member_order applies; a grid of
+ *     more than 2^31 cells returns the pre-filter cloud unchanged, as the reference does). The append order above decides the member order inside a voxel.
+ *   n_pre[2] / n_ds[2] <- the pre-filter and filtered lengths of the two clouds; kf_ids_out (may be NULL; capacity >= the number of keyframes) <- the selected
+ *   keyframes in append order, *n_ids (may be NULL) their number. MLH_ERR_INVALID on bad options (the finiteness rules of mlh_local_map_assemble; kf_radius may
+ *   be negative), with_ua without ext_covs, n_lidar outside 1..16, a radius search without pose_cur; MLH_ERR_NOMEM beyond the point limit of the keyframe cache.
+ *   Two host waits per call (one more when a buffer grows), one upload of all tables; the launches do not depend on the number of keyframes. It writes none of
+ *   the local map's state. Beside a solve submitted with mlh_*_begin the call is correct but enqueued behind the solve on the context's stream, and its waits
+ *   include the solve (as mlh_local_map_assemble). The context is not re-entrant: pubGlobalMap's own thread needs the caller's lock or a context of its own.
+ * mlh_global_map_cloud: cloud `which` (0 / 1), pre-filter (filtered = 0) or filtered (1): 48-byte PointIWithCov records in HBM as mlh_local_map_cloud; valid
+ *   until the next mlh_global_map_assemble / release / mlh_keyframes_reset.
+ * mlh_global_map_release frees the global clouds (mlh_keyframes_reset and mlh_destroy do too). */
+typedef struct mlh_global_map_opts {
+    float kf_radius;            /* GLOBALMAP_KF_RADIUS; < 0: no search, every keyframe in index order (saveGlobalMap, cpp:865-866) */
+    float kf_res;               /* leaf of down_size_filter_global_map_keyframes (10, cpp:1293), > 0 */
+    float leaf;                 /* MAP_SURF_RES (cpp:839) or 2 * MAP_SURF_RES (cpp:896), > 0 */
+    int32_t split;              /* 0: one cloud, per keyframe surf, corner, outlier (cpp:818-827); 1: cloud 0 = per keyframe surf, outlier; cloud 1 = corner (cpp:872-882) */
+    double trace_threshold;     /* TRACE_THRESHOLD_MAPPING */
+    int with_ua;
+    double cov_measurement[9];
+} mlh_global_map_opts;
+void mlh_global_map_opts_default(mlh_global_map_opts *o, int for_save);   /* 0: pubGlobalMap's values, 1: saveGlobalMap's */
+int mlh_keyframe_attach_outlier(mlh_ctx *ctx, int32_t key, const void *points, int n, int stride_bytes, int intensity_offset_bytes, int mem);
+int mlh_global_map_assemble(mlh_ctx *ctx, const double pose_cur[7] /* may be NULL when kf_radius < 0 */, const double *ext_poses, const double *ext_covs, int n_lidar,
+                            const mlh_global_map_opts *opts, int32_t n_pre[2], int32_t n_ds[2], int32_t *kf_ids_out, int32_t *n_ids);
+int mlh_global_map_cloud(mlh_ctx *ctx, int which, int filtered, const void **device_points, int32_t *n);
+int mlh_global_map_release(mlh_ctx *ctx);
+/* host arithmetic, no context: which keyframes the global map is made of, in the order their clouds are appended (ids_out: capacity >= n; center may be NULL
+ * when kf_radius < 0) */
+int mlh_global_map_select(const float *positions_xyz, int n, const float center[3], float kf_radius, float kf_res, int32_t *ids_out, int32_t *n_ids);
+
 /* ---------------------------------------------------------------- (a5) local map index
  * replaces pcl::KdTreeFLANN<PointT>::setInputCloud(cloud) as used at
  *   estimator/src/lidarMapper/lidar_mapper_keyframe.cpp:433-434 (and estimator.cpp:1095-1109, 1230-1233).

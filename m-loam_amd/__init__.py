@@ -58,6 +58,39 @@ def local_map_opts(surrounding_kf_radius=50.0, map_sur_kf_res=1.0, leaf_surf=0.4
     return o
 
 
+class GlobalMapOpts(C.Structure):
+    """mlh_global_map_opts: pubGlobalMap's / saveGlobalMap's parameters"""
+    _fields_ = [("kf_radius", C.c_float), ("kf_res", C.c_float), ("leaf", C.c_float), ("split", C.c_int32), ("trace_threshold", C.c_double),
+                ("with_ua", C.c_int), ("cov_measurement", C.c_double * 9)]
+
+
+def global_map_opts(for_save=False, **kw) -> GlobalMapOpts:
+    """mlh_global_map_opts_default (for_save: saveGlobalMap's values, else pubGlobalMap's), then the given fields"""
+    o = GlobalMapOpts()
+    load_library().mlh_global_map_opts_default(C.byref(o), int(bool(for_save)))
+    for k, v in kw.items():
+        if k == "cov_measurement":
+            for i, x in enumerate(np.ascontiguousarray(v, np.float64).reshape(9)):
+                o.cov_measurement[i] = float(x)
+        elif k == "with_ua":
+            o.with_ua = int(bool(v))
+        else:
+            setattr(o, k, v)
+    return o
+
+
+def global_map_select(positions_xyz, center, kf_radius, kf_res):
+    """mlh_global_map_select (host arithmetic): the keyframes the global map is made of, in the order their clouds are appended"""
+    pos = np.ascontiguousarray(positions_xyz, np.float32).reshape(-1, 3)
+    c = None if center is None else np.ascontiguousarray(center, np.float32).reshape(3)
+    ids = np.zeros(max(len(pos), 1), np.int32)
+    n = C.c_int32(0)
+    rc = load_library().mlh_global_map_select(_p(pos) if len(pos) else None, len(pos), _p(c), float(kf_radius), float(kf_res), _p(ids), C.byref(n))
+    if rc != 0:
+        raise MlhError(f"mlh_global_map_select failed ({rc})")
+    return ids[:n.value].copy()
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -139,6 +172,13 @@ def load_library():
     lib.mlh_local_map_clear.argtypes = [vp]
     lib.mlh_local_map_cloud.argtypes = [vp, ci, ci, C.POINTER(vp), i32p]
     lib.mlh_local_map_info.argtypes = [vp, i32p, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    lib.mlh_keyframe_attach_outlier.argtypes = [vp, C.c_int32, vp, ci, ci, ci, ci]
+    lib.mlh_global_map_opts_default.argtypes = [C.POINTER(GlobalMapOpts), ci]
+    lib.mlh_global_map_opts_default.restype = None
+    lib.mlh_global_map_assemble.argtypes = [vp, vp, vp, vp, ci, C.POINTER(GlobalMapOpts), i32p, i32p, i32p, i32p]
+    lib.mlh_global_map_cloud.argtypes = [vp, ci, ci, C.POINTER(vp), i32p]
+    lib.mlh_global_map_release.argtypes = [vp]
+    lib.mlh_global_map_select.argtypes = [vp, ci, vp, cf, cf, vp, i32p]
     lib.mlh_downsample_current_scan.argtypes = [vp, ci, vp, ci, ci, ci, ci, cf, vp, vp, ci, vp, ci, cd, vp, C.POINTER(C.c_int32)]
     lib.mlh_track_opts_default.argtypes = [vp]
     lib.mlh_track_opts_default.restype = None
@@ -221,6 +261,7 @@ EXPORTED_SYMBOLS = [
     "mlh_shard_set", "mlh_shard_set_features", "mlh_comm_unique_id", "mlh_comm_init", "mlh_p2p_mailbox", "mlh_p2p_comm_init", "mlh_allreduce_f64",
     "mlh_pose_plus", "mlh_eval_degeneracy",
     "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
+    "mlh_keyframe_attach_outlier", "mlh_global_map_opts_default", "mlh_global_map_assemble", "mlh_global_map_cloud", "mlh_global_map_release", "mlh_global_map_select",
 ]
 
 
@@ -716,17 +757,19 @@ class Context:
         self._ck(self.lib.mlh_local_map_cloud(self.h, kind, int(bool(filtered)), C.byref(ptr), C.byref(n)))
         return DeviceCloud(ptr.value, n.value, 48)
 
-    def local_map_fetch(self, kind, filtered=True):
-        """the same cloud copied to the host as (n, 11) float32 [x y z i cov6 trace]"""
-        dc = self.local_map_cloud(kind, filtered)
+    def _fetch48(self, dc):
         if dc.n == 0:
             return np.zeros((0, 11), np.float32)
         self.synchronize()
         out = np.zeros((dc.n, 12), np.float32)
         e = _hip_runtime().hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(dc.ptr), C.c_size_t(dc.n * 48), 2)   # hipMemcpyDeviceToHost
         if e != 0:
-            raise MlhError(f"hipMemcpy of the local map failed ({e})")
+            raise MlhError(f"hipMemcpy of a map cloud failed ({e})")
         return out[:, :11].copy()
+
+    def local_map_fetch(self, kind, filtered=True):
+        """the same cloud copied to the host as (n, 11) float32 [x y z i cov6 trace]"""
+        return self._fetch48(self.local_map_cloud(kind, filtered))
 
     def local_map_clear(self):
         """clearCloud: the four map clouds (the cache and the store stay)"""
@@ -736,6 +779,38 @@ class Context:
         a, b, c, d = C.c_int32(0), C.c_int32(0), C.c_int64(0), C.c_int64(0)
         self._ck(self.lib.mlh_local_map_info(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(d)))
         return dict(n_keyframes=a.value, n_cached=b.value, store_bytes=c.value, cache_bytes=d.value)
+
+    # ---- the global map (pubGlobalMap / saveGlobalMap on the device)
+    def keyframe_attach_outlier(self, key, outlier):
+        """saveKeyframe's third cloud ((n, >= 4) [x y z lidar ...] array or device cloud), attached to the saved keyframe `key`"""
+        po, so, no, mo, ko = _src(outlier)
+        self._ck(self.lib.mlh_keyframe_attach_outlier(self.h, int(key), po, no, so, 12, mo))
+
+    def global_map_assemble(self, pose_cur, ext_poses, ext_covs, opts: GlobalMapOpts):
+        """pubGlobalMap / saveGlobalMap -> dict(n_pre, n_ds (two clouds each), kf_ids (the keyframes the map is made of, in append order))"""
+        p = None if pose_cur is None else np.ascontiguousarray(pose_cur, np.float64).reshape(7)
+        ep = np.ascontiguousarray(ext_poses, np.float64).reshape(-1, 7)
+        ec = None if ext_covs is None else np.ascontiguousarray(ext_covs, np.float64).reshape(-1, 36)
+        nk = C.c_int32(0)
+        self._ck(self.lib.mlh_local_map_info(self.h, C.byref(nk), None, None, None))
+        ids = np.zeros(max(nk.value, 1), np.int32)
+        n_pre, n_ds, n = (C.c_int32 * 2)(), (C.c_int32 * 2)(), C.c_int32(0)
+        self._ck(self.lib.mlh_global_map_assemble(self.h, _p(p), _p(ep), _p(ec), len(ep), C.byref(opts), n_pre, n_ds, ids.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                  C.byref(n)))
+        return dict(n_pre=[n_pre[0], n_pre[1]], n_ds=[n_ds[0], n_ds[1]], kf_ids=ids[:n.value].copy())
+
+    def global_map_cloud(self, which=0, filtered=True) -> "DeviceCloud":
+        """global map cloud `which` in HBM (48-byte PointIWithCov records): filtered = the _ds cloud, else the pre-filter one"""
+        ptr, n = C.c_void_p(), C.c_int32(0)
+        self._ck(self.lib.mlh_global_map_cloud(self.h, which, int(bool(filtered)), C.byref(ptr), C.byref(n)))
+        return DeviceCloud(ptr.value, n.value, 48)
+
+    def global_map_fetch(self, which=0, filtered=True):
+        """the same cloud copied to the host as (n, 11) float32 [x y z i cov6 trace]"""
+        return self._fetch48(self.global_map_cloud(which, filtered))
+
+    def global_map_release(self):
+        self._ck(self.lib.mlh_global_map_release(self.h))
 
     # ---- map / features
     def map_set(self, kind, points, min_match_sq_dis=1.0):

@@ -336,7 +336,8 @@ struct VoxBuf {   // scratch of mlh_voxel_filter
 
 // The mapper's keyframe store and the local map extractSurroundingKeyFrames builds from it (keyframes.hip; lidar_mapper_keyframe.cpp:254-354, 641-683)
 struct KfStore {
-    struct Key { double pose[7], cov[36]; float pos[3]; size_t off[2]; int n[2]; };        // one saved keyframe: pose + cov_, f32 position, its two clouds in `pts`
+    // one saved keyframe: pose + cov_, f32 position, its clouds in `pts`: [0] surf, [1] corner, [2] outlier (attached later or empty; only the global map reads it)
+    struct Key { double pose[7], cov[36]; float pos[3]; size_t off[3]; int n[3]; bool has_outlier; };
     struct Entry { int id; size_t off[2]; int n[2]; int slot; };                            // one cached keyframe: reserved records in `cache` (kept counts: cnt[2 slot + kind])
     std::vector<Key> keys;
     DevBuf pts;                  // float4 {x, y, z, lidar} of every saved cloud, appended
@@ -353,7 +354,11 @@ struct KfStore {
     DevBuf tab;                  // per-call tables (segments, poses, gather lists)
     DevBuf stage, keep, scan;    // batched association: staged records, keep flags, their scan
     std::vector<unsigned char> htab;
-    PinnedBuf h_pin;             // landing place of the two read-backs (32 ints)
+    PinnedBuf h_pin;             // landing place of the read-backs (KF_PIN_INTS ints: [0..31] the local map's, [32..63] the global map's)
+    static constexpr int KF_PIN_INTS = 64;
+    // the global map (pubGlobalMap / saveGlobalMap, cpp:780-919): clouds and lengths of its own; its per-call state words travel in `tab`, never in `dstate`
+    DevBuf gpre[2], gflt[2];     // pre-filter and filtered global clouds, 48-byte records
+    int gpre_n[2] = {0, 0}, gflt_n[2] = {0, 0};
 };
 
 struct SegBuf {    // ImageSegmenter scratch (segment.hip)
@@ -794,6 +799,7 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
                                      int n_lidar, const double cov_meas[9], int with_ua, double trace_thr, int *n_surf_out, int *n_corner_out, bool defer = false);
 // keyframes.hip
 void keyframes_release(mlh_ctx *ctx);
+void global_map_release_run(mlh_ctx *ctx);
 // grid.hip
 int grid_build(mlh_ctx *ctx, int kind_mask, bool recompute_bounds);
 int grid_build_grids(mlh_ctx *ctx, mlh::MapGrid **grids, int n_grids, bool recompute_bounds, int *pub_oob = nullptr, mlh::HostPublish *pub = nullptr,

@@ -16,6 +16,18 @@
 //   voxel_filter_run x 2 the two covariance filters (MAP_SURF_RES / MAP_CORNER_RES), bounds known, counts left on the device.
 // Host waits per call: two (the pre-filter lengths + bounds; the filtered counts) plus one for an arena that has to grow. Launches do not depend on the
 // number of keyframes.
+//
+// pubGlobalMap (cpp:796-849) and saveGlobalMap (cpp:853-901) -- the map itself -- are one more pipeline over the same store (global_map_assemble_run):
+//   host    the radius search (or every keyframe, saveGlobalMap), the thinning of the hits' positions with intensity = the keyframe's own index, and a table
+//           of 256-point TILES over the selected keyframes' (keyframe x kind) segments in destination order -- a tile never straddles a segment;
+//   gm_uct_kernel        cloudUCTAssociateToMap of one tile per workgroup: the tile's keyframe pose, compound poses and covariances are uniform and are
+//                        loaded ONCE per workgroup into LDS (no per-thread segment search, no per-thread table reads); the per-point body is uct_point /
+//                        uct_to_map of uct_dev.hpp, so the bits are kf_uct_kernel's. It leaves the staged record, the waves' keep ballots and the
+//                        tile's kept count (one LDS add per wave); without uncertainty nothing is dropped and it writes the destination and bounds itself;
+//   scan + gm_place_kernel   the exclusive scan runs over the TILE counts (N / 256 entries); a kept record goes to tile offset + its rank inside the tile
+//                        (popcounts of the ballots), the clouds' exact bounds folded once per workgroup;
+//   voxel_filter_run x 1 or 2   the covariance filter per output cloud, bounds known.
+// Nothing of it touches the local map's state: its state words travel in the per-call table, its clouds and pinned landing words are its own.
 #include "ctx.hpp"
 #include <algorithm>
 #include <cfloat>
@@ -46,6 +58,17 @@ struct KfGat {                   // one cached cloud to copy (gather into the pr
     int slot2;
 };
 struct Meas { double m[9]; };
+struct GmTile {                  // up to 256 points of one (keyframe x kind) segment of the global map
+    long long src;               // its first record in the store (float4)
+    int begin;                   // its first point's place among the call's points in destination order (cloud 0's segments, then cloud 1's)
+    int n;                       // 1 .. 256
+    int par;                     // offset (doubles) of its keyframe's pose / compound poses in the parameter table
+    int cloud;                   // the output cloud it belongs to
+};
+// the global map's state words (ints, in the per-call table): [0..1] pre-filter lengths, [2..13] their bounds (order-preserving int encoding),
+// [14..15] filtered counts, [16] total of the tile scan
+constexpr int GM_STATE_INTS = 20, GM_PIN = 32;      // GM_PIN: its first landing word in KfStore::h_pin
+constexpr int GM_MAX_LIDAR = 16, GM_TAB = 7 * GM_MAX_LIDAR + 7 + 43 * GM_MAX_LIDAR;
 
 __device__ __forceinline__ int enc_f(float f) { const int b = __float_as_int(f); return b >= 0 ? b : b ^ 0x7fffffff; }   // order-preserving as int
 inline float dec_f(int b) { const int v = b >= 0 ? b : b ^ 0x7fffffff; float f; std::memcpy(&f, &v, 4); return f; }
@@ -133,30 +156,12 @@ __global__ void kf_prefix_kernel(const KfGat *__restrict__ g, int n0, int n1, co
     dstate[k] = int(base);
 }
 
-__global__ __launch_bounds__(256) void kf_gather_kernel(const float4 *__restrict__ cache, const KfGat *__restrict__ g, int n0, int n1, int ub0, int ub1,
-                                                        const int *__restrict__ cnt, const long long *__restrict__ gofs, float4 *__restrict__ pre0,
-                                                        float4 *__restrict__ pre1, int *__restrict__ dstate)
+// the bounds of what this workgroup wrote (`any`: this thread wrote the point x y z), folded into a cloud's six state words; all 256 threads call it.
+// min / max are exact: any order gives the same result
+__device__ __forceinline__ void wg_fold_bounds(bool any, float x, float y, float z, int *__restrict__ bnd)
 {
-    const int k = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int ng = k == 0 ? n0 : n1, ub = k == 0 ? ub0 : ub1;
-    const KfGat *gk = g + (k == 0 ? 0 : n0);
-    const long long *ok = gofs + (k == 0 ? 0 : n0);
-    float4 *pre = k == 0 ? pre0 : pre1;
     float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    bool any = false;
-    if (ng > 0 && i < ub) {
-        const int e = seg_of(gk, ng, i, &KfGat::ub_begin);
-        const int local = i - gk[e].ub_begin;
-        if (local < cnt[gk[e].slot2]) {
-            const size_t s = size_t(gk[e].src + local) * REC_F4, d = size_t(ok[e] + local) * REC_F4;
-            const float4 r0 = cache[s];
-            pre[d] = r0; pre[d + 1] = cache[s + 1]; pre[d + 2] = cache[s + 2];
-            mn[0] = mx[0] = r0.x; mn[1] = mx[1] = r0.y; mn[2] = mx[2] = r0.z;
-            any = true;
-        }
-    }
-    // the bounds of what this workgroup appended, folded into the cloud's (min / max are exact: any order gives the same result)
+    if (any) { mn[0] = mx[0] = x; mn[1] = mx[1] = y; mn[2] = mx[2] = z; }
     __shared__ float red[6][4];
 #pragma unroll
     for (int d = 0; d < 3; ++d) {
@@ -170,10 +175,120 @@ __global__ __launch_bounds__(256) void kf_gather_kernel(const float4 *__restrict
         for (int d = 0; d < 3; ++d) {
             const float a = fminf(fminf(red[d][0], red[d][1]), fminf(red[d][2], red[d][3]));
             const float b = fmaxf(fmaxf(red[3 + d][0], red[3 + d][1]), fmaxf(red[3 + d][2], red[3 + d][3]));
-            atomicMin(dstate + 2 + 6 * k + d, enc_f(a));
-            atomicMax(dstate + 2 + 6 * k + 3 + d, enc_f(b));
+            atomicMin(bnd + d, enc_f(a));
+            atomicMax(bnd + 3 + d, enc_f(b));
         }
     }
+}
+
+__global__ __launch_bounds__(256) void kf_gather_kernel(const float4 *__restrict__ cache, const KfGat *__restrict__ g, int n0, int n1, int ub0, int ub1,
+                                                        const int *__restrict__ cnt, const long long *__restrict__ gofs, float4 *__restrict__ pre0,
+                                                        float4 *__restrict__ pre1, int *__restrict__ dstate)
+{
+    const int k = blockIdx.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int ng = k == 0 ? n0 : n1, ub = k == 0 ? ub0 : ub1;
+    const KfGat *gk = g + (k == 0 ? 0 : n0);
+    const long long *ok = gofs + (k == 0 ? 0 : n0);
+    float4 *pre = k == 0 ? pre0 : pre1;
+    float p3[3] = {0.f, 0.f, 0.f};
+    bool any = false;
+    if (ng > 0 && i < ub) {
+        const int e = seg_of(gk, ng, i, &KfGat::ub_begin);
+        const int local = i - gk[e].ub_begin;
+        if (local < cnt[gk[e].slot2]) {
+            const size_t s = size_t(gk[e].src + local) * REC_F4, d = size_t(ok[e] + local) * REC_F4;
+            const float4 r0 = cache[s];
+            pre[d] = r0; pre[d + 1] = cache[s + 1]; pre[d + 2] = cache[s + 2];
+            p3[0] = r0.x; p3[1] = r0.y; p3[2] = r0.z;
+            any = true;
+        }
+    }
+    wg_fold_bounds(any, p3[0], p3[1], p3[2], dstate + 2 + 6 * k);
+}
+
+// ---- the global map (pubGlobalMap / saveGlobalMap): one workgroup per tile
+// cloudUCTAssociateToMap of a tile. The tile's tables -- the extrinsics and its keyframe's [gpose 7 | compound poses n_lidar x 7 | covariances n_lidar x 36] --
+// are uniform over the workgroup: loaded once into LDS, from where uct_point reads them by the point's LiDAR id.
+// DIRECT (with_ua == 0: nothing is ever dropped): the record goes straight to its destination and the bounds are folded here.
+// otherwise: the record is staged at the point's place in destination order, each wave leaves its keep ballot (masks[4 tile + wave]) and the tile its kept count.
+template <bool DIRECT>
+__global__ __launch_bounds__(256) void gm_uct_kernel(const float4 *__restrict__ store, const GmTile *__restrict__ tiles, const double *__restrict__ par, int n_lidar,
+                                                     Meas meas, int with_ua, double trace_thr, float4 *__restrict__ stage, unsigned long long *__restrict__ masks,
+                                                     int *__restrict__ tile_cnt, float4 *__restrict__ pre0, float4 *__restrict__ pre1, int n_cloud0,
+                                                     int *__restrict__ state)
+{
+    __shared__ double tab[GM_TAB];
+    __shared__ int kept;
+    const GmTile t = tiles[blockIdx.x];
+    const int n_ext = 7 * n_lidar, n_all = n_ext + 7 + 43 * n_lidar;
+    for (int j = threadIdx.x; j < n_all; j += 256) tab[j] = j < n_ext ? par[j] : par[t.par + (j - n_ext)];
+    if (threadIdx.x == 0) kept = 0;
+    __syncthreads();
+    const double *gpose = tab + n_ext;
+    int keep = 0;
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f), r1 = r0, r2 = r0;
+    if (int(threadIdx.x) < t.n) {
+        const float4 p = store[t.src + threadIdx.x];
+        const UctPoint u = uct_point(tab, gpose + 7, gpose + 7 + 7 * n_lidar, n_lidar, meas.m, DIRECT ? 0 : with_ua, trace_thr, p.x, p.y, p.z, p.w);
+        keep = u.keep;
+        if (keep) {
+            float xyz[3];
+            uct_to_map(gpose, p.x, p.y, p.z, xyz);
+            r0 = make_float4(xyz[0], xyz[1], xyz[2], p.w);
+            r1 = make_float4(u.c6[0], u.c6[1], u.c6[2], u.c6[3]);
+            r2 = make_float4(u.c6[4], u.c6[5], float(u.tr), 0.f);
+        }
+    }
+    if (DIRECT) {
+        if (keep) {
+            float4 *o = (t.cloud ? pre1 : pre0) + size_t(t.begin - (t.cloud ? n_cloud0 : 0) + int(threadIdx.x)) * REC_F4;
+            o[0] = r0; o[1] = r1; o[2] = r2;
+        }
+        wg_fold_bounds(keep != 0, r0.x, r0.y, r0.z, state + 2 + 6 * t.cloud);
+    } else {
+        if (keep) {
+            float4 *o = stage + size_t(t.begin + int(threadIdx.x)) * REC_F4;
+            o[0] = r0; o[1] = r1; o[2] = r2;
+        }
+        const unsigned long long b = __ballot(keep);
+        if ((threadIdx.x & 63) == 0) {
+            masks[size_t(blockIdx.x) * 4 + (threadIdx.x >> 6)] = b;
+            atomicAdd(&kept, __popcll(b));
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) tile_cnt[blockIdx.x] = kept;
+    }
+}
+
+// a kept record of a tile -> its cloud, at the tile's offset (the scan over the tile counts; cloud 1's tiles come behind all of cloud 0's, so cloud 0's length
+// is the offset of cloud 1's first tile) + its rank among the tile's kept records (popcounts of the keep ballots); the clouds' lengths and bounds on the way
+__global__ __launch_bounds__(256) void gm_place_kernel(const float4 *__restrict__ stage, const GmTile *__restrict__ tiles, const unsigned long long *__restrict__ masks,
+                                                       const int *__restrict__ tile_off, int n_tiles, int tiles0, const int *__restrict__ total,
+                                                       float4 *__restrict__ pre0, float4 *__restrict__ pre1, int *__restrict__ state)
+{
+    const GmTile t = tiles[blockIdx.x];
+    const int len0 = tiles0 < n_tiles ? tile_off[tiles0] : *total;
+    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int rank = 0;
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const unsigned long long m = masks[size_t(blockIdx.x) * 4 + j];
+        if (j < w) rank += __popcll(m);
+        if (j == w) mine = m;
+    }
+    const bool keep = ((mine >> lane) & 1ull) != 0;
+    rank += __popcll(mine & ((1ull << lane) - 1ull));
+    float4 r0 = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (keep) {
+        const float4 *s = stage + size_t(t.begin + int(threadIdx.x)) * REC_F4;
+        float4 *o = (t.cloud ? pre1 : pre0) + size_t(tile_off[blockIdx.x] - (t.cloud ? len0 : 0) + rank) * REC_F4;
+        r0 = s[0];
+        o[0] = r0; o[1] = s[1]; o[2] = s[2];
+    }
+    wg_fold_bounds(keep, r0.x, r0.y, r0.z, state + 2 + 6 * t.cloud);
+    if (blockIdx.x == 0 && threadIdx.x == 0) { state[0] = len0; state[1] = *total - len0; }
 }
 
 // VoxelGridCovarianceMLOAM<PointI>::filter, plain branch (voxel_grid_covariance_mloam_impl.hpp:68-130, 180-260, 392-420), over the cached keyframes'
@@ -238,7 +353,26 @@ void keyframes_release(mlh_ctx *ctx)
     K.pts.release(); K.cache.release(); K.cache_tmp.release(); K.cnt.release(); K.dstate.release(); K.tab.release();
     K.stage.release(); K.keep.release(); K.scan.release();
     for (int k = 0; k < 2; ++k) { K.pre[k].release(); K.flt[k].release(); K.pre_n[k] = K.flt_n[k] = 0; }
+    global_map_release_run(ctx);
     std::vector<unsigned char>().swap(K.htab);
+}
+
+// one cloud appended to the store (which has room for it): device float4 records (`packed`), or a caller's records packed on the way in
+static int store_append(mlh_ctx *ctx, const void *src, int n, int stride, int ioff, int mem, bool packed)
+{
+    KfStore &K = ctx->kf;
+    hipStream_t st = ctx->stream;
+    if (n <= 0) return MLH_OK;
+    float4 *dst = K.pts.as<float4>() + K.pts_used;
+    if (packed) {
+        MLH_HIP(ctx, hipMemcpyAsync(dst, src, sizeof(float4) * size_t(n), hipMemcpyDeviceToDevice, st));
+    } else {
+        const unsigned char *s;
+        { const int rc = records_stage(ctx, records_of(src, stride, n, mem), ctx->tmp, st, &s); if (rc) return rc; }
+        pack_points_launch(st, s, stride, n, ioff, 0.f, -1, dst, nullptr);
+    }
+    K.pts_used += size_t(n);
+    return MLH_OK;
 }
 
 // saveKeyframe's store (cpp:664-681): the pose, the f32 position, the two clouds appended to the store. src[k] are device float4 records (staged) or
@@ -255,20 +389,12 @@ static int keyframe_store(mlh_ctx *ctx, const double pose[7], const double cov[3
     for (int i = 0; i < 7; ++i) key.pose[i] = pose[i];
     for (int i = 0; i < 36; ++i) key.cov[i] = cov[i];
     for (int d = 0; d < 3; ++d) key.pos[d] = float(pose[d]);                 // pose_3d.x = pose_wmap_curr.t_[0] (PointI: f32)
-    float4 *dst = K.pts.as<float4>();
     for (int k = 0; k < 2; ++k) {
         key.off[k] = K.pts_used; key.n[k] = n[k];
-        if (n[k] > 0) {
-            if (packed) {
-                MLH_HIP(ctx, hipMemcpyAsync(dst + K.pts_used, src[k], sizeof(float4) * size_t(n[k]), hipMemcpyDeviceToDevice, st));
-            } else {
-                const unsigned char *s;
-                { const int rc = records_stage(ctx, records_of(src[k], stride, n[k], mem), ctx->tmp, st, &s); if (rc) return rc; }
-                pack_points_launch(st, s, stride, n[k], ioff, 0.f, -1, dst + K.pts_used, nullptr);
-            }
-            K.pts_used += size_t(n[k]);
-        }
+        const int rc = store_append(ctx, src[k], n[k], stride, ioff, mem, packed);
+        if (rc) return rc;
     }
+    key.off[2] = K.pts_used; key.n[2] = 0; key.has_outlier = false;       // the outlier cloud: mlh_keyframe_attach_outlier
     MLH_HIP(ctx, hipGetLastError());
     if (mem == MLH_MEM_HOST && !packed) MLH_HIP(ctx, hipStreamSynchronize(st));     // the caller's clouds have been read when the call returns
     K.keys.push_back(key);
@@ -423,7 +549,7 @@ int local_map_assemble_run(mlh_ctx *ctx, const double pose_cur[7], const double 
     // buffers (growth of a store / arena / cloud that holds data waits for its copy: the one exception to the two waits)
     MLH_HIP(ctx, K.cnt.grow(sizeof(int) * size_t(2 * K.n_slots + 2), K.cnt.cap, st));
     MLH_HIP(ctx, K.dstate.ensure(sizeof(int) * 20));
-    MLH_HIP(ctx, K.h_pin.ensure(sizeof(int) * 32));
+    MLH_HIP(ctx, K.h_pin.ensure(sizeof(int) * KfStore::KF_PIN_INTS));
     int *h_pin = K.h_pin.as<int>();
     if (compact) MLH_HIP(ctx, K.cache_tmp.ensure(size_t(REC) * std::max<size_t>(2 * K.cache_used, 1024)));   // live + entering, with room for turnover
     for (int k = 0; k < 2; ++k) MLH_HIP(ctx, K.pre[k].grow(size_t(REC) * (size_t(K.pre_n[k]) + size_t(ub[k]) + 1), size_t(REC) * size_t(K.pre_n[k]), st));
@@ -522,6 +648,200 @@ int local_map_info_run(mlh_ctx *ctx, int32_t *n_keyframes, int32_t *n_cached, in
     return MLH_OK;
 }
 
+// saveKeyframe's third cloud (laser_cloud_outlier_cov, cpp:673, 677, 681), attached to a keyframe that is already in the store
+int keyframe_attach_outlier_run(mlh_ctx *ctx, int32_t key, const void *points, int n, int stride, int ioff, int mem)
+{
+    KfStore &K = ctx->kf;
+    if (key < 0 || size_t(key) >= K.keys.size()) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframe_attach_outlier: no such keyframe");
+    if (ioff < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframe_attach_outlier: bad arguments");
+    { const int rc = records_check(ctx, "mlh_keyframe_attach_outlier", records_of(points, stride, n, mem, ioff), true); if (rc) return rc; }
+    KfStore::Key &k = K.keys[size_t(key)];
+    if (k.has_outlier) return fail(ctx, MLH_ERR_STATE, "mlh_keyframe_attach_outlier: the keyframe already has an outlier cloud");
+    if (n == 0) return MLH_OK;
+    if (K.pts_used + size_t(n) > size_t(INT_MAX)) return fail(ctx, MLH_ERR_NOMEM, "keyframe store: more than 2^31 stored points");
+    MLH_HIP(ctx, K.pts.grow(sizeof(float4) * (K.pts_used + size_t(n) + 1), sizeof(float4) * K.pts_used, ctx->stream));
+    const size_t off = K.pts_used;
+    { const int rc = store_append(ctx, points, n, stride, ioff, mem, false); if (rc) return rc; }
+    MLH_HIP(ctx, hipGetLastError());
+    if (mem == MLH_MEM_HOST) MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));      // the caller's cloud has been read when the call returns
+    k.off[2] = off; k.n[2] = n; k.has_outlier = true;
+    return MLH_OK;
+}
+
+// Which keyframes the global map is made of, in the order their clouds are appended (cpp:804-810 / cpp:865-868): radiusSearch around the f32 position
+// (nearest first, equal distances by index; kf_radius < 0: every keyframe in index order), the hits in that order through the plain branch of
+// VoxelGridCovarianceMLOAM<PointI> at kf_res with intensity = the keyframe's own index (cpp:666). Keyframes that share a position voxel contribute only
+// the voxel's last member in std::sort order.
+int global_map_select_host(const float *pos, int n, const float *center, float kf_radius, float kf_res, std::vector<int> &ids)
+{
+    ids.clear();
+    if (n < 0 || (n > 0 && !pos) || !(kf_res > 0.f) || !std::isfinite(kf_res) || std::isnan(kf_radius) || (kf_radius >= 0.f && !std::isfinite(kf_radius)))
+        return MLH_ERR_INVALID;
+    std::vector<int> hits;
+    if (kf_radius < 0.f) {
+        for (int i = 0; i < n; ++i) hits.push_back(i);
+    } else {
+        if (!center || !std::isfinite(center[0]) || !std::isfinite(center[1]) || !std::isfinite(center[2])) return MLH_ERR_INVALID;
+        std::vector<std::pair<float, int>> hit;
+        for (int i = 0; i < n; ++i) {
+            const float dx = pos[3 * i] - center[0], dy = pos[3 * i + 1] - center[1], dz = pos[3 * i + 2] - center[2], d2 = dx * dx + dy * dy + dz * dz;
+            if (d2 <= kf_radius * kf_radius) hit.emplace_back(d2, i);
+        }
+        std::sort(hit.begin(), hit.end());
+        for (const auto &h : hit) hits.push_back(h.second);
+    }
+    std::vector<std::array<float, 3>> p;
+    for (int i : hits) p.push_back({pos[3 * i], pos[3 * i + 1], pos[3 * i + 2]});
+    for (int j : thin_positions(p, kf_res)) ids.push_back(hits[size_t(j)]);
+    return MLH_OK;
+}
+
+void global_map_release_run(mlh_ctx *ctx)
+{
+    KfStore &K = ctx->kf;
+    for (int k = 0; k < 2; ++k) { K.gpre[k].release(); K.gflt[k].release(); K.gpre_n[k] = K.gflt_n[k] = 0; }
+}
+
+int global_map_assemble_run(mlh_ctx *ctx, const double *pose_cur, const double *ext_poses, const double *ext_covs, int n_lidar, const mlh_global_map_opts *o,
+                            int32_t n_pre[2], int32_t n_ds[2], int32_t *kf_ids_out, int32_t *n_ids)
+{
+    if (!ext_poses || !o || !n_pre || !n_ds || n_lidar <= 0 || n_lidar > GM_MAX_LIDAR) return fail(ctx, MLH_ERR_INVALID, "mlh_global_map_assemble: bad arguments");
+    const auto pos_finite = [](float v) { return std::isfinite(v) && v > 0.f; };
+    if (std::isnan(o->kf_radius) || (o->kf_radius >= 0.f && !std::isfinite(o->kf_radius)) || !pos_finite(o->kf_res) || !pos_finite(o->leaf) ||
+        std::isnan(o->trace_threshold) || (o->split != 0 && o->split != 1))
+        return fail(ctx, MLH_ERR_INVALID, "mlh_global_map_assemble: radius, resolution and leaf must be finite (resolution and leaf > 0), split 0 or 1");
+    if (o->kf_radius >= 0.f && (!pose_cur || bad_pose(pose_cur))) return fail(ctx, MLH_ERR_INVALID, "mlh_global_map_assemble: a radius search needs the current pose");
+    if (o->with_ua && !ext_covs) return fail(ctx, MLH_ERR_INVALID, "mlh_global_map_assemble: with_ua needs the extrinsic covariances");
+    KfStore &K = ctx->kf;
+    hipStream_t st = ctx->stream;
+    for (int k = 0; k < 2; ++k) { n_pre[k] = n_ds[k] = 0; K.gpre_n[k] = K.gflt_n[k] = 0; }
+    if (n_ids) *n_ids = 0;
+    if (K.keys.empty()) return MLH_OK;                                     // cpp:796
+
+    // the selection (cpp:804-810 / 865-868)
+    std::vector<float> pos(3 * K.keys.size());
+    for (size_t i = 0; i < K.keys.size(); ++i) for (int d = 0; d < 3; ++d) pos[3 * i + size_t(d)] = K.keys[i].pos[d];
+    float c[3] = {0.f, 0.f, 0.f};
+    if (pose_cur) for (int d = 0; d < 3; ++d) c[d] = float(pose_cur[d]);
+    std::vector<int> sel;
+    if (global_map_select_host(pos.data(), int(K.keys.size()), c, o->kf_radius, o->kf_res, sel) != MLH_OK)
+        return fail(ctx, MLH_ERR_INVALID, "mlh_global_map_assemble: bad selection arguments");
+    if (kf_ids_out) for (size_t j = 0; j < sel.size(); ++j) kf_ids_out[j] = sel[j];
+    if (n_ids) *n_ids = int32_t(sel.size());
+
+    // the parameter table and the tiles, in destination order: split 0: per keyframe surf, corner, outlier (cpp:818-827) into one cloud;
+    // split 1: cloud 0 = per keyframe surf, outlier, then cloud 1 = per keyframe corner (cpp:872-882)
+    std::vector<double> par(size_t(n_lidar) * 7);
+    for (int l = 0; l < 7 * n_lidar; ++l) par[size_t(l)] = ext_poses[l];
+    std::vector<int> par_of(sel.size());
+    for (size_t j = 0; j < sel.size(); ++j) {
+        const KfStore::Key &key = K.keys[size_t(sel[j])];
+        const int p = int(par.size());
+        par_of[j] = p;
+        par.resize(par.size() + 7 + size_t(n_lidar) * 43, 0.0);
+        for (int i = 0; i < 7; ++i) par[size_t(p + i)] = key.pose[i];
+        if (o->with_ua)
+            for (int l = 0; l < n_lidar; ++l)       // compoundPoseWithCov(pose_global, pose_ext[n]) (cpp:1122-1126)
+                compound_pose_with_cov(key.pose, key.cov, ext_poses + 7 * l, ext_covs + 36 * l, &par[size_t(p + 7 + 7 * l)], &par[size_t(p + 7 + 7 * n_lidar + 36 * l)]);
+    }
+    std::vector<GmTile> tiles;
+    size_t total[2] = {0, 0}, N = 0;
+    int tiles0 = 0;
+    const auto add_segment = [&](size_t j, int kind, int cloud) {
+        const KfStore::Key &key = K.keys[size_t(sel[j])];
+        for (int at = 0; at < key.n[kind]; at += 256)
+            tiles.push_back(GmTile{(long long)(key.off[kind] + size_t(at)), int(N) + at, std::min(256, key.n[kind] - at), par_of[j], cloud});
+        total[cloud] += size_t(key.n[kind]);
+        N += size_t(key.n[kind]);
+    };
+    static const int order0[3] = {0, 1, 2}, order1[2] = {0, 2};
+    size_t need = 0;
+    for (int id : sel) need += size_t(K.keys[size_t(id)].n[0]) + size_t(K.keys[size_t(id)].n[1]) + size_t(K.keys[size_t(id)].n[2]);
+    if (need > size_t(INT_MAX) / 2) return fail(ctx, MLH_ERR_NOMEM, "global map: too many points");
+    if (o->split == 0) {
+        for (size_t j = 0; j < sel.size(); ++j) for (int kind : order0) add_segment(j, kind, 0);
+        tiles0 = int(tiles.size());
+    } else {
+        for (size_t j = 0; j < sel.size(); ++j) for (int kind : order1) add_segment(j, kind, 0);
+        tiles0 = int(tiles.size());
+        for (size_t j = 0; j < sel.size(); ++j) add_segment(j, 1, 1);
+    }
+    const int n_tiles = int(tiles.size());
+    if (n_tiles == 0) return MLH_OK;                                       // keyframes without a point
+    const bool direct = !o->with_ua;                                       // nothing is ever dropped: no staging, no scan
+
+    // buffers, and one upload of every table of the call (the state words start as: lengths known only on the direct path, empty bounds, no filtered records)
+    for (int k = 0; k < 2; ++k) if (total[k] > 0) MLH_HIP(ctx, K.gpre[k].ensure(size_t(REC) * (total[k] + 1)));
+    if (!direct) {
+        MLH_HIP(ctx, K.stage.ensure(size_t(REC) * N));
+        MLH_HIP(ctx, K.keep.ensure(sizeof(unsigned long long) * 4 * size_t(n_tiles)));
+        MLH_HIP(ctx, K.scan.ensure(sizeof(int) * size_t(n_tiles + 1)));
+    }
+    MLH_HIP(ctx, K.h_pin.ensure(sizeof(int) * KfStore::KF_PIN_INTS));
+    int *h_pin = K.h_pin.as<int>() + GM_PIN;
+    int state0[GM_STATE_INTS] = {0};
+    if (direct) { state0[0] = int(total[0]); state0[1] = int(total[1]); }
+    for (int k = 0; k < 2; ++k) for (int d = 0; d < 3; ++d) { state0[2 + 6 * k + d] = INT_MAX; state0[2 + 6 * k + 3 + d] = INT_MIN; }
+    std::vector<unsigned char> &h = K.htab;
+    h.clear();
+    const size_t o_par = put(h, par.data(), par.size());
+    const size_t o_til = put(h, tiles.data(), tiles.size());
+    const size_t o_sta = put(h, state0, size_t(GM_STATE_INTS));
+    MLH_HIP(ctx, K.tab.ensure(h.size() + 16));
+    unsigned char *dt = K.tab.as<unsigned char>();
+    MLH_HIP(ctx, hipMemcpyAsync(dt, h.data(), h.size(), hipMemcpyHostToDevice, st));
+    const GmTile *d_til = reinterpret_cast<const GmTile *>(dt + o_til);
+    const double *d_par = reinterpret_cast<const double *>(dt + o_par);
+    int *state = reinterpret_cast<int *>(dt + o_sta);
+
+    Meas meas;
+    for (int i = 0; i < 9; ++i) meas.m[i] = o->cov_measurement[i];
+    if (direct) {
+        MLH_LAUNCH(gm_uct_kernel<true>, dim3(n_tiles), dim3(256), 0, st, (const float4 *)K.pts.as<float4>(), d_til, d_par, n_lidar, meas, 0, o->trace_threshold,
+                   (float4 *)nullptr, (unsigned long long *)nullptr, (int *)nullptr, K.gpre[0].as<float4>(), K.gpre[1].as<float4>(), int(total[0]), state);
+    } else {
+        MLH_LAUNCH(gm_uct_kernel<false>, dim3(n_tiles), dim3(256), 0, st, (const float4 *)K.pts.as<float4>(), d_til, d_par, n_lidar, meas, 1, o->trace_threshold,
+                   K.stage.as<float4>(), K.keep.as<unsigned long long>(), K.scan.as<int>(), (float4 *)nullptr, (float4 *)nullptr, 0, state);
+        const int rc = device_exclusive_scan(ctx, K.scan.as<int>(), n_tiles, ctx->vox.sums, state + 16);
+        if (rc) return rc;
+        MLH_LAUNCH(gm_place_kernel, dim3(n_tiles), dim3(256), 0, st, (const float4 *)K.stage.as<float4>(), d_til, (const unsigned long long *)K.keep.as<unsigned long long>(),
+                   (const int *)K.scan.as<int>(), n_tiles, tiles0, (const int *)(state + 16), K.gpre[0].as<float4>(), K.gpre[1].as<float4>(), state);
+    }
+    MLH_HIP(ctx, hipGetLastError());
+    // wait 1: the pre-filter lengths and bounds
+    MLH_HIP(ctx, hipMemcpyAsync(h_pin, state, sizeof(int) * 14, hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, stream_wait_spin(ctx));
+    float bounds[2][6];
+    for (int k = 0; k < 2; ++k) {
+        K.gpre_n[k] = h_pin[k];
+        for (int d = 0; d < 6; ++d) bounds[k][d] = dec_f(h_pin[2 + 6 * k + d]);
+    }
+    // one covariance filter per output cloud (cpp:839-842 / 896-901), results kept in buffers of the global map's own
+    for (int k = 0; k < 2; ++k) {
+        if (K.gpre_n[k] == 0) continue;                                    // (its filtered count stays at the 0 it was uploaded with)
+        int dummy = 0;
+        const int rc = voxel_filter_run(ctx, K.gpre[k].p, REC, K.gpre_n[k], 12, 16, 40, o->leaf, float(o->trace_threshold), nullptr, &dummy, MLH_MEM_DEVICE, bounds[k], false);
+        if (rc) return rc;
+        MLH_HIP(ctx, K.gflt[k].ensure(size_t(REC) * size_t(K.gpre_n[k])));
+        MLH_HIP(ctx, hipMemcpyAsync(K.gflt[k].p, ctx->vox.out.p, size_t(REC) * size_t(K.gpre_n[k]), hipMemcpyDeviceToDevice, st));
+        MLH_HIP(ctx, hipMemcpyAsync(state + 14 + k, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, st));
+    }
+    // wait 2: the filtered counts
+    MLH_HIP(ctx, hipMemcpyAsync(h_pin + 16, state + 14, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, stream_wait_spin(ctx));
+    for (int k = 0; k < 2; ++k) { K.gflt_n[k] = h_pin[16 + k]; n_pre[k] = K.gpre_n[k]; n_ds[k] = K.gflt_n[k]; }
+    return device_error_check(ctx);
+}
+
+int global_map_cloud_run(mlh_ctx *ctx, int which, int filtered, const void **device_points, int32_t *n)
+{
+    if (which < 0 || which > 1 || (filtered != 0 && filtered != 1) || !device_points || !n) return fail(ctx, MLH_ERR_INVALID, "mlh_global_map_cloud: bad arguments");
+    const KfStore &K = ctx->kf;
+    *n = filtered ? K.gflt_n[which] : K.gpre_n[which];
+    *device_points = *n == 0 ? nullptr : (filtered ? K.gflt[which].p : K.gpre[which].p);
+    return MLH_OK;
+}
+
 }  // namespace mlh
 
 using namespace mlh;
@@ -574,6 +894,60 @@ int mlh_local_map_info(mlh_ctx *ctx, int32_t *n_keyframes, int32_t *n_cached, in
 {
     if (!ctx) return MLH_ERR_INVALID;
     return local_map_info_run(ctx, n_keyframes, n_cached, store_bytes, cache_bytes);
+}
+
+int mlh_keyframe_attach_outlier(mlh_ctx *ctx, int32_t key, const void *points, int n, int stride_bytes, int intensity_offset_bytes, int mem)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return keyframe_attach_outlier_run(ctx, key, points, n, stride_bytes, intensity_offset_bytes, mem);
+}
+
+void mlh_global_map_opts_default(mlh_global_map_opts *o, int for_save)
+{
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->kf_radius = for_save ? -1.f : 1000.f;        // GLOBALMAP_KF_RADIUS (lidar_mapper.h:81); saveGlobalMap takes every keyframe (cpp:865-866)
+    o->kf_res = 10.f;                               // down_size_filter_global_map_keyframes (cpp:1293)
+    o->leaf = for_save ? 0.8f : 0.4f;               // MAP_SURF_RES (cpp:839), 2 * MAP_SURF_RES (cpp:896)
+    o->split = for_save ? 1 : 0;
+    o->trace_threshold = 0.6;
+    o->with_ua = 1;
+    o->cov_measurement[0] = o->cov_measurement[4] = o->cov_measurement[8] = 0.0025;
+}
+
+int mlh_global_map_assemble(mlh_ctx *ctx, const double pose_cur[7], const double *ext_poses, const double *ext_covs, int n_lidar, const mlh_global_map_opts *opts,
+                            int32_t n_pre[2], int32_t n_ds[2], int32_t *kf_ids_out, int32_t *n_ids)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return global_map_assemble_run(ctx, pose_cur, ext_poses, ext_covs, n_lidar, opts, n_pre, n_ds, kf_ids_out, n_ids);
+}
+
+int mlh_global_map_cloud(mlh_ctx *ctx, int which, int filtered, const void **device_points, int32_t *n)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return global_map_cloud_run(ctx, which, filtered, device_points, n);
+}
+
+int mlh_global_map_release(mlh_ctx *ctx)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    global_map_release_run(ctx);
+    return MLH_OK;
+}
+
+int mlh_global_map_select(const float *positions_xyz, int n, const float center[3], float kf_radius, float kf_res, int32_t *ids_out, int32_t *n_ids)
+{
+    if (!n_ids || (n > 0 && !ids_out)) return MLH_ERR_INVALID;
+    std::vector<int> ids;
+    const int rc = global_map_select_host(positions_xyz, n, center, kf_radius, kf_res, ids);
+    if (rc) return rc;
+    for (size_t j = 0; j < ids.size(); ++j) ids_out[j] = ids[j];
+    *n_ids = int32_t(ids.size());
+    return MLH_OK;
 }
 
 }  // extern "C"

@@ -225,6 +225,8 @@ struct Params {
     float DISTANCE_KEYFRAMES = 1.0f, ORIENTATION_KEYFRAMES = 1.0f, SURROUNDING_KF_RADIUS = 50.0f;
     // the local map's resolutions (parameters.cpp; config_realvehicle_hercules.yaml: map_sur_kf_res, map_surf_res = 2 x 0.2, map_corner_res = 0.2)
     float MAP_SUR_KF_RES = 1.0f, MAP_SURF_RES = 0.4f, MAP_CORNER_RES = 0.2f;
+    // the outlier cloud's resolution (config_realvehicle_hercules.yaml: map_outlier_res) and the global map's keyframe search (lidar_mapper.h:81, cpp:1293)
+    float MAP_OUTLIER_RES = 0.8f, GLOBALMAP_KF_RADIUS = 1000.0f, GLOBALMAP_KF_RES = 10.0f;
 };
 inline Params &params() { static Params p; return p; }
 
@@ -1856,7 +1858,8 @@ private:
 };
 
 // The mapper's keyframes and local map in HBM (mlh_keyframe_save* / mlh_local_map_*): saveKeyframe (cpp:641-683), extractSurroundingKeyFrames (cpp:254-354) and
-// clearCloud (cpp:921-927) under the reference's names. The map clouds stay on the device; surfMapDevice / cornerMapDevice hand them to mlh_map_set_pair(_overlapped)
+// clearCloud (cpp:921-927) under the reference's names; pubGlobalMap (cpp:796-849) and saveGlobalMap (cpp:853-901) build THE map from the same store
+// (mlh_global_map_*) and return it as device clouds, fetchCloud copies one to the host. The map clouds stay on the device; surfMapDevice / cornerMapDevice hand them to mlh_map_set_pair(_overlapped)
 // (48-byte PointIWithCov records, MLH_MEM_DEVICE). Shares the Device (and its stream) with the solve that reads the maps.
 class KeyframeMap {
 public:
@@ -1867,6 +1870,14 @@ public:
         o_.leaf_surf = P.MAP_SURF_RES; o_.leaf_corner = P.MAP_CORNER_RES;
         o_.trace_threshold = P.TRACE_THRESHOLD_MAPPING; o_.with_ua = with_ua_flag ? 1 : 0;
         for (int i = 0; i < 9; ++i) o_.cov_measurement[i] = P.COV_MEASUREMENT[i];
+        for (int for_save = 0; for_save < 2; ++for_save) {
+            mlh_global_map_opts &g = g_[for_save];
+            mlh_global_map_opts_default(&g, for_save);
+            if (!for_save) g.kf_radius = P.GLOBALMAP_KF_RADIUS;
+            g.kf_res = P.GLOBALMAP_KF_RES; g.leaf = for_save ? P.MAP_SURF_RES * 2 : P.MAP_SURF_RES;
+            g.trace_threshold = o_.trace_threshold; g.with_ua = o_.with_ua;
+            for (int i = 0; i < 9; ++i) g.cov_measurement[i] = P.COV_MEASUREMENT[i];
+        }
         dev_.check(mlh_keyframes_reset(dev_.ctx()));
     }
     // pose_ext (with cov_) as the reference keeps them: used for the keyframes that enter the cache from the next extractSurroundingKeyFrames on
@@ -1886,19 +1897,98 @@ public:
         if (idx >= 0) store(pose_wmap_curr, surf_cov, corner_cov);
         return idx;
     }
-    // the store only (the caller has already taken saveKeyframe's decision through the same KeyframePolicy)
-    void store(const Pose &pose_wmap_curr, const PointICovCloud &surf_cov, const PointICovCloud &corner_cov)
+    // ... and with the frame's outlier cloud (laser_cloud_outlier, cpp:673-681), which only the global map reads: thinned as downsampleCurrentScan thins it
+    // (cpp:366-368: plain branch at MAP_OUTLIER_RES; cpp:405-418: with with_ua_flag the trace gate), then attached to the keyframe. Needs setExtrinsics.
+    int saveKeyframe(const Pose &pose_wmap_curr, const PointICovCloud &surf_cov, const PointICovCloud &corner_cov, const PointICloud &laser_cloud_outlier)
+    {
+        const int idx = kf_.save(pose_wmap_curr);
+        if (idx >= 0) attachOutlier(store(pose_wmap_curr, surf_cov, corner_cov), laser_cloud_outlier);
+        return idx;
+    }
+    // the store only (the caller has already taken saveKeyframe's decision through the same KeyframePolicy); returns the keyframe's index in the store
+    int32_t store(const Pose &pose_wmap_curr, const PointICovCloud &surf_cov, const PointICovCloud &corner_cov)
     {
         int32_t key = -1;
         dev_.check(mlh_keyframe_save(dev_.ctx(), param(pose_wmap_curr).data(), pose_wmap_curr.cov_.data(), surf_cov.points.data(), (int)surf_cov.size(),
                                      corner_cov.points.data(), (int)corner_cov.size(), (int)sizeof(PointIWithCov), 16, MLH_MEM_HOST, &key));
+        return key;
+    }
+    // what downsampleCurrentScan leaves of the outlier cloud (cpp:366-368, 405-418): laser_cloud_outlier_cov's points
+    PointICloud downsampleOutlier(const PointICloud &laser_cloud_outlier)
+    {
+        PointICloud ds;
+        if (laser_cloud_outlier.size() == 0) return ds;
+        ds.points.resize(laser_cloud_outlier.size());
+        int32_t n = 0;
+        dev_.check(mlh_voxel_filter(dev_.ctx(), laser_cloud_outlier.points.data(), (int)sizeof(PointI), (int)laser_cloud_outlier.size(), 16, -1, -1,
+                                    params().MAP_OUTLIER_RES, 0.f, ds.points.data(), &n, MLH_MEM_HOST));
+        ds.points.resize(size_t(n));
+        if (o_.with_ua && n > 0) {
+            if (pose_ext_.empty()) throw Error("KeyframeMap: setExtrinsics first");
+            std::vector<double> e, c;
+            packExt(e, c);
+            std::vector<float> cov6(size_t(n) * 6);
+            std::vector<int32_t> keep(size_t(n), 1);
+            dev_.check(mlh_point_uncertainty(dev_.ctx(), ds.points.data(), (int)sizeof(PointI), n, 16, MLH_MEM_HOST, e.data(), c.data(), (int)pose_ext_.size(),
+                                             o_.cov_measurement, o_.trace_threshold, cov6.data(), keep.data()));
+            size_t m = 0;
+            for (size_t i = 0; i < ds.points.size(); ++i) if (keep[i]) ds.points[m++] = ds.points[i];
+            ds.points.resize(m);
+        }
+        return ds;
+    }
+    void attachOutlier(int32_t key, const PointICloud &laser_cloud_outlier)
+    {
+        const PointICloud ds = downsampleOutlier(laser_cloud_outlier);
+        dev_.check(mlh_keyframe_attach_outlier(dev_.ctx(), key, ds.points.data(), (int)ds.size(), (int)sizeof(PointI), 16, MLH_MEM_HOST));
+    }
+    // One cloud of the global map in HBM: 48-byte records {x, y, z, intensity, cov_vec[6], cov_trace, pad}, valid until the next pubGlobalMap / saveGlobalMap / reset
+    struct DeviceCloud { const void *points = nullptr; int32_t n = 0; };
+    // pubGlobalMap()'s map (cpp:796-849; the publication is the caller's): laser_cloud_map_ds around pose_point_cur = the current pose's position
+    DeviceCloud pubGlobalMap(const Pose &pose_point_cur)
+    {
+        globalMap(g_[0], param(pose_point_cur).data());
+        return globalCloud(0, 1);
+    }
+    // saveGlobalMap()'s maps (cpp:853-901; the PCD writing is the caller's): laser_cloud_surf_map_ds (surf + outlier) and laser_cloud_corner_map_ds. The keyframe
+    // list is clean: what a concurrent pubGlobalMap left in the reference's global_map_keyframes (cpp:865-866) is not reproduced.
+    std::pair<DeviceCloud, DeviceCloud> saveGlobalMap()
+    {
+        globalMap(g_[1], nullptr);
+        return std::make_pair(globalCloud(0, 1), globalCloud(1, 1));
+    }
+    mlh_global_map_opts &globalOpts(bool for_save) { return g_[for_save ? 1 : 0]; }
+    const std::vector<int32_t> &lastGlobalIds() const { return gids_; }
+    DeviceCloud globalCloud(int which, int filtered) const
+    {
+        DeviceCloud d;
+        dev_.check(mlh_global_map_cloud(dev_.ctx(), which, filtered, &d.points, &d.n));
+        return d;
+    }
+    // a device cloud of 48-byte records copied into a host PointICovCloud (`copy_to_host(dst, src, bytes)`: the caller's device-to-host copy, e.g. hipMemcpy --
+    // this header stays free of the HIP runtime)
+    template <class CopyToHost> void fetchCloud(const DeviceCloud &d, PointICovCloud &out, CopyToHost copy_to_host) const
+    {
+        out.points.clear();
+        if (d.n <= 0) return;
+        dev_.check(mlh_synchronize(dev_.ctx()));
+        std::vector<float> rec(size_t(d.n) * 12);
+        copy_to_host(rec.data(), d.points, rec.size() * sizeof(float));
+        out.points.resize(size_t(d.n));
+        for (size_t i = 0; i < size_t(d.n); ++i) {
+            const float *r = rec.data() + i * 12;
+            PointIWithCov &p = out.points[i];
+            p.x = r[0]; p.y = r[1]; p.z = r[2]; p.intensity = r[3];
+            for (int k = 0; k < 6; ++k) p.cov_vec[k] = r[4 + k];
+            p.cov_trace = r[10];
+        }
     }
     // extractSurroundingKeyFrames(): true when the map was rebuilt; the ids appended come back in lastIds()
     bool extractSurroundingKeyFrames(const Pose &pose_wmap_curr)
     {
         if (pose_ext_.empty()) throw Error("KeyframeMap: setExtrinsics first");
         std::vector<double> e, c;
-        for (const Pose &p : pose_ext_) { const auto a = param(p); e.insert(e.end(), a.begin(), a.end()); c.insert(c.end(), p.cov_.begin(), p.cov_.end()); }
+        packExt(e, c);
         int32_t rebuilt = 0, n_ids = 0;
         ids_.assign(size_t(kf_.pose_keyframes_3d.size()) + 1, 0);
         dev_.check(mlh_local_map_assemble(dev_.ctx(), param(pose_wmap_curr).data(), e.data(), c.data(), (int)pose_ext_.size(), &o_, &rebuilt, &n_ds_[0], &n_ds_[1],
@@ -1915,6 +2005,21 @@ public:
     KeyframePolicy &policy() { return kf_; }
 private:
     static std::array<double, 7> param(const Pose &p) { std::array<double, 7> a; p.toParam(a.data()); return a; }
+    void packExt(std::vector<double> &e, std::vector<double> &c) const
+    {
+        for (const Pose &p : pose_ext_) { const auto a = param(p); e.insert(e.end(), a.begin(), a.end()); c.insert(c.end(), p.cov_.begin(), p.cov_.end()); }
+    }
+    void globalMap(const mlh_global_map_opts &g, const double *pose_cur)
+    {
+        if (pose_ext_.empty()) throw Error("KeyframeMap: setExtrinsics first");
+        std::vector<double> e, c;
+        packExt(e, c);
+        int32_t n_pre[2], n_ds[2], n_ids = 0, n_kf = 0;
+        dev_.check(mlh_local_map_info(dev_.ctx(), &n_kf, nullptr, nullptr, nullptr));
+        gids_.assign(size_t(n_kf) + 1, 0);
+        dev_.check(mlh_global_map_assemble(dev_.ctx(), pose_cur, e.data(), c.data(), (int)pose_ext_.size(), &g, n_pre, n_ds, gids_.data(), &n_ids));
+        gids_.resize(size_t(n_ids));
+    }
     const void *cloud(int kind, int filtered, int32_t *n) const
     {
         const void *p = nullptr;
@@ -1924,8 +2029,9 @@ private:
     Device &dev_;
     KeyframePolicy &kf_;
     mlh_local_map_opts o_{};
+    mlh_global_map_opts g_[2] = {};         // [0] pubGlobalMap's, [1] saveGlobalMap's
     std::vector<Pose> pose_ext_;
-    std::vector<int32_t> ids_;
+    std::vector<int32_t> ids_, gids_;
     int32_t n_ds_[2] = {0, 0};
 };
 
