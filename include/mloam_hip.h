@@ -427,6 +427,59 @@ int mlh_global_map_release(mlh_ctx *ctx);
  * when kf_radius < 0) */
 int mlh_global_map_select(const float *positions_xyz, int n, const float center[3], float kf_radius, float kf_res, int32_t *ids_out, int32_t *n_ids);
 
+/* ---------------------------------------------------------------- (f8) the odometry's sliding window on the device
+ * The estimator keeps, per LiDAR and kind, a CircularBuffer<PointICloud> of WINDOW_SIZE + 1 slots (surf_points_stack_[n], corner_points_stack_[n]); before every
+ * optimizeMap it thins the new scan's features into slot cir_buf_cnt_ (estimator/src/estimator/estimator.cpp:485-496), slides the window (slideWindow,
+ * cpp:1521-1536) and rebuilds one local map per LiDAR (buildLocalMap, cpp:1159-1204; buildCalibMap, cpp:1067-1110). Here the stacks live in HBM as float4 records
+ * {x, y, z, intensity} (stride 16, intensity offset 12: the layout mlh_fused_cloud hands out) and the maps are built from them in one call.
+ * mlh_window_reset: empties the store and sizes it for n_lidar (1..16) LiDARs and window_size (1..16); called again it starts over. mlh_destroy frees it.
+ *   Every other window call returns MLH_ERR_STATE before it.
+ * mlh_window_set: stack[lidar][slot] = the two clouds (cpp:489, 494, for a caller that thinned them itself); slot is the LOGICAL index 0..window_size, as the
+ *   reference's operator[]. Host or device records; n == 0 stores an empty cloud (its pointer may be NULL). A host cloud has been read when the call returns.
+ * mlh_window_set_from_scan: cpp:487-495 device to device for the scan `src` holds after mlh_extract_run + mlh_extract_voxel_run (and mlh_scan_undistort, if the
+ *   caller ran it): its less-sharp points through pcl::VoxelGrid at leaf_corner (0.2, cpp:74), its voxel-thinned less-flat cloud through pcl::VoxelGrid at
+ *   leaf_surf (0.4, cpp:73), the arithmetic of mlh_voxel_grid. src == ctx is the plain case; another context of the same device follows mlh_fuse_add_scan_from's
+ *   rules (src idle, ordered by the same two events: whatever rewrites src's scan next waits for this call's reads).
+ * mlh_window_slide: slideWindow's stack.push(stack[src_slot]) for every LiDAR and both kinds, with CircularBuffer's semantics (utility/CircularBuffer.h:61-67,
+ *   134-137, 186-197), which are not a plain shift: while fewer than window_size + 1 pushes have happened, the copy of logical slot src_slot goes to PHYSICAL slot
+ *   `size` and nothing moves; from then on it overwrites the oldest slot and the start advances, so logical i becomes i - 1 and the new last slot is a copy of the
+ *   old src_slot. operator[] is (start + i) % capacity throughout. REPRODUCED: the INITIAL phase (cpp:505-513) with its push of a still-empty slot and the state in
+ *   which the last two slots hold the same cloud. A slide copies no points: slots name reference-counted ranges of an arena.
+ * mlh_window_cloud: logical slot's cloud of `kind` in HBM for mlh_features_set(..., MLH_MEM_DEVICE); *device_points is NULL when *n == 0. Valid until the next
+ *   mlh_window_set* / _slide / _reset.
+ * mlh_window_info (outputs may be NULL): allocations = device allocations the store and its maps have made since mlh_window_reset; in steady state -- set + slide +
+ *   build on clouds no larger than those seen before -- it stops growing. bytes_used: the records the slots name; bytes_reserved: the store's device memory.
+ * mlh_window_build_local_map: pose_local = n_lidar x (window_size + 1) x 7 doubles [t, q(xyzw)], the reference's pose_local_[n][i] (cpp:1181: the Pose of
+ *   T_pivot^-1 T_i T_ext), computed by the caller; each is used exactly as mlh_transform_point_cloud uses its pose. In the reference's order:
+ *   - per LiDAR n and kind, slots 0 .. window_size - 1 (slot window_size is skipped, cpp:1182) of LiDAR n's stacks (source_lidar < 0: buildLocalMap,
+ *     cpp:1185-1191) or of LiDAR source_lidar's stacks with ITS pose_local rows, for every n (buildCalibMap, cpp:1095-1101, IDX_REF) are transformed and
+ *     appended in slot order to LiDAR n's pre-filter cloud: ONE launch for all n_lidar x window_size x 2 segments (256-point tiles, a tile never straddles a
+ *     segment, empty segments have none), the arithmetic of mlh_transform_point_cloud bit for bit, intensity copied, the stacks untouched;
+ *   - each of the 2 n_lidar pre-filter clouds through pcl::VoxelGrid<PointI> at its leaf (cpp:1103-1109, 1195-1203), the arithmetic of mlh_voxel_grid; an empty
+ *     cloud filters to an empty cloud; a grid of more than 2^31 cells returns the input.
+ *   n_pre / n_ds [2 n_lidar] <- the lengths, index 2 n + kind. One transform launch, one upload of all tables and two host waits per call (the clouds' bounds; the
+ *   filtered counts), whatever window_size and the clouds' sizes are; 2 n_lidar voxel filters.
+ * mlh_window_map_cloud: LiDAR `lidar`'s pre-filter (filtered = 0) or filtered (1) map of `kind` in HBM, for mlh_map_set_pair(..., MLH_MEM_DEVICE); NULL when
+ *   *n == 0. Valid until the next build or reset.
+ * MLH_ERR_INVALID (text in mlh_last_error) for a LiDAR or slot out of range, bad records, non-finite or non-positive leaves, a source_lidar out of range, a null
+ * or non-finite pose_local. A failed call leaves the store as it was. */
+typedef struct mlh_window_map_opts {
+    int32_t source_lidar;       /* < 0: every LiDAR's map from its own stacks (buildLocalMap); >= 0: every map from this LiDAR's stacks (buildCalibMap's IDX_REF) */
+    float leaf_surf[16];        /* per LiDAR, > 0. buildLocalMap: one ratio for all (cpp:1196, 1200); buildCalibMap: 0.4 for IDX_REF, 0.2 for the others (cpp:1103) */
+    float leaf_corner[16];
+} mlh_window_map_opts;
+/* buildLocalMap's values: source_lidar -1, every leaf 0.4 * min(2, max(0.75, n_scans * n_lidar * window_size / 192)) (cpp:1196) */
+void mlh_window_map_opts_default(mlh_window_map_opts *o, int n_scans, int n_lidar, int window_size);
+int mlh_window_reset(mlh_ctx *ctx, int n_lidar, int window_size);
+int mlh_window_set(mlh_ctx *ctx, int lidar, int slot, const void *surf, int n_surf, const void *corner, int n_corner, int stride_bytes, int intensity_offset_bytes,
+                   int mem);
+int mlh_window_set_from_scan(mlh_ctx *ctx, mlh_ctx *src, int lidar, int slot, float leaf_surf, float leaf_corner);
+int mlh_window_slide(mlh_ctx *ctx, int src_slot);
+int mlh_window_cloud(mlh_ctx *ctx, int lidar, int slot, int kind, const void **device_points, int32_t *n);
+int mlh_window_info(mlh_ctx *ctx, int32_t *n_lidar, int32_t *window_size, int64_t *pushes, int64_t *bytes_used, int64_t *bytes_reserved, int64_t *allocations);
+int mlh_window_build_local_map(mlh_ctx *ctx, const double *pose_local, const mlh_window_map_opts *opts, int32_t *n_pre, int32_t *n_ds);
+int mlh_window_map_cloud(mlh_ctx *ctx, int lidar, int kind, int filtered, const void **device_points, int32_t *n);
+
 /* ---------------------------------------------------------------- (a5) local map index
  * replaces pcl::KdTreeFLANN<PointT>::setInputCloud(cloud) as used at
  *   estimator/src/lidarMapper/lidar_mapper_keyframe.cpp:433-434 (and estimator.cpp:1095-1109, 1230-1233).

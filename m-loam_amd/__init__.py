@@ -79,6 +79,24 @@ def global_map_opts(for_save=False, **kw) -> GlobalMapOpts:
     return o
 
 
+class WindowMapOpts(C.Structure):
+    """mlh_window_map_opts: buildLocalMap's / buildCalibMap's parameters"""
+    _fields_ = [("source_lidar", C.c_int32), ("leaf_surf", C.c_float * 16), ("leaf_corner", C.c_float * 16)]
+
+
+def window_map_opts(n_scans=16, n_lidar=1, window_size=3, source_lidar=-1, leaf_surf=None, leaf_corner=None) -> WindowMapOpts:
+    """mlh_window_map_opts_default (buildLocalMap's ratio for every LiDAR), then source_lidar and the given per-LiDAR leaves (a number = the same for all)"""
+    o = WindowMapOpts()
+    load_library().mlh_window_map_opts_default(C.byref(o), int(n_scans), int(n_lidar), int(window_size))
+    o.source_lidar = int(source_lidar)
+    for name, v in (("leaf_surf", leaf_surf), ("leaf_corner", leaf_corner)):
+        if v is not None:
+            arr = getattr(o, name)
+            for i, x in enumerate(np.full(n_lidar, v, np.float32) if np.ndim(v) == 0 else np.asarray(v, np.float32)):
+                arr[i] = float(x)
+    return o
+
+
 def global_map_select(positions_xyz, center, kf_radius, kf_res):
     """mlh_global_map_select (host arithmetic): the keyframes the global map is made of, in the order their clouds are appended"""
     pos = np.ascontiguousarray(positions_xyz, np.float32).reshape(-1, 3)
@@ -179,6 +197,17 @@ def load_library():
     lib.mlh_global_map_cloud.argtypes = [vp, ci, ci, C.POINTER(vp), i32p]
     lib.mlh_global_map_release.argtypes = [vp]
     lib.mlh_global_map_select.argtypes = [vp, ci, vp, cf, cf, vp, i32p]
+    i64p = C.POINTER(C.c_int64)
+    lib.mlh_window_map_opts_default.argtypes = [C.POINTER(WindowMapOpts), ci, ci, ci]
+    lib.mlh_window_map_opts_default.restype = None
+    lib.mlh_window_reset.argtypes = [vp, ci, ci]
+    lib.mlh_window_set.argtypes = [vp, ci, ci, vp, ci, vp, ci, ci, ci, ci]
+    lib.mlh_window_set_from_scan.argtypes = [vp, vp, ci, ci, cf, cf]
+    lib.mlh_window_slide.argtypes = [vp, ci]
+    lib.mlh_window_cloud.argtypes = [vp, ci, ci, ci, C.POINTER(vp), i32p]
+    lib.mlh_window_info.argtypes = [vp, i32p, i32p, i64p, i64p, i64p, i64p]
+    lib.mlh_window_build_local_map.argtypes = [vp, vp, C.POINTER(WindowMapOpts), i32p, i32p]
+    lib.mlh_window_map_cloud.argtypes = [vp, ci, ci, ci, C.POINTER(vp), i32p]
     lib.mlh_downsample_current_scan.argtypes = [vp, ci, vp, ci, ci, ci, ci, cf, vp, vp, ci, vp, ci, cd, vp, C.POINTER(C.c_int32)]
     lib.mlh_track_opts_default.argtypes = [vp]
     lib.mlh_track_opts_default.restype = None
@@ -262,6 +291,8 @@ EXPORTED_SYMBOLS = [
     "mlh_pose_plus", "mlh_eval_degeneracy",
     "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
     "mlh_keyframe_attach_outlier", "mlh_global_map_opts_default", "mlh_global_map_assemble", "mlh_global_map_cloud", "mlh_global_map_release", "mlh_global_map_select",
+    "mlh_window_map_opts_default", "mlh_window_reset", "mlh_window_set", "mlh_window_set_from_scan", "mlh_window_slide", "mlh_window_cloud", "mlh_window_info",
+    "mlh_window_build_local_map", "mlh_window_map_cloud",
 ]
 
 
@@ -811,6 +842,72 @@ class Context:
 
     def global_map_release(self):
         self._ck(self.lib.mlh_global_map_release(self.h))
+
+    # ---- the odometry's sliding window + its local maps (surf / corner_points_stack_, slideWindow, buildLocalMap / buildCalibMap on the device)
+    def window_reset(self, n_lidar, window_size):
+        self._ck(self.lib.mlh_window_reset(self.h, int(n_lidar), int(window_size)))
+
+    def window_set(self, lidar, slot, surf, corner):
+        """stack[lidar][slot] = the two clouds ((n, >= 4) [x y z intensity ...] arrays or device clouds; an empty array stores an empty cloud)"""
+        (ps, ss, ns, ms, ks), (pc, sc, nc, mc, kc) = _src(surf), _src(corner)
+        if ns == 0:
+            ss, ms = sc, mc
+        if nc == 0:
+            sc, mc = ss, ms
+        assert ss == sc and ms == mc, "both clouds share record stride and memory kind"
+        self._ck(self.lib.mlh_window_set(self.h, int(lidar), int(slot), ps if ns else None, ns, pc if nc else None, nc, ss, 12, ms))
+
+    def window_set_from_scan(self, lidar, slot, src=None, leaf_surf=0.4, leaf_corner=0.2):
+        """estimator.cpp:487-495 for the scan `src` (default: this context) holds after extract_run + extract_voxel_run, device to device"""
+        self._ck(self.lib.mlh_window_set_from_scan(self.h, (src or self).h, int(lidar), int(slot), float(leaf_surf), float(leaf_corner)))
+
+    def window_slide(self, src_slot):
+        """slideWindow: stack.push(stack[src_slot]) for every LiDAR and both kinds (CircularBuffer::push)"""
+        self._ck(self.lib.mlh_window_slide(self.h, int(src_slot)))
+
+    def window_cloud(self, lidar, slot, kind) -> "DeviceCloud":
+        ptr, n = C.c_void_p(), C.c_int32(0)
+        self._ck(self.lib.mlh_window_cloud(self.h, int(lidar), int(slot), int(kind), C.byref(ptr), C.byref(n)))
+        return DeviceCloud(ptr.value, n.value)
+
+    def _fetch16(self, dc):
+        if dc.n == 0:
+            return np.zeros((0, 4), np.float32)
+        self.synchronize()
+        out = np.zeros((dc.n, 4), np.float32)
+        e = _hip_runtime().hipMemcpy(out.ctypes.data_as(C.c_void_p), C.c_void_p(dc.ptr), C.c_size_t(dc.n * 16), 2)   # hipMemcpyDeviceToHost
+        if e != 0:
+            raise MlhError(f"hipMemcpy of a window cloud failed ({e})")
+        return out
+
+    def window_fetch(self, lidar, slot, kind):
+        """the slot's cloud copied to the host as (n, 4) float32 [x y z intensity]"""
+        return self._fetch16(self.window_cloud(lidar, slot, kind))
+
+    def window_info(self) -> dict:
+        a, b = C.c_int32(0), C.c_int32(0)
+        v = [C.c_int64(0) for _ in range(4)]
+        self._ck(self.lib.mlh_window_info(self.h, C.byref(a), C.byref(b), *[C.byref(x) for x in v]))
+        return dict(n_lidar=a.value, window_size=b.value, pushes=v[0].value, bytes_used=v[1].value, bytes_reserved=v[2].value, allocations=v[3].value)
+
+    def window_build_local_map(self, pose_local, opts: WindowMapOpts):
+        """buildLocalMap / buildCalibMap from the store: pose_local (n_lidar, window_size + 1, 7) -> dict(n_pre, n_ds), each (n_lidar, 2) [surf, corner]"""
+        info = self.window_info()
+        p = np.ascontiguousarray(pose_local, np.float64)
+        assert p.size == info["n_lidar"] * (info["window_size"] + 1) * 7
+        n_pre, n_ds = np.zeros(2 * info["n_lidar"], np.int32), np.zeros(2 * info["n_lidar"], np.int32)
+        i32p = C.POINTER(C.c_int32)
+        self._ck(self.lib.mlh_window_build_local_map(self.h, _p(p), C.byref(opts), n_pre.ctypes.data_as(i32p), n_ds.ctypes.data_as(i32p)))
+        return dict(n_pre=n_pre.reshape(-1, 2), n_ds=n_ds.reshape(-1, 2))
+
+    def window_map_cloud(self, lidar, kind, filtered=True) -> "DeviceCloud":
+        ptr, n = C.c_void_p(), C.c_int32(0)
+        self._ck(self.lib.mlh_window_map_cloud(self.h, int(lidar), int(kind), int(bool(filtered)), C.byref(ptr), C.byref(n)))
+        return DeviceCloud(ptr.value, n.value)
+
+    def window_map_fetch(self, lidar, kind, filtered=True):
+        """LiDAR `lidar`'s local map of `kind` copied to the host as (n, 4) float32 [x y z intensity]"""
+        return self._fetch16(self.window_map_cloud(lidar, kind, filtered))
 
     # ---- map / features
     def map_set(self, kind, points, min_match_sq_dis=1.0):

@@ -361,6 +361,44 @@ struct KfStore {
     int gpre_n[2] = {0, 0}, gflt_n[2] = {0, 0};
 };
 
+// a rigid transform in single precision (+ the LiDAR index of transformCloudFeature): what the per-point transform kernels of frontend.hip and window.hip apply
+struct FuseXf { float r[9], t[3], id; };
+// rotation of the unit quaternion in double, rounded once to float: what Eigen::Matrix4f holds after `.cast<float>()`
+inline FuseXf xf_from_pose(const double pose[7], float id)
+{
+    const double tx = pose[0], ty = pose[1], tz = pose[2], qx = pose[3], qy = pose[4], qz = pose[5], qw = pose[6];
+    const double R[9] = {1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw),
+                         2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw),
+                         2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)};
+    FuseXf xf;
+    for (int i = 0; i < 9; ++i) xf.r[i] = float(R[i]);
+    xf.t[0] = float(tx); xf.t[1] = float(ty); xf.t[2] = float(tz);
+    xf.id = id;
+    return xf;
+}
+
+// The odometry's sliding window (window.hip; estimator.cpp:485-496, 1521-1536) and the local maps buildLocalMap / buildCalibMap make of it (cpp:1067-1110, 1159-1204)
+struct WinStore {
+    bool ready = false;          // mlh_window_reset has run
+    int n_lidar = 0, window = 0; // NUM_OF_LASER, WINDOW_SIZE: every stack has window + 1 slots
+    // CircularBuffer's three words (CircularBuffer.h:61-67, 134-137, 186-197); every stack is pushed together, so they share them
+    int size = 0, start = 0;
+    long long pushes = 0;
+    // The clouds: float4 {x, y, z, intensity} in one arena per kind, cut into equal slabs of `slab` records (as many slabs as there are slots: a slot's cloud
+    // is named by at most one slab, a slab by any number of slots). A slide moves names and counts, never points. A cloud larger than the slabs re-cuts the arena.
+    DevBuf arena[2];
+    size_t slab[2] = {0, 0};
+    std::vector<int> slab_refs[2], slab_n[2];      // per slab: the slots that name it, its records
+    std::vector<int> slot_slab[2];                 // per (lidar, PHYSICAL slot): its slab, -1 = the empty cloud
+    long long allocations = 0;   // device allocations of the store and its maps since the reset
+    // the local maps of the last build: every LiDAR's pre-filter clouds back to back in `pre` (cloud 2 n + kind at record map_off[2 n + kind]), the filtered
+    // ones at the same offsets in `flt`
+    DevBuf pre, flt, tab;
+    std::vector<int> map_off, map_pre_n, map_flt_n;
+    std::vector<unsigned char> htab;
+    PinnedBuf h_pin;             // landing place of the two read-backs (bounds; filtered counts)
+};
+
 struct SegBuf {    // ImageSegmenter scratch (segment.hip)
     DevBuf raw, pix, owner, range, ground, keep;
     DevBuf edge;               // the cluster search's angle verdicts per pixel (seg_edge_kernel)
@@ -536,6 +574,7 @@ struct mlh_ctx {
     mlh::DevBuf uct_buf;     // point-uncertainty scratch
     mlh::VoxBuf vox;
     mlh::KfStore kf;         // keyframe store + local map (keyframes.hip)
+    mlh::WinStore win;       // the odometry's sliding window + its local maps (window.hip)
     mlh::OdomSet odom;
     mlh::SegBuf seg;
     mlh::TrackSet track;
@@ -800,6 +839,11 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
 // keyframes.hip
 void keyframes_release(mlh_ctx *ctx);
 void global_map_release_run(mlh_ctx *ctx);
+// window.hip
+int window_reset_run(mlh_ctx *ctx, int n_lidar, int window_size);
+// stack[lidar][slot] = the cloud of `kind`: n packed float4 records on the device (read on the context's stream), or none (n == 0). Arguments already validated.
+int window_assign_device(mlh_ctx *ctx, int lidar, int slot, int kind, const float4 *dev, int n);
+int window_check_slot(mlh_ctx *ctx, const char *entry, int lidar, int slot);     // MLH_ERR_STATE before mlh_window_reset, MLH_ERR_INVALID out of range
 // grid.hip
 int grid_build(mlh_ctx *ctx, int kind_mask, bool recompute_bounds);
 int grid_build_grids(mlh_ctx *ctx, mlh::MapGrid **grids, int n_grids, bool recompute_bounds, int *pub_oob = nullptr, mlh::HostPublish *pub = nullptr,

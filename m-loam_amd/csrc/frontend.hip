@@ -10,22 +10,6 @@
 
 namespace mlh {
 
-struct FuseXf { float r[9], t[3], id; };     // a rigid transform in single precision (+ the LiDAR index of transformCloudFeature)
-
-// rotation of the unit quaternion in double, rounded once to float: what Eigen::Matrix4f holds after `.cast<float>()`
-static FuseXf xf_from_pose(const double pose[7], float id)
-{
-    const double tx = pose[0], ty = pose[1], tz = pose[2], qx = pose[3], qy = pose[4], qz = pose[5], qw = pose[6];
-    const double R[9] = {1 - 2 * (qy * qy + qz * qz), 2 * (qx * qy - qz * qw), 2 * (qx * qz + qy * qw),
-                         2 * (qx * qy + qz * qw), 1 - 2 * (qx * qx + qz * qz), 2 * (qy * qz - qx * qw),
-                         2 * (qx * qz - qy * qw), 2 * (qy * qz + qx * qw), 1 - 2 * (qx * qx + qy * qy)};
-    FuseXf xf;
-    for (int i = 0; i < 9; ++i) xf.r[i] = float(R[i]);
-    xf.t[0] = float(tx); xf.t[1] = float(ty); xf.t[2] = float(tz);
-    xf.id = id;
-    return xf;
-}
-
 __global__ __launch_bounds__(256) void gather_points_kernel(const float4 *__restrict__ pts, const int *__restrict__ list, int n, float4 *__restrict__ out)
 {
     const int i = blockIdx.x * 256 + threadIdx.x;

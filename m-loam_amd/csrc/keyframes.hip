@@ -35,6 +35,7 @@
 #include <cmath>
 #include <array>
 #include <cstddef>
+#include "bounds_dev.hpp"
 #include "dev_math.hpp"
 #include "uct_dev.hpp"
 
@@ -69,9 +70,6 @@ struct GmTile {                  // up to 256 points of one (keyframe x kind) se
 // [14..15] filtered counts, [16] total of the tile scan
 constexpr int GM_STATE_INTS = 20, GM_PIN = 32;      // GM_PIN: its first landing word in KfStore::h_pin
 constexpr int GM_MAX_LIDAR = 16, GM_TAB = 7 * GM_MAX_LIDAR + 7 + 43 * GM_MAX_LIDAR;
-
-__device__ __forceinline__ int enc_f(float f) { const int b = __float_as_int(f); return b >= 0 ? b : b ^ 0x7fffffff; }   // order-preserving as int
-inline float dec_f(int b) { const int v = b >= 0 ? b : b ^ 0x7fffffff; float f; std::memcpy(&f, &v, 4); return f; }
 
 template <class T>
 __device__ __forceinline__ int seg_of(const T *s, int n, int i, int T::*key)
@@ -154,31 +152,6 @@ __global__ void kf_prefix_kernel(const KfGat *__restrict__ g, int n0, int n1, co
     const int lo = k == 0 ? 0 : n0, hi = k == 0 ? n0 : n0 + n1;
     for (int e = lo; e < hi; ++e) { gofs[e] = base; base += cnt[g[e].slot2]; }
     dstate[k] = int(base);
-}
-
-// the bounds of what this workgroup wrote (`any`: this thread wrote the point x y z), folded into a cloud's six state words; all 256 threads call it.
-// min / max are exact: any order gives the same result
-__device__ __forceinline__ void wg_fold_bounds(bool any, float x, float y, float z, int *__restrict__ bnd)
-{
-    float mn[3] = {FLT_MAX, FLT_MAX, FLT_MAX}, mx[3] = {-FLT_MAX, -FLT_MAX, -FLT_MAX};
-    if (any) { mn[0] = mx[0] = x; mn[1] = mx[1] = y; mn[2] = mx[2] = z; }
-    __shared__ float red[6][4];
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { mn[d] = fminf(mn[d], __shfl_xor(mn[d], off)); mx[d] = fmaxf(mx[d], __shfl_xor(mx[d], off)); }
-    }
-    const int any_wg = __syncthreads_or(any ? 1 : 0);
-    if ((threadIdx.x & 63) == 0) for (int d = 0; d < 3; ++d) { red[d][threadIdx.x >> 6] = mn[d]; red[3 + d][threadIdx.x >> 6] = mx[d]; }
-    __syncthreads();
-    if (threadIdx.x == 0 && any_wg) {
-        for (int d = 0; d < 3; ++d) {
-            const float a = fminf(fminf(red[d][0], red[d][1]), fminf(red[d][2], red[d][3]));
-            const float b = fmaxf(fmaxf(red[3 + d][0], red[3 + d][1]), fmaxf(red[3 + d][2], red[3 + d][3]));
-            atomicMin(bnd + d, enc_f(a));
-            atomicMax(bnd + 3 + d, enc_f(b));
-        }
-    }
 }
 
 __global__ __launch_bounds__(256) void kf_gather_kernel(const float4 *__restrict__ cache, const KfGat *__restrict__ g, int n0, int n1, int ub0, int ub1,

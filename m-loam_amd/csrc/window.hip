@@ -1,0 +1,394 @@
+// The odometry's sliding window and the local maps built from it, on the device (gfx950).
+//
+// The estimator keeps per LiDAR and kind a CircularBuffer<PointICloud> of WINDOW_SIZE + 1 slots (surf_points_stack_[n], corner_points_stack_[n]). Before every
+// optimizeMap it thins the new scan's features into a slot (estimator/src/estimator/estimator.cpp:485-496), slides the window (slideWindow, cpp:1521-1536) and
+// rebuilds one local map per LiDAR (buildLocalMap, cpp:1159-1204; buildCalibMap, cpp:1067-1110). Here:
+//   the store   float4 {x, y, z, intensity} records, the layout of FeatSet::pts and of the keyframe store, in one arena per kind cut into equal slabs. A slot names
+//               a slab (or the empty cloud), a slab counts the slots that name it: slideWindow's push (CircularBuffer.h:186-197) moves names and counts on the host
+//               and copies no point. A cloud larger than the slabs re-cuts the arena (one allocation); in steady state nothing is allocated or freed.
+//   the maps    host: a table of 256-point TILES over the n_lidar x window_size x 2 segments in destination order (per LiDAR, per kind, per slot; a tile never
+//               straddles a segment, an empty segment has none) and one FuseXf per (LiDAR, slot) from pose_local (xf_from_pose: the rotation in double, rounded once);
+//   wm_transform_kernel   pcl::transformPointCloud of one tile per workgroup (cpp:1185-1191 / 1095-1101): the tile's transform is uniform and is loaded ONCE per workgroup
+//               into LDS; the per-point expression is transform_cloud_kernel's (frontend.hip), term for term, so the bits are mlh_transform_point_cloud's. The record
+//               goes straight to its place in the pre-filter cloud (`+=` in slot order), the intensity is copied, the source is left untouched, and the cloud's bounds
+//               are folded once per workgroup (bounds_dev.hpp);
+//   voxel_filter_run x 2 n_lidar   pcl::VoxelGrid<PointI> per pre-filter cloud at its leaf (cpp:1103-1109, 1195-1203), bounds known, counts left on the device.
+// Per build: ONE transform launch and one upload of every table, whatever window_size and the segment sizes are; host waits: two (the clouds' bounds; the filtered
+// counts), plus the one inside a voxel filter whose grid has more than 2^31 cells (the input comes back) and one for a map buffer that has to grow.
+#include "ctx.hpp"
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include "bounds_dev.hpp"
+
+namespace mlh {
+
+namespace {
+
+constexpr int WIN_MAX = 16;                 // LiDARs, window size
+struct WmTile {                             // up to 256 points of one (LiDAR x kind x slot) segment
+    long long src;                          // its first record in the arena of its kind
+    int begin;                              // its first point's place among the call's points in destination order
+    int n;                                  // 1 .. 256
+    int xf;                                 // its transform in the table
+    int cloud;                              // 2 * lidar + kind: the output cloud it belongs to
+};
+
+__global__ __launch_bounds__(256) void wm_transform_kernel(const float4 *__restrict__ arena_surf, const float4 *__restrict__ arena_corner, const WmTile *__restrict__ tiles,
+                                                           const FuseXf *__restrict__ xfs, float4 *__restrict__ pre, int *__restrict__ bounds)
+{
+    __shared__ FuseXf s_xf;
+    const WmTile t = tiles[blockIdx.x];
+    if (threadIdx.x < sizeof(FuseXf) / sizeof(float)) reinterpret_cast<float *>(&s_xf)[threadIdx.x] = reinterpret_cast<const float *>(xfs + t.xf)[threadIdx.x];
+    __syncthreads();
+    const FuseXf &xf = s_xf;
+    const bool mine = int(threadIdx.x) < t.n;
+    float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (mine) {
+        const float4 p = ((t.cloud & 1) ? arena_corner : arena_surf)[t.src + threadIdx.x];
+        // transform_cloud_kernel's expression: products and sums kept separate (no contraction)
+        o.x = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(xf.r[0], p.x), __fmul_rn(xf.r[1], p.y)), __fmul_rn(xf.r[2], p.z)), xf.t[0]);
+        o.y = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(xf.r[3], p.x), __fmul_rn(xf.r[4], p.y)), __fmul_rn(xf.r[5], p.z)), xf.t[1]);
+        o.z = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(xf.r[6], p.x), __fmul_rn(xf.r[7], p.y)), __fmul_rn(xf.r[8], p.z)), xf.t[2]);
+        o.w = p.w;
+        pre[size_t(t.begin) + threadIdx.x] = o;
+    }
+    wg_fold_bounds(mine, o.x, o.y, o.z, bounds + 6 * t.cloud);
+}
+
+template <class T> size_t put(std::vector<unsigned char> &h, const T *p, size_t n)
+{
+    size_t off = (h.size() + 15) & ~size_t(15);
+    h.resize(off + sizeof(T) * n);
+    if (n && p) std::memcpy(h.data() + off, p, sizeof(T) * n);
+    return off;
+}
+
+// a buffer of the store brought to `bytes` (contents dropped); counted when it allocates
+hipError_t win_ensure(WinStore &W, DevBuf &b, size_t bytes)
+{
+    if (bytes > b.cap) ++W.allocations;
+    return b.ensure(bytes);
+}
+
+int slot_index(const WinStore &W, int lidar, int slot) { return lidar * (W.window + 1) + (W.start + slot) % (W.window + 1); }
+
+void slab_unref(WinStore &W, int kind, int s)
+{
+    if (s >= 0 && --W.slab_refs[kind][size_t(s)] == 0) W.slab_n[kind][size_t(s)] = 0;
+}
+
+// The arena of `kind` re-cut into slabs of at least n records, the live slabs copied over. The old arena is let go of only behind those copies.
+int arena_recut(mlh_ctx *ctx, int kind, int n)
+{
+    WinStore &W = ctx->win;
+    hipStream_t st = ctx->stream;
+    const size_t n_slabs = W.slab_refs[kind].size(), slab = size_t(n) + size_t(n) / 4 + 64;
+    DevBuf fresh;
+    ++W.allocations;
+    MLH_HIP(ctx, fresh.ensure(sizeof(float4) * slab * n_slabs));
+    bool copied = false;
+    for (size_t s = 0; s < n_slabs; ++s) {
+        if (W.slab_refs[kind][s] == 0 || W.slab_n[kind][s] == 0) continue;
+        MLH_HIP(ctx, hipMemcpyAsync(fresh.as<float4>() + s * slab, W.arena[kind].as<float4>() + s * W.slab[kind], sizeof(float4) * size_t(W.slab_n[kind][s]),
+                                    hipMemcpyDeviceToDevice, st));
+        copied = true;
+    }
+    if (copied || W.arena[kind].p) MLH_HIP(ctx, hipStreamSynchronize(st));      // (an earlier launch may still be reading the old arena)
+    std::swap(W.arena[kind].p, fresh.p);
+    std::swap(W.arena[kind].cap, fresh.cap);
+    W.slab[kind] = slab;
+    return MLH_OK;
+}
+
+bool bad_pose(const double *p) { for (int i = 0; i < 7; ++i) if (!std::isfinite(p[i])) return true; return false; }
+
+}  // namespace
+
+int window_check_slot(mlh_ctx *ctx, const char *entry, int lidar, int slot)
+{
+    const WinStore &W = ctx->win;
+    if (!W.ready) return fail(ctx, MLH_ERR_STATE, (std::string(entry) + ": mlh_window_reset comes first").c_str());
+    if (lidar < 0 || lidar >= W.n_lidar) return fail(ctx, MLH_ERR_INVALID, (std::string(entry) + ": no such LiDAR").c_str());
+    if (slot < 0 || slot > W.window) return fail(ctx, MLH_ERR_INVALID, (std::string(entry) + ": the slot is outside 0 .. window_size").c_str());
+    return MLH_OK;
+}
+
+int window_reset_run(mlh_ctx *ctx, int n_lidar, int window_size)
+{
+    if (n_lidar < 1 || n_lidar > WIN_MAX || window_size < 1 || window_size > WIN_MAX)
+        return fail(ctx, MLH_ERR_INVALID, "mlh_window_reset: n_lidar and window_size are 1..16");
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    WinStore &W = ctx->win;
+    const size_t n_slots = size_t(n_lidar) * size_t(window_size + 1);
+    for (int k = 0; k < 2; ++k) {
+        W.arena[k].release();
+        W.slab[k] = 0;
+        W.slab_refs[k].assign(n_slots, 0);
+        W.slab_n[k].assign(n_slots, 0);
+        W.slot_slab[k].assign(n_slots, -1);
+    }
+    W.pre.release(); W.flt.release(); W.tab.release();
+    W.map_off.assign(size_t(2 * n_lidar), 0); W.map_pre_n.assign(size_t(2 * n_lidar), 0); W.map_flt_n.assign(size_t(2 * n_lidar), 0);
+    W.n_lidar = n_lidar; W.window = window_size;
+    W.size = 0; W.start = 0; W.pushes = 0; W.allocations = 0;
+    W.ready = true;
+    return MLH_OK;
+}
+
+int window_assign_device(mlh_ctx *ctx, int lidar, int slot, int kind, const float4 *dev, int n)
+{
+    WinStore &W = ctx->win;
+    const size_t at = size_t(slot_index(W, lidar, slot));
+    if (n > 0 && size_t(n) > W.slab[kind]) { const int rc = arena_recut(ctx, kind, n); if (rc) return rc; }
+    slab_unref(W, kind, W.slot_slab[kind][at]);
+    W.slot_slab[kind][at] = -1;
+    if (n <= 0) return MLH_OK;
+    // as many slabs as slots, and this slot names none: one is free
+    int s = 0;
+    while (W.slab_refs[kind][size_t(s)] != 0) ++s;
+    MLH_HIP(ctx, hipMemcpyAsync(W.arena[kind].as<float4>() + size_t(s) * W.slab[kind], dev, sizeof(float4) * size_t(n), hipMemcpyDeviceToDevice, ctx->stream));
+    W.slab_refs[kind][size_t(s)] = 1;
+    W.slab_n[kind][size_t(s)] = n;
+    W.slot_slab[kind][at] = s;
+    return MLH_OK;
+}
+
+static int window_set_run(mlh_ctx *ctx, int lidar, int slot, const void *surf, int n_surf, const void *corner, int n_corner, int stride, int ioff, int mem)
+{
+    { const int rc = window_check_slot(ctx, "mlh_window_set", lidar, slot); if (rc) return rc; }
+    if (ioff < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_window_set: bad intensity_offset_bytes (the stored clouds keep the intensity)");
+    const void *src[2] = {surf, corner};
+    const int n[2] = {n_surf, n_corner};
+    Records r[2];
+    size_t off[2] = {0, 0}, total = 0;
+    for (int k = 0; k < 2; ++k) {
+        r[k] = records_of(src[k], stride, n[k], mem, ioff);
+        { const int rc = records_check(ctx, "mlh_window_set", r[k], true); if (rc) return rc; }
+        off[k] = total; total += ((r[k].bytes() + 255) / 256) * 256;
+    }
+    hipStream_t st = ctx->stream;
+    // records that are not the store's own float4 {x, y, z, intensity} are packed into a scratch block first (not ctx->tmp: the host clouds are staged there)
+    const bool as_stored = stride == int(sizeof(float4)) && ioff == 12;
+    if (mem == MLH_MEM_HOST && total > 0) MLH_HIP(ctx, ctx->tmp.ensure(total));
+    if (!as_stored) MLH_HIP(ctx, ctx->knn_q.ensure(sizeof(float4) * (size_t(n[0]) + size_t(n[1]) + 1)));
+    const float4 *packed[2] = {nullptr, nullptr};
+    for (int k = 0; k < 2; ++k) {
+        if (n[k] == 0) continue;
+        const unsigned char *s;
+        { const int rc = records_stage(ctx, r[k], ctx->tmp, st, &s, off[k]); if (rc) return rc; }
+        if (as_stored) { packed[k] = reinterpret_cast<const float4 *>(s); continue; }
+        float4 *dst = ctx->knn_q.as<float4>() + (k == 0 ? 0 : n[0]);
+        pack_points_launch(st, s, stride, n[k], ioff, 0.f, -1, dst, nullptr);
+        packed[k] = dst;
+    }
+    MLH_HIP(ctx, hipGetLastError());
+    for (int k = 0; k < 2; ++k) { const int rc = window_assign_device(ctx, lidar, slot, k, packed[k], n[k]); if (rc) return rc; }
+    if (mem == MLH_MEM_HOST) MLH_HIP(ctx, hipStreamSynchronize(st));      // the caller's clouds have been read when the call returns
+    return MLH_OK;
+}
+
+static int window_slide_run(mlh_ctx *ctx, int src_slot)
+{
+    { const int rc = window_check_slot(ctx, "mlh_window_slide", 0, src_slot); if (rc) return rc; }
+    WinStore &W = ctx->win;
+    const int cap = W.window + 1;
+    const int from = (W.start + src_slot) % cap;            // operator[] (CircularBuffer.h:134-137)
+    const int to = W.size < cap ? W.size : W.start;         // push (CircularBuffer.h:186-197)
+    for (int k = 0; k < 2; ++k)
+        for (int l = 0; l < W.n_lidar; ++l) {
+            const int s = W.slot_slab[k][size_t(l * cap + from)];
+            if (s >= 0) ++W.slab_refs[k][size_t(s)];        // (first: `to` may be `from`)
+            slab_unref(W, k, W.slot_slab[k][size_t(l * cap + to)]);
+            W.slot_slab[k][size_t(l * cap + to)] = s;
+        }
+    if (W.size < cap) ++W.size;
+    else W.start = (W.start + 1) % cap;
+    ++W.pushes;
+    return MLH_OK;
+}
+
+static int window_cloud_run(mlh_ctx *ctx, int lidar, int slot, int kind, const void **device_points, int32_t *n)
+{
+    { const int rc = window_check_slot(ctx, "mlh_window_cloud", lidar, slot); if (rc) return rc; }
+    if (kind < 0 || kind > 1 || !device_points || !n) return fail(ctx, MLH_ERR_INVALID, "mlh_window_cloud: bad arguments");
+    const WinStore &W = ctx->win;
+    const int s = W.slot_slab[kind][size_t(slot_index(W, lidar, slot))];
+    *n = s < 0 ? 0 : W.slab_n[kind][size_t(s)];
+    *device_points = s < 0 ? nullptr : W.arena[kind].as<float4>() + size_t(s) * W.slab[kind];
+    return MLH_OK;
+}
+
+static int window_info_run(mlh_ctx *ctx, int32_t *n_lidar, int32_t *window_size, int64_t *pushes, int64_t *bytes_used, int64_t *bytes_reserved, int64_t *allocations)
+{
+    const WinStore &W = ctx->win;
+    if (!W.ready) return fail(ctx, MLH_ERR_STATE, "mlh_window_info: mlh_window_reset comes first");
+    if (n_lidar) *n_lidar = W.n_lidar;
+    if (window_size) *window_size = W.window;
+    if (pushes) *pushes = W.pushes;
+    if (bytes_used) {
+        int64_t used = 0;
+        for (int k = 0; k < 2; ++k) for (size_t s = 0; s < W.slab_refs[k].size(); ++s) if (W.slab_refs[k][s] > 0) used += int64_t(sizeof(float4)) * W.slab_n[k][s];
+        *bytes_used = used;
+    }
+    if (bytes_reserved) *bytes_reserved = int64_t(W.arena[0].cap + W.arena[1].cap + W.pre.cap + W.flt.cap + W.tab.cap);
+    if (allocations) *allocations = W.allocations;
+    return MLH_OK;
+}
+
+static int window_build_local_map_run(mlh_ctx *ctx, const double *pose_local, const mlh_window_map_opts *o, int32_t *n_pre, int32_t *n_ds)
+{
+    WinStore &W = ctx->win;
+    if (!W.ready) return fail(ctx, MLH_ERR_STATE, "mlh_window_build_local_map: mlh_window_reset comes first");
+    if (!pose_local || !o || !n_pre || !n_ds) return fail(ctx, MLH_ERR_INVALID, "mlh_window_build_local_map: bad arguments (pose_local, opts, n_pre and n_ds are needed)");
+    if (o->source_lidar >= W.n_lidar) return fail(ctx, MLH_ERR_INVALID, "mlh_window_build_local_map: no such source_lidar");
+    const auto pos_finite = [](float v) { return std::isfinite(v) && v > 0.f; };
+    for (int l = 0; l < W.n_lidar; ++l)
+        if (!pos_finite(o->leaf_surf[l]) || !pos_finite(o->leaf_corner[l])) return fail(ctx, MLH_ERR_INVALID, "mlh_window_build_local_map: every LiDAR's leaves must be finite and > 0");
+    const int cap = W.window + 1, n_clouds = 2 * W.n_lidar;
+    for (int i = 0; i < W.n_lidar * cap; ++i) if (bad_pose(pose_local + 7 * i)) return fail(ctx, MLH_ERR_INVALID, "mlh_window_build_local_map: non-finite pose_local");
+    hipStream_t st = ctx->stream;
+
+    // the transforms and the tiles, in destination order
+    std::vector<FuseXf> xfs(size_t(W.n_lidar * cap));
+    for (int i = 0; i < W.n_lidar * cap; ++i) xfs[size_t(i)] = xf_from_pose(pose_local + 7 * i, 0.f);
+    std::vector<WmTile> tiles;
+    std::vector<int> off(size_t(n_clouds), 0), len(size_t(n_clouds), 0);
+    size_t N = 0;
+    for (int l = 0; l < W.n_lidar; ++l) {
+        const int from = o->source_lidar < 0 ? l : o->source_lidar;
+        for (int k = 0; k < 2; ++k) {
+            const int c = 2 * l + k;
+            off[size_t(c)] = int(N);
+            for (int i = 0; i < W.window; ++i) {            // slot window_size is skipped (cpp:1182)
+                const int s = W.slot_slab[k][size_t(slot_index(W, from, i))];
+                const int n = s < 0 ? 0 : W.slab_n[k][size_t(s)];
+                for (int at = 0; at < n; at += 256)
+                    tiles.push_back(WmTile{(long long)(size_t(s) * W.slab[k] + size_t(at)), int(N) + at, std::min(256, n - at), from * cap + i, c});
+                N += size_t(n);
+                if (N > size_t(INT_MAX) / 2) return fail(ctx, MLH_ERR_NOMEM, "window map: too many points");
+            }
+            len[size_t(c)] = int(N) - off[size_t(c)];
+        }
+    }
+    W.map_off = off; W.map_pre_n = len; W.map_flt_n.assign(size_t(n_clouds), 0);
+    for (int c = 0; c < n_clouds; ++c) { n_pre[c] = len[size_t(c)]; n_ds[c] = 0; }
+    if (tiles.empty()) return MLH_OK;                       // every contributing slot is empty
+
+    // buffers, and one upload of every table of the call (the state words start as: empty bounds, no filtered records)
+    MLH_HIP(ctx, win_ensure(W, W.pre, sizeof(float4) * (N + 1)));
+    MLH_HIP(ctx, win_ensure(W, W.flt, sizeof(float4) * (N + 1)));
+    MLH_HIP(ctx, W.h_pin.ensure(sizeof(int) * 7 * 2 * WIN_MAX));
+    int *h_pin = W.h_pin.as<int>();
+    std::vector<int> state0(size_t(7 * n_clouds), 0);       // [6 c .. 6 c + 5] cloud c's bounds (order-preserving int encoding), [6 n_clouds + c] its filtered count
+    for (int c = 0; c < n_clouds; ++c) for (int d = 0; d < 3; ++d) { state0[size_t(6 * c + d)] = INT_MAX; state0[size_t(6 * c + 3 + d)] = INT_MIN; }
+    std::vector<unsigned char> &h = W.htab;
+    h.clear();
+    const size_t o_xf = put(h, xfs.data(), xfs.size());
+    const size_t o_til = put(h, tiles.data(), tiles.size());
+    const size_t o_sta = put(h, state0.data(), state0.size());
+    MLH_HIP(ctx, win_ensure(W, W.tab, h.size() + 16));
+    unsigned char *dt = W.tab.as<unsigned char>();
+    MLH_HIP(ctx, hipMemcpyAsync(dt, h.data(), h.size(), hipMemcpyHostToDevice, st));
+    int *state = reinterpret_cast<int *>(dt + o_sta);
+    float4 *pre = W.pre.as<float4>(), *flt = W.flt.as<float4>();
+
+    MLH_LAUNCH(wm_transform_kernel, dim3(unsigned(tiles.size())), dim3(256), 0, st, (const float4 *)W.arena[0].as<float4>(), (const float4 *)W.arena[1].as<float4>(),
+               reinterpret_cast<const WmTile *>(dt + o_til), reinterpret_cast<const FuseXf *>(dt + o_xf), pre, state);
+    MLH_HIP(ctx, hipGetLastError());
+    // wait 1: the pre-filter clouds' bounds
+    MLH_HIP(ctx, hipMemcpyAsync(h_pin, state, sizeof(int) * 6 * size_t(n_clouds), hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, stream_wait_spin(ctx));
+    // pcl::VoxelGrid<PointI> per cloud (cpp:1103-1109, 1195-1203)
+    for (int c = 0; c < n_clouds; ++c) {
+        const int n = len[size_t(c)];
+        if (n == 0) continue;                               // (its filtered count stays at the 0 it was uploaded with)
+        float bounds[6];
+        for (int d = 0; d < 6; ++d) bounds[d] = dec_f(h_pin[6 * c + d]);
+        const float leaf = (c & 1) ? o->leaf_corner[c >> 1] : o->leaf_surf[c >> 1];
+        int dummy = 0;
+        const int rc = voxel_filter_run(ctx, pre + off[size_t(c)], 16, n, 12, -1, -1, leaf, 0.f, nullptr, &dummy, MLH_MEM_DEVICE, bounds, false, true);
+        if (rc) return rc;
+        MLH_HIP(ctx, hipMemcpyAsync(flt + off[size_t(c)], ctx->vox.out.p, sizeof(float4) * size_t(n), hipMemcpyDeviceToDevice, st));
+        MLH_HIP(ctx, hipMemcpyAsync(state + 6 * n_clouds + c, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, st));
+    }
+    // wait 2: the filtered counts
+    MLH_HIP(ctx, hipMemcpyAsync(h_pin, state + 6 * n_clouds, sizeof(int) * size_t(n_clouds), hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, stream_wait_spin(ctx));
+    for (int c = 0; c < n_clouds; ++c) { W.map_flt_n[size_t(c)] = h_pin[c]; n_ds[c] = h_pin[c]; }
+    return device_error_check(ctx);
+}
+
+static int window_map_cloud_run(mlh_ctx *ctx, int lidar, int kind, int filtered, const void **device_points, int32_t *n)
+{
+    { const int rc = window_check_slot(ctx, "mlh_window_map_cloud", lidar, 0); if (rc) return rc; }
+    if (kind < 0 || kind > 1 || (filtered != 0 && filtered != 1) || !device_points || !n) return fail(ctx, MLH_ERR_INVALID, "mlh_window_map_cloud: bad arguments");
+    const WinStore &W = ctx->win;
+    const size_t c = size_t(2 * lidar + kind);
+    *n = filtered ? W.map_flt_n[c] : W.map_pre_n[c];
+    *device_points = *n == 0 ? nullptr : (filtered ? W.flt : W.pre).as<float4>() + W.map_off[c];
+    return MLH_OK;
+}
+
+}  // namespace mlh
+
+using namespace mlh;
+
+extern "C" {
+
+void mlh_window_map_opts_default(mlh_window_map_opts *o, int n_scans, int n_lidar, int window_size)
+{
+    if (!o) return;
+    std::memset(o, 0, sizeof(*o));
+    o->source_lidar = -1;
+    const float ratio = 0.4 * std::min(2.0, std::max(0.75, 1.0 / 192 * float(n_scans * n_lidar * window_size)));      // cpp:1196
+    for (int l = 0; l < WIN_MAX; ++l) o->leaf_surf[l] = o->leaf_corner[l] = ratio;
+}
+
+int mlh_window_reset(mlh_ctx *ctx, int n_lidar, int window_size)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_reset_run(ctx, n_lidar, window_size);
+}
+
+int mlh_window_set(mlh_ctx *ctx, int lidar, int slot, const void *surf, int n_surf, const void *corner, int n_corner, int stride_bytes, int intensity_offset_bytes,
+                   int mem)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_set_run(ctx, lidar, slot, surf, n_surf, corner, n_corner, stride_bytes, intensity_offset_bytes, mem);
+}
+
+int mlh_window_slide(mlh_ctx *ctx, int src_slot)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return window_slide_run(ctx, src_slot);
+}
+
+int mlh_window_cloud(mlh_ctx *ctx, int lidar, int slot, int kind, const void **device_points, int32_t *n)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return window_cloud_run(ctx, lidar, slot, kind, device_points, n);
+}
+
+int mlh_window_info(mlh_ctx *ctx, int32_t *n_lidar, int32_t *window_size, int64_t *pushes, int64_t *bytes_used, int64_t *bytes_reserved, int64_t *allocations)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return window_info_run(ctx, n_lidar, window_size, pushes, bytes_used, bytes_reserved, allocations);
+}
+
+int mlh_window_build_local_map(mlh_ctx *ctx, const double *pose_local, const mlh_window_map_opts *opts, int32_t *n_pre, int32_t *n_ds)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_build_local_map_run(ctx, pose_local, opts, n_pre, n_ds);
+}
+
+int mlh_window_map_cloud(mlh_ctx *ctx, int lidar, int kind, int filtered, const void **device_points, int32_t *n)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return window_map_cloud_run(ctx, lidar, kind, filtered, device_points, n);
+}
+
+}  // extern "C"

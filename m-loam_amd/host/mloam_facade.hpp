@@ -1586,8 +1586,117 @@ public:
         dev_.check(mlh_pure_odom_add_matches_gf(dev_.ctx(), kind, rel, pv, pi, pe, 5, 0u, P.MIN_MATCH_SQ_DIS, P.MIN_PLANE_DIS, frame - 1, laser, gf_ratio, seed, sel.data(), &n_sel));
         sel_feature_idx.assign(sel.begin(), sel.begin() + n_sel);
     }
+    // addMatches for the feature set of `type` that is already staged on the device (SlidingWindowMap::useFeatures: a window cloud, no host hop)
+    template <typename PoseT>
+    void addStagedMatches(char type, const PoseT &pose_local, int frame, int laser, size_t n_neigh = 5, bool check_fov = true)
+    {
+        double pose[7];
+        detail::pose_to_param(pose_local, pose);
+        const Params &P = params();
+        dev_.check(mlh_pure_odom_add_matches(dev_.ctx(), type == 's' ? MLH_SURF : MLH_CORNER, pose, (int)n_neigh, check_fov ? MLH_FLAG_CHECK_FOV : 0u, P.MIN_MATCH_SQ_DIS,
+                                             P.MIN_PLANE_DIS, frame - 1, laser));
+    }
 private:
     Device &dev_;
+};
+
+// The estimator's window in HBM (mlh_window_*): surf_points_stack_ / corner_points_stack_ (CircularBuffer<PointICloud> of WINDOW_SIZE + 1 slots per LiDAR), the
+// thinning of a new scan into a slot (estimator.cpp:485-496), slideWindow (cpp:1521-1536) and buildLocalMap / buildCalibMap (cpp:1159-1204 / 1067-1110) under the
+// reference's names. The stacks and the maps stay on the device; useLocalMap / useFeatures stage them for WindowFactorTable::addStagedMatches, so the loop of
+// cpp:1228-1266 runs without a host cloud:
+//     win.buildLocalMap(pose_local_);
+//     for n: win.useLocalMap(n); for i in pivot + 1 .. WINDOW_SIZE, kind: if (win.useFeatures(n, i, kind)) table.addStagedMatches(type, pose_local_[n][i], i - pivot, n);
+// pose_local[n][i] is the reference's pose_local_[n][i] = Pose(T_pivot^-1 T_i T_ext) (cpp:1181), computed by the caller.
+class SlidingWindowMap {
+public:
+    struct DeviceCloud { const void *points = nullptr; int32_t n = 0; };      // float4 {x, y, z, intensity} records in HBM: stride 16, intensity offset 12
+    SlidingWindowMap(Device &dev, int num_of_laser, int window_size, int n_scans) : dev_(dev), n_laser_(num_of_laser), window_(window_size)
+    {
+        dev_.check(mlh_window_reset(dev_.ctx(), num_of_laser, window_size));
+        mlh_window_map_opts_default(&o_, n_scans, num_of_laser, window_size);
+    }
+    // the leaves of down_size_filter_surf_ / down_size_filter_corner_ (cpp:73-74) for setCloudFromScan
+    void setScanLeaves(float leaf_surf, float leaf_corner) { scan_leaf_[0] = leaf_surf; scan_leaf_[1] = leaf_corner; }
+    // surf_points_stack_[n][slot] = surf; corner_points_stack_[n][slot] = corner (cpp:489, 494: the caller thinned them)
+    void setCloud(size_t n, size_t slot, const PointICloud &surf, const PointICloud &corner)
+    {
+        dev_.check(mlh_window_set(dev_.ctx(), (int)n, (int)slot, surf.points.data(), (int)surf.size(), corner.points.data(), (int)corner.size(), (int)sizeof(PointI),
+                                  point_traits<PointI>::intensity_off, MLH_MEM_HOST));
+    }
+    // cpp:487-495 for the scan `src` holds (FeatureExtract::extractCloudOnDevice; `src` may be this Device or an idle one of the same GPU), device to device
+    void setCloudFromScan(size_t n, size_t slot, Device &src) { dev_.check(mlh_window_set_from_scan(dev_.ctx(), src.ctx(), (int)n, (int)slot, scan_leaf_[0], scan_leaf_[1])); }
+    void slideWindow(size_t cir_buf_cnt) { dev_.check(mlh_window_slide(dev_.ctx(), (int)cir_buf_cnt)); }
+    // pose_local[n][i]: NUM_OF_LASER x (WINDOW_SIZE + 1) poses
+    template <typename PoseTable> void buildLocalMap(const PoseTable &pose_local)
+    {
+        mlh_window_map_opts o = o_;
+        o.source_lidar = -1;
+        build(pose_local, o);
+    }
+    // every LiDAR's map from IDX_REF's stacks, 0.4 for the reference LiDAR and 0.2 for the others (cpp:1095-1109)
+    template <typename PoseTable> void buildCalibMap(const PoseTable &pose_local, int idx_ref)
+    {
+        mlh_window_map_opts o = o_;
+        o.source_lidar = idx_ref;
+        for (int n = 0; n < n_laser_; ++n) o.leaf_surf[n] = o.leaf_corner[n] = n == idx_ref ? 0.4f : 0.2f;
+        build(pose_local, o);
+    }
+    mlh_window_map_opts &opts() { return o_; }
+    // {surf,corner}_points_local_map_filtered_[n] (filtered) or {surf,corner}_points_local_map_[n]; valid until the next build
+    DeviceCloud localMap(size_t n, int kind, bool filtered = true) const
+    {
+        DeviceCloud d;
+        dev_.check(mlh_window_map_cloud(dev_.ctx(), (int)n, kind, filtered ? 1 : 0, &d.points, &d.n));
+        return d;
+    }
+    // {surf,corner}_points_stack_[n][slot]; valid until the next setCloud* / slideWindow
+    DeviceCloud stackCloud(size_t n, size_t slot, int kind) const
+    {
+        DeviceCloud d;
+        dev_.check(mlh_window_cloud(dev_.ctx(), (int)n, (int)slot, kind, &d.points, &d.n));
+        return d;
+    }
+    size_t mapSize(size_t n, int kind, bool filtered = true) const { return filtered ? n_ds_[2 * n + size_t(kind)] : n_pre_[2 * n + size_t(kind)]; }
+    // kdtree_{surf,corner}_points_local_map->setInputCloud(..._local_map_filtered_[n]) (cpp:1228-1232): both indices of LiDAR n in one set of launches
+    void useLocalMap(size_t n, float min_match_sq_dis = params().MIN_MATCH_SQ_DIS)
+    {
+        const DeviceCloud s = localMap(n, MLH_SURF), c = localMap(n, MLH_CORNER);
+        if (s.n == 0 || c.n == 0) throw Error("useLocalMap: empty local map");
+        dev_.check(mlh_map_set_pair(dev_.ctx(), s.points, s.n, c.points, c.n, 16, min_match_sq_dis, MLH_MEM_DEVICE));
+    }
+    // the features of (LiDAR n, slot, kind) become the staged feature set of `kind`; returns their number (0: nothing staged, nothing to match)
+    int useFeatures(size_t n, size_t slot, int kind)
+    {
+        const DeviceCloud f = stackCloud(n, slot, kind);
+        if (f.n > 0) dev_.check(mlh_features_set(dev_.ctx(), kind, f.points, 16, f.n, 12, -1, MLH_MEM_DEVICE));
+        return f.n;
+    }
+    // a device cloud copied into a host PointICloud (`copy_to_host(dst, src, bytes)`: the caller's device-to-host copy -- this header stays free of the HIP runtime)
+    template <class CopyToHost> void fetchCloud(const DeviceCloud &d, PointICloud &out, CopyToHost copy_to_host) const
+    {
+        out.points.clear();
+        if (d.n <= 0) return;
+        dev_.check(mlh_synchronize(dev_.ctx()));
+        std::vector<float> rec(size_t(d.n) * 4);
+        copy_to_host(rec.data(), d.points, rec.size() * sizeof(float));
+        out.points.resize(size_t(d.n));
+        for (size_t i = 0; i < size_t(d.n); ++i) { PointI &p = out.points[i]; p.x = rec[4 * i]; p.y = rec[4 * i + 1]; p.z = rec[4 * i + 2]; p.intensity = rec[4 * i + 3]; }
+    }
+    Device &device() { return dev_; }
+private:
+    template <typename PoseTable> void build(const PoseTable &pose_local, const mlh_window_map_opts &o)
+    {
+        std::vector<double> p(size_t(n_laser_) * size_t(window_ + 1) * 7);
+        for (int n = 0; n < n_laser_; ++n)
+            for (int i = 0; i <= window_; ++i) detail::pose_to_param(pose_local[size_t(n)][size_t(i)], &p[(size_t(n) * size_t(window_ + 1) + size_t(i)) * 7]);
+        n_pre_.assign(size_t(2 * n_laser_), 0); n_ds_.assign(size_t(2 * n_laser_), 0);
+        dev_.check(mlh_window_build_local_map(dev_.ctx(), p.data(), &o, n_pre_.data(), n_ds_.data()));
+    }
+    Device &dev_;
+    int n_laser_, window_;
+    mlh_window_map_opts o_{};
+    float scan_leaf_[2] = {0.4f, 0.2f};
+    std::vector<int32_t> n_pre_, n_ds_;
 };
 
 // every voxel filter of the device walks a voxel's members in the order libstdc++'s unstable std::sort leaves them, as the reference's filters do
