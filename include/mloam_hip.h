@@ -295,14 +295,20 @@ int mlh_pure_odom_add_matches_gf(mlh_ctx *ctx, int kind, const double rel_pose[7
  * loss-corrected with HuberLoss(huber_delta) (1.0 at estimator.cpp:602; <= 0: no loss), every listed block variable -- reduced on the device:
  * JtJ D x D row-major (symmetric, both triangles filled), Jtr D, cost = sum rho(r^2)/2, n_residuals. evalDegenracy (estimator.cpp:1598-1680)
  * reads its diagonal 6x6 blocks (mlh_eval_degeneracy on each); with several GPUs (factors split over the ranks) the record is summed with
- * mlh_allreduce_f64 -- D (D + 1) / 2 + D + 2 = 326 doubles for the 24-dimensional hercules window. Deterministic (no atomics). */
+ * mlh_allreduce_f64 -- D (D + 1) / 2 + D + 2 = 326 doubles for the 24-dimensional hercules window. Deterministic (no atomics).
+ * An installed window prior (mlh_window_prior_set / mlh_window_marginalize) or extrinsic prior is NOT added here: evalResidual evaluates res_ids_proj only
+ * (estimator.cpp:1588-1593), and evalDegenracy must keep seeing the feature factors alone. */
 int mlh_pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
                             double huber_delta, double *JtJ, double *Jtr, double *cost, int32_t *n_residuals);
 /* The coupled window problem solved on the device: n_iters Gauss-Newton iterations on the staged (or device-built) factor table -- per iteration the
  * normal equations above, then ONE workgroup gathers the rows / columns of the blocks that are not held constant, factorises them (Cholesky in LDS; + 1e-6 I
  * and a second attempt when not positive definite) and applies PoseLocalParameterization::Plus block by block; three launches per iteration, the poses stay in
  * HBM until the call returns. replaces the ceres::Solve of Estimator::optimizeMap on the LidarPureOdom / LidarOnlineCalib factors (estimator.cpp:593-680,
- * 852-861) for the part of that problem built here (no marginalisation prior -- SURVEY section 2 #13 -- and Gauss-Newton steps, not Ceres' trust region).
+ * 852-861) for the part of that problem built here (Gauss-Newton steps, not Ceres' trust region). With a window prior installed in the context (below) every
+ * iteration adds its MarginalizationFactor term (estimator.cpp:658-665) -- and, with bit 1 of mlh_window_ext_prior_set, the extrinsics' PriorFactor rows (cpp:675-685)
+ * -- to the assembled system on the device, one more one-workgroup launch between the assembly and the factorisation; `cost` then includes them, n_residuals
+ * still counts the feature factors. Without either, the launches and every output bit are what they are without this feature. A prior whose block map does not
+ * fit (n_frames, n_ext) is MLH_ERR_STATE.
  *   const_block_mask  bit b set = block b of [pivot | frames 0.. | extrinsics 0..] is held constant (estimator.cpp:636 para_pose_[0], :642 the reference LiDAR's
  *                     extrinsic; 1u | 1u << (1 + n_frames) for the reference's choice)
  *   V_update          NULL (identity) or 36 doubles per block, row-major: what Estimator::evalDegenracy (estimator.cpp:1598-1680; facade evalDegenracy) left in
@@ -313,6 +319,51 @@ int mlh_pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *f
  * parts of the factor table would apply different updates. Sharded callers all-reduce mlh_pure_odom_normal_eq's H / g (mlh_allreduce_f64) and solve on the host. */
 int mlh_pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int n_frames, double *exts, int n_ext, double huber_delta, int n_iters,
                            uint32_t const_block_mask, const double *V_update, double *cost, int32_t *n_residuals, int32_t *status);
+
+/* ---------------------------------------------------------------- (f9) the window's marginalisation prior, on the device
+ * A context holds at most one window prior -- what the reference keeps in last_marginalization_info_ / last_marginalization_parameter_blocks_: n_keep kept
+ * blocks (6 local parameters each), a block map kept block k -> block id of the window layout [pivot | frames 0.. | extrinsics 0..], the linearisation points x0
+ * (7 doubles per kept block, [t, q(xyzw)]), linearized_jacobians J0 (n x n row-major, n = 6 n_keep) and linearized_residuals r0 (n). It stays in HBM between the
+ * call that makes it and the solves that read it (mlh_pure_odom_gn_solve above).
+ * mlh_window_prior_set: installs a caller's prior (restoring saved state; at most 21 kept blocks, distinct ids in 0..21).
+ * mlh_window_prior_get: reads it back; every buffer may be NULL. info: see the struct. MLH_ERR_STATE when a buffer is asked for and no prior is installed.
+ * mlh_window_prior_clear: drops it (Estimator::clearState, estimator.cpp:1729-1731).
+ * mlh_window_prior_evaluate: MarginalizationFactor::Evaluate (marginalization_factor.cpp:358-410) at the given state -- the n residuals r0 + J0 dx, with dx per
+ *   kept block x - x0 for the translation and 2 positify(q0^-1 q).vec() for the rotation, the sign flip of cpp:383-386 as written; H (D x D, D = 6 (1 + n_frames
+ *   + n_ext)) = J0^T J0 scattered through the block map; g (D) = J0^T (r0 + J0 dx); cost = 0.5 |r0 + J0 dx|^2. Outputs may be NULL. The extrinsic prior is not part
+ *   of it. MLH_ERR_STATE without a prior or when its block map does not fit (n_frames, n_ext).
+ * mlh_window_ext_prior_set: the PriorFactor of every extrinsic (prior_factor.hpp:27-72; estimator.cpp:675-685, 891-900). rows = n_ext x 9: t[3], q[4] (x y z w),
+ *   pos_scale, rot_scale (tbl_[n], qbl_[n], PRIOR_FACTOR_POS, PRIOR_FACTOR_ROT): 6 residuals sqrt_info [P - t, 2 (q^-1 Q).vec()] and the 6 x 6 Jacobian
+ *   sqrt_info [I, 0; 0, LeftQuatMatrix(Q^-1 q).topLeftCorner<3, 3>()] (common/algos/math.hpp:77-87) -- the Jacobian the reference's own comment calls wrong,
+ *   reproduced. flags bit 0: the rows enter mlh_window_marginalize (cpp:891-900, whatever ESTIMATE_EXTRINSIC is); bit 1: they also enter mlh_pure_odom_gn_solve
+ *   (cpp:675-685, online calibration only). n_ext = 0 removes them.
+ * mlh_window_marginalize: replaces estimator.cpp:871-1063 (MarginalizationInfo::preMarginalize / marginalize / getParameterBlocks, marginalization_factor.cpp:
+ *   126-144, 189-341) for the factors the device table holds, at the given state (the solve's result): the table's normal equations over ALL blocks
+ *   (marginalisation ignores constness) with the loss correction of ResidualBlockInfo::Evaluate (marginalization_factor.cpp:50-81; for HuberLoss on a scalar
+ *   residual rho[2] <= 0, the sqrt(rho[1]) branch: what mlh_pure_odom_normal_eq applies), plus the installed prior's term with its pivot block in the drop set
+ *   (cpp:877-889), plus the extrinsic prior rows when their bit 0 is set. The pivot block is marginalised (m = 6): Amm = 0.5 (Amm + Amm^T), pseudo-inverse
+ *   through a symmetric eigen-decomposition with eps = 1e-8, Schur complement, second decomposition, J0 = sqrt(S) V^T, r0 = sqrt(S^-1) V^T b -- all f64, on the
+ *   device (cyclic Jacobi in one workgroup). The result REPLACES the installed prior: kept blocks [frames | extrinsics] in window order, x0 = this call's poses,
+ *   block map already slid as addr_shift does (cpp:1042-1050): frame i -> block i (frame 0 is the next window's pivot), extrinsic e -> 1 + n_frames + e. When
+ *   nothing touches the pivot (empty table, no prior on block 0) the prior is cleared and info.valid = 0 (the reference's m == 0). At most 22 blocks
+ *   (MLH_ERR_UNSUPPORTED before anything is enqueued); under a communicator MLH_ERR_UNSUPPORTED. The LidarOnlineCalib factors on the accumulated features
+ *   (cpp:921-938, 960-977) are not in the device table and stay outside. The only host wait is the one that fills info_out. */
+typedef struct mlh_window_prior_info {
+    int32_t valid, n_keep, n;             /* n = 6 n_keep */
+    int32_t kept_mm, kept_rr;             /* eigenvalues > 1e-8 kept: of Amm (6) and of the Schur complement (n); -1: the prior was installed by mlh_window_prior_set */
+    int32_t sweeps_mm, sweeps_rr;         /* Jacobi sweeps the two decompositions used */
+    int32_t reserved;
+    double min_kept_mm, max_dropped_mm;   /* smallest kept / largest dropped eigenvalue (0 when there is none) */
+    double min_kept_rr, max_dropped_rr;
+} mlh_window_prior_info;
+int mlh_window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const double *x0, const double *J0, const double *r0);
+int mlh_window_prior_get(mlh_ctx *ctx, mlh_window_prior_info *info, int32_t *block_ids, double *x0, double *J0, double *r0);
+int mlh_window_prior_clear(mlh_ctx *ctx);
+int mlh_window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
+                              double *residuals, double *H, double *g, double *cost);
+int mlh_window_ext_prior_set(mlh_ctx *ctx, int n_ext, const double *rows, uint32_t flags);
+int mlh_window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
+                           mlh_window_prior_info *info_out);
 
 /* (f1) cloudUCTAssociateToMap (lidar_mapper_keyframe.cpp:1116-1158): moves one keyframe's feature cloud into the map frame while
  * building the local map (extractSurroundingKeyFrames, cpp:254-354). Per point (intensity = LiDAR index n):

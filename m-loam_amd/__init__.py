@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("MLOAM_HIP_LIB") or os.path.join(_HERE, "lib", "libmlo
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "mloam_hip.h")
 
 SURF, CORNER = 0, 1
+cd_ = C.c_double
 ALL_KINDS = -1
 MEM_HOST, MEM_DEVICE = 0, 1
 FLAG_CHECK_FOV, FLAG_WITH_UA, FLAG_NO_LOSS, FLAG_POSE_COV = 1, 2, 4, 8
@@ -107,6 +108,15 @@ def global_map_select(positions_xyz, center, kf_radius, kf_res):
     if rc != 0:
         raise MlhError(f"mlh_global_map_select failed ({rc})")
     return ids[:n.value].copy()
+
+
+class WindowPriorInfo(C.Structure):
+    """mlh_window_prior_info"""
+    _fields_ = [("valid", C.c_int32), ("n_keep", C.c_int32), ("n", C.c_int32), ("kept_mm", C.c_int32), ("kept_rr", C.c_int32), ("sweeps_mm", C.c_int32),
+                ("sweeps_rr", C.c_int32), ("reserved", C.c_int32), ("min_kept_mm", cd_), ("max_dropped_mm", cd_), ("min_kept_rr", cd_), ("max_dropped_rr", cd_)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
 class SegmentParams(C.Structure):
@@ -231,6 +241,12 @@ def load_library():
     lib.mlh_pure_odom_evaluate.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp]
     lib.mlh_pure_odom_normal_eq.argtypes = [vp, vp, vp, ci, vp, ci, cd, vp, vp, C.POINTER(cd), C.POINTER(C.c_int32)]
     lib.mlh_pure_odom_gn_solve.argtypes = [vp, vp, vp, ci, vp, ci, cd, ci, C.c_uint32, vp, C.POINTER(cd), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mlh_window_prior_set.argtypes = [vp, ci, vp, vp, vp, vp]
+    lib.mlh_window_prior_get.argtypes = [vp, C.POINTER(WindowPriorInfo), vp, vp, vp, vp]
+    lib.mlh_window_prior_clear.argtypes = [vp]
+    lib.mlh_window_prior_evaluate.argtypes = [vp, vp, vp, ci, vp, ci, vp, vp, vp, C.POINTER(cd)]
+    lib.mlh_window_ext_prior_set.argtypes = [vp, ci, vp, C.c_uint32]
+    lib.mlh_window_marginalize.argtypes = [vp, vp, vp, ci, vp, ci, cd, C.POINTER(WindowPriorInfo)]
     lib.mlh_voxel_filter.argtypes = [vp, vp, ci, ci, ci, ci, ci, cf, cf, vp, C.POINTER(C.c_int32), ci]
     lib.mlh_map_set.argtypes = [vp, ci, vp, ci, ci, cf, ci]
     lib.mlh_map_set_pair.argtypes = [vp, vp, ci, vp, ci, ci, cf, ci]
@@ -293,6 +309,7 @@ EXPORTED_SYMBOLS = [
     "mlh_keyframe_attach_outlier", "mlh_global_map_opts_default", "mlh_global_map_assemble", "mlh_global_map_cloud", "mlh_global_map_release", "mlh_global_map_select",
     "mlh_window_map_opts_default", "mlh_window_reset", "mlh_window_set", "mlh_window_set_from_scan", "mlh_window_slide", "mlh_window_cloud", "mlh_window_info",
     "mlh_window_build_local_map", "mlh_window_map_cloud",
+    "mlh_window_prior_set", "mlh_window_prior_get", "mlh_window_prior_clear", "mlh_window_prior_evaluate", "mlh_window_ext_prior_set", "mlh_window_marginalize",
 ]
 
 
@@ -648,6 +665,55 @@ class Context:
         cost, n, st = C.c_double(0), C.c_int32(0), C.c_int32(0)
         self._ck(self.lib.mlh_pure_odom_gn_solve(self.h, _p(pv), _p(fr), len(fr), _p(ex), len(ex), float(huber_delta), int(n_iters), mask, _p(V), C.byref(cost), C.byref(n), C.byref(st)))
         return dict(frames=fr, exts=ex, cost=cost.value, count=n.value, status=st.value)
+
+    @staticmethod
+    def _window_poses(pivot, frames, exts):
+        return (np.ascontiguousarray(pivot, np.float64), np.ascontiguousarray(frames, np.float64).reshape(-1, 7), np.ascontiguousarray(exts, np.float64).reshape(-1, 7))
+
+    def window_prior_set(self, block_ids, x0, J0, r0):
+        """install a window prior (mlh_window_prior_set): kept block k -> window block block_ids[k], linearisation points, linearized_jacobians / _residuals"""
+        ids = np.ascontiguousarray(block_ids, np.int32); nk = len(ids)
+        x = np.ascontiguousarray(x0, np.float64).reshape(nk, 7); J = np.ascontiguousarray(J0, np.float64).reshape(6 * nk, 6 * nk)
+        r = np.ascontiguousarray(r0, np.float64).reshape(6 * nk)
+        self._ck(self.lib.mlh_window_prior_set(self.h, nk, _p(ids), _p(x), _p(J), _p(r)))
+
+    def window_prior_info(self):
+        info = WindowPriorInfo()
+        self._ck(self.lib.mlh_window_prior_get(self.h, C.byref(info), None, None, None, None))
+        return info.as_dict()
+
+    def window_prior_get(self):
+        """the installed prior (mlh_window_prior_get) or None"""
+        info = self.window_prior_info()
+        if not info["valid"]:
+            return None
+        nk, n = info["n_keep"], info["n"]
+        ids = np.zeros(nk, np.int32); x0 = np.zeros((nk, 7)); J0 = np.zeros((n, n)); r0 = np.zeros(n)
+        self._ck(self.lib.mlh_window_prior_get(self.h, None, _p(ids), _p(x0), _p(J0), _p(r0)))
+        return dict(info=info, block_ids=ids, x0=x0, J0=J0, r0=r0)
+
+    def window_prior_clear(self):
+        self._ck(self.lib.mlh_window_prior_clear(self.h))
+
+    def window_prior_evaluate(self, pivot, frames, exts):
+        """MarginalizationFactor::Evaluate at a state (mlh_window_prior_evaluate): residuals, H, g, cost"""
+        pv, fr, ex = self._window_poses(pivot, frames, exts)
+        D = 6 * (1 + len(fr) + len(ex)); n = self.window_prior_info()["n"]
+        res = np.zeros(n); H = np.zeros((D, D)); g = np.zeros(D); cost = C.c_double(0)
+        self._ck(self.lib.mlh_window_prior_evaluate(self.h, _p(pv), _p(fr), len(fr), _p(ex), len(ex), _p(res), _p(H), _p(g), C.byref(cost)))
+        return dict(residuals=res, H=H, g=g, cost=cost.value)
+
+    def window_ext_prior_set(self, rows, in_marginalization=True, in_solve=False):
+        """the extrinsics' PriorFactor (mlh_window_ext_prior_set): rows (n_ext, 9) = t, q(xyzw), pos_scale, rot_scale; None / empty removes them"""
+        r = np.zeros((0, 9)) if rows is None else np.ascontiguousarray(rows, np.float64).reshape(-1, 9)
+        self._ck(self.lib.mlh_window_ext_prior_set(self.h, len(r), _p(r) if len(r) else None, (1 if in_marginalization else 0) | (2 if in_solve else 0)))
+
+    def window_marginalize(self, pivot, frames, exts, huber_delta=1.0):
+        """marginalise the pivot at the given state (mlh_window_marginalize); the result replaces the installed prior -> info"""
+        pv, fr, ex = self._window_poses(pivot, frames, exts)
+        info = WindowPriorInfo()
+        self._ck(self.lib.mlh_window_marginalize(self.h, _p(pv), _p(fr), len(fr), _p(ex), len(ex), float(huber_delta), C.byref(info)))
+        return info.as_dict()
 
     def downsample_current_scan(self, kind, points4, leaf, ext_poses, ext_covs, cov_measurement, with_ua=True, trace_threshold=0.6, fetch=True):
         """downsampleCurrentScan for one kind; the result becomes the kind's feature set and, with fetch, is also returned (m, 11)

@@ -805,6 +805,51 @@ int mlh_pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, 
     return pure_odom_gn_solve(ctx, pivot, frames, n_frames, exts, n_ext, huber_delta, n_iters, const_block_mask, V_update, cost, n_residuals, status);
 }
 
+int mlh_window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const double *x0, const double *J0, const double *r0)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_prior_set(ctx, n_keep, block_ids, x0, J0, r0);
+}
+
+int mlh_window_prior_get(mlh_ctx *ctx, mlh_window_prior_info *info, int32_t *block_ids, double *x0, double *J0, double *r0)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_prior_get(ctx, info, block_ids, x0, J0, r0);
+}
+
+int mlh_window_prior_clear(mlh_ctx *ctx)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return window_prior_clear(ctx);
+}
+
+int mlh_window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
+                              double *residuals, double *H, double *g, double *cost)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_prior_evaluate(ctx, pivot, frames, n_frames, exts, n_ext, residuals, H, g, cost);
+}
+
+int mlh_window_ext_prior_set(mlh_ctx *ctx, int n_ext, const double *rows, uint32_t flags)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_ext_prior_set(ctx, n_ext, rows, flags);
+}
+
+int mlh_window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
+                           mlh_window_prior_info *info_out)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    // as mlh_pure_odom_gn_solve: this rank's sums are not the job's
+    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_window_marginalize under a communicator: build the whole factor table on one rank");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return window_marginalize(ctx, pivot, frames, n_frames, exts, n_ext, huber_delta, info_out);
+}
+
 int mlh_pure_odom_begin(mlh_ctx *ctx)
 {
     if (!ctx) return MLH_ERR_INVALID;

@@ -424,6 +424,22 @@ struct OdomSet {   // staged LidarPureOdom factor table (odom.hip)
     bool device_built = false;   // table appended from match passes on the device (padded regions): normal equations only
 };
 
+// The odometry window's marginalisation prior and the extrinsics' PriorFactor rows (marg.hip; estimator.cpp:658-685, 871-1063)
+struct MargPrior {
+    bool valid = false;
+    int n_keep = 0;                       // kept blocks, 6 local parameters each
+    int shape_frames = -1, shape_ext = -1;   // the window a marginalisation made it for (-1: installed by the caller, only the block ids are known)
+    int ids[22] = {0};                    // kept block -> block of the window layout [pivot | frames | extrinsics]
+    DevBuf ids_dev, x0, J0, r0, JtJ;      // the same map; 7 doubles per kept block; n x n; n; n x n (n = 6 n_keep)
+    DevBuf work;                          // marginalisation: the eigenvectors when they do not fit in LDS, the device's info record
+    DevBuf eval;                          // mlh_window_prior_evaluate: outputs and poses
+    PinnedBuf h_info;                     // landing place of the info record; the new block map on its way to the device
+    mlh_window_prior_info info = {};
+    int ext_n = 0;                        // extrinsics with a PriorFactor (0: none installed)
+    unsigned ext_flags = 0;               // bit 0: the rows enter the marginalisation, bit 1: the solve
+    DevBuf ext_rows;                      // 9 doubles per extrinsic
+};
+
 constexpr int FUSE_BLOCKS = 64;           // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
 constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
@@ -576,6 +592,7 @@ struct mlh_ctx {
     mlh::KfStore kf;         // keyframe store + local map (keyframes.hip)
     mlh::WinStore win;       // the odometry's sliding window + its local maps (window.hip)
     mlh::OdomSet odom;
+    mlh::MargPrior marg;     // the window's prior (marg.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}
@@ -716,6 +733,22 @@ int pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frame
                         double *H, double *g, double *cost, int32_t *n_res);
 int pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int n_frames, double *exts, int n_ext, double huber_delta, int n_iters,
                        uint32_t const_block_mask, const double *V_update, double *cost, int32_t *n_res, int32_t *status_out);
+// the table's normal equations at the given state enqueued into OdomSet::ne_out (zeros for an empty table), the poses left in OdomSet::poses; nothing waited for
+int window_assemble(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta);
+// marg.hip
+int window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const double *x0, const double *J0, const double *r0);
+int window_prior_get(mlh_ctx *ctx, mlh_window_prior_info *info, int32_t *block_ids, double *x0, double *J0, double *r0);
+int window_prior_clear(mlh_ctx *ctx);
+int window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
+                          double *residuals, double *H, double *g, double *cost);
+int window_ext_prior_set(mlh_ctx *ctx, int n_ext, const double *rows, uint32_t flags);
+int window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
+                       mlh_window_prior_info *info_out);
+// MLH_OK, or MLH_ERR_STATE (text set) when the installed prior's block map -- or, with ext_bit, the extrinsic prior that bit enables -- does not fit the window
+int window_prior_fits(mlh_ctx *ctx, const char *entry, int n_frames, int n_ext, uint32_t ext_bit);
+bool window_prior_in_solve(const mlh_ctx *ctx);      // a prior, or extrinsic rows with bit 1, is installed: mlh_pure_odom_gn_solve adds the term
+// one launch: the prior's term (and the extrinsic rows `ext_bit` enables) at the poses in `poses_dev` added into `ne_dev`; nothing when neither is installed
+void window_prior_term_enqueue(mlh_ctx *ctx, const double *poses_dev, int n_frames, int n_ext, double *ne_dev, uint32_t ext_bit, double *res_out);
 // voxelgrid.hip
 int device_exclusive_scan(mlh_ctx *ctx, int *data, long long n, mlh::DevBuf &sums, int *grand_total);
 // A kernel that cannot honour its contract (today: the device std::sort when a queue wait runs out, or a range it was never told about) sets

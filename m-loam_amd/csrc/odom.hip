@@ -539,10 +539,34 @@ int pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frame
     return MLH_OK;
 }
 
+int window_assemble(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta)
+{
+    OdomSet &O = ctx->odom;
+    if (O.n > 0 && O.n_tiles > 0) {
+        OdomNeArgs G;
+        size_t n_out = 0;
+        const int rc = odom_ne_prepare(ctx, pivot, frames, n_frames, exts, n_ext, G, n_out);
+        if (rc) return rc;
+        G.huber_delta = huber_delta;
+        odom_ne_enqueue(ctx, G, n_frames, n_ext, n_out);
+        MLH_HIP(ctx, hipGetLastError());
+        return MLH_OK;
+    }
+    const int D = 6 * (1 + n_frames + n_ext);
+    const size_t n_out = size_t(D) * D + D + 2;
+    OdomArgs A;
+    const int rc = odom_upload_poses(ctx, pivot, frames, n_frames, exts, n_ext, A);
+    if (rc) return rc;
+    MLH_HIP(ctx, O.ne_out.ensure(sizeof(double) * n_out));
+    MLH_HIP(ctx, hipMemsetAsync(O.ne_out.p, 0, sizeof(double) * n_out, ctx->stream));
+    return MLH_OK;
+}
+
 // ---- the coupled window problem solved ON THE DEVICE: Gauss-Newton on [pivot | frames | extrinsics] with some blocks held
 // constant -- Estimator::optimizeMap holds para_pose_[0] and para_ex_pose_[IDX_REF] constant (estimator.cpp:636, 642) -- and a per-block V_update
 // (what Estimator::evalDegenracy leaves in every PoseLocalParameterization before the solve, estimator.cpp:1598-1680: identity, a projector, or zero
-// for a frozen extrinsic). One workgroup: the free rows / columns of J^T J are gathered into LDS, factorised by a right-looking Cholesky (the trailing
+// for a frozen extrinsic). With a window prior installed (marg.hip) its term -- the MarginalizationFactor the reference adds whenever last_marginalization_info_
+// exists, estimator.cpp:658-665 -- and the extrinsics' PriorFactor rows (cpp:675-685) go into the assembled system by one more one-workgroup launch. One workgroup: the free rows / columns of J^T J are gathered into LDS, factorised by a right-looking Cholesky (the trailing
 // update spread over the 256 threads; + 1e-6 I and a second attempt when a pivot is not positive), two column-oriented substitutions, then one thread
 // per free block applies PoseLocalParameterization::Plus. An iteration is three launches (rows -> tile sums, assembly, solve); the poses never leave HBM.
 struct OdomSolveArgs {
@@ -632,6 +656,8 @@ int pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int 
     if (rc) return rc;
     const int nb = 1 + n_frames + n_ext, D = 6 * nb;
     if (nb > 22) return fail(ctx, MLH_ERR_UNSUPPORTED, "at most 22 parameter blocks");
+    const bool with_prior = window_prior_in_solve(ctx);
+    if (with_prior) { rc = window_prior_fits(ctx, "mlh_pure_odom_gn_solve", n_frames, n_ext, 2u); if (rc) return rc; }
     const unsigned free_mask = (~const_block_mask) & ((nb >= 32) ? 0xffffffffu : ((1u << nb) - 1u));
     int nf = 0;
     for (int b = 0; b < nb; ++b) if ((free_mask >> b) & 1u) nf += 6;
@@ -650,6 +676,7 @@ int pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int 
     S.ne = O.ne_out.as<double>(); S.poses = O.poses.as<double>(); S.V = V_update ? O.solve_aux.as<double>() : nullptr; S.n_blocks = nb; S.free_mask = free_mask; S.status = d_status;
     for (int it = 0; it < n_iters; ++it) {
         odom_ne_enqueue(ctx, G, n_frames, n_ext, n_out);
+        if (with_prior) window_prior_term_enqueue(ctx, O.poses.as<double>(), n_frames, n_ext, O.ne_out.as<double>(), 2u, nullptr);
         MLH_LAUNCH(odom_window_solve_kernel, dim3(1), dim3(256), lds, st, S);
     }
     MLH_HIP(ctx, hipGetLastError());

@@ -1491,6 +1491,39 @@ inline int solveWindow(Device &dev, const double pivot[7], std::vector<std::arra
     return status;
 }
 
+// The window's marginalisation prior (estimator.cpp:658-665, 871-1063), device-resident: what the reference keeps in last_marginalization_info_ /
+// last_marginalization_parameter_blocks_ lives in the context; solveWindow picks it up from there (the MarginalizationFactor of cpp:658-665).
+//   marginalizeWindow   cpp:871-1063 after the solve, at its result: the new prior replaces the old one, block map already slid (frame 0 = the next pivot)
+//   setExtrinsicPrior   the PriorFactor of every extrinsic (cpp:891-900 in the marginalisation; in_solve: cpp:675-685 as well, online calibration)
+//   clearWindowPrior    Estimator::clearState (cpp:1729-1731)
+inline mlh_window_prior_info marginalizeWindow(Device &dev, const double pivot[7], const std::vector<std::array<double, 7>> &frames,
+                                               const std::vector<std::array<double, 7>> &exts, double huber_delta)
+{
+    mlh_window_prior_info info;
+    dev.check(mlh_window_marginalize(dev.ctx(), pivot, frames.empty() ? nullptr : frames[0].data(), (int)frames.size(), exts.empty() ? nullptr : exts[0].data(),
+                                     (int)exts.size(), huber_delta, &info));
+    return info;
+}
+// tbl / qbl: 3 and 4 (x y z w) doubles per extrinsic, as tbl_[n] / qbl_[n].coeffs()
+inline void setExtrinsicPrior(Device &dev, const std::vector<std::array<double, 3>> &tbl, const std::vector<std::array<double, 4>> &qbl, double prior_factor_pos,
+                              double prior_factor_rot, bool in_solve)
+{
+    std::vector<double> rows(tbl.size() * 9);
+    for (size_t n = 0; n < tbl.size(); ++n) {
+        for (int k = 0; k < 3; ++k) rows[n * 9 + k] = tbl[n][k];
+        for (int k = 0; k < 4; ++k) rows[n * 9 + 3 + k] = qbl[n][k];
+        rows[n * 9 + 7] = prior_factor_pos; rows[n * 9 + 8] = prior_factor_rot;
+    }
+    dev.check(mlh_window_ext_prior_set(dev.ctx(), (int)tbl.size(), rows.empty() ? nullptr : rows.data(), in_solve ? 3u : 1u));
+}
+inline void clearWindowPrior(Device &dev) { dev.check(mlh_window_prior_clear(dev.ctx())); }
+inline mlh_window_prior_info windowPriorInfo(Device &dev)
+{
+    mlh_window_prior_info info;
+    dev.check(mlh_window_prior_get(dev.ctx(), &info, nullptr, nullptr, nullptr, nullptr));
+    return info;
+}
+
 // Estimator::evalDegenracy (estimator.cpp:1598-1680) on the window's normal equations, in the reference's argument order minus the Jacobian
 // (J^T J comes from evalWindowNormalEquations instead of a ceres::CRSMatrix): local_param_ids = the OPT_WINDOW_SIZE + 1 pose blocks, then one per
 // LiDAR extrinsic. Pose blocks: the mapper's rule per diagonal block with that block's threshold eig_thre[i]; a degenerate block gets
