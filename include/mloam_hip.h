@@ -297,7 +297,11 @@ int mlh_pure_odom_add_matches_gf(mlh_ctx *ctx, int kind, const double rel_pose[7
  * reads its diagonal 6x6 blocks (mlh_eval_degeneracy on each); with several GPUs (factors split over the ranks) the record is summed with
  * mlh_allreduce_f64 -- D (D + 1) / 2 + D + 2 = 326 doubles for the 24-dimensional hercules window. Deterministic (no atomics).
  * An installed window prior (mlh_window_prior_set / mlh_window_marginalize) or extrinsic prior is NOT added here: evalResidual evaluates res_ids_proj only
- * (estimator.cpp:1588-1593), and evalDegenracy must keep seeing the feature factors alone. */
+ * (estimator.cpp:1588-1593), and evalDegenracy must keep seeing the feature factors alone.
+ * With a calibration store in use (f10 below: mlh_calib_use) its LidarOnlineCalib factors ARE added -- the reference pushes them to res_ids_proj (cpp:733, 778), so
+ * evalResidual / evalDegenracy see them: JtJ / Jtr get the diagonal block and gradient rows of their extrinsic, cost and n_residuals count them. An empty factor
+ * table with a non-empty store in use is legal and returns the store's system. n_ext must cover the store's largest extrinsic index (MLH_ERR_INVALID). Under a
+ * communicator the record stays additive: every rank holds its OWN store and adds its own factors, so a store must not be replicated over the ranks. */
 int mlh_pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
                             double huber_delta, double *JtJ, double *Jtr, double *cost, int32_t *n_residuals);
 /* The coupled window problem solved on the device: n_iters Gauss-Newton iterations on the staged (or device-built) factor table -- per iteration the
@@ -308,7 +312,10 @@ int mlh_pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *f
  * iteration adds its MarginalizationFactor term (estimator.cpp:658-665) -- and, with bit 1 of mlh_window_ext_prior_set, the extrinsics' PriorFactor rows (cpp:675-685)
  * -- to the assembled system on the device, one more one-workgroup launch between the assembly and the factorisation; `cost` then includes them, n_residuals
  * still counts the feature factors. Without either, the launches and every output bit are what they are without this feature. A prior whose block map does not
- * fit (n_frames, n_ext) is MLH_ERR_STATE.
+ * fit (n_frames, n_ext) is MLH_ERR_STATE. With a calibration store in use (f10 below) every iteration's system includes its factors (cpp:729-733, 776-778 inside
+ * ceres::Solve): two more launches per iteration, n_residuals counts them; not in use or empty: the launches and every output bit are unchanged. Unlike
+ * mlh_pure_odom_normal_eq and mlh_window_marginalize the solve still needs a non-empty factor table: on an empty one it is MLH_ERR_STATE, store or no store (the
+ * reference's calibration problem always holds the reference LiDAR's window factors).
  *   const_block_mask  bit b set = block b of [pivot | frames 0.. | extrinsics 0..] is held constant (estimator.cpp:636 para_pose_[0], :642 the reference LiDAR's
  *                     extrinsic; 1u | 1u << (1 + n_frames) for the reference's choice)
  *   V_update          NULL (identity) or 36 doubles per block, row-major: what Estimator::evalDegenracy (estimator.cpp:1598-1680; facade evalDegenracy) left in
@@ -347,7 +354,10 @@ int mlh_pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, 
  *   block map already slid as addr_shift does (cpp:1042-1050): frame i -> block i (frame 0 is the next window's pivot), extrinsic e -> 1 + n_frames + e. When
  *   nothing touches the pivot (empty table, no prior on block 0) the prior is cleared and info.valid = 0 (the reference's m == 0). At most 22 blocks
  *   (MLH_ERR_UNSUPPORTED before anything is enqueued); under a communicator MLH_ERR_UNSUPPORTED. The LidarOnlineCalib factors on the accumulated features
- *   (cpp:921-938, 960-977) are not in the device table and stay outside. The only host wait is the one that fills info_out. */
+ *   (cpp:921-938, 960-977) enter the assembled system when a calibration store is in use (f10 below): they carry no drop set and never touch the pivot, so they land
+ *   in Arr only. The store is NOT cleared by the call; the caller clears it, as the reference does after the marginalisation on calibration frames (cpp:936-937,
+ *   975-976). The only host wait is the one that fills info_out -- and, with a store in use, the first call after an append to the store (or with another
+ *   n_ext) waits twice more while the store's tile lists for this extrinsic count go to the device. */
 typedef struct mlh_window_prior_info {
     int32_t valid, n_keep, n;             /* n = 6 n_keep */
     int32_t kept_mm, kept_rr;             /* eigenvalues > 1e-8 kept: of Amm (6) and of the Schur complement (n); -1: the prior was installed by mlh_window_prior_set */
@@ -364,6 +374,41 @@ int mlh_window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double 
 int mlh_window_ext_prior_set(mlh_ctx *ctx, int n_ext, const double *rows, uint32_t flags);
 int mlh_window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
                            mlh_window_prior_info *info_out);
+
+/* ---------------------------------------------------------------- (f10) the accumulated calibration features, on the device
+ * The online extrinsic calibration (ESTIMATE_EXTRINSIC == 1): Estimator::optimizeMap gives window factors to the reference LiDAR only (estimator.cpp:687-712,
+ * 744-760); the extrinsic of every other LiDAR n is constrained by the one-block LidarOnlineCalibPlaneNormFactor / LidarOnlineCalibEdgeFactor
+ * (lidar_online_calib_factor.hpp:35-62, 135-165) built from cumu_surf_map_features_[n] / cumu_corner_map_features_[n]: LiDAR n's pivot-frame correspondences,
+ * accumulated over N_CUMU_FEATURE frames and added to the problem on every N_CUMU_FEATURE-th frame (cpp:714-735, 762-780) and to the marginalisation (cpp:921-938,
+ * 960-977). A context keeps those lists as a store of factor records in HBM (point[3], coeff[6], sqrt_info as f64, type 0 plane / 1 edge) in 256-factor tiles, every
+ * tile belonging to one extrinsic. The store persists across windows: mlh_pure_odom_begin and mlh_pure_odom_set do not touch it.
+ * mlh_calib_accumulate: twin of mlh_pure_odom_add_matches. Matches the staged feature set of `kind` -- LiDAR ext_idx's pivot-frame features -- against the resident
+ *   map -- buildCalibMap's map of that LiDAR (mlh_window_build_local_map with source_lidar >= 0) -- at rel_pose = pose_local_[n][pivot_idx] with k_neigh 10 and
+ *   MLH_FLAG_CHECK_FOV (cpp:1131-1149) and appends the valid correspondences to the store in feature order, s = 1.0: cpp:714-719, 762-767 without the host lists.
+ *   Nothing comes back to the host. MLH_ERR_STATE without staged features or a map, MLH_ERR_INVALID for a negative ext_idx.
+ * mlh_calib_add: the same append from host lists (callers that keep them; tests). ext_idx is per factor; the factors are grouped by extrinsic into tiles, stable
+ *   within a group. sqrt_info may be NULL (= 1.0).
+ * mlh_calib_use: whether the store's factors enter mlh_pure_odom_normal_eq, mlh_pure_odom_gn_solve and mlh_window_marginalize -- the
+ *   frame_cnt_ % N_CUMU_FEATURE == 0 gate of cpp:721, 769, 921, 960, whose arithmetic stays the caller's. Off by default.
+ * mlh_calib_clear: empties the store and turns `use` off (cpp:736-740, 781-785, 936-937, 975-976; Estimator::clearState cpp:175-176).
+ * mlh_calib_info: see the struct; n_valid reads one device word back when mlh_calib_accumulate has appended.
+ * mlh_calib_evaluate: per-factor residual (n_valid) and 1 x 7 Jacobian row (n_valid x 7, 7th column zero, may be NULL), without the loss correction, in the order
+ *   the factors were given -- for a store made by mlh_calib_add alone; MLH_ERR_STATE otherwise, as mlh_pure_odom_evaluate refuses device-built tables. exts: n_ext x 7,
+ *   covering the store's largest extrinsic index (MLH_ERR_INVALID). An edge factor whose point lies exactly on its line has nu = 0: residual 0 and a zero row, as
+ *   Eigen's normalized() leaves the zero vector. */
+typedef struct mlh_calib_store_info {
+    int32_t n_appends;                    /* mlh_calib_accumulate / mlh_calib_add calls since the last clear */
+    int32_t n_tiles, n_slots;             /* n_slots = 256 n_tiles, padding included */
+    int32_t n_valid;                      /* factors */
+    int32_t max_ext;                      /* largest extrinsic index (-1: empty) */
+    int32_t in_use;
+} mlh_calib_store_info;
+int mlh_calib_accumulate(mlh_ctx *ctx, int kind, const double rel_pose[7], int k_neigh, uint32_t flags, float min_match_sq_dis, float min_plane_dis, int ext_idx);
+int mlh_calib_add(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info, const int32_t *ext_idx);
+int mlh_calib_use(mlh_ctx *ctx, int on);
+int mlh_calib_clear(mlh_ctx *ctx);
+int mlh_calib_info(mlh_ctx *ctx, mlh_calib_store_info *out);
+int mlh_calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians);
 
 /* (f1) cloudUCTAssociateToMap (lidar_mapper_keyframe.cpp:1116-1158): moves one keyframe's feature cloud into the map frame while
  * building the local map (extractSurroundingKeyFrames, cpp:254-354). Per point (intensity = LiDAR index n):

@@ -119,6 +119,14 @@ class WindowPriorInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class CalibStoreInfo(C.Structure):
+    """mlh_calib_store_info"""
+    _fields_ = [("n_appends", C.c_int32), ("n_tiles", C.c_int32), ("n_slots", C.c_int32), ("n_valid", C.c_int32), ("max_ext", C.c_int32), ("in_use", C.c_int32)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -263,6 +271,12 @@ def load_library():
     lib.mlh_std_sort_permutation.argtypes = [vp, vp, ci, ci, vp, ci]
     lib.mlh_debug_bad_launch.argtypes = [vp]
     lib.mlh_pure_odom_begin.argtypes = [vp]
+    lib.mlh_calib_accumulate.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, ci]
+    lib.mlh_calib_add.argtypes = [vp, ci, vp, vp, vp, vp, vp]
+    lib.mlh_calib_use.argtypes = [vp, ci]
+    lib.mlh_calib_clear.argtypes = [vp]
+    lib.mlh_calib_info.argtypes = [vp, C.POINTER(CalibStoreInfo)]
+    lib.mlh_calib_evaluate.argtypes = [vp, vp, ci, vp, vp]
     lib.mlh_pure_odom_add_matches.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, ci, ci]
     lib.mlh_pure_odom_add_matches_gf.argtypes = [vp, ci, vp, vp, vp, vp, ci, C.c_uint32, cf, cf, ci, ci, cf, C.c_uint64, vp, C.POINTER(C.c_int32)]
     lib.mlh_knn.argtypes = [vp, ci, vp, ci, ci, vp, vp]
@@ -310,6 +324,7 @@ EXPORTED_SYMBOLS = [
     "mlh_window_map_opts_default", "mlh_window_reset", "mlh_window_set", "mlh_window_set_from_scan", "mlh_window_slide", "mlh_window_cloud", "mlh_window_info",
     "mlh_window_build_local_map", "mlh_window_map_cloud",
     "mlh_window_prior_set", "mlh_window_prior_get", "mlh_window_prior_clear", "mlh_window_prior_evaluate", "mlh_window_ext_prior_set", "mlh_window_marginalize",
+    "mlh_calib_accumulate", "mlh_calib_add", "mlh_calib_use", "mlh_calib_clear", "mlh_calib_info", "mlh_calib_evaluate",
 ]
 
 
@@ -714,6 +729,40 @@ class Context:
         info = WindowPriorInfo()
         self._ck(self.lib.mlh_window_marginalize(self.h, _p(pv), _p(fr), len(fr), _p(ex), len(ex), float(huber_delta), C.byref(info)))
         return info.as_dict()
+
+    def calib_add(self, types, points, coeffs, ext_idx, sqrt_info=None):
+        """append LidarOnlineCalib factors to the context's calibration store from host lists (mlh_calib_add); ext_idx is per factor"""
+        t = np.ascontiguousarray(types, np.int32); ei = np.ascontiguousarray(ext_idx, np.int32)
+        p = np.ascontiguousarray(points, np.float64); c = np.ascontiguousarray(coeffs, np.float64)
+        assert p.shape == (len(t), 3) and c.shape == (len(t), 6) and ei.shape == (len(t),)
+        si = None if sqrt_info is None else np.ascontiguousarray(sqrt_info, np.float64)
+        self._ck(self.lib.mlh_calib_add(self.h, len(t), _p(t), _p(p), _p(c), _p(si), _p(ei)))
+
+    def calib_accumulate(self, kind, rel_pose, ext_idx, k_neigh=10, flags=FLAG_CHECK_FOV, min_match_sq_dis=1.0, min_plane_dis=0.2):
+        """match the staged features of `kind` (LiDAR ext_idx's pivot-frame features) against the resident map (buildCalibMap's) at rel_pose and append the valid
+        correspondences to the calibration store, all on the device (mlh_calib_accumulate)"""
+        p = np.ascontiguousarray(rel_pose, np.float64)
+        self._ck(self.lib.mlh_calib_accumulate(self.h, kind, _p(p), int(k_neigh), int(flags), float(min_match_sq_dis), float(min_plane_dis), int(ext_idx)))
+
+    def calib_use(self, on=True):
+        """whether the store's factors enter pure_odom_normal_eq / pure_odom_gn_solve / window_marginalize (the frame_cnt % N_CUMU_FEATURE == 0 gate)"""
+        self._ck(self.lib.mlh_calib_use(self.h, 1 if on else 0))
+
+    def calib_clear(self):
+        self._ck(self.lib.mlh_calib_clear(self.h))
+
+    def calib_info(self):
+        info = CalibStoreInfo()
+        self._ck(self.lib.mlh_calib_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    def calib_evaluate(self, exts, want_jacobians=True):
+        """per-factor residual and 1 x 7 Jacobian row of a store made by calib_add, in the order given (mlh_calib_evaluate)"""
+        ex = np.ascontiguousarray(exts, np.float64).reshape(-1, 7)
+        n = self.calib_info()["n_valid"]
+        r = np.zeros(n); J = np.zeros((n, 7)) if want_jacobians else None
+        self._ck(self.lib.mlh_calib_evaluate(self.h, _p(ex), len(ex), _p(r), _p(J)))
+        return r, J
 
     def downsample_current_scan(self, kind, points4, leaf, ext_poses, ext_covs, cov_measurement, with_ua=True, trace_threshold=0.6, fetch=True):
         """downsampleCurrentScan for one kind; the result becomes the kind's feature set and, with fetch, is also returned (m, 11)

@@ -1,0 +1,437 @@
+// The accumulated calibration features of the online extrinsic calibration on gfx950: the one-block factors
+//   LidarOnlineCalibPlaneNormFactor::Evaluate   estimator/src/factor/lidar_online_calib_factor.hpp:35-62
+//   LidarOnlineCalibEdgeFactor::Evaluate        estimator/src/factor/lidar_online_calib_factor.hpp:135-165
+// that Estimator::optimizeMap builds from cumu_surf_map_features_[n] / cumu_corner_map_features_[n] on every N_CUMU_FEATURE-th frame (estimator.cpp:714-735,
+// 762-780) and hands to the marginalisation as well (cpp:921-938, 960-977). With ESTIMATE_EXTRINSIC == 1 they are the only feature terms on the extrinsic of a
+// LiDAR other than the reference one. The store lives in HBM across windows: a record is the factor table's (point[3], coeff[6], sqrt_info, f64) plus a type;
+// 256 records form a tile and every tile belongs to ONE extrinsic, so a workgroup computes R(Q_ext), t_ext once.
+//   calib_append_kernel   the valid correspondences of a match pass, packed in feature order behind the store's last tile (no host round trip)
+//   calib_ne_kernel       one workgroup per tile, one lane per factor: residual and 1x6 row, Huber correction, the tile's 29 sums (21 upper-triangle
+//                         products, 6 J^T r, cost, count) reduced per wavefront in registers and combined in wavefront order
+//   calib_ne_add_kernel   one workgroup behind the window's assembly: per extrinsic the tiles' sums in tile order into its diagonal block and gradient rows
+//                         (the sums stream through LDS; 29 threads add them sequentially)
+//   calib_eval_kernel     per-factor residual and 1x7 row (host-staged stores; the tests' view of the factor)
+// Fixed summation order everywhere, no atomics: identical bits run to run.
+#include "ctx.hpp"
+#include "dev_math.hpp"
+#include "calib_group.hpp"
+#include <cfloat>
+
+namespace mlh {
+
+constexpr int CAL_OUT = 32;       // 21 + 6 + cost + count = 29, padded
+constexpr int CAL_NSUM = 29;
+
+struct C3 { double x, y, z; };
+__device__ __forceinline__ C3 c_rowmul(const C3 &a, const double *M) { return {a.x * M[0] + a.y * M[3] + a.z * M[6], a.x * M[1] + a.y * M[4] + a.z * M[7], a.x * M[2] + a.y * M[5] + a.z * M[8]}; }   // a^T M
+__device__ __forceinline__ C3 c_row_skew(const C3 &a, const C3 &v) { return {a.y * v.z - a.z * v.y, a.z * v.x - a.x * v.z, a.x * v.y - a.y * v.x}; }                                              // a^T [v]x
+__device__ __forceinline__ C3 c_cross(const C3 &a, const C3 &b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+
+// the workgroup's extrinsic: R (9, row-major), t (3), q (4, xyzw) -- written by one thread, read by all
+__device__ __forceinline__ void calib_stage_ext(const double *pe, double *s_ext)
+{
+    qtorot(q4{pe[3], pe[4], pe[5], pe[6]}, s_ext);
+    s_ext[9] = pe[0]; s_ext[10] = pe[1]; s_ext[11] = pe[2];
+    s_ext[12] = pe[3]; s_ext[13] = pe[4]; s_ext[14] = pe[5]; s_ext[15] = pe[6];
+}
+
+// one factor at the staged extrinsic: residual and the six columns of its row, both times sqrt_info (hpp:35-62 / 135-165 term by term)
+__device__ __forceinline__ void calib_factor(const double *tb, int type, const double *s_ext, double &r_out, double *J6)
+{
+    const double *R = s_ext;
+    const C3 p{tb[0], tb[1], tb[2]};
+    const double s = tb[9];
+    const d3 rp = qrot(q4{s_ext[12], s_ext[13], s_ext[14], s_ext[15]}, d3{p.x, p.y, p.z});       // Q_ext * point_
+    const C3 lp{rp.x + s_ext[9], rp.y + s_ext[10], rp.z + s_ext[11]};
+    C3 jt, jr;
+    double res;
+    if (type == 0) {
+        const C3 w{tb[3], tb[4], tb[5]};
+        res = (w.x * lp.x + w.y * lp.y + w.z * lp.z) + tb[6];
+        jt = w;
+        const C3 k = c_row_skew(c_rowmul(w, R), p);                 // w^T R [p]x
+        jr = C3{-k.x, -k.y, -k.z};
+    } else {
+        const C3 la{tb[3], tb[4], tb[5]}, lb{tb[6], tb[7], tb[8]};
+        const C3 nu = c_cross(C3{lp.x - la.x, lp.y - la.y, lp.z - la.z}, C3{lp.x - lb.x, lp.y - lb.y, lp.z - lb.z});
+        const C3 de{la.x - lb.x, la.y - lb.y, la.z - lb.z};
+        const double n2 = nu.x * nu.x + nu.y * nu.y + nu.z * nu.z, de_n = sqrt(de.x * de.x + de.y * de.y + de.z * de.z);
+        res = sqrt(n2) / de_n;
+        C3 nh = nu;
+        if (n2 > 0.0) { const double nn = sqrt(n2); nh = C3{nu.x / nn, nu.y / nn, nu.z / nn}; }     // Eigen normalized(): zero stays zero, so nu = 0 gives a zero row
+        const double k = 1.0 / de_n;
+        const C3 eta{k * nh.x, k * nh.y, k * nh.z};
+        const C3 ed = c_row_skew(eta, de);                          // eta [lpa - lpb]x
+        jt = C3{-ed.x, -ed.y, -ed.z};
+        jr = c_row_skew(c_rowmul(ed, R), p);                        // eta [lpa - lpb]x R [p]x
+    }
+    r_out = s * res;
+    J6[0] = s * jt.x; J6[1] = s * jt.y; J6[2] = s * jt.z; J6[3] = s * jr.x; J6[4] = s * jr.y; J6[5] = s * jr.z;
+}
+
+struct CalibNeArgs {
+    const double *tab;      // slots x 10
+    const int *type, *perm; // slots
+    const int *tile_ext;    // tiles
+    const int *tile_pos;    // tiles: the tile's rank in (extrinsic, tile) order = its row of `partial`
+    const double *exts;     // n_ext x 7
+    int n_ext;
+    double huber_delta;
+    double *partial;        // tiles x CAL_OUT
+};
+
+// sum over the 64 lanes by a butterfly: every lane ends with the same bits, whatever the run
+__device__ __forceinline__ double calib_wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void calib_ne_kernel(CalibNeArgs G)
+{
+    __shared__ double s_ext[16];
+    __shared__ double s_w[4][CAL_OUT];
+    const int tile = blockIdx.x, k = threadIdx.x, lane = k & 63, wave = k >> 6;
+    if (k == 0) calib_stage_ext(G.exts + 7 * min(max(G.tile_ext[tile], 0), G.n_ext - 1), s_ext);
+    __syncthreads();
+    const size_t slot = size_t(tile) * CALIB_TILE + k;
+    double v[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};     // 6 corrected columns, corrected residual, cost, count: zeros for padding
+    if (G.perm[slot] >= 0) {
+        double r, J[6];
+        calib_factor(G.tab + slot * 10, G.type[slot], s_ext, r, J);
+        double sq = r * r, rho0 = sq, rho1 = 1.0;
+        if (G.huber_delta > 0.0) {
+            const double bb = G.huber_delta * G.huber_delta;
+            if (sq > bb) { const double rr = sqrt(sq); rho0 = 2.0 * G.huber_delta * rr - bb; rho1 = fmax(DBL_MIN, G.huber_delta / rr); }
+        }
+        const double sc = sqrt(rho1);
+#pragma unroll
+        for (int c = 0; c < 6; ++c) v[c] = J[c] * sc;
+        v[6] = r * sc; v[7] = 0.5 * rho0; v[8] = 1.0;
+    }
+    int o = 0;
+#pragma unroll
+    for (int a = 0; a < 6; ++a)
+#pragma unroll
+        for (int b = a; b < 7; ++b) {
+            // row a of the upper triangle (b < 6), then its J^T r entry (b == 6): outputs 0..20 are the products in row-major order, 21..26 the gradient
+            const double sum = calib_wave_sum(v[a] * v[b]);
+            const int dst = b < 6 ? o++ : 21 + a;
+            if (lane == 0) s_w[wave][dst] = sum;
+        }
+    { const double sum = calib_wave_sum(v[7]); if (lane == 0) s_w[wave][27] = sum; }
+    { const double sum = calib_wave_sum(v[8]); if (lane == 0) s_w[wave][28] = sum; }
+    __syncthreads();
+    if (k < CAL_OUT) G.partial[size_t(G.tile_pos[tile]) * CAL_OUT + k] = k < CAL_NSUM ? ((s_w[0][k] + s_w[1][k]) + s_w[2][k]) + s_w[3][k] : 0.0;
+}
+
+struct CalibAddArgs {
+    const double *partial;              // n_tiles x CAL_OUT, rows sorted by (extrinsic, tile): calib_ne_kernel writes a tile's sums to its rank in that order
+    const int *ext_start;               // rows of extrinsic e: ext_start[e] .. ext_start[e + 1]
+    int n_tiles, n_frames, n_ext;
+    double *ne;                         // D*D + D + 2: added to
+};
+
+// One workgroup behind the window's assembly. A thread that owned an output and fetched its tiles from HBM one after the other spent a memory latency per tile
+// (0.74 ms for 2 980 tiles); here all 1024 threads stream the rows through LDS, 256 rows at a time and the next 256 already on their way in registers, and
+// threads 0..28 add them IN ROW ORDER -- per extrinsic in tile order, onto what the assembly left -- so the sums are the sequential ones, bit for bit.
+constexpr int CAL_STAGE = 256;          // rows per LDS stage: 64 KiB
+__global__ __launch_bounds__(1024) void calib_ne_add_kernel(CalibAddArgs F)
+{
+    __shared__ double s_p[CAL_STAGE * CAL_OUT];
+    const int t = threadIdx.x, D = 6 * (1 + F.n_frames + F.n_ext);
+    const size_t n_all = size_t(F.n_tiles) * CAL_OUT;
+    constexpr int PER = CAL_STAGE * CAL_OUT / 1024;                 // 8 doubles per thread and stage
+    double reg[PER];
+#pragma unroll
+    for (int j = 0; j < PER; ++j) { const size_t q = size_t(t) + 1024 * size_t(j); reg[j] = q < n_all ? F.partial[q] : 0.0; }
+    // the walking threads: o < 27 owns output o of the current extrinsic's block, 27 / 28 the cost and the count
+    int e = -1, next = 0, a = 0, b = 0;
+    size_t at = 0;
+    double acc = 0.0;
+    if (t < 21) { int left = t; while (left >= 6 - a) { left -= 6 - a; ++a; } b = a + left; }
+    if (t == 27 || t == 28) { at = size_t(D) * D + D + (t - 27); acc = F.ne[at]; }
+    for (int row0 = 0; row0 < F.n_tiles; row0 += CAL_STAGE) {
+        __syncthreads();                                            // the previous stage has been walked
+#pragma unroll
+        for (int j = 0; j < PER; ++j) s_p[t + 1024 * j] = reg[j];
+        __syncthreads();
+        if (row0 + CAL_STAGE < F.n_tiles) {
+            const size_t base = size_t(row0 + CAL_STAGE) * CAL_OUT;
+#pragma unroll
+            for (int j = 0; j < PER; ++j) { const size_t q = base + size_t(t) + 1024 * size_t(j); reg[j] = q < n_all ? F.partial[q] : 0.0; }
+        }
+        if (t < CAL_NSUM) {
+            const int rows = min(CAL_STAGE, F.n_tiles - row0);
+            int r = 0;
+            while (r < rows) {
+                int end = rows;
+                if (t < 27) {
+                    if (row0 + r == next) {                         // the rows of the next extrinsic that has any begin here
+                        if (e >= 0) { F.ne[at] = acc; if (t < 21 && a != b) F.ne[at + size_t(b - a) * (D - 1)] = acc; }
+                        do { ++e; } while (e < F.n_ext - 1 && F.ext_start[e + 1] == F.ext_start[e]);
+                        next = F.ext_start[e + 1];
+                        const int off = 6 * (1 + F.n_frames + e);
+                        at = t < 21 ? size_t(off + a) * D + off + b : size_t(D) * D + off + (t - 21);
+                        acc = F.ne[at];                             // the assembly left both triangles with the same bits: the upper entry stands for both
+                    }
+                    end = min(rows, next - row0);
+                    if (end <= r) end = rows;                       // (lists that do not add up to n_tiles: never loop in place)
+                }
+                // one extrinsic's rows of this stage: sixteen LDS reads in flight, the additions in row order
+                for (; r + 16 <= end; r += 16) {
+                    double x[16];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) x[j] = s_p[(r + j) * CAL_OUT + t];
+#pragma unroll
+                    for (int j = 0; j < 16; ++j) acc += x[j];
+                }
+                for (; r < end; ++r) acc += s_p[r * CAL_OUT + t];
+            }
+        }
+    }
+    if (t < 27 && e >= 0) { F.ne[at] = acc; if (t < 21 && a != b) F.ne[at + size_t(b - a) * (D - 1)] = acc; }
+    if (t == 27 || t == 28) F.ne[at] = acc;
+}
+
+struct CalibEvalArgs {
+    const double *tab;
+    const int *type, *perm, *tile_ext;
+    const double *exts;
+    int n_ext;
+    double *r, *J;          // n_given, n_given x 7 (J may be null): in the order the factors were given
+};
+__global__ __launch_bounds__(256) void calib_eval_kernel(CalibEvalArgs E)
+{
+    __shared__ double s_ext[16];
+    const int tile = blockIdx.x, k = threadIdx.x;
+    if (k == 0) calib_stage_ext(E.exts + 7 * min(max(E.tile_ext[tile], 0), E.n_ext - 1), s_ext);
+    __syncthreads();
+    const size_t slot = size_t(tile) * CALIB_TILE + k;
+    const int i = E.perm[slot];
+    if (i < 0) return;
+    double r, J[6];
+    calib_factor(E.tab + slot * 10, E.type[slot], s_ext, r, J);
+    E.r[i] = r;
+    if (E.J) {
+#pragma unroll
+        for (int c = 0; c < 6; ++c) E.J[size_t(i) * 7 + c] = J[c];
+        E.J[size_t(i) * 7 + 6] = 0.0;
+    }
+}
+
+// the valid correspondences of a match pass -> records behind the store's last tile, in feature order; the rest of the reserved region is padding. The twin of
+// odom.hip's odom_append_kernel (same scan-and-pack; kept apart so that the window table's kernel stays exactly as it was): a change to one belongs in both.
+// The region is reserved from the STAGED feature count (no host round trip for the number of valid ones), so a device-built store has more slots than factors. One workgroup. n_valid (one word, this kernel its only writer while it runs) counts what was appended.
+struct CalibAppend {
+    const float4 *feat;
+    const Corr *corr;
+    int m, type, base_slot, cap_slots;
+    double *tab;
+    int *types, *perm, *n_valid;
+};
+__global__ __launch_bounds__(1024) void calib_append_kernel(CalibAppend P)
+{
+    __shared__ int wsum[16];
+    __shared__ int s_running;
+    if (threadIdx.x == 0) s_running = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int c0 = 0; c0 < P.m; c0 += 1024) {
+        const int i = c0 + threadIdx.x;
+        const bool v = i < P.m && P.corr[i].valid != 0 && P.feat[i].w >= 0.f;
+        const unsigned long long b = __ballot(v);
+        const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) wsum[wave] = __popcll(b);
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < 16; ++w) { const int x = wsum[w]; if (w < wave) before += x; total += x; }
+        const int running = s_running;
+        if (v) {
+            const int slot = P.base_slot + running + before + in_wave;     // running + before + in_wave < m <= cap_slots
+            const float4 f = P.feat[i];
+            const Corr c = P.corr[i];
+            double *t = P.tab + size_t(slot) * 10;
+            t[0] = double(f.x); t[1] = double(f.y); t[2] = double(f.z);
+#pragma unroll
+            for (int k = 0; k < 6; ++k) t[3 + k] = double(c.c[k]);
+            t[9] = 1.0;                                                     // the reference constructs them with s = 1.0 (estimator.cpp:728, 774)
+            P.types[slot] = P.type;
+            P.perm[slot] = slot;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) s_running = running + total;
+        __syncthreads();
+    }
+    for (int q = s_running + threadIdx.x; q < P.cap_slots; q += 1024) P.perm[P.base_slot + q] = -1;
+    if (threadIdx.x == 0) *P.n_valid += s_running;
+}
+
+// ---- host side
+static int calib_grow(mlh_ctx *ctx, int n_tiles_new)
+{
+    CalibStore &S = ctx->calib;
+    hipStream_t st = ctx->stream;
+    const size_t have = size_t(S.n_tiles) * CALIB_TILE, want = size_t(n_tiles_new) * CALIB_TILE;
+    hipError_t e;
+    if ((e = S.tab.grow(sizeof(double) * 10 * want, sizeof(double) * 10 * have, st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc calibration store", e);
+    if ((e = S.type.grow(sizeof(int) * want, sizeof(int) * have, st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc calibration store", e);
+    if ((e = S.perm.grow(sizeof(int) * want, sizeof(int) * have, st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc calibration store", e);
+    return MLH_OK;
+}
+
+int calib_add(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info, const int32_t *ext_idx)
+{
+    if (n <= 0 || !type || !points || !coeffs || !ext_idx) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: bad arguments");
+    for (int i = 0; i < n; ++i) {
+        if (type[i] != 0 && type[i] != 1) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: factor type must be 0 (plane) or 1 (edge)");
+        if (ext_idx[i] < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: negative extrinsic index");
+    }
+    CalibStore &S = ctx->calib;
+    const CalibGrouping G = calib_group(n, ext_idx, S.n_given);
+    const size_t slots = size_t(G.n_tiles) * CALIB_TILE, base = size_t(S.n_tiles) * CALIB_TILE;
+    std::vector<double> tab(slots * 10, 0.0);
+    std::vector<int> types(slots, 0);
+    for (int i = 0; i < n; ++i) {
+        const size_t s = size_t(G.slot_of[size_t(i)]);
+        double *t = tab.data() + s * 10;
+        for (int k = 0; k < 3; ++k) t[k] = points[size_t(i) * 3 + k];
+        for (int k = 0; k < 6; ++k) t[3 + k] = coeffs[size_t(i) * 6 + k];
+        t[9] = sqrt_info ? sqrt_info[i] : 1.0;
+        types[s] = type[i];
+    }
+    { const int rc = calib_grow(ctx, S.n_tiles + G.n_tiles); if (rc) return rc; }
+    hipStream_t st = ctx->stream;
+    MLH_HIP(ctx, hipMemcpyAsync(S.tab.as<double>() + base * 10, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
+    MLH_HIP(ctx, hipMemcpyAsync(S.type.as<int>() + base, types.data(), sizeof(int) * slots, hipMemcpyHostToDevice, st));
+    MLH_HIP(ctx, hipMemcpyAsync(S.perm.as<int>() + base, G.perm.data(), sizeof(int) * slots, hipMemcpyHostToDevice, st));
+    MLH_HIP(ctx, hipStreamSynchronize(st));                // the staging vectors end with this call
+    S.h_tile_ext.insert(S.h_tile_ext.end(), G.tile_ext.begin(), G.tile_ext.end());
+    S.n_tiles += G.n_tiles; S.n_appends += 1; S.n_given += n; S.max_ext = std::max(S.max_ext, G.max_ext); S.lists_n_ext = -1;
+    return MLH_OK;
+}
+
+int calib_accumulate(mlh_ctx *ctx, int kind, int ext_idx)
+{
+    if (ext_idx < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_accumulate: negative extrinsic index");
+    FeatSet &f = ctx->feat[kind];
+    if (f.m <= 0 || !f.matched || f.n_blocks != 1) return fail(ctx, MLH_ERR_STATE, "mlh_calib_accumulate: a single-block match pass must have run for this kind");
+    CalibStore &S = ctx->calib;
+    hipStream_t st = ctx->stream;
+    const int cap_tiles = (f.m + CALIB_TILE - 1) / CALIB_TILE;
+    { const int rc = calib_grow(ctx, S.n_tiles + cap_tiles); if (rc) return rc; }
+    if (!S.n_valid_dev.p) {
+        MLH_HIP(ctx, S.n_valid_dev.ensure(sizeof(int)));
+        MLH_HIP(ctx, hipMemsetAsync(S.n_valid_dev.p, 0, sizeof(int), st));
+    }
+    CalibAppend P;
+    P.feat = f.pts.as<float4>(); P.corr = f.corr.as<Corr>(); P.m = f.m; P.type = kind;
+    P.base_slot = S.n_tiles * CALIB_TILE; P.cap_slots = cap_tiles * CALIB_TILE;
+    P.tab = S.tab.as<double>(); P.types = S.type.as<int>(); P.perm = S.perm.as<int>(); P.n_valid = S.n_valid_dev.as<int>();
+    MLH_LAUNCH(calib_append_kernel, dim3(1), dim3(1024), 0, st, P);
+    MLH_HIP(ctx, hipGetLastError());
+    for (int t = 0; t < cap_tiles; ++t) S.h_tile_ext.push_back(ext_idx);
+    S.n_tiles += cap_tiles; S.n_appends += 1; S.max_ext = std::max(S.max_ext, ext_idx); S.lists_n_ext = -1; S.device_built = true;
+    return MLH_OK;
+}
+
+int calib_use(mlh_ctx *ctx, int on)
+{
+    ctx->calib.in_use = on != 0;
+    return MLH_OK;
+}
+
+int calib_clear(mlh_ctx *ctx)
+{
+    CalibStore &S = ctx->calib;
+    if (S.n_valid_dev.p) MLH_HIP(ctx, hipMemsetAsync(S.n_valid_dev.p, 0, sizeof(int), ctx->stream));
+    S.h_tile_ext.clear();
+    S.n_tiles = 0; S.n_appends = 0; S.n_given = 0; S.max_ext = -1; S.lists_n_ext = -1; S.in_use = false; S.device_built = false;
+    return MLH_OK;
+}
+
+int calib_info(mlh_ctx *ctx, mlh_calib_store_info *out)
+{
+    if (!out) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_info: null output");
+    CalibStore &S = ctx->calib;
+    int n_dev = 0;
+    if (S.device_built && S.n_valid_dev.p) {
+        MLH_HIP(ctx, hipMemcpyAsync(&n_dev, S.n_valid_dev.p, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+        MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    out->n_appends = S.n_appends; out->n_tiles = S.n_tiles; out->n_slots = S.n_tiles * CALIB_TILE; out->n_valid = S.n_given + n_dev;
+    out->max_ext = S.max_ext; out->in_use = S.in_use ? 1 : 0;
+    return MLH_OK;
+}
+
+bool calib_active(const mlh_ctx *ctx) { return ctx->calib.in_use && ctx->calib.n_tiles > 0; }
+
+// the tile -> extrinsic keys and every extrinsic's tile list on the device, for this extrinsic count
+static int calib_sync_lists(mlh_ctx *ctx, int n_ext)
+{
+    CalibStore &S = ctx->calib;
+    if (S.lists_n_ext == n_ext) return MLH_OK;
+    std::vector<int> start, tiles;
+    calib_ext_lists(S.h_tile_ext, n_ext, start, tiles);
+    std::vector<int> all(S.h_tile_ext);
+    all.insert(all.end(), start.begin(), start.end());
+    std::vector<int> pos(tiles.size(), 0);                 // n_ext covers the store (calib_ne_prepare): `tiles` is a permutation of all tiles
+    for (size_t k = 0; k < tiles.size(); ++k) pos[size_t(tiles[k])] = int(k);
+    all.insert(all.end(), pos.begin(), pos.end());
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));       // an earlier launch may still read the lists this replaces
+    MLH_HIP(ctx, S.lists.ensure(sizeof(int) * all.size()));
+    MLH_HIP(ctx, hipMemcpyAsync(S.lists.p, all.data(), sizeof(int) * all.size(), hipMemcpyHostToDevice, ctx->stream));
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    S.lists_n_ext = n_ext;
+    return MLH_OK;
+}
+
+int calib_ne_prepare(mlh_ctx *ctx, int n_ext)
+{
+    CalibStore &S = ctx->calib;
+    if (n_ext <= S.max_ext) return fail(ctx, MLH_ERR_INVALID, "the extrinsics do not cover the largest extrinsic index of the calibration store");
+    { const int rc = calib_sync_lists(ctx, n_ext); if (rc) return rc; }
+    MLH_HIP(ctx, S.partial.ensure(sizeof(double) * CAL_OUT * size_t(S.n_tiles)));
+    return MLH_OK;
+}
+
+void calib_ne_enqueue(mlh_ctx *ctx, const double *poses_dev, int n_frames, int n_ext, double huber_delta, double *ne_dev)
+{
+    CalibStore &S = ctx->calib;
+    const int *lists = S.lists.as<int>();
+    CalibNeArgs G;
+    G.tab = S.tab.as<double>(); G.type = S.type.as<int>(); G.perm = S.perm.as<int>(); G.tile_ext = lists; G.tile_pos = lists + S.n_tiles + n_ext + 1;
+    G.exts = poses_dev + 7 * size_t(1 + n_frames); G.n_ext = n_ext; G.huber_delta = huber_delta; G.partial = S.partial.as<double>();
+    MLH_LAUNCH(calib_ne_kernel, dim3(S.n_tiles), dim3(256), 0, ctx->stream, G);
+    CalibAddArgs F;
+    F.partial = S.partial.as<double>(); F.ext_start = lists + S.n_tiles;
+    F.n_tiles = S.n_tiles; F.n_frames = n_frames; F.n_ext = n_ext; F.ne = ne_dev;
+    MLH_LAUNCH(calib_ne_add_kernel, dim3(1), dim3(1024), 0, ctx->stream, F);
+}
+
+int calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians)
+{
+    CalibStore &S = ctx->calib;
+    if (S.device_built) return fail(ctx, MLH_ERR_STATE, "mlh_calib_evaluate: per-factor outputs need a store made by mlh_calib_add alone: a device-built one is padded");
+    if (S.n_given <= 0) return fail(ctx, MLH_ERR_STATE, "mlh_calib_evaluate: the store is empty");
+    if (!exts || !residuals || n_ext <= S.max_ext) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_evaluate: the extrinsics do not cover the store's largest extrinsic index");
+    { const int rc = calib_sync_lists(ctx, n_ext); if (rc) return rc; }
+    hipStream_t st = ctx->stream;
+    const size_t n = size_t(S.n_given), ne7 = 7 * size_t(n_ext);
+    MLH_HIP(ctx, S.eval.ensure(sizeof(double) * (ne7 + n + 7 * n)));
+    double *d = S.eval.as<double>();
+    MLH_HIP(ctx, hipMemcpyAsync(d, exts, sizeof(double) * ne7, hipMemcpyHostToDevice, st));
+    CalibEvalArgs E;
+    E.tab = S.tab.as<double>(); E.type = S.type.as<int>(); E.perm = S.perm.as<int>(); E.tile_ext = S.lists.as<int>();
+    E.exts = d; E.n_ext = n_ext; E.r = d + ne7; E.J = jacobians ? d + ne7 + n : nullptr;
+    MLH_LAUNCH(calib_eval_kernel, dim3(S.n_tiles), dim3(256), 0, st, E);
+    MLH_HIP(ctx, hipGetLastError());
+    MLH_HIP(ctx, hipMemcpyAsync(residuals, E.r, sizeof(double) * n, hipMemcpyDeviceToHost, st));
+    if (jacobians) MLH_HIP(ctx, hipMemcpyAsync(jacobians, E.J, sizeof(double) * 7 * n, hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, hipStreamSynchronize(st));
+    return MLH_OK;
+}
+
+}  // namespace mlh

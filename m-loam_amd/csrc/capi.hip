@@ -873,6 +873,57 @@ int mlh_pure_odom_add_matches(mlh_ctx *ctx, int kind, const double rel_pose[7], 
     return pure_odom_add_matches(ctx, kind, frame_idx, ext_idx);
 }
 
+int mlh_calib_accumulate(mlh_ctx *ctx, int kind, const double rel_pose[7], int k_neigh, uint32_t flags, float min_match_sq_dis, float min_plane_dis, int ext_idx)
+{
+    if (!ctx || kind < 0 || kind > 1 || !rel_pose) return MLH_ERR_INVALID;
+    if (k_neigh != 5 && k_neigh != 10) return fail(ctx, MLH_ERR_UNSUPPORTED, "N_NEIGH is 5 or 10");
+    if (ext_idx < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_accumulate: negative extrinsic index");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = ensure_state(ctx, 0);
+    if (rc) return rc;
+    if ((rc = upload_pose(ctx, rel_pose))) return rc;
+    MatchArgs a;
+    a.kind_mask = 1 << kind; a.flags = flags & MLH_FLAG_CHECK_FOV; a.min_match_sq_dis = min_match_sq_dis; a.min_plane_dis = min_plane_dis;
+    a.huber_delta = 0.0; a.cov_measurement_trace = 0.0; a.dense = false; a.pose_sel = 0; a.k_neigh[0] = k_neigh;
+    if ((rc = match_launch(ctx, a))) return rc;          // as mlh_pure_odom_add_matches: the correspondences stay in HBM
+    ctx->map_read_unsynced = true;
+    return calib_accumulate(ctx, kind, ext_idx);
+}
+
+int mlh_calib_add(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info, const int32_t *ext_idx)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return calib_add(ctx, n, type, points, coeffs, sqrt_info, ext_idx);
+}
+
+int mlh_calib_use(mlh_ctx *ctx, int on)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return calib_use(ctx, on);
+}
+
+int mlh_calib_clear(mlh_ctx *ctx)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return calib_clear(ctx);
+}
+
+int mlh_calib_info(mlh_ctx *ctx, mlh_calib_store_info *out)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return calib_info(ctx, out);
+}
+
+int mlh_calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return calib_evaluate(ctx, exts, n_ext, residuals, jacobians);
+}
+
 int mlh_pure_odom_add_matches_gf(mlh_ctx *ctx, int kind, const double rel_pose[7], const double pivot[7], const double pose_i[7], const double ext[7], int k_neigh,
                                  uint32_t flags, float min_match_sq_dis, float min_plane_dis, int frame_idx, int ext_idx, float gf_ratio, uint64_t seed,
                                  int32_t *sel_out, int32_t *n_sel)

@@ -440,6 +440,22 @@ struct MargPrior {
     DevBuf ext_rows;                      // 9 doubles per extrinsic
 };
 
+// The accumulated calibration features (calib.hip): cumu_surf_map_features_ / cumu_corner_map_features_ of the estimator (estimator.cpp:714-735, 762-780) as
+// one-block LidarOnlineCalib factors in HBM. Slot s of the store: tab[10 s ..] = point[3], coeff[6], sqrt_info; type[s]; perm[s] = -1 for padding, else the
+// factor's index in the order the store was given it. 256 slots = one tile, every tile belongs to ONE extrinsic (h_tile_ext). Persists across windows.
+struct CalibStore {
+    DevBuf tab, type, perm;
+    DevBuf lists;                         // [tile_ext (n_tiles) | ext_start (n_ext + 1) | tile_pos (n_tiles)]: a tile's extrinsic; the rows of extrinsic e in `partial`;
+                                          // a tile's rank in (extrinsic, tile) order = its row of `partial`
+    DevBuf partial;                       // n_tiles x 32: a tile's 21 + 6 + cost + count sums, rows sorted by (extrinsic, tile)
+    DevBuf n_valid_dev;                   // one int: the correspondences mlh_calib_accumulate has appended
+    DevBuf eval;                          // mlh_calib_evaluate: the extrinsics, residuals and Jacobian rows
+    std::vector<int> h_tile_ext;
+    int n_tiles = 0, n_appends = 0, n_given = 0, max_ext = -1;   // n_given: factors handed over by mlh_calib_add
+    int lists_n_ext = -1;                 // the extrinsic count `lists` was made for (-1: stale)
+    bool in_use = false, device_built = false;
+};
+
 constexpr int FUSE_BLOCKS = 64;           // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
 constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
@@ -593,6 +609,7 @@ struct mlh_ctx {
     mlh::WinStore win;       // the odometry's sliding window + its local maps (window.hip)
     mlh::OdomSet odom;
     mlh::MargPrior marg;     // the window's prior (marg.hip)
+    mlh::CalibStore calib;   // the accumulated calibration features (calib.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}
@@ -734,6 +751,17 @@ int pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frame
 int pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int n_frames, double *exts, int n_ext, double huber_delta, int n_iters,
                        uint32_t const_block_mask, const double *V_update, double *cost, int32_t *n_res, int32_t *status_out);
 // the table's normal equations at the given state enqueued into OdomSet::ne_out (zeros for an empty table), the poses left in OdomSet::poses; nothing waited for
+// calib.hip: the store of accumulated LidarOnlineCalib factors and its term in the window's normal equations
+int calib_add(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info, const int32_t *ext_idx);
+int calib_accumulate(mlh_ctx *ctx, int kind, int ext_idx);       // appends the valid correspondences the last match pass of `kind` left in HBM
+int calib_use(mlh_ctx *ctx, int on);
+int calib_clear(mlh_ctx *ctx);
+int calib_info(mlh_ctx *ctx, mlh_calib_store_info *out);
+int calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians);
+bool calib_active(const mlh_ctx *ctx);                            // in use and not empty: the calls below have something to add
+int calib_ne_prepare(mlh_ctx *ctx, int n_ext);                    // MLH_ERR_INVALID when n_ext does not cover the store; buffers and tile lists for this n_ext
+// two launches behind the assembly: tile sums at the extrinsics of poses_dev ([pivot | frames | extrinsics], 7 each), then their addition into ne_dev (D*D + D + 2)
+void calib_ne_enqueue(mlh_ctx *ctx, const double *poses_dev, int n_frames, int n_ext, double huber_delta, double *ne_dev);
 int window_assemble(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta);
 // marg.hip
 int window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const double *x0, const double *J0, const double *r0);

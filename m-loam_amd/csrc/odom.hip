@@ -479,12 +479,13 @@ static int odom_upload_poses(mlh_ctx *ctx, const double pivot[7], const double *
 static int odom_ne_prepare(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, OdomNeArgs &G, size_t &n_out)
 {
     OdomSet &O = ctx->odom;
-    if (O.n <= 0) return fail(ctx, MLH_ERR_STATE, "mlh_pure_odom_set has not been called");
+    if (O.n <= 0) return fail(ctx, MLH_ERR_STATE, calib_active(ctx) ? "the factor table is empty: the window solve needs window factors beside the calibration store's (mlh_pure_odom_normal_eq and mlh_window_marginalize accept the store alone)" : "mlh_pure_odom_set has not been called");
     if (!pivot || !frames || !exts || n_frames <= O.max_frame || n_ext <= O.max_ext)
         return fail(ctx, MLH_ERR_INVALID, "pose arrays do not cover the block indices of the staged factors");
     const int D = 6 * (1 + n_frames + n_ext);
     n_out = size_t(D) * D + D + 2;
     if (n_out * sizeof(double) > 150 * 1024) return fail(ctx, MLH_ERR_UNSUPPORTED, "window too large for the LDS-resident assembly (6 (1 + frames + extrinsics) <= 136)");
+    if (calib_active(ctx)) { const int crc = calib_ne_prepare(ctx, n_ext); if (crc) return crc; }
     int rc = odom_upload_poses(ctx, pivot, frames, n_frames, exts, n_ext, G.A);
     if (rc) return rc;
     hipStream_t st = ctx->stream;
@@ -504,7 +505,8 @@ static int odom_ne_prepare(mlh_ctx *ctx, const double pivot[7], const double *fr
     return MLH_OK;
 }
 
-// one evaluation of the coupled normal equations at the poses resident in O.poses -> O.ne_out (two launches, nothing waited for)
+// one evaluation of the coupled normal equations at the poses resident in O.poses -> O.ne_out (two launches, nothing waited for); with a calibration store in
+// use (calib.hip) its one-block factors follow in two more launches (estimator.cpp:714-735, 762-780)
 static void odom_ne_enqueue(mlh_ctx *ctx, const OdomNeArgs &G, int n_frames, int n_ext, size_t n_out)
 {
     OdomSet &O = ctx->odom;
@@ -513,6 +515,7 @@ static void odom_ne_enqueue(mlh_ctx *ctx, const OdomNeArgs &G, int n_frames, int
     F.partial = O.partial.as<double>(); F.tile_group = O.tile_group.as<int>(); F.n_tiles = O.n_tiles; F.n_frames = n_frames; F.n_ext = n_ext;
     F.out = O.ne_out.as<double>();
     MLH_LAUNCH(odom_ne_finish_kernel, dim3(1), dim3(256), n_out * sizeof(double), ctx->stream, F);
+    if (calib_active(ctx)) calib_ne_enqueue(ctx, O.poses.as<double>(), n_frames, n_ext, G.huber_delta, O.ne_out.as<double>());
 }
 
 int pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
@@ -522,12 +525,20 @@ int pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frame
     OdomSet &O = ctx->odom;
     OdomNeArgs G;
     size_t n_out = 0;
-    int rc = odom_ne_prepare(ctx, pivot, frames, n_frames, exts, n_ext, G, n_out);
-    if (rc) return rc;
     const int D = 6 * (1 + n_frames + n_ext);
-    G.huber_delta = huber_delta;
-    odom_ne_enqueue(ctx, G, n_frames, n_ext, n_out);
-    MLH_HIP(ctx, hipGetLastError());
+    if (O.n <= 0 && calib_active(ctx)) {
+        // an empty factor table with a calibration store in use: the store's system alone
+        if (!pivot || !exts || n_frames < 0 || n_ext < 1 || (n_frames > 0 && !frames)) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
+        const int rc = window_assemble(ctx, pivot, frames, n_frames, exts, n_ext, huber_delta);
+        if (rc) return rc;
+        n_out = size_t(D) * D + D + 2;
+    } else {
+        int rc = odom_ne_prepare(ctx, pivot, frames, n_frames, exts, n_ext, G, n_out);
+        if (rc) return rc;
+        G.huber_delta = huber_delta;
+        odom_ne_enqueue(ctx, G, n_frames, n_ext, n_out);
+        MLH_HIP(ctx, hipGetLastError());
+    }
     hipStream_t st = ctx->stream;
     std::vector<double> h(n_out);
     MLH_HIP(ctx, hipMemcpyAsync(h.data(), O.ne_out.p, sizeof(double) * n_out, hipMemcpyDeviceToHost, st));
@@ -554,11 +565,17 @@ int window_assemble(mlh_ctx *ctx, const double pivot[7], const double *frames, i
     }
     const int D = 6 * (1 + n_frames + n_ext);
     const size_t n_out = size_t(D) * D + D + 2;
+    const bool cal = calib_active(ctx);
+    if (cal) { const int crc = calib_ne_prepare(ctx, n_ext); if (crc) return crc; }
     OdomArgs A;
     const int rc = odom_upload_poses(ctx, pivot, frames, n_frames, exts, n_ext, A);
     if (rc) return rc;
     MLH_HIP(ctx, O.ne_out.ensure(sizeof(double) * n_out));
     MLH_HIP(ctx, hipMemsetAsync(O.ne_out.p, 0, sizeof(double) * n_out, ctx->stream));
+    if (cal) {
+        calib_ne_enqueue(ctx, O.poses.as<double>(), n_frames, n_ext, huber_delta, O.ne_out.as<double>());
+        MLH_HIP(ctx, hipGetLastError());
+    }
     return MLH_OK;
 }
 

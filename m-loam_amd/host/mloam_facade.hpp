@@ -1472,9 +1472,13 @@ inline void evalWindowNormalEquations(Device &dev, const double pivot[7], const 
 // ceres::Solve of Estimator::optimizeMap's LiDAR factors (estimator.cpp:593-680), device-resident: n_iters Gauss-Newton iterations on the staged factor table
 // with the reference's constant blocks (para_pose_[0], estimator.cpp:636; para_ex_pose_[IDX_REF], :642) and every block's V_update_ as evalDegenracy left it
 // (local_param_ids in the reference's order: pivot + window poses, then extrinsics). frames / exts: in the linearisation point, out the result.
+// extra_const_mask: further blocks of [pivot | frames | extrinsics] to hold constant. With ESTIMATE_EXTRINSIC == 1 the other LiDARs' extrinsics have rows only on
+// calibration frames (useCalibFactors below); on every other frame evalDegenracy freezes them (V_update_ = 0, estimator.cpp:1671-1676) and their blocks must be
+// held constant here, or the gathered system is singular and only the + 1e-6 I retry saves it.
 // Returns the solver status (0 solved, 1 regularised, 2 an update was skipped).
 inline int solveWindow(Device &dev, const double pivot[7], std::vector<std::array<double, 7>> &frames, std::vector<std::array<double, 7>> &exts, double huber_delta,
-                       int n_iters, const std::vector<PoseLocalParameterization *> *local_param_ids = nullptr, int idx_ref = 0, double *final_cost = nullptr)
+                       int n_iters, const std::vector<PoseLocalParameterization *> *local_param_ids = nullptr, int idx_ref = 0, double *final_cost = nullptr,
+                       uint32_t extra_const_mask = 0)
 {
     const int nb = 1 + (int)frames.size() + (int)exts.size();
     std::vector<double> V;
@@ -1482,7 +1486,7 @@ inline int solveWindow(Device &dev, const double pivot[7], std::vector<std::arra
         V.resize(size_t(nb) * 36);
         for (int b = 0; b < nb; ++b) for (int k = 0; k < 36; ++k) V[size_t(b) * 36 + k] = (*local_param_ids)[size_t(b)]->V_update_[k];
     }
-    const uint32_t const_mask = 1u | (1u << (1 + (int)frames.size() + idx_ref));
+    const uint32_t const_mask = 1u | (1u << (1 + (int)frames.size() + idx_ref)) | extra_const_mask;
     int32_t n = 0, status = 0;
     double cost = 0.0;
     dev.check(mlh_pure_odom_gn_solve(dev.ctx(), pivot, frames.empty() ? nullptr : frames[0].data(), (int)frames.size(), exts.empty() ? nullptr : exts[0].data(),
@@ -1522,6 +1526,34 @@ inline mlh_window_prior_info windowPriorInfo(Device &dev)
     mlh_window_prior_info info;
     dev.check(mlh_window_prior_get(dev.ctx(), &info, nullptr, nullptr, nullptr, nullptr));
     return info;
+}
+
+// The accumulated calibration features (estimator.cpp:714-735, 762-780, 921-938, 960-977), device-resident: cumu_surf_map_features_ / cumu_corner_map_features_
+// live in the context as a store of LidarOnlineCalib factors (WindowFactorTable::accumulateMatches / accumulateStagedMatches fill it; it persists across windows).
+//   useCalibFactors     the frame_cnt_ % N_CUMU_FEATURE == 0 gate (cpp:721, 769, 921, 960): whether the store's factors enter evalWindowNormalEquations,
+//                       solveWindow and marginalizeWindow; the gate's arithmetic stays the caller's
+//   clearCalibFactors   cpp:736-740, 781-785, 936-937, 975-976 and clearState (cpp:175-176); also turns the gate off
+//   addCalibFeatures    the same append from a host list of matched features (callers that keep cumu_*_map_features_ themselves)
+inline void useCalibFactors(Device &dev, bool on) { dev.check(mlh_calib_use(dev.ctx(), on ? 1 : 0)); }
+inline void clearCalibFactors(Device &dev) { dev.check(mlh_calib_clear(dev.ctx())); }
+inline mlh_calib_store_info calibFactorInfo(Device &dev)
+{
+    mlh_calib_store_info info;
+    dev.check(mlh_calib_info(dev.ctx(), &info));
+    return info;
+}
+template <typename FeatureT>
+inline void addCalibFeatures(Device &dev, const std::vector<FeatureT> &features, int laser, double s = 1.0)
+{
+    if (features.empty()) return;
+    std::vector<int32_t> type, ei(features.size(), laser);
+    std::vector<double> pts, coef, si(features.size(), s);
+    for (const FeatureT &f : features) {
+        type.push_back(f.type_ == 's' ? 0 : 1);
+        for (int k = 0; k < 3; ++k) pts.push_back(f.point_[k]);
+        for (int k = 0; k < 6; ++k) coef.push_back(k < (int)f.coeffs_.size() ? f.coeffs_[k] : 0.0);
+    }
+    dev.check(mlh_calib_add(dev.ctx(), (int)features.size(), type.data(), pts.data(), coef.data(), si.data(), ei.data()));
 }
 
 // Estimator::evalDegenracy (estimator.cpp:1598-1680) on the window's normal equations, in the reference's argument order minus the Jacobian
@@ -1628,6 +1660,28 @@ public:
         const Params &P = params();
         dev_.check(mlh_pure_odom_add_matches(dev_.ctx(), type == 's' ? MLH_SURF : MLH_CORNER, pose, (int)n_neigh, check_fov ? MLH_FLAG_CHECK_FOV : 0u, P.MIN_MATCH_SQ_DIS,
                                              P.MIN_PLANE_DIS, frame - 1, laser));
+    }
+    // The calibration branch (ESTIMATE_EXTRINSIC == 1, estimator.cpp:1131-1149, 714-719, 762-767): LiDAR `laser`'s pivot-frame features matched against
+    // buildCalibMap's map of that LiDAR at pose_local_[laser][pivot_idx]; the valid correspondences join the context's calibration store (not this table), where the
+    // reference pushes them to cumu_surf_map_features_ / cumu_corner_map_features_. N_NEIGH 10 and the FOV check, as the reference's calls have them.
+    template <typename PointT, typename PoseT>
+    void accumulateMatches(const PointCloud<PointT> &features_in_lidar_frame, char type, const PoseT &pose_local, int laser, size_t n_neigh = 10, bool check_fov = true)
+    {
+        const int m = (int)features_in_lidar_frame.size();
+        if (m == 0) return;
+        const int kind = type == 's' ? MLH_SURF : MLH_CORNER;
+        dev_.check(mlh_features_set(dev_.ctx(), kind, features_in_lidar_frame.points.data(), (int)sizeof(PointT), m, point_traits<PointT>::intensity_off,
+                                    point_traits<PointT>::cov_off, MLH_MEM_HOST));
+        accumulateStagedMatches(type, pose_local, laser, n_neigh, check_fov);
+    }
+    template <typename PoseT>
+    void accumulateStagedMatches(char type, const PoseT &pose_local, int laser, size_t n_neigh = 10, bool check_fov = true)
+    {
+        double pose[7];
+        detail::pose_to_param(pose_local, pose);
+        const Params &P = params();
+        dev_.check(mlh_calib_accumulate(dev_.ctx(), type == 's' ? MLH_SURF : MLH_CORNER, pose, (int)n_neigh, check_fov ? MLH_FLAG_CHECK_FOV : 0u, P.MIN_MATCH_SQ_DIS,
+                                        P.MIN_PLANE_DIS, laser));
     }
 private:
     Device &dev_;

@@ -1,0 +1,129 @@
+"""The NumPy restatement of the online-calibration factors (tests/calib_cases.py) held against the reference's own lines, the inputs of the GPU tests held to the
+eigenvalue condition, and the C-ABI of the calibration store. CPU only; tests/test_gpu_calib_store.py compares the device against this restatement."""
+import ctypes as C
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import calib_cases as cc
+import marg_cases as mc
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CALIB_SYMBOLS = ["mlh_calib_accumulate", "mlh_calib_add", "mlh_calib_use", "mlh_calib_clear", "mlh_calib_info", "mlh_calib_evaluate"]
+
+
+def test_restated_factors_are_the_references(orc):
+    """1. >= 200 factors of each kind at perturbed extrinsics against LidarOnlineCalib{PlaneNorm,Edge}Factor::Evaluate compiled from the reference's lines;
+    both branches of HuberLoss(1.0) occur among them"""
+    if orc.ref_lib() is None:
+        pytest.skip("no reference build")
+    p = cc.calib_problem()
+    w = p["window"]
+    rng = np.random.default_rng(8)
+    cal = cc.concat([p["cal"], cc.make_calib(rng, w["exts_gt"], (0, 260, 240))])
+    assert (cal["types"] == 0).sum() >= 200 and (cal["types"] == 1).sum() >= 200
+    s = rng.uniform(0.5, 2.0, len(cal["types"]))
+    r, J = cc.calib_eval(cal, w["exts"], s)
+    worst_r = worst_j = 0.0
+    for i in range(len(r)):
+        rr, Jr = orc.ref_online_calib("s" if cal["types"][i] == 0 else "c", cal["points"][i], cal["coeffs"][i], s[i], w["exts"][cal["ei"][i]])
+        worst_r = max(worst_r, abs(r[i] - rr) / max(1.0, abs(rr)))
+        worst_j = max(worst_j, float(np.abs(J[i] - Jr).max()))
+        assert abs(r[i] - rr) <= 1e-12 * max(1.0, abs(rr)), i
+        np.testing.assert_allclose(J[i], Jr, rtol=1e-11, atol=1e-11)
+    print(f"restated factors: residual {worst_r:.2e}, Jacobian {worst_j:.2e}")
+    r1 = cc.calib_eval(cal, w["exts"])[0]
+    n_outer = int((np.abs(r1) > 1.0).sum())
+    assert 0 < n_outer < len(r1) and cc.calib_system(cal, w["exts"], 1)[4] == n_outer
+
+
+def test_edge_factor_on_its_line(orc):
+    """nu = 0: the reference's lines return a zero residual and a zero row (Eigen's normalized() leaves the zero vector), no NaN -- and so does the restatement"""
+    if orc.ref_lib() is None:
+        pytest.skip("no reference build")
+    cal = dict(types=np.array([1], np.int32), points=np.array([[0.5, 0.0, 0.0]]), coeffs=np.array([[1.0, 0, 0, -1.0, 0, 0]]), ei=np.array([0], np.int32))
+    rr, Jr = orc.ref_online_calib("c", cal["points"][0], cal["coeffs"][0], 1.0, cc.IDENT)
+    r, J = cc.calib_eval(cal, cc.IDENT[None, :])
+    assert rr == 0.0 and not Jr.any() and r[0] == 0.0 and not J.any()
+
+
+def test_restated_assembly_is_the_references_optimize_map(orc):
+    """2. window system + calibration term, constant columns zeroed, against Estimator::optimizeMap with ESTIMATE_EXTRINSIC = 1 on a calibration frame; on any
+    other frame the term is absent"""
+    if orc.ref_lib() is None:
+        pytest.skip("no reference build")
+    p = cc.calib_problem()
+    w, cal = p["window"], p["cal"]
+    nf, ne = w["n_frames"], w["n_ext"]
+    assert not (w["ei"] != 0).any()
+    rows_w = np.zeros((len(w["types"]), 12))
+    rows_w[:, 0] = 0; rows_w[:, 1] = w["fi"] + 1; rows_w[:, 2] = w["types"]; rows_w[:, 3:6] = w["points"]; rows_w[:, 6:12] = w["coeffs"]
+    rows_c = np.zeros((len(cal["types"]), 12))
+    rows_c[:, 0] = cal["ei"]; rows_c[:, 1] = 0; rows_c[:, 2] = cal["types"]; rows_c[:, 3:6] = cal["points"]; rows_c[:, 6:12] = cal["coeffs"]
+    poses = np.vstack([w["pivot"][None, :], w["frames"]])
+    D = 6 * (1 + nf + ne)
+    free = np.ones(D, bool); free[:6] = False; free[6 * (1 + nf):6 * (2 + nf)] = False
+    for frame_cnt, with_calib in ((10, True), (7, False)):
+        got = orc.ref_optimize_map(poses, w["exts"], np.vstack([rows_w, rows_c]), estimate_extrinsic=1, frame_cnt=frame_cnt, n_cumu_feature=10, num_iterations=4)
+        A, _, cost = cc.window_system(orc, w, cal if with_calib else None, w["pivot"], w["frames"], w["exts"])
+        H = A * np.outer(free, free)
+        e_h, e_c = float(np.abs(got["H"] - H).max()) / float(np.abs(H).max()), abs(got["cost"] - cost) / cost
+        print(f"frame_cnt {frame_cnt}: H {e_h:.2e}, cost {e_c:.2e}, blocks {got['n_blocks']}")
+        assert e_h <= 1e-10 and e_c <= 1e-11
+        assert got["n_blocks"] == len(w["types"]) + (len(cal["types"]) if with_calib else 0)
+        if not with_calib:
+            assert not got["H"][6 * (2 + nf):, 6 * (2 + nf):].any()
+
+
+def test_no_eigenvalue_near_the_threshold():
+    """3. for every matrix the GPU chains decompose (extrinsic prior rows on), no eigenvalue of the restatement lies in [1e-10, 1e-6]"""
+    for label, lam in cc.decomposed_spectra():
+        bad = lam[(lam >= 1e-10) & (lam <= 1e-6)]
+        assert bad.size == 0, (label, bad)
+
+
+def test_chain_store_changes_the_solution():
+    """the store's term moves an extrinsic by > 1e-5 in the chains: the GPU chain test is not vacuous"""
+    for nf, ne in cc.CHAIN_SHAPES:
+        a, b = cc.chain_reference(nf, ne), cc.chain_reference(nf, ne, False)
+        assert max(np.abs(x[2] - y[2]).max() for x, y in zip(a, b)) > 1e-5, (nf, ne)
+
+
+def test_store_cases_cross_the_tile_edges():
+    for name, counts in cc.STORE_COUNTS.items():
+        c = cc.store_case(name)
+        per_append = sorted(int((p["ei"] == e).sum()) for p in c["parts"] for e in range(len(counts[0])))
+        assert {1, 255, 256, 257} <= set(per_append) if name == "1x4" else {255, 257} <= set(per_append)
+        assert len(c["parts"][1]["types"]) >= 5000
+        r = cc.calib_eval(c["all"], c["window"]["exts"])[0]
+        assert 0 < (np.abs(r) > 1.0).sum() < len(r)
+
+
+def test_library_exports_the_calibration_store(mla):
+    """4. the header declares every calibration entry point and the built library exports it"""
+    hdr = open(os.path.join(ROOT, "include", "mloam_hip.h")).read()
+    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    lib = C.CDLL(os.path.join(ROOT, "m-loam_amd", "lib", "libmloam_hip.so"))
+    for nm in CALIB_SYMBOLS:
+        assert re.search(r"\bint\s+" + nm + r"\s*\(\s*mlh_ctx\s*\*", hdr), nm
+        assert nm in mla.EXPORTED_SYMBOLS, nm
+        assert getattr(lib, nm) is not None, nm
+    assert "mlh_calib_store_info" in hdr
+    assert C.sizeof(mla.CalibStoreInfo) == 24
+
+
+def test_tile_bookkeeping_under_sanitizers(tmp_path):
+    """the host-side grouping / padding of mlh_calib_add (m-loam_amd/csrc/calib_group.hpp) in a stand-alone program built with -fsanitize=address,undefined:
+    counts 0, 1, 255..257, interleaved extrinsics"""
+    exe = tmp_path / "calib_group_main"
+    src = os.path.join(ROOT, "tests", "host", "calib_group_main.cpp")
+    cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
+           "-I", os.path.join(ROOT, "m-loam_amd", "csrc"), src, "-o", str(exe)]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    assert b.returncode == 0, b.stderr[-2000:]
+    r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
+    assert "calib_group: ok" in r.stdout
