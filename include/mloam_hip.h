@@ -410,6 +410,96 @@ int mlh_calib_clear(mlh_ctx *ctx);
 int mlh_calib_info(mlh_ctx *ctx, mlh_calib_store_info *out);
 int mlh_calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians);
 
+/* ---------------------------------------------------------------- (f11) Scan Context place recognition, on the device
+ * The front of the loop-closure process: SCManager (mloam_loop/src/scan_context.cpp:155-323) as PoseGraph::detectLoop drives it (mloam_loop/src/pose_graph.cpp:
+ * 281-328). A context keeps one store in HBM: per entry the descriptor (f32, num_ring x num_sector, column-major as Eigen stores it), the ring key (f32), the sector
+ * key and the column norms (f64), and on the host the optional position. FGR, the pose graph and the geometric verification are not part of this library.
+ * Reproduced, with the lines restated:
+ *   descriptor (cpp:155-186): z' = float(double(z) + lidar_height); range = sqrt(x x + y y) in f32; dropped only if range > max_radius (a point at exactly
+ *     max_radius stays); ring = max(min(R, int(ceil(double(range) / max_radius * R))), 1); angle = xy2theta (cpp:38-51) as written, signed zeros and infinities
+ *     included; sector = max(min(S, int(ceil(double(angle) / 360.0 * S))), 1); a cell is the maximum of z', starting at -1000; cells still equal to -1000 become 0,
+ *     so a z' of exactly -1000 or below reads as empty. The maximum is order-independent: the descriptor is bit-exact whatever the schedule. Every value is a
+ *     widened float, so it is stored as f32.
+ *   CHOSEN: xy2theta calls unqualified atan on floats; which overload a translation unit gets depends on its includes. The float overloads are restated (atanf,
+ *     then (180 / M_PI) * ... in double, returned as float). The choice matters only within a few f32 ulps of a sector edge: a point whose sector value lies within
+ *     4e-4 sectors of an integer is not binned by the kernel; the host decides it with its own libm and its verdict is applied before the keys are made
+ *     (mlh_sc_store_info::points_host_decided counts them: ~0.08 % of a cloud, and every point on an axis).
+ *   CHOSEN: x = y = 0 makes the reference convert a NaN to int; what x86 does is restated (ring 1, sector 1).
+ *   DEPARTURE: a point with a non-finite coordinate is skipped and counted (points_skipped); the reference's behaviour there is undefined.
+ *   keys (cpp:188-218, 225): ring key = row means in f64, cast to f32; sector key = column means in f64; the f64 column norms distDirectSC recomputes for every
+ *     shift are kept beside them. Sums run left to right (Eigen's reduction order is not restated).
+ *   candidates (cpp:246-278): early return when que_index < num_exclude_recent + 1 (the period counter does not advance); the searched set is the prefix
+ *     [0, que_index - num_exclude_recent) AS OF THE LAST REBUILD, rebuilt when counter % tree_making_period == 0 -- stale in between, reproduced. Exact k-NN with
+ *     nanoflann's L2_Adaptor arithmetic in f32 (nanoflann.hpp:432-461: groups of four, result += d0 d0 + d1 d1 + d2 d2 + d3 d3, then the tail), bit-exact.
+ *     CHOSEN: a brute-force kernel replaces the tree, and equal distances go to the lower index (in the reference: the tree's visiting order). With fewer searched
+ *     entries than num_candidates the reference's zero-filled index array re-scores entry 0, which changes nothing: every searched entry is scored once
+ *     (n_candidates_scored).
+ *   score (cpp:80-153, 286-322): fast alignment = first-lowest Frobenius norm over all S shifts of the candidate's sector key; search radius
+ *     round(0.5 search_ratio S), the shifts within it visited in ascending order; distDirectSC in f64 skips columns where either norm is 0 -- with no effective
+ *     column the distance is NaN, NaN never wins: nearest_index stays -1 and score 1e7; strict < over shifts and over candidates, in candidate order;
+ *     yaw_diff_rad = deg2rad(float(shift * (360.0 / S))) with the reference's float deg2rad; then score < dist_thres; then detectLoop's rejection
+ *     |t_que - t_match| > loop_distance_threshold (pose_graph.cpp:296-315) on the stored positions -- none when either entry has no position.
+ * mlh_sc_reset = setParameter: validates (MLH_ERR_INVALID outside num_ring >= 1, num_sector >= 1, num_ring * num_sector <= 8192, 1 <= num_candidates <= 256,
+ *   a finite positive max_radius, tree_making_period >= 1, num_exclude_recent >= 0, a finite lidar_height and search_ratio >= 0), empties the store, frees its
+ *   memory and zeroes the period counter. opts == NULL: the defaults. The other calls return MLH_ERR_STATE before the first reset.
+ * mlh_sc_add = makeAndSaveScancontextAndKeys of the concatenation of n_clouds <= 3 clouds (full_cloud_ + outlier_cloud_, pose_graph.cpp:283-286): records of
+ *   stride_bytes in `mem`, only xyz read; empty clouds are allowed (n[k] == 0, clouds[k] may be NULL). position (3 doubles, may be NULL) is the keyframe's
+ *   pose_w_.t_. *index_out (may be NULL) <- the entry's index. One host wait (the undecided points), one more when there are more than 2048 of them.
+ * mlh_sc_add_keyframe: the same from keyframe `key` of the store of (f5) / (f7): its surf, corner and outlier clouds device to device, its stored translation.
+ *   DEPARTURE: the mapper's store has no full cloud, so these descriptors are built from thinned features: comparable with each other, not with descriptors of
+ *   full clouds.
+ * mlh_sc_detect = detectLoopClosureID(que_index) + detectLoop's rejection. Five launches and one copy whatever the size of the store and num_candidates (key
+ *   distances, selection, one workgroup per candidate, the ordered argmin, the marker of the wait) and ONE host wait. A result that the distance test rejects keeps
+ *   score, shift, yaw and nearest_index, has match_index -1 and rejected_by_distance 1. The early return gives {-1, score -1, yaw 0, nearest -1}.
+ * mlh_sc_candidates: the candidate search alone, stateless: the min(prefix, num_candidates) nearest ring keys of entry que_index among entries [0, prefix), in
+ *   the order they are scored, with their squared distances (d2_out may be NULL). idx_out: capacity >= num_candidates.
+ * mlh_sc_distance = distanceBtnScanContext(descriptor i, descriptor j): (min distance, its shift); the distance is 1e7 and the shift 0 when every shift is NaN.
+ * mlh_sc_fetch: entry `index` as f64 num_ring x num_sector column-major (desc), f32 num_ring (ring_key), f64 num_sector (sector_key); each may be NULL. The
+ *   host makes getScanContextImage of it.
+ * mlh_keyframes_reset does not touch this store; mlh_destroy frees it. */
+typedef struct mlh_sc_opts {
+    double lidar_height;             /* LIDAR_HEIGHT */
+    int32_t num_ring, num_sector;    /* PC_NUM_RING, PC_NUM_SECTOR */
+    double max_radius;               /* PC_MAX_RADIUS */
+    int32_t num_exclude_recent;      /* NUM_EXCLUDE_RECENT */
+    int32_t num_candidates;          /* NUM_CANDIDATES_FROM_TREE */
+    double search_ratio;             /* SEARCH_RATIO */
+    double dist_thres;               /* SC_DIST_THRES */
+    int32_t tree_making_period;      /* TREE_MAKING_PERIOD */
+    int32_t reserved;
+    double loop_distance_threshold;  /* LOOP_DISTANCE_THRESHOLD; < 0: no rejection */
+} mlh_sc_opts;
+typedef struct mlh_sc_result {
+    int32_t match_index;             /* -1: no loop */
+    int32_t nearest_index;           /* the argmin before the threshold (-1: nothing scored below 1e7) */
+    int32_t shift;                   /* nn_align, in sectors */
+    int32_t n_candidates_scored;
+    int32_t rejected_by_distance;
+    float yaw_diff_rad;
+    double score;                    /* min_dist */
+} mlh_sc_result;
+typedef struct mlh_sc_store_info {
+    int32_t n_entries;
+    int32_t searched_prefix;         /* entries [0, searched_prefix) as of the last rebuild */
+    int32_t period_counter;          /* tree_making_period_conter_ */
+    int32_t desc_tile_points;        /* points a workgroup of the descriptor kernel takes per pass */
+    int32_t desc_wrap_points;        /* points all its workgroups take per pass: a larger cloud goes round the grid-stride loop again */
+    int32_t last_host_decided, last_skipped;     /* of the most recent add */
+    int32_t reserved;
+    int64_t points_host_decided;     /* since the last reset: points the host binned with its libm */
+    int64_t points_skipped;          /* ... points with a non-finite coordinate */
+    int64_t bytes_hbm;               /* device memory the store holds */
+} mlh_sc_store_info;
+void mlh_sc_opts_default(mlh_sc_opts *o);    /* mloam_loop/config/config_loop_realvehicle.yaml: 2.0, 20, 60, 80.0, 50, 50, 0.1, 0.5, 10, 50.0 */
+int mlh_sc_reset(mlh_ctx *ctx, const mlh_sc_opts *opts);
+int mlh_sc_add(mlh_ctx *ctx, const void *const *clouds, const int32_t *n, int n_clouds, int stride_bytes, int mem, const double *position, int32_t *index_out);
+int mlh_sc_add_keyframe(mlh_ctx *ctx, int32_t key, int32_t *index_out);
+int mlh_sc_detect(mlh_ctx *ctx, int32_t que_index, mlh_sc_result *result);
+int mlh_sc_candidates(mlh_ctx *ctx, int32_t que_index, int32_t prefix, int32_t *idx_out, float *d2_out, int32_t *n_out);
+int mlh_sc_distance(mlh_ctx *ctx, int32_t i, int32_t j, double *dist, int32_t *shift);
+int mlh_sc_fetch(mlh_ctx *ctx, int32_t index, double *desc, float *ring_key, double *sector_key);
+int mlh_sc_info(mlh_ctx *ctx, mlh_sc_store_info *out);
+
 /* (f1) cloudUCTAssociateToMap (lidar_mapper_keyframe.cpp:1116-1158): moves one keyframe's feature cloud into the map frame while
  * building the local map (extractSurroundingKeyFrames, cpp:254-354). Per point (intensity = LiDAR index n):
  *   with_ua: point_sel = pose_ext[n]^-1 * p; Sigma = evalPointUncertainty(point_sel, pose_global (+) pose_ext[n]) where the

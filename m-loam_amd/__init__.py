@@ -127,6 +127,41 @@ class CalibStoreInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ScOpts(C.Structure):
+    """mlh_sc_opts"""
+    _fields_ = [("lidar_height", cd_), ("num_ring", C.c_int32), ("num_sector", C.c_int32), ("max_radius", cd_), ("num_exclude_recent", C.c_int32),
+                ("num_candidates", C.c_int32), ("search_ratio", cd_), ("dist_thres", cd_), ("tree_making_period", C.c_int32), ("reserved", C.c_int32),
+                ("loop_distance_threshold", cd_)]
+
+
+class ScResult(C.Structure):
+    """mlh_sc_result"""
+    _fields_ = [("match_index", C.c_int32), ("nearest_index", C.c_int32), ("shift", C.c_int32), ("n_candidates_scored", C.c_int32),
+                ("rejected_by_distance", C.c_int32), ("yaw_diff_rad", C.c_float), ("score", cd_)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class ScStoreInfo(C.Structure):
+    """mlh_sc_store_info"""
+    _fields_ = [("n_entries", C.c_int32), ("searched_prefix", C.c_int32), ("period_counter", C.c_int32), ("desc_tile_points", C.c_int32),
+                ("desc_wrap_points", C.c_int32), ("last_host_decided", C.c_int32), ("last_skipped", C.c_int32), ("reserved", C.c_int32),
+                ("points_host_decided", C.c_int64), ("points_skipped", C.c_int64), ("bytes_hbm", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+def sc_opts(**kw) -> ScOpts:
+    """mlh_sc_opts_default (config_loop_realvehicle.yaml), then the given fields"""
+    o = ScOpts()
+    load_library().mlh_sc_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -277,6 +312,16 @@ def load_library():
     lib.mlh_calib_clear.argtypes = [vp]
     lib.mlh_calib_info.argtypes = [vp, C.POINTER(CalibStoreInfo)]
     lib.mlh_calib_evaluate.argtypes = [vp, vp, ci, vp, vp]
+    lib.mlh_sc_opts_default.argtypes = [C.POINTER(ScOpts)]
+    lib.mlh_sc_opts_default.restype = None
+    lib.mlh_sc_reset.argtypes = [vp, C.POINTER(ScOpts)]
+    lib.mlh_sc_add.argtypes = [vp, vp, vp, ci, ci, ci, vp, C.POINTER(C.c_int32)]
+    lib.mlh_sc_add_keyframe.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.mlh_sc_detect.argtypes = [vp, C.c_int32, C.POINTER(ScResult)]
+    lib.mlh_sc_candidates.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int32)]
+    lib.mlh_sc_distance.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(cd), C.POINTER(C.c_int32)]
+    lib.mlh_sc_fetch.argtypes = [vp, C.c_int32, vp, vp, vp]
+    lib.mlh_sc_info.argtypes = [vp, C.POINTER(ScStoreInfo)]
     lib.mlh_pure_odom_add_matches.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, ci, ci]
     lib.mlh_pure_odom_add_matches_gf.argtypes = [vp, ci, vp, vp, vp, vp, ci, C.c_uint32, cf, cf, ci, ci, cf, C.c_uint64, vp, C.POINTER(C.c_int32)]
     lib.mlh_knn.argtypes = [vp, ci, vp, ci, ci, vp, vp]
@@ -325,6 +370,7 @@ EXPORTED_SYMBOLS = [
     "mlh_window_build_local_map", "mlh_window_map_cloud",
     "mlh_window_prior_set", "mlh_window_prior_get", "mlh_window_prior_clear", "mlh_window_prior_evaluate", "mlh_window_ext_prior_set", "mlh_window_marginalize",
     "mlh_calib_accumulate", "mlh_calib_add", "mlh_calib_use", "mlh_calib_clear", "mlh_calib_info", "mlh_calib_evaluate",
+    "mlh_sc_opts_default", "mlh_sc_reset", "mlh_sc_add", "mlh_sc_add_keyframe", "mlh_sc_detect", "mlh_sc_candidates", "mlh_sc_distance", "mlh_sc_fetch", "mlh_sc_info",
 ]
 
 
@@ -763,6 +809,65 @@ class Context:
         r = np.zeros(n); J = np.zeros((n, 7)) if want_jacobians else None
         self._ck(self.lib.mlh_calib_evaluate(self.h, _p(ex), len(ex), _p(r), _p(J)))
         return r, J
+
+    # ---- Scan Context place recognition (SCManager + detectLoop's distance rejection on the device)
+    def sc_reset(self, opts: ScOpts = None):
+        """setParameter: empties the store and zeroes the period counter (mlh_sc_reset); None: the shipped configuration"""
+        self._sc_opts = opts if opts is not None else sc_opts()
+        self._ck(self.lib.mlh_sc_reset(self.h, C.byref(self._sc_opts)))
+
+    def sc_add(self, clouds, position=None):
+        """makeAndSaveScancontextAndKeys of the concatenation of up to three clouds ((n, >= 3) float32 arrays, torch CUDA tensors or device clouds, all of one
+        stride and memory kind; a single cloud may be given bare) -> the entry's index (mlh_sc_add)"""
+        if not isinstance(clouds, (list, tuple)):
+            clouds = [clouds]
+        src = [_src(c) for c in clouds]
+        live = [s for s in src if s[2] > 0] or src[:1]
+        stride, mem = (live[0][1], live[0][3]) if live else (16, MEM_HOST)
+        assert all(s[1] == stride and s[3] == mem for s in live), "the clouds share record stride and memory kind"
+        ptrs = (C.c_void_p * max(len(src), 1))(*[(s[0] if s[2] > 0 else None) for s in src])
+        ns = (C.c_int32 * max(len(src), 1))(*[s[2] for s in src])
+        pos = None if position is None else np.ascontiguousarray(position, np.float64).reshape(3)
+        idx = C.c_int32(-1)
+        self._ck(self.lib.mlh_sc_add(self.h, ptrs, ns, len(src), stride, mem, _p(pos), C.byref(idx)))
+        return idx.value
+
+    def sc_add_keyframe(self, key):
+        """the same from keyframe `key` of the mapper's store: its surf, corner and outlier clouds device to device, its stored translation (mlh_sc_add_keyframe)"""
+        idx = C.c_int32(-1)
+        self._ck(self.lib.mlh_sc_add_keyframe(self.h, int(key), C.byref(idx)))
+        return idx.value
+
+    def sc_detect(self, que_index) -> dict:
+        """detectLoopClosureID + detectLoop's distance rejection (mlh_sc_detect)"""
+        r = ScResult()
+        self._ck(self.lib.mlh_sc_detect(self.h, int(que_index), C.byref(r)))
+        return r.as_dict()
+
+    def sc_candidates(self, que_index, prefix):
+        """the candidate search alone: (indices in scoring order, squared key distances) among entries [0, prefix) (mlh_sc_candidates)"""
+        k = self._sc_opts.num_candidates
+        idx, d2, n = np.zeros(k, np.int32), np.zeros(k, np.float32), C.c_int32(0)
+        self._ck(self.lib.mlh_sc_candidates(self.h, int(que_index), int(prefix), _p(idx), _p(d2), C.byref(n)))
+        return idx[:n.value].copy(), d2[:n.value].copy()
+
+    def sc_distance(self, i, j):
+        """distanceBtnScanContext(descriptor i, descriptor j) -> (distance, shift) (mlh_sc_distance)"""
+        d, s = C.c_double(0.0), C.c_int32(0)
+        self._ck(self.lib.mlh_sc_distance(self.h, int(i), int(j), C.byref(d), C.byref(s)))
+        return d.value, s.value
+
+    def sc_fetch(self, index):
+        """entry `index` -> (descriptor (num_ring, num_sector) float64, ring key float32, sector key float64) (mlh_sc_fetch)"""
+        R, S = self._sc_opts.num_ring, self._sc_opts.num_sector
+        desc, rk, sk = np.zeros((S, R)), np.zeros(R, np.float32), np.zeros(S)
+        self._ck(self.lib.mlh_sc_fetch(self.h, int(index), _p(desc), _p(rk), _p(sk)))
+        return np.ascontiguousarray(desc.T), rk, sk
+
+    def sc_info(self) -> dict:
+        info = ScStoreInfo()
+        self._ck(self.lib.mlh_sc_info(self.h, C.byref(info)))
+        return info.as_dict()
 
     def downsample_current_scan(self, kind, points4, leaf, ext_poses, ext_covs, cov_measurement, with_ua=True, trace_threshold=0.6, fetch=True):
         """downsampleCurrentScan for one kind; the result becomes the kind's feature set and, with fetch, is also returned (m, 11)

@@ -13,6 +13,7 @@
 #include <sched.h>
 #include "../../include/mloam_hip.h"
 #include "records.hpp"
+#include "sc_host.hpp"
 
 namespace mlh {
 
@@ -456,6 +457,25 @@ struct CalibStore {
     bool in_use = false, device_built = false;
 };
 
+// The Scan Context store (scancontext.hip; mloam_loop/src/scan_context.cpp:155-323): per entry the descriptor (f32, num_ring x num_sector, column-major), the ring
+// key (f32 x num_ring), the sector key and the column norms (f64 x num_sector each), appended; the positions and the period bookkeeping on the host.
+struct ScStore {
+    mlh_sc_opts opts;
+    bool configured = false;
+    DevBuf desc, ring_key, sector_key, col_norm;
+    int n = 0, cap = 0;                   // entries, entries the four buffers have room for
+    std::vector<double> pos;              // 3 per entry
+    std::vector<unsigned char> has_pos;
+    ScBook book;
+    DevBuf unc;                           // float4 {x, y, z', ring} of the points an add left undecided
+    DevBuf counters;                      // ints: [0] undecided, [1] skipped (non-finite)
+    DevBuf keys;                          // one u64 per searched entry: (f32 bits of the key distance) << 32 | index
+    DevBuf work;                          // a query's small arrays (scancontext.hip: ScWork)
+    PinnedBuf h_pin;                      // landing place of the counters, the undecided points, a query's result, a fetched entry
+    int last_host_decided = 0, last_skipped = 0;
+    long long points_host_decided = 0, points_skipped = 0;
+};
+
 constexpr int FUSE_BLOCKS = 64;           // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
 constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
@@ -610,6 +630,7 @@ struct mlh_ctx {
     mlh::OdomSet odom;
     mlh::MargPrior marg;     // the window's prior (marg.hip)
     mlh::CalibStore calib;   // the accumulated calibration features (calib.hip)
+    mlh::ScStore sc;         // the Scan Context store (scancontext.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}

@@ -2367,4 +2367,102 @@ private:
     bool in_flight_ = false;
 };
 
+// ------------------------------------------------------------------ Scan Context place recognition (mloam_loop: scan_context.hpp / scan_context.cpp:155-323)
+// SCManager with the reference's names over the context's store in HBM. A caller that keeps PoseGraph (pose_graph.cpp) replaces its sc_manager_ member by one of
+// these and keeps its call sites: setParameter once; makeAndSaveScancontextAndKeys per keyframe (PoseGraph::detectLoop, cpp:283-286; the position overload lets
+// detectLoop's distance rejection run inside detectLoopClosureID); detectLoopClosureID(que_index); getDataBaseSize. getScanContextImage is OpenCV colouring of the
+// descriptor: fetchScanContext returns the matrix (column-major, as Eigen stores it) and the colouring stays with the caller. What is reproduced, chosen and left
+// out: include/mloam_hip.h (f11).
+struct QueryResult {                                      // scan_context.hpp:44-60
+    QueryResult(int match_index, double score, float yaw_diff_rad) : match_index_(match_index), score_(score), yaw_diff_rad_(yaw_diff_rad) {}
+    int match_index_;
+    double score_;
+    float yaw_diff_rad_;
+};
+
+class SCManager {
+public:
+    explicit SCManager(Device &dev) : dev_(dev) {}
+    // scan_context.hpp:81-119: pc_unit_sectorangle and pc_unit_ringgap are 360 / pc_num_sector and pc_max_radius / pc_num_ring in every caller; the store derives them
+    void setParameter(double lidar_height, int pc_num_ring, int pc_num_sector, double pc_max_radius, double /*pc_unit_sectorangle*/, double /*pc_unit_ringgap*/,
+                      int num_exclude_recent, int num_candidates_from_tree, double search_ratio, double sc_dist_thres, int tree_making_period,
+                      double loop_distance_threshold = -1.0)
+    {
+        mlh_sc_opts_default(&opts_);
+        opts_.lidar_height = lidar_height; opts_.num_ring = pc_num_ring; opts_.num_sector = pc_num_sector; opts_.max_radius = pc_max_radius;
+        opts_.num_exclude_recent = num_exclude_recent; opts_.num_candidates = num_candidates_from_tree; opts_.search_ratio = search_ratio;
+        opts_.dist_thres = sc_dist_thres; opts_.tree_making_period = tree_making_period; opts_.loop_distance_threshold = loop_distance_threshold;
+        dev_.check(mlh_sc_reset(dev_.ctx(), &opts_));
+    }
+    // makeAndSaveScancontextAndKeys(scan_down): any cloud type whose points begin with x, y, z; `position`: the keyframe's pose_w_.t_ (3 doubles) or nullptr
+    template <class CloudT> int makeAndSaveScancontextAndKeys(const CloudT &scan_down, const double *position = nullptr)
+    {
+        const void *clouds[1] = {scan_down.points.empty() ? nullptr : static_cast<const void *>(scan_down.points.data())};
+        const int32_t n[1] = {int32_t(scan_down.points.size())};
+        return add(clouds, n, 1, int(sizeof(scan_down.points[0])), position);
+    }
+    // the concatenation detectLoop makes on the host (full_cloud_ + outlier_cloud_), without making it
+    template <class CloudT> int makeAndSaveScancontextAndKeys(const CloudT &full_cloud, const CloudT &outlier_cloud, const double *position = nullptr)
+    {
+        const void *clouds[2] = {full_cloud.points.empty() ? nullptr : static_cast<const void *>(full_cloud.points.data()),
+                                 outlier_cloud.points.empty() ? nullptr : static_cast<const void *>(outlier_cloud.points.data())};
+        const int32_t n[2] = {int32_t(full_cloud.points.size()), int32_t(outlier_cloud.points.size())};
+        return add(clouds, n, 2, int(sizeof(full_cloud.points[0])), position);
+    }
+    // from a keyframe of the mapper's store on the same context (thinned features: comparable with each other, not with descriptors of full clouds)
+    int makeAndSaveScancontextAndKeysFromKeyframe(int key)
+    {
+        int32_t idx = -1;
+        dev_.check(mlh_sc_add_keyframe(dev_.ctx(), key, &idx));
+        return idx;
+    }
+    QueryResult detectLoopClosureID(const int &que_index)
+    {
+        dev_.check(mlh_sc_detect(dev_.ctx(), que_index, &last_));
+        return QueryResult(last_.match_index, last_.score, last_.yaw_diff_rad);
+    }
+    const mlh_sc_result &lastResult() const { return last_; }      // nearest_index, shift, n_candidates_scored, rejected_by_distance of the last query
+    size_t getDataBaseSize() const
+    {
+        mlh_sc_store_info info;
+        dev_.check(mlh_sc_info(dev_.ctx(), &info));
+        return size_t(info.n_entries);
+    }
+    std::pair<double, int> distanceBtnScanContext(int i, int j)
+    {
+        double d = 0.0;
+        int32_t s = 0;
+        dev_.check(mlh_sc_distance(dev_.ctx(), i, j, &d, &s));
+        return std::make_pair(d, int(s));
+    }
+    // polarcontexts_[que_index]: num_ring x num_sector doubles, column-major (what getScanContextImage colours)
+    std::vector<double> fetchScanContext(int que_index)
+    {
+        std::vector<double> desc(size_t(opts_.num_ring) * size_t(opts_.num_sector));
+        dev_.check(mlh_sc_fetch(dev_.ctx(), que_index, desc.data(), nullptr, nullptr));
+        return desc;
+    }
+    const mlh_sc_opts &options() const { return opts_; }
+private:
+    int add(const void *const *clouds, const int32_t *n, int n_clouds, int stride, const double *position)
+    {
+        int32_t idx = -1;
+        dev_.check(mlh_sc_add(dev_.ctx(), clouds, n, n_clouds, stride, MLH_MEM_HOST, position, &idx));
+        return idx;
+    }
+    Device &dev_;
+    mlh_sc_opts opts_{};
+    mlh_sc_result last_{};
+};
+
+// PoseGraph::detectLoop (pose_graph.cpp:281-328) up to the geometric verification: descriptor of full_cloud_ + outlier_cloud_, query, distance rejection against
+// the matched keyframe's position (here inside the query: setParameter's loop_distance_threshold) -> (match index or -1, yaw difference)
+template <class CloudT>
+inline std::pair<int, double> detectLoop(SCManager &sc_manager, const CloudT &full_cloud, const CloudT &outlier_cloud, const double t_que[3], const int que_index)
+{
+    sc_manager.makeAndSaveScancontextAndKeys(full_cloud, outlier_cloud, t_que);
+    const QueryResult qr = sc_manager.detectLoopClosureID(que_index);
+    return std::make_pair(qr.match_index_, double(qr.yaw_diff_rad_));
+}
+
 }  // namespace mloam_hip
