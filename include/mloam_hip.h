@@ -500,6 +500,111 @@ int mlh_sc_distance(mlh_ctx *ctx, int32_t i, int32_t j, double *dist, int32_t *s
 int mlh_sc_fetch(mlh_ctx *ctx, int32_t index, double *desc, float *ring_key, double *sector_key);
 int mlh_sc_info(mlh_ctx *ctx, mlh_sc_store_info *out);
 
+/* ---------------------------------------------------------------- (f12) loop-closure local registration, on the device
+ * The geometric verification that turns a Scan Context candidate into a loop edge: PoseGraph::constructLocalMap (mloam_loop/src/pose_graph.cpp:364-419) and
+ * LoopRegistration::performLocalRegistration (mloam_loop/src/loop_registration.cpp:104-211) with the loop package's own match functions (mloam_loop/include/
+ * mloam_loop/utility/feature_extract.hpp:28-43, 77-247) and factor (mloam_loop/include/mloam_loop/factor/lidar_map_plane_norm_factor.hpp:47-87). FGR / FPFH
+ * (performGlobalRegistration), checkTemporalConsistency, the pose graph and its optimisation are not part of this library: a caller keeps FGR on the host (the
+ * two surf clouds are fetched with mlh_loop_cloud) or starts from the Scan Context yaw. A loop process uses a context of its own: mlh_loop_match, mlh_loop_evaluate
+ * and mlh_loop_register OVERWRITE the context's two map indexes (mlh_map_set) and its solver state; they return MLH_ERR_STATE while a solve submitted with
+ * mlh_*_begin is uncollected and MLH_ERR_UNSUPPORTED under a communicator. DEPARTURE from the plan of staging the data clouds as the context's feature sets: the
+ * kernels read them where mlh_loop_build_clouds / mlh_loop_set_clouds left them, so the feature sets are NOT touched.
+ * The four clouds: `which` = MLH_LOOP_MODEL_SURF / MODEL_CORNER (laser_cloud_*_from_map: the match side) / DATA_SURF / DATA_CORNER (laser_cloud_*: the query side),
+ * 16-byte {x, y, z, intensity} records in HBM.
+ * mlh_loop_build_clouds = constructLocalMap. Two lists of (keyframe key of the store of (f5), 4 x 4 f32 row-major matrix): the data list carries
+ *   T_ini_map_kf.cast<float>() per keyframe (cpp:381-385), the model list T_relative.cast<float>() (cpp:405-408). WHICH keys go in -- the index windows, the
+ *   `que_index + j < 0` and `match_index + j >= que_index` skips, missing keyframes -- and the f64 matrix chains are host arithmetic of the caller (the C++ facade's
+ *   LoopLocalMap restates them). On the device: ONE launch transforms every segment of all four clouds (pcl::transformPointCloud in f32: ((r0 x + r1 y) + r2 z) + t,
+ *   no contraction, intensity carried; the launch the window's local maps use), concatenated in list order; then four pcl::VoxelGrid<PointXYZI> filters through the
+ *   context's voxel-grid path at opts->leaf_surf / leaf_corner (mlh_set_voxel_member_order applies). n_pre[4] / n_ds[4] <- the pre-filter and filtered counts.
+ *   Launches do not depend on the number of keyframes; two host waits (the clouds' bounds; the filtered counts); no device allocation once the buffers have grown
+ *   (mlh_loop_info::allocations). A key that is not in the store, a non-finite matrix entry or more than 4096 keys in a list: MLH_ERR_INVALID, nothing launched.
+ * mlh_loop_set_clouds: the four (already filtered) clouds given directly, for callers with their own keyframe containers: records of stride_bytes with xyz at 0
+ *   and the intensity at intensity_offset_bytes (< 0: stored as 0), all host or all device; empty clouds are allowed (n[k] == 0, clouds[k] may be NULL). They become
+ *   the filtered clouds; the pre-filter clouds are emptied.
+ * mlh_loop_cloud: the pre-filter (filtered = 0) or filtered (1) cloud `which`; *device_points is NULL for an empty one. Valid until the next build / set.
+ * mlh_loop_match = matchSurfFromMap (kind MLH_SURF) / matchCornerFromMap (MLH_CORNER) of the filtered data cloud against the filtered model cloud at T (16 doubles,
+ *   row-major, cast to f32 as cpp:145, 152 do) -- a test and diagnosis entry in the spirit of mlh_match_coeffs. Per data point i: valid[i]; coeffs[4 i ..] (surf) or
+ *   coeffs[8 i ..] = feature1, feature2 (corner), zeros where invalid; *n_features <- features.size() (corner: two per matched point). Outputs may be NULL.
+ *   Per point, in f32 with no contraction: point_sel = ((r0 x + r1 y) + r2 z) + t; the exact 5 nearest model points through the context's map index, built with
+ *   min_match_sq_dis = match_sq_dis_surf / _corner so that the 27-cell search is exact for the acceptance test sq_dis[4] < 2.0 / 5.0 (strict);
+ *   surf (hpp:203-243): colPivHouseholderQr().solve(-1) as the mapper path restates it, negative_OA_dot_norm = 1 / norm.norm(), normalize, a neighbour with
+ *     double(fabs(n . q + d)) > plane_dis rejects, coeffs (n, d) widened to f64;
+ *   corner (hpp:105-167): centroid and 3 x 3 covariance in f32 (center /= (1.0 * 5): Eigen converts the double to the vector's scalar, a division by 5.0f),
+ *     SelfAdjointEigenSolver<Matrix3f> as the mapper path restates it, eig[2] > line_eig_ratio * eig[1]; X1 = 0.1f * dir + center, X2 = -0.1f * dir + center (Eigen
+ *     promotes a double literal that multiplies a float expression to float); n = (X1 - X0) x (X2 - X0); w2 = n.normalized(); w1 = (w2 x (X2 - X1)).normalized();
+ *     ld_1 = n.norm() / (X1 - X2).norm(); ld_p1 = -(w1 . X0 - ld_1); ld_p2 = -(w2 . X0 - 0); TWO features per point, (w1, ld_p1) * 0.5 and (w2, ld_p2) * 0.5 in f64,
+ *     in that order.
+ *   CHOSEN: sums of three f32 terms (dot products, squared norms, the matrix-vector product) run left to right, as in every row of this library; Eigen's own
+ *     reduction order is not restated. CHOSEN: equal distances go to the lower index (the reference: FLANN's visiting order). CHOSEN: a model cloud with fewer than
+ *     five points matches nothing (the reference reads past the end of the search result there).
+ * mlh_loop_evaluate (test entry): matches both kinds at T_match, then evaluates every feature at `pose` [t, q(xyzw)] once: H (6 x 6 row-major J^T J), g (J^T r),
+ *   *cost = sum of rho / 2, counts[2] = residual blocks of surf / corner, as Ceres would hand them to the linear solver. Per block: a = w . (q p + t) + d, r = a w
+ *   (3 rows, sqrt_info_ = I), J = [W, -W R [p]x] with W = w w^T; Huber(huber_delta) on s = |r|^2 as Ceres corrects a block (rho'' <= 0: scaled by sqrt(rho')). The
+ *   kernel uses the block's scalar form (residual |w| a, row |w| j: the same J^T J, J^T r and s up to rounding). Tile partials summed in a fixed order: two runs give
+ *   the same bits.
+ * mlh_loop_register = performLocalRegistration(the four filtered clouds, T_ini) -> *result. Per outer iteration (cpp:117-198): para_pose from
+ *   Quaterniond(T.block<3,3>) (Eigen's matrix-to-quaternion conversion, not normalised) and T's translation; both matches at T.cast<float>(); the 0.2 rule (cpp:158:
+ *   1.0 * surf_num / surf_size <= min_match_ratio && 1.0 * corner_num / corner_size <= min_match_ratio breaks; corner_num counts features, two per matched point,
+ *   against points, so its ratio reaches 2; an empty data cloud of a kind gives NaN, which does not break); ceres::Solve as the project's Ceres-shaped
+ *   Levenberg-Marquardt (max_lm_iterations, no degeneracy handling, identity V_update) in the launch-per-iteration form: one evaluate launch and one one-workgroup
+ *   step launch per iteration, kernel boundaries the only synchronisation between workgroups; opti_cost = min(final_cost, opti_cost) from 1e7; T rebuilt from
+ *   q.toRotationMatrix() in f64. A break in outer iteration 0 returns T_ini bit for bit with cost 1e7; a break later keeps the earlier T and cost. With both data
+ *   clouds empty no break happens, the solve has no residual block, terminates at once with cost 0 and is accepted (what the restated solver does; Ceres reports
+ *   the same cost). accepted = opti_cost <= local_registration_threshold (cpp:202).
+ *   DEPARTURE: max_solver_time_in_seconds = 0.03 (cpp:188) is a wall-clock cut-off and is not applied.
+ *   Host waits: ONE per outer iteration entered (its two counts, its LM summary and pose arrive together: the solve is enqueued behind the matches without waiting
+ *   for the counts, and discarded when the 0.2 rule breaks), plus what staging the two model clouds costs when they changed since the last call (mlh_map_set x 2).
+ * mlh_loop_opts_default: 0.4 / 0.4, 20, 2, 5, 2000, 1.0, 2.0 / 5.0, 0.2, 3, 0.2. Options are validated by every call that takes them (NULL: the defaults):
+ *   MLH_ERR_INVALID outside finite leaves, thresholds and huber_delta > 0, 0 <= history_search_num <= 4096, 1 <= max_outer <= 8, 0 <= max_lm_iterations <= 200,
+ *   plane_dis >= 0, line_eig_ratio >= 0, and a NaN anywhere. */
+enum { MLH_LOOP_MODEL_SURF = 0, MLH_LOOP_MODEL_CORNER = 1, MLH_LOOP_DATA_SURF = 2, MLH_LOOP_DATA_CORNER = 3 };
+typedef struct mlh_loop_opts {
+    float leaf_surf, leaf_corner;            /* down_size_filter_{surf,corner}_map_ (pose_graph.cpp:33-34) */
+    int32_t history_search_num;              /* LOOP_HISTORY_SEARCH_NUM (the facade's window; the library itself does not read it) */
+    int32_t max_outer;                       /* cpp:117 */
+    int32_t max_lm_iterations;               /* options.max_num_iterations */
+    int32_t reserved;
+    double local_registration_threshold;     /* LOOP_LOCAL_REGISTRATION_THRESHOLD */
+    double huber_delta;                      /* ceres::HuberLoss(1) */
+    float match_sq_dis_surf, match_sq_dis_corner;
+    double plane_dis;
+    float line_eig_ratio;
+    int32_t reserved2;
+    double min_match_ratio;
+} mlh_loop_opts;
+typedef struct mlh_loop_outer_stat {
+    int32_t entered;                         /* the outer iteration matched */
+    int32_t ran;                             /* ... and solved (0: the 0.2 rule broke the loop here) */
+    int32_t surf_num, corner_num;            /* features.size() of the two matches */
+    int32_t lm_iterations, successful_steps;
+    int32_t termination;                     /* as mlh_iter_stat::termination */
+    int32_t reserved;
+    double initial_cost, final_cost;
+} mlh_loop_outer_stat;
+typedef struct mlh_loop_result {
+    double T_relative[16];                   /* row-major */
+    double para_pose[7];                     /* the last para_pose [t, q(xyzw)] (a break in outer iteration 0: that of T_ini) */
+    double opti_cost;
+    int32_t accepted;
+    int32_t n_outer;                         /* outer iterations entered */
+    mlh_loop_outer_stat outer[8];
+} mlh_loop_result;
+typedef struct mlh_loop_info {
+    int32_t n_pre[4], n_ds[4];
+    int64_t allocations;                     /* device allocations of the loop store since the context was made */
+    int64_t bytes_hbm;
+} mlh_loop_info;
+void mlh_loop_opts_default(mlh_loop_opts *o);
+int mlh_loop_build_clouds(mlh_ctx *ctx, const int32_t *data_keys, const float *data_T, int n_data, const int32_t *model_keys, const float *model_T, int n_model,
+                          const mlh_loop_opts *opts, int32_t *n_pre, int32_t *n_ds);
+int mlh_loop_set_clouds(mlh_ctx *ctx, const void *const *clouds, const int32_t *n, int stride_bytes, int intensity_offset_bytes, int mem);
+int mlh_loop_cloud(mlh_ctx *ctx, int which, int filtered, const void **device_points, int32_t *n);
+int mlh_loop_info_get(mlh_ctx *ctx, mlh_loop_info *out);
+int mlh_loop_match(mlh_ctx *ctx, int kind, const double *T, const mlh_loop_opts *opts, uint8_t *valid, double *coeffs, int32_t *n_features);
+int mlh_loop_evaluate(mlh_ctx *ctx, const double *T_match, const double *pose, const mlh_loop_opts *opts, double *H, double *g, double *cost, int32_t *counts);
+int mlh_loop_register(mlh_ctx *ctx, const double *T_ini, const mlh_loop_opts *opts, mlh_loop_result *result);
+
 /* (f1) cloudUCTAssociateToMap (lidar_mapper_keyframe.cpp:1116-1158): moves one keyframe's feature cloud into the map frame while
  * building the local map (extractSurroundingKeyFrames, cpp:254-354). Per point (intensity = LiDAR index n):
  *   with_ua: point_sel = pose_ext[n]^-1 * p; Sigma = evalPointUncertainty(point_sel, pose_global (+) pose_ext[n]) where the

@@ -162,6 +162,48 @@ def sc_opts(**kw) -> ScOpts:
     return o
 
 
+class LoopOpts(C.Structure):
+    """mlh_loop_opts"""
+    _fields_ = [("leaf_surf", C.c_float), ("leaf_corner", C.c_float), ("history_search_num", C.c_int32), ("max_outer", C.c_int32), ("max_lm_iterations", C.c_int32),
+                ("reserved", C.c_int32), ("local_registration_threshold", cd_), ("huber_delta", cd_), ("match_sq_dis_surf", C.c_float),
+                ("match_sq_dis_corner", C.c_float), ("plane_dis", cd_), ("line_eig_ratio", C.c_float), ("reserved2", C.c_int32), ("min_match_ratio", cd_)]
+
+
+class LoopOuterStat(C.Structure):
+    """mlh_loop_outer_stat"""
+    _fields_ = [("entered", C.c_int32), ("ran", C.c_int32), ("surf_num", C.c_int32), ("corner_num", C.c_int32), ("lm_iterations", C.c_int32),
+                ("successful_steps", C.c_int32), ("termination", C.c_int32), ("reserved", C.c_int32), ("initial_cost", cd_), ("final_cost", cd_)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
+
+
+class LoopResult(C.Structure):
+    """mlh_loop_result"""
+    _fields_ = [("T_relative", cd_ * 16), ("para_pose", cd_ * 7), ("opti_cost", cd_), ("accepted", C.c_int32), ("n_outer", C.c_int32), ("outer", LoopOuterStat * 8)]
+
+    def as_dict(self):
+        return dict(T_relative=np.array(self.T_relative).reshape(4, 4), para_pose=np.array(self.para_pose), opti_cost=self.opti_cost, accepted=bool(self.accepted),
+                    n_outer=self.n_outer, outer=[self.outer[i].as_dict() for i in range(self.n_outer)])
+
+
+class LoopInfo(C.Structure):
+    """mlh_loop_info"""
+    _fields_ = [("n_pre", C.c_int32 * 4), ("n_ds", C.c_int32 * 4), ("allocations", C.c_int64), ("bytes_hbm", C.c_int64)]
+
+
+def loop_opts(**kw) -> LoopOpts:
+    """mlh_loop_opts_default (pose_graph.cpp:33-34, loop_registration.cpp, feature_extract.hpp), then the given fields"""
+    o = LoopOpts()
+    load_library().mlh_loop_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+LOOP_MODEL_SURF, LOOP_MODEL_CORNER, LOOP_DATA_SURF, LOOP_DATA_CORNER = 0, 1, 2, 3
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -322,6 +364,15 @@ def load_library():
     lib.mlh_sc_distance.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(cd), C.POINTER(C.c_int32)]
     lib.mlh_sc_fetch.argtypes = [vp, C.c_int32, vp, vp, vp]
     lib.mlh_sc_info.argtypes = [vp, C.POINTER(ScStoreInfo)]
+    lib.mlh_loop_opts_default.argtypes = [C.POINTER(LoopOpts)]
+    lib.mlh_loop_opts_default.restype = None
+    lib.mlh_loop_build_clouds.argtypes = [vp, vp, vp, ci, vp, vp, ci, C.POINTER(LoopOpts), vp, vp]
+    lib.mlh_loop_set_clouds.argtypes = [vp, vp, vp, ci, ci, ci]
+    lib.mlh_loop_cloud.argtypes = [vp, ci, ci, C.POINTER(C.c_void_p), C.POINTER(C.c_int32)]
+    lib.mlh_loop_info_get.argtypes = [vp, C.POINTER(LoopInfo)]
+    lib.mlh_loop_match.argtypes = [vp, ci, vp, C.POINTER(LoopOpts), vp, vp, C.POINTER(C.c_int32)]
+    lib.mlh_loop_evaluate.argtypes = [vp, vp, vp, C.POINTER(LoopOpts), vp, vp, C.POINTER(cd), vp]
+    lib.mlh_loop_register.argtypes = [vp, vp, C.POINTER(LoopOpts), C.POINTER(LoopResult)]
     lib.mlh_pure_odom_add_matches.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, ci, ci]
     lib.mlh_pure_odom_add_matches_gf.argtypes = [vp, ci, vp, vp, vp, vp, ci, C.c_uint32, cf, cf, ci, ci, cf, C.c_uint64, vp, C.POINTER(C.c_int32)]
     lib.mlh_knn.argtypes = [vp, ci, vp, ci, ci, vp, vp]
@@ -371,6 +422,7 @@ EXPORTED_SYMBOLS = [
     "mlh_window_prior_set", "mlh_window_prior_get", "mlh_window_prior_clear", "mlh_window_prior_evaluate", "mlh_window_ext_prior_set", "mlh_window_marginalize",
     "mlh_calib_accumulate", "mlh_calib_add", "mlh_calib_use", "mlh_calib_clear", "mlh_calib_info", "mlh_calib_evaluate",
     "mlh_sc_opts_default", "mlh_sc_reset", "mlh_sc_add", "mlh_sc_add_keyframe", "mlh_sc_detect", "mlh_sc_candidates", "mlh_sc_distance", "mlh_sc_fetch", "mlh_sc_info",
+    "mlh_loop_opts_default", "mlh_loop_build_clouds", "mlh_loop_set_clouds", "mlh_loop_cloud", "mlh_loop_info_get", "mlh_loop_match", "mlh_loop_evaluate", "mlh_loop_register",
 ]
 
 
@@ -868,6 +920,71 @@ class Context:
         info = ScStoreInfo()
         self._ck(self.lib.mlh_sc_info(self.h, C.byref(info)))
         return info.as_dict()
+
+    # ---- loop-closure local registration (constructLocalMap + performLocalRegistration on the device)
+    def loop_build_clouds(self, data, model, opts: LoopOpts = None):
+        """constructLocalMap: data / model = lists of (keyframe key, 4 x 4 float32 matrix) -> (n_pre[4], n_ds[4]) in the order model surf, model corner, data surf,
+        data corner (mlh_loop_build_clouds)"""
+        def pack(lst):
+            keys = np.ascontiguousarray([k for k, _ in lst], np.int32)
+            mats = np.ascontiguousarray([np.asarray(m, np.float32).reshape(16) for _, m in lst], np.float32).reshape(-1, 16)
+            return keys, mats
+        dk, dm = pack(data)
+        mk, mm = pack(model)
+        n_pre, n_ds = np.zeros(4, np.int32), np.zeros(4, np.int32)
+        self._ck(self.lib.mlh_loop_build_clouds(self.h, _p(dk), _p(dm), len(dk), _p(mk), _p(mm), len(mk), C.byref(opts) if opts is not None else None, _p(n_pre), _p(n_ds)))
+        return n_pre, n_ds
+
+    def loop_set_clouds(self, model_surf, model_corner, data_surf, data_corner):
+        """the four filtered clouds given directly: (n, 4) float32 arrays {x, y, z, intensity} or torch CUDA tensors, all of one kind (mlh_loop_set_clouds)"""
+        src = [_src(c) for c in (model_surf, model_corner, data_surf, data_corner)]
+        mem = src[0][3]
+        assert all(s[3] == mem and s[1] == 16 for s in src), "four (n, 4) clouds of one memory kind"
+        ptrs = (C.c_void_p * 4)(*[(s[0] if s[2] > 0 else None) for s in src])
+        ns = (C.c_int32 * 4)(*[s[2] for s in src])
+        self._ck(self.lib.mlh_loop_set_clouds(self.h, ptrs, ns, 16, 12, mem))
+
+    def loop_cloud(self, which, filtered=True, fetch=True):
+        """cloud `which` (LOOP_MODEL_SURF ..), pre-filter or filtered: a DeviceCloud, or with fetch its (n, 4) float32 copy (mlh_loop_cloud)"""
+        ptr, n = C.c_void_p(), C.c_int32(0)
+        self._ck(self.lib.mlh_loop_cloud(self.h, int(which), int(bool(filtered)), C.byref(ptr), C.byref(n)))
+        if not fetch:
+            return DeviceCloud(ptr.value, n.value, 16)
+        out = np.zeros((n.value, 4), np.float32)
+        if n.value:
+            self.synchronize()
+            assert _hip_runtime().hipMemcpy(_p(out), ptr, out.nbytes, 2) == 0
+        return out
+
+    def loop_info(self) -> dict:
+        info = LoopInfo()
+        self._ck(self.lib.mlh_loop_info_get(self.h, C.byref(info)))
+        return dict(n_pre=list(info.n_pre), n_ds=list(info.n_ds), allocations=int(info.allocations), bytes_hbm=int(info.bytes_hbm))
+
+    def loop_match(self, kind, T, opts: LoopOpts = None):
+        """matchSurfFromMap / matchCornerFromMap of the filtered data cloud at T (4 x 4) -> (valid (m,), coeffs (m, 4) or (m, 2, 4), features.size()) (mlh_loop_match)"""
+        m = self.loop_info()["n_ds"][2 + kind]
+        T = np.ascontiguousarray(T, np.float64).reshape(16)
+        valid = np.zeros(m, np.uint8)
+        coeffs = np.zeros((m, 4) if kind == SURF else (m, 2, 4))
+        n = C.c_int32(0)
+        self._ck(self.lib.mlh_loop_match(self.h, int(kind), _p(T), C.byref(opts) if opts is not None else None, _p(valid), _p(coeffs), C.byref(n)))
+        return valid.astype(bool), coeffs, n.value
+
+    def loop_evaluate(self, T_match, pose, opts: LoopOpts = None) -> dict:
+        """both matches at T_match, then one evaluation of every residual block at pose [t, q(xyzw)] -> H, g, cost, counts (mlh_loop_evaluate)"""
+        T = np.ascontiguousarray(T_match, np.float64).reshape(16)
+        x = np.ascontiguousarray(pose, np.float64).reshape(7)
+        H, g, cost, counts = np.zeros((6, 6)), np.zeros(6), cd_(0.0), np.zeros(2, np.int32)
+        self._ck(self.lib.mlh_loop_evaluate(self.h, _p(T), _p(x), C.byref(opts) if opts is not None else None, _p(H), _p(g), C.byref(cost), _p(counts)))
+        return dict(H=H, g=g, cost=cost.value, counts=counts)
+
+    def loop_register(self, T_ini, opts: LoopOpts = None) -> dict:
+        """performLocalRegistration(the four filtered clouds, T_ini) (mlh_loop_register)"""
+        T = np.ascontiguousarray(T_ini, np.float64).reshape(16)
+        r = LoopResult()
+        self._ck(self.lib.mlh_loop_register(self.h, _p(T), C.byref(opts) if opts is not None else None, C.byref(r)))
+        return r.as_dict()
 
     def downsample_current_scan(self, kind, points4, leaf, ext_poses, ext_covs, cov_measurement, with_ua=True, trace_threshold=0.6, fetch=True):
         """downsampleCurrentScan for one kind; the result becomes the kind's feature set and, with fetch, is also returned (m, 11)

@@ -476,6 +476,22 @@ struct ScStore {
     long long points_host_decided = 0, points_skipped = 0;
 };
 
+// The loop closure's local registration (loopreg.hip; mloam_loop/src/pose_graph.cpp:364-419, loop_registration.cpp:104-211): the four clouds of constructLocalMap
+// (model surf / corner, data surf / corner: float4 {x, y, z, intensity}, back to back at off[]), pre-filter and filtered, and the per-slot features of the matches.
+struct LoopStore {
+    DevBuf pre, flt, tab;
+    int off[4] = {0, 0, 0, 0}, pre_n[4] = {0, 0, 0, 0}, flt_n[4] = {0, 0, 0, 0};
+    std::vector<unsigned char> htab;
+    DevBuf slots;                // double4 {w, d} per feature slot: one per surf data point, then two per corner data point
+    DevBuf valid;                // one byte per feature slot
+    DevBuf counts;               // ints: [0] surf, [1] corner features.size() of the last match
+    PinnedBuf h_pin;             // landing place of the read-backs
+    long long allocations = 0;
+    unsigned long long cloud_gen = 0;                   // bumped by every build / set
+    unsigned long long staged_gen = ~0ull, staged_epoch = ~0ull;   // the clouds and the stage_epoch the context's map indexes were staged from / left at
+    float staged_sq[2] = {0.f, 0.f};
+};
+
 constexpr int FUSE_BLOCKS = 64;           // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
 constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
@@ -631,6 +647,7 @@ struct mlh_ctx {
     mlh::MargPrior marg;     // the window's prior (marg.hip)
     mlh::CalibStore calib;   // the accumulated calibration features (calib.hip)
     mlh::ScStore sc;         // the Scan Context store (scancontext.hip)
+    mlh::LoopStore loop;     // the loop closure's local maps and matches (loopreg.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}

@@ -52,11 +52,6 @@ __device__ unsigned long long g_stage_clk_knn[4096 * 8];
 #include "knn_dev.hpp"
 #include "reduce_dev.hpp"
 namespace mlh {
-struct Lin {
-    double r;
-    double J[6];
-};
-
 __device__ __forceinline__ double sqrt_info_of(double trace)
 {
     double s = sqrt(1 / trace);
@@ -131,50 +126,6 @@ __device__ __forceinline__ Lin eval_factor(bool valid, int kind, const d3 &p, co
         else eval_edge(p, coef, w, q, t, R, L);
     }
     return L;
-}
-
-// accumulate one (possibly invalid) row and reduce the 29 sums over the workgroup -> partials[tile]
-// (mult: how many identical residual blocks the row stands for -- 1, except for the feature a selection picked repeatedly, select.hip: apply_keep_kernel)
-template <int MODE = 0>      // 0: plain stores, 1: agent-scope monotonic stores, 2: tagged words (reduce_dev.hpp: reduce_acc32)
-__device__ __forceinline__ void reduce_rows(bool valid, Lin L, double huber_delta, bool no_loss, int kind, double *lds_red /*4*32*/,
-                                            double *__restrict__ partial_out, int mult = 1, unsigned tag = 0u)
-{
-    double acc[32];
-    if (valid) {
-        double s = L.r * L.r, rho0 = s, rho1 = 1.0;
-        if (!no_loss && huber_delta > 0.0) {
-            const double b = huber_delta * huber_delta;
-            if (s > b) {
-                const double rr = sqrt(s);
-                rho0 = 2.0 * huber_delta * rr - b;
-                rho1 = fmax(DBL_MIN, huber_delta / rr);
-            }
-        }
-        const double sc = sqrt(rho1);
-        double r = L.r * sc;
-        double J[6];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) J[i] = L.J[i] * sc;
-        int q = 0;
-#pragma unroll
-        for (int i = 0; i < 6; ++i)
-#pragma unroll
-            for (int j = i; j < 6; ++j) acc[q++] = J[i] * J[j];
-#pragma unroll
-        for (int i = 0; i < 6; ++i) acc[NE_G + i] = J[i] * r;
-        acc[NE_COST] = 0.5 * rho0;
-        acc[NE_CNT] = 1.0;
-        if (mult > 1) {
-            const double k = double(mult);
-#pragma unroll
-            for (int i = 0; i < 29; ++i) acc[i] *= k;
-        }
-    } else {
-#pragma unroll
-        for (int i = 0; i < 29; ++i) acc[i] = 0.0;
-    }
-    acc[29] = acc[30] = acc[31] = 0.0;
-    reduce_acc32<MODE>(acc, kind, lds_red, partial_out, tag);
 }
 
 // feature_extract.hpp:696-715

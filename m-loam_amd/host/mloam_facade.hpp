@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "../../include/mloam_hip.h"
+#include "../csrc/loopreg_host.hpp"
 
 // Inside the reference tree (-DMLOAM_FACADE_CERES_BASES): the per-factor classes ARE ceres::SizedCostFunction<...> and PoseLocalParameterization IS a
 // ceres::LocalParameterization -- `new`ed by the caller, handed to problem.AddResidualBlock / AddParameterBlock and owned (deleted) by ceres::Problem, as the
@@ -2464,5 +2465,105 @@ inline std::pair<int, double> detectLoop(SCManager &sc_manager, const CloudT &fu
     const QueryResult qr = sc_manager.detectLoopClosureID(que_index);
     return std::make_pair(qr.match_index_, double(qr.yaw_diff_rad_));
 }
+
+// ------------------------------------------------------------------ loop-closure local registration (mloam_loop: pose_graph.cpp:364-474, loop_registration.cpp:104-211)
+// PoseGraph::checkGeometricConsistency's two device steps with the reference's names. LoopLocalMap::constructLocalMap chooses the keyframes as cpp:374-410 do,
+// forms T_ini_map_kf / T_relative in f64 and hands the lists to mlh_loop_build_clouds: the four clouds are made and stay in HBM (fetchCloud serves a caller that runs
+// FGR on the host in between). LoopRegistration::performLocalRegistration has the reference's signature shape (four clouds + T_ini -> (accepted, T_relative)) and an
+// overload that registers the clouds constructLocalMap left on the device. 4 x 4 matrices are row-major arrays of 16. What is reproduced, chosen and departed from:
+// include/mloam_hip.h (f12); the host arithmetic: csrc/loopreg_host.hpp.
+typedef std::array<double, 16> Mat4;
+
+class LoopLocalMap {
+public:
+    // pose_w_.T_ of a keyframe and its key in the context's keyframe store
+    struct Keyframe { int key; Mat4 T; };
+    struct DeviceCloud { const void *points = nullptr; int32_t n = 0; };      // float4 {x, y, z, intensity} records in HBM: stride 16, intensity offset 12
+    explicit LoopLocalMap(Device &dev) : dev_(dev) { mlh_loop_opts_default(&opts_); }
+    mlh_loop_opts &options() { return opts_; }
+    // poses_by_index: every keyframe getKeyFrame(index) would find; an absent index is a missing keyframe (cpp:379, 403). cur_kf is keyframe que_index, old_kf
+    // keyframe match_index (cpp:397): both must be present.
+    void constructLocalMap(int que_index, int match_index, const Mat4 &pose_ini, const std::map<int, Keyframe> &poses_by_index)
+    {
+        const auto has = [&](int i) { return poses_by_index.count(i) != 0; };
+        if (!has(que_index) || !has(match_index)) throw Error("LoopLocalMap::constructLocalMap: the query and the matched keyframe must be in poses_by_index");
+        data_index_ = mlh::loop_data_window(que_index, opts_.history_search_num, has);
+        model_index_ = mlh::loop_model_window(que_index, match_index, opts_.history_search_num, has);
+        const Mat4 &T_cur = poses_by_index.at(que_index).T, &T_old = poses_by_index.at(match_index).T;
+        std::vector<int32_t> dk, mk;
+        std::vector<float> dT(16 * data_index_.size()), mT(16 * model_index_.size());
+        for (size_t e = 0; e < data_index_.size(); ++e) {
+            const Keyframe &kf = poses_by_index.at(data_index_[e]);
+            dk.push_back(kf.key);
+            mlh::loop_data_transform(pose_ini.data(), T_cur.data(), kf.T.data(), dT.data() + 16 * e);
+        }
+        for (size_t e = 0; e < model_index_.size(); ++e) {
+            const Keyframe &kf = poses_by_index.at(model_index_[e]);
+            mk.push_back(kf.key);
+            mlh::loop_model_transform(T_old.data(), kf.T.data(), mT.data() + 16 * e);
+        }
+        dev_.check(mlh_loop_build_clouds(dev_.ctx(), dk.data(), dT.data(), int(dk.size()), mk.data(), mT.data(), int(mk.size()), &opts_, n_pre_, n_ds_));
+    }
+    const std::vector<int> &dataKeyframes() const { return data_index_; }      // the keyframe indices of the last call, in list order
+    const std::vector<int> &modelKeyframes() const { return model_index_; }
+    size_t size(int which, bool filtered = true) const { return size_t(filtered ? n_ds_[which] : n_pre_[which]); }
+    // laser_cloud_surf_from_map_ds_ (MLH_LOOP_MODEL_SURF), laser_cloud_surf_ds_ (MLH_LOOP_DATA_SURF), ...; valid until the next constructLocalMap / setClouds
+    DeviceCloud cloud(int which, bool filtered = true) const
+    {
+        DeviceCloud d;
+        dev_.check(mlh_loop_cloud(dev_.ctx(), which, filtered ? 1 : 0, &d.points, &d.n));
+        return d;
+    }
+    // ... copied into a host cloud, for a caller that runs FGR on the host (`copy_to_host(dst, src, bytes)`: the caller's device-to-host copy -- this header stays
+    // free of the HIP runtime)
+    template <class CopyToHost> void fetchCloud(int which, PointICloud &out, CopyToHost copy_to_host, bool filtered = true) const
+    {
+        const DeviceCloud d = cloud(which, filtered);
+        out.points.clear();
+        if (d.n <= 0) return;
+        dev_.check(mlh_synchronize(dev_.ctx()));
+        std::vector<float> rec(size_t(d.n) * 4);
+        copy_to_host(rec.data(), d.points, rec.size() * sizeof(float));
+        out.points.resize(size_t(d.n));
+        for (size_t i = 0; i < size_t(d.n); ++i) { PointI &p = out.points[i]; p.x = rec[4 * i]; p.y = rec[4 * i + 1]; p.z = rec[4 * i + 2]; p.intensity = rec[4 * i + 3]; }
+    }
+private:
+    Device &dev_;
+    mlh_loop_opts opts_{};
+    std::vector<int> data_index_, model_index_;
+    int32_t n_pre_[4] = {0, 0, 0, 0}, n_ds_[4] = {0, 0, 0, 0};
+};
+
+class LoopRegistration {
+public:
+    explicit LoopRegistration(Device &dev) : dev_(dev) { mlh_loop_opts_default(&opts_); }
+    mlh_loop_opts &options() { return opts_; }
+    // performLocalRegistration(laser_cloud_surf_from_map, laser_cloud_corner_from_map, laser_cloud_surf, laser_cloud_corner, T_ini) (loop_registration.cpp:104-108)
+    template <class CloudPtr>
+    std::pair<bool, Mat4> performLocalRegistration(const CloudPtr &laser_cloud_surf_from_map, const CloudPtr &laser_cloud_corner_from_map, const CloudPtr &laser_cloud_surf,
+                                                   const CloudPtr &laser_cloud_corner, const Mat4 &T_ini)
+    {
+        const auto &ms = detail::deref(laser_cloud_surf_from_map, 0), &mc = detail::deref(laser_cloud_corner_from_map, 0);
+        const auto &ds = detail::deref(laser_cloud_surf, 0), &dc = detail::deref(laser_cloud_corner, 0);
+        const void *clouds[4] = {ptr_of(ms), ptr_of(mc), ptr_of(ds), ptr_of(dc)};
+        const int32_t n[4] = {int32_t(ms.points.size()), int32_t(mc.points.size()), int32_t(ds.points.size()), int32_t(dc.points.size())};
+        dev_.check(mlh_loop_set_clouds(dev_.ctx(), clouds, n, int(sizeof(PointI)), int(offsetof(PointI, intensity)), MLH_MEM_HOST));
+        return performLocalRegistration(T_ini);
+    }
+    // the same on the clouds LoopLocalMap::constructLocalMap (or mlh_loop_set_clouds) left on this context
+    std::pair<bool, Mat4> performLocalRegistration(const Mat4 &T_ini)
+    {
+        dev_.check(mlh_loop_register(dev_.ctx(), T_ini.data(), &opts_, &last_));
+        Mat4 T;
+        for (int i = 0; i < 16; ++i) T[size_t(i)] = last_.T_relative[i];
+        return std::make_pair(last_.accepted != 0, T);
+    }
+    const mlh_loop_result &lastResult() const { return last_; }      // opti_cost, para_pose and the per-outer-iteration records of the last call
+private:
+    template <class CloudT> static const void *ptr_of(const CloudT &c) { return c.points.empty() ? nullptr : static_cast<const void *>(c.points.data()); }
+    Device &dev_;
+    mlh_loop_opts opts_{};
+    mlh_loop_result last_{};
+};
 
 }  // namespace mloam_hip
