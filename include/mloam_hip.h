@@ -413,7 +413,8 @@ int mlh_calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *resi
 /* ---------------------------------------------------------------- (f11) Scan Context place recognition, on the device
  * The front of the loop-closure process: SCManager (mloam_loop/src/scan_context.cpp:155-323) as PoseGraph::detectLoop drives it (mloam_loop/src/pose_graph.cpp:
  * 281-328). A context keeps one store in HBM: per entry the descriptor (f32, num_ring x num_sector, column-major as Eigen stores it), the ring key (f32), the sector
- * key and the column norms (f64), and on the host the optional position. FGR, the pose graph and the geometric verification are not part of this library.
+ * key and the column norms (f64), and on the host the optional position. The geometric verification is sections (f12) and (f13); the pose graph is not part of
+ * this library.
  * Reproduced, with the lines restated:
  *   descriptor (cpp:155-186): z' = float(double(z) + lidar_height); range = sqrt(x x + y y) in f32; dropped only if range > max_radius (a point at exactly
  *     max_radius stays); ring = max(min(R, int(ceil(double(range) / max_radius * R))), 1); angle = xy2theta (cpp:38-51) as written, signed zeros and infinities
@@ -504,8 +505,8 @@ int mlh_sc_info(mlh_ctx *ctx, mlh_sc_store_info *out);
  * The geometric verification that turns a Scan Context candidate into a loop edge: PoseGraph::constructLocalMap (mloam_loop/src/pose_graph.cpp:364-419) and
  * LoopRegistration::performLocalRegistration (mloam_loop/src/loop_registration.cpp:104-211) with the loop package's own match functions (mloam_loop/include/
  * mloam_loop/utility/feature_extract.hpp:28-43, 77-247) and factor (mloam_loop/include/mloam_loop/factor/lidar_map_plane_norm_factor.hpp:47-87). FGR / FPFH
- * (performGlobalRegistration), checkTemporalConsistency, the pose graph and its optimisation are not part of this library: a caller keeps FGR on the host (the
- * two surf clouds are fetched with mlh_loop_cloud) or starts from the Scan Context yaw. A loop process uses a context of its own: mlh_loop_match, mlh_loop_evaluate
+ * (performGlobalRegistration) is section (f13); checkTemporalConsistency, the pose graph and its optimisation are not part of this library. T_ini comes from
+ * mlh_fgr_register on the same clouds, or from the Scan Context yaw. A loop process uses a context of its own: mlh_loop_match, mlh_loop_evaluate
  * and mlh_loop_register OVERWRITE the context's two map indexes (mlh_map_set) and its solver state; they return MLH_ERR_STATE while a solve submitted with
  * mlh_*_begin is uncollected and MLH_ERR_UNSUPPORTED under a communicator. DEPARTURE from the plan of staging the data clouds as the context's feature sets: the
  * kernels read them where mlh_loop_build_clouds / mlh_loop_set_clouds left them, so the feature sets are NOT touched.
@@ -604,6 +605,112 @@ int mlh_loop_info_get(mlh_ctx *ctx, mlh_loop_info *out);
 int mlh_loop_match(mlh_ctx *ctx, int kind, const double *T, const mlh_loop_opts *opts, uint8_t *valid, double *coeffs, int32_t *n_features);
 int mlh_loop_evaluate(mlh_ctx *ctx, const double *T_match, const double *pose, const mlh_loop_opts *opts, double *H, double *g, double *cost, int32_t *counts);
 int mlh_loop_register(mlh_ctx *ctx, const double *T_ini, const mlh_loop_opts *opts, mlh_loop_result *result);
+
+/* ---------------------------------------------------------------- (f13) FPFH + Fast Global Registration for the loop closure, on the device
+ * The step between (f11) and (f12): LoopRegistration::performGlobalRegistration (mloam_loop/src/loop_registration.cpp:18-101) -- pcl::NormalEstimation and
+ * pcl::FPFHEstimationOMP over the two filtered surf clouds (cpp:46-66), then fgr::CApp (mloam_loop/ThirdParty/FastGlobalRegistration/app.cpp): NormalizePoints
+ * (app.cpp:324-390), AdvancedMatching (113-320), OptimizePairwise (392-505), GetOutputTrans (519-534). Cloud 0 is the MODEL surf cloud (laser_map, pointcloud_[0]),
+ * cloud 1 the DATA surf cloud (laser_cloud); T maps data into the model frame. The clouds are read where mlh_loop_build_clouds / mlh_loop_set_clouds left them
+ * (`which` = MLH_LOOP_MODEL_SURF or MLH_LOOP_DATA_SURF everywhere below); no cloud crosses the bus: what leaves HBM is the mutual pairs' records (two indices and
+ * two normalised points each) and a few scalars. On the device: normals, SPFH, FPFH, NormalizePoints, the 33-dimensional matching and the gather; on the host, in
+ * csrc/fgr_host.hpp: the tuple test and OptimizePairwise (bounded by 3 tuple_max_cnt correspondences) and GetOutputTrans. The per-pair, per-bin, eigen33 and distance
+ * arithmetic lives once, in fgr_host.hpp, for the kernels, the host tail and the tests' restatement. PCL and FLANN are not available to this project: what
+ * fgr_host.hpp restates of PCL 1.8.0 (computeMeanAndCovarianceMatrix, eigen33 / computeRoots, solvePlaneParameters, flipNormalTowardsViewpoint, computePairFeatures,
+ * computePointSPFHSignature, weightPointSPFHSignature) and of FLANN (the L2 functor, RadiusResultSet's strict comparison) is restated from memory of those
+ * sources and could not be checked against them; the header's comment lists each.
+ * Every entry: MLH_ERR_STATE while a solve submitted with mlh_*_begin is uncollected, MLH_ERR_UNSUPPORTED under a communicator; options validated by every call
+ * (NULL: the defaults), MLH_ERR_INVALID on NaN or outside: finite radii > 0 and <= 1e3, div_factor finite and > 1, use_absolute_scale 0 / 1, max_corr_dist finite
+ * and > 0, 0 <= iteration_number <= 10000, 0 < tuple_scale <= 1, 1 <= tuple_max_cnt <= 1000000, a threshold that is not NaN. No device allocation once the buffers
+ * have grown (mlh_fgr_info_t::allocations).
+ * The self-index: per cloud the grid build of the map indexes (grid.hip) over a MapGrid of the store's own -- the context's two map indexes are NOT touched -- at cell
+ *   edge max(normal_radius, fpfh_radius) (x 1.001), so that the 27-cell walk is an exact radius search for both radii; one host wait (the cloud's bounds).
+ *   DEPARTURE: the order of the points inside a cell is then fixed (ascending original index, one more launch) because the grid build's is not, and every sum below
+ *   runs in that order: two runs give the same bits. CHOSEN: a neighbour counts when its f32 squared distance (dx dx + dy dy) + dz dz is strictly < r * r (the f32
+ *   product), FLANN's RadiusResultSet; the query point itself is a neighbour, as in PCL. A cloud with a non-finite coordinate: MLH_ERR_INVALID (PCL skips such points).
+ * mlh_fgr_features(which) = NormalEstimation::compute (radius search, viewpoint (0, 0, 0)) + FPFHEstimationOMP::compute for cloud `which`. An empty cloud gives zero
+ *   features and success.
+ *   normals: the nine sums of computeMeanAndCovarianceMatrix in f32, un-centred (PCL 1.8.0), 16 lanes per point, each lane its candidates in walk order, then a
+ *     fixed butterfly (DEPARTURE: PCL sums in ascending distance order); fewer than 3 neighbours: NaN normal and curvature; eigen33 (scaled by the largest absolute
+ *     coefficient, closed-form roots, eigenvector = the largest of the three row cross products) -> the smallest eigenvalue and its vector; curvature =
+ *     |lambda / trace| (0 when the trace is 0); flipNormalTowardsViewpoint.
+ *   SPFH: per point over its fpfh_radius neighbours but itself (by index), computePairFeatures in f32 (swap decided on acos(fabs(angle)); f3 the cosine of the
+ *     source side; v = dp x n1 normalised, w = n1 x v, f2 = v . n2, f1 = atan2f(w . n2, n1 . n2); zero distance or zero |v| skips the pair); bins
+ *     floor(11 ((f1 + pi) d_pi)) and floor(11 ((f + 1) 0.5)) in f64 on the f32 feature as PCL writes them, clamped to [0, 10]. Every pair adds the same hist_incr =
+ *     100.f / (k - 1), so the device keeps INTEGER counts and the f32 bin value is the result of `count` sequential f32 additions of hist_incr.
+ *     CHOSEN (NaN): a pair with a NaN normal on either side gives NaN features; x86 converts floor(NaN) to INT_MIN, which the clamp sends to bin 0 -- restated: a NaN
+ *     feature counts in bin 0 of its block. So a non-finite normal anywhere in the support leaves every histogram FINITE, with bin 0 of the three blocks over-counted;
+ *     FPFH has no non-finite output for finite clouds (a point whose only neighbour is itself has all 33 bins zero).
+ *   FPFH: weightPointSPFHSignature: neighbours with squared distance 0 skipped, weight 1.f / d2, the 33 sums in neighbour (walk) order, the three block sums in PCL's
+ *     interleaved order, each block scaled by float(100.0 / sum) when its sum is non-zero. One wavefront per point, one lane per bin.
+ * mlh_fgr_fetch(which, what, out, k_out): a test and diagnosis entry. MLH_FGR_NORMALS: 4 f32 per point (nx, ny, nz, curvature); MLH_FGR_SPFH: int32 [n x 33] counts,
+ *   and k_out (may be NULL) <- the per-point neighbour counts (the point itself included); MLH_FGR_FPFH: 33 f32 per point. MLH_ERR_STATE when that stage has not been
+ *   computed (or set) for the staged cloud.
+ * mlh_fgr_set_normals / mlh_fgr_set_spfh / mlh_fgr_set_features (test entries; host arrays of the cloud's size): override one stage's output so that the next can be
+ *   run on exactly known inputs: mlh_fgr_spfh(which) runs SPFH + FPFH from the normals in place, mlh_fgr_fpfh(which) FPFH from the counts in place.
+ *   mlh_fgr_set_features(which, n, feat) also lets a caller bring its own descriptors: n must be the cloud's size, or the cloud may be empty / unset, in which case
+ *   the features alone are staged for mlh_fgr_match (n rows; mlh_fgr_register needs the points).
+ * mlh_fgr_match(pairs_out, capacity, n_pairs) = AdvancedMatching up to and including the cross check (app.cpp:113-235) on the two feature sets. The i_to_j cache
+ *   and the Mi / Mj walk reduce to the set of mutual nearest neighbours; the larger cloud is i (app.cpp:121-127: cloud 1 only when strictly larger); pairs come in
+ *   ascending i and are un-swapped (app.cpp:309-316): pairs_out[2 e] = the model index, [2 e + 1] = the data index; at most `capacity` pairs are written, *n_pairs <-
+ *   their number (min(n0, n1) always suffices). Feature distance in f32 as FLANN's L2 functor: four squared differences summed left to right, then added to the
+ *   running sum; the 33rd term alone; no contraction; the exact arg-min (a tiled brute-force kernel; the fixed order rules out MFMA). CHOSEN: equal distances go to
+ *   the lower index. CHOSEN: a row with a non-finite entry is never a nearest neighbour and matches nothing (the reference hands NaN to FLANN). One empty side:
+ *   no pairs.
+ * mlh_fgr_register = performGlobalRegistration end to end: features for both clouds unless still valid for the staged clouds and radii; NormalizePoints (DEPARTURE:
+ *   mean in a fixed tree order -- 256 strided sequential chains, then a tree -- where the reference sums sequentially; the shift and the divide in f32 as written);
+ *   match; the matched pairs' normalised points gathered into a pinned record; then the host tail: the tuple test (app.cpp:242-307; DEPARTURE: srand(time(NULL))
+ *   is not reproducible: opts->seed feeds the generator of fgr_host.hpp, rand() % ncorr becomes next() % ncorr), OptimizePairwise(true) (f64 JTJ / JTr in
+ *   correspondence order, f32 points and delta; CHOSEN: a plain Cholesky for llt(), the Z Y X product through quaternions as Eigen forms it) and GetOutputTrans.
+ *   Fewer than 10 correspondences: OptimizePairwise returns at once (app.cpp:412), T = GetOutputTrans of the identity (rotation I, translation Means[0] - Means[1]);
+ *   the reference then compares final_cost_normalize_, a member no constructor initialises, against the threshold: indeterminate. CHOSEN: the cost is NaN and
+ *   accepted = 0. Otherwise accepted = cost <= global_registration_threshold (cpp:92). CHOSEN: an empty cloud has mean 0 (the reference divides 0 by 0, then reads
+ *   data[0] of an empty feature set): no pairs, T = GetOutputTrans of the identity. Host waits: per cloud whose features are computed 1 (the bounds); 1 for the
+ *   normalisation scalars, the pair count and the records.
+ * mlh_fgr_info: sizes, validity, allocations, launches of the last f13 call, bytes held. */
+enum { MLH_FGR_NORMALS = 0, MLH_FGR_SPFH = 1, MLH_FGR_FPFH = 2 };
+typedef struct mlh_fgr_opts {
+    float normal_radius, fpfh_radius;        /* NORMAL_RADIUS, FPFH_RADIUS */
+    double div_factor;                       /* DIV_FACTOR */
+    int32_t use_absolute_scale;              /* USE_ABSOLUTE_SCALE */
+    int32_t iteration_number;                /* ITERATION_NUMBER */
+    double max_corr_dist;                    /* MAX_CORR_DIST */
+    float tuple_scale;                       /* TUPLE_SCALE */
+    int32_t tuple_max_cnt;                   /* TUPLE_MAX_CNT */
+    double global_registration_threshold;    /* LOOP_GLOBAL_REGISTRATION_THRESHOLD */
+    uint64_t seed;                           /* the tuple test's generator (default 1) */
+} mlh_fgr_opts;
+typedef struct mlh_fgr_result {
+    double T_relative[16];                   /* row-major: GetOutputTrans().cast<double>() */
+    double final_cost_normalize;             /* NaN with fewer than 10 correspondences */
+    double final_cost;
+    double global_scale, start_scale;        /* GlobalScale, StartScale */
+    double means[6];                         /* Means[0], Means[1] */
+    int32_t accepted;
+    int32_t swapped;                         /* the data cloud was i */
+    int32_t n_mutual, n_tuples, n_corres;    /* after the cross check; tuples accepted; correspondences = 3 n_tuples */
+    int32_t n_trials;                        /* tuple-test trials run */
+    int32_t host_waits;
+    int32_t reserved;
+} mlh_fgr_result;
+typedef struct mlh_fgr_info_t {
+    int32_t n[2];                            /* cloud sizes the feature buffers were last sized for (model, data) */
+    int32_t have_normals[2], have_spfh[2], have_features[2];
+    int32_t launches;                        /* kernel launches of the last f13 call (the grid build's own five to seven are not counted) */
+    int32_t host_waits;                      /* ... and its host waits */
+    int64_t allocations;                     /* device allocations of the FGR store since the context was made */
+    int64_t bytes_hbm;
+} mlh_fgr_info_t;
+void mlh_fgr_opts_default(mlh_fgr_opts *o);  /* config_loop_realvehicle.yaml: 1.0, 1.5, 1.4, 1, 0.025, 64, 0.95, 1000, 2.0; seed 1 */
+int mlh_fgr_features(mlh_ctx *ctx, int which, const mlh_fgr_opts *opts);
+int mlh_fgr_spfh(mlh_ctx *ctx, int which, const mlh_fgr_opts *opts);
+int mlh_fgr_fpfh(mlh_ctx *ctx, int which, const mlh_fgr_opts *opts);
+int mlh_fgr_fetch(mlh_ctx *ctx, int which, int what, void *out, int32_t *k_out);
+int mlh_fgr_set_normals(mlh_ctx *ctx, int which, int32_t n, const float *normals4);
+int mlh_fgr_set_spfh(mlh_ctx *ctx, int which, int32_t n, const int32_t *counts, const int32_t *k);
+int mlh_fgr_set_features(mlh_ctx *ctx, int which, int32_t n, const float *features);
+int mlh_fgr_match(mlh_ctx *ctx, const mlh_fgr_opts *opts, int32_t *pairs_out, int32_t capacity, int32_t *n_pairs);
+int mlh_fgr_register(mlh_ctx *ctx, const mlh_fgr_opts *opts, mlh_fgr_result *result);
+int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
 
 /* (f1) cloudUCTAssociateToMap (lidar_mapper_keyframe.cpp:1116-1158): moves one keyframe's feature cloud into the map frame while
  * building the local map (extractSurroundingKeyFrames, cpp:254-354). Per point (intensity = LiDAR index n):

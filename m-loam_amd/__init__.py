@@ -204,6 +204,42 @@ def loop_opts(**kw) -> LoopOpts:
 LOOP_MODEL_SURF, LOOP_MODEL_CORNER, LOOP_DATA_SURF, LOOP_DATA_CORNER = 0, 1, 2, 3
 
 
+class FgrOpts(C.Structure):
+    """mlh_fgr_opts"""
+    _fields_ = [("normal_radius", C.c_float), ("fpfh_radius", C.c_float), ("div_factor", cd_), ("use_absolute_scale", C.c_int32), ("iteration_number", C.c_int32),
+                ("max_corr_dist", cd_), ("tuple_scale", C.c_float), ("tuple_max_cnt", C.c_int32), ("global_registration_threshold", cd_), ("seed", C.c_uint64)]
+
+
+class FgrResult(C.Structure):
+    """mlh_fgr_result"""
+    _fields_ = [("T_relative", cd_ * 16), ("final_cost_normalize", cd_), ("final_cost", cd_), ("global_scale", cd_), ("start_scale", cd_), ("means", cd_ * 6),
+                ("accepted", C.c_int32), ("swapped", C.c_int32), ("n_mutual", C.c_int32), ("n_tuples", C.c_int32), ("n_corres", C.c_int32), ("n_trials", C.c_int32),
+                ("host_waits", C.c_int32), ("reserved", C.c_int32)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("reserved", "T_relative", "means", "accepted", "swapped")}
+        d.update(T_relative=np.array(self.T_relative).reshape(4, 4), means=np.array(self.means).reshape(2, 3), accepted=bool(self.accepted), swapped=bool(self.swapped))
+        return d
+
+
+class FgrInfo(C.Structure):
+    """mlh_fgr_info_t"""
+    _fields_ = [("n", C.c_int32 * 2), ("have_normals", C.c_int32 * 2), ("have_spfh", C.c_int32 * 2), ("have_features", C.c_int32 * 2), ("launches", C.c_int32),
+                ("host_waits", C.c_int32), ("allocations", C.c_int64), ("bytes_hbm", C.c_int64)]
+
+
+def fgr_opts(**kw) -> FgrOpts:
+    """mlh_fgr_opts_default (config_loop_realvehicle.yaml; seed 1), then the given fields"""
+    o = FgrOpts()
+    load_library().mlh_fgr_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
+FGR_NORMALS, FGR_SPFH, FGR_FPFH = 0, 1, 2
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -373,6 +409,17 @@ def load_library():
     lib.mlh_loop_match.argtypes = [vp, ci, vp, C.POINTER(LoopOpts), vp, vp, C.POINTER(C.c_int32)]
     lib.mlh_loop_evaluate.argtypes = [vp, vp, vp, C.POINTER(LoopOpts), vp, vp, C.POINTER(cd), vp]
     lib.mlh_loop_register.argtypes = [vp, vp, C.POINTER(LoopOpts), C.POINTER(LoopResult)]
+    lib.mlh_fgr_opts_default.argtypes = [C.POINTER(FgrOpts)]
+    lib.mlh_fgr_opts_default.restype = None
+    for fn in (lib.mlh_fgr_features, lib.mlh_fgr_spfh, lib.mlh_fgr_fpfh):
+        fn.argtypes = [vp, ci, C.POINTER(FgrOpts)]
+    lib.mlh_fgr_fetch.argtypes = [vp, ci, ci, vp, vp]
+    lib.mlh_fgr_set_normals.argtypes = [vp, ci, C.c_int32, vp]
+    lib.mlh_fgr_set_spfh.argtypes = [vp, ci, C.c_int32, vp, vp]
+    lib.mlh_fgr_set_features.argtypes = [vp, ci, C.c_int32, vp]
+    lib.mlh_fgr_match.argtypes = [vp, C.POINTER(FgrOpts), vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.mlh_fgr_register.argtypes = [vp, C.POINTER(FgrOpts), C.POINTER(FgrResult)]
+    lib.mlh_fgr_info.argtypes = [vp, C.POINTER(FgrInfo)]
     lib.mlh_pure_odom_add_matches.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, ci, ci]
     lib.mlh_pure_odom_add_matches_gf.argtypes = [vp, ci, vp, vp, vp, vp, ci, C.c_uint32, cf, cf, ci, ci, cf, C.c_uint64, vp, C.POINTER(C.c_int32)]
     lib.mlh_knn.argtypes = [vp, ci, vp, ci, ci, vp, vp]
@@ -423,6 +470,8 @@ EXPORTED_SYMBOLS = [
     "mlh_calib_accumulate", "mlh_calib_add", "mlh_calib_use", "mlh_calib_clear", "mlh_calib_info", "mlh_calib_evaluate",
     "mlh_sc_opts_default", "mlh_sc_reset", "mlh_sc_add", "mlh_sc_add_keyframe", "mlh_sc_detect", "mlh_sc_candidates", "mlh_sc_distance", "mlh_sc_fetch", "mlh_sc_info",
     "mlh_loop_opts_default", "mlh_loop_build_clouds", "mlh_loop_set_clouds", "mlh_loop_cloud", "mlh_loop_info_get", "mlh_loop_match", "mlh_loop_evaluate", "mlh_loop_register",
+    "mlh_fgr_opts_default", "mlh_fgr_features", "mlh_fgr_spfh", "mlh_fgr_fpfh", "mlh_fgr_fetch", "mlh_fgr_set_normals", "mlh_fgr_set_spfh", "mlh_fgr_set_features",
+    "mlh_fgr_match", "mlh_fgr_register", "mlh_fgr_info",
 ]
 
 
@@ -984,6 +1033,56 @@ class Context:
         T = np.ascontiguousarray(T_ini, np.float64).reshape(16)
         r = LoopResult()
         self._ck(self.lib.mlh_loop_register(self.h, _p(T), C.byref(opts) if opts is not None else None, C.byref(r)))
+        return r.as_dict()
+
+    # ---- FPFH + Fast Global Registration over the loop store's two surf clouds (performGlobalRegistration on the device)
+    def fgr_info(self) -> dict:
+        info = FgrInfo()
+        self._ck(self.lib.mlh_fgr_info(self.h, C.byref(info)))
+        return dict(n=list(info.n), have_normals=list(info.have_normals), have_spfh=list(info.have_spfh), have_features=list(info.have_features),
+                    launches=info.launches, host_waits=info.host_waits, allocations=int(info.allocations), bytes_hbm=int(info.bytes_hbm))
+
+    def fgr_features(self, which, opts: FgrOpts = None, first=FGR_NORMALS):
+        """normals + SPFH + FPFH of cloud `which` (LOOP_MODEL_SURF / LOOP_DATA_SURF); first = FGR_SPFH / FGR_FPFH: from the normals / the SPFH counts in place
+        (mlh_fgr_features, mlh_fgr_spfh, mlh_fgr_fpfh)"""
+        fn = (self.lib.mlh_fgr_features, self.lib.mlh_fgr_spfh, self.lib.mlh_fgr_fpfh)[first]
+        self._ck(fn(self.h, int(which), C.byref(opts) if opts is not None else None))
+
+    def fgr_fetch(self, which, what):
+        """FGR_NORMALS -> (n, 4) float32; FGR_SPFH -> ((n, 33) int32 counts, (n,) int32 neighbour counts); FGR_FPFH -> (n, 33) float32 (mlh_fgr_fetch)"""
+        n = self.fgr_info()["n"][which >> 1] if what == FGR_FPFH else self.loop_info()["n_ds"][which]
+        if what == FGR_SPFH:
+            out, k = np.zeros((n, 33), np.int32), np.zeros(n, np.int32)
+            self._ck(self.lib.mlh_fgr_fetch(self.h, int(which), what, _p(out), _p(k)))
+            return out, k
+        out = np.zeros((n, 4 if what == FGR_NORMALS else 33), np.float32)
+        self._ck(self.lib.mlh_fgr_fetch(self.h, int(which), what, _p(out), None))
+        return out
+
+    def fgr_set_normals(self, which, normals4):
+        a = np.ascontiguousarray(normals4, np.float32).reshape(-1, 4)
+        self._ck(self.lib.mlh_fgr_set_normals(self.h, int(which), len(a), _p(a)))
+
+    def fgr_set_spfh(self, which, counts, k):
+        a, b = np.ascontiguousarray(counts, np.int32).reshape(-1, 33), np.ascontiguousarray(k, np.int32).reshape(-1)
+        assert len(a) == len(b)
+        self._ck(self.lib.mlh_fgr_set_spfh(self.h, int(which), len(a), _p(a), _p(b)))
+
+    def fgr_set_features(self, which, features):
+        a = np.ascontiguousarray(features, np.float32).reshape(-1, 33)
+        self._ck(self.lib.mlh_fgr_set_features(self.h, int(which), len(a), _p(a)))
+
+    def fgr_match(self, opts: FgrOpts = None):
+        """AdvancedMatching up to the cross check on the two feature sets -> (m, 2) int32 (model index, data index) in ascending i (mlh_fgr_match)"""
+        cap = max(1, min(self.fgr_info()["n"]))
+        out, n = np.zeros((cap, 2), np.int32), C.c_int32(0)
+        self._ck(self.lib.mlh_fgr_match(self.h, C.byref(opts) if opts is not None else None, _p(out), cap, C.byref(n)))
+        return out[:n.value].copy()
+
+    def fgr_register(self, opts: FgrOpts = None) -> dict:
+        """performGlobalRegistration(model surf cloud, data surf cloud) (mlh_fgr_register)"""
+        r = FgrResult()
+        self._ck(self.lib.mlh_fgr_register(self.h, C.byref(opts) if opts is not None else None, C.byref(r)))
         return r.as_dict()
 
     def downsample_current_scan(self, kind, points4, leaf, ext_poses, ext_covs, cov_measurement, with_ua=True, trace_threshold=0.6, fetch=True):

@@ -492,7 +492,30 @@ struct LoopStore {
     float staged_sq[2] = {0.f, 0.f};
 };
 
-constexpr int FUSE_BLOCKS = 64;           // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
+// FPFH + Fast Global Registration over the loop store's two filtered surf clouds (fgr.hip; mloam_loop/src/loop_registration.cpp:18-101, ThirdParty/
+// FastGlobalRegistration/app.cpp). s = 0: the model surf cloud (pointcloud_[0]), s = 1: the data surf cloud. Everything per point is kept in the cloud's ORIGINAL order.
+struct FgrStore {
+    static constexpr unsigned long long NO_GEN = ~0ull;
+    MapGrid grid[2];             // the self-index: grid.hip's build over {x, y, z, original index}, cell edge max(normal_radius, fpfh_radius)
+    DevBuf ordered[2];           // the cell-sorted points with the order inside a cell fixed (ascending original index)
+    DevBuf normals[2];           // float4 {nx, ny, nz, curvature}
+    DevBuf spfh[2], nbr_k[2];    // int32 [n x 33] counts; int32 [n] fpfh_radius neighbours (the point itself included)
+    DevBuf spfh_val[2];          // f32 [n x 33]: the counts as PCL's f32 bin values
+    DevBuf feat[2];              // f32 [n x 33] FPFH (or a caller's descriptors)
+    DevBuf npts[2];              // float4 normalised points (NormalizePoints)
+    DevBuf nn[2];                // u64 (distance bits, row) keys: nn[s][r] = row r of cloud s's nearest row of the other cloud
+    DevBuf scal;                 // 8 floats (per cloud: mean xyz, max norm) + 2 ints (pair count, pad)
+    DevBuf pairs;                // FgrPair records
+    PinnedBuf h_pin;
+    int fn[2] = {0, 0};          // rows of feat[s]
+    float index_edge[2] = {0.f, 0.f}, normals_radius[2] = {0.f, 0.f}, fpfh_radius[2] = {0.f, 0.f};
+    unsigned long long index_gen[2] = {NO_GEN, NO_GEN}, normals_gen[2] = {NO_GEN, NO_GEN}, spfh_gen[2] = {NO_GEN, NO_GEN}, feat_gen[2] = {NO_GEN, NO_GEN};
+    bool feat_user[2] = {false, false};      // feat[s] came through mlh_fgr_set_features / set_spfh / set_normals: mlh_fgr_register does not recompute it
+    long long allocations = 0;
+    int launches = 0, host_waits = 0;        // of the last call
+};
+
+constexpr int FUSE_BLOCKS = 64;          // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
 constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
 constexpr int TRACK_RING_SLOTS = TRACK_MAX_RING + 3;   // ring_start[0 .. 256] + the slot the walks' upper bound is clamped to
@@ -648,6 +671,7 @@ struct mlh_ctx {
     mlh::CalibStore calib;   // the accumulated calibration features (calib.hip)
     mlh::ScStore sc;         // the Scan Context store (scancontext.hip)
     mlh::LoopStore loop;     // the loop closure's local maps and matches (loopreg.hip)
+    mlh::FgrStore fgr;       // FPFH + Fast Global Registration over the loop store's surf clouds (fgr.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}

@@ -2468,10 +2468,10 @@ inline std::pair<int, double> detectLoop(SCManager &sc_manager, const CloudT &fu
 
 // ------------------------------------------------------------------ loop-closure local registration (mloam_loop: pose_graph.cpp:364-474, loop_registration.cpp:104-211)
 // PoseGraph::checkGeometricConsistency's two device steps with the reference's names. LoopLocalMap::constructLocalMap chooses the keyframes as cpp:374-410 do,
-// forms T_ini_map_kf / T_relative in f64 and hands the lists to mlh_loop_build_clouds: the four clouds are made and stay in HBM (fetchCloud serves a caller that runs
-// FGR on the host in between). LoopRegistration::performLocalRegistration has the reference's signature shape (four clouds + T_ini -> (accepted, T_relative)) and an
-// overload that registers the clouds constructLocalMap left on the device. 4 x 4 matrices are row-major arrays of 16. What is reproduced, chosen and departed from:
-// include/mloam_hip.h (f12); the host arithmetic: csrc/loopreg_host.hpp.
+// forms T_ini_map_kf / T_relative in f64 and hands the lists to mlh_loop_build_clouds: the four clouds are made and stay in HBM (fetchCloud serves a caller that
+// wants them on the host). LoopRegistration::performGlobalRegistration (FPFH + FGR) and performLocalRegistration have the reference's signature shapes (two clouds
+// -> (accepted, T_relative); four clouds + T_ini -> (accepted, T_relative)) and overloads that register the clouds constructLocalMap left on the device. 4 x 4
+// matrices are row-major arrays of 16. What is reproduced, chosen and departed from: include/mloam_hip.h (f12), (f13); the host arithmetic: csrc/loopreg_host.hpp.
 typedef std::array<double, 16> Mat4;
 
 class LoopLocalMap {
@@ -2559,11 +2559,36 @@ public:
         return std::make_pair(last_.accepted != 0, T);
     }
     const mlh_loop_result &lastResult() const { return last_; }      // opti_cost, para_pose and the per-outer-iteration records of the last call
+
+    // performGlobalRegistration(laser_map, laser_cloud) (loop_registration.cpp:37-38): FPFH + Fast Global Registration of the two surf clouds on the device
+    // (include/mloam_hip.h (f13)) -> (accepted, T_relative). The two clouds become the context's model / data surf clouds; its two corner clouds are emptied (the
+    // reference's performLocalRegistration call that follows hands all four clouds over again).
+    mlh_fgr_opts &globalOptions() { return fgr_opts_; }
+    template <class CloudPtr> std::pair<bool, Mat4> performGlobalRegistration(const CloudPtr &laser_map, const CloudPtr &laser_cloud)
+    {
+        const auto &m = detail::deref(laser_map, 0), &d = detail::deref(laser_cloud, 0);
+        const void *clouds[4] = {ptr_of(m), nullptr, ptr_of(d), nullptr};
+        const int32_t n[4] = {int32_t(m.points.size()), 0, int32_t(d.points.size()), 0};
+        dev_.check(mlh_loop_set_clouds(dev_.ctx(), clouds, n, int(sizeof(PointI)), int(offsetof(PointI, intensity)), MLH_MEM_HOST));
+        return performGlobalRegistration();
+    }
+    // the same on the surf clouds LoopLocalMap::constructLocalMap left on this context: checkGeometricConsistency then reads as in the reference, and no cloud
+    // crosses the bus between constructLocalMap and performLocalRegistration
+    std::pair<bool, Mat4> performGlobalRegistration()
+    {
+        dev_.check(mlh_fgr_register(dev_.ctx(), &fgr_opts_, &fgr_last_));
+        Mat4 T;
+        for (int i = 0; i < 16; ++i) T[size_t(i)] = fgr_last_.T_relative[i];
+        return std::make_pair(fgr_last_.accepted != 0, T);
+    }
+    const mlh_fgr_result &lastGlobalResult() const { return fgr_last_; }      // final_cost_normalize_, the counts and the host waits of the last call
 private:
     template <class CloudT> static const void *ptr_of(const CloudT &c) { return c.points.empty() ? nullptr : static_cast<const void *>(c.points.data()); }
     Device &dev_;
     mlh_loop_opts opts_{};
     mlh_loop_result last_{};
+    mlh_fgr_opts fgr_opts_ = [] { mlh_fgr_opts o; mlh_fgr_opts_default(&o); return o; }();
+    mlh_fgr_result fgr_last_{};
 };
 
 }  // namespace mloam_hip
