@@ -413,8 +413,8 @@ int mlh_calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *resi
 /* ---------------------------------------------------------------- (f11) Scan Context place recognition, on the device
  * The front of the loop-closure process: SCManager (mloam_loop/src/scan_context.cpp:155-323) as PoseGraph::detectLoop drives it (mloam_loop/src/pose_graph.cpp:
  * 281-328). A context keeps one store in HBM: per entry the descriptor (f32, num_ring x num_sector, column-major as Eigen stores it), the ring key (f32), the sector
- * key and the column norms (f64), and on the host the optional position. The geometric verification is sections (f12) and (f13); the pose graph is not part of
- * this library.
+ * key and the column norms (f64), and on the host the optional position. The geometric verification is sections (f12) and (f13); the pose graph is section
+ * (f14).
  * Reproduced, with the lines restated:
  *   descriptor (cpp:155-186): z' = float(double(z) + lidar_height); range = sqrt(x x + y y) in f32; dropped only if range > max_radius (a point at exactly
  *     max_radius stays); ring = max(min(R, int(ceil(double(range) / max_radius * R))), 1); angle = xy2theta (cpp:38-51) as written, signed zeros and infinities
@@ -505,7 +505,7 @@ int mlh_sc_info(mlh_ctx *ctx, mlh_sc_store_info *out);
  * The geometric verification that turns a Scan Context candidate into a loop edge: PoseGraph::constructLocalMap (mloam_loop/src/pose_graph.cpp:364-419) and
  * LoopRegistration::performLocalRegistration (mloam_loop/src/loop_registration.cpp:104-211) with the loop package's own match functions (mloam_loop/include/
  * mloam_loop/utility/feature_extract.hpp:28-43, 77-247) and factor (mloam_loop/include/mloam_loop/factor/lidar_map_plane_norm_factor.hpp:47-87). FGR / FPFH
- * (performGlobalRegistration) is section (f13); checkTemporalConsistency, the pose graph and its optimisation are not part of this library. T_ini comes from
+ * (performGlobalRegistration) is section (f13), the pose graph and its optimisation section (f14); checkTemporalConsistency stays with the caller. T_ini comes from
  * mlh_fgr_register on the same clouds, or from the Scan Context yaw. A loop process uses a context of its own: mlh_loop_match, mlh_loop_evaluate
  * and mlh_loop_register OVERWRITE the context's two map indexes (mlh_map_set) and its solver state; they return MLH_ERR_STATE while a solve submitted with
  * mlh_*_begin is uncollected and MLH_ERR_UNSUPPORTED under a communicator. DEPARTURE from the plan of staging the data clouds as the context's feature sets: the
@@ -711,6 +711,102 @@ int mlh_fgr_set_features(mlh_ctx *ctx, int which, int32_t n, const float *featur
 int mlh_fgr_match(mlh_ctx *ctx, const mlh_fgr_opts *opts, int32_t *pairs_out, int32_t capacity, int32_t *n_pairs);
 int mlh_fgr_register(mlh_ctx *ctx, const mlh_fgr_opts *opts, mlh_fgr_result *result);
 int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
+
+/* ---------------------------------------------------------------- (f14) pose-graph optimisation for the loop closure, on the device
+ * What consumes the verified transform of (f12) / (f13): KeyFrame::updateLoopInfo and one pass of PoseGraph::optimizePoseGraph (mloam_loop/src/pose_graph.cpp:
+ * 136-147, 491-653) with the factor RelativeRTError (mloam_loop/include/mloam_loop/pose_graph.h:290-352) under ceres::QuaternionParameterization. A context keeps, per
+ * keyframe and in HBM, one 176-byte record: pose_w_, last_pose_w_ (KeyFrame::updatePose, keyframe.cpp:89-93), loop_info_ (each [t, q(xyzw)], f64) and loop_index_
+ * (-1: has_loop_ false); the host keeps global_index_, earliest_loop_index_ and a mirror of the loop indices. The optimisation thread with its 2 s sleep, the
+ * mutexes, updatePath / publish*, savePoseGraph / loadPoseGraph's files and the visualisation stay with the caller. Ceres is not available to this project: its
+ * trust-region policy is the project's Ceres-shaped Levenberg-Marquardt of the other solves, and what csrc/pg_host.hpp restates of Ceres 1.12 (QuaternionProduct, QuaternionRotatePoint,
+ * QuaternionParameterization's Plus and Jacobian, HuberLoss, Corrector) is from memory of that source; the header's comment lists each.
+ * Every entry but the bookkeeping ones: MLH_ERR_STATE while a solve submitted with mlh_*_begin is uncollected, MLH_ERR_UNSUPPORTED under a communicator.
+ * mlh_pg_opts_default: max_num_iterations 5 (cpp:522), 4 sequential edges (cpp:555), t_var 0.1, q_var 0.01 (cpp:566, 581), HuberLoss(1.0) (cpp:525). Options are
+ *   validated by every call that takes them (NULL: the defaults): MLH_ERR_INVALID outside 0 <= max_num_iterations <= 200, n_sequential == 4 (the band's shape is
+ *   fixed), finite variances and huber_delta > 0.
+ * mlh_pg_reset: forgets every keyframe (the buffers stay).  mlh_pg_info: the counts, earliest_loop_index_, the largest supported number of loop edges of one
+ *   problem (128), allocations and bytes held.
+ * mlh_pg_add_keyframe = the bookkeeping of PoseGraph::addKeyFrame (cpp:94-96): the keyframe gets index global_index_++; *index_out (may be NULL) <- it. CHOSEN:
+ *   last_pose_w_ and loop_info_ start as the identity (the reference's KeyFrame leaves them default-constructed). A non-finite pose: MLH_ERR_INVALID.
+ * mlh_pg_set_loop = KeyFrame::updateLoopInfo(loop_index, loop_info) plus the earliest-index rule (cpp:140-142); loadKeyFrame's loop case (cpp:187-206) is this call
+ *   after an add. Requires 0 <= loop_index < index < the number of keyframes, otherwise MLH_ERR_INVALID; a second call for a keyframe overwrites the first (the
+ *   earliest index never moves forward again, as in the reference).
+ * mlh_pg_optimize(cur_index) = the body of cpp:505-642 with first_looped_index = earliest_loop_index_, over the M keyframes first..cur:
+ *   - block `first` is constant; every keyframe gets its sequential edges to i - 1 .. i - 4 with the measurement taken from the CURRENT poses (cpp:559-563:
+ *     Eigen's q.inverse() * v and q.inverse() * q, not normalised), no loss; a keyframe with a loop gets one edge (loop keyframe, keyframe) under HuberLoss;
+ *   - ceres::Solve as the project's Ceres-shaped Levenberg-Marquardt: Jacobi scaling fixed at iteration 0, the clamped diagonal over the radius, the model cost
+ *     change, step validity, the function / parameter / gradient tolerances, the radius update and the diagonal's reuse. Every decision is taken on the device in a
+ *     state record; the launches of an iteration return at once when the solve has terminated; the number of launches (3 + 10 max_num_iterations + 1) does not
+ *     depend on M or L (the one exception: cur == first has no free block and only the loop's head is launched per iteration, 3 + max_num_iterations + 1); ONE host wait (the summary). No floating-point atomics: two runs give the same bits;
+ *   - the linear system (S H S + D / radius) y = S g is solved exactly as B + W^T W: B the block band of the sequential edges plus the diagonal (banded block
+ *     Cholesky, one workgroup, a 5 x 5-block window in LDS), W the 6 L rows of the loop edges' corrected Jacobians; [Y | y_b] = L^-1 [W^T | S g] with one lane per
+ *     column; C = I + Y^T Y and Y^T y_b by v_mfma_f64_16x16x4_f64 with K split over workgroups and a fixed-order second stage; C z = Y^T y_b by a dense Cholesky in
+ *     one workgroup (LDS up to 84 rows, HBM beyond); L^T x = y_b - Y z in one sweep. A non-positive pivot in B or in C, or a model cost change <= 0, makes the
+ *     step invalid: the radius is halved as the policy prescribes (five in a row: termination 4);
+ *   - write-back (cpp:615-641): updatePose(Pose(q, t)) on first..cur (Pose's constructor normalises q; the constant block too: its last pose becomes its pose),
+ *     pose_drift = cur * last^-1 left-multiplied onto every later keyframe through updatePose. Keyframes before `first` keep their bits.
+ *   *result: num_iterations, num_successful_steps, initial / final cost, termination (0 iteration limit, 1 gradient, 2 parameter, 3 function tolerance, 4 failure),
+ *   M, L, first, the final radius, pose_drift, launches and host waits.
+ *   MLH_ERR_STATE when no loop has been set or cur_index < earliest_loop_index_; MLH_ERR_INVALID for a cur_index that names no keyframe; MLH_ERR_UNSUPPORTED, with
+ *   nothing changed, when first..cur holds more than 128 loop edges.
+ *   DEPARTURE: the model cost change's quadratic term is summed per edge (|J S step|^2) rather than through the assembled matrix: the same number up to rounding.
+ *   CHOSEN: cur == first (M = 1) has no free block: termination 1 at iteration 0, then the write-back.
+ * mlh_pg_poses: n poses from `first` (7 doubles each) and, when last_poses is not NULL, the last poses.  mlh_pg_device_poses: the records in HBM for device
+ *   consumers: *records (NULL while empty), their stride (176; the pose at offset 0, the last pose at 56, loop_info_ at 112, loop_index_ at 168) and their number.
+ *   Valid until the next mlh_pg_add_keyframe.
+ * Stage entries (tests and diagnosis; they leave the stored poses untouched):
+ * mlh_pg_linearize(cur_index): the problem's edges at the stored poses in the reference's order (per keyframe: to i - 1 .. i - 4, then the loop edge): *n_edges;
+ *   edge_ij[2 e ..] = the two local indices (0 = first); residuals[6 e ..]; Ji / Jj[36 e ..] = the 6 x 6 row-major local Jacobians over [rotation 3, translation 3] of
+ *   the two endpoints, all as Ceres hands them to the linear solver (a loop edge scaled by sqrt(rho')); *cost = sum of rho / 2; for M <= 128 (beyond, with H or g
+ *   not NULL: MLH_ERR_UNSUPPORTED) H (n x n row-major, n = 6 (M - 1): the band the device assembled plus W^T W formed on the host from the device's rows) and g (the
+ *   device's). Arrays are sized by the caller for 5 M edges; any may be NULL.
+ * mlh_pg_solve_step(cur_index, radius): one linear solve at the stored poses with the given radius: step[n] = the Jacobi-scaled LM step (-y), delta[n] = S step,
+ *   *ok = 0 when a pivot failed.
+ * mlh_pg_optimize_forced(cur_index, fail_mask): mlh_pg_optimize, write-back included, with the linear solve of iteration k + 1 declared FAILED when bit k of
+ *   fail_mask is set, as a non-positive pivot would make it: the policy's invalid-step branch (radius /= decrease_factor, decrease_factor doubled, the diagonal
+ *   reused, termination 4 after five in a row) on demand, for the tests -- well-posed graphs never take it on their own.
+ * mlh_pg_time_stages(cur_index): a measurement entry (scripts/pgbench.py): the launches of mlh_pg_optimize WITHOUT the write-back, with an event recorded behind
+ *   every stage; *result as mlh_pg_optimize fills it (drift: the identity), stage_ms[8] <- the milliseconds between the events, summed over the iterations:
+ *   [0] linearise (begin, the initial and the candidates' linearisations), [1] assemble, [2] band factor (with the loop's head), [3] multi-column substitution,
+ *   [4] Gram, [5] dense solve, [6] y_b - Y z and the back-substitution, [7] the LM bookkeeping (candidate and decisions). The events themselves cost a few
+ *   microseconds of queue time each, which the figures include. */
+enum { MLH_PG_STAGES = 8 };
+typedef struct mlh_pg_opts {
+    int32_t max_num_iterations;              /* options.max_num_iterations (cpp:522) */
+    int32_t n_sequential;                    /* cpp:555: 4 */
+    double t_var, q_var;                     /* cpp:566, 581 */
+    double huber_delta;                      /* cpp:525 */
+} mlh_pg_opts;
+typedef struct mlh_pg_result {
+    int32_t num_iterations, num_successful_steps;
+    int32_t termination;                     /* as mlh_iter_stat::termination */
+    int32_t n_keyframes, n_loops;            /* M, L of the problem */
+    int32_t first_index;
+    int32_t launches, host_waits;
+    double initial_cost, final_cost, final_radius;
+    double drift[7];                         /* pose_drift [t, q(xyzw)] */
+    double solve_radius;                     /* the radius the last linear solve ran with (1e4 when none ran) */
+} mlh_pg_result;
+typedef struct mlh_pg_info_t {
+    int32_t n_keyframes, n_loops;
+    int32_t earliest_loop_index;             /* -1: none yet */
+    int32_t max_loops;
+    int64_t allocations;                     /* device allocations of the pose graph since the context was made */
+    int64_t bytes_hbm;
+} mlh_pg_info_t;
+void mlh_pg_opts_default(mlh_pg_opts *o);
+int mlh_pg_reset(mlh_ctx *ctx);
+int mlh_pg_info(mlh_ctx *ctx, mlh_pg_info_t *out);
+int mlh_pg_add_keyframe(mlh_ctx *ctx, const double *pose, int32_t *index_out);
+int mlh_pg_set_loop(mlh_ctx *ctx, int32_t index, int32_t loop_index, const double *rel_pose);
+int mlh_pg_optimize(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, mlh_pg_result *result);
+int mlh_pg_poses(mlh_ctx *ctx, int32_t first, int32_t n, double *poses, double *last_poses);
+int mlh_pg_device_poses(mlh_ctx *ctx, const void **records, int32_t *stride_bytes, int32_t *count);
+int mlh_pg_linearize(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, int32_t *n_edges, int32_t *edge_ij, double *residuals, double *Ji, double *Jj,
+                     double *cost, double *H, double *g);
+int mlh_pg_solve_step(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, double radius, double *step, double *delta, int32_t *ok);
+int mlh_pg_optimize_forced(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, uint32_t fail_mask, mlh_pg_result *result);
+int mlh_pg_time_stages(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, mlh_pg_result *result, double *stage_ms);
 
 /* (f1) cloudUCTAssociateToMap (lidar_mapper_keyframe.cpp:1116-1158): moves one keyframe's feature cloud into the map frame while
  * building the local map (extractSurroundingKeyFrames, cpp:254-354). Per point (intensity = LiDAR index n):

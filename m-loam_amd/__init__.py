@@ -240,6 +240,38 @@ def fgr_opts(**kw) -> FgrOpts:
 FGR_NORMALS, FGR_SPFH, FGR_FPFH = 0, 1, 2
 
 
+class PgOpts(C.Structure):
+    """mlh_pg_opts"""
+    _fields_ = [("max_num_iterations", C.c_int32), ("n_sequential", C.c_int32), ("t_var", cd_), ("q_var", cd_), ("huber_delta", cd_)]
+
+
+class PgResult(C.Structure):
+    """mlh_pg_result"""
+    _fields_ = [("num_iterations", C.c_int32), ("num_successful_steps", C.c_int32), ("termination", C.c_int32), ("n_keyframes", C.c_int32), ("n_loops", C.c_int32),
+                ("first_index", C.c_int32), ("launches", C.c_int32), ("host_waits", C.c_int32), ("initial_cost", cd_), ("final_cost", cd_), ("final_radius", cd_),
+                ("drift", cd_ * 7), ("solve_radius", cd_)]
+
+    def as_dict(self):
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k != "drift"}
+        d["drift"] = np.array(self.drift)
+        return d
+
+
+class PgInfo(C.Structure):
+    """mlh_pg_info_t"""
+    _fields_ = [("n_keyframes", C.c_int32), ("n_loops", C.c_int32), ("earliest_loop_index", C.c_int32), ("max_loops", C.c_int32), ("allocations", C.c_int64),
+                ("bytes_hbm", C.c_int64)]
+
+
+def pg_opts(**kw) -> PgOpts:
+    """mlh_pg_opts_default (pose_graph.cpp:522, 525, 555, 566), then the given fields"""
+    o = PgOpts()
+    load_library().mlh_pg_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    return o
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -420,6 +452,19 @@ def load_library():
     lib.mlh_fgr_match.argtypes = [vp, C.POINTER(FgrOpts), vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.mlh_fgr_register.argtypes = [vp, C.POINTER(FgrOpts), C.POINTER(FgrResult)]
     lib.mlh_fgr_info.argtypes = [vp, C.POINTER(FgrInfo)]
+    lib.mlh_pg_opts_default.argtypes = [C.POINTER(PgOpts)]
+    lib.mlh_pg_opts_default.restype = None
+    lib.mlh_pg_reset.argtypes = [vp]
+    lib.mlh_pg_info.argtypes = [vp, C.POINTER(PgInfo)]
+    lib.mlh_pg_add_keyframe.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    lib.mlh_pg_set_loop.argtypes = [vp, C.c_int32, C.c_int32, vp]
+    lib.mlh_pg_optimize.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.POINTER(PgResult)]
+    lib.mlh_pg_poses.argtypes = [vp, C.c_int32, C.c_int32, vp, vp]
+    lib.mlh_pg_device_poses.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mlh_pg_linearize.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.POINTER(C.c_int32), vp, vp, vp, vp, C.POINTER(cd_), vp, vp]
+    lib.mlh_pg_solve_step.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), cd_, vp, vp, C.POINTER(C.c_int32)]
+    lib.mlh_pg_time_stages.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.POINTER(PgResult), vp]
+    lib.mlh_pg_optimize_forced.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.c_uint32, C.POINTER(PgResult)]
     lib.mlh_pure_odom_add_matches.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, ci, ci]
     lib.mlh_pure_odom_add_matches_gf.argtypes = [vp, ci, vp, vp, vp, vp, ci, C.c_uint32, cf, cf, ci, ci, cf, C.c_uint64, vp, C.POINTER(C.c_int32)]
     lib.mlh_knn.argtypes = [vp, ci, vp, ci, ci, vp, vp]
@@ -472,6 +517,8 @@ EXPORTED_SYMBOLS = [
     "mlh_loop_opts_default", "mlh_loop_build_clouds", "mlh_loop_set_clouds", "mlh_loop_cloud", "mlh_loop_info_get", "mlh_loop_match", "mlh_loop_evaluate", "mlh_loop_register",
     "mlh_fgr_opts_default", "mlh_fgr_features", "mlh_fgr_spfh", "mlh_fgr_fpfh", "mlh_fgr_fetch", "mlh_fgr_set_normals", "mlh_fgr_set_spfh", "mlh_fgr_set_features",
     "mlh_fgr_match", "mlh_fgr_register", "mlh_fgr_info",
+    "mlh_pg_opts_default", "mlh_pg_reset", "mlh_pg_info", "mlh_pg_add_keyframe", "mlh_pg_set_loop", "mlh_pg_optimize", "mlh_pg_poses", "mlh_pg_device_poses",
+    "mlh_pg_linearize", "mlh_pg_solve_step", "mlh_pg_time_stages", "mlh_pg_optimize_forced",
 ]
 
 
@@ -1084,6 +1131,80 @@ class Context:
         r = FgrResult()
         self._ck(self.lib.mlh_fgr_register(self.h, C.byref(opts) if opts is not None else None, C.byref(r)))
         return r.as_dict()
+
+    # ---- pose-graph optimisation (PoseGraph::addKeyFrame's bookkeeping, updateLoopInfo, optimizePoseGraph on the device)
+    def pg_reset(self):
+        self._ck(self.lib.mlh_pg_reset(self.h))
+
+    def pg_info(self) -> dict:
+        info = PgInfo()
+        self._ck(self.lib.mlh_pg_info(self.h, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _ in info._fields_}
+
+    def pg_add_keyframe(self, pose) -> int:
+        """the keyframe's index (mlh_pg_add_keyframe); pose [t, q(xyzw)]"""
+        p, idx = np.ascontiguousarray(pose, np.float64).reshape(7), C.c_int32(-1)
+        self._ck(self.lib.mlh_pg_add_keyframe(self.h, _p(p), C.byref(idx)))
+        return idx.value
+
+    def pg_set_loop(self, index, loop_index, rel_pose):
+        """KeyFrame::updateLoopInfo + the earliest-index rule (mlh_pg_set_loop)"""
+        p = np.ascontiguousarray(rel_pose, np.float64).reshape(7)
+        self._ck(self.lib.mlh_pg_set_loop(self.h, int(index), int(loop_index), _p(p)))
+
+    def pg_optimize(self, cur_index, opts: PgOpts = None) -> dict:
+        """one pass of optimizePoseGraph's body for cur_index (mlh_pg_optimize)"""
+        r = PgResult()
+        self._ck(self.lib.mlh_pg_optimize(self.h, int(cur_index), C.byref(opts) if opts is not None else None, C.byref(r)))
+        return r.as_dict()
+
+    def pg_optimize_forced(self, cur_index, fail_mask, opts: PgOpts = None) -> dict:
+        """pg_optimize with the linear solve of iteration k + 1 declared failed for every set bit k of fail_mask (mlh_pg_optimize_forced: a test entry)"""
+        r = PgResult()
+        self._ck(self.lib.mlh_pg_optimize_forced(self.h, int(cur_index), C.byref(opts) if opts is not None else None, int(fail_mask), C.byref(r)))
+        return r.as_dict()
+
+    def pg_poses(self, first=0, n=None, last=False):
+        """(n, 7) poses from `first`; with last: (poses, last poses) (mlh_pg_poses)"""
+        n = self.pg_info()["n_keyframes"] - first if n is None else n
+        a, b = np.zeros((n, 7)), np.zeros((n, 7))
+        self._ck(self.lib.mlh_pg_poses(self.h, int(first), int(n), _p(a), _p(b) if last else None))
+        return (a, b) if last else a
+
+    def pg_device_poses(self):
+        """(device pointer or None, stride in bytes, count) of the keyframe records in HBM (mlh_pg_device_poses)"""
+        ptr, stride, cnt = C.c_void_p(None), C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mlh_pg_device_poses(self.h, C.byref(ptr), C.byref(stride), C.byref(cnt)))
+        return ptr.value, stride.value, cnt.value
+
+    def pg_linearize(self, cur_index, opts: PgOpts = None, dense=True) -> dict:
+        """the problem's edges at the stored poses -> dict(ij (E, 2), r (E, 6), Ji, Jj (E, 6, 6), cost, H (n, n), g (n,)) (mlh_pg_linearize)"""
+        info = self.pg_info()
+        M = max(1, cur_index - max(info["earliest_loop_index"], 0) + 1)
+        n = 6 * (M - 1)
+        ij, r, Ji, Jj = np.zeros((5 * M, 2), np.int32), np.zeros((5 * M, 6)), np.zeros((5 * M, 6, 6)), np.zeros((5 * M, 6, 6))
+        H, g = (np.zeros((n, n)), np.zeros(n)) if dense else (None, None)
+        ne, cost = C.c_int32(0), cd_(0.0)
+        self._ck(self.lib.mlh_pg_linearize(self.h, int(cur_index), C.byref(opts) if opts is not None else None, C.byref(ne), _p(ij), _p(r), _p(Ji), _p(Jj), C.byref(cost),
+                                           _p(H) if dense else None, _p(g) if dense else None))
+        e = ne.value
+        return dict(ij=ij[:e].copy(), r=r[:e].copy(), Ji=Ji[:e].copy(), Jj=Jj[:e].copy(), cost=cost.value, H=H, g=g)
+
+    def pg_solve_step(self, cur_index, radius, opts: PgOpts = None) -> dict:
+        """one linear solve at the stored poses with the given radius -> dict(step, delta, ok) (mlh_pg_solve_step)"""
+        info = self.pg_info()
+        n = 6 * max(0, cur_index - max(info["earliest_loop_index"], 0))
+        step, delta, ok = np.zeros(n), np.zeros(n), C.c_int32(0)
+        self._ck(self.lib.mlh_pg_solve_step(self.h, int(cur_index), C.byref(opts) if opts is not None else None, float(radius), _p(step), _p(delta), C.byref(ok)))
+        return dict(step=step, delta=delta, ok=bool(ok.value))
+
+    PG_STAGE_NAMES = ("linearize", "assemble", "band_factor", "substitution", "gram", "dense_solve", "back_substitution", "lm_bookkeeping")
+
+    def pg_time_stages(self, cur_index, opts: PgOpts = None):
+        """the launches of pg_optimize without the write-back, timed per stage -> (result dict, {stage: ms}) (mlh_pg_time_stages)"""
+        r, ms = PgResult(), np.zeros(8)
+        self._ck(self.lib.mlh_pg_time_stages(self.h, int(cur_index), C.byref(opts) if opts is not None else None, C.byref(r), _p(ms)))
+        return r.as_dict(), dict(zip(self.PG_STAGE_NAMES, ms.tolist()))
 
     def downsample_current_scan(self, kind, points4, leaf, ext_poses, ext_covs, cov_measurement, with_ua=True, trace_threshold=0.6, fetch=True):
         """downsampleCurrentScan for one kind; the result becomes the kind's feature set and, with fetch, is also returned (m, 11)

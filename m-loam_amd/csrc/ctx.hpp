@@ -515,6 +515,26 @@ struct FgrStore {
     int launches = 0, host_waits = 0;        // of the last call
 };
 
+// The loop closure's pose graph (posegraph.hip; mloam_loop/src/pose_graph.cpp:92-150, 491-653): one PgKeyframe record per keyframe in HBM, the work buffers of
+// one optimisation (sized by its M keyframes and L loop edges), and the host's bookkeeping -- global_index_, earliest_loop_index_ and a mirror of the loop indices
+// (what sizes a problem before anything is launched).
+struct PgKeyframe {
+    double pose[7], last[7], loop_rel[7];    // [t, q(xyzw)]: pose_w_, last_pose_w_, loop_info_
+    int loop_index, pad;                     // -1: has_loop_ == false
+};
+static_assert(sizeof(PgKeyframe) == 176, "the pose graph's keyframe record: three poses and the loop index, 176 bytes");
+struct PgStore {
+    DevBuf kf;                   // PgKeyframe[count]
+    DevBuf work;                 // one allocation carved into the buffers of an optimisation (posegraph.hip: pg_problem)
+    DevBuf state;                // PgState
+    PinnedBuf h_pin;
+    std::vector<int> loop_index; // host mirror of PgKeyframe::loop_index
+    std::vector<int> h_loops;    // the problem's loop list on its way to the device
+    int count = 0, earliest_loop = -1;
+    long long allocations = 0;
+    int launches = 0, host_waits = 0;        // of the last call
+};
+
 constexpr int FUSE_BLOCKS = 64;          // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
 constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
@@ -672,6 +692,7 @@ struct mlh_ctx {
     mlh::ScStore sc;         // the Scan Context store (scancontext.hip)
     mlh::LoopStore loop;     // the loop closure's local maps and matches (loopreg.hip)
     mlh::FgrStore fgr;       // FPFH + Fast Global Registration over the loop store's surf clouds (fgr.hip)
+    mlh::PgStore pg;         // the loop closure's pose graph and its optimisation (posegraph.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}

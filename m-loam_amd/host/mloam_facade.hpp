@@ -2591,4 +2591,76 @@ private:
     mlh_fgr_result fgr_last_{};
 };
 
+// ------------------------------------------------------------------ the pose graph (mloam_loop: pose_graph.cpp:92-150, 491-653; keyframe.cpp:84-105)
+// PoseGraph over the context's keyframe records (include/mloam_hip.h (f14)), templated over the caller's Pose (the reference's own, or the stand-in): addKeyFrame is
+// the bookkeeping of cpp:94-96 (the loop detection around it is SCManager, LoopLocalMap and LoopRegistration above), updateLoopInfo is cpp:140-142,
+// optimizePoseGraph(cur_index) ONE pass of the body of cpp:505-642 on the device. The optimisation thread with its 2 s sleep and optimize_buf_, the mutexes,
+// updatePath / publish*, savePoseGraph / loadPoseGraph's files and the visualisation stay with the caller; loadKeyFrame's loop case (cpp:187-206) is addKeyFrame
+// followed by updateLoopInfo.
+template <typename PoseT>
+class PoseGraph {
+public:
+    explicit PoseGraph(Device &dev) : dev_(dev) { mlh_pg_opts_default(&opts_); dev_.check(mlh_pg_reset(dev_.ctx())); }
+    mlh_pg_opts &options() { return opts_; }
+    // cur_kf->index_ = global_index_++ (cpp:94-95): the index the keyframe got
+    int addKeyFrame(const PoseT &pose_w)
+    {
+        double p[7];
+        int32_t index = -1;
+        detail::pose_to_param(pose_w, p);
+        dev_.check(mlh_pg_add_keyframe(dev_.ctx(), p, &index));
+        return index;
+    }
+    // cur_kf->updateLoopInfo(loop_index, loop_info) and the earliest_loop_index_ rule (cpp:140-142); the caller then queues index for optimizePoseGraph (cpp:144-146)
+    void updateLoopInfo(int index, int loop_index, const PoseT &loop_info)
+    {
+        double p[7];
+        detail::pose_to_param(loop_info, p);
+        dev_.check(mlh_pg_set_loop(dev_.ctx(), index, loop_index, p));
+    }
+    // one pass of the loop body for cur_index (cpp:505-642): true when it ran (pgo_flag_ is set), false when there is no loop yet or cur_index lies before the
+    // earliest looped keyframe (the reference's buffer never holds such an index)
+    bool optimizePoseGraph(int cur_index)
+    {
+        const int rc = mlh_pg_optimize(dev_.ctx(), cur_index, &opts_, &last_);
+        if (rc == MLH_ERR_STATE) return false;
+        dev_.check(rc);
+        pgo_flag_ = true;
+        return true;
+    }
+    // getKeyFrame(index)->getPose(pose) / getLastPose(pose)
+    void getPose(int index, PoseT &pose) const
+    {
+        double p[7];
+        dev_.check(mlh_pg_poses(dev_.ctx(), index, 1, p, nullptr));
+        detail::pose_from_param(pose, p);
+    }
+    void getLastPose(int index, PoseT &pose) const
+    {
+        double p[7], l[7];
+        dev_.check(mlh_pg_poses(dev_.ctx(), index, 1, p, l));
+        detail::pose_from_param(pose, l);
+    }
+    // every pose in one read-back (what updatePath walks the list for, cpp:785-860)
+    void getPoses(std::vector<PoseT> &poses) const
+    {
+        const size_t n = size_t(getKeyFrameSize());
+        std::vector<double> p(7 * n + 1);
+        dev_.check(mlh_pg_poses(dev_.ctx(), 0, int32_t(n), p.data(), nullptr));
+        poses.resize(n);
+        for (size_t i = 0; i < n; ++i) detail::pose_from_param(poses[i], p.data() + 7 * i);
+    }
+    int getKeyFrameSize() const { return info().n_keyframes; }
+    int earliestLoopIndex() const { return info().earliest_loop_index; }
+    bool pgoFlag() const { return pgo_flag_; }
+    void clearPgoFlag() { pgo_flag_ = false; }
+    const mlh_pg_result &lastResult() const { return last_; }          // the solver summary, M, L and pose_drift of the last pass
+private:
+    mlh_pg_info_t info() const { mlh_pg_info_t i; dev_.check(mlh_pg_info(dev_.ctx(), &i)); return i; }
+    Device &dev_;
+    mlh_pg_opts opts_{};
+    mlh_pg_result last_{};
+    bool pgo_flag_ = false;
+};
+
 }  // namespace mloam_hip
