@@ -1,4 +1,4 @@
-// A cloud's bounding box folded on the device while a kernel writes the cloud (keyframes.hip, window.hip): six state words per cloud in an order-preserving
+// A cloud's bounding box folded on the device while a kernel writes the cloud (keyframes.hip, cloudbuild.hip): six state words per cloud in an order-preserving
 // int encoding of the floats, so that atomicMin / atomicMax fold them; the host decodes them for the voxel filter that follows (known_bounds).
 #pragma once
 #include <hip/hip_runtime.h>

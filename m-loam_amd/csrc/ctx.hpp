@@ -193,6 +193,20 @@ struct DevBuf {
     void release() { if (p) { (void)hipFree(p); p = nullptr; cap = 0; } }
     template <typename T> T *as() const { return static_cast<T *>(p); }
 };
+// a buffer of a store brought to `bytes` (contents dropped); counted in the store's `allocations` when it allocates
+inline hipError_t ensure_counted(DevBuf &b, size_t bytes, long long &allocations)
+{
+    if (bytes > b.cap) ++allocations;
+    return b.ensure(bytes);
+}
+// n records appended to a host table at the next 16-byte boundary (p == nullptr: room only); their offset. A call's tables go to the device in one upload.
+template <class T> size_t put(std::vector<unsigned char> &h, const T *p, size_t n)
+{
+    size_t off = (h.size() + 15) & ~size_t(15);
+    h.resize(off + sizeof(T) * n);
+    if (n && p) std::memcpy(h.data() + off, p, sizeof(T) * n);
+    return off;
+}
 
 // Page-locked host memory, owned the way DevBuf owns device memory: every pinned block of the library is one of these (the only place that allocates or frees one),
 // a member of the context or of one of its sub-structures, and freed with it.
@@ -362,7 +376,7 @@ struct KfStore {
     int gpre_n[2] = {0, 0}, gflt_n[2] = {0, 0};
 };
 
-// a rigid transform in single precision (+ the LiDAR index of transformCloudFeature): what the per-point transform kernels of frontend.hip and window.hip apply
+// a rigid transform in single precision (+ the LiDAR index of transformCloudFeature): what the per-point transform kernels of frontend.hip and cloudbuild.hip apply
 struct FuseXf { float r[9], t[3], id; };
 // rotation of the unit quaternion in double, rounded once to float: what Eigen::Matrix4f holds after `.cast<float>()`
 inline FuseXf xf_from_pose(const double pose[7], float id)
@@ -970,6 +984,29 @@ int cloud_uct_associate_run(mlh_ctx *ctx, const void *points, int stride, int n,
 int voxel_filter_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off, float leaf,
                      float trace_thr, void *out_host, int *n_out, int mem, const float *known_bounds = nullptr, bool sync_total = true,
                      bool centroid_all = false);
+// A filter whose result stays on the device, collected: voxel_filter_run over n > 0 device records with the bounds decoded from the cloud's six state words
+// (bounds_dev.hpp) as the host read them back, then ctx->vox.out (n records' room: the filter never returns more) copied to `dst` and ctx->vox.total to the device
+// word `count_word`. Nothing is waited for. voxelgrid.hip.
+int voxel_filter_collect(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off, float leaf, float trace_thr,
+                         const int enc_bounds[6], bool centroid_all, void *dst, int *count_word);
+// cloudbuild.hip: stored clouds transformed and concatenated into map clouds, each then voxel-filtered (the odometry window's local maps, the loop closure's)
+struct CloudSegment {                       // one stored cloud on its way into a map cloud; the caller lists them in destination order
+    size_t src;                             // its first record in its arena
+    int n;                                  // its records (0: contributes nothing)
+    int xf;                                 // its transform in the call's table
+    int cloud;                              // the output cloud it is appended to; odd: read from the second arena
+};
+struct CloudBuildBufs {                     // the calling store's own: clouds, table, their allocation counter, and a pinned landing place of >= 7 n_clouds ints
+    DevBuf &pre, &flt, &tab;
+    std::vector<unsigned char> &htab;
+    long long &allocations;
+    int *h_pin;
+};
+// Cloud c = its segments' records, each under its transform, back to back at record off[c] of B.pre (len[c] of them, as the caller summed them), and its
+// pcl::VoxelGrid at leaf[c] at the same offset of B.flt, flt_n[c] records. ONE transform launch, one upload, two host waits. Without a record: MLH_OK at once,
+// nothing touched, flt_n as the caller left it.
+int stored_clouds_build(mlh_ctx *ctx, const float4 *arena_even, const float4 *arena_odd, const std::vector<FuseXf> &xfs, const std::vector<CloudSegment> &segs,
+                        int n_clouds, const int *off, const int *len, const float *leaf, const CloudBuildBufs &B, int *flt_n);
 // frontend.hip
 void gather_points_launch(mlh_ctx *ctx, const float4 *pts, const int *list, int n, float4 *out);
 int transform_cloud_launch(mlh_ctx *ctx, void *dev, int stride, int n, const double pose[7]);
@@ -1117,5 +1154,8 @@ void comm_destroy(mlh_ctx *ctx);   // in-place ncclAllReduce of SolverState::ne 
 int lm_begin_launch(mlh_ctx *ctx, double map_eig_thre, int max_iterations, int stat_slot, int min_blocks = 0, const double *init_pose = nullptr);
 int lm_step_launch(mlh_ctx *ctx, int max_iterations, int stat_slot);
 int lm_finish_launch(mlh_ctx *ctx, int stat_slot);
+// loopreg.hip: what every entry of the loop process that runs kernels against the context's maps and solver state begins with (loop registration, FGR, the pose
+// graph): refused while a submitted solve is uncollected (MLH_ERR_STATE) or under a communicator (MLH_ERR_UNSUPPORTED); then a pending last iteration is flushed
+int loop_process_gate(mlh_ctx *ctx, const char *entry);
 
 }  // namespace mlh

@@ -311,12 +311,6 @@ __global__ __launch_bounds__(TPB) void fgr_mutual_kernel(const unsigned long lon
 struct FgrPinned { float scal[8]; int counts[2]; int pad[6]; };        // the pair records follow
 static_assert(sizeof(FgrPinned) == 64, "the pinned header");
 
-hipError_t fgr_ensure(FgrStore &F, DevBuf &b, size_t bytes)
-{
-    if (bytes > b.cap) ++F.allocations;
-    return b.ensure(bytes);
-}
-
 size_t grid_bytes(const MapGrid &g) { return g.raw.cap + g.sorted.cap + g.cell_id.cap + g.cell_start.cap + g.cell_fill.cap + g.block_sums.cap + g.bounds.cap + g.occ.cap; }
 
 int fgr_opts_take(mlh_ctx *ctx, const char *entry, const mlh_fgr_opts *opts, mlh_fgr_opts &o)
@@ -328,10 +322,9 @@ int fgr_opts_take(mlh_ctx *ctx, const char *entry, const mlh_fgr_opts *opts, mlh
 
 int fgr_gate(mlh_ctx *ctx, const char *entry)
 {
-    if (ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, (std::string(entry) + ": a solve submitted with mlh_*_begin has not been collected").c_str());
-    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, (std::string(entry) + ": not under a communicator (a loop process uses a context of its own)").c_str());
-    ctx->fgr.launches = 0; ctx->fgr.host_waits = 0;
-    return gn_flush_pending(ctx);
+    { const int rc = loop_process_gate(ctx, entry); if (rc) return rc; }
+    ctx->fgr.launches = 0; ctx->fgr.host_waits = 0;          // (a refused call leaves the previous call's counts)
+    return MLH_OK;
 }
 
 int side_of(mlh_ctx *ctx, const char *entry, int which, int *s)
@@ -347,11 +340,11 @@ int fgr_buffers_ensure(mlh_ctx *ctx, int s, int n)
 {
     FgrStore &F = ctx->fgr;
     const size_t rows = size_t(n) + 1;
-    MLH_HIP(ctx, fgr_ensure(F, F.normals[s], sizeof(float4) * rows));
-    MLH_HIP(ctx, fgr_ensure(F, F.spfh[s], sizeof(int) * FGR_DIM * rows));
-    MLH_HIP(ctx, fgr_ensure(F, F.nbr_k[s], sizeof(int) * rows));
-    MLH_HIP(ctx, fgr_ensure(F, F.spfh_val[s], sizeof(float) * FGR_DIM * rows));
-    MLH_HIP(ctx, fgr_ensure(F, F.feat[s], sizeof(float) * FGR_DIM * rows));
+    MLH_HIP(ctx, ensure_counted(F.normals[s], sizeof(float4) * rows, F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.spfh[s], sizeof(int) * FGR_DIM * rows, F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.nbr_k[s], sizeof(int) * rows, F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.spfh_val[s], sizeof(float) * FGR_DIM * rows, F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.feat[s], sizeof(float) * FGR_DIM * rows, F.allocations));
     return MLH_OK;
 }
 
@@ -371,7 +364,7 @@ int fgr_index_ensure(mlh_ctx *ctx, int s, float edge)
     { const int rc = grid_build_grids(ctx, &gp, 1, true); if (rc) return rc; }
     ++F.host_waits;
     if (grid_bytes(g) > before) ++F.allocations;
-    MLH_HIP(ctx, fgr_ensure(F, F.ordered[s], sizeof(float4) * (size_t(n) + 1)));
+    MLH_HIP(ctx, ensure_counted(F.ordered[s], sizeof(float4) * (size_t(n) + 1), F.allocations));
     MLH_LAUNCH(fgr_order_kernel, dim3((n + TPB - 1) / TPB), dim3(TPB), 0, ctx->stream, g.dev(), F.ordered[s].as<float4>());
     F.launches += 2;
     MLH_HIP(ctx, hipGetLastError());
@@ -437,10 +430,10 @@ int fgr_match_enqueue(mlh_ctx *ctx, bool with_points, bool *swapped_out)
     const int n0 = F.fn[0], n1 = F.fn[1];
     const bool swapped = n1 > n0;                                          // app.cpp:121-127
     *swapped_out = swapped;
-    MLH_HIP(ctx, fgr_ensure(F, F.nn[0], sizeof(unsigned long long) * (size_t(n0) + 1)));
-    MLH_HIP(ctx, fgr_ensure(F, F.nn[1], sizeof(unsigned long long) * (size_t(n1) + 1)));
-    MLH_HIP(ctx, fgr_ensure(F, F.pairs, sizeof(FgrPair) * (size_t(std::min(n0, n1)) + 1)));
-    MLH_HIP(ctx, fgr_ensure(F, F.scal, 64));
+    MLH_HIP(ctx, ensure_counted(F.nn[0], sizeof(unsigned long long) * (size_t(n0) + 1), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.nn[1], sizeof(unsigned long long) * (size_t(n1) + 1), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.pairs, sizeof(FgrPair) * (size_t(std::min(n0, n1)) + 1), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.scal, 64, F.allocations));
     MLH_HIP(ctx, hipMemsetAsync(F.nn[0].p, 0xFF, sizeof(unsigned long long) * (size_t(n0) + 1), st));
     MLH_HIP(ctx, hipMemsetAsync(F.nn[1].p, 0xFF, sizeof(unsigned long long) * (size_t(n1) + 1), st));
     if (n0 > 0 && n1 > 0) {
@@ -521,9 +514,9 @@ int register_run(mlh_ctx *ctx, const mlh_fgr_opts &o, mlh_fgr_result *res)
         if (!features_valid(ctx, s, o)) { const int rc = fgr_stages_run(ctx, s, o, STAGE_NORMALS); if (rc) return rc; }
     const int n0 = cloud_n(ctx, 0), n1 = cloud_n(ctx, 1);
     hipStream_t st = ctx->stream;
-    MLH_HIP(ctx, fgr_ensure(F, F.npts[0], sizeof(float4) * (size_t(n0) + 1)));
-    MLH_HIP(ctx, fgr_ensure(F, F.npts[1], sizeof(float4) * (size_t(n1) + 1)));
-    MLH_HIP(ctx, fgr_ensure(F, F.scal, 64));
+    MLH_HIP(ctx, ensure_counted(F.npts[0], sizeof(float4) * (size_t(n0) + 1), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.npts[1], sizeof(float4) * (size_t(n1) + 1), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.scal, 64, F.allocations));
     MLH_LAUNCH(fgr_norm_stats_kernel, dim3(2), dim3(TPB), 0, st, cloud_pts(ctx, 0), n0, cloud_pts(ctx, 1), n1, F.scal.as<float>());
     ++F.launches;
     if (std::max(n0, n1) > 0) {

@@ -307,14 +307,6 @@ std::vector<int> thin_positions(const std::vector<std::array<float, 3>> &pos, fl
     return out;
 }
 
-template <class T> size_t put(std::vector<unsigned char> &h, const T *p, size_t n)
-{
-    size_t off = (h.size() + 15) & ~size_t(15);
-    h.resize(off + sizeof(T) * n);
-    if (n && p) std::memcpy(h.data() + off, p, sizeof(T) * n);
-    return off;
-}
-
 bool bad_pose(const double *p) { for (int i = 0; i < 7; ++i) if (!std::isfinite(p[i])) return true; return false; }
 
 }  // namespace
@@ -578,21 +570,14 @@ int local_map_assemble_run(mlh_ctx *ctx, const double pose_cur[7], const double 
     // wait 1: the pre-filter lengths and bounds
     MLH_HIP(ctx, hipMemcpyAsync(h_pin, ds, sizeof(int) * 14, hipMemcpyDeviceToHost, st));
     MLH_HIP(ctx, stream_wait_spin(ctx));
-    float bounds[2][6];
-    for (int k = 0; k < 2; ++k) {
-        K.pre_n[k] = h_pin[k];
-        for (int d = 0; d < 6; ++d) bounds[k][d] = dec_f(h_pin[2 + 6 * k + d]);
-    }
+    for (int k = 0; k < 2; ++k) K.pre_n[k] = h_pin[k];
     // the two covariance filters (cpp:343-346), results left in the context
     const float leaf[2] = {o->leaf_surf, o->leaf_corner};
     for (int k = 0; k < 2; ++k) {
         if (K.pre_n[k] == 0) { MLH_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(ds + 14 + k), 0, 1, st)); continue; }
-        int dummy = 0;
-        int rc = voxel_filter_run(ctx, K.pre[k].p, REC, K.pre_n[k], 12, 16, 40, leaf[k], float(o->trace_threshold), nullptr, &dummy, MLH_MEM_DEVICE, bounds[k], false);
+        MLH_HIP(ctx, K.flt[k].ensure(size_t(REC) * size_t(K.pre_n[k])));      // (ahead of the filter, which neither reads nor names this buffer: ensure enqueues nothing)
+        const int rc = voxel_filter_collect(ctx, K.pre[k].p, REC, K.pre_n[k], 12, 16, 40, leaf[k], float(o->trace_threshold), h_pin + 2 + 6 * k, false, K.flt[k].p, ds + 14 + k);
         if (rc) return rc;
-        MLH_HIP(ctx, K.flt[k].ensure(size_t(REC) * size_t(K.pre_n[k])));
-        MLH_HIP(ctx, hipMemcpyAsync(K.flt[k].p, ctx->vox.out.p, size_t(REC) * size_t(K.pre_n[k]), hipMemcpyDeviceToDevice, st));
-        MLH_HIP(ctx, hipMemcpyAsync(ds + 14 + k, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, st));
     }
     // wait 2: the filtered counts
     MLH_HIP(ctx, hipMemcpyAsync(h_pin + 16, ds + 14, sizeof(int) * 2, hipMemcpyDeviceToHost, st));
@@ -784,20 +769,13 @@ int global_map_assemble_run(mlh_ctx *ctx, const double *pose_cur, const double *
     // wait 1: the pre-filter lengths and bounds
     MLH_HIP(ctx, hipMemcpyAsync(h_pin, state, sizeof(int) * 14, hipMemcpyDeviceToHost, st));
     MLH_HIP(ctx, stream_wait_spin(ctx));
-    float bounds[2][6];
-    for (int k = 0; k < 2; ++k) {
-        K.gpre_n[k] = h_pin[k];
-        for (int d = 0; d < 6; ++d) bounds[k][d] = dec_f(h_pin[2 + 6 * k + d]);
-    }
+    for (int k = 0; k < 2; ++k) K.gpre_n[k] = h_pin[k];
     // one covariance filter per output cloud (cpp:839-842 / 896-901), results kept in buffers of the global map's own
     for (int k = 0; k < 2; ++k) {
         if (K.gpre_n[k] == 0) continue;                                    // (its filtered count stays at the 0 it was uploaded with)
-        int dummy = 0;
-        const int rc = voxel_filter_run(ctx, K.gpre[k].p, REC, K.gpre_n[k], 12, 16, 40, o->leaf, float(o->trace_threshold), nullptr, &dummy, MLH_MEM_DEVICE, bounds[k], false);
+        MLH_HIP(ctx, K.gflt[k].ensure(size_t(REC) * size_t(K.gpre_n[k])));    // (ahead of the filter, which neither reads nor names this buffer: ensure enqueues nothing)
+        const int rc = voxel_filter_collect(ctx, K.gpre[k].p, REC, K.gpre_n[k], 12, 16, 40, o->leaf, float(o->trace_threshold), h_pin + 2 + 6 * k, false, K.gflt[k].p, state + 14 + k);
         if (rc) return rc;
-        MLH_HIP(ctx, K.gflt[k].ensure(size_t(REC) * size_t(K.gpre_n[k])));
-        MLH_HIP(ctx, hipMemcpyAsync(K.gflt[k].p, ctx->vox.out.p, size_t(REC) * size_t(K.gpre_n[k]), hipMemcpyDeviceToDevice, st));
-        MLH_HIP(ctx, hipMemcpyAsync(state + 14 + k, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, st));
     }
     // wait 2: the filtered counts
     MLH_HIP(ctx, hipMemcpyAsync(h_pin + 16, state + 14, sizeof(int) * 2, hipMemcpyDeviceToHost, st));

@@ -2,9 +2,9 @@
 // LoopRegistration::performLocalRegistration (mloam_loop/src/loop_registration.cpp:104-211). include/mloam_hip.h, section (f12), has the contract and every
 // CHOSEN / DEPARTURE; loopreg_host.hpp the host arithmetic (options, pose conversions, the 0.2 rule).
 //   the clouds   model surf / corner and data surf / corner, float4 {x, y, z, intensity}, back to back in one pre-filter and one filtered buffer.
-//                mlh_loop_build_clouds: host tables of 256-point tiles over the (cloud x keyframe) segments and one FuseXf per list entry, ONE wm_transform_kernel
-//                launch (xform_tiles_dev.hpp: the window maps' launch) out of the keyframe store, then voxel_filter_run x 4 with known bounds -- the shape of
-//                window.hip's map build. Two host waits.
+//                mlh_loop_build_clouds: the (cloud x keyframe) segments of the keyframe store in destination order and one FuseXf per list entry, handed to
+//                stored_clouds_build (cloudbuild.hip: the builder shared with the window maps): ONE transform launch, then a voxel filter per cloud with known
+//                bounds. Two host waits.
 //   loop_match_kernel<KIND>   matchSurfFromMap / matchCornerFromMap (feature_extract.hpp:77-247): 16 lanes per data point; point_sel in f32; exact 5-NN through
 //                knn_group over the context's map index; the fit by every lane of the group (plane_fit_qr_f / eig3_largest_f of dev_math.hpp, the mapper path's
 //                restatements), lane 0 stores. Features go to per-point slots (surf: one, corner: two), invalid ones zeroed; no compaction. features.size() is an
@@ -22,8 +22,6 @@
 #include "dev_math.hpp"
 #include "knn_dev.hpp"
 #include "reduce_dev.hpp"
-#include "bounds_dev.hpp"
-#include "xform_tiles_dev.hpp"
 #include "loopreg_host.hpp"
 
 namespace mlh {
@@ -182,20 +180,6 @@ __global__ __launch_bounds__(TPB) void loop_eval_kernel(const double4 *__restric
     reduce_rows(ok, L, huber_delta, false, kind, s_red, partials + size_t(tile) * NE_STRIDE);
 }
 
-template <class T> size_t put(std::vector<unsigned char> &h, const T *p, size_t n)
-{
-    size_t off = (h.size() + 15) & ~size_t(15);
-    h.resize(off + sizeof(T) * n);
-    if (n && p) std::memcpy(h.data() + off, p, sizeof(T) * n);
-    return off;
-}
-
-hipError_t loop_ensure(LoopStore &L, DevBuf &b, size_t bytes)
-{
-    if (bytes > b.cap) ++L.allocations;
-    return b.ensure(bytes);
-}
-
 int loop_opts_take(mlh_ctx *ctx, const char *entry, const mlh_loop_opts *opts, mlh_loop_opts &o)
 {
     if (opts) o = *opts; else loop_opts_defaults(o);
@@ -213,14 +197,6 @@ LoopXf xf_of(const double T[16])
 }
 
 int tiles_of(int slots) { return (slots + TPB - 1) / TPB; }
-
-// what every entry that runs kernels against the context's maps and solver state begins with
-int loop_solver_gate(mlh_ctx *ctx, const char *entry)
-{
-    if (ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, (std::string(entry) + ": a solve submitted with mlh_*_begin has not been collected").c_str());
-    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, (std::string(entry) + ": not under a communicator (a loop process uses a context of its own)").c_str());
-    return gn_flush_pending(ctx);
-}
 
 // the two filtered model clouds into the context's map indexes, when they or the thresholds changed or another call restaged the maps since
 int loop_stage_maps(mlh_ctx *ctx, const mlh_loop_opts &o)
@@ -242,9 +218,9 @@ int loop_slots_ensure(mlh_ctx *ctx)
 {
     LoopStore &L = ctx->loop;
     const size_t n_slots = size_t(L.flt_n[MLH_LOOP_DATA_SURF]) + 2 * size_t(L.flt_n[MLH_LOOP_DATA_CORNER]);
-    MLH_HIP(ctx, loop_ensure(L, L.slots, sizeof(double4) * (n_slots + 1)));
-    MLH_HIP(ctx, loop_ensure(L, L.valid, n_slots + 16));
-    MLH_HIP(ctx, loop_ensure(L, L.counts, sizeof(int) * 4));
+    MLH_HIP(ctx, ensure_counted(L.slots, sizeof(double4) * (n_slots + 1), L.allocations));
+    MLH_HIP(ctx, ensure_counted(L.valid, n_slots + 16, L.allocations));
+    MLH_HIP(ctx, ensure_counted(L.counts, sizeof(int) * 4, L.allocations));
     return MLH_OK;
 }
 
@@ -339,9 +315,8 @@ int build_clouds_run(mlh_ctx *ctx, const int32_t *data_keys, const float *data_T
             if (keys[s][e] < 0 || size_t(keys[s][e]) >= K.keys.size()) return fail(ctx, MLH_ERR_INVALID, "mlh_loop_build_clouds: no such keyframe");
             for (int q = 0; q < 16; ++q) if (!std::isfinite(mats[s][16 * e + q])) return fail(ctx, MLH_ERR_INVALID, "mlh_loop_build_clouds: non-finite matrix");
         }
-    hipStream_t st = ctx->stream;
     ++L.cloud_gen;
-    // the transforms (model list, then data list) and the tiles, in destination order: cloud 2 side + kind, list order inside a cloud
+    // the transforms (model list, then data list) and the segments, in destination order: cloud 2 side + kind, list order inside a cloud
     std::vector<FuseXf> xfs(size_t(n_model + n_data));
     for (int s = 0; s < 2; ++s)
         for (int e = 0; e < n_list[s]; ++e) {
@@ -350,17 +325,15 @@ int build_clouds_run(mlh_ctx *ctx, const int32_t *data_keys, const float *data_T
             for (int r = 0; r < 3; ++r) { for (int c = 0; c < 3; ++c) x.r[r * 3 + c] = M[r * 4 + c]; x.t[r] = M[r * 4 + 3]; }
             x.id = 0.f;
         }
-    std::vector<WmTile> tiles;
+    std::vector<CloudSegment> segs;
     size_t N = 0;
     for (int c = 0; c < 4; ++c) {
         const int s = c >> 1, kind = c & 1;
         L.off[c] = int(N);
         for (int e = 0; e < n_list[s]; ++e) {
             const KfStore::Key &k = K.keys[size_t(keys[s][e])];
-            const int n = k.n[kind];
-            for (int at = 0; at < n; at += 256)
-                tiles.push_back(WmTile{(long long)(k.off[kind] + size_t(at)), int(N) + at, std::min(256, n - at), (s ? n_model : 0) + e, c});
-            N += size_t(n);
+            segs.push_back(CloudSegment{k.off[kind], k.n[kind], (s ? n_model : 0) + e, c});
+            N += size_t(k.n[kind]);
             if (N > size_t(INT_MAX) / 4) return fail(ctx, MLH_ERR_NOMEM, "mlh_loop_build_clouds: too many points");
         }
         L.pre_n[c] = int(N) - L.off[c];
@@ -368,47 +341,13 @@ int build_clouds_run(mlh_ctx *ctx, const int32_t *data_keys, const float *data_T
         if (n_pre) n_pre[c] = L.pre_n[c];
         if (n_ds) n_ds[c] = 0;
     }
-    if (tiles.empty()) return MLH_OK;
-    MLH_HIP(ctx, loop_ensure(L, L.pre, sizeof(float4) * (N + 1)));
-    MLH_HIP(ctx, loop_ensure(L, L.flt, sizeof(float4) * (N + 1)));
     { const int rc = loop_pin(ctx); if (rc) return rc; }
-    int *h_pin = L.h_pin.as<int>();
-    std::vector<int> state0(28, 0);                     // [6 c .. 6 c + 5] cloud c's bounds (order-preserving int encoding), [24 + c] its filtered count
-    for (int c = 0; c < 4; ++c) for (int d = 0; d < 3; ++d) { state0[size_t(6 * c + d)] = INT_MAX; state0[size_t(6 * c + 3 + d)] = INT_MIN; }
-    std::vector<unsigned char> &h = L.htab;
-    h.clear();
-    const size_t o_xf = put(h, xfs.data(), xfs.size());
-    const size_t o_til = put(h, tiles.data(), tiles.size());
-    const size_t o_sta = put(h, state0.data(), state0.size());
-    MLH_HIP(ctx, loop_ensure(L, L.tab, h.size() + 16));
-    unsigned char *dt = L.tab.as<unsigned char>();
-    MLH_HIP(ctx, hipMemcpyAsync(dt, h.data(), h.size(), hipMemcpyHostToDevice, st));
-    int *state = reinterpret_cast<int *>(dt + o_sta);
-    float4 *pre = L.pre.as<float4>(), *flt = L.flt.as<float4>();
-    // every cloud reads the keyframe store's one arena: the kernel's two source pointers are the same
-    MLH_LAUNCH(wm_transform_kernel, dim3(unsigned(tiles.size())), dim3(256), 0, st, (const float4 *)K.pts.as<float4>(), (const float4 *)K.pts.as<float4>(),
-               reinterpret_cast<const WmTile *>(dt + o_til), reinterpret_cast<const FuseXf *>(dt + o_xf), pre, state);
-    MLH_HIP(ctx, hipGetLastError());
-    // wait 1: the pre-filter clouds' bounds
-    MLH_HIP(ctx, hipMemcpyAsync(h_pin, state, sizeof(int) * 24, hipMemcpyDeviceToHost, st));
-    MLH_HIP(ctx, stream_wait_spin(ctx));
-    for (int c = 0; c < 4; ++c) {                       // pcl::VoxelGrid<PointXYZI>, pose_graph.cpp:388-391, 411-414
-        const int n = L.pre_n[c];
-        if (n == 0) continue;
-        float bounds[6];
-        for (int d = 0; d < 6; ++d) bounds[d] = dec_f(h_pin[6 * c + d]);
-        const float leaf = (c & 1) ? o.leaf_corner : o.leaf_surf;
-        int dummy = 0;
-        const int rc = voxel_filter_run(ctx, pre + L.off[c], 16, n, 12, -1, -1, leaf, 0.f, nullptr, &dummy, MLH_MEM_DEVICE, bounds, false, true);
-        if (rc) return rc;
-        MLH_HIP(ctx, hipMemcpyAsync(flt + L.off[c], ctx->vox.out.p, sizeof(float4) * size_t(n), hipMemcpyDeviceToDevice, st));
-        MLH_HIP(ctx, hipMemcpyAsync(state + 24 + c, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, st));
-    }
-    // wait 2: the filtered counts
-    MLH_HIP(ctx, hipMemcpyAsync(h_pin, state + 24, sizeof(int) * 4, hipMemcpyDeviceToHost, st));
-    MLH_HIP(ctx, stream_wait_spin(ctx));
-    for (int c = 0; c < 4; ++c) { L.flt_n[c] = h_pin[c]; if (n_ds) n_ds[c] = h_pin[c]; }
-    return device_error_check(ctx);
+    // every cloud reads the keyframe store's one arena; pcl::VoxelGrid<PointXYZI> per cloud, pose_graph.cpp:388-391, 411-414
+    const float leaf[4] = {o.leaf_surf, o.leaf_corner, o.leaf_surf, o.leaf_corner};
+    const int rc = stored_clouds_build(ctx, K.pts.as<float4>(), K.pts.as<float4>(), xfs, segs, 4, L.off, L.pre_n, leaf,
+                                       CloudBuildBufs{L.pre, L.flt, L.tab, L.htab, L.allocations, L.h_pin.as<int>()}, L.flt_n);
+    if (n_ds) for (int c = 0; c < 4; ++c) n_ds[c] = L.flt_n[c];
+    return rc;
 }
 
 int set_clouds_run(mlh_ctx *ctx, const void *const *clouds, const int32_t *n, int stride, int ioff, int mem)
@@ -426,7 +365,7 @@ int set_clouds_run(mlh_ctx *ctx, const void *const *clouds, const int32_t *n, in
     }
     hipStream_t st = ctx->stream;
     ++L.cloud_gen;
-    MLH_HIP(ctx, loop_ensure(L, L.flt, sizeof(float4) * (N + 1)));
+    MLH_HIP(ctx, ensure_counted(L.flt, sizeof(float4) * (N + 1), L.allocations));
     if (mem == MLH_MEM_HOST && host_total > 0) MLH_HIP(ctx, ctx->tmp.ensure(host_total));
     size_t at = 0;
     for (int c = 0; c < 4; ++c) {
@@ -446,7 +385,7 @@ int set_clouds_run(mlh_ctx *ctx, const void *const *clouds, const int32_t *n, in
 int match_run(mlh_ctx *ctx, int kind, const double *T, const mlh_loop_opts &o, uint8_t *valid, double *coeffs, int32_t *n_features)
 {
     LoopStore &L = ctx->loop;
-    { const int rc = loop_solver_gate(ctx, "mlh_loop_match"); if (rc) return rc; }
+    { const int rc = loop_process_gate(ctx, "mlh_loop_match"); if (rc) return rc; }
     int rc = loop_stage_maps(ctx, o);
     if (rc || (rc = loop_slots_ensure(ctx)) || (rc = loop_state_ensure(ctx, 1))) return rc;
     if ((rc = loop_match_enqueue(ctx, o, xf_of(T), 1 << kind))) return rc;
@@ -467,7 +406,7 @@ int match_run(mlh_ctx *ctx, int kind, const double *T, const mlh_loop_opts &o, u
 
 int evaluate_run(mlh_ctx *ctx, const double *T_match, const double *pose, const mlh_loop_opts &o, double *H, double *g, double *cost, int32_t *counts)
 {
-    { const int rc = loop_solver_gate(ctx, "mlh_loop_evaluate"); if (rc) return rc; }
+    { const int rc = loop_process_gate(ctx, "mlh_loop_evaluate"); if (rc) return rc; }
     int rc = loop_stage_maps(ctx, o);
     if (rc || (rc = loop_slots_ensure(ctx)) || (rc = loop_state_ensure(ctx, 1))) return rc;
     if ((rc = loop_match_enqueue(ctx, o, xf_of(T_match), 3)) || (rc = loop_eval_enqueue(ctx, o, 0, pose))) return rc;
@@ -485,7 +424,7 @@ int evaluate_run(mlh_ctx *ctx, const double *T_match, const double *pose, const 
 int register_run(mlh_ctx *ctx, const double *T_ini, const mlh_loop_opts &o, mlh_loop_result *res)
 {
     LoopStore &L = ctx->loop;
-    { const int rc = loop_solver_gate(ctx, "mlh_loop_register"); if (rc) return rc; }
+    { const int rc = loop_process_gate(ctx, "mlh_loop_register"); if (rc) return rc; }
     int rc = loop_stage_maps(ctx, o);
     if (rc || (rc = loop_slots_ensure(ctx)) || (rc = loop_state_ensure(ctx, o.max_outer))) return rc;
     hipStream_t st = ctx->stream;
@@ -531,6 +470,13 @@ int register_run(mlh_ctx *ctx, const double *T_ini, const mlh_loop_opts &o, mlh_
 }
 
 }  // namespace
+
+int loop_process_gate(mlh_ctx *ctx, const char *entry)
+{
+    if (ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, (std::string(entry) + ": a solve submitted with mlh_*_begin has not been collected").c_str());
+    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, (std::string(entry) + ": not under a communicator (a loop process uses a context of its own)").c_str());
+    return gn_flush_pending(ctx);
+}
 
 }  // namespace mlh
 

@@ -686,10 +686,9 @@ __global__ __launch_bounds__(PG_TPB) void pg_writeback_kernel(PgDev P)
 
 int pg_gate(mlh_ctx *ctx, const char *entry)
 {
-    if (ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, (std::string(entry) + ": a solve submitted with mlh_*_begin has not been collected").c_str());
-    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, (std::string(entry) + ": not under a communicator (a loop process uses a context of its own)").c_str());
-    ctx->pg.launches = 0; ctx->pg.host_waits = 0;
-    return gn_flush_pending(ctx);
+    { const int rc = loop_process_gate(ctx, entry); if (rc) return rc; }
+    ctx->pg.launches = 0; ctx->pg.host_waits = 0;          // (a refused call leaves the previous call's counts)
+    return MLH_OK;
 }
 
 int pg_opts_take(mlh_ctx *ctx, const char *entry, const mlh_pg_opts *opts, mlh_pg_opts &o)

@@ -15,6 +15,7 @@
 // Streaming kernels: ~ (stride + 8) B/point per pass + 1/8 B/cell (bits) + 8 B per 32 cells for the popcount scan.
 #include "ctx.hpp"
 #include "std_sort_mt.hpp"
+#include "bounds_dev.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -504,6 +505,19 @@ int voxel_filter_run(mlh_ctx *ctx, const void *points, int stride, int n, int in
         MLH_HIP(ctx, hipStreamSynchronize(st));
     }
     return device_error_check(ctx);
+}
+
+int voxel_filter_collect(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off, float leaf, float trace_thr,
+                         const int enc_bounds[6], bool centroid_all, void *dst, int *count_word)
+{
+    float bounds[6];
+    for (int d = 0; d < 6; ++d) bounds[d] = dec_f(enc_bounds[d]);
+    int dummy = 0;
+    const int rc = voxel_filter_run(ctx, points, stride, n, intensity_off, cov_off, trace_off, leaf, trace_thr, nullptr, &dummy, MLH_MEM_DEVICE, bounds, false, centroid_all);
+    if (rc) return rc;
+    MLH_HIP(ctx, hipMemcpyAsync(dst, ctx->vox.out.p, size_t(stride) * size_t(n), hipMemcpyDeviceToDevice, ctx->stream));
+    MLH_HIP(ctx, hipMemcpyAsync(count_word, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+    return MLH_OK;
 }
 
 // Two device-resident clouds of the same record layout thinned (plain branch) in ONE set of launches: the second cloud's voxels are

@@ -6,41 +6,20 @@
 //   the store   float4 {x, y, z, intensity} records, the layout of FeatSet::pts and of the keyframe store, in one arena per kind cut into equal slabs. A slot names
 //               a slab (or the empty cloud), a slab counts the slots that name it: slideWindow's push (CircularBuffer.h:186-197) moves names and counts on the host
 //               and copies no point. A cloud larger than the slabs re-cuts the arena (one allocation); in steady state nothing is allocated or freed.
-//   the maps    host: a table of 256-point TILES over the n_lidar x window_size x 2 segments in destination order (per LiDAR, per kind, per slot; a tile never
-//               straddles a segment, an empty segment has none) and one FuseXf per (LiDAR, slot) from pose_local (xf_from_pose: the rotation in double, rounded once);
-//   wm_transform_kernel   pcl::transformPointCloud of one tile per workgroup (cpp:1185-1191 / 1095-1101): the tile's transform is uniform and is loaded ONCE per workgroup
-//               into LDS; the per-point expression is transform_cloud_kernel's (frontend.hip), term for term, so the bits are mlh_transform_point_cloud's. The record
-//               goes straight to its place in the pre-filter cloud (`+=` in slot order), the intensity is copied, the source is left untouched, and the cloud's bounds
-//               are folded once per workgroup (bounds_dev.hpp);
-//   voxel_filter_run x 2 n_lidar   pcl::VoxelGrid<PointI> per pre-filter cloud at its leaf (cpp:1103-1109, 1195-1203), bounds known, counts left on the device.
-// Per build: ONE transform launch and one upload of every table, whatever window_size and the segment sizes are; host waits: two (the clouds' bounds; the filtered
-// counts), plus the one inside a voxel filter whose grid has more than 2^31 cells (the input comes back) and one for a map buffer that has to grow.
+//   the maps    host: the n_lidar x window_size x 2 stored clouds as SEGMENTS in destination order (per LiDAR, per kind, per slot) and one FuseXf per (LiDAR, slot)
+//               from pose_local (xf_from_pose: the rotation in double, rounded once); stored_clouds_build (cloudbuild.hip: the builder shared with the loop closure's
+//               local maps) does the rest: pcl::transformPointCloud of every segment into its pre-filter cloud (cpp:1185-1191 / 1095-1101; `+=` in slot order) in ONE
+//               launch, then pcl::VoxelGrid<PointI> per pre-filter cloud at its leaf (cpp:1103-1109, 1195-1203). Two host waits per build.
 #include "ctx.hpp"
 #include <algorithm>
 #include <climits>
 #include <cmath>
-#include "bounds_dev.hpp"
-#include "xform_tiles_dev.hpp"
 
 namespace mlh {
 
 namespace {
 
 constexpr int WIN_MAX = 16;                 // LiDARs, window size
-template <class T> size_t put(std::vector<unsigned char> &h, const T *p, size_t n)
-{
-    size_t off = (h.size() + 15) & ~size_t(15);
-    h.resize(off + sizeof(T) * n);
-    if (n && p) std::memcpy(h.data() + off, p, sizeof(T) * n);
-    return off;
-}
-
-// a buffer of the store brought to `bytes` (contents dropped); counted when it allocates
-hipError_t win_ensure(WinStore &W, DevBuf &b, size_t bytes)
-{
-    if (bytes > b.cap) ++W.allocations;
-    return b.ensure(bytes);
-}
 
 int slot_index(const WinStore &W, int lidar, int slot) { return lidar * (W.window + 1) + (W.start + slot) % (W.window + 1); }
 
@@ -218,24 +197,23 @@ static int window_build_local_map_run(mlh_ctx *ctx, const double *pose_local, co
         if (!pos_finite(o->leaf_surf[l]) || !pos_finite(o->leaf_corner[l])) return fail(ctx, MLH_ERR_INVALID, "mlh_window_build_local_map: every LiDAR's leaves must be finite and > 0");
     const int cap = W.window + 1, n_clouds = 2 * W.n_lidar;
     for (int i = 0; i < W.n_lidar * cap; ++i) if (bad_pose(pose_local + 7 * i)) return fail(ctx, MLH_ERR_INVALID, "mlh_window_build_local_map: non-finite pose_local");
-    hipStream_t st = ctx->stream;
-
-    // the transforms and the tiles, in destination order
+    // the transforms and the segments, in destination order
     std::vector<FuseXf> xfs(size_t(W.n_lidar * cap));
     for (int i = 0; i < W.n_lidar * cap; ++i) xfs[size_t(i)] = xf_from_pose(pose_local + 7 * i, 0.f);
-    std::vector<WmTile> tiles;
+    std::vector<CloudSegment> segs;
     std::vector<int> off(size_t(n_clouds), 0), len(size_t(n_clouds), 0);
+    std::vector<float> leaf(size_t(n_clouds), 0.f);
     size_t N = 0;
     for (int l = 0; l < W.n_lidar; ++l) {
         const int from = o->source_lidar < 0 ? l : o->source_lidar;
         for (int k = 0; k < 2; ++k) {
             const int c = 2 * l + k;
             off[size_t(c)] = int(N);
+            leaf[size_t(c)] = k ? o->leaf_corner[l] : o->leaf_surf[l];      // pcl::VoxelGrid<PointI> per cloud (cpp:1103-1109, 1195-1203)
             for (int i = 0; i < W.window; ++i) {            // slot window_size is skipped (cpp:1182)
                 const int s = W.slot_slab[k][size_t(slot_index(W, from, i))];
                 const int n = s < 0 ? 0 : W.slab_n[k][size_t(s)];
-                for (int at = 0; at < n; at += 256)
-                    tiles.push_back(WmTile{(long long)(size_t(s) * W.slab[k] + size_t(at)), int(N) + at, std::min(256, n - at), from * cap + i, c});
+                segs.push_back(CloudSegment{s < 0 ? 0 : size_t(s) * W.slab[k], n, from * cap + i, c});
                 N += size_t(n);
                 if (N > size_t(INT_MAX) / 2) return fail(ctx, MLH_ERR_NOMEM, "window map: too many points");
             }
@@ -244,50 +222,11 @@ static int window_build_local_map_run(mlh_ctx *ctx, const double *pose_local, co
     }
     W.map_off = off; W.map_pre_n = len; W.map_flt_n.assign(size_t(n_clouds), 0);
     for (int c = 0; c < n_clouds; ++c) { n_pre[c] = len[size_t(c)]; n_ds[c] = 0; }
-    if (tiles.empty()) return MLH_OK;                       // every contributing slot is empty
-
-    // buffers, and one upload of every table of the call (the state words start as: empty bounds, no filtered records)
-    MLH_HIP(ctx, win_ensure(W, W.pre, sizeof(float4) * (N + 1)));
-    MLH_HIP(ctx, win_ensure(W, W.flt, sizeof(float4) * (N + 1)));
     MLH_HIP(ctx, W.h_pin.ensure(sizeof(int) * 7 * 2 * WIN_MAX));
-    int *h_pin = W.h_pin.as<int>();
-    std::vector<int> state0(size_t(7 * n_clouds), 0);       // [6 c .. 6 c + 5] cloud c's bounds (order-preserving int encoding), [6 n_clouds + c] its filtered count
-    for (int c = 0; c < n_clouds; ++c) for (int d = 0; d < 3; ++d) { state0[size_t(6 * c + d)] = INT_MAX; state0[size_t(6 * c + 3 + d)] = INT_MIN; }
-    std::vector<unsigned char> &h = W.htab;
-    h.clear();
-    const size_t o_xf = put(h, xfs.data(), xfs.size());
-    const size_t o_til = put(h, tiles.data(), tiles.size());
-    const size_t o_sta = put(h, state0.data(), state0.size());
-    MLH_HIP(ctx, win_ensure(W, W.tab, h.size() + 16));
-    unsigned char *dt = W.tab.as<unsigned char>();
-    MLH_HIP(ctx, hipMemcpyAsync(dt, h.data(), h.size(), hipMemcpyHostToDevice, st));
-    int *state = reinterpret_cast<int *>(dt + o_sta);
-    float4 *pre = W.pre.as<float4>(), *flt = W.flt.as<float4>();
-
-    MLH_LAUNCH(wm_transform_kernel, dim3(unsigned(tiles.size())), dim3(256), 0, st, (const float4 *)W.arena[0].as<float4>(), (const float4 *)W.arena[1].as<float4>(),
-               reinterpret_cast<const WmTile *>(dt + o_til), reinterpret_cast<const FuseXf *>(dt + o_xf), pre, state);
-    MLH_HIP(ctx, hipGetLastError());
-    // wait 1: the pre-filter clouds' bounds
-    MLH_HIP(ctx, hipMemcpyAsync(h_pin, state, sizeof(int) * 6 * size_t(n_clouds), hipMemcpyDeviceToHost, st));
-    MLH_HIP(ctx, stream_wait_spin(ctx));
-    // pcl::VoxelGrid<PointI> per cloud (cpp:1103-1109, 1195-1203)
-    for (int c = 0; c < n_clouds; ++c) {
-        const int n = len[size_t(c)];
-        if (n == 0) continue;                               // (its filtered count stays at the 0 it was uploaded with)
-        float bounds[6];
-        for (int d = 0; d < 6; ++d) bounds[d] = dec_f(h_pin[6 * c + d]);
-        const float leaf = (c & 1) ? o->leaf_corner[c >> 1] : o->leaf_surf[c >> 1];
-        int dummy = 0;
-        const int rc = voxel_filter_run(ctx, pre + off[size_t(c)], 16, n, 12, -1, -1, leaf, 0.f, nullptr, &dummy, MLH_MEM_DEVICE, bounds, false, true);
-        if (rc) return rc;
-        MLH_HIP(ctx, hipMemcpyAsync(flt + off[size_t(c)], ctx->vox.out.p, sizeof(float4) * size_t(n), hipMemcpyDeviceToDevice, st));
-        MLH_HIP(ctx, hipMemcpyAsync(state + 6 * n_clouds + c, ctx->vox.total.p, sizeof(int), hipMemcpyDeviceToDevice, st));
-    }
-    // wait 2: the filtered counts
-    MLH_HIP(ctx, hipMemcpyAsync(h_pin, state + 6 * n_clouds, sizeof(int) * size_t(n_clouds), hipMemcpyDeviceToHost, st));
-    MLH_HIP(ctx, stream_wait_spin(ctx));
-    for (int c = 0; c < n_clouds; ++c) { W.map_flt_n[size_t(c)] = h_pin[c]; n_ds[c] = h_pin[c]; }
-    return device_error_check(ctx);
+    const int rc = stored_clouds_build(ctx, W.arena[0].as<float4>(), W.arena[1].as<float4>(), xfs, segs, n_clouds, off.data(), len.data(), leaf.data(),
+                                       CloudBuildBufs{W.pre, W.flt, W.tab, W.htab, W.allocations, W.h_pin.as<int>()}, W.map_flt_n.data());
+    for (int c = 0; c < n_clouds; ++c) n_ds[c] = W.map_flt_n[size_t(c)];
+    return rc;
 }
 
 static int window_map_cloud_run(mlh_ctx *ctx, int lidar, int kind, int filtered, const void **device_points, int32_t *n)

@@ -447,3 +447,27 @@ def test_pinned_memory_and_host_waits_have_one_owner(mla):
     assert sum(t.count("milliseconds(200)") for t in text.values()) == 1
     for gone in ("solve_pending", "h_pts_cap", "h_rings_cap", "select_host_cap", "vox_order_host_cap"):
         assert not [f for f, t in text.items() if gone in t], gone
+
+
+def test_stored_cloud_builder_and_loop_gate_have_one_owner(mla):
+    """The map builder over stored clouds is one translation unit (csrc/cloudbuild.hip: the transform kernel defined and launched there alone, the header that
+    compiled it into two objects gone); the loop process's entry rule, the host-table packer and the counted allocation are written once; a stage's own gate is at
+    most the shared gate plus its counter resets."""
+    import re
+    pkg = os.path.dirname(os.path.abspath(mla.__file__))
+    csrc = os.path.join(pkg, "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp"))}
+    assert len(text) >= 20
+    assert [f for f, t in text.items() if re.search(r"__global__[^;{]*\bwm_transform_kernel\s*\(", t)] == ["cloudbuild.hip"]
+    assert [f for f, t in text.items() if re.search(r"MLH_LAUNCH\(\s*wm_transform_kernel\b|hipLaunchKernelGGL\(\s*wm_transform_kernel\b|wm_transform_kernel\s*<<<", t)] == ["cloudbuild.hip"]
+    assert "xform_tiles_dev.hpp" not in os.listdir(csrc) and "xform_tiles_dev.hpp" not in open(os.path.join(pkg, "build.py")).read()
+    assert "cloudbuild.hip" in open(os.path.join(pkg, "build.py")).read()
+    assert sum(t.count("a loop process uses a context of its own") for t in text.values()) == 1
+    assert sum(t.count("size_t put(") for t in text.values()) == 1
+    for gone in ("win_ensure", "loop_ensure", "fgr_ensure", "loop_solver_gate"):
+        assert not [f for f, t in text.items() if gone in t], gone
+    for name in ("fgr_gate", "pg_gate"):
+        for f, t in text.items():
+            for m in re.finditer(r"^int " + name + r"\([^)]*\)\s*\{\n(.*?)^\}", t, re.S | re.M):
+                body = [ln for ln in m.group(1).splitlines() if ln.strip()]
+                assert len(body) <= 3 and "loop_process_gate(ctx, entry)" in body[0] and "pending" not in m.group(1), (f, name, body)

@@ -104,6 +104,59 @@ def test_build_clouds_is_transform_concatenation_and_voxel_grid(mla, ctx, orc):
     assert np.array_equal(_bits64(got["T_relative"]), _bits64(again["T_relative"]))
 
 
+def test_build_clouds_at_tile_edges(mla, ctx, orc):
+    """keyframes whose (surf, corner) sizes sit on the edges of the 256-point transform tile -- (0, 257), (1, 0), (513, 256), (255, 1), (256, 513), (7, 7): points
+    uniform in +-20 m, intensity 0..16 -- in both lists under twelve distinct transforms, then a build without a model list, one without a data list and one whose
+    keyframes are all empty: n_pre, the pre-filter clouds (the restatement's f32 transform + concatenation) and the filtered clouds (the voxel-grid restatement of
+    those at the loop's own leaf, 0.4) bit for bit; zeros and empty clouds where a list is empty; a repeat of the largest build allocates nothing"""
+    rng = np.random.default_rng(1207)
+
+    def crafted(n):
+        a = np.empty((n, 4), np.float32)
+        a[:, :3] = rng.uniform(-20, 20, (n, 3))
+        a[:, 3] = rng.uniform(0, 16, n)
+        return a
+
+    sizes = [(0, 257), (1, 0), (513, 256), (255, 1), (256, 513), (7, 7)]
+    clouds = [(crafted(ns), crafted(nc)) for ns, nc in sizes]
+    eye7 = np.array([0, 0, 0, 0, 0, 0, 1.0])
+    keys = [ctx.keyframe_save(eye7, np.eye(6), surf, corner) for surf, corner in clouds]
+    k_none = ctx.keyframe_save(eye7, np.eye(6), lc.EMPTY, lc.EMPTY)
+    T = lambda i: lc.yaw_T(17.0 * i - 40.0, (0.5 * i - 2.0, 1.5 - 0.3 * i, 0.1 * i)).astype(np.float32)
+    model_all = [(k, T(i)) for i, k in enumerate(keys)]
+    data_all = [(k, T(6 + i)) for i, k in reversed(list(enumerate(keys)))]
+
+    def check(data, model, label):
+        n_pre, n_ds = ctx.loop_build_clouds(data, model)
+        for which in range(4):
+            lst, kind = (model, data)[which >> 1], which & 1
+            parts = [lc.transform(clouds[keys.index(k)][kind], Tf) for k, Tf in lst if k != k_none and len(clouds[keys.index(k)][kind])]
+            want_pre = np.concatenate(parts) if parts else lc.EMPTY
+            want_flt = orc.voxel_grid(want_pre, lc.LEAF) if len(want_pre) else lc.EMPTY
+            pre, flt = ctx.loop_cloud(which, filtered=False), ctx.loop_cloud(which, filtered=True)
+            print(label, which, "n_pre", n_pre[which], len(want_pre), "n_ds", n_ds[which], len(want_flt))
+            assert n_pre[which] == len(want_pre) and n_ds[which] == len(want_flt), (label, which, n_pre, n_ds)
+            assert _same_cloud(pre, want_pre), (label, which)
+            assert _same_cloud(flt, want_flt), (label, which)
+        info = ctx.loop_info()
+        assert info["n_pre"] == list(n_pre) and info["n_ds"] == list(n_ds), label
+
+    check(data_all, model_all, "both")
+    assert ctx.loop_info()["n_pre"] == [1032, 1034, 1032, 1034]
+    a0 = ctx.loop_info()["allocations"]
+    check(data_all, model_all, "both again")
+    assert ctx.loop_info()["allocations"] == a0
+    check(data_all, [], "no model")
+    assert ctx.loop_info()["n_pre"][:2] == [0, 0] and ctx.loop_info()["n_ds"][:2] == [0, 0]
+    check([], model_all, "no data")
+    assert ctx.loop_info()["n_pre"][2:] == [0, 0] and ctx.loop_info()["n_ds"][2:] == [0, 0]
+    check([(k_none, T(3))], [(k_none, T(4)), (k_none, T(5))], "all empty")
+    assert ctx.loop_info()["n_pre"] == [0, 0, 0, 0] and ctx.loop_info()["n_ds"] == [0, 0, 0, 0]
+    assert all(len(ctx.loop_cloud(w, filtered=f)) == 0 for w in range(4) for f in (False, True))
+    check(data_all, model_all, "both after the empty ones")
+    assert ctx.loop_info()["allocations"] == a0
+
+
 @pytest.mark.parametrize("pose", ["T_ini", "truth", "far"])
 def test_match_on_the_scene(mla, ctx, pose):
     """both kinds at the hand-over pose, the truth and a pose far off: validity, features.size() and every coefficient's bits"""
@@ -254,15 +307,39 @@ def test_state_errors_and_repeatability(mla, ctx, synth, case16, feats16):
         other.loop_set_clouds(*s["clouds4"])
         c = other.loop_register(s["T_ini"])
         assert np.array_equal(_bits64(a["T_relative"]), _bits64(c["T_relative"])) and a["opti_cost"] == c["opti_cost"] and a["outer"] == c["outer"]
-        # MLH_ERR_STATE while a submitted solve is uncollected
+        # MLH_ERR_STATE while a submitted solve is uncollected: the loop registration, and the other stages of the loop process -- FGR and the pose graph, each in
+        # a state in which nothing but the open solve stands in its entries' way, and with the counters of a call that ran
+        for which in (mla.LOOP_MODEL_SURF, mla.LOOP_DATA_SURF):
+            other.fgr_features(which)
+        pairs = other.fgr_match()
+        other.pg_reset()
+        for p in ([0, 0, 0, 0, 0, 0, 1.0], [1.0, 0.05, 0, 0, 0, 0, 1.0], [2.0, 0.2, 0.05, 0, 0, 0, 1.0]):
+            other.pg_add_keyframe(p)
+        other.pg_set_loop(2, 0, [2.1, 0.1, 0.0, 0, 0, 0, 1.0])
+        lin = other.pg_linearize(2)
         other.map_set(mla.SURF, case16["surf_map"])
         other.map_set(mla.CORNER, case16["corner_map"])
         other.scan2map_begin(case16["p0"])
         with pytest.raises(mla.MlhError, match="mlh error -3"):
             other.loop_register(s["T_ini"])
+        fgr_info, pg_info = other.fgr_info(), other.pg_info()
+        assert fgr_info["launches"] > 0 and pg_info["n_keyframes"] == 3 and pg_info["n_loops"] == 1
+        refused = [lambda: other.fgr_features(mla.LOOP_MODEL_SURF), other.fgr_match, other.fgr_register,
+                   lambda: other.pg_optimize(2), lambda: other.pg_linearize(2), lambda: other.pg_solve_step(2, 1e4)]
+        for call in refused:
+            with pytest.raises(mla.MlhError, match="mlh error -3.*has not been collected"):
+                call()
+        assert other.fgr_info() == fgr_info and other.pg_info() == pg_info
         other.scan2map_end()
         d = other.loop_register(s["T_ini"])
         assert np.array_equal(_bits64(a["T_relative"]), _bits64(d["T_relative"]))
+        other.fgr_features(mla.LOOP_MODEL_SURF)
+        assert np.array_equal(other.fgr_match(), pairs)
+        assert other.fgr_register()["n_corres"] >= 0
+        again = other.pg_linearize(2)
+        assert np.array_equal(_bits64(again["r"]), _bits64(lin["r"])) and again["cost"] == lin["cost"]
+        assert other.pg_solve_step(2, 1e4)["step"].shape == (12,)
+        assert other.pg_optimize(2)["n_keyframes"] == 3
     finally:
         other.close()
     # MLH_ERR_INVALID on bad options
