@@ -436,6 +436,11 @@ int mlh_create(mlh_ctx **out, int device_id)
     if (!c) return MLH_ERR_NOMEM;
     c->device = device_id;
     if (const char *e = std::getenv("MLH_KNN_LANES")) c->knn_lanes_override = std::atoi(e);
+    if (const char *e = std::getenv("MLH_KNN_WG_THREADS")) {
+        const int v = std::atoi(e);
+        if (v != 256 && v != 512 && v != 1024) { delete c; return MLH_ERR_INVALID; }
+        c->knn_wg_override = v;
+    }
     if (query_device_caps(c) != MLH_OK) { delete c; return MLH_ERR_HIP; }
     // the solver's stream: the whole device, or -- MLH_SOLVER_CU_MASK=<hex word>[,<hex word>...], bit i of word w = compute unit 32 w + i -- a part of it (a
     // deployment that keeps compute units for other work; the tests of the residency gates)

@@ -737,6 +737,8 @@ struct mlh_ctx {
     int fused_parts = 0;
     float fused_minmax[2][6];   // folded by mlh_fused_cloud: the voxel filter of a fused cloud needs no bounds pass of its own
     int knn_lanes_override = 0;   // MLH_KNN_LANES=8|16|32, or SSCC (816, 832, 1632: surf lanes, corner lanes), in the environment at mlh_create: pins the correspondence kernel's lanes per query (tests, tuning)
+    int knn_wg_override = 0;      // MLH_KNN_WG_THREADS=256|512|1024, in the environment at mlh_create: pins the workgroup width of the correspondence launches that have wide forms (match.hip: knn_wg_threads_for; tests, A/B runs)
+    int knn_wg_last = 0;          // the width the last such launch took
     int gn_final_defer = 1;       // mlh_set_gn_schedule: 0: a solve submitted with mlh_gn_solve_begin* finishes its LAST iteration in its own fit launch (classic); 1: that
                                   // iteration, too, only leaves its records -- the next mlh_gn_solve_begin_chained completes it in its first launch (and publishes the pose
                                   // from there), mlh_gn_solve_end or any other solver call completes it with a one-workgroup launch if no successor did

@@ -309,10 +309,11 @@ __device__ __forceinline__ void knn_feature_warm(const KParams &P, const KindL &
 
 // MB = more than one pose block in the launch (config 4); without it the block bookkeeping (a per-lane block index and the
 // per-block K lookup it drags along) compiles away
-template <int G, bool MB, bool K10, bool PRE, bool WARM>
+// W: threads per workgroup (TPB, or 512 / 1024 in the wide prologue forms)
+template <int G, bool MB, bool K10, bool PRE, bool WARM, int W = TPB>
 __device__ __forceinline__ void knn_features_body(const KParams &P, const KindL &K, int kind, int own_mode, int tile, int *s_run, const double *s_pose, int m_feat)
 {
-    constexpr int FPB = TPB / G;          // queries per workgroup
+    constexpr int FPB = W / G;            // queries per workgroup
     constexpr int RUNW = 2 * KNN_RUN_WORDS;
     const int grp = threadIdx.x / G, gl = threadIdx.x % G;
     const int f = tile * FPB + grp;
@@ -354,14 +355,16 @@ __device__ __forceinline__ void knn_features_body(const KParams &P, const KindL 
     }
 }
 
-// The prologue of a correspondence launch that completes a Gauss-Newton iteration first (all TPB threads of the workgroup, converged):
+// The prologue of a correspondence launch that completes a Gauss-Newton iteration first (all W threads of the workgroup, converged; the first GN_SUM_THREADS of
+// them sum, the first wavefront solves, the others of a wide workgroup only stand at the barriers):
 //   s_pose <- the pose that iteration linearised at; the records its fit launch left are summed (sum_partials<TPB, 12>'s arithmetic -- same slices, same four chains,
 //   same association: the same bits --, inlined: the record loads leave at once instead of behind an argument block's trip through scratch, and nobody waits for the
 //   per-kind counts, which only statistics read); gn_finish_wave solves and applies Plus on the first wavefront; s_pose holds the updated pose when this returns.
 // MODE 1: an iteration of the running solve. MODE 2: the LAST iteration of the PREVIOUS solve (thresholds from the launch arguments).
 // b: the pose block this workgroup's features belong to (0 without blocks): the records summed are that block's tiles -- its surf tiles, then its corner tiles, as the
 // classic finish walks them -- and the thresholds that block's.
-template <int MODE, bool MB = false>
+constexpr int GN_SUM_THREADS = 256;      // the sum's geometry: 8 slices x 32 columns, whatever the workgroup's width (the association is part of the result's bits)
+template <int MODE, bool MB = false, int W = TPB>
 __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_pose, double *f_ne, double *f_cnt2, double *f_scratch)
 {
     // (the pose is requested here and stored behind the records' sum: its trip and the records' run together, not one behind the other)
@@ -371,9 +374,11 @@ __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_p
         else if (MB && P.pre_from_state) pose_v = (b == 0 ? P.state->x : P.state->xb[b])[threadIdx.x];
         else pose_v = P.x_prev[7 * b + threadIdx.x];
     }
+    static_assert(W >= GN_SUM_THREADS && W % 64 == 0, "the sum takes the first 256 threads of the workgroup");
     {
-        constexpr int NS = TPB / 32, U = 12;
+        constexpr int NS = GN_SUM_THREADS / 32, U = 12;
         const int c = threadIdx.x & 31, sl = threadIdx.x >> 5;
+        const bool sums = W == GN_SUM_THREADS || threadIdx.x < GN_SUM_THREADS;      // (uniform over a wavefront; the others of a wide workgroup walk no records)
         int lo0 = 0, n0 = P.pre_tiles, lo1 = 0, n1 = 0;
         if constexpr (MB) {
             lo0 = P.k[0].m > 0 ? P.k[0].blk_start[b] / TPB : 0;
@@ -382,7 +387,7 @@ __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_p
             n1 = P.k[1].m > 0 ? (P.k[0].tiles_b + (P.k[1].blk_start[b + 1] + TPB - 1) / TPB) - lo1 : 0;
             n0 = max(n0, 0); n1 = max(n1, 0);
         }
-        const int ntot = n0 + n1;
+        const int ntot = sums ? n0 + n1 : 0;
         const double *__restrict__ rec = P.partials;
         double ch[4] = {0.0, 0.0, 0.0, 0.0};
         for (int j = sl; j < ntot; j += U * NS) {
@@ -396,7 +401,7 @@ __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_p
 #pragma unroll
             for (int u = 0; u < U; ++u) ch[u & 3] += tv[u];
         }
-        f_scratch[sl * 32 + c] = (ch[0] + ch[1]) + (ch[2] + ch[3]);
+        if (sums) f_scratch[sl * 32 + c] = (ch[0] + ch[1]) + (ch[2] + ch[3]);
         if (threadIdx.x < 7) s_pose[threadIdx.x] = pose_v;
         __syncthreads();
         if (threadIdx.x < 32) {
@@ -434,113 +439,29 @@ __device__ __forceinline__ void publish_final_pose(const KParams &P, const doubl
 //   predecessor's serial finish and the chain launch between the two frames are gone.
 // WARM: the search is bounded by the previous iteration's neighbours (knn_feature_warm). All three only in the single-block, K = 5 launches of mlh_gn_solve*.
 // DEVM: the feature counts come from P.m_dev (G = 0 only: lanes per kind); the grid was sized for a bound, the workgroups beyond the real tiles leave
+// W: threads per workgroup. W / lanes queries per workgroup and as many run tables in LDS; the prologue's sum and solve take the first GN_SUM_THREADS threads
+//   and the first wavefront whatever W is. One prologue per workgroup: with W = 1024 a frame-sized launch runs one per compute unit instead of four.
 template <int G, bool MB, bool K10, int PRE = 0, bool WARM = false, bool DEVM = false>
 __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
 {
-    __shared__ int s_run[(G == 16) ? (TPB / 16) * 2 * KNN_RUN_WORDS : (TPB / 8) * 2 * KNN_RUN_WORDS];
-    __shared__ double s_pose[PRE ? 8 : 1];
-    // every argument this launch's path reads -- tile counts, the prologue's, the search's of both kinds, ownership --: one batch, one wait
-    const KindL k0 = P.k[0], k1 = P.k[1];
-    {
-        const arg_i4 c0 = MLH_KIND_COUNTS(k0), c1 = MLH_KIND_COUNTS(k1), d0 = MLH_GRID_DIMS(k0), d1 = MLH_GRID_DIMS(k1), w = MLH_WORDS(P);
-        const arg_f4 o0 = MLH_GRID_ORIGIN(k0), o1 = MLH_GRID_ORIGIN(k1);
-        const int kb0 = P.kb[0];
-#define MLH_KNN_KINDS "s"(k0.feat), "s"(k0.nbr), "s"(c0), "s"(k0.lanes), "s"(k0.grid.sorted), "s"(k0.grid.raw), "s"(k0.grid.cell_start), "s"(o0), "s"(d0), "s"(k1.feat), "s"(k1.nbr), \
-                      "s"(c1), "s"(k1.lanes), "s"(k1.grid.sorted), "s"(k1.grid.raw), "s"(k1.grid.cell_start), "s"(o1), "s"(d1), "s"(w), "s"(kb0)
-        if constexpr (PRE == 0) {
-            const arg_d4 ip0{P.init_pose[0], P.init_pose[1], P.init_pose[2], P.init_pose[3]};
-            const arg_d2 ip1{P.init_pose[4], P.init_pose[5]};
-            const double ip2 = P.init_pose[6];
-            const double *const pose_b0 = P.pose_b0, *const pose_bn = P.pose_bn;
-            asm volatile("; kernel arguments in registers" ::MLH_KNN_KINDS, "s"(ip0), "s"(ip1), "s"(ip2), "s"(pose_b0), "s"(pose_bn));
-        } else {
-            // (a start pose in the arguments is read per lane, by index: nothing to name)
-            const double *const x_prev = P.x_prev;
-            double *const x_next = P.x_next, *const partials = P.partials;
-            const int pre_tiles = P.pre_tiles, pre_from_init = P.pre_from_init;
-            if constexpr (PRE == 1) {
-                const double thre0 = P.thre_b[0];
-                const int freeze0 = P.freeze_b[0];
-                asm volatile("; kernel arguments in registers" ::MLH_KNN_KINDS, "s"(x_prev), "s"(x_next), "s"(partials), "s"(pre_tiles), "s"(pre_from_init), "s"(thre0), "s"(freeze0));
-            } else {
-                SolverState *const state = P.state;
-                HostPublish *const pre_publish = P.pre_publish;
-                const unsigned long long pre_publish_seq = P.pre_publish_seq;
-                const double pre_thre = P.pre_thre;
-                const int pre_freeze = P.pre_freeze;
-                asm volatile("; kernel arguments in registers" ::MLH_KNN_KINDS, "s"(x_prev), "s"(x_next), "s"(partials), "s"(pre_tiles), "s"(pre_from_init), "s"(state), "s"(pre_publish),
-                             "s"(pre_publish_seq), "s"(pre_thre), "s"(pre_freeze));
-            }
-        }
-#undef MLH_KNN_KINDS
-    }
-    int m0 = k0.m, m1 = k1.m, ta0 = k0.tiles_a;
-    int total = k0.tiles_a + k1.tiles_a;
-    if constexpr (DEVM) {
-        static_assert(G == 0 && !MB && PRE == 0, "device-side counts: per-kind lanes, one block, no prologue");
-        m0 = P.m_dev[0]; m1 = P.m_dev[1];
-        const int f0 = TPB / k0.lanes, f1 = TPB / k1.lanes;
-        ta0 = (m0 + f0 - 1) / f0;
-        total = ta0 + (m1 + f1 - 1) / f1;
-        if ((int(blockIdx.x) >> 3) >= ((total + 7) >> 3)) return;     // (xcd_tile is a bijection only on the first 8 * ceil(total / 8) workgroups)
-    }
-    int tile = xcd_tile(total);
-    if (tile >= total) return;
-    const int kind = tile >= ta0 ? 1 : 0;
-    // this workgroup's kind and the ownership word, as values the compiler cannot fetch again: behind the prologue it would rather re-read both kinds' arguments
-    // and select once more than keep the selection in registers
-    KindL K = pick_kind(kind != 0, k0, k1);
-    int own_mode = P.own_mode;
-    if constexpr (PRE != 0 && !MB) {
-        asm volatile("" : "+s"(K.feat), "+s"(K.nbr), "+s"(K.nbr_stride), "+s"(K.lanes), "+s"(K.grid.sorted), "+s"(K.grid.raw), "+s"(K.grid.cell_start), "+s"(own_mode));
-        // (the grid's origin and dimensions are left out: the compiler selects those four-word groups as vectors, on the vector unit)
-    }
-    if constexpr (PRE != 0) {
-        __shared__ double f_ne[NE_STRIDE], f_cnt2[2], f_scratch[(TPB / 32) * 32];
-        int pb = 0;
-        bool writer = tile == 0;
-        if constexpr (MB) {
-            // pose blocks start on 256-slot boundaries and a workgroup serves 16 or 32 consecutive slots of ONE kind: all of them in one block. The block's pose is
-            // written by the workgroup of its first surf tile (the host defers a solve over blocks only when every block has surf features)
-            const int tk = kind ? tile - ta0 : tile;
-            const int lanes = (G == 0) ? K.lanes : G;
-            const int f0 = tk * (TPB / lanes);
-            pb = block_of_slot(P.k[kind], P.n_blocks, f0);
-            writer = kind == 0 && f0 == P.k[0].blk_start[pb];
-        }
-        gn_prologue<PRE, MB>(P, pb, s_pose, f_ne, f_cnt2, f_scratch);
-        if constexpr (PRE == 2) {
-            __shared__ double s_chain[8];
-            if (threadIdx.x == 0) {
-                if (tile == 0) publish_final_pose(P, s_pose);
-                double xc[7], out[7];
-                for (int i = 0; i < 7; ++i) xc[i] = s_pose[i];
-                double cp[7], cc[7];
-                for (int i = 0; i < 7; ++i) { cp[i] = P.chain_prev[i]; cc[i] = P.chain_cur[i]; }
-                chain_start_pose(xc, cp, cc, out);
-                for (int i = 0; i < 7; ++i) s_chain[i] = out[i];
-            }
-            __syncthreads();
-            if (threadIdx.x < 7) s_pose[threadIdx.x] = s_chain[threadIdx.x];
-            __syncthreads();
-        }
-        if (writer && threadIdx.x < 7) P.x_next[7 * pb + threadIdx.x] = s_pose[threadIdx.x];
-    }
-    if (kind) tile -= ta0;
-    const int m_feat = kind ? m1 : m0;
-    if constexpr (G == 0) {
-        if (K.lanes == 8) knn_features_body<8, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
-        else if (K.lanes == 32) knn_features_body<32, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
-        else knn_features_body<16, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
-    } else {
-        knn_features_body<G, MB, K10, PRE != 0, WARM>(P, K, kind, own_mode, tile, s_run, s_pose, m_feat);
-    }
+    constexpr int W = TPB;
+#include "knn_features_kernel.inc"
+}
+
+// The wide forms of the single-block, K = 5 launches of mlh_gn_solve* (PRE 1 warm and cold, PRE 2, PRE 0 warm): the same body, prologue and argument batch in
+// workgroups of 512 or 1024 threads. Kernels of their own: the 256-thread instantiations above keep their names and their code.
+template <int W, int G, int PRE, bool WARM>
+__global__ __launch_bounds__(W) void knn_features_wide_kernel(KParams P)
+{
+    static_assert(W == 512 || W == 1024, "wide workgroups: 512 or 1024 threads");
+    constexpr bool MB = false, K10 = false, DEVM = false;
+#include "knn_features_kernel.inc"
 }
 
 // a pending last iteration completed by itself (no chained successor took it): one workgroup, the same prologue, the same publication
 __global__ __launch_bounds__(TPB) void gn_final_kernel(KParams P)
 {
-    __shared__ double s_pose[8], f_ne[NE_STRIDE], f_cnt2[2], f_scratch[(TPB / 32) * 32];
+    __shared__ double s_pose[8], f_ne[NE_STRIDE], f_cnt2[2], f_scratch[(GN_SUM_THREADS / 32) * 32];
     gn_prologue<2>(P, 0, s_pose, f_ne, f_cnt2, f_scratch);
     if (threadIdx.x == 0) publish_final_pose(P, s_pose);
 }
@@ -1264,7 +1185,20 @@ void knn_lanes_for(const mlh_ctx *ctx, int kind_mask, int lanes[2])
     }
 }
 
-static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
+// Threads per workgroup of a correspondence launch. Only the single-block, K = 5 launches of mlh_gn_solve* have wide forms (knn_features_wide_kernel); every other
+// launch is 256 threads. Every workgroup of those launches runs the Gauss-Newton prologue, so what counts is workgroups per compute unit: a launch goes wide when
+// its 256-thread grid (tiles256) would put more than one workgroup on a compute unit of the solver's stream (caps.cu_solver: the device's, or the CU mask's), and
+// stays narrow otherwise -- wider workgroups would only leave compute units without work. KNN_WG_WIDE is the measured choice (profiles/r08_knn_workgroup_width.txt);
+// MLH_KNN_WG_THREADS in the environment at mlh_create pins the width of the launches that have wide forms (tests, A/B runs).
+constexpr int KNN_WG_WIDE = 1024;
+static int knn_wg_threads_for(const mlh_ctx *ctx, bool has_wide_form, int tiles256)
+{
+    if (!has_wide_form) return TPB;
+    if (ctx->knn_wg_override) return ctx->knn_wg_override;
+    return tiles256 > ctx->caps.cu_solver ? KNN_WG_WIDE : TPB;
+}
+
+static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg = nullptr)
 {
     // a solve whose last iteration is still a set of tile records (mlh_ctx::gn_pending): any launch that writes records -- other than the chained successor's first,
     // which consumes them -- completes that solve first
@@ -1286,6 +1220,17 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         P.knn_lanes = both ? (lanes[0] == lanes[1] ? lanes[0] : 0) : lanes[(a.kind_mask & 1) ? 0 : 1];
         if (P.knn_lanes == 32) P.knn_lanes = 0;      // (32 lanes per query exist in the per-kind kernels only)
     }
+    int wg = TPB;
+    {
+        // (the launches match_launch sends through MLH_KNN_LAUNCH_GN, on one rank)
+        const bool prologue_or_warm = a.gn_iter >= 1 || a.pre_final || a.warm;
+        const bool sharded = ctx->shard_lo || ctx->shard_hi || ctx->own_mod > 1;
+        const bool has_wide_form = prologue_or_warm && P.n_blocks == 1 && kmax == 5 && !a.gn_blocks && !a.m_dev && !sharded;
+        int tiles256 = 0;
+        for (int k = 0; k < 2; ++k) if ((a.kind_mask & (1 << k)) && ctx->feat[k].m > 0) tiles256 += (ctx->feat[k].m + TPB / lanes[k] - 1) / (TPB / lanes[k]);
+        wg = knn_wg_threads_for(ctx, has_wide_form, tiles256);
+    }
+    if (knn_wg) *knn_wg = wg;
     for (int k = 0; k < 2; ++k) {
         KindP &K = P.k[k];
         if (!(a.kind_mask & (1 << k))) continue;
@@ -1314,7 +1259,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
         K.J_out = a.dense ? fs.J.as<double>() : nullptr;
         K.m = fs.m;
         K.lanes = lanes[k];
-        K.tiles_a = (fs.m + TPB / K.lanes - 1) / (TPB / K.lanes);
+        K.tiles_a = (fs.m + wg / K.lanes - 1) / (wg / K.lanes);
         K.tiles_b = (fs.m + TPB - 1) / TPB;
         K.nbr_stride = fs.nbr_stride;
         for (int b = 0; b <= MAX_BLOCKS; ++b) K.blk_start[b] = fs.blk_start[std::min(b, fs.n_blocks)];
@@ -1413,14 +1358,14 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P)
 }
 
 template <typename Kern>
-static void launch_timed(mlh_ctx *ctx, int kid, Kern kern, int grid, const KParams &P)
+static void launch_timed(mlh_ctx *ctx, int kid, Kern kern, int grid, const KParams &P, int block = TPB)
 {
     hipEvent_t a = nullptr, b = nullptr;
     if (prof_kernel_events(ctx, kid, &a, &b)) {
-        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(TPB), 0, ctx->stream, a, b, 0, P);   // start/stop = the dispatch's own timestamps
+        hipExtLaunchKernelGGL(kern, dim3(grid), dim3(block), 0, ctx->stream, a, b, 0, P);   // start/stop = the dispatch's own timestamps
         if (launch_check_enabled()) launch_check("correspondence / fit / linearise kernel (event-bracketed launch)");
     } else
-        MLH_LAUNCH(kern, dim3(grid), dim3(TPB), 0, ctx->stream, P);
+        MLH_LAUNCH(kern, dim3(grid), dim3(block), 0, ctx->stream, P);
 }
 
 int gn_flush_pending(mlh_ctx *ctx)
@@ -1447,14 +1392,16 @@ int gn_flush_pending(mlh_ctx *ctx)
 int match_launch(mlh_ctx *ctx, const MatchArgs &a)
 {
     KParams P;
-    int rc = fill_params(ctx, a, P);
+    int wg = TPB;
+    int rc = fill_params(ctx, a, P, &wg);
     if (rc) return rc;
-    // kernel A: correspondences (8 or 16 lanes per feature); kernel B: fit + linearise + reduce (one lane per feature)
+    // kernel A: correspondences (8 or 16 lanes per feature, wg threads per workgroup); kernel B: fit + linearise + reduce (one lane per feature)
     const int grid_a = ((P.k[0].tiles_a + P.k[1].tiles_a + 7) / 8) * 8;
     const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
     const bool mb = P.n_blocks > 1;
     bool k10 = false;
     for (int b = 0; b < P.n_blocks; ++b) k10 = k10 || P.kb[b] == 10;
+    if (wg != TPB && !((P.pre_finish || P.warm) && !mb && !k10 && !a.gn_blocks && !P.m_dev)) return fail(ctx, MLH_ERR_STATE, "a wide correspondence grid for a launch without a wide kernel");
     if (P.m_dev) {
         // the feature counts are on the device only (mlh_downsample_scan2map): per-kind lanes, both kinds, one block, K = 5, records only
         if (mb || k10 || P.finish != TAIL_RECORDS || P.pre_finish || (a.kind_mask & 3) != 3) return fail(ctx, MLH_ERR_UNSUPPORTED, "device-side feature counts: one block, N_NEIGH 5, both kinds, records only");
@@ -1477,6 +1424,17 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
             else if (P.pre_finish) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, false, false, 1, false>, grid_a, P); \
             else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, false, false, 0, true>, grid_a, P); \
         } while (0)
+#define MLH_KNN_LAUNCH_GN_WIDE(W_, G_) do { \
+            if (P.pre_finish == PRE_SOLVE) launch_timed(ctx, MLH_K_KNN_FIRST, knn_features_wide_kernel<W_, G_, 2, false>, grid_a, P, W_); \
+            else if (P.pre_finish && P.warm) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, true>, grid_a, P, W_); \
+            else if (P.pre_finish) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, false>, grid_a, P, W_); \
+            else launch_timed(ctx, MLH_K_KNN, knn_features_wide_kernel<W_, G_, 0, true>, grid_a, P, W_); \
+        } while (0)
+#define MLH_KNN_LAUNCH_GN_W(G_) do { \
+            if (wg == 1024) MLH_KNN_LAUNCH_GN_WIDE(1024, G_); \
+            else if (wg == 512) MLH_KNN_LAUNCH_GN_WIDE(512, G_); \
+            else MLH_KNN_LAUNCH_GN(G_); \
+        } while (0)
 #define MLH_KNN_LAUNCH_GN_MB(G_) do { \
             if (k10) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, true, true, 1, true>, grid_a, P); \
             else launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, true, false, 1, true>, grid_a, P); \
@@ -1489,13 +1447,16 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
             else MLH_KNN_LAUNCH_GN_MB(8);
         }
         else if (P.pre_finish || P.warm) {
-            if (P.knn_lanes == 0) MLH_KNN_LAUNCH_GN(0);
-            else if (P.knn_lanes == 16) MLH_KNN_LAUNCH_GN(16);
-            else MLH_KNN_LAUNCH_GN(8);
+            if (P.knn_lanes == 0) MLH_KNN_LAUNCH_GN_W(0);
+            else if (P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_W(16);
+            else MLH_KNN_LAUNCH_GN_W(8);
+            ctx->knn_wg_last = wg;
         }
         else if (P.knn_lanes == 0) MLH_KNN_LAUNCH(0);
         else if (P.knn_lanes == 16) MLH_KNN_LAUNCH(16);
         else MLH_KNN_LAUNCH(8);
+#undef MLH_KNN_LAUNCH_GN_W
+#undef MLH_KNN_LAUNCH_GN_WIDE
 #undef MLH_KNN_LAUNCH_GN
 #undef MLH_KNN_LAUNCH_GN_MB
 #undef MLH_KNN_LAUNCH
@@ -1622,3 +1583,6 @@ int knn_launch(mlh_ctx *ctx, int kind, const float *q_host, int nq, int32_t *idx
 }
 
 }  // namespace mlh
+
+// For the tests of the width rule (not part of the C-ABI header): threads per workgroup of the context's last correspondence launch that has wide forms, 0 before any
+extern "C" int mlh_debug_knn_wg_threads(mlh_ctx *ctx) { return ctx ? ctx->knn_wg_last : 0; }

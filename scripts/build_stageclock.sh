@@ -3,7 +3,9 @@
 set -e
 cd "$(dirname "$0")/../m-loam_amd/csrc"
 mkdir -p ../lib/dbg
-for f in capi grid match solver extract comm select voxel voxelgrid odom track frontend segment stdsort; do
+# (every translation unit of the product library: m-loam_amd/build.py's SOURCES)
+SOURCES=$(python3 -c "import importlib.util as u; s = u.spec_from_file_location('b', '../build.py'); m = u.module_from_spec(s); s.loader.exec_module(m); print(' '.join(x[:-4] for x in m.SOURCES))")
+for f in $SOURCES; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -ffp-contract=off -DMLH_STAGE_CLOCK -I../../include -c $f.hip -o ../lib/dbg/$f.o &
 done
 wait
