@@ -921,6 +921,45 @@ int mlh_global_map_release(mlh_ctx *ctx);
  * when kf_radius < 0) */
 int mlh_global_map_select(const float *positions_xyz, int n, const float center[3], float kf_radius, float kf_res, int32_t *ids_out, int32_t *n_ids);
 
+/* ---------------------------------------------------------------- (f15) loop-corrected poses into the keyframe store
+ * What consumes the poses of (f14): the mapper receives every keyframe's corrected pose on /loop_info (published by mloam_loop/src/pose_graph.cpp:873-910, taken
+ * in at lidar_mapper_keyframe.cpp:197-201, 1082-1095) and calls updateKeyframe() (cpp:685-688) -- which in the reference is a stub that prints "received loop info,
+ * need to update all keyframes" under "TODO: using loop info to update keyframes". There is nothing to reproduce; every rule here is CHOSEN:
+ *   CHOSEN replacement: keys first_key .. first_key + n - 1 of the store of (f5) take poses[7 i ..] = [t, q(xyzw)] as given (not normalised); with covs != NULL
+ *     also covs[36 i ..] (6 x 6 row-major, as mlh_keyframe_save), with covs == NULL the stored covariance stays -- the loop side carries no new one
+ *     (publishLoopInfo sends the mapper's own cov_ back);
+ *   CHOSEN position: the f32 position the radius searches read is recomputed as float(t), as mlh_keyframe_save computes it;
+ *   CHOSEN "changed": a keyframe counts as changed when any of its 7 pose doubles -- or, with covs, any of its 36 covariance doubles -- differs BITWISE from what
+ *     was stored (mlh_pg_optimize leaves the keyframes before its first looped index bit-identical, so they stay cached);
+ *   CHOSEN drift tail: with drift_tail != 0 and a changed LAST key of the range, drift = new(last) * old(last)^-1 and every key beyond the range gets
+ *     pose <- drift * pose (Pose::operator* and Pose::inverse as csrc/pg_host.hpp restates them, on the host): what optimizePoseGraph does to the keyframes behind
+ *     cur_index (pose_graph.cpp:630-641), here for keyframes the mapper saved after the loop side's snapshot. Those keys count as changed. drift_out (may be NULL)
+ *     <- the drift, or the identity when none was applied. The caller left-multiplies it onto its own pose_wmap_wodom / pose_wmap_curr;
+ *   CHOSEN invalidation: with *n_changed > 0 every cached entry of a changed keyframe is erased (its slot recycled, the order of the remaining entries kept: the
+ *     erase of extractSurroundingKeyFrames, cpp:274-293, with "changed" in the place of "left the radius") and both pre-filter and both filtered local-map clouds are
+ *     emptied exactly as mlh_local_map_clear empties them. The next mlh_local_map_assemble rebuilds: it re-associates the erased keyframes from the store in its one
+ *     batch, appended in search order behind the survivors. With *n_changed == 0 nothing is touched: the filtered clouds stay and the next assemble returns
+ *     rebuilt = 0. CHOSEN: changed entries are not re-associated in place (after a real correction nearly every cached keyframe has changed, and it would need a
+ *     second definition of the cache order);
+ *   CHOSEN the global map: the clouds of (f7) are left as they are -- STALE until the next mlh_global_map_assemble, which transforms every selected keyframe with
+ *     its stored pose on every call anyway.
+ * mlh_keyframes_update_poses: the update from host arrays. Host memory only: no launch, no host wait. MLH_ERR_INVALID, with nothing changed, for a range outside
+ *   the store, n <= 0, NULL poses or n_changed, a non-finite pose (what mlh_keyframe_save refuses), a non-finite covariance. Beside a solve submitted with mlh_*_begin
+ *   the rule of mlh_local_map_assemble applies (the call touches nothing a solve reads).
+ * mlh_keyframes_update_from_pose_graph: the same update with covs = NULL and the poses taken from pg_ctx's records in HBM (stride 176, pose at offset 0:
+ *   mlh_pg_device_poses); pose-graph index first_index + i -> store key first_key + i; n < 0: every pose-graph keyframe from first_index. ONE strided
+ *   device-to-pinned-host copy of 56 bytes per keyframe on ctx's stream -- ordered behind pg_ctx's stream by an event when the contexts differ (same device, as
+ *   mlh_fuse_add_scan_from) --, ONE host wait, then the host rules. The call returns only after the copy has completed, so no reader event outlives it; the caller
+ *   holds whatever lock guards pg_ctx, as publishLoopInfo holds m_keyframelist. MLH_ERR_INVALID, with nothing changed, for a range outside either side or an empty
+ *   pose graph; MLH_ERR_STATE while pg_ctx has an uncollected solve, MLH_ERR_UNSUPPORTED when pg_ctx is under a communicator (as (f14)) or on another device.
+ * mlh_keyframe_poses: what the store holds for keys first_key .. first_key + n - 1: poses (7 n), covs (36 n), positions (3 n, f32); each may be NULL. Host memory
+ *   only, no wait. MLH_ERR_INVALID for a range outside the store (n == 0 is an empty read). */
+int mlh_keyframes_update_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, const double *poses /* 7 n */, const double *covs /* 36 n or NULL */, int drift_tail,
+                               int32_t *n_changed, double drift_out[7] /* may be NULL */);
+int mlh_keyframes_update_from_pose_graph(mlh_ctx *ctx, mlh_ctx *pg_ctx /* may equal ctx */, int32_t first_index, int32_t first_key,
+                                         int32_t n /* < 0: all pg keyframes from first_index */, int drift_tail, int32_t *n_changed, double drift_out[7]);
+int mlh_keyframe_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, double *poses, double *covs, float *positions /* each may be NULL */);
+
 /* ---------------------------------------------------------------- (f8) the odometry's sliding window on the device
  * The estimator keeps, per LiDAR and kind, a CircularBuffer<PointICloud> of WINDOW_SIZE + 1 slots (surf_points_stack_[n], corner_points_stack_[n]); before every
  * optimizeMap it thins the new scan's features into slot cir_buf_cnt_ (estimator/src/estimator/estimator.cpp:485-496), slides the window (slideWindow,

@@ -360,6 +360,9 @@ def load_library():
     lib.mlh_global_map_cloud.argtypes = [vp, ci, ci, C.POINTER(vp), i32p]
     lib.mlh_global_map_release.argtypes = [vp]
     lib.mlh_global_map_select.argtypes = [vp, ci, vp, cf, cf, vp, i32p]
+    lib.mlh_keyframes_update_poses.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, ci, i32p, vp]
+    lib.mlh_keyframes_update_from_pose_graph.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, ci, i32p, vp]
+    lib.mlh_keyframe_poses.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
     i64p = C.POINTER(C.c_int64)
     lib.mlh_window_map_opts_default.argtypes = [C.POINTER(WindowMapOpts), ci, ci, ci]
     lib.mlh_window_map_opts_default.restype = None
@@ -509,6 +512,7 @@ EXPORTED_SYMBOLS = [
     "mlh_pose_plus", "mlh_eval_degeneracy",
     "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
     "mlh_keyframe_attach_outlier", "mlh_global_map_opts_default", "mlh_global_map_assemble", "mlh_global_map_cloud", "mlh_global_map_release", "mlh_global_map_select",
+    "mlh_keyframes_update_poses", "mlh_keyframes_update_from_pose_graph", "mlh_keyframe_poses",
     "mlh_window_map_opts_default", "mlh_window_reset", "mlh_window_set", "mlh_window_set_from_scan", "mlh_window_slide", "mlh_window_cloud", "mlh_window_info",
     "mlh_window_build_local_map", "mlh_window_map_cloud",
     "mlh_window_prior_set", "mlh_window_prior_get", "mlh_window_prior_clear", "mlh_window_prior_evaluate", "mlh_window_ext_prior_set", "mlh_window_marginalize",
@@ -1399,6 +1403,31 @@ class Context:
 
     def global_map_release(self):
         self._ck(self.lib.mlh_global_map_release(self.h))
+
+    # ---- loop-corrected poses into the keyframe store (updateKeyframe, a stub in the reference)
+    def keyframes_update_poses(self, first_key, poses, covs=None, drift_tail=False) -> dict:
+        """keys first_key .. take poses (n, 7) [t, q(xyzw)] and, when given, covs (n, 6, 6) -> dict(n_changed, drift (7,)) (mlh_keyframes_update_poses)"""
+        p = np.ascontiguousarray(poses, np.float64).reshape(-1, 7)
+        c = None if covs is None else np.ascontiguousarray(covs, np.float64).reshape(-1, 36)
+        assert c is None or len(c) == len(p), "one covariance per pose"
+        nc, drift = C.c_int32(0), np.zeros(7)
+        self._ck(self.lib.mlh_keyframes_update_poses(self.h, int(first_key), len(p), _p(p) if len(p) else None, _p(c), int(bool(drift_tail)), C.byref(nc), _p(drift)))
+        return dict(n_changed=nc.value, drift=drift)
+
+    def keyframes_update_from_pose_graph(self, pg_ctx=None, first_index=0, first_key=0, n=-1, drift_tail=False) -> dict:
+        """the same update with the poses of pg_ctx's pose-graph records in HBM (None: this context's); n < 0: every pose-graph keyframe from first_index
+        -> dict(n_changed, drift (7,)) (mlh_keyframes_update_from_pose_graph)"""
+        src = self if pg_ctx is None else pg_ctx
+        nc, drift = C.c_int32(0), np.zeros(7)
+        self._ck(self.lib.mlh_keyframes_update_from_pose_graph(self.h, src.h, int(first_index), int(first_key), int(n), int(bool(drift_tail)), C.byref(nc), _p(drift)))
+        return dict(n_changed=nc.value, drift=drift)
+
+    def keyframe_poses(self, first_key=0, n=None) -> dict:
+        """what the store holds -> dict(poses (n, 7), covs (n, 6, 6), positions (n, 3) float32) (mlh_keyframe_poses)"""
+        n = self.local_map_info()["n_keyframes"] - first_key if n is None else n
+        poses, covs, pos = np.zeros((max(n, 0), 7)), np.zeros((max(n, 0), 6, 6)), np.zeros((max(n, 0), 3), np.float32)
+        self._ck(self.lib.mlh_keyframe_poses(self.h, int(first_key), int(n), _p(poses), _p(covs), _p(pos)))
+        return dict(poses=poses, covs=covs, positions=pos)
 
     # ---- the odometry's sliding window + its local maps (surf / corner_points_stack_, slideWindow, buildLocalMap / buildCalibMap on the device)
     def window_reset(self, n_lidar, window_size):

@@ -371,6 +371,7 @@ struct KfStore {
     std::vector<unsigned char> htab;
     PinnedBuf h_pin;             // landing place of the read-backs (KF_PIN_INTS ints: [0..31] the local map's, [32..63] the global map's)
     static constexpr int KF_PIN_INTS = 64;
+    PinnedBuf h_poses;           // landing place of the pose graph's poses on their way into `keys` (mlh_keyframes_update_from_pose_graph: 7 doubles per keyframe)
     // the global map (pubGlobalMap / saveGlobalMap, cpp:780-919): clouds and lengths of its own; its per-call state words travel in `tab`, never in `dstate`
     DevBuf gpre[2], gflt[2];     // pre-filter and filtered global clouds, 48-byte records
     int gpre_n[2] = {0, 0}, gflt_n[2] = {0, 0};

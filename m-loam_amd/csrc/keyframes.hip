@@ -28,6 +28,10 @@
 //                        (popcounts of the ballots), the clouds' exact bounds folded once per workgroup;
 //   voxel_filter_run x 1 or 2   the covariance filter per output cloud, bounds known.
 // Nothing of it touches the local map's state: its state words travel in the per-call table, its clouds and pinned landing words are its own.
+//
+// updateKeyframe (cpp:685-688, a stub in the reference) -- loop-corrected poses into the store (keyframes_update_run, keyframes_update_from_pg_run) -- has no
+// kernel of its own: the poses, the "changed" test, the drift and the cache's erase are host work (kf_update_host.hpp); the pose graph's records reach the host by
+// one strided copy; the re-association a correction causes is the next local_map_assemble_run's ordinary batch over the erased keyframes.
 #include "ctx.hpp"
 #include <algorithm>
 #include <cfloat>
@@ -35,8 +39,10 @@
 #include <cmath>
 #include <array>
 #include <cstddef>
+#include <string>
 #include "bounds_dev.hpp"
 #include "dev_math.hpp"
+#include "kf_update_host.hpp"
 #include "uct_dev.hpp"
 
 namespace mlh {
@@ -320,6 +326,7 @@ void keyframes_release(mlh_ctx *ctx)
     for (int k = 0; k < 2; ++k) { K.pre[k].release(); K.flt[k].release(); K.pre_n[k] = K.flt_n[k] = 0; }
     global_map_release_run(ctx);
     std::vector<unsigned char>().swap(K.htab);
+    K.h_poses.release();
 }
 
 // one cloud appended to the store (which has room for it): device float4 records (`packed`), or a caller's records packed on the way in
@@ -402,6 +409,70 @@ int local_map_clear_run(mlh_ctx *ctx)
     // clearCloud (cpp:921-927): the four map clouds only; the cache and the store stay
     KfStore &K = ctx->kf;
     for (int k = 0; k < 2; ++k) K.pre_n[k] = K.flt_n[k] = 0;
+    return MLH_OK;
+}
+
+// (f15) mlh_keyframes_update_poses: host memory only -- the rules are kf_update_host.hpp's; what a change costs is paid by the next mlh_local_map_assemble, whose
+// kf_uct_kernel chain re-associates the erased keyframes in one batch
+int keyframes_update_run(mlh_ctx *ctx, const char *entry, int32_t first_key, int32_t n, const double *poses, const double *covs, int drift_tail, int32_t *n_changed,
+                         double *drift_out)
+{
+    KfStore &K = ctx->kf;
+    if (!n_changed) return fail(ctx, MLH_ERR_INVALID, (std::string(entry) + ": null n_changed").c_str());
+    if (const char *f = kf_update_fault(K.keys.size(), first_key, n, poses, covs)) return fail(ctx, MLH_ERR_INVALID, (std::string(entry) + ": " + f).c_str());
+    std::vector<char> changed;
+    double drift[7];
+    *n_changed = kf_update_apply(K.keys, first_key, n, poses, covs, drift_tail, changed, drift);
+    if (drift_out) std::memcpy(drift_out, drift, sizeof(drift));
+    if (*n_changed > 0) {
+        kf_erase_changed(K.entries, K.free_slots, changed);
+        return local_map_clear_run(ctx);       // the next assemble rebuilds; the global clouds stay as they are until the next mlh_global_map_assemble
+    }
+    return MLH_OK;
+}
+
+// (f15) mlh_keyframes_update_from_pose_graph: the poses of pg's records (stride sizeof(PgKeyframe), pose at offset 0) through ONE strided copy into pinned memory
+// on ctx's stream -- behind pg's work so far by an event when the contexts differ (as mlh_fuse_add_scan_from) --, one host wait, then the host rules
+int keyframes_update_from_pg_run(mlh_ctx *ctx, mlh_ctx *pg, int32_t first_index, int32_t first_key, int32_t n, int drift_tail, int32_t *n_changed, double *drift_out)
+{
+    const char *entry = "mlh_keyframes_update_from_pose_graph";
+    if (ctx->device != pg->device) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_keyframes_update_from_pose_graph: both contexts must be on the same device");
+    { const int rc = loop_process_gate(pg, entry); if (rc) return pg == ctx ? rc : fail(ctx, rc, mlh_last_error(pg)); }
+    const PgStore &G = pg->pg;
+    KfStore &K = ctx->kf;
+    if (!n_changed) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph: null n_changed");
+    if (G.count == 0) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph: the pose graph is empty");
+    if (first_index < 0 || first_index >= G.count) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph: first_index names no pose-graph keyframe");
+    if (n < 0) n = G.count - first_index;
+    if (n == 0 || (long long)first_index + n > (long long)G.count)
+        return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph: the range lies outside the pose graph");
+    if (first_key < 0 || size_t(first_key) + size_t(n) > K.keys.size())
+        return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph: the range lies outside the store");
+    static_assert(offsetof(PgKeyframe, pose) == 0, "the pose is the record's head");
+    const size_t row = sizeof(double) * 7;
+    MLH_HIP(ctx, K.h_poses.ensure(row * size_t(n), row * size_t(n) / 4));       // (no copy of an earlier call is in flight: every call waits for its own)
+    hipStream_t st = ctx->stream;
+    if (pg != ctx) {
+        if (!ctx->ev_handover) MLH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_handover, hipEventDisableTiming));
+        MLH_HIP(ctx, hipEventRecord(ctx->ev_handover, pg->stream));
+        MLH_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_handover, 0));
+    }
+    MLH_HIP(ctx, hipMemcpy2DAsync(K.h_poses.p, row, G.kf.as<PgKeyframe>() + first_index, sizeof(PgKeyframe), row, size_t(n), hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, stream_wait_spin(ctx));     // the copy has completed when the call returns: no reader event has to outlive it
+    { const int rc = device_error_check(ctx); if (rc) return rc; }
+    return keyframes_update_run(ctx, entry, first_key, n, K.h_poses.as<double>(), nullptr, drift_tail, n_changed, drift_out);
+}
+
+int keyframe_poses_run(mlh_ctx *ctx, int32_t first_key, int32_t n, double *poses, double *covs, float *positions)
+{
+    const KfStore &K = ctx->kf;
+    if (first_key < 0 || n < 0 || size_t(first_key) + size_t(n) > K.keys.size()) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframe_poses: the range lies outside the store");
+    for (size_t i = 0; i < size_t(n); ++i) {
+        const KfStore::Key &key = K.keys[size_t(first_key) + i];
+        if (poses) std::memcpy(poses + 7 * i, key.pose, sizeof(key.pose));
+        if (covs) std::memcpy(covs + 36 * i, key.cov, sizeof(key.cov));
+        if (positions) std::memcpy(positions + 3 * i, key.pos, sizeof(key.pos));
+    }
     return MLH_OK;
 }
 
@@ -833,6 +904,28 @@ int mlh_local_map_clear(mlh_ctx *ctx)
 {
     if (!ctx) return MLH_ERR_INVALID;
     return local_map_clear_run(ctx);
+}
+
+int mlh_keyframes_update_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, const double *poses, const double *covs, int drift_tail, int32_t *n_changed,
+                               double drift_out[7])
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return keyframes_update_run(ctx, "mlh_keyframes_update_poses", first_key, n, poses, covs, drift_tail, n_changed, drift_out);
+}
+
+int mlh_keyframes_update_from_pose_graph(mlh_ctx *ctx, mlh_ctx *pg_ctx, int32_t first_index, int32_t first_key, int32_t n, int drift_tail, int32_t *n_changed,
+                                         double drift_out[7])
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (!pg_ctx) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph: null pose-graph context");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return keyframes_update_from_pg_run(ctx, pg_ctx, first_index, first_key, n, drift_tail, n_changed, drift_out);
+}
+
+int mlh_keyframe_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, double *poses, double *covs, float *positions)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    return keyframe_poses_run(ctx, first_key, n, poses, covs, positions);
 }
 
 int mlh_local_map_cloud(mlh_ctx *ctx, int kind, int filtered, const void **device_points, int32_t *n)

@@ -2047,6 +2047,22 @@ public:
         for (const auto &h : hit) ids.push_back(h.second);
         return ids;
     }
+    // loop-corrected poses for the first n keyframes (KeyframeMap::updateKeyframe): poses = 7 n doubles [t, q(xyzw)], positions = 3 n floats as the store holds
+    // them; cov_ stays. The last keyframe's pose is what the next saveKeyframe test measures against.
+    void updatePoses(const double *poses, const float *positions, size_t n)
+    {
+        n = std::min(n, pose_keyframes_6d.size());
+        for (size_t i = 0; i < n; ++i) {
+            pose_keyframes_6d[i].fromParam(poses + 7 * i);
+            PointI &p = pose_keyframes_3d.points[i];
+            p.x = positions[3 * i]; p.y = positions[3 * i + 1]; p.z = positions[3 * i + 2];
+        }
+        if (n > 0 && n == pose_keyframes_6d.size()) {
+            const PointI &p = pose_keyframes_3d.points[n - 1];
+            prev_[0] = p.x; prev_[1] = p.y; prev_[2] = p.z;
+            q_prev_ = pose_keyframes_6d[n - 1].q_;
+        }
+    }
     PointICloud pose_keyframes_3d;
     std::vector<Pose> pose_keyframes_6d;
 private:
@@ -2058,6 +2074,8 @@ private:
 // clearCloud (cpp:921-927) under the reference's names; pubGlobalMap (cpp:796-849) and saveGlobalMap (cpp:853-901) build THE map from the same store
 // (mlh_global_map_*) and return it as device clouds, fetchCloud copies one to the host. The map clouds stay on the device; surfMapDevice / cornerMapDevice hand them to mlh_map_set_pair(_overlapped)
 // (48-byte PointIWithCov records, MLH_MEM_DEVICE). Shares the Device (and its stream) with the solve that reads the maps.
+template <typename PoseT> class PoseGraph;
+
 class KeyframeMap {
 public:
     KeyframeMap(Device &dev, KeyframePolicy &kf, bool with_ua_flag = false) : dev_(dev), kf_(kf)
@@ -2194,6 +2212,33 @@ public:
         return rebuilt != 0;
     }
     void clearCloud() { dev_.check(mlh_local_map_clear(dev_.ctx())); }
+    // updateKeyframe() (cpp:685-688: in the reference a stub under "TODO: using loop info to update keyframes"; include/mloam_hip.h (f15) has every rule chosen
+    // here) over a /loop_info-shaped list: loop_poses[i] is keyframe i's corrected pose (cpp:197-201 receives them, pose_graph.cpp:873-910 publishes them). The
+    // store and the KeyframePolicy take the poses; keyframes the mapper saved after the loop side's snapshot get the drift of the list's last keyframe; changed
+    // keyframes leave the cache and the local map is rebuilt by the next extractSurroundingKeyFrames. Returns the drift (the identity when the list's last
+    // keyframe did not move): the caller left-multiplies it onto pose_wmap_wodom / pose_wmap_curr. lastChanged() = the number of keyframes that changed.
+    Pose updateKeyframe(const std::vector<Pose> &loop_poses)
+    {
+        if (loop_poses.empty()) return Pose();
+        std::vector<double> p(7 * loop_poses.size());
+        for (size_t i = 0; i < loop_poses.size(); ++i) loop_poses[i].toParam(p.data() + 7 * i);
+        double drift[7];
+        dev_.check(mlh_keyframes_update_poses(dev_.ctx(), 0, int32_t(loop_poses.size()), p.data(), nullptr, 1, &n_changed_, drift));
+        return updated(drift);
+    }
+    // the same over the pose graph's records in HBM (pose-graph index i = store key i), without the host list: one strided copy and one host wait. The caller
+    // holds whatever guards `pg` (as publishLoopInfo holds m_keyframelist); pg may live on this Device or on one of its own on the same GPU.
+    template <typename PoseT> Pose updateKeyframe(PoseGraph<PoseT> &pg)
+    {
+        int32_t n_kf = 0;
+        dev_.check(mlh_local_map_info(dev_.ctx(), &n_kf, nullptr, nullptr, nullptr));
+        const int32_t n = std::min<int32_t>(n_kf, pg.getKeyFrameSize());
+        if (n <= 0) return Pose();
+        double drift[7];
+        dev_.check(mlh_keyframes_update_from_pose_graph(dev_.ctx(), pg.device().ctx(), 0, 0, n, 1, &n_changed_, drift));
+        return updated(drift);
+    }
+    int lastChanged() const { return n_changed_; }
     // laser_cloud_{surf,corner}_from_map_cov_ds in HBM
     const void *surfMapDevice(int32_t *n) const { return cloud(MLH_SURF, 1, n); }
     const void *cornerMapDevice(int32_t *n) const { return cloud(MLH_CORNER, 1, n); }
@@ -2202,6 +2247,19 @@ public:
     KeyframePolicy &policy() { return kf_; }
 private:
     static std::array<double, 7> param(const Pose &p) { std::array<double, 7> a; p.toParam(a.data()); return a; }
+    // the store's poses into the KeyframePolicy; the drift as a Pose
+    Pose updated(const double drift[7])
+    {
+        int32_t n_kf = 0;
+        dev_.check(mlh_local_map_info(dev_.ctx(), &n_kf, nullptr, nullptr, nullptr));
+        std::vector<double> p(7 * size_t(n_kf) + 1);
+        std::vector<float> pos(3 * size_t(n_kf) + 1);
+        dev_.check(mlh_keyframe_poses(dev_.ctx(), 0, n_kf, p.data(), nullptr, pos.data()));
+        kf_.updatePoses(p.data(), pos.data(), size_t(n_kf));
+        Pose d;
+        d.fromParam(drift);
+        return d;
+    }
     void packExt(std::vector<double> &e, std::vector<double> &c) const
     {
         for (const Pose &p : pose_ext_) { const auto a = param(p); e.insert(e.end(), a.begin(), a.end()); c.insert(c.end(), p.cov_.begin(), p.cov_.end()); }
@@ -2230,6 +2288,7 @@ private:
     std::vector<Pose> pose_ext_;
     std::vector<int32_t> ids_, gids_;
     int32_t n_ds_[2] = {0, 0};
+    int32_t n_changed_ = 0;
 };
 
 // The mapper's frame loop, pipelined, with the precondition of the overlap checked per frame instead of assumed:
@@ -2313,6 +2372,18 @@ public:
         in_flight_ = false;
         closeFrame(p, true);
         return p;
+    }
+    // The hook where the reference drains loop_info_buf and calls updateKeyframe() (cpp:1082-1095), for the device KeyframeMap: call it BETWEEN frames with no solve
+    // in flight (before the first process(), or after finish()). `update` is one of km's updateKeyframe overloads bound by the caller; its drift is
+    // left-multiplied onto pose_wmap_wodom, and when a keyframe changed the local map is rebuilt around drift * pose_wmap_curr (the last frame's pose). Returns the drift.
+    template <class Update> Pose applyLoopInfo(Update update, const Pose &pose_wmap_curr)
+    {
+        if (!km_) throw Error("PipelinedMapper::applyLoopInfo needs the device KeyframeMap");
+        if (in_flight_) throw Error("PipelinedMapper::applyLoopInfo: a frame is in flight (call finish() first)");
+        const Pose drift = update(*km_);
+        wmap_wodom_ = poseMul(drift, wmap_wodom_);
+        if (km_->lastChanged() > 0) rebuild(poseMul(drift, pose_wmap_curr));
+        return drift;
     }
     const PointICovCloud &surfMap() const { return surf_map_; }
     const PointICovCloud &cornerMap() const { return corner_map_; }
@@ -2655,6 +2726,7 @@ public:
     bool pgoFlag() const { return pgo_flag_; }
     void clearPgoFlag() { pgo_flag_ = false; }
     const mlh_pg_result &lastResult() const { return last_; }          // the solver summary, M, L and pose_drift of the last pass
+    Device &device() { return dev_; }                                  // for the consumer of the corrected poses (KeyframeMap::updateKeyframe)
 private:
     mlh_pg_info_t info() const { mlh_pg_info_t i; dev_.check(mlh_pg_info(dev_.ctx(), &i)); return i; }
     Device &dev_;
