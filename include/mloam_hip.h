@@ -960,6 +960,76 @@ int mlh_keyframes_update_from_pose_graph(mlh_ctx *ctx, mlh_ctx *pg_ctx /* may eq
                                          int32_t n /* < 0: all pg keyframes from first_index */, int drift_tail, int32_t *n_changed, double drift_out[7]);
 int mlh_keyframe_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, double *poses, double *covs, float *positions /* each may be NULL */);
 
+/* ---------------------------------------------------------------- (f16) the initial extrinsic calibration, on the device
+ * InitialExtrinsics (estimator/src/initial/initial_extrinsics.h:34-40, initial_extrinsics.cpp:20-22, 26-116, 119-241, 243-309) as Estimator::process drives it while
+ * ESTIMATE_EXTRINSIC == 2 (estimator/src/estimator/estimator.cpp:437-467): the relative poses of one mlh_track_cloud per LiDAR go to mlh_initext_add_pose, and
+ * mlh_initext_calibrate solves the hand-eye problem for every LiDAR that has no rotation yet; what it returns seeds the extrinsics that the window solve of
+ * (f8)-(f10) refines. A context keeps in HBM: Q_ (n_lidar x 1200 x 4 f64, row-major), v_pose_ (300 x n_lidar x 7 f64, each pose [t, q(xyzw)]) and one result
+ * record per LiDAR (calib_ext_'s q and t, the singular values, the flags); on the host the options, the heap pq_pose_ (std::priority_queue under the reference's own
+ * comparator), pose_laser_add_, cov_rot_state_ / cov_pos_state_ and a mirror of calib_ext_. saveStatistics, decomposeE, calibTimeDelay (empty in the reference),
+ * evalCalib / computeMeanPose stay with the caller. Eigen is not available to this project: csrc/initext_host.hpp lists what is restated from memory of Eigen 3.3.
+ * Quaternions of this section are (x, y, z, w), Eigen's coefficient order.
+ * Reproduced (csrc/initext_host.hpp has the list with the lines): rotCmp reads LiDAR 0's w, not idx_ref's; Q_'s block is written only by a rotation stage and only
+ *   for the set last accepted; a rotation stage without a new accepted set rewrites that block with the Huber weight of the moment; b and w are not weighted while A
+ *   and G are; rot_cov(1) is the second-smallest singular value; the sign rule `if (x[0] < 0) x = -x` acts on the quaternion's x component; a heap smaller than
+ *   window_size returns before anything is written.
+ * Chosen: abs is the double overload; mlh_initext_reset also empties the heap (the reference's clearState forgets to); non-finite poses are refused; the 4 x 4 block
+ *   is computed on the host (so that its bits do not depend on the device's atan2) and travels as a kernel argument; a LiDAR list may not name idx_ref.
+ * mlh_initext_opts_default: n_lidar 2, idx_ref 0, planar_movement 0, window_size 4, n_pose 300 (cpp:22), eps_r 0.05, eps_t 0.1 (cpp:20-21), rot_cov_thre 0 (= the
+ *   rule of cpp:58: 0.05 planar, 0.25 otherwise), QBL the identity, TBL zero.
+ * mlh_initext_reset = clearState + setParameter: validates the options (NULL: the defaults; MLH_ERR_INVALID outside 1 <= n_lidar <= 8, 0 <= idx_ref < n_lidar,
+ *   1 <= window_size, 1 <= n_pose <= 300, finite positive eps and finite rot_cov_thre >= 0, finite QBL / TBL with non-zero quaternions), sizes and clears the state.
+ *   The only call of this section that allocates; every other one returns MLH_ERR_STATE before it.
+ * mlh_initext_add_pose = addPose (cpp:79-102): checkScrewMotion of every LiDAR against idx_ref on the host; an accepted set takes slot pq_pose_.size() or, once
+ *   n_pose sets are held, the slot of the heap's top, and goes to HBM as the argument of one small launch (no copy, no host wait). *accepted <- 0 / 1.
+ * mlh_initext_calibrate = for each of the n listed LiDARs (distinct, not idx_ref), with stages MLH_INITEXT_ROT: calibExRotation (cpp:119-241); MLH_INITEXT_TRANS:
+ *   calibExTranslation (cpp:243-309) with the rotation calib_ext_ holds; both: the call site's nesting -- the translation runs only where this call's rotation
+ *   converged, the decision rot_cov(1) > rot_cov_thre_ being taken on the device. ONE launch (one workgroup of 256 per LiDAR), ONE device-to-pinned copy of the
+ *   records, ONE host wait, whatever n. Singular values by one-sided (Hestenes) Jacobi on the tall matrices themselves (csrc/svd_dev.hpp), fixed summation order, no
+ *   atomics: two runs give the same bits. out[i] describes lidars[i]. While the heap holds fewer than window_size sets a rotation stage does nothing (rot_ran 0; with
+ *   nothing else to do the call launches nothing). cov_rot_state_ / cov_pos_state_ follow setCovRotation / setCovTranslation.
+ *   MLH_ERR_INVALID, with nothing changed, for a bad list or stages.
+ * mlh_initext_info: counts, flags, bytes, allocations since the context was made, launches and host waits of the last add_pose / calibrate.
+ * mlh_initext_read_state (tests): Q (n_lidar x 1200 x 4), sets (300 x n_lidar x 7), calib_ext (n_lidar x 7 as [t, q(xyzw)]); each may be NULL. */
+enum { MLH_INITEXT_ROT = 1, MLH_INITEXT_TRANS = 2 };
+enum { MLH_INITEXT_MAX_LIDAR = 8, MLH_INITEXT_N_POSE = 300 };
+typedef struct mlh_initext_opts {
+    int32_t n_lidar, idx_ref, planar_movement, window_size;
+    int32_t n_pose, reserved;                /* N_POSE (cpp:22) */
+    double eps_r, eps_t;                     /* EPSILON_R, EPSILON_T (cpp:20-21) */
+    double rot_cov_thre;                     /* 0: cpp:58 */
+    double qbl[MLH_INITEXT_MAX_LIDAR][4];    /* QBL (x, y, z, w) */
+    double tbl[MLH_INITEXT_MAX_LIDAR][3];    /* TBL */
+} mlh_initext_opts;
+typedef struct mlh_initext_result {
+    double q[4];                             /* calib_ext_[lidar].q_ (x, y, z, w) */
+    double t[3];                             /* calib_ext_[lidar].t_ */
+    double rot_sv[4];                        /* singular values of Q_[lidar], descending; rot_cov(1) = rot_sv[2] */
+    double trans_sv[4];                      /* of A (three; [3] = 0) or G (four), descending */
+    int32_t lidar;
+    int32_t rot_ran, rot_converged;          /* calibExRotation got past the window check; returned true */
+    int32_t trans_solved, trans_rank;        /* calibExTranslation ran; the rank Eigen's solve would use */
+    int32_t rot_sweeps, trans_sweeps;        /* Jacobi sweeps, the last (rotation-free) one included */
+    int32_t slot;                            /* pose_laser_add_.first the rotation stage wrote (-1: none) */
+} mlh_initext_result;
+typedef struct mlh_initext_info_t {
+    int32_t configured, n_lidar;
+    int32_t n_sets, heap_size;               /* v_pose_.size(), pq_pose_.size() */
+    int32_t last_slot;                       /* pose_laser_add_.first (-1: nothing accepted yet) */
+    int32_t cov_rot_mask, cov_pos_mask;      /* bit n: cov_rot_state_[n], cov_pos_state_[n] */
+    int32_t full_cov_rot, full_cov_pos;
+    int32_t launches, host_waits;            /* of the last mlh_initext_add_pose / mlh_initext_calibrate */
+    int32_t reserved;
+    int64_t allocations, bytes_hbm;
+    double rot_cov_thre;                     /* rot_cov_thre_ in force */
+} mlh_initext_info_t;
+void mlh_initext_opts_default(mlh_initext_opts *o);
+int mlh_initext_reset(mlh_ctx *ctx, const mlh_initext_opts *opts);
+int mlh_initext_add_pose(mlh_ctx *ctx, const double *poses /* n_lidar x 7 */, int32_t *accepted);
+int mlh_initext_calibrate(mlh_ctx *ctx, const int32_t *lidars, int32_t n, int32_t stages, mlh_initext_result *out /* n */);
+int mlh_initext_info(mlh_ctx *ctx, mlh_initext_info_t *out);
+int mlh_initext_read_state(mlh_ctx *ctx, double *Q, double *sets, double *calib_ext);
+
 /* ---------------------------------------------------------------- (f8) the odometry's sliding window on the device
  * The estimator keeps, per LiDAR and kind, a CircularBuffer<PointICloud> of WINDOW_SIZE + 1 slots (surf_points_stack_[n], corner_points_stack_[n]); before every
  * optimizeMap it thins the new scan's features into slot cir_buf_cnt_ (estimator/src/estimator/estimator.cpp:485-496), slides the window (slideWindow,

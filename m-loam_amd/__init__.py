@@ -272,6 +272,47 @@ def pg_opts(**kw) -> PgOpts:
     return o
 
 
+class InitExtOpts(C.Structure):
+    """mlh_initext_opts"""
+    _fields_ = [("n_lidar", C.c_int32), ("idx_ref", C.c_int32), ("planar_movement", C.c_int32), ("window_size", C.c_int32), ("n_pose", C.c_int32), ("reserved", C.c_int32),
+                ("eps_r", cd_), ("eps_t", cd_), ("rot_cov_thre", cd_), ("qbl", (cd_ * 4) * 8), ("tbl", (cd_ * 3) * 8)]
+
+
+class InitExtResult(C.Structure):
+    """mlh_initext_result"""
+    _fields_ = [("q", cd_ * 4), ("t", cd_ * 3), ("rot_sv", cd_ * 4), ("trans_sv", cd_ * 4), ("lidar", C.c_int32), ("rot_ran", C.c_int32), ("rot_converged", C.c_int32),
+                ("trans_solved", C.c_int32), ("trans_rank", C.c_int32), ("rot_sweeps", C.c_int32), ("trans_sweeps", C.c_int32), ("slot", C.c_int32)]
+
+    def as_dict(self):
+        d = {k: int(getattr(self, k)) for k, t in self._fields_ if t is C.c_int32}
+        d.update(q=np.array(self.q), t=np.array(self.t), rot_sv=np.array(self.rot_sv), trans_sv=np.array(self.trans_sv))
+        return d
+
+
+class InitExtInfo(C.Structure):
+    """mlh_initext_info_t"""
+    _fields_ = [("configured", C.c_int32), ("n_lidar", C.c_int32), ("n_sets", C.c_int32), ("heap_size", C.c_int32), ("last_slot", C.c_int32), ("cov_rot_mask", C.c_int32),
+                ("cov_pos_mask", C.c_int32), ("full_cov_rot", C.c_int32), ("full_cov_pos", C.c_int32), ("launches", C.c_int32), ("host_waits", C.c_int32),
+                ("reserved", C.c_int32), ("allocations", C.c_int64), ("bytes_hbm", C.c_int64), ("rot_cov_thre", cd_)]
+
+
+INITEXT_ROT, INITEXT_TRANS = 1, 2
+
+
+def initext_opts(qbl=None, tbl=None, **kw) -> InitExtOpts:
+    """mlh_initext_opts_default (initial_extrinsics.cpp:20-22, 58), then the given fields; qbl (n, 4) as (x, y, z, w), tbl (n, 3)"""
+    o = InitExtOpts()
+    load_library().mlh_initext_opts_default(C.byref(o))
+    for k, v in kw.items():
+        setattr(o, k, v)
+    for name, src in (("qbl", qbl), ("tbl", tbl)):
+        if src is not None:
+            for i, row in enumerate(np.asarray(src, np.float64)):
+                for j, v in enumerate(row):
+                    getattr(o, name)[i][j] = float(v)
+    return o
+
+
 class SegmentParams(C.Structure):
     _fields_ = [("vertical_scans", C.c_int32), ("horizon_scans", C.c_int32), ("min_cluster_size", C.c_int32), ("segment_valid_point_num", C.c_int32),
                 ("segment_valid_line_num", C.c_int32), ("segment_theta", C.c_float), ("roi_range", C.c_double), ("segment_flag", C.c_int32)]
@@ -468,6 +509,13 @@ def load_library():
     lib.mlh_pg_solve_step.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), cd_, vp, vp, C.POINTER(C.c_int32)]
     lib.mlh_pg_time_stages.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.POINTER(PgResult), vp]
     lib.mlh_pg_optimize_forced.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.c_uint32, C.POINTER(PgResult)]
+    lib.mlh_initext_opts_default.argtypes = [C.POINTER(InitExtOpts)]
+    lib.mlh_initext_opts_default.restype = None
+    lib.mlh_initext_reset.argtypes = [vp, C.POINTER(InitExtOpts)]
+    lib.mlh_initext_add_pose.argtypes = [vp, vp, C.POINTER(C.c_int32)]
+    lib.mlh_initext_calibrate.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(InitExtResult)]
+    lib.mlh_initext_info.argtypes = [vp, C.POINTER(InitExtInfo)]
+    lib.mlh_initext_read_state.argtypes = [vp, vp, vp, vp]
     lib.mlh_pure_odom_add_matches.argtypes = [vp, ci, vp, ci, C.c_uint32, cf, cf, ci, ci]
     lib.mlh_pure_odom_add_matches_gf.argtypes = [vp, ci, vp, vp, vp, vp, ci, C.c_uint32, cf, cf, ci, ci, cf, C.c_uint64, vp, C.POINTER(C.c_int32)]
     lib.mlh_knn.argtypes = [vp, ci, vp, ci, ci, vp, vp]
@@ -513,6 +561,7 @@ EXPORTED_SYMBOLS = [
     "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
     "mlh_keyframe_attach_outlier", "mlh_global_map_opts_default", "mlh_global_map_assemble", "mlh_global_map_cloud", "mlh_global_map_release", "mlh_global_map_select",
     "mlh_keyframes_update_poses", "mlh_keyframes_update_from_pose_graph", "mlh_keyframe_poses",
+    "mlh_initext_opts_default", "mlh_initext_reset", "mlh_initext_add_pose", "mlh_initext_calibrate", "mlh_initext_info", "mlh_initext_read_state",
     "mlh_window_map_opts_default", "mlh_window_reset", "mlh_window_set", "mlh_window_set_from_scan", "mlh_window_slide", "mlh_window_cloud", "mlh_window_info",
     "mlh_window_build_local_map", "mlh_window_map_cloud",
     "mlh_window_prior_set", "mlh_window_prior_get", "mlh_window_prior_clear", "mlh_window_prior_evaluate", "mlh_window_ext_prior_set", "mlh_window_marginalize",
@@ -1209,6 +1258,38 @@ class Context:
         r, ms = PgResult(), np.zeros(8)
         self._ck(self.lib.mlh_pg_time_stages(self.h, int(cur_index), C.byref(opts) if opts is not None else None, C.byref(r), _p(ms)))
         return r.as_dict(), dict(zip(self.PG_STAGE_NAMES, ms.tolist()))
+
+    # ---- the initial extrinsic calibration (InitialExtrinsics: addPose, calibExRotation, calibExTranslation on the device)
+    def initext_reset(self, opts: InitExtOpts = None):
+        """clearState + setParameter (mlh_initext_reset)"""
+        self._ck(self.lib.mlh_initext_reset(self.h, C.byref(opts) if opts is not None else None))
+
+    def initext_add_pose(self, poses) -> bool:
+        """addPose for one set of relative poses (n_lidar, 7) as [t, q(xyzw)] (mlh_initext_add_pose)"""
+        p, acc = np.ascontiguousarray(poses, np.float64), C.c_int32(0)
+        if p.size != 7 * self.initext_info()["n_lidar"]:
+            raise ValueError("poses must be (n_lidar, 7)")
+        self._ck(self.lib.mlh_initext_add_pose(self.h, _p(p), C.byref(acc)))
+        return bool(acc.value)
+
+    def initext_calibrate(self, lidars, stages=INITEXT_ROT | INITEXT_TRANS) -> list:
+        """calibExRotation and / or calibExTranslation for the listed LiDARs in one launch -> one dict per LiDAR (mlh_initext_calibrate)"""
+        ls = np.ascontiguousarray(lidars, np.int32).reshape(-1)
+        out = (InitExtResult * max(1, len(ls)))()
+        self._ck(self.lib.mlh_initext_calibrate(self.h, _p(ls), len(ls), int(stages), out))
+        return [out[i].as_dict() for i in range(len(ls))]
+
+    def initext_info(self) -> dict:
+        info = InitExtInfo()
+        self._ck(self.lib.mlh_initext_info(self.h, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+
+    def initext_read_state(self) -> dict:
+        """Q (n_lidar, 1200, 4), the stored sets (300, n_lidar, 7) and calib_ext_ (n_lidar, 7) (mlh_initext_read_state: a test entry)"""
+        n = self.initext_info()["n_lidar"]
+        Q, sets, ext = np.zeros((max(n, 1), 1200, 4)), np.zeros((300, max(n, 1), 7)), np.zeros((max(n, 1), 7))
+        self._ck(self.lib.mlh_initext_read_state(self.h, _p(Q), _p(sets), _p(ext)))
+        return dict(Q=Q, sets=sets, calib_ext=ext)
 
     def downsample_current_scan(self, kind, points4, leaf, ext_poses, ext_covs, cov_measurement, with_ua=True, trace_threshold=0.6, fetch=True):
         """downsampleCurrentScan for one kind; the result becomes the kind's feature set and, with fetch, is also returned (m, 11)

@@ -7,6 +7,7 @@
 #include <atomic>
 #include <chrono>
 #include <cstddef>
+#include <memory>
 #include <string>
 #include <vector>
 #include <cstdlib>
@@ -550,6 +551,26 @@ struct PgStore {
     int launches = 0, host_waits = 0;        // of the last call
 };
 
+// The initial extrinsic calibration (initext.hip; estimator/src/initial/initial_extrinsics.cpp): Q_ and v_pose_ in HBM, one IeRecord per LiDAR (calib_ext_, the
+// singular values and the flags of the last solve), and the host's bookkeeping (initext_host.hpp: IeBook -- options, the heap, pose_laser_add_, the cov states).
+// Everything is made by mlh_initext_reset: a context that never calls it holds null pointers.
+struct IeBook;
+struct IeRecord {
+    double q[4], t[3];                       // calib_ext_: q (x, y, z, w), t
+    double rot_sv[4], trans_sv[4];           // descending
+    int rot_ran, rot_converged, trans_solved, trans_rank, rot_sweeps, trans_sweeps;
+};
+static_assert(sizeof(IeRecord) == 144, "the initial-extrinsics record: 15 doubles and 6 ints");
+struct InitExtStore {
+    DevBuf Q;                    // n_lidar x 1200 x 4
+    DevBuf sets;                 // 300 x n_lidar x 7
+    DevBuf rec;                  // IeRecord[n_lidar]
+    PinnedBuf h_rec;
+    std::shared_ptr<IeBook> book;
+    long long allocations = 0;
+    int launches = 0, host_waits = 0;        // of the last call
+};
+
 constexpr int FUSE_BLOCKS = 64;          // workgroups per kind of the fusion kernel: each leaves one partial bounding box of what it appended (frontend.hip)
 constexpr int TRACK_SHELLS = 4;          // the tracker's index cells are 1/4 of its acceptance radius (track.hip: nearest_in_radius)
 constexpr int TRACK_MAX_RING = 255;      // ring ids 0..255 (mloam_hip.h; track.hip: track_rings_kernel refuses anything else)
@@ -708,6 +729,7 @@ struct mlh_ctx {
     mlh::LoopStore loop;     // the loop closure's local maps and matches (loopreg.hip)
     mlh::FgrStore fgr;       // FPFH + Fast Global Registration over the loop store's surf clouds (fgr.hip)
     mlh::PgStore pg;         // the loop closure's pose graph and its optimisation (posegraph.hip)
+    mlh::InitExtStore ie;    // the initial extrinsic calibration (initext.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
     mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}

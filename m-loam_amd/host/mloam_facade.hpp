@@ -2735,4 +2735,110 @@ private:
     bool pgo_flag_ = false;
 };
 
+// ------------------------------------------------------------------ the initial extrinsic calibration (estimator/src/initial/initial_extrinsics.{h,cpp})
+// InitialExtrinsics over the context's state (include/mloam_hip.h (f16)) with the reference's names and the members its call site reads, templated over the caller's
+// Pose (the reference's own, or the stand-in), so that estimator.cpp:437-467 reads unchanged. What the reference's setParameter takes from the globals of
+// parameters.h (NUM_OF_LASER, IDX_REF, PLANAR_MOVEMENT, WINDOW_SIZE, QBL, TBL) is filled into options() before setParameter(). step() is that whole block of the
+// call site in ONE fused device call. saveStatistics stays the caller's (a no-op here, so that the call site compiles); decomposeE and calibTimeDelay are not carried.
+template <typename PoseT>
+class InitialExtrinsics {
+public:
+    explicit InitialExtrinsics(Device &dev) : dev_(dev) { mlh_initext_opts_default(&opts_); }
+    mlh_initext_opts &options() { return opts_; }
+    void clearState()
+    {
+        calib_ext_.clear(); cov_rot_state_.clear(); cov_pos_state_.clear(); v_rot_cov_.clear(); v_pos_cov_.clear();
+        full_cov_rot_state_ = full_cov_pos_state_ = false;
+    }
+    // cpp:44-63; also resets the device state and -- unlike the reference's clearState -- the heap
+    void setParameter()
+    {
+        dev_.check(mlh_initext_reset(dev_.ctx(), &opts_));
+        const size_t n = size_t(opts_.n_lidar);
+        calib_ext_.assign(n, PoseT());
+        cov_rot_state_.assign(n, false); cov_pos_state_.assign(n, false);
+        v_rot_cov_.assign(n, std::vector<double>()); v_pos_cov_.assign(n, std::vector<double>());
+        std::vector<double> ext(7 * n);          // calib_ext_ = Pose(QBL, TBL) (cpp:46)
+        dev_.check(mlh_initext_read_state(dev_.ctx(), nullptr, nullptr, ext.data()));
+        for (size_t l = 0; l < n; ++l) detail::pose_from_param(calib_ext_[l], ext.data() + 7 * l);
+        refresh();
+    }
+    bool addPose(const std::vector<PoseT> &pose_laser)
+    {
+        if (pose_laser.size() != size_t(opts_.n_lidar)) throw Error("InitialExtrinsics::addPose: one pose per LiDAR");
+        double p[MLH_INITEXT_MAX_LIDAR * 7];
+        for (size_t i = 0; i < pose_laser.size(); ++i) detail::pose_to_param(pose_laser[i], p + 7 * i);
+        int32_t accepted = 0;
+        dev_.check(mlh_initext_add_pose(dev_.ctx(), p, &accepted));
+        return accepted != 0;
+    }
+    bool calibExRotation(const size_t &idx_ref, const size_t &idx_data, PoseT &calib_result)
+    {
+        const mlh_initext_result r = one(idx_ref, idx_data, MLH_INITEXT_ROT);
+        if (r.rot_converged) calib_result = calib_ext_[idx_data];
+        return r.rot_converged != 0;
+    }
+    bool calibExTranslation(const size_t &idx_ref, const size_t &idx_data, PoseT &calib_result)
+    {
+        const mlh_initext_result r = one(idx_ref, idx_data, MLH_INITEXT_TRANS);
+        if (r.trans_solved) calib_result = calib_ext_[idx_data];
+        return r.trans_solved != 0;
+    }
+    // estimator.cpp:437-467 in one fused call: addPose, and when it accepted the set and the window is full (cir_buf_cnt_ == WINDOW_SIZE), calibExRotation for every
+    // LiDAR without a rotation and calibExTranslation where it converged. Returns the LiDARs that got their extrinsic in this call (calib_ext_[n] holds it: what the
+    // call site copies into qbl_ / tbl_ / QBL / TBL), *accepted <- addPose's answer; full_cov_rot_state_ && full_cov_pos_state_ then ends the initialisation as at cpp:459-464.
+    std::vector<size_t> step(const std::vector<PoseT> &pose_rlt, bool window_full, bool *accepted = nullptr)
+    {
+        std::vector<size_t> solved;
+        const bool added = addPose(pose_rlt);
+        if (accepted) *accepted = added;
+        if (!(added && window_full)) return solved;
+        int32_t lidars[MLH_INITEXT_MAX_LIDAR], n = 0;
+        for (size_t l = 0; l < cov_rot_state_.size(); ++l)
+            if (!cov_rot_state_[l]) lidars[n++] = int32_t(l);
+        if (n == 0) return solved;
+        mlh_initext_result out[MLH_INITEXT_MAX_LIDAR];
+        dev_.check(mlh_initext_calibrate(dev_.ctx(), lidars, n, MLH_INITEXT_ROT | MLH_INITEXT_TRANS, out));
+        for (int32_t i = 0; i < n; ++i) {
+            take(out[i]);
+            if (out[i].rot_converged && out[i].trans_solved) solved.push_back(size_t(out[i].lidar));
+        }
+        refresh();
+        return solved;
+    }
+    void saveStatistics() const {}
+    std::vector<PoseT> calib_ext_;
+    std::vector<std::vector<double>> v_rot_cov_, v_pos_cov_;
+    std::vector<bool> cov_rot_state_, cov_pos_state_;
+    bool full_cov_rot_state_ = false, full_cov_pos_state_ = false;
+    double rot_cov_thre_ = 0.25;
+private:
+    mlh_initext_result one(size_t idx_ref, size_t idx_data, int32_t stage)
+    {
+        if (idx_ref != size_t(opts_.idx_ref)) throw Error("InitialExtrinsics: idx_ref is not the one given to setParameter");
+        const int32_t l = int32_t(idx_data);
+        mlh_initext_result r;
+        dev_.check(mlh_initext_calibrate(dev_.ctx(), &l, 1, stage, &r));
+        take(r);
+        refresh();
+        return r;
+    }
+    void take(const mlh_initext_result &r)
+    {
+        const double p[7] = {r.t[0], r.t[1], r.t[2], r.q[0], r.q[1], r.q[2], r.q[3]};
+        detail::pose_from_param(calib_ext_[size_t(r.lidar)], p);
+        if (r.rot_ran) v_rot_cov_[size_t(r.lidar)].push_back(r.rot_sv[2]);          // cpp:198-199
+    }
+    void refresh()
+    {
+        mlh_initext_info_t info;
+        dev_.check(mlh_initext_info(dev_.ctx(), &info));
+        for (size_t l = 0; l < cov_rot_state_.size(); ++l) { cov_rot_state_[l] = (info.cov_rot_mask >> l) & 1; cov_pos_state_[l] = (info.cov_pos_mask >> l) & 1; }
+        full_cov_rot_state_ = info.full_cov_rot != 0; full_cov_pos_state_ = info.full_cov_pos != 0;
+        rot_cov_thre_ = info.rot_cov_thre;
+    }
+    Device &dev_;
+    mlh_initext_opts opts_{};
+};
+
 }  // namespace mloam_hip
