@@ -724,8 +724,13 @@ int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
  * mlh_pg_opts_default: max_num_iterations 5 (cpp:522), 4 sequential edges (cpp:555), t_var 0.1, q_var 0.01 (cpp:566, 581), HuberLoss(1.0) (cpp:525). Options are
  *   validated by every call that takes them (NULL: the defaults): MLH_ERR_INVALID outside 0 <= max_num_iterations <= 200, n_sequential == 4 (the band's shape is
  *   fixed), finite variances and huber_delta > 0.
- * mlh_pg_reset: forgets every keyframe (the buffers stay).  mlh_pg_info: the counts, earliest_loop_index_, the largest supported number of loop edges of one
- *   problem (128), allocations and bytes held.
+ * mlh_pg_reset: forgets every keyframe (the buffers and the reserved capacity stay).  mlh_pg_info: the counts, earliest_loop_index_, the context's capacity of
+ *   loop edges of one problem (max_loops: 128 until mlh_pg_reserve raises it), allocations and bytes held.
+ * mlh_pg_reserve(max_loops): the largest number of loop edges one problem of this context may hold, 128 <= max_loops <= MLH_PG_LOOPS_LIMIT (1024), otherwise
+ *   MLH_ERR_INVALID. Bookkeeping only: nothing is allocated (the buffers grow with the problems that come), mlh_pg_reset keeps it. The capacity is the caller's
+ *   decision because of the memory behind it: Y is 6 (M - 1) x (6 L + 1) doubles, the dense stage's Gram image and factor about 2 x (6 L)^2 doubles -- at the
+ *   limit, L = 1024, 0.6 GB for the dense stage and 0.3 GB of Y per 1000 keyframes. The earliest looped index never moves forward (cpp:140-142), so a run's L only
+ *   grows: with loop_skip_interval 3 the 129th edge arrives after about 390 keyframes of revisit.
  * mlh_pg_add_keyframe = the bookkeeping of PoseGraph::addKeyFrame (cpp:94-96): the keyframe gets index global_index_++; *index_out (may be NULL) <- it. CHOSEN:
  *   last_pose_w_ and loop_info_ start as the identity (the reference's KeyFrame leaves them default-constructed). A non-finite pose: MLH_ERR_INVALID.
  * mlh_pg_set_loop = KeyFrame::updateLoopInfo(loop_index, loop_info) plus the earliest-index rule (cpp:140-142); loadKeyFrame's loop case (cpp:187-206) is this call
@@ -736,19 +741,22 @@ int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
  *     Eigen's q.inverse() * v and q.inverse() * q, not normalised), no loss; a keyframe with a loop gets one edge (loop keyframe, keyframe) under HuberLoss;
  *   - ceres::Solve as the project's Ceres-shaped Levenberg-Marquardt: Jacobi scaling fixed at iteration 0, the clamped diagonal over the radius, the model cost
  *     change, step validity, the function / parameter / gradient tolerances, the radius update and the diagonal's reuse. Every decision is taken on the device in a
- *     state record; the launches of an iteration return at once when the solve has terminated; the number of launches (3 + 10 max_num_iterations + 1) does not
- *     depend on M or L (the one exception: cur == first has no free block and only the loop's head is launched per iteration, 3 + max_num_iterations + 1); ONE host wait (the summary). No floating-point atomics: two runs give the same bits;
+ *     state record; the launches of an iteration return at once when the solve has terminated; the number of launches (3 + 10 max_num_iterations + 1; for L > 128
+ *     3 + (9 + 3 ceil(6 L / 64)) max_num_iterations + 1) does not depend on M, nor on L up to 128 (the one exception: cur == first has no free block and only the loop's head is launched per iteration, 3 + max_num_iterations + 1); ONE host wait (the summary). No floating-point atomics: two runs give the same bits;
  *   - the linear system (S H S + D / radius) y = S g is solved exactly as B + W^T W: B the block band of the sequential edges plus the diagonal (banded block
  *     Cholesky, one workgroup, a 5 x 5-block window in LDS), W the 6 L rows of the loop edges' corrected Jacobians; [Y | y_b] = L^-1 [W^T | S g] with one lane per
- *     column; C = I + Y^T Y and Y^T y_b by v_mfma_f64_16x16x4_f64 with K split over workgroups and a fixed-order second stage; C z = Y^T y_b by a dense Cholesky in
- *     one workgroup (LDS up to 84 rows, HBM beyond); L^T x = y_b - Y z in one sweep. A non-positive pivot in B or in C, or a model cost change <= 0, makes the
+ *     column; C = I + Y^T Y and Y^T y_b by v_mfma_f64_16x16x4_f64 with K split over workgroups and a fixed-order second stage; C z = Y^T y_b by a dense Cholesky: for
+ *     L <= 128 in one workgroup (LDS up to 84 rows, HBM beyond), exactly as before mlh_pg_reserve existed; for L > 128 (chosen by the problem's L, never by the
+ *     capacity) by a blocked left-looking Cholesky over the whole device on 64-wide panels -- the partials summed by one workgroup per tile, each panel's update
+ *     in v_mfma_f64_16x16x4_f64, the right-hand side carried as one more row (the forward substitution), a blocked backward substitution -- in
+ *     3 ceil(6 L / 64) launches that replace the one, synchronised by kernel boundaries only; L^T x = y_b - Y z in one sweep. A non-positive pivot in B or in C, or a model cost change <= 0, makes the
  *     step invalid: the radius is halved as the policy prescribes (five in a row: termination 4);
  *   - write-back (cpp:615-641): updatePose(Pose(q, t)) on first..cur (Pose's constructor normalises q; the constant block too: its last pose becomes its pose),
  *     pose_drift = cur * last^-1 left-multiplied onto every later keyframe through updatePose. Keyframes before `first` keep their bits.
  *   *result: num_iterations, num_successful_steps, initial / final cost, termination (0 iteration limit, 1 gradient, 2 parameter, 3 function tolerance, 4 failure),
  *   M, L, first, the final radius, pose_drift, launches and host waits.
  *   MLH_ERR_STATE when no loop has been set or cur_index < earliest_loop_index_; MLH_ERR_INVALID for a cur_index that names no keyframe; MLH_ERR_UNSUPPORTED, with
- *   nothing changed, when first..cur holds more than 128 loop edges.
+ *   nothing changed, when first..cur holds more loop edges than the context's capacity (128, or what mlh_pg_reserve set; the message names it).
  *   DEPARTURE: the model cost change's quadratic term is summed per edge (|J S step|^2) rather than through the assembled matrix: the same number up to rounding.
  *   CHOSEN: cur == first (M = 1) has no free block: termination 1 at iteration 0, then the write-back.
  * mlh_pg_poses: n poses from `first` (7 doubles each) and, when last_poses is not NULL, the last poses.  mlh_pg_device_poses: the records in HBM for device
@@ -771,6 +779,7 @@ int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
  *   [4] Gram, [5] dense solve, [6] y_b - Y z and the back-substitution, [7] the LM bookkeeping (candidate and decisions). The events themselves cost a few
  *   microseconds of queue time each, which the figures include. */
 enum { MLH_PG_STAGES = 8 };
+enum { MLH_PG_LOOPS_LIMIT = 1024 };          /* the ceiling of mlh_pg_reserve */
 typedef struct mlh_pg_opts {
     int32_t max_num_iterations;              /* options.max_num_iterations (cpp:522) */
     int32_t n_sequential;                    /* cpp:555: 4 */
@@ -797,6 +806,7 @@ typedef struct mlh_pg_info_t {
 void mlh_pg_opts_default(mlh_pg_opts *o);
 int mlh_pg_reset(mlh_ctx *ctx);
 int mlh_pg_info(mlh_ctx *ctx, mlh_pg_info_t *out);
+int mlh_pg_reserve(mlh_ctx *ctx, int32_t max_loops);
 int mlh_pg_add_keyframe(mlh_ctx *ctx, const double *pose, int32_t *index_out);
 int mlh_pg_set_loop(mlh_ctx *ctx, int32_t index, int32_t loop_index, const double *rel_pose);
 int mlh_pg_optimize(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, mlh_pg_result *result);

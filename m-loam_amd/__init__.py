@@ -263,6 +263,9 @@ class PgInfo(C.Structure):
                 ("bytes_hbm", C.c_int64)]
 
 
+PG_LOOPS_LIMIT = 1024          # MLH_PG_LOOPS_LIMIT
+
+
 def pg_opts(**kw) -> PgOpts:
     """mlh_pg_opts_default (pose_graph.cpp:522, 525, 555, 566), then the given fields"""
     o = PgOpts()
@@ -500,6 +503,7 @@ def load_library():
     lib.mlh_pg_opts_default.restype = None
     lib.mlh_pg_reset.argtypes = [vp]
     lib.mlh_pg_info.argtypes = [vp, C.POINTER(PgInfo)]
+    lib.mlh_pg_reserve.argtypes = [vp, C.c_int32]
     lib.mlh_pg_add_keyframe.argtypes = [vp, vp, C.POINTER(C.c_int32)]
     lib.mlh_pg_set_loop.argtypes = [vp, C.c_int32, C.c_int32, vp]
     lib.mlh_pg_optimize.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.POINTER(PgResult)]
@@ -571,7 +575,7 @@ EXPORTED_SYMBOLS = [
     "mlh_fgr_opts_default", "mlh_fgr_features", "mlh_fgr_spfh", "mlh_fgr_fpfh", "mlh_fgr_fetch", "mlh_fgr_set_normals", "mlh_fgr_set_spfh", "mlh_fgr_set_features",
     "mlh_fgr_match", "mlh_fgr_register", "mlh_fgr_info",
     "mlh_pg_opts_default", "mlh_pg_reset", "mlh_pg_info", "mlh_pg_add_keyframe", "mlh_pg_set_loop", "mlh_pg_optimize", "mlh_pg_poses", "mlh_pg_device_poses",
-    "mlh_pg_linearize", "mlh_pg_solve_step", "mlh_pg_time_stages", "mlh_pg_optimize_forced",
+    "mlh_pg_linearize", "mlh_pg_solve_step", "mlh_pg_time_stages", "mlh_pg_optimize_forced", "mlh_pg_reserve",
 ]
 
 
@@ -1193,6 +1197,10 @@ class Context:
         info = PgInfo()
         self._ck(self.lib.mlh_pg_info(self.h, C.byref(info)))
         return {k: int(getattr(info, k)) for k, _ in info._fields_}
+
+    def pg_reserve(self, max_loops):
+        """the context's capacity of loop edges of one problem, 128 .. PG_LOOPS_LIMIT; allocates nothing, survives pg_reset (mlh_pg_reserve)"""
+        self._ck(self.lib.mlh_pg_reserve(self.h, int(max_loops)))
 
     def pg_add_keyframe(self, pose) -> int:
         """the keyframe's index (mlh_pg_add_keyframe); pose [t, q(xyzw)]"""

@@ -547,6 +547,7 @@ struct PgStore {
     std::vector<int> loop_index; // host mirror of PgKeyframe::loop_index
     std::vector<int> h_loops;    // the problem's loop list on its way to the device
     int count = 0, earliest_loop = -1;
+    int max_loops = 128;                     // the capacity of loop edges of one problem (mlh_pg_reserve; pg_host.hpp: PG_MAX_LOOPS until then); mlh_pg_reset keeps it
     long long allocations = 0;
     int launches = 0, host_waits = 0;        // of the last call
 };

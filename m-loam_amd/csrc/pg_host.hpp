@@ -35,7 +35,9 @@
 
 namespace mlh {
 
-constexpr int PG_MAX_LOOPS = 128;            // loop edges of one problem (the forward substitution has one lane per column of [W^T | b]: 6 x 128 + 1)
+constexpr int PG_MAX_LOOPS = 128;            // a context's capacity of loop edges until mlh_pg_reserve raises it (up to MLH_PG_LOOPS_LIMIT), and the largest L whose
+                                             // dense stage is the one-workgroup pg_dense_kernel (its right-hand side in LDS: 6 x 128 doubles); beyond it the blocked stage
+constexpr int PG_PANEL = 64;                 // the blocked dense stage's panel width: a 64 x 64 f64 diagonal block is 32 KiB of LDS
 constexpr int PG_SEQ = 4;                    // sequential edges per keyframe (pose_graph.cpp:555)
 constexpr int PG_SLOTS = PG_SEQ + 1;         // edge slots per keyframe: to i - 1 .. i - 4, then the loop edge
 
@@ -52,6 +54,40 @@ inline const char *pg_opts_fault(const mlh_pg_opts &o)
     if (!std::isfinite(o.q_var) || !(o.q_var > 0.0)) return "q_var";
     if (!std::isfinite(o.huber_delta) || !(o.huber_delta > 0.0)) return "huber_delta";
     return nullptr;
+}
+
+// ---- the blocked dense stage's launch plan (posegraph.hip: L > PG_MAX_LOOPS). The bordered matrix [C; r^T] (m = 6 L columns, m + 1 rows: the last row is the
+// right-hand side, which the panel solves turn into L^-1 r) is cut into PG_PANEL-wide tiles: T = ceil(m / 64) column panels, Tb = ceil((m + 1) / 64) row tiles. The
+// factorisation is LEFT-looking; one entry below is one kernel launch whose workgroup w covers tile (or row tile) lo + w:
+//   PG_STEP_SUM            every tile (k, i), k < T, k <= i < Tb: the Gram partials summed in split order (workgroups = the number of those tiles)
+//   PG_STEP_UPDATE  k      tiles (k, i), i = lo .. hi - 1 (lo = k): minus the products of the panels 0 .. k - 1 (k >= 1)
+//   PG_STEP_PANEL   k      tile (k, k) factored (every workgroup READS it and factors it for itself; workgroup lo = k stores the factor in the diagonal buffer,
+//                          never over the tile), tiles (k, i), i = k + 1 .. hi - 1 solved in place
+//   PG_STEP_BACK    k      the backward substitution's panel k, from T - 1 down: row tile k solved, row tiles lo = 0 .. k - 1 updated with it
+// 3 T launches in all, a function of m alone.
+enum { PG_STEP_SUM = 0, PG_STEP_UPDATE, PG_STEP_PANEL, PG_STEP_BACK };
+struct PgDenseStep { int kind, k, lo, hi; };
+inline int pg_dense_panels(int m) { return (m + PG_PANEL - 1) / PG_PANEL; }
+inline int pg_dense_row_tiles(int m) { return (m + 1 + PG_PANEL - 1) / PG_PANEL; }
+inline int pg_dense_launches(int m) { return m > 0 ? 3 * pg_dense_panels(m) : 0; }
+// launch `index` (0 .. pg_dense_launches(m) - 1) of the stage: what the host enqueues, in this order
+inline PgDenseStep pg_dense_step(int m, int index)
+{
+    const int T = pg_dense_panels(m), Tb = pg_dense_row_tiles(m);
+    if (index == 0) return {PG_STEP_SUM, 0, 0, T * Tb - T * (T - 1) / 2};
+    if (index < 2 * T) {
+        const int k = index / 2;
+        return {index % 2 ? PG_STEP_PANEL : PG_STEP_UPDATE, k, k, Tb};
+    }
+    const int k = T - 1 - (index - 2 * T);
+    return {PG_STEP_BACK, k, 0, k + 1};
+}
+// workgroup w of PG_STEP_SUM -> its tile (k, i): the tiles row by row of the upper-stored factor, row k holding i = k .. Tb - 1
+MLH_PG_HD void pg_dense_sum_tile(int w, int Tb, int *k_out, int *i_out)
+{
+    int k = 0;
+    while (w >= Tb - k) { w -= Tb - k; ++k; }
+    *k_out = k; *i_out = k + w;
 }
 
 // quaternions below are (w, x, y, z); poses in memory are [t, q(xyzw)]

@@ -15,7 +15,9 @@
 //   pg_forward_kernel    [Y | y_b] = L^-1 [W^T | S g]: one lane per column, each workgroup starts at the first non-zero block of its columns, L's block row is
 //                        staged once per step in LDS (double-buffered) for all lanes; Y stored with the column index fastest
 //   pg_gram_kernel       Y^T Y by v_mfma_f64_16x16x4_f64 on 32 x 32 macro-tiles of the lower triangle, K (= n) split over workgroups, partials to HBM
-//   pg_dense_kernel      one workgroup: the partials summed in split order, C = I + Y^T Y factored and C z = Y^T y_b solved -- in LDS up to 84 rows, in HBM beyond
+//   pg_dense_kernel      L <= 128: one workgroup: the partials summed in split order, C = I + Y^T Y factored and C z = Y^T y_b solved -- in LDS up to 84 rows, in HBM beyond
+//   L > 128 (chosen by the problem's L, never by the context's capacity): the blocked dense stage over the whole device, 3 ceil(6 L / 64) launches in the order of
+//   pg_host.hpp's pg_dense_step -- see "the blocked dense stage" below
 //   pg_yz_kernel         y_b - Y z
 //   pg_back_kernel       one workgroup: L^T x = y_b - Y z in one sweep from the last block to the first; step = -x
 //   pg_candidate_kernel  x (+) S step, and the per-keyframe terms of step . S g, |x - candidate|^2, |x|^2
@@ -50,8 +52,9 @@ struct PgState {
 struct PgDev {
     PgKeyframe *kf;
     int first, cur, count, M, NB, L, n, m, ncol, ncp, ks, rows_per;
+    int T, Tb, ld;                           // the blocked dense stage (L > PG_MAX_LOOPS): column panels, row tiles, the factor's leading dimension 64 Tb; else 0
     double t_var, q_var, huber;
-    double *x, *meas, *lr, *lJi, *lJj, *cost_e, *sas_e, *Bb, *hd, *g, *S, *diag, *gs, *gm, *Lrow, *Linv, *Y, *Gpart, *C, *z, *rvec, *step, *red;
+    double *x, *meas, *lr, *lJi, *lJj, *cost_e, *sas_e, *Bb, *hd, *g, *S, *diag, *gs, *gm, *Lrow, *Linv, *Y, *Gpart, *C, *Dg, *z, *zw, *rvec, *step, *red;
     int *loops;
     PgState *st;
 };
@@ -513,6 +516,192 @@ __global__ __launch_bounds__(PG_TPB) void pg_dense_kernel(PgDev P)
     if (t == 0 && sh_fail) S.lin_ok = 0;
 }
 
+// ---------------------------------------------------------------- the blocked dense stage (L > PG_MAX_LOOPS; m = 6 L up to 6144)
+// The bordered matrix [C; r^T] -- C = I + Y^T Y (m x m), r = Y^T y_b as row m, which the Gram image already holds -- is factored by a blocked Cholesky over
+// PG_PANEL = 64-wide tiles, T = ceil(m / 64) column panels and Tb = ceil((m + 1) / 64) row tiles. Carrying r along as one more row of the panel solves leaves
+// L^-1 r in that row: the forward substitution is free. Only the TRANSPOSED factor is stored: U[j][r] = L[r][j] in P.C, row-major with leading dimension
+// ld = 64 Tb, the contraction index j slow. Then both operands of a v_mfma_f64_16x16x4_f64 step of the update are 16 consecutive doubles of one row of U per quarter
+// wavefront (the layout pg_gram_kernel documents) with no LDS transpose, the tile stores are 16 consecutive doubles too, and the backward substitution U z = w reads
+// rows of U. Columns >= m of the last panel and rows > m are padding: zeros, a pivot of 1, never flagged.
+// The factored DIAGONAL tiles live in P.Dg (T x 64 x 64), not in P.C: within a panel's launch every workgroup reads tile (k, k) of P.C, so the one that stores the
+// factor must not store it there -- no address is written by one workgroup and read by another inside a launch.
+// LEFT-looking: tile (k, i) is written once by the summation, once by the update of panel k (minus the products of ALL earlier panels, j ascending in one
+// accumulator chain) and once by the panel solve. Right-looking would rewrite the whole trailing matrix once per panel (m^2 / 2 doubles x T: 14 GB of stores at
+// m = 6144) and take three launches per panel (factor, solve, trailing update) where this takes two; the price is that panel k's update has only Tb - k workgroups
+// with a contraction of 64 k -- the reads (about T^3 / 3 tiles) are served from rows of U that stay in L2 / MALL.
+// Launches (pg_host.hpp: pg_dense_step), synchronised by kernel boundaries only:
+//   pg_csum_kernel     one workgroup per tile: the Gram partials summed in split order, 1 added on the diagonal, stored transposed through LDS. 256 threads,
+//                      33 KiB LDS, 18 VGPRs
+//   pg_cupdate_kernel  k = 1 .. T - 1, workgroup i - k for tile (k, i): 4 wavefronts, each a 32 x 32 quadrant = 2 x 2 MFMA accumulators (32 AccVGPRs), four steps'
+//                      operands in flight (56 VGPRs), straight from HBM / L2, no LDS
+//   pg_cpanel_kernel   k = 0 .. T - 1, workgroup i - k: EVERY workgroup factors the diagonal tile (k, k) for itself in LDS (the same operations in the same order:
+//                      the same bits; 64 column steps, two barriers each) -- that spares a launch per panel; workgroup 0 stores it, into P.Dg (T tiles of 64 x 64, a
+//                      buffer of its own: tile (k, k) of P.C is READ by every workgroup of the launch, so none may write it), and reports a non-positive pivot
+//                      (lin_ok = 0, the factorisation goes on with 1 in its place, as pg_dense_kernel does); the others solve X L_kk^T = tile for their tile, 16
+//                      rows of it in registers per thread, one barrier per column. 256 threads, 33 KiB LDS, 91 VGPRs
+//   pg_cback_kernel    k = T - 1 .. 0, workgroup jt <= k: every workgroup solves the 64 x 64 triangle of panel k for z_k (one wavefront, shuffles); workgroup k stores
+//                      z_k, workgroup jt < k subtracts U[tile jt][panel k] z_k from its 64 entries of w (a wavefront per row, a fixed xor-tree). 33 KiB LDS, 24 VGPRs.
+//                      Blocked over launches rather than one wide workgroup, which streams the whole factor (151 MB at m = 6144) through one compute unit:
+//                      measured with a 1024-thread variant (equal bits), the dense stage of five iterations took 9.18 / 21.2 / 195.8 ms at L = 129 / 256 / 1024
+//                      against 9.14 / 18.9 / 131.6 ms this way, both before the diagonal factors got their own buffer
+// Every sum has one order; no atomics; every kernel returns at once when the solve is over or the band's factorisation failed (force_fail included).
+
+__global__ __launch_bounds__(PG_TPB) void pg_csum_kernel(PgDev P)
+{
+    __shared__ double Tl[PG_PANEL * (PG_PANEL + 1)];
+    const PgState &S = *P.st;
+    if (S.done || !S.lin_ok) return;
+    int k, i;
+    pg_dense_sum_tile(int(blockIdx.x), P.Tb, &k, &i);
+    const int t = threadIdx.x, m = P.m, ncp = P.ncp;
+    const size_t gs = size_t(ncp) * ncp;
+    for (int idx = t; idx < PG_PANEL * PG_PANEL; idx += PG_TPB) {
+        const int rr = idx >> 6, cc = idx & 63, r = i * PG_PANEL + rr, c = k * PG_PANEL + cc;
+        double v = 0.0;
+        if (r <= m && c < m && c <= r) {
+            for (int kz = 0; kz < P.ks; ++kz) v += P.Gpart[kz * gs + size_t(r) * ncp + c];
+            if (r == c) v = 1.0 + v;
+        }
+        Tl[cc * (PG_PANEL + 1) + rr] = v;
+    }
+    __syncthreads();
+    for (int idx = t; idx < PG_PANEL * PG_PANEL; idx += PG_TPB) {
+        const int cc = idx >> 6, rr = idx & 63;
+        P.C[(size_t(k) * PG_PANEL + cc) * P.ld + size_t(i) * PG_PANEL + rr] = Tl[cc * (PG_PANEL + 1) + rr];
+    }
+}
+
+// tile (k, i) -= sum over j < 64 k of U[j][64 k + c] U[j][64 i + r]; the result's row is c (the slow index of U), its column r
+__global__ __launch_bounds__(PG_TPB) void pg_cupdate_kernel(PgDev P, int k)
+{
+    const PgState &S = *P.st;
+    if (S.done || !S.lin_ok) return;
+    const int i = k + int(blockIdx.x);
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63, lr = l >> 4, lc = l & 15;
+    const int a0 = (w >> 1) * 32, b0 = (w & 1) * 32;
+    const size_t ld = size_t(P.ld);
+    const double *Uk = P.C + size_t(k) * PG_PANEL + a0 + lc, *Ui = P.C + size_t(i) * PG_PANEL + b0 + lc;
+    pg_d4 acc[2][2];
+    for (int a = 0; a < 2; ++a)
+        for (int c = 0; c < 2; ++c) acc[a][c] = pg_d4{0.0, 0.0, 0.0, 0.0};
+    const int K = k * PG_PANEL;
+    for (int j0 = 0; j0 < K; j0 += 16) {                 // (K is a multiple of 64) four steps' operands in flight
+        double av[4][2], cv[4][2];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const size_t ro = size_t(j0 + 4 * u + lr) * ld;
+            av[u][0] = Uk[ro]; av[u][1] = Uk[ro + 16]; cv[u][0] = Ui[ro]; cv[u][1] = Ui[ro + 16];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            acc[0][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][0], cv[u][0], acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][0], cv[u][1], acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][1], cv[u][0], acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[u][1], cv[u][1], acc[1][1], 0, 0, 0);
+        }
+    }
+    for (int a = 0; a < 2; ++a)
+        for (int c = 0; c < 2; ++c)
+            for (int q = 0; q < 4; ++q) {
+                double *o = P.C + (size_t(k) * PG_PANEL + a0 + a * 16 + lr + 4 * q) * ld + size_t(i) * PG_PANEL + b0 + c * 16 + lc;
+                *o = *o - acc[a][c][q];
+            }
+}
+
+__global__ __launch_bounds__(PG_TPB) void pg_cpanel_kernel(PgDev P, int k)
+{
+    __shared__ double Dl[PG_PANEL * PG_PANEL];           // Dl[c * 64 + r] = L_kk[r][c], r >= c
+    __shared__ double xs[2][PG_PANEL];
+    PgState &S = *P.st;
+    if (S.done || !S.lin_ok) return;
+    const int t = threadIdx.x, m = P.m, i = k + int(blockIdx.x);
+    const size_t ld = size_t(P.ld);
+    const double *Ukk = P.C + size_t(k) * PG_PANEL * ld + size_t(k) * PG_PANEL;
+    for (int idx = t; idx < PG_PANEL * PG_PANEL; idx += PG_TPB) Dl[idx] = Ukk[size_t(idx >> 6) * ld + (idx & 63)];
+    __syncthreads();
+    int fail = 0;
+    const int r = t & 63, q = t >> 6;
+    for (int j = 0; j < PG_PANEL; ++j) {
+        double p = Dl[j * PG_PANEL + j];
+        if (k * PG_PANEL + j >= m) p = 1.0;              // padding
+        else if (!(p > 0.0)) { fail = 1; p = 1.0; }
+        const double dj = sqrt(p);
+        if (t > j && t < PG_PANEL) Dl[j * PG_PANEL + t] /= dj;
+        __syncthreads();
+        if (t == 0) Dl[j * PG_PANEL + j] = dj;           // (read by no one before the next barrier: lrj below is taken for r > j only)
+        const double lrj = r > j ? Dl[j * PG_PANEL + r] : 0.0;
+        for (int c = j + 1 + q; c < PG_PANEL; c += 4)
+            if (r >= c) Dl[c * PG_PANEL + r] -= Dl[j * PG_PANEL + c] * lrj;
+        __syncthreads();
+    }
+    if (i == k) {
+        // the factor goes to a buffer of its own: the other workgroups of this launch read tile (k, k) of P.C, which therefore nobody writes here
+        double *out = P.Dg + size_t(k) * PG_PANEL * PG_PANEL;
+        for (int idx = t; idx < PG_PANEL * PG_PANEL; idx += PG_TPB) out[idx] = Dl[idx];
+        if (t == 0 && fail) S.lin_ok = 0;
+        return;
+    }
+    // thread (r, q): column r of the tile, its rows c = 4 u + q
+    double *Tki = P.C + size_t(k) * PG_PANEL * ld + size_t(i) * PG_PANEL + r;
+    double v[16];
+#pragma unroll
+    for (int u = 0; u < 16; ++u) v[u] = Tki[size_t(4 * u + q) * ld];
+#pragma unroll
+    for (int c = 0; c < PG_PANEL; ++c) {
+        if (q == (c & 3)) {
+            const double x = v[c >> 2] / Dl[c * PG_PANEL + c];
+            xs[c & 1][r] = x;
+            Tki[size_t(c) * ld] = x;
+        }
+        __syncthreads();
+        const double x = xs[c & 1][r];
+#pragma unroll
+        for (int u = c >> 2; u < 16; ++u)
+            if (4 * u + q > c) v[u] -= Dl[c * PG_PANEL + 4 * u + q] * x;
+    }
+}
+
+// panel k of U z = w, w = L^-1 r (column m of U): z_k from the panel's triangle, then w -= U[.][panel k] z_k on the row tiles above
+__global__ __launch_bounds__(PG_TPB) void pg_cback_kernel(PgDev P, int k)
+{
+    __shared__ double Dl[PG_PANEL * (PG_PANEL + 1)];
+    __shared__ double zs[PG_PANEL];
+    const PgState &S = *P.st;
+    if (S.done || !S.lin_ok) return;
+    const int t = threadIdx.x, m = P.m, jt = int(blockIdx.x);
+    const size_t ld = size_t(P.ld);
+    const bool first = k == P.T - 1;                     // w still lies in the factor's bordering row
+    const double *Dkk = P.Dg + size_t(k) * PG_PANEL * PG_PANEL;
+    for (int idx = t; idx < PG_PANEL * PG_PANEL; idx += PG_TPB) Dl[(idx >> 6) * (PG_PANEL + 1) + (idx & 63)] = Dkk[idx];
+    __syncthreads();
+    if (t < PG_PANEL) {
+        const int c = t, gc = k * PG_PANEL + c;
+        // the last panel's share of the bordering row lies in its diagonal tile when m is no multiple of 64, in a row tile of its own otherwise
+        double wv = !first ? P.zw[gc] : m < P.T * PG_PANEL ? Dl[c * (PG_PANEL + 1) + (m - k * PG_PANEL)] : P.C[size_t(gc) * ld + m];
+        double mine = 0.0;
+        for (int r = PG_PANEL - 1; r >= 0; --r) {
+            double zr = __shfl(wv / Dl[r * (PG_PANEL + 1) + r], r);
+            if (k * PG_PANEL + r >= m) zr = 0.0;
+            if (c < r) wv -= Dl[c * (PG_PANEL + 1) + r] * zr;
+            if (c == r) mine = zr;
+        }
+        zs[c] = mine;
+    }
+    __syncthreads();
+    if (jt == k) {
+        if (t < PG_PANEL) P.z[k * PG_PANEL + t] = zs[t];
+        return;
+    }
+    const int w = t >> 6, l = t & 63;
+    const double zl = zs[l];
+    for (int rr = 0; rr < 16; ++rr) {
+        const int j = jt * PG_PANEL + w * 16 + rr;
+        double v = P.C[size_t(j) * ld + size_t(k) * PG_PANEL + l] * zl;
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        if (l == 0) P.zw[j] = (first ? P.C[size_t(j) * ld + m] : P.zw[j]) - v;
+    }
+}
+
 __global__ __launch_bounds__(PG_TPB) void pg_yz_kernel(PgDev P)
 {
     const PgState &S = *P.st;
@@ -714,10 +903,13 @@ int pg_problem(mlh_ctx *ctx, const char *entry, int cur_index, const mlh_pg_opts
     loops.clear();
     for (int k = 0; k < P.M; ++k)
         if (G.loop_index[size_t(P.first + k)] >= 0) loops.push_back(k);
-    if (int(loops.size()) > PG_MAX_LOOPS)
+    if (int(loops.size()) > G.max_loops)
         return fail(ctx, MLH_ERR_UNSUPPORTED, (std::string(entry) + ": " + std::to_string(loops.size()) + " loop edges between the earliest looped keyframe and cur_index; at most " +
-                                               std::to_string(PG_MAX_LOOPS) + " are supported (mlh_pg_info::max_loops)").c_str());
+                                               std::to_string(G.max_loops) + " are supported (mlh_pg_info::max_loops; mlh_pg_reserve raises it up to " +
+                                               std::to_string(int(MLH_PG_LOOPS_LIMIT)) + ")").c_str());
     P.L = int(loops.size()); P.m = 6 * P.L; P.ncol = P.m + 1; P.ncp = ((P.ncol + 31) / 32) * 32;
+    const bool blocked = P.L > PG_MAX_LOOPS;
+    if (blocked) { P.T = pg_dense_panels(P.m); P.Tb = pg_dense_row_tiles(P.m); P.ld = P.Tb * PG_PANEL; }
     const size_t gbytes = size_t(P.ncp) * P.ncp * sizeof(double);
     const int ks_max = int(std::max<size_t>(1, (size_t(128) << 20) / gbytes));
     int rows_per = std::max(256, (P.n + 63) / 64);
@@ -730,10 +922,19 @@ int pg_problem(mlh_ctx *ctx, const char *entry, int cur_index, const mlh_pg_opts
     const auto take = [&](size_t doubles) { const size_t at = off; off += ((doubles + 1 + 15) / 16) * 16; return at; };
     const size_t o_x = take(2 * M * 7), o_meas = take(M * PG_SEQ * 7), o_lr = take(2 * E * 6), o_Ji = take(2 * E * 36), o_Jj = take(2 * E * 36), o_ce = take(2 * E),
                  o_sas = take(E), o_Bb = take(NB * 180), o_hd = take(NB * 6), o_g = take(NB * 6), o_S = take(NB * 6), o_diag = take(NB * 6), o_gs = take(NB * 6),
-                 o_gm = take(NB), o_Lrow = take(NB * 180), o_Linv = take(NB * 6), o_Y = take(n * P.ncp), o_G = take(size_t(P.ks) * P.ncp * P.ncp), o_C = take(m * m),
-                 o_z = take(m), o_rv = take(n), o_step = take(n), o_red = take(3 * M), o_loops = take((size_t(P.L) + 1) / 2 + 1);
+                 o_gm = take(NB), o_Lrow = take(NB * 180), o_Linv = take(NB * 6), o_Y = take(n * P.ncp), o_G = take(size_t(P.ks) * P.ncp * P.ncp),
+                 o_C = take(blocked ? size_t(P.T) * PG_PANEL * P.ld : m * m), o_z = take(blocked ? size_t(P.T) * PG_PANEL : m), o_rv = take(n), o_step = take(n),
+                 o_red = take(3 * M), o_loops = take((size_t(P.L) + 1) / 2 + 1), o_zw = take(blocked ? size_t(P.T) * PG_PANEL : 0),
+                 o_Dg = take(blocked ? size_t(P.T) * PG_PANEL * PG_PANEL : 0);
     const size_t before = G.work.cap + G.state.cap + G.h_pin.cap;
-    MLH_HIP(ctx, G.work.ensure(off * sizeof(double)));
+    {   // (ensure frees before it allocates: after a failure the work buffer is empty and the next call allocates again; the keyframe store is not touched)
+        const hipError_t e = G.work.ensure(off * sizeof(double));
+        if (e != hipSuccess) {
+            G.work.p = nullptr; G.work.cap = 0;
+            (void)hipGetLastError();
+            return fail(ctx, MLH_ERR_HIP, (std::string(entry) + ": the work buffers of " + std::to_string(off * sizeof(double)) + " bytes could not be allocated").c_str(), e);
+        }
+    }
     MLH_HIP(ctx, G.state.ensure(sizeof(PgState)));
     MLH_HIP(ctx, G.h_pin.ensure(sizeof(PgState), 0, true));
     if (G.work.cap + G.state.cap + G.h_pin.cap != before) ++G.allocations;
@@ -741,7 +942,7 @@ int pg_problem(mlh_ctx *ctx, const char *entry, int cur_index, const mlh_pg_opts
     P.kf = G.kf.as<PgKeyframe>();
     P.x = w + o_x; P.meas = w + o_meas; P.lr = w + o_lr; P.lJi = w + o_Ji; P.lJj = w + o_Jj; P.cost_e = w + o_ce; P.sas_e = w + o_sas; P.Bb = w + o_Bb; P.hd = w + o_hd;
     P.g = w + o_g; P.S = w + o_S; P.diag = w + o_diag; P.gs = w + o_gs; P.gm = w + o_gm; P.Lrow = w + o_Lrow; P.Linv = w + o_Linv; P.Y = w + o_Y; P.Gpart = w + o_G;
-    P.C = w + o_C; P.z = w + o_z; P.rvec = w + o_rv; P.step = w + o_step; P.red = w + o_red; P.loops = reinterpret_cast<int *>(w + o_loops);
+    P.C = w + o_C; P.z = w + o_z; P.zw = w + o_zw; P.Dg = w + o_Dg; P.rvec = w + o_rv; P.step = w + o_step; P.red = w + o_red; P.loops = reinterpret_cast<int *>(w + o_loops);
     P.st = G.state.as<PgState>();
     hipStream_t st = ctx->stream;
     if (P.L) MLH_HIP(ctx, hipMemcpyAsync(P.loops, loops.data(), sizeof(int) * loops.size(), hipMemcpyHostToDevice, st));
@@ -811,12 +1012,26 @@ int pg_enqueue_solve(mlh_ctx *ctx, const PgDev &P, int loop_head, PgTimer *T = n
         pg_mark(T, PG_T_FORWARD);
         MLH_LAUNCH(pg_gram_kernel, dim3(nmt * (nmt + 1) / 2, P.ks), dim3(PG_WAVE), 0, st, P);
         pg_mark(T, PG_T_GRAM);
-        MLH_LAUNCH(pg_dense_kernel, dim3(1), dim3(PG_TPB), 0, st, P);
+        if (P.L <= PG_MAX_LOOPS) {
+            MLH_LAUNCH(pg_dense_kernel, dim3(1), dim3(PG_TPB), 0, st, P);
+            ++G.launches;
+        } else {
+            const int ns = pg_dense_launches(P.m);
+            for (int s = 0; s < ns; ++s) {
+                const PgDenseStep d = pg_dense_step(P.m, s);
+                const dim3 grid(unsigned(d.hi - d.lo));
+                if (d.kind == PG_STEP_SUM) MLH_LAUNCH(pg_csum_kernel, grid, dim3(PG_TPB), 0, st, P);
+                else if (d.kind == PG_STEP_UPDATE) MLH_LAUNCH(pg_cupdate_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
+                else if (d.kind == PG_STEP_PANEL) MLH_LAUNCH(pg_cpanel_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
+                else MLH_LAUNCH(pg_cback_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
+            }
+            G.launches += ns;
+        }
         pg_mark(T, PG_T_DENSE);
         MLH_LAUNCH(pg_yz_kernel, dim3(pg_blocks(P.n)), dim3(PG_TPB), 0, st, P);
         MLH_LAUNCH(pg_back_kernel, dim3(1), dim3(PG_WAVE), 0, st, P);
         pg_mark(T, PG_T_BACK);
-        G.launches += 5;
+        G.launches += 4;
     }
     return MLH_OK;
 }
@@ -997,6 +1212,15 @@ int mlh_pg_reset(mlh_ctx *ctx)
     return MLH_OK;
 }
 
+int mlh_pg_reserve(mlh_ctx *ctx, int32_t max_loops)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (max_loops < PG_MAX_LOOPS || max_loops > MLH_PG_LOOPS_LIMIT)
+        return fail(ctx, MLH_ERR_INVALID, ("mlh_pg_reserve: max_loops must lie in " + std::to_string(PG_MAX_LOOPS) + " .. " + std::to_string(int(MLH_PG_LOOPS_LIMIT))).c_str());
+    ctx->pg.max_loops = max_loops;
+    return MLH_OK;
+}
+
 int mlh_pg_info(mlh_ctx *ctx, mlh_pg_info_t *out)
 {
     if (!ctx) return MLH_ERR_INVALID;
@@ -1006,7 +1230,7 @@ int mlh_pg_info(mlh_ctx *ctx, mlh_pg_info_t *out)
     out->n_keyframes = G.count;
     for (int v : G.loop_index) out->n_loops += v >= 0;
     out->earliest_loop_index = G.earliest_loop;
-    out->max_loops = PG_MAX_LOOPS;
+    out->max_loops = G.max_loops;
     out->allocations = G.allocations;
     out->bytes_hbm = int64_t(G.kf.cap + G.work.cap + G.state.cap);
     return MLH_OK;

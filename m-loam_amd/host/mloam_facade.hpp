@@ -2673,6 +2673,10 @@ class PoseGraph {
 public:
     explicit PoseGraph(Device &dev) : dev_(dev) { mlh_pg_opts_default(&opts_); dev_.check(mlh_pg_reset(dev_.ctx())); }
     mlh_pg_opts &options() { return opts_; }
+    // the largest number of loop edges one optimisation may hold: 128 until this is called, up to MLH_PG_LOOPS_LIMIT (the reference has no limit; the memory behind
+    // it -- include/mloam_hip.h (f14), mlh_pg_reserve -- is the caller's decision). Allocates nothing.
+    void reserveLoops(int max_loops) { dev_.check(mlh_pg_reserve(dev_.ctx(), max_loops)); }
+    int maxLoops() const { return info().max_loops; }
     // cur_kf->index_ = global_index_++ (cpp:94-95): the index the keyframe got
     int addKeyFrame(const PoseT &pose_w)
     {

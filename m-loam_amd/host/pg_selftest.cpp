@@ -4,11 +4,14 @@
 //   - after updateLoopInfo one pass runs: M = 27 keyframes, L = 1, the cost falls, the relative pose of the looped pair moves towards the measurement, keyframes 0 and
 //     1 keep their bits, the last pose of every problem keyframe is its pose before the pass, keyframe 29 is pose_drift * its old pose;
 //   - the same calls through the plain C-ABI on a second context end in the same bits;
-//   - a second pass from the optimised poses runs and leaves the first pass's poses as the last poses.
+//   - a second pass from the optimised poses runs and leaves the first pass's poses as the last poses;
+//   - the capacity of loop edges is 128 until reserveLoops raises it, a value outside 128 .. MLH_PG_LOOPS_LIMIT is refused, and a new PoseGraph on the same device
+//     (its constructor resets the store) keeps what was reserved.
 // Usage: pg_selftest  (exit status 0 = pass)
 #include <cmath>
 #include <cstdio>
 #include <cstring>
+#include <exception>
 #include <vector>
 
 #include "mloam_facade.hpp"
@@ -122,6 +125,15 @@ int main()
     pg.clearPgoFlag();
     EXPECT(pg.optimizePoseGraph(29) && pg.pgoFlag());
     for (int k = 2; k < N; ++k) { Pose last; pg.getLastPose(k, last); EXPECT(same_bits(last, got[size_t(k)])); }
+
+    // the capacity of loop edges
+    EXPECT(pg.maxLoops() == 128);
+    pg.reserveLoops(300);
+    EXPECT(pg.maxLoops() == 300);
+    bool refused = false;
+    try { pg.reserveLoops(MLH_PG_LOOPS_LIMIT + 1); } catch (const std::exception &) { refused = true; }
+    EXPECT(refused && pg.maxLoops() == 300);
+    { PoseGraph<Pose> again(dev); EXPECT(again.getKeyFrameSize() == 0 && again.maxLoops() == 300); }
 
     if (fails) { std::printf("pg_selftest: %d check(s) failed\n", fails); return 1; }
     std::printf("pg_selftest: ok\n");

@@ -1,6 +1,9 @@
 """Pose-graph optimisation on the MI355X (mlh_pg_optimize; m-loam_amd/csrc/posegraph.hip) at M = 500 / 2000 / 5000 keyframes with L = 5 / 20 / 50 loop edges:
 1 m steps on a gentle curve with small random rotations and a drifting estimate (tests/pg_cases.py's generator), loop l from keyframe M - 1 - 3 l back to keyframe
 7 l (so the problem starts at keyframe 0 and ends at M - 1), each measured at the true relative pose plus 1 cm / 1 mrad.
+--shapes M:L[,M:L...] picks other shapes; a shape with L > 50 closes loop l from keyframe M - 1 - 3 l back to keyframe l, and one with L > 128 reserves the
+capacity first (mlh_pg_reserve) and runs the blocked dense stage. The many-loop legs are --shapes 2000:256, 5000:512 and 5000:1024, the boundary comparison of
+the two dense stages --shapes 2000:128 and 2000:129: ONE process per leg, so that no leg inherits another's buffers or clocks.
   optimize      mlh_pg_optimize, host clock around the call (its one host wait included); the graph is uploaded again before every repetition, outside the clock
   stage legs    mlh_pg_time_stages: the same launches without the write-back, an event behind every stage, summed over the iterations of the pass: linearize,
                 assemble, band_factor (also per block column: the time over (M - 1) x the iterations that factored), substitution, gram, dense_solve,
@@ -11,7 +14,7 @@
                 between the device's pass and the restatement's
 Host clock / events after warm-up; median with p10 / p90. One JSON line per leg on stdout and appended to --out; every line carries --parent (the commit the work
 was measured on top of).
-Usage: python scripts/pgbench.py [--reps 10] [--warmup 2] [--cpu-m 500] [--parent <hash>] [--out profiles/f14_pgbench.jsonl]"""
+Usage: python scripts/pgbench.py [--reps 10] [--warmup 2] [--cpu-m 500] [--shapes M:L,...] [--parent <hash>] [--out profiles/f14_pgbench.jsonl]"""
 import argparse
 import importlib
 import json
@@ -35,6 +38,7 @@ def main():
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--cpu-m", type=int, default=500)
+    ap.add_argument("--shapes", default=None, help="M:L[,M:L...] instead of the three default shapes")
     ap.add_argument("--parent", default="unknown")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
@@ -52,8 +56,12 @@ def main():
         lines.append(line)
 
     ctx = mla.Context(0)
-    for M, L in SHAPES:
-        loops = [(M - 1 - 3 * l, 7 * l) for l in range(L)]
+    shapes = SHAPES if args.shapes is None else tuple(tuple(int(v) for v in sh.split(":")) for sh in args.shapes.split(","))
+    for M, L in shapes:
+        loops = [(M - 1 - 3 * l, 7 * l if L <= 50 else l) for l in range(L)]
+        assert all(0 <= i < j for j, i in loops), "the shape's loops do not fit"
+        if L > 128:
+            ctx.pg_reserve(mla.PG_LOOPS_LIMIT)
         G = pc.make_graph(M + 3, loops, seed=100 + L, drift_t=2e-3, drift_r=2e-4)
         cur = M - 1
         shape = dict(M=M, L=L)
