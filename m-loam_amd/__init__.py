@@ -1725,6 +1725,15 @@ class Context:
                                               C.byref(cost), C.byref(cnt)))
         return dict(valid=valid, coeffs=coeffs, r=r, J=J, H=H, g=g, cost=cost.value, count=cnt.value)
 
+    def match_coeffs(self, kind):
+        """mlh_match_coeffs: validity and coefficients of the correspondences the last launch that matched `kind` left on the device -> valid (m,), coeffs (m, 6), count"""
+        m = self._m[kind]
+        valid = np.zeros(m, np.uint8)
+        coeffs = np.zeros((m, 6), np.float64)
+        n = C.c_int32(0)
+        self._ck(self.lib.mlh_match_coeffs(self.h, kind, _p(valid), _p(coeffs), C.byref(n)))
+        return dict(valid=valid, coeffs=coeffs, count=n.value)
+
     def match_neighbours(self, kind):
         """mlh_match_neighbours: the neighbour records of the last correspondence launch of `kind` -> (m, stride, 4) float32 [x y z squared distance]"""
         stride = C.c_int32(0)
