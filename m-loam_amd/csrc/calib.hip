@@ -282,8 +282,10 @@ static int calib_grow(mlh_ctx *ctx, int n_tiles_new)
     return MLH_OK;
 }
 
-int calib_add(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info, const int32_t *ext_idx)
+extern "C" int mlh_calib_add(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info, const int32_t *ext_idx)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n <= 0 || !type || !points || !coeffs || !ext_idx) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: bad arguments");
     for (int i = 0; i < n; ++i) {
         if (type[i] != 0 && type[i] != 1) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: factor type must be 0 (plane) or 1 (edge)");
@@ -337,14 +339,17 @@ int calib_accumulate(mlh_ctx *ctx, int kind, int ext_idx)
     return MLH_OK;
 }
 
-int calib_use(mlh_ctx *ctx, int on)
+extern "C" int mlh_calib_use(mlh_ctx *ctx, int on)
 {
+    if (!ctx) return MLH_ERR_INVALID;
     ctx->calib.in_use = on != 0;
     return MLH_OK;
 }
 
-int calib_clear(mlh_ctx *ctx)
+extern "C" int mlh_calib_clear(mlh_ctx *ctx)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     CalibStore &S = ctx->calib;
     if (S.n_valid_dev.p) MLH_HIP(ctx, hipMemsetAsync(S.n_valid_dev.p, 0, sizeof(int), ctx->stream));
     S.h_tile_ext.clear();
@@ -352,8 +357,10 @@ int calib_clear(mlh_ctx *ctx)
     return MLH_OK;
 }
 
-int calib_info(mlh_ctx *ctx, mlh_calib_store_info *out)
+extern "C" int mlh_calib_info(mlh_ctx *ctx, mlh_calib_store_info *out)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (!out) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_info: null output");
     CalibStore &S = ctx->calib;
     int n_dev = 0;
@@ -411,8 +418,10 @@ void calib_ne_enqueue(mlh_ctx *ctx, const double *poses_dev, int n_frames, int n
     MLH_LAUNCH(calib_ne_add_kernel, dim3(1), dim3(1024), 0, ctx->stream, F);
 }
 
-int calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians)
+extern "C" int mlh_calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     CalibStore &S = ctx->calib;
     if (S.device_built) return fail(ctx, MLH_ERR_STATE, "mlh_calib_evaluate: per-factor outputs need a store made by mlh_calib_add alone: a device-built one is padded");
     if (S.n_given <= 0) return fail(ctx, MLH_ERR_STATE, "mlh_calib_evaluate: the store is empty");
@@ -435,3 +444,21 @@ int calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residual
 }
 
 }  // namespace mlh
+
+using namespace mlh;
+
+extern "C" {
+
+int mlh_calib_accumulate(mlh_ctx *ctx, int kind, const double rel_pose[7], int k_neigh, uint32_t flags, float min_match_sq_dis, float min_plane_dis, int ext_idx)
+{
+    if (!ctx || kind < 0 || kind > 1 || !rel_pose) return MLH_ERR_INVALID;
+    if (k_neigh != 5 && k_neigh != 10) return fail(ctx, MLH_ERR_UNSUPPORTED, "N_NEIGH is 5 or 10");
+    if (ext_idx < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_accumulate: negative extrinsic index");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = match_for_factors(ctx, kind, rel_pose, k_neigh, flags, min_match_sq_dis, min_plane_dis);      // as mlh_pure_odom_add_matches: the correspondences stay in HBM
+    if (rc) return rc;
+    ctx->map_read_unsynced = true;
+    return calib_accumulate(ctx, kind, ext_idx);
+}
+
+}  // extern "C"

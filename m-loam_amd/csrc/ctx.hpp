@@ -5,6 +5,7 @@
 #include <cstdio>
 #include <cstring>
 #include <atomic>
+#include <cfloat>
 #include <chrono>
 #include <cstddef>
 #include <memory>
@@ -97,7 +98,7 @@ static_assert(offsetof(HostPublish, x) == 0 && offsetof(HostPublish, xb) == 56 &
               "the publication record: pose, block poses, done word and sequence word where they have always been; the two matrices behind them");
 
 // ---------------------------------------------------------------- the solver's launch modes
-// Named once, here; the hosts (capi.hip, the launchers of match.hip / track.hip) and the kernels use the names, never the numbers. Unscoped, `int` underneath and
+// Named once, here; the hosts (solve_host.hip, the launchers of match.hip / track.hip) and the kernels use the names, never the numbers. Unscoped, `int` underneath and
 // the values the fields have always had: the parameter blocks' layouts and the kernels' comparisons are what they were.
 enum LaunchTail : int {   // ::finish -- what the last workgroup of a fit / linearise launch does behind its tiles' records
     TAIL_RECORDS = 0,     // nothing: the launch leaves the records (a consumer sums them)
@@ -592,6 +593,50 @@ struct TrackArgs {
     unsigned long long publish_seq = 0;
 };
 
+// The body-frame union of the LiDARs' mapping features (mlh_fuse_* / mlh_fused_cloud, frontend.hip). Appends never wait for the host: the record counts and the
+// appends' partial bounding boxes stay on the device while `dirty`; mlh_fused_cloud publishes them once. n[] and minmax[] are the clouds' while !dirty. Nothing
+// but frontend.hip and the predicates that recognise a fused cloud among a caller's inputs (is_fused_cloud / is_fused_pair) reads or writes the members.
+struct FusedClouds {
+    DevBuf pts[2];             // float4 {x,y,z,lidar index}
+    int n[2] = {0, 0};         // valid when !dirty
+    float minmax[2][6];        // folded by mlh_fused_cloud: the voxel filter of a fused cloud needs no bounds pass of its own
+    bool dirty = false;
+    size_t bound[2] = {0, 0};  // host-side upper bounds of the counts (capacity)
+    DevBuf cnt;                // the two record counts, device side: a prefix table, one pair per append
+    DevBuf part;               // per-append, per-kind, per-workgroup partial bounds of the appended points
+    int parts = 0;             // appends since the reset
+    PinnedBuf host;            // one FusedPublish
+    unsigned long long seq = 0;
+    void mark_dirty() { dirty = true; }
+    void publish_empty()       // no records, boxes that contain nothing
+    {
+        n[0] = n[1] = 0;
+        for (int k = 0; k < 2; ++k) for (int d = 0; d < 6; ++d) minmax[k][d] = d < 3 ? FLT_MAX : -FLT_MAX;
+        dirty = false;
+    }
+    void take_published()      // what the publication launch left in `host`
+    {
+        const FusedPublish *pub = host.as<FusedPublish>();
+        n[0] = pub->count[0]; n[1] = pub->count[1];
+        for (int k = 0; k < 2; ++k) for (int d = 0; d < 6; ++d) minmax[k][d] = pub->box[k * 6 + d];
+        dirty = false;
+    }
+};
+
+// Launches of one context that read what ANOTHER context of the same device holds (mlh_fuse_add_scan_from, mlh_window_set_from_scan: its scan buffers;
+// mlh_features_copy, mlh_keyframes_update_from_pose_graph: copies the call itself waits for). Ordered on the device, in two halves: borrow_begin makes the
+// reader's stream wait for the owner's work so far (an event of the reader's on the owner's stream); borrow_end leaves, behind the reading launches, an event of
+// the OWNER's on the reader's stream, which wait_readers makes the owner's next rewrite of its scan wait for. ONE reader context per owner: a second reader
+// would record over the first one's event. The owner is idle while another thread borrows from it: `reader_pending` is the only word both threads touch.
+struct ScanHandoff {
+    hipEvent_t ev_handover = nullptr;      // the reader's: recorded on the owner's stream, waited for on the reader's
+    hipEvent_t ev_reader = nullptr;        // the owner's: recorded on the reader's stream behind its reading launches
+    std::atomic<bool> reader_pending{false};
+    int wait_readers(mlh_ctx *ctx);                   // ctx: the owner, in front of whatever rewrites its scan buffers
+    int borrow_begin(mlh_ctx *ctx, mlh_ctx *src);     // ctx: the reader (this struct's context), src: the owner
+    int borrow_end(mlh_ctx *ctx, mlh_ctx *src);
+};
+
 struct Profile {
     unsigned mask = 0;     // bit k: bracket launches of kernel id k
     int every = 1;         // bracket every n-th launch of a kernel id only (event pairs cost ~6 us of host/queue time each)
@@ -711,10 +756,10 @@ struct mlh_ctx {
         bool valid = false, consumed_recorded = false, src_pinned = false;
         unsigned long long issued = 0, used = 0;     // (tests)
     } ahead;
-    mlh::PinnedBuf h_state;  // three HostPublish records the device writes the result pose(s) into (capi.hip: publish_slot)
+    mlh::PinnedBuf h_state;  // three HostPublish records the device writes the result pose(s) into (solve_host.hip: publish_slot)
     mlh::PinnedBuf h_occ;    // mirror of the two maps' occupancy totals (grid.hip): {cells, squares} per kind, written behind every index build
     unsigned long long publish_seq = 0;
-    // mlh_scan2map_cov: the two matrices of the most recently collected scan2map solve, copied out of its pinned record at collection (capi.hip: pose_cov_*)
+    // mlh_scan2map_cov: the two matrices of the most recently collected scan2map solve, copied out of its pinned record at collection (solve_host.hip: pose_cov_*)
     struct PoseCov {
         enum State : int { NONE /* nothing collected yet */, VALID, UNFLAGGED /* collected without MLH_FLAG_POSE_COV */, NOT_A_RESULT /* its pose_out was not a result */ } state = NONE;
         double H[36], cov[36];
@@ -733,16 +778,11 @@ struct mlh_ctx {
     mlh::InitExtStore ie;    // the initial extrinsic calibration (initext.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;
-    mlh::DevBuf fused[2];    // body-frame union of the LiDARs' mapping features (mlh_fuse_*): float4 {x,y,z,lidar index}
-    int fused_n[2] = {0, 0};   // valid when !fused_dirty
+    mlh::FusedClouds fused;  // body-frame union of the LiDARs' mapping features (mlh_fuse_*)
     mlh::PinnedBuf h_dev_err;   // one int a kernel sets when it has to give up (device std::sort: a wait that was never released); see device_error_check
     mlh::PinnedHalves h_rings;  // the ring tables of mlh_scan_upload on their way to the device
-    hipEvent_t ev_handover = nullptr;      // mlh_features_copy: recorded on the source context's stream, waited for on this one's
-    // mlh_fuse_add_scan_from(dst, this): a launch on ANOTHER context's stream reads this context's scan buffers; recorded there behind it, waited for on this
-    // context's stream by whatever rewrites the scan next (scan_wait_readers). Set by the thread that drives dst while this context is idle.
-    hipEvent_t ev_scan_reader = nullptr;
-    std::atomic<bool> scan_reader_pending{false};
-    mlh::PinnedBuf h_sync;                  // the word stream_wait_spin's launch stores into
+    mlh::ScanHandoff handoff;              // this context as the reader, or the owner, of a cross-context read
+    mlh::PinnedBuf h_sync;                 // the word stream_wait_spin's launch stores into
     unsigned long long sync_seq = 0;
     unsigned long long counts_seq = 0;      // publications of the thinned feature counts straight from a kernel (voxel.hip)
     // downsample_current_scan_pair_run(.., defer = true): the thinning was enqueued and NOT waited for -- where its two counts will be (device; pinned host + the
@@ -752,14 +792,6 @@ struct mlh_ctx {
     const unsigned long long *thin_seq_host = nullptr;
     unsigned long long thin_seq = 0;
     mlh::PinnedBuf h_scratch;   // one ScratchBlock: the landing place of the few-int read-backs (record counts) that end a staging call
-    mlh::PinnedBuf fused_host;  // one FusedPublish
-    unsigned long long fused_seq = 0;
-    mlh::DevBuf fused_cnt;   // the two record counts, device side (appends never wait for the host)
-    size_t fused_bound[2] = {0, 0};   // host-side upper bounds of the counts (capacity)
-    bool fused_dirty = false;
-    mlh::DevBuf fused_part;  // per-append, per-kind, per-workgroup partial bounds of the appended points
-    int fused_parts = 0;
-    float fused_minmax[2][6];   // folded by mlh_fused_cloud: the voxel filter of a fused cloud needs no bounds pass of its own
     int knn_lanes_override = 0;   // MLH_KNN_LANES=8|16|32, or SSCC (816, 832, 1632: surf lanes, corner lanes), in the environment at mlh_create: pins the correspondence kernel's lanes per query (tests, tuning)
     int knn_wg_override = 0;      // MLH_KNN_WG_THREADS=256|512|1024, in the environment at mlh_create: pins the workgroup width of the correspondence launches that have wide forms (match.hip: knn_wg_threads_for; tests, A/B runs)
     int knn_wg_last = 0;          // the width the last such launch took
@@ -830,6 +862,27 @@ int fail_launch(mlh_ctx *ctx, const char *kernel, hipError_t e);
         }                                                                          \
     } while (0)
 
+inline int ScanHandoff::wait_readers(mlh_ctx *ctx)
+{
+    if (reader_pending.exchange(false, std::memory_order_acq_rel)) MLH_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev_reader, 0));
+    return MLH_OK;
+}
+inline int ScanHandoff::borrow_begin(mlh_ctx *ctx, mlh_ctx *src)
+{
+    if (!ev_handover) MLH_HIP(ctx, hipEventCreateWithFlags(&ev_handover, hipEventDisableTiming));
+    MLH_HIP(ctx, hipEventRecord(ev_handover, src->stream));
+    MLH_HIP(ctx, hipStreamWaitEvent(ctx->stream, ev_handover, 0));
+    return MLH_OK;
+}
+inline int ScanHandoff::borrow_end(mlh_ctx *ctx, mlh_ctx *src)
+{
+    ScanHandoff &owner = src->handoff;
+    if (!owner.ev_reader) MLH_HIP(ctx, hipEventCreateWithFlags(&owner.ev_reader, hipEventDisableTiming));
+    MLH_HIP(ctx, hipEventRecord(owner.ev_reader, ctx->stream));
+    owner.reader_pending.store(true, std::memory_order_release);
+    return MLH_OK;
+}
+
 // ---- intake of a caller's records (records.hpp, capi.hip): every entry point that takes a cloud validates it with records_check (MLH_ERR_INVALID, mlh_last_error
 // = "<entry>: bad <argument>") and reads it where records_stage says; the *_run functions below take records their entry point has validated
 int records_check(mlh_ctx *ctx, const char *entry, const mlh::Records &r, bool allow_empty = false);
@@ -839,6 +892,10 @@ int records_stage(mlh_ctx *ctx, const mlh::Records &r, mlh::DevBuf &staging, hip
 // the one pack kernel: records -> float4 {x, y, z, w} (+ the covariance diagonal when covd != nullptr); w = the f32 at byte offset w_off >= 0, or one of
 enum { PACK_W_ZERO = -1, PACK_W_INDEX = -2 /* the record's index, as int bits */, PACK_W_VALUE = -3 /* w_value */ };
 void pack_points_launch(hipStream_t st, const unsigned char *dev, int stride, int n, int w_off, float w_value, int cov_off, float4 *out, float4 *covd);
+int stage_points(mlh_ctx *ctx, const mlh::Records &r, int w_off, mlh::DevBuf &dst, mlh::DevBuf *covd, mlh::DevBuf &tmp, const unsigned char **dev_src = nullptr);
+// "hex[,hex...]" -> CU-mask words / the first half of the device's compute units as mask words (capi.hip; the solver's and the staging stream's masks)
+std::vector<uint32_t> parse_cu_mask(const char *text, int cu_count);
+std::vector<uint32_t> lower_half_cu_mask(int cu_count);
 
 // profiling brackets (HIP events on the context's stream)
 void prof_begin(mlh_ctx *ctx, int id);
@@ -847,54 +904,31 @@ void prof_collect(mlh_ctx *ctx);
 // events whose timestamps come from the dispatch itself (hipExtLaunchKernelGGL); false when kernel id is not profiled
 bool prof_kernel_events(mlh_ctx *ctx, int id, hipEvent_t *start, hipEvent_t *stop);
 
-// extract.hip
+// extract.hip, scan.hip
 int extract_run(mlh_ctx *ctx);
+int scan_totals(mlh_ctx *ctx, bool want_vox);
 // voxel.hip
 int ring_voxel_run(mlh_ctx *ctx, float leaf);
-int point_uncertainty_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int mem, const double *ext_poses,
-                          const double *ext_covs, int n_lidar, const double cov_meas[9], double trace_thr, float *cov6_host, int *keep_host);
 // track.hip
 int track_set_prev_rings(mlh_ctx *ctx, int kind, const unsigned char *d_src, int stride, int n, int intensity_off, int *host_bad);
 int track_match_launch(mlh_ctx *ctx, int kind_mask, const mlh::TrackArgs &a);
 int track_linearize_launch(mlh_ctx *ctx, int kind_mask, const mlh::TrackArgs &a);
 int track_lm_loop_launch(mlh_ctx *ctx, int kind_mask, const mlh::TrackArgs &a);      // one round's whole LM loop (begin at the round's pose .. termination) in one launch
-// segment.hip
-int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensity_off, int n, int mem, const mlh_segment_params &prm,
-                      float *cloud_out, int32_t *n_out, int32_t *scan_start, int32_t *scan_end, float *outlier_out, int32_t outlier_capacity, int32_t *n_outlier);
 // odom.hip
-int pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info,
-                  const int32_t *frame_idx, const int32_t *ext_idx);
-int pure_odom_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
-                       double *residuals, double *jacobians);
-int pure_odom_begin(mlh_ctx *ctx);
 int pure_odom_add_matches(mlh_ctx *ctx, int kind, int frame_idx, int ext_idx);
+// solve_host.hip: what mlh_pure_odom_add_matches, mlh_pure_odom_add_matches_gf and mlh_calib_accumulate begin with -- the state, rel_pose into it, one match pass
+// of `kind` whose correspondences (validity + f32 coefficients) stay in HBM
+int match_for_factors(mlh_ctx *ctx, int kind, const double rel_pose[7], int k_neigh, uint32_t flags, float min_match_sq_dis, float min_plane_dis);
 int pure_odom_feature_rows(mlh_ctx *ctx, int kind, const double pivot[7], const double pose_i[7], const double ext[7]);      // odom.hip: validity + scored rows of the staged features -> FeatSet::flag8 / J
-int pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
-                        double *H, double *g, double *cost, int32_t *n_res);
-int pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int n_frames, double *exts, int n_ext, double huber_delta, int n_iters,
-                       uint32_t const_block_mask, const double *V_update, double *cost, int32_t *n_res, int32_t *status_out);
 // the table's normal equations at the given state enqueued into OdomSet::ne_out (zeros for an empty table), the poses left in OdomSet::poses; nothing waited for
 // calib.hip: the store of accumulated LidarOnlineCalib factors and its term in the window's normal equations
-int calib_add(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info, const int32_t *ext_idx);
 int calib_accumulate(mlh_ctx *ctx, int kind, int ext_idx);       // appends the valid correspondences the last match pass of `kind` left in HBM
-int calib_use(mlh_ctx *ctx, int on);
-int calib_clear(mlh_ctx *ctx);
-int calib_info(mlh_ctx *ctx, mlh_calib_store_info *out);
-int calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *residuals, double *jacobians);
 bool calib_active(const mlh_ctx *ctx);                            // in use and not empty: the calls below have something to add
 int calib_ne_prepare(mlh_ctx *ctx, int n_ext);                    // MLH_ERR_INVALID when n_ext does not cover the store; buffers and tile lists for this n_ext
 // two launches behind the assembly: tile sums at the extrinsics of poses_dev ([pivot | frames | extrinsics], 7 each), then their addition into ne_dev (D*D + D + 2)
 void calib_ne_enqueue(mlh_ctx *ctx, const double *poses_dev, int n_frames, int n_ext, double huber_delta, double *ne_dev);
 int window_assemble(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta);
 // marg.hip
-int window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const double *x0, const double *J0, const double *r0);
-int window_prior_get(mlh_ctx *ctx, mlh_window_prior_info *info, int32_t *block_ids, double *x0, double *J0, double *r0);
-int window_prior_clear(mlh_ctx *ctx);
-int window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
-                          double *residuals, double *H, double *g, double *cost);
-int window_ext_prior_set(mlh_ctx *ctx, int n_ext, const double *rows, uint32_t flags);
-int window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
-                       mlh_window_prior_info *info_out);
 // MLH_OK, or MLH_ERR_STATE (text set) when the installed prior's block map -- or, with ext_bit, the extrinsic prior that bit enables -- does not fit the window
 int window_prior_fits(mlh_ctx *ctx, const char *entry, int n_frames, int n_ext, uint32_t ext_bit);
 bool window_prior_in_solve(const mlh_ctx *ctx);      // a prior, or extrinsic rows with bit 1, is installed: mlh_pure_odom_gn_solve adds the term
@@ -968,7 +1002,7 @@ inline ScratchBlock *scratch_block(mlh_ctx *ctx)
 // Everything enqueued on the context's stream so far (kernels, and copies into PINNED host memory) has completed when this returns. A one-thread launch stores a
 // sequence number into pinned host memory (system-scope release) and the host spins on that word: a few microseconds, where hipStreamSynchronize's wake-up
 // costs tens -- a mapper frame has three such read-backs (fused cloud sizes, thinned record counts, feature counts). Falls back to the blocking call after
-// 200 ms (a profiler, a fault). capi.hip has the definition.
+// 200 ms (a profiler, a fault). solve_host.hip has the definition.
 hipError_t stream_wait_spin(mlh_ctx *ctx);
 // the two halves of it: post a marker behind what is enqueued now; wait for a posted marker later
 hipError_t stream_flag_post(mlh_ctx *ctx, unsigned long long *seq_out);
@@ -1004,9 +1038,6 @@ void compound_pose_with_cov(const double p1[7], const double c1[36], const doubl
 int downsample_current_scan_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int mem, float leaf, const double *ext_poses,
                                 const double *ext_covs, int n_lidar, const double cov_meas[9], int with_ua, double trace_thr, mlh::DevBuf &pts_out,
                                 mlh::DevBuf &covd_out, float *out11_dev, int *n_out, const float *known_bounds = nullptr);
-int cloud_uct_associate_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off,
-                            const double pose_global[7], const double cov_global[36], const double *ext_poses, const double *ext_covs,
-                            int n_lidar, const double cov_meas[9], int with_ua, double trace_thr, void *out, int *n_out, int mem);
 int voxel_filter_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off, float leaf,
                      float trace_thr, void *out_host, int *n_out, int mem, const float *known_bounds = nullptr, bool sync_total = true,
                      bool centroid_all = false);
@@ -1058,54 +1089,8 @@ int grid_build_grids(mlh_ctx *ctx, mlh::MapGrid **grids, int n_grids, bool recom
 void knn_lanes_for(const mlh_ctx *ctx, int kind_mask, int lanes[2]);
 int map_stage_and_build(mlh_ctx *ctx, int n_maps, const int *kinds, const unsigned char *const *src, const int *n, int stride, const float *sq_dis,
                         mlh::HostPublish *pub, unsigned long long seq);
-// match.hip
-struct MatchArgs {
-    int kind_mask = 3;   // bit MLH_SURF, bit MLH_CORNER: which feature kinds take part in the launch
-    uint32_t flags = 0;
-    float min_match_sq_dis = 1.f, min_plane_dis = 0.2f;
-    double huber_delta = 0.1, cov_measurement_trace = 0.0075;
-    bool dense = false;  // also write r / J per feature
-    int pose_sel = 0;    // 0: SolverState::x, 1: SolverState::cand
-    LaunchTail finish = TAIL_RECORDS;
-    int lm_max_it = 30, lm_min_blocks = 0;
-    LmExpect lm_expect_done = LM_VERDICT_READ;   // read by the launch that runs an LM begin (TAIL_LM_BEGIN, LMC_BEGIN, LMC_LOOP)
-    int stat_slot = -1;
-    int n_blocks = 1;    // pose blocks
-    int k_neigh[8] = {5, 5, 5, 5, 5, 5, 5, 5};
-    double eig_thre[8] = {100, 100, 100, 100, 100, 100, 100, 100};
-    int freeze[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    const double *init_pose = nullptr;       // host: block 0's pose for this launch comes from the kernel arguments and is written to the state by the finish
-    // Gauss-Newton with the finish done by the consumer: this launch pair is iteration `gn_iter` of `gn_iters` (>= 2). The fit kernel of every iteration but
-    // the last only leaves its tiles' partial records; the correspondence kernel of iteration i >= 1 starts by summing them (every workgroup, same order, same
-    // bits) and running the 6 x 6 solve + Plus itself. gn_iter < 0: the classic form (the fit kernel's last-arriving workgroup finishes).
-    int gn_iter = -1, gn_iters = 0;
-    int gn_slot_base = 0;     // this solve's pair of SolverState::xi slots (0 or 2)
-    bool gn_blocks = false;   // the solve runs over pose blocks: per-block iteration poses in SolverState::xib
-    bool warm = false;   // the neighbour records of the previous iteration (same features, same map) bound this iteration's search
-    // iteration 0 of a CHAINED solve that also completes the PREVIOUS solve, whose last iteration left only its tiles' records (mlh_ctx::gn_pending): every workgroup of
-    // this correspondence launch sums them, solves, applies Plus -> the previous frame's final pose; tile 0's workgroup publishes it to that solve's host record and
-    // stores it as the state's pose; then the chained start pose of THIS frame (transformUpdate + transformAssociateToMap) is computed from it, in every workgroup
-    bool pre_final = false;
-    int pre_final_tiles = 0, pre_final_slot = 0, pre_final_freeze = 0;
-    double pre_final_thre = 100.0;
-    HostPublish *pre_final_publish = nullptr;
-    unsigned long long pre_final_seq = 0;
-    const double *chain_prev = nullptr, *chain_cur = nullptr;   // host: the two odometry poses of the chain (7 doubles each)
-    LmConsumer lmc = LMC_NONE;
-    int lmc_j = 0;       // lm_consume_launch: the launch's number within its loop (1, 2, ...: record buffer (j - 1) & 1 is read, j & 1 written)
-    // The fit of an outer iteration inside the loop launch that follows it (lm_loop_kernel<.., FIT>; one launch boundary fewer): match_launch with `no_fit` ends behind
-    // the correspondence kernel, lm_consume_launch (LMC_LOOP) with `fit_in_loop` begins with the fit. Only together, and only where loop_fit_fusable() says so (tagged
-    // records: the fit's record leaves as the loop's own do); capi.hip builds the pair in one place (s2m_loop_args).
-    bool no_fit = false, fit_in_loop = false;
-    const int *m_dev = nullptr;   // device: the two feature counts (surf, corner) when the host has not read them (mlh_downsample_scan2map); FeatSet::m then holds upper bounds
-    HostPublish *publish = nullptr;          // pinned host record the launch writes the pose(s) to: honoured by TAIL_GN, TAIL_LM_STEP and every consumer-side launch
-    unsigned long long publish_seq = 0;
-};
-int match_launch(mlh_ctx *ctx, const MatchArgs &a);
+// match.hip (its launchers and their arguments: solve_host.hpp)
 int gn_flush_pending(mlh_ctx *ctx);      // completes a pending last iteration with a one-workgroup launch (no-op when nothing is pending)
-int linearize_launch(mlh_ctx *ctx, const MatchArgs &a);
-int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a);
-bool loop_fit_fusable(const MatchArgs &loop_args);   // the loop launch described by these arguments would exchange tagged records (ctx.hpp: loop_tagged_arm's conditions)
 int lm_loop_occupancy(int blocks_per_cu[2], int blocks_per_cu_cov[2]);      // hipOccupancyMaxActiveBlocksPerMultiprocessor of lm_loop_kernel<false> / <true>; _cov: of the instantiations that publish the pose covariance
 int track_loop_occupancy(int *blocks_per_cu);     // ... of track_lm_loop_kernel (track.hip)
 // the arrival counters of the fused finishes and of lm_loop_kernel's barrier: four zeroed words, whoever asks first ([0]: the finish tickets of match.hip and

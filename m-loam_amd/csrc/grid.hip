@@ -13,6 +13,9 @@
 // so the next build starts from zeros without a clear launch; with few chunks (<= 4096) the add pass also sums the chunk
 // totals before it itself instead of a separate single-workgroup scan launch.
 #include "ctx.hpp"
+#include "solve_host.hpp"
+#include <cstdlib>
+#include <vector>
 #include <cmath>
 #include <climits>
 
@@ -592,3 +595,157 @@ int grid_build(mlh_ctx *ctx, int kind_mask, bool recompute_bounds)
 }
 
 }  // namespace mlh
+
+using namespace mlh;
+
+extern "C" {
+
+// ---------------------------------------------------------------- map
+// host records are copied to the staging buffer first (both clouds back to back); device records are read in place
+static int map_set_impl(mlh_ctx *ctx, int n_maps, const int *kinds, const void *const *points, const int *n, int stride_bytes, float min_match_sq_dis, int mem)
+{
+    if (ctx) ++ctx->stage_epoch;
+    if (!(min_match_sq_dis > 0.f)) return fail(ctx, MLH_ERR_INVALID, "min_match_sq_dis must be positive");
+    Records r[2];
+    size_t off[2] = {0, 0}, total = 0;
+    for (int k = 0; k < n_maps; ++k) {
+        r[k] = records_of(points[k], stride_bytes, n[k], mem);
+        { const int rc = records_check(ctx, n_maps == 1 ? "mlh_map_set" : "mlh_map_set_pair", r[k]); if (rc) return rc; }
+        off[k] = total; total += ((r[k].bytes() + 255) / 256) * 256;
+    }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    // the overlapped path runs on the staging stream beside whatever the main stream has queued (a scan upload's pack kernel may still be reading ctx->tmp):
+    // it stages through a buffer of its own
+    DevBuf &tmp = (ctx->stream2 && ctx->stream == ctx->stream2) ? ctx->tmp_stage : ctx->tmp;
+    if (mem == MLH_MEM_HOST) MLH_HIP(ctx, tmp.ensure(total));
+    const unsigned char *src[2] = {nullptr, nullptr};
+    for (int k = 0; k < n_maps; ++k) { const int rc = records_stage(ctx, r[k], tmp, ctx->stream, &src[k], off[k]); if (rc) return rc; }
+    HostPublish *pub;
+    unsigned long long seq;
+    int rc = publish_slot(ctx, &pub, &seq);
+    if (rc) return rc;
+    float sq[2] = {min_match_sq_dis, min_match_sq_dis};
+    rc = map_stage_and_build(ctx, n_maps, kinds, src, n, stride_bytes, sq, pub, seq);
+    if (rc) return rc;
+    for (int k = 0; k < n_maps; ++k) ctx->feat[kinds[k]].matched = false;
+    return MLH_OK;
+}
+
+int mlh_map_set(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int n, float min_match_sq_dis, int mem)
+{
+    if (!ctx || kind < 0 || kind > 1) return MLH_ERR_INVALID;
+    const void *pts[1] = {points};
+    return map_set_impl(ctx, 1, &kind, pts, &n, stride_bytes, min_match_sq_dis, mem);
+}
+
+int mlh_map_set_pair(mlh_ctx *ctx, const void *surf_points, int n_surf, const void *corner_points, int n_corner, int stride_bytes,
+                     float min_match_sq_dis, int mem)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    const int kinds[2] = {MLH_SURF, MLH_CORNER};
+    const void *pts[2] = {surf_points, corner_points};
+    const int n[2] = {n_surf, n_corner};
+    return map_set_impl(ctx, 2, kinds, pts, n, stride_bytes, min_match_sq_dis, mem);
+}
+
+// The next maps staged WHILE the main stream is busy with something that does not read a map: a submitted solve (mlh_gn_solve_begin) still running on the
+// current set, or -- no solve in flight, device-resident clouds -- the frame's own front end (upload, extractCloud, fusion, thinning: the local map comes from
+// earlier keyframes and does not wait for the scan). Pack + fit check + index build go to the context's second stream and into the other map set; the call
+// returns when they are complete (the host waits, the main stream does not) and the context has switched to the new set, so every launch enqueued after this
+// call reads it. With host-resident clouds and no solve in flight it behaves like mlh_map_set_pair (the upload staging buffer is shared with the main stream).
+int mlh_map_set_pair_overlapped(mlh_ctx *ctx, const void *surf_points, int n_surf, const void *corner_points, int n_corner, int stride_bytes,
+                                float min_match_sq_dis, int mem)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (!ctx->solves.pending() && mem != MLH_MEM_DEVICE) return mlh_map_set_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, min_match_sq_dis, mem);
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->map_read_unsynced) {
+        // mlh_pure_odom_add_matches returns with its map-reading launch still queued. Whatever set it reads, it must be done before a set is rewritten -- also
+        // with a solve in flight (begin(A); add_matches(A); overlapped -> B; end; begin(B); overlapped -> A would otherwise rewrite A under that launch): the
+        // main stream is drained, the solve included. Rare (the window's factor table is not built beside a pipelined mapper solve), so correctness first.
+        MLH_HIP(ctx, stream_wait_spin(ctx));
+        ctx->map_read_unsynced = false;
+    }
+    if (!ctx->stream2) {
+        // The staging stream may use the first half of the compute units: its kernels are atomics- / latency-bound and lose ~5 % on half the device, while the
+        // solver's launches they run beside lose less to them (step 0.1452 -> 0.1415 ms, three alternations in one gpurun call; every other CU, a quarter of the
+        // CUs and 8 CUs per 32 measured no better). The mask is sized from the device's compute-unit count. MLH_STAGE_CU_MASK=<hex word>[,<hex word>...]
+        // overrides (32 compute units per word; a single word is repeated over the first half of the words, a second one over the other half -- round 3's
+        // "lo,hi" form; "ffffffff,ffffffff" = no mask).
+        std::vector<uint32_t> words = lower_half_cu_mask(ctx->caps.cu_count);
+        if (const char *m = std::getenv("MLH_STAGE_CU_MASK")) {
+            const int nw = int(words.size());
+            std::vector<uint32_t> given = parse_cu_mask(m, 32 * nw);
+            int n_given = 1;
+            for (const char *q = m; *q; ++q) n_given += *q == ',';
+            if (!given.empty() && n_given <= 2 && nw > 2) {
+                const uint32_t lo = given[0], hi = n_given == 2 ? given[1] : given[0];
+                for (int i = 0; i < nw; ++i) given[size_t(i)] = i < nw / 2 ? lo : hi;
+            }
+            if (!given.empty()) {
+                if (ctx->caps.cu_count % 32) given.back() &= (1u << (ctx->caps.cu_count % 32)) - 1u;
+                words = given;
+            }
+        }
+        int bits = 0;
+        for (uint32_t w : words) bits += __builtin_popcount(w);
+        if (bits <= 0 || bits >= ctx->caps.cu_count) MLH_HIP(ctx, hipStreamCreateWithFlags(&ctx->stream2, hipStreamNonBlocking));
+        else {
+            MLH_HIP(ctx, hipExtStreamCreateWithCUMask(&ctx->stream2, uint32_t(words.size()), words.data()));
+            ctx->caps.staging_masked = true;
+        }
+        for (int i = 0; i < 2; ++i) MLH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_set_built[i], hipEventDisableTiming));
+    }
+    // The other set's last reader is the solve submitted BEFORE the one in flight; with at most one solve in flight here it has been collected, i.e. it is done:
+    // no device-side wait is needed before its buffers are overwritten. (Round 3 first ordered the two streams with events on the solver's stream -- a record
+    // after every solve, a wait before the next: two barrier packets, ~10 us of idle stream per frame in the kernel trace. Both are gone: the host orders.)
+    if (ctx->solves.in_flight() > 1) return fail(ctx, MLH_ERR_STATE, "collect the older solve (mlh_gn_solve_end) before staging the next frame's maps");
+    const int target = 1 - ctx->map_set_cur;
+    // ... unless the caller stages twice beside ONE solve (begin on A; overlapped -> B; overlapped -> A again with that solve uncollected): then the target's reader
+    // is the solve in flight, and the set is rewritten only once the main stream has run dry (scripts/soak_schedule.py found this as a rare, timing-dependent
+    // difference of 1e-5 m: the index of A rebuilt under a correspondence launch)
+    if (ctx->solves.set_has_reader(target)) MLH_HIP(ctx, stream_wait_spin(ctx));
+    hipStream_t main_stream = ctx->stream;
+    ctx->stream = ctx->stream2;                    // everything map_set_impl enqueues (and its profiling brackets) goes to the staging stream ...
+    ctx->map = ctx->map_sets[target];              // ... and into the other set
+    const int kinds[2] = {MLH_SURF, MLH_CORNER};
+    const void *pts[2] = {surf_points, corner_points};
+    const int n[2] = {n_surf, n_corner};
+    const int rc = map_set_impl(ctx, 2, kinds, pts, n, stride_bytes, min_match_sq_dis, mem);
+    ctx->stream = main_stream;
+    if (rc) { ctx->map = ctx->map_sets[ctx->map_set_cur]; return rc; }
+    ctx->map_set_cur = target;
+    // the index must be complete before anything that reads it is enqueued on the solver's stream: waited for HERE, on the host (the build is ~30 us of
+    // small launches, the solve in flight another ~100), so that the solver's stream carries no cross-stream wait at all
+    MLH_HIP(ctx, hipEventRecord(ctx->ev_set_built[target], ctx->stream2));
+    hipEvent_t built = ctx->ev_set_built[target];
+    return host_wait(ctx, [=] { return hipEventQuery(built) != hipErrorNotReady; }, ctx->stream2, nullptr);
+}
+
+int mlh_map_rebuild(mlh_ctx *ctx, int kind)
+{
+    if (!ctx || kind < MLH_ALL_KINDS || kind > 1) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return grid_build(ctx, kind == MLH_ALL_KINDS ? 3 : (1 << kind), false);
+}
+
+int mlh_map_info(mlh_ctx *ctx, int kind, int32_t *n_points, int32_t *occupied_cells, double *mean_cell_population, int32_t *knn_lanes)
+{
+    if (!ctx || kind < 0 || kind > 1) return MLH_ERR_INVALID;
+    const MapGrid &g = ctx->map[kind];
+    if (n_points) *n_points = g.built ? g.n : 0;
+    if (occupied_cells) *occupied_cells = g.built ? g.occupied : 0;
+    if (mean_cell_population) *mean_cell_population = (g.built && g.n > 0) ? double(g.pop_sq) / double(g.n) : 0.0;
+    if (knn_lanes) { int lanes[2]; knn_lanes_for(ctx, 3, lanes); *knn_lanes = lanes[kind]; }
+    return MLH_OK;
+}
+
+int mlh_knn(mlh_ctx *ctx, int kind, const float *queries_xyz, int nq, int k, int32_t *idx, float *sqdist)
+{
+    if (!ctx || kind < 0 || kind > 1 || !queries_xyz || !idx || !sqdist) return MLH_ERR_INVALID;
+    if (k != 5) return fail(ctx, MLH_ERR_UNSUPPORTED, "only k = 5 is implemented");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return knn_launch(ctx, kind, queries_xyz, nq, idx, sqdist);
+}
+
+}  // extern "C"

@@ -452,11 +452,7 @@ int keyframes_update_from_pg_run(mlh_ctx *ctx, mlh_ctx *pg, int32_t first_index,
     const size_t row = sizeof(double) * 7;
     MLH_HIP(ctx, K.h_poses.ensure(row * size_t(n), row * size_t(n) / 4));       // (no copy of an earlier call is in flight: every call waits for its own)
     hipStream_t st = ctx->stream;
-    if (pg != ctx) {
-        if (!ctx->ev_handover) MLH_HIP(ctx, hipEventCreateWithFlags(&ctx->ev_handover, hipEventDisableTiming));
-        MLH_HIP(ctx, hipEventRecord(ctx->ev_handover, pg->stream));
-        MLH_HIP(ctx, hipStreamWaitEvent(st, ctx->ev_handover, 0));
-    }
+    if (pg != ctx) { const int hrc = ctx->handoff.borrow_begin(ctx, pg); if (hrc) return hrc; }
     MLH_HIP(ctx, hipMemcpy2DAsync(K.h_poses.p, row, G.kf.as<PgKeyframe>() + first_index, sizeof(PgKeyframe), row, size_t(n), hipMemcpyDeviceToHost, st));
     MLH_HIP(ctx, stream_wait_spin(ctx));     // the copy has completed when the call returns: no reader event has to outlive it
     { const int rc = device_error_check(ctx); if (rc) return rc; }

@@ -330,16 +330,19 @@ static void prior_info_reset(MargPrior &P)
     P.info.kept_mm = P.info.kept_rr = P.info.sweeps_mm = P.info.sweeps_rr = -1;      // not the result of a marginalisation
 }
 
-int window_prior_clear(mlh_ctx *ctx)
+extern "C" int mlh_window_prior_clear(mlh_ctx *ctx)
 {
+    if (!ctx) return MLH_ERR_INVALID;
     MargPrior &P = ctx->marg;
     P.valid = false; P.n_keep = 0; P.shape_frames = P.shape_ext = -1;
     prior_info_reset(P);
     return MLH_OK;
 }
 
-int window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const double *x0, const double *J0, const double *r0)
+extern "C" int mlh_window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const double *x0, const double *J0, const double *r0)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n_keep < 1 || !block_ids || !x0 || !J0 || !r0) return fail(ctx, MLH_ERR_INVALID, "mlh_window_prior_set: bad arguments");
     if (n_keep > MARG_MAX_KEEP) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_window_prior_set: at most 21 kept blocks");
     for (int k = 0; k < n_keep; ++k) {
@@ -363,8 +366,10 @@ int window_prior_set(mlh_ctx *ctx, int n_keep, const int32_t *block_ids, const d
     return MLH_OK;
 }
 
-int window_prior_get(mlh_ctx *ctx, mlh_window_prior_info *info, int32_t *block_ids, double *x0, double *J0, double *r0)
+extern "C" int mlh_window_prior_get(mlh_ctx *ctx, mlh_window_prior_info *info, int32_t *block_ids, double *x0, double *J0, double *r0)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     MargPrior &P = ctx->marg;
     if (info) { *info = P.info; info->valid = P.valid ? 1 : 0; }
     if (!P.valid) {
@@ -381,8 +386,10 @@ int window_prior_get(mlh_ctx *ctx, mlh_window_prior_info *info, int32_t *block_i
     return MLH_OK;
 }
 
-int window_ext_prior_set(mlh_ctx *ctx, int n_ext, const double *rows, uint32_t flags)
+extern "C" int mlh_window_ext_prior_set(mlh_ctx *ctx, int n_ext, const double *rows, uint32_t flags)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     MargPrior &P = ctx->marg;
     if (n_ext < 0 || n_ext > MARG_MAX_KEEP || (n_ext > 0 && !rows) || (flags & ~3u)) return fail(ctx, MLH_ERR_INVALID, "mlh_window_ext_prior_set: bad arguments");
     if (n_ext == 0) { P.ext_n = 0; P.ext_flags = 0; return MLH_OK; }
@@ -425,9 +432,11 @@ void window_prior_term_enqueue(mlh_ctx *ctx, const double *poses_dev, int n_fram
     MLH_LAUNCH(window_prior_term_kernel, dim3(1), dim3(256), 0, ctx->stream, T);
 }
 
-int window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
-                          double *residuals, double *H, double *g, double *cost)
+extern "C" int mlh_window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
+                                         double *residuals, double *H, double *g, double *cost)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     MargPrior &P = ctx->marg;
     if (!pivot || n_frames < 0 || n_ext < 0 || (n_frames > 0 && !frames) || (n_ext > 0 && !exts)) return fail(ctx, MLH_ERR_INVALID, "mlh_window_prior_evaluate: bad arguments");
     if (!P.valid) return fail(ctx, MLH_ERR_STATE, "mlh_window_prior_evaluate: no prior is installed");
@@ -455,9 +464,13 @@ int window_prior_evaluate(mlh_ctx *ctx, const double pivot[7], const double *fra
     return MLH_OK;
 }
 
-int window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
-                       mlh_window_prior_info *info_out)
+extern "C" int mlh_window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
+                                      mlh_window_prior_info *info_out)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    // as mlh_pure_odom_gn_solve: this rank's sums are not the job's
+    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_window_marginalize under a communicator: build the whole factor table on one rank");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     MargPrior &P = ctx->marg;
     if (!pivot || !frames || !exts || n_frames < 1 || n_ext < 1) return fail(ctx, MLH_ERR_INVALID, "mlh_window_marginalize: bad arguments");
     const int nb = 1 + n_frames + n_ext, n_keep = nb - 1, n = 6 * n_keep;
@@ -468,7 +481,7 @@ int window_marginalize(mlh_ctx *ctx, const double pivot[7], const double *frames
     for (int k = 0; P.valid && k < P.n_keep; ++k) prior_on_pivot = prior_on_pivot || P.ids[k] == 0;
     const bool table = ctx->odom.n > 0 && ctx->odom.n_tiles > 0;
     if (!table && !prior_on_pivot) {                       // MarginalizationInfo::marginalize with m == 0 (cpp:210-215): no prior comes out
-        window_prior_clear(ctx);
+        mlh_window_prior_clear(ctx);
         if (info_out) *info_out = P.info;
         return MLH_OK;
     }

@@ -19,6 +19,7 @@
 // blockIdx -> tile mapping is XCD-aware: consecutive tiles go to the same XCD (blockIdx % 8), so each XCD's L2 holds one
 // contiguous eighth of the (spatially coherent) feature list's map neighbourhood.
 #include "ctx.hpp"
+#include "solve_host.hpp"
 #include "dev_math.hpp"
 #include "solver_dev.hpp"
 #include "p2p_dev.hpp"

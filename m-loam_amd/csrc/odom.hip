@@ -13,6 +13,9 @@
 #include "ctx.hpp"
 #include "dev_math.hpp"
 #include <cfloat>
+#include <algorithm>
+#include <random>
+#include <vector>
 
 namespace mlh {
 
@@ -285,9 +288,11 @@ __global__ __launch_bounds__(256) void odom_ne_finish_kernel(OdomNeFinish F)
     for (int q = threadIdx.x; q < n_out; q += 256) F.out[q] = Hs[q];
 }
 
-int pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info,
-                  const int32_t *frame_idx, const int32_t *ext_idx)
+extern "C" int mlh_pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info,
+                                 const int32_t *frame_idx, const int32_t *ext_idx)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n <= 0 || !type || !points || !coeffs || !frame_idx || !ext_idx) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     OdomSet &O = ctx->odom;
     std::vector<double> tab(size_t(n) * 10);
@@ -394,8 +399,9 @@ __global__ __launch_bounds__(1024) void odom_append_kernel(OdomAppend P)
     for (int q = s_running + threadIdx.x; q < P.cap_slots; q += 1024) P.perm[P.base_slot + q] = -1;
 }
 
-int pure_odom_begin(mlh_ctx *ctx)
+extern "C" int mlh_pure_odom_begin(mlh_ctx *ctx)
 {
+    if (!ctx) return MLH_ERR_INVALID;
     OdomSet &O = ctx->odom;
     O.n = 0; O.n_tiles = 0; O.max_frame = 0; O.max_ext = 0; O.group_ext = 1; O.tile_group_keyed = false; O.device_built = true;
     O.h_tile_group.clear(); O.h_tile_frame.clear(); O.h_tile_ext.clear();
@@ -428,9 +434,11 @@ int pure_odom_add_matches(mlh_ctx *ctx, int kind, int frame_idx, int ext_idx)
     return MLH_OK;
 }
 
-int pure_odom_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
-                       double *residuals, double *jacobians)
+extern "C" int mlh_pure_odom_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
+                                      double *residuals, double *jacobians)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (ctx->odom.device_built) return fail(ctx, MLH_ERR_STATE, "per-factor outputs need a host-staged table (mlh_pure_odom_set): a device-built one is padded");
     OdomSet &O = ctx->odom;
     if (O.n <= 0) return fail(ctx, MLH_ERR_STATE, "mlh_pure_odom_set has not been called");
@@ -518,9 +526,11 @@ static void odom_ne_enqueue(mlh_ctx *ctx, const OdomNeArgs &G, int n_frames, int
     if (calib_active(ctx)) calib_ne_enqueue(ctx, O.poses.as<double>(), n_frames, n_ext, G.huber_delta, O.ne_out.as<double>());
 }
 
-int pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
-                        double *H, double *g, double *cost, int32_t *n_res)
+extern "C" int mlh_pure_odom_normal_eq(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext, double huber_delta,
+                                       double *H, double *g, double *cost, int32_t *n_res)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (!H || !g) return fail(ctx, MLH_ERR_INVALID, "null output");
     OdomSet &O = ctx->odom;
     OdomNeArgs G;
@@ -662,9 +672,13 @@ __global__ __launch_bounds__(256) void odom_window_solve_kernel(OdomSolveArgs S)
     if (t == 0) { S.status[0] = solved ? max(S.status[0], used_reg) : 2; S.status[1] += 1; }
 }
 
-int pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int n_frames, double *exts, int n_ext, double huber_delta, int n_iters,
-                       uint32_t const_block_mask, const double *V_update, double *cost, int32_t *n_res, int32_t *status_out)
+extern "C" int mlh_pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int n_frames, double *exts, int n_ext, double huber_delta, int n_iters,
+                                      uint32_t const_block_mask, const double *V_update, double *cost, int32_t *n_res, int32_t *status_out)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    // the window solve factorises THIS rank's J^T J / J^T r: with the factor table sharded over several ranks every rank would apply a different update
+    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_pure_odom_gn_solve under a communicator: all-reduce mlh_pure_odom_normal_eq's H / g (mlh_allreduce_f64) and solve on the host, or build the whole factor table on every rank");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n_iters <= 0 || !frames || !exts) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     OdomSet &O = ctx->odom;
     OdomNeArgs G;
@@ -712,3 +726,53 @@ int pure_odom_gn_solve(mlh_ctx *ctx, const double pivot[7], double *frames, int 
 }
 
 }  // namespace mlh
+
+using namespace mlh;
+
+extern "C" {
+
+int mlh_pure_odom_add_matches(mlh_ctx *ctx, int kind, const double rel_pose[7], int k_neigh, uint32_t flags, float min_match_sq_dis,
+                              float min_plane_dis, int frame_idx, int ext_idx)
+{
+    if (!ctx || kind < 0 || kind > 1 || !rel_pose) return MLH_ERR_INVALID;
+    if (k_neigh != 5 && k_neigh != 10) return fail(ctx, MLH_ERR_UNSUPPORTED, "N_NEIGH is 5 or 10");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = match_for_factors(ctx, kind, rel_pose, k_neigh, flags, min_match_sq_dis, min_plane_dis);
+    if (rc) return rc;
+    ctx->map_read_unsynced = true;                       // (nothing here waits for that launch: see mlh_map_set_pair_overlapped)
+    return pure_odom_add_matches(ctx, kind, frame_idx, ext_idx);
+}
+
+int mlh_pure_odom_add_matches_gf(mlh_ctx *ctx, int kind, const double rel_pose[7], const double pivot[7], const double pose_i[7], const double ext[7], int k_neigh,
+                                 uint32_t flags, float min_match_sq_dis, float min_plane_dis, int frame_idx, int ext_idx, float gf_ratio, uint64_t seed,
+                                 int32_t *sel_out, int32_t *n_sel)
+{
+    if (!ctx || kind < 0 || kind > 1 || !rel_pose || !pivot || !pose_i || !ext || !(gf_ratio > 0.f)) return MLH_ERR_INVALID;
+    if (k_neigh != 5 && k_neigh != 10) return fail(ctx, MLH_ERR_UNSUPPORTED, "N_NEIGH is 5 or 10");
+    if (distributed(ctx)) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_pure_odom_add_matches_gf: the selection loop is sequential over ALL features of the group; a sharded feature set cannot run it");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = match_for_factors(ctx, kind, rel_pose, k_neigh, flags, min_match_sq_dis, min_plane_dis);
+    if (rc) return rc;
+    FeatSet &f = ctx->feat[kind];
+    std::vector<int32_t> sel;
+    if (gf_ratio == 1.0f) {
+        // "if (gf_ratio == 1.0)": every matched feature, in feature order (estimator.cpp:1379-1412)
+        if (sel_out || n_sel) {
+            MLH_HIP(ctx, f.flag8.ensure((size_t(f.m) + 63) & ~size_t(63)));
+            if ((rc = pure_odom_feature_rows(ctx, kind, pivot, pose_i, ext))) return rc;      // (its validity bytes)
+            std::vector<uint8_t> v(size_t(f.m));
+            MLH_HIP(ctx, hipMemcpyAsync(v.data(), f.flag8.p, size_t(f.m), hipMemcpyDeviceToHost, ctx->stream));
+            MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+            for (int i = 0; i < f.m; ++i) if (v[size_t(i)]) sel.push_back(i);
+        } else ctx->map_read_unsynced = true;
+    } else {
+        if ((rc = pure_odom_feature_rows(ctx, kind, pivot, pose_i, ext))) return rc;
+        std::mt19937 rng(static_cast<uint32_t>(seed));
+        if ((rc = odom_good_feature_select(ctx, kind, gf_ratio, rng, sel))) return rc;
+    }
+    if (n_sel) *n_sel = int32_t(sel.size());
+    if (sel_out) std::copy(sel.begin(), sel.end(), sel_out);
+    return pure_odom_add_matches(ctx, kind, frame_idx, ext_idx);
+}
+
+}  // extern "C"

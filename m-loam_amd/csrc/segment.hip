@@ -689,9 +689,15 @@ static bool seg_rows_lds_granted(int device, size_t bytes)
     return true;
 }
 
-int segment_cloud_run(mlh_ctx *ctx, const void *points, int stride, int intensity_off, int n, int mem, const mlh_segment_params &prm,
-                      float *cloud_out, int32_t *n_out, int32_t *scan_start, int32_t *scan_end, float *outlier_out, int32_t outlier_capacity, int32_t *n_outlier)
+extern "C" int mlh_segment_cloud(mlh_ctx *ctx, const void *points, int stride, int intensity_off, int n, int mem, const mlh_segment_params *prm_in,
+                                 float *cloud_out, int32_t *n_out, int32_t *scan_start, int32_t *scan_end, float *outlier_out, int32_t outlier_capacity, int32_t *n_outlier)
 {
+    if (!ctx || !prm_in) return MLH_ERR_INVALID;
+    if (outlier_out && outlier_capacity < 0) return fail(ctx, MLH_ERR_INVALID, "negative outlier capacity");
+    { const int rc = records_check(ctx, "mlh_segment_cloud", records_of(points, stride, n, mem, intensity_off)); if (rc) return rc; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    { const int wrc = ctx->handoff.wait_readers(ctx); if (wrc) return wrc; }
+    const mlh_segment_params &prm = *prm_in;
     SegSetup S;
     if (!seg_setup(prm, S)) return fail(ctx, MLH_ERR_UNSUPPORTED, "ImageSegmenter is set up for 16, 32 or 64 vertical scans (image_segmenter.cpp:18-61)");
     if (prm.horizon_scans <= 0 || prm.horizon_scans > 65535) return fail(ctx, MLH_ERR_INVALID, "horizon_scans out of range");

@@ -3,6 +3,7 @@
 // that consume those rows. The loops are sequential by construction (each greedy pick changes the information matrix the
 // next score is computed against), which is why the reference gives them a 20 ms wall-clock budget (lidar_mapper.h:82).
 #include "ctx.hpp"
+#include "solve_host.hpp"
 #include "alive_pool.hpp"
 #include <chrono>
 #include <climits>

@@ -15,6 +15,9 @@
 //                         through the shared workgroup reduction -> partial records consumed by the LM kernels of solver.hip.
 // Small launches (a frame has ~2 k sharp/flat features): latency-bound by construction; nothing here is tuned beyond that.
 #include "ctx.hpp"
+#include "solve_host.hpp"
+#include <algorithm>
+#include <vector>
 #include "dev_math.hpp"
 #include "knn_dev.hpp"
 #include "solver_dev.hpp"
@@ -632,3 +635,203 @@ int track_linearize_launch(mlh_ctx *ctx, int kind_mask, const TrackArgs &a)
 }
 
 }  // namespace mlh
+
+using namespace mlh;
+
+extern "C" {
+
+// ---------------------------------------------------------------- scan-to-scan odometry (LidarTracker)
+void mlh_track_opts_default(mlh_track_opts *o)
+{
+    if (!o) return;
+    o->distance_sq_threshold = 25.0f; o->nearby_scan = 2.5f; o->huber_delta = 0.1; o->max_outer = 2; o->max_lm_iterations = 4;
+}
+
+static TrackArgs track_args(const mlh_track_opts *o, int pose_sel)
+{
+    TrackArgs a;
+    a.pose_sel = pose_sel; a.dist_sq_thr = o->distance_sq_threshold; a.nearby_scan = o->nearby_scan; a.huber_delta = o->huber_delta;
+    return a;
+}
+
+// previous-frame cloud of one kind: packed copies + ring table, everything enqueued and nothing waited for; *host_bad is valid after
+// the next synchronisation of the stream
+static int track_stage_prev(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int n, int intensity_offset_bytes, int mem,
+                            float distance_sq_threshold, int *host_bad)
+{
+    TrackSet &T = ctx->track;
+    MapGrid &g = T.grid[kind];
+    g.built = false;
+    const Records r = records_of(points, stride_bytes, n, mem, intensity_offset_bytes);
+    const unsigned char *d_src;
+    int rc = records_check(ctx, "mlh_track_set_prev", r);
+    if (rc || (rc = stage_points(ctx, r, PACK_W_INDEX, g.raw, nullptr, ctx->tmp, &d_src))) return rc;
+    // second copy in the original order with the ring id in w: what the scan-line walks stream over
+    MLH_HIP(ctx, T.walk[kind].ensure(sizeof(float4) * size_t(n)));
+    pack_points_launch(ctx->stream, d_src, stride_bytes, n, intensity_offset_bytes, 0.f, -1, T.walk[kind].as<float4>(), nullptr);
+    if ((rc = track_set_prev_rings(ctx, kind, d_src, stride_bytes, n, intensity_offset_bytes, host_bad))) return rc;
+    g.n = n;
+    g.min_match_sq_dis = distance_sq_threshold / float(TRACK_SHELLS * TRACK_SHELLS);   // cell edge = 1.001 * sqrt(thr) / TRACK_SHELLS
+    return MLH_OK;
+}
+
+// index build of the staged previous-frame clouds (one host round trip for all of them: the bounding boxes) + the deferred ring check
+static int track_build_prev(mlh_ctx *ctx, int kind_mask, const int *host_bad)
+{
+    MapGrid *gp[2];
+    int ng = 0;
+    for (int k = 0; k < 2; ++k) if (kind_mask & (1 << k)) gp[ng++] = &ctx->track.grid[k];
+    int rc = grid_build_grids(ctx, gp, ng, true);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); for (int k = 0; k < ng; ++k) gp[k]->built = false; return rc; }
+    for (int k = 0; k < 2; ++k)
+        if ((kind_mask & (1 << k)) && host_bad[k]) {
+            ctx->track.grid[k].built = false;
+            return fail(ctx, MLH_ERR_INVALID, "previous-frame cloud must be ordered by ring id (int(intensity) non-decreasing, 0 <= id <= 255)");
+        }
+    return MLH_OK;
+}
+
+int mlh_track_set_prev(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int n, int intensity_offset_bytes, int mem,
+                       float distance_sq_threshold)
+{
+    if (!ctx || kind < 0 || kind > 1 || intensity_offset_bytes < 0 || !(distance_sq_threshold > 0.f)) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int bad[2] = {0, 0};
+    int rc = track_stage_prev(ctx, kind, points, stride_bytes, n, intensity_offset_bytes, mem, distance_sq_threshold, &bad[kind]);
+    if (rc) { (void)hipStreamSynchronize(ctx->stream); return rc; }
+    if ((rc = track_build_prev(ctx, 1 << kind, bad))) return rc;
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));      // host buffers: the staging copy is reused by the next call
+    return MLH_OK;
+}
+
+static int track_stage_cur(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int m, int intensity_offset_bytes, int mem)
+{
+    TrackSet &T = ctx->track;
+    const Records r = records_of(points, stride_bytes, m, mem, intensity_offset_bytes);
+    int rc = records_check(ctx, "mlh_track_set_cur", r);
+    if (rc || (rc = stage_points(ctx, r, intensity_offset_bytes >= 0 ? intensity_offset_bytes : PACK_W_ZERO, T.cur[kind], nullptr, ctx->tmp))) return rc;
+    MLH_HIP(ctx, T.corr[kind].ensure(sizeof(Corr) * size_t(m)));
+    T.m[kind] = m;
+    return MLH_OK;
+}
+
+int mlh_track_set_cur(mlh_ctx *ctx, int kind, const void *points, int stride_bytes, int m, int intensity_offset_bytes, int mem)
+{
+    if (!ctx || kind < 0 || kind > 1) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = track_stage_cur(ctx, kind, points, stride_bytes, m, intensity_offset_bytes, mem);
+    if (rc) return rc;
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return MLH_OK;
+}
+
+// the features of the scan the context holds become the tracker's current (which = 0: sharp corners, flat surfs) or previous
+// (which = 1: less-sharp corners, voxel-thinned less-flat surfs) frame, device to device
+int mlh_track_set_from_scan(mlh_ctx *ctx, int which, float distance_sq_threshold)
+{
+    if (!ctx || which < 0 || which > 1) return MLH_ERR_INVALID;
+    ScanBuf &sb = ctx->scan;
+    if (!sb.extracted) return fail(ctx, MLH_ERR_STATE, "extract_run has not been called");
+    if (which == 1 && !sb.voxelised) return fail(ctx, MLH_ERR_STATE, "extract_voxel_run has not been called (the previous frame's surf cloud is the thinned one)");
+    if (which == 1 && !(distance_sq_threshold > 0.f)) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    int rc = scan_totals(ctx, which == 1);
+    if (rc) return rc;
+    const int corner_list = which == 0 ? 0 : 1;                 // corner_points_sharp / corner_points_less_sharp
+    const int n_corner = sb.h_totals[corner_list], n_flat = sb.h_totals[2], n_vox = sb.h_totals[4];
+    if (n_corner <= 0 || (which == 0 ? n_flat : n_vox) <= 0) return fail(ctx, MLH_ERR_STATE, "the scan produced no features of one kind");
+    MLH_HIP(ctx, ctx->knn_q.ensure(sizeof(float4) * size_t(std::max(n_corner, n_flat))));     // gather scratch (not ctx->tmp: the staging calls may use that)
+    float4 *g = ctx->knn_q.as<float4>();
+    gather_points_launch(ctx, sb.pts.as<float4>(), sb.lists[corner_list].as<int>(), n_corner, g);
+    if (which == 0) {
+        // nothing to wait for: every consumer of these buffers is a later launch on the same stream
+        if ((rc = track_stage_cur(ctx, MLH_CORNER, g, 16, n_corner, 12, MLH_MEM_DEVICE))) return rc;
+        gather_points_launch(ctx, sb.pts.as<float4>(), sb.lists[2].as<int>(), n_flat, g);
+        return track_stage_cur(ctx, MLH_SURF, g, 16, n_flat, 12, MLH_MEM_DEVICE);
+    }
+    int bad[2] = {0, 0};
+    if ((rc = track_stage_prev(ctx, MLH_CORNER, g, 16, n_corner, 12, MLH_MEM_DEVICE, distance_sq_threshold, &bad[MLH_CORNER]))) { (void)hipStreamSynchronize(st); return rc; }
+    if ((rc = track_stage_prev(ctx, MLH_SURF, sb.vox_out.p, 16, n_vox, 12, MLH_MEM_DEVICE, distance_sq_threshold, &bad[MLH_SURF]))) { (void)hipStreamSynchronize(st); return rc; }
+    return track_build_prev(ctx, 3, bad);      // both indices in one set of launches, one host round trip
+}
+
+int mlh_track_match(mlh_ctx *ctx, int kind, const double pose[7], const mlh_track_opts *opts, uint8_t *valid, double *coeffs)
+{
+    if (!ctx || kind < 0 || kind > 1 || !pose || !opts) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = solver_begin(ctx, 0);
+    if (rc) return rc;
+    TrackArgs a = track_args(opts, 0);
+    a.init_pose = pose;
+    if ((rc = track_match_launch(ctx, 1 << kind, a))) return rc;
+    const int m = ctx->track.m[kind];
+    std::vector<Corr> hc(m);
+    MLH_HIP(ctx, hipMemcpyAsync(hc.data(), ctx->track.corr[kind].p, sizeof(Corr) * size_t(m), hipMemcpyDeviceToHost, ctx->stream));
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < m; ++i) {
+        if (valid) valid[i] = hc[i].valid ? 1 : 0;
+        if (coeffs) for (int k = 0; k < 6; ++k) coeffs[size_t(i) * 6 + k] = double(hc[i].c[k]);
+    }
+    return MLH_OK;
+}
+
+// LidarTracker::trackCloud's rounds (lidar_tracker.cpp:42-121: match at the current estimate, then Ceres on the fixed correspondences -- Huber 0.1, <= 4
+// iterations, no degeneracy handling; fewer than 10 correspondences -> the round is skipped). Without per-round records the pose goes in with the first round's
+// kernel arguments and comes back from the last launch through pinned host memory; with records the state is uploaded and read back. `loop`: a round is the match
+// and ONE launch that runs its LM loop to the end on the device (track.hip: track_lm_loop_kernel; *given_up: it gave its barrier up); otherwise the LM begin /
+// step run in the linearisation kernel's last workgroup, 2 + max_lm_iterations launches per round.
+static int track_rounds(mlh_ctx *ctx, double pose_inout[7], const mlh_track_opts *opts, mlh_iter_stat *stats, bool loop, bool *given_up)
+{
+    const bool lean = stats == nullptr;
+    int rc;
+    if (!lean && (rc = upload_pose(ctx, pose_inout))) return rc;
+    HostPublish *rec = nullptr;
+    unsigned long long seq = 0;
+    if (loop && (rc = publish_slot(ctx, &rec, &seq))) return rc;
+    for (int outer = 0; outer < opts->max_outer; ++outer) {
+        TrackArgs m = track_args(opts, 0);
+        if (lean && outer == 0) m.init_pose = pose_inout;
+        if ((rc = track_match_launch(ctx, 3, m))) return rc;
+        TrackArgs b = track_args(opts, 0);
+        b.finish = loop ? TAIL_RECORDS : TAIL_LM_BEGIN; b.lm_max_it = opts->max_lm_iterations; b.lm_min_blocks = 10; b.stat_slot = stats ? outer : -1;
+        if (lean && outer == 0) b.init_pose = pose_inout;
+        if (loop) {
+            if (outer == opts->max_outer - 1) { b.publish = rec; b.publish_seq = seq; }
+            if ((rc = track_lm_loop_launch(ctx, 3, b))) return rc;
+            continue;
+        }
+        if ((rc = track_linearize_launch(ctx, 3, b))) return rc;
+        for (int it = 0; it < opts->max_lm_iterations; ++it) {
+            TrackArgs s = track_args(opts, 1);
+            s.finish = TAIL_LM_STEP; s.lm_max_it = opts->max_lm_iterations;
+            if (lean && outer == opts->max_outer - 1 && it == opts->max_lm_iterations - 1) {
+                if ((rc = publish_slot(ctx, &s.publish, &seq))) return rc;
+                s.publish_seq = seq;
+            }
+            if ((rc = track_linearize_launch(ctx, 3, s))) return rc;
+        }
+        if (stats && (rc = lm_finish_launch(ctx, outer))) return rc;     // fills the record's LM summary
+    }
+    return lean ? collect_loop_pose(ctx, seq, rec, pose_inout, given_up) : fetch_pose_and_stats(ctx, pose_inout, stats, opts->max_outer);
+}
+
+int mlh_track_cloud(mlh_ctx *ctx, double pose_inout[7], const mlh_track_opts *opts, mlh_iter_stat *stats)
+{
+    if (!ctx || !pose_inout || !opts || opts->max_outer <= 0 || opts->max_lm_iterations <= 0) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    const TrackSet &T = ctx->track;
+    int rc = gn_flush_pending(ctx);      // (not solver_begin: the state is allocated only behind the check of what was staged)
+    if (rc) return rc;
+    if (!(T.grid[0].built && T.grid[1].built && T.m[0] > 0 && T.m[1] > 0)) return fail(ctx, MLH_ERR_STATE, "track_set_prev / track_set_cur are required for both kinds");
+    if ((rc = ensure_state(ctx, opts->max_outer))) return rc;
+    // the loop: no statistics, one GPU, a frame's worth of features (Schedule::TRACK_LOOP, ctx.hpp, keeps the launch per LM iteration)
+    const int tiles = tiles_of(T.m[0]) + tiles_of(T.m[1]);
+    const bool loop = !stats && schedule_on(Schedule::TRACK_LOOP) && !distributed(ctx) && loop_tiles_ok(ctx, 2, tiles);
+    bool given_up = false;
+    if ((rc = track_rounds(ctx, pose_inout, opts, stats, loop, &given_up)) || !given_up) return rc;
+    note_loop_given_up(ctx, 2, tiles);
+    return track_rounds(ctx, pose_inout, opts, stats, false, &given_up);
+}
+
+}  // extern "C"

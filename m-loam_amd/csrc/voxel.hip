@@ -320,9 +320,12 @@ __global__ __launch_bounds__(256) void compact_records_kernel(const unsigned cha
     for (int k = 0; k < stride / 4; ++k) d[k] = s[k];
 }
 
-int point_uncertainty_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int mem, const double *ext_poses,
-                          const double *ext_covs, int n_lidar, const double cov_meas[9], double trace_thr, float *cov6_host, int *keep_host)
+extern "C" int mlh_point_uncertainty(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int mem, const double *ext_poses,
+                                     const double *ext_covs, int n_lidar, const double cov_meas[9], double trace_thr, float *cov6_host, int32_t *keep_host)
 {
+    if (!ctx || !ext_poses || !ext_covs || !cov_meas || !cov6_host || !keep_host) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_point_uncertainty", records_of(points, stride, n, mem, intensity_off)); if (rc) return rc; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n_lidar <= 0 || n_lidar > 16) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     hipStream_t st = ctx->stream;
     const unsigned char *src;
@@ -392,10 +395,13 @@ void compound_pose_with_cov(const double p1[7], const double c1[36], const doubl
     for (int i = 0; i < 36; ++i) cc[i] = C1.a[i] + C2p.a[i] + (((m1.a[i] + m2.a[i]) + m3.a[i]) + m4.a[i]) / 12 + B.a[i] / 4;
 }
 
-int cloud_uct_associate_run(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off,
-                            const double pose_global[7], const double cov_global[36], const double *ext_poses, const double *ext_covs,
-                            int n_lidar, const double cov_meas[9], int with_ua, double trace_thr, void *out, int *n_out, int mem)
+extern "C" int mlh_cloud_uct_associate_to_map(mlh_ctx *ctx, const void *points, int stride, int n, int intensity_off, int cov_off, int trace_off,
+                                              const double pose_global[7], const double cov_global[36], const double *ext_poses, const double *ext_covs,
+                                              int n_lidar, const double cov_meas[9], int with_ua, double trace_thr, void *out, int32_t *n_out, int mem)
 {
+    if (!ctx) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_cloud_uct_associate_to_map", records_of(points, stride, n, mem, intensity_off, cov_off, trace_off)); if (rc) return rc; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n_lidar <= 0 || n_lidar > 16 || !out || !n_out || !pose_global || !ext_poses) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
     if (with_ua && (!cov_global || !ext_covs || !cov_meas)) return fail(ctx, MLH_ERR_INVALID, "with_ua needs the pose / extrinsic / measurement covariances");
     hipStream_t st = ctx->stream;

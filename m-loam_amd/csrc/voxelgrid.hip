@@ -593,3 +593,29 @@ int voxel_filter_run2(mlh_ctx *ctx, const void *src0, int n0, const float bounds
 }
 
 }  // namespace mlh
+
+using namespace mlh;
+
+extern "C" {
+
+int mlh_voxel_filter(mlh_ctx *ctx, const void *points, int stride_bytes, int n, int intensity_offset_bytes, int cov_offset_bytes,
+                     int trace_offset_bytes, float leaf, float trace_threshold, void *out, int32_t *n_out, int mem)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_voxel_filter", records_of(points, stride_bytes, n, mem, intensity_offset_bytes, cov_offset_bytes, trace_offset_bytes)); if (rc) return rc; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return voxel_filter_run(ctx, points, stride_bytes, n, intensity_offset_bytes, cov_offset_bytes, trace_offset_bytes, leaf, trace_threshold,
+                            out, n_out, mem);
+}
+
+// pcl::VoxelGrid<PointXYZI>::filter (PCL 1.8.0): one centroid per occupied voxel, every field averaged (CentroidPoint), output in
+// ascending voxel index -- Estimator::buildLocalMap / buildCalibMap thin the window's clouds with it (estimator.cpp:1124-1130, 1194-1203)
+int mlh_voxel_grid(mlh_ctx *ctx, const void *points, int stride_bytes, int n, int intensity_offset_bytes, float leaf, void *out, int32_t *n_out, int mem)
+{
+    if (!ctx || intensity_offset_bytes < 12) return MLH_ERR_INVALID;
+    { const int rc = records_check(ctx, "mlh_voxel_grid", records_of(points, stride_bytes, n, mem, intensity_offset_bytes)); if (rc) return rc; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return voxel_filter_run(ctx, points, stride_bytes, n, intensity_offset_bytes, -1, -1, leaf, 0.f, out, n_out, mem, nullptr, true, true);
+}
+
+}  // extern "C"

@@ -301,4 +301,39 @@ int mlh_window_map_cloud(mlh_ctx *ctx, int lidar, int kind, int filtered, const 
     return window_map_cloud_run(ctx, lidar, kind, filtered, device_points, n);
 }
 
+
+// cpp:487-495 for the scan `src` holds: its less-sharp points through pcl::VoxelGrid at leaf_corner, its voxel-thinned less-flat cloud through pcl::VoxelGrid at
+// leaf_surf (voxel_filter_run, centroid_all: the arithmetic of mlh_voxel_grid), the results named by stack[lidar][slot] (window.hip)
+int mlh_window_set_from_scan(mlh_ctx *ctx, mlh_ctx *src, int lidar, int slot, float leaf_surf, float leaf_corner)
+{
+    if (!ctx || !src) return MLH_ERR_INVALID;
+    { const int rc = window_check_slot(ctx, "mlh_window_set_from_scan", lidar, slot); if (rc) return rc; }
+    if (!std::isfinite(leaf_surf) || !(leaf_surf > 0.f) || !std::isfinite(leaf_corner) || !(leaf_corner > 0.f))
+        return fail(ctx, MLH_ERR_INVALID, "mlh_window_set_from_scan: the leaves must be finite and > 0");
+    if (ctx->device != src->device) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_window_set_from_scan: both contexts must be on the same device");
+    ScanBuf &sb = src->scan;
+    if (!sb.extracted || !sb.voxelised) return fail(ctx, MLH_ERR_STATE, "mlh_window_set_from_scan: mlh_extract_run and mlh_extract_voxel_run on the source context come first");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    int rc = scan_totals(src, true);       // the list sizes: fetched once per scan, on the source's own stream (this context's, or an idle one's)
+    if (rc) return src == ctx ? rc : fail(ctx, MLH_ERR_HIP, mlh_last_error(src));
+    const int n_in[2] = {sb.h_totals[4], sb.h_totals[1]};      // the thinned less-flat cloud -> SURF, the less-sharp points -> CORNER
+    const float leaf[2] = {leaf_surf, leaf_corner};
+    if (n_in[MLH_CORNER] > 0) MLH_HIP(ctx, ctx->knn_q.ensure(sizeof(float4) * size_t(n_in[MLH_CORNER])));     // gather scratch (not ctx->tmp: the staging calls may use that)
+    if (src != ctx && (rc = ctx->handoff.borrow_begin(ctx, src))) return rc;
+    for (int k = 0; k < 2 && !rc; ++k) {
+        int n_out = 0;
+        if (n_in[k] > 0) {
+            const void *in = sb.vox_out.p;
+            if (k == MLH_CORNER) {
+                gather_points_launch(ctx, sb.pts.as<float4>(), sb.lists[1].as<int>(), n_in[k], ctx->knn_q.as<float4>());
+                in = ctx->knn_q.p;
+            }
+            rc = voxel_filter_run(ctx, in, 16, n_in[k], 12, -1, -1, leaf[k], 0.f, nullptr, &n_out, MLH_MEM_DEVICE, nullptr, true, true);
+        }
+        if (!rc) rc = window_assign_device(ctx, lidar, slot, k, ctx->vox.out.as<float4>(), n_out);      // copied out of the filter's buffer, behind the filter
+    }
+    if (src != ctx) { const int erc = ctx->handoff.borrow_end(ctx, src); if (!rc) rc = erc; }
+    return rc;
+}
+
 }  // extern "C"

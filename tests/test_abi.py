@@ -471,3 +471,32 @@ def test_stored_cloud_builder_and_loop_gate_have_one_owner(mla):
             for m in re.finditer(r"^int " + name + r"\([^)]*\)\s*\{\n(.*?)^\}", t, re.S | re.M):
                 body = [ln for ln in m.group(1).splitlines() if ln.strip()]
                 assert len(body) <= 3 and "loop_process_gate(ctx, entry)" in body[0] and "pending" not in m.group(1), (f, name, body)
+
+
+def test_entry_points_sit_beside_their_kernels(mla):
+    """csrc/capi.hip holds what belongs to the context itself and defines no kernel; every subsystem's entry points are defined once, in the unit that owns the
+    state they touch; the forwarding twins of the odometry / prior / calibration entry points are gone; the fused clouds are one struct that only its owner
+    (frontend.hip) and the unit with the two fused-input predicates reach into."""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(mla.__file__)), "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp", ".inc"))}
+    assert len(text) >= 20
+    capi = text["capi.hip"]
+    assert "__global__" not in capi
+    definition = re.compile(r'^(?:extern "C" )?(?:int|void|const char|void) \*?(mlh_\w+)\(', re.M)
+    moved = ("mlh_fuse_", "mlh_fused_cloud", "mlh_scan_upload", "mlh_extract_", "mlh_map_", "mlh_knn", "mlh_track_", "mlh_gn_solve", "mlh_scan2map", "mlh_match_",
+             "mlh_features_", "mlh_downsample_", "mlh_pure_odom_", "mlh_window_", "mlh_calib_", "mlh_voxel_")
+    in_capi = definition.findall(capi)
+    assert "mlh_create" in in_capi and "mlh_destroy" in in_capi
+    assert not [n for n in in_capi if n.startswith(moved)], in_capi
+    defined = [n for f, t in text.items() if f.endswith(".hip") for n in definition.findall(t)]
+    for name in mla.EXPORTED_SYMBOLS:
+        assert defined.count(name) == 1, (name, defined.count(name))
+    for twin in ("pure_odom_set", "pure_odom_evaluate", "pure_odom_normal_eq", "pure_odom_gn_solve", "pure_odom_begin", "window_prior_set", "window_prior_get",
+                 "window_prior_clear", "window_prior_evaluate", "window_ext_prior_set", "window_marginalize", "calib_add", "calib_use", "calib_clear", "calib_info",
+                 "calib_evaluate"):
+        assert not [f for f, t in text.items() if ("int " + twin + "(") in t], twin
+    holders = sorted({"frontend.hip"} | {f for f, t in text.items() if "bool is_fused_cloud(" in t})
+    assert len(holders) == 2, holders
+    members = re.compile(r"\bfused_(?:cnt|dirty|parts|n|bound|part|host|seq|minmax)\b|\bfused\.(?:pts|n|minmax|dirty|bound|cnt|part|parts|host|seq)\b|\bFusedClouds\b")
+    assert [f for f, t in text.items() if f.endswith(".hip") and members.search(t)] == holders
+    assert not [f for f, t in text.items() if re.search(r"\bev_scan_reader\b|\bscan_reader_pending\b|\bscan_wait_readers\b|\bscan_borrow_(?:begin|end)\b", t)]

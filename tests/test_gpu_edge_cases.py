@@ -874,7 +874,7 @@ def test_launch_checks_name_the_failing_kernel(tmp_path):
 
 
 def test_pageable_scan_buffer_is_the_callers_again_when_upload_returns(mla, synth, case16, feats16):
-    """mlh_scan_upload of a PAGEABLE host buffer relies on hipMemcpyAsync having consumed the source when it returns (capi.hip, mlh_scan_upload). Pinned here: with ~5 ms
+    """mlh_scan_upload of a PAGEABLE host buffer relies on hipMemcpyAsync having consumed the source when it returns (scan.hip, mlh_scan_upload). Pinned here: with ~5 ms
     of kernels queued AHEAD of the copy on the context's stream (a 200-iteration solve submitted with mlh_gn_solve_begin), the caller overwrites its buffer the
     moment the call returns; the extraction that follows must see the ORIGINAL points. If the runtime ever defers reading pageable sources, this fails and the
     pinned staging path (MLH_SCAN_STAGE_PINNED=1) has to become the default."""
