@@ -14,18 +14,13 @@
 // Fixed summation order everywhere, no atomics: identical bits run to run.
 #include "ctx.hpp"
 #include "dev_math.hpp"
-#include "calib_group.hpp"
-#include <cfloat>
+#include "factor_dev.hpp"
+#include "tile_group.hpp"
 
 namespace mlh {
 
 constexpr int CAL_OUT = 32;       // 21 + 6 + cost + count = 29, padded
 constexpr int CAL_NSUM = 29;
-
-struct C3 { double x, y, z; };
-__device__ __forceinline__ C3 c_rowmul(const C3 &a, const double *M) { return {a.x * M[0] + a.y * M[3] + a.z * M[6], a.x * M[1] + a.y * M[4] + a.z * M[7], a.x * M[2] + a.y * M[5] + a.z * M[8]}; }   // a^T M
-__device__ __forceinline__ C3 c_row_skew(const C3 &a, const C3 &v) { return {a.y * v.z - a.z * v.y, a.z * v.x - a.x * v.z, a.x * v.y - a.y * v.x}; }                                              // a^T [v]x
-__device__ __forceinline__ C3 c_cross(const C3 &a, const C3 &b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
 
 // the workgroup's extrinsic: R (9, row-major), t (3), q (4, xyzw) -- written by one thread, read by all
 __device__ __forceinline__ void calib_stage_ext(const double *pe, double *s_ext)
@@ -39,31 +34,24 @@ __device__ __forceinline__ void calib_stage_ext(const double *pe, double *s_ext)
 __device__ __forceinline__ void calib_factor(const double *tb, int type, const double *s_ext, double &r_out, double *J6)
 {
     const double *R = s_ext;
-    const C3 p{tb[0], tb[1], tb[2]};
+    const d3 p{tb[0], tb[1], tb[2]};
     const double s = tb[9];
-    const d3 rp = qrot(q4{s_ext[12], s_ext[13], s_ext[14], s_ext[15]}, d3{p.x, p.y, p.z});       // Q_ext * point_
-    const C3 lp{rp.x + s_ext[9], rp.y + s_ext[10], rp.z + s_ext[11]};
-    C3 jt, jr;
+    const d3 rp = qrot(q4{s_ext[12], s_ext[13], s_ext[14], s_ext[15]}, p);       // Q_ext * point_
+    const d3 lp{rp.x + s_ext[9], rp.y + s_ext[10], rp.z + s_ext[11]};
+    d3 jt, jr;
     double res;
     if (type == 0) {
-        const C3 w{tb[3], tb[4], tb[5]};
+        const d3 w{tb[3], tb[4], tb[5]};
         res = (w.x * lp.x + w.y * lp.y + w.z * lp.z) + tb[6];
         jt = w;
-        const C3 k = c_row_skew(c_rowmul(w, R), p);                 // w^T R [p]x
-        jr = C3{-k.x, -k.y, -k.z};
+        const d3 k = row_skew(rowmul(w, R), p);                     // w^T R [p]x
+        jr = d3{-k.x, -k.y, -k.z};
     } else {
-        const C3 la{tb[3], tb[4], tb[5]}, lb{tb[6], tb[7], tb[8]};
-        const C3 nu = c_cross(C3{lp.x - la.x, lp.y - la.y, lp.z - la.z}, C3{lp.x - lb.x, lp.y - lb.y, lp.z - lb.z});
-        const C3 de{la.x - lb.x, la.y - lb.y, la.z - lb.z};
-        const double n2 = nu.x * nu.x + nu.y * nu.y + nu.z * nu.z, de_n = sqrt(de.x * de.x + de.y * de.y + de.z * de.z);
-        res = sqrt(n2) / de_n;
-        C3 nh = nu;
-        if (n2 > 0.0) { const double nn = sqrt(n2); nh = C3{nu.x / nn, nu.y / nn, nu.z / nn}; }     // Eigen normalized(): zero stays zero, so nu = 0 gives a zero row
-        const double k = 1.0 / de_n;
-        const C3 eta{k * nh.x, k * nh.y, k * nh.z};
-        const C3 ed = c_row_skew(eta, de);                          // eta [lpa - lpb]x
-        jt = C3{-ed.x, -ed.y, -ed.z};
-        jr = c_row_skew(c_rowmul(ed, R), p);                        // eta [lpa - lpb]x R [p]x
+        const LineFront F = point_to_line(lp, d3{tb[3], tb[4], tb[5]}, d3{tb[6], tb[7], tb[8]});
+        res = F.res;
+        const d3 ed = row_skew(F.eta, F.de);                        // eta [lpa - lpb]x
+        jt = d3{-ed.x, -ed.y, -ed.z};
+        jr = row_skew(rowmul(ed, R), p);                            // eta [lpa - lpb]x R [p]x
     }
     r_out = s * res;
     J6[0] = s * jt.x; J6[1] = s * jt.y; J6[2] = s * jt.z; J6[3] = s * jr.x; J6[4] = s * jr.y; J6[5] = s * jr.z;
@@ -100,11 +88,8 @@ __global__ __launch_bounds__(256) void calib_ne_kernel(CalibNeArgs G)
     if (G.perm[slot] >= 0) {
         double r, J[6];
         calib_factor(G.tab + slot * 10, G.type[slot], s_ext, r, J);
-        double sq = r * r, rho0 = sq, rho1 = 1.0;
-        if (G.huber_delta > 0.0) {
-            const double bb = G.huber_delta * G.huber_delta;
-            if (sq > bb) { const double rr = sqrt(sq); rho0 = 2.0 * G.huber_delta * rr - bb; rho1 = fmax(DBL_MIN, G.huber_delta / rr); }
-        }
+        double rho0, rho1;
+        huber_correct(r * r, G.huber_delta, rho0, rho1);
         const double sc = sqrt(rho1);
 #pragma unroll
         for (int c = 0; c < 6; ++c) v[c] = J[c] * sc;
@@ -221,9 +206,8 @@ __global__ __launch_bounds__(256) void calib_eval_kernel(CalibEvalArgs E)
     }
 }
 
-// the valid correspondences of a match pass -> records behind the store's last tile, in feature order; the rest of the reserved region is padding. The twin of
-// odom.hip's odom_append_kernel (same scan-and-pack; kept apart so that the window table's kernel stays exactly as it was): a change to one belongs in both.
-// The region is reserved from the STAGED feature count (no host round trip for the number of valid ones), so a device-built store has more slots than factors. One workgroup. n_valid (one word, this kernel its only writer while it runs) counts what was appended.
+// the valid correspondences of a match pass -> records behind the store's last tile (factor_dev.hpp: append_valid_matches), so a device-built store has more
+// slots than factors. n_valid (one word, this kernel its only writer while it runs) counts what was appended.
 struct CalibAppend {
     const float4 *feat;
     const Corr *corr;
@@ -233,40 +217,8 @@ struct CalibAppend {
 };
 __global__ __launch_bounds__(1024) void calib_append_kernel(CalibAppend P)
 {
-    __shared__ int wsum[16];
-    __shared__ int s_running;
-    if (threadIdx.x == 0) s_running = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c0 = 0; c0 < P.m; c0 += 1024) {
-        const int i = c0 + threadIdx.x;
-        const bool v = i < P.m && P.corr[i].valid != 0 && P.feat[i].w >= 0.f;
-        const unsigned long long b = __ballot(v);
-        const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) { const int x = wsum[w]; if (w < wave) before += x; total += x; }
-        const int running = s_running;
-        if (v) {
-            const int slot = P.base_slot + running + before + in_wave;     // running + before + in_wave < m <= cap_slots
-            const float4 f = P.feat[i];
-            const Corr c = P.corr[i];
-            double *t = P.tab + size_t(slot) * 10;
-            t[0] = double(f.x); t[1] = double(f.y); t[2] = double(f.z);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) t[3 + k] = double(c.c[k]);
-            t[9] = 1.0;                                                     // the reference constructs them with s = 1.0 (estimator.cpp:728, 774)
-            P.types[slot] = P.type;
-            P.perm[slot] = slot;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_running = running + total;
-        __syncthreads();
-    }
-    for (int q = s_running + threadIdx.x; q < P.cap_slots; q += 1024) P.perm[P.base_slot + q] = -1;
-    if (threadIdx.x == 0) *P.n_valid += s_running;
+    const int n = append_valid_matches(P.feat, P.corr, P.m, P.base_slot, P.cap_slots, P.tab, P.perm, [&](int slot) { P.types[slot] = P.type; });
+    if (threadIdx.x == 0) *P.n_valid += n;
 }
 
 // ---- host side
@@ -275,10 +227,8 @@ static int calib_grow(mlh_ctx *ctx, int n_tiles_new)
     CalibStore &S = ctx->calib;
     hipStream_t st = ctx->stream;
     const size_t have = size_t(S.n_tiles) * CALIB_TILE, want = size_t(n_tiles_new) * CALIB_TILE;
-    hipError_t e;
-    if ((e = S.tab.grow(sizeof(double) * 10 * want, sizeof(double) * 10 * have, st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc calibration store", e);
-    if ((e = S.type.grow(sizeof(int) * want, sizeof(int) * have, st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc calibration store", e);
-    if ((e = S.perm.grow(sizeof(int) * want, sizeof(int) * have, st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc calibration store", e);
+    const hipError_t e = grow_factor_slots(S.tab, S.type, sizeof(int), S.perm, want, have, st);
+    if (e != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc calibration store", e);
     return MLH_OK;
 }
 
@@ -287,31 +237,22 @@ extern "C" int mlh_calib_add(mlh_ctx *ctx, int n, const int32_t *type, const dou
     if (!ctx) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n <= 0 || !type || !points || !coeffs || !ext_idx) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: bad arguments");
-    for (int i = 0; i < n; ++i) {
-        if (type[i] != 0 && type[i] != 1) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: factor type must be 0 (plane) or 1 (edge)");
-        if (ext_idx[i] < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: negative extrinsic index");
-    }
+    for (int i = 0; i < n; ++i) if (ext_idx[i] < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: negative extrinsic index");
     CalibStore &S = ctx->calib;
-    const CalibGrouping G = calib_group(n, ext_idx, S.n_given);
+    const TileGrouping G = tile_group(n, ext_idx, S.n_given);
     const size_t slots = size_t(G.n_tiles) * CALIB_TILE, base = size_t(S.n_tiles) * CALIB_TILE;
     std::vector<double> tab(slots * 10, 0.0);
     std::vector<int> types(slots, 0);
-    for (int i = 0; i < n; ++i) {
-        const size_t s = size_t(G.slot_of[size_t(i)]);
-        double *t = tab.data() + s * 10;
-        for (int k = 0; k < 3; ++k) t[k] = points[size_t(i) * 3 + k];
-        for (int k = 0; k < 6; ++k) t[3 + k] = coeffs[size_t(i) * 6 + k];
-        t[9] = sqrt_info ? sqrt_info[i] : 1.0;
-        types[s] = type[i];
-    }
+    if (!pack_factor_rows(n, type, points, coeffs, sqrt_info, G.slot_of.data(), tab.data(), types.data(), 1))
+        return fail(ctx, MLH_ERR_INVALID, "mlh_calib_add: factor type must be 0 (plane) or 1 (edge)");
     { const int rc = calib_grow(ctx, S.n_tiles + G.n_tiles); if (rc) return rc; }
     hipStream_t st = ctx->stream;
     MLH_HIP(ctx, hipMemcpyAsync(S.tab.as<double>() + base * 10, tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, st));
     MLH_HIP(ctx, hipMemcpyAsync(S.type.as<int>() + base, types.data(), sizeof(int) * slots, hipMemcpyHostToDevice, st));
     MLH_HIP(ctx, hipMemcpyAsync(S.perm.as<int>() + base, G.perm.data(), sizeof(int) * slots, hipMemcpyHostToDevice, st));
     MLH_HIP(ctx, hipStreamSynchronize(st));                // the staging vectors end with this call
-    S.h_tile_ext.insert(S.h_tile_ext.end(), G.tile_ext.begin(), G.tile_ext.end());
-    S.n_tiles += G.n_tiles; S.n_appends += 1; S.n_given += n; S.max_ext = std::max(S.max_ext, G.max_ext); S.lists_n_ext = -1;
+    S.h_tile_ext.insert(S.h_tile_ext.end(), G.tile_key.begin(), G.tile_key.end());
+    S.n_tiles += G.n_tiles; S.n_appends += 1; S.n_given += n; S.max_ext = std::max(S.max_ext, G.max_key); S.lists_n_ext = -1;
     return MLH_OK;
 }
 

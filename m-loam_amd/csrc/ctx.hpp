@@ -438,7 +438,7 @@ struct OdomSet {   // staged LidarPureOdom factor table (odom.hip)
     DevBuf perm, tile_group, partial, ne_out, solve_aux;
     int n_tiles = 0, group_ext = 1;
     bool tile_group_keyed = true;
-    std::vector<int> h_tile_group, h_tile_frame, h_tile_ext;
+    std::vector<int> h_tile_frame, h_tile_ext;
     bool device_built = false;   // table appended from match passes on the device (padded regions): normal equations only
 };
 

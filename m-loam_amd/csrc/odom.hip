@@ -12,7 +12,8 @@
 // reference hands it, so parity means reproducing those.
 #include "ctx.hpp"
 #include "dev_math.hpp"
-#include <cfloat>
+#include "factor_dev.hpp"
+#include "tile_group.hpp"
 #include <algorithm>
 #include <random>
 #include <vector>
@@ -30,25 +31,6 @@ struct OdomArgs {
     double *J;              // n x 21 (pivot | frame | extrinsic), or null
 };
 
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 rowmul(const V3 &a, const double (&M)[9])      // a^T M
-{
-    return {a.x * M[0] + a.y * M[3] + a.z * M[6], a.x * M[1] + a.y * M[4] + a.z * M[7], a.x * M[2] + a.y * M[5] + a.z * M[8]};
-}
-__device__ __forceinline__ V3 matmul(const double (&M)[9], const V3 &v)      // M v
-{
-    return {M[0] * v.x + M[1] * v.y + M[2] * v.z, M[3] * v.x + M[4] * v.y + M[5] * v.z, M[6] * v.x + M[7] * v.y + M[8] * v.z};
-}
-__device__ __forceinline__ V3 tmatmul(const double (&M)[9], const V3 &v)     // M^T v
-{
-    return {M[0] * v.x + M[3] * v.y + M[6] * v.z, M[1] * v.x + M[4] * v.y + M[7] * v.z, M[2] * v.x + M[5] * v.y + M[8] * v.z};
-}
-__device__ __forceinline__ V3 row_skew(const V3 &a, const V3 &v)             // a^T [v]x
-{
-    return {a.y * v.z - a.z * v.y, a.z * v.x - a.x * v.z, a.x * v.y - a.y * v.x};
-}
-__device__ __forceinline__ V3 crossv(const V3 &a, const V3 &b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-
 // one factor: residual and (J != null) its three 1x7 rows [pivot | frame | extrinsic]; tb = point[3], coeff[6], sqrt_info; pp / pi / pe = the three poses
 __device__ __forceinline__ void odom_factor_core(const double *tb, int type, const double *pp, const double *pi, const double *pe, double &r_out, double *J);
 __device__ __forceinline__ void odom_factor(const OdomArgs &A, int i, double &r_out, double *J)
@@ -59,48 +41,39 @@ __device__ __forceinline__ void odom_factor(const OdomArgs &A, int i, double &r_
 __device__ __forceinline__ void odom_factor_core(const double *tb, int type, const double *pp, const double *pi, const double *pe, double &r_out, double *J)
 {
     const q4 Qp{pp[3], pp[4], pp[5], pp[6]}, Qi{pi[3], pi[4], pi[5], pi[6]}, Qe{pe[3], pe[4], pe[5], pe[6]};
-    const V3 tp{pp[0], pp[1], pp[2]}, ti{pi[0], pi[1], pi[2]}, te{pe[0], pe[1], pe[2]};
-    const V3 p{tb[0], tb[1], tb[2]};
+    const d3 tp{pp[0], pp[1], pp[2]}, ti{pi[0], pi[1], pi[2]}, te{pe[0], pe[1], pe[2]};
+    const d3 p{tb[0], tb[1], tb[2]};
     const double s = tb[9];
     // T = T_pivot^-1 * T_i * T_ext as quaternion products (hpp:47-53 / 218-224)
     const q4 Qpc{-Qp.x, -Qp.y, -Qp.z, Qp.w};
     const q4 Qpi = qmul(Qpc, Qi);
     const d3 tpi = qrot(Qpc, d3{ti.x - tp.x, ti.y - tp.y, ti.z - tp.z});
     const q4 Qx = qmul(Qpi, Qe);
-    const d3 rte = qrot(Qpi, d3{te.x, te.y, te.z});
-    const d3 rp = qrot(Qx, d3{p.x, p.y, p.z});
-    const V3 lp{rp.x + (rte.x + tpi.x), rp.y + (rte.y + tpi.y), rp.z + (rte.z + tpi.z)};
+    const d3 rte = qrot(Qpi, te);
+    const d3 rp = qrot(Qx, p);
+    const d3 lp{rp.x + (rte.x + tpi.x), rp.y + (rte.y + tpi.y), rp.z + (rte.z + tpi.z)};
     double Rp[9], Ri[9], Re[9];
     qtorot(Qp, Rp); qtorot(Qi, Ri); qtorot(Qe, Re);
-    const V3 Rep = matmul(Re, p);                         // Rext p
-    const V3 Rite = matmul(Ri, te);                       // Ri t_ext
-    const V3 RiRep = matmul(Ri, Rep);                     // Ri Rext p
-    const V3 v{RiRep.x + Rite.x + ti.x - tp.x, RiRep.y + Rite.y + ti.y - tp.y, RiRep.z + Rite.z + ti.z - tp.z};
-    V3 a;            // the 1x3 row that multiplies d(lp): w^T (plane) or eta [ba - bb]x (edge)
+    const d3 Rep = matmul(Re, p);                         // Rext p
+    const d3 Rite = matmul(Ri, te);                       // Ri t_ext
+    const d3 RiRep = matmul(Ri, Rep);                     // Ri Rext p
+    const d3 v{RiRep.x + Rite.x + ti.x - tp.x, RiRep.y + Rite.y + ti.y - tp.y, RiRep.z + Rite.z + ti.z - tp.z};
+    d3 a;            // the 1x3 row that multiplies d(lp): w^T (plane) or eta [ba - bb]x (edge)
     double res;
     if (type == 0) {
-        a = V3{tb[3], tb[4], tb[5]};
+        a = d3{tb[3], tb[4], tb[5]};
         res = (a.x * lp.x + a.y * lp.y + a.z * lp.z) + tb[6];
     } else {
-        const V3 la{tb[3], tb[4], tb[5]}, lb{tb[6], tb[7], tb[8]};
-        const V3 ba{lp.x - la.x, lp.y - la.y, lp.z - la.z}, bb{lp.x - lb.x, lp.y - lb.y, lp.z - lb.z};
-        const V3 nu = crossv(ba, bb);
-        const V3 de{la.x - lb.x, la.y - lb.y, la.z - lb.z};
-        const double nu_n = sqrt(nu.x * nu.x + nu.y * nu.y + nu.z * nu.z), de_n = sqrt(de.x * de.x + de.y * de.y + de.z * de.z);
-        res = nu_n / de_n;
-        V3 nh = nu;
-        const double n2 = nu.x * nu.x + nu.y * nu.y + nu.z * nu.z;
-        if (n2 > 0.0) { const double nn = sqrt(n2); nh = V3{nu.x / nn, nu.y / nn, nu.z / nn}; }   // Eigen normalized(): zero stays zero
-        const double k = 1.0 / de_n;
-        const V3 eta{k * nh.x, k * nh.y, k * nh.z};
-        a = row_skew(eta, V3{ba.x - bb.x, ba.y - bb.y, ba.z - bb.z});
+        const LineFront F = point_to_line(lp, d3{tb[3], tb[4], tb[5]}, d3{tb[6], tb[7], tb[8]});
+        res = F.res;
+        a = row_skew(F.eta, d3{F.ba.x - F.bb.x, F.ba.y - F.bb.y, F.ba.z - F.bb.z});
     }
     r_out = s * res;
     if (!J) return;
     // row0 = a^T Rp^T: component c = sum_k a_k Rp[c][k] = (Rp a)_c
-    const V3 row0 = matmul(Rp, a);
+    const d3 row0 = matmul(Rp, a);
     // pivot block
-    V3 rot0;
+    d3 rot0;
     if (type == 0) {
         // w^T (Rp^T [v]x): (w^T Rp^T) [v]x
         rot0 = row_skew(row0, v);
@@ -111,18 +84,18 @@ __device__ __forceinline__ void odom_factor_core(const double *tb, int type, con
     J[0] = s * (-row0.x); J[1] = s * (-row0.y); J[2] = s * (-row0.z);
     J[3] = s * rot0.x; J[4] = s * rot0.y; J[5] = s * rot0.z; J[6] = 0.0;
     // frame block: [ a Rp^T | -(a Rp^T Ri) [Rext p + t_ext]x ]
-    const V3 row1 = rowmul(row0, Ri);
-    const V3 rot1 = row_skew(row1, V3{Rep.x + te.x, Rep.y + te.y, Rep.z + te.z});
+    const d3 row1 = rowmul(row0, Ri);
+    const d3 rot1 = row_skew(row1, d3{Rep.x + te.x, Rep.y + te.y, Rep.z + te.z});
     J[7] = s * row0.x; J[8] = s * row0.y; J[9] = s * row0.z;
     J[10] = s * (-rot1.x); J[11] = s * (-rot1.y); J[12] = s * (-rot1.z); J[13] = 0.0;
     // extrinsic block: [ a Rp^T Ri | -(a Rp^T Ri) X ],  X = [Rext p]x (plane) or Rext [p]x + [t_ext]x (edge)
-    V3 rot2;
+    d3 rot2;
     if (type == 0) {
         rot2 = row_skew(row1, Rep);
     } else {
-        const V3 t1 = row_skew(rowmul(row1, Re), p);      // row1 Rext [p]x
-        const V3 t2 = row_skew(row1, te);
-        rot2 = V3{t1.x + t2.x, t1.y + t2.y, t1.z + t2.z};
+        const d3 t1 = row_skew(rowmul(row1, Re), p);      // row1 Rext [p]x
+        const d3 t2 = row_skew(row1, te);
+        rot2 = d3{t1.x + t2.x, t1.y + t2.y, t1.z + t2.z};
     }
     J[14] = s * row1.x; J[15] = s * row1.y; J[16] = s * row1.z;
     J[17] = s * (-rot2.x); J[18] = s * (-rot2.y); J[19] = s * (-rot2.z); J[20] = 0.0;
@@ -219,11 +192,8 @@ __global__ __launch_bounds__(256) void odom_ne_kernel(OdomNeArgs G)
     if (i >= 0) {
         double r, J[21];
         odom_factor(G.A, i, r, J);
-        double sq = r * r, rho0 = sq, rho1 = 1.0;
-        if (G.huber_delta > 0.0) {
-            const double bb = G.huber_delta * G.huber_delta;
-            if (sq > bb) { const double rr = sqrt(sq); rho0 = 2.0 * G.huber_delta * rr - bb; rho1 = fmax(DBL_MIN, G.huber_delta / rr); }
-        }
+        double rho0, rho1;
+        huber_correct(r * r, G.huber_delta, rho0, rho1);
         const double sc = sqrt(rho1);
 #pragma unroll
         for (int bl = 0; bl < 3; ++bl)
@@ -297,14 +267,9 @@ extern "C" int mlh_pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const
     OdomSet &O = ctx->odom;
     std::vector<double> tab(size_t(n) * 10);
     std::vector<int> idx(size_t(n) * 3);
-    for (int i = 0; i < n; ++i) {
-        double *t = tab.data() + size_t(i) * 10;
-        for (int k = 0; k < 3; ++k) t[k] = points[size_t(i) * 3 + k];
-        for (int k = 0; k < 6; ++k) t[3 + k] = coeffs[size_t(i) * 6 + k];
-        t[9] = sqrt_info ? sqrt_info[i] : 1.0;              // the reference constructs these factors with s = 1.0 (estimator.cpp:735, 751)
-        if (type[i] != 0 && type[i] != 1) return fail(ctx, MLH_ERR_INVALID, "factor type must be 0 (plane) or 1 (edge)");
-        idx[size_t(i) * 3 + 0] = type[i]; idx[size_t(i) * 3 + 1] = frame_idx[i]; idx[size_t(i) * 3 + 2] = ext_idx[i];
-    }
+    // the table stays in the given order (the reference constructs these factors with s = 1.0, estimator.cpp:735, 751)
+    if (!pack_factor_rows(n, type, points, coeffs, sqrt_info, nullptr, tab.data(), idx.data(), 3)) return fail(ctx, MLH_ERR_INVALID, "factor type must be 0 (plane) or 1 (edge)");
+    for (int i = 0; i < n; ++i) { idx[size_t(i) * 3 + 1] = frame_idx[i]; idx[size_t(i) * 3 + 2] = ext_idx[i]; }
     MLH_HIP(ctx, O.tab.ensure(sizeof(double) * tab.size()));
     MLH_HIP(ctx, O.idx.ensure(sizeof(int) * idx.size()));
     MLH_HIP(ctx, O.r.ensure(sizeof(double) * size_t(n)));
@@ -316,33 +281,24 @@ extern "C" int mlh_pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const
     int mf = 0, me = 0;
     for (int i = 0; i < n; ++i) { mf = std::max(mf, frame_idx[i]); me = std::max(me, ext_idx[i]); if (frame_idx[i] < 0 || ext_idx[i] < 0) return fail(ctx, MLH_ERR_INVALID, "negative block index"); }
     O.max_frame = mf; O.max_ext = me;
-    // factors grouped by (frame, extrinsic) for the normal-equation kernel: stable counting sort of the indices, every group padded to whole
-    // 256-factor tiles (the group key uses the staged maxima; mlh_pure_odom_normal_eq re-derives (f, e) from it)
+    // factors grouped by (frame, extrinsic) for the normal-equation kernel (tile_group.hpp); the group key uses the staged maxima,
+    // mlh_pure_odom_normal_eq re-derives (f, e) from it
     {
-        const int ne = me + 1, ng = (mf + 1) * ne;
-        std::vector<int> cnt(size_t(ng) + 1, 0);
-        for (int i = 0; i < n; ++i) cnt[size_t(frame_idx[i]) * ne + ext_idx[i] + 1]++;
-        std::vector<int> tile_start(size_t(ng) + 1, 0);
-        for (int g = 0; g < ng; ++g) tile_start[g + 1] = tile_start[g] + (cnt[g + 1] + 255) / 256;
-        const int n_tiles = tile_start[ng];
-        std::vector<int> perm(size_t(n_tiles) * 256, -1), fill(ng, 0), tgrp(size_t(n_tiles), 0);
-        for (int i = 0; i < n; ++i) {
-            const int g = frame_idx[i] * ne + ext_idx[i];
-            perm[size_t(tile_start[g]) * 256 + fill[g]++] = i;
-        }
-        for (int g = 0; g < ng; ++g) for (int t = tile_start[g]; t < tile_start[g + 1]; ++t) tgrp[t] = g;
-        O.n_tiles = n_tiles; O.group_ext = ne;
-        if (n_tiles > 0) {
-            MLH_HIP(ctx, O.perm.ensure(sizeof(int) * perm.size()));
-            MLH_HIP(ctx, O.tile_group.ensure(sizeof(int) * tgrp.size()));
-            MLH_HIP(ctx, O.partial.ensure(sizeof(double) * NE_OUT * size_t(n_tiles)));
-            MLH_HIP(ctx, hipMemcpyAsync(O.perm.p, perm.data(), sizeof(int) * perm.size(), hipMemcpyHostToDevice, ctx->stream));
-            MLH_HIP(ctx, hipMemcpyAsync(O.tile_group.p, tgrp.data(), sizeof(int) * tgrp.size(), hipMemcpyHostToDevice, ctx->stream));
+        const int ne = me + 1;
+        std::vector<int32_t> key(size_t(n), 0);
+        for (int i = 0; i < n; ++i) key[size_t(i)] = frame_idx[i] * ne + ext_idx[i];
+        const TileGrouping T = tile_group(n, key.data(), 0);
+        O.n_tiles = T.n_tiles; O.group_ext = ne;
+        if (T.n_tiles > 0) {
+            MLH_HIP(ctx, O.perm.ensure(sizeof(int) * T.perm.size()));
+            MLH_HIP(ctx, O.tile_group.ensure(sizeof(int) * T.tile_key.size()));
+            MLH_HIP(ctx, O.partial.ensure(sizeof(double) * NE_OUT * size_t(T.n_tiles)));
+            MLH_HIP(ctx, hipMemcpyAsync(O.perm.p, T.perm.data(), sizeof(int) * T.perm.size(), hipMemcpyHostToDevice, ctx->stream));
+            MLH_HIP(ctx, hipMemcpyAsync(O.tile_group.p, T.tile_key.data(), sizeof(int) * T.tile_key.size(), hipMemcpyHostToDevice, ctx->stream));
             MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
-        O.h_tile_group = tgrp;
         O.h_tile_frame.clear(); O.h_tile_ext.clear();
-        for (int t = 0; t < n_tiles; ++t) { O.h_tile_frame.push_back(tgrp[t] / ne); O.h_tile_ext.push_back(tgrp[t] % ne); }
+        for (int g : T.tile_key) { O.h_tile_frame.push_back(g / ne); O.h_tile_ext.push_back(g % ne); }
         O.tile_group_keyed = true;
     }
     O.device_built = false;
@@ -364,39 +320,8 @@ struct OdomAppend {
 };
 __global__ __launch_bounds__(1024) void odom_append_kernel(OdomAppend P)
 {
-    __shared__ int wsum[16];
-    __shared__ int s_running;
-    if (threadIdx.x == 0) s_running = 0;
-    __syncthreads();
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int c0 = 0; c0 < P.m; c0 += 1024) {
-        const int i = c0 + threadIdx.x;
-        const bool v = i < P.m && P.corr[i].valid != 0 && P.feat[i].w >= 0.f;
-        const unsigned long long b = __ballot(v);
-        const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
-        if (lane == 0) wsum[wave] = __popcll(b);
-        __syncthreads();
-        int before = 0, total = 0;
-#pragma unroll
-        for (int w = 0; w < 16; ++w) { const int x = wsum[w]; if (w < wave) before += x; total += x; }
-        const int running = s_running;
-        if (v) {
-            const int slot = P.base_slot + running + before + in_wave;
-            const float4 f = P.feat[i];
-            const Corr c = P.corr[i];
-            double *t = P.tab + size_t(slot) * 10;
-            t[0] = double(f.x); t[1] = double(f.y); t[2] = double(f.z);
-#pragma unroll
-            for (int k = 0; k < 6; ++k) t[3 + k] = double(c.c[k]);
-            t[9] = 1.0;
-            P.idx[size_t(slot) * 3 + 0] = P.type; P.idx[size_t(slot) * 3 + 1] = P.frame; P.idx[size_t(slot) * 3 + 2] = P.ext;
-            P.perm[slot] = slot;
-        }
-        __syncthreads();
-        if (threadIdx.x == 0) s_running = running + total;
-        __syncthreads();
-    }
-    for (int q = s_running + threadIdx.x; q < P.cap_slots; q += 1024) P.perm[P.base_slot + q] = -1;
+    append_valid_matches(P.feat, P.corr, P.m, P.base_slot, P.cap_slots, P.tab, P.perm,
+                         [&](int slot) { P.idx[size_t(slot) * 3 + 0] = P.type; P.idx[size_t(slot) * 3 + 1] = P.frame; P.idx[size_t(slot) * 3 + 2] = P.ext; });
 }
 
 extern "C" int mlh_pure_odom_begin(mlh_ctx *ctx)
@@ -404,7 +329,7 @@ extern "C" int mlh_pure_odom_begin(mlh_ctx *ctx)
     if (!ctx) return MLH_ERR_INVALID;
     OdomSet &O = ctx->odom;
     O.n = 0; O.n_tiles = 0; O.max_frame = 0; O.max_ext = 0; O.group_ext = 1; O.tile_group_keyed = false; O.device_built = true;
-    O.h_tile_group.clear(); O.h_tile_frame.clear(); O.h_tile_ext.clear();
+    O.h_tile_frame.clear(); O.h_tile_ext.clear();
     return MLH_OK;
 }
 
@@ -417,10 +342,8 @@ int pure_odom_add_matches(mlh_ctx *ctx, int kind, int frame_idx, int ext_idx)
     if (f.m <= 0 || !f.matched || f.n_blocks != 1) return fail(ctx, MLH_ERR_STATE, "a single-block match pass must have run for this kind");
     hipStream_t st = ctx->stream;
     const int cap_tiles = (f.m + 255) / 256, cap_slots = cap_tiles * 256, base_slot = O.n_tiles * 256, n_new = base_slot + cap_slots;
-    hipError_t e;
-    if ((e = O.tab.grow(sizeof(double) * 10 * size_t(n_new), sizeof(double) * 10 * size_t(base_slot), st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc factor table", e);
-    if ((e = O.idx.grow(sizeof(int) * 3 * size_t(n_new), sizeof(int) * 3 * size_t(base_slot), st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc factor table", e);
-    if ((e = O.perm.grow(sizeof(int) * size_t(n_new), sizeof(int) * size_t(base_slot), st)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc factor table", e);
+    const hipError_t e = grow_factor_slots(O.tab, O.idx, sizeof(int) * 3, O.perm, size_t(n_new), size_t(base_slot), st);
+    if (e != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc factor table", e);
     OdomAppend P;
     P.feat = f.pts.as<float4>(); P.corr = f.corr.as<Corr>(); P.m = f.m; P.type = kind; P.frame = frame_idx; P.ext = ext_idx;
     P.base_slot = base_slot; P.cap_slots = cap_slots; P.tab = O.tab.as<double>(); P.idx = O.idx.as<int>(); P.perm = O.perm.as<int>();
@@ -431,37 +354,6 @@ int pure_odom_add_matches(mlh_ctx *ctx, int kind, int frame_idx, int ext_idx)
     // group keys are kept as (frame, ext) pairs until the window's extrinsic count is known (pure_odom_normal_eq keys and uploads them)
     for (int t = 0; t < cap_tiles; ++t) { O.h_tile_frame.push_back(frame_idx); O.h_tile_ext.push_back(ext_idx); }
     O.tile_group_keyed = false;
-    return MLH_OK;
-}
-
-extern "C" int mlh_pure_odom_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
-                                      double *residuals, double *jacobians)
-{
-    if (!ctx) return MLH_ERR_INVALID;
-    MLH_HIP(ctx, hipSetDevice(ctx->device));
-    if (ctx->odom.device_built) return fail(ctx, MLH_ERR_STATE, "per-factor outputs need a host-staged table (mlh_pure_odom_set): a device-built one is padded");
-    OdomSet &O = ctx->odom;
-    if (O.n <= 0) return fail(ctx, MLH_ERR_STATE, "mlh_pure_odom_set has not been called");
-    if (!pivot || !frames || !exts || !residuals || n_frames <= O.max_frame || n_ext <= O.max_ext)
-        return fail(ctx, MLH_ERR_INVALID, "pose arrays do not cover the block indices of the staged factors");
-    hipStream_t st = ctx->stream;
-    const size_t np = 7 * size_t(1 + n_frames + n_ext);
-    MLH_HIP(ctx, O.poses.ensure(sizeof(double) * np));
-    std::vector<double> h(np);
-    for (int k = 0; k < 7; ++k) h[k] = pivot[k];
-    for (size_t k = 0; k < 7 * size_t(n_frames); ++k) h[7 + k] = frames[k];
-    for (size_t k = 0; k < 7 * size_t(n_ext); ++k) h[7 + 7 * size_t(n_frames) + k] = exts[k];
-    MLH_HIP(ctx, hipMemcpyAsync(O.poses.p, h.data(), sizeof(double) * np, hipMemcpyHostToDevice, st));
-    MLH_HIP(ctx, hipStreamSynchronize(st));
-    OdomArgs A;
-    A.tab = O.tab.as<double>(); A.idx = O.idx.as<int>();
-    A.pivot = O.poses.as<double>(); A.frames = A.pivot + 7; A.exts = A.frames + 7 * size_t(n_frames);
-    A.n = O.n; A.n_frames = n_frames; A.n_ext = n_ext; A.r = O.r.as<double>(); A.J = jacobians ? O.J.as<double>() : nullptr;
-    MLH_LAUNCH(pure_odom_kernel, dim3((O.n + 255) / 256), dim3(256), 0, st, A);
-    MLH_HIP(ctx, hipGetLastError());
-    MLH_HIP(ctx, hipMemcpyAsync(residuals, O.r.p, sizeof(double) * size_t(O.n), hipMemcpyDeviceToHost, st));
-    if (jacobians) MLH_HIP(ctx, hipMemcpyAsync(jacobians, O.J.p, sizeof(double) * 21 * size_t(O.n), hipMemcpyDeviceToHost, st));
-    MLH_HIP(ctx, hipStreamSynchronize(st));
     return MLH_OK;
 }
 
@@ -480,6 +372,28 @@ static int odom_upload_poses(mlh_ctx *ctx, const double pivot[7], const double *
     A.tab = O.tab.as<double>(); A.idx = O.idx.as<int>();
     A.pivot = O.poses.as<double>(); A.frames = A.pivot + 7; A.exts = A.frames + 7 * size_t(n_frames);
     A.n = O.n; A.n_frames = n_frames; A.n_ext = n_ext; A.r = nullptr; A.J = nullptr;
+    return MLH_OK;
+}
+
+extern "C" int mlh_pure_odom_evaluate(mlh_ctx *ctx, const double pivot[7], const double *frames, int n_frames, const double *exts, int n_ext,
+                                      double *residuals, double *jacobians)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    if (ctx->odom.device_built) return fail(ctx, MLH_ERR_STATE, "per-factor outputs need a host-staged table (mlh_pure_odom_set): a device-built one is padded");
+    OdomSet &O = ctx->odom;
+    if (O.n <= 0) return fail(ctx, MLH_ERR_STATE, "mlh_pure_odom_set has not been called");
+    if (!pivot || !frames || !exts || !residuals || n_frames <= O.max_frame || n_ext <= O.max_ext)
+        return fail(ctx, MLH_ERR_INVALID, "pose arrays do not cover the block indices of the staged factors");
+    hipStream_t st = ctx->stream;
+    OdomArgs A;
+    { const int rc = odom_upload_poses(ctx, pivot, frames, n_frames, exts, n_ext, A); if (rc) return rc; }
+    A.r = O.r.as<double>(); A.J = jacobians ? O.J.as<double>() : nullptr;
+    MLH_LAUNCH(pure_odom_kernel, dim3((O.n + 255) / 256), dim3(256), 0, st, A);
+    MLH_HIP(ctx, hipGetLastError());
+    MLH_HIP(ctx, hipMemcpyAsync(residuals, O.r.p, sizeof(double) * size_t(O.n), hipMemcpyDeviceToHost, st));
+    if (jacobians) MLH_HIP(ctx, hipMemcpyAsync(jacobians, O.J.p, sizeof(double) * 21 * size_t(O.n), hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, hipStreamSynchronize(st));
     return MLH_OK;
 }
 

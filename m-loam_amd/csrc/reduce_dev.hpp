@@ -97,6 +97,8 @@ __device__ __forceinline__ void reduce_rows(bool valid, Lin L, double huber_delt
 {
     double acc[32];
     if (valid) {
+        // factor_dev.hpp: huber_correct, written out: through the shared function the LM loop kernels of match.hip and loopreg.hip come out with another
+        // register assignment, and the kernels the benchmark times keep their machine code
         double s = L.r * L.r, rho0 = s, rho1 = 1.0;
         if (!no_loss && huber_delta > 0.0) {
             const double b = huber_delta * huber_delta;

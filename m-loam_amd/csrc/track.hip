@@ -22,6 +22,7 @@
 #include "knn_dev.hpp"
 #include "solver_dev.hpp"
 #include "reduce_dev.hpp"
+#include "factor_dev.hpp"
 
 namespace mlh {
 
@@ -309,47 +310,37 @@ extern "C" int mlh_debug_stage_clock_track(unsigned long long *out, int n_words)
 namespace mlh {
 #endif
 
-struct V3 { double x, y, z; };
-__device__ __forceinline__ V3 rowmul3(const V3 &a, const double (&M)[9])      // a^T M
-{
-    return {a.x * M[0] + a.y * M[3] + a.z * M[6], a.x * M[1] + a.y * M[4] + a.z * M[7], a.x * M[2] + a.y * M[5] + a.z * M[8]};
-}
-__device__ __forceinline__ V3 row_skew3(const V3 &a, const V3 &v)             // a^T [v]x
-{
-    return {a.y * v.z - a.z * v.y, a.z * v.x - a.x * v.z, a.x * v.y - a.y * v.x};
-}
-
 // the normal-equation terms of ONE matched feature at pose (q, t): LidarScanPlaneNormFactor (1 residual) or LidarScanEdgeFactorVector (3), Huber on the block's
 // squared norm -- what track_linearize_kernel and track_lm_loop_kernel accumulate (acc: zeroed by the caller)
 __device__ __forceinline__ void track_eval(const TrackParamsDev &P, int kind, const Corr &c, const float4 &fp, const q4 &q, const d3 &t, double (&acc)[32])
 {
-    const V3 p{double(fp.x), double(fp.y), double(fp.z)};
+    const d3 p{double(fp.x), double(fp.y), double(fp.z)};
     double R[9];
     qtorot(q, R);
-    const d3 rp = qrot(q, d3{p.x, p.y, p.z});
-    const V3 lp{rp.x + t.x, rp.y + t.y, rp.z + t.z};
+    const d3 rp = qrot(q, p);
+    const d3 lp{rp.x + t.x, rp.y + t.y, rp.z + t.z};
     double res[3], J[3][6];
     int rows;
     if (kind == MLH_SURF) {
         rows = 1;
-        const V3 w{double(c.c[0]), double(c.c[1]), double(c.c[2])};
+        const d3 w{double(c.c[0]), double(c.c[1]), double(c.c[2])};
         res[0] = (w.x * lp.x + w.y * lp.y + w.z * lp.z) + double(c.c[3]);
-        const V3 jr = row_skew3(rowmul3(w, R), p);
+        const d3 jr = row_skew(rowmul(w, R), p);
         J[0][0] = w.x; J[0][1] = w.y; J[0][2] = w.z; J[0][3] = -jr.x; J[0][4] = -jr.y; J[0][5] = -jr.z;
     } else {
         rows = 3;
-        const V3 la{double(c.c[0]), double(c.c[1]), double(c.c[2])}, lb{double(c.c[3]), double(c.c[4]), double(c.c[5])};
-        const V3 ba{lp.x - la.x, lp.y - la.y, lp.z - la.z}, bb{lp.x - lb.x, lp.y - lb.y, lp.z - lb.z};
-        const V3 nu{ba.y * bb.z - ba.z * bb.y, ba.z * bb.x - ba.x * bb.z, ba.x * bb.y - ba.y * bb.x};
-        const V3 de{la.x - lb.x, la.y - lb.y, la.z - lb.z};
+        const d3 la{double(c.c[0]), double(c.c[1]), double(c.c[2])}, lb{double(c.c[3]), double(c.c[4]), double(c.c[5])};
+        const d3 ba{lp.x - la.x, lp.y - la.y, lp.z - la.z}, bb{lp.x - lb.x, lp.y - lb.y, lp.z - lb.z};
+        const d3 nu = cross3(ba, bb);
+        const d3 de{la.x - lb.x, la.y - lb.y, la.z - lb.z};
         const double den = sqrt(de.x * de.x + de.y * de.y + de.z * de.z);
         res[0] = nu.x / den; res[1] = nu.y / den; res[2] = nu.z / den;
         const double eta = 1.0 / den;
         // rows of [de]x
-        const V3 sd[3] = {{0.0, -de.z, de.y}, {de.z, 0.0, -de.x}, {-de.y, de.x, 0.0}};
+        const d3 sd[3] = {{0.0, -de.z, de.y}, {de.z, 0.0, -de.x}, {-de.y, de.x, 0.0}};
 #pragma unroll
         for (int r = 0; r < 3; ++r) {
-            const V3 jr = row_skew3(rowmul3(sd[r], R), p);
+            const d3 jr = row_skew(rowmul(sd[r], R), p);
             J[r][0] = -eta * sd[r].x; J[r][1] = -eta * sd[r].y; J[r][2] = -eta * sd[r].z;
             J[r][3] = eta * jr.x; J[r][4] = eta * jr.y; J[r][5] = eta * jr.z;
         }
@@ -357,15 +348,8 @@ __device__ __forceinline__ void track_eval(const TrackParamsDev &P, int kind, co
     double sq = 0.0;
 #pragma unroll
     for (int r = 0; r < 3; ++r) if (r < rows) sq += res[r] * res[r];     // static indices: res / J stay in registers (a loop over `rows` sends them to scratch)
-    double rho0 = sq, rho1 = 1.0;
-    if (P.huber_delta > 0.0) {
-        const double b = P.huber_delta * P.huber_delta;
-        if (sq > b) {
-            const double rr = sqrt(sq);
-            rho0 = 2.0 * P.huber_delta * rr - b;
-            rho1 = fmax(DBL_MIN, P.huber_delta / rr);
-        }
-    }
+    double rho0, rho1;
+    huber_correct(sq, P.huber_delta, rho0, rho1);
     const double sc = sqrt(rho1);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {

@@ -116,14 +116,14 @@ def test_library_exports_the_calibration_store(mla):
 
 
 def test_tile_bookkeeping_under_sanitizers(tmp_path):
-    """the host-side grouping / padding of mlh_calib_add (m-loam_amd/csrc/calib_group.hpp) in a stand-alone program built with -fsanitize=address,undefined:
-    counts 0, 1, 255..257, interleaved extrinsics"""
-    exe = tmp_path / "calib_group_main"
-    src = os.path.join(ROOT, "tests", "host", "calib_group_main.cpp")
+    """the host-side grouping / padding of mlh_calib_add and mlh_pure_odom_set (m-loam_amd/csrc/tile_group.hpp) in a stand-alone program built with
+    -fsanitize=address,undefined: counts 0, 1, 255..257, interleaved extrinsics; the window table's (frame, extrinsic) keying against the inline sort it replaces"""
+    exe = tmp_path / "tile_group_main"
+    src = os.path.join(ROOT, "tests", "host", "tile_group_main.cpp")
     cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
            "-I", os.path.join(ROOT, "m-loam_amd", "csrc"), src, "-o", str(exe)]
     b = subprocess.run(cmd, capture_output=True, text=True)
     assert b.returncode == 0, b.stderr[-2000:]
     r = subprocess.run([str(exe)], capture_output=True, text=True, timeout=120)
     assert r.returncode == 0, (r.stdout[-1000:], r.stderr[-2000:])
-    assert "calib_group: ok" in r.stdout
+    assert "tile_group: ok" in r.stdout

@@ -319,6 +319,83 @@ def test_refusals(ctx, mla):
     assert lib.mlh_calib_evaluate(h, p(ex), 2, p(r), None) == ERR_STATE
 
 
+APPEND_M = (1, 63, 64, 65, 255, 256, 257, 1023, 1024, 1025, 2049)
+
+
+@pytest.fixture(scope="module")
+def append_pair(mla, case16):
+    """two contexts with the 16-ring case's surf map resident: one appends on the device, the other is fed from the host"""
+    dev, host = mla.Context(0), mla.Context(0)
+    for c in (dev, host):
+        c.map_set(mla.SURF, case16["surf_map"])
+    yield dev, host
+    dev.close(); host.close()
+
+
+@pytest.mark.parametrize("m", APPEND_M)
+def test_shared_append_at_its_edges(mla, append_pair, case16, feats16, m):
+    """9. the scan-and-pack both device routes share (factor_dev.hpp: append_valid_matches) at its boundaries -- the 64-lane ballot, the 1024-feature chunk, the
+    256-slot tile: the first m surf features of the 16-ring case, every third moved 100 m away (valid and invalid slots interleave), matched at the case's pose.
+    One mlh_pure_odom_add_matches on a fresh table / one mlh_calib_accumulate on a fresh store must give the system of mlh_pure_odom_set / mlh_calib_add fed the
+    read-back valid features and coefficients in feature order. A single append of one kind lays the factors out in the same slots and tiles as the host route
+    (the device's trailing padding tiles add 0.0), and at the parent commit the two systems had equal bits for every m of APPEND_M on both routes: array_equal."""
+    dev, host = append_pair
+    pose = case16["gt"]
+    f = np.ascontiguousarray(feats16[0][:m].copy())
+    assert len(f) == m
+    f[2::3, :3] += np.float32(100.0)
+    host.features_set(mla.SURF, f)
+    lin = host.match_linearize(mla.SURF, pose, dense=False)
+    v = lin["valid"].astype(bool)
+    nv = int(v.sum())
+    assert lin["count"] == nv and not v[2::3].any()
+    if m >= 3:
+        assert 0 < nv < m
+    else:
+        assert nv == m == 1
+    types, pts, co = np.zeros(nv, np.int32), f[v, :3].astype(np.float64), lin["coeffs"][v]
+    ones = np.ones(nv, np.int32)
+    pivot, frames, exts = cc.IDENT, cc.IDENT[None, :], np.stack([cc.IDENT, pose])
+
+    def same(a, b, label):
+        equal_bits = all(np.array_equal(a[k], b[k]) for k in ("H", "g", "cost"))
+        e = max(np.abs(a["H"] - b["H"]).max() / np.abs(b["H"]).max(), np.abs(a["g"] - b["g"]).max() / np.abs(b["g"]).max(), abs(a["cost"] - b["cost"]) / b["cost"])
+        print(f"m = {m} {label}: {'equal bits' if equal_bits else 'NOT equal bits'}, worst relative difference {e:.2e}, {nv} of {m} valid")
+        assert a["count"] == b["count"] == nv, label
+        for k in ("H", "g", "cost"):
+            assert np.array_equal(a[k], b[k]), (label, k, e)
+
+    # the window table (no store in the way)
+    for c in (dev, host):
+        c.calib_clear()
+    dev.pure_odom_begin()
+    dev.features_set(mla.SURF, f)
+    dev.pure_odom_add_matches(mla.SURF, pose, 0, 1)
+    host.pure_odom_set(types, pts, co, np.zeros(nv, np.int32), ones)
+    same(dev.pure_odom_normal_eq(pivot, frames, exts, mc.HUBER), host.pure_odom_normal_eq(pivot, frames, exts, mc.HUBER), "window table")
+    # the calibration store, alone on an empty factor table
+    for c in (dev, host):
+        c.pure_odom_begin()
+        c.calib_use(True)
+    dev.calib_accumulate(mla.SURF, pose, 1, k_neigh=5, flags=0)
+    host.calib_add(types, pts, co, ones)
+    same(dev.pure_odom_normal_eq(pivot, frames, exts, mc.HUBER), host.pure_odom_normal_eq(pivot, frames, exts, mc.HUBER), "calibration store")
+    info = dev.calib_info()
+    tiles = (m + 255) // 256
+    assert info["n_valid"] == host.calib_info()["n_valid"] == nv and info["n_tiles"] == tiles and info["n_slots"] == 256 * tiles
+    if m in (256, 1024):
+        # a second append behind the first starts on the next tile
+        dev.calib_accumulate(mla.SURF, pose, 1, k_neigh=5, flags=0)
+        host.calib_add(types, pts, co, ones)
+        info2 = dev.calib_info()
+        assert info2["n_tiles"] == 2 * tiles and info2["n_slots"] == 2 * 256 * tiles and info2["n_valid"] == 2 * nv and info2["n_appends"] == 2
+        a, b = dev.pure_odom_normal_eq(pivot, frames, exts, mc.HUBER), host.pure_odom_normal_eq(pivot, frames, exts, mc.HUBER)
+        assert a["count"] == b["count"] == 2 * nv
+        e = max(np.abs(a["H"] - b["H"]).max() / np.abs(b["H"]).max(), np.abs(a["g"] - b["g"]).max() / np.abs(b["g"]).max(), abs(a["cost"] - b["cost"]) / b["cost"])
+        print(f"m = {m} two appends: worst relative difference {e:.2e}")
+        assert e <= 1e-12                                       # test_accumulate_equals_the_host_route's bound: the host's second append starts on another tile
+
+
 def test_calib_selftest_facade_equals_the_c_abi():
     """8. m-loam_amd/host/calib_selftest: the chain through the facade and through the plain calls ends in the same poses and the same prior bits"""
     exe = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "m-loam_amd", "host", "calib_selftest")
