@@ -516,7 +516,7 @@ int orc_scan_factor_eval(char type, const double *point, const double *coeff, do
 }
 
 // stats: per outer iteration 16 doubles: [0] n_corner [1] n_surf [2] solved [3] lm iterations [4] initial cost [5] final cost
-// [6] termination [7..13] pose_after
+// [6] termination [7..13] pose_after [14] successful steps [15] evaluations
 int orc_track_cloud(const float *corner_last, int n_cl, const float *surf_last, int n_sl, const float *corner_sharp, int n_cs,
                     const float *surf_flat, int n_sf, const double *pose_ini, const double *tprm, double *pose_out, double *stats, int *n_outer)
 {
@@ -533,6 +533,7 @@ int orc_track_cloud(const float *corner_last, int n_cl, const float *surf_last, 
         o[0] = st[i].n_corner; o[1] = st[i].n_surf; o[2] = st[i].solved; o[3] = st[i].solve.num_iterations;
         o[4] = st[i].solve.initial_cost; o[5] = st[i].solve.final_cost; o[6] = st[i].solve.termination;
         for (int k = 0; k < 7; ++k) o[7 + k] = st[i].pose_after[k];
+        o[14] = st[i].solve.num_successful_steps; o[15] = st[i].solve.num_evaluations;
     }
     return 0;
 }

@@ -886,5 +886,5 @@ def track_cloud(corner_last4, surf_last4, corner_sharp4, surf_flat4, pose_ini, t
     lib().orc_track_cloud(_ptr(a[0]), len(a[0]), _ptr(a[1]), len(a[1]), _ptr(a[2]), len(a[2]), _ptr(a[3]), len(a[3]), _ptr(p0), _ptr(tprm),
                           _ptr(pose), _ptr(stats), C.byref(n_outer))
     outer = [dict(n_corner=int(o[0]), n_surf=int(o[1]), solved=bool(o[2]), lm_iterations=int(o[3]), initial_cost=o[4], final_cost=o[5],
-                  termination=int(o[6]), pose_after=o[7:14].copy()) for o in stats[:n_outer.value]]
+                  termination=int(o[6]), pose_after=o[7:14].copy(), successful_steps=int(o[14]), evaluations=int(o[15])) for o in stats[:n_outer.value]]
     return dict(pose=pose, outer=outer)

@@ -1,6 +1,10 @@
 """Bounded runs of the soak scripts (scripts/soak_*.py; the long runs and what they found: profiles/r04_soak.txt) so that the GPU suite itself exercises them:
 random call sequences under both Gauss-Newton schedules, history-independence of the whole C-ABI on a long-lived context (and on four threads), the HIP path
-against the oracle on random problems, the rows around the solver on random inputs, the mailbox communicator under random calls with ranks sharing the GPU."""
+against the oracle on random problems, the rows around the solver on random inputs, the mailbox communicator under random calls with ranks sharing the GPU.
+
+What the bounded parity soak does NOT reach: its eight scan2MapOptimization solves (`soak_parity.py 6 103` and `6 203`, hard family) accept every step and leave on the
+function tolerance at the last candidate (successful_steps == lm_iterations - 1, termination 3 in every outer iteration). The Levenberg-Marquardt loop's rejected
+steps, its kept diagonal and its other exits are tested on the crafted starts of tests/lm_cases.py (tests/test_lm_cases.py, tests/test_gpu_lm_cases.py)."""
 import os
 import subprocess
 import sys
