@@ -245,6 +245,10 @@ int mlh_create(mlh_ctx **out, int device_id)
         if (v != 256 && v != 512 && v != 1024) { delete c; return MLH_ERR_INVALID; }
         c->knn_wg_override = v;
     }
+    if (const char *e = std::getenv("MLH_GN_FIT_IN_SEARCH")) {
+        if ((e[0] != '0' && e[0] != '1') || e[1] != '\0') { delete c; return MLH_ERR_INVALID; }
+        c->gn_fit_in_search = e[0] - '0';
+    }
     if (query_device_caps(c) != MLH_OK) { delete c; return MLH_ERR_HIP; }
     // the solver's stream: the whole device, or -- MLH_SOLVER_CU_MASK=<hex word>[,<hex word>...], bit i of word w = compute unit 32 w + i -- a part of it (a
     // deployment that keeps compute units for other work; the tests of the residency gates)

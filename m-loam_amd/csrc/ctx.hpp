@@ -804,7 +804,15 @@ struct mlh_ctx {
         double thre = 100.0;
         void *rec = nullptr;      // HostPublish of that solve
         unsigned long long seq = 0;
+        const double *recs = nullptr;   // where that iteration's records are (device; null: `partials`) and how they are laid out: 1 record or 4 wavefront rows per tile
+        int rows = 1;
     } gn_pending;
+    // The fit in the tail of the search launch (match.hip: knn_features_wide_kernel<.., FIT>, fit_in_search()).
+    int gn_fit_in_search = -1;    // -1: the rule (chip-filling wide launches fuse); MLH_GN_FIT_IN_SEARCH=0|1 in the environment at mlh_create pins it: none / every launch that can (tests, A/B runs)
+    int gn_fused_launches = 0;    // fused launches the last submitted Gauss-Newton solve enqueued
+    mlh::DevBuf gn_rows;          // two sets of wavefront rows (4 x NE_STRIDE doubles per 256-feature tile), half the buffer each: a fused launch writes the set its
+    int gn_rows_set = 0;          // prologue does not read (a fast workgroup stores its row while a slow one still sums); the set the last fused launch wrote
+    struct GnRecords { const double *p = nullptr; int rows = 1; } gn_last;   // where the newest iteration that left records left them, and in which layout
     int gn_slot_base = 0;         // xi slots of the next solve
     int gn_defer = 1;             // mlh_set_gn_schedule: 0: Gauss-Newton solves keep the classic finish (the fit kernel's last-arriving workgroup) in every iteration (A/B, tests)
     int knn_warm = 1;             // mlh_set_gn_schedule: 0: iterations >= 1 of a solve search without the previous iteration's neighbours as a bound (A/B, tests)

@@ -93,6 +93,12 @@ struct KParams {
     unsigned long long *loop_tagged;   // lm_loop_kernel: two sets of tagged records (64 words per tile), or null: records + grid barrier (MLH_LOOP_TAGGED=0)
     unsigned loop_tag_base;  // this launch's tag: (launch number << 8); the iteration goes into the low byte
     int debug_stall;         // MLH_DEBUG_LOOP_STALL=1 (tests): one workgroup of lm_loop_kernel never arrives at its second barrier -- the loop must end with the error bit, not hang
+    // The fit in the tail of the search launch (knn_features_wide_kernel<.., FIT>). Appended behind everything else: no other field's offset moves.
+    // (16 bytes, one load)
+    double *rows_out;        // a fused launch: where its fits' wavefront rows go -- row (tile256 * 4 + wave) * NE_STRIDE, surf tiles, then corner tiles; the other set than `partials`
+    int pre_rows;            // how the records the prologue sums (`partials`, pre_tiles tiles) are laid out: 1 = one record per 256-feature tile (fit_linearize_kernel's),
+                             // 4 = four wavefront rows per tile (a fused launch's), summed ((w0 + w1) + w2) + w3 as the fit kernel's workgroup sums them. 0 reads as 1
+    int fit_pad_;
 };
 
 }  // namespace mlh

@@ -179,6 +179,7 @@ typedef float arg_f4 __attribute__((ext_vector_type(4)));
 typedef float arg_f2 __attribute__((ext_vector_type(2)));
 typedef double arg_d2 __attribute__((ext_vector_type(2)));
 typedef double arg_d4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long arg_u4 __attribute__((ext_vector_type(4)));      // four neighbouring pointers
 #define MLH_KIND_COUNTS(K_) arg_i4{(K_).m, (K_).tiles_a, (K_).tiles_b, (K_).nbr_stride}
 #define MLH_WORDS(P_) arg_i4{int((P_).flags), (P_).own_mode, (P_).n_blocks, (P_).use_init}
 #define MLH_GRID_ORIGIN(K_) arg_f4{(K_).grid.ox, (K_).grid.oy, (K_).grid.oz, (K_).grid.inv_h}
@@ -243,7 +244,7 @@ __device__ __forceinline__ bool owns(const KParams &P, int f, float sx, float sy
 // array by reference, the lane's pick (a select chain over keys[t]) is folded into ONE load at a selected offset before the array is scalarised, and the
 // keys then live in scratch / LDS instead of registers (seen in the ISA: 48 bytes of scratch, +10 KB of LDS per workgroup).
 // lane t (< K <= G) fetches winner t: one load per lane, all in flight together
-#define MLH_STORE_WINNERS(K_, G_, Kd_, f_, gl_, keys_)                                                          \
+#define MLH_STORE_WINNERS(K_, G_, Kd_, f_, gl_, keys_, HAND_, lds_)                                                        \
     do {                                                                                                        \
         unsigned long long kk_ = keys_[0];                                                                      \
         _Pragma("unroll") for (int t_ = 1; t_ < (K_); ++t_) kk_ = ((gl_) == t_ % (G_)) ? keys_[t_] : kk_;      \
@@ -255,6 +256,7 @@ __device__ __forceinline__ bool owns(const KParams &P, int f, float sx, float sy
                     o_ = make_float4(np_.x, np_.y, np_.z, __uint_as_float((unsigned)(kk_ >> 32)));              \
                 }                                                                                               \
                 (Kd_).nbr[size_t(f_) * (Kd_).nbr_stride + (gl_)] = o_;                                          \
+                if constexpr (HAND_) (lds_)[(gl_)] = o_;                                                        \
             }                                                                                                   \
         } else {                                                                                                \
             _Pragma("unroll") for (int t_ = 0; t_ < (K_); ++t_) {                                               \
@@ -271,23 +273,27 @@ __device__ __forceinline__ bool owns(const KParams &P, int f, float sx, float sy
         }                                                                                                       \
     } while (0)
 
-template <int K, int G>
-__device__ __forceinline__ void knn_feature(const KParams &P, const KindL &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run)
+// HAND (the fused launches, knn_features_wide_kernel<.., FIT>): the lanes that store the K = 5 winners also leave them in LDS at lds_nbr[0 .. 4], for the lane
+// that fits this feature behind the search
+template <int K, int G, bool HAND = false>
+__device__ __forceinline__ void knn_feature(const KParams &P, const KindL &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run, float4 *lds_nbr = nullptr)
 {
+    static_assert(!HAND || K <= G, "the hand-over is the one-record-per-lane store's");
     unsigned long long keys[K];
     if constexpr (G == 32) knn_group_bounded<K, 32, true>(Kd.grid, sx, sy, sz, gl, lds_run, 0x7f800000u, keys);
     else if constexpr (G == 16) knn_group16_pruned<K>(Kd.grid, sx, sy, sz, gl, lds_run, keys);
     else knn_group8_pruned<K>(Kd.grid, sx, sy, sz, gl, lds_run, keys);
     MLH_KSTAGE(4);
-    MLH_STORE_WINNERS(K, G, Kd, f, gl, keys);
+    MLH_STORE_WINNERS(K, G, Kd, f, gl, keys, HAND, lds_nbr);
     MLH_KSTAGE(5);
 }
 
 // The same feature one Gauss-Newton iteration later: `old` is this lane's share (lane t: records t, t + G, ... below K) of the neighbour records the previous
 // iteration left -- K points of the SAME map. Their largest squared distance from the query's new position bounds the K-th neighbour's from above, so the search
 // is a single walk over the cells within that bound (knn_group_bounded). A feature that had fewer than K neighbours (w = +inf) searches as before.
-template <int K, int G, int NREC>
-__device__ __forceinline__ void knn_feature_warm(const KParams &P, const KindL &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run, const float4 (&old)[NREC])
+template <int K, int G, int NREC, bool HAND = false>
+__device__ __forceinline__ void knn_feature_warm(const KParams &P, const KindL &Kd, int f, float sx, float sy, float sz, int gl, int *lds_run, const float4 (&old)[NREC],
+                                                 float4 *lds_nbr = nullptr)
 {
     unsigned bits = 0u;
 #pragma unroll
@@ -300,19 +306,21 @@ __device__ __forceinline__ void knn_feature_warm(const KParams &P, const KindL &
         }
     }
     bits = group_max_u32<G>(bits);
-    if (bits >= 0x7f800000u) { knn_feature<K, G>(P, Kd, f, sx, sy, sz, gl, lds_run); return; }     // uniform over the group
+    if (bits >= 0x7f800000u) { knn_feature<K, G, HAND>(P, Kd, f, sx, sy, sz, gl, lds_run, lds_nbr); return; }     // uniform over the group
     unsigned long long keys[K];
     knn_group_bounded<K, G>(Kd.grid, sx, sy, sz, gl, lds_run, bits, keys);
     MLH_KSTAGE(4);
-    MLH_STORE_WINNERS(K, G, Kd, f, gl, keys);
+    MLH_STORE_WINNERS(K, G, Kd, f, gl, keys, HAND, lds_nbr);
     MLH_KSTAGE(5);
 }
 
 // MB = more than one pose block in the launch (config 4); without it the block bookkeeping (a per-lane block index and the
 // per-block K lookup it drags along) compiles away
 // W: threads per workgroup (TPB, or 512 / 1024 in the wide prologue forms)
-template <int G, bool MB, bool K10, bool PRE, bool WARM, int W = TPB>
-__device__ __forceinline__ void knn_features_body(const KParams &P, const KindL &K, int kind, int own_mode, int tile, int *s_run, const double *s_pose, int m_feat)
+// HAND: the K = 5 winners also go to s_nbr[5 * query of the workgroup ..] (knn_feature)
+template <int G, bool MB, bool K10, bool PRE, bool WARM, int W = TPB, bool HAND = false>
+__device__ __forceinline__ void knn_features_body(const KParams &P, const KindL &K, int kind, int own_mode, int tile, int *s_run, const double *s_pose, int m_feat,
+                                                  float4 *s_nbr = nullptr)
 {
     constexpr int FPB = W / G;            // queries per workgroup
     constexpr int RUNW = 2 * KNN_RUN_WORDS;
@@ -349,10 +357,10 @@ __device__ __forceinline__ void knn_features_body(const KParams &P, const KindL 
     // even compiled in, so the ordinary frame's kernel keeps the K = 5 register footprint
     if constexpr (WARM) {
         if (K10 && (MB ? P.kb[b] : P.kb[0]) == 10) knn_feature_warm<10, G, NREC>(P, K, f, sx, sy, sz, gl, s_run + grp * RUNW, old);
-        else knn_feature_warm<5, G, NREC>(P, K, f, sx, sy, sz, gl, s_run + grp * RUNW, old);
+        else knn_feature_warm<5, G, NREC, HAND>(P, K, f, sx, sy, sz, gl, s_run + grp * RUNW, old, s_nbr + (HAND ? grp * 5 : 0));
     } else {
         if (K10 && (MB ? P.kb[b] : P.kb[0]) == 10) knn_feature<10, G>(P, K, f, sx, sy, sz, gl, s_run + grp * RUNW);
-        else knn_feature<5, G>(P, K, f, sx, sy, sz, gl, s_run + grp * RUNW);
+        else knn_feature<5, G, HAND>(P, K, f, sx, sy, sz, gl, s_run + grp * RUNW, s_nbr + (HAND ? grp * 5 : 0));
     }
 }
 
@@ -365,7 +373,9 @@ __device__ __forceinline__ void knn_features_body(const KParams &P, const KindL 
 // b: the pose block this workgroup's features belong to (0 without blocks): the records summed are that block's tiles -- its surf tiles, then its corner tiles, as the
 // classic finish walks them -- and the thresholds that block's.
 constexpr int GN_SUM_THREADS = 256;      // the sum's geometry: 8 slices x 32 columns, whatever the workgroup's width (the association is part of the result's bits)
-template <int MODE, bool MB = false, int W = TPB>
+// ROWS (the wide kernels and gn_final_kernel): the records may be a fused launch's wavefront rows, four per tile (P.pre_rows == 4): a tile's value is then formed where
+// it is loaded, ((w0 + w1) + w2) + w3 -- what the fit kernel's workgroup stores as the tile's record -- and enters the same slices and chains.
+template <int MODE, bool MB = false, int W = TPB, bool ROWS = false>
 __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_pose, double *f_ne, double *f_cnt2, double *f_scratch)
 {
     // (the pose is requested here and stored behind the records' sum: its trip and the records' run together, not one behind the other)
@@ -391,16 +401,75 @@ __device__ __forceinline__ void gn_prologue(const KParams &P, int b, double *s_p
         const int ntot = sums ? n0 + n1 : 0;
         const double *__restrict__ rec = P.partials;
         double ch[4] = {0.0, 0.0, 0.0, 0.0};
-        for (int j = sl; j < ntot; j += U * NS) {
-            double tv[U];
+        bool rows4 = false;
+        if constexpr (ROWS) rows4 = P.pre_rows == 4;
+        if (ROWS && rows4) {                 // (uniform)
+            static_assert(!ROWS || !MB, "wavefront rows: single-block launches only");
+            if constexpr (W > GN_SUM_THREADS) {
+                // Four times the loads of a record sum: a wide workgroup shares them out by CHAIN. Part p (threads 256 p .. 256 p + 255; 2 or 4 parts) walks slice sl, column c
+                // like the summing thread it mirrors, but only the tiles of chains p, p + parts, ...: chain k takes u = k, k + 4, k + 8 of every batch, in that order, so
+                // each chain is the same sequence of additions as in one thread. The chains meet in LDS and the summing thread adds them (ch0 + ch1) + (ch2 + ch3).
+                constexpr int PARTS = W / GN_SUM_THREADS >= 4 ? 4 : 2, CPP = 4 / PARTS;
+                __shared__ double s_ch[4 * GN_SUM_THREADS];
+                const int part = threadIdx.x / GN_SUM_THREADS, t8 = threadIdx.x % GN_SUM_THREADS, pc = t8 & 31, psl = t8 >> 5, nall = n0 + n1;
+                if (part < PARTS) {
+                    double chp[CPP];
 #pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const int jj = j + NS * u;
-                const int tile = jj < n0 ? lo0 + jj : lo1 + (jj - n0);
-                tv[u] = jj < ntot ? rec[size_t(tile) * NE_STRIDE + c] : 0.0;
+                    for (int kk = 0; kk < CPP; ++kk) chp[kk] = 0.0;
+                    for (int j = psl; j < nall; j += U * NS) {
+                        double wv[CPP][U / 4][4];
+#pragma unroll
+                        for (int kk = 0; kk < CPP; ++kk)
+#pragma unroll
+                            for (int v = 0; v < U / 4; ++v) {
+                                const int jj = j + NS * (part + PARTS * kk + 4 * v);
+#pragma unroll
+                                for (int w = 0; w < 4; ++w) wv[kk][v][w] = jj < nall ? rec[(size_t(jj) * 4 + w) * NE_STRIDE + pc] : 0.0;
+                            }
+#pragma unroll
+                        for (int kk = 0; kk < CPP; ++kk)
+#pragma unroll
+                            for (int v = 0; v < U / 4; ++v) chp[kk] += ((wv[kk][v][0] + wv[kk][v][1]) + wv[kk][v][2]) + wv[kk][v][3];
+                    }
+#pragma unroll
+                    for (int kk = 0; kk < CPP; ++kk) s_ch[(part + PARTS * kk) * GN_SUM_THREADS + t8] = chp[kk];
+                }
+                __syncthreads();
+                if (sums) {
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) ch[k] = s_ch[k * GN_SUM_THREADS + t8];
+                }
+            } else {      // (gn_final_kernel: one workgroup of 256 threads)
+                for (int j = sl; j < ntot; j += U * NS) {
+                    double tv[U];
+#pragma unroll
+                    for (int h = 0; h < U; h += U / 2) {          // half a batch of tiles at a time: 24 row loads in flight
+                        double wv[U / 2][4];
+#pragma unroll
+                        for (int u = 0; u < U / 2; ++u) {
+                            const int jj = j + NS * (h + u);
+#pragma unroll
+                            for (int w = 0; w < 4; ++w) wv[u][w] = jj < ntot ? rec[(size_t(jj) * 4 + w) * NE_STRIDE + c] : 0.0;
+                        }
+#pragma unroll
+                        for (int u = 0; u < U / 2; ++u) tv[h + u] = ((wv[u][0] + wv[u][1]) + wv[u][2]) + wv[u][3];
+                    }
+#pragma unroll
+                    for (int u = 0; u < U; ++u) ch[u & 3] += tv[u];
+                }
             }
+        } else {
+            for (int j = sl; j < ntot; j += U * NS) {
+                double tv[U];
 #pragma unroll
-            for (int u = 0; u < U; ++u) ch[u & 3] += tv[u];
+                for (int u = 0; u < U; ++u) {
+                    const int jj = j + NS * u;
+                    const int tile = jj < n0 ? lo0 + jj : lo1 + (jj - n0);
+                    tv[u] = jj < ntot ? rec[size_t(tile) * NE_STRIDE + c] : 0.0;
+                }
+#pragma unroll
+                for (int u = 0; u < U; ++u) ch[u & 3] += tv[u];
+            }
         }
         if (sums) f_scratch[sl * 32 + c] = (ch[0] + ch[1]) + (ch[2] + ch[3]);
         if (threadIdx.x < 7) s_pose[threadIdx.x] = pose_v;
@@ -430,6 +499,11 @@ __device__ __forceinline__ void publish_final_pose(const KParams &P, const doubl
     }
 }
 
+// (the fit kernel's pieces the fused correspondence launches run behind their search; defined with that kernel, below)
+template <int K, int KV>
+__device__ __forceinline__ bool fit_feature(float min_match_sq_dis, float min_plane_dis, int kind, const float4 (&v)[KV], float (&coef)[6]);
+__device__ __forceinline__ double feature_weight_pref(uint32_t flags, double cov_measurement_trace, const KindL &K, const float4 &cd);
+
 // G = lanes per query for both kinds, or 0: per kind (KindP::lanes -- a workgroup serves one kind, so the choice is uniform over it)
 // PRE 1: the launch completes the previous Gauss-Newton iteration first -- EVERY workgroup sums the records the previous fit launch's tiles left (same order,
 //   same code: the same bits everywhere), runs the 6 x 6 solve + Plus on one wavefront and goes on with the pose in LDS; the kernel boundary behind the fit
@@ -446,15 +520,25 @@ template <int G, bool MB, bool K10, int PRE = 0, bool WARM = false, bool DEVM = 
 __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
 {
     constexpr int W = TPB;
+    constexpr bool FIT = false;
 #include "knn_features_kernel.inc"
 }
 
 // The wide forms of the single-block, K = 5 launches of mlh_gn_solve* (PRE 1 warm and cold, PRE 2, PRE 0 warm): the same body, prologue and argument batch in
 // workgroups of 512 or 1024 threads. Kernels of their own: the 256-thread instantiations above keep their names and their code.
-template <int W, int G, int PRE, bool WARM>
+// FIT: the launch also FITS -- it is a whole Gauss-Newton iteration whose fit launch would have been fit_linearize_kernel<5, false, false> leaving records (the host's
+//   fit_in_search(): single block, K = 5, one rank, no dense rows, a prologue in front, every kind at 64 queries or more per workgroup). Behind the search the
+//   workgroup's queries ARE the features 64 w .. 64 w + 63 of one or two wavefront rows of a 256-feature tile (a wide tile starts at a multiple of 64): the lanes that
+//   stored a query's five winners left them in LDS as well, and the workgroup's first one or two wavefronts take one feature per lane -- feature f on lane f & 63 --
+//   through that kernel's body: fit_feature<5>, the Corr store, eval_factor at the pose in s_pose, the Huber scaling and the butterfly, up to the wavefront's row
+//   (reduce_rows_wave), which goes to P.rows_out[(tile256 * 4 + wave) * 32]. The next launch's prologue adds a tile's four rows as the fit kernel's workgroup does
+//   (gn_prologue<.., ROWS>): the same bits, without the launch boundary, the trip that fetches the neighbour records back and the search's idle tail. The rows of a
+//   kind's last 256-feature tile that no workgroup produces are written as zeros by the workgroup of the kind's last wide tile. No workgroup waits for another.
+template <int W, int G, int PRE, bool WARM, bool FIT = false>
 __global__ __launch_bounds__(W) void knn_features_wide_kernel(KParams P)
 {
     static_assert(W == 512 || W == 1024, "wide workgroups: 512 or 1024 threads");
+    static_assert(!FIT || (PRE != 0 && (G == 0 || W / G >= 64)), "the fused form: a prologue in front, whole wavefront rows per workgroup");
     constexpr bool MB = false, K10 = false, DEVM = false;
 #include "knn_features_kernel.inc"
 }
@@ -463,7 +547,7 @@ __global__ __launch_bounds__(W) void knn_features_wide_kernel(KParams P)
 __global__ __launch_bounds__(TPB) void gn_final_kernel(KParams P)
 {
     __shared__ double s_pose[8], f_ne[NE_STRIDE], f_cnt2[2], f_scratch[(GN_SUM_THREADS / 32) * 32];
-    gn_prologue<2>(P, 0, s_pose, f_ne, f_cnt2, f_scratch);
+    gn_prologue<2, false, TPB, true>(P, 0, s_pose, f_ne, f_cnt2, f_scratch);      // (records or a fused launch's rows: P.pre_rows)
     if (threadIdx.x == 0) publish_final_pose(P, s_pose);
 }
 
@@ -1199,7 +1283,57 @@ static int knn_wg_threads_for(const mlh_ctx *ctx, bool has_wide_form, int tiles2
     return tiles256 > ctx->caps.cu_solver ? KNN_WG_WIDE : TPB;
 }
 
-static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg = nullptr)
+static int knn_tiles256(const mlh_ctx *ctx, int kind_mask, const int lanes[2])
+{
+    int tiles256 = 0;
+    for (int k = 0; k < 2; ++k) if ((kind_mask & (1 << k)) && ctx->feat[k].m > 0) tiles256 += (ctx->feat[k].m + TPB / lanes[k] - 1) / (TPB / lanes[k]);
+    return tiles256;
+}
+
+// The width of a correspondence launch over these kinds, in ONE place: fill_params asks it for the launch it builds, gn_solve_submit (through gn_search_width) for the
+// launch it is about to plan -- the two cannot disagree on the rule, the lanes or the sharding. gn_shape: the launch is one of mlh_gn_solve*'s single-block, K = 5
+// launches with a prologue or a bounded search and host-side counts (the only ones that have wide forms).
+static int knn_width_of(const mlh_ctx *ctx, int kind_mask, bool gn_shape)
+{
+    int lanes[2];
+    knn_lanes_for(ctx, kind_mask, lanes);
+    const bool sharded = ctx->shard_lo || ctx->shard_hi || ctx->own_mod > 1;
+    return knn_wg_threads_for(ctx, gn_shape && !sharded, knn_tiles256(ctx, kind_mask, lanes));
+}
+int gn_search_width(const mlh_ctx *ctx, int kind_mask) { return knn_width_of(ctx, kind_mask, true); }
+
+// The two sets of wavefront rows of a frame with `tiles256` 256-feature tiles (mlh_ctx::gn_rows; a set begins at a multiple of 256 bytes in its half of the buffer).
+size_t gn_rows_bytes(int tiles256) { return 2 * sizeof(double) * NE_STRIDE * 4 * size_t(tiles256) + 512; }
+static double *gn_rows_set_ptr(const mlh_ctx *ctx, int set) { return reinterpret_cast<double *>(static_cast<char *>(ctx->gn_rows.p) + size_t(set) * ((ctx->gn_rows.cap / 2) & ~size_t(255))); }
+
+// One Gauss-Newton iteration as ONE launch -- the fit in the tail of its search (knn_features_wide_kernel<.., FIT>) -- or as two. Fused: a launch that goes wide
+// anyway, has a prologue in front (PRE 1 / PRE 2), whose fit launch would be fit_linearize_kernel<5, false, false> leaving records (single block, K = 5 and one rank
+// come with the wide form; no dense rows, no statistics, no publication from the fit), and whose every kind puts whole wavefront rows -- 64 queries or more -- into
+// a workgroup. Everything else keeps two launches.
+// Of the launches that can fuse, the rule fuses the chip-filling ones -- more than KNN_LATENCY_LIMIT queries, the throughput regime of knn_lanes_for, where the gain
+// was measured (profiles/r09_gn_fit_in_search.txt: one 1 024-thread workgroup per compute unit, half of them idle through the search's last 4 us). A smaller frame that
+// goes wide (the 16-ring frame of tests/test_gpu_launch_census.py: 5 451 features, 86 wide workgroups on 256 compute units) keeps its two launches: not measured, and
+// recorded that way. MLH_GN_FIT_IN_SEARCH=1 fuses every launch that can, =0 none (tests, A/B runs).
+static bool fit_in_search(const mlh_ctx *ctx, const MatchArgs &a, const KParams &P, int wg)
+{
+    if (ctx->gn_fit_in_search == 0 || wg == TPB || P.pre_finish == PRE_NONE) return false;
+    if (P.finish != TAIL_RECORDS || a.no_fit || a.dense || a.lmc != LMC_NONE || P.stat || P.own_mode || P.n_blocks != 1 || a.gn_blocks || P.m_dev) return false;
+    long long queries = 0;
+    for (int k = 0; k < 2; ++k) {
+        if (!(a.kind_mask & (1 << k))) continue;
+        if (P.k[k].lanes < 8 || wg / P.k[k].lanes < 64) return false;
+        queries += P.k[k].m;
+    }
+    return ctx->gn_fit_in_search > 0 || queries > KNN_LATENCY_LIMIT;
+}
+
+struct GnLaunchPlan {
+    bool fused = false;                // fit_in_search()
+    const double *rec_in = nullptr;    // the records the search launch's prologue sums when they are not in `partials`: a fused launch's rows
+    int rows_in = 1;
+};
+
+static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg = nullptr, GnLaunchPlan *plan = nullptr)
 {
     // a solve whose last iteration is still a set of tile records (mlh_ctx::gn_pending): any launch that writes records -- other than the chained successor's first,
     // which consumes them -- completes that solve first
@@ -1225,11 +1359,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg
     {
         // (the launches match_launch sends through MLH_KNN_LAUNCH_GN, on one rank)
         const bool prologue_or_warm = a.gn_iter >= 1 || a.pre_final || a.warm;
-        const bool sharded = ctx->shard_lo || ctx->shard_hi || ctx->own_mod > 1;
-        const bool has_wide_form = prologue_or_warm && P.n_blocks == 1 && kmax == 5 && !a.gn_blocks && !a.m_dev && !sharded;
-        int tiles256 = 0;
-        for (int k = 0; k < 2; ++k) if ((a.kind_mask & (1 << k)) && ctx->feat[k].m > 0) tiles256 += (ctx->feat[k].m + TPB / lanes[k] - 1) / (TPB / lanes[k]);
-        wg = knn_wg_threads_for(ctx, has_wide_form, tiles256);
+        wg = knn_width_of(ctx, a.kind_mask, prologue_or_warm && P.n_blocks == 1 && kmax == 5 && !a.gn_blocks && !a.m_dev);
     }
     if (knn_wg) *knn_wg = wg;
     for (int k = 0; k < 2; ++k) {
@@ -1355,6 +1485,20 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg
     P.publish_seq = a.publish_seq;
     P.ticket = ctx->ticket.as<unsigned>();
     P.stat = (a.stat_slot >= 0) ? ctx->stats.as<IterStatDev>() + a.stat_slot : nullptr;
+    P.pre_rows = 1;
+    if (plan) {
+        // the records this launch's prologue sums: the previous iteration's (mlh_ctx::gn_last) or the previous solve's (MatchArgs::pre_final_recs) -- tile records in
+        // `partials`, or a fused launch's wavefront rows
+        plan->rec_in = nullptr; plan->rows_in = 1;
+        if (P.pre_finish == PRE_ITERATION && !a.gn_blocks && ctx->gn_last.rows == 4) { plan->rec_in = ctx->gn_last.p; plan->rows_in = 4; }
+        if (P.pre_finish == PRE_SOLVE && a.pre_final_rows == 4) { plan->rec_in = a.pre_final_recs; plan->rows_in = 4; }
+        plan->fused = fit_in_search(ctx, a, P, wg);
+        if (plan->fused) {
+            if ((e = ctx->gn_rows.ensure(gn_rows_bytes(tiles_b_total))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc wavefront rows", e);
+            // (a set the prologue reads lies in this buffer; a reallocation would have been refused before the launch was planned: gn_solve_submit's `consume`)
+            P.rows_out = gn_rows_set_ptr(ctx, ctx->gn_rows_set ^ 1);
+        }
+    }
     return MLH_OK;
 }
 
@@ -1375,7 +1519,8 @@ int gn_flush_pending(mlh_ctx *ctx)
     KParams P;
     std::memset(&P, 0, sizeof(P));
     SolverState *S = ctx->state.as<SolverState>();
-    P.partials = ctx->partials.as<double>();
+    P.partials = ctx->gn_pending.rows == 4 ? const_cast<double *>(ctx->gn_pending.recs) : ctx->partials.as<double>();
+    P.pre_rows = ctx->gn_pending.rows;
     P.state = S;
     P.pre_finish = PRE_SOLVE;
     P.pre_tiles = ctx->gn_pending.tiles;
@@ -1394,8 +1539,16 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
 {
     KParams P;
     int wg = TPB;
-    int rc = fill_params(ctx, a, P, &wg);
+    GnLaunchPlan plan;
+    int rc = fill_params(ctx, a, P, &wg, &plan);
     if (rc) return rc;
+    // (the search launch's prologue reads the previous iteration's records where and how that iteration left them; the fit launch, if there is one, writes `partials`)
+    double *const partials = P.partials;
+    if (plan.rows_in == 4) {
+        if (wg == TPB) return fail(ctx, MLH_ERR_STATE, "wavefront rows in front of a launch without a wide kernel");
+        P.partials = const_cast<double *>(plan.rec_in);
+        P.pre_rows = 4;
+    }
     // kernel A: correspondences (8 or 16 lanes per feature, wg threads per workgroup); kernel B: fit + linearise + reduce (one lane per feature)
     const int grid_a = ((P.k[0].tiles_a + P.k[1].tiles_a + 7) / 8) * 8;
     const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
@@ -1447,6 +1600,21 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
             else if (P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_MB(16);
             else MLH_KNN_LAUNCH_GN_MB(8);
         }
+        else if (plan.fused) {
+            // the whole iteration in this launch (fit_in_search()): the search's profiler id, no MLH_K_FIT launch
+#define MLH_KNN_LAUNCH_GN_FUSED(W_, G_) do { \
+            if (P.pre_finish == PRE_SOLVE) launch_timed(ctx, MLH_K_KNN_FIRST, knn_features_wide_kernel<W_, G_, 2, false, true>, grid_a, P, W_); \
+            else if (P.warm) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, true, true>, grid_a, P, W_); \
+            else launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, false, true>, grid_a, P, W_); \
+        } while (0)
+            if (wg == 1024 && P.knn_lanes == 0) MLH_KNN_LAUNCH_GN_FUSED(1024, 0);
+            else if (wg == 1024 && P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_FUSED(1024, 16);
+            else if (wg == 1024 && P.knn_lanes == 8) MLH_KNN_LAUNCH_GN_FUSED(1024, 8);
+            else if (wg == 512 && P.knn_lanes == 8) MLH_KNN_LAUNCH_GN_FUSED(512, 8);
+            else return fail(ctx, MLH_ERR_STATE, "a fused Gauss-Newton launch without a fused kernel");
+#undef MLH_KNN_LAUNCH_GN_FUSED
+            ctx->knn_wg_last = wg;
+        }
         else if (P.pre_finish || P.warm) {
             if (P.knn_lanes == 0) MLH_KNN_LAUNCH_GN_W(0);
             else if (P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_W(16);
@@ -1461,6 +1629,17 @@ int match_launch(mlh_ctx *ctx, const MatchArgs &a)
 #undef MLH_KNN_LAUNCH_GN
 #undef MLH_KNN_LAUNCH_GN_MB
 #undef MLH_KNN_LAUNCH
+    }
+    P.partials = partials;
+    P.pre_rows = 1;
+    ctx->gn_last.p = nullptr; ctx->gn_last.rows = 1;
+    if (plan.fused) {
+        ctx->gn_rows_set ^= 1;
+        ctx->gn_last.p = P.rows_out; ctx->gn_last.rows = 4;
+        ++ctx->gn_fused_launches;
+        MLH_HIP(ctx, hipGetLastError());
+        for (int k = 0; k < 2; ++k) if (a.kind_mask & (1 << k)) ctx->feat[k].matched = true;
+        return MLH_OK;
     }
     if (a.no_fit) {
         // the fit rides in the loop launch behind this one (lm_consume_launch, fit_in_loop): single block, N_NEIGH 5, both kinds, records only
@@ -1587,3 +1766,5 @@ int knn_launch(mlh_ctx *ctx, int kind, const float *q_host, int nq, int32_t *idx
 
 // For the tests of the width rule (not part of the C-ABI header): threads per workgroup of the context's last correspondence launch that has wide forms, 0 before any
 extern "C" int mlh_debug_knn_wg_threads(mlh_ctx *ctx) { return ctx ? ctx->knn_wg_last : 0; }
+// ... and of the fused iterations: how many launches of the last submitted Gauss-Newton solve carried their fit (fit_in_search())
+extern "C" int mlh_debug_gn_fused_launches(mlh_ctx *ctx) { return ctx ? ctx->gn_fused_launches : 0; }

@@ -135,6 +135,67 @@ __device__ __forceinline__ void reduce_rows(bool valid, Lin L, double huber_delt
     reduce_acc32<MODE>(acc, kind, lds_red, partial_out, tag);
 }
 
+// The same row reduced over ONE wavefront only, as far as reduce_acc32 goes before its workgroup barrier: the 32 doubles it leaves in lds_red[wave * 32 ..] go to
+// row_out instead (match.hip: the fit in the tail of a search launch; the reader adds a tile's four rows ((w0 + w1) + w2) + w3, which is reduce_acc32's own sum). The
+// count column is mirrored into column NE_CNT + 1 + kind here, row by row: four mirrored rows add up to the mirrored sum. Called by all 64 lanes of a wavefront
+// that holds the features 64 w .. 64 w + 63 of its kind on lanes 0 .. 63 (the butterfly's tree is a function of the lane). Huber scaling and butterfly: reduce_rows'
+// and reduce_acc32's statements, repeated (those two stay untouched: the kernels built on them keep their machine code).
+__device__ __forceinline__ void reduce_rows_wave(bool valid, Lin L, double huber_delta, bool no_loss, int kind, double *__restrict__ row_out)
+{
+    double acc[32];
+    if (valid) {
+        double s = L.r * L.r, rho0 = s, rho1 = 1.0;
+        if (!no_loss && huber_delta > 0.0) {
+            const double b = huber_delta * huber_delta;
+            if (s > b) {
+                const double rr = sqrt(s);
+                rho0 = 2.0 * huber_delta * rr - b;
+                rho1 = fmax(DBL_MIN, huber_delta / rr);
+            }
+        }
+        const double sc = sqrt(rho1);
+        double r = L.r * sc;
+        double J[6];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) J[i] = L.J[i] * sc;
+        int q = 0;
+#pragma unroll
+        for (int i = 0; i < 6; ++i)
+#pragma unroll
+            for (int j = i; j < 6; ++j) acc[q++] = J[i] * J[j];
+#pragma unroll
+        for (int i = 0; i < 6; ++i) acc[NE_G + i] = J[i] * r;
+        acc[NE_COST] = 0.5 * rho0;
+        acc[NE_CNT] = 1.0;
+    } else {
+#pragma unroll
+        for (int i = 0; i < 29; ++i) acc[i] = 0.0;
+    }
+    acc[29] = acc[30] = acc[31] = 0.0;
+    const int lane = threadIdx.x & 63;
+#define MLH_RED_STEP(H, MASK)                                              \
+    {                                                                      \
+        const bool up = (lane & (MASK)) != 0;                              \
+        _Pragma("unroll") for (int i = 0; i < (H); ++i) {                  \
+            const double keep = up ? acc[i + (H)] : acc[i];                \
+            const double send = up ? acc[i] : acc[i + (H)];                \
+            acc[i] = keep + __shfl_xor(send, (MASK));                      \
+        }                                                                  \
+    }
+#pragma unroll
+    for (int i = 0; i < 16; ++i) acc[i] = swap_add<true>(acc[i], acc[i + 16]);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = swap_add<false>(acc[i], acc[i + 8]);
+    MLH_RED_STEP(4, 8)
+    MLH_RED_STEP(2, 4)
+    MLH_RED_STEP(1, 2)
+#undef MLH_RED_STEP
+    acc[0] += __shfl_xor(acc[0], 1);
+    const double cnt = __shfl(acc[0], 2 * NE_CNT);
+    const int col = lane >> 1;
+    if ((lane & 1) == 0) row_out[col] = (col == NE_CNT + 1 + kind) ? cnt : acc[0];
+}
+
 // ---- the HostPublish record (ctx.hpp), written by ONE thread of the launch the host waits for: the pose, the `done` word, then `seq` -- last, as a system-scope
 // release store, so a host that finds the sequence number it waits for finds this launch's record behind it. `done`: DoneBits (ctx.hpp).
 __device__ __forceinline__ void publish_seq(HostPublish *pub, unsigned long long seq)

@@ -571,6 +571,7 @@ int mlh_gn_solve(mlh_ctx *ctx, double pose_inout[7], int n_iters, const mlh_solv
     unsigned long long seq = 0;
     const bool fused_publish = !stats && (!distributed(ctx) || ctx->p2p.active);
     const bool defer = !stats && n_iters >= 2 && gn_defer_applies(ctx, mask);
+    ctx->gn_fused_launches = 0;
     for (int it = 0; it < n_iters; ++it) {
         MatchArgs a = gn_iter_args(ctx, opts, mask, it, n_iters, pose_inout, defer);
         if (!distributed(ctx) || ctx->p2p.active) {
@@ -623,8 +624,12 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     const bool defer = n_iters >= 2 && gn_defer_applies(ctx, mask);
     // The previous solve may have left its LAST iteration as tile records (gn_pending). A chained, deferred solve completes it in its own first launch -- unless this
     // frame needs a larger record buffer (the records would not survive the reallocation); everything else completes it now, before the chain launch reads the pose.
-    const bool consume = !pose_in && defer && ctx->gn_pending.active && sizeof(double) * NE_STRIDE * size_t(feature_tiles(ctx, mask)) <= ctx->partials.cap;
+    // A predecessor that left wavefront rows (a fused last iteration) needs a successor whose first launch reads rows -- a wide one -- and whose own rows fit the buffer
+    // the pending set lies in.
+    const bool rows_ok = ctx->gn_pending.rows != 4 || (gn_search_width(ctx, mask) != 256 && gn_rows_bytes(feature_tiles(ctx, mask)) <= ctx->gn_rows.cap);
+    const bool consume = !pose_in && defer && ctx->gn_pending.active && sizeof(double) * NE_STRIDE * size_t(feature_tiles(ctx, mask)) <= ctx->partials.cap && rows_ok;
     mlh_ctx::GnPending pend = ctx->gn_pending;
+    ctx->gn_fused_launches = 0;
     if (ctx->gn_pending.active && !consume && (rc = gn_flush_pending(ctx))) return rc;
     if (!pose_in && !consume && (rc = enqueue_chain_pose(ctx, wodom_prev, wodom_cur, nullptr))) return rc;
     // this solve's own last iteration: left to a successor (or to mlh_gn_solve_end) when the schedule says so
@@ -640,6 +645,7 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
             if (it == 0) {
                 a.pre_final_tiles = pend.tiles; a.pre_final_slot = pend.slot; a.pre_final_thre = pend.thre; a.pre_final_freeze = pend.freeze;
                 a.pre_final_publish = static_cast<HostPublish *>(pend.rec); a.pre_final_seq = pend.seq;
+                a.pre_final_recs = pend.recs; a.pre_final_rows = pend.rows;
                 a.chain_prev = wodom_prev; a.chain_cur = wodom_cur;
             }
         }
@@ -658,6 +664,8 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
         ctx->gn_pending.freeze = 0;
         ctx->gn_pending.rec = rec;
         ctx->gn_pending.seq = seq;
+        ctx->gn_pending.recs = ctx->gn_last.p;       // (a fused last iteration: its set of wavefront rows)
+        ctx->gn_pending.rows = ctx->gn_last.rows;
     }
     ctx->solves.commit(seq, ctx->map_set_cur);
     return MLH_OK;
@@ -703,6 +711,7 @@ int mlh_gn_solve_blocks(mlh_ctx *ctx, double *poses_inout, int n_iters, const ml
     const int nb = bo->n_blocks;
     int rc = solver_begin(ctx, n_iters * nb);
     if (rc) return rc;
+    ctx->gn_fused_launches = 0;
     if ((rc = upload_pose(ctx, poses_inout))) return rc;
     for (int b = 1; b < nb; ++b) if ((rc = upload_block_pose(ctx, b, poses_inout + 7 * b))) return rc;
     const int mask = solve_kind_mask(ctx);

@@ -38,6 +38,8 @@ struct MatchArgs {
     double pre_final_thre = 100.0;
     HostPublish *pre_final_publish = nullptr;
     unsigned long long pre_final_seq = 0;
+    const double *pre_final_recs = nullptr;  // device: the predecessor's records (null: the context's `partials`), one record or four wavefront rows per tile
+    int pre_final_rows = 1;
     const double *chain_prev = nullptr, *chain_cur = nullptr;   // host: the two odometry poses of the chain (7 doubles each)
     LmConsumer lmc = LMC_NONE;
     int lmc_j = 0;       // lm_consume_launch: the launch's number within its loop (1, 2, ...: record buffer (j - 1) & 1 is read, j & 1 written)
@@ -50,6 +52,8 @@ struct MatchArgs {
     unsigned long long publish_seq = 0;
 };
 int match_launch(mlh_ctx *ctx, const MatchArgs &a);
+int gn_search_width(const mlh_ctx *ctx, int kind_mask);      // threads per workgroup a single-block, K = 5 Gauss-Newton correspondence launch over these kinds takes on one rank
+size_t gn_rows_bytes(int tiles256);                            // what mlh_ctx::gn_rows has to hold for a frame of that many 256-feature tiles
 int linearize_launch(mlh_ctx *ctx, const MatchArgs &a);
 int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a);
 bool loop_fit_fusable(const MatchArgs &loop_args);   // the loop launch described by these arguments would exchange tagged records (ctx.hpp: loop_tagged_arm's conditions)

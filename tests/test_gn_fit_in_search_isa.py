@@ -1,0 +1,48 @@
+"""The fused Gauss-Newton launches (match.hip: knn_features_wide_kernel<W, G, PRE, WARM, FIT = true>) fit a 1 024-thread workgroup's register file.
+
+A correspondence kernel of 78-82 VGPRs takes in the body of a fit kernel of 95; a 1 024-thread workgroup has 128 registers per lane (VGPR + AGPR), and a kernel
+that spills pays for it with scratch traffic on the launch chain. Checked where it shows: in the kernel descriptors of the gfx950 code object, compiled with the
+library's own flags (no GPU needed) -- for every fused instantiation `.amdhsa_private_segment_fixed_size` is 0 and `.amdhsa_next_free_vgpr` (the unified count:
+architectural VGPRs up to the accumulation offset, AGPRs behind it) is at most 128.
+
+The instantiations the host can launch (match.hip: match_launch, MLH_KNN_LAUNCH_GN_FUSED): 1 024 threads with 8, 16 or per-kind lanes, 512 threads with 8 lanes
+-- a workgroup has to hold whole wavefront rows, 64 queries or more, of every kind --, each as PRE 1 warm, PRE 1 cold and PRE 2.
+"""
+import importlib
+import os
+import re
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+# <W, G, PRE, WARM, FIT = true>
+FUSED = [(w, g, pre, warm) for (w, g) in ((1024, 0), (1024, 8), (1024, 16), (512, 8)) for (pre, warm) in ((1, True), (1, False), (2, False))]
+KERNEL = re.compile(r"\.amdhsa_kernel (\S+)(.*?)\.end_amdhsa_kernel", re.S)
+
+
+def _mangled(w, g, pre, warm):
+    return f"_ZN3mlh24knn_features_wide_kernelILi{w}ELi{g}ELi{pre}ELb{int(warm)}ELb1EEEvNS_7KParamsE"
+
+
+@pytest.fixture(scope="module")
+def descriptors(tmp_path_factory):
+    b = importlib.import_module("m-loam_amd.build")
+    out = tmp_path_factory.mktemp("isa") / "match.s"
+    flags = [f for f in b.FLAGS if f != "-fPIC"]
+    subprocess.run([b._hipcc()] + flags + ["--cuda-device-only", "-S", os.path.join(b.CSRC, "match.hip"), "-o", str(out)], check=True, cwd=ROOT)
+    return {m.group(1): dict(re.findall(r"\.amdhsa_(\w+) (\S+)", m.group(2))) for m in KERNEL.finditer(out.read_text())}
+
+
+def test_every_fused_instantiation_is_in_the_code_object(descriptors):
+    fused = sorted(k for k in descriptors if "knn_features_wide_kernel" in k and k.endswith("ELb1EEEvNS_7KParamsE"))
+    assert fused == sorted(_mangled(*f) for f in FUSED), fused
+
+
+@pytest.mark.parametrize("inst", FUSED, ids=lambda f: f"W{f[0]}-G{f[1]}-PRE{f[2]}-{'warm' if f[3] else 'cold'}")
+def test_no_scratch_and_at_most_128_registers(descriptors, inst):
+    d = descriptors[_mangled(*inst)]
+    print(inst, "next_free_vgpr", d["next_free_vgpr"], "accum_offset", d.get("accum_offset"), "scratch", d["private_segment_fixed_size"], "lds", d["group_segment_fixed_size"])
+    assert int(d["private_segment_fixed_size"]) == 0, d["private_segment_fixed_size"]
+    assert int(d["next_free_vgpr"]) <= 128, d["next_free_vgpr"]
