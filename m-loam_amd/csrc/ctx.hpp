@@ -15,6 +15,7 @@
 #include <sched.h>
 #include "../../include/mloam_hip.h"
 #include "records.hpp"
+#include "launch_modes.hpp"
 #include "sc_host.hpp"
 
 namespace mlh {
@@ -97,27 +98,7 @@ static_assert(offsetof(HostPublish, x) == 0 && offsetof(HostPublish, xb) == 56 &
               offsetof(HostPublish, H_final) == 520 && offsetof(HostPublish, cov) == 808 && sizeof(HostPublish) == 1096,
               "the publication record: pose, block poses, done word and sequence word where they have always been; the two matrices behind them");
 
-// ---------------------------------------------------------------- the solver's launch modes
-// Named once, here; the hosts (solve_host.hip, the launchers of match.hip / track.hip) and the kernels use the names, never the numbers. Unscoped, `int` underneath and
-// the values the fields have always had: the parameter blocks' layouts and the kernels' comparisons are what they were.
-enum LaunchTail : int {   // ::finish -- what the last workgroup of a fit / linearise launch does behind its tiles' records
-    TAIL_RECORDS = 0,     // nothing: the launch leaves the records (a consumer sums them)
-    TAIL_GN = 1,          // the Gauss-Newton finish: reduce + 6 x 6 solve + Plus
-    TAIL_REDUCE = 2,      // the local reduce into SolverState::ne only (an RCCL all-reduce and an update kernel follow)
-    TAIL_LM_BEGIN = 3,    // the Levenberg-Marquardt begin (match_launch; linearize_launch on the rows a selection kept; track_linearize_launch)
-    TAIL_LM_STEP = 4      // the Levenberg-Marquardt step (linearize_launch, track_linearize_launch)
-};
-// MatchArgs::lmc -- the consumer-side LM launches (lm_consume_launch): every workgroup sums the records its predecessor left, then runs the LM begin (BEGIN: behind a
-// match launch that left records) or step (STEP) and evaluates at the candidate -- or (LOOP) the whole loop of an outer iteration in this launch (lm_loop_kernel)
-enum LmConsumer : int { LMC_NONE = 0, LMC_BEGIN = 1, LMC_STEP = 2, LMC_LOOP = 3 };
-// ::lm_expect_done -- what an LM begin may assume about the previous outer iteration's loop: there is none, this is the first of a solve (clears lm_overflow and
-// lm_used_max); the host READ its verdict before it enqueued this launch; or it did not (UNREAD): if that loop has not terminated, SolverState::lm_overflow is raised
-// (the launches go on; the host discards the result). Ordered: >= LM_VERDICT_READ is "not the first".
-enum LmExpect : int { LM_FIRST_OF_SOLVE = -1, LM_VERDICT_READ = 0, LM_VERDICT_UNREAD = 1 };
-// KParams::pre_finish (the kernels' PRE template argument carries the same values as an int) -- the prologue of a correspondence launch completes the previous
-// Gauss-Newton ITERATION of its own solve from the records that iteration's fit launch left, or the predecessor SOLVE's last iteration: publishes that solve's pose
-// and chains this frame's start pose from it
-enum PreFinish : int { PRE_NONE = 0, PRE_ITERATION = 1, PRE_SOLVE = 2 };
+// ---------------------------------------------------------------- the solver's launch modes: launch_modes.hpp (LaunchTail, LmConsumer, LmExpect, PreFinish)
 enum : int { LM_OVERFLOW_BARRIER_GIVEN_UP = 4 };   // SolverState::lm_overflow: 0 / 1 = a loop outgrew its look-ahead; this value (the one-launch loops store it) = a barrier was given up on
 // HostPublish::done (reduce_dev.hpp: publish_pose): the LM loop has terminated (a Gauss-Newton solve: the pose is final) | the look-ahead of launches overflowed, a
 // loop had not ended where the host assumed it had | a one-launch loop gave a barrier up | the launch had no features
@@ -793,26 +774,31 @@ struct mlh_ctx {
     unsigned long long thin_seq = 0;
     mlh::PinnedBuf h_scratch;   // one ScratchBlock: the landing place of the few-int read-backs (record counts) that end a staging call
     int knn_lanes_override = 0;   // MLH_KNN_LANES=8|16|32, or SSCC (816, 832, 1632: surf lanes, corner lanes), in the environment at mlh_create: pins the correspondence kernel's lanes per query (tests, tuning)
-    int knn_wg_override = 0;      // MLH_KNN_WG_THREADS=256|512|1024, in the environment at mlh_create: pins the workgroup width of the correspondence launches that have wide forms (match.hip: knn_wg_threads_for; tests, A/B runs)
+    int knn_wg_override = 0;      // MLH_KNN_WG_THREADS=256|512|1024, in the environment at mlh_create: pins the workgroup width of the correspondence launches that have wide forms (match_plan_host.hpp: knn_plan_width; tests, A/B runs)
     int knn_wg_last = 0;          // the width the last such launch took
     int gn_final_defer = 1;       // mlh_set_gn_schedule: 0: a solve submitted with mlh_gn_solve_begin* finishes its LAST iteration in its own fit launch (classic); 1: that
                                   // iteration, too, only leaves its records -- the next mlh_gn_solve_begin_chained completes it in its first launch (and publishes the pose
                                   // from there), mlh_gn_solve_end or any other solver call completes it with a one-workgroup launch if no successor did
-    struct GnPending {            // the last iteration of the newest submitted solve is still a set of tile records
+    // An iteration's records: where a Gauss-Newton iteration that finished nothing left what the next launch's prologue sums (match.hip: prologue_reads).
+    struct GnRecords {
+        double *p = nullptr;      // device; null: the context's `partials` (the fit launch's tile records)
+        int rows = 1;             // per 256-feature tile: 1 record (fit_linearize_kernel's) or 4 wavefront rows (a fused launch's, in mlh_ctx::gn_rows)
+        int tiles = 0;            // 256-feature tiles
+    };
+    struct GnPending {            // the last iteration of the newest submitted solve is still a set of records
         bool active = false;
-        int tiles = 0, slot = 0, freeze = 0;
+        GnRecords recs;
+        int slot = 0, freeze = 0; // the SolverState::xi slot of the pose those records update
         double thre = 100.0;
         void *rec = nullptr;      // HostPublish of that solve
         unsigned long long seq = 0;
-        const double *recs = nullptr;   // where that iteration's records are (device; null: `partials`) and how they are laid out: 1 record or 4 wavefront rows per tile
-        int rows = 1;
     } gn_pending;
-    // The fit in the tail of the search launch (match.hip: knn_features_wide_kernel<.., FIT>, fit_in_search()).
+    // The fit in the tail of the search launch (match.hip: knn_features_wide_kernel<.., FIT>; match_plan_host.hpp: knn_fit_in_search).
     int gn_fit_in_search = -1;    // -1: the rule (chip-filling wide launches fuse); MLH_GN_FIT_IN_SEARCH=0|1 in the environment at mlh_create pins it: none / every launch that can (tests, A/B runs)
     int gn_fused_launches = 0;    // fused launches the last submitted Gauss-Newton solve enqueued
     mlh::DevBuf gn_rows;          // two sets of wavefront rows (4 x NE_STRIDE doubles per 256-feature tile), half the buffer each: a fused launch writes the set its
     int gn_rows_set = 0;          // prologue does not read (a fast workgroup stores its row while a slow one still sums); the set the last fused launch wrote
-    struct GnRecords { const double *p = nullptr; int rows = 1; } gn_last;   // where the newest iteration that left records left them, and in which layout
+    GnRecords gn_last;            // the newest iteration that left records
     int gn_slot_base = 0;         // xi slots of the next solve
     int gn_defer = 1;             // mlh_set_gn_schedule: 0: Gauss-Newton solves keep the classic finish (the fit kernel's last-arriving workgroup) in every iteration (A/B, tests)
     int knn_warm = 1;             // mlh_set_gn_schedule: 0: iterations >= 1 of a solve search without the previous iteration's neighbours as a bound (A/B, tests)

@@ -20,6 +20,7 @@
 // contiguous eighth of the (spatially coherent) feature list's map neighbourhood.
 #include "ctx.hpp"
 #include "solve_host.hpp"
+#include "match_plan_host.hpp"
 #include "dev_math.hpp"
 #include "solver_dev.hpp"
 #include "p2p_dev.hpp"
@@ -527,7 +528,7 @@ __global__ __launch_bounds__(TPB) void knn_features_kernel(KParams P)
 // The wide forms of the single-block, K = 5 launches of mlh_gn_solve* (PRE 1 warm and cold, PRE 2, PRE 0 warm): the same body, prologue and argument batch in
 // workgroups of 512 or 1024 threads. Kernels of their own: the 256-thread instantiations above keep their names and their code.
 // FIT: the launch also FITS -- it is a whole Gauss-Newton iteration whose fit launch would have been fit_linearize_kernel<5, false, false> leaving records (the host's
-//   fit_in_search(): single block, K = 5, one rank, no dense rows, a prologue in front, every kind at 64 queries or more per workgroup). Behind the search the
+//   knn_fit_in_search(): single block, K = 5, one rank, no dense rows, a prologue in front, every kind at 64 queries or more per workgroup). Behind the search the
 //   workgroup's queries ARE the features 64 w .. 64 w + 63 of one or two wavefront rows of a 256-feature tile (a wide tile starts at a multiple of 64): the lanes that
 //   stored a query's five winners left them in LDS as well, and the workgroup's first one or two wavefronts take one feature per lane -- feature f on lane f & 63 --
 //   through that kernel's body: fit_feature<5>, the Corr store, eval_factor at the pose in s_pose, the Huber scaling and the butterfly, up to the wavefront's row
@@ -1246,6 +1247,14 @@ __global__ __launch_bounds__(TPB) void knn_queries_kernel(GridDev grid, const fl
 }
 
 // ---------------------------------------------------------------- host launchers
+// How a launch comes about: fill_params turns MatchArgs and the context into the parameter block and -- for match_launch -- PLANS the correspondence launch, once:
+// it fills the planner's input record (plan_in_of + what the launch is) and asks knn_plan() of match_plan_host.hpp, a pure function, for the form (the kernel's
+// template arguments as data), the profiler id, whether the launch carries its fit and which fit launch follows, or for the refusal. Every rule about which kernel a
+// launch gets -- the width, the fit in the search's tail, the lanes collapse, the pose-block schedule, what device-side counts and no_fit allow -- is written there
+// and nowhere in this file. match_launch looks the form up in KNN_KERNELS, the one expansion of the list of forms that instantiates the correspondence kernels, and
+// launches it; the fit, linearise and consumer kernels are chosen by one expression each, lm_loop_kernel from one table (LM_LOOP_KERNELS). Where an iteration's
+// records lie is one descriptor (mlh_ctx::GnRecords: gn_last, gn_pending.recs, LaunchPlan::front), and prologue_reads the one place that points a launch at it.
+//
 // lanes per query, per kind. A small launch (a 16-ring frame) leaves most SIMDs idle and is bound by the latency of its trips: 16 lanes.
 // A full frame keeps ~5 wavefronts per SIMD busy and is bound by VALU issue, where the per-query instruction count is what matters:
 // 8 lanes (twice the queries per wavefront) for a kind whose map is sparse enough that a query's candidates fit one or two 8-lane trips,
@@ -1270,70 +1279,50 @@ void knn_lanes_for(const mlh_ctx *ctx, int kind_mask, int lanes[2])
     }
 }
 
-// Threads per workgroup of a correspondence launch. Only the single-block, K = 5 launches of mlh_gn_solve* have wide forms (knn_features_wide_kernel); every other
-// launch is 256 threads. Every workgroup of those launches runs the Gauss-Newton prologue, so what counts is workgroups per compute unit: a launch goes wide when
-// its 256-thread grid (tiles256) would put more than one workgroup on a compute unit of the solver's stream (caps.cu_solver: the device's, or the CU mask's), and
-// stays narrow otherwise -- wider workgroups would only leave compute units without work. KNN_WG_WIDE is the measured choice (profiles/r08_knn_workgroup_width.txt);
-// MLH_KNN_WG_THREADS in the environment at mlh_create pins the width of the launches that have wide forms (tests, A/B runs).
-constexpr int KNN_WG_WIDE = 1024;
-static int knn_wg_threads_for(const mlh_ctx *ctx, bool has_wide_form, int tiles256)
+// What the planner (match_plan_host.hpp) needs of the context, for a launch over these kinds; the caller adds what its launch is.
+static KnnPlanIn plan_in_of(const mlh_ctx *ctx, int kind_mask)
 {
-    if (!has_wide_form) return TPB;
-    if (ctx->knn_wg_override) return ctx->knn_wg_override;
-    return tiles256 > ctx->caps.cu_solver ? KNN_WG_WIDE : TPB;
+    KnnPlanIn in;
+    in.kind_mask = kind_mask;
+    knn_lanes_for(ctx, kind_mask, in.lanes);
+    for (int k = 0; k < 2; ++k) in.m[k] = ctx->feat[k].m;
+    in.cu_solver = ctx->caps.cu_solver;
+    in.wg_pin = ctx->knn_wg_override;
+    in.fit_pin = ctx->gn_fit_in_search;
+    in.sharded = ctx->shard_lo || ctx->shard_hi || ctx->own_mod > 1;
+    return in;
 }
 
-static int knn_tiles256(const mlh_ctx *ctx, int kind_mask, const int lanes[2])
+// gn_solve_submit's question about the solve it is about to plan: a predecessor left its last iteration as wavefront rows -- can this solve's first launch (iteration
+// 0 of a deferred solve that completes its predecessor: PRE 2, records only) read them? Asked of the planner itself, with what fill_params will give it.
+bool gn_first_launch_takes_rows(const mlh_ctx *ctx, int kind_mask)
 {
-    int tiles256 = 0;
-    for (int k = 0; k < 2; ++k) if ((kind_mask & (1 << k)) && ctx->feat[k].m > 0) tiles256 += (ctx->feat[k].m + TPB / lanes[k] - 1) / (TPB / lanes[k]);
-    return tiles256;
+    KnnPlanIn in = plan_in_of(ctx, kind_mask);
+    in.pre_finish = PRE_SOLVE;
+    in.rows_in = 4;
+    return knn_plan(in).err == MLH_OK;
 }
-
-// The width of a correspondence launch over these kinds, in ONE place: fill_params asks it for the launch it builds, gn_solve_submit (through gn_search_width) for the
-// launch it is about to plan -- the two cannot disagree on the rule, the lanes or the sharding. gn_shape: the launch is one of mlh_gn_solve*'s single-block, K = 5
-// launches with a prologue or a bounded search and host-side counts (the only ones that have wide forms).
-static int knn_width_of(const mlh_ctx *ctx, int kind_mask, bool gn_shape)
-{
-    int lanes[2];
-    knn_lanes_for(ctx, kind_mask, lanes);
-    const bool sharded = ctx->shard_lo || ctx->shard_hi || ctx->own_mod > 1;
-    return knn_wg_threads_for(ctx, gn_shape && !sharded, knn_tiles256(ctx, kind_mask, lanes));
-}
-int gn_search_width(const mlh_ctx *ctx, int kind_mask) { return knn_width_of(ctx, kind_mask, true); }
 
 // The two sets of wavefront rows of a frame with `tiles256` 256-feature tiles (mlh_ctx::gn_rows; a set begins at a multiple of 256 bytes in its half of the buffer).
 size_t gn_rows_bytes(int tiles256) { return 2 * sizeof(double) * NE_STRIDE * 4 * size_t(tiles256) + 512; }
 static double *gn_rows_set_ptr(const mlh_ctx *ctx, int set) { return reinterpret_cast<double *>(static_cast<char *>(ctx->gn_rows.p) + size_t(set) * ((ctx->gn_rows.cap / 2) & ~size_t(255))); }
 
-// One Gauss-Newton iteration as ONE launch -- the fit in the tail of its search (knn_features_wide_kernel<.., FIT>) -- or as two. Fused: a launch that goes wide
-// anyway, has a prologue in front (PRE 1 / PRE 2), whose fit launch would be fit_linearize_kernel<5, false, false> leaving records (single block, K = 5 and one rank
-// come with the wide form; no dense rows, no statistics, no publication from the fit), and whose every kind puts whole wavefront rows -- 64 queries or more -- into
-// a workgroup. Everything else keeps two launches.
-// Of the launches that can fuse, the rule fuses the chip-filling ones -- more than KNN_LATENCY_LIMIT queries, the throughput regime of knn_lanes_for, where the gain
-// was measured (profiles/r09_gn_fit_in_search.txt: one 1 024-thread workgroup per compute unit, half of them idle through the search's last 4 us). A smaller frame that
-// goes wide (the 16-ring frame of tests/test_gpu_launch_census.py: 5 451 features, 86 wide workgroups on 256 compute units) keeps its two launches: not measured, and
-// recorded that way. MLH_GN_FIT_IN_SEARCH=1 fuses every launch that can, =0 none (tests, A/B runs).
-static bool fit_in_search(const mlh_ctx *ctx, const MatchArgs &a, const KParams &P, int wg)
+// A launch with a prologue sums THESE records: the three fields that say where an iteration's records are, set together.
+static void prologue_reads(KParams &P, const mlh_ctx::GnRecords &recs, double *partials)
 {
-    if (ctx->gn_fit_in_search == 0 || wg == TPB || P.pre_finish == PRE_NONE) return false;
-    if (P.finish != TAIL_RECORDS || a.no_fit || a.dense || a.lmc != LMC_NONE || P.stat || P.own_mode || P.n_blocks != 1 || a.gn_blocks || P.m_dev) return false;
-    long long queries = 0;
-    for (int k = 0; k < 2; ++k) {
-        if (!(a.kind_mask & (1 << k))) continue;
-        if (P.k[k].lanes < 8 || wg / P.k[k].lanes < 64) return false;
-        queries += P.k[k].m;
-    }
-    return ctx->gn_fit_in_search > 0 || queries > KNN_LATENCY_LIMIT;
+    P.partials = recs.p ? recs.p : partials;
+    P.pre_rows = recs.rows;
+    P.pre_tiles = recs.tiles;
 }
 
-struct GnLaunchPlan {
-    bool fused = false;                // fit_in_search()
-    const double *rec_in = nullptr;    // the records the search launch's prologue sums when they are not in `partials`: a fused launch's rows
-    int rows_in = 1;
+struct LaunchPlan {
+    KnnPlan knn;
+    mlh_ctx::GnRecords front;          // the records the search launch's prologue sums: the previous iteration's (mlh_ctx::gn_last) or the previous solve's (gn_pending)
 };
 
-static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg = nullptr, GnLaunchPlan *plan = nullptr)
+// The parameter block of a launch described by `a` -- as its fit / linearise kernel reads it (`partials`: the records it writes). match_launch passes `plan`: the
+// correspondence launch in front is planned here, once; a launch that does not exist is refused at the end, behind the validation of the staged kinds.
+static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, LaunchPlan *plan = nullptr)
 {
     // a solve whose last iteration is still a set of tile records (mlh_ctx::gn_pending): any launch that writes records -- other than the chained successor's first,
     // which consumes them -- completes that solve first
@@ -1348,20 +1337,20 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg
         P.freeze_b[b] = a.freeze[b];
         kmax = std::max(kmax, P.kb[b]);
     }
-    int lanes[2];
-    knn_lanes_for(ctx, a.kind_mask, lanes);
-    {
-        const bool both = (a.kind_mask & 3) == 3;
-        P.knn_lanes = both ? (lanes[0] == lanes[1] ? lanes[0] : 0) : lanes[(a.kind_mask & 1) ? 0 : 1];
-        if (P.knn_lanes == 32) P.knn_lanes = 0;      // (32 lanes per query exist in the per-kind kernels only)
+    P.pre_finish = a.gn_iter >= 1 ? PRE_ITERATION : (a.gn_iter == 0 && a.pre_final) ? PRE_SOLVE : PRE_NONE;
+    P.stat = (a.stat_slot >= 0) ? ctx->stats.as<IterStatDev>() + a.stat_slot : nullptr;
+    KnnPlanIn in = plan_in_of(ctx, a.kind_mask);
+    in.mb = P.n_blocks > 1; in.k10 = kmax == 10; in.gn_blocks = a.gn_blocks; in.m_dev = a.m_dev != nullptr;
+    in.pre_finish = P.pre_finish; in.warm = a.warm; in.tail = a.finish;
+    in.no_fit = a.no_fit; in.dense = a.dense; in.lmc = a.lmc != LMC_NONE; in.stat = P.stat != nullptr;
+    if (plan) {
+        if (P.pre_finish == PRE_ITERATION) plan->front = ctx->gn_last;
+        if (P.pre_finish == PRE_SOLVE) plan->front = a.pre_final->recs;
+        in.rows_in = P.pre_finish ? plan->front.rows : 1;
+        plan->knn = knn_plan(in);
     }
-    int wg = TPB;
-    {
-        // (the launches match_launch sends through MLH_KNN_LAUNCH_GN, on one rank)
-        const bool prologue_or_warm = a.gn_iter >= 1 || a.pre_final || a.warm;
-        wg = knn_width_of(ctx, a.kind_mask, prologue_or_warm && P.n_blocks == 1 && kmax == 5 && !a.gn_blocks && !a.m_dev);
-    }
-    if (knn_wg) *knn_wg = wg;
+    const int wg = knn_plan_width(in);     // (tiles_a counts workgroups of this width)
+    P.knn_lanes = knn_plan_lanes(in);
     for (int k = 0; k < 2; ++k) {
         KindP &K = P.k[k];
         if (!(a.kind_mask & (1 << k))) continue;
@@ -1389,7 +1378,7 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg
         K.r_out = a.dense ? fs.r.as<double>() : nullptr;
         K.J_out = a.dense ? fs.J.as<double>() : nullptr;
         K.m = fs.m;
-        K.lanes = lanes[k];
+        K.lanes = in.lanes[k];
         K.tiles_a = (fs.m + wg / K.lanes - 1) / (wg / K.lanes);
         K.tiles_b = (fs.m + TPB - 1) / TPB;
         K.nbr_stride = fs.nbr_stride;
@@ -1425,8 +1414,6 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg
         // iteration i >= 1 of a deferred-finish solve over pose blocks: every block's pose of iteration i in SolverState::xib[i & 1][b]; iteration 1 updates the poses
         // the state holds (x, xb[b])
         SolverState *S = ctx->state.as<SolverState>();
-        P.pre_finish = PRE_ITERATION;
-        P.pre_tiles = tiles_b_total;
         P.pre_from_init = 0;
         P.pre_from_state = a.gn_iter == 1 ? 1 : 0;
         P.x_prev = &S->xib[(a.gn_iter - 1) & 1][0][0];
@@ -1438,28 +1425,24 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg
         // iteration 1 finds pose 0 where iteration 0 found it -- the kernel arguments, the state's x (a chained solve behind a chain launch), or iteration 0's slot
         // (a chained solve whose first launch computed the start pose itself, MatchArgs::pre_final)
         SolverState *S = ctx->state.as<SolverState>();
-        P.pre_finish = PRE_ITERATION;
-        P.pre_tiles = tiles_b_total;
         P.pre_from_init = (a.gn_iter == 1 && a.init_pose) ? 1 : 0;
         P.x_prev = (a.gn_iter == 1 && !a.pre_final) ? S->x : S->xi[a.gn_slot_base + ((a.gn_iter - 1) & 1)];
         P.x_next = S->xi[a.gn_slot_base + (a.gn_iter & 1)];
         P.pose0 = S->xi[a.gn_slot_base + (a.gn_iter & 1)];
         P.use_init = 0;
-    } else if (a.gn_iter == 0 && a.pre_final) {
+    } else if (P.pre_finish == PRE_SOLVE) {
         // iteration 0 of a chained solve that completes its predecessor first (knn_features_kernel<.., PRE = 2>): the predecessor's records, thresholds, last pose slot
         // and host record; this frame's start pose goes to xi[base] (the fit kernel of this iteration and iteration 1's prologue read it there)
         SolverState *S = ctx->state.as<SolverState>();
-        P.pre_finish = PRE_SOLVE;
-        P.pre_tiles = a.pre_final_tiles;
         P.pre_from_init = 0;
-        P.x_prev = S->xi[a.pre_final_slot];
+        P.x_prev = S->xi[a.pre_final->slot];
         P.x_next = S->xi[a.gn_slot_base];
         P.pose0 = S->xi[a.gn_slot_base];
         P.use_init = 0;
-        P.pre_publish = a.pre_final_publish;
-        P.pre_publish_seq = a.pre_final_seq;
-        P.pre_thre = a.pre_final_thre;
-        P.pre_freeze = a.pre_final_freeze;
+        P.pre_publish = static_cast<HostPublish *>(a.pre_final->rec);
+        P.pre_publish_seq = a.pre_final->seq;
+        P.pre_thre = a.pre_final->thre;
+        P.pre_freeze = a.pre_final->freeze;
         for (int i = 0; i < 7; ++i) { P.chain_prev[i] = a.chain_prev[i]; P.chain_cur[i] = a.chain_cur[i]; }
     }
     {   // where the launch's poses are, when they are not init_pose (load_pose)
@@ -1484,16 +1467,10 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, int *knn_wg
     }
     P.publish_seq = a.publish_seq;
     P.ticket = ctx->ticket.as<unsigned>();
-    P.stat = (a.stat_slot >= 0) ? ctx->stats.as<IterStatDev>() + a.stat_slot : nullptr;
     P.pre_rows = 1;
     if (plan) {
-        // the records this launch's prologue sums: the previous iteration's (mlh_ctx::gn_last) or the previous solve's (MatchArgs::pre_final_recs) -- tile records in
-        // `partials`, or a fused launch's wavefront rows
-        plan->rec_in = nullptr; plan->rows_in = 1;
-        if (P.pre_finish == PRE_ITERATION && !a.gn_blocks && ctx->gn_last.rows == 4) { plan->rec_in = ctx->gn_last.p; plan->rows_in = 4; }
-        if (P.pre_finish == PRE_SOLVE && a.pre_final_rows == 4) { plan->rec_in = a.pre_final_recs; plan->rows_in = 4; }
-        plan->fused = fit_in_search(ctx, a, P, wg);
-        if (plan->fused) {
+        if (plan->knn.err) return fail(ctx, plan->knn.err, plan->knn.why);
+        if (plan->knn.fused) {
             if ((e = ctx->gn_rows.ensure(gn_rows_bytes(tiles_b_total))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc wavefront rows", e);
             // (a set the prologue reads lies in this buffer; a reallocation would have been refused before the launch was planned: gn_solve_submit's `consume`)
             P.rows_out = gn_rows_set_ptr(ctx, ctx->gn_rows_set ^ 1);
@@ -1519,11 +1496,9 @@ int gn_flush_pending(mlh_ctx *ctx)
     KParams P;
     std::memset(&P, 0, sizeof(P));
     SolverState *S = ctx->state.as<SolverState>();
-    P.partials = ctx->gn_pending.rows == 4 ? const_cast<double *>(ctx->gn_pending.recs) : ctx->partials.as<double>();
-    P.pre_rows = ctx->gn_pending.rows;
+    prologue_reads(P, ctx->gn_pending.recs, ctx->partials.as<double>());
     P.state = S;
     P.pre_finish = PRE_SOLVE;
-    P.pre_tiles = ctx->gn_pending.tiles;
     P.x_prev = S->xi[ctx->gn_pending.slot];
     P.pre_publish = static_cast<HostPublish *>(ctx->gn_pending.rec);
     P.pre_publish_seq = ctx->gn_pending.seq;
@@ -1535,130 +1510,66 @@ int gn_flush_pending(mlh_ctx *ctx)
     return MLH_OK;
 }
 
+// The kernel of every form in the list (match_plan_host.hpp: MLH_KNN_FORMS), in the list's order: KNN_KERNELS[knn_form_index(form)]. This expansion is what
+// instantiates the correspondence kernels; nothing else names one.
+using KernelFn = void (*)(KParams);
+template <int W, int G, bool MB, bool K10, int PRE, bool WARM, bool DEVM, bool FIT>
+constexpr KernelFn knn_kernel_of()
+{
+    if constexpr (W == TPB) return knn_features_kernel<G, MB, K10, PRE, WARM, DEVM>;
+    else return knn_features_wide_kernel<W, G, PRE, WARM, FIT>;
+}
+#define MLH_KNN_KERNEL_ENTRY(W, G, MB, K10, PRE, WARM, DEVM, FIT) knn_kernel_of<W, G, bool(MB), bool(K10), PRE, bool(WARM), bool(DEVM), bool(FIT)>(),
+static const KernelFn KNN_KERNELS[KNN_FORM_COUNT] = {MLH_KNN_FORMS(MLH_KNN_KERNEL_ENTRY)};
+#undef MLH_KNN_KERNEL_ENTRY
+static_assert(KNN_WG_NARROW == TPB && KNN_FUSE_MIN_QUERIES == KNN_LATENCY_LIMIT, "the planner's two constants are the kernels'");
+
+static KernelFn fit_kernel_of(KnnFit fit)
+{
+    switch (fit) {
+    case KNN_FIT_DEVM: return fit_linearize_kernel<5, false, false, true>;
+    case KNN_FIT_LM_BEGIN: return fit_linearize_kernel<5, true>;
+    case KNN_FIT_K10_RECORDS: return fit_linearize_kernel<10, false, false>;
+    case KNN_FIT_K10: return fit_linearize_kernel<10, false>;
+    case KNN_FIT_RECORDS: return fit_linearize_kernel<5, false, false>;
+    case KNN_FIT_FINISH: return fit_linearize_kernel<5, false>;
+    default: return nullptr;
+    }
+}
+
 int match_launch(mlh_ctx *ctx, const MatchArgs &a)
 {
     KParams P;
-    int wg = TPB;
-    GnLaunchPlan plan;
-    int rc = fill_params(ctx, a, P, &wg, &plan);
+    LaunchPlan plan;
+    int rc = fill_params(ctx, a, P, &plan);
     if (rc) return rc;
-    // (the search launch's prologue reads the previous iteration's records where and how that iteration left them; the fit launch, if there is one, writes `partials`)
-    double *const partials = P.partials;
-    if (plan.rows_in == 4) {
-        if (wg == TPB) return fail(ctx, MLH_ERR_STATE, "wavefront rows in front of a launch without a wide kernel");
-        P.partials = const_cast<double *>(plan.rec_in);
-        P.pre_rows = 4;
-    }
-    // kernel A: correspondences (8 or 16 lanes per feature, wg threads per workgroup); kernel B: fit + linearise + reduce (one lane per feature)
+    const KnnPlan &kp = plan.knn;
+    const int form = knn_form_index(kp.form);
+    if (form < 0) return fail(ctx, MLH_ERR_STATE, "the planned correspondence kernel is not in the list of forms");      // (unreachable: tests/host/match_plan_main.cpp)
+    // kernel A: correspondences (8, 16 or 32 lanes per feature, form.W threads per workgroup); kernel B: fit + linearise + reduce (one lane per feature)
     const int grid_a = ((P.k[0].tiles_a + P.k[1].tiles_a + 7) / 8) * 8;
     const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
-    const bool mb = P.n_blocks > 1;
-    bool k10 = false;
-    for (int b = 0; b < P.n_blocks; ++b) k10 = k10 || P.kb[b] == 10;
-    if (wg != TPB && !((P.pre_finish || P.warm) && !mb && !k10 && !a.gn_blocks && !P.m_dev)) return fail(ctx, MLH_ERR_STATE, "a wide correspondence grid for a launch without a wide kernel");
-    if (P.m_dev) {
-        // the feature counts are on the device only (mlh_downsample_scan2map): per-kind lanes, both kinds, one block, K = 5, records only
-        if (mb || k10 || P.finish != TAIL_RECORDS || P.pre_finish || (a.kind_mask & 3) != 3) return fail(ctx, MLH_ERR_UNSUPPORTED, "device-side feature counts: one block, N_NEIGH 5, both kinds, records only");
-        if (P.warm) launch_timed(ctx, MLH_K_KNN, knn_features_kernel<0, false, false, 0, true, true>, grid_a, P);
-        else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<0, false, false, 0, false, true>, grid_a, P);
-        if (!a.no_fit) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, false, false, true>, grid_b, P);
-        MLH_HIP(ctx, hipGetLastError());
-        for (int k = 0; k < 2; ++k) ctx->feat[k].matched = !a.no_fit;       // (no_fit: the loop launch behind this one writes the correspondences)
-        return MLH_OK;
-    }
-    {
-        // <lanes, pose blocks, any block with K = 10>
-#define MLH_KNN_LAUNCH(G_) do { \
-            if (mb) { if (k10) launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, true, true>, grid_a, P); else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, true, false>, grid_a, P); } \
-            else { if (k10) launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, false, true>, grid_a, P); else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, false, false>, grid_a, P); } \
-        } while (0)
-#define MLH_KNN_LAUNCH_GN(G_) do { \
-            if (P.pre_finish == PRE_SOLVE) launch_timed(ctx, MLH_K_KNN_FIRST, knn_features_kernel<G_, false, false, 2, false>, grid_a, P); \
-            else if (P.pre_finish && P.warm) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, false, false, 1, true>, grid_a, P); \
-            else if (P.pre_finish) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, false, false, 1, false>, grid_a, P); \
-            else launch_timed(ctx, MLH_K_KNN, knn_features_kernel<G_, false, false, 0, true>, grid_a, P); \
-        } while (0)
-#define MLH_KNN_LAUNCH_GN_WIDE(W_, G_) do { \
-            if (P.pre_finish == PRE_SOLVE) launch_timed(ctx, MLH_K_KNN_FIRST, knn_features_wide_kernel<W_, G_, 2, false>, grid_a, P, W_); \
-            else if (P.pre_finish && P.warm) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, true>, grid_a, P, W_); \
-            else if (P.pre_finish) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, false>, grid_a, P, W_); \
-            else launch_timed(ctx, MLH_K_KNN, knn_features_wide_kernel<W_, G_, 0, true>, grid_a, P, W_); \
-        } while (0)
-#define MLH_KNN_LAUNCH_GN_W(G_) do { \
-            if (wg == 1024) MLH_KNN_LAUNCH_GN_WIDE(1024, G_); \
-            else if (wg == 512) MLH_KNN_LAUNCH_GN_WIDE(512, G_); \
-            else MLH_KNN_LAUNCH_GN(G_); \
-        } while (0)
-#define MLH_KNN_LAUNCH_GN_MB(G_) do { \
-            if (k10) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, true, true, 1, true>, grid_a, P); \
-            else launch_timed(ctx, MLH_K_KNN_PRE, knn_features_kernel<G_, true, false, 1, true>, grid_a, P); \
-        } while (0)
-        if ((P.pre_finish || P.warm) && (mb || k10 || a.gn_blocks)) {     // (a.gn_blocks: a blocks solve over ONE block keeps the blocks' pose slots)
-            // a solve over pose blocks (or with N_NEIGH = 10): the finish in the consumer and the bounded search come together or not at all
-            if (!(P.pre_finish == PRE_ITERATION && P.warm)) return fail(ctx, MLH_ERR_UNSUPPORTED, "pose blocks: the deferred finish and the bounded search are one schedule");
-            if (P.knn_lanes == 0) MLH_KNN_LAUNCH_GN_MB(0);
-            else if (P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_MB(16);
-            else MLH_KNN_LAUNCH_GN_MB(8);
+    // (the search launch's prologue reads the previous iteration's records where and how that iteration left them; the fit launch, if there is one, writes `partials`)
+    KParams S = P;
+    if (P.pre_finish) prologue_reads(S, plan.front, P.partials);
+    launch_timed(ctx, kp.kid, KNN_KERNELS[form], grid_a, S, kp.form.W);
+    if (kp.gn_shape) ctx->knn_wg_last = kp.form.W;
+    if (kp.fit != KNN_FIT_NONE) launch_timed(ctx, MLH_K_FIT, fit_kernel_of(kp.fit), grid_b, P);
+    if (!P.m_dev) {
+        // what this iteration leaves for the next launch's prologue: its fit launch's tile records, or (fused) the set of wavefront rows it wrote
+        ctx->gn_last = mlh_ctx::GnRecords{nullptr, 1, P.k[0].tiles_b + P.k[1].tiles_b};
+        if (kp.fused) {
+            ctx->gn_rows_set ^= 1;
+            ctx->gn_last.p = P.rows_out; ctx->gn_last.rows = 4;
+            ++ctx->gn_fused_launches;
         }
-        else if (plan.fused) {
-            // the whole iteration in this launch (fit_in_search()): the search's profiler id, no MLH_K_FIT launch
-#define MLH_KNN_LAUNCH_GN_FUSED(W_, G_) do { \
-            if (P.pre_finish == PRE_SOLVE) launch_timed(ctx, MLH_K_KNN_FIRST, knn_features_wide_kernel<W_, G_, 2, false, true>, grid_a, P, W_); \
-            else if (P.warm) launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, true, true>, grid_a, P, W_); \
-            else launch_timed(ctx, MLH_K_KNN_PRE, knn_features_wide_kernel<W_, G_, 1, false, true>, grid_a, P, W_); \
-        } while (0)
-            if (wg == 1024 && P.knn_lanes == 0) MLH_KNN_LAUNCH_GN_FUSED(1024, 0);
-            else if (wg == 1024 && P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_FUSED(1024, 16);
-            else if (wg == 1024 && P.knn_lanes == 8) MLH_KNN_LAUNCH_GN_FUSED(1024, 8);
-            else if (wg == 512 && P.knn_lanes == 8) MLH_KNN_LAUNCH_GN_FUSED(512, 8);
-            else return fail(ctx, MLH_ERR_STATE, "a fused Gauss-Newton launch without a fused kernel");
-#undef MLH_KNN_LAUNCH_GN_FUSED
-            ctx->knn_wg_last = wg;
-        }
-        else if (P.pre_finish || P.warm) {
-            if (P.knn_lanes == 0) MLH_KNN_LAUNCH_GN_W(0);
-            else if (P.knn_lanes == 16) MLH_KNN_LAUNCH_GN_W(16);
-            else MLH_KNN_LAUNCH_GN_W(8);
-            ctx->knn_wg_last = wg;
-        }
-        else if (P.knn_lanes == 0) MLH_KNN_LAUNCH(0);
-        else if (P.knn_lanes == 16) MLH_KNN_LAUNCH(16);
-        else MLH_KNN_LAUNCH(8);
-#undef MLH_KNN_LAUNCH_GN_W
-#undef MLH_KNN_LAUNCH_GN_WIDE
-#undef MLH_KNN_LAUNCH_GN
-#undef MLH_KNN_LAUNCH_GN_MB
-#undef MLH_KNN_LAUNCH
     }
-    P.partials = partials;
-    P.pre_rows = 1;
-    ctx->gn_last.p = nullptr; ctx->gn_last.rows = 1;
-    if (plan.fused) {
-        ctx->gn_rows_set ^= 1;
-        ctx->gn_last.p = P.rows_out; ctx->gn_last.rows = 4;
-        ++ctx->gn_fused_launches;
-        MLH_HIP(ctx, hipGetLastError());
-        for (int k = 0; k < 2; ++k) if (a.kind_mask & (1 << k)) ctx->feat[k].matched = true;
-        return MLH_OK;
-    }
-    if (a.no_fit) {
-        // the fit rides in the loop launch behind this one (lm_consume_launch, fit_in_loop): single block, N_NEIGH 5, both kinds, records only
-        if (k10 || P.n_blocks != 1 || P.finish != TAIL_RECORDS || (a.kind_mask & 3) != 3 || a.dense) return fail(ctx, MLH_ERR_UNSUPPORTED, "match_launch without its fit: single block, N_NEIGH 5, both kinds, records only");
-        MLH_HIP(ctx, hipGetLastError());
-        for (int k = 0; k < 2; ++k) ctx->feat[k].matched = false;
-        return MLH_OK;
-    }
-    if (P.finish == TAIL_LM_BEGIN) {
-        if (k10 || P.n_blocks != 1) return fail(ctx, MLH_ERR_UNSUPPORTED, "the fused Levenberg-Marquardt begin is single-block, N_NEIGH = 5");
-        launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, true>, grid_b, P);
-    } else if (k10 && P.finish == TAIL_RECORDS) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<10, false, false>, grid_b, P);
-    else if (k10) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<10, false>, grid_b, P);
-    else if (P.finish == TAIL_RECORDS) launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, false, false>, grid_b, P);
-    else launch_timed(ctx, MLH_K_FIT, fit_linearize_kernel<5, false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
-    for (int k = 0; k < 2; ++k) if (a.kind_mask & (1 << k)) ctx->feat[k].matched = true;
+    // (no_fit: the loop launch behind this one writes the correspondences; both kinds, as the planner saw to)
+    for (int k = 0; k < 2; ++k) if (a.kind_mask & (1 << k)) ctx->feat[k].matched = !a.no_fit;
     return MLH_OK;
 }
+
 
 static bool pose_cov_launch(const KParams &P) { return (P.flags & MLH_FLAG_POSE_COV) != 0 && P.publish != nullptr; }
 
@@ -1672,12 +1583,14 @@ int linearize_launch(mlh_ctx *ctx, const MatchArgs &a)
     const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
     // (the covariance of MLH_FLAG_POSE_COV rides in a publication: launches that publish nothing are the default kernels)
     const bool lm = P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP;
-    if (lm && pose_cov_launch(P)) launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<true, true>, grid_b, P);
-    else if (lm) launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<true>, grid_b, P);
-    else launch_timed(ctx, MLH_K_LINEARIZE, linearize_kernel<false>, grid_b, P);
+    launch_timed(ctx, MLH_K_LINEARIZE, lm && pose_cov_launch(P) ? linearize_kernel<true, true> : lm ? linearize_kernel<true> : linearize_kernel<false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
 }
+
+// lm_loop_kernel<DEVM, FIT, COV>, every instantiation: [FIT][COV][DEVM] (lm_consume_launch launches one, lm_loop_occupancy asks the device about all of them)
+static const KernelFn LM_LOOP_KERNELS[2][2][2] = {{{lm_loop_kernel<false, false, false>, lm_loop_kernel<true, false, false>}, {lm_loop_kernel<false, false, true>, lm_loop_kernel<true, false, true>}},
+                                                  {{lm_loop_kernel<false, true, false>, lm_loop_kernel<true, true, false>}, {lm_loop_kernel<false, true, true>, lm_loop_kernel<true, true, true>}}};
 
 int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a)
 {
@@ -1699,23 +1612,13 @@ int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a)
         if (a.lm_expect_done == LM_FIRST_OF_SOLVE) ++ctx->caps.loop_launches;      // (the first loop of a frame)
         // the iterations' records as tagged words summed by polling (MLH_LOOP_TAGGED=0: plain records behind a grid barrier, as through round 5)
         { hipError_t e = loop_tagged_arm(ctx, size_t(P.k[0].tiles_b + P.k[1].tiles_b), a.lm_max_it, &P.loop_tagged, &P.loop_tag_base); if (e != hipSuccess) return fail(ctx, MLH_ERR_HIP, "tagged records", e); }
-        if (a.fit_in_loop) {
-            if (!P.loop_tagged) return fail(ctx, MLH_ERR_INVALID, "the fit rides in the one-launch loop with tagged records only");
-            if (cov && P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true, true, true>, grid_b, P);
-            else if (cov) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false, true, true>, grid_b, P);
-            else if (P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true, true>, grid_b, P);
-            else launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false, true>, grid_b, P);
-            for (int k = 0; k < 2; ++k) ctx->feat[k].matched = true;
-        }
-        else if (cov && P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true, false, true>, grid_b, P);
-        else if (cov) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false, false, true>, grid_b, P);
-        else if (P.m_dev) launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<true>, grid_b, P);
-        else launch_timed(ctx, MLH_K_LINEARIZE, lm_loop_kernel<false>, grid_b, P);
+        if (a.fit_in_loop && !P.loop_tagged) return fail(ctx, MLH_ERR_INVALID, "the fit rides in the one-launch loop with tagged records only");
+        launch_timed(ctx, MLH_K_LINEARIZE, LM_LOOP_KERNELS[a.fit_in_loop][cov][P.m_dev != nullptr], grid_b, P);
+        if (a.fit_in_loop) for (int k = 0; k < 2; ++k) ctx->feat[k].matched = true;
+    } else {
+        const bool begin = a.lmc == LMC_BEGIN, cov = pose_cov_launch(P);
+        launch_timed(ctx, MLH_K_LINEARIZE, begin ? (cov ? lm_consume_kernel<true, true> : lm_consume_kernel<true>) : (cov ? lm_consume_kernel<false, true> : lm_consume_kernel<false>), grid_b, P);
     }
-    else if (a.lmc == LMC_BEGIN && pose_cov_launch(P)) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<true, true>, grid_b, P);
-    else if (a.lmc == LMC_BEGIN) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<true>, grid_b, P);
-    else if (pose_cov_launch(P)) launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<false, true>, grid_b, P);
-    else launch_timed(ctx, MLH_K_LINEARIZE, lm_consume_kernel<false>, grid_b, P);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
 }
@@ -1727,19 +1630,15 @@ bool loop_fit_fusable(const MatchArgs &loop_args)
 
 int lm_loop_occupancy(int blocks_per_cu[2], int blocks_per_cu_cov[2])
 {
-    // (the forms with and without the fit in front: the smaller number gates both)
-    int with_fit[2] = {0, 0};
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu[0], lm_loop_kernel<false>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu[1], lm_loop_kernel<true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[0], lm_loop_kernel<false, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[1], lm_loop_kernel<true, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    for (int i = 0; i < 2; ++i) blocks_per_cu[i] = std::min(blocks_per_cu[i], with_fit[i]);
-    // the instantiations that publish the covariance (MLH_FLAG_POSE_COV): gated by their own numbers
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu_cov[0], lm_loop_kernel<false, false, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&blocks_per_cu_cov[1], lm_loop_kernel<true, false, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[0], lm_loop_kernel<false, true, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&with_fit[1], lm_loop_kernel<true, true, true>, TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-    for (int i = 0; i < 2; ++i) blocks_per_cu_cov[i] = std::min(blocks_per_cu_cov[i], with_fit[i]);
+    // per COV (the instantiations that publish the covariance, MLH_FLAG_POSE_COV, are gated by their own numbers) and DEVM: the forms with and without the fit in
+    // front -- the smaller number gates both
+    for (int cov = 0; cov < 2; ++cov)
+        for (int devm = 0; devm < 2; ++devm) {
+            int n[2] = {0, 0};
+            for (int fit = 0; fit < 2; ++fit)
+                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[fit], LM_LOOP_KERNELS[fit][cov][devm], TPB, 0) != hipSuccess) return MLH_ERR_HIP;
+            (cov ? blocks_per_cu_cov : blocks_per_cu)[devm] = std::min(n[0], n[1]);
+        }
     return MLH_OK;
 }
 
@@ -1766,5 +1665,5 @@ int knn_launch(mlh_ctx *ctx, int kind, const float *q_host, int nq, int32_t *idx
 
 // For the tests of the width rule (not part of the C-ABI header): threads per workgroup of the context's last correspondence launch that has wide forms, 0 before any
 extern "C" int mlh_debug_knn_wg_threads(mlh_ctx *ctx) { return ctx ? ctx->knn_wg_last : 0; }
-// ... and of the fused iterations: how many launches of the last submitted Gauss-Newton solve carried their fit (fit_in_search())
+// ... and of the fused iterations: how many launches of the last submitted Gauss-Newton solve carried their fit (knn_fit_in_search())
 extern "C" int mlh_debug_gn_fused_launches(mlh_ctx *ctx) { return ctx ? ctx->gn_fused_launches : 0; }

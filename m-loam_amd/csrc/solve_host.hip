@@ -624,11 +624,11 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     const bool defer = n_iters >= 2 && gn_defer_applies(ctx, mask);
     // The previous solve may have left its LAST iteration as tile records (gn_pending). A chained, deferred solve completes it in its own first launch -- unless this
     // frame needs a larger record buffer (the records would not survive the reallocation); everything else completes it now, before the chain launch reads the pose.
-    // A predecessor that left wavefront rows (a fused last iteration) needs a successor whose first launch reads rows -- a wide one -- and whose own rows fit the buffer
-    // the pending set lies in.
-    const bool rows_ok = ctx->gn_pending.rows != 4 || (gn_search_width(ctx, mask) != 256 && gn_rows_bytes(feature_tiles(ctx, mask)) <= ctx->gn_rows.cap);
+    // A predecessor that left wavefront rows (a fused last iteration) needs a successor whose first launch reads rows (the planner says) and whose own rows fit the
+    // buffer the pending set lies in.
+    const bool rows_ok = ctx->gn_pending.recs.rows != 4 || (gn_first_launch_takes_rows(ctx, mask) && gn_rows_bytes(feature_tiles(ctx, mask)) <= ctx->gn_rows.cap);
     const bool consume = !pose_in && defer && ctx->gn_pending.active && sizeof(double) * NE_STRIDE * size_t(feature_tiles(ctx, mask)) <= ctx->partials.cap && rows_ok;
-    mlh_ctx::GnPending pend = ctx->gn_pending;
+    const mlh_ctx::GnPending pend = ctx->gn_pending;
     ctx->gn_fused_launches = 0;
     if (ctx->gn_pending.active && !consume && (rc = gn_flush_pending(ctx))) return rc;
     if (!pose_in && !consume && (rc = enqueue_chain_pose(ctx, wodom_prev, wodom_cur, nullptr))) return rc;
@@ -641,13 +641,8 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
         MatchArgs a = gn_iter_args(ctx, opts, mask, it, n_iters, pose_in, defer, leave_final);
         if (defer) a.gn_slot_base = base;
         if (consume) {
-            a.pre_final = true;                // iteration 0: complete the predecessor, publish its pose, chain; iterations >= 1: pose 0 sits in its slot
-            if (it == 0) {
-                a.pre_final_tiles = pend.tiles; a.pre_final_slot = pend.slot; a.pre_final_thre = pend.thre; a.pre_final_freeze = pend.freeze;
-                a.pre_final_publish = static_cast<HostPublish *>(pend.rec); a.pre_final_seq = pend.seq;
-                a.pre_final_recs = pend.recs; a.pre_final_rows = pend.rows;
-                a.chain_prev = wodom_prev; a.chain_cur = wodom_cur;
-            }
+            a.pre_final = &pend;               // iteration 0: complete the predecessor, publish its pose, chain; iterations >= 1: pose 0 sits in its slot
+            if (it == 0) { a.chain_prev = wodom_prev; a.chain_cur = wodom_cur; }
         }
         if (it == n_iters - 1 && !leave_final) {
             a.publish = rec;
@@ -658,14 +653,12 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     }
     if (leave_final) {
         ctx->gn_pending.active = true;
-        ctx->gn_pending.tiles = ctx->n_partial_tiles;
+        ctx->gn_pending.recs = ctx->gn_last;         // (tile records in `partials`, or a fused last iteration's set of wavefront rows)
         ctx->gn_pending.slot = base + ((n_iters - 1) & 1);
         ctx->gn_pending.thre = opts->map_eig_thre;
         ctx->gn_pending.freeze = 0;
         ctx->gn_pending.rec = rec;
         ctx->gn_pending.seq = seq;
-        ctx->gn_pending.recs = ctx->gn_last.p;       // (a fused last iteration: its set of wavefront rows)
-        ctx->gn_pending.rows = ctx->gn_last.rows;
     }
     ctx->solves.commit(seq, ctx->map_set_cur);
     return MLH_OK;

@@ -33,13 +33,10 @@ struct MatchArgs {
     // iteration 0 of a CHAINED solve that also completes the PREVIOUS solve, whose last iteration left only its tiles' records (mlh_ctx::gn_pending): every workgroup of
     // this correspondence launch sums them, solves, applies Plus -> the previous frame's final pose; tile 0's workgroup publishes it to that solve's host record and
     // stores it as the state's pose; then the chained start pose of THIS frame (transformUpdate + transformAssociateToMap) is computed from it, in every workgroup
-    bool pre_final = false;
-    int pre_final_tiles = 0, pre_final_slot = 0, pre_final_freeze = 0;
-    double pre_final_thre = 100.0;
-    HostPublish *pre_final_publish = nullptr;
-    unsigned long long pre_final_seq = 0;
-    const double *pre_final_recs = nullptr;  // device: the predecessor's records (null: the context's `partials`), one record or four wavefront rows per tile
-    int pre_final_rows = 1;
+    // pre_final: that solve's pending record, as gn_solve_submit copied it before the solve's own launches overwrite mlh_ctx::gn_pending -- where its records are, its
+    // last pose slot, threshold, host record and sequence number. Set for EVERY iteration of the completing solve (iterations >= 1 find pose 0 in its slot, not in
+    // the state); read by iteration 0.
+    const mlh_ctx::GnPending *pre_final = nullptr;
     const double *chain_prev = nullptr, *chain_cur = nullptr;   // host: the two odometry poses of the chain (7 doubles each)
     LmConsumer lmc = LMC_NONE;
     int lmc_j = 0;       // lm_consume_launch: the launch's number within its loop (1, 2, ...: record buffer (j - 1) & 1 is read, j & 1 written)
@@ -52,7 +49,7 @@ struct MatchArgs {
     unsigned long long publish_seq = 0;
 };
 int match_launch(mlh_ctx *ctx, const MatchArgs &a);
-int gn_search_width(const mlh_ctx *ctx, int kind_mask);      // threads per workgroup a single-block, K = 5 Gauss-Newton correspondence launch over these kinds takes on one rank
+bool gn_first_launch_takes_rows(const mlh_ctx *ctx, int kind_mask);   // the planner's answer: iteration 0 of a deferred solve over these kinds that completes its predecessor can read that solve's wavefront rows
 size_t gn_rows_bytes(int tiles256);                            // what mlh_ctx::gn_rows has to hold for a frame of that many 256-feature tiles
 int linearize_launch(mlh_ctx *ctx, const MatchArgs &a);
 int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a);

@@ -5,8 +5,11 @@ that spills pays for it with scratch traffic on the launch chain. Checked where 
 library's own flags (no GPU needed) -- for every fused instantiation `.amdhsa_private_segment_fixed_size` is 0 and `.amdhsa_next_free_vgpr` (the unified count:
 architectural VGPRs up to the accumulation offset, AGPRs behind it) is at most 128.
 
-The instantiations the host can launch (match.hip: match_launch, MLH_KNN_LAUNCH_GN_FUSED): 1 024 threads with 8, 16 or per-kind lanes, 512 threads with 8 lanes
+The instantiations the host can launch (match_plan_host.hpp: the fused entries of MLH_KNN_FORMS): 1 024 threads with 8, 16 or per-kind lanes, 512 threads with 8 lanes
 -- a workgroup has to hold whole wavefront rows, 64 queries or more, of every kind --, each as PRE 1 warm, PRE 1 cold and PRE 2.
+
+And the code object holds the correspondence kernels of the planner's list of forms (match_plan_host.hpp: MLH_KNN_FORMS), all of them and no other: the list is
+printed by the planner's stand-alone program (tests/host/match_plan_main.cpp, `forms`).
 """
 import importlib
 import os
@@ -46,3 +49,21 @@ def test_no_scratch_and_at_most_128_registers(descriptors, inst):
     print(inst, "next_free_vgpr", d["next_free_vgpr"], "accum_offset", d.get("accum_offset"), "scratch", d["private_segment_fixed_size"], "lds", d["group_segment_fixed_size"])
     assert int(d["private_segment_fixed_size"]) == 0, d["private_segment_fixed_size"]
     assert int(d["next_free_vgpr"]) <= 128, d["next_free_vgpr"]
+
+
+def test_the_correspondence_kernels_are_the_planners_list_of_forms(descriptors, tmp_path):
+    exe = tmp_path / "match_plan_main"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "m-loam_amd", "csrc"), os.path.join(ROOT, "tests", "host", "match_plan_main.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe), "forms"], check=True, capture_output=True, text=True, timeout=60).stdout
+    listed = set()
+    for line in out.splitlines():
+        w, g, mb, k10, pre, warm, devm, fit = (int(v) for v in line.split())
+        if w == 256:
+            assert not fit, line
+            listed.add(f"_ZN3mlh19knn_features_kernelILi{g}ELb{mb}ELb{k10}ELi{pre}ELb{warm}ELb{devm}EEEvNS_7KParamsE")
+        else:
+            assert not (mb or k10 or devm), line
+            listed.add(f"_ZN3mlh24knn_features_wide_kernelILi{w}ELi{g}ELi{pre}ELb{warm}ELb{fit}EEEvNS_7KParamsE")
+    built = {k for k in descriptors if "knn_features_kernel" in k or "knn_features_wide_kernel" in k}
+    assert len(listed) == len(out.splitlines()) == 68, len(listed)
+    assert built - listed == set() and listed - built == set(), (sorted(built - listed), sorted(listed - built))
