@@ -259,6 +259,8 @@ int mlh_voxel_filter(mlh_ctx *ctx, const void *points, int stride_bytes, int n, 
  * mlh_pure_odom_set stages the factor table once per optimisation: type[i] 0 = plane ('s'), 1 = edge ('c'); points n x 3;
  * coeffs n x 6 (plane: [n, d, -, -], edge: the two line points); sqrt_info may be NULL (= 1.0, as the reference constructs them);
  * frame_idx / ext_idx select rows of the pose arrays given to mlh_pure_odom_evaluate.
+ * Types and block indices are checked before the context or the device is touched: a type that is neither 0 nor 1, a negative index or one beyond 19 (a window
+ * has at most 22 parameter blocks: the pivot, at most 20 frames, at most 20 extrinsics) is MLH_ERR_INVALID, and a rejected call leaves the staged table as it was.
  * mlh_pure_odom_evaluate: residuals n; jacobians n x 21 row-major [pivot 1x7 | frame 1x7 | extrinsic 1x7] or NULL. The columns
  * are the reference's expressions term by term (two of them are not exact derivatives; see m-loam_amd/csrc/odom.hip). */
 int mlh_pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const double *points, const double *coeffs, const double *sqrt_info,
@@ -296,6 +298,7 @@ int mlh_pure_odom_add_matches_gf(mlh_ctx *ctx, int kind, const double rel_pose[7
  * JtJ D x D row-major (symmetric, both triangles filled), Jtr D, cost = sum rho(r^2)/2, n_residuals. evalDegenracy (estimator.cpp:1598-1680)
  * reads its diagonal 6x6 blocks (mlh_eval_degeneracy on each); with several GPUs (factors split over the ranks) the record is summed with
  * mlh_allreduce_f64 -- D (D + 1) / 2 + D + 2 = 326 doubles for the 24-dimensional hercules window. Deterministic (no atomics).
+ * At most 22 parameter blocks (D = 132: the assembly is LDS-resident); more is MLH_ERR_UNSUPPORTED here and in mlh_pure_odom_gn_solve.
  * An installed window prior (mlh_window_prior_set / mlh_window_marginalize) or extrinsic prior is NOT added here: evalResidual evaluates res_ids_proj only
  * (estimator.cpp:1588-1593), and evalDegenracy must keep seeing the feature factors alone.
  * With a calibration store in use (f10 below: mlh_calib_use) its LidarOnlineCalib factors ARE added -- the reference pushes them to res_ids_proj (cpp:733, 778), so

@@ -169,6 +169,7 @@ __global__ __launch_bounds__(256) void pure_odom_kernel(OdomArgs A)
 // fixed order. No atomics anywhere.
 constexpr int NE_ROW = 22;        // LDS doubles per factor: v[18], r, cost, count, pad
 constexpr int NE_OUT = 192;       // 171 + 18 + 2, padded
+constexpr int ODOM_MAX_BLOCKS = 22;   // pivot + frames + extrinsics of the largest window: D = 132, the LDS-resident assembly and the solve's Cholesky are sized for it
 struct OdomNeArgs {
     OdomArgs A;
     const int *perm;        // tiles * 256 factor indices grouped by (frame, ext); -1 = padding
@@ -264,6 +265,13 @@ extern "C" int mlh_pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const
     if (!ctx) return MLH_ERR_INVALID;
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     if (n <= 0 || !type || !points || !coeffs || !frame_idx || !ext_idx) return fail(ctx, MLH_ERR_INVALID, "bad arguments");
+    // types and block indices are checked before anything in the context or on the device is touched: a rejected call leaves the staged table as it was.
+    // A window has at most ODOM_MAX_BLOCKS blocks, one of them the pivot and at least one of each other kind: no index beyond ODOM_MAX_BLOCKS - 3 can be covered
+    for (int i = 0; i < n; ++i) {
+        if (type[i] != 0 && type[i] != 1) return fail(ctx, MLH_ERR_INVALID, "factor type must be 0 (plane) or 1 (edge)");
+        if (frame_idx[i] < 0 || ext_idx[i] < 0) return fail(ctx, MLH_ERR_INVALID, "negative block index");
+        if (frame_idx[i] > ODOM_MAX_BLOCKS - 3 || ext_idx[i] > ODOM_MAX_BLOCKS - 3) return fail(ctx, MLH_ERR_INVALID, "block index beyond the largest window (22 parameter blocks)");
+    }
     OdomSet &O = ctx->odom;
     std::vector<double> tab(size_t(n) * 10);
     std::vector<int> idx(size_t(n) * 3);
@@ -279,7 +287,7 @@ extern "C" int mlh_pure_odom_set(mlh_ctx *ctx, int n, const int32_t *type, const
     MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     O.n = n;
     int mf = 0, me = 0;
-    for (int i = 0; i < n; ++i) { mf = std::max(mf, frame_idx[i]); me = std::max(me, ext_idx[i]); if (frame_idx[i] < 0 || ext_idx[i] < 0) return fail(ctx, MLH_ERR_INVALID, "negative block index"); }
+    for (int i = 0; i < n; ++i) { mf = std::max(mf, frame_idx[i]); me = std::max(me, ext_idx[i]); }
     O.max_frame = mf; O.max_ext = me;
     // factors grouped by (frame, extrinsic) for the normal-equation kernel (tile_group.hpp); the group key uses the staged maxima,
     // mlh_pure_odom_normal_eq re-derives (f, e) from it
@@ -406,7 +414,9 @@ static int odom_ne_prepare(mlh_ctx *ctx, const double pivot[7], const double *fr
         return fail(ctx, MLH_ERR_INVALID, "pose arrays do not cover the block indices of the staged factors");
     const int D = 6 * (1 + n_frames + n_ext);
     n_out = size_t(D) * D + D + 2;
-    if (n_out * sizeof(double) > 150 * 1024) return fail(ctx, MLH_ERR_UNSUPPORTED, "window too large for the LDS-resident assembly (6 (1 + frames + extrinsics) <= 136)");
+    // (the byte bound alone let 23 blocks, D = 138, through: 153 472 B)
+    if (1 + n_frames + n_ext > ODOM_MAX_BLOCKS || n_out * sizeof(double) > 150 * 1024)
+        return fail(ctx, MLH_ERR_UNSUPPORTED, "window too large for the LDS-resident assembly (at most 22 parameter blocks, 6 (1 + frames + extrinsics) <= 132)");
     if (calib_active(ctx)) { const int crc = calib_ne_prepare(ctx, n_ext); if (crc) return crc; }
     int rc = odom_upload_poses(ctx, pivot, frames, n_frames, exts, n_ext, G.A);
     if (rc) return rc;
