@@ -87,6 +87,7 @@ static int p2p_allreduce(mlh_ctx *ctx, double *buf, int n)
 {
     if (n > P2P_MAX_DOUBLES) return fail(ctx, MLH_ERR_UNSUPPORTED, "the mailbox communicator carries records of up to 512 doubles");
     P2pArgs a;
+    (void)device_error_word(ctx);
     p2p_fill(ctx, a.d);
     a.buf = buf; a.n = n;
     MLH_LAUNCH(p2p_allreduce_kernel, dim3(1), dim3(256), 0, ctx->stream, a);

@@ -16,6 +16,7 @@
 #include "../../include/mloam_hip.h"
 #include "records.hpp"
 #include "launch_modes.hpp"
+#include "solve_plan_host.hpp"
 #include "sc_host.hpp"
 
 namespace mlh {
@@ -63,11 +64,10 @@ struct SolverState {
     int num_invalid;
     int evaluations;
     int lm_overflow;         // split-submission scan2map: an outer iteration was begun while the previous one's LM loop had not terminated inside its look-ahead budget
-    // Gauss-Newton with the finish deferred to the consumer (match.hip): iteration i's pose of a solve lives in xi[base + (i & 1)] -- written by ONE workgroup of
-    // iteration i's correspondence launch while the others may still be reading xi[base + ((i - 1) & 1)]; consecutive solves alternate base 0 / 2 (a solve's first
-    // launch may still be reading the previous solve's last slot while it fills its own first one)
+    // Gauss-Newton with the finish deferred to the consumer (match.hip): the iteration poses of a solve, single-block (two pairs of slots) and over pose blocks (per
+    // parity, per block). Which launch reads and writes which slot is ONE rule, solve_plan_host.hpp: pose_plan
     double xi[4][7];
-    double xib[2][8][7];     // the same for a solve over several pose blocks (mlh_gn_solve_blocks): iteration i's pose of block b in xib[i & 1][b]
+    double xib[2][8][7];
     double lm_used_max;      // split-submission scan2map: the largest LM iteration count of the solve's outer iterations so far (the host sizes the next frame's look-ahead by it)
     double pad2[1];
 };
@@ -672,10 +672,35 @@ struct mlh_ctx {
     mlh::DevBuf oob_flag;    // map staging: bit k set = the cloud of kind k has points outside its grid box
     bool oob_init = false;
     mlh::DevBuf ticket;      // arrival counter of the fused GN finish
-    mlh::DevBuf loop_tagged; // lm_loop_kernel: the iterations' records as tagged words (two sets of 64 words per tile; match.hip: lm_consume_launch)
-    unsigned loop_launch_seq = 0;   // ... and the launch number their tags carry (24 bits)
-    mlh::DevBuf lm_pp;       // two LmState records of the consumer-side Levenberg-Marquardt schedule
-    unsigned long long lmc_count = 0;     // consumer launches so far (its parity picks the record a launch writes)
+    // The Levenberg-Marquardt side of the solver chain (match.hip: lm_consume_launch). One owner: match.hip calls the methods, no other unit names a member.
+    struct LmChain {
+        mlh::DevBuf pp;                       // two LmState records of the consumer-side schedule: launch g reads [(g - 1) & 1], one workgroup of it writes [g & 1]
+        unsigned long long count = 0;         // consumer launches so far
+        mlh::DevBuf tagged;                   // lm_loop_kernel: the iterations' records as tagged words (reduce_dev.hpp: lmc_sum_records_tagged), two sets of 64 words per tile
+        unsigned launch_seq = 0;              // ... and the launch number their tags carry (24 bits). Zero is never a tag
+        hipError_t ensure_states(hipStream_t st)
+        {
+            if (pp.p) return hipSuccess;
+            const hipError_t e = pp.ensure(2 * sizeof(mlh::LmState));
+            return e != hipSuccess ? e : hipMemsetAsync(pp.p, 0, 2 * sizeof(mlh::LmState), st);
+        }
+        unsigned next_seq() const { const unsigned n = (launch_seq + 1u) & 0xffffffu; return n ? n : 1u; }
+        // the tagged sets of a loop over `tiles` tiles; a fresh allocation and a wrap of the launch number clear the words
+        hipError_t ensure_tagged(size_t tiles, hipStream_t st)
+        {
+            const size_t bytes = sizeof(unsigned long long) * 64 * tiles * 2;
+            const bool clear = bytes > tagged.cap || next_seq() <= launch_seq;
+            const hipError_t e = tagged.ensure(bytes);
+            if (e != hipSuccess || !clear) return e;
+            return hipMemsetAsync(tagged.p, 0, tagged.cap, st);
+        }
+        // the transitions: a consumer launch is certain; a loop launch with tagged records is
+        void consumer_launch() { ++count; }
+        void tagged_launch() { launch_seq = next_seq(); }
+        mlh::LmState *state_in() const { return pp.as<mlh::LmState>() + ((count - 1) & 1); }
+        mlh::LmState *state_out() const { return pp.as<mlh::LmState>() + (count & 1); }
+        unsigned tag_base() const { return launch_seq << 8; }       // (launch number << 8; the iteration goes into the low byte)
+    } lm;
     mlh::DevBuf stats;       // IterStatDev[...]
     mlh::DevBuf knn_q, knn_idx, knn_d;
     mlh::DevBuf tmp;         // H2D staging of caller records before packing
@@ -782,7 +807,7 @@ struct mlh_ctx {
     // An iteration's records: where a Gauss-Newton iteration that finished nothing left what the next launch's prologue sums (match.hip: prologue_reads).
     struct GnRecords {
         double *p = nullptr;      // device; null: the context's `partials` (the fit launch's tile records)
-        int rows = 1;             // per 256-feature tile: 1 record (fit_linearize_kernel's) or 4 wavefront rows (a fused launch's, in mlh_ctx::gn_rows)
+        int rows = 1;             // per 256-feature tile: 1 record (fit_linearize_kernel's) or 4 wavefront rows (a fused launch's, in GnChain::rows)
         int tiles = 0;            // 256-feature tiles
     };
     struct GnPending {            // the last iteration of the newest submitted solve is still a set of records
@@ -792,14 +817,34 @@ struct mlh_ctx {
         double thre = 100.0;
         void *rec = nullptr;      // HostPublish of that solve
         unsigned long long seq = 0;
-    } gn_pending;
+    };
     // The fit in the tail of the search launch (match.hip: knn_features_wide_kernel<.., FIT>; match_plan_host.hpp: knn_fit_in_search).
     int gn_fit_in_search = -1;    // -1: the rule (chip-filling wide launches fuse); MLH_GN_FIT_IN_SEARCH=0|1 in the environment at mlh_create pins it: none / every launch that can (tests, A/B runs)
     int gn_fused_launches = 0;    // fused launches the last submitted Gauss-Newton solve enqueued
-    mlh::DevBuf gn_rows;          // two sets of wavefront rows (4 x NE_STRIDE doubles per 256-feature tile), half the buffer each: a fused launch writes the set its
-    int gn_rows_set = 0;          // prologue does not read (a fast workgroup stores its row while a slow one still sums); the set the last fused launch wrote
-    GnRecords gn_last;            // the newest iteration that left records
-    int gn_slot_base = 0;         // xi slots of the next solve
+    // The Gauss-Newton chain: what an iteration leaves for the launch behind it, and a submitted solve for its successor. One owner: match.hip and solve_host.hip
+    // call the transitions, no other unit names a member (tests/test_abi.py); the slot arithmetic is solve_plan_host.hpp's.
+    struct GnChain {
+        GnPending pending;
+        GnRecords last;           // the newest iteration that left records
+        mlh::DevBuf rows;         // two sets of wavefront rows (4 x NE_STRIDE doubles per 256-feature tile), half the buffer each, a set beginning at a multiple of 256 bytes:
+        int rows_set = 0;         // a fused launch writes the set its prologue does not read (a fast workgroup stores its row while a slow one still sums); the set last written
+        int slot_base = 0;        // xi slots of the next submitted solve
+        static size_t rows_bytes(int tiles256) { return 2 * sizeof(double) * mlh::NE_STRIDE * 4 * size_t(tiles256) + 512; }
+        bool rows_hold(int tiles256) const { return rows_bytes(tiles256) <= rows.cap; }
+        double *rows_ptr(int set) const { return reinterpret_cast<double *>(static_cast<char *>(rows.p) + size_t(set) * ((rows.cap / 2) & ~size_t(255))); }
+        // a launch left its iteration: its fit launch's tile records in `partials`, or (fused) the other set of wavefront rows
+        void launch_left(bool fused, int tiles)
+        {
+            last = GnRecords{nullptr, 1, tiles};
+            if (fused) { rows_set ^= 1; last.p = rows_ptr(rows_set); last.rows = 4; }
+        }
+        // a submitted solve takes its pair of xi slots; the next one gets the other
+        int solve_begins() { const int base = slot_base; slot_base = mlh::gn_next_slot_base(base); return base; }
+        // ... and left its last iteration as the records `last` names, its pose in its last slot
+        void solve_left_last(int base, int n_iters, double thre, void *rec, unsigned long long seq) { pending = GnPending{true, last, mlh::gn_last_slot(base, n_iters), 0, thre, rec, seq}; }
+        // a successor's first launch consumed the pending iteration, or gn_flush_pending completes it: what it was
+        GnPending take_pending() { const GnPending p = pending; pending.active = false; return p; }
+    } gn;
     int gn_defer = 1;             // mlh_set_gn_schedule: 0: Gauss-Newton solves keep the classic finish (the fit kernel's last-arriving workgroup) in every iteration (A/B, tests)
     int knn_warm = 1;             // mlh_set_gn_schedule: 0: iterations >= 1 of a solve search without the previous iteration's neighbours as a bound (A/B, tests)
     // multi-GPU
@@ -1106,25 +1151,6 @@ inline bool schedule_on(Schedule s)
         case Schedule::TRACK_LOOP: e = std::getenv("MLH_TRACK_LOOP"); break;
     }
     return !(e && std::atoi(e) == 0);
-}
-
-// The tagged record sets of the one-launch LM loops (match.hip: lm_loop_kernel, track.hip: track_lm_loop_kernel; reduce_dev.hpp: lmc_sum_records_tagged): two sets of
-// 64 words per tile, and the number this launch's tags carry. *buf stays null where the loop keeps its grid barrier (MLH_LOOP_TAGGED=0; more iterations than the tag's
-// iteration byte counts). Zero is never a tag: a fresh allocation and a wrap of the 24-bit launch number clear the words.
-inline hipError_t loop_tagged_arm(mlh_ctx *ctx, size_t tiles, int lm_max_it, unsigned long long **buf, unsigned *tag_base)
-{
-    *buf = nullptr; *tag_base = 0u;
-    if (!schedule_on(Schedule::LOOP_TAGGED) || lm_max_it > 200 || tiles == 0) return hipSuccess;
-    const size_t bytes = sizeof(unsigned long long) * 64 * tiles * 2;
-    bool clear = bytes > ctx->loop_tagged.cap;
-    hipError_t e = ctx->loop_tagged.ensure(bytes);
-    if (e != hipSuccess) return e;
-    ctx->loop_launch_seq = (ctx->loop_launch_seq + 1u) & 0xffffffu;
-    if (ctx->loop_launch_seq == 0u) { ctx->loop_launch_seq = 1u; clear = true; }
-    if (clear && (e = hipMemsetAsync(ctx->loop_tagged.p, 0, ctx->loop_tagged.cap, ctx->stream)) != hipSuccess) return e;
-    *buf = ctx->loop_tagged.as<unsigned long long>();
-    *tag_base = ctx->loop_launch_seq << 8;
-    return hipSuccess;
 }
 
 inline hipError_t ensure_ticket(mlh_ctx *ctx)

@@ -1247,13 +1247,14 @@ __global__ __launch_bounds__(TPB) void knn_queries_kernel(GridDev grid, const fl
 }
 
 // ---------------------------------------------------------------- host launchers
-// How a launch comes about: fill_params turns MatchArgs and the context into the parameter block and -- for match_launch -- PLANS the correspondence launch, once:
-// it fills the planner's input record (plan_in_of + what the launch is) and asks knn_plan() of match_plan_host.hpp, a pure function, for the form (the kernel's
-// template arguments as data), the profiler id, whether the launch carries its fit and which fit launch follows, or for the refusal. Every rule about which kernel a
-// launch gets -- the width, the fit in the search's tail, the lanes collapse, the pose-block schedule, what device-side counts and no_fit allow -- is written there
-// and nowhere in this file. match_launch looks the form up in KNN_KERNELS, the one expansion of the list of forms that instantiates the correspondence kernels, and
-// launches it; the fit, linearise and consumer kernels are chosen by one expression each, lm_loop_kernel from one table (LM_LOOP_KERNELS). Where an iteration's
-// records lie is one descriptor (mlh_ctx::GnRecords: gn_last, gn_pending.recs, LaunchPlan::front), and prologue_reads the one place that points a launch at it.
+// How a launch comes about -- match_launch, linearize_launch and lm_consume_launch in ONE order:
+//   1. describe and plan: describe() reads MatchArgs and the context into the planners' records; pose_plan (where the launch's poses are), knn_plan (the correspondence
+//      kernel, whether it carries its fit, which fit launch follows) and lm_plan (the linearise / consumer / loop kernel) answer or refuse -- pure functions of
+//      match_plan_host.hpp and solve_plan_host.hpp. Every rule about which kernel a launch gets and which slot a pose lives in is written there, not in this file.
+//   2. - 5. prepare(): validate the staged kinds (may refuse; nothing has allocated, released, launched or counted so far), complete a pending solve (ahead of the
+//      buffers: an `ensure` may free what the pending records lie in), ensure the buffers, advance the chain state (mlh_ctx::GnChain, ::LmChain).
+//   6. fill_params only reads; 7. the form's kernel out of KNN_KERNELS / LM_KERNELS, the two expansions of the lists that instantiate the kernels, is launched.
+// Where an iteration's records lie is one descriptor (mlh_ctx::GnRecords: GnChain::last, GnPending::recs, LaunchPlan::front); prologue_reads points a launch at it.
 //
 // lanes per query, per kind. A small launch (a 16-ring frame) leaves most SIMDs idle and is bound by the latency of its trips: 16 lanes.
 // A full frame keeps ~5 wavefronts per SIMD busy and is bound by VALU issue, where the per-query instruction count is what matters:
@@ -1294,7 +1295,7 @@ static KnnPlanIn plan_in_of(const mlh_ctx *ctx, int kind_mask)
 }
 
 // gn_solve_submit's question about the solve it is about to plan: a predecessor left its last iteration as wavefront rows -- can this solve's first launch (iteration
-// 0 of a deferred solve that completes its predecessor: PRE 2, records only) read them? Asked of the planner itself, with what fill_params will give it.
+// 0 of a deferred solve that completes its predecessor: PRE 2, records only) read them? Asked of the planner itself, with what describe() will give it.
 bool gn_first_launch_takes_rows(const mlh_ctx *ctx, int kind_mask)
 {
     KnnPlanIn in = plan_in_of(ctx, kind_mask);
@@ -1302,10 +1303,6 @@ bool gn_first_launch_takes_rows(const mlh_ctx *ctx, int kind_mask)
     in.rows_in = 4;
     return knn_plan(in).err == MLH_OK;
 }
-
-// The two sets of wavefront rows of a frame with `tiles256` 256-feature tiles (mlh_ctx::gn_rows; a set begins at a multiple of 256 bytes in its half of the buffer).
-size_t gn_rows_bytes(int tiles256) { return 2 * sizeof(double) * NE_STRIDE * 4 * size_t(tiles256) + 512; }
-static double *gn_rows_set_ptr(const mlh_ctx *ctx, int set) { return reinterpret_cast<double *>(static_cast<char *>(ctx->gn_rows.p) + size_t(set) * ((ctx->gn_rows.cap / 2) & ~size_t(255))); }
 
 // A launch with a prologue sums THESE records: the three fields that say where an iteration's records are, set together.
 static void prologue_reads(KParams &P, const mlh_ctx::GnRecords &recs, double *partials)
@@ -1315,90 +1312,157 @@ static void prologue_reads(KParams &P, const mlh_ctx::GnRecords &recs, double *p
     P.pre_tiles = recs.tiles;
 }
 
+// The one place that turns a slot of the pose plan (solve_plan_host.hpp) into an address in the solver state.
+static double *pose_slot_ptr(SolverState *S, PoseSlot s)
+{
+    switch (s.kind) {
+    case SLOT_STATE_X: return S->x;
+    case SLOT_STATE_CAND: return S->cand;
+    case SLOT_STATE_XB: return &S->xb[0][0];
+    case SLOT_XI: return S->xi[s.n];
+    case SLOT_XIB: return &S->xib[s.n][0][0];
+    default: return nullptr;
+    }
+}
+
+// the pinned record a launch described by `a` publishes to (TAIL_GN, TAIL_LM_STEP and every consumer-side launch), and the statistics record it fills
+static HostPublish *publication_of(const MatchArgs &a) { return (a.finish == TAIL_GN || a.finish == TAIL_LM_STEP || a.lmc) ? a.publish : nullptr; }
+static IterStatDev *stat_of(const mlh_ctx *ctx, const MatchArgs &a) { return a.stat_slot >= 0 ? ctx->stats.as<IterStatDev>() + a.stat_slot : nullptr; }
+
 struct LaunchPlan {
-    KnnPlan knn;
-    mlh_ctx::GnRecords front;          // the records the search launch's prologue sums: the previous iteration's (mlh_ctx::gn_last) or the previous solve's (gn_pending)
+    PosePlan pose;
+    KnnPlanIn in;                      // (its lanes and the width that follows from it size the correspondence tiles of every launcher's block)
+    KnnPlan knn;                       // match_launch
+    LmPlan lm;                         // linearize_launch, lm_consume_launch
+    mlh_ctx::GnRecords front;          // the records the search launch's prologue sums: the previous iteration's (GnChain::last) or the previous solve's (MatchArgs::pre_final)
+    int n_blocks = 1, kmax = 5, tiles = 0;     // pose blocks, the largest N_NEIGH over them, fit / linearise tiles over the launch's kinds
+    bool cov = false;                  // the covariance of MLH_FLAG_POSE_COV rides in this launch's publication
+    bool search = false;               // match_launch: a correspondence launch, its iteration leaves records
+    bool loop = false, tagged = false; // lm_consume_launch: the one-launch loop; it exchanges tagged records
 };
 
-// The parameter block of a launch described by `a` -- as its fit / linearise kernel reads it (`partials`: the records it writes). match_launch passes `plan`: the
-// correspondence launch in front is planned here, once; a launch that does not exist is refused at the end, behind the validation of the staged kinds.
-static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, LaunchPlan *plan = nullptr)
+// Step 1, the description: what the three planners decide on. Reads; changes nothing.
+static LaunchPlan describe(const mlh_ctx *ctx, const MatchArgs &a)
 {
-    // a solve whose last iteration is still a set of tile records (mlh_ctx::gn_pending): any launch that writes records -- other than the chained successor's first,
-    // which consumes them -- completes that solve first
-    if (ctx->gn_pending.active && !a.pre_final) { const int frc = gn_flush_pending(ctx); if (frc) return frc; }
-    std::memset(&P, 0, sizeof(P));
-    int tiles_b_total = 0;
-    P.n_blocks = a.n_blocks > 0 ? a.n_blocks : 1;
-    int kmax = 5;
-    for (int b = 0; b < P.n_blocks; ++b) {
-        P.kb[b] = a.k_neigh[b] == 10 ? 10 : 5;
-        P.thre_b[b] = a.eig_thre[b];
-        P.freeze_b[b] = a.freeze[b];
-        kmax = std::max(kmax, P.kb[b]);
-    }
-    P.pre_finish = a.gn_iter >= 1 ? PRE_ITERATION : (a.gn_iter == 0 && a.pre_final) ? PRE_SOLVE : PRE_NONE;
-    P.stat = (a.stat_slot >= 0) ? ctx->stats.as<IterStatDev>() + a.stat_slot : nullptr;
-    KnnPlanIn in = plan_in_of(ctx, a.kind_mask);
-    in.mb = P.n_blocks > 1; in.k10 = kmax == 10; in.gn_blocks = a.gn_blocks; in.m_dev = a.m_dev != nullptr;
-    in.pre_finish = P.pre_finish; in.warm = a.warm; in.tail = a.finish;
-    in.no_fit = a.no_fit; in.dense = a.dense; in.lmc = a.lmc != LMC_NONE; in.stat = P.stat != nullptr;
-    if (plan) {
-        if (P.pre_finish == PRE_ITERATION) plan->front = ctx->gn_last;
-        if (P.pre_finish == PRE_SOLVE) plan->front = a.pre_final->recs;
-        in.rows_in = P.pre_finish ? plan->front.rows : 1;
-        plan->knn = knn_plan(in);
-    }
-    const int wg = knn_plan_width(in);     // (tiles_a counts workgroups of this width)
-    P.knn_lanes = knn_plan_lanes(in);
+    LaunchPlan pl;
+    pl.n_blocks = a.n_blocks > 0 ? a.n_blocks : 1;
+    for (int b = 0; b < pl.n_blocks; ++b) if (a.k_neigh[b] == 10) pl.kmax = 10;
+    PosePlanIn pi;
+    pi.gn_iter = a.gn_iter; pi.gn_blocks = a.gn_blocks; pi.pre_final = a.pre_final != nullptr; pi.init_pose = a.init_pose != nullptr;
+    pi.pose_sel = a.pose_sel; pi.slot_base = a.gn_slot_base; pi.pre_slot = a.pre_final ? a.pre_final->slot : 0;
+    pl.pose = pose_plan(pi);
+    KnnPlanIn &in = pl.in;
+    in = plan_in_of(ctx, a.kind_mask);
+    in.mb = pl.n_blocks > 1; in.k10 = pl.kmax == 10; in.gn_blocks = a.gn_blocks; in.m_dev = a.m_dev != nullptr;
+    in.pre_finish = pl.pose.pre_finish; in.warm = a.warm; in.tail = a.finish;
+    in.no_fit = a.no_fit; in.dense = a.dense; in.lmc = a.lmc != LMC_NONE; in.stat = stat_of(ctx, a) != nullptr;
+    if (in.pre_finish == PRE_ITERATION) pl.front = ctx->gn.last;
+    if (in.pre_finish == PRE_SOLVE) pl.front = a.pre_final->recs;
+    in.rows_in = in.pre_finish ? pl.front.rows : 1;
+    for (int k = 0; k < 2; ++k) if (a.kind_mask & (1 << k)) pl.tiles += tiles_of(ctx->feat[k].m);
+    pl.cov = (a.flags & MLH_FLAG_POSE_COV) != 0 && publication_of(a) != nullptr;
+    return pl;
+}
+
+// ... and of a linearise / LM launch, for lm_plan. schedule_on() is read here, at launch time: tests change the switches in the middle of a context's life.
+static LmPlanIn lm_in_of(const mlh_ctx *ctx, const MatchArgs &a, const LaunchPlan &pl, LmFamily family)
+{
+    LmPlanIn in;
+    in.family = family; in.tail = a.finish; in.lmc = a.lmc; in.lmc_j = a.lmc_j;
+    in.cov = pl.cov; in.m_dev = a.m_dev != nullptr; in.fit_in_loop = a.fit_in_loop;
+    in.n_blocks = a.n_blocks; in.dense = a.dense;
+    in.kind_mask = a.kind_mask; in.matched_mask = (ctx->feat[0].matched ? 1 : 0) | (ctx->feat[1].matched ? 2 : 0);
+    // (the mailbox communicator rides in the finishing workgroup of a Gauss-Newton launch and of an LM begin / step launch; other launches exchange nothing)
+    in.n_ranks = ((a.finish == TAIL_GN || a.finish == TAIL_LM_BEGIN || a.finish == TAIL_LM_STEP) && ctx->p2p.active) ? ctx->n_ranks : 1;
+    in.tiles = pl.tiles; in.gate_tiles = (pl.cov ? ctx->caps.loop_max_tiles_cov : ctx->caps.loop_max_tiles)[a.m_dev ? 1 : 0];
+    in.tagged = schedule_on(Schedule::LOOP_TAGGED) && a.lm_max_it <= 200;
+    return in;
+}
+
+// Steps 2 to 5 of a planned launch. Up to the end of step 2 nothing allocates, releases, launches or counts; behind step 5 nothing refuses.
+static int prepare(mlh_ctx *ctx, const MatchArgs &a, const LaunchPlan &pl)
+{
+    // 2. the staged kinds
     for (int k = 0; k < 2; ++k) {
-        KindP &K = P.k[k];
         if (!(a.kind_mask & (1 << k))) continue;
-        FeatSet &fs = ctx->feat[k];
-        MapGrid &mg = ctx->map[k];
+        const FeatSet &fs = ctx->feat[k];
+        const MapGrid &mg = ctx->map[k];
         if (!mg.built) return fail(ctx, MLH_ERR_STATE, "map_set has not been called for this kind");
         if (fs.m <= 0) return fail(ctx, MLH_ERR_STATE, "features_set has not been called for this kind");
-        if (fs.n_blocks != P.n_blocks) return fail(ctx, MLH_ERR_STATE, "the staged features hold a different number of pose blocks than requested");
+        if (fs.n_blocks != pl.n_blocks) return fail(ctx, MLH_ERR_STATE, "the staged features hold a different number of pose blocks than requested");
         // the cell edge was derived from the acceptance radius given at map_set; a larger radius here would break exactness
         if (a.min_match_sq_dis > 0.f && std::sqrt(a.min_match_sq_dis) > mg.h)
             return fail(ctx, MLH_ERR_INVALID, "min_match_sq_dis exceeds the value the map grid was built for");
-        hipError_t e;
+    }
+    if (pl.tiles == 0) return fail(ctx, MLH_ERR_STATE, "no map/features staged for the requested kinds");
+    // 3. a solve whose last iteration is still a set of tile records (GnChain::pending): any launch that writes records -- other than the chained successor's first,
+    // which consumes them -- completes that solve first
+    if (!a.pre_final) { const int frc = gn_flush_pending(ctx); if (frc) return frc; }
+    // 4. the buffers
+    hipError_t e;
+    for (int k = 0; k < 2; ++k) {
+        if (!(a.kind_mask & (1 << k))) continue;
+        FeatSet &fs = ctx->feat[k];
         if ((e = fs.corr.ensure(sizeof(Corr) * size_t(fs.m))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc corr", e);
-        if (fs.nbr_stride < kmax) { fs.nbr.release(); fs.nbr_stride = kmax; }
+        if (fs.nbr_stride < pl.kmax) { fs.nbr.release(); fs.nbr_stride = pl.kmax; }
         if ((e = fs.nbr.ensure(sizeof(float4) * size_t(fs.nbr_stride) * size_t(fs.m))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc nbr", e);
         if (a.dense) {
             if ((e = fs.r.ensure(sizeof(double) * size_t(fs.m))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc r", e);
             if ((e = fs.J.ensure(sizeof(double) * 6 * size_t(fs.m))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc J", e);
         }
-        K.grid = mg.dev();
+    }
+    // (two sets of records: the consumer-side Levenberg-Marquardt launches alternate between them)
+    if ((e = ctx->partials.ensure(sizeof(double) * NE_STRIDE * size_t(pl.tiles) * 2)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc partials", e);
+    if ((e = ensure_ticket(ctx)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc ticket", e);
+    if (ctx->p2p.active) (void)device_error_word(ctx);      // (the word a mailbox exchange that gives up sets: p2p_fill reads it)
+    if (a.lmc && (e = ctx->lm.ensure_states(ctx->stream)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc lm state", e);
+    if (pl.tagged && (e = ctx->lm.ensure_tagged(size_t(pl.tiles), ctx->stream)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "tagged records", e);
+    // (a set of rows the prologue reads lies in this buffer; a reallocation would have been refused before the launch was planned: gn_solve_submit's `consume`)
+    if (pl.knn.fused && (e = ctx->gn.rows.ensure(mlh_ctx::GnChain::rows_bytes(pl.tiles))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc wavefront rows", e);
+    // 5. the chain state
+    ctx->n_partial_tiles = pl.tiles;
+    if (a.lmc) ctx->lm.consumer_launch();
+    if (pl.tagged) ctx->lm.tagged_launch();
+    // (what a correspondence launch's iteration leaves for the next launch's prologue: its fit launch's tile records, or -- fused -- the set of wavefront rows it writes)
+    if (pl.search && !a.m_dev) ctx->gn.launch_left(pl.knn.fused, pl.tiles);
+    return MLH_OK;
+}
+
+// Step 6: the parameter block of the planned launch -- as its fit / linearise kernel reads it (`partials`: the records it writes). Only reads.
+static void fill_params(const mlh_ctx *ctx, const MatchArgs &a, const LaunchPlan &pl, KParams &P)
+{
+    std::memset(&P, 0, sizeof(P));
+    SolverState *S = ctx->state.as<SolverState>();
+    P.n_blocks = pl.n_blocks;
+    for (int b = 0; b < P.n_blocks; ++b) {
+        P.kb[b] = a.k_neigh[b] == 10 ? 10 : 5;
+        P.thre_b[b] = a.eig_thre[b];
+        P.freeze_b[b] = a.freeze[b];
+    }
+    P.pre_finish = pl.pose.pre_finish;
+    P.stat = stat_of(ctx, a);
+    const int wg = knn_plan_width(pl.in);     // (tiles_a counts workgroups of this width)
+    P.knn_lanes = knn_plan_lanes(pl.in);
+    for (int k = 0; k < 2; ++k) {
+        KindP &K = P.k[k];
+        if (!(a.kind_mask & (1 << k))) continue;
+        const FeatSet &fs = ctx->feat[k];
+        K.grid = ctx->map[k].dev();
         K.feat = fs.pts.as<float4>();
         K.covd = fs.has_cov ? fs.covd.as<float4>() : nullptr;
-        K.nbr = fs.nbr.as<float4>();
-        K.corr = fs.corr.as<Corr>();
-        K.r_out = a.dense ? fs.r.as<double>() : nullptr;
-        K.J_out = a.dense ? fs.J.as<double>() : nullptr;
-        K.m = fs.m;
-        K.lanes = in.lanes[k];
+        K.nbr = fs.nbr.as<float4>(); K.corr = fs.corr.as<Corr>();
+        K.r_out = a.dense ? fs.r.as<double>() : nullptr; K.J_out = a.dense ? fs.J.as<double>() : nullptr;
+        K.m = fs.m; K.lanes = pl.in.lanes[k];
         K.tiles_a = (fs.m + wg / K.lanes - 1) / (wg / K.lanes);
-        K.tiles_b = (fs.m + TPB - 1) / TPB;
+        K.tiles_b = tiles_of(fs.m);
         K.nbr_stride = fs.nbr_stride;
         for (int b = 0; b <= MAX_BLOCKS; ++b) K.blk_start[b] = fs.blk_start[std::min(b, fs.n_blocks)];
-        tiles_b_total += K.tiles_b;
     }
-    if (tiles_b_total == 0) return fail(ctx, MLH_ERR_STATE, "no map/features staged for the requested kinds");
-    hipError_t e;
-    // (two sets of records: the consumer-side Levenberg-Marquardt launches alternate between them)
-    if ((e = ctx->partials.ensure(sizeof(double) * NE_STRIDE * size_t(tiles_b_total) * 2)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc partials", e);
-    if ((e = ensure_ticket(ctx)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc ticket", e);
-    ctx->n_partial_tiles = tiles_b_total;
     P.partials = ctx->partials.as<double>();
-    P.state = ctx->state.as<SolverState>();
-    P.pose_sel = a.pose_sel;
-    P.flags = a.flags;
-    P.min_match_sq_dis = a.min_match_sq_dis;
-    P.min_plane_dis = a.min_plane_dis;
-    P.huber_delta = a.huber_delta;
-    P.cov_measurement_trace = a.cov_measurement_trace;
+    P.state = S;
+    P.pose_sel = a.pose_sel; P.flags = a.flags;
+    P.min_match_sq_dis = a.min_match_sq_dis; P.min_plane_dis = a.min_plane_dis;
+    P.huber_delta = a.huber_delta; P.cov_measurement_trace = a.cov_measurement_trace;
     P.own_mod = ctx->own_mod; P.own_rem = ctx->own_rem;
     P.own_mode = (ctx->shard_lo ? 1 : 0) | (ctx->shard_hi ? 2 : 0) | (ctx->own_mod > 1 ? 4 : 0);
     for (int i = 0; i < 4; ++i) { P.lo[i] = ctx->lo_plane[i]; P.hi[i] = ctx->hi_plane[i]; }
@@ -1407,76 +1471,38 @@ static int fill_params(mlh_ctx *ctx, const MatchArgs &a, KParams &P, LaunchPlan 
     // the mailbox communicator rides in the finishing workgroup of a Gauss-Newton launch and of an LM begin / step launch; other launches exchange nothing
     if ((a.finish == TAIL_GN || a.finish == TAIL_LM_BEGIN || a.finish == TAIL_LM_STEP) && ctx->p2p.active) p2p_fill(ctx, P.p2p);
     else { P2pDev none{}; none.n_ranks = 1; P.p2p = none; }
-    P.use_init = a.init_pose ? 1 : 0;
     for (int i = 0; i < 7; ++i) P.init_pose[i] = a.init_pose ? a.init_pose[i] : 0.0;
     P.warm = a.warm ? 1 : 0;
-    if (a.gn_iter >= 1 && a.gn_blocks) {
-        // iteration i >= 1 of a deferred-finish solve over pose blocks: every block's pose of iteration i in SolverState::xib[i & 1][b]; iteration 1 updates the poses
-        // the state holds (x, xb[b])
-        SolverState *S = ctx->state.as<SolverState>();
-        P.pre_from_init = 0;
-        P.pre_from_state = a.gn_iter == 1 ? 1 : 0;
-        P.x_prev = &S->xib[(a.gn_iter - 1) & 1][0][0];
-        P.x_next = &S->xib[a.gn_iter & 1][0][0];
-        P.pose0 = &S->xib[a.gn_iter & 1][0][0];
-        P.use_init = 0;
-    } else if (a.gn_iter >= 1) {
-        // iteration i >= 1 of a deferred-finish solve: the correspondence kernel turns iteration i - 1's records and pose into pose i (SolverState::xi[base + (i & 1)]);
-        // iteration 1 finds pose 0 where iteration 0 found it -- the kernel arguments, the state's x (a chained solve behind a chain launch), or iteration 0's slot
-        // (a chained solve whose first launch computed the start pose itself, MatchArgs::pre_final)
-        SolverState *S = ctx->state.as<SolverState>();
-        P.pre_from_init = (a.gn_iter == 1 && a.init_pose) ? 1 : 0;
-        P.x_prev = (a.gn_iter == 1 && !a.pre_final) ? S->x : S->xi[a.gn_slot_base + ((a.gn_iter - 1) & 1)];
-        P.x_next = S->xi[a.gn_slot_base + (a.gn_iter & 1)];
-        P.pose0 = S->xi[a.gn_slot_base + (a.gn_iter & 1)];
-        P.use_init = 0;
-    } else if (P.pre_finish == PRE_SOLVE) {
-        // iteration 0 of a chained solve that completes its predecessor first (knn_features_kernel<.., PRE = 2>): the predecessor's records, thresholds, last pose slot
-        // and host record; this frame's start pose goes to xi[base] (the fit kernel of this iteration and iteration 1's prologue read it there)
-        SolverState *S = ctx->state.as<SolverState>();
-        P.pre_from_init = 0;
-        P.x_prev = S->xi[a.pre_final->slot];
-        P.x_next = S->xi[a.gn_slot_base];
-        P.pose0 = S->xi[a.gn_slot_base];
-        P.use_init = 0;
-        P.pre_publish = static_cast<HostPublish *>(a.pre_final->rec);
-        P.pre_publish_seq = a.pre_final->seq;
-        P.pre_thre = a.pre_final->thre;
-        P.pre_freeze = a.pre_final->freeze;
+    // where the launch's poses are (solve_plan_host.hpp: pose_plan)
+    P.use_init = pl.pose.use_init; P.pre_from_init = pl.pose.pre_from_init; P.pre_from_state = pl.pose.pre_from_state;
+    P.x_prev = pose_slot_ptr(S, pl.pose.x_prev); P.x_next = pose_slot_ptr(S, pl.pose.x_next); P.pose0 = pose_slot_ptr(S, pl.pose.pose0);
+    P.pose_b0 = pose_slot_ptr(S, pl.pose.pose_b0); P.pose_bn = pose_slot_ptr(S, pl.pose.pose_bn);
+    if (P.pre_finish == PRE_SOLVE) {
+        // iteration 0 of a chained solve that completes its predecessor first (knn_features_kernel<.., PRE = 2>): the predecessor's thresholds and host record, and
+        // the two odometry poses this frame's start pose is chained with
+        P.pre_publish = static_cast<HostPublish *>(a.pre_final->rec); P.pre_publish_seq = a.pre_final->seq;
+        P.pre_thre = a.pre_final->thre; P.pre_freeze = a.pre_final->freeze;
         for (int i = 0; i < 7; ++i) { P.chain_prev[i] = a.chain_prev[i]; P.chain_cur[i] = a.chain_cur[i]; }
     }
-    {   // where the launch's poses are, when they are not init_pose (load_pose)
-        SolverState *S = ctx->state.as<SolverState>();
-        P.pose_b0 = P.pose0 ? P.pose0 : (P.pose_sel ? S->cand : S->x);
-        P.pose_bn = P.pose0 ? P.pose0 : &S->xb[0][0];
-    }
     P.m_dev = a.m_dev;
-    P.publish = (a.finish == TAIL_GN || a.finish == TAIL_LM_STEP || a.lmc) ? a.publish : nullptr;
+    P.publish = publication_of(a);
     if (a.lmc) {
-        if (!ctx->lm_pp.p) {
-            if ((e = ctx->lm_pp.ensure(2 * sizeof(LmState))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc lm state", e);
-            if ((e = hipMemsetAsync(ctx->lm_pp.p, 0, 2 * sizeof(LmState), ctx->stream)) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "memset lm state", e);
-        }
-        const unsigned long long g = ++ctx->lmc_count;
-        P.lm_in = ctx->lm_pp.as<LmState>() + ((g - 1) & 1);
-        P.lm_out = ctx->lm_pp.as<LmState>() + (g & 1);
-        const size_t set = size_t(NE_STRIDE) * size_t(tiles_b_total);
+        P.lm_in = ctx->lm.state_in(); P.lm_out = ctx->lm.state_out();
+        const size_t set = size_t(NE_STRIDE) * size_t(pl.tiles);
         P.partials_in = ctx->partials.as<double>() + set * size_t((a.lmc_j - 1) & 1);
         P.partials = ctx->partials.as<double>() + set * size_t(a.lmc_j & 1);
         if (a.lmc == LMC_LOOP) { P.partials_in = ctx->partials.as<double>(); P.partials = ctx->partials.as<double>(); }     // (the loop kernel alternates by itself)
     }
+    if (pl.loop) {
+        { const char *e = std::getenv("MLH_DEBUG_LOOP_STALL"); P.debug_stall = (e && std::atoi(e) != 0) ? 1 : 0; }
+        P.loop_timeout_ticks = ctx->caps.loop_timeout_ticks;
+        // the iterations' records as tagged words summed by polling (MLH_LOOP_TAGGED=0: plain records behind a grid barrier, as through round 5)
+        if (pl.tagged) { P.loop_tagged = ctx->lm.tagged.as<unsigned long long>(); P.loop_tag_base = ctx->lm.tag_base(); }
+    }
     P.publish_seq = a.publish_seq;
     P.ticket = ctx->ticket.as<unsigned>();
     P.pre_rows = 1;
-    if (plan) {
-        if (plan->knn.err) return fail(ctx, plan->knn.err, plan->knn.why);
-        if (plan->knn.fused) {
-            if ((e = ctx->gn_rows.ensure(gn_rows_bytes(tiles_b_total))) != hipSuccess) return fail(ctx, MLH_ERR_HIP, "alloc wavefront rows", e);
-            // (a set the prologue reads lies in this buffer; a reallocation would have been refused before the launch was planned: gn_solve_submit's `consume`)
-            P.rows_out = gn_rows_set_ptr(ctx, ctx->gn_rows_set ^ 1);
-        }
-    }
-    return MLH_OK;
+    if (pl.knn.fused) P.rows_out = ctx->gn.last.p;      // (the set GnChain::launch_left just turned to)
 }
 
 template <typename Kern>
@@ -1492,26 +1518,24 @@ static void launch_timed(mlh_ctx *ctx, int kid, Kern kern, int grid, const KPara
 
 int gn_flush_pending(mlh_ctx *ctx)
 {
-    if (!ctx || !ctx->gn_pending.active) return MLH_OK;
+    if (!ctx || !ctx->gn.pending.active) return MLH_OK;
+    const mlh_ctx::GnPending pend = ctx->gn.take_pending();
     KParams P;
     std::memset(&P, 0, sizeof(P));
     SolverState *S = ctx->state.as<SolverState>();
-    prologue_reads(P, ctx->gn_pending.recs, ctx->partials.as<double>());
+    prologue_reads(P, pend.recs, ctx->partials.as<double>());
     P.state = S;
     P.pre_finish = PRE_SOLVE;
-    P.x_prev = S->xi[ctx->gn_pending.slot];
-    P.pre_publish = static_cast<HostPublish *>(ctx->gn_pending.rec);
-    P.pre_publish_seq = ctx->gn_pending.seq;
-    P.pre_thre = ctx->gn_pending.thre;
-    P.pre_freeze = ctx->gn_pending.freeze;
-    ctx->gn_pending.active = false;
+    P.x_prev = pose_slot_ptr(S, PoseSlot{SLOT_XI, pend.slot});
+    P.pre_publish = static_cast<HostPublish *>(pend.rec); P.pre_publish_seq = pend.seq;
+    P.pre_thre = pend.thre; P.pre_freeze = pend.freeze;
     launch_timed(ctx, MLH_K_SOLVE, gn_final_kernel, 1, P);
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
 }
 
-// The kernel of every form in the list (match_plan_host.hpp: MLH_KNN_FORMS), in the list's order: KNN_KERNELS[knn_form_index(form)]. This expansion is what
-// instantiates the correspondence kernels; nothing else names one.
+// The kernel of every form in the lists (match_plan_host.hpp: MLH_KNN_FORMS; solve_plan_host.hpp: MLH_LM_FORMS), in the lists' order: KNN_KERNELS[knn_form_index(form)],
+// LM_KERNELS[lm_form_index(form)]. These expansions are what instantiates the correspondence, linearise, consumer and loop kernels; nothing else names one.
 using KernelFn = void (*)(KParams);
 template <int W, int G, bool MB, bool K10, int PRE, bool WARM, bool DEVM, bool FIT>
 constexpr KernelFn knn_kernel_of()
@@ -1523,6 +1547,16 @@ constexpr KernelFn knn_kernel_of()
 static const KernelFn KNN_KERNELS[KNN_FORM_COUNT] = {MLH_KNN_FORMS(MLH_KNN_KERNEL_ENTRY)};
 #undef MLH_KNN_KERNEL_ENTRY
 static_assert(KNN_WG_NARROW == TPB && KNN_FUSE_MIN_QUERIES == KNN_LATENCY_LIMIT, "the planner's two constants are the kernels'");
+template <int F, bool A, bool B, bool C>
+constexpr KernelFn lm_kernel_of()
+{
+    if constexpr (F == LM_LINEARIZE) return linearize_kernel<A, B>;
+    else if constexpr (F == LM_CONSUME) return lm_consume_kernel<A, B>;
+    else return lm_loop_kernel<A, B, C>;
+}
+#define MLH_LM_KERNEL_ENTRY(F, A, B, C) lm_kernel_of<F, bool(A), bool(B), bool(C)>(),
+static const KernelFn LM_KERNELS[LM_FORM_COUNT] = {MLH_LM_FORMS(MLH_LM_KERNEL_ENTRY)};
+#undef MLH_LM_KERNEL_ENTRY
 
 static KernelFn fit_kernel_of(KnnFit fit)
 {
@@ -1539,90 +1573,59 @@ static KernelFn fit_kernel_of(KnnFit fit)
 
 int match_launch(mlh_ctx *ctx, const MatchArgs &a)
 {
-    KParams P;
-    LaunchPlan plan;
-    int rc = fill_params(ctx, a, P, &plan);
-    if (rc) return rc;
-    const KnnPlan &kp = plan.knn;
+    LaunchPlan pl = describe(ctx, a);
+    pl.search = true;
+    if (a.pre_final && (a.pre_final->slot >> 1) == (a.gn_slot_base >> 1)) return fail(ctx, MLH_ERR_STATE, "the predecessor's last pose slot lies in this solve's own pair");      // (x_prev != x_next: solve_plan_host.hpp)
+    const KnnPlan &kp = pl.knn = knn_plan(pl.in);
+    if (kp.err) return fail(ctx, kp.err, kp.why);
     const int form = knn_form_index(kp.form);
     if (form < 0) return fail(ctx, MLH_ERR_STATE, "the planned correspondence kernel is not in the list of forms");      // (unreachable: tests/host/match_plan_main.cpp)
+    const int rc = prepare(ctx, a, pl);
+    if (rc) return rc;
+    KParams P;
+    fill_params(ctx, a, pl, P);
     // kernel A: correspondences (8, 16 or 32 lanes per feature, form.W threads per workgroup); kernel B: fit + linearise + reduce (one lane per feature)
     const int grid_a = ((P.k[0].tiles_a + P.k[1].tiles_a + 7) / 8) * 8;
-    const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
+    const int grid_b = ((pl.tiles + 7) / 8) * 8;
     // (the search launch's prologue reads the previous iteration's records where and how that iteration left them; the fit launch, if there is one, writes `partials`)
     KParams S = P;
-    if (P.pre_finish) prologue_reads(S, plan.front, P.partials);
+    if (P.pre_finish) prologue_reads(S, pl.front, P.partials);
     launch_timed(ctx, kp.kid, KNN_KERNELS[form], grid_a, S, kp.form.W);
     if (kp.gn_shape) ctx->knn_wg_last = kp.form.W;
     if (kp.fit != KNN_FIT_NONE) launch_timed(ctx, MLH_K_FIT, fit_kernel_of(kp.fit), grid_b, P);
-    if (!P.m_dev) {
-        // what this iteration leaves for the next launch's prologue: its fit launch's tile records, or (fused) the set of wavefront rows it wrote
-        ctx->gn_last = mlh_ctx::GnRecords{nullptr, 1, P.k[0].tiles_b + P.k[1].tiles_b};
-        if (kp.fused) {
-            ctx->gn_rows_set ^= 1;
-            ctx->gn_last.p = P.rows_out; ctx->gn_last.rows = 4;
-            ++ctx->gn_fused_launches;
-        }
-    }
+    if (kp.fused && !P.m_dev) ++ctx->gn_fused_launches;
     MLH_HIP(ctx, hipGetLastError());
     // (no_fit: the loop launch behind this one writes the correspondences; both kinds, as the planner saw to)
     for (int k = 0; k < 2; ++k) if (a.kind_mask & (1 << k)) ctx->feat[k].matched = !a.no_fit;
     return MLH_OK;
 }
 
-
-static bool pose_cov_launch(const KParams &P) { return (P.flags & MLH_FLAG_POSE_COV) != 0 && P.publish != nullptr; }
-
-int linearize_launch(mlh_ctx *ctx, const MatchArgs &a)
+// linearize_launch and lm_consume_launch behind their plan: the kernel is LM_KERNELS' entry for the planned form
+static int lm_launch_planned(mlh_ctx *ctx, const MatchArgs &a, LmFamily family)
 {
-    for (int k = 0; k < 2; ++k)
-        if ((a.kind_mask & (1 << k)) && !ctx->feat[k].matched) return fail(ctx, MLH_ERR_STATE, "linearize needs a previous match of this kind");
-    KParams P;
-    int rc = fill_params(ctx, a, P);
+    LaunchPlan pl = describe(ctx, a);
+    const LmPlanIn in = lm_in_of(ctx, a, pl, family);
+    pl.lm = lm_plan(in);
+    if (pl.lm.err) return fail(ctx, pl.lm.err, pl.lm.why);
+    const int form = lm_form_index(pl.lm.form);
+    if (form < 0) return fail(ctx, MLH_ERR_STATE, "the planned linearise kernel is not in the list of forms");      // (unreachable: tests/host/solve_plan_main.cpp)
+    pl.loop = pl.lm.form.family == LM_LOOP;
+    pl.tagged = pl.loop && in.tagged;
+    const int rc = prepare(ctx, a, pl);
     if (rc) return rc;
-    const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
-    // (the covariance of MLH_FLAG_POSE_COV rides in a publication: launches that publish nothing are the default kernels)
-    const bool lm = P.finish == TAIL_LM_BEGIN || P.finish == TAIL_LM_STEP;
-    launch_timed(ctx, MLH_K_LINEARIZE, lm && pose_cov_launch(P) ? linearize_kernel<true, true> : lm ? linearize_kernel<true> : linearize_kernel<false>, grid_b, P);
+    if (pl.loop && a.lm_expect_done == LM_FIRST_OF_SOLVE) ++ctx->caps.loop_launches;      // (the first loop of a frame)
+    KParams P;
+    fill_params(ctx, a, pl, P);
+    launch_timed(ctx, MLH_K_LINEARIZE, LM_KERNELS[form], ((pl.tiles + 7) / 8) * 8, P);
+    if (pl.loop && a.fit_in_loop) for (int k = 0; k < 2; ++k) ctx->feat[k].matched = true;
     MLH_HIP(ctx, hipGetLastError());
     return MLH_OK;
 }
 
-// lm_loop_kernel<DEVM, FIT, COV>, every instantiation: [FIT][COV][DEVM] (lm_consume_launch launches one, lm_loop_occupancy asks the device about all of them)
-static const KernelFn LM_LOOP_KERNELS[2][2][2] = {{{lm_loop_kernel<false, false, false>, lm_loop_kernel<true, false, false>}, {lm_loop_kernel<false, false, true>, lm_loop_kernel<true, false, true>}},
-                                                  {{lm_loop_kernel<false, true, false>, lm_loop_kernel<true, true, false>}, {lm_loop_kernel<false, true, true>, lm_loop_kernel<true, true, true>}}};
+int linearize_launch(mlh_ctx *ctx, const MatchArgs &a) { return lm_launch_planned(ctx, a, LM_LINEARIZE); }
+int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a) { return lm_launch_planned(ctx, a, LM_CONSUME); }
 
-int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a)
-{
-    for (int k = 0; k < 2; ++k)
-        if ((a.kind_mask & (1 << k)) && !ctx->feat[k].matched && !a.fit_in_loop) return fail(ctx, MLH_ERR_STATE, "the Levenberg-Marquardt launches need a previous match of this kind");
-    if (a.lmc == LMC_NONE || a.lmc_j < 1 || a.n_blocks > 1 || a.dense) return fail(ctx, MLH_ERR_INVALID, "lm_consume_launch: single block, no dense rows");
-    if (a.fit_in_loop && (a.lmc != LMC_LOOP || (a.kind_mask & 3) != 3 || !loop_fit_fusable(a))) return fail(ctx, MLH_ERR_INVALID, "the fit rides in the one-launch loop with tagged records only");
-    KParams P;
-    int rc = fill_params(ctx, a, P);
-    if (rc) return rc;
-    if (P.p2p.n_ranks > 1) return fail(ctx, MLH_ERR_UNSUPPORTED, "the consumer-side Levenberg-Marquardt schedule is single-GPU");
-    const int grid_b = ((P.k[0].tiles_b + P.k[1].tiles_b + 7) / 8) * 8;
-    if (a.lmc == LMC_LOOP) {
-        { const char *e = std::getenv("MLH_DEBUG_LOOP_STALL"); P.debug_stall = (e && std::atoi(e) != 0) ? 1 : 0; }
-        // every tile's workgroup has to be resident for the barrier: the host's gate (capi.hip: loop_tiles_ok) is what the device admits, asked at mlh_create
-        const bool cov = pose_cov_launch(P);
-        if (P.k[0].tiles_b + P.k[1].tiles_b > (cov ? ctx->caps.loop_max_tiles_cov : ctx->caps.loop_max_tiles)[P.m_dev ? 1 : 0]) return fail(ctx, MLH_ERR_INVALID, "lm_loop_kernel: more tiles than can be resident at once on this device");
-        P.loop_timeout_ticks = ctx->caps.loop_timeout_ticks;
-        if (a.lm_expect_done == LM_FIRST_OF_SOLVE) ++ctx->caps.loop_launches;      // (the first loop of a frame)
-        // the iterations' records as tagged words summed by polling (MLH_LOOP_TAGGED=0: plain records behind a grid barrier, as through round 5)
-        { hipError_t e = loop_tagged_arm(ctx, size_t(P.k[0].tiles_b + P.k[1].tiles_b), a.lm_max_it, &P.loop_tagged, &P.loop_tag_base); if (e != hipSuccess) return fail(ctx, MLH_ERR_HIP, "tagged records", e); }
-        if (a.fit_in_loop && !P.loop_tagged) return fail(ctx, MLH_ERR_INVALID, "the fit rides in the one-launch loop with tagged records only");
-        launch_timed(ctx, MLH_K_LINEARIZE, LM_LOOP_KERNELS[a.fit_in_loop][cov][P.m_dev != nullptr], grid_b, P);
-        if (a.fit_in_loop) for (int k = 0; k < 2; ++k) ctx->feat[k].matched = true;
-    } else {
-        const bool begin = a.lmc == LMC_BEGIN, cov = pose_cov_launch(P);
-        launch_timed(ctx, MLH_K_LINEARIZE, begin ? (cov ? lm_consume_kernel<true, true> : lm_consume_kernel<true>) : (cov ? lm_consume_kernel<false, true> : lm_consume_kernel<false>), grid_b, P);
-    }
-    MLH_HIP(ctx, hipGetLastError());
-    return MLH_OK;
-}
-
+// the loop launch described by these arguments can carry its fit: tagged records (LmPlanIn::tagged), exactly one block, no dense rows
 bool loop_fit_fusable(const MatchArgs &loop_args)
 {
     return schedule_on(Schedule::LOOP_TAGGED) && loop_args.lm_max_it <= 200 && loop_args.n_blocks == 1 && !loop_args.dense;
@@ -1632,13 +1635,17 @@ int lm_loop_occupancy(int blocks_per_cu[2], int blocks_per_cu_cov[2])
 {
     // per COV (the instantiations that publish the covariance, MLH_FLAG_POSE_COV, are gated by their own numbers) and DEVM: the forms with and without the fit in
     // front -- the smaller number gates both
-    for (int cov = 0; cov < 2; ++cov)
-        for (int devm = 0; devm < 2; ++devm) {
-            int n[2] = {0, 0};
-            for (int fit = 0; fit < 2; ++fit)
-                if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n[fit], LM_LOOP_KERNELS[fit][cov][devm], TPB, 0) != hipSuccess) return MLH_ERR_HIP;
-            (cov ? blocks_per_cu_cov : blocks_per_cu)[devm] = std::min(n[0], n[1]);
-        }
+    int *out[2] = {blocks_per_cu, blocks_per_cu_cov};
+    bool seen[2][2] = {{false, false}, {false, false}};
+    for (int i = 0; i < LM_FORM_COUNT; ++i) {
+        const LmForm &f = LM_FORMS[i];      // lm_loop_kernel<DEVM = a, FIT = b, COV = c>
+        if (f.family != LM_LOOP) continue;
+        int n = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, LM_KERNELS[i], TPB, 0) != hipSuccess) return MLH_ERR_HIP;
+        int &o = out[f.c][f.a];
+        o = seen[f.c][f.a] ? std::min(o, n) : n;
+        seen[f.c][f.a] = true;
+    }
     return MLH_OK;
 }
 

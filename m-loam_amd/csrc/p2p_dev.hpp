@@ -62,14 +62,14 @@ __device__ __forceinline__ bool p2p_exchange(const P2pDev &a, double *rec, int n
     return ok;
 }
 
-// fills the device-side descriptor from the context
-inline void p2p_fill(mlh_ctx *ctx, P2pDev &d)
+// fills the device-side descriptor from the context (only reads: the caller has made sure of the error word, device_error_word)
+inline void p2p_fill(const mlh_ctx *ctx, P2pDev &d)
 {
     for (int r = 0; r < P2P_MAX_RANKS; ++r) d.peer[r] = static_cast<P2pMailbox *>(ctx->p2p.peer[r]);
     d.n_ranks = ctx->p2p.active ? ctx->n_ranks : 1;
     d.rank = ctx->rank;
     d.counter = static_cast<unsigned long long *>(ctx->p2p.counter);
-    d.err = ctx->p2p.active ? device_error_word(ctx) : nullptr;
+    d.err = ctx->p2p.active ? ctx->h_dev_err.as<int>() : nullptr;
 }
 
 }  // namespace mlh

@@ -543,16 +543,15 @@ static bool gn_defer_applies(const mlh_ctx *ctx, int kind_mask)
 // in the same map: the previous iteration's five bound the search (not with ownership planes: a feature that changes hands between iterations would bring another
 // frame's records). `defer`: one GPU, no per-iteration statistics -- the fit launch of every iteration but the last (or every one, `leave_final`) only leaves its
 // tiles' records, and the next iteration's correspondence launch, whose every workgroup sums and solves for itself (match.hip: knn_features_kernel<.., PRE>), finishes
-// it; the start pose then goes in with iteration 1 as well (iteration 0's pose, the one iteration 1 updates).
+// it. Which iterations the start pose goes in with is the pose plan's rule (solve_plan_host.hpp).
 static MatchArgs gn_iter_args(const mlh_ctx *ctx, const mlh_solver_opts *opts, int mask, int it, int n_iters, const double *pose, bool defer, bool leave_final = false)
 {
     MatchArgs a = args_from_opts(opts, mask, 0);
-    if (it == 0) a.init_pose = pose;
+    if (gn_start_pose_goes_in(it, defer)) a.init_pose = pose;
     a.warm = it >= 1 && ctx->knn_warm && !ctx->shard_lo && !ctx->shard_hi;
     a.finish = TAIL_GN;
     if (defer) {
         a.gn_iter = it; a.gn_iters = n_iters;
-        if (it == 1) a.init_pose = pose;
         if (it < n_iters - 1 || leave_final) a.finish = TAIL_RECORDS;
     }
     return a;
@@ -622,20 +621,19 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
     if (!mask) return fail(ctx, MLH_ERR_STATE, "no map/features staged");
     slot->kind = mlh_ctx::SolveSlot::GN;
     const bool defer = n_iters >= 2 && gn_defer_applies(ctx, mask);
-    // The previous solve may have left its LAST iteration as tile records (gn_pending). A chained, deferred solve completes it in its own first launch -- unless this
+    // The previous solve may have left its LAST iteration as tile records (GnChain::pending). A chained, deferred solve completes it in its own first launch -- unless this
     // frame needs a larger record buffer (the records would not survive the reallocation); everything else completes it now, before the chain launch reads the pose.
     // A predecessor that left wavefront rows (a fused last iteration) needs a successor whose first launch reads rows (the planner says) and whose own rows fit the
     // buffer the pending set lies in.
-    const bool rows_ok = ctx->gn_pending.recs.rows != 4 || (gn_first_launch_takes_rows(ctx, mask) && gn_rows_bytes(feature_tiles(ctx, mask)) <= ctx->gn_rows.cap);
-    const bool consume = !pose_in && defer && ctx->gn_pending.active && sizeof(double) * NE_STRIDE * size_t(feature_tiles(ctx, mask)) <= ctx->partials.cap && rows_ok;
-    const mlh_ctx::GnPending pend = ctx->gn_pending;
+    const mlh_ctx::GnPending pend = ctx->gn.pending;
+    const bool rows_ok = pend.recs.rows != 4 || (gn_first_launch_takes_rows(ctx, mask) && ctx->gn.rows_hold(feature_tiles(ctx, mask)));
+    const bool consume = !pose_in && defer && pend.active && sizeof(double) * NE_STRIDE * size_t(feature_tiles(ctx, mask)) <= ctx->partials.cap && rows_ok;
     ctx->gn_fused_launches = 0;
-    if (ctx->gn_pending.active && !consume && (rc = gn_flush_pending(ctx))) return rc;
+    if (!consume && (rc = gn_flush_pending(ctx))) return rc;
     if (!pose_in && !consume && (rc = enqueue_chain_pose(ctx, wodom_prev, wodom_cur, nullptr))) return rc;
     // this solve's own last iteration: left to a successor (or to mlh_gn_solve_end) when the schedule says so
     const bool leave_final = defer && ctx->gn_final_defer;
-    const int base = ctx->gn_slot_base;
-    ctx->gn_slot_base ^= 2;
+    const int base = ctx->gn.solve_begins();
     for (int it = 0; it < n_iters; ++it) {
         // (pose_in is null when chained: the kernels read the state's pose, or compute it: `consume`)
         MatchArgs a = gn_iter_args(ctx, opts, mask, it, n_iters, pose_in, defer, leave_final);
@@ -649,17 +647,9 @@ static int gn_solve_submit(mlh_ctx *ctx, const double *pose_in, const double *wo
             a.publish_seq = seq;
         }
         if ((rc = match_launch(ctx, a))) return rc;
-        if (it == 0 && consume) ctx->gn_pending.active = false;       // consumed by the launch just enqueued
+        if (it == 0 && consume) ctx->gn.take_pending();       // consumed by the launch just enqueued
     }
-    if (leave_final) {
-        ctx->gn_pending.active = true;
-        ctx->gn_pending.recs = ctx->gn_last;         // (tile records in `partials`, or a fused last iteration's set of wavefront rows)
-        ctx->gn_pending.slot = base + ((n_iters - 1) & 1);
-        ctx->gn_pending.thre = opts->map_eig_thre;
-        ctx->gn_pending.freeze = 0;
-        ctx->gn_pending.rec = rec;
-        ctx->gn_pending.seq = seq;
-    }
+    if (leave_final) ctx->gn.solve_left_last(base, n_iters, opts->map_eig_thre, rec, seq);      // (tile records in `partials`, or a fused last iteration's set of wavefront rows)
     ctx->solves.commit(seq, ctx->map_set_cur);
     return MLH_OK;
 }
@@ -683,7 +673,7 @@ int mlh_gn_solve_end(mlh_ctx *ctx, double pose_out[7])
     if (!ctx->solves.pending()) return fail(ctx, MLH_ERR_STATE, "no solve in flight (mlh_gn_solve_begin)");
     const unsigned long long seq = ctx->solves.oldest();
     if (ctx->solves.slot[seq & 1].kind != mlh_ctx::SolveSlot::GN) return fail(ctx, MLH_ERR_STATE, "the oldest solve in flight was submitted with mlh_scan2map_begin: collect it with mlh_scan2map_end");
-    if (ctx->gn_pending.active && ctx->gn_pending.seq == seq) {      // nobody chained a successor behind it: its last iteration is completed here
+    if (ctx->gn.pending.active && ctx->gn.pending.seq == seq) {      // nobody chained a successor behind it: its last iteration is completed here
         const int frc = gn_flush_pending(ctx);
         if (frc) return frc;
     }

@@ -23,19 +23,16 @@ struct MatchArgs {
     double eig_thre[8] = {100, 100, 100, 100, 100, 100, 100, 100};
     int freeze[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const double *init_pose = nullptr;       // host: block 0's pose for this launch comes from the kernel arguments and is written to the state by the finish
-    // Gauss-Newton with the finish done by the consumer: this launch pair is iteration `gn_iter` of `gn_iters` (>= 2). The fit kernel of every iteration but
-    // the last only leaves its tiles' partial records; the correspondence kernel of iteration i >= 1 starts by summing them (every workgroup, same order, same
-    // bits) and running the 6 x 6 solve + Plus itself. gn_iter < 0: the classic form (the fit kernel's last-arriving workgroup finishes).
+    // Gauss-Newton with the finish done by the consumer: this launch pair is iteration `gn_iter` of `gn_iters` (>= 2). The fit kernel of every iteration but the last
+    // only leaves its tiles' records; the correspondence kernel of the next iteration -- or of a CHAINED successor's iteration 0, pre_final -- starts by completing it
+    // (every workgroup, same order, same bits). gn_iter < 0: the classic form (the fit kernel's last-arriving workgroup finishes). Where each launch's poses are
+    // read and written follows from these fields alone: solve_plan_host.hpp, pose_plan.
     int gn_iter = -1, gn_iters = 0;
-    int gn_slot_base = 0;     // this solve's pair of SolverState::xi slots (0 or 2)
-    bool gn_blocks = false;   // the solve runs over pose blocks: per-block iteration poses in SolverState::xib
+    int gn_slot_base = 0;     // this solve's pair of SolverState::xi slots (mlh_ctx::GnChain::solve_begins)
+    bool gn_blocks = false;   // the solve runs over pose blocks
     bool warm = false;   // the neighbour records of the previous iteration (same features, same map) bound this iteration's search
-    // iteration 0 of a CHAINED solve that also completes the PREVIOUS solve, whose last iteration left only its tiles' records (mlh_ctx::gn_pending): every workgroup of
-    // this correspondence launch sums them, solves, applies Plus -> the previous frame's final pose; tile 0's workgroup publishes it to that solve's host record and
-    // stores it as the state's pose; then the chained start pose of THIS frame (transformUpdate + transformAssociateToMap) is computed from it, in every workgroup
-    // pre_final: that solve's pending record, as gn_solve_submit copied it before the solve's own launches overwrite mlh_ctx::gn_pending -- where its records are, its
-    // last pose slot, threshold, host record and sequence number. Set for EVERY iteration of the completing solve (iterations >= 1 find pose 0 in its slot, not in
-    // the state); read by iteration 0.
+    // the predecessor's pending record, as gn_solve_submit copied it (mlh_ctx::GnChain::pending) -- where its records are, its last pose slot, threshold, host record
+    // and sequence number. Set for EVERY iteration of the completing solve; iteration 0 publishes that solve's pose and chains this frame's start pose from it
     const mlh_ctx::GnPending *pre_final = nullptr;
     const double *chain_prev = nullptr, *chain_cur = nullptr;   // host: the two odometry poses of the chain (7 doubles each)
     LmConsumer lmc = LMC_NONE;
@@ -50,10 +47,9 @@ struct MatchArgs {
 };
 int match_launch(mlh_ctx *ctx, const MatchArgs &a);
 bool gn_first_launch_takes_rows(const mlh_ctx *ctx, int kind_mask);   // the planner's answer: iteration 0 of a deferred solve over these kinds that completes its predecessor can read that solve's wavefront rows
-size_t gn_rows_bytes(int tiles256);                            // what mlh_ctx::gn_rows has to hold for a frame of that many 256-feature tiles
 int linearize_launch(mlh_ctx *ctx, const MatchArgs &a);
 int lm_consume_launch(mlh_ctx *ctx, const MatchArgs &a);
-bool loop_fit_fusable(const MatchArgs &loop_args);   // the loop launch described by these arguments would exchange tagged records (ctx.hpp: loop_tagged_arm's conditions)
+bool loop_fit_fusable(const MatchArgs &loop_args);   // the loop launch described by these arguments can carry its fit (tagged records, one block, no dense rows)
 
 // solve_host.hip
 int ensure_state(mlh_ctx *ctx, int n_stats);

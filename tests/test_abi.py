@@ -473,6 +473,28 @@ def test_stored_cloud_builder_and_loop_gate_have_one_owner(mla):
                 assert len(body) <= 3 and "loop_process_gate(ctx, entry)" in body[0] and "pending" not in m.group(1), (f, name, body)
 
 
+def test_solver_chain_state_has_one_owner(mla):
+    """What one solver launch leaves for the next is two structs of the context (csrc/ctx.hpp: GnChain, LmChain) whose transitions are methods; the loose members
+    they replaced are gone; only the launchers (match.hip) and the solves' host (solve_host.hip) reach into them, and neither writes a member itself; the slot
+    arithmetic of the iteration poses is written in the plan's header alone."""
+    csrc = os.path.join(os.path.dirname(os.path.abspath(mla.__file__)), "csrc")
+    text = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp", ".inc"))}
+    assert len(text) >= 20
+    for gone in ("gn_pending", "gn_last", "gn_rows", "gn_rows_set", "lm_pp", "lmc_count", "loop_launch_seq", "loop_tagged_arm", "ctx->gn_slot_base", "ctx->loop_tagged", "LM_LOOP_KERNELS"):
+        assert not [f for f, t in text.items() if re.search(r"\b" + gone + r"\b", t)], gone
+    assert "struct GnChain" in text["ctx.hpp"] and "struct LmChain" in text["ctx.hpp"]
+    reach = re.compile(r"->gn\.|->lm\.|\bGnChain\b|\bLmChain\b")
+    assert [f for f, t in text.items() if f.endswith(".hip") and reach.search(t)] == ["match.hip", "solve_host.hip"]
+    assert [f for f, t in text.items() if f != "ctx.hpp" and f.endswith((".hpp", ".inc")) and re.search(r"->gn\.|->lm\.", t)] == []
+    writes = re.compile(r"->(?:gn|lm)\.[\w.]+\s*(?:=[^=]|[-+^|&]=|\+\+|--)|(?:\+\+|--)\s*ctx->(?:gn|lm)\.")
+    for f in ("match.hip", "solve_host.hip"):
+        assert not writes.search(text[f]), (f, writes.search(text[f]).group(0))
+    # the slot rule: xi / xib are indexed where a slot becomes a pointer (match.hip: pose_slot_ptr), the base is turned over in the plan's header
+    assert [f for f, t in text.items() if re.search(r"->xib?\[", t)] == ["match.hip"]
+    assert len(re.findall(r"->xib?\[", text["match.hip"])) == 2
+    assert [f for f, t in text.items() if re.search(r"slot_base\s*\^|\^=\s*2\b", t)] == ["solve_plan_host.hpp"]
+
+
 def test_entry_points_sit_beside_their_kernels(mla):
     """csrc/capi.hip holds what belongs to the context itself and defines no kernel; every subsystem's entry points are defined once, in the unit that owns the
     state they touch; the forwarding twins of the odometry / prior / calibration entry points are gone; the fused clouds are one struct that only its owner

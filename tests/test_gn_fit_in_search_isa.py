@@ -9,7 +9,8 @@ The instantiations the host can launch (match_plan_host.hpp: the fused entries o
 -- a workgroup has to hold whole wavefront rows, 64 queries or more, of every kind --, each as PRE 1 warm, PRE 1 cold and PRE 2.
 
 And the code object holds the correspondence kernels of the planner's list of forms (match_plan_host.hpp: MLH_KNN_FORMS), all of them and no other: the list is
-printed by the planner's stand-alone program (tests/host/match_plan_main.cpp, `forms`).
+printed by the planner's stand-alone program (tests/host/match_plan_main.cpp, `forms`). The same for the 15 linearise / consumer / loop kernels of
+solve_plan_host.hpp's MLH_LM_FORMS (tests/host/solve_plan_main.cpp, `forms`).
 """
 import importlib
 import os
@@ -66,4 +67,27 @@ def test_the_correspondence_kernels_are_the_planners_list_of_forms(descriptors, 
             listed.add(f"_ZN3mlh24knn_features_wide_kernelILi{w}ELi{g}ELi{pre}ELb{warm}ELb{fit}EEEvNS_7KParamsE")
     built = {k for k in descriptors if "knn_features_kernel" in k or "knn_features_wide_kernel" in k}
     assert len(listed) == len(out.splitlines()) == 68, len(listed)
+    assert built - listed == set() and listed - built == set(), (sorted(built - listed), sorted(listed - built))
+
+
+def test_the_linearise_and_lm_kernels_are_the_planners_list_of_forms(descriptors, tmp_path):
+    """... and the 15 linearise / consumer / loop kernels of solve_plan_host.hpp's MLH_LM_FORMS (tests/host/solve_plan_main.cpp, `forms`: "family A B C"), all of them
+    and no other: linearize_kernel<LM, COV>, lm_consume_kernel<FIRST, COV>, lm_loop_kernel<DEVM, FIT, COV>"""
+    exe = tmp_path / "solve_plan_main"
+    subprocess.run(["g++", "-O1", "-std=c++17", "-I", os.path.join(ROOT, "m-loam_amd", "csrc"), os.path.join(ROOT, "tests", "host", "solve_plan_main.cpp"), "-o", str(exe)], check=True)
+    out = subprocess.run([str(exe), "forms"], check=True, capture_output=True, text=True, timeout=60).stdout
+    listed = set()
+    for line in out.splitlines():
+        fam, a, b, c = (int(v) for v in line.split())
+        if fam == 0:
+            assert not c, line
+            listed.add(f"_ZN3mlh16linearize_kernelILb{a}ELb{b}EEEvNS_7KParamsE")
+        elif fam == 1:
+            assert not c, line
+            listed.add(f"_ZN3mlh17lm_consume_kernelILb{a}ELb{b}EEEvNS_7KParamsE")
+        else:
+            assert fam == 2, line
+            listed.add(f"_ZN3mlh14lm_loop_kernelILb{a}ELb{b}ELb{c}EEEvNS_7KParamsE")
+    built = {k for k in descriptors if k.startswith(("_ZN3mlh16linearize_kernel", "_ZN3mlh17lm_consume_kernel", "_ZN3mlh14lm_loop_kernel"))}
+    assert len(listed) == len(out.splitlines()) == 15, len(listed)
     assert built - listed == set() and listed - built == set(), (sorted(built - listed), sorted(listed - built))
