@@ -206,11 +206,34 @@ int mlh_downsample_current_scan(mlh_ctx *ctx, int kind, const void *points, int 
 /* The same for both feature kinds in one call (the mapper thins the surf and the corner cloud back to back, cpp:359-368). When both
  * clouds are the context's fused clouds (mlh_fused_cloud) they run through ONE thinning pipeline -- half the dependent launches, one
  * host round trip; other inputs take the two single calls. Records of both clouds share stride / intensity offset / memory kind;
- * afterwards both feature sets are staged exactly as two single calls leave them. */
+ * afterwards both feature sets are staged exactly as two single calls leave them. A gate that keeps nothing of a kind (every trace above
+ * trace_threshold) is no error of the thinning, in any form: the kind's count comes back 0 and its feature set is staged empty; the solver
+ * calls then answer as they do for a kind that was never staged (MLH_ERR_STATE). */
 int mlh_downsample_current_scan_pair(mlh_ctx *ctx, const void *surf_points, int n_surf, const void *corner_points, int n_corner, int stride_bytes,
                                      int intensity_offset_bytes, int mem, float leaf_surf, float leaf_corner, const double *ext_poses,
                                      const double *ext_covs, int n_lidar, const double cov_measurement[9], int with_ua, double trace_threshold,
                                      int32_t *n_surf_features, int32_t *n_corner_features);
+/* The staged feature set of `kind` as the solver will read it (whatever staged it: mlh_features_set, mlh_features_copy, the thinning calls, mlh_downsample_
+ * scan2map), read only: *n records of 7 floats [x y z intensity cxx cyy czz] -- the point, the LiDAR index the thinning left with it (0 from mlh_features_set,
+ * which stages none), and the diagonal of its cov_vec that the factors' weight is made from (zeros for a set staged without covariance) -- copied to out (HOST,
+ * room for `capacity` records; may be NULL when capacity is 0). *n is always set.
+ * MLH_ERR_INVALID when capacity < *n (nothing is copied; call again with room for *n), MLH_ERR_UNSUPPORTED for a set staged in several pose blocks
+ * (mlh_features_set_block: their padding slots are not this call's business). Waits for the context's stream, as the other fetches do. */
+int mlh_features_fetch(mlh_ctx *ctx, int kind, float *out, int capacity, int32_t *n);
+/* Which form the most recent mlh_downsample_current_scan_pair or mlh_downsample_scan2map took to thin its two clouds (every form stages the same bits; the
+ * forms differ in launches and host round trips). Noted on the host where the decision is made: the calls themselves launch, copy and wait as before. */
+enum {
+    MLH_THIN_NONE = 0,           /* no such call yet, or the most recent one was refused before it chose */
+    MLH_THIN_SORT_FIRST = 1,     /* both fused clouds through one pipeline, voxel keys made inside the std::sort launch (up to 4 LiDARs, the default member order) */
+    MLH_THIN_SHARED_GRID = 2,    /* both fused clouds through one pipeline over a shared occupancy grid */
+    MLH_THIN_SINGLE_CALLS = 3    /* mlh_downsample_current_scan once per kind (inputs that are not the context's fused clouds, grids too large to share) */
+};
+typedef struct mlh_thin_info_t {
+    int32_t path;                /* MLH_THIN_* */
+    int32_t n_in[2];             /* the call's input records: surf, corner */
+    int32_t reserved;
+} mlh_thin_info_t;
+int mlh_thin_info(mlh_ctx *ctx, mlh_thin_info_t *out);
 
 /* ---------------------------------------------------------------- (f1) covariance-aware voxel thinning
  * replaces pcl::VoxelGridCovarianceMLOAM<PointT>::filter (mloam_pcl/include/mloam_pcl/voxel_grid_covariance_mloam_impl.hpp:68-457),

@@ -26,6 +26,7 @@ FLAG_CHECK_FOV, FLAG_WITH_UA, FLAG_NO_LOSS, FLAG_POSE_COV = 1, 2, 4, 8
 GF_METHODS = {"wo_gf": 0, "rnd": 1, "fps": 2, "gd_fix": 3, "gd_float": 4}
 K_KNN, K_FIT, K_LINEARIZE, K_SOLVE, K_GRID_BUILD, K_EXTRACT, K_ALLREDUCE, K_KNN_PRE, K_KNN_FIRST = range(9)
 K_ALL = 0x1FF
+THIN_NONE, THIN_SORT_FIRST, THIN_SHARED_GRID, THIN_SINGLE_CALLS = range(4)
 
 
 class MlhError(RuntimeError):
@@ -349,6 +350,11 @@ class DeviceInfo(C.Structure):
                     loop_fallbacks=int(self.loop_fallbacks), scan_uploads_from_ahead=int(self.scan_uploads_from_ahead))
 
 
+class ThinInfo(C.Structure):
+    """mlh_thin_info_t (include/mloam_hip.h)."""
+    _fields_ = [("path", C.c_int32), ("n_in", C.c_int32 * 2), ("reserved", C.c_int32)]
+
+
 _lib = None
 
 
@@ -426,6 +432,8 @@ def load_library():
     lib.mlh_track_set_from_scan.argtypes = [vp, ci, cf]
     lib.mlh_downsample_current_scan_pair.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, cf, cf, vp, vp, ci, vp, ci, C.c_double, vp, vp]
     lib.mlh_downsample_scan2map.argtypes = [vp, vp, ci, vp, ci, ci, ci, ci, cf, cf, vp, vp, ci, vp, ci, C.c_double, vp, vp, vp, vp]
+    lib.mlh_features_fetch.argtypes = [vp, ci, vp, ci, C.POINTER(C.c_int32)]
+    lib.mlh_thin_info.argtypes = [vp, C.POINTER(ThinInfo)]
     lib.mlh_voxel_grid.argtypes = [vp, vp, ci, ci, ci, cf, vp, vp, ci]
     lib.mlh_transform_point_cloud.argtypes = [vp, vp, ci, ci, vp, ci]
     lib.mlh_transform_to_end.argtypes = [vp, vp, ci, ci, ci, vp, ci, cf, ci]
@@ -557,7 +565,7 @@ EXPORTED_SYMBOLS = [
     "mlh_comm_finalize", "mlh_profile_enable", "mlh_profile_sample", "mlh_profile_reset", "mlh_profile_get",
     "mlh_segment_params_default", "mlh_segment_cloud", "mlh_scan_upload", "mlh_scan_upload_ahead", "mlh_extract_run", "mlh_extract_fetch", "mlh_extract_voxel_run", "mlh_extract_fetch_voxel",
     "mlh_point_uncertainty", "mlh_downsample_current_scan", "mlh_voxel_filter", "mlh_pure_odom_set", "mlh_pure_odom_evaluate", "mlh_pure_odom_normal_eq", "mlh_track_opts_default", "mlh_track_set_prev", "mlh_track_set_cur",
-    "mlh_track_set_from_scan", "mlh_downsample_current_scan_pair", "mlh_downsample_scan2map", "mlh_voxel_grid", "mlh_transform_point_cloud", "mlh_transform_to_end", "mlh_scan_undistort", "mlh_fuse_reset", "mlh_fuse_add_scan", "mlh_fuse_add_scan_from", "mlh_fuse_add_rings", "mlh_fused_cloud", "mlh_track_match", "mlh_track_cloud", "mlh_cloud_uct_associate_to_map", "mlh_compound_pose_with_cov",
+    "mlh_track_set_from_scan", "mlh_downsample_current_scan_pair", "mlh_downsample_scan2map", "mlh_features_fetch", "mlh_thin_info", "mlh_voxel_grid", "mlh_transform_point_cloud", "mlh_transform_to_end", "mlh_scan_undistort", "mlh_fuse_reset", "mlh_fuse_add_scan", "mlh_fuse_add_scan_from", "mlh_fuse_add_rings", "mlh_fused_cloud", "mlh_track_match", "mlh_track_cloud", "mlh_cloud_uct_associate_to_map", "mlh_compound_pose_with_cov",
     "mlh_map_set", "mlh_map_set_pair", "mlh_map_set_pair_overlapped", "mlh_map_rebuild", "mlh_map_info", "mlh_set_voxel_member_order", "mlh_debug_bad_launch", "mlh_set_extract_tie_order", "mlh_set_gn_schedule", "mlh_std_sort_permutation", "mlh_pure_odom_begin", "mlh_pure_odom_add_matches", "mlh_pure_odom_add_matches_gf", "mlh_pure_odom_gn_solve", "mlh_knn", "mlh_features_set", "mlh_features_set_block", "mlh_gn_solve_blocks",
     "mlh_match_linearize", "mlh_match_coeffs", "mlh_match_neighbours", "mlh_linearize", "mlh_good_feature_matching", "mlh_solver_opts_default", "mlh_gn_solve", "mlh_gn_solve_begin", "mlh_gn_solve_begin_chained", "mlh_gn_solve_end", "mlh_features_copy", "mlh_scan2map", "mlh_scan2map_begin", "mlh_scan2map_begin_chained", "mlh_scan2map_end", "mlh_scan2map_cov",
     "mlh_shard_set", "mlh_shard_set_features", "mlh_comm_unique_id", "mlh_comm_init", "mlh_p2p_mailbox", "mlh_p2p_comm_init", "mlh_allreduce_f64",
@@ -1345,6 +1353,25 @@ class Context:
         self._m = getattr(self, "_m", {})
         self._m[SURF], self._m[CORNER] = a.value, b.value
         return x, (a.value, b.value)
+
+    def features_fetch(self, kind) -> np.ndarray:
+        """the staged feature set of `kind` as the solver will read it -> (n, 7) f32 [x y z intensity cxx cyy czz] (mlh_features_fetch)"""
+        n = C.c_int32(0)
+        rc = self.lib.mlh_features_fetch(self.h, kind, None, 0, C.byref(n))       # the count first: a set with records answers a capacity of 0 with "invalid"
+        if rc != 0 and not (rc == -1 and n.value > 0):
+            self._ck(rc)
+        out = np.zeros((n.value, 7), np.float32)
+        if n.value:
+            self._ck(self.lib.mlh_features_fetch(self.h, kind, _p(out), n.value, C.byref(n)))
+        return out
+
+    THIN_PATH_NAMES = ("none", "sort-first", "shared-grid", "single-calls")
+
+    def thin_info(self) -> dict:
+        """the form the most recent downsample_current_scan_pair / downsample_scan2map took -> dict(path, n_in) (mlh_thin_info)"""
+        t = ThinInfo()
+        self._ck(self.lib.mlh_thin_info(self.h, C.byref(t)))
+        return dict(path=self.THIN_PATH_NAMES[t.path], n_in=(int(t.n_in[0]), int(t.n_in[1])))
 
     def cloud_uct_associate_to_map(self, points11, pose_global, cov_global, ext, ext_cov, cov_meas, with_ua, trace_threshold):
         """cloudUCTAssociateToMap on (n, 11) records [x y z i cov6 trace] -> kept, transformed records in input order."""

@@ -797,7 +797,12 @@ struct mlh_ctx {
     const int *thin_counts_host = nullptr;
     const unsigned long long *thin_seq_host = nullptr;
     unsigned long long thin_seq = 0;
-    mlh::PinnedBuf h_scratch;   // one ScratchBlock: the landing place of the few-int read-backs (record counts) that end a staging call
+    // the form the most recent mlh_downsample_current_scan_pair / mlh_downsample_scan2map took (mlh_thin_info): host words, stored where the decision is made
+    struct ThinNote {
+        int path = MLH_THIN_NONE, n_in[2] = {0, 0};
+        void begin(int n_surf, int n_corner) { path = MLH_THIN_NONE; n_in[0] = n_surf; n_in[1] = n_corner; }
+    } thin_note;
+    mlh::PinnedBuf h_scratch;  // one ScratchBlock: the landing place of the few-int read-backs (record counts) that end a staging call
     int knn_lanes_override = 0;   // MLH_KNN_LANES=8|16|32, or SSCC (816, 832, 1632: surf lanes, corner lanes), in the environment at mlh_create: pins the correspondence kernel's lanes per query (tests, tuning)
     int knn_wg_override = 0;      // MLH_KNN_WG_THREADS=256|512|1024, in the environment at mlh_create: pins the workgroup width of the correspondence launches that have wide forms (match_plan_host.hpp: knn_plan_width; tests, A/B runs)
     int knn_wg_last = 0;          // the width the last such launch took

@@ -325,6 +325,40 @@ int mlh_features_copy(mlh_ctx *dst, mlh_ctx *src, int kind)
     return MLH_OK;
 }
 
+// The staged feature set of `kind`, read only (include/mloam_hip.h): FeatSet::pts and the diagonal FeatSet::covd side by side, 7 floats per record
+int mlh_features_fetch(mlh_ctx *ctx, int kind, float *out, int capacity, int32_t *n)
+{
+    if (n) *n = 0;
+    if (!ctx || kind < 0 || kind > 1 || !n) return MLH_ERR_INVALID;
+    const FeatSet &f = ctx->feat[kind];
+    *n = f.m;
+    if (f.m > 0 && f.n_blocks > 1) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_features_fetch: the set was staged in several pose blocks");
+    if (capacity < f.m || (f.m > 0 && !out)) return fail(ctx, MLH_ERR_INVALID, "mlh_features_fetch: room for fewer records than are staged");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    const size_t m = size_t(f.m > 0 ? f.m : 0);
+    std::vector<float4> h(2 * m);
+    if (m > 0) {
+        MLH_HIP(ctx, hipMemcpyAsync(h.data(), f.pts.p, sizeof(float4) * m, hipMemcpyDeviceToHost, ctx->stream));
+        if (f.has_cov) MLH_HIP(ctx, hipMemcpyAsync(h.data() + m, f.covd.p, sizeof(float4) * m, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    for (size_t i = 0; i < m; ++i) {
+        float *o = out + 7 * i;
+        const float4 p = h[i], c = f.has_cov ? h[m + i] : make_float4(0.f, 0.f, 0.f, 0.f);
+        o[0] = p.x; o[1] = p.y; o[2] = p.z; o[3] = p.w; o[4] = c.x; o[5] = c.y; o[6] = c.z;
+    }
+    return MLH_OK;
+}
+
+int mlh_thin_info(mlh_ctx *ctx, mlh_thin_info_t *out)
+{
+    if (!ctx || !out) return MLH_ERR_INVALID;
+    out->path = ctx->thin_note.path;
+    out->n_in[0] = ctx->thin_note.n_in[0]; out->n_in[1] = ctx->thin_note.n_in[1];
+    out->reserved = 0;
+    return MLH_OK;
+}
+
 // are these records this context's own fused cloud of `kind` (mlh_fused_cloud: device float4 records whose exact bounding box is known)?
 static bool is_fused_cloud(const mlh_ctx *ctx, int kind, const void *points, int n, int stride_bytes, int mem)
 {
@@ -380,6 +414,7 @@ int mlh_downsample_current_scan_pair(mlh_ctx *ctx, const void *surf_points, int 
 {
     if (ctx) ++ctx->stage_epoch;
     if (!ctx || !n_surf_features || !n_corner_features) return MLH_ERR_INVALID;
+    ctx->thin_note.begin(n_surf, n_corner);
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     const bool fused_pair = is_fused_pair(ctx, surf_points, n_surf, corner_points, n_corner, stride_bytes, intensity_offset_bytes, mem);
     if (fused_pair) {
@@ -396,6 +431,7 @@ int mlh_downsample_current_scan_pair(mlh_ctx *ctx, const void *surf_points, int 
         }
         if (rc != MLH_ERR_UNSUPPORTED) return rc;            // a grid too large for the shared index space: one by one below
     }
+    ctx->thin_note.path = MLH_THIN_SINGLE_CALLS;
     int rc = mlh_downsample_current_scan(ctx, MLH_SURF, surf_points, stride_bytes, n_surf, intensity_offset_bytes, mem, leaf_surf, ext_poses, ext_covs, n_lidar,
                                          cov_measurement, with_ua, trace_threshold, nullptr, n_surf_features);
     if (rc) return rc;
@@ -1160,6 +1196,7 @@ int mlh_downsample_scan2map(mlh_ctx *ctx, const void *surf_points, int n_surf, c
 {
     if (!ctx || !pose_inout || !opts_in || !n_surf_features || !n_corner_features || opts_in->max_outer <= 0) return MLH_ERR_INVALID;
     const mlh_solver_opts opts_v = scan2map_opts(opts_in), *opts = &opts_v;      // (CHECK_FOV does not apply to scan2map: see scan2map_opts)
+    ctx->thin_note.begin(n_surf, n_corner);
     { const int crc = pose_cov_refuse_distributed(ctx, opts); if (crc) return crc; }
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     auto two_calls = [&]() -> int {

@@ -822,6 +822,7 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
         }
         const long long off1 = ((ncell[0] + 31) / 32) * 32;
         if (fits && off1 + ncell[1] <= 2147483647ll - 64) {
+            ctx->thin_note.path = MLH_THIN_SORT_FIRST;
             G.src0 = static_cast<const unsigned char *>(surf); G.src1 = static_cast<const unsigned char *>(corner); G.stride = stride; G.n0 = n_surf;
             G.inv_leaf0 = inv[0]; G.inv_leaf1 = inv[1];
             for (int d = 0; d < 3; ++d) { G.min_b0[d] = min_b[0][d]; G.min_b1[d] = min_b[1][d]; }
@@ -858,6 +859,7 @@ int downsample_current_scan_pair_run(mlh_ctx *ctx, const void *surf, int n_surf,
             return thin_counts_collect(ctx, P, A.counts, defer, n_surf_out, n_corner_out);
         }
     }
+    ctx->thin_note.path = MLH_THIN_SHARED_GRID;
     MLH_HIP(ctx, ctx->uct_buf.ensure(sizeof(double) * size_t(n_lidar) * 43 + sizeof(float) * 6 * size_t(n) + 64));
     double *d_ext = ctx->uct_buf.as<double>();
     double *d_cov = d_ext + size_t(n_lidar) * 7;

@@ -29,6 +29,14 @@ def test_version_and_structs(mla):
     o = mla.default_opts()
     assert (o.min_match_sq_dis, o.min_plane_dis, o.huber_delta, o.map_eig_thre, o.max_outer, o.max_lm_iterations) == (1.0, pytest.approx(0.2), 0.1, 100.0, 2, 30)
     assert ctypes.sizeof(mla.IterStat) == 6 * 4 + 8 * (2 + 6 + 36 + 6 + 7)
+    # mlh_thin_info_t: path, n_in[2], reserved; the paths' names follow the header's enum
+    assert ctypes.sizeof(mla.ThinInfo) == 16 and [f for f, _ in mla.ThinInfo._fields_] == ["path", "n_in", "reserved"]
+    hdr = open(mla.HEADER_PATH).read()
+    for value, name in enumerate(("MLH_THIN_NONE", "MLH_THIN_SORT_FIRST", "MLH_THIN_SHARED_GRID", "MLH_THIN_SINGLE_CALLS")):
+        assert re.search(r"\b%s = %d\b" % (name, value), hdr), name
+    assert (mla.THIN_NONE, mla.THIN_SORT_FIRST, mla.THIN_SHARED_GRID, mla.THIN_SINGLE_CALLS) == (0, 1, 2, 3)
+    assert mla.Context.THIN_PATH_NAMES == ("none", "sort-first", "shared-grid", "single-calls")
+    assert {"mlh_features_fetch", "mlh_thin_info"} <= set(mla.EXPORTED_SYMBOLS)
 
 
 def test_host_helpers_match_oracle(mla, orc):

@@ -1698,8 +1698,9 @@ def test_mapper_inputs_stay_on_device(mla, orc, synth, case16):
         np.testing.assert_array_equal(pose_dev, pose_host)
         # both kinds through ONE thinning pipeline (mlh_downsample_current_scan_pair on the fused clouds) and through the fall-back of
         # two single calls (host buffers): the same feature sets, the same pose
-        for src in ((c.fused_cloud(mla.SURF), c.fused_cloud(mla.CORNER)), (ref[mla.SURF], ref[mla.CORNER])):
+        for src, path in (((c.fused_cloud(mla.SURF), c.fused_cloud(mla.CORNER)), "sort-first"), ((ref[mla.SURF], ref[mla.CORNER]), "single-calls")):
             m_pair = c.downsample_current_scan_pair(src[0], src[1], 0.4, 0.2, ext, covs, meas, True, 0.6)
+            assert c.thin_info()["path"] == path          # which form ran: the comparisons below are between two forms, not one form with itself
             assert list(m_pair) == m_dev
             a = c.match_linearize(mla.SURF, case16["p0"], flags=mla.FLAG_WITH_UA)
             b = c.match_linearize(mla.CORNER, case16["p0"], flags=mla.FLAG_WITH_UA)
