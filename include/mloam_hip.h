@@ -638,8 +638,9 @@ int mlh_loop_register(mlh_ctx *ctx, const double *T_ini, const mlh_loop_opts *op
  * (app.cpp:324-390), AdvancedMatching (113-320), OptimizePairwise (392-505), GetOutputTrans (519-534). Cloud 0 is the MODEL surf cloud (laser_map, pointcloud_[0]),
  * cloud 1 the DATA surf cloud (laser_cloud); T maps data into the model frame. The clouds are read where mlh_loop_build_clouds / mlh_loop_set_clouds left them
  * (`which` = MLH_LOOP_MODEL_SURF or MLH_LOOP_DATA_SURF everywhere below); no cloud crosses the bus: what leaves HBM is the mutual pairs' records (two indices and
- * two normalised points each) and a few scalars. On the device: normals, SPFH, FPFH, NormalizePoints, the 33-dimensional matching and the gather; on the host, in
- * csrc/fgr_host.hpp: the tuple test and OptimizePairwise (bounded by 3 tuple_max_cnt correspondences) and GetOutputTrans. The per-pair, per-bin, eigen33 and distance
+ * two normalised points each) and a few scalars -- from mlh_fgr_register_device one 136-byte record. On the device: normals, SPFH, FPFH, NormalizePoints, the
+ * 33-dimensional matching and the gather; on the host (mlh_fgr_register), in csrc/fgr_host.hpp: the tuple test and OptimizePairwise (bounded by 3 tuple_max_cnt
+ * correspondences; mlh_fgr_register_device runs both on the device, from the same header's functions) and GetOutputTrans. The per-pair, per-bin, eigen33 and distance
  * arithmetic lives once, in fgr_host.hpp, for the kernels, the host tail and the tests' restatement. PCL and FLANN are not available to this project: what
  * fgr_host.hpp restates of PCL 1.8.0 (computeMeanAndCovarianceMatrix, eigen33 / computeRoots, solvePlaneParameters, flipNormalTowardsViewpoint, computePairFeatures,
  * computePointSPFHSignature, weightPointSPFHSignature) and of FLANN (the L2 functor, RadiusResultSet's strict comparison) is restated from memory of those
@@ -692,6 +693,23 @@ int mlh_loop_register(mlh_ctx *ctx, const double *T_ini, const mlh_loop_opts *op
  *   accepted = 0. Otherwise accepted = cost <= global_registration_threshold (cpp:92). CHOSEN: an empty cloud has mean 0 (the reference divides 0 by 0, then reads
  *   data[0] of an empty feature set): no pairs, T = GetOutputTrans of the identity. Host waits: per cloud whose features are computed 1 (the bounds); 1 for the
  *   normalisation scalars, the pair count and the records.
+ * mlh_fgr_register_device = mlh_fgr_register with the tail ON THE DEVICE: same contract, options, validation, gates and result struct. Behind the match, on the
+ *   context's stream and with no host wait in between, four launches read the pair count where the cross check left it: the tuple test as independent trials
+ *   (the generator of fgr_host.hpp is xorshift64*, a linear map over GF(2): the state in front of draw k is A^k s0, reached through a table of A^(2^b); trial t
+ *   uses draws 3 t .. 3 t + 2 whatever earlier trials decided) -- a count per segment of FGR_TT_RUN x FGR_TT_TPB trials, one exclusive prefix, then an ordered
+ *   emit of the accepted trials of rank < tuple_max_cnt: exactly the tuples of the sequential loop, in its order, and its n_trials -- and OptimizePairwise in one
+ *   workgroup (the working q in registers up to FGR_OPT_REG_MAX correspondences, in HBM beyond). No pair record leaves HBM: one 136-byte record (the scalars, the
+ *   counts, trans, the two costs) comes back, then one wait; GetOutputTrans and `accepted` are host code on that record. host_waits = 1 with the features reused.
+ *   EQUAL to mlh_fgr_register: swapped, n_mutual, n_tuples, n_corres, n_trials, the tuples themselves, global_scale, start_scale, means. NOT bit-equal: the 28 f64
+ *   sums of an OptimizePairwise iteration run in another order (each of 256 threads its correspondences t, t + 256, .. in index order, a butterfly per wavefront,
+ *   the four wavefronts in order; the host sums sequentially) and sin / cos / sqrt are the device's; every iteration rounds delta to f32, which absorbs nearly all of
+ *   it: T_relative within 1e-6, the costs within 1e-9 relative. Two runs, and two contexts, give the same bits.
+ * mlh_fgr_tail_tuple_test / mlh_fgr_tail_optimize (test and diagnosis entries): host records pq [n x 6] = (p, q) of normalised points are staged as the pairs
+ *   0 .. n - 1 and exactly the kernels of mlh_fgr_register_device run on them. tuple_test: corres_out [3 x n_tuples] <- indices into the records, *n_trials as
+ *   mlh_fgr_result::n_trials; capacity_tuples must be at least min(tuple_max_cnt, 100 n), the most tuples the call can return (MLH_ERR_INVALID otherwise: nothing
+ *   is truncated). optimize: every record is one correspondence, in its order; start_scale = StartScale (finite, > 0); trans [16] f32 row-major (TransOutput_),
+ *   cost = {final_cost, final_cost_normalize}, *optimised = 0 with fewer than 10 records (identity, NaN costs). MLH_ERR_INVALID for bad options, n < 0 or a NULL
+ *   output; they overwrite the pairs of the last match. A refused call changes nothing.
  * mlh_fgr_info: sizes, validity, allocations, launches of the last f13 call, bytes held. */
 enum { MLH_FGR_NORMALS = 0, MLH_FGR_SPFH = 1, MLH_FGR_FPFH = 2 };
 typedef struct mlh_fgr_opts {
@@ -736,6 +754,10 @@ int mlh_fgr_set_spfh(mlh_ctx *ctx, int which, int32_t n, const int32_t *counts, 
 int mlh_fgr_set_features(mlh_ctx *ctx, int which, int32_t n, const float *features);
 int mlh_fgr_match(mlh_ctx *ctx, const mlh_fgr_opts *opts, int32_t *pairs_out, int32_t capacity, int32_t *n_pairs);
 int mlh_fgr_register(mlh_ctx *ctx, const mlh_fgr_opts *opts, mlh_fgr_result *result);
+int mlh_fgr_register_device(mlh_ctx *ctx, const mlh_fgr_opts *opts, mlh_fgr_result *result);
+int mlh_fgr_tail_tuple_test(mlh_ctx *ctx, const float *pq, int32_t n, int32_t swapped, const mlh_fgr_opts *opts, int32_t *corres_out, int32_t capacity_tuples,
+                            int32_t *n_tuples, int32_t *n_trials);
+int mlh_fgr_tail_optimize(mlh_ctx *ctx, const float *pq, int32_t n, double start_scale, const mlh_fgr_opts *opts, float *trans, double *cost, int32_t *optimised);
 int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
 
 /* ---------------------------------------------------------------- (f14) pose-graph optimisation for the loop closure, on the device

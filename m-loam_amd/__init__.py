@@ -506,6 +506,9 @@ def load_library():
     lib.mlh_fgr_set_features.argtypes = [vp, ci, C.c_int32, vp]
     lib.mlh_fgr_match.argtypes = [vp, C.POINTER(FgrOpts), vp, C.c_int32, C.POINTER(C.c_int32)]
     lib.mlh_fgr_register.argtypes = [vp, C.POINTER(FgrOpts), C.POINTER(FgrResult)]
+    lib.mlh_fgr_register_device.argtypes = [vp, C.POINTER(FgrOpts), C.POINTER(FgrResult)]
+    lib.mlh_fgr_tail_tuple_test.argtypes = [vp, vp, C.c_int32, C.c_int32, C.POINTER(FgrOpts), vp, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    lib.mlh_fgr_tail_optimize.argtypes = [vp, vp, C.c_int32, C.c_double, C.POINTER(FgrOpts), vp, vp, C.POINTER(C.c_int32)]
     lib.mlh_fgr_info.argtypes = [vp, C.POINTER(FgrInfo)]
     lib.mlh_pg_opts_default.argtypes = [C.POINTER(PgOpts)]
     lib.mlh_pg_opts_default.restype = None
@@ -581,7 +584,7 @@ EXPORTED_SYMBOLS = [
     "mlh_sc_opts_default", "mlh_sc_reset", "mlh_sc_add", "mlh_sc_add_keyframe", "mlh_sc_detect", "mlh_sc_candidates", "mlh_sc_distance", "mlh_sc_fetch", "mlh_sc_info",
     "mlh_loop_opts_default", "mlh_loop_build_clouds", "mlh_loop_set_clouds", "mlh_loop_cloud", "mlh_loop_info_get", "mlh_loop_match", "mlh_loop_evaluate", "mlh_loop_register",
     "mlh_fgr_opts_default", "mlh_fgr_features", "mlh_fgr_spfh", "mlh_fgr_fpfh", "mlh_fgr_fetch", "mlh_fgr_set_normals", "mlh_fgr_set_spfh", "mlh_fgr_set_features",
-    "mlh_fgr_match", "mlh_fgr_register", "mlh_fgr_info",
+    "mlh_fgr_match", "mlh_fgr_register", "mlh_fgr_register_device", "mlh_fgr_tail_tuple_test", "mlh_fgr_tail_optimize", "mlh_fgr_info",
     "mlh_pg_opts_default", "mlh_pg_reset", "mlh_pg_info", "mlh_pg_add_keyframe", "mlh_pg_set_loop", "mlh_pg_optimize", "mlh_pg_poses", "mlh_pg_device_poses",
     "mlh_pg_linearize", "mlh_pg_solve_step", "mlh_pg_time_stages", "mlh_pg_optimize_forced", "mlh_pg_reserve",
 ]
@@ -1196,6 +1199,31 @@ class Context:
         r = FgrResult()
         self._ck(self.lib.mlh_fgr_register(self.h, C.byref(opts) if opts is not None else None, C.byref(r)))
         return r.as_dict()
+
+    def fgr_register_device(self, opts: FgrOpts = None) -> dict:
+        """fgr_register with the tuple test and OptimizePairwise on the device: the same tuples, one 136-byte record to the host, one wait
+        (mlh_fgr_register_device)"""
+        r = FgrResult()
+        self._ck(self.lib.mlh_fgr_register_device(self.h, C.byref(opts) if opts is not None else None, C.byref(r)))
+        return r.as_dict()
+
+    def fgr_tail_tuple_test(self, pq, swapped=False, opts: FgrOpts = None, capacity_tuples=None):
+        """the device tuple test on host records pq (n, 6) = (p, q) -> ((k, 3) int32 indices into the records, n_trials). capacity_tuples: the rows of the output
+        (default: min(tuple_max_cnt, 100 n), the least the call accepts) (mlh_fgr_tail_tuple_test)"""
+        a = np.ascontiguousarray(pq, np.float32).reshape(-1, 6)
+        o = opts if opts is not None else fgr_opts()
+        cap = min(int(o.tuple_max_cnt), 100 * len(a)) if capacity_tuples is None else int(capacity_tuples)
+        out, k, t = np.zeros((max(cap, 1), 3), np.int32), C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mlh_fgr_tail_tuple_test(self.h, _p(a), len(a), int(bool(swapped)), C.byref(o), _p(out), cap, C.byref(k), C.byref(t)))
+        return out[:k.value].copy(), int(t.value)
+
+    def fgr_tail_optimize(self, pq, start_scale=1.0, opts: FgrOpts = None):
+        """the device OptimizePairwise on host records pq (n, 6), every record one correspondence -> (trans (4, 4) float32, (final_cost, final_cost_normalize),
+        optimised) (mlh_fgr_tail_optimize)"""
+        a = np.ascontiguousarray(pq, np.float32).reshape(-1, 6)
+        trans, cost, ran = np.zeros(16, np.float32), np.zeros(2, np.float64), C.c_int32(0)
+        self._ck(self.lib.mlh_fgr_tail_optimize(self.h, _p(a), len(a), float(start_scale), C.byref(opts) if opts is not None else None, _p(trans), _p(cost), C.byref(ran)))
+        return trans.reshape(4, 4), (float(cost[0]), float(cost[1])), bool(ran.value)
 
     # ---- pose-graph optimisation (PoseGraph::addKeyFrame's bookkeeping, updateLoopInfo, optimizePoseGraph on the device)
     def pg_reset(self):

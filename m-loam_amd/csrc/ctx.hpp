@@ -511,6 +511,10 @@ struct FgrStore {
     bool feat_user[2] = {false, false};      // feat[s] came through mlh_fgr_set_features / set_spfh / set_normals: mlh_fgr_register does not recompute it
     long long allocations = 0;
     int launches = 0, host_waits = 0;        // of the last call
+    // the device tail (mlh_fgr_register_device; fgr.hip): the generator's jump table (uploaded once), the tuple test's per-segment counts and base ranks, the
+    // correspondences, the tail's record and head words, the optimiser's working copy of (p, q) beyond the register-resident limit
+    DevBuf rng_table, tt_counts, corres, tail, work;
+    bool rng_table_ready = false;
 };
 
 // The loop closure's pose graph (posegraph.hip; mloam_loop/src/pose_graph.cpp:92-150, 491-653): one PgKeyframe record per keyframe in HBM, the work buffers of

@@ -14,6 +14,10 @@
 //   fgr_nn_kernel       exact 33-dimensional nearest row: 128 queries per workgroup in registers, tiles of 32 rows in LDS (every lane reads the same word: a
 //                broadcast), the dataset split over blockIdx.y; results merge through atomicMin on (distance bits, row) keys -- a minimum is order-independent.
 //   fgr_mutual_kernel   one workgroup: the cross check, an ordered compaction in ascending i, the un-swap and the gather of the normalised points.
+//   the device tail (mlh_fgr_register_device), behind fgr_mutual_kernel with no host wait in between:
+//   fgr_tuple_count_kernel / fgr_tuple_scan_kernel / fgr_tuple_emit_kernel   the tuple test over independent trials: a count per segment of consecutive trials, the
+//                exclusive prefix, the accepted trials of rank < tuple_max_cnt written in trial order. Integer decisions only; no atomics.
+//   fgr_optimize_kernel   OptimizePairwise in ONE workgroup: 28 f64 sums per iteration in a fixed order, the 6 x 6 solve by every thread.
 #include "ctx.hpp"
 #include <algorithm>
 #include <cmath>
@@ -307,6 +311,227 @@ __global__ __launch_bounds__(TPB) void fgr_mutual_kernel(const unsigned long lon
     if (threadIdx.x == 0) { counts[0] = s_base; counts[1] = 0; }
 }
 
+// ---------------------------------------------------------------- the device tail (mlh_fgr_register_device): the tuple test as count -> scan -> emit over
+// independent trials (fgr_host.hpp has the plan's arithmetic and the trial), then OptimizePairwise in one workgroup. Four launches behind fgr_mutual_kernel; the
+// pair count is read where that kernel left it.
+// the record the one device-to-pinned copy brings to the host, and the words the tuple test's kernels hand to the optimiser (device only)
+struct FgrTailRecord {
+    float scal[8];                       // per cloud: mean xyz, max norm (fgr_norm_stats_kernel); zeros from the test entries
+    int32_t n_mutual, pad;
+    float trans[16];
+    double final_cost, final_cost_normalize;
+    int32_t n_tuples, n_corres, n_trials, optimised;
+};
+static_assert(sizeof(FgrTailRecord) == 136, "the tail's record");
+struct FgrTailHead { int32_t n_tuples, n_corres, n_trials, total, cap_segment, pad[3]; };
+constexpr size_t TAIL_HEAD_AT = 192, TAIL_BYTES = TAIL_HEAD_AT + sizeof(FgrTailHead);
+
+// inclusive prefix over the wavefront, lanes in order (integers: exact in any order)
+__device__ __forceinline__ int wave_incl_scan(int v)
+{
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v += o; }
+    return v;
+}
+
+// seg_counts[segment] <- the accepted trials of the segment (0 for a segment behind the last trial). One workgroup per segment of the LARGEST pair count possible.
+__global__ __launch_bounds__(FGR_TT_TPB) void fgr_tuple_count_kernel(const uint64_t *__restrict__ table, const FgrPair *__restrict__ pairs, const int *__restrict__ n_pairs, int pair_cap,
+                                                                     int swapped, float scale, uint64_t seed, int *__restrict__ seg_counts)
+{
+    __shared__ int s_wave[FGR_TT_TPB / 64];
+    const int ncorr = max(0, min(*n_pairs, pair_cap));
+    long long b, e;
+    fgr_tt_run(fgr_tt_total_trials(ncorr), blockIdx.x, threadIdx.x, &b, &e);
+    int c = __popc(fgr_tt_run_mask(table, pairs, ncorr, swapped != 0, scale, seed, b, e));
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
+    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) { int tot = 0; for (int w = 0; w < FGR_TT_TPB / 64; ++w) tot += s_wave[w]; seg_counts[blockIdx.x] = tot; }
+}
+
+// seg_base[s] <- the accepted trials in front of segment s (saturated at the cap: such a segment emits nothing); head <- the tuples kept, n_trials when the cap is
+// never reached, the segment that holds rank cap - 1 (-1: none). ONE workgroup.
+__global__ __launch_bounds__(TPB) void fgr_tuple_scan_kernel(const int *__restrict__ seg_counts, int nseg, const int *__restrict__ n_pairs, int pair_cap, int tuple_max_cnt,
+                                                             int *__restrict__ seg_base, FgrTailHead *__restrict__ head)
+{
+    __shared__ int s_wave[TPB / 64];
+    __shared__ long long s_carry;
+    if (threadIdx.x == 0) { s_carry = 0; head->cap_segment = -1; }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int at = 0; at < nseg; at += TPB) {                            // (uniform over the workgroup)
+        const int i = at + threadIdx.x;
+        const int c = i < nseg ? seg_counts[i] : 0;
+        const int incl = wave_incl_scan(c);
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        long long before = s_carry + (incl - c);
+        for (int w = 0; w < wave; ++w) before += s_wave[w];
+        if (i < nseg) {
+            seg_base[i] = int(before < (long long)tuple_max_cnt ? before : (long long)tuple_max_cnt);
+            if (before < (long long)tuple_max_cnt && before + c >= (long long)tuple_max_cnt) head->cap_segment = i;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) { long long tot = 0; for (int w = 0; w < TPB / 64; ++w) tot += s_wave[w]; s_carry += tot; }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const long long total = s_carry;
+        const int ncorr = max(0, min(*n_pairs, pair_cap));
+        const int tuples = fgr_tt_tuples(total, tuple_max_cnt);
+        head->n_tuples = tuples; head->n_corres = 3 * tuples;
+        head->total = int(total < 0x7fffffffll ? total : 0x7fffffffll);
+        if (!fgr_tt_cap_reached(total, tuple_max_cnt)) head->n_trials = int(fgr_tt_total_trials(ncorr));      // (otherwise the emit kernel's thread of rank cap - 1 writes it)
+    }
+}
+
+// the accepted trials of rank < tuple_max_cnt -> corres[3 rank ..], ranks in trial order: the segment's base + the accepted trials of the threads in front (a scan
+// over each wavefront, the wavefronts' totals added in wavefront order -- the pattern of fgr_mutual_kernel with a count per lane in place of a ballot's bit) + those
+// of the thread's own run in front. Only the segments that keep something recompute their trials. No atomics.
+__global__ __launch_bounds__(FGR_TT_TPB) void fgr_tuple_emit_kernel(const uint64_t *__restrict__ table, const FgrPair *__restrict__ pairs, const int *__restrict__ n_pairs, int pair_cap,
+                                                                    int swapped, float scale, uint64_t seed, int tuple_max_cnt, const int *__restrict__ seg_counts,
+                                                                    const int *__restrict__ seg_base, int *__restrict__ corres, int corres_cap_tuples, FgrTailHead *__restrict__ head)
+{
+    __shared__ int s_wave[FGR_TT_TPB / 64];
+    const int ncorr = max(0, min(*n_pairs, pair_cap));
+    const int base = seg_base[blockIdx.x];
+    if (!fgr_tt_segment_emits(base, seg_counts[blockIdx.x], tuple_max_cnt)) return;          // (uniform over the workgroup)
+    long long b, e;
+    fgr_tt_run(fgr_tt_total_trials(ncorr), blockIdx.x, threadIdx.x, &b, &e);
+    const uint32_t mask = fgr_tt_run_mask(table, pairs, ncorr, swapped != 0, scale, seed, b, e);
+    const int c = __popc(mask);
+    const int incl = wave_incl_scan(c);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 63) s_wave[wave] = incl;
+    __syncthreads();
+    int rank = base + (incl - c);
+    for (int w = 0; w < wave; ++w) rank += s_wave[w];
+    if (mask == 0u) return;
+    FgrRng rng = fgr_rng_at(table, seed, uint64_t(b) * 3ull);
+    for (long long t = b; t < e; ++t) {
+        int r[3];
+        fgr_trial_draw(ncorr, rng, r);
+        if (!((mask >> int(t - b)) & 1u)) continue;
+        if (fgr_tt_rank_kept(rank, tuple_max_cnt) && rank < corres_cap_tuples) { corres[3 * size_t(rank)] = r[0]; corres[3 * size_t(rank) + 1] = r[1]; corres[3 * size_t(rank) + 2] = r[2]; }
+        if (fgr_tt_rank_is_last(rank, tuple_max_cnt)) head->n_trials = int(t);
+        ++rank;
+    }
+}
+
+// OptimizePairwise (fgr_host.hpp: fgr_optimize_pairwise) on the head's n_corres correspondences. ONE workgroup; thread t owns the correspondences t, t + TPB, ..
+// and adds them to its 28 sums in that order; a __shfl_xor butterfly per wavefront (both partners add the same two values: every lane ends with the same bits), the
+// four wavefronts' sums added in wavefront order by every thread -- the fixed order of calib_ne_kernel -- so that every thread solves the same 6 x 6 system,
+// forms the same delta and moves its own copies of q with it; no broadcast. REG: p and the working q live in registers (n <= FGR_OPT_REG_MAX); otherwise in `work`.
+template <bool REG>
+__device__ __forceinline__ void fgr_optimize_body(const FgrPair *__restrict__ pairs, int pair_cap, const int *__restrict__ corres, int n, double par, double div_factor, double max_corr_dist,
+                                                  int iteration_number, float *__restrict__ work, double *s_red, float trans[16], double cost[2])
+{
+    float p[REG ? FGR_OPT_QREG : 1][3], q[REG ? FGR_OPT_QREG : 1][3];
+    if constexpr (REG) {
+#pragma unroll
+        for (int k = 0; k < FGR_OPT_QREG; ++k) {
+            const int c = int(threadIdx.x) + k * FGR_OPT_TPB;
+#pragma unroll
+            for (int d = 0; d < 3; ++d) { p[k][d] = 0.f; q[k][d] = 0.f; }
+            if (c < n) {
+                const FgrPair rec = pairs[max(0, min(corres[c], pair_cap - 1))];
+#pragma unroll
+                for (int d = 0; d < 3; ++d) { p[k][d] = rec.p[d]; q[k][d] = rec.q[d]; }
+            }
+        }
+    } else {
+        for (int c = threadIdx.x; c < n; c += FGR_OPT_TPB) {
+            const FgrPair rec = pairs[max(0, min(corres[c], pair_cap - 1))];
+            for (int d = 0; d < 3; ++d) { work[6 * size_t(c) + d] = rec.p[d]; work[6 * size_t(c) + 3 + d] = rec.q[d]; }
+        }
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int itr = 0; itr < iteration_number; ++itr) {                  // (uniform over the workgroup)
+        par = fgr_par_step(par, itr, max_corr_dist, div_factor);
+        double acc[FGR_OPT_SUMS];
+#pragma unroll
+        for (int i = 0; i < FGR_OPT_SUMS; ++i) acc[i] = 0.0;
+        if constexpr (REG) {
+#pragma unroll
+            for (int k = 0; k < FGR_OPT_QREG; ++k)
+                if (int(threadIdx.x) + k * FGR_OPT_TPB < n) fgr_pairwise_accumulate(p[k], q[k], par, acc);
+        } else {
+            for (int c = threadIdx.x; c < n; c += FGR_OPT_TPB) {
+                const float *w = work + 6 * size_t(c);
+                const float pp[3] = {w[0], w[1], w[2]}, qq[3] = {w[3], w[4], w[5]};
+                fgr_pairwise_accumulate(pp, qq, par, acc);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < FGR_OPT_SUMS; ++i) {
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1) acc[i] += __shfl_xor(acc[i], m);
+        }
+        if (lane == 0) {
+#pragma unroll
+            for (int i = 0; i < FGR_OPT_SUMS; ++i) s_red[wave * FGR_OPT_SUMS + i] = acc[i];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < FGR_OPT_SUMS; ++i)
+            acc[i] = ((s_red[i] + s_red[FGR_OPT_SUMS + i]) + s_red[2 * FGR_OPT_SUMS + i]) + s_red[3 * FGR_OPT_SUMS + i];
+        __syncthreads();
+        float delta[16];
+        fgr_pairwise_delta(acc, delta);
+        fgr_mat4_mul(delta, trans, trans);
+        if constexpr (REG) {
+#pragma unroll
+            for (int k = 0; k < FGR_OPT_QREG; ++k) fgr_transform_point(delta, q[k]);
+        } else {
+            for (int c = threadIdx.x; c < n; c += FGR_OPT_TPB) {
+                float *w = work + 6 * size_t(c) + 3;
+                float qq[3] = {w[0], w[1], w[2]};
+                fgr_transform_point(delta, qq);
+                w[0] = qq[0]; w[1] = qq[1]; w[2] = qq[2];
+            }
+        }
+        cost[0] = acc[FGR_OPT_R2];
+        cost[1] = acc[FGR_OPT_R2] / double(n);
+    }
+}
+
+// scal (may be null: start_scale_given is StartScale): the normalisation's scalars, copied into the record with the pair count. ONE workgroup of FGR_OPT_TPB.
+__global__ __launch_bounds__(FGR_OPT_TPB) void fgr_optimize_kernel(const FgrPair *__restrict__ pairs, int pair_cap, const int *__restrict__ corres, const FgrTailHead *__restrict__ head, int corres_cap,
+                                                                   const float *__restrict__ scal, const int *__restrict__ n_pairs, int use_absolute_scale, double start_scale_given,
+                                                                   double div_factor, double max_corr_dist, int iteration_number, float *__restrict__ work,
+                                                                   FgrTailRecord *__restrict__ out)
+{
+    static_assert(FGR_OPT_TPB == 256, "four wavefronts: the sums are added ((w0 + w1) + w2) + w3");
+    __shared__ double s_red[(FGR_OPT_TPB / 64) * FGR_OPT_SUMS];
+    const int n = max(0, min(head->n_corres, corres_cap));
+    float trans[16];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) trans[i] = (i % 5 == 0) ? 1.f : 0.f;
+    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    double cost[2] = {nan, nan};
+    const bool run = n >= FGR_MIN_CORRES && pair_cap > 0;               // app.cpp:412
+    if (run) {
+        double start_scale = start_scale_given;
+        if (scal) {                                                     // app.cpp:371-377
+            float scale = 0.f;
+            if (scal[3] > scale) scale = scal[3];
+            if (scal[7] > scale) scale = scal[7];
+            start_scale = double(use_absolute_scale ? scale : 1.0f);
+        }
+        if (n <= FGR_OPT_REG_MAX) fgr_optimize_body<true>(pairs, pair_cap, corres, n, start_scale, div_factor, max_corr_dist, iteration_number, work, s_red, trans, cost);
+        else fgr_optimize_body<false>(pairs, pair_cap, corres, n, start_scale, div_factor, max_corr_dist, iteration_number, work, s_red, trans, cost);
+    }
+    if (threadIdx.x == 0) {
+        for (int i = 0; i < 8; ++i) out->scal[i] = scal ? scal[i] : 0.f;
+        out->n_mutual = *n_pairs; out->pad = 0;
+        for (int i = 0; i < 16; ++i) out->trans[i] = trans[i];
+        out->final_cost = cost[0]; out->final_cost_normalize = cost[1];
+        out->n_tuples = head->n_tuples; out->n_corres = n; out->n_trials = head->n_trials; out->optimised = run ? 1 : 0;
+    }
+}
+
 // ---------------------------------------------------------------- host side
 struct FgrPinned { float scal[8]; int counts[2]; int pad[6]; };        // the pair records follow
 static_assert(sizeof(FgrPinned) == 64, "the pinned header");
@@ -505,10 +730,152 @@ int match_run(mlh_ctx *ctx, int32_t *pairs_out, int32_t capacity, int32_t *n_pai
     return MLH_OK;
 }
 
-int register_run(mlh_ctx *ctx, const mlh_fgr_opts &o, mlh_fgr_result *res)
+// ---- the device tail's host side
+// the most tuples a call can keep, and so the correspondences the buffers hold
+int tail_tuples_cap(int pair_cap, int tuple_max_cnt) { return int(std::min<long long>(tuple_max_cnt, fgr_tt_total_trials(pair_cap))); }
+int *pair_count_dev(FgrStore &F) { return reinterpret_cast<int *>(F.scal.as<float>() + 8); }
+FgrTailHead *tail_head_dev(FgrStore &F) { return reinterpret_cast<FgrTailHead *>(F.tail.as<unsigned char>() + TAIL_HEAD_AT); }
+
+// the tail's buffers for up to pair_cap pairs and n_corres_cap correspondences; the generator's table goes to the device the first time
+int fgr_tail_ensure(mlh_ctx *ctx, int pair_cap, int n_corres_cap)
 {
     FgrStore &F = ctx->fgr;
-    { const int rc = fgr_gate(ctx, "mlh_fgr_register"); if (rc) return rc; }
+    const size_t nseg = size_t(fgr_tt_segments(pair_cap));
+    MLH_HIP(ctx, ensure_counted(F.rng_table, sizeof(uint64_t) * FGR_RNG_TABLE_WORDS, F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.tt_counts, sizeof(int) * 2 * (nseg + 1), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.corres, sizeof(int) * (size_t(n_corres_cap) + 3), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.tail, TAIL_BYTES, F.allocations));
+    if (n_corres_cap > FGR_OPT_REG_MAX) MLH_HIP(ctx, ensure_counted(F.work, sizeof(float) * 6 * size_t(n_corres_cap), F.allocations));
+    if (!F.rng_table_ready) {
+        MLH_HIP(ctx, hipMemcpyAsync(F.rng_table.p, fgr_rng_table(), sizeof(uint64_t) * FGR_RNG_TABLE_WORDS, hipMemcpyHostToDevice, ctx->stream));
+        F.rng_table_ready = true;
+    }
+    return MLH_OK;
+}
+
+// count -> scan -> emit on the pairs and the pair count where they stand on the device (at most pair_cap pairs); the buffers hold tail_tuples_cap tuples
+int fgr_tuple_enqueue(mlh_ctx *ctx, const mlh_fgr_opts &o, bool swapped, int pair_cap)
+{
+    FgrStore &F = ctx->fgr;
+    hipStream_t st = ctx->stream;
+    const int nseg = fgr_tt_segments(pair_cap);
+    const uint64_t *table = F.rng_table.as<uint64_t>();
+    const FgrPair *pairs = F.pairs.as<FgrPair>();
+    int *counts = F.tt_counts.as<int>(), *base = counts + nseg + 1;
+    if (nseg > 0) {
+        MLH_LAUNCH(fgr_tuple_count_kernel, dim3(nseg), dim3(FGR_TT_TPB), 0, st, table, pairs, (const int *)pair_count_dev(F), pair_cap, swapped ? 1 : 0, o.tuple_scale, o.seed, counts);
+        ++F.launches;
+    }
+    MLH_LAUNCH(fgr_tuple_scan_kernel, dim3(1), dim3(TPB), 0, st, (const int *)counts, nseg, (const int *)pair_count_dev(F), pair_cap, o.tuple_max_cnt, base, tail_head_dev(F));
+    ++F.launches;
+    if (nseg > 0) {
+        MLH_LAUNCH(fgr_tuple_emit_kernel, dim3(nseg), dim3(FGR_TT_TPB), 0, st, table, pairs, (const int *)pair_count_dev(F), pair_cap, swapped ? 1 : 0, o.tuple_scale, o.seed,
+                   o.tuple_max_cnt, (const int *)counts, (const int *)base, F.corres.as<int>(), tail_tuples_cap(pair_cap, o.tuple_max_cnt), tail_head_dev(F));
+        ++F.launches;
+    }
+    MLH_HIP(ctx, hipGetLastError());
+    return MLH_OK;
+}
+
+// OptimizePairwise on the head's correspondences; scal: the normalisation's scalars on the device, or null with StartScale given
+int fgr_optimize_enqueue(mlh_ctx *ctx, const mlh_fgr_opts &o, int pair_cap, int n_corres_cap, const float *scal, double start_scale)
+{
+    FgrStore &F = ctx->fgr;
+    MLH_LAUNCH(fgr_optimize_kernel, dim3(1), dim3(FGR_OPT_TPB), 0, ctx->stream, (const FgrPair *)F.pairs.as<FgrPair>(), pair_cap, (const int *)F.corres.as<int>(),
+               (const FgrTailHead *)tail_head_dev(F), n_corres_cap, scal, (const int *)pair_count_dev(F), o.use_absolute_scale, start_scale, o.div_factor, o.max_corr_dist,
+               o.iteration_number, n_corres_cap > FGR_OPT_REG_MAX ? F.work.as<float>() : nullptr, F.tail.as<FgrTailRecord>());
+    ++F.launches;
+    MLH_HIP(ctx, hipGetLastError());
+    return MLH_OK;
+}
+
+// the record into the pinned block; ONE wait
+int fgr_tail_fetch(mlh_ctx *ctx, FgrTailRecord *rec)
+{
+    FgrStore &F = ctx->fgr;
+    MLH_HIP(ctx, F.h_pin.ensure(256, 4096, true));
+    MLH_HIP(ctx, hipMemcpyAsync(F.h_pin.p, F.tail.p, sizeof(FgrTailRecord), hipMemcpyDeviceToHost, ctx->stream));
+    MLH_HIP(ctx, stream_wait_spin(ctx));
+    ++F.host_waits;
+    { const int rc = device_error_check(ctx); if (rc) return rc; }
+    std::memcpy(rec, F.h_pin.p, sizeof(FgrTailRecord));
+    return MLH_OK;
+}
+
+// host records (n x {p, q}) -> the pair buffer and the pair count, through the pinned block; nothing is waited for: the block is not written again before
+// the call's one wait
+int fgr_stage_pairs(mlh_ctx *ctx, const float *pq, int n, size_t pin_bytes)
+{
+    FgrStore &F = ctx->fgr;
+    MLH_HIP(ctx, ensure_counted(F.pairs, sizeof(FgrPair) * (size_t(n) + 1), F.allocations));
+    MLH_HIP(ctx, ensure_counted(F.scal, 64, F.allocations));
+    MLH_HIP(ctx, F.h_pin.ensure(pin_bytes, 4096, true));
+    unsigned char *pin = F.h_pin.as<unsigned char>();
+    int *cnt = reinterpret_cast<int *>(pin + 256);
+    cnt[0] = n; cnt[1] = 0;
+    FgrPair *rec = reinterpret_cast<FgrPair *>(pin + 320);
+    for (int e = 0; e < n; ++e) {
+        rec[e].i = rec[e].j = e;
+        for (int d = 0; d < 3; ++d) { rec[e].p[d] = pq[6 * size_t(e) + d]; rec[e].q[d] = pq[6 * size_t(e) + 3 + d]; }
+    }
+    MLH_HIP(ctx, hipMemcpyAsync(pair_count_dev(F), cnt, 8, hipMemcpyHostToDevice, ctx->stream));
+    if (n) MLH_HIP(ctx, hipMemcpyAsync(F.pairs.p, rec, sizeof(FgrPair) * size_t(n), hipMemcpyHostToDevice, ctx->stream));
+    return MLH_OK;
+}
+
+int tail_tuple_test_run(mlh_ctx *ctx, const mlh_fgr_opts &o, const float *pq, int n, bool swapped, int32_t *corres_out, int32_t *n_tuples, int32_t *n_trials)
+{
+    FgrStore &F = ctx->fgr;
+    { const int rc = fgr_gate(ctx, "mlh_fgr_tail_tuple_test"); if (rc) return rc; }
+    const int tuples_cap = tail_tuples_cap(n, o.tuple_max_cnt);
+    { const int rc = fgr_tail_ensure(ctx, n, 3 * tuples_cap); if (rc) return rc; }
+    { const int rc = fgr_stage_pairs(ctx, pq, n, 320 + sizeof(FgrPair) * (size_t(n) + 1) + sizeof(int) * (3 * size_t(tuples_cap) + 3)); if (rc) return rc; }
+    { const int rc = fgr_tuple_enqueue(ctx, o, swapped, n); if (rc) return rc; }
+    // the head and the correspondences, behind the staged records in the pinned block; ONE wait
+    unsigned char *pin = F.h_pin.as<unsigned char>();
+    FgrTailHead *head = reinterpret_cast<FgrTailHead *>(pin);
+    int *got = reinterpret_cast<int *>(pin + 320 + sizeof(FgrPair) * (size_t(n) + 1));
+    MLH_HIP(ctx, hipMemcpyAsync(head, tail_head_dev(F), sizeof(FgrTailHead), hipMemcpyDeviceToHost, ctx->stream));
+    if (tuples_cap) MLH_HIP(ctx, hipMemcpyAsync(got, F.corres.p, sizeof(int) * 3 * size_t(tuples_cap), hipMemcpyDeviceToHost, ctx->stream));
+    MLH_HIP(ctx, stream_wait_spin(ctx));
+    ++F.host_waits;
+    { const int rc = device_error_check(ctx); if (rc) return rc; }
+    const int k = std::max(0, std::min(head->n_tuples, tuples_cap));
+    if (k) std::memcpy(corres_out, got, sizeof(int) * 3 * size_t(k));
+    *n_tuples = k; *n_trials = head->n_trials;
+    return MLH_OK;
+}
+
+int tail_optimize_run(mlh_ctx *ctx, const mlh_fgr_opts &o, const float *pq, int n, double start_scale, float *trans, double *cost, int32_t *optimised)
+{
+    FgrStore &F = ctx->fgr;
+    { const int rc = fgr_gate(ctx, "mlh_fgr_tail_optimize"); if (rc) return rc; }
+    { const int rc = fgr_tail_ensure(ctx, n, n); if (rc) return rc; }
+    const size_t ids_at = 320 + sizeof(FgrPair) * (size_t(n) + 1);
+    { const int rc = fgr_stage_pairs(ctx, pq, n, ids_at + sizeof(int) * (size_t(n) + 1)); if (rc) return rc; }
+    // every record is a correspondence, in its order
+    unsigned char *pin = F.h_pin.as<unsigned char>();
+    FgrTailHead *head = reinterpret_cast<FgrTailHead *>(pin + 288);
+    *head = FgrTailHead();
+    head->n_tuples = n / 3; head->n_corres = n; head->total = n / 3; head->cap_segment = -1;
+    int *ids = reinterpret_cast<int *>(pin + ids_at);
+    for (int e = 0; e < n; ++e) ids[e] = e;
+    MLH_HIP(ctx, hipMemcpyAsync(tail_head_dev(F), head, sizeof(FgrTailHead), hipMemcpyHostToDevice, ctx->stream));
+    if (n) MLH_HIP(ctx, hipMemcpyAsync(F.corres.p, ids, sizeof(int) * size_t(n), hipMemcpyHostToDevice, ctx->stream));
+    { const int rc = fgr_optimize_enqueue(ctx, o, n, n, nullptr, start_scale); if (rc) return rc; }
+    FgrTailRecord rec;
+    { const int rc = fgr_tail_fetch(ctx, &rec); if (rc) return rc; }
+    std::memcpy(trans, rec.trans, sizeof(rec.trans));
+    cost[0] = rec.final_cost; cost[1] = rec.final_cost_normalize;
+    *optimised = rec.optimised;
+    return MLH_OK;
+}
+
+// features (unless valid), NormalizePoints, the match: what both register entries enqueue in front of their tails
+int register_front(mlh_ctx *ctx, const mlh_fgr_opts &o, const char *entry, mlh_fgr_result *res, bool *swapped)
+{
+    FgrStore &F = ctx->fgr;
+    { const int rc = fgr_gate(ctx, entry); if (rc) return rc; }
     std::memset(res, 0, sizeof(*res));
     for (int s = 0; s < 2; ++s)
         if (!features_valid(ctx, s, o)) { const int rc = fgr_stages_run(ctx, s, o, STAGE_NORMALS); if (rc) return rc; }
@@ -524,8 +891,14 @@ int register_run(mlh_ctx *ctx, const mlh_fgr_opts &o, mlh_fgr_result *res)
                    o.use_absolute_scale, F.npts[0].as<float4>(), F.npts[1].as<float4>());
         ++F.launches;
     }
+    return fgr_match_enqueue(ctx, true, swapped);
+}
+
+int register_run(mlh_ctx *ctx, const mlh_fgr_opts &o, mlh_fgr_result *res)
+{
+    FgrStore &F = ctx->fgr;
     bool swapped = false;
-    { const int rc = fgr_match_enqueue(ctx, true, &swapped); if (rc) return rc; }
+    { const int rc = register_front(ctx, o, "mlh_fgr_register", res, &swapped); if (rc) return rc; }
     std::vector<FgrPair> pairs;
     FgrPinned head;
     { const int rc = fgr_fetch_pairs(ctx, pairs, &head); if (rc) return rc; }
@@ -535,6 +908,35 @@ int register_run(mlh_ctx *ctx, const mlh_fgr_opts &o, mlh_fgr_result *res)
     if (head.scal[7] > scale) scale = head.scal[7];
     const float global_scale = o.use_absolute_scale ? 1.0f : scale, start_scale = o.use_absolute_scale ? scale : 1.0f;
     fgr_host_tail(pairs, swapped, head.scal, head.scal + 4, global_scale, start_scale, o, *res);
+    res->host_waits = F.host_waits;
+    if (ctx->prof.mask) prof_collect(ctx);
+    return MLH_OK;
+}
+
+// the same call with the tail on the device: four launches behind the match, one 136-byte record to the host, GetOutputTrans and `accepted` on it
+int register_device_run(mlh_ctx *ctx, const mlh_fgr_opts &o, mlh_fgr_result *res)
+{
+    FgrStore &F = ctx->fgr;
+    bool swapped = false;
+    { const int rc = register_front(ctx, o, "mlh_fgr_register_device", res, &swapped); if (rc) return rc; }
+    const int pair_cap = std::min(F.fn[0], F.fn[1]);
+    const int n_corres_cap = 3 * tail_tuples_cap(pair_cap, o.tuple_max_cnt);
+    { const int rc = fgr_tail_ensure(ctx, pair_cap, n_corres_cap); if (rc) return rc; }
+    { const int rc = fgr_tuple_enqueue(ctx, o, swapped, pair_cap); if (rc) return rc; }
+    { const int rc = fgr_optimize_enqueue(ctx, o, pair_cap, n_corres_cap, F.scal.as<float>(), 1.0); if (rc) return rc; }
+    FgrTailRecord rec;
+    { const int rc = fgr_tail_fetch(ctx, &rec); if (rc) return rc; }
+    float scale = 0.f;                                                   // app.cpp:371-377
+    if (rec.scal[3] > scale) scale = rec.scal[3];
+    if (rec.scal[7] > scale) scale = rec.scal[7];
+    const float global_scale = o.use_absolute_scale ? 1.0f : scale, start_scale = o.use_absolute_scale ? scale : 1.0f;
+    fgr_output_trans(rec.trans, rec.scal, rec.scal + 4, global_scale, res->T_relative);
+    res->final_cost = rec.final_cost; res->final_cost_normalize = rec.final_cost_normalize;
+    res->accepted = (rec.optimised && rec.final_cost_normalize <= o.global_registration_threshold) ? 1 : 0;
+    res->swapped = swapped ? 1 : 0;
+    res->n_mutual = rec.n_mutual; res->n_tuples = rec.n_tuples; res->n_corres = rec.n_corres; res->n_trials = rec.n_trials;
+    res->global_scale = double(global_scale); res->start_scale = double(start_scale);
+    for (int d = 0; d < 3; ++d) { res->means[d] = double(rec.scal[d]); res->means[3 + d] = double(rec.scal[4 + d]); }
     res->host_waits = F.host_waits;
     if (ctx->prof.mask) prof_collect(ctx);
     return MLH_OK;
@@ -664,6 +1066,41 @@ int mlh_fgr_register(mlh_ctx *ctx, const mlh_fgr_opts *opts, mlh_fgr_result *res
     return register_run(ctx, o, result);
 }
 
+int mlh_fgr_register_device(mlh_ctx *ctx, const mlh_fgr_opts *opts, mlh_fgr_result *result)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (!result) return fail(ctx, MLH_ERR_INVALID, "mlh_fgr_register_device: null result");
+    mlh_fgr_opts o;
+    { const int rc = fgr_opts_take(ctx, "mlh_fgr_register_device", opts, o); if (rc) return rc; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return register_device_run(ctx, o, result);
+}
+
+int mlh_fgr_tail_tuple_test(mlh_ctx *ctx, const float *pq, int32_t n, int32_t swapped, const mlh_fgr_opts *opts, int32_t *corres_out, int32_t capacity_tuples, int32_t *n_tuples,
+                            int32_t *n_trials)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    mlh_fgr_opts o;
+    { const int rc = fgr_opts_take(ctx, "mlh_fgr_tail_tuple_test", opts, o); if (rc) return rc; }
+    if (n < 0 || n > 20000000 || (n > 0 && !pq) || (swapped != 0 && swapped != 1) || !n_tuples || !n_trials)
+        return fail(ctx, MLH_ERR_INVALID, "mlh_fgr_tail_tuple_test: 0 <= n <= 20000000 records with their array, swapped 0 or 1, non-null n_tuples and n_trials");
+    if (capacity_tuples < tail_tuples_cap(n, o.tuple_max_cnt) || (capacity_tuples > 0 && !corres_out))
+        return fail(ctx, MLH_ERR_INVALID, "mlh_fgr_tail_tuple_test: capacity_tuples must hold min(tuple_max_cnt, 100 n) tuples, with their array");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return tail_tuple_test_run(ctx, o, pq, n, swapped != 0, corres_out, n_tuples, n_trials);
+}
+
+int mlh_fgr_tail_optimize(mlh_ctx *ctx, const float *pq, int32_t n, double start_scale, const mlh_fgr_opts *opts, float *trans, double *cost, int32_t *optimised)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    mlh_fgr_opts o;
+    { const int rc = fgr_opts_take(ctx, "mlh_fgr_tail_optimize", opts, o); if (rc) return rc; }
+    if (n < 0 || n > 3000000 || (n > 0 && !pq) || !std::isfinite(start_scale) || !(start_scale > 0.0) || !trans || !cost || !optimised)
+        return fail(ctx, MLH_ERR_INVALID, "mlh_fgr_tail_optimize: 0 <= n <= 3000000 records with their array, a finite start_scale > 0, non-null trans, cost and optimised");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return tail_optimize_run(ctx, o, pq, n, start_scale, trans, cost, optimised);
+}
+
 int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out)
 {
     if (!ctx) return MLH_ERR_INVALID;
@@ -671,7 +1108,7 @@ int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out)
     const FgrStore &F = ctx->fgr;
     const unsigned long long gen = ctx->loop.cloud_gen;
     std::memset(out, 0, sizeof(*out));
-    size_t bytes = F.scal.cap + F.pairs.cap;
+    size_t bytes = F.scal.cap + F.pairs.cap + F.rng_table.cap + F.tt_counts.cap + F.corres.cap + F.tail.cap + F.work.cap;
     for (int s = 0; s < 2; ++s) {
         out->n[s] = F.fn[s];
         out->have_normals[s] = F.normals_gen[s] == gen; out->have_spfh[s] = F.spfh_gen[s] == gen; out->have_features[s] = F.feat_gen[s] == gen;

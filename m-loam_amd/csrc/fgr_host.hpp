@@ -1,7 +1,8 @@
 // FPFH + Fast Global Registration (fgr.hip; include/mloam_hip.h section (f13)): the arithmetic that exists ONCE -- for the kernels (__host__ __device__), for the
-// host tail of mlh_fgr_register (the tuple test, OptimizePairwise, GetOutputTrans: bounded by 3 tuple_max_cnt correspondences) and for the tests' CPU restatement
-// (tests/host/fgr_ref.cpp) -- and the option validation. A header of its own so that a stand-alone host program can run it under a sanitizer
-// (tests/host/fgr_host_main.cpp).
+// host tail of mlh_fgr_register (the tuple test, OptimizePairwise, GetOutputTrans: bounded by 3 tuple_max_cnt correspondences), for the device tail of
+// mlh_fgr_register_device (the same trial, the same per-correspondence term and solve, and the plan that cuts the tuple test into independent trials) and for the
+// tests' CPU restatement (tests/host/fgr_ref.cpp) -- and the option validation. A header of its own so that a stand-alone host program can run it under a sanitizer
+// (tests/host/fgr_host_main.cpp; tests/host/fgr_tail_main.cpp replays the device plan).
 // Restated from mloam_loop/ThirdParty/FastGlobalRegistration/app.cpp, with its lines: NormalizePoints' per-point arithmetic (324-390), the tuple test (242-307),
 // OptimizePairwise (392-505), TransformPoints (507-517), GetOutputTrans (519-534).
 // Restated FROM MEMORY of PCL 1.8.0 and FLANN 1.8 -- neither library's source is available to this project, so none of this could be checked against it:
@@ -31,6 +32,8 @@
 #else
 #define MLH_FGR_HD inline
 #endif
+// the pieces of one tuple-test trial: left to the inliner's judgement, the host's sequential loop over them came out 15 % slower than the loop written out
+#define MLH_FGR_HD_FORCE __attribute__((always_inline)) MLH_FGR_HD
 
 namespace mlh {
 
@@ -234,7 +237,7 @@ MLH_FGR_HD bool fgr_row_finite(const float *a)
     return ok;
 }
 
-// ---------------------------------------------------------------- the host tail
+// ---------------------------------------------------------------- the tail: the host's (fgr_host_tail) and what the device's kernels share with it
 // one mutual pair after the un-swap: i indexes cloud 0 (model), j cloud 1 (data); p, q their NORMALISED points
 struct FgrPair { int32_t i, j; float p[3], q[3]; };
 static_assert(sizeof(FgrPair) == 32, "the pinned pair record");
@@ -242,18 +245,75 @@ static_assert(sizeof(FgrPair) == 32, "the pinned pair record");
 // the tuple test's generator (DEPARTURE from srand(time(NULL)) / rand()): xorshift64*, 31 bits per draw like rand()
 struct FgrRng {
     uint64_t s;
-    explicit FgrRng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull) { if (s == 0) s = 0x2545F4914F6CDD1Dull; }
-    uint32_t next()
+    MLH_FGR_HD explicit FgrRng(uint64_t seed) : s(seed * 0x9E3779B97F4A7C15ull + 0xD1B54A32D192ED03ull) { if (s == 0) s = 0x2545F4914F6CDD1Dull; }
+    MLH_FGR_HD uint32_t next()
     {
         s ^= s >> 12; s ^= s << 25; s ^= s >> 27;
         return uint32_t((s * 0x2545F4914F6CDD1Dull) >> 33);
     }
 };
 
-inline float fgr_dist3(const float a[3], const float b[3])
+// The state update of next() is a linear map A over GF(2)^64 (three xor-shifts), so the state in front of draw k is A^k s0: a product of the A^(2^b) of k's set
+// bits. The table: FGR_RNG_POWERS matrices of 64 words, word i of matrix b = A^(2^b) applied to bit i. Built once on the host (fgr_rng_table()) and handed to the
+// device once per context; 2^FGR_RNG_POWERS draws are more than 3 x 100 x any pair count an int32 holds.
+constexpr int FGR_RNG_POWERS = 44;
+constexpr int FGR_RNG_TABLE_WORDS = FGR_RNG_POWERS * 64;
+
+MLH_FGR_HD uint64_t fgr_gf2_apply(const uint64_t *m, uint64_t v)
+{
+    uint64_t r = 0;
+    for (int i = 0; i < 64; ++i) r ^= ((v >> i) & 1ull) ? m[i] : 0ull;
+    return r;
+}
+inline void fgr_rng_table_build(uint64_t *table)
+{
+    for (int i = 0; i < 64; ++i) {
+        uint64_t s = 1ull << i;
+        s ^= s >> 12; s ^= s << 25; s ^= s >> 27;
+        table[i] = s;
+    }
+    for (int b = 1; b < FGR_RNG_POWERS; ++b)
+        for (int i = 0; i < 64; ++i) table[b * 64 + i] = fgr_gf2_apply(table + (b - 1) * 64, table[(b - 1) * 64 + i]);
+}
+inline const uint64_t *fgr_rng_table()
+{
+    static const std::vector<uint64_t> t = [] { std::vector<uint64_t> v; v.resize(FGR_RNG_TABLE_WORDS); fgr_rng_table_build(v.data()); return v; }();
+    return t.data();
+}
+// the generator as it stands in front of draw k (k < 2^FGR_RNG_POWERS) of the sequence FgrRng(seed) starts
+MLH_FGR_HD FgrRng fgr_rng_at(const uint64_t *table, uint64_t seed, uint64_t k)
+{
+    FgrRng r(seed);
+    for (int b = 0; b < FGR_RNG_POWERS; ++b)
+        if ((k >> b) & 1ull) r.s = fgr_gf2_apply(table + b * 64, r.s);
+    return r;
+}
+inline FgrRng fgr_rng_at(uint64_t seed, uint64_t k) { return fgr_rng_at(fgr_rng_table(), seed, k); }
+
+MLH_FGR_HD_FORCE float fgr_dist3(const float a[3], const float b[3])
 {
     const float dx = a[0] - b[0], dy = a[1] - b[1], dz = a[2] - b[2];
-    return std::sqrt((dx * dx + dy * dy) + dz * dz);
+    return sqrtf((dx * dx + dy * dy) + dz * dz);
+}
+
+// One trial of the tuple test (app.cpp:256-291): three draws of rng (fgr_trial_draw: the emit pass repeats them alone for a trial it knows to be accepted),
+// r[] <- the three pair indices; true when the three side lengths of the two triangles agree
+// within `scale`. ncorr > 0. The only text of this arithmetic: fgr_tuple_test below, the device's count and emit kernels and the tests' replay call it.
+MLH_FGR_HD_FORCE void fgr_trial_draw(int ncorr, FgrRng &rng, int r[3])
+{
+    const int r0 = int(rng.next() % uint32_t(ncorr)), r1 = int(rng.next() % uint32_t(ncorr)), r2 = int(rng.next() % uint32_t(ncorr));
+    r[0] = r0; r[1] = r1; r[2] = r2;
+}
+MLH_FGR_HD_FORCE bool fgr_trial_accepts(const FgrPair *pairs, int ncorr, bool swapped, float scale, FgrRng &rng, int r[3])
+{
+    fgr_trial_draw(ncorr, rng, r);
+    const int r0 = r[0], r1 = r[1], r2 = r[2];
+    const FgrPair &c0 = pairs[size_t(r0)], &c1 = pairs[size_t(r1)], &c2 = pairs[size_t(r2)];
+    const float *i0 = swapped ? c0.q : c0.p, *i1 = swapped ? c1.q : c1.p, *i2 = swapped ? c2.q : c2.p;
+    const float *j0 = swapped ? c0.p : c0.q, *j1 = swapped ? c1.p : c1.q, *j2 = swapped ? c2.p : c2.q;
+    const float li0 = fgr_dist3(i0, i1), li1 = fgr_dist3(i1, i2), li2 = fgr_dist3(i2, i0);
+    const float lj0 = fgr_dist3(j0, j1), lj1 = fgr_dist3(j1, j2), lj2 = fgr_dist3(j2, j0);
+    return (li0 * scale < lj0) && (lj0 < li0 / scale) && (li1 * scale < lj1) && (lj1 < li1 / scale) && (li2 * scale < lj2) && (lj2 < li2 / scale);
 }
 
 // app.cpp:242-307 on the cross-checked pairs. swapped: cloud 1 was `i` (the li side). corres <- 3 entries per accepted tuple (indices into pairs); returns the
@@ -265,17 +325,13 @@ inline int fgr_tuple_test(const std::vector<FgrPair> &pairs, bool swapped, float
     const long long number_of_trial = (long long)ncorr * 100;
     FgrRng rng(seed);
     const float scale = tuple_scale;
+    const FgrPair *const recs = pairs.data();     // (read once: the loop's stores into corres could alias the vector's own words)
     int cnt = 0;
     long long t = 0;
     for (t = 0; t < number_of_trial; ++t) {
-        const int r0 = int(rng.next() % uint32_t(ncorr)), r1 = int(rng.next() % uint32_t(ncorr)), r2 = int(rng.next() % uint32_t(ncorr));
-        const FgrPair &c0 = pairs[size_t(r0)], &c1 = pairs[size_t(r1)], &c2 = pairs[size_t(r2)];
-        const float *i0 = swapped ? c0.q : c0.p, *i1 = swapped ? c1.q : c1.p, *i2 = swapped ? c2.q : c2.p;
-        const float *j0 = swapped ? c0.p : c0.q, *j1 = swapped ? c1.p : c1.q, *j2 = swapped ? c2.p : c2.q;
-        const float li0 = fgr_dist3(i0, i1), li1 = fgr_dist3(i1, i2), li2 = fgr_dist3(i2, i0);
-        const float lj0 = fgr_dist3(j0, j1), lj1 = fgr_dist3(j1, j2), lj2 = fgr_dist3(j2, j0);
-        if ((li0 * scale < lj0) && (lj0 < li0 / scale) && (li1 * scale < lj1) && (lj1 < li1 / scale) && (li2 * scale < lj2) && (lj2 < li2 / scale)) {
-            corres.push_back(r0); corres.push_back(r1); corres.push_back(r2);
+        int r[3];
+        if (fgr_trial_accepts(recs, ncorr, swapped, scale, rng, r)) {
+            corres.push_back(r[0]); corres.push_back(r[1]); corres.push_back(r[2]);
             ++cnt;
         }
         if (cnt >= tuple_max_cnt) break;        // (the reference leaves the loop before the counter's increment: trials = t, as its printout had it)
@@ -284,6 +340,45 @@ inline int fgr_tuple_test(const std::vector<FgrPair> &pairs, bool swapped, float
     return cnt;
 }
 
+// ---- the same test as a plan of independent trials (fgr.hip: fgr_tuple_count_kernel / _scan_kernel / _emit_kernel; tests/host/fgr_tail_main.cpp replays it).
+// Trial t uses draws 3 t .. 3 t + 2 whatever earlier trials decided, so the trials are cut into segments of FGR_TT_RUN x FGR_TT_TPB consecutive trials, one per
+// workgroup, and every thread owns a run of FGR_TT_RUN consecutive trials of its segment: it jumps to draw 3 t_first (fgr_rng_at) and steps on from there. The
+// accepted trials' ranks in trial order are: the segment's base (the exclusive prefix of the segments' counts) + the accepted trials of the segment's threads
+// before this one + those of this thread's run before this trial. The result of the sequential loop above is the trials of rank < tuple_max_cnt.
+constexpr int FGR_TT_RUN = 16, FGR_TT_TPB = 256;
+constexpr long long FGR_TT_SEGMENT = (long long)FGR_TT_RUN * FGR_TT_TPB;
+MLH_FGR_HD long long fgr_tt_total_trials(int ncorr) { return ncorr > 0 ? (long long)ncorr * 100 : 0; }
+MLH_FGR_HD int fgr_tt_segments(int ncorr) { return int((fgr_tt_total_trials(ncorr) + FGR_TT_SEGMENT - 1) / FGR_TT_SEGMENT); }
+// the run of `thread` of `segment`: [*begin, *end) (empty behind the last trial)
+MLH_FGR_HD void fgr_tt_run(long long total_trials, int segment, int thread, long long *begin, long long *end)
+{
+    const long long b = (long long)segment * FGR_TT_SEGMENT + (long long)thread * FGR_TT_RUN;
+    const long long e = b + FGR_TT_RUN;
+    *begin = b < total_trials ? b : total_trials;
+    *end = e < total_trials ? e : total_trials;
+}
+// bit i of the result: trial begin + i is accepted. Never draws -- and so never divides by ncorr -- when the run is empty.
+MLH_FGR_HD uint32_t fgr_tt_run_mask(const uint64_t *table, const FgrPair *pairs, int ncorr, bool swapped, float scale, uint64_t seed, long long begin, long long end)
+{
+    static_assert(FGR_TT_RUN <= 32, "a run's accepted trials are one 32-bit mask");
+    if (begin >= end) return 0u;
+    FgrRng rng = fgr_rng_at(table, seed, uint64_t(begin) * 3ull);
+    uint32_t mask = 0u;
+    for (long long t = begin; t < end; ++t) {
+        int r[3];
+        if (fgr_trial_accepts(pairs, ncorr, swapped, scale, rng, r)) mask |= 1u << int(t - begin);
+    }
+    return mask;
+}
+// a segment recomputes its trials in the emit pass only when some of its accepted trials are kept
+MLH_FGR_HD bool fgr_tt_segment_emits(int base, int count, int tuple_max_cnt) { return count > 0 && base < tuple_max_cnt; }
+MLH_FGR_HD bool fgr_tt_rank_kept(int rank, int tuple_max_cnt) { return rank < tuple_max_cnt; }
+// the trial that is written as n_trials by the emit pass: the one whose acceptance made the count reach the cap
+MLH_FGR_HD bool fgr_tt_rank_is_last(int rank, int tuple_max_cnt) { return rank == tuple_max_cnt - 1; }
+MLH_FGR_HD int fgr_tt_tuples(long long total_accepted, int tuple_max_cnt) { return total_accepted < (long long)tuple_max_cnt ? int(total_accepted) : tuple_max_cnt; }
+// n_trials when the cap is never reached (0 for ncorr = 0); otherwise the emit pass's trial index stands
+MLH_FGR_HD bool fgr_tt_cap_reached(long long total_accepted, int tuple_max_cnt) { return total_accepted >= (long long)tuple_max_cnt; }
+
 struct FgrTail {
     float trans[16];                 // TransOutput_, row-major
     double final_cost, final_cost_normalize;
@@ -291,7 +386,7 @@ struct FgrTail {
 };
 
 // 4 x 4 f32 row-major product, sums left to right
-inline void fgr_mat4_mul(const float A[16], const float B[16], float C[16])
+MLH_FGR_HD void fgr_mat4_mul(const float A[16], const float B[16], float C[16])
 {
     float t[16];
     for (int r = 0; r < 4; ++r)
@@ -301,7 +396,7 @@ inline void fgr_mat4_mul(const float A[16], const float B[16], float C[16])
 }
 
 // -JTJ.llt().solve(JTr): CHOSEN a plain (unblocked, lower) Cholesky and two triangular solves
-inline void fgr_llt_solve6(const double A[36], const double b[6], double x[6])
+MLH_FGR_HD void fgr_llt_solve6(const double A[36], const double b[6], double x[6])
 {
     double L[36] = {0};
     for (int j = 0; j < 6; ++j) {
@@ -321,7 +416,7 @@ inline void fgr_llt_solve6(const double A[36], const double b[6], double x[6])
 }
 
 // AngleAxisd(rz, Z) * AngleAxisd(ry, Y) * AngleAxisd(rx, X): Eigen multiplies angle-axes as quaternions, then toRotationMatrix()
-inline void fgr_zyx_rotation(double rx, double ry, double rz, double R[9])
+MLH_FGR_HD void fgr_zyx_rotation(double rx, double ry, double rz, double R[9])
 {
     const auto qmul = [](const double a[4], const double b[4], double o[4]) {      // (x, y, z, w)
         o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
@@ -338,6 +433,71 @@ inline void fgr_zyx_rotation(double rx, double ry, double rz, double R[9])
     R[0] = 1.0 - (tyy + tzz); R[1] = txy - twz; R[2] = txz + twy;
     R[3] = txy + twz; R[4] = 1.0 - (txx + tzz); R[5] = tyz - twx;
     R[6] = txz - twy; R[7] = tyz + twx; R[8] = 1.0 - (txx + tyy);
+}
+
+// ---- one iteration of OptimizePairwise, in the pieces fgr_optimize_pairwise below and fgr.hip's fgr_optimize_kernel share
+// the sums of one iteration: the upper triangle of JTJ row by row ((0,0) (0,1) .. (5,5): 21), JTr (6), r2
+constexpr int FGR_OPT_SUMS = 28, FGR_OPT_JTR = 21, FGR_OPT_R2 = 27;
+MLH_FGR_HD constexpr int fgr_tri(int i, int j) { return i * 6 - i * (i - 1) / 2 + (j - i); }      // i <= j
+// the device keeps the working copy of q in registers up to this many correspondences (FGR_OPT_QREG per thread of one workgroup of FGR_OPT_TPB) and in an HBM
+// buffer beyond; the default tuple_max_cnt = 1000 gives 3000
+constexpr int FGR_OPT_TPB = 256, FGR_OPT_QREG = 12;
+constexpr int FGR_OPT_REG_MAX = 3072;
+static_assert(FGR_OPT_REG_MAX == FGR_OPT_TPB * FGR_OPT_QREG, "the register-resident limit");
+
+// the schedule of `par` in front of iteration itr (app.cpp:420-423)
+MLH_FGR_HD double fgr_par_step(double par, int itr, double max_corr_dist, double div_factor)
+{
+    return (itr % 4 == 0 && par > max_corr_dist) ? par / div_factor : par;
+}
+
+// one correspondence's term of app.cpp:436-476 added to the sums: rpq = p - q, the line-process weight s = (par / (rpq . rpq + par))^2 (temp in f32), the three
+// rows  J(1) = -q2, J(2) = q1, J(3) = -1 | J(2) = -q0, J(0) = q2, J(4) = -1 | J(0) = -q1, J(1) = q0, J(5) = -1  and the r2 contribution. Every sum receives its
+// terms in the order the reference's loops give them (row by row); JTJ is symmetric to the bit (a product commutes), so its upper triangle is the whole of it.
+MLH_FGR_HD void fgr_pairwise_accumulate(const float p[3], const float qq[3], double par, double acc[FGR_OPT_SUMS])
+{
+    const float rpq[3] = {p[0] - qq[0], p[1] - qq[1], p[2] - qq[2]};
+    const float dot = (rpq[0] * rpq[0] + rpq[1] * rpq[1]) + rpq[2] * rpq[2];
+    const float temp = float(par / (double(dot) + par));
+    const double s = double(temp * temp);
+    const int idx[3][3] = {{1, 2, 3}, {2, 0, 4}, {0, 1, 5}};
+    const double val[3][3] = {{-double(qq[2]), double(qq[1]), -1.0}, {-double(qq[0]), double(qq[2]), -1.0}, {-double(qq[1]), double(qq[0]), -1.0}};
+    for (int row = 0; row < 3; ++row) {
+        const double r = double(rpq[row]);
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b)
+                if (idx[row][a] <= idx[row][b]) acc[fgr_tri(idx[row][a], idx[row][b])] += (val[row][a] * val[row][b]) * s;
+            acc[FGR_OPT_JTR + idx[row][a]] += (val[row][a] * r) * s;
+        }
+        acc[FGR_OPT_R2] += r * r * s;
+    }
+    acc[FGR_OPT_R2] += (par * (1.0 - std::sqrt(s)) * (1.0 - std::sqrt(s)));
+}
+
+// the sums -> delta (app.cpp:478-497): result = -JTJ.llt().solve(JTr), the Z Y X rotation, the f32 4 x 4
+MLH_FGR_HD void fgr_pairwise_delta(const double acc[FGR_OPT_SUMS], float delta[16])
+{
+    double JTJ[36], JTr[6], x[6];
+    for (int i = 0; i < 6; ++i) {
+        for (int j = i; j < 6; ++j) JTJ[i * 6 + j] = JTJ[j * 6 + i] = acc[fgr_tri(i, j)];
+        JTr[i] = acc[FGR_OPT_JTR + i];
+    }
+    fgr_llt_solve6(JTJ, JTr, x);
+    for (int i = 0; i < 6; ++i) x[i] = -x[i];
+    double R[9];
+    fgr_zyx_rotation(x[0], x[1], x[2], R);
+    const float d[16] = {float(R[0]), float(R[1]), float(R[2]), float(x[3]), float(R[3]), float(R[4]), float(R[5]), float(x[4]),
+                         float(R[6]), float(R[7]), float(R[8]), float(x[5]), 0.f, 0.f, 0.f, 1.f};
+    for (int i = 0; i < 16; ++i) delta[i] = d[i];
+}
+
+// TransformPoints on one point: temp = R * p + t
+MLH_FGR_HD void fgr_transform_point(const float delta[16], float qq[3])
+{
+    const float a = qq[0], b = qq[1], d = qq[2];
+    qq[0] = ((delta[0] * a + delta[1] * b) + delta[2] * d) + delta[3];
+    qq[1] = ((delta[4] * a + delta[5] * b) + delta[6] * d) + delta[7];
+    qq[2] = ((delta[8] * a + delta[9] * b) + delta[10] * d) + delta[11];
 }
 
 // OptimizePairwise(decrease_mu_ = true), app.cpp:392-505, over the correspondences corres[c] -> pairs[corres[c]] (p: pointcloud_[0], q: pcj_copy). Every
@@ -358,44 +518,15 @@ inline FgrTail fgr_optimize_pairwise(const std::vector<FgrPair> &pairs, const st
     float trans[16];
     for (int i = 0; i < 16; ++i) trans[i] = out.trans[i];
     for (int itr = 0; itr < iteration_number; ++itr) {
-        if (itr % 4 == 0 && par > max_corr_dist) par /= div_factor;
-        double JTJ[36] = {0}, JTr[6] = {0}, r2 = 0.0;
-        for (size_t c = 0; c < n; ++c) {
-            const float *p = pairs[size_t(corres[c])].p, *qq = &q[3 * c];
-            const float rpq[3] = {p[0] - qq[0], p[1] - qq[1], p[2] - qq[2]};
-            const float dot = (rpq[0] * rpq[0] + rpq[1] * rpq[1]) + rpq[2] * rpq[2];
-            const float temp = float(par / (double(dot) + par));
-            const double s = double(temp * temp);
-            // the three rows: J(1) = -q2, J(2) = q1, J(3) = -1 | J(2) = -q0, J(0) = q2, J(4) = -1 | J(0) = -q1, J(1) = q0, J(5) = -1
-            const int idx[3][3] = {{1, 2, 3}, {2, 0, 4}, {0, 1, 5}};
-            const double val[3][3] = {{-double(qq[2]), double(qq[1]), -1.0}, {-double(qq[0]), double(qq[2]), -1.0}, {-double(qq[1]), double(qq[0]), -1.0}};
-            for (int row = 0; row < 3; ++row) {
-                const double r = double(rpq[row]);
-                for (int a = 0; a < 3; ++a) {
-                    for (int b = 0; b < 3; ++b) JTJ[idx[row][a] * 6 + idx[row][b]] += (val[row][a] * val[row][b]) * s;
-                    JTr[idx[row][a]] += (val[row][a] * r) * s;
-                }
-                r2 += r * r * s;
-            }
-            r2 += (par * (1.0 - std::sqrt(s)) * (1.0 - std::sqrt(s)));
-        }
-        double x[6];
-        fgr_llt_solve6(JTJ, JTr, x);
-        for (int i = 0; i < 6; ++i) x[i] = -x[i];
-        double R[9];
-        fgr_zyx_rotation(x[0], x[1], x[2], R);
-        float delta[16] = {float(R[0]), float(R[1]), float(R[2]), float(x[3]), float(R[3]), float(R[4]), float(R[5]), float(x[4]),
-                           float(R[6]), float(R[7]), float(R[8]), float(x[5]), 0.f, 0.f, 0.f, 1.f};
+        par = fgr_par_step(par, itr, max_corr_dist, div_factor);
+        double acc[FGR_OPT_SUMS] = {0};
+        for (size_t c = 0; c < n; ++c) fgr_pairwise_accumulate(pairs[size_t(corres[c])].p, &q[3 * c], par, acc);
+        float delta[16];
+        fgr_pairwise_delta(acc, delta);
         fgr_mat4_mul(delta, trans, trans);
-        for (size_t c = 0; c < n; ++c) {                 // TransformPoints: temp = R * p + t
-            float *qq = &q[3 * c];
-            const float a = qq[0], b = qq[1], d = qq[2];
-            qq[0] = ((delta[0] * a + delta[1] * b) + delta[2] * d) + delta[3];
-            qq[1] = ((delta[4] * a + delta[5] * b) + delta[6] * d) + delta[7];
-            qq[2] = ((delta[8] * a + delta[9] * b) + delta[10] * d) + delta[11];
-        }
-        out.final_cost = r2;
-        out.final_cost_normalize = r2 / double(n);
+        for (size_t c = 0; c < n; ++c) fgr_transform_point(delta, &q[3 * c]);
+        out.final_cost = acc[FGR_OPT_R2];
+        out.final_cost_normalize = acc[FGR_OPT_R2] / double(n);
     }
     for (int i = 0; i < 16; ++i) out.trans[i] = trans[i];      // TransOutput_ = trans * Identity
     return out;

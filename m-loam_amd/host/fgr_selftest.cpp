@@ -3,6 +3,8 @@
 //   - the host-cloud form (the reference's signature shape) finds the transform that made the scene within 1e-4 and accepts it;
 //   - the overload on the clouds left on the device returns the same bits, with one host wait (the features are reused);
 //   - chained as checkGeometricConsistency chains it, performLocalRegistration starts from that transform with the four clouds handed over again and runs;
+//   - with the tail on the device (setGlobalRegistrationTail(true)) the same call returns the same counts and tuples' number, T within 1e-6 of the host tail's,
+//     one host wait; back on the host tail the first call's bits return;
 //   - with a tuple scale of 1 no tuple passes: T = GetOutputTrans of the identity, not accepted.
 // Usage: fgr_selftest  (exit status 0 = pass)
 #include <cmath>
@@ -75,6 +77,21 @@ int main()
     for (int i = 0; i < 16; ++i) lerr = std::max(lerr, std::fabs(local.second[size_t(i)] - truth[size_t(i)]));
     std::printf("performLocalRegistration from it: accepted %d, max |T - truth| %.2e, cost %.3e\n", int(local.first), lerr, reg.lastResult().opti_cost);
     EXPECT(local.first && lerr < 5e-2);
+    // the tail on the device: the same tuples, T within the f32 bar, one wait; then the host tail again, bit for bit
+    EXPECT(!reg.globalRegistrationTailOnDevice());
+    (void)reg.performGlobalRegistration(model, data);
+    reg.setGlobalRegistrationTail(true);
+    const std::pair<bool, Mat4> on_dev = reg.performGlobalRegistration();
+    const mlh_fgr_result rd = reg.lastGlobalResult();
+    double derr = 0.0;
+    for (int i = 0; i < 16; ++i) derr = std::max(derr, std::fabs(on_dev.second[size_t(i)] - got.second[size_t(i)]));
+    std::printf("performGlobalRegistration, device tail: accepted %d, max |T - host tail's T| %.2e, cost %.3e, %d tuples of %d trials, %d host waits\n", int(on_dev.first), derr,
+                rd.final_cost_normalize, rd.n_tuples, rd.n_trials, rd.host_waits);
+    EXPECT(on_dev.first == got.first && derr <= 1e-6 && rd.host_waits == 1);
+    EXPECT(rd.n_mutual == r0.n_mutual && rd.n_tuples == r0.n_tuples && rd.n_corres == r0.n_corres && rd.n_trials == r0.n_trials && rd.swapped == r0.swapped);
+    reg.setGlobalRegistrationTail(false);
+    const std::pair<bool, Mat4> back = reg.performGlobalRegistration();
+    EXPECT(std::memcmp(back.second.data(), got.second.data(), sizeof(double) * 16) == 0);
     reg.globalOptions().tuple_scale = 1.0f;
     const std::pair<bool, Mat4> none = reg.performGlobalRegistration(model, data);
     const mlh_fgr_result r1 = reg.lastGlobalResult();

@@ -2647,12 +2647,16 @@ public:
     // crosses the bus between constructLocalMap and performLocalRegistration
     std::pair<bool, Mat4> performGlobalRegistration()
     {
-        dev_.check(mlh_fgr_register(dev_.ctx(), &fgr_opts_, &fgr_last_));
+        dev_.check(fgr_tail_on_device_ ? mlh_fgr_register_device(dev_.ctx(), &fgr_opts_, &fgr_last_) : mlh_fgr_register(dev_.ctx(), &fgr_opts_, &fgr_last_));
         Mat4 T;
         for (int i = 0; i < 16; ++i) T[size_t(i)] = fgr_last_.T_relative[i];
         return std::make_pair(fgr_last_.accepted != 0, T);
     }
     const mlh_fgr_result &lastGlobalResult() const { return fgr_last_; }      // final_cost_normalize_, the counts and the host waits of the last call
+    // where the tuple test and OptimizePairwise of performGlobalRegistration() run: false (the default) on the host (mlh_fgr_register), true on the device
+    // (mlh_fgr_register_device: the same tuples, no pair record leaves HBM, one host wait; T_relative agrees within 1e-6)
+    void setGlobalRegistrationTail(bool onDevice) { fgr_tail_on_device_ = onDevice; }
+    bool globalRegistrationTailOnDevice() const { return fgr_tail_on_device_; }
 private:
     template <class CloudT> static const void *ptr_of(const CloudT &c) { return c.points.empty() ? nullptr : static_cast<const void *>(c.points.data()); }
     Device &dev_;
@@ -2660,6 +2664,7 @@ private:
     mlh_loop_result last_{};
     mlh_fgr_opts fgr_opts_ = [] { mlh_fgr_opts o; mlh_fgr_opts_default(&o); return o; }();
     mlh_fgr_result fgr_last_{};
+    bool fgr_tail_on_device_ = false;
 };
 
 // ------------------------------------------------------------------ the pose graph (mloam_loop: pose_graph.cpp:92-150, 491-653; keyframe.cpp:84-105)
