@@ -16,6 +16,7 @@
 #include "dev_math.hpp"
 #include "factor_dev.hpp"
 #include "tile_group.hpp"
+#include "wg_dev.hpp"
 
 namespace mlh {
 
@@ -68,14 +69,6 @@ struct CalibNeArgs {
     double *partial;        // tiles x CAL_OUT
 };
 
-// sum over the 64 lanes by a butterfly: every lane ends with the same bits, whatever the run
-__device__ __forceinline__ double calib_wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void calib_ne_kernel(CalibNeArgs G)
 {
     __shared__ double s_ext[16];
@@ -101,12 +94,12 @@ __global__ __launch_bounds__(256) void calib_ne_kernel(CalibNeArgs G)
 #pragma unroll
         for (int b = a; b < 7; ++b) {
             // row a of the upper triangle (b < 6), then its J^T r entry (b == 6): outputs 0..20 are the products in row-major order, 21..26 the gradient
-            const double sum = calib_wave_sum(v[a] * v[b]);
+            const double sum = wave_sum(v[a] * v[b]);
             const int dst = b < 6 ? o++ : 21 + a;
             if (lane == 0) s_w[wave][dst] = sum;
         }
-    { const double sum = calib_wave_sum(v[7]); if (lane == 0) s_w[wave][27] = sum; }
-    { const double sum = calib_wave_sum(v[8]); if (lane == 0) s_w[wave][28] = sum; }
+    { const double sum = wave_sum(v[7]); if (lane == 0) s_w[wave][27] = sum; }
+    { const double sum = wave_sum(v[8]); if (lane == 0) s_w[wave][28] = sum; }
     __syncthreads();
     if (k < CAL_OUT) G.partial[size_t(G.tile_pos[tile]) * CAL_OUT + k] = k < CAL_NSUM ? ((s_w[0][k] + s_w[1][k]) + s_w[2][k]) + s_w[3][k] : 0.0;
 }

@@ -15,6 +15,7 @@
 #include "ctx.hpp"
 #include "sort_dev.hpp"
 #include "stdsort_dev.hpp"
+#include "wg_dev.hpp"
 #include <algorithm>
 
 namespace mlh {
@@ -396,8 +397,7 @@ __global__ __launch_bounds__(LTPB) void label_kernel(LabelArgs A)
             if (lb <= 0) my_lf++;
         }
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) my_lf += __shfl_xor(my_lf, off);
+    my_lf = wave_sum(my_lf);
     if ((threadIdx.x & 63) == 0 && my_lf) atomicAdd(&s_cnt[3], my_lf);
     for (int t = threadIdx.x; t < STAGE_STRIDE; t += LTPB) A.stage[ring * STAGE_STRIDE + t] = s_stage[t];
     __syncthreads();
@@ -436,10 +436,7 @@ __global__ __launch_bounds__(256) void emit_kernel(EmitArgs A)
             acc[0] += c.x; acc[1] += c.y; acc[2] += c.z; acc[3] += c.w;
         }
 #pragma unroll
-        for (int l = 0; l < 4; ++l) {
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) acc[l] += __shfl_xor(acc[l], off);
-        }
+        for (int l = 0; l < 4; ++l) acc[l] = wave_sum(acc[l]);
         if (threadIdx.x < 4) {
             const int v = threadIdx.x == 0 ? acc[0] : (threadIdx.x == 1 ? acc[1] : (threadIdx.x == 2 ? acc[2] : acc[3]));
             s_off[threadIdx.x] = v;

@@ -23,6 +23,7 @@
 #include <cmath>
 #include "knn_dev.hpp"
 #include "fgr_host.hpp"
+#include "wg_dev.hpp"
 
 namespace mlh {
 
@@ -326,15 +327,6 @@ static_assert(sizeof(FgrTailRecord) == 136, "the tail's record");
 struct FgrTailHead { int32_t n_tuples, n_corres, n_trials, total, cap_segment, pad[3]; };
 constexpr size_t TAIL_HEAD_AT = 192, TAIL_BYTES = TAIL_HEAD_AT + sizeof(FgrTailHead);
 
-// inclusive prefix over the wavefront, lanes in order (integers: exact in any order)
-__device__ __forceinline__ int wave_incl_scan(int v)
-{
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(v, d); if (lane >= d) v += o; }
-    return v;
-}
-
 // seg_counts[segment] <- the accepted trials of the segment (0 for a segment behind the last trial). One workgroup per segment of the LARGEST pair count possible.
 __global__ __launch_bounds__(FGR_TT_TPB) void fgr_tuple_count_kernel(const uint64_t *__restrict__ table, const FgrPair *__restrict__ pairs, const int *__restrict__ n_pairs, int pair_cap,
                                                                      int swapped, float scale, uint64_t seed, int *__restrict__ seg_counts)
@@ -344,11 +336,8 @@ __global__ __launch_bounds__(FGR_TT_TPB) void fgr_tuple_count_kernel(const uint6
     long long b, e;
     fgr_tt_run(fgr_tt_total_trials(ncorr), blockIdx.x, threadIdx.x, &b, &e);
     int c = __popc(fgr_tt_run_mask(table, pairs, ncorr, swapped != 0, scale, seed, b, e));
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) c += __shfl_xor(c, m);
-    if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) { int tot = 0; for (int w = 0; w < FGR_TT_TPB / 64; ++w) tot += s_wave[w]; seg_counts[blockIdx.x] = tot; }
+    c = block_sum<FGR_TT_TPB / 64>(c, s_wave);
+    if (threadIdx.x == 0) seg_counts[blockIdx.x] = c;
 }
 
 // seg_base[s] <- the accepted trials in front of segment s (saturated at the cap: such a segment emits nothing); head <- the tuples kept, n_trials when the cap is
@@ -465,10 +454,7 @@ __device__ __forceinline__ void fgr_optimize_body(const FgrPair *__restrict__ pa
             }
         }
 #pragma unroll
-        for (int i = 0; i < FGR_OPT_SUMS; ++i) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) acc[i] += __shfl_xor(acc[i], m);
-        }
+        for (int i = 0; i < FGR_OPT_SUMS; ++i) acc[i] = wave_sum(acc[i]);
         if (lane == 0) {
 #pragma unroll
             for (int i = 0; i < FGR_OPT_SUMS; ++i) s_red[wave * FGR_OPT_SUMS + i] = acc[i];

@@ -9,6 +9,7 @@
 // and the entry points that own nothing but these launches: mlh_transform_*, mlh_fuse_*, mlh_fused_cloud (mlh_ctx::fused is this unit's), mlh_debug_bad_launch.
 #include "ctx.hpp"
 #include "dev_math.hpp"
+#include "wg_dev.hpp"
 #include <cfloat>
 
 namespace mlh {
@@ -126,22 +127,8 @@ __global__ __launch_bounds__(256) void fuse_append_kernel(FuseArgs A)
         m[0] = fminf(m[0], o.x); m[1] = fminf(m[1], o.y); m[2] = fminf(m[2], o.z);
         m[3] = fmaxf(m[3], o.x); m[4] = fmaxf(m[4], o.y); m[5] = fmaxf(m[5], o.z);
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { m[d] = fminf(m[d], __shfl_xor(m[d], off)); m[3 + d] = fmaxf(m[3 + d], __shfl_xor(m[3 + d], off)); }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int d = 0; d < 6; ++d) lds[threadIdx.x >> 6][d] = m[d];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int d = threadIdx.x;
-        float r = lds[0][d];
-        for (int w = 1; w < 4; ++w) r = d < 3 ? fminf(r, lds[w][d]) : fmaxf(r, lds[w][d]);
-        A.part[(kind * FUSE_BLOCKS + blockIdx.x) * 6 + d] = r;
-    }
+    float r;
+    if (block_fold_bounds<1>(m, lds, r)) A.part[(kind * FUSE_BLOCKS + blockIdx.x) * 6 + threadIdx.x] = r;
 }
 // the scan's thinned less-flat cloud -> fused SURF, its less-sharp corners -> fused CORNER (rings [ring_begin, ring_end)); counts on the device
 int fuse_append_launch(mlh_ctx *ctx, ScanBuf &sb, int ring_begin, int ring_end, int lidar_idx, const double ext_pose[7])
@@ -311,22 +298,8 @@ __global__ __launch_bounds__(256) void fused_publish_kernel(const int *__restric
             for (int d = 0; d < 6; ++d) v[k * 6 + d] = d < 3 ? fminf(v[k * 6 + d], q[d]) : fmaxf(v[k * 6 + d], q[d]);
         }
     }
-#pragma unroll
-    for (int c = 0; c < 12; ++c) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { const float o = __shfl_xor(v[c], off, 64); v[c] = (c % 6) < 3 ? fminf(v[c], o) : fmaxf(v[c], o); }
-    }
-    if ((t & 63) == 0) {
-#pragma unroll
-        for (int c = 0; c < 12; ++c) s_red[t >> 6][c] = v[c];
-    }
-    __syncthreads();
-    if (t < 12) {
-        const bool lo = (t % 6) < 3;
-        float r = s_red[0][t];
-        for (int w = 1; w < 4; ++w) r = lo ? fminf(r, s_red[w][t]) : fmaxf(r, s_red[w][t]);
-        h_box[t] = r;
-    }
+    float r;
+    if (block_fold_bounds<2>(v, s_red, r)) h_box[t] = r;
     if (t == 0) { h_cnt[0] = cnt2[0]; h_cnt[1] = cnt2[1]; }
     __threadfence_system();
     __syncthreads();

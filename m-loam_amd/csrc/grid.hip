@@ -14,6 +14,8 @@
 // totals before it itself instead of a separate single-workgroup scan launch.
 #include "ctx.hpp"
 #include "solve_host.hpp"
+#include "bounds_dev.hpp"
+#include "wg_dev.hpp"
 #include <cstdlib>
 #include <vector>
 #include <cmath>
@@ -21,53 +23,23 @@
 
 namespace mlh {
 
-__device__ __forceinline__ int float_order_key(float f)
-{
-    int k = __float_as_int(f);
-    return k >= 0 ? k : k ^ 0x7fffffff;
-}
-static inline float key_to_float(int k)
-{
-    int b = k >= 0 ? k : k ^ 0x7fffffff;
-    float f;
-    std::memcpy(&f, &b, sizeof(f));
-    return f;
-}
-
-// bounding box as order-preserving integer keys: one partial record per workgroup (no atomics: a few thousand wavefronts hammering six
+// bounding box as order-preserving integer keys (enc_f): one partial record per workgroup (no atomics: a few thousand wavefronts hammering six
 // words cost 0.5 ms on a 500 k map), folded by the host, which needs the box for the grid dimensions anyway
 constexpr int BOUNDS_BLOCKS = 128;
 constexpr float GRID_MARGIN_XY = 2.f, GRID_MARGIN_Z = 1.f;
 __global__ __launch_bounds__(256) void bounds_kernel(const float4 *__restrict__ pts, int n, int *__restrict__ partial)
 {
     __shared__ int lds[4][6];
-    int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+    int m[6] = {INT_MAX, INT_MAX, INT_MAX, INT_MIN, INT_MIN, INT_MIN};
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         float4 p = pts[i];
-        int kx = float_order_key(p.x), ky = float_order_key(p.y), kz = float_order_key(p.z);
-        mn[0] = min(mn[0], kx); mx[0] = max(mx[0], kx);
-        mn[1] = min(mn[1], ky); mx[1] = max(mx[1], ky);
-        mn[2] = min(mn[2], kz); mx[2] = max(mx[2], kz);
+        int kx = enc_f(p.x), ky = enc_f(p.y), kz = enc_f(p.z);
+        m[0] = min(m[0], kx); m[3] = max(m[3], kx);
+        m[1] = min(m[1], ky); m[4] = max(m[4], ky);
+        m[2] = min(m[2], kz); m[5] = max(m[5], kz);
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) {
-            mn[d] = min(mn[d], __shfl_xor(mn[d], off));
-            mx[d] = max(mx[d], __shfl_xor(mx[d], off));
-        }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int d = 0; d < 3; ++d) { lds[threadIdx.x >> 6][d] = mn[d]; lds[threadIdx.x >> 6][3 + d] = mx[d]; }
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int d = threadIdx.x;
-        int r = lds[0][d];
-        for (int w = 1; w < 4; ++w) r = d < 3 ? min(r, lds[w][d]) : max(r, lds[w][d]);
-        partial[blockIdx.x * 6 + d] = r;
-    }
+    int r;
+    if (block_fold_bounds<1>(m, lds, r)) partial[blockIdx.x * 6 + threadIdx.x] = r;
 }
 
 // ---- one job per map; kernels take both jobs and split their grid between them
@@ -208,25 +180,6 @@ __global__ __launch_bounds__(256) void pack_count_kernel(GridJobs G, PackJobs P)
     if (__ballot(bad) != 0ull && lane == 0) atomicOr(P.oob, 1 << job);
 }
 
-__device__ __forceinline__ int block_exclusive_scan_256(int v, int *lds, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) if (w < wave) base += lds[w];
-    total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return base + incl - v;
-}
-
 // in-place INCLUSIVE scan of A[i] = cell_start[i + 1], i in [0, ncell): chunk-local part (8 ints = 2 x int4 per thread).
 // Inclusive, so that cell_start[c + 1] = start of cell c + 1 and (with cell_start[0] = 0) the array is the exclusive prefix.
 __global__ __launch_bounds__(256) void scan_local_kernel(GridJobs G)
@@ -248,17 +201,16 @@ __global__ __launch_bounds__(256) void scan_local_kernel(GridJobs G)
     if (base < n_pad) v0 = A4[base / 4];
     if (base + 4 < n_pad) v1 = A4[base / 4 + 1];
     const int s = ((v0.x + v0.y) + (v0.z + v0.w)) + ((v1.x + v1.y) + (v1.z + v1.w));
-    long long occ_nz = 0, occ_sq = 0;                                    // occupancy statistics: one partial per workgroup, summed by occ_total()
+    long long occ[2] = {0, 0};                                           // occupancy statistics (non-empty cells, squared populations): one partial per workgroup, summed by occ_total()
     if (J.occ) {
-        occ_nz = (v0.x > 0) + (v0.y > 0) + (v0.z > 0) + (v0.w > 0) + (v1.x > 0) + (v1.y > 0) + (v1.z > 0) + (v1.w > 0);
-        occ_sq = (long long)v0.x * v0.x + (long long)v0.y * v0.y + (long long)v0.z * v0.z + (long long)v0.w * v0.w +
+        occ[0] = (v0.x > 0) + (v0.y > 0) + (v0.z > 0) + (v0.w > 0) + (v1.x > 0) + (v1.y > 0) + (v1.z > 0) + (v1.w > 0);
+        occ[1] = (long long)v0.x * v0.x + (long long)v0.y * v0.y + (long long)v0.z * v0.z + (long long)v0.w * v0.w +
                  (long long)v1.x * v1.x + (long long)v1.y * v1.y + (long long)v1.z * v1.z + (long long)v1.w * v1.w;
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { occ_nz += __shfl_xor(occ_nz, off); occ_sq += __shfl_xor(occ_sq, off); }
-        if ((threadIdx.x & 63) == 0) { lds_occ[2 * (threadIdx.x >> 6)] = occ_nz; lds_occ[2 * (threadIdx.x >> 6) + 1] = occ_sq; }
+        wave_sum(occ);
+        if ((threadIdx.x & 63) == 0) { lds_occ[2 * (threadIdx.x >> 6)] = occ[0]; lds_occ[2 * (threadIdx.x >> 6) + 1] = occ[1]; }
     }
     int total;
-    int ex = block_exclusive_scan_256(s, lds, total);
+    int ex = block_excl_scan<4>(s, lds, total);
     int4 o0, o1;
     ex += v0.x; o0.x = ex; ex += v0.y; o0.y = ex; ex += v0.z; o0.z = ex; ex += v0.w; o0.w = ex;
     ex += v1.x; o1.x = ex; ex += v1.y; o1.y = ex; ex += v1.z; o1.z = ex; ex += v1.w; o1.w = ex;
@@ -278,8 +230,7 @@ __device__ __forceinline__ void occ_total(long long *occ, int n_part, long long 
 {
     long long nz = 0, sq = 0;
     for (int i = threadIdx.x; i < n_part; i += 256) { nz += occ[2 + 2 * i]; sq += occ[3 + 2 * i]; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { nz += __shfl_xor(nz, off); sq += __shfl_xor(sq, off); }
+    nz = wave_sum(nz); sq = wave_sum(sq);
     if ((threadIdx.x & 63) == 0) { lds[2 * (threadIdx.x >> 6)] = nz; lds[2 * (threadIdx.x >> 6) + 1] = sq; }
     __syncthreads();
     if (threadIdx.x == 0) { occ[0] = lds[0] + lds[2] + lds[4] + lds[6]; occ[1] = lds[1] + lds[3] + lds[5] + lds[7]; }
@@ -297,7 +248,7 @@ __global__ __launch_bounds__(256) void scan_sums_kernel(GridJobs G)
         int i = start + threadIdx.x;
         int v = (i < J.nb_scan) ? J.block_sums[i] : 0;
         int total;
-        int ex = block_exclusive_scan_256(v, lds, total);
+        int ex = block_excl_scan<4>(v, lds, total);
         if (i < J.nb_scan) J.block_sums[i] = carry + ex;
         carry += total;
     }
@@ -317,11 +268,7 @@ __global__ __launch_bounds__(256) void scan_add_kernel(GridJobs G)
     } else {
         int s = 0;
         for (int i = threadIdx.x; i < b; i += 256) s += J.block_sums[i];
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
-        __syncthreads();
-        add = (lds[0] + lds[1]) + (lds[2] + lds[3]);
+        add = block_sum<4>(s, lds);
     }
     if (b == 0) {                                                        // first chunk: offset 0 -- the idle workgroup totals the occupancy statistics
         if (J.occ) {
@@ -371,7 +318,7 @@ static int bounds_finish(mlh_ctx *ctx, MapGrid &g, const int *hp, float min_matc
     for (int blk = 0; blk < grid_pts; ++blk)
         for (int d = 0; d < 3; ++d) { hb[d] = std::min(hb[d], hp[blk * 6 + d]); hb[3 + d] = std::max(hb[3 + d], hp[blk * 6 + 3 + d]); }
     float mn[3], mx[3];
-    for (int d = 0; d < 3; ++d) { mn[d] = key_to_float(hb[d]); mx[d] = key_to_float(hb[3 + d]); }
+    for (int d = 0; d < 3; ++d) { mn[d] = dec_f(hb[d]); mx[d] = dec_f(hb[3 + d]); }
     // a geometry becomes the kind's (and reusable by the next staging call) only once every check has passed and every buffer for it is sized: a refusal
     // leaves the kind without a box -- a "valid" box whose cell count does not fit an int, with cell arrays sized for another, would be built into by the
     // next cloud that fits it (make_job narrows ncell, the count pass adds into cell_start[c + 1] far outside the allocation)

@@ -12,6 +12,7 @@
 //   No float atomics, fixed summation order: two runs give the same bits. Per calibration: one launch, one device-to-pinned copy of the records, one host wait.
 #include "ctx.hpp"
 #include "initext_host.hpp"
+#include "wg_dev.hpp"
 
 namespace mlh {
 
@@ -41,10 +42,7 @@ struct IeBlockRed {
     template <int N> __device__ __forceinline__ void sum(double (&v)[N])
     {
         static_assert(N <= 4, "at most four sums at a time");
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1)
-#pragma unroll
-            for (int i = 0; i < N; ++i) v[i] += __shfl_xor(v[i], off);
+        wave_sum(v);
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
         if (lane == 0)
 #pragma unroll

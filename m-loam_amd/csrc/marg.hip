@@ -12,6 +12,7 @@
 // (n <= 90) and in HBM beyond that.
 #include "ctx.hpp"
 #include "dev_math.hpp"
+#include "wg_dev.hpp"
 
 namespace mlh {
 
@@ -142,7 +143,7 @@ constexpr int MARG_THREADS = 1024;
 
 __device__ __forceinline__ double block_max(double v, double *s_red)
 {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    v = wave_max(v);
     __syncthreads();                                    // s_red may still be read from the previous call
     if ((threadIdx.x & 63) == 0) s_red[threadIdx.x >> 6] = v;
     __syncthreads();

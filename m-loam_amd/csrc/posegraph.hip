@@ -31,6 +31,7 @@
 #include <string>
 #include <vector>
 #include "pg_host.hpp"
+#include "wg_dev.hpp"
 
 namespace mlh {
 
@@ -696,8 +697,7 @@ __global__ __launch_bounds__(PG_TPB) void pg_cback_kernel(PgDev P, int k)
     const double zl = zs[l];
     for (int rr = 0; rr < 16; ++rr) {
         const int j = jt * PG_PANEL + w * 16 + rr;
-        double v = P.C[size_t(j) * ld + size_t(k) * PG_PANEL + l] * zl;
-        for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+        const double v = wave_sum(P.C[size_t(j) * ld + size_t(k) * PG_PANEL + l] * zl);
         if (l == 0) P.zw[j] = (first ? P.C[size_t(j) * ld + m] : P.zw[j]) - v;
     }
 }

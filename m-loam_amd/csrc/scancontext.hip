@@ -14,6 +14,7 @@
 // mlh_sc_detect: those four + the marker launch of the wait, one copy, ONE host wait -- whatever the size of the store and num_candidates.
 // No float atomics: every cross-workgroup combination is an integer max or an ordered reduction.
 #include "ctx.hpp"
+#include "wg_dev.hpp"
 #include <algorithm>
 #include <cmath>
 
@@ -246,8 +247,7 @@ __global__ __launch_bounds__(256) void sc_score_kernel(ScScoreArgs A)
             sum += dot / (n1 * n2);
             cnt += 1.0;
         }
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { sum += __shfl_xor(sum, o); cnt += __shfl_xor(cnt, o); }
+        sum = wave_sum(sum); cnt = wave_sum(cnt);
         const double dist = 1.0 - sum / cnt;              // no effective column: 0 / 0, a NaN that never wins
         if (sc_better(dist, sh, best, best_s)) { best = dist; best_s = sh; }
     }

@@ -23,6 +23,7 @@
 #include "ctx.hpp"
 #include <mutex>
 #include "alive_pool.hpp"
+#include "wg_dev.hpp"
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -280,13 +281,7 @@ __global__ __launch_bounds__(SEG_ROW_TPB) void seg_rows_kernel(SegRows A)
         const int col = int(unsigned(k));
         if (col < hs) s_order[col] = full ? i : -1;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) mine += __shfl_xor(mine, off);
-    if (lane == 0) s_wave_tot[wave] = mine;
-    __syncthreads();
-    int size0 = 0;
-#pragma unroll
-    for (int w = 0; w < SEG_ROW_TPB / 64; ++w) size0 += s_wave_tot[w];
+    const int size0 = block_sum<SEG_ROW_TPB / 64>(mine, s_wave_tot);
     __syncthreads();
     // the erasure list: outlier pixels, columns ascending -> their fill-time positions (a block-wide compaction: thread t owns columns [cpt t, cpt (t + 1)))
     int n_erase = 0;
@@ -301,9 +296,7 @@ __global__ __launch_bounds__(SEG_ROW_TPB) void seg_rows_kernel(SegRows A)
                 if ((A.outmask[px >> 5] >> (px & 31)) & 1u) { flags |= 1 << u; ++cnt; }
             }
         }
-        int incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+        const int incl = wave_incl_scan(cnt);
         if (lane == 63) s_wave_tot[wave] = incl;
         __syncthreads();
         int base = 0;
@@ -344,9 +337,7 @@ __global__ __launch_bounds__(SEG_ROW_TPB) void seg_rows_kernel(SegRows A)
             }
             if (start) { flags |= 1 << u; ++cnt; }
         }
-        int incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+        const int incl = wave_incl_scan(cnt);
         if (lane == 63) s_wave_tot[wave] = incl;
         __syncthreads();                                               // (also: every read of s_order as positions lies before this barrier)
         int base = 0;
@@ -362,9 +353,7 @@ __global__ __launch_bounds__(SEG_ROW_TPB) void seg_rows_kernel(SegRows A)
         else if (size0 > lo) w = (1ull << (size0 - lo)) - 1ull;
         s_alive[lane] = w;
         const int pc = __popcll(w);
-        int incl = pc;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+        const int incl = wave_incl_scan(pc);
         s_pref[lane] = incl - pc;
         if (lane == 63) s_pref[64] = incl;
         if (lane == 0) { s_misc[0] = size0; s_misc[1] = 0; }
@@ -436,9 +425,7 @@ __global__ __launch_bounds__(SEG_ROW_TPB) void seg_rows_kernel(SegRows A)
         __syncthreads();
         if (wave == 0) {
             const int pc = __popcll(s_alive[lane]);
-            int incl = pc;
-#pragma unroll
-            for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+            const int incl = wave_incl_scan(pc);
             s_pref[lane] = incl - pc;
             if (lane == 63) s_pref[64] = incl;
             if (lane == 0) { s_misc[0] = cnt0 - s_misc[1]; s_misc[1] = 0; }
@@ -451,9 +438,7 @@ __global__ __launch_bounds__(SEG_ROW_TPB) void seg_rows_kernel(SegRows A)
         const int i0 = t * ipt;
         int cnt = 0;
         for (int u = 0; u < ipt; ++u) { const int i = i0 + u; if (i < size0 && ((s_alive[i >> 6] >> (i & 63)) & 1ull)) ++cnt; }
-        int incl = cnt;
-#pragma unroll
-        for (int off = 1; off < 64; off <<= 1) { const int v = __shfl_up(incl, off); if (lane >= off) incl += v; }
+        const int incl = wave_incl_scan(cnt);
         if (lane == 63) s_wave_tot[wave] = incl;
         __syncthreads();
         int base = 0;

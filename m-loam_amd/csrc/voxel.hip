@@ -18,6 +18,7 @@
 #include "dev_math.hpp"
 #include "sort_dev.hpp"
 #include "uct_dev.hpp"
+#include "wg_dev.hpp"
 #include <cfloat>
 
 namespace mlh {
@@ -80,11 +81,7 @@ __global__ __launch_bounds__(RV_TPB) void ring_voxel_kernel(RingVoxelArgs A)
             if (PTS_IN_LDS) spts[tid * KPL + r] = p[r];
         }
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { m[d] = fminf(m[d], __shfl_xor(m[d], o)); m[3 + d] = fmaxf(m[3 + d], __shfl_xor(m[3 + d], o)); }
-    }
+    wave_fold_bounds<1>(m);
     if (lane == 0) {
 #pragma unroll
         for (int d = 0; d < 6; ++d) s_red[wave][d] = m[d];
@@ -147,7 +144,7 @@ __global__ __launch_bounds__(RV_TPB) void ring_voxel_kernel(RingVoxelArgs A)
         start[r] = e < n && (e == 0 || prev != vox);
         mine += start[r] ? 1 : 0;
     }
-    int incl = mine;
+    int incl = mine;                                   // (the ladder stays spelled out here: through wave_incl_scan three of the nine instances grow by two instructions)
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(incl, o); if (lane >= o) incl += t; }
     if (lane == 63) s_scan[wave] = incl;
@@ -188,8 +185,7 @@ __global__ __launch_bounds__(256) void ring_vox_compact_kernel(const float4 *__r
     if (threadIdx.x < 64) {
         int acc = 0;
         for (int r = threadIdx.x; r < ring; r += 64) acc += ring_vox[r];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+        acc = wave_sum(acc);
         if (threadIdx.x == 0) s_dst = acc;
     }
     __syncthreads();
@@ -599,29 +595,12 @@ __device__ __forceinline__ void vsp_chunk(const VspArgs &A, int c, int &lo, int 
 }
 __device__ __forceinline__ bool vsp_head(const VspArgs &A, int i) { return i == 0 || i == A.n0 || A.keys[i] != A.keys[i - 1]; }
 
-// block-wide exclusive scan of one int per thread (256 threads); total = the sum
-__device__ __forceinline__ int vsp_block_scan(int v, int *lds4, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) { const int t = __shfl_up(incl, off); if (lane >= off) incl += t; }
-    if (lane == 63) lds4[wave] = incl;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) if (w < wave) base += lds4[w];
-    total = lds4[0] + lds4[1] + lds4[2] + lds4[3];
-    __syncthreads();
-    return base + incl - v;
-}
 // sum of a[0 .. upto) over the workgroup (every thread gets it) and, on the way, of a[0 .. upto2)
 __device__ __forceinline__ void vsp_prefix2(const int *a, int upto, int upto2, int *lds8, int &s1, int &s2)
 {
     int p1 = 0, p2 = 0;
     for (int j = threadIdx.x; j < max(upto, upto2); j += VSP_TPB) { const int v = a[j]; p1 += j < upto ? v : 0; p2 += j < upto2 ? v : 0; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { p1 += __shfl_xor(p1, off); p2 += __shfl_xor(p2, off); }
+    p1 = wave_sum(p1); p2 = wave_sum(p2);
     if ((threadIdx.x & 63) == 0) { lds8[threadIdx.x >> 6] = p1; lds8[4 + (threadIdx.x >> 6)] = p2; }
     __syncthreads();
     s1 = lds8[0] + lds8[1] + lds8[2] + lds8[3];
@@ -637,8 +616,7 @@ __global__ __launch_bounds__(VSP_TPB) void vsp_heads_kernel(VspArgs A)
     int cnt = 0;
 #pragma unroll
     for (int u = 0; u < VSP_PER; ++u) { const int i = lo + threadIdx.x * VSP_PER + u; cnt += (i < hi && vsp_head(A, i)) ? 1 : 0; }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) cnt += __shfl_xor(cnt, off);
+    cnt = wave_sum(cnt);
     if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = cnt;
     __syncthreads();
     if (threadIdx.x == 0) A.heads[blockIdx.x] = lds4[0] + lds4[1] + lds4[2] + lds4[3];
@@ -658,7 +636,7 @@ __global__ __launch_bounds__(VSP_TPB) void vsp_aggregate_kernel(VspArgs A)
 #pragma unroll
     for (int u = 0; u < VSP_PER; ++u) { const int i = lo + threadIdx.x * VSP_PER + u; if (i < hi && vsp_head(A, i)) { flags |= 1u << u; ++cnt; } }
     int h;
-    int li = vsp_block_scan(cnt, lds4, h);
+    int li = block_excl_scan<4>(cnt, lds4, h);
 #pragma unroll
     for (int u = 0; u < VSP_PER; ++u) if (flags & (1u << u)) s_head[li++] = lo + threadIdx.x * VSP_PER + u;
     __syncthreads();
@@ -706,11 +684,8 @@ __global__ __launch_bounds__(VSP_TPB) void vsp_aggregate_kernel(VspArgs A)
         A.keep[slot] = keep;
         kept += keep;
     }
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) kept += __shfl_xor(kept, off);
-    if ((threadIdx.x & 63) == 0) lds4[threadIdx.x >> 6] = kept;
-    __syncthreads();
-    if (threadIdx.x == 0) A.kept[blockIdx.x] = lds4[0] + lds4[1] + lds4[2] + lds4[3];
+    kept = block_sum<4>(kept, lds4);
+    if (threadIdx.x == 0) A.kept[blockIdx.x] = kept;
 }
 
 __global__ __launch_bounds__(VSP_TPB) void vsp_features_kernel(VspArgs A)
@@ -736,7 +711,7 @@ __global__ __launch_bounds__(VSP_TPB) void vsp_features_kernel(VspArgs A)
 #pragma unroll
     for (int u = 0; u < VSP_PER; ++u) { const int k = threadIdx.x * VSP_PER + u; if (k < h && A.keep[slot0 + k]) { flags |= 1 << u; ++cnt; } }
     int total;
-    int dst = kept0 + vsp_block_scan(cnt, lds4, total);
+    int dst = kept0 + block_excl_scan<4>(cnt, lds4, total);
     const bool second = c >= A.nch0;
     for (int u = 0; u < VSP_PER; ++u) {
         if (!(flags & (1 << u))) continue;

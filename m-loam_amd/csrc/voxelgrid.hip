@@ -16,6 +16,7 @@
 #include "ctx.hpp"
 #include "std_sort_mt.hpp"
 #include "bounds_dev.hpp"
+#include "wg_dev.hpp"
 #include <algorithm>
 #include <cfloat>
 #include <cmath>
@@ -27,25 +28,6 @@ namespace mlh {
 
 constexpr int VS_ITEMS = 8, VS_CHUNK = 256 * VS_ITEMS;
 
-__device__ __forceinline__ int vblock_scan(int v, int *lds, int &total)
-{
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int incl = v;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        int t = __shfl_up(incl, off);
-        if (lane >= off) incl += t;
-    }
-    if (lane == 63) lds[wave] = incl;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) if (w < wave) base += lds[w];
-    total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return base + incl - v;
-}
-
 // generic in-place exclusive scan of int data[0..n): local / sums / add
 __global__ __launch_bounds__(256) void vscan_local_kernel(int *__restrict__ data, long long n, int *__restrict__ sums)
 {
@@ -55,7 +37,7 @@ __global__ __launch_bounds__(256) void vscan_local_kernel(int *__restrict__ data
 #pragma unroll
     for (int k = 0; k < VS_ITEMS; ++k) { v[k] = (base + k < n) ? data[base + k] : 0; s += v[k]; }
     int total;
-    int ex = vblock_scan(s, lds, total);
+    int ex = block_excl_scan<4>(s, lds, total);
 #pragma unroll
     for (int k = 0; k < VS_ITEMS; ++k) { if (base + k < n) data[base + k] = ex; ex += v[k]; }
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
@@ -68,7 +50,7 @@ __global__ __launch_bounds__(256) void vscan_sums_kernel(int *__restrict__ sums,
         const int i = start + threadIdx.x;
         const int v = (i < nb) ? sums[i] : 0;
         int total;
-        const int ex = vblock_scan(v, lds, total);
+        const int ex = block_excl_scan<4>(v, lds, total);
         if (i < nb) sums[i] = carry + ex;
         carry += total;
     }
@@ -91,7 +73,7 @@ __global__ __launch_bounds__(256) void vscan_popc_local_kernel(const unsigned *_
 #pragma unroll
     for (int k = 0; k < VS_ITEMS; ++k) { v[k] = (base + k < n) ? __popc(mask[base + k]) : 0; s += v[k]; }
     int total;
-    int ex = vblock_scan(s, lds, total);
+    int ex = block_excl_scan<4>(s, lds, total);
 #pragma unroll
     for (int k = 0; k < VS_ITEMS; ++k) { if (base + k < n) out[base + k] = ex; ex += v[k]; }
     if (threadIdx.x == 0) sums[blockIdx.x] = total;
@@ -111,8 +93,7 @@ __global__ __launch_bounds__(256) void vscan_reduce_kernel(const int *__restrict
     int s = 0;
 #pragma unroll
     for (int k = 0; k < VS_ITEMS; ++k) s += (base + k < n) ? vs_item<POPC>(in, base + k) : 0;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+    s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) lds[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) sums[blockIdx.x] = lds[0] + lds[1] + lds[2] + lds[3];
@@ -123,15 +104,14 @@ __global__ __launch_bounds__(256) void vscan_final_kernel(const int *in, int *ou
     __shared__ int lds[4], lds_off[4];
     int acc = 0;
     for (int j = threadIdx.x; j < int(blockIdx.x); j += 256) acc += sums[j];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
+    acc = wave_sum(acc);
     if ((threadIdx.x & 63) == 0) lds_off[threadIdx.x >> 6] = acc;
     const long long base = (long long)blockIdx.x * VS_CHUNK + threadIdx.x * VS_ITEMS;
     int v[VS_ITEMS], s = 0;
 #pragma unroll
     for (int k = 0; k < VS_ITEMS; ++k) { v[k] = (base + k < n) ? vs_item<POPC>(in, base + k) : 0; s += v[k]; }
     int total;
-    int ex = vblock_scan(s, lds, total);            // (its barriers also publish lds_off)
+    int ex = block_excl_scan<4>(s, lds, total);            // (its barriers also publish lds_off)
     const int offset = lds_off[0] + lds_off[1] + lds_off[2] + lds_off[3];
     ex += offset;
 #pragma unroll
@@ -388,22 +368,8 @@ __global__ __launch_bounds__(256) void vbounds_kernel(const unsigned char *src, 
 #pragma unroll
         for (int d = 0; d < 3; ++d) { m[d] = fminf(m[d], p[d]); m[3 + d] = fmaxf(m[3 + d], p[d]); }
     }
-#pragma unroll
-    for (int d = 0; d < 3; ++d) {
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) { m[d] = fminf(m[d], __shfl_xor(m[d], off)); m[3 + d] = fmaxf(m[3 + d], __shfl_xor(m[3 + d], off)); }
-    }
-    if ((threadIdx.x & 63) == 0) {
-#pragma unroll
-        for (int d = 0; d < 6; ++d) lds[threadIdx.x >> 6][d] = m[d];
-    }
-    __syncthreads();
-    if (threadIdx.x < 6) {
-        const int d = threadIdx.x;
-        float r = lds[0][d];
-        for (int w = 1; w < 4; ++w) r = d < 3 ? fminf(r, lds[w][d]) : fmaxf(r, lds[w][d]);
-        partial[blockIdx.x * 6 + d] = r;
-    }
+    float r;
+    if (block_fold_bounds<1>(m, lds, r)) partial[blockIdx.x * 6 + threadIdx.x] = r;
 }
 
 // known_bounds: the exact min/max of the points if the caller already has them (skips the bounds pass and its round trip).
