@@ -475,6 +475,19 @@ int mlh_calib_evaluate(mlh_ctx *ctx, const double *exts, int n_ext, double *resi
  * mlh_sc_add_keyframe: the same from keyframe `key` of the store of (f5) / (f7): its surf, corner and outlier clouds device to device, its stored translation.
  *   DEPARTURE: the mapper's store has no full cloud, so these descriptors are built from thinned features: comparable with each other, not with descriptors of
  *   full clouds.
+ * mlh_sc_add_keyframes (row f17: the per-keyframe addKeyFrameIntoDB loop of loadPoseGraph / loadKeyFrame, pose_graph.cpp:696-781, 225-279, 77-90, in one call):
+ *   DEFINED AS n calls of mlh_sc_add_keyframe(first_key + i), i = 0..n-1. Reproduced bit for bit: every entry's descriptor, ring key, sector key and column norms,
+ *   its position, points_host_decided, points_skipped and the store's capacity (the buffers grow ONCE, to the capacity the single adds would have doubled their
+ *   way to). DEPARTURE: last_host_decided / last_skipped are those of the whole batch. *first_index_out (may be NULL) <- the index of the first new entry; n == 0
+ *   changes nothing; first_key < 0, n < 0 or first_key + n beyond the stored keyframes: MLH_ERR_INVALID, nothing changed. A batch holds fewer than 2^31 points.
+ *   Three launches and ONE host wait whatever n (descriptor kernel, the marker of the wait, finish kernel); one more of each only when the batch leaves more
+ *   than 2048 points undecided, as the single add does; a batch without a point launches the finish kernel alone. CHOSEN: the host cuts each keyframe's points
+ *   (surf, corner, outlier back to back) into chunks of a multiple of 256 points, as many per keyframe as bring the grid to two workgroups per compute unit
+ *   when n alone does not, at most 64; a workgroup builds its chunk's cells in LDS and merges them into the entry's slot with integer max, so the result does not
+ *   depend on the cutting. CHOSEN: the undecided points of the whole batch share one list (capacity: the batch's points) and one counter; a point's entry
+ *   travels in a parallel int array, its ring in the record's fourth word as in the single add. The host decides them with its libm and groups the verdicts by
+ *   entry; the finish kernel runs one workgroup per entry. mlh_sc_last_batch reports the last batch of the context (zero before the first, and after
+ *   mlh_sc_reset).
  * mlh_sc_detect = detectLoopClosureID(que_index) + detectLoop's rejection. Five launches and one copy whatever the size of the store and num_candidates (key
  *   distances, selection, one workgroup per candidate, the ordered argmin, the marker of the wait) and ONE host wait. A result that the distance test rejects keeps
  *   score, shift, yaw and nearest_index, has match_index -1 and rejected_by_distance 1. The early return gives {-1, score -1, yaw 0, nearest -1}.
@@ -521,6 +534,18 @@ void mlh_sc_opts_default(mlh_sc_opts *o);    /* mloam_loop/config/config_loop_re
 int mlh_sc_reset(mlh_ctx *ctx, const mlh_sc_opts *opts);
 int mlh_sc_add(mlh_ctx *ctx, const void *const *clouds, const int32_t *n, int n_clouds, int stride_bytes, int mem, const double *position, int32_t *index_out);
 int mlh_sc_add_keyframe(mlh_ctx *ctx, int32_t key, int32_t *index_out);
+typedef struct mlh_sc_batch_info {
+    int32_t n_entries, n_chunks;     /* of the last mlh_sc_add_keyframes: entries added, workgroups of its descriptor kernel */
+    int32_t launches, host_waits;    /* kernel launches (the waits' markers included) and host waits it took */
+    int32_t first_index;             /* index of its first entry */
+    int32_t chunk_points;            /* the plan's constants: a chunk holds a multiple of this many points (but an entry's last) ... */
+    int32_t max_chunks_per_entry;    /* ... an entry is cut into at most this many ... */
+    int32_t target_workgroups;       /* ... and only while the grid is below this: two per compute unit */
+    int64_t n_points;
+    int64_t points_host_decided, points_skipped;
+} mlh_sc_batch_info;
+int mlh_sc_add_keyframes(mlh_ctx *ctx, int32_t first_key, int32_t n, int32_t *first_index_out);
+int mlh_sc_last_batch(mlh_ctx *ctx, mlh_sc_batch_info *out);
 int mlh_sc_detect(mlh_ctx *ctx, int32_t que_index, mlh_sc_result *result);
 int mlh_sc_candidates(mlh_ctx *ctx, int32_t que_index, int32_t prefix, int32_t *idx_out, float *d2_out, int32_t *n_out);
 int mlh_sc_distance(mlh_ctx *ctx, int32_t i, int32_t j, double *dist, int32_t *shift);
@@ -765,8 +790,9 @@ int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
  * 136-147, 491-653) with the factor RelativeRTError (mloam_loop/include/mloam_loop/pose_graph.h:290-352) under ceres::QuaternionParameterization. A context keeps, per
  * keyframe and in HBM, one 176-byte record: pose_w_, last_pose_w_ (KeyFrame::updatePose, keyframe.cpp:89-93), loop_info_ (each [t, q(xyzw)], f64) and loop_index_
  * (-1: has_loop_ false); the host keeps global_index_, earliest_loop_index_ and a mirror of the loop indices. The optimisation thread with its 2 s sleep, the
- * mutexes, updatePath / publish*, savePoseGraph / loadPoseGraph's files and the visualisation stay with the caller. Ceres is not available to this project: its
- * trust-region policy is the project's Ceres-shaped Levenberg-Marquardt of the other solves, and what csrc/pg_host.hpp restates of Ceres 1.12 (QuaternionProduct, QuaternionRotatePoint,
+ * mutexes, updatePath / publish* and the visualisation stay with the caller; savePoseGraph / loadPoseGraph are section (f17): the session image. The file
+ * itself (fopen / fwrite of the image's bytes) is the caller's or the facade's. Ceres is not available to this project: its trust-region policy is the
+ * project's Ceres-shaped Levenberg-Marquardt of the other solves, and what csrc/pg_host.hpp restates of Ceres 1.12 (QuaternionProduct, QuaternionRotatePoint,
  * QuaternionParameterization's Plus and Jacobian, HuberLoss, Corrector) is from memory of that source; the header's comment lists each.
  * Every entry but the bookkeeping ones: MLH_ERR_STATE while a solve submitted with mlh_*_begin is uncollected, MLH_ERR_UNSUPPORTED under a communicator.
  * mlh_pg_opts_default: max_num_iterations 5 (cpp:522), 4 sequential edges (cpp:555), t_var 0.1, q_var 0.01 (cpp:566, 581), HuberLoss(1.0) (cpp:525). Options are
@@ -1512,6 +1538,59 @@ int mlh_p2p_comm_init(mlh_ctx *ctx, int n_ranks, int rank, const void *ipc_handl
 int mlh_comm_finalize(mlh_ctx *ctx);
 /* in-place sum of n doubles (HOST buffer, any n) over the ranks -- the standalone "mlh_allreduce_normal_eq" of SURVEY 8b */
 int mlh_allreduce_f64(mlh_ctx *ctx, double *host_inout, int n);
+
+/* ---------------------------------------------------------------- (f17) the session image: a mapping session saved and restored
+ * What PoseGraph::savePoseGraph (mloam_loop/src/pose_graph.cpp:655-694) and loadPoseGraph (cpp:696-781, through loadKeyFrame, cpp:225-279, and addKeyFrameIntoDB,
+ * cpp:77-90) keep over a restart: every keyframe with its clouds, the place index and the pose graph. Here: one versioned, checksummed, canonical byte image of
+ * the keyframe store of (f5) / (f7) / (f15), the Scan Context store of (f11) and the pose graph of (f14); csrc/session_host.hpp states the format.
+ * Reproduced: what the reference's files carry per keyframe -- pose, the clouds, the loop edge (index and relative pose) -- and that a loaded map answers like the
+ *   one that was saved: after an import every entry point of (f5) .. (f15) gives the bits it gave on the exporting context.
+ * CHOSEN: one binary image instead of pose_graph.txt + four .pcd files per keyframe; the format is this project's own. The image also carries what the reference
+ *   recomputes on load: the Scan Context entries with the period counter and the searched prefix (a loaded store answers mlh_sc_detect as the saved one would
+ *   have, stale prefix included), and each keyframe's covariance. A caller that wants the index rebuilt instead -- other num_ring / num_sector, or an image
+ *   without the SC section -- imports KEYFRAMES | PG, calls mlh_sc_reset and mlh_sc_add_keyframes(0, K): loadPoseGraph's addKeyFrameIntoDB loop in one call.
+ * CHOSEN: the image is CANONICAL: the clouds are stored key by key (surf, corner, outlier) whatever order the store's arena got them in (outlier clouds are
+ *   attached later), and the local-map cache, the map clouds and all scratch stay out, so two contexts with the same content give the same bytes whatever their
+ *   call histories, and export(import(image)) == image. (The SC section carries the store's statistics counters; last_host_decided / last_skipped are those of the
+ *   last add, so a store filled by mlh_sc_add_keyframes and one filled by single adds differ in those two words and in nothing else.)
+ * DEPARTURE: not in the image, because transient: the odometry window, the calibration store, the marginalisation prior, the initial-extrinsics state. No PCD or
+ *   text formats, no compression, little-endian hosts only, no import from another context's device memory.
+ * Checksum of a section of u32 words w_i: sum (w_i XOR 0x9E3779B9) (2 i + 1) mod 2^64 -- an integer sum, taken on the device in any order with the same bits.
+ * mlh_session_export_size: the bytes an export of `sections` (an OR of MLH_SESSION_*; KEYFRAMES stands for the keyframes and their points) takes now.
+ * mlh_session_export: the image into dst (`mem`: MLH_MEM_HOST or MLH_MEM_DEVICE), *written <- its length. capacity too small: MLH_ERR_INVALID, *written <- the
+ *   length needed, nothing touched. MLH_SESSION_SC before the first mlh_sc_reset: MLH_ERR_STATE. ONE pack launch whatever the number of keyframes: 256-record
+ *   tiles that never straddle a cloud; a thread moves one 16-byte record from the store's arena to its canonical place in a staging image and adds its four
+ *   checksum terms, the workgroup's sum goes to the section's word by one 64-bit integer atomic add (order-independent: no float atomics). The SC and PG
+ *   sections are copied into the staging image device to device (a fixed number of copies) and checksummed there by the same launch. Then one copy to dst and ONE
+ *   host wait (for a device dst one more, behind the 208-byte header, which is written last from the read-back checksums). Beside a solve submitted with
+ *   mlh_*_begin: correct, but enqueued behind the solve on the context's stream, as mlh_local_map_assemble.
+ * An export refuses what no import would take: 2^31 or more stored points is MLH_ERR_UNSUPPORTED before anything runs; an image written into host memory is held
+ *   to the import's validation before the call returns (a pose graph with a non-finite pose: MLH_ERR_STATE); a device destination is not read back. The staging
+ *   image belongs to the call: neither an export nor an import leaves an image-sized buffer in the context.
+ * mlh_session_inspect: host only, no context: validates the header, the section table and every section's contents (bounds, overlaps, record sizes, counts
+ *   against lengths, n[] >= 0, finite poses, the SC options as mlh_sc_reset does, loop indices, max_loops <= MLH_PG_LOOPS_LIMIT, every padding byte zero) AND the payload checksums.
+ * mlh_session_import: the same validation on the host before the context is touched (the payload checksums excepted), the requested sections uploaded into NEW
+ *   buffers, their checksums taken on the device by the pack kernel; only if every one matches are the buffers swapped into the stores: the keyframe store as
+ *   mlh_keyframes_reset followed by the saves would leave it (offsets = the prefix sums, cache and map clouds empty); the SC store with its options, entries,
+ *   positions, period counter, searched prefix and counters; the pose graph with count, earliest loop and the loop indices, max_loops raised as by mlh_pg_reserve
+ *   when the image's is larger. Any failure -- a corrupt image is MLH_ERR_INVALID with the reason in mlh_last_error -- leaves the context exactly as it was; a
+ *   requested section the image lacks is MLH_ERR_INVALID; stores not named in `sections` are untouched. ONE host wait, launches independent of the keyframes.
+ * mlh_session_last_info: the last successful export or import of the context (zeroes before). */
+enum { MLH_SESSION_KEYFRAMES = 1, MLH_SESSION_SC = 2, MLH_SESSION_PG = 4 };
+typedef struct mlh_session_info {
+    uint32_t version;
+    uint32_t sections;               /* MLH_SESSION_* the image holds (import: those imported) */
+    int32_t launches, host_waits;    /* of the export / import (mlh_session_inspect: 0) */
+    int64_t total_bytes;
+    int64_t count[4];                /* per stored section -- keyframes, points, Scan Context entries, pose-graph keyframes --: elements, */
+    int64_t bytes[4];                /* ... bytes, */
+    uint64_t checksum[4];            /* ... checksum; zero for an absent section */
+} mlh_session_info;
+int mlh_session_export_size(mlh_ctx *ctx, uint32_t sections, size_t *bytes);
+int mlh_session_export(mlh_ctx *ctx, uint32_t sections, void *dst, size_t capacity, int mem, size_t *written);
+int mlh_session_inspect(const void *image, size_t bytes, mlh_session_info *out);
+int mlh_session_import(mlh_ctx *ctx, const void *image, size_t bytes, uint32_t sections, mlh_session_info *out);
+int mlh_session_last_info(mlh_ctx *ctx, mlh_session_info *out);
 
 /* host-side helpers mirroring the reference's small functions (no GPU work) */
 /* PoseLocalParameterization::Plus with V_update_ (row-major 6x6; NULL = identity) */

@@ -154,6 +154,39 @@ class ScStoreInfo(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_ if k != "reserved"}
 
 
+class ScBatchInfo(C.Structure):
+    """mlh_sc_batch_info"""
+    _fields_ = [("n_entries", C.c_int32), ("n_chunks", C.c_int32), ("launches", C.c_int32), ("host_waits", C.c_int32), ("first_index", C.c_int32),
+                ("chunk_points", C.c_int32), ("max_chunks_per_entry", C.c_int32), ("target_workgroups", C.c_int32),
+                ("n_points", C.c_int64), ("points_host_decided", C.c_int64), ("points_skipped", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+SESSION_KEYFRAMES, SESSION_SC, SESSION_PG = 1, 2, 4
+SESSION_ALL = SESSION_KEYFRAMES | SESSION_SC | SESSION_PG
+
+
+class SessionInfo(C.Structure):
+    """mlh_session_info; the arrays are per stored section: keyframes, points, Scan Context entries, pose-graph keyframes"""
+    _fields_ = [("version", C.c_uint32), ("sections", C.c_uint32), ("launches", C.c_int32), ("host_waits", C.c_int32), ("total_bytes", C.c_int64),
+                ("count", C.c_int64 * 4), ("bytes", C.c_int64 * 4), ("checksum", C.c_uint64 * 4)]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k in ("count", "bytes", "checksum") else getattr(self, k)) for k, _ in self._fields_}
+
+
+def session_inspect(image) -> dict:
+    """the header and section table of a session image (bytes or a uint8 array), validated on the host, payload checksums included (mlh_session_inspect)"""
+    buf = np.frombuffer(bytes(image), np.uint8) if not isinstance(image, np.ndarray) else np.ascontiguousarray(image, np.uint8)
+    info = SessionInfo()
+    rc = load_library().mlh_session_inspect(buf.ctypes.data_as(C.c_void_p) if len(buf) else None, len(buf), C.byref(info))
+    if rc != 0:
+        raise MlhError(f"mlh error {rc}: not a valid session image")
+    return info.as_dict()
+
+
 def sc_opts(**kw) -> ScOpts:
     """mlh_sc_opts_default (config_loop_realvehicle.yaml), then the given fields"""
     o = ScOpts()
@@ -482,6 +515,13 @@ def load_library():
     lib.mlh_sc_reset.argtypes = [vp, C.POINTER(ScOpts)]
     lib.mlh_sc_add.argtypes = [vp, vp, vp, ci, ci, ci, vp, C.POINTER(C.c_int32)]
     lib.mlh_sc_add_keyframe.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
+    lib.mlh_sc_add_keyframes.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(C.c_int32)]
+    lib.mlh_sc_last_batch.argtypes = [vp, C.POINTER(ScBatchInfo)]
+    lib.mlh_session_export_size.argtypes = [vp, C.c_uint32, C.POINTER(C.c_size_t)]
+    lib.mlh_session_export.argtypes = [vp, C.c_uint32, vp, C.c_size_t, ci, C.POINTER(C.c_size_t)]
+    lib.mlh_session_inspect.argtypes = [vp, C.c_size_t, C.POINTER(SessionInfo)]
+    lib.mlh_session_import.argtypes = [vp, vp, C.c_size_t, C.c_uint32, C.POINTER(SessionInfo)]
+    lib.mlh_session_last_info.argtypes = [vp, C.POINTER(SessionInfo)]
     lib.mlh_sc_detect.argtypes = [vp, C.c_int32, C.POINTER(ScResult)]
     lib.mlh_sc_candidates.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, C.POINTER(C.c_int32)]
     lib.mlh_sc_distance.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(cd), C.POINTER(C.c_int32)]
@@ -581,12 +621,13 @@ EXPORTED_SYMBOLS = [
     "mlh_window_build_local_map", "mlh_window_map_cloud",
     "mlh_window_prior_set", "mlh_window_prior_get", "mlh_window_prior_clear", "mlh_window_prior_evaluate", "mlh_window_ext_prior_set", "mlh_window_marginalize",
     "mlh_calib_accumulate", "mlh_calib_add", "mlh_calib_use", "mlh_calib_clear", "mlh_calib_info", "mlh_calib_evaluate",
-    "mlh_sc_opts_default", "mlh_sc_reset", "mlh_sc_add", "mlh_sc_add_keyframe", "mlh_sc_detect", "mlh_sc_candidates", "mlh_sc_distance", "mlh_sc_fetch", "mlh_sc_info",
+    "mlh_sc_opts_default", "mlh_sc_reset", "mlh_sc_add", "mlh_sc_add_keyframe", "mlh_sc_add_keyframes", "mlh_sc_last_batch", "mlh_sc_detect", "mlh_sc_candidates", "mlh_sc_distance", "mlh_sc_fetch", "mlh_sc_info",
     "mlh_loop_opts_default", "mlh_loop_build_clouds", "mlh_loop_set_clouds", "mlh_loop_cloud", "mlh_loop_info_get", "mlh_loop_match", "mlh_loop_evaluate", "mlh_loop_register",
     "mlh_fgr_opts_default", "mlh_fgr_features", "mlh_fgr_spfh", "mlh_fgr_fpfh", "mlh_fgr_fetch", "mlh_fgr_set_normals", "mlh_fgr_set_spfh", "mlh_fgr_set_features",
     "mlh_fgr_match", "mlh_fgr_register", "mlh_fgr_register_device", "mlh_fgr_tail_tuple_test", "mlh_fgr_tail_optimize", "mlh_fgr_info",
     "mlh_pg_opts_default", "mlh_pg_reset", "mlh_pg_info", "mlh_pg_add_keyframe", "mlh_pg_set_loop", "mlh_pg_optimize", "mlh_pg_poses", "mlh_pg_device_poses",
     "mlh_pg_linearize", "mlh_pg_solve_step", "mlh_pg_time_stages", "mlh_pg_optimize_forced", "mlh_pg_reserve",
+    "mlh_session_export_size", "mlh_session_export", "mlh_session_inspect", "mlh_session_import", "mlh_session_last_info",
 ]
 
 
@@ -1054,6 +1095,19 @@ class Context:
         self._ck(self.lib.mlh_sc_add_keyframe(self.h, int(key), C.byref(idx)))
         return idx.value
 
+    def sc_add_keyframes(self, first_key, n):
+        """keyframes [first_key, first_key + n) of the mapper's store as n entries, in a fixed number of launches: what n sc_add_keyframe calls leave -> the first
+        entry's index (mlh_sc_add_keyframes)"""
+        idx = C.c_int32(-1)
+        self._ck(self.lib.mlh_sc_add_keyframes(self.h, int(first_key), int(n), C.byref(idx)))
+        return idx.value
+
+    def sc_last_batch(self) -> dict:
+        """launches, host waits, chunks and point counts of the last sc_add_keyframes (mlh_sc_last_batch)"""
+        info = ScBatchInfo()
+        self._ck(self.lib.mlh_sc_last_batch(self.h, C.byref(info)))
+        return info.as_dict()
+
     def sc_detect(self, que_index) -> dict:
         """detectLoopClosureID + detectLoop's distance rejection (mlh_sc_detect)"""
         r = ScResult()
@@ -1083,6 +1137,35 @@ class Context:
     def sc_info(self) -> dict:
         info = ScStoreInfo()
         self._ck(self.lib.mlh_sc_info(self.h, C.byref(info)))
+        return info.as_dict()
+
+    # ---- the session image (row f17): the keyframe store, the Scan Context store and the pose graph saved and restored
+    def session_export_size(self, sections=SESSION_ALL) -> int:
+        n = C.c_size_t(0)
+        self._ck(self.lib.mlh_session_export_size(self.h, int(sections), C.byref(n)))
+        return n.value
+
+    def session_export(self, sections=SESSION_ALL) -> bytes:
+        """the canonical byte image of the named stores (mlh_session_export into host memory)"""
+        buf = np.zeros(max(self.session_export_size(sections), 1), np.uint8)
+        n = C.c_size_t(0)
+        self._ck(self.lib.mlh_session_export(self.h, int(sections), _p(buf), buf.nbytes, MEM_HOST, C.byref(n)))
+        return buf[:n.value].tobytes()
+
+    def session_import(self, image, sections=SESSION_ALL) -> dict:
+        """the named sections of an image into this context's stores; a refused image leaves the context as it was (mlh_session_import)"""
+        buf = np.frombuffer(bytes(image), np.uint8)
+        info = SessionInfo()
+        self._ck(self.lib.mlh_session_import(self.h, buf.ctypes.data_as(C.c_void_p) if len(buf) else None, len(buf), int(sections), C.byref(info)))
+        # the bindings' copy of the SC options (sc_fetch and sc_candidates size their outputs by it)
+        if int(sections) & SESSION_SC:
+            at = int(np.frombuffer(bytes(image)[128:136], "<u8")[0])          # the SC section's offset: the third slot of the section table
+            self._sc_opts = ScOpts.from_buffer_copy(bytes(image)[at:at + C.sizeof(ScOpts)])
+        return info.as_dict()
+
+    def session_last_info(self) -> dict:
+        info = SessionInfo()
+        self._ck(self.lib.mlh_session_last_info(self.h, C.byref(info)))
         return info.as_dict()
 
     # ---- loop-closure local registration (constructLocalMap + performLocalRegistration on the device)

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include <climits>
 #include "bounds_dev.hpp"
+#include "tile_group.hpp"
 
 namespace mlh {
 
@@ -54,7 +55,7 @@ int stored_clouds_build(mlh_ctx *ctx, const float4 *arena_even, const float4 *ar
     std::vector<WmTile> tiles;
     size_t N = 0;
     for (const CloudSegment &s : segs) {
-        for (int at = 0; at < s.n; at += 256) tiles.push_back(WmTile{(long long)(s.src + size_t(at)), int(N) + at, std::min(256, s.n - at), s.xf, s.cloud});
+        segment_tiles(s.n, [&](int at, int len) { tiles.push_back(WmTile{(long long)(s.src + size_t(at)), int(N) + at, len, s.xf, s.cloud}); });
         N += size_t(s.n);
     }
     if (tiles.empty()) return MLH_OK;                       // every segment is empty

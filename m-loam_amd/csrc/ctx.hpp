@@ -457,6 +457,10 @@ struct CalibStore {
 
 // The Scan Context store (scancontext.hip; mloam_loop/src/scan_context.cpp:155-323): per entry the descriptor (f32, num_ring x num_sector, column-major), the ring
 // key (f32 x num_ring), the sector key and the column norms (f64 x num_sector each), appended; the positions and the period bookkeeping on the host.
+struct ScBatchStats {                      // the last mlh_sc_add_keyframes (mlh_sc_batch_info without the plan's constants)
+    int n_entries = 0, n_chunks = 0, launches = 0, host_waits = 0, first_index = 0;
+    long long n_points = 0, host_decided = 0, skipped = 0;
+};
 struct ScStore {
     mlh_sc_opts opts;
     bool configured = false;
@@ -472,6 +476,11 @@ struct ScStore {
     PinnedBuf h_pin;                      // landing place of the counters, the undecided points, a query's result, a fetched entry
     int last_host_decided = 0, last_skipped = 0;
     long long points_host_decided = 0, points_skipped = 0;
+    // the batched build (mlh_sc_add_keyframes)
+    DevBuf unc_entry;                     // int per undecided point: its entry of the batch
+    DevBuf batch_tab;                     // the call's tables: [ScBatchEntry per entry | ScChunk per chunk | n + 1 ints: the verdicts' range per entry]
+    std::vector<unsigned char> htab;
+    ScBatchStats batch;
 };
 
 // The loop closure's local registration (loopreg.hip; mloam_loop/src/pose_graph.cpp:364-419, loop_registration.cpp:104-211): the four clouds of constructLocalMap
@@ -536,6 +545,15 @@ struct PgStore {
     int max_loops = 128;                     // the capacity of loop edges of one problem (mlh_pg_reserve; pg_host.hpp: PG_MAX_LOOPS until then); mlh_pg_reset keeps it
     long long allocations = 0;
     int launches = 0, host_waits = 0;        // of the last call
+};
+
+// The session image (session.hip; session_host.hpp has the format): the staging image the pack kernel fills or checks, the call's tile table, the sections'
+// checksum words, and what the last successful export / import did.
+struct SessStore {
+    DevBuf stage, tab, sums;
+    PinnedBuf h_pin;             // the checksum words' landing place; the header on its way into a device dst
+    std::vector<unsigned char> htab, himg;
+    mlh_session_info last = {};
 };
 
 // The initial extrinsic calibration (initext.hip; estimator/src/initial/initial_extrinsics.cpp): Q_ and v_pose_ in HBM, one IeRecord per LiDAR (calib_ext_, the
@@ -785,6 +803,7 @@ struct mlh_ctx {
     mlh::LoopStore loop;     // the loop closure's local maps and matches (loopreg.hip)
     mlh::FgrStore fgr;       // FPFH + Fast Global Registration over the loop store's surf clouds (fgr.hip)
     mlh::PgStore pg;         // the loop closure's pose graph and its optimisation (posegraph.hip)
+    mlh::SessStore sess;     // the session image's staging and the last export / import (session.hip)
     mlh::InitExtStore ie;    // the initial extrinsic calibration (initext.hip)
     mlh::SegBuf seg;
     mlh::TrackSet track;

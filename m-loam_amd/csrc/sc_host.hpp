@@ -121,6 +121,45 @@ inline int sc_search_radius(double search_ratio, int S)
     return r >= double(S) ? S : int(r);
 }
 
+// The batched build (mlh_sc_add_keyframes): one workgroup of sc_desc_batch_kernel per chunk, a chunk being a run of one entry's points (its three clouds back to
+// back). An entry is cut into as many chunks as bring the grid to `target_workgroups` when the entries alone do not -- at most SC_BATCH_MAX_CHUNKS per entry, and
+// never chunks of fewer than SC_BATCH_CHUNK_POINTS points (one pass of the workgroup), so a small entry is one chunk and an empty one none. Every chunk but an
+// entry's last holds a multiple of SC_BATCH_CHUNK_POINTS points.
+constexpr int SC_BATCH_CHUNK_POINTS = 256;
+constexpr int SC_BATCH_MAX_CHUNKS = 64;
+struct ScChunk { int entry, first, count, pad; };      // points [first, first + count) of entry `entry` of the batch
+inline int sc_batch_chunks_wanted(int n_entries, int target_workgroups)
+{
+    if (n_entries < 1) return 1;
+    const long long w = ((long long)target_workgroups + n_entries - 1) / n_entries;
+    return w < 1 ? 1 : (w > SC_BATCH_MAX_CHUNKS ? SC_BATCH_MAX_CHUNKS : int(w));
+}
+// chunks of entries 0..n_entries-1 with n_points[] points each, appended to out[] (room for sc_batch_chunk_bound of them) in entry order; their number
+inline size_t sc_batch_chunk_bound(int n_entries, int target_workgroups) { return size_t(n_entries > 0 ? n_entries : 0) * size_t(sc_batch_chunks_wanted(n_entries, target_workgroups)); }
+inline size_t sc_batch_plan(const int *n_points, int n_entries, int target_workgroups, ScChunk *out)
+{
+    const int wanted = sc_batch_chunks_wanted(n_entries, target_workgroups);
+    size_t n_chunks = 0;
+    for (int e = 0; e < n_entries; ++e) {
+        const int n = n_points[e];
+        if (n <= 0) continue;
+        const int passes = (n - 1) / SC_BATCH_CHUNK_POINTS + 1;                    // <= 2^23
+        const int chunks = passes < wanted ? passes : wanted;
+        const long long per = (long long)((passes - 1) / chunks + 1) * SC_BATCH_CHUNK_POINTS;      // (2^31 for one chunk of 2^31 - 1 points)
+        for (long long at = 0; at < n; at += per) {
+            const long long left = (long long)n - at;
+            out[n_chunks++] = ScChunk{e, int(at), int(left < per ? left : per), 0};
+        }
+    }
+    return n_chunks;
+}
+// the store's room after growing for `more` entries at n entries and cap rooms: the doubling of the single add, repeated
+inline long long sc_grown_cap(long long n, long long cap, long long more)
+{
+    while (n + more > cap) cap = cap * 2 > 64 ? cap * 2 : 64;
+    return cap;
+}
+
 // deg2rad(nn_align * PC_UNIT_SECTORANGLE) (cpp:33-36, 319-321); PC_UNIT_SECTORANGLE = 360.0 / double(PC_NUM_SECTOR)
 inline float sc_deg2rad(const float degrees) { return degrees * 3.14159265358979323846 / 180.0; }
 inline float sc_yaw(int shift, int S) { return sc_deg2rad(float(shift * (360.0 / double(S)))); }

@@ -5,6 +5,8 @@
 //                      per workgroup. Points within SC_EDGE_MARGIN_SECTORS of a sector edge go to the undecided list (one global counter: ~0.08 % of a cloud).
 //   sc_finish_kernel   one workgroup: the host's verdicts on the undecided points, decode, empty cells -> 0, the descriptor as f32 in place of the integers, the
 //                      ring key, sector key and column norms of cpp:188-218 into the entry's slot
+//   sc_desc_batch_kernel / sc_finish_batch_kernel   the same two steps for a batch of keyframes of the mapper's store (mlh_sc_add_keyframes): a workgroup per chunk
+//                      of one entry's points, then a workgroup per entry; the bodies are those of the two kernels above (sc_point, sc_finish_body)
 //   sc_keydist_kernel  nanoflann's L2_Adaptor (nanoflann.hpp:432-461) in f32 against every searched entry: (distance bits << 32 | index), one thread per entry
 //   sc_select_kernel   one workgroup: the num_candidates smallest of those words by an 8-pass byte-wise radix selection, then ranked -> the candidates in the order
 //                      cpp:286 visits them (equal distances: the lower index first)
@@ -36,6 +38,24 @@ struct ScDescArgs {
     int *counters;
 };
 
+// one point of makeScancontext (cpp:163-175) as far as the device takes it: the sc_* arithmetic of sc_host.hpp, for sc_desc_kernel and sc_desc_batch_kernel alike
+enum { SC_PT_DROPPED = 0, SC_PT_SKIPPED, SC_PT_UNDECIDED, SC_PT_BINNED };
+struct ScPoint { int what, ring, cell, e; float zf; };
+__device__ __forceinline__ ScPoint sc_point(float x, float y, float z, int R, int S, double lidar_height, double max_radius)
+{
+    ScPoint p = {SC_PT_DROPPED, 0, 0, 0, 0.f};
+    if (!(isfinite(x) && isfinite(y) && isfinite(z))) { p.what = SC_PT_SKIPPED; return p; }
+    const float range = sc_range(x, y);
+    if (double(range) > max_radius) return p;
+    p.zf = sc_height(z, lidar_height);
+    p.ring = sc_ring(range, max_radius, R);
+    const double sv = sc_sector_value(sc_xy2theta(x, y), S);
+    if (sc_in_band(sv)) { p.what = SC_PT_UNDECIDED; return p; }      // this libm does not speak for the host's so close to an edge (a NaN is not in the band)
+    p.e = sc_encode(p.zf);
+    if (p.e > sc_encode(SC_NO_POINT)) { p.what = SC_PT_BINNED; p.cell = sc_bin(p.ring, sc_sector(sv, S), R); }
+    return p;
+}
+
 __global__ __launch_bounds__(SC_DESC_THREADS) void sc_desc_kernel(ScDescArgs A)
 {
     extern __shared__ int s_grid[];
@@ -46,25 +66,63 @@ __global__ __launch_bounds__(SC_DESC_THREADS) void sc_desc_kernel(ScDescArgs A)
         int j = int(i), k = 0;
         if (j >= A.c[0].n) { j -= A.c[0].n; k = 1; if (j >= A.c[1].n) { j -= A.c[1].n; k = 2; } }
         const float *rec = reinterpret_cast<const float *>(A.c[k].p + size_t(j) * size_t(A.stride));
-        const float x = rec[0], y = rec[1], z = rec[2];
-        if (!(isfinite(x) && isfinite(y) && isfinite(z))) { atomicAdd(&A.counters[1], 1); continue; }
-        const float range = sc_range(x, y);
-        if (double(range) > A.max_radius) continue;
-        const float zf = sc_height(z, A.lidar_height);
-        const int ring = sc_ring(range, A.max_radius, A.R);
-        const double sv = sc_sector_value(sc_xy2theta(x, y), A.S);
-        if (sc_in_band(sv)) {                       // this libm does not speak for the host's so close to an edge (a NaN is not in the band)
+        const float x = rec[0], y = rec[1];
+        const ScPoint p = sc_point(x, y, rec[2], A.R, A.S, A.lidar_height, A.max_radius);
+        if (p.what == SC_PT_SKIPPED) atomicAdd(&A.counters[1], 1);
+        else if (p.what == SC_PT_UNDECIDED) {
             const int u = atomicAdd(&A.counters[0], 1);
-            if (u < A.n_total) A.unc[u] = make_float4(x, y, zf, __int_as_float(ring));
-            continue;
+            if (u < A.n_total) A.unc[u] = make_float4(x, y, p.zf, __int_as_float(p.ring));
         }
-        const int e = sc_encode(zf);
-        if (e > empty) atomicMax(&s_grid[sc_bin(ring, sc_sector(sv, A.S), A.R)], e);
+        else if (p.what == SC_PT_BINNED) atomicMax(&s_grid[p.cell], p.e);
     }
     __syncthreads();
     for (int b = threadIdx.x; b < bins; b += SC_DESC_THREADS) {
         const int e = s_grid[b];
         if (e > empty) atomicMax(&A.grid[b], e);
+    }
+}
+
+// The batched build (mlh_sc_add_keyframes): one workgroup per chunk of sc_host.hpp's plan -- a run of ONE entry's points, its keyframe's three clouds back to back in
+// the order sc_desc_kernel reads them. The same LDS image of the polar grid, flushed into the entry's own slot; the undecided points of the whole batch go to one
+// list through one counter, each with its entry in the parallel array unc_entry (the fourth word keeps the ring, as in the single add).
+struct ScBatchEntry { unsigned long long off[3]; int n[3]; int pad; };      // a keyframe's clouds: first records in KfStore::pts, lengths
+struct ScDescBatchArgs {
+    const float4 *pts;
+    const ScBatchEntry *entries;
+    const ScChunk *chunks;
+    int R, S, unc_cap;
+    double lidar_height, max_radius;
+    int *grid0;           // the slot of the batch's first entry; entry e's is R * S * e cells further
+    float4 *unc;          // unc_cap = the batch's point count
+    int *unc_entry;
+    int *counters;
+};
+
+__global__ __launch_bounds__(SC_DESC_THREADS) void sc_desc_batch_kernel(ScDescBatchArgs A)
+{
+    extern __shared__ int s_grid[];
+    const int bins = A.R * A.S, empty = sc_encode(SC_NO_POINT);
+    const ScChunk ch = A.chunks[blockIdx.x];
+    const ScBatchEntry en = A.entries[ch.entry];
+    for (int b = threadIdx.x; b < bins; b += SC_DESC_THREADS) s_grid[b] = empty;
+    __syncthreads();
+    for (long long o = threadIdx.x; o < ch.count; o += SC_DESC_THREADS) {
+        int j = ch.first + int(o), k = 0;
+        if (j >= en.n[0]) { j -= en.n[0]; k = 1; if (j >= en.n[1]) { j -= en.n[1]; k = 2; } }
+        const float4 v = A.pts[en.off[k] + (unsigned long long)j];
+        const ScPoint p = sc_point(v.x, v.y, v.z, A.R, A.S, A.lidar_height, A.max_radius);
+        if (p.what == SC_PT_SKIPPED) atomicAdd(&A.counters[1], 1);
+        else if (p.what == SC_PT_UNDECIDED) {
+            const int u = atomicAdd(&A.counters[0], 1);
+            if (u < A.unc_cap) { A.unc[u] = make_float4(v.x, v.y, p.zf, __int_as_float(p.ring)); A.unc_entry[u] = ch.entry; }
+        }
+        else if (p.what == SC_PT_BINNED) atomicMax(&s_grid[p.cell], p.e);
+    }
+    __syncthreads();
+    int *grid = A.grid0 + size_t(ch.entry) * size_t(bins);
+    for (int b = threadIdx.x; b < bins; b += SC_DESC_THREADS) {
+        const int e = s_grid[b];
+        if (e > empty) atomicMax(&grid[b], e);
     }
 }
 
@@ -76,9 +134,9 @@ struct ScFinishArgs {
     double *sector_key, *col_norm;
 };
 
-__global__ __launch_bounds__(1024) void sc_finish_kernel(ScFinishArgs F)
+// the body of both finish kernels: one workgroup of 1024 threads, s_cell = R * S ints of LDS
+__device__ __forceinline__ void sc_finish_body(const ScFinishArgs &F, int *s_cell)
 {
-    extern __shared__ int s_cell[];
     const int bins = F.R * F.S;
     for (int b = threadIdx.x; b < bins; b += 1024) s_cell[b] = F.grid[b];
     __syncthreads();
@@ -106,6 +164,35 @@ __global__ __launch_bounds__(1024) void sc_finish_kernel(ScFinishArgs F)
         F.sector_key[c] = acc / double(F.R);
         F.col_norm[c] = sqrt(sq);
     }
+}
+
+__global__ __launch_bounds__(1024) void sc_finish_kernel(ScFinishArgs F)
+{
+    extern __shared__ int s_cell[];
+    sc_finish_body(F, s_cell);
+}
+
+// the batch's: one workgroup per entry, with that entry's range of the verdicts (grouped by entry on the host: fix_start[e] .. fix_start[e + 1])
+struct ScFinishBatchArgs {
+    int *grid0;
+    const int2 *fix;
+    const int *fix_start;
+    int R, S;
+    float *ring_key0;
+    double *sector_key0, *col_norm0;
+};
+
+__global__ __launch_bounds__(1024) void sc_finish_batch_kernel(ScFinishBatchArgs B)
+{
+    extern __shared__ int s_cell[];
+    const size_t e = blockIdx.x;
+    ScFinishArgs F;
+    F.grid = B.grid0 + e * size_t(B.R) * size_t(B.S);
+    F.fix = B.fix + B.fix_start[e]; F.n_fix = B.fix_start[e + 1] - B.fix_start[e]; F.R = B.R; F.S = B.S;
+    F.ring_key = B.ring_key0 + e * size_t(B.R);
+    F.sector_key = B.sector_key0 + e * size_t(B.S);
+    F.col_norm = B.col_norm0 + e * size_t(B.S);
+    sc_finish_body(F, s_cell);
 }
 
 // a query's small arrays, one block of device memory
@@ -299,11 +386,13 @@ int sc_pin(mlh_ctx *ctx, size_t bytes)
     return MLH_OK;
 }
 
-int sc_room(mlh_ctx *ctx)
+// room for `more` entries behind the stored ones: the buffers grow once, to the capacity that many single adds would have doubled their way to
+int sc_room(mlh_ctx *ctx, int more)
 {
     ScStore &S = ctx->sc;
-    if (S.n < S.cap) return MLH_OK;
-    const size_t have = size_t(S.n), want = std::max<size_t>(64, 2 * size_t(S.cap));
+    if ((long long)S.n + more <= (long long)S.cap) return MLH_OK;
+    const size_t have = size_t(S.n), want = size_t(sc_grown_cap(S.n, S.cap, more));
+    if (want > size_t(INT32_MAX)) return fail(ctx, MLH_ERR_INVALID, "Scan Context store: more than 2^31 entries");
     const size_t R = size_t(S.opts.num_ring), C = size_t(S.opts.num_sector);
     hipStream_t st = ctx->stream;
     hipError_t e;
@@ -324,7 +413,7 @@ int sc_add_run(mlh_ctx *ctx, const ScCloudDev dev[3], int stride, const double *
     const long long total = (long long)dev[0].n + dev[1].n + dev[2].n;
     if (total > (long long)INT32_MAX) return fail(ctx, MLH_ERR_INVALID, "mlh_sc_add: more than 2^31 points");
     const int n_total = int(total);
-    { const int rc = sc_room(ctx); if (rc) return rc; }
+    { const int rc = sc_room(ctx, 1); if (rc) return rc; }
     { const int rc = sc_pin(ctx, SC_PIN_HEAD + sizeof(float4) * SC_UNC_FIRST); if (rc) return rc; }
     MLH_HIP(ctx, S.counters.ensure(2 * sizeof(int)));
     MLH_HIP(ctx, S.unc.ensure(sizeof(float4) * size_t(std::max(n_total, 1))));
@@ -391,6 +480,136 @@ int sc_add_run(mlh_ctx *ctx, const ScCloudDev dev[3], int stride, const double *
     return MLH_OK;
 }
 
+// n > 0 entries from keyframes [first_key, first_key + n) of the mapper's store: what n sc_add_run calls leave, in a fixed number of launches and at most two waits
+int sc_add_batch_run(mlh_ctx *ctx, int first_key, int n, int32_t *first_index_out)
+{
+    ScStore &S = ctx->sc;
+    const KfStore &K = ctx->kf;
+    hipStream_t st = ctx->stream;
+    const int R = S.opts.num_ring, C = S.opts.num_sector, bins = R * C;
+    std::vector<ScBatchEntry> ent(static_cast<size_t>(n));
+    std::vector<int> n_points(size_t(n), 0);
+    long long total = 0;
+    for (int i = 0; i < n; ++i) {
+        const KfStore::Key &k = K.keys[size_t(first_key) + size_t(i)];
+        long long of_entry = 0;
+        for (int c = 0; c < 3; ++c) { ent[size_t(i)].off[c] = k.off[c]; ent[size_t(i)].n[c] = k.n[c]; of_entry += k.n[c]; }
+        ent[size_t(i)].pad = 0;
+        total += of_entry;
+        if (total > (long long)INT32_MAX) return fail(ctx, MLH_ERR_INVALID, "mlh_sc_add_keyframes: more than 2^31 points in one batch");
+        n_points[size_t(i)] = int(of_entry);
+    }
+    const int n_total = int(total), target = 2 * std::max(ctx->caps.cu_count, 1);
+    std::vector<ScChunk> chunks(sc_batch_chunk_bound(n, target));
+    const size_t n_chunks = sc_batch_plan(n_points.data(), n, target, chunks.data());
+    { const int rc = sc_room(ctx, n); if (rc) return rc; }
+    const size_t pin_first = SC_PIN_HEAD + (sizeof(float4) + sizeof(int)) * SC_UNC_FIRST;
+    { const int rc = sc_pin(ctx, std::max(pin_first, SC_PIN_HEAD + sizeof(int) * (size_t(n) + 1))); if (rc) return rc; }
+    MLH_HIP(ctx, S.counters.ensure(2 * sizeof(int)));
+    MLH_HIP(ctx, S.unc.ensure(sizeof(float4) * size_t(std::max(n_total, 1))));
+    MLH_HIP(ctx, S.unc_entry.ensure(sizeof(int) * size_t(std::max(n_total, 1))));
+    // every table of the call in one upload; the verdicts' ranges follow into their place once the host has made them
+    std::vector<unsigned char> &h = S.htab;
+    h.clear();
+    const size_t o_ent = put(h, ent.data(), ent.size());
+    const size_t o_chk = put(h, chunks.data(), n_chunks);
+    const size_t o_rng = put<int>(h, nullptr, size_t(n) + 1);
+    MLH_HIP(ctx, S.batch_tab.ensure(h.size() + 16));
+    unsigned char *dt = S.batch_tab.as<unsigned char>();
+    MLH_HIP(ctx, hipMemcpyAsync(dt, h.data(), o_rng, hipMemcpyHostToDevice, st));
+    MLH_HIP(ctx, hipMemsetAsync(dt + o_rng, 0, sizeof(int) * (size_t(n) + 1), st));      // no verdicts: every entry's range is empty
+    int *slot0 = reinterpret_cast<int *>(S.desc.as<float>() + size_t(S.n) * bins);
+    MLH_HIP(ctx, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(slot0), sc_encode(SC_NO_POINT), size_t(bins) * size_t(n), st));
+    MLH_HIP(ctx, hipMemsetAsync(S.counters.p, 0, 2 * sizeof(int), st));
+    ScBatchStats B;
+    B.n_entries = n; B.n_chunks = int(n_chunks); B.first_index = S.n; B.n_points = n_total;
+    int n_unc = 0, n_skipped = 0;
+    std::vector<int> start(size_t(n) + 1, 0);
+    std::vector<int2> fix;
+    if (n_chunks > 0) {
+        ScDescBatchArgs A;
+        A.pts = K.pts.as<float4>(); A.entries = reinterpret_cast<const ScBatchEntry *>(dt + o_ent); A.chunks = reinterpret_cast<const ScChunk *>(dt + o_chk);
+        A.R = R; A.S = C; A.unc_cap = n_total; A.lidar_height = S.opts.lidar_height; A.max_radius = S.opts.max_radius;
+        A.grid0 = slot0; A.unc = S.unc.as<float4>(); A.unc_entry = S.unc_entry.as<int>(); A.counters = S.counters.as<int>();
+        MLH_LAUNCH(sc_desc_batch_kernel, dim3(unsigned(n_chunks)), dim3(SC_DESC_THREADS), sizeof(int) * size_t(bins), st, A);
+        MLH_HIP(ctx, hipGetLastError());
+        B.launches += 1;
+        // the counters and the first undecided points with their entries in one wait
+        unsigned char *pin = S.h_pin.as<unsigned char>();
+        int *hc = reinterpret_cast<int *>(pin);
+        float4 *hu = reinterpret_cast<float4 *>(pin + SC_PIN_HEAD);
+        int *he = reinterpret_cast<int *>(pin + SC_PIN_HEAD + sizeof(float4) * SC_UNC_FIRST);
+        const size_t first = size_t(std::min(n_total, SC_UNC_FIRST));
+        MLH_HIP(ctx, hipMemcpyAsync(hc, S.counters.p, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+        MLH_HIP(ctx, hipMemcpyAsync(hu, S.unc.p, sizeof(float4) * first, hipMemcpyDeviceToHost, st));
+        MLH_HIP(ctx, hipMemcpyAsync(he, S.unc_entry.p, sizeof(int) * first, hipMemcpyDeviceToHost, st));
+        MLH_HIP(ctx, stream_wait_spin(ctx));
+        B.launches += 1; B.host_waits += 1;
+        n_unc = std::min(hc[0], n_total); n_skipped = hc[1];
+        std::vector<float4> pts(hu, hu + std::min(n_unc, SC_UNC_FIRST));
+        std::vector<int> of(he, he + std::min(n_unc, SC_UNC_FIRST));
+        if (n_unc > SC_UNC_FIRST) {
+            const size_t rest = size_t(n_unc - SC_UNC_FIRST);
+            { const int rc = sc_pin(ctx, SC_PIN_HEAD + (sizeof(float4) + sizeof(int)) * rest); if (rc) return rc; }
+            hu = reinterpret_cast<float4 *>(S.h_pin.as<unsigned char>() + SC_PIN_HEAD);
+            he = reinterpret_cast<int *>(S.h_pin.as<unsigned char>() + SC_PIN_HEAD + sizeof(float4) * rest);
+            MLH_HIP(ctx, hipMemcpyAsync(hu, S.unc.as<float4>() + SC_UNC_FIRST, sizeof(float4) * rest, hipMemcpyDeviceToHost, st));
+            MLH_HIP(ctx, hipMemcpyAsync(he, S.unc_entry.as<int>() + SC_UNC_FIRST, sizeof(int) * rest, hipMemcpyDeviceToHost, st));
+            MLH_HIP(ctx, stream_wait_spin(ctx));
+            B.launches += 1; B.host_waits += 1;
+            pts.insert(pts.end(), hu, hu + rest);
+            of.insert(of.end(), he, he + rest);
+        }
+        // the host's verdicts (sc_decide_sector), grouped by entry: a counting sort; within an entry their order does not matter to a maximum
+        const int empty = sc_encode(SC_NO_POINT);
+        std::vector<int2> verdict(pts.size(), make_int2(-1, 0));
+        for (size_t u = 0; u < pts.size(); ++u) {
+            const float4 &p = pts[u];
+            int ring;
+            std::memcpy(&ring, &p.w, 4);
+            const int e = sc_encode(p.z);
+            if (e > empty && ring >= 1 && ring <= R && of[u] >= 0 && of[u] < n) {
+                verdict[u] = make_int2(sc_bin(ring, sc_decide_sector(p.x, p.y, C), R), e);
+                start[size_t(of[u]) + 1] += 1;
+            }
+        }
+        for (int i = 0; i < n; ++i) start[size_t(i) + 1] += start[size_t(i)];
+        fix.resize(size_t(start[size_t(n)]));
+        std::vector<int> at(start.begin(), start.end() - 1);
+        for (size_t u = 0; u < pts.size(); ++u) if (verdict[u].x >= 0) fix[size_t(at[size_t(of[u])]++)] = verdict[u];
+    }
+    if (!fix.empty()) {
+        // the verdicts and their ranges travel through the pinned block (the stream is idle behind the wait: nothing reads it)
+        const size_t at_fix = (SC_PIN_HEAD + sizeof(int) * start.size() + 15) & ~size_t(15);
+        { const int rc = sc_pin(ctx, at_fix + sizeof(int2) * fix.size()); if (rc) return rc; }
+        unsigned char *pin = S.h_pin.as<unsigned char>();
+        std::memcpy(pin + SC_PIN_HEAD, start.data(), sizeof(int) * start.size());
+        MLH_HIP(ctx, hipMemcpyAsync(dt + o_rng, pin + SC_PIN_HEAD, sizeof(int) * start.size(), hipMemcpyHostToDevice, st));
+        std::memcpy(pin + at_fix, fix.data(), sizeof(int2) * fix.size());
+        MLH_HIP(ctx, hipMemcpyAsync(S.unc.p, pin + at_fix, sizeof(int2) * fix.size(), hipMemcpyHostToDevice, st));      // (8 <= 16 bytes per point: it fits)
+    }
+    ScFinishBatchArgs F;
+    F.grid0 = slot0; F.fix = S.unc.as<int2>(); F.fix_start = reinterpret_cast<const int *>(dt + o_rng); F.R = R; F.S = C;
+    F.ring_key0 = S.ring_key.as<float>() + size_t(S.n) * R;
+    F.sector_key0 = S.sector_key.as<double>() + size_t(S.n) * C;
+    F.col_norm0 = S.col_norm.as<double>() + size_t(S.n) * C;
+    MLH_LAUNCH(sc_finish_batch_kernel, dim3(unsigned(n)), dim3(1024), sizeof(int) * size_t(bins), st, F);
+    MLH_HIP(ctx, hipGetLastError());
+    B.launches += 1;
+    for (int i = 0; i < n; ++i) {
+        const KfStore::Key &k = K.keys[size_t(first_key) + size_t(i)];
+        for (int d = 0; d < 3; ++d) S.pos.push_back(k.pose[d]);
+        S.has_pos.push_back(1);
+    }
+    S.last_host_decided = n_unc; S.last_skipped = n_skipped;
+    S.points_host_decided += n_unc; S.points_skipped += n_skipped;
+    B.host_decided = n_unc; B.skipped = n_skipped;
+    S.batch = B;
+    if (first_index_out) *first_index_out = S.n;
+    S.n += n;
+    return MLH_OK;
+}
+
 int sc_work(mlh_ctx *ctx, ScWork **W)
 {
     MLH_HIP(ctx, ctx->sc.work.ensure(sizeof(ScWork)));
@@ -446,7 +665,8 @@ int mlh_sc_reset(mlh_ctx *ctx, const mlh_sc_opts *opts)
     MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     ScStore &S = ctx->sc;
     S.desc.release(); S.ring_key.release(); S.sector_key.release(); S.col_norm.release();
-    S.unc.release(); S.counters.release(); S.keys.release(); S.work.release();
+    S.unc.release(); S.counters.release(); S.keys.release(); S.work.release(); S.unc_entry.release(); S.batch_tab.release();
+    S.batch = ScBatchStats();
     S.opts = o; S.configured = true;
     S.n = 0; S.cap = 0; S.pos.clear(); S.has_pos.clear(); S.book = ScBook();
     S.last_host_decided = S.last_skipped = 0; S.points_host_decided = S.points_skipped = 0;
@@ -498,6 +718,31 @@ int mlh_sc_add_keyframe(mlh_ctx *ctx, int32_t key, int32_t *index_out)
         dev[c].p = k.n[c] > 0 ? reinterpret_cast<const unsigned char *>(K.pts.as<float4>() + k.off[c]) : nullptr;
     }
     return sc_add_run(ctx, dev, int(sizeof(float4)), k.pose, index_out);
+}
+
+int mlh_sc_add_keyframes(mlh_ctx *ctx, int32_t first_key, int32_t n, int32_t *first_index_out)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    { const int rc = sc_require(ctx, "mlh_sc_add_keyframes"); if (rc) return rc; }
+    ScStore &S = ctx->sc;
+    if (first_key < 0 || n < 0 || (long long)first_key + n > (long long)ctx->kf.keys.size()) return fail(ctx, MLH_ERR_INVALID, "mlh_sc_add_keyframes: no such keyframes");
+    if ((long long)S.n + n > (long long)INT32_MAX) return fail(ctx, MLH_ERR_INVALID, "mlh_sc_add_keyframes: more than 2^31 entries");
+    if (n == 0) { if (first_index_out) *first_index_out = S.n; return MLH_OK; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return sc_add_batch_run(ctx, first_key, n, first_index_out);
+}
+
+int mlh_sc_last_batch(mlh_ctx *ctx, mlh_sc_batch_info *out)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (!out) return fail(ctx, MLH_ERR_INVALID, "mlh_sc_last_batch: null output");
+    const ScBatchStats &B = ctx->sc.batch;
+    std::memset(out, 0, sizeof(*out));
+    out->n_entries = B.n_entries; out->n_chunks = B.n_chunks; out->launches = B.launches; out->host_waits = B.host_waits;
+    out->first_index = B.first_index; out->chunk_points = SC_BATCH_CHUNK_POINTS; out->max_chunks_per_entry = SC_BATCH_MAX_CHUNKS;
+    out->target_workgroups = 2 * std::max(ctx->caps.cu_count, 1);
+    out->n_points = B.n_points; out->points_host_decided = B.host_decided; out->points_skipped = B.skipped;
+    return MLH_OK;
 }
 
 int mlh_sc_detect(mlh_ctx *ctx, int32_t que_index, mlh_sc_result *result)
@@ -615,7 +860,7 @@ int mlh_sc_info(mlh_ctx *ctx, mlh_sc_store_info *out)
     out->desc_tile_points = SC_DESC_THREADS; out->desc_wrap_points = SC_DESC_THREADS * SC_DESC_MAX_BLOCKS;
     out->last_host_decided = S.last_host_decided; out->last_skipped = S.last_skipped;
     out->points_host_decided = S.points_host_decided; out->points_skipped = S.points_skipped;
-    out->bytes_hbm = int64_t(S.desc.cap + S.ring_key.cap + S.sector_key.cap + S.col_norm.cap + S.unc.cap + S.counters.cap + S.keys.cap + S.work.cap);
+    out->bytes_hbm = int64_t(S.desc.cap + S.ring_key.cap + S.sector_key.cap + S.col_norm.cap + S.unc.cap + S.counters.cap + S.keys.cap + S.work.cap + S.unc_entry.cap + S.batch_tab.cap);
     return MLH_OK;
 }
 

@@ -10,6 +10,13 @@ namespace mlh {
 
 constexpr int CALIB_TILE = 256;
 
+// the 256-record tiles of one stored cloud of n records, in order: emit(first record, records). A tile never straddles a cloud. (cloudbuild.hip: the map builder
+// over stored clouds; session_host.hpp: the session image's pack)
+template <class Emit> inline void segment_tiles(int n, Emit emit)
+{
+    for (int at = 0; at < n; at += CALIB_TILE) emit(at, n - at < CALIB_TILE ? n - at : CALIB_TILE);
+}
+
 struct TileGrouping {
     std::vector<int> slot_of;    // n: factor i -> slot relative to the grouping's first slot
     std::vector<int> perm;       // tiles * 256: slot -> first + i for the factor i it holds, or -1 for padding

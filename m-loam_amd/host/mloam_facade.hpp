@@ -2063,6 +2063,19 @@ public:
             q_prev_ = pose_keyframes_6d[n - 1].q_;
         }
     }
+    // after a session import (loadSession): the bookkeeping n saves would have left -- every keyframe's pose and f32 position as the store holds them, and the
+    // previous-keyframe state of the saveKeyframe test from the last imported key
+    void restore(const double *poses, const float *positions, size_t n)
+    {
+        pose_keyframes_3d.clear();
+        pose_keyframes_6d.assign(n, Pose());
+        for (size_t i = 0; i < n; ++i) {
+            PointI p;
+            p.x = positions[3 * i]; p.y = positions[3 * i + 1]; p.z = positions[3 * i + 2]; p.intensity = float(i);
+            pose_keyframes_3d.push_back(p);
+        }
+        updatePoses(poses, positions, n);
+    }
     PointICloud pose_keyframes_3d;
     std::vector<Pose> pose_keyframes_6d;
 private:
@@ -2488,6 +2501,15 @@ public:
         dev_.check(mlh_sc_add_keyframe(dev_.ctx(), key, &idx));
         return idx;
     }
+    // loadPoseGraph's addKeyFrameIntoDB loop (pose_graph.cpp:696-781, 225-279, 77-90) over keyframes [first, first + n) of the mapper's store, in one call with a
+    // fixed number of launches: the entries n makeAndSaveScancontextAndKeysFromKeyframe calls would leave -> the first one's index. After setParameter with other
+    // options it rebuilds the place index without remapping; it also serves a mapper-only run whose loop closure is switched on later.
+    int rebuildFromKeyframes(int first, int n)
+    {
+        int32_t idx = -1;
+        dev_.check(mlh_sc_add_keyframes(dev_.ctx(), first, n, &idx));
+        return idx;
+    }
     QueryResult detectLoopClosureID(const int &que_index)
     {
         dev_.check(mlh_sc_detect(dev_.ctx(), que_index, &last_));
@@ -2667,12 +2689,68 @@ private:
     bool fgr_tail_on_device_ = false;
 };
 
+// ------------------------------------------------------------------ the session image (mloam_loop: pose_graph.cpp:655-781, 225-279, 77-90)
+// PoseGraph::savePoseGraph / loadPoseGraph as one byte image of the context's keyframe store, Scan Context store and pose graph (include/mloam_hip.h (f17);
+// csrc/session_host.hpp has the format). SessionImage owns the bytes and reads / writes them with plain fread / fwrite; saveSession exports, loadSession imports
+// (a refused image throws and leaves the context as it was) and, given the mapper's KeyframePolicy, restores its bookkeeping from the imported keys.
+class SessionImage {
+public:
+    std::vector<unsigned char> bytes;
+    bool save(const std::string &path) const
+    {
+        FILE *f = std::fopen(path.c_str(), "wb");
+        if (!f) return false;
+        const bool ok = bytes.empty() || std::fwrite(bytes.data(), 1, bytes.size(), f) == bytes.size();
+        return std::fclose(f) == 0 && ok;
+    }
+    bool load(const std::string &path)
+    {
+        bytes.clear();
+        FILE *f = std::fopen(path.c_str(), "rb");
+        if (!f) return false;
+        unsigned char buf[65536];
+        size_t got;
+        while ((got = std::fread(buf, 1, sizeof(buf), f)) > 0) bytes.insert(bytes.end(), buf, buf + got);
+        const bool ok = std::ferror(f) == 0;
+        std::fclose(f);
+        return ok;
+    }
+    // host only: the header, the section table, every section's contents and checksum
+    bool inspect(mlh_session_info &info) const { return mlh_session_inspect(bytes.data(), bytes.size(), &info) == MLH_OK; }
+};
+
+inline SessionImage saveSession(Device &dev, uint32_t sections = MLH_SESSION_KEYFRAMES | MLH_SESSION_SC | MLH_SESSION_PG)
+{
+    SessionImage img;
+    size_t need = 0, written = 0;
+    dev.check(mlh_session_export_size(dev.ctx(), sections, &need));
+    img.bytes.resize(need);
+    dev.check(mlh_session_export(dev.ctx(), sections, img.bytes.data(), img.bytes.size(), MLH_MEM_HOST, &written));
+    img.bytes.resize(written);
+    return img;
+}
+
+inline mlh_session_info loadSession(Device &dev, const SessionImage &image, uint32_t sections = MLH_SESSION_KEYFRAMES | MLH_SESSION_SC | MLH_SESSION_PG,
+                                    KeyframePolicy *policy = nullptr)
+{
+    mlh_session_info info;
+    dev.check(mlh_session_import(dev.ctx(), image.bytes.data(), image.bytes.size(), sections, &info));
+    if (policy && (sections & MLH_SESSION_KEYFRAMES)) {
+        const size_t n = size_t(info.count[0]);
+        std::vector<double> poses(7 * n + 1);
+        std::vector<float> pos(3 * n + 1);
+        dev.check(mlh_keyframe_poses(dev.ctx(), 0, int32_t(n), poses.data(), nullptr, pos.data()));
+        policy->restore(poses.data(), pos.data(), n);
+    }
+    return info;
+}
+
 // ------------------------------------------------------------------ the pose graph (mloam_loop: pose_graph.cpp:92-150, 491-653; keyframe.cpp:84-105)
 // PoseGraph over the context's keyframe records (include/mloam_hip.h (f14)), templated over the caller's Pose (the reference's own, or the stand-in): addKeyFrame is
 // the bookkeeping of cpp:94-96 (the loop detection around it is SCManager, LoopLocalMap and LoopRegistration above), updateLoopInfo is cpp:140-142,
 // optimizePoseGraph(cur_index) ONE pass of the body of cpp:505-642 on the device. The optimisation thread with its 2 s sleep and optimize_buf_, the mutexes,
-// updatePath / publish*, savePoseGraph / loadPoseGraph's files and the visualisation stay with the caller; loadKeyFrame's loop case (cpp:187-206) is addKeyFrame
-// followed by updateLoopInfo.
+// updatePath / publish*, and the visualisation stay with the caller; savePoseGraph / loadPoseGraph are the session image (SessionImage, saveSession /
+// loadSession above; include/mloam_hip.h (f17)); loadKeyFrame's loop case (cpp:187-206) is addKeyFrame followed by updateLoopInfo.
 template <typename PoseT>
 class PoseGraph {
 public:
@@ -2729,6 +2807,16 @@ public:
         dev_.check(mlh_pg_poses(dev_.ctx(), 0, int32_t(n), p.data(), nullptr));
         poses.resize(n);
         for (size_t i = 0; i < n; ++i) detail::pose_from_param(poses[i], p.data() + 7 * i);
+    }
+    // savePoseGraph (cpp:655-694) / loadPoseGraph (cpp:696-781): the session image of this context in `path` -- the keyframes with their clouds and the place
+    // index too when the context holds them (`sections`); loading replaces the named stores, or throws and leaves them alone
+    bool savePoseGraph(const std::string &path, uint32_t sections = MLH_SESSION_PG) { return saveSession(dev_, sections).save(path); }
+    bool loadPoseGraph(const std::string &path, uint32_t sections = MLH_SESSION_PG)
+    {
+        SessionImage img;
+        if (!img.load(path)) return false;
+        loadSession(dev_, img, sections);
+        return true;
     }
     int getKeyFrameSize() const { return info().n_keyframes; }
     int earliestLoopIndex() const { return info().earliest_loop_index; }
