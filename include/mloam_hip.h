@@ -805,6 +805,7 @@ int mlh_fgr_info(mlh_ctx *ctx, mlh_fgr_info_t *out);
  *   decision because of the memory behind it: Y is 6 (M - 1) x (6 L + 1) doubles, the dense stage's Gram image and factor about 2 x (6 L)^2 doubles -- at the
  *   limit, L = 1024, 0.6 GB for the dense stage and 0.3 GB of Y per 1000 keyframes. The earliest looped index never moves forward (cpp:140-142), so a run's L only
  *   grows: with loop_skip_interval 3 the 129th edge arrives after about 390 keyframes of revisit.
+ *   mlh_pg_marginals (f18) holds O(M) more -- 252 doubles per keyframe and, up to 128 loops, the packed dense factor -- and reuses Y: its section has the figures.
  * mlh_pg_add_keyframe = the bookkeeping of PoseGraph::addKeyFrame (cpp:94-96): the keyframe gets index global_index_++; *index_out (may be NULL) <- it. CHOSEN:
  *   last_pose_w_ and loop_info_ start as the identity (the reference's KeyFrame leaves them default-constructed). A non-finite pose: MLH_ERR_INVALID.
  * mlh_pg_set_loop = KeyFrame::updateLoopInfo(loop_index, loop_info) plus the earliest-index rule (cpp:140-142); loadKeyFrame's loop case (cpp:187-206) is this call
@@ -1011,7 +1012,7 @@ int mlh_global_map_select(const float *positions_xyz, int n, const float center[
  * need to update all keyframes" under "TODO: using loop info to update keyframes". There is nothing to reproduce; every rule here is CHOSEN:
  *   CHOSEN replacement: keys first_key .. first_key + n - 1 of the store of (f5) take poses[7 i ..] = [t, q(xyzw)] as given (not normalised); with covs != NULL
  *     also covs[36 i ..] (6 x 6 row-major, as mlh_keyframe_save), with covs == NULL the stored covariance stays -- the loop side carries no new one
- *     (publishLoopInfo sends the mapper's own cov_ back);
+ *     (publishLoopInfo sends the mapper's own cov_ back; section (f18) computes one on the device and has an entry that carries it here);
  *   CHOSEN position: the f32 position the radius searches read is recomputed as float(t), as mlh_keyframe_save computes it;
  *   CHOSEN "changed": a keyframe counts as changed when any of its 7 pose doubles -- or, with covs, any of its 36 covariance doubles -- differs BITWISE from what
  *     was stored (mlh_pg_optimize leaves the keyframes before its first looped index bit-identical, so they stay cached);
@@ -1043,6 +1044,62 @@ int mlh_keyframes_update_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, const
 int mlh_keyframes_update_from_pose_graph(mlh_ctx *ctx, mlh_ctx *pg_ctx /* may equal ctx */, int32_t first_index, int32_t first_key,
                                          int32_t n /* < 0: all pg keyframes from first_index */, int drift_tail, int32_t *n_changed, double drift_out[7]);
 int mlh_keyframe_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, double *poses, double *covs, float *positions /* each may be NULL */);
+
+/* ---------------------------------------------------------------- (f18) pose-graph marginal covariances, on the device
+ * What (f14) did not hand back: the uncertainty of the corrected poses. The mapper weighs every keyframe's points by its 6 x 6 pose covariance (f1); after a loop
+ * closure the poses of (f15) are consistent while the stored covariances are still what the odometry had accumulated. Nothing in the reference computes this
+ * (publishLoopInfo sends the mapper's own cov_ back); every rule is CHOSEN.
+ * mlh_pg_marginals(cur_index, form): the 6 x 6 diagonal blocks of H^-1, where H is exactly the matrix mlh_pg_linearize(cur_index) describes -- the problem
+ *   first = earliest_loop_index_ .. cur at the STORED poses, the sequential measurements taken from those poses, loop edges Huber-corrected, block `first`
+ *   constant, no Levenberg-Marquardt diagonal and no Jacobi scaling, over the tangent of the solver's Plus in the order [rotation 3, translation 3] (CHOSEN: what
+ *   ceres::Covariance would give on that problem). The block of `first` is zero: that is the gauge. A stage-style entry: the stored poses, the last poses and
+ *   every buffer of (f14) that outlives a call keep their bits; an optimise after it gives the bits of one without it.
+ *   - form MLH_PG_COV_LOCAL: the blocks as defined. form MLH_PG_COV_STORE: each block as A Sigma A^T in the keyframe store's convention, the left perturbation
+ *     T = exp(xi^) T_bar with xi = [rho, phi] of (f1): A = [[2 [t]x, I], [2 I, 0]] (rows rho, phi; columns rotation, translation; t the keyframe's stored
+ *     translation), because Plus turns by the angle 2 |d_r| about d_r on the left and adds d_t: phi = 2 d_r, rho = d_t - phi x t (csrc/pg_marg_host.hpp).
+ *     covs (36 M doubles, row-major, may be NULL) <- the blocks of first..cur in the form asked for. Every block is symmetric to the bit (one triangle is
+ *     computed, the other copied).
+ *   - the method: H = B + W^T W as (f14) splits it; B = L L^T, Y = L^-1 W^T, C = I + Y^T Y and its dense Cholesky by the kernels of (f14), fed S = 1 and a zero
+ *     diagonal; then by Woodbury H^-1 = B^-1 - Z C^-1 Z^T with Z = L^-T Y: a selected inversion of the band (Takahashi's recursion, one workgroup, a 5 x 5-block
+ *     window in LDS), Z by one lane per column in one backward sweep, Q = L_c^-1 Z^T by a blocked triangular solve whose panel updates run on
+ *     v_mfma_f64_16x16x4_f64 (O((6 L)^2 n): where the time goes at large L), and a tail that subtracts each block's 6 x 6 Gram of Q and writes both forms. No
+ *     n x n matrix is formed. Launches: 13 + 1 for L <= 128, 13 + 3 ceil(6 L / 64) beyond -- not a function of M (the one exception: cur == first, 4 launches,
+ *     the one zero block, ok = 1); ONE host wait. No floating-point atomics: two runs give the same bits.
+ *   - memory beyond what an optimise of the same problem holds: 72 M doubles of results, 180 (M - 1) doubles of the band's inverse and, for L <= 128, the packed
+ *     dense factor (ceil(6 L / 64) * 64)^2 doubles (at most 4.7 MB; beyond 128 the blocked stage's factor is used in place) -- O(M) in all; Z and Q overwrite Y
+ *     (the 0.3 GB per 1000 keyframes at L = 1024 that mlh_pg_reserve states). Allocated by the first call, grown as the others are, counted in mlh_pg_info; a
+ *     context that never calls this entry holds what it held before.
+ *   *result: ok (0 when a pivot of B or of C was not positive: nothing is published, covs is not written, and no earlier result stays valid), M, L, first,
+ *   launches, host waits. Errors as mlh_pg_optimize: MLH_ERR_STATE without a loop, below the earliest index or beside an uncollected solve; MLH_ERR_INVALID for a
+ *   cur_index that names no keyframe or an unknown form; MLH_ERR_UNSUPPORTED above the context's loop capacity or under a communicator -- each with nothing
+ *   touched, an earlier valid result included.
+ * mlh_pg_device_marginals: both forms in HBM for device consumers, 36 doubles per keyframe of first..cur: *cov_local, *cov_store, and the problem they belong to
+ *   (*first_index, *n_keyframes; either may be NULL). The result goes stale -- both pointers NULL, *first_index -1, *n_keyframes 0 -- with mlh_pg_optimize /
+ *   mlh_pg_optimize_forced, mlh_pg_set_loop, mlh_pg_reset and mlh_session_import of the pose graph; mlh_pg_add_keyframe does not invalidate it. It is not part of
+ *   the session image.
+ * mlh_keyframes_update_from_pose_graph_cov: mlh_keyframes_update_from_pose_graph with covariances: the strided pose copy plus ONE copy of the store-form blocks
+ *   of the range, STILL ONE host wait, then the host rules of mlh_keyframes_update_poses with covs != NULL. CHOSEN rules:
+ *     cov_mode MLH_KF_COV_RELATIVE: key i takes its store-form block;
+ *     cov_mode MLH_KF_COV_ABSOLUTE: key i takes its block plus the stored covariance of the key that `first` maps to -- with left perturbations a common-mode
+ *       error of the anchor is the same world-frame vector on every keyframe, so to first order the sum needs no adjoint (compoundPoseWithCov's method 1 with an
+ *       identity transport);
+ *     the key of `first` itself keeps its covariance; keys of the range before it, and the keys beyond the range (the drift tail), keep theirs.
+ *   MLH_ERR_STATE when pg_ctx holds no valid marginals, or the range reaches beyond their `cur`; MLH_ERR_INVALID for an unknown cov_mode, or with
+ *   MLH_KF_COV_ABSOLUTE when `first` maps to no key of the store; the other errors are (f15)'s. */
+enum { MLH_PG_COV_LOCAL = 0, MLH_PG_COV_STORE = 1 };
+enum { MLH_KF_COV_RELATIVE = 0, MLH_KF_COV_ABSOLUTE = 1 };
+typedef struct mlh_pg_marginals_result {
+    int32_t ok;                              /* 0: a pivot of B or C was not positive */
+    int32_t n_keyframes, n_loops;            /* M, L of the problem */
+    int32_t first_index;
+    int32_t launches, host_waits;
+} mlh_pg_marginals_result;
+int mlh_pg_marginals(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, int32_t form, double *covs /* 36 M, row-major, or NULL */,
+                     mlh_pg_marginals_result *result);
+int mlh_pg_device_marginals(mlh_ctx *ctx, const double **cov_local, const double **cov_store, int32_t *first_index, int32_t *n_keyframes);
+int mlh_keyframes_update_from_pose_graph_cov(mlh_ctx *ctx, mlh_ctx *pg_ctx /* may equal ctx */, int32_t first_index, int32_t first_key,
+                                             int32_t n /* < 0: all pg keyframes from first_index */, int drift_tail, int32_t cov_mode, int32_t *n_changed,
+                                             double drift_out[7]);
 
 /* ---------------------------------------------------------------- (f16) the initial extrinsic calibration, on the device
  * InitialExtrinsics (estimator/src/initial/initial_extrinsics.h:34-40, initial_extrinsics.cpp:20-22, 26-116, 119-241, 243-309) as Estimator::process drives it while

@@ -298,6 +298,13 @@ class PgInfo(C.Structure):
 
 
 PG_LOOPS_LIMIT = 1024          # MLH_PG_LOOPS_LIMIT
+PG_COV_LOCAL, PG_COV_STORE = 0, 1          # MLH_PG_COV_*: the solver's tangent [rotation, translation] / the keyframe store's left perturbation [rho, phi]
+KF_COV_RELATIVE, KF_COV_ABSOLUTE = 0, 1    # MLH_KF_COV_*
+
+
+class PgMarginalsResult(C.Structure):
+    """mlh_pg_marginals_result"""
+    _fields_ = [("ok", C.c_int32), ("n_keyframes", C.c_int32), ("n_loops", C.c_int32), ("first_index", C.c_int32), ("launches", C.c_int32), ("host_waits", C.c_int32)]
 
 
 def pg_opts(**kw) -> PgOpts:
@@ -445,6 +452,7 @@ def load_library():
     lib.mlh_global_map_select.argtypes = [vp, ci, vp, cf, cf, vp, i32p]
     lib.mlh_keyframes_update_poses.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, ci, i32p, vp]
     lib.mlh_keyframes_update_from_pose_graph.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, ci, i32p, vp]
+    lib.mlh_keyframes_update_from_pose_graph_cov.argtypes = [vp, vp, C.c_int32, C.c_int32, C.c_int32, ci, C.c_int32, i32p, vp]
     lib.mlh_keyframe_poses.argtypes = [vp, C.c_int32, C.c_int32, vp, vp, vp]
     i64p = C.POINTER(C.c_int64)
     lib.mlh_window_map_opts_default.argtypes = [C.POINTER(WindowMapOpts), ci, ci, ci]
@@ -564,6 +572,8 @@ def load_library():
     lib.mlh_pg_solve_step.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), cd_, vp, vp, C.POINTER(C.c_int32)]
     lib.mlh_pg_time_stages.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.POINTER(PgResult), vp]
     lib.mlh_pg_optimize_forced.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.c_uint32, C.POINTER(PgResult)]
+    lib.mlh_pg_marginals.argtypes = [vp, C.c_int32, C.POINTER(PgOpts), C.c_int32, vp, C.POINTER(PgMarginalsResult)]
+    lib.mlh_pg_device_marginals.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     lib.mlh_initext_opts_default.argtypes = [C.POINTER(InitExtOpts)]
     lib.mlh_initext_opts_default.restype = None
     lib.mlh_initext_reset.argtypes = [vp, C.POINTER(InitExtOpts)]
@@ -615,7 +625,7 @@ EXPORTED_SYMBOLS = [
     "mlh_pose_plus", "mlh_eval_degeneracy",
     "mlh_keyframes_reset", "mlh_keyframe_save", "mlh_keyframe_save_staged", "mlh_local_map_assemble", "mlh_local_map_clear", "mlh_local_map_cloud", "mlh_local_map_info",
     "mlh_keyframe_attach_outlier", "mlh_global_map_opts_default", "mlh_global_map_assemble", "mlh_global_map_cloud", "mlh_global_map_release", "mlh_global_map_select",
-    "mlh_keyframes_update_poses", "mlh_keyframes_update_from_pose_graph", "mlh_keyframe_poses",
+    "mlh_keyframes_update_poses", "mlh_keyframes_update_from_pose_graph", "mlh_keyframes_update_from_pose_graph_cov", "mlh_keyframe_poses",
     "mlh_initext_opts_default", "mlh_initext_reset", "mlh_initext_add_pose", "mlh_initext_calibrate", "mlh_initext_info", "mlh_initext_read_state",
     "mlh_window_map_opts_default", "mlh_window_reset", "mlh_window_set", "mlh_window_set_from_scan", "mlh_window_slide", "mlh_window_cloud", "mlh_window_info",
     "mlh_window_build_local_map", "mlh_window_map_cloud",
@@ -626,7 +636,7 @@ EXPORTED_SYMBOLS = [
     "mlh_fgr_opts_default", "mlh_fgr_features", "mlh_fgr_spfh", "mlh_fgr_fpfh", "mlh_fgr_fetch", "mlh_fgr_set_normals", "mlh_fgr_set_spfh", "mlh_fgr_set_features",
     "mlh_fgr_match", "mlh_fgr_register", "mlh_fgr_register_device", "mlh_fgr_tail_tuple_test", "mlh_fgr_tail_optimize", "mlh_fgr_info",
     "mlh_pg_opts_default", "mlh_pg_reset", "mlh_pg_info", "mlh_pg_add_keyframe", "mlh_pg_set_loop", "mlh_pg_optimize", "mlh_pg_poses", "mlh_pg_device_poses",
-    "mlh_pg_linearize", "mlh_pg_solve_step", "mlh_pg_time_stages", "mlh_pg_optimize_forced", "mlh_pg_reserve",
+    "mlh_pg_linearize", "mlh_pg_solve_step", "mlh_pg_time_stages", "mlh_pg_optimize_forced", "mlh_pg_reserve", "mlh_pg_marginals", "mlh_pg_device_marginals",
     "mlh_session_export_size", "mlh_session_export", "mlh_session_inspect", "mlh_session_import", "mlh_session_last_info",
 ]
 
@@ -1380,6 +1390,23 @@ class Context:
 
     PG_STAGE_NAMES = ("linearize", "assemble", "band_factor", "substitution", "gram", "dense_solve", "back_substitution", "lm_bookkeeping")
 
+    def pg_marginals(self, cur_index, opts: PgOpts = None, form=PG_COV_LOCAL) -> dict:
+        """the 6 x 6 diagonal blocks of H^-1 of the problem first..cur at the stored poses -> dict(cov (M, 6, 6) in `form`, ok, n_keyframes, n_loops, first_index,
+        launches, host_waits); with ok == 0 cov is None (mlh_pg_marginals)"""
+        info = self.pg_info()
+        r = PgMarginalsResult()
+        cov = np.zeros((max(info["n_keyframes"], 1), 6, 6))
+        self._ck(self.lib.mlh_pg_marginals(self.h, int(cur_index), C.byref(opts) if opts is not None else None, int(form), _p(cov), C.byref(r)))
+        out = {k: getattr(r, k) for k, _ in r._fields_}
+        out["cov"] = cov[:r.n_keyframes].copy() if r.ok else None
+        return out
+
+    def pg_device_marginals(self):
+        """(device pointer of the local form or None, of the store form or None, first_index, n_keyframes) of the valid marginals in HBM (mlh_pg_device_marginals)"""
+        a, b, first, n = C.c_void_p(), C.c_void_p(), C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.mlh_pg_device_marginals(self.h, C.byref(a), C.byref(b), C.byref(first), C.byref(n)))
+        return a.value, b.value, first.value, n.value
+
     def pg_time_stages(self, cur_index, opts: PgOpts = None):
         """the launches of pg_optimize without the write-back, timed per stage -> (result dict, {stage: ms}) (mlh_pg_time_stages)"""
         r, ms = PgResult(), np.zeros(8)
@@ -1647,6 +1674,15 @@ class Context:
         src = self if pg_ctx is None else pg_ctx
         nc, drift = C.c_int32(0), np.zeros(7)
         self._ck(self.lib.mlh_keyframes_update_from_pose_graph(self.h, src.h, int(first_index), int(first_key), int(n), int(bool(drift_tail)), C.byref(nc), _p(drift)))
+        return dict(n_changed=nc.value, drift=drift)
+
+    def keyframes_update_from_pose_graph_cov(self, pg_ctx=None, first_index=0, first_key=0, n=-1, drift_tail=False, cov_mode=KF_COV_RELATIVE) -> dict:
+        """keyframes_update_from_pose_graph with the store-form marginal covariances of pg_ctx's last pg_marginals; cov_mode KF_COV_RELATIVE / KF_COV_ABSOLUTE
+        -> dict(n_changed, drift (7,)) (mlh_keyframes_update_from_pose_graph_cov)"""
+        src = self if pg_ctx is None else pg_ctx
+        nc, drift = C.c_int32(0), np.zeros(7)
+        self._ck(self.lib.mlh_keyframes_update_from_pose_graph_cov(self.h, src.h, int(first_index), int(first_key), int(n), int(bool(drift_tail)), int(cov_mode), C.byref(nc),
+                                                                   _p(drift)))
         return dict(n_changed=nc.value, drift=drift)
 
     def keyframe_poses(self, first_key=0, n=None) -> dict:

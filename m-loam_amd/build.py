@@ -16,7 +16,7 @@ OBJDIR = os.path.join(HERE, "build")
 LIB = os.path.join(LIBDIR, "libmloam_hip.so")
 SOURCES = ["capi.hip", "solve_host.hip", "scan.hip", "grid.hip", "match.hip", "solver.hip", "extract.hip", "comm.hip", "select.hip", "voxel.hip", "voxelgrid.hip", "odom.hip", "track.hip",
            "frontend.hip", "segment.hip", "stdsort.hip", "keyframes.hip", "cloudbuild.hip", "window.hip", "marg.hip", "calib.hip", "scancontext.hip", "loopreg.hip", "fgr.hip", "posegraph.hip", "initext.hip", "session.hip"]
-HEADERS = ["ctx.hpp", "solve_host.hpp", "records.hpp", "alive_pool.hpp", "dev_math.hpp", "inv6.hpp", "solver_dev.hpp", "knn_dev.hpp", "reduce_dev.hpp", "sort_dev.hpp", "stdsort_dev.hpp", "std_sort_mt.hpp", "p2p_dev.hpp", "kparams.hpp", "knn_features_kernel.inc", "uct_dev.hpp", "bounds_dev.hpp", "wg_dev.hpp", "factor_dev.hpp", "tile_group.hpp", "sc_host.hpp", "loopreg_host.hpp", "fgr_host.hpp", "pg_host.hpp", "kf_update_host.hpp", "initext_host.hpp", "session_host.hpp", "match_plan_host.hpp", "solve_plan_host.hpp", "launch_modes.hpp", "svd_dev.hpp", os.path.join("..", "..", "include", "mloam_hip.h")]
+HEADERS = ["ctx.hpp", "solve_host.hpp", "records.hpp", "alive_pool.hpp", "dev_math.hpp", "inv6.hpp", "solver_dev.hpp", "knn_dev.hpp", "reduce_dev.hpp", "sort_dev.hpp", "stdsort_dev.hpp", "std_sort_mt.hpp", "p2p_dev.hpp", "kparams.hpp", "knn_features_kernel.inc", "uct_dev.hpp", "bounds_dev.hpp", "wg_dev.hpp", "factor_dev.hpp", "tile_group.hpp", "sc_host.hpp", "loopreg_host.hpp", "fgr_host.hpp", "pg_host.hpp", "pg_marg_host.hpp", "pgcov.inc", "kf_update_host.hpp", "initext_host.hpp", "session_host.hpp", "match_plan_host.hpp", "solve_plan_host.hpp", "launch_modes.hpp", "svd_dev.hpp", os.path.join("..", "..", "include", "mloam_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wall", "-Wno-unused-function"]
 
 

@@ -545,6 +545,14 @@ struct PgStore {
     int max_loops = 128;                     // the capacity of loop edges of one problem (mlh_pg_reserve; pg_host.hpp: PG_MAX_LOOPS until then); mlh_pg_reset keeps it
     long long allocations = 0;
     int launches = 0, host_waits = 0;        // of the last call
+    // the marginal covariances of (f18) (pgcov.inc): both forms (36 doubles per keyframe of marg_first .. marg_cur, the local form first), the buffers beyond an
+    // optimise's, the blocks' landing place on the host. Allocated by the first mlh_pg_marginals only. marg_valid goes with the stored poses and loops it was
+    // computed from (invalidate_marginals)
+    DevBuf marg_out, marg_work;
+    PinnedBuf h_marg;
+    bool marg_valid = false;
+    int marg_first = -1, marg_cur = -1;
+    void invalidate_marginals() { marg_valid = false; marg_first = marg_cur = -1; }
 };
 
 // The session image (session.hip; session_host.hpp has the format): the staging image the pack kernel fills or checks, the call's tile table, the sections'

@@ -431,11 +431,59 @@ int keyframes_update_run(mlh_ctx *ctx, const char *entry, int32_t first_key, int
     return MLH_OK;
 }
 
+int keyframes_update_from_pg_cov_run(mlh_ctx *ctx, mlh_ctx *pg, const char *entry, int32_t first_index, int32_t first_key, int32_t n, int drift_tail, int cov_mode,
+                                     int32_t *n_changed, double *drift_out)
+{
+    const std::string e = std::string(entry) + ": ";
+    if (cov_mode != MLH_KF_COV_RELATIVE && cov_mode != MLH_KF_COV_ABSOLUTE) return fail(ctx, MLH_ERR_INVALID, (e + "cov_mode must be MLH_KF_COV_RELATIVE or MLH_KF_COV_ABSOLUTE").c_str());
+    if (ctx->device != pg->device) return fail(ctx, MLH_ERR_UNSUPPORTED, (e + "both contexts must be on the same device").c_str());
+    { const int rc = loop_process_gate(pg, entry); if (rc) return pg == ctx ? rc : fail(ctx, rc, mlh_last_error(pg)); }
+    const PgStore &G = pg->pg;
+    KfStore &K = ctx->kf;
+    if (!n_changed) return fail(ctx, MLH_ERR_INVALID, (e + "null n_changed").c_str());
+    if (G.count == 0) return fail(ctx, MLH_ERR_INVALID, (e + "the pose graph is empty").c_str());
+    if (first_index < 0 || first_index >= G.count) return fail(ctx, MLH_ERR_INVALID, (e + "first_index names no pose-graph keyframe").c_str());
+    if (n < 0) n = G.count - first_index;
+    if (n == 0 || (long long)first_index + n > (long long)G.count) return fail(ctx, MLH_ERR_INVALID, (e + "the range lies outside the pose graph").c_str());
+    if (first_key < 0 || size_t(first_key) + size_t(n) > K.keys.size()) return fail(ctx, MLH_ERR_INVALID, (e + "the range lies outside the store").c_str());
+    if (!G.marg_valid) return fail(ctx, MLH_ERR_STATE, (e + "the pose graph holds no valid marginal covariances (mlh_pg_marginals; an optimise, a new loop, a reset or an import made them stale)").c_str());
+    if (first_index + n - 1 > G.marg_cur) return fail(ctx, MLH_ERR_STATE, (e + "the range reaches beyond the keyframes the marginal covariances were computed for").c_str());
+    const long long anchor = (long long)first_key + ((long long)G.marg_first - first_index);     // the key `first` maps to
+    if (cov_mode == MLH_KF_COV_ABSOLUTE && (anchor < 0 || anchor >= (long long)K.keys.size()))
+        return fail(ctx, MLH_ERR_INVALID, (e + "MLH_KF_COV_ABSOLUTE: the problem's first keyframe maps to no key of the store").c_str());
+    const size_t row = sizeof(double) * 7, blk = sizeof(double) * 36, N = size_t(n);
+    const size_t cov_at = ((row * N + 63) / 64) * 64;
+    MLH_HIP(ctx, K.h_poses.ensure(cov_at + blk * N, (cov_at + blk * N) / 4));
+    const int lo = std::max(first_index, G.marg_first), n_blocks = first_index + n - lo;      // the pose-graph indices of the range that have a block
+    const int Mm = G.marg_cur - G.marg_first + 1;
+    hipStream_t st = ctx->stream;
+    if (pg != ctx) { const int hrc = ctx->handoff.borrow_begin(ctx, pg); if (hrc) return hrc; }
+    MLH_HIP(ctx, hipMemcpy2DAsync(K.h_poses.p, row, G.kf.as<PgKeyframe>() + first_index, sizeof(PgKeyframe), row, N, hipMemcpyDeviceToHost, st));
+    double *hc = reinterpret_cast<double *>(static_cast<char *>(K.h_poses.p) + cov_at);
+    if (n_blocks > 0)
+        MLH_HIP(ctx, hipMemcpyAsync(hc + size_t(36) * size_t(lo - first_index), G.marg_out.as<double>() + size_t(36) * (size_t(Mm) + size_t(lo - G.marg_first)), blk * size_t(n_blocks),
+                                    hipMemcpyDeviceToHost, st));
+    MLH_HIP(ctx, stream_wait_spin(ctx));
+    { const int rc = device_error_check(ctx); if (rc) return rc; }
+    double add[36];
+    for (int c = 0; c < 36; ++c) add[c] = cov_mode == MLH_KF_COV_ABSOLUTE ? K.keys[size_t(anchor)].cov[c] : 0.0;
+    for (int i = 0; i < n; ++i) {
+        double *c = hc + size_t(36) * size_t(i);
+        if (first_index + i <= G.marg_first) std::memcpy(c, K.keys[size_t(first_key) + size_t(i)].cov, blk);      // before `first`, and `first` itself
+        else if (cov_mode == MLH_KF_COV_ABSOLUTE) for (int q = 0; q < 36; ++q) c[q] = c[q] + add[q];
+    }
+    return keyframes_update_run(ctx, entry, first_key, n, K.h_poses.as<double>(), hc, drift_tail, n_changed, drift_out);
+}
+
 // (f15) mlh_keyframes_update_from_pose_graph: the poses of pg's records (stride sizeof(PgKeyframe), pose at offset 0) through ONE strided copy into pinned memory
 // on ctx's stream -- behind pg's work so far by an event when the contexts differ (as mlh_fuse_add_scan_from) --, one host wait, then the host rules
-int keyframes_update_from_pg_run(mlh_ctx *ctx, mlh_ctx *pg, int32_t first_index, int32_t first_key, int32_t n, int drift_tail, int32_t *n_changed, double *drift_out)
+// (f18) cov_mode >= 0 (mlh_keyframes_update_from_pose_graph_cov): also ONE copy of the store-form marginal blocks of the range into the same pinned block, behind the
+// pose copy and in front of the same wait; then covs per key by the mode's rule -- a key that keeps its covariance is handed its own bits
+int keyframes_update_from_pg_run(mlh_ctx *ctx, mlh_ctx *pg, int32_t first_index, int32_t first_key, int32_t n, int drift_tail, int32_t *n_changed, double *drift_out,
+                                 int cov_mode = -1)
 {
-    const char *entry = "mlh_keyframes_update_from_pose_graph";
+    const char *entry = cov_mode >= 0 ? "mlh_keyframes_update_from_pose_graph_cov" : "mlh_keyframes_update_from_pose_graph";
+    if (cov_mode >= 0) return keyframes_update_from_pg_cov_run(ctx, pg, entry, first_index, first_key, n, drift_tail, cov_mode, n_changed, drift_out);
     if (ctx->device != pg->device) return fail(ctx, MLH_ERR_UNSUPPORTED, "mlh_keyframes_update_from_pose_graph: both contexts must be on the same device");
     { const int rc = loop_process_gate(pg, entry); if (rc) return pg == ctx ? rc : fail(ctx, rc, mlh_last_error(pg)); }
     const PgStore &G = pg->pg;
@@ -916,6 +964,16 @@ int mlh_keyframes_update_from_pose_graph(mlh_ctx *ctx, mlh_ctx *pg_ctx, int32_t 
     if (!pg_ctx) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph: null pose-graph context");
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     return keyframes_update_from_pg_run(ctx, pg_ctx, first_index, first_key, n, drift_tail, n_changed, drift_out);
+}
+
+int mlh_keyframes_update_from_pose_graph_cov(mlh_ctx *ctx, mlh_ctx *pg_ctx, int32_t first_index, int32_t first_key, int32_t n, int drift_tail, int32_t cov_mode,
+                                             int32_t *n_changed, double drift_out[7])
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (!pg_ctx) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph_cov: null pose-graph context");
+    if (cov_mode < 0) return fail(ctx, MLH_ERR_INVALID, "mlh_keyframes_update_from_pose_graph_cov: cov_mode must be MLH_KF_COV_RELATIVE or MLH_KF_COV_ABSOLUTE");
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return keyframes_update_from_pg_run(ctx, pg_ctx, first_index, first_key, n, drift_tail, n_changed, drift_out, cov_mode);
 }
 
 int mlh_keyframe_poses(mlh_ctx *ctx, int32_t first_key, int32_t n, double *poses, double *covs, float *positions)

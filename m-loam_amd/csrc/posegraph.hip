@@ -24,6 +24,8 @@
 //   pg_linearize_kernel  (at the candidate, into the other slot), pg_decide_kernel
 //   pg_writeback_kernel  updatePose on first..cur, the drift onto every later keyframe
 // No floating-point atomics: every sum has one order, two runs give the same bits.
+// The marginal covariances of section (f18) -- mlh_pg_marginals: these kernels on the undamped system, then four of its own -- are pgcov.inc, included at the end of
+// this file's namespace.
 #include "ctx.hpp"
 #include <algorithm>
 #include <cmath>
@@ -31,6 +33,7 @@
 #include <string>
 #include <vector>
 #include "pg_host.hpp"
+#include "pg_marg_host.hpp"
 #include "wg_dev.hpp"
 
 namespace mlh {
@@ -455,7 +458,8 @@ __global__ __launch_bounds__(PG_WAVE) void pg_gram_kernel(PgDev P)
             for (int q = 0; q < 4; ++q) G[size_t(mI * 32 + a * 16 + lr + 4 * q) * ncp + nI * 32 + c * 16 + lc] = acc[a][c][q];
 }
 
-__global__ __launch_bounds__(PG_TPB) void pg_dense_kernel(PgDev P)
+// keep_factor: the factor is left in P.C also when it was computed in LDS (mlh_pg_marginals reads it; an optimise does not)
+__global__ __launch_bounds__(PG_TPB) void pg_dense_kernel(PgDev P, int keep_factor)
 {
     __shared__ double Cl[PG_DENSE_LDS * PG_DENSE_LDS];
     __shared__ double rhs[6 * PG_MAX_LOOPS];
@@ -514,6 +518,8 @@ __global__ __launch_bounds__(PG_TPB) void pg_dense_kernel(PgDev P)
         __syncthreads();
     }
     for (int r = t; r < m; r += PG_TPB) P.z[r] = rhs[r];
+    if (keep_factor && Cm == Cl)
+        for (int idx = t; idx < m * m; idx += PG_TPB) P.C[idx] = Cl[idx];
     if (t == 0 && sh_fail) S.lin_ok = 0;
 }
 
@@ -996,6 +1002,36 @@ int pg_enqueue_begin(mlh_ctx *ctx, const PgDev &P, int max_it, double radius0)
     return MLH_OK;
 }
 
+// [Y | y_b] = L^-1 [W^T | S g], the Gram image and the dense stage (P.NB > 0): the launches between the band's factorisation and y_b - Y z
+int pg_enqueue_reduce(mlh_ctx *ctx, const PgDev &P, PgTimer *T, int keep_factor)
+{
+    hipStream_t st = ctx->stream;
+    PgStore &G = ctx->pg;
+    const int nmt = P.ncp / 32;
+    MLH_LAUNCH(pg_forward_kernel, dim3((P.ncp + PG_WAVE - 1) / PG_WAVE), dim3(PG_WAVE), 0, st, P);
+    pg_mark(T, PG_T_FORWARD);
+    MLH_LAUNCH(pg_gram_kernel, dim3(nmt * (nmt + 1) / 2, P.ks), dim3(PG_WAVE), 0, st, P);
+    pg_mark(T, PG_T_GRAM);
+    G.launches += 2;
+    if (P.L <= PG_MAX_LOOPS) {
+        MLH_LAUNCH(pg_dense_kernel, dim3(1), dim3(PG_TPB), 0, st, P, keep_factor);
+        ++G.launches;
+    } else {
+        const int ns = pg_dense_launches(P.m);
+        for (int s = 0; s < ns; ++s) {
+            const PgDenseStep d = pg_dense_step(P.m, s);
+            const dim3 grid(unsigned(d.hi - d.lo));
+            if (d.kind == PG_STEP_SUM) MLH_LAUNCH(pg_csum_kernel, grid, dim3(PG_TPB), 0, st, P);
+            else if (d.kind == PG_STEP_UPDATE) MLH_LAUNCH(pg_cupdate_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
+            else if (d.kind == PG_STEP_PANEL) MLH_LAUNCH(pg_cpanel_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
+            else MLH_LAUNCH(pg_cback_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
+        }
+        G.launches += ns;
+    }
+    pg_mark(T, PG_T_DENSE);
+    return MLH_OK;
+}
+
 // assemble + the linear solve of one iteration (the launches between the loop's head and the candidate)
 int pg_enqueue_solve(mlh_ctx *ctx, const PgDev &P, int loop_head, PgTimer *T = nullptr, int force_fail = 0)
 {
@@ -1007,31 +1043,11 @@ int pg_enqueue_solve(mlh_ctx *ctx, const PgDev &P, int loop_head, PgTimer *T = n
     ++G.launches;
     pg_mark(T, PG_T_FACTOR);
     if (P.NB > 0) {
-        const int nmt = P.ncp / 32;
-        MLH_LAUNCH(pg_forward_kernel, dim3((P.ncp + PG_WAVE - 1) / PG_WAVE), dim3(PG_WAVE), 0, st, P);
-        pg_mark(T, PG_T_FORWARD);
-        MLH_LAUNCH(pg_gram_kernel, dim3(nmt * (nmt + 1) / 2, P.ks), dim3(PG_WAVE), 0, st, P);
-        pg_mark(T, PG_T_GRAM);
-        if (P.L <= PG_MAX_LOOPS) {
-            MLH_LAUNCH(pg_dense_kernel, dim3(1), dim3(PG_TPB), 0, st, P);
-            ++G.launches;
-        } else {
-            const int ns = pg_dense_launches(P.m);
-            for (int s = 0; s < ns; ++s) {
-                const PgDenseStep d = pg_dense_step(P.m, s);
-                const dim3 grid(unsigned(d.hi - d.lo));
-                if (d.kind == PG_STEP_SUM) MLH_LAUNCH(pg_csum_kernel, grid, dim3(PG_TPB), 0, st, P);
-                else if (d.kind == PG_STEP_UPDATE) MLH_LAUNCH(pg_cupdate_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
-                else if (d.kind == PG_STEP_PANEL) MLH_LAUNCH(pg_cpanel_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
-                else MLH_LAUNCH(pg_cback_kernel, grid, dim3(PG_TPB), 0, st, P, d.k);
-            }
-            G.launches += ns;
-        }
-        pg_mark(T, PG_T_DENSE);
+        { const int rc = pg_enqueue_reduce(ctx, P, T, 0); if (rc) return rc; }
         MLH_LAUNCH(pg_yz_kernel, dim3(pg_blocks(P.n)), dim3(PG_TPB), 0, st, P);
         MLH_LAUNCH(pg_back_kernel, dim3(1), dim3(PG_WAVE), 0, st, P);
         pg_mark(T, PG_T_BACK);
-        G.launches += 4;
+        G.launches += 2;
     }
     return MLH_OK;
 }
@@ -1054,6 +1070,7 @@ int optimize_run(mlh_ctx *ctx, const char *entry, int cur_index, const mlh_pg_op
     { const int rc = pg_gate(ctx, entry); if (rc) return rc; }
     PgDev P;
     { const int rc = pg_problem(ctx, entry, cur_index, o, P); if (rc) return rc; }
+    if (!stage_ms) G.invalidate_marginals();                 // (f18): the poses they were computed at are about to move
     hipStream_t st = ctx->stream;
     PgTimer timer;
     timer.st = st;
@@ -1191,6 +1208,8 @@ int solve_step_run(mlh_ctx *ctx, int cur_index, const mlh_pg_opts &o, double rad
     return MLH_OK;
 }
 
+#include "pgcov.inc"
+
 }  // namespace
 
 }  // namespace mlh
@@ -1209,6 +1228,7 @@ int mlh_pg_reset(mlh_ctx *ctx)
     if (!ctx) return MLH_ERR_INVALID;
     PgStore &G = ctx->pg;
     G.count = 0; G.earliest_loop = -1; G.loop_index.clear();
+    G.invalidate_marginals();
     return MLH_OK;
 }
 
@@ -1232,7 +1252,7 @@ int mlh_pg_info(mlh_ctx *ctx, mlh_pg_info_t *out)
     out->earliest_loop_index = G.earliest_loop;
     out->max_loops = G.max_loops;
     out->allocations = G.allocations;
-    out->bytes_hbm = int64_t(G.kf.cap + G.work.cap + G.state.cap);
+    out->bytes_hbm = int64_t(G.kf.cap + G.work.cap + G.state.cap + G.marg_out.cap + G.marg_work.cap);
     return MLH_OK;
 }
 
@@ -1276,6 +1296,7 @@ int mlh_pg_set_loop(mlh_ctx *ctx, int32_t index, int32_t loop_index, const doubl
     MLH_HIP(ctx, hipMemcpyAsync(reinterpret_cast<char *>(G.kf.as<PgKeyframe>() + index) + offsetof(PgKeyframe, loop_rel), &rec, sizeof(rec), hipMemcpyHostToDevice, ctx->stream));
     MLH_HIP(ctx, hipStreamSynchronize(ctx->stream));
     G.loop_index[size_t(index)] = loop_index;
+    G.invalidate_marginals();
     if (G.earliest_loop > loop_index || G.earliest_loop == -1) G.earliest_loop = loop_index;      // pose_graph.cpp:141-142
     return MLH_OK;
 }
@@ -1356,6 +1377,30 @@ int mlh_pg_solve_step(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, 
     if (!std::isfinite(radius) || !(radius > 0.0)) return fail(ctx, MLH_ERR_INVALID, "mlh_pg_solve_step: the radius must be finite and > 0");
     MLH_HIP(ctx, hipSetDevice(ctx->device));
     return solve_step_run(ctx, cur_index, o, radius, step, delta, ok);
+}
+
+int mlh_pg_marginals(mlh_ctx *ctx, int32_t cur_index, const mlh_pg_opts *opts, int32_t form, double *covs, mlh_pg_marginals_result *result)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (!result) return fail(ctx, MLH_ERR_INVALID, "mlh_pg_marginals: null result");
+    if (form != MLH_PG_COV_LOCAL && form != MLH_PG_COV_STORE) return fail(ctx, MLH_ERR_INVALID, "mlh_pg_marginals: form must be MLH_PG_COV_LOCAL or MLH_PG_COV_STORE");
+    mlh_pg_opts o;
+    { const int rc = pg_opts_take(ctx, "mlh_pg_marginals", opts, o); if (rc) return rc; }
+    MLH_HIP(ctx, hipSetDevice(ctx->device));
+    return marginals_run(ctx, cur_index, o, form, covs, result);
+}
+
+int mlh_pg_device_marginals(mlh_ctx *ctx, const double **cov_local, const double **cov_store, int32_t *first_index, int32_t *n_keyframes)
+{
+    if (!ctx) return MLH_ERR_INVALID;
+    if (!cov_local || !cov_store) return fail(ctx, MLH_ERR_INVALID, "mlh_pg_device_marginals: null output");
+    const PgStore &G = ctx->pg;
+    const int M = G.marg_valid ? G.marg_cur - G.marg_first + 1 : 0;
+    *cov_local = M ? G.marg_out.as<double>() : nullptr;
+    *cov_store = M ? G.marg_out.as<double>() + size_t(36) * size_t(M) : nullptr;
+    if (first_index) *first_index = M ? G.marg_first : -1;
+    if (n_keyframes) *n_keyframes = M;
+    return MLH_OK;
 }
 
 }  // extern "C"

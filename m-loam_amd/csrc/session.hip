@@ -324,6 +324,7 @@ int session_import_run(mlh_ctx *ctx, const void *image, size_t bytes, uint32_t s
         swap_buf(G.kf, pgkf);
         ++G.allocations;
         G.count = ph.count; G.earliest_loop = ph.earliest_loop;
+        G.invalidate_marginals();
         G.loop_index.resize(size_t(ph.count));
         for (int i = 0; i < ph.count; ++i) {
             SessPgRecord r;

@@ -2241,15 +2241,23 @@ public:
     }
     // the same over the pose graph's records in HBM (pose-graph index i = store key i), without the host list: one strided copy and one host wait. The caller
     // holds whatever guards `pg` (as publishLoopInfo holds m_keyframelist); pg may live on this Device or on one of its own on the same GPU.
-    template <typename PoseT> Pose updateKeyframe(PoseGraph<PoseT> &pg)
+    // cov_mode < 0 (the default): the poses only, the stored covariances stay. cov_mode = MLH_KF_COV_RELATIVE / MLH_KF_COV_ABSOLUTE: the opt-in of (f18) -- the keyframes
+    // pg.computeMarginals(cur) covered also take their marginal covariance in the store's convention (the rules are the header's); the keyframes behind `cur` get the
+    // drift and keep theirs. Throws (MLH_ERR_STATE) when pg holds no valid marginals.
+    template <typename PoseT> Pose updateKeyframe(PoseGraph<PoseT> &pg, int cov_mode = -1)
     {
         int32_t n_kf = 0;
         dev_.check(mlh_local_map_info(dev_.ctx(), &n_kf, nullptr, nullptr, nullptr));
-        const int32_t n = std::min<int32_t>(n_kf, pg.getKeyFrameSize());
+        int32_t n = std::min<int32_t>(n_kf, pg.getKeyFrameSize());
         if (n <= 0) return Pose();
         double drift[7];
-        dev_.check(mlh_keyframes_update_from_pose_graph(dev_.ctx(), pg.device().ctx(), 0, 0, n, 1, &n_changed_, drift));
-        return updated(drift);
+        if (cov_mode < 0) {
+            dev_.check(mlh_keyframes_update_from_pose_graph(dev_.ctx(), pg.device().ctx(), 0, 0, n, 1, &n_changed_, drift));
+        } else {
+            if (pg.marginalsCur() >= 0) n = std::min<int32_t>(n, pg.marginalsCur() + 1);
+            dev_.check(mlh_keyframes_update_from_pose_graph_cov(dev_.ctx(), pg.device().ctx(), 0, 0, n, 1, cov_mode, &n_changed_, drift));
+        }
+        return updated(drift, cov_mode >= 0);
     }
     int lastChanged() const { return n_changed_; }
     // laser_cloud_{surf,corner}_from_map_cov_ds in HBM
@@ -2261,14 +2269,17 @@ public:
 private:
     static std::array<double, 7> param(const Pose &p) { std::array<double, 7> a; p.toParam(a.data()); return a; }
     // the store's poses into the KeyframePolicy; the drift as a Pose
-    Pose updated(const double drift[7])
+    Pose updated(const double drift[7], bool with_covs = false)
     {
         int32_t n_kf = 0;
         dev_.check(mlh_local_map_info(dev_.ctx(), &n_kf, nullptr, nullptr, nullptr));
-        std::vector<double> p(7 * size_t(n_kf) + 1);
+        std::vector<double> p(7 * size_t(n_kf) + 1), c(with_covs ? 36 * size_t(n_kf) + 1 : 1);
         std::vector<float> pos(3 * size_t(n_kf) + 1);
-        dev_.check(mlh_keyframe_poses(dev_.ctx(), 0, n_kf, p.data(), nullptr, pos.data()));
+        dev_.check(mlh_keyframe_poses(dev_.ctx(), 0, n_kf, p.data(), with_covs ? c.data() : nullptr, pos.data()));
         kf_.updatePoses(p.data(), pos.data(), size_t(n_kf));
+        if (with_covs)          // (f18) the covariance route: the policy's copies follow the store's
+            for (size_t i = 0; i < std::min(size_t(n_kf), kf_.pose_keyframes_6d.size()); ++i)
+                std::copy(c.begin() + 36 * i, c.begin() + 36 * (i + 1), kf_.pose_keyframes_6d[i].cov_.begin());
         Pose d;
         d.fromParam(drift);
         return d;
@@ -2389,6 +2400,12 @@ public:
     // The hook where the reference drains loop_info_buf and calls updateKeyframe() (cpp:1082-1095), for the device KeyframeMap: call it BETWEEN frames with no solve
     // in flight (before the first process(), or after finish()). `update` is one of km's updateKeyframe overloads bound by the caller; its drift is
     // left-multiplied onto pose_wmap_wodom, and when a keyframe changed the local map is rebuilt around drift * pose_wmap_curr (the last frame's pose). Returns the drift.
+    // The covariance route of (f18) is an opt-in of the update the caller binds: [&](KeyframeMap &km) { return km.updateKeyframe(pg, MLH_KF_COV_RELATIVE); } -- or
+    // the overload below, which binds it.
+    template <typename PoseT> Pose applyLoopInfo(PoseGraph<PoseT> &pg, const Pose &pose_wmap_curr, int cov_mode = -1)
+    {
+        return applyLoopInfo([&pg, cov_mode](KeyframeMap &km) { return km.updateKeyframe(pg, cov_mode); }, pose_wmap_curr);
+    }
     template <class Update> Pose applyLoopInfo(Update update, const Pose &pose_wmap_curr)
     {
         if (!km_) throw Error("PipelinedMapper::applyLoopInfo needs the device KeyframeMap");
@@ -2818,6 +2835,34 @@ public:
         loadSession(dev_, img, sections);
         return true;
     }
+    // (f18) the marginal covariances of first..cur at the stored poses (after optimizePoseGraph: at the corrected ones), in the keyframe store's convention
+    // ([rho, phi], left perturbation). false when there is no loop yet or cur lies before the earliest looped keyframe, and when a pivot failed (nothing is kept).
+    // The result goes stale with the next optimizePoseGraph / updateLoopInfo / loadPoseGraph: marginalCov then throws until the next computeMarginals.
+    bool computeMarginals(int cur_index)
+    {
+        marg_first_ = marg_cur_ = -1;
+        marg_.assign(size_t(36) * size_t(std::max(1, getKeyFrameSize())), 0.0);
+        const int rc = mlh_pg_marginals(dev_.ctx(), cur_index, &opts_, MLH_PG_COV_STORE, marg_.data(), &last_marg_);
+        if (rc == MLH_ERR_STATE) return false;
+        dev_.check(rc);
+        if (!last_marg_.ok) return false;
+        marg_first_ = last_marg_.first_index; marg_cur_ = cur_index;
+        return true;
+    }
+    // keyframe `index`'s 6 x 6 block, row-major (the block of `first` is zero: the gauge)
+    std::array<double, 36> marginalCov(int index) const
+    {
+        const double *lo = nullptr, *st = nullptr;
+        int32_t first = -1, n = 0;
+        dev_.check(mlh_pg_device_marginals(dev_.ctx(), &lo, &st, &first, &n));
+        if (!st || first != marg_first_ || index < marg_first_ || index > marg_cur_) throw Error("PoseGraph::marginalCov: no valid marginal covariance for this keyframe");
+        std::array<double, 36> c;
+        std::copy(marg_.begin() + 36 * size_t(index - marg_first_), marg_.begin() + 36 * size_t(index - marg_first_ + 1), c.begin());
+        return c;
+    }
+    int marginalsFirst() const { return marg_first_; }
+    int marginalsCur() const { return marg_cur_; }
+    const mlh_pg_marginals_result &lastMarginals() const { return last_marg_; }
     int getKeyFrameSize() const { return info().n_keyframes; }
     int earliestLoopIndex() const { return info().earliest_loop_index; }
     bool pgoFlag() const { return pgo_flag_; }
@@ -2829,6 +2874,9 @@ private:
     Device &dev_;
     mlh_pg_opts opts_{};
     mlh_pg_result last_{};
+    mlh_pg_marginals_result last_marg_{};
+    std::vector<double> marg_;
+    int marg_first_ = -1, marg_cur_ = -1;
     bool pgo_flag_ = false;
 };
 
